@@ -2,7 +2,8 @@
 """bench.py -- throughput of the ray-trace imaging hot path on MI355X.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak]
-                  [--workload standin|seed_medium|config5] [--no-cpu-baseline] [--no-config5] [--no-seed-medium]
+                  [--workload standin|seed_medium|config5] [--dump-outputs DIR]
+                  [--full [--no-cpu-baseline] [--no-config5] [--no-seed-medium]]
 
 N > 1 may be started either way:
   * `python bench.py --gpus N ...`  -- this process spawns the N ranks itself (a
@@ -27,10 +28,17 @@ strong` (default for N > 1, BASELINE config 4) splits the fixed workload; `--sca
 every rank the whole single-GPU workload (N times as many columns).  Tiles are assembled on rank 0
 with ONE collective per step: gather of (tile | I_ang) buffers (ASE) or sum-reduce (seeded).
 
-Sub-records of the line (all beside `value`, never part of it): `roofline_small` = the two input files the
-reference ships (BASELINE config 2), `roofline_config5`, `roofline_seed_medium`, `cpu_baseline` (the unmodified
-reference CPU loop on every hardware thread of the box), `multi_gpu_cabi` = the product's own multi-GPU arm
-(rt_hip_multi_image_loop with ndev = N, in a child process).
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step when
+--dump-outputs is given, and prints the line.  `--full` adds the sub-records that take runs of their own (all
+beside `value`, never part of it): `steady_state`, `roofline_two_kernel`, `peak_measured`, `image_loop`,
+`roofline_small` = the two input files the reference ships (BASELINE config 2), `roofline_config5`,
+`roofline_seed_medium`, `cpu_baseline` (the unmodified reference CPU loop on every hardware thread of the box),
+`multi_gpu_cabi` = the product's own multi-GPU arm (rt_hip_multi_image_loop with ndev = N, in a child process) and,
+at N > 1, the weak-scaling form of the workload.
+
+--dump-outputs DIR: after the timed steps, the image and I_ang that the last timed step handed to its caller (rank 0:
+the assembled ones) are written as DIR/image.npy and DIR/I_ang.npy (float64, flat).  An image above
+DUMP_IMAGE_MAX_BYTES is written as a fixed, seeded sample of its elements (DIR/image_sample_index.npy says which).
 
 Rank 0 prints ONE JSON line; DESIGN.md section 5 describes every field.
 """
@@ -50,6 +58,8 @@ ROOT = Path(__file__).resolve().parent
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 N_SIMD = 1024          # 256 CUs x 4 SIMDs (MI355X_MICROARCH.md)
 KERNEL_SOURCES = ("rt_device.h", "rt_freq.hip", "rt_fused.hip", "rt_march.hip", "rt_math.h", "rt_path.hip")
+DUMP_IMAGE_MAX_BYTES = 16 << 20  # --dump-outputs: larger images (config 5: 68.7 GB) are sampled down to this
+                                 # (sample + its index stay far below 64 MB)
 
 
 # --------------------------------------------------------------------------- self-launch
@@ -640,6 +650,22 @@ def measure_cabi_multi(n_dev: int, workload: str, share_gpu: bool) -> dict:
     return {"error": f"child exited with {r.returncode}", "stderr_tail": r.stderr[-800:]}
 
 
+# --------------------------------------------------------------------------- outputs
+def dump_outputs(torch, out_dir: str, image, iang) -> None:
+    """Writes what the last timed step computed (device tensors, flat float64) under out_dir as .npy files."""
+    import numpy as np
+
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    n = image.numel()
+    if n * 8 > DUMP_IMAGE_MAX_BYTES:
+        pick = np.sort(np.random.default_rng(0).choice(n, DUMP_IMAGE_MAX_BYTES // 8, replace=False))
+        np.save(d / "image_sample_index.npy", pick.astype(np.float64))
+        image = image.index_select(0, torch.from_numpy(pick).to(image.device))
+    np.save(d / "image.npy", image.double().cpu().numpy())
+    np.save(d / "I_ang.npy", iang.double().cpu().numpy())
+
+
 # --------------------------------------------------------------------------- main
 def main() -> int:
     ap = argparse.ArgumentParser()
@@ -648,10 +674,16 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--scaling", choices=("strong", "weak"), default=None)
     ap.add_argument("--workload", choices=("standin", "seed_medium", "config5"), default="standin")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the sub-records that take runs of their own (steady state, two-kernel form, HBM "
+                         "peak, image loop, config 5, seed_medium, the small files, CPU baselines, multi_gpu_cabi, weak "
+                         "scaling); a plain run times only the headline workload")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the image and I_ang of the last timed step as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-config5", action="store_true", help="skip the config-5 sub-record of the default N = 1 run")
     ap.add_argument("--no-seed-medium", action="store_true", help="skip the seeded sub-record of the default N = 1 run")
-    ap.add_argument("--no-extras", action="store_true", help="only the timed loop (profiling runs)")
+    ap.add_argument("--no-extras", action="store_true", help="only the timed loop, even with --full")
     ap.add_argument("--no-small", action="store_true", help="skip the ASE_small / seed_small sub-record of the default N = 1 run")
     ap.add_argument("--no-cabi-multi", action="store_true", help="skip the rt_hip_multi_image_loop sub-record (a child process)")
     ap.add_argument("--clock-ramp-steps", type=int, default=None,
@@ -663,6 +695,9 @@ def main() -> int:
                     help="N > 1: leave the tiles on their GPUs (config 5: gathering the 68.7 GB image takes longer than "
                          "tracing it, SURVEY.md 7.3-6); the collective is then reported as absent")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    extras = args.full and not args.no_extras
 
     if args.cabi_multi_child:
         return cabi_multi_child(args.cabi_multi_child, args.workload)
@@ -716,10 +751,12 @@ def main() -> int:
 
     plan.set_timing_ring(max(1, args.steps))  # HIP events around each kernel of every timed step, read after the loop
 
+    out = [(image, iang)]  # what the last step handed to its caller: (image, I_ang), (None, None) off rank 0
+
     def step():
         plan.run(stream, image.data_ptr(), iang.data_ptr())
         if world > 1 and not args.no_assemble:
-            asm.assemble()
+            out[0] = asm.assemble()
 
     for _ in range(args.warmup):
         step()
@@ -743,6 +780,8 @@ def main() -> int:
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, *out[0])
 
     kms = plan.ring_times()  # (march_ms, freq_ms) of the timed steps, recorded on the launch stream
     fused = plan.last_fused()  # one launch for the whole path: the first time is the launch's, the second ~0
@@ -765,7 +804,7 @@ def main() -> int:
     # period.  The number of steps comes from the all-reduced time, so that every rank issues the same number
     # of collectives.
     steady = None
-    if not args.no_extras:
+    if extras:
         n_ss = max(args.steps, int(6.0 / max(dt_max / args.steps, 1e-4)) + 1)
         torch.cuda.synchronize()
         if world > 1:
@@ -784,7 +823,7 @@ def main() -> int:
     # The weak-scaling form of the same workload (every rank the whole single-GPU workload) is measured after
     # the timed run, same protocol, and reported beside it -- extra information, never `value`.
     weak = None
-    if world > 1 and scaling == "strong" and not args.no_extras and args.workload == "standin":
+    if world > 1 and scaling == "strong" and extras and args.workload == "standin":
         wfull, _ = build_workload(rt, problem_mod, args.workload, world, "weak")
         wmine = multigpu.shard(wfull, rank, world)
         wplan = backend.Plan(wmine, device=local)
@@ -894,7 +933,7 @@ def main() -> int:
                               "bytes_per_ray_step": alg["path"] / max(1, stats["cell_steps"])},
         }
         line["launches_per_step"] = 1 if fused else 2
-        if fused and world == 1 and not args.no_extras:
+        if fused and world == 1 and extras:
             # the same workload as two kernels (RT_HIP_FUSED=2), for the per-kernel figures of earlier rounds: mean of
             # 8 runs after 2, HIP events on the launch stream
             try:
@@ -934,7 +973,7 @@ def main() -> int:
                                  "collective": "none (--no-assemble: tiles stay on their GPUs)" if args.no_assemble else asm.describe()}
             if weak is not None:
                 line["multi_gpu"]["weak_scaling"] = weak
-        if world == 1 and not args.no_extras:
+        if world == 1 and extras:
             try:
                 line["peak_measured"] = measure_hbm_peak(torch, dev)
             except Exception as exc:  # noqa: BLE001
@@ -978,7 +1017,7 @@ def main() -> int:
         # the same workload with ndev = N, in a fresh child process while this job's ranks sit idle on the host
         # (ranks 1 .. N-1 wait on the rendezvous store, not in a GPU-side barrier).  Beside it, `value` above is the
         # one-process-per-GPU form (multigpu.Assembler over torch.distributed).
-        if not args.no_extras and not args.no_cabi_multi and args.workload in ("standin", "seed_medium"):
+        if extras and not args.no_cabi_multi and args.workload in ("standin", "seed_medium"):
             plan.close()
             torch.cuda.synchronize()
             try:

@@ -16,6 +16,8 @@ Writes, for each shipped input (ASE_small, seed_small):
                          every STRIDE-th ray of the reference's own ray list
   <name>_ref_path.npz    RayTrace::calc_ray_path outputs (x, y, I per sub-segment
                          boundary) on a small sub-grid, step factors 0.5 and 0.25
+and ASE_small_ref_slice.npz: image / I_ang of the reference's CPU loop
+(RayTraceImageCPULoop) on the ray list 100000 ... 139999 of ASE_small.
 Only data is stored -- no reference source text in any encoding.
 """
 import hashlib
@@ -65,6 +67,13 @@ def main():
         np.savez_compressed(OUT / f"{name}_ref_path.npz", i0=np.array(sub[0]), n=np.array(sub[1]), **paths)
         print(f"{name}: |image|={np.linalg.norm(r['image']):.12g} |I_ang|={np.linalg.norm(r['I_ang']):.12g} "
               f"ref cpu {r['seconds']:.2f}s, {n} probe rays")
+    # the reference's CPU loop on a list of rays (tests/test_oracle_pin.py::test_live_reference_slice)
+    p = rt.datfile.load(OUT / "ASE_small.dat.xz")
+    ids = np.arange(100000, 140000, dtype=np.int64)
+    s = ref.cpu_loop(p, p.build_rays(ids))
+    assert s["failure_code"] == 0
+    np.savez_compressed(OUT / "ASE_small_ref_slice.npz", id_range=np.array([ids[0], ids[-1] + 1]), image=s["image"],
+                        I_ang=s["I_ang"])
 
 
 def main_scaled_and_sliced():

@@ -15,7 +15,9 @@ ROOT = Path(__file__).resolve().parents[1]
 
 
 @pytest.fixture(scope="module")
-def lib():
+def lib(hip):
+    # through the `hip` fixture: torch's HIP runtime must be loaded before this library's, or a GPU test later in the
+    # same session finds no device through torch and RCCL cannot initialise
     backend.build_library()
     return backend.HipLibrary.get()
 

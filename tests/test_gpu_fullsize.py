@@ -187,7 +187,7 @@ def test_bench_two_rank_launch_rehearsal(hip):
     root = Path(__file__).resolve().parents[1]
     env = dict(os.environ, RT_BENCH_BACKEND="gloo", RT_BENCH_SHARE_GPU="1")
     env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -209,3 +209,34 @@ def test_bench_two_rank_launch_rehearsal(hip):
     for path, v in _fracs(line):
         assert v is None or v <= 1.0, (path, v)
     assert line["warmup"] == 1 and line["warmup_requested"] == 1
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(hip, ase_small, tmp_path):
+    """A plain `bench.py` run times exactly --steps steps of the headline workload, measures none of the --full
+    sub-records, and --dump-outputs writes the image and I_ang its last timed step computed."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    root = Path(__file__).resolve().parents[1]
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["metric"] == "ray_steps_per_sec" and line["unit"] == "ray-steps/s" and line["higher_is_better"] is True
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["config"]["ray_steps_total"] == 75601675
+    for key in ("steady_state", "roofline_two_kernel", "peak_measured", "image_loop", "roofline_config5",
+                "roofline_seed_medium", "roofline_small", "cpu_baseline", "multi_gpu_cabi"):
+        assert key not in line, key
+    p = rt.scale_problem(ase_small, 16.0)
+    with hip.Plan(p) as plan:
+        ref = plan.set_ray_grid().run().fetch()
+    img, iang = np.load(tmp_path / "image.npy"), np.load(tmp_path / "I_ang.npy")
+    assert img.dtype == np.float64 and img.shape == ref["image"].shape and iang.shape == ref["I_ang"].shape
+    assert rel_l2(img, ref["image"]) < 1e-12 and rel_l2(iang, ref["I_ang"]) < 1e-12

@@ -350,3 +350,33 @@ def test_bench_sub_records_never_show_a_fraction_above_one():
     for rec in (hot, meas, cool, iss):
         for path, v in _fracs(rec):
             assert v is None or v <= 1.0, (path, v)
+
+
+def test_bench_dump_outputs_writes_float64_and_samples_large_images(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: image and I_ang as flat float64 .npy files; an image above DUMP_IMAGE_MAX_BYTES is
+    written as a fixed, seeded sample whose element indices are written beside it."""
+    import importlib.util
+    import sys
+    from pathlib import Path
+
+    import torch
+    root = Path(__file__).resolve().parents[1]
+    spec = importlib.util.spec_from_file_location("bench_dump", root / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    sys.modules["bench_dump"] = bench
+    spec.loader.exec_module(bench)
+    image = torch.arange(1000, dtype=torch.float64) * 0.5
+    iang = torch.arange(7, dtype=torch.float64)
+    bench.dump_outputs(torch, str(tmp_path / "whole"), image, iang)
+    img = np.load(tmp_path / "whole" / "image.npy")
+    assert img.dtype == np.float64 and np.array_equal(img, image.numpy())
+    assert np.array_equal(np.load(tmp_path / "whole" / "I_ang.npy"), iang.numpy())
+    assert not (tmp_path / "whole" / "image_sample_index.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_IMAGE_MAX_BYTES", 8 * 100)
+    for d in ("a", "b"):
+        bench.dump_outputs(torch, str(tmp_path / d), image, iang)
+    idx = np.load(tmp_path / "a" / "image_sample_index.npy")
+    sample = np.load(tmp_path / "a" / "image.npy")
+    assert idx.dtype == np.float64 and len(idx) == 100 == len(np.unique(idx)) and sample.dtype == np.float64
+    assert np.array_equal(sample, idx * 0.5)                                   # the values at those indices
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "image_sample_index.npy"))  # the same sample every run
