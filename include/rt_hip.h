@@ -275,6 +275,31 @@ int rt_hip_plan_set_step_factor(rt_hip_plan *plan, double c);
 int rt_hip_plan_enable_path(rt_hip_plan *plan, int on);
 int rt_hip_plan_fetch_path(rt_hip_plan *plan, float *path, int32_t *err);
 
+/* Spectra mode, replaces RayTrace::calc_ray (src/RayTraceImage.cpp:189-204) for every ray of the plan: with it
+ * enabled a run produces, instead of the image, what calc_ray returns per ray -- the spectrum Iv [n_rays][K] (row
+ * stride K), the exit ray ray2 [n_rays] and the return code err [n_rays] (0, -1, -2, -3; Helper.h:514-594, a negative
+ * intensity wins over a NaN).  A ray with error -1 has a spectrum of zeros and ray2 = 0 (the reference leaves ray2
+ * untouched there); the spectrum of a ray with error -2 / -3 is not meant to be read.  The march runs as in image mode
+ * (two-kernel form), rt_spec_kernel (raytrace-miniapp_amd/csrc/rt_spec.hip) takes the place of the frequency kernel:
+ * rt_hip_plan_kernel_times reports it as freq_ms.  rt_hip_plan_run takes no image buffers in this mode (NULL, NULL) and
+ * rt_hip_plan_fetch no image pointers; it still reports failure_code (bit -err of every failing ray), the first failed
+ * rays and the counters.  Works with ray lists and ray grids and together with the probe; together with the path tracer
+ * it is RT_ERR_ARG.  Any pointer of fetch_spectra may be NULL.  spectra_ptr: device pointer of Iv of the last run (valid
+ * until the next run or change of the ray set), for torch views. */
+int rt_hip_plan_enable_spectra(rt_hip_plan *plan, int on);
+int rt_hip_plan_fetch_spectra(rt_hip_plan *plan, double *Iv, rt_ray *ray2, int32_t *err);
+double *rt_hip_plan_spectra_ptr(rt_hip_plan *plan);
+
+/* Host-pointer batched form of RayTrace::calc_ray: n independent calls in one.  rays and ray2 are [n][4] doubles
+ * (x, y, a, b) as calc_ray takes and returns them; the coordinates are rounded to float exactly as calc_ray rounds
+ * them (src/RayTraceImage.cpp:195-199).  Iv [n][K], err [n]; Iv, ray2, err and stats may be NULL.  gain: [N] tables
+ * with Nv = K, seed may be NULL, method 1 (backward) or 2 (forward), dz the length of one plasma segment.  The rays are
+ * traced in chunks whose spectra take at most 1 GiB of device memory, and a chunk travels to the host while the next
+ * one runs, so device memory stays bounded for any n.  n = 0 is RT_OK; 2^32 - 4096 rays or more are RT_ERR_ARG.
+ * stats: counters and kernel times summed over the chunks, total_ms = wall time of the call. */
+int rt_hip_calc_rays(int device, int N, double dz, const rt_gain *gain, const rt_seed *seed, int K, int method,
+                     const double *rays, size_t n, double *Iv, double *ray2, int32_t *err, rt_stats *stats);
+
 /* Profiling aid (no reference counterpart): bit 0 = skip the frequency / deposit kernel, bit 1 = skip
  * the march and run the frequency pass over the records of the previous run of this plan, bit 2 = the
  * frequency kernel keeps its per-work-group I_ang sums to itself (I_ang stays zero).  0 = normal. */

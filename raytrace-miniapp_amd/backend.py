@@ -7,6 +7,7 @@ mirror of the reference's operator interface for this path.
   image_loop(...)       the back-end loop, same meaning as RayTraceImageCudaLoop
                         (src/RayTraceImageCuda.cu:145-221) behind the signature of
                         src/RayTraceImage.cpp:47-75
+  calc_rays / calc_ray  RayTrace::calc_ray (src/RayTraceImage.cpp:189-204), batched: per-ray spectrum, exit ray, code
   create_image(p, method)
                         mirror of RayTrace::create_image (src/RayTraceImage.cpp:227-434):
                         checks, mode select, ray list, dispatch on the method
@@ -136,6 +137,7 @@ class Plan:
 
     def fetch(self, want_image: bool = True) -> dict:
         b = self.problem.beam
+        want_image = want_image and not getattr(self, "_spectra", False)  # a spectra run has no image
         image = np.empty(b.nx * b.ny * b.nv) if want_image else None
         iang = np.empty(b.na * b.nb) if want_image else None
         code = C.c_uint(0)
@@ -176,6 +178,43 @@ class Plan:
         self.hl.check(self.hl.lib.rt_hip_plan_fetch_path(self._h, cabi._fp(path), err.ctypes.data_as(C.POINTER(C.c_int32))),
                       "rt_hip_plan_fetch_path")
         return dict(x=path[:, :, 0].copy(), y=path[:, :, 1].copy(), I=path[:, :, 2].copy(), err=err)
+
+    def enable_spectra(self, on: bool = True) -> "Plan":
+        """Spectra mode (RayTrace::calc_ray for every ray): a run produces Iv, ray2, err per ray instead of the image."""
+        self.hl.check(self.hl.lib.rt_hip_plan_enable_spectra(self._h, int(on)), "rt_hip_plan_enable_spectra")
+        self._spectra = bool(on)
+        return self
+
+    def fetch_spectra(self) -> dict:
+        """Iv [n_rays][K] float64, ray2 [n_rays] (RAY_DTYPE), err [n_rays] int32 (0, -1, -2, -3) of the last run."""
+        n, K = self.n_rays, self.problem.beam.nv
+        Iv = np.empty((n, K))
+        ray2 = np.zeros(n, cabi.RAY_DTYPE)
+        err = np.zeros(n, np.int32)
+        self.hl.check(self.hl.lib.rt_hip_plan_fetch_spectra(self._h, cabi._dp(Iv), cabi.rays_ptr(ray2),
+                                                            err.ctypes.data_as(C.POINTER(C.c_int32))),
+                      "rt_hip_plan_fetch_spectra")
+        return dict(Iv=Iv, ray2=ray2, err=err)
+
+    def spectra_ptr(self) -> int:
+        """Device pointer of Iv [n_rays][K] of the last spectra run (for torch views), 0 if there is none."""
+        return int(self.hl.lib.rt_hip_plan_spectra_ptr(self._h) or 0)
+
+    def spectra_tensor(self):
+        """torch view [n_rays][K] (float64, on the plan's device) of Iv of the last spectra run: no copy, valid until
+        the plan's next run."""
+        import torch
+
+        class _View:  # the CUDA array interface, which torch.as_tensor reads
+            pass
+
+        ptr = self.spectra_ptr()
+        if not ptr or not self.n_rays:
+            return torch.empty((0, self.problem.beam.nv), dtype=torch.float64, device=torch.device("cuda", self.device))
+        v = _View()
+        v.__cuda_array_interface__ = dict(shape=(self.n_rays, self.problem.beam.nv), typestr="<f8", data=(ptr, False),
+                                          version=2, strides=None)
+        return torch.as_tensor(v, device=torch.device("cuda", self.device))
 
     def kernel_ms(self) -> float:
         """Device time of the last run's trace kernel (waits for it)."""
@@ -346,6 +385,38 @@ def create_image(problem: Problem, method: str = "auto", device: int = 0, device
         msgs = [t for bit, t in _FAILURE_TEXT.items() if out["failure_code"] & (1 << bit)]
         raise RayTraceError("Some rays failed: " + "; ".join(msgs))
     return out
+
+
+def calc_rays(problem: Problem, rays, method: int | None = None, device: int = 0) -> dict:
+    """n calls of RayTrace::calc_ray (src/RayTraceImage.cpp:189-204) in one, through rt_hip_calc_rays: host arrays
+    in, host arrays out, device memory bounded for any n.  `rays`: RAY_DTYPE records or an [n][4] float64 array of
+    (x, y, a, b), rounded to float as calc_ray rounds its arguments.
+
+    Returns dict(Iv [n][K], ray2 (RAY_DTYPE), err [n] int32, stats)."""
+    hl = HipLibrary.get()
+    m = cabi.Marshalled(problem)
+    rays = np.asarray(rays)
+    r4 = cabi.rays_to_array(rays) if rays.dtype == cabi.RAY_DTYPE else cabi.rays_to_array(cabi.rays_from_array(rays))
+    r4 = np.ascontiguousarray(r4, np.float64)
+    n, K = r4.shape[0], problem.beam.nv
+    Iv = np.empty((n, K))
+    ray2 = np.zeros((n, 4))
+    err = np.zeros(n, np.int32)
+    st = cabi.RtStats()
+    rc = hl.lib.rt_hip_calc_rays(device, m.N, problem.beam.dz, m.gain, m.seed_ref, K,
+                                 problem.method if method is None else method, cabi._dp(r4), n, cabi._dp(Iv),
+                                 cabi._dp(ray2), err.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(st))
+    hl.check(rc, "rt_hip_calc_rays")
+    return dict(Iv=Iv, ray2=cabi.rays_from_array(ray2), err=err,
+                stats={k: getattr(st, k) for k, _ in cabi.RtStats._fields_})
+
+
+def calc_ray(problem: Problem, ray, method: int | None = None, device: int = 0):
+    """Mirror of RayTrace::calc_ray for one ray (x, y, a, b): returns (err, Iv [K], ray2 (x, y, a, b))."""
+    ray = np.asarray(ray)
+    one = ray.reshape(1) if ray.dtype == cabi.RAY_DTYPE else np.asarray(ray, np.float64).reshape(1, 4)
+    out = calc_rays(problem, one, method, device)
+    return int(out["err"][0]), out["Iv"][0], tuple(float(out["ray2"][0][k]) for k in ("x", "y", "a", "b"))
 
 
 def calc_ray_path(problem: Problem, x, y, a, b, method: int | None = None, c: float = 0.5, device: int = 0):

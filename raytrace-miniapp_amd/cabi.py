@@ -117,6 +117,25 @@ def rays_ptr(rays: np.ndarray):
     return rays.ctypes.data_as(C.POINTER(RtRay))
 
 
+def rays_from_array(a: np.ndarray) -> np.ndarray:
+    """[n][4] float64 (x, y, a, b) -> rt_ray records, every coordinate rounded as the C cast (float) rounds it
+    (what RayTrace::calc_ray does with its arguments and Problem.build_rays with the grids)."""
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim != 2 or a.shape[1] != 4:
+        raise ValueError("rays: expected an [n][4] array of (x, y, a, b)")
+    out = np.empty(a.shape[0], dtype=RAY_DTYPE)
+    for c, name in enumerate(("x", "y", "a", "b")):
+        out[name] = a[:, c].astype(np.float32)
+    return out
+
+
+def rays_to_array(rays: np.ndarray) -> np.ndarray:
+    """rt_ray records -> [n][4] float64 (x, y, a, b), exactly (every float is a double)."""
+    rays = np.asarray(rays, dtype=RAY_DTYPE)
+    return np.stack([rays[name].astype(np.float64) for name in ("x", "y", "a", "b")], axis=1) if len(rays) \
+        else np.zeros((0, 4))
+
+
 def declare_hip_api(lib: C.CDLL) -> None:
     """Attach argtypes/restype for every symbol include/rt_hip.h declares."""
     P = C.POINTER
@@ -183,6 +202,15 @@ def declare_hip_api(lib: C.CDLL) -> None:
     lib.rt_hip_plan_enable_path.restype = C.c_int
     lib.rt_hip_plan_fetch_path.argtypes = [vp, c_float_p, P(C.c_int32)]
     lib.rt_hip_plan_fetch_path.restype = C.c_int
+    lib.rt_hip_plan_enable_spectra.argtypes = [vp, C.c_int]
+    lib.rt_hip_plan_enable_spectra.restype = C.c_int
+    lib.rt_hip_plan_fetch_spectra.argtypes = [vp, c_double_p, P(RtRay), P(C.c_int32)]
+    lib.rt_hip_plan_fetch_spectra.restype = C.c_int
+    lib.rt_hip_plan_spectra_ptr.argtypes = [vp]
+    lib.rt_hip_plan_spectra_ptr.restype = vp
+    lib.rt_hip_calc_rays.argtypes = [C.c_int, C.c_int, C.c_double, P(RtGain), P(RtSeed), C.c_int, C.c_int, c_double_p,
+                                     C.c_size_t, c_double_p, c_double_p, P(C.c_int32), P(RtStats)]
+    lib.rt_hip_calc_rays.restype = C.c_int
     lib.rt_hip_plan_set_debug.argtypes = [vp, C.c_uint]
     lib.rt_hip_plan_set_debug.restype = C.c_int
     lib.rt_hip_plan_destroy.argtypes = [vp]
@@ -196,5 +224,6 @@ HIP_API_SYMBOLS = [
     "rt_hip_plan_set_rays", "rt_hip_plan_set_ray_grid", "rt_hip_plan_run", "rt_hip_plan_fetch",
     "rt_hip_plan_kernel_ms", "rt_hip_plan_kernel_times", "rt_hip_plan_last_fused", "rt_hip_plan_set_timing_ring", "rt_hip_plan_ring_times", "rt_hip_plan_image_ptr", "rt_hip_plan_iang_ptr", "rt_hip_plan_enable_probe",
     "rt_hip_plan_fetch_probe", "rt_hip_plan_set_exact_emission", "rt_hip_plan_set_step_factor", "rt_hip_plan_enable_path",
-    "rt_hip_plan_fetch_path", "rt_hip_plan_set_debug", "rt_hip_plan_destroy",
+    "rt_hip_plan_fetch_path", "rt_hip_plan_enable_spectra", "rt_hip_plan_fetch_spectra", "rt_hip_plan_spectra_ptr",
+    "rt_hip_calc_rays", "rt_hip_plan_set_debug", "rt_hip_plan_destroy",
 ]

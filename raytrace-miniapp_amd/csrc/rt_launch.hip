@@ -3,12 +3,13 @@
 // Replaces the launch half of RayTraceImageCudaLoop (src/RayTraceImageCuda.cu:198-203: one thread-per-ray
 // launch): a run is the march kernel (persistent lanes over LDS-resident tables, rt_march.hip) -> one
 // 96-byte record per ray -> the frequency / deposit kernel (rt_freq.hip), back to back on one queue, or the
-// path tracer (rt_path.hip) in place of the frequency kernel.  This is the only translation unit with the
+// path tracer (rt_path.hip) or the spectra kernel (rt_spec.hip) in place of the frequency kernel.  This is the only translation unit with the
 // kernels of the path in it; the rest of the library reaches them through the functions declared in
 // rt_runtime.h.
 #include "rt_path.hip" // debug path tracer (before rt_freq.hip: no FMA contraction there)
 #include "rt_freq.hip" // kernel B (includes rt_march.hip, kernel A)
 #include "rt_fused.hip" // both as two phases of one launch
+#include "rt_spec.hip" // spectra mode: per-ray spectra in place of the deposit
 
 #include "rt_runtime.h"
 
@@ -173,6 +174,45 @@ int launch_freq_any(rt_hip_plan *p, hipStream_t stream, unsigned tile_begin = 0,
     return (S == 6) ? launch_freq<6, false, false>(p, stream, 0) : launch_freq<0, false, false>(p, stream, 0);
 }
 
+// spectra mode: rt_spec_kernel over all tiles, one 16-wave work-group per CU (the staging rows of 16 waves and the
+// exponent tables take 148 KB of LDS)
+template <int SF, bool EMIS> int launch_spec(rt_hip_plan *p, hipStream_t stream)
+{
+    const int wg_waves = rt::FREQ_WG_WAVES;
+    const size_t lds   = ((size_t) 2 * rt::EXP_TAB + (size_t) wg_waves * rt::WAVE * rt::XS_ROW) * sizeof(double);
+    if (lds > p->lds_limit)
+        return fail_arg("spectra kernel: the staging rows do not fit into the LDS of this device");
+    const unsigned long long want = ((unsigned long long) p->P.n_tiles + (unsigned) wg_waves - 1) / (unsigned) wg_waves;
+    const unsigned grid           = (unsigned) (want < (unsigned long long) p->cu_count ? want : (unsigned long long) p->cu_count);
+    if (grid == 0)
+        return RT_OK;
+    p->P.tile_begin = 0;
+    p->P.tile_end   = p->P.n_tiles;
+    p->P.freq_id    = 0;
+    const rt::FreqKArg f = freq_args(p, false, 0, (unsigned long long) grid * (unsigned) wg_waves);
+    rt::SpecKArg a;
+    memset(&a, 0, sizeof(a));
+    a.hot       = f.hot;
+    a.hot.image = nullptr;
+    a.hot.iang  = nullptr;
+    a.cold      = f.cold;
+    a.out       = p->spec[p->spec_sel];
+    const int rc = allow_lds(reinterpret_cast<const void *>(&rt::rt_spec_kernel<SF, EMIS>), p->device, lds, p->lds_limit);
+    if (rc != RT_OK)
+        return rc;
+    hipLaunchKernelGGL((rt::rt_spec_kernel<SF, EMIS>), dim3(grid), dim3((unsigned) wg_waves * 64), lds, stream, a);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+int launch_spec_any(rt_hip_plan *p, hipStream_t stream)
+{
+    const int S = p->P.L * RT_N_SUB;
+    if (p->P.use_emis)
+        return (S == 6) ? launch_spec<6, true>(p, stream) : launch_spec<0, true>(p, stream);
+    return (S == 6) ? launch_spec<6, false>(p, stream) : launch_spec<0, false>(p, stream);
+}
+
 } // namespace
 
 namespace rt {
@@ -327,7 +367,7 @@ int plan_launch_run(rt_hip_plan *p, hipStream_t stream)
     // of sixteen waves marching less.  Two kernels stay the rule for this mode; RT_HIP_FUSED_SEED=1 takes the one launch.)
     const bool fused_emis = p->P.use_emis && p->P.method == 1 && p->P.own_cells && p->P.rays.nga * p->P.rays.ngb >= 32;
     const bool fused_gain = !p->P.use_emis && p->P.rays.list == nullptr && env_unsigned("RT_HIP_FUSED_SEED", 0, 0, 1) == 1;
-    const bool fused_cand = lds_tab && n_launch == 1 && p->n_rays > 0 && !p->path_on && !p->probe_on && p->P.debug == 0 &&
+    const bool fused_cand = lds_tab && n_launch == 1 && p->n_rays > 0 && !p->path_on && !p->spectra_on && !p->probe_on && p->P.debug == 0 &&
                             (fused_emis || fused_gain) && !p->P.exclusive && p->P.safe == 0 &&
                             p->n_iang * sizeof(double) <= 32 * 1024 && env_unsigned("RT_HIP_FUSED", 1, 1, 2) == 1;
     unsigned bthr = lds_tab ? 1024u : 256u;
@@ -412,6 +452,23 @@ int plan_launch_run(rt_hip_plan *p, hipStream_t stream)
         HIP_TRY(hipMemsetAsync(p->path_err, 0, (size_t) p->n_rays * sizeof(int32_t), stream));
         p->P.path     = p->path_dev;
         p->P.path_err = p->path_err;
+    }
+    if (p->spectra_on) {
+        // the buffers of this run's set, kept while they are large enough (no zeroing: the kernel writes every element)
+        rt::SpecOut &o = p->spec[p->spec_sel];
+        if (p->spec_rays[p->spec_sel] < (size_t) p->n_rays || !o.Iv) {
+            plan_quiesce(p);
+            (void) hipFree(o.Iv);
+            o = {};
+            p->spec_rays[p->spec_sel] = 0;
+            const size_t n = (size_t) p->n_rays, iv_bytes = align_up(n * (size_t) p->P.K * sizeof(double) + 16, 256);
+            unsigned char *b = nullptr;
+            HIP_TRY(dev_malloc((void **) &b, iv_bytes + align_up(n * sizeof(rt_ray) + 16, 256) + n * sizeof(int32_t) + 16));
+            o.Iv   = reinterpret_cast<double *>(b);
+            o.ray2 = reinterpret_cast<rt_ray *>(b + iv_bytes);
+            o.err  = reinterpret_cast<int32_t *>(b + iv_bytes + align_up(n * sizeof(rt_ray) + 16, 256));
+            p->spec_rays[p->spec_sel] = n;
+        }
     }
     HIP_TRY(hipEventRecord(p->ev0, stream));
     p->last_fused = false;
@@ -560,6 +617,11 @@ int plan_launch_run(rt_hip_plan *p, hipStream_t stream)
             hipLaunchKernelGGL(rt::rt_path_kernel, dim3((unsigned) ((p->n_rays + 255) / 256)), dim3(256), 0, stream, p->P);
             HIP_TRY(hipGetLastError());
         }
+    } else if (p->spectra_on) {
+        // the spectra kernel replaces the frequency / deposit kernel: no image is produced
+        const int rc = launch_spec_any(p, stream);
+        if (rc != RT_OK)
+            return rc;
     } else if (!(p->P.debug & 1u)) {
         const int rc = launch_freq_any(p, stream);
         if (rc != RT_OK)

@@ -16,6 +16,8 @@
 #include <cstring>
 #include <memory>
 #include <mutex>
+#include <string>
+#include <thread>
 
 using namespace rtr;
 
@@ -183,6 +185,8 @@ void rt_hip_plan_destroy(rt_hip_plan *p)
     pool_free(p->device, p->rec);
     (void) hipFree(p->path_dev);
     (void) hipFree(p->path_err);
+    (void) hipFree(p->spec[0].Iv); // (ray2 and err of a set live in the same allocation)
+    (void) hipFree(p->spec[1].Iv);
     pool_free(p->device, p->arena);
     pool_free(p->device, p->rays_dev);
     pool_free(p->device, p->grid_dev);
@@ -805,6 +809,8 @@ int rt_hip_plan_enable_path(rt_hip_plan *p, int on)
 {
     if (!p)
         return fail_arg("rt_hip_plan_enable_path: NULL plan");
+    if (on && p->spectra_on)
+        return fail_arg("rt_hip_plan_enable_path: the plan is in spectra mode (one per-ray output at a time)");
     p->path_on = on != 0;
     return RT_OK;
 }
@@ -822,6 +828,37 @@ int rt_hip_plan_fetch_path(rt_hip_plan *p, float *path, int32_t *err)
         HIP_TRY(hipMemcpy(err, p->path_err, (size_t) p->n_rays * sizeof(int32_t), hipMemcpyDeviceToHost));
     return RT_OK;
 }
+
+int rt_hip_plan_enable_spectra(rt_hip_plan *p, int on)
+{
+    if (!p)
+        return fail_arg("rt_hip_plan_enable_spectra: NULL plan");
+    if (on && p->path_on)
+        return fail_arg("rt_hip_plan_enable_spectra: the path tracer is enabled (one per-ray output at a time)");
+    p->spectra_on = on != 0;
+    return RT_OK;
+}
+
+int rt_hip_plan_fetch_spectra(rt_hip_plan *p, double *Iv, rt_ray *ray2, int32_t *err)
+{
+    if (!p || !p->ran || !p->last_spectra)
+        return fail_arg("rt_hip_plan_fetch_spectra: the last run was not a spectra run");
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipStreamSynchronize(p->last_stream));
+    const size_t n       = (size_t) p->n_rays;
+    const rt::SpecOut &o = p->spec[p->spec_last];
+    if (n == 0)
+        return RT_OK;
+    if (Iv)
+        HIP_TRY(hipMemcpy(Iv, o.Iv, n * (size_t) p->P.K * sizeof(double), hipMemcpyDeviceToHost));
+    if (ray2)
+        HIP_TRY(hipMemcpy(ray2, o.ray2, n * sizeof(rt_ray), hipMemcpyDeviceToHost));
+    if (err)
+        HIP_TRY(hipMemcpy(err, o.err, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+double *rt_hip_plan_spectra_ptr(rt_hip_plan *p) { return p && p->ran && p->last_spectra ? p->spec[p->spec_last].Iv : nullptr; }
 
 int rt_hip_plan_enable_probe(rt_hip_plan *p, int on)
 {
@@ -865,12 +902,17 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
         return fail_arg("rt_hip_plan_run: NULL plan");
     HIP_TRY(hipSetDevice(p->device));
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
-    if (!image_dev) {
+    const bool spectra = p->spectra_on; // no image, no I_ang: neither allocated nor zeroed
+    if (spectra && (image_dev || iang_dev))
+        return fail_arg("rt_hip_plan_run: a spectra run takes no image buffers");
+    if (spectra && p->path_on)
+        return fail_arg("rt_hip_plan_run: spectra mode and the path tracer are both enabled");
+    if (!spectra && !image_dev) {
         if (!p->image_own)
             HIP_TRY(pool_alloc(p->device, (void **) &p->image_own, p->n_image * sizeof(double)));
         image_dev = p->image_own;
     }
-    if (!iang_dev) {
+    if (!spectra && !iang_dev) {
         if (!p->iang_own)
             HIP_TRY(pool_alloc(p->device, (void **) &p->iang_own, p->n_iang * sizeof(double)));
         iang_dev = p->iang_own;
@@ -885,7 +927,7 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
         HIP_TRY(hipMemsetAsync(p->probe, 0, (size_t) p->n_rays * (sizeof(rt_ray) + 8), stream));
     static_assert(sizeof(rt::DevCtl) % 8 == 0 && alignof(rt::DevCtl) >= 8, "zeroed in 8-byte words");
     // (exclusive mode writes every image row exactly once: its image is not zeroed)
-    rc = launch_zero3(stream, p->P.exclusive ? nullptr : image_dev, p->n_image * sizeof(double), iang_dev, p->n_iang * sizeof(double),
+    rc = launch_zero3(stream, (p->P.exclusive || spectra) ? nullptr : image_dev, p->n_image * sizeof(double), iang_dev, p->n_iang * sizeof(double),
                       p->ctl, sizeof(rt::DevCtl));
     if (rc != RT_OK)
         return rc;
@@ -906,6 +948,8 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
     p->last_stream = stream;
     p->last_image  = image_dev;
     p->last_iang   = iang_dev;
+    p->last_spectra = spectra;
+    p->spec_last   = p->spec_sel;
     p->ran         = true;
     p->queued      = false; // (`ran` + last_stream cover it from here)
     p->repeated    = false;
@@ -918,6 +962,8 @@ int rt_hip_plan_fetch(rt_hip_plan *p, double *image, double *I_ang, unsigned int
 {
     if (!p || !p->ran)
         return fail_arg("rt_hip_plan_fetch: plan has not run");
+    if (p->last_spectra && (image || I_ang))
+        return fail_arg("rt_hip_plan_fetch: the last run was a spectra run, it has no image (rt_hip_plan_fetch_spectra)");
     HIP_TRY(hipSetDevice(p->device));
     HIP_TRY(hipStreamSynchronize(p->last_stream));
     // the control block behind the chunk counters: failure code, failed rays, statistics
@@ -934,7 +980,8 @@ int rt_hip_plan_fetch(rt_hip_plan *p, double *image, double *I_ang, unsigned int
     else
         HIP_TRY(read_ctl());
     // rays that failed in the frequency pass have been deposited: repeat the pass without them
-    if ((c.failure_code & ((1u << 2) | (1u << 3))) && !p->path_on && !(p->P.debug & 1u) && !p->repeated) {
+    // (not after a spectra run: nothing was deposited, and the per-ray codes say which rays failed)
+    if ((c.failure_code & ((1u << 2) | (1u << 3))) && !p->path_on && !p->last_spectra && !(p->P.debug & 1u) && !p->repeated) {
         const int rc = plan_repeat_checked(p);
         if (rc != RT_OK)
             return rc;
@@ -1155,6 +1202,120 @@ int rt_hip_image_loop(int device, int N, const rt_beam *beam, const rt_gain *gai
     rt_hip_plan_destroy(p); // waits for whatever is still in flight
     release_queue(device, q);
     lap("destroy");
+    return rc;
+}
+
+int rt_hip_calc_rays(int device, int N, double dz, const rt_gain *gain, const rt_seed *seed, int K, int method, const double *rays,
+                     size_t n, double *Iv, double *ray2, int32_t *err, rt_stats *stats)
+{
+    if (!gain || K < 1)
+        return fail_arg("rt_hip_calc_rays: NULL gain tables or K < 1");
+    if (!rays && n)
+        return fail_arg("rt_hip_calc_rays: NULL ray list");
+    if (n > MAX_LIST_RAYS)
+        return fail_arg("rt_hip_calc_rays: 2^32 - 4096 rays or more: split the call");
+    if (stats)
+        memset(stats, 0, sizeof(*stats));
+    if (n == 0)
+        return RT_OK;
+    const auto t_start = std::chrono::steady_clock::now();
+    // calc_ray has no beam: a one-cell stand-in carries dz and K (the spectra kernel reads neither grids nor dv)
+    const double zero = 0.0;
+    std::vector<double> dv((size_t) K, 0.0);
+    rt_beam beam;
+    memset(&beam, 0, sizeof(beam));
+    beam.nx = beam.ny = beam.na = beam.nb = 1;
+    beam.nv = K;
+    beam.dx = beam.dy = beam.da = beam.db = 1.0;
+    beam.dz = dz;
+    beam.x = beam.y = beam.a = beam.b = &zero;
+    beam.dv = dv.data();
+    // rays per chunk: the spectra of a chunk take at most 1 GiB of device memory, whole 64-ray tiles
+    // (RT_HIP_CALC_RAYS_CHUNK: rays per chunk, for tests of the chunked path)
+    size_t chunk = ((size_t) 1 << 30) / ((size_t) K * sizeof(double)) / 64 * 64;
+    chunk        = chunk < 64 ? 64 : chunk;
+    chunk        = (size_t) env_unsigned("RT_HIP_CALC_RAYS_CHUNK", (unsigned) (chunk > 0xffffff00ull ? 0xffffff00ull : chunk), 1, 0xffffff00u);
+    const bool overlap = env_unsigned("RT_HIP_CALC_RAYS_OVERLAP", 1, 0, 1) == 1; // 0: download a chunk before the next one starts (A/B)
+    hipStream_t q  = lease_queue(device);
+    rt_hip_plan *p = nullptr;
+    int rc         = plan_create_on(&p, nullptr, device, N, &beam, gain, seed, method, 1.0);
+    if (rc != RT_OK) {
+        release_queue(device, q);
+        return rc;
+    }
+    rc = rt_hip_plan_enable_spectra(p, 1);
+    std::vector<rt_ray> list, exit_rays[2];
+    std::thread download;
+    int rc_down[2] = { RT_OK, RT_OK };
+    std::string err_down[2];
+    // chunk c of the outputs, device -> caller, on a thread of its own: blocking copies do not wait for the run's queue
+    auto fetch_chunk = [&](unsigned set, size_t begin, size_t count) {
+        const rt::SpecOut o = p->spec[set];
+        rc_down[set]        = [&]() {
+            HIP_TRY(hipSetDevice(device));
+            if (Iv)
+                HIP_TRY(hipMemcpy(Iv + begin * (size_t) K, o.Iv, count * (size_t) K * sizeof(double), hipMemcpyDeviceToHost));
+            if (err)
+                HIP_TRY(hipMemcpy(err + begin, o.err, count * sizeof(int32_t), hipMemcpyDeviceToHost));
+            if (ray2) {
+                exit_rays[set].resize(count);
+                HIP_TRY(hipMemcpy(exit_rays[set].data(), o.ray2, count * sizeof(rt_ray), hipMemcpyDeviceToHost));
+                for (size_t r = 0; r < count; r++) {
+                    const rt_ray &e = exit_rays[set][r];
+                    double *d       = ray2 + 4 * (begin + r);
+                    d[0] = e.x, d[1] = e.y, d[2] = e.a, d[3] = e.b;
+                }
+            }
+            return (int) RT_OK;
+        }();
+        if (rc_down[set] != RT_OK)
+            err_down[set] = last_error(); // (the error text is per thread)
+    };
+    unsigned set = 0;
+    for (size_t begin = 0; begin < n && rc == RT_OK; begin += chunk, set ^= 1u) {
+        const size_t count = n - begin < chunk ? n - begin : chunk;
+        list.resize(count);
+        for (size_t r = 0; r < count; r++) { // RayTraceImage.cpp:195-199: the coordinates are rounded to float
+            const double *s = rays + 4 * (begin + r);
+            list[r]         = rt_ray{ (float) s[0], (float) s[1], (float) s[2], (float) s[3] };
+        }
+        rc = rt_hip_plan_set_rays(p, list.data(), count);
+        p->spec_sel = set;
+        if (rc == RT_OK)
+            rc = rt_hip_plan_run(p, q, nullptr, nullptr); // asynchronous: the previous chunk is still on its way down
+        if (download.joinable())
+            download.join();
+        rt_stats st;
+        unsigned int code = 0;
+        if (rc == RT_OK)
+            rc = rt_hip_plan_fetch(p, nullptr, nullptr, &code, nullptr, 0, nullptr, &st); // waits for the run
+        if (rc == RT_OK && stats) {
+            stats->n_rays += st.n_rays;
+            stats->cell_steps += st.cell_steps;
+            stats->n_escaped += st.n_escaped;
+            stats->n_skipped += st.n_skipped;
+            stats->kernel_ms += st.kernel_ms;
+            stats->march_ms += st.march_ms;
+            stats->freq_ms += st.freq_ms;
+        }
+        if (rc == RT_OK) {
+            download = std::thread(fetch_chunk, set, begin, count);
+            if (!overlap)
+                download.join();
+        }
+    }
+    if (download.joinable())
+        download.join();
+    for (unsigned d = 0; d < 2 && rc == RT_OK; d++) {
+        if (rc_down[d] != RT_OK) {
+            rc           = rc_down[d];
+            last_error() = err_down[d];
+        }
+    }
+    rt_hip_plan_destroy(p);
+    release_queue(device, q);
+    if (stats)
+        stats->total_ms = (float) std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     return rc;
 }
 

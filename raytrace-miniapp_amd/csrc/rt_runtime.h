@@ -6,12 +6,13 @@
 //                   rt_hip_image_loop (the host-pointer entry the C++ adapter calls)
 //   rt_raygrid.hip  a ray list that is really a tensor grid: recognition + bit-wise verification,
 //                   list-mode launch tangents and the probe of the host's libm
-//   rt_launch.hip   the kernels (rt_march.hip, rt_freq.hip, rt_path.hip) and how a run puts them on a queue
+//   rt_launch.hip   the kernels (rt_march.hip, rt_freq.hip, rt_path.hip, rt_spec.hip) and how a run puts them on a queue
 //   rt_multi.hip    all devices of the node: RCCL loader, communicator, rt_hip_multi_image_loop
 // Only rt_launch.hip and rt_multi.hip contain device code.
 #pragma once
 
 #include "rt_device.h"
+#include "rt_spec.h"
 
 #include <chrono>
 #include <string>
@@ -38,6 +39,14 @@ struct rt_hip_plan {
     float *path_dev    = nullptr; // [n_rays][3L+1][3]
     int32_t *path_err  = nullptr; // [n_rays]
     size_t path_rays   = 0;
+    // spectra mode (rt_hip_plan_enable_spectra): per-ray spectra instead of the image.  Two buffer sets, so that the
+    // host-pointer entry (rt_hip_calc_rays) can download one chunk while the next runs; a plan of its own uses set 0.
+    bool spectra_on    = false;
+    bool last_spectra  = false;   // the last run was a spectra run
+    unsigned spec_sel  = 0;       // buffer set the next run writes
+    unsigned spec_last = 0;       // ... and the one the last run wrote
+    rt::SpecOut spec[2] = {};
+    size_t spec_rays[2] = { 0, 0 }; // rays each set has room for
     size_t rec_bytes   = 0;
     hipEvent_t evm     = nullptr; // between march and frequency kernels
     const rt_ray *host_rays = nullptr; // ray list still on the host, uploaded by the next run (rt_hip_image_loop)

@@ -1,0 +1,375 @@
+#pragma once
+// rt_spec.hip -- spectra mode: RayTrace::calc_ray (src/RayTraceImage.cpp:189-204) for every ray of a run.
+//
+// What RayTrace_calc_ray does after the march (Helper.h:514-594), per ray and with nothing deposited: the -1 test, the
+// exit ray, the seed spectrum of a seeded, non-escaped ray, the emission recurrence per sub-segment or the gain-only
+// product, then the -2 / -3 scan.  Reads the tile-wise march records (rt_device.h) as rt_freq_kernel does and has its
+// shape: lanes = rays, a wave owns a tile of 64 consecutive rays, VEC frequencies per step, the float64 building
+// blocks of rt_freq.hip (so the two modes take the same arithmetic, rt_hip_plan_set_exact_emission included).
+//
+// Outputs: Iv [n_rays][K] (row stride K, not Kp), ray2 [n_rays], err [n_rays].  No image, no I_ang, no atomics on data.
+//
+// The stores are the hot part: n K 8 bytes, more than the image path moves.  A lane that wrote its own row would
+// put the 64 lanes of a store instruction into 64 rows; instead the wave stages 16 frequencies of its 64 rows in LDS
+// ([64][XS_ROW], the staging of the exclusive deposit in rt_freq.hip) and writes them as row segments of 128
+// contiguous bytes, 16 bytes per lane and eight rows per instruction.  A tile's output is one contiguous block of
+// 64 K doubles, so the eight row segments of an instruction lie K doubles apart inside it.
+#include "rt_freq.hip"
+#include "rt_spec.h"
+
+namespace rt {
+
+#pragma clang fp contract(fast) // (the float64 half, as in rt_freq.hip; the float32 preamble has nothing to contract)
+
+// 16 bytes from the staging rows to the output: written once, never read by this kernel
+// Ordinary stores: the 128-byte row segments of a group start wherever the row does (K doubles apart: 32 bytes off a
+// cache line per row for K = 52, 16 for K = 82), so most segments cover two lines in part and the next group of the same
+// row fills them up a few microseconds later -- in L2, if the lines may stay there.  The streaming stores of the exclusive
+// deposit (whole aligned lines there) send the parts to memory one by one: measured 1.89 against 1.27 ms on the stand-in,
+// 4.20 against 2.42 ms on seed_small (profiles/spectra_ab.txt; RT_SPEC_NT_STORES builds that form for the A/B).
+typedef double f64x2s __attribute__((ext_vector_type(2)));
+#ifdef RT_SPEC_NT_STORES
+#define SPEC_STORE16(src, dst) __builtin_nontemporal_store(*reinterpret_cast<const f64x2s *>(src), reinterpret_cast<f64x2s *>(dst))
+#else
+#define SPEC_STORE16(src, dst) (*reinterpret_cast<f64x2s *>(dst) = *reinterpret_cast<const f64x2s *>(src))
+#endif
+
+// slot s of the record of ray ridx, zero if the ray never entered that sub-segment: rec_slot (rt_device.h) with the
+// load behind the test instead of a select between two addresses (which parks the zero slot in scratch)
+__device__ __forceinline__ RecSlot spec_slot(const unsigned char *rec, unsigned ridx, unsigned rec_stride, int s, int S, unsigned flags_steps,
+                                             bool backward)
+{
+    const int n_done = (int) ((flags_steps >> REC_NDONE_SHIFT) & REC_NDONE_MASK);
+    RecSlot r        = { 0.0f, 0.0f, 0 };
+    if (backward ? s >= S - n_done : s < n_done) {
+        const float *q = reinterpret_cast<const float *>(rec + rec_slot_off(ridx, s, rec_stride));
+        r.g            = q[0];
+        r.e            = q[1];
+        r.c            = reinterpret_cast<const int *>(q)[2];
+    }
+    return r;
+}
+
+template <int SF, bool EMIS>
+__device__ __forceinline__ void spec_tile(const FreqHot &H, const unsigned hflags, ColdPtr C, const SpecOut &O, const double *tab,
+                                          double *stage, const unsigned tile, const int lane)
+{
+    const int S           = SF ? SF : H.L * RT_N_SUB;
+    const int K           = H.K;
+    const int Kp          = H.Kp;
+    const unsigned n_rays = H.n_rays;
+    const unsigned row0   = tile * WAVE;
+    const unsigned ridx   = row0 + (unsigned) lane;
+    const bool have       = ridx < n_rays;
+    const bool backward   = H.method == 1;
+    const unsigned rrec      = have ? ridx : 0u;
+    const unsigned char *rec = H.rec;
+    const bool probe_on   = (hflags & FQ_PROBE) != 0;
+    const bool seeded     = (hflags & FQ_HAS_SEED) != 0;
+
+    // ---- per-ray preamble: record, -1 test, exit ray, seed factor (Helper.h:514-533) ----
+    unsigned fl = 0;
+    rt_ray ray  = { 0, 0, 0, 0 };
+    RecMeta m   = { 0, 0, 0, 0, 1, 0 };
+    RecSlot raw[SF ? SF : 1];
+#pragma unroll
+    for (int s = 0; s < (SF ? SF : 1); s++)
+        raw[s] = RecSlot{ 0.0f, 0.0f, 0 };
+    const DevRays R     = load_cold(&C->rays);
+    const bool need_ray = seeded && !backward; // the forward seed is taken at the launch ray
+    if (have) {
+        m = *reinterpret_cast<const RecMeta *>(rec + rec_meta_off(rrec, S, H.rec_stride));
+        if (SF) {
+            const unsigned char *slot0 = rec + rec_slot_off(rrec, 0, H.rec_stride);
+#pragma unroll
+            for (int s = 0; s < SF; s++)
+                raw[s] = *reinterpret_cast<const RecSlot *>(slot0 + (size_t) s * REC_SLOT_ROW);
+        }
+        if (need_ray) {
+            float ta, tb;
+            load_ray(R, ridx, ray, ta, tb, false);
+        }
+        fl = m.flags_steps & REC_FLAG_MASK;
+    }
+    auto report = [&](const unsigned bit) { // failure code and the first failing launch rays, as the image path reports them
+        atomicOr(&H.ctl->failure_code, 1u << bit);
+        const unsigned slot_f = atomicAdd(&H.ctl->n_failed, 1u);
+        if (slot_f < RT_N_FAILED_MAX) {
+            rt_ray r = ray;
+            if (!need_ray) {
+                float ta, tb;
+                load_ray(R, ridx, r, ta, tb, false);
+            }
+            H.ctl->failed[slot_f] = r;
+        }
+    };
+    const bool err1 = have && (double) (m.sz * m.sz) < 0.01; // Helper.h:515
+    rt_ray r2       = { 0.0f, 0.0f, 0.0f, 0.0f };            // (the reference leaves ray2 untouched on error -1: zeros here)
+    double f0       = 0.0;
+    if (have && !err1) {
+        r2.x = m.px; // Helper.h:518-521
+        r2.y = m.py;
+        r2.a = atanf_flt32_kernel(m.sx / m.sz) * 1e3f;
+        r2.b = atanf_flt32_kernel(m.sy / m.sz) * 1e3f;
+        // the seed factor of place_ray (rt_freq.hip), the image path's own: asked for the exit angles and for own-cell
+        // placement, which is two index computations that nothing here uses -- no grid is searched, none is needed
+        if (seeded && !(fl & F_ESCAPED))
+            f0 = place_ray(FQ_HAS_SEED | FQ_NEED_EXIT | FQ_OWN_CELLS, C, R, 0, backward, ridx, m, fl, ray).f0;
+    }
+    if (have) {
+        O.ray2[ridx] = r2;
+        if (probe_on) {
+            C->probe.ray2[ridx]  = r2;
+            C->probe.flags[ridx] = fl | (err1 ? F_ERR1 : 0u);
+            C->probe.steps[ridx] = m.flags_steps >> REC_STEPS_SHIFT;
+        }
+    }
+    if (err1)
+        report(1);
+    // a ray with error -1, and one whose every update is the identity (F_SKIP), gets a row of zeros
+    const bool live     = have && !err1 && !(fl & F_SKIP);
+    const bool any_live = __ballot(live) != 0ull;
+
+    // ---- the march record of this lane's ray (as freq_tile keeps it) ----
+    float gs[SF ? SF : 1];
+    double rs[SF ? SF : 1];
+    unsigned off[SF ? SF : 1];
+    const bool exact_emis = (hflags & FQ_EXACT_EMIS) != 0;
+    bool irregular = false, big = false;
+    if (SF) {
+        const int n_done = (int) ((m.flags_steps >> REC_NDONE_SHIFT) & REC_NDONE_MASK);
+#pragma unroll
+        for (int s = 0; s < SF; s++) {
+            const bool written = live && (backward ? s >= SF - n_done : s < n_done);
+            const RecSlot sl   = written ? raw[s] : RecSlot{ 0.0f, 0.0f, 0 };
+            gs[s]              = sl.g;
+            off[s]             = (unsigned) sl.c * (unsigned) Kp * 4u;
+            const bool regular = fabsf(gs[s]) >= RT_RS_MIN && fabsf(gs[s]) <= H.gs_cap && !exact_emis;
+            rs[s]              = regular ? div_fast((double) sl.e, (double) gs[s]) : 0.0;
+            irregular          = irregular || (!regular && (gs[s] != 0.0f || sl.e != 0.0f));
+            big                = big || !(fabsf(gs[s]) <= H.gs_cap * (80.0f / 708.0f));
+        }
+    }
+    const bool all_regular = __ballot(irregular) == 0ull;
+    const bool all_small   = all_regular && __ballot(big) == 0ull;
+    const bool gv_nan      = (hflags & FQ_GV_NAN) != 0;
+    const ConstF64 sfk     = (ConstF64) (unsigned long long) H.seed_fk;
+
+    auto load_rows = [&](FVec (&w)[SF ? SF : 1], const int kb) {
+#pragma unroll
+        for (int s = 0; s < (SF ? SF : 1); s++) {
+            const float *base = (s < RT_N_SUB ? H.gv0 : H.gv1) + kb;
+            unsigned o        = off[s];
+            asm volatile("" : "+v"(o)); // (SGPR base + 32-bit VGPR offset, see freq_tile)
+            w[s] = *reinterpret_cast<const FVec *>(reinterpret_cast<const char *>(base) + o);
+        }
+    };
+
+    double iv_min = 0.0;   // min over k of Iv, NaNs ignored: negative <=> error -2
+    bool has_nan  = false; // error -3 unless -2 (Helper.h:588-593: negative wins)
+    // a full tile and an even K: every 16-frequency group that lies inside K leaves as 16-byte stores
+    const bool wide_ok = row0 + WAVE <= n_rays && (K & 1) == 0;
+
+    for (int kb = 0; kb < K; kb += VEC) {
+        double Iv[VEC];
+#pragma unroll
+        for (int j = 0; j < VEC; j++)
+            Iv[j] = 0.0;
+        if (!any_live) {
+            // nothing to integrate: the rows are zeros
+        } else if (EMIS) {
+            if (SF) {
+                FVec w[SF ? SF : 1];
+                load_rows(w, kb);
+                if (all_small) {
+#pragma unroll
+                    for (int s = 0; s < SF; s++)
+                        ase_step_f32(Iv, gs[s], rs[s], w[s].v, tab + EXP_TAB);
+                } else if (all_regular) {
+#pragma unroll
+                    for (int s = 0; s < SF; s++)
+                        ase_step(Iv, gs[s], rs[s], w[s].v, tab);
+                } else
+#pragma unroll
+                for (int s = 0; s < SF; s++) {
+                    if (fabsf(gs[s]) >= RT_RS_MIN && fabsf(gs[s]) <= H.gs_cap && !exact_emis) {
+                        ase_step(Iv, gs[s], rs[s], w[s].v, tab);
+                    } else {
+                        const float e1 = live ? spec_slot(rec, rrec, H.rec_stride, s, SF, m.flags_steps, backward).e : 0.0f;
+                        if (gs[s] != 0.0f || e1 != 0.0f) { // else the update is the identity
+#pragma unroll
+                            for (int j = 0; j < VEC; j++)
+                                Iv[j] = ase_update(Iv[j], gs[s], e1, w[s].v[j], tab);
+                        }
+                    }
+                }
+                if (gv_nan) {
+#pragma unroll
+                    for (int j = 0; j < VEC; j++) {
+                        bool wn = false;
+#pragma unroll
+                        for (int s = 0; s < SF; s++)
+                            wn = wn || !(fabsf(w[s].v[j]) <= FLT_MAX);
+                        Iv[j] = wn ? __builtin_nan("") : Iv[j];
+                    }
+                }
+            } else {
+                bool wnan[VEC];
+#pragma unroll
+                for (int j = 0; j < VEC; j++)
+                    wnan[j] = false;
+                for (int s = 0; s < S; s++) {
+                    const RecSlot sl = spec_slot(rec, rrec, H.rec_stride, s, S, m.flags_steps, backward);
+                    const float g1 = sl.g, e1 = sl.e;
+                    const float *row = H.gain[s / RT_N_SUB + 1].gv + (size_t) sl.c * (size_t) Kp + kb;
+                    const FVec w     = *reinterpret_cast<const FVec *>(row);
+#pragma unroll
+                    for (int j = 0; j < VEC; j++)
+                        wnan[j] = wnan[j] || !(fabsf(w.v[j]) <= FLT_MAX);
+                    if (fabsf(g1) >= RT_RS_MIN && fabsf(g1) <= H.gs_cap && !exact_emis) {
+                        const double r1 = div_fast((double) e1, (double) g1);
+                        ase_step(Iv, g1, r1, w.v, tab);
+                    } else if (g1 != 0.0f || e1 != 0.0f) {
+#pragma unroll
+                        for (int j = 0; j < VEC; j++)
+                            Iv[j] = ase_update(Iv[j], g1, e1, w.v[j], tab);
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < VEC; j++)
+                    Iv[j] = wnan[j] ? __builtin_nan("") : Iv[j];
+            }
+        } else {
+            // gain only, Helper.h:569-580: f64 products summed in sub-segment order
+            double gl[VEC];
+#pragma unroll
+            for (int j = 0; j < VEC; j++)
+                gl[j] = 0.0;
+            if (SF) {
+                FVec w[SF ? SF : 1];
+                load_rows(w, kb);
+#pragma unroll
+                for (int s = 0; s < SF; s++) {
+#pragma unroll
+                    for (int j = 0; j < VEC; j++)
+                        gl[j] += (double) gs[s] * (double) w[s].v[j];
+                }
+            } else {
+                for (int s = 0; s < S; s++) {
+                    const RecSlot sl = spec_slot(rec, rrec, H.rec_stride, s, S, m.flags_steps, backward);
+                    const float *row = H.gain[s / RT_N_SUB + 1].gv + (size_t) sl.c * (size_t) Kp + kb;
+                    const FVec w     = *reinterpret_cast<const FVec *>(row);
+#pragma unroll
+                    for (int j = 0; j < VEC; j++)
+                        gl[j] += (double) sl.g * (double) w.v[j];
+                }
+            }
+            // Iv = f0 f[4][k] exp(gl); for f0 = 0 exactly 0 unless exp overflows (0 * inf), see freq_tile
+            bool need = f0 != 0.0;
+#pragma unroll
+            for (int j = 0; j < VEC; j++)
+                need = need || gl[j] > 700.0 || gl[j] != gl[j];
+#pragma unroll
+            for (int j = 0; j < VEC; j++)
+                Iv[j] = f0 * sfk[kb + j];
+            if (__ballot(need) != 0ull) {
+                double eg[VEC];
+                exp_tab_vec(gl, tab, eg);
+#pragma unroll
+                for (int j = 0; j < VEC; j++)
+                    Iv[j] *= eg[j];
+            }
+        }
+        // ---- scan (Helper.h:582-587) and staging: the lane's four values into its staging row ----
+        double *mine = stage + lane * XS_ROW + (kb & 12);
+#pragma unroll
+        for (int j = 0; j < VEC; j++) {
+            const double v = (live && kb + j < K) ? Iv[j] : 0.0; // (the padding columns K .. Kp-1 are not part of the spectrum)
+            iv_min         = fmin(iv_min, v);
+            has_nan        = has_nan || v != v;
+            mine[j]        = v;
+        }
+        if ((kb & 12) == 12 || kb + VEC >= K) {
+            __builtin_amdgcn_wave_barrier();
+            const int kbase = kb & ~15;
+            const int width = K - kbase < 16 ? K - kbase : 16; // frequencies of this group
+            if (wide_ok && width == 16) {
+                // eight lanes cover the 128 staged bytes of a row, a store instruction eight rows
+                double *dst        = O.Iv + ((size_t) (row0 + (unsigned) (lane >> 3)) * (size_t) K + (size_t) (kbase + 2 * (lane & 7)));
+                const size_t gstep = (size_t) 8 * (size_t) K; // eight rows on
+                const double *src  = stage + (lane >> 3) * XS_ROW + 2 * (lane & 7);
+#pragma unroll 4
+                for (int g = 0; g < WAVE / 8; g++)
+                    SPEC_STORE16(src + g * 8 * XS_ROW, dst + (size_t) g * gstep);
+            } else if (wide_ok) {
+                // the last, narrower group of a row (2 .. 14 frequencies): still 16 bytes per lane, the wave's lanes dealt over
+                // the 64 x hw pieces row by row.  (Folding a left-over of two frequencies into the group before it, as rows
+                // of 18 in the two spare doubles of the staging rows, was built and measured: seed_small, K = 82, 2.375
+                // against 2.413 ms, the stand-in, which has no such left-over, 1.254 against 1.226 ms.  Not kept.)
+                const unsigned hw = (unsigned) width >> 1; // 16-byte pieces per row
+                for (unsigned q = (unsigned) lane; q < WAVE * hw; q += WAVE) {
+                    const unsigned row = q / hw, piece = q - row * hw;
+                    SPEC_STORE16(stage + row * XS_ROW + 2 * piece, O.Iv + ((size_t) (row0 + row) * (size_t) K + (size_t) kbase + 2 * piece));
+                }
+            } else {
+                // ragged tile or odd K: 8 bytes per lane, four rows per instruction
+                const int k = kbase + (lane & 15);
+#pragma unroll 4
+                for (int g = 0; g < WAVE / 4; g++) {
+                    const unsigned row = row0 + (unsigned) (4 * g + (lane >> 4));
+                    if (row < n_rays && k < K)
+                        O.Iv[(size_t) row * (size_t) K + (size_t) k] = stage[(4 * g + (lane >> 4)) * XS_ROW + (lane & 15)];
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+    const bool bad_neg = live && iv_min < 0.0, bad_nan = live && has_nan;
+    if (have)
+        O.err[ridx] = err1 ? -1 : (bad_neg ? -2 : (bad_nan ? -3 : 0));
+    if (bad_neg || bad_nan)
+        report(bad_neg ? 2u : 3u);
+}
+
+// One work-group of FREQ_WG_WAVES waves per CU, tiles handed out from the eight sharded counters of the control block
+// (DevCtl::next_tile_f, rt_freq_kernel says why eight), one tile per fetch: every tile costs the same here.
+// LDS of a work-group, all dynamic: the two exponent tables of rt_freq_kernel, then [64][XS_ROW] staging doubles per wave.
+template <int SF, bool EMIS>
+__global__ void __launch_bounds__(FREQ_WG_WAVES * 64, EMIS ? RT_FREQ_WAVES : RT_FREQ_WAVES_SEED) rt_spec_kernel(const SpecKArg A)
+{
+    extern __shared__ __align__(16) unsigned char spec_lds[];
+    const FreqHot &H = A.hot;
+    double *exp2_tab = reinterpret_cast<double *>(spec_lds);
+    double *stage    = exp2_tab + 2 * EXP_TAB + (size_t) (unsigned) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6)) * (size_t) (WAVE * XS_ROW);
+    for (int c = (int) threadIdx.x; c < EXP_TAB; c += (int) blockDim.x) {
+        const double e        = exp2((double) c * (1.0 / EXP_TAB));
+        exp2_tab[c]           = e;
+        exp2_tab[EXP_TAB + c] = __hiloint2double(__double2hiint(e) - (c << 12), __double2loint(e));
+    }
+    __syncthreads();
+    const int lane             = lane_id();
+    const unsigned n_tiles_run = H.tile_end - H.tile_begin;
+    unsigned shard = blockIdx.x & 7u, tried = 0;
+    for (;;) {
+        unsigned t = 0;
+        if (lane == 0)
+            t = atomicAdd(&H.ctl->next_tile_f[H.freq_id][shard][0], 1u);
+        t = (unsigned) __builtin_amdgcn_readfirstlane((int) t);
+        if (t >= (n_tiles_run + 7u - shard) / 8u) { // this shard is empty: on to the next one, until all eight have been seen empty
+            if (++tried == 8)
+                break;
+            shard = (shard + 1) & 7u;
+            continue;
+        }
+        const unsigned tile = H.tile_begin + t * 8u + shard;
+        // the cold half of the argument block, the flag word and the lane number opaque per tile, as in rt_freq_kernel
+        ColdPtr C = (ColdPtr) ((const RT_CONST_AS char *) __builtin_amdgcn_kernarg_segment_ptr() + offsetof(SpecKArg, cold));
+        asm volatile("" : "+s"(C));
+        unsigned hflags = H.flags;
+        int lane_t      = lane;
+        asm volatile("" : "+s"(hflags), "+v"(lane_t));
+        spec_tile<SF, EMIS>(H, hflags, C, A.out, exp2_tab, stage, tile, lane_t);
+    }
+}
+
+} // namespace rt

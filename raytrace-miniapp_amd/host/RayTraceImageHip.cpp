@@ -12,6 +12,8 @@
 //   RayTraceImageHipMultiGPULoop  all devices of the node ("hip-multigpu" arm) through
 //        rt_hip_multi_image_loop: stands where the reference runs RayTraceImageThreadLoop
 //        (src/RayTraceImage.cpp:89-134) with setGPU called in the spawning thread (:116).
+//   RayTraceCalcRaysHip           n calls of RayTrace::calc_ray (src/RayTraceImage.cpp:189-204) in one, through
+//        rt_hip_calc_rays: per-ray spectrum, exit ray and return code
 #include "RayTrace.h"
 #include "common/RayTraceImageHelper.h"
 #include "utilities/RayUtilityMacros.h"
@@ -33,13 +35,11 @@ struct Flat {
     bool has_seed;
 };
 
-Flat flatten(int N, const RayTrace::EUV_beam_struct &b, const RayTrace::ray_gain_struct *g,
-             const RayTrace::ray_seed_struct *s)
+// gain and seed tables alone (what calc_ray takes: it has no beam)
+Flat flatten_tables(int N, const RayTrace::ray_gain_struct *g, const RayTrace::ray_seed_struct *s)
 {
     Flat f;
-    f.beam.nx = b.nx; f.beam.ny = b.ny; f.beam.na = b.na; f.beam.nb = b.nb; f.beam.nv = b.nv;
-    f.beam.dx = b.dx; f.beam.dy = b.dy; f.beam.da = b.da; f.beam.db = b.db; f.beam.dz = b.dz;
-    f.beam.x = b.x; f.beam.y = b.y; f.beam.a = b.a; f.beam.b = b.b; f.beam.dv = b.dv;
+    memset(&f.beam, 0, sizeof(f.beam));
     f.gain.resize((size_t) N);
     for (int i = 0; i < N; i++) {
         rt_gain &o = f.gain[(size_t) i];
@@ -57,6 +57,16 @@ Flat flatten(int N, const RayTrace::EUV_beam_struct &b, const RayTrace::ray_gain
         }
         f.seed.f0 = s->f0;
     }
+    return f;
+}
+
+Flat flatten(int N, const RayTrace::EUV_beam_struct &b, const RayTrace::ray_gain_struct *g,
+             const RayTrace::ray_seed_struct *s)
+{
+    Flat f    = flatten_tables(N, g, s);
+    f.beam.nx = b.nx; f.beam.ny = b.ny; f.beam.na = b.na; f.beam.nb = b.nb; f.beam.nv = b.nv;
+    f.beam.dx = b.dx; f.beam.dy = b.dy; f.beam.da = b.da; f.beam.db = b.db; f.beam.dz = b.dz;
+    f.beam.x = b.x; f.beam.y = b.y; f.beam.a = b.a; f.beam.b = b.b; f.beam.dv = b.dv;
     return f;
 }
 
@@ -131,4 +141,16 @@ void RayTraceImageHipMultiGPULoop(int N, const RayTrace::EUV_beam_struct &beam,
         memcpy(&r, &failed[i], sizeof(r));
         failed_rays.push_back(r);
     }
+}
+
+// n independent RayTrace::calc_ray calls (src/RayTraceImage.cpp:189-204: trace a ray, return its spectrum Iv[K], its
+// exit ray and its return code) on device 0.  rays / ray2: [n][4] doubles (x, y, a, b) as calc_ray takes and returns
+// them; Iv: [n][K]; err: [n] (0, -1, -2, -3).  Returns RT_OK or the status of the C ABI (rt_hip_last_error has the text).
+int RayTraceCalcRaysHip(size_t n, const double *rays, int N, double dz, const RayTrace::ray_gain_struct *gain,
+    const RayTrace::ray_seed_struct *seed, int K, int method, double *Iv, double *ray2, int *err)
+{
+    static_assert(sizeof(int) == sizeof(int32_t), "err is handed over as int32_t");
+    Flat f = flatten_tables(N, gain, seed);
+    return rt_hip_calc_rays(0, N, dz, f.gain.data(), f.has_seed ? &f.seed : NULL, K, method, rays, n, Iv, ray2,
+                            reinterpret_cast<int32_t *>(err), &g_last_stats);
 }
