@@ -104,6 +104,35 @@ class Oracle:
         out["Iv"] = Iv
         return out
 
+    def exit_rays(self, problem, rays, n_threads: int = 1):
+        """(ray2, err) of every ray and nothing else of the probe: what decides where a ray is deposited and whether
+        it is (tests/element_gate.py).  The probe is serial; n_threads > 1 runs contiguous chunks of the list in host
+        threads (ctypes releases the GIL for the call)."""
+        m = cabi.Marshalled(problem)
+        n = len(rays)
+        rays = np.ascontiguousarray(rays, dtype=cabi.RAY_DTYPE)
+        ray2 = np.zeros(n, cabi.RAY_DTYPE)
+        err = np.zeros(n, np.int32)
+
+        def part(lo, hi):
+            if hi <= lo:
+                return 0
+            return self.lib.rt_oracle_probe(
+                m.N, C.byref(m.beam), m.gain, m.seed_ref, problem.method, cabi.rays_ptr(rays[lo:hi]), hi - lo,
+                None, None, None, cabi.rays_ptr(ray2[lo:hi]), None, None, None, err[lo:hi].ctypes.data_as(P(C.c_int32)))
+
+        n_threads = max(1, min(int(n_threads), n // 1024 + 1))
+        edges = np.linspace(0, n, n_threads + 1).astype(np.int64)
+        if n_threads == 1:
+            rcs = [part(0, n)]
+        else:
+            from concurrent.futures import ThreadPoolExecutor
+            with ThreadPoolExecutor(n_threads) as ex:
+                rcs = list(ex.map(part, edges[:-1], edges[1:]))
+        if any(rcs):
+            raise RuntimeError(f"rt_oracle_probe failed: {rcs}")
+        return ray2, err
+
 
     def calc_ray_path(self, problem, rays, c: float = 0.5):
         """Per ray: x, y, I at the 3(N-1)+1 sub-segment boundaries -> dict(x, y, I [n][N2], err)."""

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import rel_l2
+from element_gate import DEFAULT_TIER, TIGHT_TIER, assert_elements, contribution_counts, counts_from_oracle, gate_outputs
 
 rt = importlib.import_module("raytrace-miniapp_amd")
 problem_mod = importlib.import_module("raytrace-miniapp_amd.problem")
@@ -25,6 +26,7 @@ def test_ase_medium_standin_vs_oracle(hip, oracle, ase_small):
     assert out["failure_code"] == 0 and ref["failure_code"] == 0
     assert out["stats"]["cell_steps"] == ref["counters"]["cell_steps"]
     assert rel_l2(out["image"], ref["image"]) < TOL and rel_l2(out["I_ang"], ref["I_ang"]) < TOL
+    gate_outputs(out, ref, p, contribution_counts(p), DEFAULT_TIER, "full size: stand-in, 6 384 000 rays, against the 16-thread oracle")
     # ASE property (SURVEY.md 8(c) i): ray ijkm lands in angle cell (k, m), so every
     # I_ang cell is a sum over all pixels and sum(I_ang) = sum_pixels sum_k 2 dv_k image
     K = p.beam.nv
@@ -40,6 +42,8 @@ def test_seed_medium_like_subsample_vs_oracle(hip, oracle, seed_small):
     ref = oracle.image_loop(p, n_threads=min(16, os.cpu_count() or 1))
     assert out["stats"]["cell_steps"] == ref["counters"]["cell_steps"]
     assert rel_l2(out["image"], ref["image"]) < TOL and rel_l2(out["I_ang"], ref["I_ang"]) < TOL
+    gate_outputs(out, ref, p, counts_from_oracle(oracle, p, n_threads=min(16, os.cpu_count() or 1)), TIGHT_TIER,
+                 "full size: seed_small x scale_problem(2) against the 16-thread oracle")
 
 
 def test_synthetic_config5_tile_vs_oracle(hip, oracle, ase_small):
@@ -54,6 +58,7 @@ def test_synthetic_config5_tile_vs_oracle(hip, oracle, ase_small):
     assert out["stats"]["cell_steps"] == ref["counters"]["cell_steps"]
     assert rel_l2(out["image"], ref["image"]) < TOL and rel_l2(out["I_ang"], ref["I_ang"]) < TOL
     assert np.linalg.norm(ref["image"]) > 0
+    gate_outputs(out, ref, p, contribution_counts(p), DEFAULT_TIER, "full size: config 5 tile, 96 x 64 pixels, K = 512")
 
 
 def test_exclusive_pixel_mode_equals_atomic_mode(hip, oracle, ase_small):
@@ -70,6 +75,10 @@ def test_exclusive_pixel_mode_equals_atomic_mode(hip, oracle, ase_small):
     assert np.array_equal(a["image"], a2["image"])
     assert rel_l2(a["image"], ref["image"]) < 2e-7 and rel_l2(b["image"], ref["image"]) < 2e-7
     assert rel_l2(a["I_ang"], ref["I_ang"]) < 2e-7
+    counts = contribution_counts(p)
+    gate_outputs(a, ref, p, counts, DEFAULT_TIER, "full size: exclusive pixel mode (rows stored), 70 x 33 pixels, K = 128")
+    gate_outputs(b, ref, p, counts, DEFAULT_TIER, "full size: the same grid as a list (rows added)")
+    gate_outputs(a, b, p, counts, "reordering", "full size: exclusive pixel mode against the list")
     assert (a["image"] == 0).reshape(-1, 128).all(axis=1).sum() == (ref["image"] == 0).reshape(-1, 128).all(axis=1).sum()
 
 
@@ -86,6 +95,8 @@ def test_seed_medium_standin_full_size_vs_oracle(hip, oracle, seed_small):
     assert out["stats"]["cell_steps"] == ref["counters"]["cell_steps"]
     assert rel_l2(out["image"], ref["image"]) < TOL and rel_l2(out["I_ang"], ref["I_ang"]) < TOL
     assert np.linalg.norm(ref["image"]) > 0
+    gate_outputs(out, ref, p, counts_from_oracle(oracle, p, n_threads=min(16, os.cpu_count() or 1)), TIGHT_TIER,
+                 "full size: seeded stand-in, 124 848 000 rays, against the 16-thread oracle")
 
 
 def test_config5_full_size_tiles_vs_oracle(hip, oracle, ase_small):
@@ -121,6 +132,7 @@ def test_config5_full_size_tiles_vs_oracle(hip, oracle, ase_small):
         assert small["stats"]["cell_steps"] == ref["counters"]["cell_steps"]
         assert np.array_equal(small["image"], tile), "full-size rows differ from the same tile traced alone"
         assert rel_l2(tile, ref["image"]) < TOL
+        assert_elements(tile, ref["image"], contribution_counts(q)[0], DEFAULT_TIER, f"full size: config 5, tile at ({i0}, {j0}) of 4096 x 4096 x 512", (T, T, K))
         steps_tiles += ref["counters"]["cell_steps"]
     assert steps_tiles > 0
     del image, img
@@ -141,6 +153,11 @@ def test_config5_centre_tile_vs_reference_frequency_slices(hip, ase_small):
     assert rel_l2(img.sum(axis=2), fx["row_sums"]) < TOL
     assert rel_l2(out["I_ang"], fx["I_ang"]) < TOL
     assert np.linalg.norm(fx["rows"]) > 0
+    # one ray per pixel: every element of a row is one ray's Iv, a row sum K of them, I_ang all T x T rays
+    nq = (T + 3) // 4
+    assert_elements(img[::4, ::4, :], fx["rows"], np.ones(nq * nq, np.int64), DEFAULT_TIER, "full size: config 5 centre tile, every 4th pixel's row, against the reference's frequency slices", (nq, nq, K))
+    assert_elements(img.sum(axis=2), fx["row_sums"], np.ones(T * T, np.int64), DEFAULT_TIER, "full size: config 5 centre tile, row sums, against the reference's frequency slices")
+    assert_elements(out["I_ang"], fx["I_ang"], np.full(out["I_ang"].size, T * T), DEFAULT_TIER, "full size: config 5 centre tile, I_ang, against the reference's frequency slices")
 
 
 def copy_beam_window(p, i0, j0, T):
@@ -240,3 +257,4 @@ def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(hip, ase_small, 
     img, iang = np.load(tmp_path / "image.npy"), np.load(tmp_path / "I_ang.npy")
     assert img.dtype == np.float64 and img.shape == ref["image"].shape and iang.shape == ref["I_ang"].shape
     assert rel_l2(img, ref["image"]) < 1e-12 and rel_l2(iang, ref["I_ang"]) < 1e-12
+    gate_outputs(dict(image=img, I_ang=iang), ref, p, contribution_counts(p), "reordering", "full size: bench.py --dump-outputs against a plan run")

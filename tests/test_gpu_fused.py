@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import rel_l2
+from element_gate import DEFAULT_TIER, TIGHT_TIER, contribution_counts, counts_from_oracle, gate_outputs
 
 rt = importlib.import_module("raytrace-miniapp_amd")
 problem_mod = importlib.import_module("raytrace-miniapp_amd.problem")
@@ -31,9 +32,11 @@ def run_grid(hip, p, fused, **grid):
     return out
 
 
-def same_images(a, b, tol=1e-13):
-    """Two device runs of one problem: the deposit order of the atomics differs, nothing else."""
+def same_images(a, b, p, counts, label, tol=1e-13):
+    """Two device runs of one problem: the deposit order of the atomics differs, nothing else -- whole-array and,
+    with the counts of the rays deposited into every element, under the reordering gate of element_gate.py."""
     assert rel_l2(a["image"], b["image"]) < tol and rel_l2(a["I_ang"], b["I_ang"]) < tol
+    gate_outputs(a, b, p, counts, "reordering", f"one launch: {label}, against the two kernels")
     for key in ("n_rays", "cell_steps", "n_escaped", "n_skipped"):
         assert a["stats"][key] == b["stats"][key], key
     assert a["failure_code"] == b["failure_code"]
@@ -44,7 +47,10 @@ def test_one_launch_run_of_the_shipped_file_equals_the_reference_and_the_two_ker
     assert one["fused"] and not two["fused"]
     assert one["stats"]["n_rays"] == 399000 and one["stats"]["cell_steps"] == 4768067
     assert rel_l2(one["image"], ase_ref["image"]) < TIGHT and rel_l2(one["I_ang"], ase_ref["I_ang"]) < TIGHT
-    same_images(one, two)
+    counts = contribution_counts(ase_small)
+    gate_outputs(one, ase_ref, ase_small, counts, DEFAULT_TIER, "one launch: ASE_small against ASE_small_ref_cpu.npz")
+    gate_outputs(two, ase_ref, ase_small, counts, DEFAULT_TIER, "two kernels: ASE_small against ASE_small_ref_cpu.npz")
+    same_images(one, two, ase_small, counts, "ASE_small")
     # the default (no environment) is the one-launch run
     with hip.Plan(ase_small) as plan:
         plan.set_ray_grid().run()
@@ -62,11 +68,13 @@ def test_one_launch_run_on_scaled_problems_takes_every_work_group_size(hip, orac
         pytest.skip("fewer than 32 rays per pixel: the run keeps two kernels")
     one, two = run_grid(hip, p, True), run_grid(hip, p, False)
     assert one["fused"] and not two["fused"]
-    same_images(one, two)
+    counts = contribution_counts(p)
+    same_images(one, two, p, counts, f"scale_problem({scale:g})")
     if scale <= 2.0:
         ref = oracle.image_loop(p, p.build_rays())
         assert one["stats"]["cell_steps"] == ref["counters"]["cell_steps"]
         assert rel_l2(one["image"], ref["image"]) < TIGHT and rel_l2(one["I_ang"], ref["I_ang"]) < TIGHT
+        gate_outputs(one, ref, p, counts, DEFAULT_TIER, f"one launch: scale_problem({scale:g}) against the oracle")
 
 
 def test_one_launch_run_with_ragged_ray_ranges_and_strides(hip, oracle, ase_small):
@@ -77,11 +85,13 @@ def test_one_launch_run_with_ragged_ray_ranges_and_strides(hip, oracle, ase_smal
         one = run_grid(hip, ase_small, True, first=first, stride=stride, count=count)
         two = run_grid(hip, ase_small, False, first=first, stride=stride, count=count)
         assert one["fused"] and one["stats"]["n_rays"] == count
-        same_images(one, two)
         ids = first + stride * np.arange(count, dtype=np.int64)
+        counts = contribution_counts(ase_small, ase_small.build_rays(ids))
+        same_images(one, two, ase_small, counts, f"rays {first} + {stride} i, i < {count}")
         ref = oracle.image_loop(ase_small, ase_small.build_rays(ids))
         assert one["stats"]["cell_steps"] == ref["counters"]["cell_steps"]
         assert rel_l2(one["image"], ref["image"]) < TIGHT and rel_l2(one["I_ang"], ref["I_ang"]) < TIGHT
+        gate_outputs(one, ref, ase_small, counts, DEFAULT_TIER, f"one launch: rays {first} + {stride} i, i < {count}, against the oracle")
 
 
 @pytest.mark.parametrize("N", [2, 4])
@@ -94,15 +104,18 @@ def test_one_launch_run_for_other_numbers_of_lengths(hip, oracle, ase_small, N):
     one, two = run_grid(hip, p, True), run_grid(hip, p, False)
     # (N = 4: three lengths of tables fill the LDS, no room for the frequency pass beside them -- two kernels)
     assert one["fused"] == (N == 2) and not two["fused"]
-    same_images(one, two)
+    counts = contribution_counts(p)
+    same_images(one, two, p, counts, f"N = {N}")
     ref = oracle.image_loop(p, p.build_rays())
     assert rel_l2(one["image"], ref["image"]) < TIGHT and rel_l2(one["I_ang"], ref["I_ang"]) < TIGHT
+    gate_outputs(one, ref, p, counts, DEFAULT_TIER, f"one launch: N = {N} against the oracle")
 
 
 def test_one_launch_run_reports_failing_rays_like_the_cpu_loop(hip, oracle, ase_small):
     """Error -3 / -2 (Helper.h:582-594) found by the frequency phase: the run is repeated on the march records
     (checking pass + deposit without the failing rays) by the stand-alone frequency kernel."""
     from test_gpu_edges import same_outputs_in_a_failing_run
+    # (NaN and sign-flipped tables: outside the element gate, whole-array comparison only)
     p = copy.copy(ase_small)
     g = ase_small.gain[2]
     gv = g.gv.copy()
@@ -152,8 +165,10 @@ def test_exact_emission_mode_inside_the_one_launch(hip, oracle, ase_small):
             assert plan.last_fused()
     finally:
         os.environ.pop("RT_HIP_FUSED", None)
-    ref = oracle.image_loop(ase_small, ase_small.build_rays(np.arange(64 * 900 + 5, dtype=np.int64)))
+    rays = ase_small.build_rays(np.arange(64 * 900 + 5, dtype=np.int64))
+    ref = oracle.image_loop(ase_small, rays)
     assert rel_l2(out["image"], ref["image"]) < 1e-11 and rel_l2(out["I_ang"], ref["I_ang"]) < 1e-11
+    gate_outputs(out, ref, ase_small, contribution_counts(ase_small, rays), TIGHT_TIER, "one launch: exact emission, 57 605 rays, against the oracle")
 
 
 @pytest.mark.parametrize("seed", range(12))
@@ -170,11 +185,13 @@ def test_random_grids_through_the_one_launch_run(hip, oracle, ase_small, seed):
         pytest.skip("fewer than 32 rays per pixel")
     one, two = run_grid(hip, p, True), run_grid(hip, p, False)
     assert one["fused"] and not two["fused"]
-    same_images(one, two, tol=1e-12)
+    counts = contribution_counts(p)
+    same_images(one, two, p, counts, f"random grid {1000 + seed} ({nx} x {ny} x {na} x {nb}, K = {p.beam.nv})", tol=1e-12)
     if p.n_rays_total <= 400000:
         ref = oracle.image_loop(p, p.build_rays())
         assert one["stats"]["cell_steps"] == ref["counters"]["cell_steps"]
         assert rel_l2(one["image"], ref["image"]) < TIGHT and rel_l2(one["I_ang"], ref["I_ang"]) < TIGHT
+        gate_outputs(one, ref, p, counts, DEFAULT_TIER, f"one launch: random grid {1000 + seed} against the oracle")
 
 
 @pytest.mark.parametrize("split", ["2", "3"])
@@ -189,11 +206,14 @@ def test_tiles_split_over_four_waves_give_the_same_image(hip, oracle, ase_small,
         p = ase_small if nv == 52 else problem_mod.resample_frequency(ase_small, nv)
         one, two = run_grid(hip, p, True, count=64 * 700 + 9), run_grid(hip, p, False, count=64 * 700 + 9)
         assert one["fused"] and not two["fused"]
-        same_images(one, two, tol=1e-12)
-    ref = oracle.image_loop(ase_small, ase_small.build_rays(np.arange(64 * 700 + 9, dtype=np.int64)))
+        same_images(one, two, p, contribution_counts(p, p.build_rays(np.arange(64 * 700 + 9, dtype=np.int64))),
+                    f"tile split {split}, K = {nv}", tol=1e-12)
+    rays = ase_small.build_rays(np.arange(64 * 700 + 9, dtype=np.int64))
+    ref = oracle.image_loop(ase_small, rays)
     one = run_grid(hip, ase_small, True, count=64 * 700 + 9)
     assert rel_l2(one["image"], ref["image"]) < TIGHT and rel_l2(one["I_ang"], ref["I_ang"]) < TIGHT
-    # a failing run: NaNs in the lineshape of one length
+    gate_outputs(one, ref, ase_small, contribution_counts(ase_small, rays), DEFAULT_TIER, f"one launch: tile split {split} against the oracle")
+    # a failing run: NaNs in the lineshape of one length (outside the element gate, whole-array comparison only)
     p = copy.copy(ase_small)
     g = ase_small.gain[2]
     gv = g.gv.copy()
@@ -226,8 +246,10 @@ def test_invalid_rays_are_reported_once_however_a_tile_is_split(hip, oracle, ase
     assert ref["failure_code"] == 1 << 1 and one["failure_code"] == two["failure_code"] == ref["failure_code"]
     n_bad = len(ref["failed_rays"])
     assert n_bad == 4 and len(one["failed_rays"]) == n_bad and len(two["failed_rays"]) == n_bad
-    same_images(one, two, tol=1e-12)
+    counts = counts_from_oracle(oracle, p, rays)          # (the four invalid rays deposit nothing and are not counted)
+    same_images(one, two, p, counts, f"invalid rays, tile split {split}", tol=1e-12)
     assert rel_l2(one["image"], ref["image"]) < TIGHT
+    gate_outputs(one, ref, p, counts, DEFAULT_TIER, f"one launch: invalid rays, tile split {split}, against the oracle")
 
 
 @pytest.mark.parametrize("env", [
@@ -251,12 +273,13 @@ def test_consumer_waves_late_zone_and_list_storage_leave_the_image_alone(hip, or
     one, two = run_grid(hip, ase_small, True, count=n), run_grid(hip, ase_small, False, count=n)
     assert one["fused"] and not two["fused"]
     assert one["stats"]["n_rays"] == n
-    same_images(one, two, tol=1e-12)
+    same_images(one, two, ase_small, contribution_counts(ase_small, ase_small.build_rays(np.arange(n, dtype=np.int64))),
+                f"96 017 rays, {env}", tol=1e-12)
     whole = run_grid(hip, ase_small, True)
     assert whole["stats"]["cell_steps"] == 4768067 and whole["failure_code"] == 0
 
 
-def test_seeded_mode_as_one_launch(hip, seed_small, seed_ref, monkeypatch):
+def test_seeded_mode_as_one_launch(hip, oracle, seed_small, seed_ref, monkeypatch):
     """The gain-only instance of the one-launch kernel (RT_HIP_FUSED_SEED=1; two kernels are the rule for this mode,
     profiles/r05_seed_fused_ab.txt): row caches for the consumers beside the tables, for the others over them once the
     march is done.  seed_small.dat against the reference's CPU loop and against the two-kernel run."""
@@ -270,12 +293,16 @@ def test_seeded_mode_as_one_launch(hip, seed_small, seed_ref, monkeypatch):
         assert one["fused"]
         assert one["stats"]["n_rays"] == 7803000 and one["stats"]["cell_steps"] == 53573880
         assert rel_l2(one["image"], seed_ref["image"]) < 1e-12 and rel_l2(one["I_ang"], seed_ref["I_ang"]) < 1e-12
-        same_images(one, two, tol=1e-12)
+        counts = counts_from_oracle(oracle, seed_small)
+        gate_outputs(one, seed_ref, seed_small, counts, TIGHT_TIER, f"one launch: seed_small {extra} against seed_small_ref_cpu.npz")
+        same_images(one, two, seed_small, counts, f"seed_small {extra}", tol=1e-12)
         for k in extra:
             monkeypatch.delenv(k)
     part = run_grid(hip, seed_small, True, count=64 * 3000 + 5)
     monkeypatch.delenv("RT_HIP_FUSED_SEED")
-    same_images(part, run_grid(hip, seed_small, True, count=64 * 3000 + 5), tol=1e-12)
+    same_images(part, run_grid(hip, seed_small, True, count=64 * 3000 + 5), seed_small,
+                counts_from_oracle(oracle, seed_small, seed_small.build_rays(np.arange(64 * 3000 + 5, dtype=np.int64))),
+                "seed_small, 192 005 rays", tol=1e-12)
 
 
 @pytest.mark.parametrize("env", [{"RT_HIP_LATE2_X10": "0"}, {"RT_HIP_LATE2_X10": "400", "RT_HIP_LATE_WAVES": "1"},

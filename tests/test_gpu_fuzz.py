@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import rel_l2
+from element_gate import DEFAULT_TIER, TIGHT_TIER, contribution_counts, counts_from_oracle, gate_outputs
 
 rt = importlib.import_module("raytrace-miniapp_amd")
 problem_mod = importlib.import_module("raytrace-miniapp_amd.problem")
@@ -79,6 +80,8 @@ def test_random_problem_matches_oracle(hip, oracle, ase_small, seed_small, seed)
                 assert rel_l2(out[key], ref[key]) < (1e-10 if p.seed is not None else 2e-7)
             else:
                 assert not out[key].any()
+        gate_outputs(out, ref, p, counts_from_oracle(oracle, p, rays), TIGHT_TIER if p.seed is not None else DEFAULT_TIER,
+                     f"fuzz: random list {1000 + seed} (N = {p.N}, K = {p.beam.nv}, {len(rays)} rays, seeded {p.seed is not None})")
 
 
 @pytest.mark.parametrize("seed", range(6))
@@ -110,6 +113,9 @@ def test_random_wide_angle_grids_match_oracle(hip, oracle, ase_small, seed_small
     assert out["failure_code"] == ref["failure_code"]
     if ref["failure_code"] == 0 and np.linalg.norm(ref["image"]) > 0:
         assert rel_l2(out["image"], ref["image"]) < (1e-10 if p.seed is not None else 2e-7)
+    if ref["failure_code"] == 0:
+        gate_outputs(out, ref, q, counts_from_oracle(oracle, q, rays), TIGHT_TIER if p.seed is not None else DEFAULT_TIER,
+                     f"fuzz: random wide-angle grid {5000 + seed} (N = {q.N}, K = {q.beam.nv}, seeded {p.seed is not None})")
 
 
 def random_grid_case(rng, ase_small, seed_small):
@@ -168,6 +174,12 @@ def test_random_uniform_grids_match_oracle(hip, oracle, ase_small, seed_small, s
         out = plan.set_ray_grid().run().fetch()
     ok, err = check_grid_case(out, ref, p.seed is not None)
     assert ok, (n, err, out["failure_code"], ref["failure_code"])
+    counts, tier = counts_from_oracle(oracle, p, rays), TIGHT_TIER if p.seed is not None else DEFAULT_TIER
+    if ref["failure_code"] == 0:
+        gate_outputs(out, ref, p, counts, tier, f"fuzz: random grid {77000 + seed} {n} (N = {p.N}, K = {p.beam.nv}, seeded {p.seed is not None})")
     if seed % 4 == 0:   # and through the host-pointer entry, which recognises the list as a grid
-        ok, err = check_grid_case(hip.image_loop(p, rays), ref, p.seed is not None)
+        via = hip.image_loop(p, rays)
+        ok, err = check_grid_case(via, ref, p.seed is not None)
         assert ok, ("image_loop", n, err)
+        if ref["failure_code"] == 0:
+            gate_outputs(via, ref, p, counts, tier, f"fuzz: random grid {77000 + seed} through the host-pointer entry")

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import rel_l2
+from element_gate import DEFAULT_TIER, TIGHT_TIER, contribution_counts, counts_from_oracle, gate_outputs
 
 rt = importlib.import_module("raytrace-miniapp_amd")
 pytestmark = pytest.mark.gpu
@@ -23,6 +24,9 @@ def test_multi_loop_ase_tiles_equal_the_single_device_image(hip, oracle, ase_sma
     ref = oracle.image_loop(ase_small, n_threads=8)
     assert rel_l2(out["image"], ref["image"]) < 1e-6 and rel_l2(out["I_ang"], ref["I_ang"]) < 1e-6
     assert rel_l2(out["image"], one["image"]) < 1e-12 and rel_l2(out["I_ang"], one["I_ang"]) < 1e-12
+    counts = contribution_counts(ase_small)
+    gate_outputs(out, ref, ase_small, counts, DEFAULT_TIER, "multi: ASE_small tiles, one device, against the oracle")
+    gate_outputs(out, one, ase_small, counts, "reordering", "multi: ASE_small tiles, one device, against image_loop")
 
 
 def test_multi_loop_seeded_takes_the_sum_reduce_path(hip, oracle, seed_small):
@@ -32,6 +36,7 @@ def test_multi_loop_seeded_takes_the_sum_reduce_path(hip, oracle, seed_small):
     ref = oracle.image_loop(p, n_threads=8)
     assert out["stats"]["cell_steps"] == ref["counters"]["cell_steps"]
     assert rel_l2(out["image"], ref["image"]) < 1e-9 and rel_l2(out["I_ang"], ref["I_ang"]) < 1e-9
+    gate_outputs(out, ref, p, counts_from_oracle(oracle, p), TIGHT_TIER, "multi: seeded sum-reduce path, one device, against the oracle")
 
 
 def test_multi_loop_arbitrary_list_falls_back_to_chunks(hip, oracle, ase_small):
@@ -41,6 +46,7 @@ def test_multi_loop_arbitrary_list_falls_back_to_chunks(hip, oracle, ase_small):
     ref = oracle.image_loop(ase_small, rays, n_threads=8)
     assert out["stats"]["cell_steps"] == ref["counters"]["cell_steps"]
     assert rel_l2(out["image"], ref["image"]) < 1e-6 and rel_l2(out["I_ang"], ref["I_ang"]) < 1e-6
+    gate_outputs(out, ref, ase_small, contribution_counts(ase_small, rays), DEFAULT_TIER, "multi: arbitrary list as chunks, one device, against the oracle")
 
 
 def test_image_loop_recognises_the_grid_and_survives_a_list_that_only_looks_like_one(hip, oracle, ase_small, monkeypatch):
@@ -52,6 +58,8 @@ def test_image_loop_recognises_the_grid_and_survives_a_list_that_only_looks_like
     monkeypatch.delenv("RT_HIP_NO_GRID_DETECT")
     assert a["stats"]["cell_steps"] == b["stats"]["cell_steps"]
     assert rel_l2(a["image"], b["image"]) < 1e-12 and rel_l2(a["I_ang"], b["I_ang"]) < 1e-12
+    counts = contribution_counts(ase_small)
+    gate_outputs(a, b, ase_small, counts, "reordering", "multi: list recognised as a grid against the uploaded list")
     # one ray moved: the periods still say "grid", the ray-by-ray check says no, the list itself is traced
     odd = rays.copy()
     odd["x"][123457] = odd["x"][0]
@@ -60,6 +68,8 @@ def test_image_loop_recognises_the_grid_and_survives_a_list_that_only_looks_like
     ref = oracle.image_loop(ase_small, odd, n_threads=8)
     assert c["stats"]["cell_steps"] == ref["counters"]["cell_steps"]
     assert rel_l2(c["image"], ref["image"]) < 1e-6 and rel_l2(c["I_ang"], ref["I_ang"]) < 1e-6
+    odd_counts = contribution_counts(ase_small, odd)
+    gate_outputs(c, ref, ase_small, odd_counts, DEFAULT_TIER, "multi: look-alike list through image_loop against the oracle")
     assert rel_l2(c["image"], a["image"]) > 0
     # the all-devices entry speculates likewise (devices start tracing the guessed grid while the list is verified, the
     # verdict arrives before the collective): the look-alike list ends the first attempt and is traced as ray chunks,
@@ -70,8 +80,10 @@ def test_image_loop_recognises_the_grid_and_survives_a_list_that_only_looks_like
         d = hip.multi_image_loop(ase_small, odd)
         assert d["mode"] == 2 and d["stats"]["cell_steps"] == ref["counters"]["cell_steps"]
         assert rel_l2(d["image"], ref["image"]) < 1e-6 and rel_l2(d["I_ang"], ref["I_ang"]) < 1e-6
+        gate_outputs(d, ref, ase_small, odd_counts, DEFAULT_TIER, f"multi: look-alike list, loop-back '{loop}', against the oracle")
         e = hip.multi_image_loop(ase_small, rays)
         assert e["mode"] == 1 and rel_l2(e["image"], a["image"]) < 1e-12
+        gate_outputs(e, a, ase_small, counts, "reordering", f"multi: grid list, loop-back '{loop}', against image_loop")
     monkeypatch.delenv("RT_HIP_MULTI_LOOPBACK")
 
 
@@ -93,9 +105,11 @@ def test_pool_trim_and_concurrent_image_loops(hip, ase_small):
     for g in got:
         assert g["stats"]["cell_steps"] == want["stats"]["cell_steps"]
         assert rel_l2(g["image"], want["image"]) < 1e-12
+        gate_outputs(g, want, ase_small, contribution_counts(ase_small), "reordering", "multi: two concurrent image_loop calls against one")
     hip.HipLibrary.get().lib.rt_hip_pool_trim()
     again = hip.image_loop(ase_small)
     assert rel_l2(again["image"], want["image"]) < 1e-12
+    gate_outputs(again, want, ase_small, contribution_counts(ase_small), "reordering", "multi: image_loop after the pool trim")
 
 
 def test_timing_ring_keeps_the_last_runs(hip, ase_small):
@@ -161,6 +175,9 @@ def test_multi_loop_partition_and_assembly_for_several_devices(hip, oracle, ase_
     ref = oracle.image_loop(p, n_threads=8)
     assert rel_l2(out["image"], ref["image"]) < 1e-6 and rel_l2(out["I_ang"], ref["I_ang"]) < 1e-6
     assert rel_l2(out["image"], one["image"]) < 1e-12 and rel_l2(out["I_ang"], one["I_ang"]) < 1e-12
+    counts = contribution_counts(p)
+    gate_outputs(out, ref, p, counts, DEFAULT_TIER, f"multi: {ndev} devices (loop-back), ASE tiles, against the oracle")
+    gate_outputs(out, one, p, counts, "reordering", f"multi: {ndev} devices (loop-back), ASE tiles, against one device")
     # seeded: ray chunks of the seed-beam grid, full images summed
     q = rt.scale_problem(seed_small, 0.02)
     one = hip.image_loop(q)
@@ -168,12 +185,14 @@ def test_multi_loop_partition_and_assembly_for_several_devices(hip, oracle, ase_
     assert out["mode"] == 2
     assert out["stats"]["n_rays"] == q.n_rays_total and out["stats"]["cell_steps"] == one["stats"]["cell_steps"]
     assert rel_l2(out["image"], one["image"]) < 1e-12 and rel_l2(out["I_ang"], one["I_ang"]) < 1e-12
+    gate_outputs(out, one, q, counts_from_oracle(oracle, q), "reordering", f"multi: {ndev} devices (loop-back), seeded chunks, against one device")
     # an arbitrary list: chunks of the list itself
     rays = ase_small.build_rays()[7:-3:5].copy()
     ref = oracle.image_loop(ase_small, rays, n_threads=8)
     out = hip.multi_image_loop(ase_small, rays)
     assert out["mode"] == 2 and out["stats"]["cell_steps"] == ref["counters"]["cell_steps"]
     assert rel_l2(out["image"], ref["image"]) < 1e-6 and rel_l2(out["I_ang"], ref["I_ang"]) < 1e-6
+    gate_outputs(out, ref, ase_small, contribution_counts(ase_small, rays), DEFAULT_TIER, f"multi: {ndev} devices (loop-back), list chunks, against the oracle")
 
 
 _CHILD = r"""

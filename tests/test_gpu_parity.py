@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import rel_l2
+from element_gate import DEFAULT_TIER, TIGHT_TIER, contribution_counts, counts_from_oracle, gate_outputs
 
 rt = importlib.import_module("raytrace-miniapp_amd")
 pytestmark = pytest.mark.gpu
@@ -38,6 +39,7 @@ def test_ase_small_image_vs_reference(hip, ase_small, ase_ref):
     assert out["stats"]["cell_steps"] == 4768067          # SURVEY.md 3.3, measured on the reference
     assert rel_l2(out["image"], ase_ref["image"]) < TOL_TIGHT
     assert rel_l2(out["I_ang"], ase_ref["I_ang"]) < TOL_TIGHT
+    gate_outputs(out, ase_ref, ase_small, contribution_counts(ase_small), DEFAULT_TIER, "parity: ASE_small against ASE_small_ref_cpu.npz")
     # the reference harness' own gate against the golden image embedded in the file
     assert rel_l2(out["image"], ase_small.golden_image) < 5.2e-7
 
@@ -57,7 +59,7 @@ def test_ase_small_march_record_bit_exact(hip, oracle, ase_small):
     assert out["failure_code"] == 0
 
 
-def test_seed_small_image_vs_reference(hip, seed_small, seed_ref):
+def test_seed_small_image_vs_reference(hip, oracle, seed_small, seed_ref):
     with hip.Plan(seed_small) as plan:
         out = plan.set_ray_grid().run().fetch()
     assert out["failure_code"] == 0
@@ -65,6 +67,7 @@ def test_seed_small_image_vs_reference(hip, seed_small, seed_ref):
     assert out["stats"]["cell_steps"] == 53573880
     assert rel_l2(out["image"], seed_ref["image"]) < TOL
     assert rel_l2(out["I_ang"], seed_ref["I_ang"]) < TOL
+    gate_outputs(out, seed_ref, seed_small, counts_from_oracle(oracle, seed_small), TIGHT_TIER, "parity: seed_small against seed_small_ref_cpu.npz")
     assert rel_l2(out["image"], seed_small.golden_image) < 5.2e-7
 
 
@@ -103,4 +106,8 @@ def test_exact_emission_mode_matches_the_cpu_loop_to_rounding(hip, oracle, ase_s
     assert rel_l2(fast["image"], ase_ref["image"]) < TOL_TIGHT
     assert 1e-12 < rel_l2(fast["image"], exact["image"]) < TOL_TIGHT      # the two modes do differ, by a float rounding
     assert rel_l2(again["image"], fast["image"]) < 1e-13
+    counts = contribution_counts(ase_small)
+    gate_outputs(exact, ase_ref, ase_small, counts, TIGHT_TIER, "parity: ASE_small, exact emission, against ASE_small_ref_cpu.npz")
+    gate_outputs(fast, ase_ref, ase_small, counts, DEFAULT_TIER, "parity: ASE_small, default emission before the exact run")
+    gate_outputs(again, fast, ase_small, counts, "reordering", "parity: default emission after the exact run against before it")
     assert exact["stats"]["cell_steps"] == fast["stats"]["cell_steps"]

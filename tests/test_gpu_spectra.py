@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, rel_l2
+from element_gate import assert_elements, contribution_counts, gate_outputs, reordering_tol
 
 rt = importlib.import_module("raytrace-miniapp_amd")
 problem_mod = importlib.import_module("raytrace-miniapp_amd.problem")
@@ -131,6 +132,8 @@ def test_spectra_sum_to_the_image_full_size_on_the_device(hip, ase_small):
     note(f"stand-in 6 384 000 rays, sums of the spectra against image mode: image rel-L2 {e_img:.3e}, I_ang rel-L2 {e_ang:.3e}")
     assert np.linalg.norm(img["image"]) > 0 and np.linalg.norm(img["I_ang"]) > 0
     assert e_img < GATE and e_ang < GATE
+    # element by element: the same rows summed in another order
+    gate_outputs(dict(image=image, I_ang=iang), img, p, contribution_counts(p), "reordering", "spectra: stand-in 6 384 000 rays, sums of the spectra against image mode")
 
 
 def test_spectra_sum_to_the_image_ase_small_host_arrays(hip, ase_small):
@@ -149,6 +152,7 @@ def test_spectra_sum_to_the_image_ase_small_host_arrays(hip, ase_small):
     e_img, e_ang = rel_l2(image, img["image"]), rel_l2(iang, img["I_ang"])
     note(f"ASE_small, sums of the spectra against image mode: image rel-L2 {e_img:.3e}, I_ang rel-L2 {e_ang:.3e}")
     assert e_img < GATE and e_ang < GATE
+    gate_outputs(dict(image=image, I_ang=iang), img, p, contribution_counts(p), "reordering", "spectra: ASE_small, sums of the spectra against image mode")
 
 
 def test_spectra_sum_to_the_image_seeded(hip, seed_small):
@@ -166,6 +170,8 @@ def test_spectra_sum_to_the_image_seeded(hip, seed_small):
     e = rel_l2(lhs, rhs)
     note(f"seed_small, every 19th ray, sum over rays of Iv scale against sum over pixels of the image: rel-L2 {e:.3e}")
     assert np.linalg.norm(rhs) > 0 and e < GATE
+    # per frequency: both sides are sums of the same len(rays) non-negative terms, in other orders
+    assert_elements(lhs, rhs, np.full(K, len(rays)), reordering_tol(np.full(K, len(rays)), K), "spectra: seed_small, every 19th ray, sum over rays against sum over pixels, per frequency")
 
 
 # ---------------------------------------------------------------- 3. return codes
