@@ -1,0 +1,326 @@
+// rt_devmath.hip -- test-only unit: the float64 building blocks of the frequency pass (rt_freq.hip) and the two float
+// kernels of the march (rt_march.hip), each behind one elementwise kernel, so that tests/test_gpu_devmath.py can run
+// them on a device on inputs of its own choosing.  Builds to librt_hip_devmath.so with the product's flags; nothing
+// of it is linked into librt_hip.so.
+//
+// The C face takes host arrays and gives host arrays: every call allocates, copies, launches, synchronises and
+// frees, and returns 0 or the hipError_t of the first HIP call that failed, the frees included (rt_devmath_error names it).  Kernels: 256
+// threads per work-group, a grid-stride loop, the two exponent tables filled in LDS by RT_FILL_EXP_TABLES -- the
+// fill the product's kernels run -- and __syncthreads() before the first use.
+#include "rt_freq.hip" // (includes rt_march.hip), as rt_launch.hip has it
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+
+namespace {
+
+using namespace rt;
+
+constexpr int DM_BLOCK = 256;
+
+enum : int { DM_EXP_TAB = 0, DM_EXP_TAB_VEC = 1 };
+enum : int { DM_STEP_F64 = 0, DM_STEP_F32 = 1 };
+enum : int { DM_DEPOSIT_FAST = 0, DM_DEPOSIT_4 = 1 };
+enum : int { DM_TAN = 0, DM_ATAN = 1 };
+
+// out[0..512): the tables as the first work-group sees them; out[512..1024): as the last one does
+__global__ void __launch_bounds__(DM_BLOCK) dm_tables_kernel(double *out)
+{
+    __shared__ double exp2_tab[2 * EXP_TAB];
+    RT_FILL_EXP_TABLES(exp2_tab)
+    __syncthreads();
+    // each thread copies entries that other threads wrote (thread t wrote entries t and 256 + t)
+    for (int c = (int) threadIdx.x; c < 2 * EXP_TAB; c += (int) blockDim.x) {
+        const int e = (c + 37) % (2 * EXP_TAB);
+        if (blockIdx.x == 0)
+            out[e] = exp2_tab[e];
+        if (blockIdx.x == gridDim.x - 1) // (a launch of one work-group: it is both)
+            out[2 * EXP_TAB + e] = exp2_tab[e];
+    }
+}
+
+// exp_tab: one argument per thread and pass.  exp_tab_vec: VEC consecutive arguments per thread, the lock-step form;
+// a ragged last group is padded with zeros and only its valid results are stored.
+__global__ void __launch_bounds__(DM_BLOCK) dm_exp_kernel(int which, const double *x, double *out, size_t n)
+{
+    __shared__ double exp2_tab[2 * EXP_TAB];
+    RT_FILL_EXP_TABLES(exp2_tab)
+    __syncthreads();
+    const size_t stride = (size_t) gridDim.x * blockDim.x;
+    const size_t first  = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (which == DM_EXP_TAB) {
+        for (size_t i = first; i < n; i += stride)
+            out[i] = exp_tab(x[i], exp2_tab);
+    } else {
+        const size_t groups = (n + VEC - 1) / VEC;
+        for (size_t g = first; g < groups; g += stride) {
+            double xv[VEC], ev[VEC];
+#pragma unroll
+            for (int j = 0; j < VEC; j++)
+                xv[j] = g * VEC + j < n ? x[g * VEC + j] : 0.0;
+            exp_tab_vec(xv, exp2_tab, ev);
+#pragma unroll
+            for (int j = 0; j < VEC; j++)
+                if (g * VEC + j < n)
+                    out[g * VEC + j] = ev[j];
+        }
+    }
+}
+
+__global__ void __launch_bounds__(DM_BLOCK) dm_update_kernel(const double *Iv, const float *gs, const float *es, const float *w,
+                                                            double *out, size_t n)
+{
+    __shared__ double exp2_tab[2 * EXP_TAB];
+    RT_FILL_EXP_TABLES(exp2_tab)
+    __syncthreads();
+    const size_t stride = (size_t) gridDim.x * blockDim.x;
+    for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        out[i] = ase_update(Iv[i], gs[i], es[i], w[i], exp2_tab);
+}
+
+// ase_step / ase_step_f32: group g holds one (gs, rs) and VEC (Iv, w) pairs, as a lane of the frequency loop does
+__global__ void __launch_bounds__(DM_BLOCK) dm_step_kernel(int which, const double *Iv, const float *gs, const double *rs,
+                                                          const float *w, double *out, size_t groups)
+{
+    __shared__ double exp2_tab[2 * EXP_TAB];
+    RT_FILL_EXP_TABLES(exp2_tab)
+    __syncthreads();
+    const size_t stride = (size_t) gridDim.x * blockDim.x;
+    for (size_t g = (size_t) blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += stride) {
+        double iv[VEC];
+        float wv[VEC];
+#pragma unroll
+        for (int j = 0; j < VEC; j++) {
+            iv[j] = Iv[g * VEC + j];
+            wv[j] = w[g * VEC + j];
+        }
+        if (which == DM_STEP_F64)
+            ase_step(iv, gs[g], rs[g], wv, exp2_tab);
+        else
+            ase_step_f32(iv, gs[g], rs[g], wv, exp2_tab + EXP_TAB);
+#pragma unroll
+        for (int j = 0; j < VEC; j++)
+            out[g * VEC + j] = iv[j];
+    }
+}
+
+__global__ void __launch_bounds__(DM_BLOCK) dm_div_kernel(const double *a, const double *b, double *q, size_t n)
+{
+    const size_t stride = (size_t) gridDim.x * blockDim.x;
+    for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        q[i] = div_fast(a[i], b[i]);
+}
+
+// the four deposit cells of ray i: v[4 i + a] on axis a
+struct DmAxes {
+    int n[4];
+    const double *g[4];
+    double d[4], inv_d[4], g0[4], gl[4];
+};
+__global__ void __launch_bounds__(DM_BLOCK) dm_deposit_kernel(int which, const DmAxes X, const double *v, int *idx, size_t n)
+{
+    const size_t stride = (size_t) gridDim.x * blockDim.x;
+    for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        int ix[4];
+        if (which == DM_DEPOSIT_4) {
+            const AxisIn A[4] = { { X.n[0], X.g[0], X.d[0], X.inv_d[0], X.g0[0], X.gl[0], v[4 * i + 0] },
+                                  { X.n[1], X.g[1], X.d[1], X.inv_d[1], X.g0[1], X.gl[1], v[4 * i + 1] },
+                                  { X.n[2], X.g[2], X.d[2], X.inv_d[2], X.g0[2], X.gl[2], v[4 * i + 2] },
+                                  { X.n[3], X.g[3], X.d[3], X.inv_d[3], X.g0[3], X.gl[3], v[4 * i + 3] } };
+            deposit_index4(A, ix);
+        } else {
+#pragma unroll
+            for (int a = 0; a < 4; a++)
+                ix[a] = deposit_index_fast(X.n[a], X.g[a], X.d[a], X.inv_d[a], v[4 * i + a]);
+        }
+#pragma unroll
+        for (int a = 0; a < 4; a++)
+            idx[4 * i + a] = ix[a];
+    }
+}
+
+__global__ void __launch_bounds__(DM_BLOCK) dm_tan_kernel(int which, const float *x, float *out, size_t n)
+{
+    const size_t stride = (size_t) gridDim.x * blockDim.x;
+    for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        out[i] = which == DM_TAN ? tanf_flt32_kernel(x[i]) : atanf_flt32_kernel(x[i]);
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------
+// device buffers of one call: freed when the call returns, whatever it returns
+struct Bufs {
+    void *p[8];
+    int n = 0;
+    ~Bufs() { (void) release(); } // (only on the early returns, where the call already reports an earlier error)
+    // frees every buffer; the first error of the frees, or st if the call had failed before
+    int release(int st)
+    {
+        const int fr = release();
+        return st ? st : fr;
+    }
+    int release()
+    {
+        int first = 0;
+        for (int i = 0; i < n; i++) {
+            const hipError_t e = hipFree(p[i]);
+            if (e != hipSuccess && !first)
+                first = (int) e;
+        }
+        n = 0;
+        return first;
+    }
+    hipError_t in(void **d, const void *h, size_t bytes)
+    {
+        hipError_t e = out(d, bytes);
+        if (e == hipSuccess && bytes)
+            e = hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice);
+        return e;
+    }
+    hipError_t out(void **d, size_t bytes)
+    {
+        *d = nullptr;
+        if (n >= 8)
+            return hipErrorOutOfMemory;
+        hipError_t e = hipMalloc(d, bytes ? bytes : 1);
+        if (e == hipSuccess)
+            p[n++] = *d;
+        return e;
+    }
+};
+
+#define DM_TRY(expr)                  \
+    do {                              \
+        const hipError_t e_ = (expr); \
+        if (e_ != hipSuccess)         \
+            return (int) e_;          \
+    } while (0)
+
+unsigned grid_for(size_t items)
+{
+    const size_t blocks = (items + DM_BLOCK - 1) / DM_BLOCK;
+    return (unsigned) (blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks)); // beyond that the grid-stride loop takes over
+}
+
+int finish(void *host, const void *dev, size_t bytes)
+{
+    DM_TRY(hipGetLastError());
+    DM_TRY(hipDeviceSynchronize());
+    if (bytes)
+        DM_TRY(hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+} // namespace
+
+#define DM_API extern "C" __attribute__((visibility("default")))
+
+DM_API const char *rt_devmath_error(int status) { return hipGetErrorString((hipError_t) status); }
+
+DM_API int rt_devmath_vec(void) { return rt::VEC; }
+
+// out[1024]: [first work-group: tab[0..256), tab2[0..256)][last work-group: the same], n_blocks >= 1 work-groups launched
+DM_API int rt_devmath_tables(double *out, unsigned n_blocks)
+{
+    Bufs B;
+    double *d;
+    if (n_blocks < 1)
+        n_blocks = 1;
+    DM_TRY(B.out((void **) &d, 4 * EXP_TAB * sizeof(double)));
+    DM_TRY(hipMemset(d, 0xff, 4 * EXP_TAB * sizeof(double)));
+    dm_tables_kernel<<<n_blocks, DM_BLOCK>>>(d);
+    return B.release(finish(out, d, 4 * EXP_TAB * sizeof(double)));
+}
+
+DM_API int rt_devmath_exp(int which, const double *x, double *out, size_t n)
+{
+    Bufs B;
+    double *dx, *dout;
+    if (which != DM_EXP_TAB && which != DM_EXP_TAB_VEC)
+        return (int) hipErrorInvalidValue;
+    DM_TRY(B.in((void **) &dx, x, n * sizeof(double)));
+    DM_TRY(B.out((void **) &dout, n * sizeof(double)));
+    dm_exp_kernel<<<grid_for(which == DM_EXP_TAB ? n : (n + VEC - 1) / VEC), DM_BLOCK>>>(which, dx, dout, n);
+    return B.release(finish(out, dout, n * sizeof(double)));
+}
+
+DM_API int rt_devmath_update(const double *Iv, const float *gs, const float *es, const float *w, double *out, size_t n)
+{
+    Bufs B;
+    double *dIv, *dout;
+    float *dgs, *des, *dw;
+    DM_TRY(B.in((void **) &dIv, Iv, n * sizeof(double)));
+    DM_TRY(B.in((void **) &dgs, gs, n * sizeof(float)));
+    DM_TRY(B.in((void **) &des, es, n * sizeof(float)));
+    DM_TRY(B.in((void **) &dw, w, n * sizeof(float)));
+    DM_TRY(B.out((void **) &dout, n * sizeof(double)));
+    dm_update_kernel<<<grid_for(n), DM_BLOCK>>>(dIv, dgs, des, dw, dout, n);
+    return B.release(finish(out, dout, n * sizeof(double)));
+}
+
+// Iv, w, out: [groups][VEC]; gs, rs: [groups]
+DM_API int rt_devmath_step(int which, const double *Iv, const float *gs, const double *rs, const float *w, double *out, size_t groups)
+{
+    Bufs B;
+    double *dIv, *drs, *dout;
+    float *dgs, *dw;
+    if (which != DM_STEP_F64 && which != DM_STEP_F32)
+        return (int) hipErrorInvalidValue;
+    DM_TRY(B.in((void **) &dIv, Iv, groups * VEC * sizeof(double)));
+    DM_TRY(B.in((void **) &dgs, gs, groups * sizeof(float)));
+    DM_TRY(B.in((void **) &drs, rs, groups * sizeof(double)));
+    DM_TRY(B.in((void **) &dw, w, groups * VEC * sizeof(float)));
+    DM_TRY(B.out((void **) &dout, groups * VEC * sizeof(double)));
+    dm_step_kernel<<<grid_for(groups), DM_BLOCK>>>(which, dIv, dgs, drs, dw, dout, groups);
+    return B.release(finish(out, dout, groups * VEC * sizeof(double)));
+}
+
+DM_API int rt_devmath_div(const double *a, const double *b, double *q, size_t n)
+{
+    Bufs B;
+    double *da, *db, *dq;
+    DM_TRY(B.in((void **) &da, a, n * sizeof(double)));
+    DM_TRY(B.in((void **) &db, b, n * sizeof(double)));
+    DM_TRY(B.out((void **) &dq, n * sizeof(double)));
+    dm_div_kernel<<<grid_for(n), DM_BLOCK>>>(da, db, dq, n);
+    return B.release(finish(q, dq, n * sizeof(double)));
+}
+
+// four axes: grid g[a] of n_grid[a] >= 1 points with spacing d[a]; v, idx: [n][4]
+DM_API int rt_devmath_deposit(int which, const int *n_grid, const double *const *g, const double *d, const double *v, int *idx, size_t n)
+{
+    Bufs B;
+    DmAxes X;
+    double *dv;
+    int *didx;
+    if (which != DM_DEPOSIT_FAST && which != DM_DEPOSIT_4)
+        return (int) hipErrorInvalidValue;
+    for (int a = 0; a < 4; a++) {
+        if (n_grid[a] < 1)
+            return (int) hipErrorInvalidValue;
+        double *dg;
+        DM_TRY(B.in((void **) &dg, g[a], (size_t) n_grid[a] * sizeof(double)));
+        X.n[a]     = n_grid[a];
+        X.g[a]     = dg;
+        X.d[a]     = d[a];
+        X.inv_d[a] = 1.0 / d[a]; // as rt_hip_plan_create has it
+        X.g0[a]    = g[a][0];
+        X.gl[a]    = g[a][n_grid[a] - 1];
+    }
+    DM_TRY(B.in((void **) &dv, v, n * 4 * sizeof(double)));
+    DM_TRY(B.out((void **) &didx, n * 4 * sizeof(int)));
+    dm_deposit_kernel<<<grid_for(n), DM_BLOCK>>>(which, X, dv, didx, n);
+    return B.release(finish(idx, didx, n * 4 * sizeof(int)));
+}
+
+DM_API int rt_devmath_tan(int which, const float *x, float *out, size_t n)
+{
+    Bufs B;
+    float *dx, *dout;
+    if (which != DM_TAN && which != DM_ATAN)
+        return (int) hipErrorInvalidValue;
+    DM_TRY(B.in((void **) &dx, x, n * sizeof(float)));
+    DM_TRY(B.out((void **) &dout, n * sizeof(float)));
+    dm_tan_kernel<<<grid_for(n), DM_BLOCK>>>(which, dx, dout, n);
+    return B.release(finish(out, dout, n * sizeof(float)));
+}

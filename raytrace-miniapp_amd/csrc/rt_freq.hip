@@ -49,12 +49,35 @@ struct alignas(16) FVec { float v[VEC]; };
 // different summation order of the deposit, the source-function form of the update
 // below).  Inside that contract exp and division are 1-2 ulp table / Newton kernels and
 // FMA contraction is allowed.
+// The bounds stated below are measured, on the host and on a device: tests/test_devmath_host.py runs a C restatement
+// of exp_tab, exp_tab_vec, ase_step and ase_step_f32 (tests/devmath_ref.c) with correctly rounded tables against exp /
+// expm1 in long double -- exp_tab 1.96 ulp, exp_tab_vec 2.28 ulp, e^x - 1 of ase_step to 1.4e-13 e^x (1.04e-10 of
+// e^x - 1 for tiny x), of ase_step_f32 to 1.9e-10 e^x (1.1e-7 for tiny x) --; tests/test_gpu_devmath.py runs the
+// functions themselves on a device through rt_devmath.hip, requires them to equal that restatement bit for bit when
+// it is fed the device's tables, and applies the same bounds plus the 1 ulp of a table entry, and 2 ulp to div_fast.
+// The device's figures: profiles/devmath_parity.txt.
 #pragma clang fp contract(fast)
+
+constexpr int EXP_TAB = 256;
+// The two exponent tables of a work-group, [2][EXP_TAB] doubles of LDS: tab[j] = 2^(j/256) as the device library's exp2
+// gives it (within 1 ulp of the correctly rounded value, not always equal to it), and tab[EXP_TAB + j] = the same
+// double with j << 12 taken from its high word (ase_step_f32).  Every thread of the work-group runs it; the caller
+// puts __syncthreads() between this and the first use.  The one fill of the product: rt_freq_kernel, rt_fused_kernel,
+// rt_spec_kernel and the device-side unit tests (rt_devmath.hip) all expand this.
+// (A macro, not a function: as a __forceinline__ function the same loop came out of the compiler with the two
+// induction variables in the other order, and the register allocation of all 22 instances of the three kernels
+// moved with it -- same register counts, other instruction text.  Expanded in place the device assembly is
+// identical to that of the three copies this replaces, line for line: `make asm` before and after.)
+#define RT_FILL_EXP_TABLES(exp2_tab)                                                                        \
+    for (int c = (int) threadIdx.x; c < EXP_TAB; c += (int) blockDim.x) {                                   \
+        const double e        = exp2((double) c * (1.0 / EXP_TAB));                                         \
+        exp2_tab[c]           = e;                                                                          \
+        exp2_tab[EXP_TAB + c] = __hiloint2double(__double2hiint(e) - (c << 12), __double2loint(e));         \
+    }
 
 // exp(x), <= 2 ulp: x = (256 m + j) ln2/256 + r, |r| <= ln2/512;
 // exp(x) = 2^m * 2^(j/256) * (1 + r + ... + r^5/120)  (remainder r^6/720 < 1e-20).
 // tab[j] = 2^(j/256) lives in LDS.  Overflow -> inf, underflow -> 0, NaN -> NaN.
-constexpr int EXP_TAB = 256;
 __device__ __forceinline__ double exp_tab(double x, const double *tab)
 {
     const double L2E   = 369.3299304675746;        // 256 / ln 2
@@ -75,6 +98,9 @@ __device__ __forceinline__ double exp_tab(double x, const double *tab)
 
 // The same kernel for VEC arguments at once: the four chains advance in lock step (the table
 // reads are issued together), rint comes from the magic-constant add.  e^x of a NaN is NaN.
+// <= 2.3 ulp, not 2: the polynomial stops at r^4/24, and the r^5/120 it leaves out is up to 0.17 ulp (measured with
+// correctly rounded tables: 2.28 ulp at x = 542.7166426675452, 2.27 at -502.54930561685239; a table entry of the
+// device adds up to 1 ulp).  The seeded kernel's 1e-11 gate does not need the term, and it costs instructions there.
 __device__ __forceinline__ void exp_tab_vec(const double (&x)[VEC], const double *tab, double (&e)[VEC])
 {
     const double L2E   = 369.3299304675746;
@@ -145,7 +171,8 @@ __device__ __forceinline__ double ase_update(double Iv, float gs, float es, floa
 //     S = 2^m 2^(j/256),  e^r - 1 = r Q(r),  e^gl - 1 = (S - 1) + S r Q(r),
 // so one branch-free sequence covers |gl| < 1e-3 (where the CPU switches to a cubic whose
 // own truncation, gl^3/24, is 4e-11) as well as large gains.  |r| <= ln2/512, so the
-// quadratic Q = 1 + r/2 + r^2/6 is e^r - 1 to 1e-10 -- two orders below the rounding of rs.
+// quadratic Q = 1 + r/2 + r^2/6 is e^r - 1 to r^3/24 <= 1.04e-10 of itself (measured: 1.0354e-10 at r = ln2/512; of
+// e^gl that is 1.4e-13) -- two orders below the rounding of rs.
 // The caller keeps |gs * w| <= 708 (DevParams::gs_cap): e^gl stays a normal double, S is
 // assembled by an integer add into the exponent field, and the reduction needs one constant
 // (|256 m + j| < 2^18, so the rounding of ln2/256 moves r by < 6e-14).  A NaN lineshape value
@@ -194,8 +221,9 @@ __device__ __forceinline__ void ase_step(double (&Iv)[VEC], const float gs, cons
 // the product is rounded to float before it is widened), so nothing is lost by reducing it in float:
 //     n = rint(x 256/ln2) by the magic-constant add (|n| < 2^22), r = x - n ln2/256 with the constant split in two
 //     floats (two fma, |error| < 3e-10), rq = r (1 + r/2 + r^2/6) in float (relative 1e-7 of a term below 1.4e-3);
-// S = 2^m 2^(j/256) and everything that carries magnitude stay float64: e^x - 1 = (S - 1) + S rq to 3e-10 of S,
-// against 1e-10 for the all-float64 form and 1.2e-7 for the rounding of rs that both share.  Five float64-rate
+// S = 2^m 2^(j/256) and everything that carries magnitude stay float64: e^x - 1 = (S - 1) + S rq to 3e-10 of S
+// (measured 1.9e-10; 2^-23 of e^x - 1 for tiny x), against 1e-10 for the all-float64 form (measured 1.4e-13) and
+// 1.2e-7 for the rounding of rs that both share.  Five float64-rate
 // instructions per update instead of eleven (the kernel is bound by VALU issue, and a float64 instruction
 // costs two to three float32 ones).
 __device__ __forceinline__ void ase_step_f32(double (&Iv)[VEC], const float gs, const double rs, const float (&w)[VEC],
@@ -1001,11 +1029,7 @@ __global__ void __launch_bounds__(FREQ_WG_WAVES * 64, EMIS ? RT_FREQ_WAVES : RT_
     double *cache          = excl ? mine : mine + FREQ_WAVE_XPOSE;
     for (size_t c = threadIdx.x; c < (size_t) (blockDim.x >> 6) * per_wave; c += blockDim.x)
         waves_base[c] = 0.0;
-    for (int c = (int) threadIdx.x; c < EXP_TAB; c += (int) blockDim.x) {
-        const double e        = exp2((double) c * (1.0 / EXP_TAB));
-        exp2_tab[c]           = e;
-        exp2_tab[EXP_TAB + c] = __hiloint2double(__double2hiint(e) - (c << 12), __double2loint(e));
-    }
+    RT_FILL_EXP_TABLES(exp2_tab)
     if (lds_iang) {
         for (int c = (int) threadIdx.x; c < n_ang; c += (int) blockDim.x)
             lds_iang[c] = 0.0;

@@ -89,11 +89,7 @@ __global__ void __launch_bounds__(1024) rt_fused_kernel(const FusedKArg A)
     // barrier that also publishes these)
     for (unsigned c = threadIdx.x; c < A.lay.n_free * A.lay.per_wave; c += blockDim.x)
         buf_free[c] = 0.0;
-    for (int c = (int) threadIdx.x; c < EXP_TAB; c += (int) blockDim.x) {
-        const double e        = exp2((double) c * (1.0 / EXP_TAB));
-        exp2_tab[c]           = e;
-        exp2_tab[EXP_TAB + c] = __hiloint2double(__double2hiint(e) - (c << 12), __double2loint(e));
-    }
+    RT_FILL_EXP_TABLES(exp2_tab)
     for (int c = (int) threadIdx.x; c < n_ang; c += (int) blockDim.x)
         lds_iang[c] = 0.0;
     // (the tile counters of every wave start at zero = free, rt_march.hip)

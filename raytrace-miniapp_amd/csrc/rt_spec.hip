@@ -341,11 +341,7 @@ __global__ void __launch_bounds__(FREQ_WG_WAVES * 64, EMIS ? RT_FREQ_WAVES : RT_
     const FreqHot &H = A.hot;
     double *exp2_tab = reinterpret_cast<double *>(spec_lds);
     double *stage    = exp2_tab + 2 * EXP_TAB + (size_t) (unsigned) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6)) * (size_t) (WAVE * XS_ROW);
-    for (int c = (int) threadIdx.x; c < EXP_TAB; c += (int) blockDim.x) {
-        const double e        = exp2((double) c * (1.0 / EXP_TAB));
-        exp2_tab[c]           = e;
-        exp2_tab[EXP_TAB + c] = __hiloint2double(__double2hiint(e) - (c << 12), __double2loint(e));
-    }
+    RT_FILL_EXP_TABLES(exp2_tab)
     __syncthreads();
     const int lane             = lane_id();
     const unsigned n_tiles_run = H.tile_end - H.tile_begin;
