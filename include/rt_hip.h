@@ -235,6 +235,15 @@ int rt_hip_plan_kernel_times(rt_hip_plan *plan, float *march_ms, float *freq_ms)
  * tables; RT_HIP_FUSED=2 in the environment keeps the two-kernel run. */
 int rt_hip_plan_last_fused(rt_hip_plan *plan);
 
+/* The instance of the march the plan's last run took, as bits: 1 = the short division sequences (tables and step
+ * factor inside the ranges plan_create verifies; otherwise the generic instance, all other bits 0); 2 and 4 together =
+ * the integrator step skips the division of the step candidate h1 where it cannot set the step, and its loop condition
+ * goes without the |n - n0| < 0.05 test -- taken where plan_create has proved from the tables that the test holds;
+ * 8 = the divisions of h2 and h4 are skipped likewise (launches of at least 8192 rays per compute unit).
+ * RT_HIP_MARCH_PRUNE in the environment at plan creation: 0 keeps bits 2, 4 and 8 off, 2 sets bit 8 at every launch
+ * size.  Every instance gives the same march records. */
+int rt_hip_plan_last_march_instance(rt_hip_plan *plan);
+
 /* Timing many back-to-back runs without waiting for each: keep the event triples of the last n_runs runs
  * (1 <= n_runs <= 4096); rt_hip_plan_ring_times waits for the last run and returns the kernel durations of
  * the most recent runs, oldest first (at most max_runs of them; *n_runs = how many).  Without a ring a plan

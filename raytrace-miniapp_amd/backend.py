@@ -233,6 +233,11 @@ class Plan:
         """The last run took the whole path in one launch (rt_fused.hip): kernel_times() = (launch, 0)."""
         return bool(self.hl.lib.rt_hip_plan_last_fused(self._h))
 
+    def last_march_instance(self) -> int:
+        """Bits of the march instance of the last run (include/rt_hip.h): 1 short divisions, 2 h1 pruned, 4 no |n - n0| test,
+        8 h2 and h4 pruned."""
+        return int(self.hl.lib.rt_hip_plan_last_march_instance(self._h))
+
     def set_timing_ring(self, n_runs: int) -> "Plan":
         """Keep the kernel-event triples of the last n_runs runs (include/rt_hip.h)."""
         self.hl.check(self.hl.lib.rt_hip_plan_set_timing_ring(self._h, int(n_runs)), "rt_hip_plan_set_timing_ring")

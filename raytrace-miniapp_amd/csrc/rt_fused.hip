@@ -64,7 +64,7 @@ constexpr int fused_wave_doubles(int maxq) { return 4 * XP_ROW + maxq * WAVE; }
 // row cache behind its transposition rows (lay.per_wave says how much, H.nslot how many rows): only a handful of such
 // buffers fit beside the march tables -- they go to the consumers, which run the frequency pass during the march; a wave
 // that leaves the march takes a buffer over the tables once the last marcher is done.
-template <bool BOUNDED, int SF, int MAXQ, bool EMIS = true>
+template <bool BOUNDED, int SF, int MAXQ, bool EMIS = true, int OPT = 0>
 __global__ void __launch_bounds__(1024) rt_fused_kernel(const FusedKArg A)
 {
     extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -111,7 +111,7 @@ __global__ void __launch_bounds__(1024) rt_fused_kernel(const FusedKArg A)
     // against 2.65 ms, 8-rank shard 0.537 / 0.536 against 0.534; profiles/r04_prio_ab.txt)
     march_load_tables<true>(A.P, lds_raw);
     if (!consumer)
-        march_wave<true, BOUNDED, true, EMIS ? 1 : 0>(A.P, lds_raw, list); // (emission runs are backward runs: rt_launch.hip asks for it)
+        march_wave<true, BOUNDED, true, EMIS ? 1 : 0, OPT>(A.P, lds_raw, list); // (emission runs are backward runs: rt_launch.hip asks for it)
 
     // ---- phase 2: this wave's rays have run out; frequency pass on the work-group's finished tiles ----
     const int lane = lane_id();

@@ -205,6 +205,17 @@ template <int SF, bool EMIS> int launch_spec(rt_hip_plan *p, hipStream_t stream)
     return RT_OK;
 }
 
+// the BOUNDED instances of the march by OPT (rt_march.hip): 0 as before; 3 = h1 pruned, no |n - n0| test; 7 = h2 and h4
+// pruned as well
+template <bool LDS_TAB, int MODE> void (*march_bounded(int opt))(const rt::DevParams)
+{
+    return opt == 7 ? rt::rt_march_kernel<LDS_TAB, true, MODE, 7> : opt == 3 ? rt::rt_march_kernel<LDS_TAB, true, MODE, 3> : rt::rt_march_kernel<LDS_TAB, true, MODE, 0>;
+}
+template <int SF, int MAXQ, bool EMIS> void (*fused_bounded(int opt))(const rt::FusedKArg)
+{
+    return opt == 7 ? rt::rt_fused_kernel<true, SF, MAXQ, EMIS, 7> : opt == 3 ? rt::rt_fused_kernel<true, SF, MAXQ, EMIS, 3> : rt::rt_fused_kernel<true, SF, MAXQ, EMIS, 0>;
+}
+
 int launch_spec_any(rt_hip_plan *p, hipStream_t stream)
 {
     const int S = p->P.L * RT_N_SUB;
@@ -399,10 +410,21 @@ int plan_launch_run(rt_hip_plan *p, hipStream_t stream)
     // alone, the same source compiles to a march that is 5 - 9 % SLOWER: RT_HIP_MARCH_MODE = 2 / 4 / 0 to see it)
     if (!p->P.use_emis && p->P.method == 2 && !p->path_on)
         mode = (int) env_unsigned("RT_HIP_MARCH_MODE", 3, 0, 4);
+    // (the two shortcuts of block [C], rt_march.hip OPT: BOUNDED instances whose tables allow the proof of the |n - n0|
+    // test -- every shipped one; other tables keep the old instance, as RT_HIP_MARCH_PRUNE=0 at plan creation does.
+    // The branch round the divisions of h2 and h4 pays where the waves compete for issue slots and costs where a
+    // launch is a few rays per lane -- measured, profiles/step_prune_ab.txt: 24.9 K rays per CU -2.0 %, 3.1 K a wash,
+    // 1.6 K +1 ... 2 %, nothing in between -- so it is taken from 8 K rays per CU and launch; RT_HIP_MARCH_PRUNE=2
+    // takes it at every size, for the tests)
+    const unsigned long long launch_rays = p->n_rays / n_launch;
+    const bool prune_h24 = p->march_prune == 2 || (p->cu_count && launch_rays / (unsigned long long) p->cu_count >= 8192ull);
+    const int opt = (bounded && p->march_prune && p->ntest_proven)
+                        ? (rt::MARCH_OPT_PRUNE | rt::MARCH_OPT_NO_NTEST | (prune_h24 ? rt::MARCH_OPT_PRUNE_H24 : 0)) : 0;
+    p->last_march_inst = (bounded ? 1 : 0) | (opt << 1);
     const march_fn kernel =
-        lds_tab ? (bounded ? (mode == 1 ? rt::rt_march_kernel<true, true, 1> : mode == 2 ? rt::rt_march_kernel<true, true, 2> : mode == 3 ? rt::rt_march_kernel<true, true, 3> : mode == 4 ? rt::rt_march_kernel<true, true, 4> : rt::rt_march_kernel<true, true, 0>)
+        lds_tab ? (bounded ? (mode == 1 ? march_bounded<true, 1>(opt) : mode == 2 ? march_bounded<true, 2>(opt) : mode == 3 ? march_bounded<true, 3>(opt) : mode == 4 ? march_bounded<true, 4>(opt) : march_bounded<true, 0>(opt))
                            : (mode == 1 ? rt::rt_march_kernel<true, false, 1> : rt::rt_march_kernel<true, false, 0>))
-                : (bounded ? rt::rt_march_kernel<false, true, 0> : rt::rt_march_kernel<false, false, 0>);
+                : (bounded ? march_bounded<false, 0>(opt) : rt::rt_march_kernel<false, false, 0>);
     if (lds_tab) {
         const int rc = allow_lds(reinterpret_cast<const void *>(kernel), p->device, mlds, p->lds_limit);
         if (rc != RT_OK)
@@ -557,12 +579,12 @@ int plan_launch_run(rt_hip_plan *p, hipStream_t stream)
             const int S  = p->P.L * RT_N_SUB;
             using fused_fn = void (*)(const rt::FusedKArg);
             const fused_fn fk =
-                !emis     ? (S == 6 ? (bounded ? rt::rt_fused_kernel<true, 6, 3, false> : rt::rt_fused_kernel<false, 6, 3, false>)
-                                    : (bounded ? rt::rt_fused_kernel<true, 0, 3, false> : rt::rt_fused_kernel<false, 0, 3, false>))
-                : maxq == 2 ? (S == 6 ? (bounded ? rt::rt_fused_kernel<true, 6, 2> : rt::rt_fused_kernel<false, 6, 2>)
-                                    : (bounded ? rt::rt_fused_kernel<true, 0, 2> : rt::rt_fused_kernel<false, 0, 2>))
-                          : (S == 6 ? (bounded ? rt::rt_fused_kernel<true, 6, 3> : rt::rt_fused_kernel<false, 6, 3>)
-                                    : (bounded ? rt::rt_fused_kernel<true, 0, 3> : rt::rt_fused_kernel<false, 0, 3>));
+                !emis     ? (S == 6 ? (bounded ? fused_bounded<6, 3, false>(opt) : rt::rt_fused_kernel<false, 6, 3, false>)
+                                    : (bounded ? fused_bounded<0, 3, false>(opt) : rt::rt_fused_kernel<false, 0, 3, false>))
+                : maxq == 2 ? (S == 6 ? (bounded ? fused_bounded<6, 2, true>(opt) : rt::rt_fused_kernel<false, 6, 2>)
+                                    : (bounded ? fused_bounded<0, 2, true>(opt) : rt::rt_fused_kernel<false, 0, 2>))
+                          : (S == 6 ? (bounded ? fused_bounded<6, 3, true>(opt) : rt::rt_fused_kernel<false, 6, 3>)
+                                    : (bounded ? fused_bounded<0, 3, true>(opt) : rt::rt_fused_kernel<false, 0, 3>));
             {
                 const int rc = allow_lds(reinterpret_cast<const void *>(fk), p->device, flds, p->lds_limit);
                 if (rc != RT_OK)
@@ -692,6 +714,18 @@ int rt_hip_debug_ray_iters(unsigned short *out, unsigned long long n)
 {
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(rt::g_ray_iters), (size_t) n * sizeof(unsigned short)));
+    return RT_OK;
+}
+#endif
+#ifdef RT_INSTRUMENT
+// diagnostic build only: read and clear the counters of the step-candidate pruning (rt_math.h, g_prune): wave-iterations
+// of block [C] in which the division of h1 and those of h2 and h4 were executed, and wave-iterations of [C] in a pruning instance
+int rt_hip_debug_prune_counters(unsigned long long *out4)
+{
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpyFromSymbol(out4, HIP_SYMBOL(rt::g_prune), 4 * sizeof(unsigned long long)));
+    unsigned long long z[4] = { 0 };
+    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(rt::g_prune), z, sizeof(z)));
     return RT_OK;
 }
 #endif

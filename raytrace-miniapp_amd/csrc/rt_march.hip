@@ -80,25 +80,65 @@ __device__ __forceinline__ void load_ray(const DevRays &R, unsigned ridx, rt_ray
 // Wide-argument fallbacks of the two float kernels below.  Kept out of line: inlined, the
 // double-precision libm bodies park ~40 VGPRs of polynomial coefficients across the whole
 // calling kernel for a branch that the shipped inputs never take.
-// Neither hands a NaN or an infinity to the device library's float64 routines: its f64 tangent faulted on an infinity
-// (the argument reduction indexes a table with the exponent; found by tests/test_gpu_edges.py in round 4), so the
-// non-finite cases get libm's answers here -- tan(+-inf) = tan(NaN) = NaN, atan(+-inf) = +-pi/2, atan(NaN) = NaN.
+// tan_wide hands no NaN or infinity to the device library's float64 tangent: it faulted on an infinity (the argument
+// reduction indexes a table with the exponent; found by tests/test_gpu_edges.py in round 4), so the non-finite cases get
+// libm's answers here -- tan(+-inf) = tan(NaN) = NaN.
 __device__ __attribute__((noinline)) float tan_wide(float x)
 {
     if (!(fabsf(x) <= FLT_MAX))
         return x - x;
     return (float) tan((double) x);
 }
+// atanf beyond its first branch, |x| >= 7/16 (exit directions more than 23.6 degrees off the axis): the other branches of
+// the same libm routine (s_atanf.c: argument reduction to atan(1/2), atan(1), atan(3/2) or pi/2 as hi + lo pairs, then
+// the polynomial of atanf_flt32_kernel), restated in float in its order.  Checked against the host atanf for EVERY float
+// of [7/16, 2^25), both signs, and a sample beyond, where the result is +-pi/2 (tests/test_atanf_wide.py): 0 mismatches.  (Until this was restated the
+// float-rounded f64 arc tangent stood in, which differs from libm's float routine in the last bit for a few per cent of
+// the arguments: found by tests/test_gpu_march_prune.py with rays launched up to a radian off the axis.)
 __device__ __attribute__((noinline)) float atan_wide(float x)
 {
-    if (x != x)
-        return x + x;
-    if (!(fabsf(x) <= FLT_MAX))
-        return copysignf(1.5707963705062866f, x); // (float) (pi / 2), what atanf(+-inf) returns
-    return (float) atan((double) x);
+    const float A0 = 3.3333334327e-01f, A1 = -2.0000000298e-01f, A2 = 1.4285714924e-01f, A3 = -1.1111110449e-01f,
+                A4 = 9.0908870101e-02f, A5 = -7.6918758452e-02f, A6 = 6.6610731184e-02f, A7 = -5.8335702866e-02f,
+                A8 = 4.9768779427e-02f, A9 = -3.6531571299e-02f, A10 = 1.6285819933e-02f;
+    const unsigned hx = __float_as_uint(x), ix = hx & 0x7fffffffu;
+    const bool neg = (hx >> 31) != 0u;
+    if (ix >= 0x4c000000u) { // |x| >= 2^25, infinities, NaN
+        if (ix > 0x7f800000u)
+            return x + x;
+        const float r = 1.5707962513e+00f + 7.5497894159e-08f;
+        return neg ? -r : r;
+    }
+    float hi, lo;
+    x = fabsf(x);
+    if (ix < 0x3f980000u) { // |x| < 1.1875
+        if (ix < 0x3f300000u) { // 7/16 <= |x| < 11/16
+            hi = 4.6364760399e-01f;
+            lo = 5.0121582440e-09f;
+            x  = (2.0f * x - 1.0f) / (2.0f + x);
+        } else {
+            hi = 7.8539812565e-01f;
+            lo = 3.7748947079e-08f;
+            x  = (x - 1.0f) / (x + 1.0f);
+        }
+    } else {
+        if (ix < 0x401c0000u) { // |x| < 2.4375
+            hi = 9.8279368877e-01f;
+            lo = 3.4473217170e-08f;
+            x  = (x - 1.5f) / (1.0f + 1.5f * x);
+        } else {
+            hi = 1.5707962513e+00f;
+            lo = 7.5497894159e-08f;
+            x  = -1.0f / x;
+        }
+    }
+    const float z = x * x, w = z * z;
+    const float s1 = z * (A0 + w * (A2 + w * (A4 + w * (A6 + w * (A8 + w * A10)))));
+    const float s2 = w * (A1 + w * (A3 + w * (A5 + w * (A7 + w * A9))));
+    const float r  = hi - ((x * (s1 + s2) - lo) - x);
+    return neg ? -r : r;
 }
 
-// The three float kernels below (ktanf_flt32 / tanf_flt32_wide / tanf_flt32_kernel, atanf_flt32_kernel) restate
+// atan_wide above and the three float kernels below (ktanf_flt32 / tanf_flt32_wide / tanf_flt32_kernel, atanf_flt32_kernel) restate
 // routines of fdlibm as shipped in GNU libc 2.35 (sysdeps/ieee754/flt-32/k_tanf.c, e_rem_pio2f.c, s_atanf.c;
 // float conversions by Ian Lance Taylor, Cygnus Support) -- same coefficients, same evaluation order, because
 // bit-exactness with the reference platform's libm requires it.  Their notice:
@@ -532,7 +572,14 @@ template <bool LDS_TAB> __device__ __forceinline__ void march_load_tables(const 
 // method -- every ASE run; 2: gain only, forward method -- every seeded run of create_image; 0: as DevParams says): as
 // run-time booleans they live in SGPR pairs that the register allocator spills into VGPR lanes and reads back
 // (v_readlane + wait states) in the cell set-up and the retirement block, i.e. in almost every iteration.
-template <bool LDS_TAB, bool BOUNDED, bool FUSED, int MODE = 0>
+//
+// OPT (BOUNDED only; rt_launch.hip picks 0, 3 or 7; RT_HIP_MARCH_PRUNE=0 keeps 0): bit 0 (MARCH_OPT_PRUNE) -- the
+// integrator step skips, wave by wave, the division of the step candidate h1 when it cannot set the step (block [C]);
+// bit 2 (MARCH_OPT_PRUNE_H24, large launches) -- likewise those of h2 and h4, behind one branch; bit 1
+// (MARCH_OPT_NO_NTEST) -- rt_hip_plan_create has proved that |n - n0| < 0.05 (Helper.h:280) holds in every step these
+// tables allow, and the loop condition of [C] goes without it.  The march records are the same floats in every instance.
+enum : int { MARCH_OPT_PRUNE = 1, MARCH_OPT_NO_NTEST = 2, MARCH_OPT_PRUNE_H24 = 4 };
+template <bool LDS_TAB, bool BOUNDED, bool FUSED, int MODE = 0, int OPT = 0>
 __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *lds_raw, const TileList done)
 {
     const int lane        = lane_id();
@@ -584,7 +631,11 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
     // dry that much earlier, drain and turn to the frequency pass while the old waves are still busy, and the final
     // drain is run by one wave per SIMD that nothing on its SIMD outranks.  Zone 0: chunks [0, n_main), zone 1: the rest,
     // with counters of its own (next_tile[..][shard][8]).
+#ifdef RT_MARCH_ONE_COUNTER // (the one-counter experiment knows no zones: with a late zone it would drop the chunks it draws past n_main)
+    const unsigned n_main = n_chunks;
+#else
     const unsigned n_main = n_chunks - (P.late_chunks < n_chunks ? P.late_chunks : 0u);
+#endif
     // (unsigned: waves late_first .. late_first + late_waves - 1; through readfirstlane, so that the compiler knows it for
     // wave-uniform -- derived from threadIdx.x it counts as divergent, and with it `zone`, `more` and every branch of the
     // loop head that tests them, which then run as exec-mask code instead of scalar branches)
@@ -1226,7 +1277,52 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
                 float fy = qy - sy * t;
                 float fz = -sz * t;
                 float h;
-                if (BOUNDED) {
+                if (BOUNDED && (OPT & MARCH_OPT_PRUNE)) {
+                    // The same candidates, but a division is executed only where its quotient can matter.  Four of the
+                    // five candidates are quotients num / den with num >= 0, den >= 0, and the step is their minimum
+                    // with dzcap: a candidate whose exact quotient exceeds dzcap rounds to a float >= dzcap (or, where the
+                    // short sequence is out of its range, to something huge, infinite or NaN that the minimum passes
+                    // over, see below), so leaving it out of the minimum returns the same float.  Sufficient, without a
+                    // division: p = RN(RN(K dzcap) den) < num with K = 1.00002f.  The two products lose at most 2^-24
+                    // each, so p >= K (1 - 2^-24)^2 dzcap den > dzcap den (K - 1 = 168 x 2^-23 against the 2^-23 needed)
+                    // and num > p gives num / den > dzcap.  A product that lands in the subnormal range (absolute
+                    // error 2^-150) could only mislead a numerator below 2^-125: those of h1 and h4 are at least
+                    // 5e-12 (c_h3 >= 1e-8), and for h2 it takes |sz| dzcap < 2^-125 while num >= 2^-24 lim2, i.e.
+                    // num / |sz| > 2^101 lim2 dzcap > dzcap (lim2 >= 5e-6 dz / 3 >= 1e-18 under the BOUNDED ranges).
+                    // A comparison with a NaN or against den = inf is false: that candidate is divided as before.
+                    // K is small enough to keep pruning h2 right after a dzcap step, where h2 / dzcap is about
+                    // 1.0001 / (1.00001 |sz|) >= 1.00008.  The decision is taken for the wave (one scalar branch per
+                    // candidate or pair of candidates): on the 6.4 M-ray stand-in dzcap sets 63 % of the steps, h3 35 %, h4 0.8 %, h2 0.6 %, h1
+                    // none, so h3 is always divided.
+                    const float kd = 1.00002f * dzcap;
+                    const float at = fabsf(t), az = fabsf(sz);
+                    const float n2 = 1.0001f * (lim2 - fabsf(rz));
+                    const float n4 = P.c_h3 * (fabsf(sy) + 5e-4f), d4 = fabsf(fy) + 1e-8f;
+                    h = fmin_nan_drop(fdiv_nr(P.c_h3 * (fabsf(sx) + 5e-4f), (fabsf(fx) + 1e-8f)), dzcap);
+#ifdef RT_INSTRUMENT
+                    const bool cnt_lane = lane == (int) __ffsll((long long) __ballot(1)) - 1;
+                    if (cnt_lane)
+                        atomicAdd(&g_prune[3], 1ull);
+#endif
+                    if (__ballot(!(P.c_h1 > kd * at)) != 0ull) {
+                        h = fmin_nan_drop(fdiv_nr(P.c_h1, at), h);
+#ifdef RT_INSTRUMENT
+                        if (cnt_lane)
+                            atomicAdd(&g_prune[0], 1ull);
+#endif
+                    }
+                    // h2 and h4 behind ONE branch, their two divisions interleaved when it is taken: a branch each ran the
+                    // stand-in 1.6 % faster than none but 2 - 3 % slower on launches of a few rays per lane, whose waves
+                    // wait on their own dependency chain and not on the issue slots (profiles/step_prune_ab.txt); merged
+                    // it is 2.0 % on the stand-in, and the small launches go without it (rt_launch.hip)
+                    if (!(OPT & MARCH_OPT_PRUNE_H24) || __ballot(!(n2 > kd * az) | !(n4 > kd * d4)) != 0ull) {
+                        h = fmin_nan_drop(fmin_nan_drop(fdiv_nr(n2, az), fdiv_nr(n4, d4)), h);
+#ifdef RT_INSTRUMENT
+                        if (cnt_lane)
+                            atomicAdd(&g_prune[1], 1ull);
+#endif
+                    }
+                } else if (BOUNDED) {
                     // The step candidates (Helper.h:288-297) without the range bookkeeping of an IEEE division
                     // (fdiv_nr, rt_math.h): exact wherever a candidate can be the minimum; a candidate that the
                     // short sequence gets wrong is huge, infinite or NaN on both paths (its true value is above
@@ -1260,7 +1356,10 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
                 hsum += h;
                 RT_TICK(0);
                 // (double)|n - n0| < 0.05 (Helper.h:280) <=> |n - n0| < 0.05f: 0.05f is the smallest float above 0.05
-                run = (fabsf(rx) < lim0) & (fabsf(ry) < lim1) & (fabsf(rz) < lim2) & (fabsf(n - n0) < 0.05f);
+                // (MARCH_OPT_NO_NTEST: the last test is known to hold, rt_plan.hip "the largest index change a step can see")
+                run = (fabsf(rx) < lim0) & (fabsf(ry) < lim1) & (fabsf(rz) < lim2);
+                if (!(BOUNDED && (OPT & MARCH_OPT_NO_NTEST)))
+                    run = run & (fabsf(n - n0) < 0.05f);
             }
             if (!run) {
                 // integrator loop over: close this cross-cell iteration (Helper.h:343-348)
@@ -1335,12 +1434,12 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
     }
 }
 
-template <bool LDS_TAB, bool BOUNDED, int MODE = 0>
+template <bool LDS_TAB, bool BOUNDED, int MODE = 0, int OPT = 0>
 __global__ void __launch_bounds__(LDS_TAB ? 1024 : 256) rt_march_kernel(const DevParams P)
 {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     march_load_tables<LDS_TAB>(P, lds_raw);
-    march_wave<LDS_TAB, BOUNDED, false, MODE>(P, lds_raw, TileList{ nullptr, nullptr, nullptr, nullptr, 0u, nullptr, nullptr, 0u, 0u, 0u });
+    march_wave<LDS_TAB, BOUNDED, false, MODE, OPT>(P, lds_raw, TileList{ nullptr, nullptr, nullptr, nullptr, 0u, nullptr, nullptr, 0u, 0u, 0u });
 }
 
 } // namespace rt

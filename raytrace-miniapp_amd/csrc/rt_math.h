@@ -14,6 +14,9 @@ namespace rt {
 // march loops.  g_inst[2i] = wave-level iterations, g_inst[2i+1] = active-lane
 // iterations, i = 0 inner (Helper.h:279), 1 cross (:326), 2 cell (:463).
 __device__ unsigned long long g_inst[8];
+// ... and the step-candidate pruning of block [C] (rt_march.hip): wave-iterations in which the division of h1 [0] and
+// those of h2 and h4 [1] were executed ([2] unused), and wave-iterations of [C] in an instance that prunes [3]
+__device__ unsigned long long g_prune[4];
 struct Inst {
     unsigned w[3] = { 0, 0, 0 }, a[3] = { 0, 0, 0 };
     __device__ __forceinline__ void tick(int i)

@@ -350,7 +350,7 @@ int rtr::plan_create_on(rt_hip_plan **out, hipStream_t upload_q, int device, int
     // march blob: headers + grids + fused corner nodes of every length, copied to LDS
     // verbatim by rt_march_kernel<true>
     std::vector<unsigned char> blob(align_up(sizeof(rt::BlobGain) * (size_t) N, 16));
-    bool tiny_spacing = false, bad_index = false, all_bounded = true;
+    bool tiny_spacing = false, bad_index = false, all_bounded = true, ntest_proven = true;
     for (int i = 1; i < N; i++) {
         const rt_gain &g  = gain[i];
         const size_t npix = (size_t) g.Nx * (size_t) g.Ny;
@@ -431,6 +431,20 @@ int rtr::plan_create_on(rt_hip_plan **out, hipStream_t upload_q, int device, int
             }
             if (!(n_lo - dn >= 0.25 && n_hi + dn <= 4.0 && dn / w_min <= 1e12 && w_min >= 1e-12))
                 all_bounded = false;
+            // The largest index change a step can see.  The loop condition of the integrator tests the n of the step just
+            // taken, n0 + rx gxn + ry gyn with the r that passed |rx| < 0.1 wx, |ry| < 0.1 wy one step earlier (no
+            // overshoot enters), and |gxn| wx <= 1.2 dn (the two edge differences of the cell weighted with v, 1 - v for
+            // v in the cell box with its 10 % margin: |v| + |1 - v| <= 1.2), likewise gyn: |n - n0| <= 0.24 dn plus a few
+            // roundings of floats below 4 (< 2e-6).  On the mirrored half plane (y[0] >= 0) the box of the first y
+            // interval reaches down to |y| = 0, where u = -y[0] / wy: |u| + |1 - u| = 1 + 2 y[0] / wy there, which is what
+            // weights the edge differences of gyn (a grid that starts at y = 0, as every shipped one does, adds nothing).
+            // With a safety factor of 8 -- tables anywhere near the limit keep the test -- the march goes without it
+            // (rt_march.hip, MARCH_OPT_NO_NTEST) when 8 x 0.1 (1.2 + fy) dn <= 0.05 - 1e-5.
+            // (The ranges above assume the same 10 % margin; a mirrored grid that starts far from y = 0 extrapolates n
+            // further than dn.  Such tables are not known; the generic instance can be forced with RT_HIP_MARCH_IEEE=1.)
+            const double fy = g.y[0] >= 0.0 ? std::max(1.2, 1.0 + 2.0 * g.y[0] / (g.y[1] - g.y[0])) : 1.2;
+            if (!(8.0 * 0.1 * (1.2 + fy) * dn <= 0.05 - 1e-5))
+                ntest_proven = false;
         }
     }
     // (dz: a straight ray in a medium without refraction advances by up to 1250 cm per integrator step, Helper.h:288-297;
@@ -438,6 +452,8 @@ int rtr::plan_create_on(rt_hip_plan **out, hipStream_t upload_q, int device, int
     if (!(beam->dz >= 1e-12 && beam->dz <= 1e6))
         all_bounded = false;
     p->tables_bounded = all_bounded;
+    p->ntest_proven   = all_bounded && ntest_proven;
+    p->march_prune    = (int) env_unsigned("RT_HIP_MARCH_PRUNE", 1, 0, 2);
     if (tiny_spacing) {
         delete p;
         return fail_arg("rt_hip_plan_create: gain grid not strictly increasing, or spacing below 1e-30");
@@ -1096,6 +1112,7 @@ int rt_hip_plan_kernel_times(rt_hip_plan *p, float *march_ms, float *freq_ms)
 }
 
 int rt_hip_plan_last_fused(rt_hip_plan *p) { return p && p->ran && p->last_fused ? 1 : 0; }
+int rt_hip_plan_last_march_instance(rt_hip_plan *p) { return p && p->ran ? p->last_march_inst : 0; }
 
 double *rt_hip_plan_image_ptr(rt_hip_plan *p) { return p ? p->image_own : nullptr; }
 double *rt_hip_plan_iang_ptr(rt_hip_plan *p) { return p ? p->iang_own : nullptr; }

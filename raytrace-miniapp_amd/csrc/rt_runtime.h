@@ -83,6 +83,13 @@ struct rt_hip_plan {
     // the refractive-index tables and the segment length lie in the ranges under which the march's divisions
     // need no scaling (rt_march.hip, template parameter BOUNDED); checked by rt_hip_plan_create
     bool tables_bounded   = false;
+    // the integrator's loop condition |n - n0| < 0.05 (Helper.h:280) holds in every step these tables allow (proved by
+    // rt_hip_plan_create from the largest index difference between neighbouring nodes): the march may go without it
+    bool ntest_proven     = false;
+    // RT_HIP_MARCH_PRUNE (read by rt_hip_plan_create; 0: the march without the step-candidate pruning and with the
+    // |n - n0| test, whatever the tables allow) and the instance the last run took (rt_hip_plan_last_march_instance)
+    int march_prune       = 1; // (2: h2 / h4 pruned at every launch size)
+    int last_march_inst   = 0;
     // links of the fused kernel's work-group tile lists (rt_fused.hip), one word per 64-ray tile; last run fused?
     unsigned *tile_next   = nullptr;
     size_t tile_next_n    = 0;

@@ -1,0 +1,213 @@
+"""Which step candidate sets each integrator step, and how each integrator loop ends: an instrumented copy of the
+march of oracle/rt_oracle.c (march_impl, cross_cell, step_linear_medium; Helper.h:270-351, 404-513), vectorised over the
+rays with numpy.  Every float operation is a float32 operation in the oracle's order, the double ones are float64; only
+tanf is numpy's, which may differ from libm's in the last bit -- the copy counts, it is not the yardstick for the records
+(that is Oracle.probe).  tests/test_gpu_march_prune.py uses it to make sure that its synthetic tables exercise what
+they are built for.
+
+  steps(problem, rays) -> dict(winner=[dzcap, h1, h2, h3, h4] steps each candidate set (ties to the earlier one of the
+                               reference's `<` chain h1, dzcap, h2, h3, h4), inner=integrator steps, cells=cell steps,
+                               n_exit=integrator loops ended by |n - n0| >= 0.05 alone, n_exit_rays=rays with such a loop,
+                               max_dn=largest |n - n0| any step saw,
+                               prunable=[h1, h2, h4] steps in which the division-free test of rt_march.hip, block [C],
+                               num > RN(RN(1.00002f dzcap) den), says the candidate cannot set the step,
+                               prune_wrong=such steps in which the candidate's float quotient is below dzcap after all)
+"""
+import importlib
+
+import numpy as np
+
+F = np.float32
+N_SUB = 3
+
+
+def _interval_index(g, v):
+    # the unique u in [1, n-1] with (u == 1 || g[u-1] < v) && (u == n-1 || g[u] >= v)
+    return np.clip(np.searchsorted(g, v, side="left"), 1, len(g) - 1)
+
+
+def _lerp2(u, v, f00, f10, f01, f11):
+    u1 = F(1) - u
+    v1 = F(1) - v
+    return (u * f10 + u1 * f00) * v1 + (u * f11 + u1 * f01) * v
+
+
+def _renorm(sx, sy, sz):
+    q = sx * sx + sy * sy + sz * sz
+    inv = (1.0 / np.sqrt(q).astype(np.float64)).astype(F)
+    return sx * inv, sy * inv, sz * inv
+
+
+def steps(problem, rays, c=0.5):
+    old = np.seterr(all="ignore")
+    try:
+        return _steps(problem, rays, F(c))
+    finally:
+        np.seterr(**old)
+
+
+def _steps(p, rays, c):
+    n_r = len(rays)
+    N, method, use_emis = p.N, p.method, p.use_emis
+    dz0 = F(p.beam.dz)
+    px, py = rays["x"].astype(F), rays["y"].astype(F)
+    pz = np.zeros(n_r, F)
+    sx, sy = np.tan(F(1e-3) * rays["a"].astype(F)).astype(F), np.tan(F(1e-3) * rays["b"].astype(F)).astype(F)
+    sz = np.ones(n_r, F)
+    if method == 1:
+        sx, sy, sz = -sx, -sy, -sz
+    sx, sy, sz = _renorm(sx, sy, sz)
+    escaped = np.zeros(n_r, bool)
+    winner = np.zeros(5, np.int64)
+    exit_ray = np.zeros(n_r, bool)
+    n_exit = inner = cells = 0
+    max_dn = 0.0
+    prunable = np.zeros(3, np.int64)
+    prune_wrong = 0
+    for seg in range(N - 1):
+        g = p.gain[N - seg - 1 if method == 1 else seg + 1]
+        Nx = g.Nx
+        lo_x, hi_x, lo_y, hi_y = F(g.x[0]), F(g.x[-1]), F(g.y[0]), F(g.y[-1])
+        mirror = bool(lo_y >= 0)
+        if mirror:
+            lo_y = -hi_y
+        z = np.zeros(n_r, F)
+        for iz in range(N_SUB):
+            z_stop = F(dz0 * (F(iz) + F(1)) / F(N_SUB))
+            while True:
+                act = ~escaped & (z < F(0.995) * z_stop)
+                esc = act & ((px < lo_x) | (px > hi_x) | (py < lo_y) | (py > hi_y) | ((sz * sz).astype(np.float64) < 0.01))
+                escaped |= esc
+                act &= ~esc
+                i = np.nonzero(act)[0]
+                if len(i) == 0:
+                    break
+                ya = np.abs(py[i]) if mirror else py[i]
+                k1 = _interval_index(g.x, px[i].astype(np.float64))
+                k2 = _interval_index(g.y, ya.astype(np.float64))
+                c00, c10, c01, c11 = (k1 - 1) + (k2 - 1) * Nx, k1 + (k2 - 1) * Nx, (k1 - 1) + k2 * Nx, k1 + k2 * Nx
+                xc0, xc1, yc0, yc1 = g.x[k1 - 1], g.x[k1], g.y[k2 - 1], g.y[k2]
+                nc = [g.n[c00], g.n[c10], g.n[c01], g.n[c11]]
+                pz[i] = 0
+                box = [(xc0 - 0.1 * (xc1 - xc0)).astype(F), (xc1 + 0.1 * (xc1 - xc0)).astype(F),
+                       (yc0 - 0.1 * (yc1 - yc0)).astype(F), (yc1 + 0.1 * (yc1 - yc0)).astype(F)]
+                if mirror:
+                    box[2] = np.where(k2 <= 1, -box[3], box[2])
+                dzrem = z_stop - z[i]
+                # ---- cross_cell
+                zc = np.zeros(len(i), F)
+                wx, wy = (xc1 - xc0).astype(F), (yc1 - yc0).astype(F)
+                while True:
+                    ya = np.abs(py[i]) if mirror else py[i]
+                    m = (px[i] > box[0]) & (px[i] < box[1]) & (ya > box[2]) & (ya < box[3]) & \
+                        (zc.astype(np.float64) < 0.999 * dzrem.astype(np.float64))
+                    j = np.nonzero(m)[0]
+                    if len(j) == 0:
+                        break
+                    r = i[j]
+                    u = ((px[r].astype(np.float64) - xc0[j]) / wx[j].astype(np.float64)).astype(F)
+                    v = ((ya[j].astype(np.float64) - yc0[j]) / wy[j].astype(np.float64)).astype(F)
+                    n0 = _lerp2(u, v, nc[0][j].astype(F), nc[1][j].astype(F), nc[2][j].astype(F), nc[3][j].astype(F))
+                    ud, vd = u.astype(np.float64), v.astype(np.float64)
+                    gx = ((1.0 - vd) * (nc[1][j] - nc[0][j]) / wx[j].astype(np.float64) +
+                          vd * (nc[3][j] - nc[2][j]) / wx[j].astype(np.float64)).astype(F)
+                    gy = ((1.0 - ud) * (nc[2][j] - nc[0][j]) / wy[j].astype(np.float64) +
+                          ud * (nc[3][j] - nc[1][j]) / wy[j].astype(np.float64)).astype(F)
+                    if mirror:
+                        gy = np.where(py[r] < 0, -gy, gy)
+                    lim0, lim1, lim2 = F(0.1) * wx[j], F(0.1) * wy[j], dzrem[j] - zc[j]
+                    # ---- step_linear_medium
+                    dzcap = c * F(1.00001) * lim2
+                    rx, ry, rz = np.zeros(len(j), F), np.zeros(len(j), F), np.zeros(len(j), F)
+                    n = n0.copy()
+                    s0, s1, s2 = sx[r], sy[r], sz[r]
+                    alive = np.ones(len(j), bool)
+                    while True:
+                        geo = (np.abs(rx) < lim0) & (np.abs(ry) < lim1) & (np.abs(rz) < lim2)
+                        ntest = np.abs(n - n0).astype(np.float64) < 0.05
+                        ex = alive & geo & ~ntest
+                        n_exit += int(ex.sum())
+                        exit_ray[r[ex]] = True
+                        alive &= geo & ntest
+                        q = np.nonzero(alive)[0]
+                        if len(q) == 0:
+                            break
+                        a0, a1, a2 = s0[q], s1[q], s2[q]
+                        nn = n0[q] + rx[q] * gx[q] + ry[q] * gy[q]
+                        n[q] = nn
+                        max_dn = max(max_dn, float(np.abs(nn - n0[q]).max()))
+                        t = (a0 * gx[q] + a1 * gy[q] + F(1e-12)) / nn
+                        fx = gx[q] / nn - a0 * t
+                        fy = gy[q] / nn - a1 * t
+                        fz = -a2 * t
+                        h = c * F(0.1) / np.abs(t)
+                        w = np.ones(len(q), np.int64)
+                        cand = [dzcap[q], F(1.0001) * (lim2[q] - np.abs(rz[q])) / np.abs(a2),
+                                c * F(0.05) * (np.abs(a0) + F(5e-4)) / (np.abs(fx) + F(1e-8)),
+                                c * F(0.05) * (np.abs(a1) + F(5e-4)) / (np.abs(fy) + F(1e-8))]
+                        kd = F(1.00002) * cand[0]
+                        for pi, (num, den, quo) in enumerate((
+                                (np.full(len(q), c * F(0.1), F), np.abs(t), h),
+                                (F(1.0001) * (lim2[q] - np.abs(rz[q])), np.abs(a2), cand[1]),
+                                (c * F(0.05) * (np.abs(a1) + F(5e-4)), np.abs(fy) + F(1e-8), cand[3]))):
+                            pr = num > kd * den
+                            prunable[pi] += int(pr.sum())
+                            prune_wrong += int((pr & (quo < cand[0])).sum())
+                        # h = h < dzcap ? h : dzcap, then h = h < h_k ? h : h_k for h2, h3, h4
+                        keep = h < cand[0]
+                        w = np.where(keep, 1, 0)
+                        h = np.where(keep, h, cand[0])
+                        for ci, wi in ((1, 2), (2, 3), (3, 4)):
+                            keep = h < cand[ci]
+                            w = np.where(keep, w, wi)
+                            h = np.where(keep, h, cand[ci])
+                        winner += np.bincount(w, minlength=5)
+                        inner += len(q)
+                        ht = h * t
+                        c1 = F(0.5) * h * h * (F(1) - ht / F(3) + ht * ht / F(12))
+                        rx[q] += a0 * h + c1 * fx
+                        ry[q] += a1 * h + c1 * fy
+                        rz[q] += a2 * h + c1 * fz
+                        c2 = h * (F(1) - F(0.5) * ht + ht * ht / F(6))
+                        s0[q], s1[q], s2[q] = _renorm(a0 + c2 * fx, a1 + c2 * fy, a2 + c2 * fz)
+                    sx[r], sy[r], sz[r] = s0, s1, s2
+                    px[r] += rx
+                    py[r] += ry
+                    pz[r] += rz
+                    zc[j] += np.abs(rz)
+                z[i] += np.abs(pz[i])
+                cells += len(i)
+    return dict(winner=winner, inner=inner, cells=cells, n_exit=n_exit, n_exit_rays=int(exit_ray.sum()), max_dn=max_dn, prunable=prunable, prune_wrong=prune_wrong)
+
+
+# ------------------------------------------------------------------ the synthetic tables of the march tests
+def synthetic(nfun, a_max, b_max, w=1e-3, dz=0.05, a_c=0.0, L=1, mirror=False, y0=0.0):
+    """Nx = Ny = 8 tables of cell width w with the index nfun(ix, iy), one pixel near the middle, 38 x 28 = 1064 launch
+    angles a_c +- a_max by +- b_max mrad, L lengths (every length the same table); mirror: the y grid starts at y0 >= 0."""
+    pm = importlib.import_module("raytrace-miniapp_amd.problem")
+    x = w * np.arange(8)
+    y = w * np.arange(8) + (y0 if mirror else -3.5 * w)     # (y[0] >= 0: the mirrored half plane of Helper.h:449-453)
+    X, Y = np.meshgrid(np.arange(8.0), np.arange(8.0))    # node indices, ix fastest
+    rng = np.random.default_rng(5)
+    nv = 4
+    g = pm.Gain(x, y, nfun(X, Y).reshape(-1), rng.uniform(1, 50, 64), rng.uniform(0.1, 5, 64), rng.uniform(0.1, 1, 64 * nv), nv)
+    a, b = a_c + np.linspace(-a_max, a_max, 38), np.linspace(-b_max, b_max, 28)
+    beam = pm.Beam(x=[3.4 * w], y=[y0 + 3.6 * w if mirror else 0.1 * w], a=a, b=b, dv=np.full(nv, 1.0), dx=w, dy=w,
+                   da=a[1] - a[0], db=b[1] - b[0], dz=dz)
+    return pm.Problem(beam=beam, gain=[g] * (L + 1))
+
+
+# name -> (problem, candidates that must set at least 1 % of the steps; 1 = h1, 2 = h2, 4 = h4 of march_steps.steps()["winner"],
+#          the |n - n0| test proved away -- largest neighbour difference of the index at most 0.05 / (8 x 0.24) = 0.026 --
+#          which is what lets a table take the instance with the shortcuts at all)
+BINDING_CASES = {
+    # rays launched a radian off the axis, along a steep x gradient, with next to no y component: c 0.1 / |t| is the
+    # smallest candidate (h3 needs |s.x| near 1 to lose to it, h4 |s.y| below 5e-4)
+    "x_steep": (lambda: synthetic(lambda X, Y: 1.0 + 0.025 * X, 200, 0.3, w=0.02, dz=0.5, a_c=1000), (1,), True),
+    # a y-dominated gradient on the mirrored half plane
+    "y_dominated": (lambda: synthetic(lambda X, Y: 1.0 + 0.0002 * X + 0.004 * Y, 30, 30, mirror=True), (4,), True),
+    # wide cells and a weak gradient over two lengths: integrator loops long enough for the end of the sub-segment (h2)
+    "weak_wide": (lambda: synthetic(lambda X, Y: 1.0 + 0.01 * X + 0.0001 * Y, 1000, 0.4, w=0.05, dz=0.5, L=2), (2, 4), True),
+}
+
+
