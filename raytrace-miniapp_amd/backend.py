@@ -7,6 +7,8 @@ mirror of the reference's operator interface for this path.
   image_loop(...)       the back-end loop, same meaning as RayTraceImageCudaLoop
                         (src/RayTraceImageCuda.cu:145-221) behind the signature of
                         src/RayTraceImage.cpp:47-75
+  step_loop(...)        the same loop with the application's per-step record in place of the image cube: E_v, nf, I_ang
+  step_outputs_from_image  their definition as reductions of a cube, in numpy (no device)
   calc_rays / calc_ray  RayTrace::calc_ray (src/RayTraceImage.cpp:189-204), batched: per-ray spectrum, exit ray, code
   create_image(p, method)
                         mirror of RayTrace::create_image (src/RayTraceImage.cpp:227-434):
@@ -138,14 +140,16 @@ class Plan:
     def fetch(self, want_image: bool = True) -> dict:
         b = self.problem.beam
         want_image = want_image and not getattr(self, "_spectra", False)  # a spectra run has no image
+        want_iang = want_image
+        want_image = want_image and not getattr(self, "_step", False)     # ... and a step run has I_ang only
         image = np.empty(b.nx * b.ny * b.nv) if want_image else None
-        iang = np.empty(b.na * b.nb) if want_image else None
+        iang = np.empty(b.na * b.nb) if want_iang else None
         code = C.c_uint(0)
         nf = C.c_int(0)
         failed = np.zeros(cabi.RT_N_FAILED_MAX, dtype=cabi.RAY_DTYPE)
         st = cabi.RtStats()
         rc = self.hl.lib.rt_hip_plan_fetch(
-            self._h, cabi._dp(image) if want_image else None, cabi._dp(iang) if want_image else None,
+            self._h, cabi._dp(image) if want_image else None, cabi._dp(iang) if want_iang else None,
             C.byref(code), cabi.rays_ptr(failed), cabi.RT_N_FAILED_MAX, C.byref(nf), C.byref(st))
         self.hl.check(rc, "rt_hip_plan_fetch")
         return dict(image=image, I_ang=iang, failure_code=code.value, failed_rays=failed[:nf.value].copy(),
@@ -215,6 +219,46 @@ class Plan:
         v.__cuda_array_interface__ = dict(shape=(self.n_rays, self.problem.beam.nv), typestr="<f8", data=(ptr, False),
                                           version=2, strides=None)
         return torch.as_tensor(v, device=torch.device("cuda", self.device))
+
+    def enable_step(self, on: bool = True) -> "Plan":
+        """Step mode (include/rt_hip.h): a run produces E_v, nf and I_ang -- the image cube reduced on the way, never
+        allocated.  run() then takes no image_ptr."""
+        self.hl.check(self.hl.lib.rt_hip_plan_enable_step(self._h, int(on)), "rt_hip_plan_enable_step")
+        self._step = bool(on)
+        return self
+
+    def fetch_step(self) -> dict:
+        """E_v [nv], nf [nx * ny] (p = ix + iy nx), I_ang [na * nb] of the last step run (waits for it)."""
+        b = self.problem.beam
+        E_v, nf, iang = np.empty(b.nv), np.empty(b.nx * b.ny), np.empty(b.na * b.nb)
+        self.hl.check(self.hl.lib.rt_hip_plan_fetch_step(self._h, cabi._dp(E_v), cabi._dp(nf), cabi._dp(iang)),
+                      "rt_hip_plan_fetch_step")
+        return dict(E_v=E_v, nf=nf, I_ang=iang)
+
+    def step_ptrs(self) -> tuple:
+        """Device pointers (E_v, nf) of the last step run."""
+        e, n = C.c_void_p(), C.c_void_p()
+        self.hl.check(self.hl.lib.rt_hip_plan_step_ptrs(self._h, C.byref(e), C.byref(n)), "rt_hip_plan_step_ptrs")
+        return int(e.value or 0), int(n.value or 0)
+
+    def step_tensors(self) -> dict:
+        """torch views (float64, on the plan's device, no copy) of E_v [nv], nf [ny][nx] and I_ang [nb][na] (the plan's own
+        buffer; None if every run was handed the caller's) of the last step run: valid until the plan's next run; read
+        them on the run's stream or after a fetch."""
+        import torch
+
+        class _View:  # the CUDA array interface, which torch.as_tensor reads
+            pass
+
+        def view(ptr, shape):
+            v = _View()
+            v.__cuda_array_interface__ = dict(shape=shape, typestr="<f8", data=(ptr, False), version=2, strides=None)
+            return torch.as_tensor(v, device=torch.device("cuda", self.device))
+
+        b = self.problem.beam
+        e, n = self.step_ptrs()
+        ang = self.iang_ptr
+        return dict(E_v=view(e, (b.nv,)), nf=view(n, (b.ny, b.nx)), I_ang=view(ang, (b.nb, b.na)) if ang else None)
 
     def kernel_ms(self) -> float:
         """Device time of the last run's trace kernel (waits for it)."""
@@ -321,6 +365,48 @@ def image_loop(problem: Problem, rays: np.ndarray | None = None, device: int = 0
     hl.check(rc, "rt_hip_image_loop")
     return dict(image=image, I_ang=iang, failure_code=code.value, failed_rays=failed[:nf.value].copy(),
                 stats={k: getattr(st, k) for k, _ in cabi.RtStats._fields_}, call_ms=call_ms)
+
+
+def step_loop(problem: Problem, rays: np.ndarray | None = None, device: int = 0) -> dict:
+    """image_loop with the small outputs (rt_hip_step_loop): E_v [nv], nf [nx * ny], I_ang, failure_code, failed_rays,
+    stats -- the image cube is never built."""
+    hl = HipLibrary.get()
+    m = cabi.Marshalled(problem)
+    if rays is None:
+        rays = problem.build_rays()
+    rays = np.ascontiguousarray(rays, dtype=cabi.RAY_DTYPE)
+    b = problem.beam
+    E_v, nf, iang = np.zeros(b.nv), np.zeros(b.nx * b.ny), np.zeros(b.na * b.nb)
+    code = C.c_uint(0)
+    nfail = C.c_int(0)
+    failed = np.zeros(cabi.RT_N_FAILED_MAX, dtype=cabi.RAY_DTYPE)
+    st = cabi.RtStats()
+    t0 = time.perf_counter()
+    rc = hl.lib.rt_hip_step_loop(device, m.N, C.byref(m.beam), m.gain, m.seed_ref, problem.method,
+                                 cabi.rays_ptr(rays), len(rays), problem.scale, cabi._dp(E_v), cabi._dp(nf),
+                                 cabi._dp(iang), C.byref(code), cabi.rays_ptr(failed),
+                                 cabi.RT_N_FAILED_MAX, C.byref(nfail), C.byref(st))
+    call_ms = (time.perf_counter() - t0) * 1e3
+    hl.check(rc, "rt_hip_step_loop")
+    return dict(E_v=E_v, nf=nf, I_ang=iang, failure_code=code.value, failed_rays=failed[:nfail.value].copy(),
+                stats={k: getattr(st, k) for k, _ in cabi.RtStats._fields_}, call_ms=call_ms)
+
+
+def step_outputs_from_image(problem: Problem, image) -> dict:
+    """The definition of the step outputs as reductions of an image cube [ny * nx * nv] (k fastest, p = ix + iy nx):
+    E_v[k] = sum_p image[k + nv p], nf[p] = sum_k 2 dv[k] image[k + nv p] -- accumulated in np.longdouble, returned as
+    float64.  Needs no device."""
+    b = problem.beam
+    cube = np.asarray(image, dtype=np.float64).reshape(b.nx * b.ny, b.nv)
+    w = (2.0 * np.asarray(b.dv, dtype=np.float64)).astype(np.longdouble)   # (2 dv is exact: RayTraceImageCPU.cpp:66)
+    E_v = np.zeros(b.nv, np.longdouble)
+    nf = np.empty(b.nx * b.ny)
+    step = max(1, (1 << 22) // b.nv)                      # pixels per block: the long-double copy stays at 64 MB
+    for lo in range(0, b.nx * b.ny, step):
+        part = cube[lo:lo + step].astype(np.longdouble)
+        E_v += part.sum(axis=0)
+        nf[lo:lo + step] = (part * w[None, :]).sum(axis=1)
+    return dict(E_v=E_v.astype(np.float64), nf=nf)
 
 
 def multi_image_loop(problem: Problem, rays: np.ndarray | None = None, n_devices: int = 0) -> dict:

@@ -214,6 +214,18 @@ def declare_hip_api(lib: C.CDLL) -> None:
     lib.rt_hip_calc_rays.argtypes = [C.c_int, C.c_int, C.c_double, P(RtGain), P(RtSeed), C.c_int, C.c_int, c_double_p,
                                      C.c_size_t, c_double_p, c_double_p, P(C.c_int32), P(RtStats)]
     lib.rt_hip_calc_rays.restype = C.c_int
+    if hasattr(lib, "rt_hip_plan_enable_step"):   # (a library built from an earlier commit, loaded for an A/B, has none)
+        lib.rt_hip_plan_enable_step.argtypes = [vp, C.c_int]
+        lib.rt_hip_plan_enable_step.restype = C.c_int
+        lib.rt_hip_plan_fetch_step.argtypes = [vp, c_double_p, c_double_p, c_double_p]
+        lib.rt_hip_plan_fetch_step.restype = C.c_int
+        lib.rt_hip_plan_step_ptrs.argtypes = [vp, P(vp), P(vp)]
+        lib.rt_hip_plan_step_ptrs.restype = C.c_int
+        lib.rt_hip_step_loop.argtypes = [
+            C.c_int, C.c_int, P(RtBeam), P(RtGain), P(RtSeed), C.c_int, P(RtRay), C.c_size_t,
+            C.c_double, c_double_p, c_double_p, c_double_p, P(C.c_uint), P(RtRay), C.c_int, P(C.c_int),
+            P(RtStats)]
+        lib.rt_hip_step_loop.restype = C.c_int
     lib.rt_hip_plan_set_debug.argtypes = [vp, C.c_uint]
     lib.rt_hip_plan_set_debug.restype = C.c_int
     lib.rt_hip_plan_destroy.argtypes = [vp]
@@ -228,5 +240,6 @@ HIP_API_SYMBOLS = [
     "rt_hip_plan_kernel_ms", "rt_hip_plan_kernel_times", "rt_hip_plan_last_fused", "rt_hip_plan_last_march_instance", "rt_hip_plan_set_timing_ring", "rt_hip_plan_ring_times", "rt_hip_plan_image_ptr", "rt_hip_plan_iang_ptr", "rt_hip_plan_enable_probe",
     "rt_hip_plan_fetch_probe", "rt_hip_plan_set_exact_emission", "rt_hip_plan_set_step_factor", "rt_hip_plan_enable_path",
     "rt_hip_plan_fetch_path", "rt_hip_plan_enable_spectra", "rt_hip_plan_fetch_spectra", "rt_hip_plan_spectra_ptr",
-    "rt_hip_calc_rays", "rt_hip_plan_set_debug", "rt_hip_plan_destroy",
+    "rt_hip_calc_rays", "rt_hip_plan_enable_step", "rt_hip_plan_fetch_step", "rt_hip_plan_step_ptrs", "rt_hip_step_loop",
+    "rt_hip_plan_set_debug", "rt_hip_plan_destroy",
 ]

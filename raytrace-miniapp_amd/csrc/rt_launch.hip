@@ -3,13 +3,14 @@
 // Replaces the launch half of RayTraceImageCudaLoop (src/RayTraceImageCuda.cu:198-203: one thread-per-ray
 // launch): a run is the march kernel (persistent lanes over LDS-resident tables, rt_march.hip) -> one
 // 96-byte record per ray -> the frequency / deposit kernel (rt_freq.hip), back to back on one queue, or the
-// path tracer (rt_path.hip) or the spectra kernel (rt_spec.hip) in place of the frequency kernel.  This is the only translation unit with the
+// path tracer (rt_path.hip), the spectra kernel (rt_spec.hip) or the step kernel (rt_step.hip) in place of the frequency kernel.  This is the only translation unit with the
 // kernels of the path in it; the rest of the library reaches them through the functions declared in
 // rt_runtime.h.
 #include "rt_path.hip" // debug path tracer (before rt_freq.hip: no FMA contraction there)
 #include "rt_freq.hip" // kernel B (includes rt_march.hip, kernel A)
 #include "rt_fused.hip" // both as two phases of one launch
 #include "rt_spec.hip" // spectra mode: per-ray spectra in place of the deposit
+#include "rt_step.hip" // step mode: E_v, nf and I_ang, the image cube reduced on the way
 
 #include "rt_runtime.h"
 
@@ -216,6 +217,45 @@ template <int SF, int MAXQ, bool EMIS> void (*fused_bounded(int opt))(const rt::
     return opt == 7 ? rt::rt_fused_kernel<true, SF, MAXQ, EMIS, 7> : opt == 3 ? rt::rt_fused_kernel<true, SF, MAXQ, EMIS, 3> : rt::rt_fused_kernel<true, SF, MAXQ, EMIS, 0>;
 }
 
+// step mode: rt_step_kernel over all tiles, one 16-wave work-group per CU; the I_ang histogram in LDS where the frequency
+// kernel keeps it there
+template <int SF, bool EMIS> int launch_step(rt_hip_plan *p, hipStream_t stream)
+{
+    const int wg_waves = rt::FREQ_WG_WAVES;
+    const bool in_lds  = p->n_iang * sizeof(double) <= 32 * 1024;
+    const size_t lds   = rt::step_lds_doubles(in_lds, (int) p->n_iang, p->P.Kp, wg_waves) * sizeof(double);
+    if (lds > p->lds_limit)
+        return fail_arg("step kernel: the E_v accumulator (nv doubles) does not fit into the LDS of this device");
+    const unsigned long long want = ((unsigned long long) (p->P.tile_end - p->P.tile_begin) + (unsigned) wg_waves - 1) / (unsigned) wg_waves;
+    const unsigned grid           = (unsigned) (want < (unsigned long long) p->cu_count ? want : (unsigned long long) p->cu_count);
+    if (grid == 0)
+        return RT_OK;
+    const rt::FreqKArg f = freq_args(p, in_lds, 0, (unsigned long long) grid * (unsigned) wg_waves);
+    rt::StepKArg a;
+    memset(&a, 0, sizeof(a));
+    a.hot       = f.hot;
+    a.hot.image = nullptr; // never touched: there is no cube
+    a.cold      = f.cold;
+    a.out       = p->step;
+    const int rc = allow_lds(reinterpret_cast<const void *>(&rt::rt_step_kernel<SF, EMIS>), p->device, lds, p->lds_limit);
+    if (rc != RT_OK)
+        return rc;
+    hipLaunchKernelGGL((rt::rt_step_kernel<SF, EMIS>), dim3(grid), dim3((unsigned) wg_waves * 64), lds, stream, a);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+int launch_step_any(rt_hip_plan *p, hipStream_t stream)
+{
+    p->P.tile_begin = 0;
+    p->P.tile_end   = p->P.n_tiles;
+    p->P.freq_id    = 0;
+    const int S = p->P.L * RT_N_SUB;
+    if (p->P.use_emis)
+        return (S == 6) ? launch_step<6, true>(p, stream) : launch_step<0, true>(p, stream);
+    return (S == 6) ? launch_step<6, false>(p, stream) : launch_step<0, false>(p, stream);
+}
+
 int launch_spec_any(rt_hip_plan *p, hipStream_t stream)
 {
     const int S = p->P.L * RT_N_SUB;
@@ -298,14 +338,17 @@ int plan_repeat_checked(rt_hip_plan *p)
     HIP_TRY(hipMemsetAsync(p->ctl->next_tile_f, 0, sizeof(p->ctl->next_tile_f), stream));
     p->P.bad  = p->bad_dev;
     p->P.safe = 1;
-    int rc    = launch_freq_any(p, stream);
+    const bool step = p->last_step; // a step run: the step kernel honours the same marks, E_v and nf start over
+    int rc    = step ? launch_step_any(p, stream) : launch_freq_any(p, stream);
     if (rc == RT_OK) {
-        if (!p->P.exclusive)
+        if (step)
+            HIP_TRY(hipMemsetAsync(p->step_dev, 0, p->step_doubles * sizeof(double), stream));
+        else if (!p->P.exclusive)
             HIP_TRY(hipMemsetAsync(p->last_image, 0, p->n_image * sizeof(double), stream));
         HIP_TRY(hipMemsetAsync(p->last_iang, 0, p->n_iang * sizeof(double), stream));
         HIP_TRY(hipMemsetAsync(p->ctl->next_tile_f, 0, sizeof(p->ctl->next_tile_f), stream));
         p->P.safe = 2;
-        rc        = launch_freq_any(p, stream);
+        rc        = step ? launch_step_any(p, stream) : launch_freq_any(p, stream);
     }
     p->P.safe = 0;
     p->P.bad  = nullptr;
@@ -378,7 +421,7 @@ int plan_launch_run(rt_hip_plan *p, hipStream_t stream)
     // of sixteen waves marching less.  Two kernels stay the rule for this mode; RT_HIP_FUSED_SEED=1 takes the one launch.)
     const bool fused_emis = p->P.use_emis && p->P.method == 1 && p->P.own_cells && p->P.rays.nga * p->P.rays.ngb >= 32;
     const bool fused_gain = !p->P.use_emis && p->P.rays.list == nullptr && env_unsigned("RT_HIP_FUSED_SEED", 0, 0, 1) == 1;
-    const bool fused_cand = lds_tab && n_launch == 1 && p->n_rays > 0 && !p->path_on && !p->spectra_on && !p->probe_on && p->P.debug == 0 &&
+    const bool fused_cand = lds_tab && n_launch == 1 && p->n_rays > 0 && !p->path_on && !p->spectra_on && !p->step_on && !p->probe_on && p->P.debug == 0 &&
                             (fused_emis || fused_gain) && !p->P.exclusive && p->P.safe == 0 &&
                             p->n_iang * sizeof(double) <= 32 * 1024 && env_unsigned("RT_HIP_FUSED", 1, 1, 2) == 1;
     unsigned bthr = lds_tab ? 1024u : 256u;
@@ -644,6 +687,13 @@ int plan_launch_run(rt_hip_plan *p, hipStream_t stream)
         const int rc = launch_spec_any(p, stream);
         if (rc != RT_OK)
             return rc;
+    } else if (p->step_on) {
+        // the step kernel replaces the frequency / deposit kernel: E_v, nf and I_ang, no image cube
+        if (!(p->P.debug & 1u)) {
+            const int rc = launch_step_any(p, stream);
+            if (rc != RT_OK)
+                return rc;
+        }
     } else if (!(p->P.debug & 1u)) {
         const int rc = launch_freq_any(p, stream);
         if (rc != RT_OK)

@@ -187,6 +187,7 @@ void rt_hip_plan_destroy(rt_hip_plan *p)
     (void) hipFree(p->path_err);
     (void) hipFree(p->spec[0].Iv); // (ray2 and err of a set live in the same allocation)
     (void) hipFree(p->spec[1].Iv);
+    pool_free(p->device, p->step_dev);
     pool_free(p->device, p->arena);
     pool_free(p->device, p->rays_dev);
     pool_free(p->device, p->grid_dev);
@@ -602,22 +603,30 @@ void rtr::plan_stage_outputs(rt_hip_plan *p)
     constexpr size_t ctl_tail = offsetof(rt::DevCtl, failure_code), ctl_bytes = sizeof(rt::DevCtl) - ctl_tail;
     if (!p || !p->ran || !p->last_stream)
         return;
+    // (a step run: E_v and nf travel where the image does)
+    const double *big    = p->last_step ? p->step_dev : p->last_image;
+    const size_t n_big   = p->last_step ? p->step_doubles : p->n_image;
     const size_t off_ang = align_up(ctl_bytes, 256), off_img = off_ang + align_up(p->n_iang * sizeof(double), 256);
-    const size_t total   = off_img + p->n_image * sizeof(double);
+    const size_t total   = off_img + n_big * sizeof(double);
     if (total > ((size_t) 4 << 20))
         return;
+    if (p->out_staging && p->out_staging_bytes < total) {
+        pinned_free(p->out_staging);
+        p->out_staging = nullptr;
+    }
     if (!p->out_staging) {
         void *h = nullptr;
         if (pinned_alloc(&h, total) != hipSuccess)
             return;
-        p->out_staging = static_cast<unsigned char *>(h);
+        p->out_staging       = static_cast<unsigned char *>(h);
+        p->out_staging_bytes = total;
     }
     hipError_t e = hipMemcpyAsync(p->out_staging, reinterpret_cast<const unsigned char *>(p->ctl) + ctl_tail, ctl_bytes,
                                   hipMemcpyDeviceToHost, p->last_stream);
     if (e == hipSuccess)
         e = hipMemcpyAsync(p->out_staging + off_ang, p->last_iang, p->n_iang * sizeof(double), hipMemcpyDeviceToHost, p->last_stream);
     if (e == hipSuccess)
-        e = hipMemcpyAsync(p->out_staging + off_img, p->last_image, p->n_image * sizeof(double), hipMemcpyDeviceToHost, p->last_stream);
+        e = hipMemcpyAsync(p->out_staging + off_img, big, n_big * sizeof(double), hipMemcpyDeviceToHost, p->last_stream);
     if (e != hipSuccess) {
         (void) hipGetLastError(); // fetched the ordinary way
         return;
@@ -827,6 +836,8 @@ int rt_hip_plan_enable_path(rt_hip_plan *p, int on)
         return fail_arg("rt_hip_plan_enable_path: NULL plan");
     if (on && p->spectra_on)
         return fail_arg("rt_hip_plan_enable_path: the plan is in spectra mode (one per-ray output at a time)");
+    if (on && p->step_on)
+        return fail_arg("rt_hip_plan_enable_path: the plan is in step mode (one output mode at a time)");
     p->path_on = on != 0;
     return RT_OK;
 }
@@ -851,6 +862,8 @@ int rt_hip_plan_enable_spectra(rt_hip_plan *p, int on)
         return fail_arg("rt_hip_plan_enable_spectra: NULL plan");
     if (on && p->path_on)
         return fail_arg("rt_hip_plan_enable_spectra: the path tracer is enabled (one per-ray output at a time)");
+    if (on && p->step_on)
+        return fail_arg("rt_hip_plan_enable_spectra: the plan is in step mode (one output mode at a time)");
     p->spectra_on = on != 0;
     return RT_OK;
 }
@@ -875,6 +888,27 @@ int rt_hip_plan_fetch_spectra(rt_hip_plan *p, double *Iv, rt_ray *ray2, int32_t 
 }
 
 double *rt_hip_plan_spectra_ptr(rt_hip_plan *p) { return p && p->ran && p->last_spectra ? p->spec[p->spec_last].Iv : nullptr; }
+
+int rt_hip_plan_enable_step(rt_hip_plan *p, int on)
+{
+    if (!p)
+        return fail_arg("rt_hip_plan_enable_step: NULL plan");
+    if (on && (p->path_on || p->spectra_on))
+        return fail_arg("rt_hip_plan_enable_step: the path tracer or spectra mode is enabled (one output mode at a time)");
+    p->step_on = on != 0;
+    return RT_OK;
+}
+
+int rt_hip_plan_step_ptrs(rt_hip_plan *p, double **E_v_dev, double **nf_dev)
+{
+    if (!p || !p->ran || !p->last_step)
+        return fail_arg("rt_hip_plan_step_ptrs: the last run was not a step run");
+    if (E_v_dev)
+        *E_v_dev = p->step.E_v;
+    if (nf_dev)
+        *nf_dev = p->step.nf;
+    return RT_OK;
+}
 
 int rt_hip_plan_enable_probe(rt_hip_plan *p, int on)
 {
@@ -923,7 +957,21 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
         return fail_arg("rt_hip_plan_run: a spectra run takes no image buffers");
     if (spectra && p->path_on)
         return fail_arg("rt_hip_plan_run: spectra mode and the path tracer are both enabled");
-    if (!spectra && !image_dev) {
+    const bool step = p->step_on; // E_v, nf and I_ang: the image cube is neither allocated nor written
+    if (step && (spectra || p->path_on))
+        return fail_arg("rt_hip_plan_run: step mode together with spectra mode or the path tracer");
+    if (step && image_dev)
+        return fail_arg("rt_hip_plan_run: a step run takes no image buffer");
+    if (step && !p->step_dev) {
+        const size_t nf_off = align_up((size_t) p->P.K * sizeof(double), 256) / sizeof(double);
+        // (one row and a cell to spare: on an axis of one grid point the reference's getIndex answers 1 for the coordinate
+        // g[0] + d/2 exactly, deposit_index4 of rt_freq.hip likewise)
+        p->step_doubles     = nf_off + (size_t) p->P.beam.nx * (size_t) p->P.beam.ny + (size_t) p->P.beam.nx + 2;
+        HIP_TRY(pool_alloc(p->device, (void **) &p->step_dev, p->step_doubles * sizeof(double)));
+        p->step.E_v = p->step_dev;
+        p->step.nf  = p->step_dev + nf_off;
+    }
+    if (!spectra && !step && !image_dev) {
         if (!p->image_own)
             HIP_TRY(pool_alloc(p->device, (void **) &p->image_own, p->n_image * sizeof(double)));
         image_dev = p->image_own;
@@ -943,8 +991,10 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
         HIP_TRY(hipMemsetAsync(p->probe, 0, (size_t) p->n_rays * (sizeof(rt_ray) + 8), stream));
     static_assert(sizeof(rt::DevCtl) % 8 == 0 && alignof(rt::DevCtl) >= 8, "zeroed in 8-byte words");
     // (exclusive mode writes every image row exactly once: its image is not zeroed)
-    rc = launch_zero3(stream, (p->P.exclusive || spectra) ? nullptr : image_dev, p->n_image * sizeof(double), iang_dev, p->n_iang * sizeof(double),
-                      p->ctl, sizeof(rt::DevCtl));
+    // (step mode: E_v and nf take the image's place in the zeroing launch, exclusive or not)
+    rc = step ? launch_zero3(stream, p->step_dev, p->step_doubles * sizeof(double), iang_dev, p->n_iang * sizeof(double), p->ctl, sizeof(rt::DevCtl))
+              : launch_zero3(stream, (p->P.exclusive || spectra) ? nullptr : image_dev, p->n_image * sizeof(double), iang_dev,
+                             p->n_iang * sizeof(double), p->ctl, sizeof(rt::DevCtl));
     if (rc != RT_OK)
         return rc;
     p->P.image   = image_dev;
@@ -965,6 +1015,7 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
     p->last_image  = image_dev;
     p->last_iang   = iang_dev;
     p->last_spectra = spectra;
+    p->last_step   = step;
     p->spec_last   = p->spec_sel;
     p->ran         = true;
     p->queued      = false; // (`ran` + last_stream cover it from here)
@@ -973,24 +1024,22 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
     return RT_OK;
 }
 
-int rt_hip_plan_fetch(rt_hip_plan *p, double *image, double *I_ang, unsigned int *failure_code,
-                      rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats)
+} // extern "C"
+
+// Wait for the last run and read the control block behind the chunk counters (failure code, failed rays, statistics);
+// a run whose frequency pass reported failing rays is repeated without them first.  `staged`: the outputs that
+// travelled behind the kernels (plan_stage_outputs) are still this run's.
+static int plan_settle(rt_hip_plan *p, rt::DevCtl &c, bool &staged)
 {
-    if (!p || !p->ran)
-        return fail_arg("rt_hip_plan_fetch: plan has not run");
-    if (p->last_spectra && (image || I_ang))
-        return fail_arg("rt_hip_plan_fetch: the last run was a spectra run, it has no image (rt_hip_plan_fetch_spectra)");
     HIP_TRY(hipSetDevice(p->device));
     HIP_TRY(hipStreamSynchronize(p->last_stream));
-    // the control block behind the chunk counters: failure code, failed rays, statistics
-    rt::DevCtl c;
     constexpr size_t ctl_tail = offsetof(rt::DevCtl, failure_code), ctl_bytes = sizeof(rt::DevCtl) - ctl_tail;
     auto read_ctl = [&]() {
         return hipMemcpy(reinterpret_cast<unsigned char *>(&c) + ctl_tail, reinterpret_cast<const unsigned char *>(p->ctl) + ctl_tail,
                          ctl_bytes, hipMemcpyDeviceToHost);
     };
     // (outputs that travelled behind the kernels already: plan_stage_outputs)
-    bool staged = p->out_staged && p->out_staging;
+    staged = p->out_staged && p->out_staging;
     if (staged)
         memcpy(reinterpret_cast<unsigned char *>(&c) + ctl_tail, p->out_staging, ctl_bytes);
     else
@@ -1005,6 +1054,26 @@ int rt_hip_plan_fetch(rt_hip_plan *p, double *image, double *I_ang, unsigned int
         p->out_staged = staged = false;
         HIP_TRY(read_ctl());
     }
+    return RT_OK;
+}
+
+extern "C" {
+
+int rt_hip_plan_fetch(rt_hip_plan *p, double *image, double *I_ang, unsigned int *failure_code,
+                      rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats)
+{
+    if (!p || !p->ran)
+        return fail_arg("rt_hip_plan_fetch: plan has not run");
+    if (p->last_spectra && (image || I_ang))
+        return fail_arg("rt_hip_plan_fetch: the last run was a spectra run, it has no image (rt_hip_plan_fetch_spectra)");
+    if (p->last_step && image)
+        return fail_arg("rt_hip_plan_fetch: the last run was a step run, it has no image (rt_hip_plan_fetch_step)");
+    rt::DevCtl c;
+    bool staged  = false;
+    const int rs = plan_settle(p, c, staged);
+    if (rs != RT_OK)
+        return rs;
+    constexpr size_t ctl_tail = offsetof(rt::DevCtl, failure_code), ctl_bytes = sizeof(rt::DevCtl) - ctl_tail;
     if (staged) {
         const size_t off_ang = align_up(ctl_bytes, 256), off_img = off_ang + align_up(p->n_iang * sizeof(double), 256);
         if (image)
@@ -1039,6 +1108,37 @@ int rt_hip_plan_fetch(rt_hip_plan *p, double *image, double *I_ang, unsigned int
         HIP_TRY(hipEventElapsedTime(&stats->freq_ms, p->evm, p->ev1));
         stats->total_ms  = (float) std::chrono::duration<double, std::milli>(
                               std::chrono::steady_clock::now() - p->t_created).count();
+    }
+    return RT_OK;
+}
+
+int rt_hip_plan_fetch_step(rt_hip_plan *p, double *E_v, double *nf, double *I_ang)
+{
+    if (!p || !p->ran || !p->last_step)
+        return fail_arg("rt_hip_plan_fetch_step: the last run was not a step run");
+    rt::DevCtl c;
+    bool staged  = false;
+    const int rs = plan_settle(p, c, staged); // (a failing run is repeated here as rt_hip_plan_fetch repeats it)
+    if (rs != RT_OK)
+        return rs;
+    const size_t n_pix = (size_t) p->P.beam.nx * (size_t) p->P.beam.ny, n_k = (size_t) p->P.K;
+    if (staged) {
+        constexpr size_t ctl_bytes = sizeof(rt::DevCtl) - offsetof(rt::DevCtl, failure_code);
+        const size_t off_ang = align_up(ctl_bytes, 256), off_img = off_ang + align_up(p->n_iang * sizeof(double), 256);
+        const double *s      = reinterpret_cast<const double *>(p->out_staging + off_img);
+        if (E_v)
+            memcpy(E_v, s, n_k * sizeof(double));
+        if (nf)
+            memcpy(nf, s + (p->step.nf - p->step.E_v), n_pix * sizeof(double));
+        if (I_ang)
+            memcpy(I_ang, p->out_staging + off_ang, p->n_iang * sizeof(double));
+    } else {
+        if (E_v)
+            HIP_TRY(hipMemcpy(E_v, p->step.E_v, n_k * sizeof(double), hipMemcpyDeviceToHost));
+        if (nf)
+            HIP_TRY(hipMemcpy(nf, p->step.nf, n_pix * sizeof(double), hipMemcpyDeviceToHost));
+        if (I_ang)
+            HIP_TRY(hipMemcpy(I_ang, p->last_iang, p->n_iang * sizeof(double), hipMemcpyDeviceToHost));
     }
     return RT_OK;
 }
@@ -1153,17 +1253,15 @@ int rt_hip_plan_fetch_probe(rt_hip_plan *p, float *gvl, float *evl, int32_t *ivl
     return RT_OK;
 }
 
-int rt_hip_image_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed,
-                      int method, const rt_ray *rays, size_t n_rays, double scale, double *image,
-                      double *I_ang, unsigned int *failure_code, rt_ray *failed_rays, int max_failed,
-                      int *n_failed, rt_stats *stats)
+} // extern "C"
+
+// rt_hip_image_loop, and rt_hip_step_loop (image == NULL: E_v and nf instead, through step mode)
+static int host_pointer_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed,
+                             int method, const rt_ray *rays, size_t n_rays, double scale, double *image, double *E_v, double *nf,
+                             double *I_ang, unsigned int *failure_code, rt_ray *failed_rays, int max_failed,
+                             int *n_failed, rt_stats *stats)
 {
-    if (!image || !I_ang)
-        return fail_arg("rt_hip_image_loop: NULL output");
-    if (!rays && n_rays)
-        return fail_arg("rt_hip_image_loop: NULL ray list");
-    if (n_rays > MAX_LIST_RAYS)
-        return fail_arg("rt_hip_image_loop: 2^32 - 4096 rays or more: split the call");
+    const bool step = image == nullptr;
     // RT_HIP_TIMING=1: wall-clock split of this call on stderr (diagnostic)
     static const bool timing = getenv("RT_HIP_TIMING") != nullptr;
     auto t_prev = std::chrono::steady_clock::now();
@@ -1182,6 +1280,14 @@ int rt_hip_image_loop(int device, int N, const rt_beam *beam, const rt_gain *gai
     if (rc != RT_OK) {
         release_queue(device, q);
         return rc;
+    }
+    if (step) {
+        rc = rt_hip_plan_enable_step(p, 1);
+        if (rc != RT_OK) {
+            rt_hip_plan_destroy(p);
+            release_queue(device, q);
+            return rc;
+        }
     }
     // (the seed-factor tables of a seeded plan are filled by a kernel outside this queue: rt_hip_plan_set_ray_grid)
     if (seed && q && hipStreamSynchronize(q) != hipSuccess)
@@ -1214,12 +1320,45 @@ int rt_hip_image_loop(int device, int N, const rt_beam *beam, const rt_gain *gai
             plan_stage_outputs(p);
     }
     if (rc == RT_OK)
-        rc = rt_hip_plan_fetch(p, image, I_ang, failure_code, failed_rays, max_failed, n_failed, stats);
+        rc = rt_hip_plan_fetch(p, image, step ? nullptr : I_ang, failure_code, failed_rays, max_failed, n_failed, stats);
+    if (rc == RT_OK && step)
+        rc = rt_hip_plan_fetch_step(p, E_v, nf, I_ang);
     lap("fetch (wait + D2H)");
     rt_hip_plan_destroy(p); // waits for whatever is still in flight
     release_queue(device, q);
     lap("destroy");
     return rc;
+}
+
+extern "C" {
+
+int rt_hip_image_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed,
+                      int method, const rt_ray *rays, size_t n_rays, double scale, double *image,
+                      double *I_ang, unsigned int *failure_code, rt_ray *failed_rays, int max_failed,
+                      int *n_failed, rt_stats *stats)
+{
+    if (!image || !I_ang)
+        return fail_arg("rt_hip_image_loop: NULL output");
+    if (!rays && n_rays)
+        return fail_arg("rt_hip_image_loop: NULL ray list");
+    if (n_rays > MAX_LIST_RAYS)
+        return fail_arg("rt_hip_image_loop: 2^32 - 4096 rays or more: split the call");
+    return host_pointer_loop(device, N, beam, gain, seed, method, rays, n_rays, scale, image, nullptr, nullptr, I_ang, failure_code,
+                             failed_rays, max_failed, n_failed, stats);
+}
+
+int rt_hip_step_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed, int method,
+                     const rt_ray *rays, size_t n_rays, double scale, double *E_v, double *nf, double *I_ang,
+                     unsigned int *failure_code, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats)
+{
+    if (!E_v || !nf || !I_ang)
+        return fail_arg("rt_hip_step_loop: NULL output");
+    if (!rays && n_rays)
+        return fail_arg("rt_hip_step_loop: NULL ray list");
+    if (n_rays > MAX_LIST_RAYS)
+        return fail_arg("rt_hip_step_loop: 2^32 - 4096 rays or more: split the call");
+    return host_pointer_loop(device, N, beam, gain, seed, method, rays, n_rays, scale, nullptr, E_v, nf, I_ang, failure_code,
+                             failed_rays, max_failed, n_failed, stats);
 }
 
 int rt_hip_calc_rays(int device, int N, double dz, const rt_gain *gain, const rt_seed *seed, int K, int method, const double *rays,

@@ -6,13 +6,14 @@
 //                   rt_hip_image_loop (the host-pointer entry the C++ adapter calls)
 //   rt_raygrid.hip  a ray list that is really a tensor grid: recognition + bit-wise verification,
 //                   list-mode launch tangents and the probe of the host's libm
-//   rt_launch.hip   the kernels (rt_march.hip, rt_freq.hip, rt_path.hip, rt_spec.hip) and how a run puts them on a queue
+//   rt_launch.hip   the kernels (rt_march.hip, rt_freq.hip, rt_path.hip, rt_spec.hip, rt_step.hip) and how a run puts them on a queue
 //   rt_multi.hip    all devices of the node: RCCL loader, communicator, rt_hip_multi_image_loop
 // Only rt_launch.hip and rt_multi.hip contain device code.
 #pragma once
 
 #include "rt_device.h"
 #include "rt_spec.h"
+#include "rt_step.h"
 
 #include <chrono>
 #include <string>
@@ -29,6 +30,7 @@ struct rt_hip_plan {
     hipStream_t upload_q = nullptr;
     unsigned char *out_staging = nullptr; // page-locked copy of the last run's outputs, queued behind its kernels (plan_stage_outputs)
     bool out_staged            = false;
+    size_t out_staging_bytes   = 0;
     rt_ray *rays_dev   = nullptr;
     double *grid_dev   = nullptr; // ray grids when rays are generated
     float *tan_dev     = nullptr; // tangents: grid mode [nga + ngb], list mode [2 n_rays]
@@ -47,6 +49,13 @@ struct rt_hip_plan {
     unsigned spec_last = 0;       // ... and the one the last run wrote
     rt::SpecOut spec[2] = {};
     size_t spec_rays[2] = { 0, 0 }; // rays each set has room for
+    // step mode (rt_hip_plan_enable_step): E_v and nf instead of the image cube.  One allocation, zeroed by the run's
+    // zeroing launch: E_v [K] at its start, nf [nx * ny] behind it at a 256-byte boundary.
+    bool step_on       = false;
+    bool last_step     = false;   // the last run was a step run
+    double *step_dev   = nullptr;
+    size_t step_doubles = 0;      // doubles of the allocation
+    rt::StepOut step   = {};
     size_t rec_bytes   = 0;
     hipEvent_t evm     = nullptr; // between march and frequency kernels
     const rt_ray *host_rays = nullptr; // ray list still on the host, uploaded by the next run (rt_hip_image_loop)
@@ -139,7 +148,7 @@ void release_queue(int device, hipStream_t q);
 void plan_quiesce(rt_hip_plan *p);
 // the list stays on the host until the run, which uploads it in slices beside the march
 int plan_set_rays_deferred(rt_hip_plan *p, const rt_ray *rays, size_t n_rays);
-// after rt_hip_plan_run: queues the download of control block, I_ang and image (if they are small) behind the kernels, into
+// after rt_hip_plan_run: queues the download of control block, I_ang and image (step mode: E_v and nf) -- if they are small -- behind the kernels, into
 // page-locked staging, so that rt_hip_plan_fetch finds them on the host when the queue has drained
 void plan_stage_outputs(rt_hip_plan *p);
 // rt_hip_plan_create with the table upload queued on `upload_q` from page-locked staging instead of waited for (nullptr:
@@ -169,7 +178,7 @@ int tan_mode(int device);
 // ---- rt_launch.hip -----------------------------------------------------------------------------------
 // march -> records -> frequency pass (or the path tracer) on `stream`; records ev0 / evm / ev1 of the plan
 int plan_launch_run(rt_hip_plan *p, hipStream_t stream);
-// a run that reported failing rays: repeat the frequency pass without them
+// a run that reported failing rays: repeat the frequency pass (in step mode: the step kernel) without them
 int plan_repeat_checked(rt_hip_plan *p);
 int launch_tan(const rt_ray *rays_dev, unsigned long long n, float *sxy_dev, hipStream_t stream);
 int launch_seed_tab(const rt::DevSeed &sd, const rt::DevRays &R, size_t n_points, double *sf, unsigned char *sin);

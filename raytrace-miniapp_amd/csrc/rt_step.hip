@@ -1,0 +1,427 @@
+#pragma once
+// rt_step.hip -- step mode: the arrays of the application's per-step record (intensity_step_struct,
+// src/RayTraceStructures.h:361-369) straight from the march records, without the image cube.
+//
+// What RayTraceImageCPULoop leaves in image[nx ny nv] (RayTraceImageCPU.cpp:27-69), reduced on the way:
+//   E_v[k] = sum over pixels p of image[k + nv p]            the frequency profile
+//   nf[p]  = sum over k of 2 dv[k] image[k + nv p]           the frequency-integrated near-field image
+//   I_ang                                                     as the frequency kernel leaves it
+// rt_step_kernel stands where rt_freq_kernel stands in the two-kernel run, reads the same tile-wise march records
+// (rt_device.h) and has its shape: lanes = rays, a wave owns a tile of 64 consecutive rays, VEC frequencies per step,
+// the float64 building blocks, the per-ray preamble (place_ray: seed factor, deposit cells, own-cell mode) and the
+// tile-wide choice between ase_step_f32 / ase_step / ase_update of freq_tile -- so every Iv_r[k] is the value image
+// mode computes for that ray, bit for bit, rt_hip_plan_set_exact_emission included.  Only the deposit differs:
+//   E_v   : per batch of VEC frequencies one sum over the lanes that deposit into the image (pixel valid, ray live),
+//           the wave sum of the few-runs deposit of rt_freq.hip, times scale, added to the work-group's E_v[Kp] in LDS;
+//           flushed once per work-group at the end of the launch with f64 atomics, like the I_ang histogram.  No
+//           global atomic per ray and frequency.
+//   nf    : the lane's sum over k of 2 dv[k] Iv[k] (the I_ang value) times scale, reduced over runs of lanes with
+//           equal pixel by one segmented scan per tile, one f64 global atomic per run -- a plain store where the host
+//           has proved one ray per pixel (DevParams::exclusive).
+// Nothing of nx ny nv is allocated or written.  Failing runs take the checking repeat of the frequency kernel
+// (plan_repeat_checked): FQ_SAFE_CHECK integrates without depositing and marks, FQ_SAFE_SKIP leaves the marked rays out.
+#include "rt_spec.hip" // (rt_freq.hip and spec_slot)
+#include "rt_step.h"
+
+namespace rt {
+
+#pragma clang fp contract(fast) // (the float64 half, as in rt_freq.hip)
+
+// doubles of dynamic LDS of a work-group (layout: rt_step_kernel)
+inline size_t step_lds_doubles(bool iang_in_lds, int n_ang, int Kp, int wg_waves)
+{
+    return (size_t) 2 * EXP_TAB + (iang_in_lds ? (size_t) ((n_ang + 1) & ~1) : 0) + (size_t) Kp + (size_t) wg_waves * (size_t) (4 * XP_ROW);
+}
+
+template <int SF, bool EMIS>
+__device__ __forceinline__ void step_tile(const FreqHot &H, const unsigned hflags, ColdPtr C, double *lds_iang,
+                                          double *lds_ev, const double *tab, double *xpose, const unsigned tile, const int lane)
+{
+    const int S           = SF ? SF : H.L * RT_N_SUB;
+    const int K           = H.K;
+    const int Kp          = H.Kp;
+    const unsigned n_rays = H.n_rays;
+    const unsigned ridx   = tile * WAVE + (unsigned) lane;
+    const bool have       = ridx < n_rays;
+    const bool backward   = H.method == 1;
+    const unsigned rrec      = have ? ridx : 0u;
+    const unsigned char *rec = H.rec;
+    const bool safe_check = (hflags & FQ_SAFE_CHECK) != 0, safe_skip = (hflags & FQ_SAFE_SKIP) != 0;
+    const bool probe_on   = (hflags & FQ_PROBE) != 0;
+
+    // ---- per-ray preamble: exit ray, seed factor, deposit cells (freq_tile's, load for load) ----
+    unsigned fl = 0, steps = 0;
+    rt_ray ray  = { 0, 0, 0, 0 };
+    RecMeta m   = { 0, 0, 0, 0, 1, 0 };
+    RecSlot raw[SF ? SF : 1];
+#pragma unroll
+    for (int s = 0; s < (SF ? SF : 1); s++)
+        raw[s] = RecSlot{ 0.0f, 0.0f, 0 };
+    const DevRays R     = load_cold(&C->rays);
+    const bool own      = (hflags & FQ_OWN_CELLS) != 0;
+    const bool need_ray = !own || probe_on;
+    if (have) {
+        m = *reinterpret_cast<const RecMeta *>(rec + rec_meta_off(rrec, S, H.rec_stride));
+        if (SF) {
+            const unsigned char *slot0 = rec + rec_slot_off(rrec, 0, H.rec_stride);
+#pragma unroll
+            for (int s = 0; s < SF; s++)
+                raw[s] = *reinterpret_cast<const RecSlot *>(slot0 + (size_t) s * REC_SLOT_ROW);
+        }
+        if (need_ray) {
+            float ta, tb;
+            load_ray(R, ridx, ray, ta, tb, false);
+        }
+        fl    = m.flags_steps & REC_FLAG_MASK;
+        steps = m.flags_steps >> REC_STEPS_SHIFT;
+    }
+    auto start_ray = [&]() { // the launch ray, for the failure reports
+        rt_ray r = ray;
+        if (!need_ray) {
+            float ta, tb;
+            load_ray(R, ridx, r, ta, tb, false);
+        }
+        return r;
+    };
+    const bool err1 = have && (double) (m.sz * m.sz) < 0.01; // Helper.h:515
+    double f0       = 0.0;
+    int pix = -1, ang = -1;
+    if (have && !err1) {
+        const Placed P = place_ray(hflags, C, R, H.nx, backward, ridx, m, fl, ray);
+        f0  = P.f0;
+        pix = P.pix;
+        ang = P.ang;
+    }
+    if (have && probe_on) {
+        C->probe.flags[ridx] = fl | (err1 ? F_ERR1 : 0u);
+        C->probe.steps[ridx] = steps;
+    }
+    if (err1 && !safe_skip) { // error -1: the ray is reported (once) and deposits nothing
+        atomicOr(&H.ctl->failure_code, 1u << 1);
+        unsigned slot_f = atomicAdd(&H.ctl->n_failed, 1u);
+        if (slot_f < RT_N_FAILED_MAX)
+            H.ctl->failed[slot_f] = start_ray();
+    }
+    const bool live = have && !err1 && !(fl & F_SKIP) && !(safe_skip && H.bad[ridx]);
+    if (__ballot(live) == 0ull)
+        return;
+    if (!live) {
+        pix = -1;
+        ang = -1;
+    }
+    // the pixel of this launch that only this ray deposits into (exclusive mode: the host has proved one ray per pixel)
+    int own_pix = -1;
+    if ((hflags & FQ_EXCLUSIVE) && have) {
+        const unsigned j = ridx % (unsigned) H.ny, i = ridx / (unsigned) H.ny;
+        own_pix          = (int) (i + j * (unsigned) H.nx);
+    }
+
+    // ---- the march record of this lane's ray, and the tile-wide choice of the update (as freq_tile takes it: over
+    // every lane that holds a ray, live or not -- the choice decides the arithmetic, and the arithmetic is image mode's) ----
+    float gs[SF ? SF : 1];
+    double rs[SF ? SF : 1];
+    unsigned off[SF ? SF : 1];
+    const bool exact_emis = (hflags & FQ_EXACT_EMIS) != 0;
+    bool irregular = false, big = false;
+    if (SF) {
+        const int n_done = (int) ((m.flags_steps >> REC_NDONE_SHIFT) & REC_NDONE_MASK);
+#pragma unroll
+        for (int s = 0; s < SF; s++) {
+            const bool written = backward ? s >= SF - n_done : s < n_done;
+            const RecSlot sl   = written ? raw[s] : RecSlot{ 0.0f, 0.0f, 0 };
+            gs[s]              = sl.g;
+            off[s]             = (unsigned) sl.c * (unsigned) Kp * 4u;
+            const bool regular = fabsf(gs[s]) >= RT_RS_MIN && fabsf(gs[s]) <= H.gs_cap && !exact_emis;
+            rs[s]              = regular ? div_fast((double) sl.e, (double) gs[s]) : 0.0;
+            irregular          = irregular || (!regular && (gs[s] != 0.0f || sl.e != 0.0f));
+            big                = big || !(fabsf(gs[s]) <= H.gs_cap * (80.0f / 708.0f));
+        }
+    }
+    const bool all_regular = __ballot(irregular) == 0ull;
+    const bool all_small   = all_regular && __ballot(big) == 0ull;
+    const bool gv_nan      = (hflags & FQ_GV_NAN) != 0;
+    const ConstF64 dv2     = (ConstF64) (unsigned long long) H.dv2;
+    const ConstF64 sfk     = (ConstF64) (unsigned long long) H.seed_fk;
+
+    auto load_rows = [&](FVec (&w)[SF ? SF : 1], const int kb) {
+#pragma unroll
+        for (int s = 0; s < (SF ? SF : 1); s++) {
+            const float *base = (s < RT_N_SUB ? H.gv0 : H.gv1) + kb;
+            unsigned o        = off[s];
+            asm volatile("" : "+v"(o)); // (SGPR base + 32-bit VGPR offset, see freq_tile)
+            w[s] = *reinterpret_cast<const FVec *>(reinterpret_cast<const char *>(base) + o);
+        }
+    };
+
+    double angsum = 0.0; // RayTraceImageCPU.cpp:63-68, sequential in k like the CPU
+    double iv_min = 0.0; // min over k of Iv, NaNs ignored: negative <=> error -2 (Helper.h:582-594)
+    const bool dep = pix >= 0; // this lane's ray deposits into the image
+
+    for (int kb = 0; kb < K; kb += VEC) {
+        double Iv[VEC];
+        if (EMIS) {
+#pragma unroll
+            for (int j = 0; j < VEC; j++)
+                Iv[j] = 0.0;
+            if (SF) {
+                FVec w[SF ? SF : 1];
+                load_rows(w, kb);
+                if (all_small) {
+#pragma unroll
+                    for (int s = 0; s < SF; s++)
+                        ase_step_f32(Iv, gs[s], rs[s], w[s].v, tab + EXP_TAB);
+                } else if (all_regular) {
+#pragma unroll
+                    for (int s = 0; s < SF; s++)
+                        ase_step(Iv, gs[s], rs[s], w[s].v, tab);
+                } else
+#pragma unroll
+                for (int s = 0; s < SF; s++) {
+                    if (fabsf(gs[s]) >= RT_RS_MIN && fabsf(gs[s]) <= H.gs_cap && !exact_emis) {
+                        ase_step(Iv, gs[s], rs[s], w[s].v, tab);
+                    } else {
+                        const float e1 = have ? spec_slot(rec, rrec, H.rec_stride, s, SF, m.flags_steps, backward).e : 0.0f;
+                        if (gs[s] != 0.0f || e1 != 0.0f) { // else the update is the identity
+#pragma unroll
+                            for (int j = 0; j < VEC; j++)
+                                Iv[j] = ase_update(Iv[j], gs[s], e1, w[s].v[j], tab);
+                        }
+                    }
+                }
+                if (gv_nan) {
+#pragma unroll
+                    for (int j = 0; j < VEC; j++) {
+                        bool wn = false;
+#pragma unroll
+                        for (int s = 0; s < SF; s++)
+                            wn = wn || !(fabsf(w[s].v[j]) <= FLT_MAX);
+                        Iv[j] = wn ? __builtin_nan("") : Iv[j];
+                    }
+                }
+            } else {
+                bool wnan[VEC];
+#pragma unroll
+                for (int j = 0; j < VEC; j++)
+                    wnan[j] = false;
+                for (int s = 0; s < S; s++) {
+                    const RecSlot sl = spec_slot(rec, rrec, H.rec_stride, s, S, m.flags_steps, backward);
+                    const float g1 = sl.g, e1 = sl.e;
+                    const float *row = H.gain[s / RT_N_SUB + 1].gv + (size_t) sl.c * (size_t) Kp + kb;
+                    const FVec w     = *reinterpret_cast<const FVec *>(row);
+#pragma unroll
+                    for (int j = 0; j < VEC; j++)
+                        wnan[j] = wnan[j] || !(fabsf(w.v[j]) <= FLT_MAX);
+                    if (fabsf(g1) >= RT_RS_MIN && fabsf(g1) <= H.gs_cap && !exact_emis) {
+                        const double r1 = div_fast((double) e1, (double) g1);
+                        ase_step(Iv, g1, r1, w.v, tab);
+                    } else if (g1 != 0.0f || e1 != 0.0f) {
+#pragma unroll
+                        for (int j = 0; j < VEC; j++)
+                            Iv[j] = ase_update(Iv[j], g1, e1, w.v[j], tab);
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < VEC; j++)
+                    Iv[j] = wnan[j] ? __builtin_nan("") : Iv[j];
+            }
+        } else {
+            // gain only, Helper.h:569-580: f64 products summed in sub-segment order
+            double gl[VEC];
+#pragma unroll
+            for (int j = 0; j < VEC; j++)
+                gl[j] = 0.0;
+            if (SF) {
+                FVec w[SF ? SF : 1];
+                load_rows(w, kb);
+#pragma unroll
+                for (int s = 0; s < SF; s++) {
+#pragma unroll
+                    for (int j = 0; j < VEC; j++)
+                        gl[j] += (double) gs[s] * (double) w[s].v[j];
+                }
+            } else {
+                for (int s = 0; s < S; s++) {
+                    const RecSlot sl = spec_slot(rec, rrec, H.rec_stride, s, S, m.flags_steps, backward);
+                    const float *row = H.gain[s / RT_N_SUB + 1].gv + (size_t) sl.c * (size_t) Kp + kb;
+                    const FVec w     = *reinterpret_cast<const FVec *>(row);
+#pragma unroll
+                    for (int j = 0; j < VEC; j++)
+                        gl[j] += (double) sl.g * (double) w.v[j];
+                }
+            }
+            // Iv = f0 f[4][k] exp(gl); for f0 = 0 exactly 0 unless exp overflows (0 * inf), see freq_tile
+            bool need = f0 != 0.0;
+#pragma unroll
+            for (int j = 0; j < VEC; j++)
+                need = need || gl[j] > 700.0 || gl[j] != gl[j];
+#pragma unroll
+            for (int j = 0; j < VEC; j++)
+                Iv[j] = f0 * sfk[kb + j];
+            if (__ballot(need) != 0ull) {
+                double eg[VEC];
+                exp_tab_vec(gl, tab, eg);
+#pragma unroll
+                for (int j = 0; j < VEC; j++)
+                    Iv[j] *= eg[j];
+            }
+        }
+        // (no masking of the lane's own sums, as in freq_tile: lanes without a live ray are dropped below; the padding
+        // columns K .. Kp-1 carry w = dv = 0, hence Iv = 0)
+#pragma unroll
+        for (int j = 0; j < VEC; j++) {
+            iv_min = fmin(iv_min, Iv[j]);
+            angsum += dv2[kb + j] * Iv[j]; // RayTraceImageCPU.cpp:66: (2.0 * dv) * Iv
+        }
+        if (!safe_check) { // the checking pass of a failing run integrates without depositing
+            // E_v: the wave sum of the few-runs deposit (rt_freq.hip) over the depositing lanes -- the lanes park their
+            // four values in [4][XP_ROW], lane (j, q) = (lane / 16, lane % 16) adds four neighbours of frequency j, a
+            // row_shr tree finishes the sum in lane 15 of the row; one LDS atomic per frequency and tile
+#pragma unroll
+            for (int j = 0; j < VEC; j++)
+                xpose[j * XP_ROW + lane] = dep ? Iv[j] : 0.0;
+            __builtin_amdgcn_wave_barrier();
+            const double *src = xpose + (lane >> 4) * XP_ROW + 4 * (lane & 15);
+            double t          = (src[0] + src[1]) + (src[2] + src[3]);
+            __builtin_amdgcn_wave_barrier();
+            t = dpp_step<0x111, 0xf>(t);
+            t = dpp_step<0x112, 0xf>(t);
+            t = dpp_step<0x114, 0xf>(t);
+            t = dpp_step<0x118, 0xf>(t);
+            if ((lane & 15) == 15 && t != 0.0) // (kb + 3 < Kp: the accumulator has Kp entries)
+                unsafeAtomicAdd(&lds_ev[kb + (lane >> 4)], t * H.scale); // RayTraceImageCPU.cpp:59, once per summed value
+        }
+    }
+    // a NaN intensity makes the I_ang sum NaN (Helper.h:590-593: error -3, after the sign test)
+    const bool bad_neg = iv_min < 0.0, bad_nan = angsum != angsum;
+    const bool failing = bad_neg || bad_nan;
+    if (live && failing && !safe_skip) {
+        atomicOr(&H.ctl->failure_code, bad_neg ? (1u << 2) : (1u << 3));
+        unsigned slot_f = atomicAdd(&H.ctl->n_failed, 1u);
+        if (slot_f < RT_N_FAILED_MAX)
+            H.ctl->failed[slot_f] = start_ray();
+        if (safe_check)
+            H.bad[ridx] = 1;
+    }
+    if (safe_check)
+        return;
+    // a failing ray adds nothing to I_ang (RayTraceImageCPU.cpp:29-36: `continue` before the deposit)
+    if (ang >= 0 && !failing) {
+        if (lds_iang)
+            unsafeAtomicAdd(&lds_iang[ang], angsum);
+        else
+            unsafeAtomicAdd(&H.iang[ang], angsum);
+    }
+    // nf: the same per-ray sum, scaled, summed over each run of lanes with equal pixel (the segmented scan of the
+    // seeded deposit, once per tile instead of once per frequency); the last lane of a run owns the total
+    {
+        const double mine  = (dep && !failing) ? angsum * H.scale : 0.0;
+        const int pix_prev = __shfl_up(pix, 1, WAVE);
+        const bool head    = lane == 0 || pix_prev != pix;
+        int run_start      = head ? lane : -1;
+#pragma unroll
+        for (int o = 1; o < WAVE; o <<= 1) {
+            const int t = __shfl_up(run_start, o, WAVE);
+            if (lane >= o && t > run_start)
+                run_start = t;
+        }
+        const int head_next = __shfl_down(head ? 1 : 0, 1, WAVE);
+        const bool tail     = (lane == WAVE - 1 || head_next != 0) && dep;
+        double a            = mine;
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            const double t = __shfl_up(a, 1 << i, WAVE);
+            if ((lane - (1 << i)) >= run_start)
+                a += t;
+        }
+        if (tail) {
+            // (the output pointer is read from the argument block here, behind the cold half, rather than kept across the tile)
+            double *nf_out = reinterpret_cast<const RT_CONST_AS StepOut *>(reinterpret_cast<const RT_CONST_AS char *>(C) + (offsetof(StepKArg, out) - offsetof(StepKArg, cold)))->nf;
+            if (pix == own_pix)
+                nf_out[pix] = a; // the only ray of this pixel in the launch: a run of one lane, nothing to add to
+            else if (a != 0.0)
+                unsafeAtomicAdd(&nf_out[pix], a);
+        }
+    }
+}
+
+// One work-group of FREQ_WG_WAVES waves per CU, tiles handed out from the eight sharded counters of the control block
+// exactly as rt_freq_kernel hands them out (DevCtl::next_tile_f, guided chunks for the gain-only instance).
+// LDS of a work-group, all dynamic (launch_step sizes it with step_lds_doubles):
+//   [the two exponent tables of rt_freq_kernel][I_ang histogram, na*nb doubles rounded up to even (if it fits)]
+//   [E_v accumulator, Kp doubles][per wave: the transposition rows [4][XP_ROW] of the wave sum]
+template <int SF, bool EMIS>
+__global__ void __launch_bounds__(FREQ_WG_WAVES * 64, EMIS ? RT_FREQ_WAVES : RT_FREQ_WAVES_SEED) rt_step_kernel(const StepKArg A)
+{
+    extern __shared__ __align__(16) unsigned char step_lds[];
+    const FreqHot &H       = A.hot;
+    const bool iang_in_lds = (H.flags & FQ_IANG_LDS) != 0;
+    const int n_ang        = H.n_ang;
+    double *exp2_tab       = reinterpret_cast<double *>(step_lds);
+    double *lds_iang       = iang_in_lds ? exp2_tab + 2 * EXP_TAB : nullptr;
+    double *lds_ev         = exp2_tab + 2 * EXP_TAB + (iang_in_lds ? ((n_ang + 1) & ~1) : 0);
+    double *xpose          = lds_ev + H.Kp + (size_t) (unsigned) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6)) * (size_t) (4 * XP_ROW);
+    RT_FILL_EXP_TABLES(exp2_tab)
+    if (lds_iang) {
+        for (int c = (int) threadIdx.x; c < n_ang; c += (int) blockDim.x)
+            lds_iang[c] = 0.0;
+    }
+    for (int c = (int) threadIdx.x; c < H.Kp; c += (int) blockDim.x)
+        lds_ev[c] = 0.0;
+    __syncthreads();
+    const int lane             = lane_id();
+    const unsigned n_tiles_run = H.tile_end - H.tile_begin;
+    unsigned shard = blockIdx.x & 7u, tried = 0;
+    auto shard_size = [&](unsigned sh) { return (n_tiles_run + 7u - sh) / 8u; };
+    unsigned s_n    = shard_size(shard);
+    const unsigned sh_shift = H.fetch_shift > 3 ? H.fetch_shift - 3 : 0;
+    constexpr unsigned TILES_PER_FETCH = EMIS ? FREQ_TILES_PER_FETCH_EMIS : FREQ_TILES_PER_FETCH_GAIN;
+    auto chunk_of = [&](unsigned left) {
+        const unsigned c = left >> sh_shift;
+        return c < 1u ? 1u : (c > TILES_PER_FETCH ? TILES_PER_FETCH : c);
+    };
+    unsigned tch = chunk_of(s_n);
+    // (the reservation and the walk over its tiles as two nested loops: as rt_freq_kernel's single loop with a window of
+    // reserved tiles the gain-only instance kept 48 bytes of stack for its loop state)
+    for (;;) {
+        unsigned base = 0;
+        if (lane == 0)
+            base = atomicAdd(&H.ctl->next_tile_f[H.freq_id][shard][0], tch);
+        base = (unsigned) __builtin_amdgcn_readfirstlane((int) base);
+        if (base >= s_n) { // this shard is empty: on to the next one, until all eight have been seen empty
+            if (++tried == 8)
+                break;
+            shard = (shard + 1) & 7u;
+            s_n   = shard_size(shard);
+            tch   = 1; // a guest takes single tiles
+            continue;
+        }
+        const unsigned t_end = s_n - base < tch ? s_n : base + tch;
+        tch                  = chunk_of(s_n - t_end);
+        for (unsigned t = base; t < t_end; t++) {
+            const unsigned tile = H.tile_begin + t * 8u + shard;
+            // the cold half of the argument block, the flag word and the lane number opaque per tile, as in rt_freq_kernel
+            ColdPtr C = (ColdPtr) ((const RT_CONST_AS char *) __builtin_amdgcn_kernarg_segment_ptr() + offsetof(StepKArg, cold));
+            asm volatile("" : "+s"(C));
+            unsigned hflags = H.flags;
+            int lane_t      = lane;
+            asm volatile("" : "+s"(hflags), "+v"(lane_t));
+            step_tile<SF, EMIS>(H, hflags, C, lds_iang, lds_ev, exp2_tab, xpose, tile, lane_t);
+        }
+    }
+    // the work-group's sums leave once: coalesced native f64 atomics (zeros, most of a small launch's histogram, stay)
+    __syncthreads();
+    for (int c = (int) threadIdx.x; c < H.K; c += (int) blockDim.x) {
+        const double v = lds_ev[c];
+        if (v != 0.0)
+            unsafeAtomicAdd(&A.out.E_v[c], v);
+    }
+    if (lds_iang && !(H.flags & FQ_DBG_NOFLUSH)) {
+        for (int c = (int) threadIdx.x; c < n_ang; c += (int) blockDim.x) {
+            const double v = lds_iang[c];
+            if (v != 0.0)
+                unsafeAtomicAdd(&H.iang[c], v);
+        }
+    }
+}
+
+} // namespace rt

@@ -12,6 +12,9 @@
 //   RayTraceImageHipMultiGPULoop  all devices of the node ("hip-multigpu" arm) through
 //        rt_hip_multi_image_loop: stands where the reference runs RayTraceImageThreadLoop
 //        (src/RayTraceImage.cpp:89-134) with setGPU called in the spawning thread (:116).
+//   RayTraceImageStepHipLoop      the one-device loop with the per-step record (intensity_step_struct,
+//        src/RayTraceStructures.h:361-369) in place of the image cube: E_v[nv], the frequency-integrated image[nx*ny],
+//        I_ang -- through rt_hip_step_loop
 //   RayTraceCalcRaysHip           n calls of RayTrace::calc_ray (src/RayTraceImage.cpp:189-204) in one, through
 //        rt_hip_calc_rays: per-ray spectrum, exit ray and return code
 #include "RayTrace.h"
@@ -114,6 +117,31 @@ void RayTraceImageHipLoop(int N, const RayTrace::EUV_beam_struct &beam, const Ra
                   failure_code, failed_rays, error);
     if (!error.empty())
         RAY_ERROR(error); // device/runtime errors end the process, as CUDA_CHECK does (RayTraceImageCuda.cu:8-18)
+}
+
+// The Loop signature with `double *E_v, double *nf` in place of `image`: E_v[k] = sum over pixels of image[k + nv p],
+// nf[p] = sum over k of 2 dv[k] image[k + nv p] -- the reductions of what RayTraceImageHipLoop would leave in image,
+// which is never built.  The physical normalisation constants of intensity_step_struct are the caller's to apply.
+void RayTraceImageStepHipLoop(int N, const RayTrace::EUV_beam_struct &beam, const RayTrace::ray_gain_struct *gain,
+    const RayTrace::ray_seed_struct *seed, int method, const std::vector<ray_struct> &rays, double scale,
+    double *E_v, double *nf, double *I_ang, unsigned int &failure_code, std::vector<ray_struct> &failed_rays)
+{
+    failure_code = 0;
+    Flat f       = flatten(N, beam, gain, seed);
+    rt_ray failed[RT_N_FAILED_MAX];
+    int n_failed      = 0;
+    unsigned int code = 0;
+    int rc = rt_hip_step_loop(0, N, &f.beam, f.gain.data(), f.has_seed ? &f.seed : NULL, method,
+                              rays.empty() ? NULL : reinterpret_cast<const rt_ray *>(&rays[0]), rays.size(), scale, E_v, nf,
+                              I_ang, &code, failed, RT_N_FAILED_MAX, &n_failed, &g_last_stats);
+    if (rc != RT_OK)
+        RAY_ERROR(std::string("HIP backend error: ") + rt_hip_last_error());
+    failure_code |= code;
+    for (int i = 0; i < n_failed; i++) {
+        ray_struct r;
+        memcpy(&r, &failed[i], sizeof(r));
+        failed_rays.push_back(r);
+    }
 }
 
 void RayTraceImageHipMultiGPULoop(int N, const RayTrace::EUV_beam_struct &beam,
