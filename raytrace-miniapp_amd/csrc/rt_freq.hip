@@ -387,6 +387,22 @@ template <typename T> __device__ __forceinline__ T load_cold(const RT_CONST_AS T
     return r;
 }
 
+// slot s of the record of ray ridx, zero if the ray never entered that sub-segment: rec_slot (rt_device.h) with the
+// load behind the test instead of a select between two addresses (which parks the zero slot in scratch)
+__device__ __forceinline__ RecSlot rec_slot_lazy(const unsigned char *rec, unsigned ridx, unsigned rec_stride, int s, int S, unsigned flags_steps,
+                                                 bool backward)
+{
+    const int n_done = (int) ((flags_steps >> REC_NDONE_SHIFT) & REC_NDONE_MASK);
+    RecSlot r        = { 0.0f, 0.0f, 0 };
+    if (backward ? s >= S - n_done : s < n_done) {
+        const float *q = reinterpret_cast<const float *>(rec + rec_slot_off(ridx, s, rec_stride));
+        r.g            = q[0];
+        r.e            = q[1];
+        r.c            = reinterpret_cast<const int *>(q)[2];
+    }
+    return r;
+}
+
 // Where a ray deposits and what it starts with -- the per-ray part of the frequency pass that does not depend on
 // the frequency (Helper.h:518-533, RayTraceImageCPU.cpp:37-54): exit angles, seed factor, the four deposit cells.
 // (Round 4 ran it for every ray of a launch in a pass of its own before the frequency kernel, result left in the
@@ -481,7 +497,6 @@ __device__ __forceinline__ void freq_tile(const FreqHot &H, const unsigned hflag
     // (records are tile-wise, rt_device.h: slot s of the 64 lanes is one contiguous run)
     const unsigned rrec      = have ? ridx : 0u;
     const unsigned char *rec = H.rec;
-    constexpr bool use_emis = EMIS; // Helper.h:402, fixed per kernel instance (see launch_freq)
     const bool safe_check = (hflags & FQ_SAFE_CHECK) != 0, safe_skip = (hflags & FQ_SAFE_SKIP) != 0;
     const bool probe_on   = (hflags & FQ_PROBE) != 0;
 
@@ -491,43 +506,12 @@ __device__ __forceinline__ void freq_tile(const FreqHot &H, const unsigned hflag
     // is made of once the frequency loop is fast (measured: 0.50 of 1.00 ms with the loop compiled out): so every
     // load that does not depend on another is issued up front -- the whole record (meta + slots) here -- and the
     // dependent rounds are as few as the mode allows (own-cell rays: none; otherwise one for the deposit cells).
-    unsigned fl = 0, steps = 0;
-    rt_ray ray  = { 0, 0, 0, 0 };
-    RecMeta m   = { 0, 0, 0, 0, 1, 0 };
-    RecSlot raw[SF ? SF : 1]; // slots as stored; those the ray never entered are masked with n_done below
-#pragma unroll
-    for (int s = 0; s < (SF ? SF : 1); s++)
-        raw[s] = RecSlot{ 0.0f, 0.0f, 0 };
-    const DevRays R = load_cold(&C->rays);
     // own-cell rays (FQ_OWN_CELLS): backward method, the rays are the beam's own grid points and the host has
     // verified that grid point i lands in deposit cell i on all four axes (grid_points_in_own_cells, the CPU's
     // getIndex on the very float the ray carries): pixel and angle cell ARE the grid indices of the ray
-    const bool own = (hflags & FQ_OWN_CELLS) != 0;
-    const bool need_ray = !own || probe_on; // (a failing own-cell ray loads its start ray when it is reported)
-    if (have) {
-        m = *reinterpret_cast<const RecMeta *>(rec + rec_meta_off(rrec, S, H.rec_stride));
-        if (SF) {
-            const unsigned char *slot0 = rec + rec_slot_off(rrec, 0, H.rec_stride);
-#pragma unroll
-            for (int s = 0; s < SF; s++)
-                raw[s] = *reinterpret_cast<const RecSlot *>(slot0 + (size_t) s * REC_SLOT_ROW);
-        }
-        if (need_ray) {
-            float ta, tb;
-            load_ray(R, ridx, ray, ta, tb, false);
-        }
-        fl    = m.flags_steps & REC_FLAG_MASK;
-        steps = m.flags_steps >> REC_STEPS_SHIFT;
-    }
-    auto start_ray = [&]() { // the launch ray, for the failure reports
-        rt_ray r = ray;
-        if (!need_ray) {
-            float ta, tb;
-            load_ray(R, ridx, r, ta, tb, false);
-        }
-        return r;
-    };
-    bool err1   = have && (double) (m.sz * m.sz) < 0.01; // Helper.h:515
+#define TILE_NEED_RAY (!(hflags & FQ_OWN_CELLS) || probe_on) // (a failing own-cell ray loads its start ray when it is reported)
+#include "rt_tile_ray.inc"
+#undef TILE_NEED_RAY
     double f0   = 0.0;
     int pix = -1, ang = -1;
     if (have && !err1) {
@@ -540,12 +524,8 @@ __device__ __forceinline__ void freq_tile(const FreqHot &H, const unsigned hflag
         C->probe.flags[ridx] = fl | (err1 ? F_ERR1 : 0u);
         C->probe.steps[ridx] = steps;
     }
-    if (err1 && !safe_skip && k0 == 0) { // error -1: the ray is reported (once) and deposits nothing
-        atomicOr(&H.ctl->failure_code, 1u << 1);
-        unsigned slot_f = atomicAdd(&H.ctl->n_failed, 1u);
-        if (slot_f < RT_N_FAILED_MAX)
-            H.ctl->failed[slot_f] = start_ray();
-    }
+    if (err1 && !safe_skip && k0 == 0) // error -1: the ray is reported (once) and deposits nothing
+        report_failure(1u << 1);
     const bool live = have && !err1 && !(fl & F_SKIP) && !(safe_skip && H.bad[ridx]);
     // exclusive mode: this ray is the only contributor of pixel own_pix and must write its
     // whole row (zeros if it contributes nothing); a ray that deposits elsewhere (never the
@@ -596,73 +576,15 @@ __device__ __forceinline__ void freq_tile(const FreqHot &H, const unsigned hflag
     }
 
     // ---- the march record of this lane's ray ---------------------------------------
-    // off[s]: byte offset of the lineshape row of sub-segment s inside its length's table (32 bits:
-    // rt_hip_plan_create refuses tables of 4 GiB), so that a row load is SGPR base + VGPR offset
-    float gs[SF ? SF : 1];
-    double rs[SF ? SF : 1]; // es/gs, the source function of the sub-segment (see ase_step)
-    unsigned off[SF ? SF : 1];
-    const bool exact_emis = (hflags & FQ_EXACT_EMIS) != 0;
-    bool irregular = false;
-    if (SF) {
-        const int n_done = (int) ((m.flags_steps >> REC_NDONE_SHIFT) & REC_NDONE_MASK);
-#pragma unroll
-        for (int s = 0; s < SF; s++) {
-            // (rec_slot's rule on the slots loaded up front: only the first n_done in marching order were written)
-            const bool written = backward ? s >= SF - n_done : s < n_done;
-            const RecSlot sl   = written ? raw[s] : RecSlot{ 0.0f, 0.0f, 0 };
-            gs[s]              = sl.g;
-            const float e1   = sl.e;
-            off[s]           = (unsigned) sl.c * (unsigned) Kp * 4u;
-            // regular: the source-function form (ase_step) takes this sub-segment; not when the gain
-            // sum is tiny or NaN, and never in the exact mode (rt_hip_plan_set_exact_emission), which
-            // runs the CPU's own formula with its per-frequency division throughout
-            // (|gs| <= gs_cap keeps |gs * gv| <= 708 for every lineshape value; NaN fails both tests)
-            const bool regular = fabsf(gs[s]) >= RT_RS_MIN && fabsf(gs[s]) <= H.gs_cap && !exact_emis;
-            rs[s]              = regular ? div_fast((double) e1, (double) gs[s]) : 0.0;
-            // (a sub-segment with both sums zero is the identity either way: x = 0, e^x - 1 = 0)
-            irregular = irregular || (!regular && (gs[s] != 0.0f || e1 != 0.0f));
-        }
-    }
-    // no such sub-segment in the whole tile (the rule): the six updates of a frequency batch run
-    // as one straight-line block, so the table reads of one overlap the arithmetic of another
-    const bool all_regular = __ballot(irregular) == 0ull;
-    // ... and every |gs w| of the tile stays below 80 (the rule as well): the float32 range reduction (ase_step_f32)
-    bool big = false;
-    if (SF) {
-#pragma unroll
-        for (int s = 0; s < SF; s++)
-            big = big || !(fabsf(gs[s]) <= H.gs_cap * (80.0f / 708.0f));
-    }
-#ifdef RT_FREQ_NO_F32
-    const bool all_small = false;
-#else
-    const bool all_small = all_regular && __ballot(big) == 0ull;
-#endif
-    // a NaN or an infinity among the lineshape values (the CPU's 0 * NaN, 0 * inf and inf / inf: every one of them
-    // leaves Iv = NaN, Helper.h:549-557) is tested per frequency only when the host scan of the tables found one
-    const bool gv_nan = (hflags & FQ_GV_NAN) != 0;
+#define TILE_MASK true
+#include "rt_tile_rec.inc"
+#undef TILE_MASK
 
     double angsum = 0.0; // RayTraceImageCPU.cpp:63-68, sequential in k like the CPU
     double iv_min = 0.0; // min over k of Iv, NaNs ignored: negative <=> error -2 (Helper.h:582-594)
     double *img_row = H.image + (size_t) (pix >= 0 ? pix : 0) * (size_t) K;
     const ConstF64 dv2 = (ConstF64) (unsigned long long) H.dv2;      // wave-uniform reads: scalar loads
     const ConstF64 sfk = (ConstF64) (unsigned long long) H.seed_fk;
-
-    // row of sub-segment s, frequencies kb .. kb+3 (SF: the tables of lengths 1 and 2 are kernel arguments)
-    auto load_rows = [&](FVec (&w)[SF ? SF : 1], const int kb) {
-#pragma unroll
-        for (int s = 0; s < (SF ? SF : 1); s++) {
-            const float *base = (s < RT_N_SUB ? H.gv0 : H.gv1) + kb;
-            // (opaque here, so that the zero-extension of the offset stays beside the load and the
-            // instruction selector finds the SGPR-base + 32-bit-VGPR-offset form)
-            unsigned o = off[s];
-            asm volatile("" : "+v"(o));
-#ifdef RT_ABL_NOLOAD
-            o &= 15u;
-#endif
-            w[s] = *reinterpret_cast<const FVec *>(reinterpret_cast<const char *>(base) + o);
-        }
-    };
 
     // The frequency loop, instantiated once per deposit mode (exclusive / few runs / row
     // cache / segmented scan) so that each instance keeps only its own deposit state in
@@ -687,114 +609,11 @@ __device__ __forceinline__ void freq_tile(const FreqHot &H, const unsigned hflag
 #endif
         for (int kb = kb_first; kb < K_loop; kb += VEC) {
             double Iv[VEC];
-            if (use_emis) {
-#pragma unroll
-                for (int j = 0; j < VEC; j++)
-                    Iv[j] = 0.0;
-                if (SF) {
-                    FVec w[SF ? SF : 1];
-                    load_rows(w, kb);
-                    if (all_small) {
-#pragma unroll
-                        for (int s = 0; s < SF; s++)
-                            ase_step_f32(Iv, gs[s], rs[s], w[s].v, tab + EXP_TAB);
-                    } else if (all_regular) {
-#pragma unroll
-                        for (int s = 0; s < SF; s++)
-                            ase_step(Iv, gs[s], rs[s], w[s].v, tab);
-                    } else
-#pragma unroll
-                    for (int s = 0; s < SF; s++) {
-                        if (fabsf(gs[s]) >= RT_RS_MIN && fabsf(gs[s]) <= H.gs_cap && !exact_emis) {
-                            ase_step(Iv, gs[s], rs[s], w[s].v, tab);
-                        } else {
-                            const float e1 = rec_slot(rec, rrec, H.rec_stride, s, SF, m.flags_steps, backward).e;
-                            if (gs[s] != 0.0f || e1 != 0.0f) { // else the update is the identity
-#pragma unroll
-                                for (int j = 0; j < VEC; j++)
-                                    Iv[j] = ase_update(Iv[j], gs[s], e1, w[s].v[j], tab);
-                            }
-                        }
-                    }
-                    if (gv_nan) {
-#pragma unroll
-                        for (int j = 0; j < VEC; j++) {
-                            bool wn = false;
-#pragma unroll
-                            for (int s = 0; s < SF; s++)
-                                wn = wn || !(fabsf(w[s].v[j]) <= FLT_MAX);
-                            Iv[j] = wn ? __builtin_nan("") : Iv[j];
-                        }
-                    }
-                } else {
-                    bool wnan[VEC]; // a NaN or infinity anywhere in this frequency's lineshape values (0 * NaN on the CPU)
-#pragma unroll
-                    for (int j = 0; j < VEC; j++)
-                        wnan[j] = false;
-                    for (int s = 0; s < S; s++) {
-                        const RecSlot sl = rec_slot(rec, rrec, H.rec_stride, s, S, m.flags_steps, backward);
-                        const float g1 = sl.g, e1 = sl.e;
-                        const int c1   = sl.c;
-                        const float *row  = H.gain[s / RT_N_SUB + 1].gv + (size_t) c1 * (size_t) Kp + kb;
-                        const FVec w = *reinterpret_cast<const FVec *>(row);
-#pragma unroll
-                        for (int j = 0; j < VEC; j++)
-                            wnan[j] = wnan[j] || !(fabsf(w.v[j]) <= FLT_MAX);
-                        if (fabsf(g1) >= RT_RS_MIN && fabsf(g1) <= H.gs_cap && !exact_emis) {
-                            const double r1 = div_fast((double) e1, (double) g1);
-                            ase_step(Iv, g1, r1, w.v, tab);
-                        } else if (g1 != 0.0f || e1 != 0.0f) {
-#pragma unroll
-                            for (int j = 0; j < VEC; j++)
-                                Iv[j] = ase_update(Iv[j], g1, e1, w.v[j], tab);
-                        }
-                    }
-#pragma unroll
-                    for (int j = 0; j < VEC; j++)
-                        Iv[j] = wnan[j] ? __builtin_nan("") : Iv[j];
-                }
-            } else {
-                // gain only, Helper.h:569-580: f64 products summed in sub-segment order
-                double gl[VEC];
-#pragma unroll
-                for (int j = 0; j < VEC; j++)
-                    gl[j] = 0.0;
-                if (SF) {
-                    FVec w[SF ? SF : 1];
-                    load_rows(w, kb);
-#pragma unroll
-                    for (int s = 0; s < SF; s++) {
-#pragma unroll
-                        for (int j = 0; j < VEC; j++)
-                            gl[j] += (double) gs[s] * (double) w[s].v[j];
-                    }
-                } else {
-                    for (int s = 0; s < S; s++) {
-                        const RecSlot sl = rec_slot(rec, rrec, H.rec_stride, s, S, m.flags_steps, backward);
-                        const float *row = H.gain[s / RT_N_SUB + 1].gv + (size_t) sl.c * (size_t) Kp + kb;
-                        const FVec w     = *reinterpret_cast<const FVec *>(row);
-#pragma unroll
-                        for (int j = 0; j < VEC; j++)
-                            gl[j] += (double) sl.g * (double) w.v[j];
-                    }
-                }
-                // Iv = f0 f[4][k] exp(gl); for f0 = 0 that is exactly 0 unless exp overflows (0 * inf):
-                // a wave none of whose lanes needs the exponential skips it
-                bool need = f0 != 0.0;
-#pragma unroll
-                for (int j = 0; j < VEC; j++)
-                    need = need || gl[j] > 700.0 || gl[j] != gl[j];
-#pragma unroll
-                for (int j = 0; j < VEC; j++)
-                    Iv[j] = f0 * sfk[kb + j];
-                if (__ballot(need) != 0ull) {
-                    double eg[VEC];
-                    exp_tab_vec(gl, tab, eg);
-#pragma unroll
-                    for (int j = 0; j < VEC; j++)
-                        Iv[j] *= eg[j];
-                }
-            }
+#define TILE_READ_SLOT rec_slot
+#define TILE_REREAD true
+#include "rt_tile_batch.inc"
+#undef TILE_READ_SLOT
+#undef TILE_REREAD
             // No masking here: lanes without a live ray sit in runs of pixel -1, which no deposit
             // mode flushes, and their error flags and I_ang sum are dropped below; the padding
             // columns K .. Kp-1 carry w = dv = 0, hence Iv = 0 (deposits test k < K themselves).
@@ -981,10 +800,7 @@ __device__ __forceinline__ void freq_tile(const FreqHot &H, const unsigned hflag
     // a NaN intensity makes the I_ang sum NaN (Helper.h:590-593: error -3, after the sign test)
     const bool bad_neg = iv_min < 0.0, bad_nan = angsum != angsum;
     if (live && (bad_neg || bad_nan) && !safe_skip) {
-        atomicOr(&H.ctl->failure_code, bad_neg ? (1u << 2) : (1u << 3));
-        unsigned slot_f = atomicAdd(&H.ctl->n_failed, 1u);
-        if (slot_f < RT_N_FAILED_MAX)
-            H.ctl->failed[slot_f] = start_ray();
+        report_failure(bad_neg ? (1u << 2) : (1u << 3));
         if (safe_check)
             H.bad[ridx] = 1;
     }

@@ -5,7 +5,11 @@
 // exit ray, the seed spectrum of a seeded, non-escaped ray, the emission recurrence per sub-segment or the gain-only
 // product, then the -2 / -3 scan.  Reads the tile-wise march records (rt_device.h) as rt_freq_kernel does and has its
 // shape: lanes = rays, a wave owns a tile of 64 consecutive rays, VEC frequencies per step, the float64 building
-// blocks of rt_freq.hip (so the two modes take the same arithmetic, rt_hip_plan_set_exact_emission included).
+// blocks of rt_freq.hip.  The loads of the preamble and the failure report (rt_tile_ray.inc), the record decode with the
+// tile-wide choice of the update (rt_tile_rec.inc) and the integration of a frequency batch (rt_tile_batch.inc) are the
+// text that freq_tile includes, so the two modes take the same arithmetic, rt_hip_plan_set_exact_emission included;
+// spec_tile's own are the exit ray, its early-out rule (a tile without a live ray still writes its rows of zeros), the
+// staging and the stores, and the -2 / -3 scan.
 //
 // Outputs: Iv [n_rays][K] (row stride K, not Kp), ray2 [n_rays], err [n_rays].  No image, no I_ang, no atomics on data.
 //
@@ -34,22 +38,6 @@ typedef double f64x2s __attribute__((ext_vector_type(2)));
 #define SPEC_STORE16(src, dst) (*reinterpret_cast<f64x2s *>(dst) = *reinterpret_cast<const f64x2s *>(src))
 #endif
 
-// slot s of the record of ray ridx, zero if the ray never entered that sub-segment: rec_slot (rt_device.h) with the
-// load behind the test instead of a select between two addresses (which parks the zero slot in scratch)
-__device__ __forceinline__ RecSlot spec_slot(const unsigned char *rec, unsigned ridx, unsigned rec_stride, int s, int S, unsigned flags_steps,
-                                             bool backward)
-{
-    const int n_done = (int) ((flags_steps >> REC_NDONE_SHIFT) & REC_NDONE_MASK);
-    RecSlot r        = { 0.0f, 0.0f, 0 };
-    if (backward ? s >= S - n_done : s < n_done) {
-        const float *q = reinterpret_cast<const float *>(rec + rec_slot_off(ridx, s, rec_stride));
-        r.g            = q[0];
-        r.e            = q[1];
-        r.c            = reinterpret_cast<const int *>(q)[2];
-    }
-    return r;
-}
-
 template <int SF, bool EMIS>
 __device__ __forceinline__ void spec_tile(const FreqHot &H, const unsigned hflags, ColdPtr C, const SpecOut &O, const double *tab,
                                           double *stage, const unsigned tile, const int lane)
@@ -68,42 +56,9 @@ __device__ __forceinline__ void spec_tile(const FreqHot &H, const unsigned hflag
     const bool seeded     = (hflags & FQ_HAS_SEED) != 0;
 
     // ---- per-ray preamble: record, -1 test, exit ray, seed factor (Helper.h:514-533) ----
-    unsigned fl = 0;
-    rt_ray ray  = { 0, 0, 0, 0 };
-    RecMeta m   = { 0, 0, 0, 0, 1, 0 };
-    RecSlot raw[SF ? SF : 1];
-#pragma unroll
-    for (int s = 0; s < (SF ? SF : 1); s++)
-        raw[s] = RecSlot{ 0.0f, 0.0f, 0 };
-    const DevRays R     = load_cold(&C->rays);
-    const bool need_ray = seeded && !backward; // the forward seed is taken at the launch ray
-    if (have) {
-        m = *reinterpret_cast<const RecMeta *>(rec + rec_meta_off(rrec, S, H.rec_stride));
-        if (SF) {
-            const unsigned char *slot0 = rec + rec_slot_off(rrec, 0, H.rec_stride);
-#pragma unroll
-            for (int s = 0; s < SF; s++)
-                raw[s] = *reinterpret_cast<const RecSlot *>(slot0 + (size_t) s * REC_SLOT_ROW);
-        }
-        if (need_ray) {
-            float ta, tb;
-            load_ray(R, ridx, ray, ta, tb, false);
-        }
-        fl = m.flags_steps & REC_FLAG_MASK;
-    }
-    auto report = [&](const unsigned bit) { // failure code and the first failing launch rays, as the image path reports them
-        atomicOr(&H.ctl->failure_code, 1u << bit);
-        const unsigned slot_f = atomicAdd(&H.ctl->n_failed, 1u);
-        if (slot_f < RT_N_FAILED_MAX) {
-            rt_ray r = ray;
-            if (!need_ray) {
-                float ta, tb;
-                load_ray(R, ridx, r, ta, tb, false);
-            }
-            H.ctl->failed[slot_f] = r;
-        }
-    };
-    const bool err1 = have && (double) (m.sz * m.sz) < 0.01; // Helper.h:515
+#define TILE_NEED_RAY (seeded && !backward) // the forward seed is taken at the launch ray
+#include "rt_tile_ray.inc"
+#undef TILE_NEED_RAY
     rt_ray r2       = { 0.0f, 0.0f, 0.0f, 0.0f };            // (the reference leaves ray2 untouched on error -1: zeros here)
     double f0       = 0.0;
     if (have && !err1) {
@@ -121,49 +76,20 @@ __device__ __forceinline__ void spec_tile(const FreqHot &H, const unsigned hflag
         if (probe_on) {
             C->probe.ray2[ridx]  = r2;
             C->probe.flags[ridx] = fl | (err1 ? F_ERR1 : 0u);
-            C->probe.steps[ridx] = m.flags_steps >> REC_STEPS_SHIFT;
+            C->probe.steps[ridx] = steps;
         }
     }
     if (err1)
-        report(1);
+        report_failure(1u << 1);
     // a ray with error -1, and one whose every update is the identity (F_SKIP), gets a row of zeros
     const bool live     = have && !err1 && !(fl & F_SKIP);
     const bool any_live = __ballot(live) != 0ull;
 
-    // ---- the march record of this lane's ray (as freq_tile keeps it) ----
-    float gs[SF ? SF : 1];
-    double rs[SF ? SF : 1];
-    unsigned off[SF ? SF : 1];
-    const bool exact_emis = (hflags & FQ_EXACT_EMIS) != 0;
-    bool irregular = false, big = false;
-    if (SF) {
-        const int n_done = (int) ((m.flags_steps >> REC_NDONE_SHIFT) & REC_NDONE_MASK);
-#pragma unroll
-        for (int s = 0; s < SF; s++) {
-            const bool written = live && (backward ? s >= SF - n_done : s < n_done);
-            const RecSlot sl   = written ? raw[s] : RecSlot{ 0.0f, 0.0f, 0 };
-            gs[s]              = sl.g;
-            off[s]             = (unsigned) sl.c * (unsigned) Kp * 4u;
-            const bool regular = fabsf(gs[s]) >= RT_RS_MIN && fabsf(gs[s]) <= H.gs_cap && !exact_emis;
-            rs[s]              = regular ? div_fast((double) sl.e, (double) gs[s]) : 0.0;
-            irregular          = irregular || (!regular && (gs[s] != 0.0f || sl.e != 0.0f));
-            big                = big || !(fabsf(gs[s]) <= H.gs_cap * (80.0f / 708.0f));
-        }
-    }
-    const bool all_regular = __ballot(irregular) == 0ull;
-    const bool all_small   = all_regular && __ballot(big) == 0ull;
-    const bool gv_nan      = (hflags & FQ_GV_NAN) != 0;
-    const ConstF64 sfk     = (ConstF64) (unsigned long long) H.seed_fk;
-
-    auto load_rows = [&](FVec (&w)[SF ? SF : 1], const int kb) {
-#pragma unroll
-        for (int s = 0; s < (SF ? SF : 1); s++) {
-            const float *base = (s < RT_N_SUB ? H.gv0 : H.gv1) + kb;
-            unsigned o        = off[s];
-            asm volatile("" : "+v"(o)); // (SGPR base + 32-bit VGPR offset, see freq_tile)
-            w[s] = *reinterpret_cast<const FVec *>(reinterpret_cast<const char *>(base) + o);
-        }
-    };
+    // ---- the march record of this lane's ray, the slots of a lane without a live ray zeroed ----
+#define TILE_MASK live
+#include "rt_tile_rec.inc"
+#undef TILE_MASK
+    const ConstF64 sfk = (ConstF64) (unsigned long long) H.seed_fk;
 
     double iv_min = 0.0;   // min over k of Iv, NaNs ignored: negative <=> error -2
     bool has_nan  = false; // error -3 unless -2 (Helper.h:588-593: negative wins)
@@ -175,110 +101,12 @@ __device__ __forceinline__ void spec_tile(const FreqHot &H, const unsigned hflag
 #pragma unroll
         for (int j = 0; j < VEC; j++)
             Iv[j] = 0.0;
-        if (!any_live) {
-            // nothing to integrate: the rows are zeros
-        } else if (EMIS) {
-            if (SF) {
-                FVec w[SF ? SF : 1];
-                load_rows(w, kb);
-                if (all_small) {
-#pragma unroll
-                    for (int s = 0; s < SF; s++)
-                        ase_step_f32(Iv, gs[s], rs[s], w[s].v, tab + EXP_TAB);
-                } else if (all_regular) {
-#pragma unroll
-                    for (int s = 0; s < SF; s++)
-                        ase_step(Iv, gs[s], rs[s], w[s].v, tab);
-                } else
-#pragma unroll
-                for (int s = 0; s < SF; s++) {
-                    if (fabsf(gs[s]) >= RT_RS_MIN && fabsf(gs[s]) <= H.gs_cap && !exact_emis) {
-                        ase_step(Iv, gs[s], rs[s], w[s].v, tab);
-                    } else {
-                        const float e1 = live ? spec_slot(rec, rrec, H.rec_stride, s, SF, m.flags_steps, backward).e : 0.0f;
-                        if (gs[s] != 0.0f || e1 != 0.0f) { // else the update is the identity
-#pragma unroll
-                            for (int j = 0; j < VEC; j++)
-                                Iv[j] = ase_update(Iv[j], gs[s], e1, w[s].v[j], tab);
-                        }
-                    }
-                }
-                if (gv_nan) {
-#pragma unroll
-                    for (int j = 0; j < VEC; j++) {
-                        bool wn = false;
-#pragma unroll
-                        for (int s = 0; s < SF; s++)
-                            wn = wn || !(fabsf(w[s].v[j]) <= FLT_MAX);
-                        Iv[j] = wn ? __builtin_nan("") : Iv[j];
-                    }
-                }
-            } else {
-                bool wnan[VEC];
-#pragma unroll
-                for (int j = 0; j < VEC; j++)
-                    wnan[j] = false;
-                for (int s = 0; s < S; s++) {
-                    const RecSlot sl = spec_slot(rec, rrec, H.rec_stride, s, S, m.flags_steps, backward);
-                    const float g1 = sl.g, e1 = sl.e;
-                    const float *row = H.gain[s / RT_N_SUB + 1].gv + (size_t) sl.c * (size_t) Kp + kb;
-                    const FVec w     = *reinterpret_cast<const FVec *>(row);
-#pragma unroll
-                    for (int j = 0; j < VEC; j++)
-                        wnan[j] = wnan[j] || !(fabsf(w.v[j]) <= FLT_MAX);
-                    if (fabsf(g1) >= RT_RS_MIN && fabsf(g1) <= H.gs_cap && !exact_emis) {
-                        const double r1 = div_fast((double) e1, (double) g1);
-                        ase_step(Iv, g1, r1, w.v, tab);
-                    } else if (g1 != 0.0f || e1 != 0.0f) {
-#pragma unroll
-                        for (int j = 0; j < VEC; j++)
-                            Iv[j] = ase_update(Iv[j], g1, e1, w.v[j], tab);
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < VEC; j++)
-                    Iv[j] = wnan[j] ? __builtin_nan("") : Iv[j];
-            }
-        } else {
-            // gain only, Helper.h:569-580: f64 products summed in sub-segment order
-            double gl[VEC];
-#pragma unroll
-            for (int j = 0; j < VEC; j++)
-                gl[j] = 0.0;
-            if (SF) {
-                FVec w[SF ? SF : 1];
-                load_rows(w, kb);
-#pragma unroll
-                for (int s = 0; s < SF; s++) {
-#pragma unroll
-                    for (int j = 0; j < VEC; j++)
-                        gl[j] += (double) gs[s] * (double) w[s].v[j];
-                }
-            } else {
-                for (int s = 0; s < S; s++) {
-                    const RecSlot sl = spec_slot(rec, rrec, H.rec_stride, s, S, m.flags_steps, backward);
-                    const float *row = H.gain[s / RT_N_SUB + 1].gv + (size_t) sl.c * (size_t) Kp + kb;
-                    const FVec w     = *reinterpret_cast<const FVec *>(row);
-#pragma unroll
-                    for (int j = 0; j < VEC; j++)
-                        gl[j] += (double) sl.g * (double) w.v[j];
-                }
-            }
-            // Iv = f0 f[4][k] exp(gl); for f0 = 0 exactly 0 unless exp overflows (0 * inf), see freq_tile
-            bool need = f0 != 0.0;
-#pragma unroll
-            for (int j = 0; j < VEC; j++)
-                need = need || gl[j] > 700.0 || gl[j] != gl[j];
-#pragma unroll
-            for (int j = 0; j < VEC; j++)
-                Iv[j] = f0 * sfk[kb + j];
-            if (__ballot(need) != 0ull) {
-                double eg[VEC];
-                exp_tab_vec(gl, tab, eg);
-#pragma unroll
-                for (int j = 0; j < VEC; j++)
-                    Iv[j] *= eg[j];
-            }
+        if (any_live) { // (else nothing to integrate: the rows are zeros)
+#define TILE_READ_SLOT rec_slot_lazy
+#define TILE_REREAD live
+#include "rt_tile_batch.inc"
+#undef TILE_READ_SLOT
+#undef TILE_REREAD
         }
         // ---- scan (Helper.h:582-587) and staging: the lane's four values into its staging row ----
         double *mine = stage + lane * XS_ROW + (kb & 12);
@@ -328,7 +156,7 @@ __device__ __forceinline__ void spec_tile(const FreqHot &H, const unsigned hflag
     if (have)
         O.err[ridx] = err1 ? -1 : (bad_neg ? -2 : (bad_nan ? -3 : 0));
     if (bad_neg || bad_nan)
-        report(bad_neg ? 2u : 3u);
+        report_failure(bad_neg ? (1u << 2) : (1u << 3));
 }
 
 // One work-group of FREQ_WG_WAVES waves per CU, tiles handed out from the eight sharded counters of the control block

@@ -8,9 +8,11 @@
 //   I_ang                                                     as the frequency kernel leaves it
 // rt_step_kernel stands where rt_freq_kernel stands in the two-kernel run, reads the same tile-wise march records
 // (rt_device.h) and has its shape: lanes = rays, a wave owns a tile of 64 consecutive rays, VEC frequencies per step,
-// the float64 building blocks, the per-ray preamble (place_ray: seed factor, deposit cells, own-cell mode) and the
-// tile-wide choice between ase_step_f32 / ase_step / ase_update of freq_tile -- so every Iv_r[k] is the value image
-// mode computes for that ray, bit for bit, rt_hip_plan_set_exact_emission included.  Only the deposit differs:
+// the float64 building blocks.  The per-ray preamble (rt_tile_ray.inc, then place_ray: seed factor, deposit cells,
+// own-cell mode), the record decode with the tile-wide choice between ase_step_f32 / ase_step / ase_update
+// (rt_tile_rec.inc) and the integration of a frequency batch (rt_tile_batch.inc) are the text that freq_tile includes
+// -- so every Iv_r[k] is the value image mode computes for that ray, bit for bit, rt_hip_plan_set_exact_emission
+// included.  Only the early-out rule and the deposit are step_tile's own:
 //   E_v   : per batch of VEC frequencies one sum over the lanes that deposit into the image (pixel valid, ray live),
 //           the wave sum of the few-runs deposit of rt_freq.hip, times scale, added to the work-group's E_v[Kp] in LDS;
 //           flushed once per work-group at the end of the launch with f64 atomics, like the I_ang histogram.  No
@@ -20,7 +22,7 @@
 //           has proved one ray per pixel (DevParams::exclusive).
 // Nothing of nx ny nv is allocated or written.  Failing runs take the checking repeat of the frequency kernel
 // (plan_repeat_checked): FQ_SAFE_CHECK integrates without depositing and marks, FQ_SAFE_SKIP leaves the marked rays out.
-#include "rt_spec.hip" // (rt_freq.hip and spec_slot)
+#include "rt_spec.hip" // (and rt_freq.hip through it)
 #include "rt_step.h"
 
 namespace rt {
@@ -49,41 +51,10 @@ __device__ __forceinline__ void step_tile(const FreqHot &H, const unsigned hflag
     const bool safe_check = (hflags & FQ_SAFE_CHECK) != 0, safe_skip = (hflags & FQ_SAFE_SKIP) != 0;
     const bool probe_on   = (hflags & FQ_PROBE) != 0;
 
-    // ---- per-ray preamble: exit ray, seed factor, deposit cells (freq_tile's, load for load) ----
-    unsigned fl = 0, steps = 0;
-    rt_ray ray  = { 0, 0, 0, 0 };
-    RecMeta m   = { 0, 0, 0, 0, 1, 0 };
-    RecSlot raw[SF ? SF : 1];
-#pragma unroll
-    for (int s = 0; s < (SF ? SF : 1); s++)
-        raw[s] = RecSlot{ 0.0f, 0.0f, 0 };
-    const DevRays R     = load_cold(&C->rays);
-    const bool own      = (hflags & FQ_OWN_CELLS) != 0;
-    const bool need_ray = !own || probe_on;
-    if (have) {
-        m = *reinterpret_cast<const RecMeta *>(rec + rec_meta_off(rrec, S, H.rec_stride));
-        if (SF) {
-            const unsigned char *slot0 = rec + rec_slot_off(rrec, 0, H.rec_stride);
-#pragma unroll
-            for (int s = 0; s < SF; s++)
-                raw[s] = *reinterpret_cast<const RecSlot *>(slot0 + (size_t) s * REC_SLOT_ROW);
-        }
-        if (need_ray) {
-            float ta, tb;
-            load_ray(R, ridx, ray, ta, tb, false);
-        }
-        fl    = m.flags_steps & REC_FLAG_MASK;
-        steps = m.flags_steps >> REC_STEPS_SHIFT;
-    }
-    auto start_ray = [&]() { // the launch ray, for the failure reports
-        rt_ray r = ray;
-        if (!need_ray) {
-            float ta, tb;
-            load_ray(R, ridx, r, ta, tb, false);
-        }
-        return r;
-    };
-    const bool err1 = have && (double) (m.sz * m.sz) < 0.01; // Helper.h:515
+    // ---- per-ray preamble: exit ray, seed factor, deposit cells (image mode's: rt_tile_ray.inc, place_ray) ----
+#define TILE_NEED_RAY (!(hflags & FQ_OWN_CELLS) || probe_on)
+#include "rt_tile_ray.inc"
+#undef TILE_NEED_RAY
     double f0       = 0.0;
     int pix = -1, ang = -1;
     if (have && !err1) {
@@ -96,12 +67,8 @@ __device__ __forceinline__ void step_tile(const FreqHot &H, const unsigned hflag
         C->probe.flags[ridx] = fl | (err1 ? F_ERR1 : 0u);
         C->probe.steps[ridx] = steps;
     }
-    if (err1 && !safe_skip) { // error -1: the ray is reported (once) and deposits nothing
-        atomicOr(&H.ctl->failure_code, 1u << 1);
-        unsigned slot_f = atomicAdd(&H.ctl->n_failed, 1u);
-        if (slot_f < RT_N_FAILED_MAX)
-            H.ctl->failed[slot_f] = start_ray();
-    }
+    if (err1 && !safe_skip) // error -1: the ray is reported (once) and deposits nothing
+        report_failure(1u << 1);
     const bool live = have && !err1 && !(fl & F_SKIP) && !(safe_skip && H.bad[ridx]);
     if (__ballot(live) == 0ull)
         return;
@@ -116,42 +83,13 @@ __device__ __forceinline__ void step_tile(const FreqHot &H, const unsigned hflag
         own_pix          = (int) (i + j * (unsigned) H.nx);
     }
 
-    // ---- the march record of this lane's ray, and the tile-wide choice of the update (as freq_tile takes it: over
-    // every lane that holds a ray, live or not -- the choice decides the arithmetic, and the arithmetic is image mode's) ----
-    float gs[SF ? SF : 1];
-    double rs[SF ? SF : 1];
-    unsigned off[SF ? SF : 1];
-    const bool exact_emis = (hflags & FQ_EXACT_EMIS) != 0;
-    bool irregular = false, big = false;
-    if (SF) {
-        const int n_done = (int) ((m.flags_steps >> REC_NDONE_SHIFT) & REC_NDONE_MASK);
-#pragma unroll
-        for (int s = 0; s < SF; s++) {
-            const bool written = backward ? s >= SF - n_done : s < n_done;
-            const RecSlot sl   = written ? raw[s] : RecSlot{ 0.0f, 0.0f, 0 };
-            gs[s]              = sl.g;
-            off[s]             = (unsigned) sl.c * (unsigned) Kp * 4u;
-            const bool regular = fabsf(gs[s]) >= RT_RS_MIN && fabsf(gs[s]) <= H.gs_cap && !exact_emis;
-            rs[s]              = regular ? div_fast((double) sl.e, (double) gs[s]) : 0.0;
-            irregular          = irregular || (!regular && (gs[s] != 0.0f || sl.e != 0.0f));
-            big                = big || !(fabsf(gs[s]) <= H.gs_cap * (80.0f / 708.0f));
-        }
-    }
-    const bool all_regular = __ballot(irregular) == 0ull;
-    const bool all_small   = all_regular && __ballot(big) == 0ull;
-    const bool gv_nan      = (hflags & FQ_GV_NAN) != 0;
-    const ConstF64 dv2     = (ConstF64) (unsigned long long) H.dv2;
-    const ConstF64 sfk     = (ConstF64) (unsigned long long) H.seed_fk;
-
-    auto load_rows = [&](FVec (&w)[SF ? SF : 1], const int kb) {
-#pragma unroll
-        for (int s = 0; s < (SF ? SF : 1); s++) {
-            const float *base = (s < RT_N_SUB ? H.gv0 : H.gv1) + kb;
-            unsigned o        = off[s];
-            asm volatile("" : "+v"(o)); // (SGPR base + 32-bit VGPR offset, see freq_tile)
-            w[s] = *reinterpret_cast<const FVec *>(reinterpret_cast<const char *>(base) + o);
-        }
-    };
+    // ---- the march record of this lane's ray, and the tile-wide choice of the update: image mode's, over every
+    // lane that holds a ray ----
+#define TILE_MASK true
+#include "rt_tile_rec.inc"
+#undef TILE_MASK
+    const ConstF64 dv2 = (ConstF64) (unsigned long long) H.dv2;
+    const ConstF64 sfk = (ConstF64) (unsigned long long) H.seed_fk;
 
     double angsum = 0.0; // RayTraceImageCPU.cpp:63-68, sequential in k like the CPU
     double iv_min = 0.0; // min over k of Iv, NaNs ignored: negative <=> error -2 (Helper.h:582-594)
@@ -159,113 +97,12 @@ __device__ __forceinline__ void step_tile(const FreqHot &H, const unsigned hflag
 
     for (int kb = 0; kb < K; kb += VEC) {
         double Iv[VEC];
-        if (EMIS) {
-#pragma unroll
-            for (int j = 0; j < VEC; j++)
-                Iv[j] = 0.0;
-            if (SF) {
-                FVec w[SF ? SF : 1];
-                load_rows(w, kb);
-                if (all_small) {
-#pragma unroll
-                    for (int s = 0; s < SF; s++)
-                        ase_step_f32(Iv, gs[s], rs[s], w[s].v, tab + EXP_TAB);
-                } else if (all_regular) {
-#pragma unroll
-                    for (int s = 0; s < SF; s++)
-                        ase_step(Iv, gs[s], rs[s], w[s].v, tab);
-                } else
-#pragma unroll
-                for (int s = 0; s < SF; s++) {
-                    if (fabsf(gs[s]) >= RT_RS_MIN && fabsf(gs[s]) <= H.gs_cap && !exact_emis) {
-                        ase_step(Iv, gs[s], rs[s], w[s].v, tab);
-                    } else {
-                        const float e1 = have ? spec_slot(rec, rrec, H.rec_stride, s, SF, m.flags_steps, backward).e : 0.0f;
-                        if (gs[s] != 0.0f || e1 != 0.0f) { // else the update is the identity
-#pragma unroll
-                            for (int j = 0; j < VEC; j++)
-                                Iv[j] = ase_update(Iv[j], gs[s], e1, w[s].v[j], tab);
-                        }
-                    }
-                }
-                if (gv_nan) {
-#pragma unroll
-                    for (int j = 0; j < VEC; j++) {
-                        bool wn = false;
-#pragma unroll
-                        for (int s = 0; s < SF; s++)
-                            wn = wn || !(fabsf(w[s].v[j]) <= FLT_MAX);
-                        Iv[j] = wn ? __builtin_nan("") : Iv[j];
-                    }
-                }
-            } else {
-                bool wnan[VEC];
-#pragma unroll
-                for (int j = 0; j < VEC; j++)
-                    wnan[j] = false;
-                for (int s = 0; s < S; s++) {
-                    const RecSlot sl = spec_slot(rec, rrec, H.rec_stride, s, S, m.flags_steps, backward);
-                    const float g1 = sl.g, e1 = sl.e;
-                    const float *row = H.gain[s / RT_N_SUB + 1].gv + (size_t) sl.c * (size_t) Kp + kb;
-                    const FVec w     = *reinterpret_cast<const FVec *>(row);
-#pragma unroll
-                    for (int j = 0; j < VEC; j++)
-                        wnan[j] = wnan[j] || !(fabsf(w.v[j]) <= FLT_MAX);
-                    if (fabsf(g1) >= RT_RS_MIN && fabsf(g1) <= H.gs_cap && !exact_emis) {
-                        const double r1 = div_fast((double) e1, (double) g1);
-                        ase_step(Iv, g1, r1, w.v, tab);
-                    } else if (g1 != 0.0f || e1 != 0.0f) {
-#pragma unroll
-                        for (int j = 0; j < VEC; j++)
-                            Iv[j] = ase_update(Iv[j], g1, e1, w.v[j], tab);
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < VEC; j++)
-                    Iv[j] = wnan[j] ? __builtin_nan("") : Iv[j];
-            }
-        } else {
-            // gain only, Helper.h:569-580: f64 products summed in sub-segment order
-            double gl[VEC];
-#pragma unroll
-            for (int j = 0; j < VEC; j++)
-                gl[j] = 0.0;
-            if (SF) {
-                FVec w[SF ? SF : 1];
-                load_rows(w, kb);
-#pragma unroll
-                for (int s = 0; s < SF; s++) {
-#pragma unroll
-                    for (int j = 0; j < VEC; j++)
-                        gl[j] += (double) gs[s] * (double) w[s].v[j];
-                }
-            } else {
-                for (int s = 0; s < S; s++) {
-                    const RecSlot sl = spec_slot(rec, rrec, H.rec_stride, s, S, m.flags_steps, backward);
-                    const float *row = H.gain[s / RT_N_SUB + 1].gv + (size_t) sl.c * (size_t) Kp + kb;
-                    const FVec w     = *reinterpret_cast<const FVec *>(row);
-#pragma unroll
-                    for (int j = 0; j < VEC; j++)
-                        gl[j] += (double) sl.g * (double) w.v[j];
-                }
-            }
-            // Iv = f0 f[4][k] exp(gl); for f0 = 0 exactly 0 unless exp overflows (0 * inf), see freq_tile
-            bool need = f0 != 0.0;
-#pragma unroll
-            for (int j = 0; j < VEC; j++)
-                need = need || gl[j] > 700.0 || gl[j] != gl[j];
-#pragma unroll
-            for (int j = 0; j < VEC; j++)
-                Iv[j] = f0 * sfk[kb + j];
-            if (__ballot(need) != 0ull) {
-                double eg[VEC];
-                exp_tab_vec(gl, tab, eg);
-#pragma unroll
-                for (int j = 0; j < VEC; j++)
-                    Iv[j] *= eg[j];
-            }
-        }
-        // (no masking of the lane's own sums, as in freq_tile: lanes without a live ray are dropped below; the padding
+#define TILE_READ_SLOT rec_slot_lazy
+#define TILE_REREAD have
+#include "rt_tile_batch.inc"
+#undef TILE_READ_SLOT
+#undef TILE_REREAD
+        // (no masking of the lane's own sums, as in image mode: lanes without a live ray are dropped below; the padding
         // columns K .. Kp-1 carry w = dv = 0, hence Iv = 0)
 #pragma unroll
         for (int j = 0; j < VEC; j++) {
@@ -295,10 +132,7 @@ __device__ __forceinline__ void step_tile(const FreqHot &H, const unsigned hflag
     const bool bad_neg = iv_min < 0.0, bad_nan = angsum != angsum;
     const bool failing = bad_neg || bad_nan;
     if (live && failing && !safe_skip) {
-        atomicOr(&H.ctl->failure_code, bad_neg ? (1u << 2) : (1u << 3));
-        unsigned slot_f = atomicAdd(&H.ctl->n_failed, 1u);
-        if (slot_f < RT_N_FAILED_MAX)
-            H.ctl->failed[slot_f] = start_ray();
+        report_failure(bad_neg ? (1u << 2) : (1u << 3));
         if (safe_check)
             H.bad[ridx] = 1;
     }
