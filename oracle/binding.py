@@ -59,6 +59,14 @@ class Oracle:
             C.c_size_t, cabi.c_float_p, P(C.c_int32)]
         L.rt_oracle_calc_ray_path.restype = C.c_int
 
+        L.rt_oracle_calc_seed.argtypes = [P(cabi.RtSeed), C.c_size_t, cabi.c_double_p, cabi.c_double_p, cabi.c_double_p]
+        L.rt_oracle_calc_seed.restype = C.c_int
+
+    def calc_seed(self, seed, pts):
+        """seed_intensity at the points pts [n][4] = (x, y, a, b) -> dict(Iv [n][dim[4]], axis [n][4]: pchip_eval of each
+        coordinate on its own axis, in range or not)."""
+        return _calc_seed(self.lib.rt_oracle_calc_seed, seed, pts)
+
     def image_loop(self, problem, rays=None, n_threads: int = 1):
         """Returns dict(image, I_ang, failure_code, failed_rays, counters, seconds)."""
         m = cabi.Marshalled(problem)
@@ -149,6 +157,34 @@ class Oracle:
         return dict(x=path[:, :, 0].copy(), y=path[:, :, 1].copy(), I=path[:, :, 2].copy(), err=err)
 
 
+def seed_record(seed):
+    """(RtSeed, the arrays it points into) of a problem.Seed."""
+    x = [np.ascontiguousarray(v, dtype=np.float64) for v in seed.x]
+    f = [np.ascontiguousarray(v, dtype=np.float64) for v in seed.f]
+    rec = cabi.RtSeed()
+    for i in range(5):
+        assert len(x[i]) == len(f[i]) >= 2
+        rec.dim[i] = len(x[i])
+        rec.x[i] = cabi._dp(x[i])
+        rec.f[i] = cabi._dp(f[i])
+    rec.f0 = float(seed.f0)
+    return rec, (x, f)
+
+
+def _calc_seed(fn, seed, pts):
+    rec, keep = seed_record(seed)
+    pts = np.ascontiguousarray(pts, dtype=np.float64)
+    assert pts.ndim == 2 and pts.shape[1] == 4
+    n = pts.shape[0]
+    Iv = np.zeros((n, rec.dim[4]))
+    axis = np.zeros((n, 4))
+    rc = fn(C.byref(rec), n, cabi._dp(pts), cabi._dp(Iv), cabi._dp(axis))
+    if rc != 0:
+        raise RuntimeError(f"calc_seed failed: {rc}")
+    del keep
+    return dict(Iv=Iv, axis=axis)
+
+
 class Reference:
     """The compiled, unmodified reference CPU path (None-safe: `available()`)."""
 
@@ -179,6 +215,14 @@ class Reference:
         L.ref_calc_ray_path_file.argtypes = [C.c_char_p, P(C.c_int), P(C.c_int), C.c_double, cabi.c_float_p,
                                              cabi.c_float_p, cabi.c_float_p]
         L.ref_calc_ray_path_file.restype = C.c_int
+
+    def calc_seed(self, seed, pts):
+        """RayTrace::calc_seed (src/RayTrace.h:85) at the points pts [n][4] -> dict(Iv [n][dim[4]], axis [n][4]: the
+        interpolant of RayTraceImageHelper.h of each coordinate on its own axis)."""
+        L = self.lib
+        L.ref_calc_seed.argtypes = [P(cabi.RtSeed), C.c_size_t, cabi.c_double_p, cabi.c_double_p, cabi.c_double_p]
+        L.ref_calc_seed.restype = C.c_int
+        return _calc_seed(L.ref_calc_seed, seed, pts)
 
     def scale_file(self, path, scale: float) -> dict:
         """The reference's scale_problem (src/CreateImageHelpers.cpp:104-150) applied to a .dat file: the grids it leaves

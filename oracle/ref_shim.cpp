@@ -14,6 +14,8 @@
  *   RayTrace::create_image    (src/RayTraceImage.cpp:227)
  *   create_image_struct::unpack (src/RayTraceStructures.cpp:2224)
  *   scale_problem             (src/CreateImageHelpers.cpp:144)
+ *   RayTrace::calc_seed       (src/RayTrace.h:85)
+ *   interp_pchip              (src/common/RayTraceImageHelper.h:168, the one calc_seed evaluates)
  */
 #include "RayTrace.h"
 #include "common/RayTraceImageHelper.h"
@@ -314,6 +316,24 @@ int ref_calc_ray_path_file(const char *path, const int *i0, const int *n, double
     memcpy(Ir, vi.data(), vi.size() * sizeof(float));
     free_info(info);
     return nerr;
+}
+
+/* RayTrace::calc_seed on a caller-owned seed at n points pts [n][4] = (x, y, a, b): Iv_out [n][dim[4]].  axis_out
+ * [n][4] (may be NULL): the interpolant of RayTraceImageHelper.h -- the global one, not interp::interp_pchip of
+ * AtomicModel/interp.cpp -- of each coordinate on its own axis, in range or not. */
+int ref_calc_seed(const rt_seed *seed, size_t n, const double *pts, double *Iv_out, double *axis_out)
+{
+    RayTrace::ray_seed_struct sd;
+    attach(sd, seed);
+    for (size_t r = 0; r < n; r++) {
+        const double *p = pts + 4 * r;
+        RayTrace::calc_seed(sd, p[0], p[1], p[2], p[3], Iv_out + r * (size_t) seed->dim[4]);
+        if (axis_out)
+            for (int d = 0; d < 4; d++)
+                axis_out[4 * r + d] = ::interp_pchip((size_t) seed->dim[d], seed->x[d], seed->f[d], p[d]);
+    }
+    detach(sd);
+    return 0;
 }
 
 } // extern "C"

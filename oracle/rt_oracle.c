@@ -151,6 +151,23 @@ static void seed_intensity(const rt_seed *sd, double x, double y, double a, doub
         Iv[k] = f * sd->f[4][k];
 }
 
+/* The seed evaluation on its own, for tests that pin it against RayTrace::calc_seed on profiles of their
+ * choosing: Iv [n][dim[4]] of seed_intensity at the points pts [n][4] = (x, y, a, b); axis [n][4] (may be NULL)
+ * receives pchip_eval of each coordinate on its own axis, in range or not. */
+int rt_oracle_calc_seed(const rt_seed *seed, size_t n, const double *pts, double *Iv, double *axis)
+{
+    if (!seed || !pts || !Iv)
+        return -1;
+    for (size_t r = 0; r < n; r++) {
+        const double *p = pts + 4 * r;
+        seed_intensity(seed, p[0], p[1], p[2], p[3], Iv + r * (size_t) seed->dim[4]);
+        if (axis)
+            for (int d = 0; d < 4; d++)
+                axis[4 * r + d] = pchip_eval((size_t) seed->dim[d], seed->x[d], seed->f[d], p[d]);
+    }
+    return 0;
+}
+
 /* Helper.h:270-313 -- adaptive 2nd-order Taylor steps in a linear-index
  * medium n = n0 + gx*x + gy*y; returns the path length, displacement in *r. */
 static float step_linear_medium(vec3f *r, vec3f *s, float n0, float gx, float gy,

@@ -47,6 +47,8 @@ int rt_oracle_calc_ray_path(int N, const rt_beam *beam, const rt_gain *gain, con
                             int method, float c, const rt_ray *rays, size_t n_rays, float *path,
                             int32_t *err);
 
+int rt_oracle_calc_seed(const rt_seed *seed, size_t n, const double *pts, double *Iv, double *axis);
+
 #ifdef __cplusplus
 }
 #endif

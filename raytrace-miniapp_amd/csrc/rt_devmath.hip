@@ -1,6 +1,7 @@
-// rt_devmath.hip -- test-only unit: the float64 building blocks of the frequency pass (rt_freq.hip) and the two float
-// kernels of the march (rt_march.hip), each behind one elementwise kernel, so that tests/test_gpu_devmath.py can run
-// them on a device on inputs of its own choosing.  Builds to librt_hip_devmath.so with the product's flags; nothing
+// rt_devmath.hip -- test-only unit: the float64 building blocks of the frequency pass (rt_freq.hip), the two float
+// kernels of the march (rt_march.hip) and the seed-profile interpolation (pchip_eval / seed_factor of rt_math.h, and
+// rt_seed_tab_kernel itself), each behind one elementwise kernel, so that tests/test_gpu_devmath.py and
+// tests/test_gpu_seed_profiles.py can run them on a device on inputs of their own choosing.  Builds to librt_hip_devmath.so with the product's flags; nothing
 // of it is linked into librt_hip.so.
 //
 // The C face takes host arrays and gives host arrays: every call allocates, copies, launches, synchronises and
@@ -147,6 +148,21 @@ __global__ void __launch_bounds__(DM_BLOCK) dm_tan_kernel(int which, const float
         out[i] = which == DM_TAN ? tanf_flt32_kernel(x[i]) : atanf_flt32_kernel(x[i]);
 }
 
+// the seed profile (rt_math.h): one axis' interpolant; the whole factor at points [m][4] = (x, y, a, b)
+__global__ void __launch_bounds__(DM_BLOCK) dm_pchip_kernel(int n, const double *xs, const double *ys, const double *x, double *y, size_t m)
+{
+    const size_t stride = (size_t) gridDim.x * blockDim.x;
+    for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < m; i += stride)
+        y[i] = pchip_eval(n, xs, ys, x[i]);
+}
+
+__global__ void __launch_bounds__(DM_BLOCK) dm_seed_factor_kernel(const DevSeed sd, const double *pts, double *f, size_t m)
+{
+    const size_t stride = (size_t) gridDim.x * blockDim.x;
+    for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < m; i += stride)
+        f[i] = seed_factor(sd, pts[4 * i + 0], pts[4 * i + 1], pts[4 * i + 2], pts[4 * i + 3]);
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------
 // device buffers of one call: freed when the call returns, whatever it returns
 struct Bufs {
@@ -208,6 +224,35 @@ int finish(void *host, const void *dev, size_t bytes)
     DM_TRY(hipDeviceSynchronize());
     if (bytes)
         DM_TRY(hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the four axes of a seed profile in ONE device buffer [x0 | f0 | x1 | f1 | ...]; the frequency axis stays empty (neither
+// seed_factor nor rt_seed_tab_kernel reads it)
+int seed_tables(Bufs &B, DevSeed &sd, const int *dim, const double *const *xs, const double *const *fs, double f0)
+{
+    size_t total = 0;
+    for (int d = 0; d < 4; d++) {
+        if (dim[d] < 2 || !xs[d] || !fs[d])
+            return (int) hipErrorInvalidValue;
+        total += 2 * (size_t) dim[d];
+    }
+    double *tab;
+    DM_TRY(B.out((void **) &tab, total * sizeof(double)));
+    size_t at = 0;
+    for (int d = 0; d < 4; d++) {
+        const size_t bytes = (size_t) dim[d] * sizeof(double);
+        DM_TRY(hipMemcpy(tab + at, xs[d], bytes, hipMemcpyHostToDevice));
+        DM_TRY(hipMemcpy(tab + at + dim[d], fs[d], bytes, hipMemcpyHostToDevice));
+        sd.x[d]   = tab + at;
+        sd.f[d]   = tab + at + dim[d];
+        sd.dim[d] = dim[d];
+        at += 2 * (size_t) dim[d];
+    }
+    sd.x[4] = sd.f[4] = nullptr;
+    sd.dim[4]         = 0;
+    sd.pad            = 0;
+    sd.f0             = f0;
     return 0;
 }
 
@@ -323,4 +368,82 @@ DM_API int rt_devmath_tan(int which, const float *x, float *out, size_t n)
     DM_TRY(B.out((void **) &dout, n * sizeof(float)));
     dm_tan_kernel<<<grid_for(n), DM_BLOCK>>>(which, dx, dout, n);
     return B.release(finish(out, dout, n * sizeof(float)));
+}
+
+// one axis of a seed profile: xs, ys [n], n >= 2; x, y [m]
+DM_API int rt_devmath_pchip(int n, const double *xs, const double *ys, const double *x, double *y, size_t m)
+{
+    Bufs B;
+    double *dxs, *dys, *dx, *dy;
+    if (n < 2)
+        return (int) hipErrorInvalidValue;
+    DM_TRY(B.in((void **) &dxs, xs, (size_t) n * sizeof(double)));
+    DM_TRY(B.in((void **) &dys, ys, (size_t) n * sizeof(double)));
+    DM_TRY(B.in((void **) &dx, x, m * sizeof(double)));
+    DM_TRY(B.out((void **) &dy, m * sizeof(double)));
+    dm_pchip_kernel<<<grid_for(m), DM_BLOCK>>>(n, dxs, dys, dx, dy, m);
+    return B.release(finish(y, dy, m * sizeof(double)));
+}
+
+// the four axes xs[d], fs[d] [dim[d]], dim[d] >= 2; pts [m][4]; f [m]
+DM_API int rt_devmath_seed_factor(const int *dim, const double *const *xs, const double *const *fs, double f0, const double *pts,
+                                  double *f, size_t m)
+{
+    Bufs B;
+    DevSeed sd;
+    double *dpts, *df;
+    const int st = seed_tables(B, sd, dim, xs, fs, f0);
+    if (st)
+        return st;
+    DM_TRY(B.in((void **) &dpts, pts, m * 4 * sizeof(double)));
+    DM_TRY(B.out((void **) &df, m * sizeof(double)));
+    dm_seed_factor_kernel<<<grid_for(m), DM_BLOCK>>>(sd, dpts, df, m);
+    return B.release(finish(f, df, m * sizeof(double)));
+}
+
+// rt_seed_tab_kernel of rt_march.hip, unchanged, on a DevRays made of the four grids g[a] [n_grid[a]], n_grid[a] >= 1:
+// sf, sin [n_grid[0] + ... + n_grid[3]].  n_blocks = 0: as many work-groups as the product launches, one thread per
+// entry; otherwise that many, so that fewer of them walk the entries in the kernel's grid-stride loop
+DM_API int rt_devmath_seed_tab(const int *dim, const double *const *xs, const double *const *fs, double f0, const int *n_grid,
+                               const double *const *g, unsigned n_blocks, double *sf, unsigned char *sin)
+{
+    Bufs B;
+    DevSeed sd;
+    const int st = seed_tables(B, sd, dim, xs, fs, f0);
+    if (st)
+        return st;
+    size_t nn = 0;
+    for (int a = 0; a < 4; a++) {
+        if (n_grid[a] < 1 || !g[a])
+            return (int) hipErrorInvalidValue;
+        nn += (size_t) n_grid[a];
+    }
+    if (nn > (size_t) 1 << 24)
+        return (int) hipErrorInvalidValue;
+    double *dg, *dsf;
+    unsigned char *dsin;
+    DM_TRY(B.out((void **) &dg, nn * sizeof(double)));
+    DevRays R = {};
+    const double **slot[4] = { &R.gx, &R.gy, &R.ga, &R.gb };
+    size_t at = 0;
+    for (int a = 0; a < 4; a++) {
+        DM_TRY(hipMemcpy(dg + at, g[a], (size_t) n_grid[a] * sizeof(double), hipMemcpyHostToDevice));
+        *slot[a] = dg + at;
+        at += (size_t) n_grid[a];
+    }
+    R.ngx = n_grid[0];
+    R.ngy = n_grid[1];
+    R.nga = n_grid[2];
+    R.ngb = n_grid[3];
+    DM_TRY(B.out((void **) &dsf, nn * sizeof(double)));
+    DM_TRY(B.out((void **) &dsin, nn));
+    DM_TRY(hipMemset(dsf, 0xff, nn * sizeof(double))); // (an entry the kernel leaves out reads as NaN / 255)
+    DM_TRY(hipMemset(dsin, 0xff, nn));
+    const unsigned blocks = n_blocks ? n_blocks : (unsigned) ((nn + 255) / 256);
+    rt::rt_seed_tab_kernel<<<blocks, 256>>>(sd, R, dsf, dsin);
+    const int rc = finish(sf, dsf, nn * sizeof(double));
+    if (rc)
+        return B.release(rc);
+    DM_TRY(hipMemcpy(sin, dsin, nn, hipMemcpyDeviceToHost));
+    return B.release(0);
 }

@@ -2,7 +2,8 @@
 
   Ref      tests/devmath_ref.c compiled with the host `cc -O2 -ffp-contract=off`: the restatement of exp_tab, exp_tab_vec,
            ase_step, ase_step_f32 and ase_update (tables handed in), and loops over the host libm's tanf / atanf
-  Device   ctypes binding of csrc/librt_hip_devmath.so (rt_devmath.hip): the same functions on a device.  Load it only
+  Device   ctypes binding of csrc/librt_hip_devmath.so (rt_devmath.hip): the same functions on a device, and the seed-profile
+           interpolation (pchip, seed_factor, seed_tab: tests/test_gpu_seed_profiles.py).  Load it only
            after the `hip` fixture of conftest.py has brought torch in -- one HIP runtime per process
   the high-precision reference: numpy.longdouble (>= 64 significand bits, asserted) exp / expm1, guarded by a cross-check
            of a 2 000-point subsample against mpmath (or the stdlib decimal module at 40 digits)
@@ -161,8 +162,12 @@ class Device:
         L.rt_devmath_div.argtypes = [_PD, _PD, _PD, sz]
         L.rt_devmath_deposit.argtypes = [ci, pi, ctypes.POINTER(_PD), _PD, _PD, pi, sz]
         L.rt_devmath_tan.argtypes = [ci, _PF, _PF, sz]
+        ppd = ctypes.POINTER(_PD)
+        L.rt_devmath_pchip.argtypes = [ci, _PD, _PD, _PD, _PD, sz]
+        L.rt_devmath_seed_factor.argtypes = [pi, ppd, ppd, ctypes.c_double, _PD, _PD, sz]
+        L.rt_devmath_seed_tab.argtypes = [pi, ppd, ppd, ctypes.c_double, pi, ppd, ctypes.c_uint, _PD, ctypes.POINTER(ctypes.c_ubyte)]
         for f in (L.rt_devmath_tables, L.rt_devmath_exp, L.rt_devmath_update, L.rt_devmath_step, L.rt_devmath_div,
-                  L.rt_devmath_deposit, L.rt_devmath_tan):
+                  L.rt_devmath_deposit, L.rt_devmath_tan, L.rt_devmath_pchip, L.rt_devmath_seed_factor, L.rt_devmath_seed_tab):
             f.restype = ci
         assert L.rt_devmath_vec() == VEC
 
@@ -224,6 +229,47 @@ class Device:
         out = np.empty_like(x)
         self._check(self.lib.rt_devmath_tan(which, _ptr(x, ctypes.c_float), _ptr(out, ctypes.c_float), x.size), "rt_devmath_tan")
         return out
+
+    def pchip(self, xs, ys, x):
+        """pchip_eval (csrc/rt_math.h) of one axis xs, ys [n >= 2] at x [m]."""
+        xs, ys, x = _f64(xs), _f64(ys), _f64(x)
+        assert xs.ndim == 1 and xs.size == ys.size >= 2
+        y = np.empty_like(x)
+        self._check(self.lib.rt_devmath_pchip(xs.size, _ptr(xs, ctypes.c_double), _ptr(ys, ctypes.c_double), _ptr(x, ctypes.c_double),
+                                              _ptr(y, ctypes.c_double), x.size), "rt_devmath_pchip")
+        return y
+
+    @staticmethod
+    def _seed_args(seed):
+        xs, fs = [_f64(seed.x[d]) for d in range(4)], [_f64(seed.f[d]) for d in range(4)]
+        assert all(a.ndim == 1 and a.size == b.size >= 2 for a, b in zip(xs, fs))
+        dim = (ctypes.c_int * 4)(*[a.size for a in xs])
+        return dim, (_PD * 4)(*[_ptr(a, ctypes.c_double) for a in xs]), (_PD * 4)(*[_ptr(a, ctypes.c_double) for a in fs]), (xs, fs)
+
+    def seed_factor(self, seed, pts):
+        """seed_factor (csrc/rt_math.h) of a Seed (its four spatial axes and f0) at pts [m][4] = (x, y, a, b) -> f [m]."""
+        dim, px, pf, keep = self._seed_args(seed)
+        pts = _f64(pts)
+        assert pts.ndim == 2 and pts.shape[1] == 4
+        f = np.empty(pts.shape[0], np.float64)
+        self._check(self.lib.rt_devmath_seed_factor(dim, px, pf, float(seed.f0), _ptr(pts, ctypes.c_double), _ptr(f, ctypes.c_double),
+                                                    pts.shape[0]), "rt_devmath_seed_factor")
+        return f
+
+    def seed_tab(self, seed, grids, n_blocks=0):
+        """rt_seed_tab_kernel (csrc/rt_march.hip) on the four ray grids -> (sf, sin), each [n0 + n1 + n2 + n3]: the per-axis
+        factor at every grid value rounded to float, and whether it lies inside the profile.  n_blocks = 0: the product's
+        launch, one thread per entry; otherwise that many work-groups of 256 (fewer: the kernel's grid-stride loop)."""
+        dim, px, pf, keep = self._seed_args(seed)
+        grids = [_f64(g) for g in grids]
+        assert len(grids) == 4 and all(g.ndim == 1 and g.size >= 1 for g in grids)
+        n_grid = (ctypes.c_int * 4)(*[g.size for g in grids])
+        gp = (_PD * 4)(*[_ptr(g, ctypes.c_double) for g in grids])
+        nn = sum(g.size for g in grids)
+        sf, sin = np.empty(nn, np.float64), np.empty(nn, np.uint8)
+        self._check(self.lib.rt_devmath_seed_tab(dim, px, pf, float(seed.f0), n_grid, gp, n_blocks, _ptr(sf, ctypes.c_double),
+                                                 _ptr(sin, ctypes.c_ubyte)), "rt_devmath_seed_tab")
+        return sf, sin
 
 
 # ------------------------------------------------------------------------------------------------ tables

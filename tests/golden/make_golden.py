@@ -18,6 +18,8 @@ Writes, for each shipped input (ASE_small, seed_small):
                          boundary) on a small sub-grid, step factors 0.5 and 0.25
 and ASE_small_ref_slice.npz: image / I_ang of the reference's CPU loop
 (RayTraceImageCPULoop) on the ray list 100000 ... 139999 of ASE_small.
+and seed_profiles_ref.npz (main_seed_profiles): RayTrace::calc_seed and the interpolant it evaluates on the crafted seed
+profiles of tests/seed_profiles.py, and RayTraceImageCPULoop on one 450-ray problem that carries such a profile.
 Only data is stored -- no reference source text in any encoding.
 """
 import hashlib
@@ -115,7 +117,38 @@ def main_scaled_and_sliced():
           f"reference {r['seconds']:.1f} s in {len(r['slices'])} slices")
 
 
+def main_seed_profiles():
+    """seed_profiles_ref.npz: for every profile of tests/seed_profiles.py its tables (<name>.x0 .. x4, .f0 .. f4, .scale =
+    seed.f0), the query points (<name>.pts [n][4]), the reference's RayTrace::calc_seed there (<name>.Iv [n][3]) and the
+    interpolant of RayTraceImageHelper.h of each coordinate on its own axis (<name>.axis [n][4]); and the image / I_ang
+    of RayTraceImageCPULoop on the end-to-end case E2E_STORED (450 rays).  Byte for byte the same on every run: no time
+    stamps (numpy writes none), fixed pseudo-random points."""
+    sys.path.insert(0, str(ROOT / "tests"))
+    import seed_profiles as sp
+    build(ref=True)
+    ref = Reference()
+    data = {"names": np.array(list(sp.profiles()))}
+    for name, seed in sp.profiles().items():
+        pts = sp.points(seed)
+        r = ref.calc_seed(seed, pts)
+        for d in range(5):
+            data[f"{name}.x{d}"], data[f"{name}.f{d}"] = seed.x[d], seed.f[d]
+        data[f"{name}.scale"] = np.float64(seed.f0)
+        data[f"{name}.pts"], data[f"{name}.Iv"], data[f"{name}.axis"] = pts, r["Iv"], r["axis"]
+        print(f"profile {name}: {len(pts)} points, {int(np.count_nonzero(r['Iv'][:, 0]))} with a non-zero factor")
+    p = sp.e2e_problem(rt.datfile.load(OUT / "seed_small.dat.xz"), sp.E2E_STORED)
+    s = ref.cpu_loop(p, p.build_rays())
+    assert s["failure_code"] == 0 and s["image"].any()
+    data["e2e.case"], data["e2e.image"], data["e2e.I_ang"] = np.array(sp.E2E_STORED), s["image"], s["I_ang"]
+    np.savez_compressed(OUT / "seed_profiles_ref.npz", **data)
+    print(f"seed_profiles_ref.npz: {(OUT / 'seed_profiles_ref.npz').stat().st_size} bytes")
+
+
 if __name__ == "__main__":
+    if "--seed-profiles" in sys.argv:
+        main_seed_profiles()
+        sys.exit(0)
     if "--scaled" not in sys.argv:
         main()
     main_scaled_and_sliced()
+    main_seed_profiles()
