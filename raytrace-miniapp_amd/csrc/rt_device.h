@@ -216,10 +216,7 @@ struct DevParams {
     // (RayTraceImageCPU.cpp:29-36); after the repeat so does this image.  0 = the normal pass.
     unsigned int safe;
     unsigned int park; // march: lanes that must wait for block [A] before it runs (rt_march.hip); 1 = every iteration
-    // march, express waves (rt_march.hip): a wave that holds a ray older than express_age loop iterations raises its
-    // wave priority (0 = never); with express_hold it also fetches no further rays from the launch's counters while it
-    // holds such a ray, so that it thins out and its iterations get shorter
-    unsigned int express_age, express_hold, express_park, express_tail;
+    unsigned int pad_march[4]; // (unused; kept because the register allocation of the kernels depends on the layout of this block)
     // the last late_chunks chunks of a march launch are handed out to the first late_waves waves of each work-group only
     // (rt_march.hip, "The end of a launch"); 0: no such zone
     unsigned int late_chunks, late_waves, late_first; // late_first: the first of those waves (the first MARCHING wave of a work-group)
@@ -255,10 +252,7 @@ enum : unsigned {
 // Waves per work-group of the frequency kernel.  One 16-wave work-group per CU (four waves per SIMD, what the
 // registers allow) instead of four 4-wave ones: one I_ang histogram and one pair of exponent tables per CU in LDS,
 // and a quarter of the atomics when the histograms are added to the result at the end of the launch.
-#ifndef RT_FREQ_WG_WAVES
-#define RT_FREQ_WG_WAVES 16
-#endif
-constexpr int FREQ_WG_WAVES = RT_FREQ_WG_WAVES;
+constexpr int FREQ_WG_WAVES = 16;
 struct FreqHot {
     const float *gv0, *gv1; // SF == 6 (N = 3): lineshape tables of lengths 1 and 2, rows of Kp floats
     const DevGain *gain;    // any N: [N] lineshape pointers, entry 0 unused

@@ -24,23 +24,15 @@
 
 namespace rt {
 
-#ifndef RT_FREQ_WAVES_SEED
-#define RT_FREQ_WAVES_SEED 4 // the gain-only instance keeps far less per-lane state
-#endif
-#ifndef RT_FREQ_WAVES
-#define RT_FREQ_WAVES 4 // waves per SIMD of the emission instance (127 VGPRs, no scratch; 168 at 3 before the argument block was split)
-#endif
+constexpr int FREQ_WAVES_SEED = 4; // the gain-only instance keeps far less per-lane state
+constexpr int FREQ_WAVES      = 4; // waves per SIMD of the emission instance (127 VGPRs, no scratch; 168 at 3 before the argument block was split)
 
 constexpr int VEC = 4; // frequencies per lane and pass; rows are padded to a multiple (DevParams::Kp)
 // tiles a wave reserves per fetch of the tile counter, at most (see rt_freq_kernel).  With eight counters a fetch per
 // tile is affordable, and for the emission instance it is what measures best (tools/ablate_shard.py with SHARDS=...:
 // stand-in halves 0.47 against 0.52 ms, quarters 0.278 / 0.282, whole 0.865 / 0.868; config 5 at 2048^2 6.64 / 6.89 ms);
 // the gain-only instance keeps the guided chunks (seed_small 1.212 against 1.228 ms)
-#ifdef RT_FREQ_TILES_PER_FETCH
-constexpr unsigned FREQ_TILES_PER_FETCH_EMIS = RT_FREQ_TILES_PER_FETCH, FREQ_TILES_PER_FETCH_GAIN = RT_FREQ_TILES_PER_FETCH;
-#else
 constexpr unsigned FREQ_TILES_PER_FETCH_EMIS = 1, FREQ_TILES_PER_FETCH_GAIN = 8;
-#endif
 struct alignas(16) FVec { float v[VEC]; };
 
 // ---- float64 building blocks of the frequency pass ---------------------------------
@@ -358,11 +350,7 @@ constexpr int FREQ_WAVE_XPOSE = 4 * XP_ROW + FREQ_MAXQ * WAVE; // doubles per wa
 // row stride of the per-wave row cache in doubles: Kp is a multiple of 4, so rows Kp apart start 8 Kp mod 128 bytes apart
 // -- for the 84 frequencies of the seeded input every fourth row on the same LDS banks; one double more makes the
 // stride odd and spreads sixteen rows over all 32 banks (lanes of different pixels add to the same column of their rows)
-#ifdef RT_FREQ_ROW_NOPAD
-__host__ __device__ constexpr int freq_row_stride(int Kp) { return Kp; }
-#else
 __host__ __device__ constexpr int freq_row_stride(int Kp) { return Kp + 1; }
-#endif
 // doubles of dynamic LDS of a work-group (layout: rt_freq_kernel)
 inline size_t freq_lds_doubles(bool iang_in_lds, int n_ang, bool exclusive, int nslot, int Kp, int wg_waves)
 {
@@ -600,9 +588,6 @@ __device__ __forceinline__ void freq_tile(const FreqHot &H, const unsigned hflag
 #ifdef RT_ABL_NOFREQ // profiling only: the tile preamble alone
         const int K_loop = K > 1000000 ? K : 0;
         const int kb_first = 0;
-#elif defined(RT_ABL_ONEBATCH) // profiling only: one batch of four frequencies per tile
-        const int K_loop = K < VEC ? K : VEC;
-        const int kb_first = 0;
 #else
         const int K_loop = k_end;
         const int kb_first = k0;
@@ -790,9 +775,6 @@ __device__ __forceinline__ void freq_tile(const FreqHot &H, const unsigned hflag
             for (int k = lane; k < K; k += WAVE) {
                 const double v = cache[q * freq_row_stride(Kp) + k];
                 cache[q * freq_row_stride(Kp) + k] = 0.0;
-#ifdef RT_ABL_NOROWFLUSH // profiling only
-                if (v == 1234.5)
-#endif
                 unsafeAtomicAdd(&H.image[(size_t) pq * (size_t) K + (size_t) k], v);
             }
         }
@@ -819,7 +801,7 @@ __device__ unsigned long long g_ft[6][8192]; // [4]: blockIdx | wave << 16 | XCC
 __device__ unsigned g_ft_n;
 #endif
 template <int SF, bool EMIS, bool EXCL>
-__global__ void __launch_bounds__(FREQ_WG_WAVES * 64, EMIS ? RT_FREQ_WAVES : RT_FREQ_WAVES_SEED) rt_freq_kernel(const FreqKArg A)
+__global__ void __launch_bounds__(FREQ_WG_WAVES * 64, EMIS ? FREQ_WAVES : FREQ_WAVES_SEED) rt_freq_kernel(const FreqKArg A)
 {
 #ifdef RT_WAVETIMES
     const unsigned long long ft_start = __builtin_amdgcn_s_memrealtime();
@@ -920,7 +902,6 @@ __global__ void __launch_bounds__(FREQ_WG_WAVES * 64, EMIS ? RT_FREQ_WAVES : RT_
 #ifdef RT_WAVETIMES
     const unsigned long long ft_loop_end = __builtin_amdgcn_s_memrealtime();
 #endif
-#ifndef RT_ABL_NOIANGFLUSH
     if (lds_iang && !(H.flags & FQ_DBG_NOFLUSH)) {
         __syncthreads();
         for (int c = (int) threadIdx.x; c < n_ang; c += (int) blockDim.x) {
@@ -929,7 +910,6 @@ __global__ void __launch_bounds__(FREQ_WG_WAVES * 64, EMIS ? RT_FREQ_WAVES : RT_
                 unsafeAtomicAdd(&H.iang[c], v);
         }
     }
-#endif
 #ifdef RT_WAVETIMES
     if (lane == 0) {
         const unsigned w = atomicAdd(&g_ft_n, 1u);

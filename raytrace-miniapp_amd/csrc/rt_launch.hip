@@ -104,7 +104,7 @@ template <int SF, bool EMIS, bool EXCL> int launch_freq(rt_hip_plan *p, hipStrea
     // Per-wave row cache for tiles with several pixel runs (seeded): up to 16 rows of Kp doubles, as many as fit
     // into the work-group's share of the 160 KB beside the exponent tables, the I_ang histogram and the per-wave
     // transposition rows (rt_freq.hip: freq_lds_doubles); fewer than 4 rows is not worth having.
-    const int waves       = EMIS ? RT_FREQ_WAVES : RT_FREQ_WAVES_SEED;
+    const int waves       = EMIS ? rt::FREQ_WAVES : rt::FREQ_WAVES_SEED;
     constexpr bool excl   = EXCL; // (= p->P.exclusive: launch_freq_any picks the instance)
     // (exclusive mode: while its flush wrote 8 bytes per lane with a pixel look-up per store, 12 waves per CU ran 3.6 %
     // faster than 16; with the regular-tile flush of 16-byte stores 16 waves win -- 22.15 against 23.0 ms on the
@@ -495,10 +495,6 @@ int plan_launch_run(rt_hip_plan *p, hipStream_t stream)
     // lanes that must wait for block [A] of the march before it runs (swept 1 ... 40 on the 6.4 M-ray
     // stand-in: 2.36 ms at 1, flat optimum 2.12 ms at 8 ... 24, 2.63 ms at 40)
     p->P.park    = env_unsigned("RT_HIP_MARCH_PARK", 12, 1, 64);
-    p->P.express_age  = env_unsigned("RT_HIP_EXPRESS_AGE", 0, 0, 1u << 20);
-    p->P.express_hold = env_unsigned("RT_HIP_EXPRESS_HOLD", 0, 0, 1);
-    p->P.express_park = env_unsigned("RT_HIP_EXPRESS_PARK", 0, 0, 64);
-    p->P.express_tail = env_unsigned("RT_HIP_EXPRESS_TAIL", 0, 0, 2);
     p->P.path_on = p->path_on ? 1u : 0u;
     p->P.spin_limit = env_unsigned("RT_HIP_MARCH_SPIN_LIMIT", 1u << 24, 1024, 0x7fffffffu); // (tests lower it)
     p->P.no_skip = p->gv_has_nan ? 1u : 0u; // the CPU loop multiplies 0 * gv[row 0] for sub-segments a ray never entered

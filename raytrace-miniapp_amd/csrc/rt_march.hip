@@ -424,22 +424,224 @@ __device__ __forceinline__ int guess_interval(int n, float g0, float inv_h, floa
     return (int) fminf(fmaxf((v - g0) * inv_h, 0.0f), (float) (n - 2)) + 1;
 }
 
-// BOUNDED: rt_hip_plan_create has verified the table and step-size ranges under which the integrator's five
-// divisions per step need none of the scaling / fix-up instructions of an IEEE division (rt_math.h, fdiv_nr);
-// otherwise (exotic tables) every division is the full sequence.  Both give the reference's floats.
+// ---- diagnostic builds (csrc/Makefile: librt_hip_instr.so, librt_hip_time.so, librt_hip_wt.so, librt_hip_wtblocks.so) ----
+// What they count lives in MarchDiag below; march_wave and tile_push call its methods on single lines, and in the
+// product build every one of them is empty.
 #ifdef RT_INSTRUMENT
-__device__ unsigned short g_ray_iters[1u << 23]; // diagnostic: loop iterations each ray occupied its lane for (ray number < 2^23)
+// -DRT_INSTRUMENT: lane occupancy of the three nested march loops.  g_inst[2i] = wave-level iterations, g_inst[2i+1] =
+// active-lane iterations, i = 0 inner (Helper.h:279), 1 cross (:326), 2 cell (:463); g_inst[6] = wave-level entries of
+// the tiny-dividend block of [C]
+__device__ unsigned long long g_inst[8];
+// ... and the step-candidate pruning of block [C]: wave-iterations in which the division of h1 [0] and those of h2 and
+// h4 [1] were executed ([2] unused), and wave-iterations of [C] in an instance that prunes [3]
+__device__ unsigned long long g_prune[4];
+__device__ unsigned short g_ray_iters[1u << 23]; // loop iterations each ray occupied its lane for (ray number < 2^23)
 #endif
-#ifdef RT_WAVETIMES // diagnostic: start / counters-dry / end time of every wave of the last launch (100 MHz clock)
+#ifdef RT_TIMEBLOCKS
+// -DRT_TIMEBLOCKS: wave clock spent in each block of the march loop, g_inst[i] = cycles between mark i and mark i+1
+// summed over waves, g_inst[7] = iterations
+__device__ unsigned long long g_inst[8];
+#endif
+#ifdef RT_WAVETIMES // start / counters-dry / end time of every wave of the last launch (100 MHz clock)
 __device__ unsigned long long g_wt[8];
 __device__ unsigned long long g_wt_end[8192], g_wt_dry[8192];
 // ... and a trace of every wave's march: every 16th loop iteration {100 MHz time | live lanes << 40 | runs of [A] in
 // the last 16 iterations << 48 | runs of [B] << 56}, up to 64 samples; [wave][0] = samples written
 constexpr int WT_TRACE = 64;
 __device__ unsigned long long g_wt_trace[8192][WT_TRACE];
-// shader-clock cycles of the last 16 iterations spent in {refill + loop head, [A1], [A2], retire + publish, [B], [C]}
+// -DRT_WAVEBLOCKS on top: shader-clock cycles of the last 16 iterations spent in {refill + loop head, [A1], [A2],
+// retire + publish, [B], [C]} (a build of its own: six cycle-counter reads per iteration disturb the times above)
 __device__ unsigned g_wt_blocks[8192][WT_TRACE][6];
+__device__ unsigned long long g_wt_pub[8192][4]; // per wave: {ticks in tile_publish, pushes, failed compare-exchanges, longest publish}
+__device__ unsigned long long g_wt_vm[8192]; // ticks waiting for the record stores before a publish
 #endif
+#if defined(RT_INSTRUMENT) || defined(RT_TIMEBLOCKS) || defined(RT_WAVETIMES)
+struct MarchDiag {
+    static __device__ __forceinline__ unsigned wave_number() { return blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); }
+    static __device__ __forceinline__ bool first_active_lane()
+    {
+        return (int) (threadIdx.x & 63) == __ffsll((long long) __ballot(1)) - 1;
+    }
+#ifdef RT_INSTRUMENT
+    unsigned w[3] = { 0, 0, 0 }, a[3] = { 0, 0, 0 }, ray_iters = 0;
+#endif
+#if defined(RT_TIMEBLOCKS) || defined(RT_WAVEBLOCKS)
+    unsigned long long tb_acc[6] = { 0, 0, 0, 0, 0, 0 }, tb_last = __builtin_readcyclecounter(), tb_iters = 0;
+#endif
+#ifdef RT_WAVETIMES
+    const unsigned long long wt_start = __builtin_amdgcn_s_memrealtime();
+    unsigned long long wt_dry = 0, pub_t0 = 0;
+    unsigned wt_a_runs = 0, wt_b_runs = 0, wave_iter = 0;
+#endif
+    // loop i (0 inner, 1 cross, 2 cell) has run once more, for the calling lanes
+    __device__ __forceinline__ void tick(int i)
+    {
+#ifdef RT_INSTRUMENT
+        a[i]++;
+        w[i] += first_active_lane() ? 1u : 0u;
+#endif
+    }
+    // block i of the loop ends here (5: [C] of the previous iteration)
+    __device__ __forceinline__ void mark(int i)
+    {
+#if defined(RT_TIMEBLOCKS) || defined(RT_WAVEBLOCKS)
+        const unsigned long long now = __builtin_readcyclecounter();
+        tb_acc[i] += now - tb_last;
+        tb_last = now;
+#endif
+    }
+    // head of a loop iteration; the trace sample every 16th
+    // (the lane's state as it is, not `st != ST_IDLE`: even a dead comparison at the call site moves two instructions
+    // of the product's loop head)
+    __device__ __forceinline__ void iteration(int st, int lane, int n_idle)
+    {
+#ifdef RT_INSTRUMENT
+        ray_iters += st != ST_IDLE ? 1u : 0u;
+#endif
+#ifdef RT_TIMEBLOCKS
+        tb_iters++;
+#endif
+#ifdef RT_WAVETIMES
+        if ((++wave_iter & 15u) == 0u) {
+            const unsigned wid = wave_number(), smp = wave_iter >> 4;
+            if (lane == 0 && wid < 8192u && smp < (unsigned) WT_TRACE) {
+                g_wt_trace[wid][smp] = (__builtin_amdgcn_s_memrealtime() & 0xffffffffffull) | ((unsigned long long) (WAVE - n_idle) << 40) |
+                                       ((unsigned long long) wt_a_runs << 48) | ((unsigned long long) wt_b_runs << 56);
+                g_wt_trace[wid][0] = smp;
+#ifdef RT_WAVEBLOCKS
+                for (int b = 0; b < 6; b++)
+                    g_wt_blocks[wid][smp][b] = (unsigned) tb_acc[b];
+#endif
+            }
+#ifdef RT_WAVEBLOCKS
+            for (int b = 0; b < 6; b++)
+                tb_acc[b] = 0;
+#endif
+            wt_a_runs = wt_b_runs = 0;
+        }
+#endif
+    }
+    // the ray counters have run dry for this wave
+    __device__ __forceinline__ void counters_dry()
+    {
+#ifdef RT_WAVETIMES
+        wt_dry = __builtin_amdgcn_s_memrealtime();
+#endif
+    }
+    // whether [A] runs in this iteration, and [B] (lanes that arrive from [A2] in this iteration not counted)
+    __device__ __forceinline__ void blocks_run(bool a_runs, bool lane_wants_b)
+    {
+#ifdef RT_WAVETIMES
+        wt_a_runs += a_runs ? 1u : 0u;
+        wt_b_runs += __ballot(lane_wants_b) != 0ull ? 1u : 0u;
+#endif
+    }
+    // the calling lane's ray retires
+    __device__ __forceinline__ void ray_retired(unsigned ridx)
+    {
+#ifdef RT_INSTRUMENT
+        if (ridx < (1u << 23))
+            g_ray_iters[ridx] = (unsigned short) (ray_iters < 65535u ? ray_iters : 65535u);
+        ray_iters = 0;
+#endif
+    }
+    // the calling lane publishes a tile: before the wait for the record stores, after it, after tile_publish
+    // (atomics: several lanes of a wave can publish in one iteration)
+    __device__ __forceinline__ void publish_begin()
+    {
+#ifdef RT_WAVETIMES
+        pub_t0 = __builtin_amdgcn_s_memrealtime();
+#endif
+    }
+    __device__ __forceinline__ void publish_stores_landed()
+    {
+#ifdef RT_WAVETIMES
+        const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+        atomicAdd(&g_wt_vm[wave_number() & 8191u], now - pub_t0);
+        pub_t0 = now;
+#endif
+    }
+    __device__ __forceinline__ void publish_end()
+    {
+#ifdef RT_WAVETIMES
+        const unsigned long long dt = __builtin_amdgcn_s_memrealtime() - pub_t0;
+        unsigned long long *q       = g_wt_pub[wave_number() & 8191u];
+        atomicAdd(&q[0], dt);
+        atomicAdd(&q[1], 1ull);
+        atomicMax(&q[3], dt);
+#endif
+    }
+    // tile_push: a compare-exchange on the list head failed
+    static __device__ __forceinline__ void push_retry()
+    {
+#ifdef RT_WAVETIMES
+        atomicAdd(&g_wt_pub[wave_number() & 8191u][2], 1ull);
+#endif
+    }
+    // block [C]: the wave entered the tiny-dividend block; division(s) i of the pruning instance executed (g_prune)
+    __device__ __forceinline__ void tiny_dividend()
+    {
+#ifdef RT_INSTRUMENT
+        if (first_active_lane())
+            atomicAdd(&g_inst[6], 1ull);
+#endif
+    }
+    __device__ __forceinline__ void prune(int i)
+    {
+#ifdef RT_INSTRUMENT
+        if (first_active_lane())
+            atomicAdd(&g_prune[i], 1ull);
+#endif
+    }
+    // the wave leaves the march: its totals
+    __device__ __forceinline__ void wave_end(int lane)
+    {
+#ifdef RT_WAVETIMES
+        if (lane == 0) {
+            const unsigned long long wt_end = __builtin_amdgcn_s_memrealtime();
+            atomicMin(&g_wt[0], wt_start);
+            atomicMax(&g_wt[1], wt_start);
+            const unsigned n = atomicAdd((unsigned *) &g_wt[6], 1u);
+            if (n < 8192)
+                g_wt_end[n] = wt_end | ((unsigned long long) (threadIdx.x >> 6) << 56), g_wt_dry[n] = wt_dry;
+        }
+#endif
+#ifdef RT_TIMEBLOCKS
+        if (lane == 0) {
+            for (int i = 0; i < 6; i++)
+                atomicAdd(&g_inst[i], tb_acc[i]);
+            atomicAdd(&g_inst[7], tb_iters);
+        }
+#endif
+#ifdef RT_INSTRUMENT
+        for (int i = 0; i < 3; i++) {
+            const unsigned tw = wave_sum_u32(w[i]), ta = wave_sum_u32(a[i]);
+            if (lane == 0) {
+                atomicAdd(&g_inst[2 * i], (unsigned long long) tw);
+                atomicAdd(&g_inst[2 * i + 1], (unsigned long long) ta);
+            }
+        }
+#endif
+    }
+};
+#else
+struct MarchDiag { // the product build: nothing
+    __device__ __forceinline__ void tick(int) {}
+    __device__ __forceinline__ void mark(int) {}
+    __device__ __forceinline__ void iteration(int, int, int) {}
+    __device__ __forceinline__ void counters_dry() {}
+    __device__ __forceinline__ void blocks_run(bool, bool) {}
+    __device__ __forceinline__ void ray_retired(unsigned) {}
+    __device__ __forceinline__ void publish_begin() {}
+    __device__ __forceinline__ void publish_stores_landed() {}
+    __device__ __forceinline__ void publish_end() {}
+    static __device__ __forceinline__ void push_retry() {}
+    __device__ __forceinline__ void tiny_dividend() {}
+    __device__ __forceinline__ void prune(int) {}
+    __device__ __forceinline__ void wave_end(int) {}
+};
+#endif
+
 // Work-group list of finished tiles of the fused kernel (rt_fused.hip): a wave that has marched all 64 rays of a
 // chunk -- one tile of the frequency pass -- pushes the tile number; waves whose rays have run out pop tiles and run
 // their frequency pass.  A lock-free stack: the head is an LDS word, the links are one word per tile in global
@@ -472,10 +674,6 @@ __device__ __forceinline__ unsigned tile_node(unsigned entry)
 {
     return (entry & TILE_ID_MASK) * 4u + ((entry & TILE_PART_FLAG) ? (entry >> TILE_PART_SHIFT) & 3u : 0u);
 }
-#ifdef RT_WAVETIMES
-__device__ unsigned long long g_wt_pub[8192][4]; // per wave: {ticks in tile_publish, pushes, failed compare-exchanges, longest publish}
-__device__ unsigned long long g_wt_vm[8192]; // ticks waiting for the record stores before a publish
-#endif
 // one lane of the calling wave executes these
 constexpr unsigned TILE_REF_GLOBAL = 1u << 31;
 __device__ __forceinline__ void tile_push(const TileList &T, unsigned tile)
@@ -489,9 +687,7 @@ __device__ __forceinline__ void tile_push(const TileList &T, unsigned tile)
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // (entry and link are in LDS before the head can name the node)
             if (__hip_atomic_compare_exchange_strong(T.head, &old, id, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))
                 return;
-#ifdef RT_WAVETIMES
-            g_wt_pub[(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) & 8191u][2]++;
-#endif
+            MarchDiag::push_retry();
         }
     }
     tile |= TILE_REF_GLOBAL;
@@ -500,9 +696,7 @@ __device__ __forceinline__ void tile_push(const TileList &T, unsigned tile)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the link is in memory before the head can name the tile
         if (__hip_atomic_compare_exchange_strong(T.head, &old, tile, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))
             return;
-#ifdef RT_WAVETIMES
-        g_wt_pub[(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) & 8191u][2]++;
-#endif
+        MarchDiag::push_retry();
     }
 }
 // a finished tile: whole, or in four parts when the work-group is down to its last marching waves (an eighth of them)
@@ -568,6 +762,9 @@ template <bool LDS_TAB> __device__ __forceinline__ void march_load_tables(const 
     }
 }
 
+// BOUNDED: rt_hip_plan_create has verified the table and step-size ranges under which the integrator's five
+// divisions per step need none of the scaling / fix-up instructions of an IEEE division (rt_math.h, fdiv_nr);
+// otherwise (exotic tables) every division is the full sequence.  Both give the reference's floats.
 // MODE fixes the two run-time switches of the march at compile time where the host knows them (1: emission, backward
 // method -- every ASE run; 2: gain only, forward method -- every seeded run of create_image; 0: as DevParams says): as
 // run-time booleans they live in SGPR pairs that the register allocator spills into VGPR lanes and reads back
@@ -592,10 +789,7 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
     // (the path tracer is a debugging run: it takes the generic instance, the others carry none of its code)
     const bool path_on    = MODE == 0 ? P.path_on != 0 : false;
     const unsigned CH     = P.chunk;
-#ifndef RT_REFILL
-#define RT_REFILL 8
-#endif
-    const int REFILL      = RT_REFILL; // refill when this many lanes are idle (or the wave is empty)
+    constexpr int REFILL  = 8; // refill when this many lanes are idle (or the wave is empty)
 
     // ---- tables: the march blob, in LDS (copied by march_load_tables, which the caller has run) or in place ----
     const unsigned char *tab = LDS_TAB ? lds_raw : P.blob;
@@ -613,7 +807,7 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
 
     unsigned chunk_next = 0, chunk_end = 0; // wave-uniform window of reserved ray indices
     // FUSED: the window is the part of ONE tile not handed out yet; the reservation it was cut from ends at fetched_end
-    unsigned fetched_end = 0, slot_busy = 0, cur_slot = 0; // (wave-uniform) slots of done.rem in use; slot of the window's tile
+    unsigned fetched_end = 0, cur_slot = 0; // (wave-uniform) slot of done.rem of the window's tile
     unsigned cslot       = 0;                               // (per lane) slot of the tile of the lane's ray
     bool more           = true;             // wave-uniform: the ray counters are not exhausted
     // The rays of a launch are handed out in chunks of CH by eight counters (shard sh owns the chunks sh, sh + 8,
@@ -631,11 +825,7 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
     // dry that much earlier, drain and turn to the frequency pass while the old waves are still busy, and the final
     // drain is run by one wave per SIMD that nothing on its SIMD outranks.  Zone 0: chunks [0, n_main), zone 1: the rest,
     // with counters of its own (next_tile[..][shard][8]).
-#ifdef RT_MARCH_ONE_COUNTER // (the one-counter experiment knows no zones: with a late zone it would drop the chunks it draws past n_main)
-    const unsigned n_main = n_chunks;
-#else
     const unsigned n_main = n_chunks - (P.late_chunks < n_chunks ? P.late_chunks : 0u);
-#endif
     // (unsigned: waves late_first .. late_first + late_waves - 1; through readfirstlane, so that the compiler knows it for
     // wave-uniform -- derived from threadIdx.x it counts as divergent, and with it `zone`, `more` and every branch of the
     // loop head that tests them, which then run as exec-mask code instead of scalar branches)
@@ -672,91 +862,17 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
     float rx = 0, ry = 0, rz = 0, n = 0, n0 = 0, gxn = 0, gyn = 0, lim2 = 0, dzcap = 0, hsum = 0;
     // totals of this lane over the whole launch
     unsigned tot_steps = 0, tot_esc = 0, tot_rays = 0, tot_skip = 0;
-#ifdef RT_INSTRUMENT
-    Inst inst;
-#endif
-
-#if defined(RT_TIMEBLOCKS) || defined(RT_WAVEBLOCKS)
-    unsigned long long tb_acc[6] = { 0, 0, 0, 0, 0, 0 }, tb_last = __builtin_readcyclecounter(), tb_iters = 0;
-#endif
-#ifdef RT_WAVETIMES
-    const unsigned long long wt_start = __builtin_amdgcn_s_memrealtime();
-    unsigned long long wt_dry = 0;
-    unsigned wt_a_runs = 0, wt_b_runs = 0;
-#endif
-#ifdef RT_INSTRUMENT
-    unsigned ray_iters = 0;
-#endif
     unsigned spin = 0; // (BOUNDED = false only)
-    // Express waves.  A launch cannot end before its longest ray has taken its last step, and a ray's steps are
-    // sequential: what the launch can do is run the waves that hold the old rays FAST.  `wave_iter` counts this wave's
-    // loop iterations, `born` is its value when the lane took its ray; a wave that holds a ray older than P.express_age
-    // iterations raises its priority (the instruction arbiter of a SIMD serves priority before age, MI355X_MICROARCH.md)
-    // and, with P.express_hold, stops fetching rays from the counters while it does: its short rays retire, fewer lanes
-    // mean fewer of the three blocks per iteration, and the long rays it holds advance at the pace of a wave that has
-    // its SIMD to itself.  Looked at every fourth iteration; everything here is wave-uniform.
-    // (Measured in round 5, profiles/r05_express_ab.txt: +-1 ... 5 % -- what ends a launch is not the old rays, rt_fused.hip.
-    // The code is compiled only into the diagnostic build librt_hip_express.so, -DRT_EXPRESS: the loop head is sensitive to
-    // every instruction.)
-#if defined(RT_EXPRESS) || defined(RT_WAVETIMES)
-    unsigned wave_iter = 0;
-#endif
-#ifdef RT_EXPRESS
-    unsigned born = 0;
-    bool old_wave = false;
-    if (P.express_tail == 1u)
-        __builtin_amdgcn_s_setprio(2);
-#else
-    constexpr bool old_wave = false;
-#endif
+    MarchDiag diag;    // (diagnostic builds; empty in the product)
     for (;;) {
-        RT_MARK(5); // [C] of the previous iteration
-#ifdef RT_INSTRUMENT
-        ray_iters += st != ST_IDLE ? 1u : 0u;
-#endif
-#ifdef RT_TIMEBLOCKS
-        tb_iters++;
-#endif
+        diag.mark(5); // [C] of the previous iteration
         // ------------------------------------------------------------ refill
         // (one ballot per iteration: the lane masks of the loop head come from `idle2`, which is taken again only when
         // a refill has changed the states; a wave all of whose lanes are idle with nothing left to fetch leaves below)
         unsigned long long idle2      = __ballot(st == ST_IDLE);
         const unsigned long long idle = idle2;
         const int n_idle              = (int) __popcll(idle);
-#if defined(RT_EXPRESS) || defined(RT_WAVETIMES)
-        wave_iter++;
-#endif
-#ifdef RT_WAVETIMES
-        if ((wave_iter & 15u) == 0u) {
-            const unsigned wid = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), smp = wave_iter >> 4;
-            if (lane == 0 && wid < 8192u && smp < (unsigned) WT_TRACE) {
-                g_wt_trace[wid][smp] = (__builtin_amdgcn_s_memrealtime() & 0xffffffffffull) | ((unsigned long long) (WAVE - n_idle) << 40) |
-                                       ((unsigned long long) wt_a_runs << 48) | ((unsigned long long) wt_b_runs << 56);
-                g_wt_trace[wid][0] = smp;
-#ifdef RT_WAVEBLOCKS
-                for (int b = 0; b < 6; b++)
-                    g_wt_blocks[wid][smp][b] = (unsigned) tb_acc[b];
-#endif
-            }
-#ifdef RT_WAVEBLOCKS
-            for (int b = 0; b < 6; b++)
-                tb_acc[b] = 0;
-#endif
-            wt_a_runs = wt_b_runs = 0;
-        }
-#endif
-#ifdef RT_EXPRESS
-        if (P.express_age != 0u && (wave_iter & 3u) == 0u) {
-            const bool o = __ballot(st != ST_IDLE && wave_iter - born > P.express_age) != 0ull;
-            if (o != old_wave) {
-                old_wave = o;
-                if (o)
-                    __builtin_amdgcn_s_setprio(3);
-                else
-                    __builtin_amdgcn_s_setprio(0);
-            }
-        }
-#endif
+        diag.iteration(st, lane, n_idle);
         // Watchdog of the instance that takes tables and step sizes as they come (BOUNDED = false: something is outside
         // the ranges rt_hip_plan_create verifies -- an index far from 1, a gradient beyond 1e12, a dz beyond 1e6 cm).
         // The reference's loops have no iteration limit, and with such inputs a ray's steps can stop advancing (an
@@ -784,21 +900,10 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
             bool got = false;
             while (need > 0) {
                 if (chunk_next == chunk_end && !(FUSED && chunk_next != fetched_end)) {
-#ifdef RT_EXPRESS
-                    if (old_wave && P.express_hold != 0u)
-                        break; // an express wave takes no new reservation (what it has reserved it still hands out)
-#endif
                     unsigned c = 0;
-#ifdef RT_MARCH_ONE_COUNTER // experiment: one counter for all waves
-                    if (lane == 0)
-                        c = atomicAdd(&P.ctl->next_tile[P.launch_id][0][0], 1u);
-                    c = (unsigned) __builtin_amdgcn_readfirstlane((int) c);
-                    shards_seen_empty = 7;
-#else
                     if (lane == 0)
                         c = atomicAdd(&P.ctl->next_tile[P.launch_id][shard][zone * 8u], 1u);
                     c = (unsigned) __builtin_amdgcn_readfirstlane((int) c) * 8u + shard + zone * n_main; // chunk number
-#endif
                     if (c >= (zone ? n_chunks : n_main)) { // this shard is empty: the next one, until all eight have been seen empty
                         if (++shards_seen_empty == 8) {
                             if (zone == 0u && late_wave && n_main < n_chunks) { // on to the chunks kept for the old waves
@@ -807,13 +912,7 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
                                 continue;
                             }
                             more = false;
-#ifdef RT_EXPRESS
-                            if (P.express_tail == 2u)
-                                __builtin_amdgcn_s_setprio(3);
-#endif
-#ifdef RT_WAVETIMES
-                            wt_dry = __builtin_amdgcn_s_memrealtime();
-#endif
+                            diag.counters_dry();
                             break;
                         }
                         shard = (shard + 1) & 7u;
@@ -828,18 +927,15 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
                 }
                 if (FUSED && chunk_next == chunk_end) {
                     // open the next tile of the reservation: a free counter slot, loaded with the tile's ray count
-#ifndef RT_FUSED_PUBLISH_WAVE
                     // (a slot is free when its counter is back at zero: the lane that took it there published the tile in
                     // the same breath, below; looked up here, once per tile, instead of being tracked in every iteration)
-                    const unsigned in_use = lane < 32 ? __hip_atomic_load(&done.rem[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) : 1u;
-                    slot_busy             = ~(unsigned) __ballot(lane < 32 && in_use == 0u);
-#endif
+                    const unsigned in_use    = lane < 32 ? __hip_atomic_load(&done.rem[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) : 1u;
+                    const unsigned slot_busy = ~(unsigned) __ballot(lane < 32 && in_use == 0u);
                     const int fs = __builtin_ffs((int) ~slot_busy) - 1;
                     if (fs < 0)
                         break; // 32 tiles of this wave in flight (never observed): no new rays until one completes
                     chunk_end = fetched_end - chunk_next < (unsigned) WAVE ? fetched_end : chunk_next + (unsigned) WAVE;
                     cur_slot  = (unsigned) fs;
-                    slot_busy |= 1u << fs;
                     if (lane == 0)
                         __hip_atomic_store(&done.rem[fs], chunk_end - chunk_next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
                 }
@@ -913,9 +1009,6 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
                 any_bits  = P.no_skip; // (non-zero: this ray is never marked F_SKIP -- a lineshape table holds a NaN, see DevParams)
                 sub       = 0;
                 st        = ST_CELL;
-#ifdef RT_EXPRESS
-                born      = wave_iter;
-#endif
             }
             idle2 = __ballot(st == ST_IDLE);
         }
@@ -926,7 +1019,7 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
                 break;
         } else {
 
-        RT_MARK(0); // refill
+        diag.mark(0); // refill
         // ------------------------------------------------------------ [A] cell loop (Helper.h:430-504)
         // Straight-line: at most one sub-segment end [A1] and one cell setup [A2] per wave
         // iteration (a lane that needs more -- several empty sub-segments in a row, or the
@@ -941,25 +1034,13 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
         // for P.park <= 12 the threshold is P.park itself, and the adaptive form runs only in the tail of the launch)
         const unsigned long long want_a = __ballot(st == ST_CELL);
         int park_at = (int) P.park;
-        if (!more || old_wave || (int) P.park > 12 || REFILL > 8) {
+        if (!more || (int) P.park > 12 || REFILL > 8) {
             const int n_live = WAVE - (int) __popcll(idle2);
             const int fifth  = (n_live * 13 + 63) >> 6; // ~ n_live / 5, at least 1 for a live lane
             park_at          = fifth < (int) P.park ? fifth : (int) P.park;
-            // an express wave holds long rays only: most of their iterations are integrator steps inside one cell, so
-            // [A] is worth deferring much longer than in a wave of average rays (P.express_park 64ths of the live lanes)
-#ifdef RT_EXPRESS
-            if (old_wave && P.express_park != 0u)
-                park_at = (n_live * (int) P.express_park + 63) >> 6;
-#endif
         }
         const bool do_a = (int) __popcll(want_a) >= park_at || (~(idle2 | want_a)) == 0ull;
-#ifdef RT_FUSED_PUBLISH_WAVE
-        bool last_of_tile = false; // FUSED: the lane's ray ends in this iteration and was the last one of its tile
-#endif
-#ifdef RT_WAVETIMES
-        wt_a_runs += (do_a && want_a != 0ull) ? 1u : 0u;
-        wt_b_runs += __ballot(st == ST_XSETUP) != 0ull ? 1u : 0u; // (lanes that arrive from [A2] in this iteration not counted)
-#endif
+        diag.blocks_run(do_a && want_a != 0ull, st == ST_XSETUP);
         if (do_a && st == ST_CELL) {
             bool in_seg        = !escaped & (z < 0.995f * z_stop);
             if (!in_seg) {
@@ -998,7 +1079,7 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
                 z_stop = iz == 0 ? zs0 : (iz == 1 ? zs1 : zs2);
                 in_seg = !fin & (z < 0.995f * z_stop);
             }
-            RT_MARK(1); // [A1]
+            diag.mark(1); // [A1]
             if ((st == ST_CELL) & in_seg) {
                 // [A2] escape test + cell setup (Helper.h:465-497)
                 // (double)(sz*sz) < 0.01 (Helper.h:466) <=> sz*sz <= 0.01f: 0.01f is the largest float below 0.01
@@ -1104,11 +1185,11 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
                         eacc += E0 * path;
                         cell_last = c00;
                         steps++;
-                        RT_TICK(2);
+                        diag.tick(2);
                     }
                 }
             }
-            RT_MARK(2); // [A2]
+            diag.mark(2); // [A2]
             // ---------------------------------------------------------- ray finished
             if (st == ST_DONE) {
                 unsigned fl = F_VALID;
@@ -1134,69 +1215,29 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
                 if (m.px == 1234.5f) // profiling only: the store stays reachable, but never happens
                     *reinterpret_cast<RecMeta *>(metap) = m;
 #endif
-#ifdef RT_INSTRUMENT
-                if (ridx < (1u << 23))
-                    g_ray_iters[ridx] = (unsigned short) (ray_iters < 65535u ? ray_iters : 65535u);
-                ray_iters = 0;
-#endif
+                diag.ray_retired(ridx);
                 tot_steps += steps;
                 tot_esc += escaped ? 1u : 0u;
                 tot_skip += (fl & F_SKIP) ? 1u : 0u;
                 tot_rays++;
                 st = ST_IDLE;
-#ifdef RT_FUSED_PUBLISH_WAVE
-                if (FUSED) // one ray of the lane's tile less; the lane that takes the counter to zero has finished the tile
-                    last_of_tile = __hip_atomic_fetch_add(&done.rem[cslot], 0xffffffffu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) == 1u;
-#else
                 // One ray of the lane's tile less; the lane that takes the counter to zero has finished the tile and
                 // publishes it on the spot: every record of the tile was stored by THIS wave (the other rays retired in
                 // earlier iterations or in this very block), so once the wave's stores have landed the tile may be read.
                 // (Round 4 collected those lanes with a ballot after the block -- in every iteration, for an event that
-                // happens once in ~35: the loop head pays for every instruction, profiles/r05_express_cost.txt.)
+                // happens once in ~35: the loop head pays for every instruction)
                 if (FUSED) {
                     if (__hip_atomic_fetch_add(&done.rem[cslot], 0xffffffffu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) == 1u) {
+                        diag.publish_begin();
                         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                        diag.publish_stores_landed();
                         tile_publish(done, ridx >> 6);
+                        diag.publish_end();
                     }
                 }
-#endif
             }
         }
-#ifdef RT_FUSED_PUBLISH_WAVE
-        if (FUSED) {
-            unsigned long long lm = __ballot(last_of_tile);
-            if (lm != 0ull) {
-#ifdef RT_WAVETIMES
-                const unsigned long long vm0 = __builtin_amdgcn_s_memrealtime();
-#endif
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this wave's record stores have landed
-#ifdef RT_WAVETIMES
-                if (lane == 0)
-                    g_wt_vm[(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) & 8191u] += __builtin_amdgcn_s_memrealtime() - vm0;
-#endif
-                do {
-                    const int l0 = (int) __ffsll((long long) lm) - 1;
-                    lm &= lm - 1ull;
-#ifdef RT_WAVETIMES
-                    const unsigned long long pub0 = __builtin_amdgcn_s_memrealtime();
-#endif
-                    if (lane == l0)
-                        tile_publish(done, ridx >> 6);
-#ifdef RT_WAVETIMES
-                    if (lane == l0) {
-                        const unsigned long long dt = __builtin_amdgcn_s_memrealtime() - pub0;
-                        unsigned long long *q = g_wt_pub[(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) & 8191u];
-                        q[0] += dt;
-                        q[1] += 1;
-                        q[3] = dt > q[3] ? dt : q[3];
-                    }
-#endif
-                    slot_busy &= ~(1u << (unsigned) __builtin_amdgcn_readlane((int) cslot, l0));
-                } while (lm != 0ull);
-            }
-        }
-#endif
-        RT_MARK(3); // DONE
+        diag.mark(3); // DONE
         // ------------------------------------------------------------ [B] cross-cell setup (Helper.h:328-342)
         if (st == ST_XSETUP) {
             const float ya   = mirror ? fabsf(py) : py;
@@ -1219,10 +1260,10 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
             n     = n0;
             hsum  = 0.0f;
             st    = ST_STEP;
-            RT_TICK(1);
+            diag.tick(1);
         }
 
-        RT_MARK(4); // [B]
+        diag.mark(4); // [B]
         // ------------------------------------------------------------ [C] one integrator step (Helper.h:279-311)
         if (st == ST_STEP) {
             const float lim0 = 0.1f * ix1.x, lim1 = 0.1f * iy1.x;
@@ -1253,10 +1294,7 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
                 // below the bound only where a lane holds an exact zero (index gradient of a uniform
                 // region; the quotient 0 is right as it is) or, once in a blue moon, such a dividend.
                 if (__ballot(fminf(fminf(fabsf(a0), fabsf(gxn)), fabsf(gyn)) < 1e-29f) != 0ull) {
-#ifdef RT_INSTRUMENT
-                    if (lane == (int) __ffsll((long long) __ballot(1)) - 1)
-                        atomicAdd(&g_inst[6], 1ull); // wave-level entries of the tiny-dividend block
-#endif
+                    diag.tiny_dividend();
                     if (fabsf(a0) < 1e-29f && a0 != 0.0f) {
                         asm volatile("" : "+v"(a0));
                         t = a0 / n;
@@ -1299,17 +1337,10 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
                     const float n2 = 1.0001f * (lim2 - fabsf(rz));
                     const float n4 = P.c_h3 * (fabsf(sy) + 5e-4f), d4 = fabsf(fy) + 1e-8f;
                     h = fmin_nan_drop(fdiv_nr(P.c_h3 * (fabsf(sx) + 5e-4f), (fabsf(fx) + 1e-8f)), dzcap);
-#ifdef RT_INSTRUMENT
-                    const bool cnt_lane = lane == (int) __ffsll((long long) __ballot(1)) - 1;
-                    if (cnt_lane)
-                        atomicAdd(&g_prune[3], 1ull);
-#endif
+                    diag.prune(3);
                     if (__ballot(!(P.c_h1 > kd * at)) != 0ull) {
                         h = fmin_nan_drop(fdiv_nr(P.c_h1, at), h);
-#ifdef RT_INSTRUMENT
-                        if (cnt_lane)
-                            atomicAdd(&g_prune[0], 1ull);
-#endif
+                        diag.prune(0);
                     }
                     // h2 and h4 behind ONE branch, their two divisions interleaved when it is taken: a branch each ran the
                     // stand-in 1.6 % faster than none but 2 - 3 % slower on launches of a few rays per lane, whose waves
@@ -1317,10 +1348,7 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
                     // it is 2.0 % on the stand-in, and the small launches go without it (rt_launch.hip)
                     if (!(OPT & MARCH_OPT_PRUNE_H24) || __ballot(!(n2 > kd * az) | !(n4 > kd * d4)) != 0ull) {
                         h = fmin_nan_drop(fmin_nan_drop(fdiv_nr(n2, az), fdiv_nr(n4, d4)), h);
-#ifdef RT_INSTRUMENT
-                        if (cnt_lane)
-                            atomicAdd(&g_prune[1], 1ull);
-#endif
+                        diag.prune(1);
                     }
                 } else if (BOUNDED) {
                     // The step candidates (Helper.h:288-297) without the range bookkeeping of an IEEE division
@@ -1354,7 +1382,7 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
                 sz += c2 * fz;
                 renormalise(sx, sy, sz);
                 hsum += h;
-                RT_TICK(0);
+                diag.tick(0);
                 // (double)|n - n0| < 0.05 (Helper.h:280) <=> |n - n0| < 0.05f: 0.05f is the smallest float above 0.05
                 // (MARCH_OPT_NO_NTEST: the last test is known to hold, rt_plan.hip "the largest index change a step can see")
                 run = (fabsf(rx) < lim0) & (fabsf(ry) < lim1) & (fabsf(rz) < lim2);
@@ -1378,59 +1406,24 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
                     eacc += E0 * path;
                     cell_last = c00;
                     steps++;
-                    RT_TICK(2);
+                    diag.tick(2);
                     st = ST_CELL;
                 }
             }
         }
         } // some lane is marching
     }
-#ifdef RT_EXPRESS
-    if (P.express_age != 0u || P.express_tail != 0u)
-        __builtin_amdgcn_s_setprio(0);
-#endif
-
-#ifdef RT_WAVETIMES
-    if (lane == 0) {
-        const unsigned long long wt_end = __builtin_amdgcn_s_memrealtime();
-        atomicMin(&g_wt[0], wt_start);
-        atomicMax(&g_wt[1], wt_start);
-        const unsigned w = atomicAdd((unsigned *) &g_wt[6], 1u);
-        if (w < 8192)
-            g_wt_end[w] = wt_end | ((unsigned long long) (threadIdx.x >> 6) << 56), g_wt_dry[w] = wt_dry;
-    }
-#endif
+    diag.wave_end(lane);
     // ---- launch totals ----
     {
         unsigned s = wave_sum_u32(tot_steps), e = wave_sum_u32(tot_esc);
         unsigned k = wave_sum_u32(tot_skip), r = wave_sum_u32(tot_rays);
-#ifndef RT_ABL_NOTOTALS
         if (lane == 0) {
             atomicAdd(&P.ctl->cell_steps, (unsigned long long) s);
             atomicAdd(&P.ctl->n_escaped, (unsigned long long) e);
             atomicAdd(&P.ctl->n_skipped, (unsigned long long) k);
             atomicAdd(&P.ctl->n_rays, (unsigned long long) r);
         }
-#else
-        if (lane == 0 && s + e + k + r == 0xffffffffu)
-            atomicAdd(&P.ctl->cell_steps, 1ull);
-#endif
-#ifdef RT_TIMEBLOCKS
-        if (lane == 0) {
-            for (int i = 0; i < 6; i++)
-                atomicAdd(&g_inst[i], tb_acc[i]);
-            atomicAdd(&g_inst[7], tb_iters);
-        }
-#endif
-#ifdef RT_INSTRUMENT
-        for (int i = 0; i < 3; i++) {
-            unsigned tw = wave_sum_u32(inst.w[i]), ta = wave_sum_u32(inst.a[i]);
-            if (lane == 0) {
-                atomicAdd(&g_inst[2 * i], (unsigned long long) tw);
-                atomicAdd(&g_inst[2 * i + 1], (unsigned long long) ta);
-            }
-        }
-#endif
     }
 }
 

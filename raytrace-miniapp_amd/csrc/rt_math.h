@@ -9,44 +9,6 @@
 
 namespace rt {
 
-#ifdef RT_INSTRUMENT
-// Diagnostic build only (make instrument): lane-occupancy of the three nested
-// march loops.  g_inst[2i] = wave-level iterations, g_inst[2i+1] = active-lane
-// iterations, i = 0 inner (Helper.h:279), 1 cross (:326), 2 cell (:463).
-__device__ unsigned long long g_inst[8];
-// ... and the step-candidate pruning of block [C] (rt_march.hip): wave-iterations in which the division of h1 [0] and
-// those of h2 and h4 [1] were executed ([2] unused), and wave-iterations of [C] in an instance that prunes [3]
-__device__ unsigned long long g_prune[4];
-struct Inst {
-    unsigned w[3] = { 0, 0, 0 }, a[3] = { 0, 0, 0 };
-    __device__ __forceinline__ void tick(int i)
-    {
-        a[i]++;
-        unsigned long long m = __ballot(1);
-        if ((int) (threadIdx.x & 63) == __ffsll((long long) m) - 1)
-            w[i]++;
-    }
-};
-#define RT_TICK(i) inst.tick(i)
-#else
-#define RT_TICK(i)
-#endif
-// Second diagnostic build (-DRT_TIMEBLOCKS): wave clock spent in each block of the march
-// loop, g_inst[i] = cycles between mark i and mark i+1 summed over waves, g_inst[7] = iterations.
-#if defined(RT_TIMEBLOCKS) || defined(RT_WAVEBLOCKS)
-#ifndef RT_INSTRUMENT
-__device__ unsigned long long g_inst[8];
-#endif
-#define RT_MARK(i)                                                      \
-    {                                                                   \
-        const unsigned long long now_ = __builtin_readcyclecounter();   \
-        tb_acc[i] += now_ - tb_last;                                    \
-        tb_last = now_;                                                 \
-    }
-#else
-#define RT_MARK(i)
-#endif
-
 // ---------------------------------------------------------------- wave helpers
 __device__ __forceinline__ int lane_id() { return (int) (threadIdx.x & (WAVE - 1)); }
 

@@ -30,13 +30,9 @@ namespace rt {
 // cache line per row for K = 52, 16 for K = 82), so most segments cover two lines in part and the next group of the same
 // row fills them up a few microseconds later -- in L2, if the lines may stay there.  The streaming stores of the exclusive
 // deposit (whole aligned lines there) send the parts to memory one by one: measured 1.89 against 1.27 ms on the stand-in,
-// 4.20 against 2.42 ms on seed_small (profiles/spectra_ab.txt; RT_SPEC_NT_STORES builds that form for the A/B).
+// 4.20 against 2.42 ms on seed_small (profiles/spectra_ab.txt).
 typedef double f64x2s __attribute__((ext_vector_type(2)));
-#ifdef RT_SPEC_NT_STORES
-#define SPEC_STORE16(src, dst) __builtin_nontemporal_store(*reinterpret_cast<const f64x2s *>(src), reinterpret_cast<f64x2s *>(dst))
-#else
 #define SPEC_STORE16(src, dst) (*reinterpret_cast<f64x2s *>(dst) = *reinterpret_cast<const f64x2s *>(src))
-#endif
 
 template <int SF, bool EMIS>
 __device__ __forceinline__ void spec_tile(const FreqHot &H, const unsigned hflags, ColdPtr C, const SpecOut &O, const double *tab,
@@ -163,7 +159,7 @@ __device__ __forceinline__ void spec_tile(const FreqHot &H, const unsigned hflag
 // (DevCtl::next_tile_f, rt_freq_kernel says why eight), one tile per fetch: every tile costs the same here.
 // LDS of a work-group, all dynamic: the two exponent tables of rt_freq_kernel, then [64][XS_ROW] staging doubles per wave.
 template <int SF, bool EMIS>
-__global__ void __launch_bounds__(FREQ_WG_WAVES * 64, EMIS ? RT_FREQ_WAVES : RT_FREQ_WAVES_SEED) rt_spec_kernel(const SpecKArg A)
+__global__ void __launch_bounds__(FREQ_WG_WAVES * 64, EMIS ? FREQ_WAVES : FREQ_WAVES_SEED) rt_spec_kernel(const SpecKArg A)
 {
     extern __shared__ __align__(16) unsigned char spec_lds[];
     const FreqHot &H = A.hot;

@@ -184,7 +184,7 @@ __device__ __forceinline__ void step_tile(const FreqHot &H, const unsigned hflag
 //   [the two exponent tables of rt_freq_kernel][I_ang histogram, na*nb doubles rounded up to even (if it fits)]
 //   [E_v accumulator, Kp doubles][per wave: the transposition rows [4][XP_ROW] of the wave sum]
 template <int SF, bool EMIS>
-__global__ void __launch_bounds__(FREQ_WG_WAVES * 64, EMIS ? RT_FREQ_WAVES : RT_FREQ_WAVES_SEED) rt_step_kernel(const StepKArg A)
+__global__ void __launch_bounds__(FREQ_WG_WAVES * 64, EMIS ? FREQ_WAVES : FREQ_WAVES_SEED) rt_step_kernel(const StepKArg A)
 {
     extern __shared__ __align__(16) unsigned char step_lds[];
     const FreqHot &H       = A.hot;

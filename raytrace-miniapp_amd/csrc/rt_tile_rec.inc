@@ -55,11 +55,7 @@ if (SF) {
     for (int s = 0; s < SF; s++)
         big = big || !(fabsf(gs[s]) <= H.gs_cap * (80.0f / 708.0f));
 }
-#ifdef RT_FREQ_NO_F32
-const bool all_small = false;
-#else
 const bool all_small = all_regular && __ballot(big) == 0ull;
-#endif
 // a NaN or an infinity among the lineshape values (the CPU's 0 * NaN, 0 * inf and inf / inf: every one of them
 // leaves Iv = NaN, Helper.h:549-557) is tested per frequency only when the host scan of the tables found one
 const bool gv_nan = (hflags & FQ_GV_NAN) != 0;

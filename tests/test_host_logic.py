@@ -193,6 +193,24 @@ def test_every_environment_switch_is_in_the_table_of_integration_md():
     assert not missing, missing
 
 
+def test_every_compile_time_switch_has_a_build_target():
+    """Every RT_* name that a preprocessor conditional of csrc/ tests is defined (-DNAME) by some target of
+    csrc/Makefile: an experiment whose build recipe is gone does not stay behind in the kernels."""
+    import re
+    from pathlib import Path
+    csrc = Path(__file__).resolve().parents[1] / "raytrace-miniapp_amd" / "csrc"
+    tested = {}
+    for f in sorted(csrc.glob("*.hip")) + sorted(csrc.glob("*.h")) + sorted(csrc.glob("*.inc")):
+        for line in f.read_text().splitlines():
+            if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", line):
+                for n in re.findall(r"\bRT_[A-Z][A-Z_0-9]*", line.split("//")[0]):
+                    tested.setdefault(n, f.name)
+    assert len(tested) >= 10, tested
+    built = set(re.findall(r"-D(RT_[A-Z][A-Z_0-9]*)", (csrc / "Makefile").read_text()))
+    orphans = {n: f for n, f in tested.items() if n not in built}
+    assert not orphans, orphans
+
+
 # ---- bench.py / multigpu plumbing that needs no GPU ---------------------------------------------------
 def test_bench_module_does_not_touch_torch_before_it_spawns_its_ranks():
     """`python bench.py --gpus N` starts its ranks as a torch.distributed.run child; that is only safe if

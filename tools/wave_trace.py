@@ -1,13 +1,14 @@
 """Diagnostic (librt_hip_wt.so): per-wave trace of the march of the one-launch run -- time, live lanes and runs of
 blocks [A] / [B] every 16 loop iterations.  Prints the slowest waves' traces and the mean iteration time by live-lane
-count.   python tools/wave_trace.py [shard8|standin|small]  (env RT_HIP_EXPRESS_* apply)"""
+count; with librt_hip_wtblocks.so (a build of its own: its cycle-counter reads disturb the times) also the kilocycles
+per block of the loop.   python tools/wave_trace.py [shard8|standin|small] [librt_hip_wt.so|librt_hip_wtblocks.so]"""
 import ctypes as C, importlib, sys
 sys.path.insert(0, '.')
 import numpy as np
 rt = importlib.import_module("raytrace-miniapp_amd")
 be = importlib.import_module("raytrace-miniapp_amd.backend")
 mg = importlib.import_module("raytrace-miniapp_amd.multigpu")
-lib = be.HipLibrary(be.CSRC / "librt_hip_wt.so")
+lib = be.HipLibrary(be.CSRC / (sys.argv[2] if len(sys.argv) > 2 else "librt_hip_wt.so"))
 base = rt.datfile.load('tests/golden/ASE_small.dat.xz')
 full = rt.scale_problem(base, 16.0)
 case = sys.argv[1] if len(sys.argv) > 1 else "shard8"
@@ -72,7 +73,7 @@ for w in last:
     print("   live:   " + " ".join(f"{x:5d}" for x in live(v)))
     print("   [A]/16: " + " ".join(f"{x:5d}" for x in aruns(v)))
     print("   [B]/16: " + " ".join(f"{x:5d}" for x in bruns(v)))
-    for b, nm in enumerate(("head+refill", "[A1]", "[A2]", "retire+publish", "[B]", "[C]")):
+    for b, nm in enumerate(("head+refill", "[A1]", "[A2]", "retire+publish", "[B]", "[C]") if BL.any() else ()):
         print(f"   kcycles {nm:15s}: " + " ".join(f"{x / 1000:5.1f}" for x in BL[w, 1:k + 1, b]))
 # long intervals: who, when
 import collections
