@@ -117,7 +117,9 @@ int rt_hip_selftest(int device, unsigned long long *n_checked, unsigned long lon
  *          (create_image hands them over zeroed, RayTraceImage.cpp:271-274).
  *   failure_code: bit (-error) set for error -1/-2/-3 (Helper.h:47-56,
  *          RayTraceImageCPU.cpp:32-36); failed_rays receives at most
- *          max_failed rays, *n_failed the number stored.
+ *          max_failed rays, *n_failed the number stored.  Where more than RT_N_FAILED_MAX rays fail
+ *          with error -2 / -3, the rays reported are the first RT_N_FAILED_MAX of them in list order
+ *          (the ones RayTraceImageCPULoop pushes first), whatever order the device met them in.
  *   stats may be NULL.
  * A ray list that is the full tensor grid of four 1-D grids in create_image's order
  * (src/RayTraceImage.cpp:300-328) is recognised: the rays are then generated on the device
@@ -168,8 +170,9 @@ int rt_hip_multi_image_loop(int ndev, int N, const rt_beam *beam, const rt_gain 
  * above apply before they generate the rays on the device. */
 int rt_hip_ray_list_grid_dims(const rt_ray *rays, size_t n_rays, int dims[4]);
 
-/* How the last rt_hip_multi_image_loop of this thread was partitioned: 1 = pixel-column tiles + gather,
- * 2 = ray chunks + sum-reduce, 0 = none yet.  (Diagnostics and tests.) */
+/* How the last rt_hip_multi_image_loop / rt_hip_multi_step_loop of this thread was partitioned: 1 = pixel-column
+ * tiles + gather, 2 = ray chunks + sum-reduce, 3 = strided ray grid + sum-reduce of the step record
+ * (rt_hip_multi_step_loop only), 0 = none yet.  (Diagnostics and tests.) */
 int rt_hip_multi_last_mode(void);
 
 /* List-mode launch tangents (Helper.h:409-410) are computed on the device by a restatement of glibc
@@ -328,17 +331,49 @@ int rt_hip_calc_rays(int device, int N, double dz, const rt_gain *gain, const rt
  *   rt_hip_plan_run takes image_dev == NULL in this mode (anything else is RT_ERR_ARG) and an optional iang_dev;
  *   rt_hip_plan_fetch takes no image pointer (I_ang is served) and reports failure_code, failed rays and counters as
  *   ever; a run with error -2 / -3 is repeated in the checking mode, so the outputs are the reductions of what the CPU
- *   loop leaves.  E_v and nf belong to the plan and are zeroed by every run.  Works with ray lists and ray grids (first /
+ *   loop leaves.  E_v and nf belong to the plan (or are lent to it, set_step_buffers below) and are zeroed by every run.  Works with ray lists and ray grids (first /
  *   stride included), the probe, exact emission and debug bits 0 and 1; together with the path tracer or spectra mode
  *   it is RT_ERR_ARG.  A plan that has only run in step mode has no image buffer (rt_hip_plan_image_ptr == NULL);
  *   switching the mode off restores image mode unchanged.
  * fetch_step: waits for the last run (repeating a failing one) and copies out; any pointer may be NULL.  step_ptrs:
  * device pointers of E_v [nv] and nf [nx*ny] of the last run (for torch views / RCCL), valid while the plan lives.
  * rt_hip_step_loop is rt_hip_image_loop with E_v and nf in place of image: the same grid recognition, error convention
- * and staging of the (small) outputs behind the kernels.  rt_hip_multi_image_loop has no step form. */
+ * and staging of the (small) outputs behind the kernels.
+ * set_step_buffers: E_v and nf in the caller's device memory, beside the caller's iang_dev -- so that the whole record is
+ * one buffer a collective can take.  Every step run after the call zeroes E_v_dev [nv] and nf_dev [nx*ny] in its
+ * zeroing launch and writes them in place of the plan's own arrays, the checking repeat of a failing run included;
+ * fetch_step and step_ptrs serve whichever buffers the last run used.  NULL, NULL restores the plan's own allocation
+ * (the default).  Alignment: 8 bytes each, what the kernels' f64 atomics and stores need (the plan's own nf sits at a
+ * 256-byte boundary behind E_v; nothing requires it).  A misaligned pointer, or one pointer NULL and the other not, is
+ * RT_ERR_ARG.  Outside step mode the call is accepted and takes effect when step mode is switched on.  The buffers must
+ * stay valid until the last run that used them has been fetched.  One exception to the sizes: on a beam whose x or y
+ * axis has a single grid point the reference's getIndex answers cell 1 for the coordinate g[0] + d/2 exactly
+ * (RayTraceImageCPU.cpp:11-16, where the reference writes past its image); nf_dev then needs nx + 2 doubles more.
+ *
+ * rt_hip_multi_step_loop: rt_hip_step_loop on all devices of the node -- arguments and error convention of
+ * rt_hip_step_loop with ndev in front; ndev, the communicator, the serialisation of callers and stats as in
+ * rt_hip_multi_image_loop.  It is the application's multi-rank step (rays N_start + it N_parallel per rank,
+ * src/RayTraceImage.cpp:300-313; ONE all-reduce of the record, intensity_step_struct::sum_reduce,
+ * src/RayTraceStructures.cpp:1603-1646) inside one process: every device builds a plan on the FULL beam in step mode
+ * and owns one buffer (E_v | pad to 256 bytes | nf | I_ang), lent to its plan through set_step_buffers and iang_dev.
+ *   A list recognised as a tensor grid (the speculation and retry of rt_hip_multi_image_loop): device d generates rays
+ *   d, d + ndev, ... (rt_hip_plan_set_ray_grid with first = d, stride = ndev); a device beyond the last ray contributes
+ *   a record of zeros.  rt_hip_multi_last_mode reports 3.  Any other list: contiguous chunks of the list, mode 2.
+ *   Never pixel-column tiles.
+ *   Assembly: ONE ncclReduce(sum, f64) of the buffer -- nv + nx*ny + na*nb doubles and the pad -- to device 0, one
+ *   download of the three arrays.  The image cube exists on no device and crosses no link.
+ * A device with failing rays runs its checking repeat before its record travels: the sums are the reductions of what
+ * RayTraceImageCPULoop leaves; failed rays are reported in the order of the devices (for a chunked list that is list
+ * order: the report equals rt_hip_step_loop's).  The result differs from
+ * rt_hip_step_loop's by summation order only.  RCCL with more than one rank has not run on hardware (as for the image
+ * arm); RT_HIP_MULTI_LOOPBACK=n rehearses n workers on device 0 with the collective replaced by copies and a sum kernel. */
 int rt_hip_plan_enable_step(rt_hip_plan *plan, int on);
+int rt_hip_plan_set_step_buffers(rt_hip_plan *plan, double *E_v_dev, double *nf_dev);
 int rt_hip_plan_fetch_step(rt_hip_plan *plan, double *E_v, double *nf, double *I_ang);
 int rt_hip_plan_step_ptrs(rt_hip_plan *plan, double **E_v_dev, double **nf_dev);
+int rt_hip_multi_step_loop(int ndev, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed, int method,
+                           const rt_ray *rays, size_t n_rays, double scale, double *E_v, double *nf, double *I_ang,
+                           unsigned int *failure_code, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats);
 int rt_hip_step_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed, int method,
                      const rt_ray *rays, size_t n_rays, double scale, double *E_v, double *nf, double *I_ang,
                      unsigned int *failure_code, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats);

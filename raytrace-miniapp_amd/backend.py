@@ -8,6 +8,7 @@ mirror of the reference's operator interface for this path.
                         (src/RayTraceImageCuda.cu:145-221) behind the signature of
                         src/RayTraceImage.cpp:47-75
   step_loop(...)        the same loop with the application's per-step record in place of the image cube: E_v, nf, I_ang
+  multi_step_loop(...)  step_loop on all devices of the node: strided ray grid per device, one sum-reduce of the record
   step_outputs_from_image  their definition as reductions of a cube, in numpy (no device)
   calc_rays / calc_ray  RayTrace::calc_ray (src/RayTraceImage.cpp:189-204), batched: per-ray spectrum, exit ray, code
   create_image(p, method)
@@ -227,6 +228,13 @@ class Plan:
         self._step = bool(on)
         return self
 
+    def set_step_buffers(self, E_v_ptr: int = 0, nf_ptr: int = 0) -> "Plan":
+        """E_v [nv] and nf [nx * ny] of the following step runs in the caller's device memory (8-byte aligned; include/rt_hip.h),
+        e.g. views of the tensor whose tail is handed to run(iang_ptr=...); (0, 0) restores the plan's own buffers."""
+        self.hl.check(self.hl.lib.rt_hip_plan_set_step_buffers(self._h, C.c_void_p(E_v_ptr or None), C.c_void_p(nf_ptr or None)),
+                      "rt_hip_plan_set_step_buffers")
+        return self
+
     def fetch_step(self) -> dict:
         """E_v [nv], nf [nx * ny] (p = ix + iy nx), I_ang [na * nb] of the last step run (waits for it)."""
         b = self.problem.beam
@@ -390,6 +398,33 @@ def step_loop(problem: Problem, rays: np.ndarray | None = None, device: int = 0)
     hl.check(rc, "rt_hip_step_loop")
     return dict(E_v=E_v, nf=nf, I_ang=iang, failure_code=code.value, failed_rays=failed[:nfail.value].copy(),
                 stats={k: getattr(st, k) for k, _ in cabi.RtStats._fields_}, call_ms=call_ms)
+
+
+def multi_step_loop(problem: Problem, rays: np.ndarray | None = None, n_devices: int = 0) -> dict:
+    """step_loop on all devices of the node (rt_hip_multi_step_loop): every device traces its share of the rays on the
+    full beam into one buffer (E_v | nf | I_ang), ONE RCCL sum-reduce assembles them (include/rt_hip.h).  n_devices <= 0:
+    every device.  Returns what step_loop returns plus `mode` (3 = strided ray grid, 2 = chunks of the list)."""
+    hl = HipLibrary.get()
+    m = cabi.Marshalled(problem)
+    if rays is None:
+        rays = problem.build_rays()
+    rays = np.ascontiguousarray(rays, dtype=cabi.RAY_DTYPE)
+    b = problem.beam
+    E_v, nf, iang = np.zeros(b.nv), np.zeros(b.nx * b.ny), np.zeros(b.na * b.nb)
+    code = C.c_uint(0)
+    nfail = C.c_int(0)
+    failed = np.zeros(cabi.RT_N_FAILED_MAX, dtype=cabi.RAY_DTYPE)
+    st = cabi.RtStats()
+    t0 = time.perf_counter()
+    rc = hl.lib.rt_hip_multi_step_loop(n_devices, m.N, C.byref(m.beam), m.gain, m.seed_ref, problem.method,
+                                       cabi.rays_ptr(rays), len(rays), problem.scale, cabi._dp(E_v), cabi._dp(nf),
+                                       cabi._dp(iang), C.byref(code), cabi.rays_ptr(failed),
+                                       cabi.RT_N_FAILED_MAX, C.byref(nfail), C.byref(st))
+    call_ms = (time.perf_counter() - t0) * 1e3
+    hl.check(rc, "rt_hip_multi_step_loop")
+    return dict(E_v=E_v, nf=nf, I_ang=iang, failure_code=code.value, failed_rays=failed[:nfail.value].copy(),
+                stats={k: getattr(st, k) for k, _ in cabi.RtStats._fields_}, mode=int(hl.lib.rt_hip_multi_last_mode()),
+                call_ms=call_ms)
 
 
 def step_outputs_from_image(problem: Problem, image) -> dict:

@@ -226,6 +226,11 @@ def declare_hip_api(lib: C.CDLL) -> None:
             C.c_double, c_double_p, c_double_p, c_double_p, P(C.c_uint), P(RtRay), C.c_int, P(C.c_int),
             P(RtStats)]
         lib.rt_hip_step_loop.restype = C.c_int
+    if hasattr(lib, "rt_hip_multi_step_loop"):   # (likewise)
+        lib.rt_hip_plan_set_step_buffers.argtypes = [vp, vp, vp]
+        lib.rt_hip_plan_set_step_buffers.restype = C.c_int
+        lib.rt_hip_multi_step_loop.argtypes = list(lib.rt_hip_step_loop.argtypes)
+        lib.rt_hip_multi_step_loop.restype = C.c_int
     lib.rt_hip_plan_set_debug.argtypes = [vp, C.c_uint]
     lib.rt_hip_plan_set_debug.restype = C.c_int
     lib.rt_hip_plan_destroy.argtypes = [vp]
@@ -241,5 +246,6 @@ HIP_API_SYMBOLS = [
     "rt_hip_plan_fetch_probe", "rt_hip_plan_set_exact_emission", "rt_hip_plan_set_step_factor", "rt_hip_plan_enable_path",
     "rt_hip_plan_fetch_path", "rt_hip_plan_enable_spectra", "rt_hip_plan_fetch_spectra", "rt_hip_plan_spectra_ptr",
     "rt_hip_calc_rays", "rt_hip_plan_enable_step", "rt_hip_plan_fetch_step", "rt_hip_plan_step_ptrs", "rt_hip_step_loop",
+    "rt_hip_plan_set_step_buffers", "rt_hip_multi_step_loop",
     "rt_hip_plan_set_debug", "rt_hip_plan_destroy",
 ]

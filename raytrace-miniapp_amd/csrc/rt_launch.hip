@@ -278,9 +278,34 @@ extern "C" __global__ void __launch_bounds__(256) rt_zero_kernel(unsigned long l
         *q                    = 0ull;
     }
 }
+// (four ranges: a step run into buffers the caller lent -- E_v, nf, I_ang, control block.  A kernel of its own, so that
+// the zeroing launch of every other run stays the instance it was.)
+extern "C" __global__ void __launch_bounds__(256) rt_zero4_kernel(unsigned long long *a, unsigned long long na, unsigned long long *b,
+                                                                 unsigned long long nb, unsigned long long *c, unsigned long long nc,
+                                                                 unsigned long long *d, unsigned long long nd)
+{
+    const unsigned long long step = (unsigned long long) gridDim.x * blockDim.x;
+    for (unsigned long long i = (unsigned long long) blockIdx.x * blockDim.x + threadIdx.x; i < na + nb + nc + nd; i += step) {
+        unsigned long long *q = i < na ? a + i : (i < na + nb ? b + (i - na) : (i < na + nb + nc ? c + (i - na - nb) : d + (i - na - nb - nc)));
+        *q                    = 0ull;
+    }
+}
 } // namespace rt
 
 namespace rtr {
+
+int launch_zero4(hipStream_t stream, void *a, size_t a_bytes, void *b, size_t b_bytes, void *c, size_t c_bytes, void *d, size_t d_bytes)
+{
+    const unsigned long long na = a ? a_bytes / 8 : 0, nb = b ? b_bytes / 8 : 0, nc = c ? c_bytes / 8 : 0, nd = d ? d_bytes / 8 : 0;
+    if (na + nb + nc + nd == 0)
+        return RT_OK;
+    unsigned long long blocks = (na + nb + nc + nd + 255) / 256;
+    blocks                    = blocks > 4096 ? 4096 : blocks;
+    hipLaunchKernelGGL(rt::rt_zero4_kernel, dim3((unsigned) blocks), dim3(256), 0, stream, (unsigned long long *) a, na,
+                       (unsigned long long *) b, nb, (unsigned long long *) c, nc, (unsigned long long *) d, nd);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
 
 int launch_zero3(hipStream_t stream, void *a, size_t a_bytes, void *b, size_t b_bytes, void *c, size_t c_bytes)
 {
@@ -341,7 +366,10 @@ int plan_repeat_checked(rt_hip_plan *p)
     const bool step = p->last_step; // a step run: the step kernel honours the same marks, E_v and nf start over
     int rc    = step ? launch_step_any(p, stream) : launch_freq_any(p, stream);
     if (rc == RT_OK) {
-        if (step)
+        if (step && p->last_step_lent) { // (the caller's buffers: exactly the K and nx * ny doubles that are the run's)
+            HIP_TRY(hipMemsetAsync(p->step.E_v, 0, (size_t) p->P.K * sizeof(double), stream));
+            HIP_TRY(hipMemsetAsync(p->step.nf, 0, (size_t) p->P.beam.nx * (size_t) p->P.beam.ny * sizeof(double), stream));
+        } else if (step)
             HIP_TRY(hipMemsetAsync(p->step_dev, 0, p->step_doubles * sizeof(double), stream));
         else if (!p->P.exclusive)
             HIP_TRY(hipMemsetAsync(p->last_image, 0, p->n_image * sizeof(double), stream));

@@ -5,7 +5,11 @@
 // multi-rank run of the application uses MPI (src/MPI_helpers.h:29-38): one host thread per device with the
 // device bound inside the worker, one RCCL communicator over the devices, ONE collective per image -- a
 // grouped send/recv gather of pixel-column tiles over xGMI (ASE) or a sum-reduce of whole images (seeded
-// mode, arbitrary lists).  librccl.so is loaded on first use.
+// mode, arbitrary lists).  rt_hip_multi_step_loop is the same call for the application's per-step record (E_v, nf,
+// I_ang; intensity_step_struct::sum_reduce, src/RayTraceStructures.cpp:1603-1646): every device traces rays d, d + ndev,
+// ... of the grid (src/RayTraceImage.cpp:300-313) into one small buffer, ONE sum-reduce assembles them.  Both entries
+// are multi_loop below: they differ in what a worker produces and in what device 0 downloads.
+// librccl.so is loaded on first use.
 #include "rt_runtime.h"
 
 #include <rccl/rccl.h> // types and prototypes only: librccl.so is loaded on first use (rccl_api below)
@@ -174,7 +178,7 @@ extern "C" __global__ void __launch_bounds__(256) rt_interleave_kernel(const dou
 } // namespace rt
 
 namespace rt {
-// loopback rehearsal of the sum-reduce (rt_hip_multi_image_loop): out = sum over parts of recv[part][.]
+// loopback rehearsal of the sum-reduce (rt_hip_multi_image_loop, rt_hip_multi_step_loop): out = sum over parts of recv[part][.]
 extern "C" __global__ void __launch_bounds__(256) rt_sum_parts_kernel(const double *recv, unsigned long long stride, int ndev,
                                                                      unsigned long long n, double *out)
 {
@@ -188,19 +192,20 @@ extern "C" __global__ void __launch_bounds__(256) rt_sum_parts_kernel(const doub
 }
 } // namespace rt
 
-extern "C" {
+namespace {
 
-int rt_hip_multi_last_mode(void) { return g_multi_mode; }
+// where the result of a call goes on the host.  image != NULL: the image arm (image | I_ang); image == NULL: the step
+// arm, the record (E_v | nf | I_ang) of step mode -- every worker's plan then runs in step mode on the FULL beam
+struct MultiOut {
+    double *image, *E_v, *nf, *I_ang;
+};
 
-int rt_hip_multi_image_loop(int ndev, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed,
-                            int method, const rt_ray *rays, size_t n_rays, double scale, double *image,
-                            double *I_ang, unsigned int *failure_code, rt_ray *failed_rays, int max_failed,
-                            int *n_failed, rt_stats *stats)
+int multi_loop(const std::string &who, int ndev, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed,
+               int method, const rt_ray *rays, size_t n_rays, double scale, const MultiOut &out,
+               unsigned int *failure_code, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats)
 {
-    if (!beam || !gain || !image || !I_ang)
-        return fail_arg("rt_hip_multi_image_loop: NULL argument");
-    if (!rays && n_rays)
-        return fail_arg("rt_hip_multi_image_loop: NULL ray list");
+    const bool step = out.image == nullptr;
+    double *const image = out.image, *const I_ang = out.I_ang;
     const int have = rt_hip_device_count();
     if (have < 1) {
         last_error() = "no HIP device";
@@ -225,7 +230,7 @@ int rt_hip_multi_image_loop(int ndev, int N, const rt_beam *beam, const rt_gain 
         std::string err;
         const int rc = multi_comms(ndev, err);
         if (rc != RT_OK) {
-            last_error() = "rt_hip_multi_image_loop: " + err;
+            last_error() = who + ": " + err;
             return rc;
         }
         R = rccl_api();
@@ -256,20 +261,40 @@ int rt_hip_multi_image_loop(int ndev, int N, const rt_beam *beam, const rt_gain 
     };
     // pixel tiles: ASE, and the rays are the beam's own grid -- every ray then deposits into the pixel
     // column it starts in (SURVEY.md 8(c) i; the frequency kernel computes the deposit cell per ray anyway)
-    const bool tiles = method == 1 && !seed && is_grid && axis_is(G.g[0], beam->x, beam->nx) &&
+    // (the step arm never cuts the image: a record on the full beam from every device is what its one sum-reduce adds)
+    const bool tiles = !step && method == 1 && !seed && is_grid && axis_is(G.g[0], beam->x, beam->nx) &&
                        axis_is(G.g[1], beam->y, beam->ny) && axis_is(G.g[2], beam->a, beam->na) &&
                        axis_is(G.g[3], beam->b, beam->nb) && !getenv("RT_HIP_MULTI_NO_TILES") &&
                        // ... and column i of the rays deposits into pixel column i of the FULL grid (a tile plan
                        // runs the deposit index on its own sub-grid with the original dx): the same host check
                        // that allows the exclusive mode; a beam that fails it takes the chunk mode
                        grid_points_in_own_cells(beam->x, beam->nx, beam->dx) && grid_points_in_own_cells(beam->y, beam->ny, beam->dy);
-    g_multi_mode = tiles ? 1 : 2;
+    // the step arm deals a grid's rays out as the application deals them to its ranks: device d generates rays d, d + ndev, ...
+    const bool strided = step && is_grid;
+    g_multi_mode       = tiles ? 1 : strided ? 3 : 2;
 
     const int nx = beam->nx, ny = beam->ny, K = beam->nv;
     const size_t n_ang = (size_t) beam->na * (size_t) beam->nb;
     const size_t n_img = (size_t) nx * (size_t) ny * (size_t) K;
     const size_t n_tile_max = tiles ? (size_t) ny * (size_t) tile_cols(nx, 0, ndev) * (size_t) K : n_img;
-    const size_t stride     = n_tile_max + n_ang; // doubles every device contributes
+    // the step record of a device, one buffer: (E_v [K] | pad to 256 bytes | nf [nx ny] | I_ang [na nb]).  On an axis of
+    // one grid point the deposit index can be 1 (rt_hip_plan_set_step_buffers in include/rt_hip.h): nf and I_ang are
+    // then followed by the cells such a ray lands in, which travel with the record and are not downloaded.
+    const size_t n_pix   = (size_t) nx * (size_t) ny;
+    const size_t nf_off  = align_up((size_t) K * sizeof(double), 256) / sizeof(double);
+    const size_t ang_off = step ? nf_off + n_pix + ((nx < 2 || ny < 2) ? (size_t) nx + 2 : 0) : n_tile_max;
+    const size_t stride  = ang_off + n_ang + ((step && (beam->na < 2 || beam->nb < 2)) ? (size_t) beam->na + 2 : 0); // doubles every device contributes
+    const size_t n_out0  = step ? stride : n_img + n_ang; // device 0: the assembled result
+    auto download = [&](const double *out0, auto &&hip_ok) {
+        if (step) {
+            hip_ok(hipMemcpy(out.E_v, out0, (size_t) K * sizeof(double), hipMemcpyDeviceToHost), "download E_v");
+            hip_ok(hipMemcpy(out.nf, out0 + nf_off, n_pix * sizeof(double), hipMemcpyDeviceToHost), "download nf");
+        } else {
+            hip_ok(hipMemcpy(image, out0, n_img * sizeof(double), hipMemcpyDeviceToHost), "download image");
+        }
+        // (the assembled image arm: I_ang behind the whole image, whatever the tiles' stride was)
+        hip_ok(hipMemcpy(I_ang, out0 + (step ? ang_off : n_img), n_ang * sizeof(double), hipMemcpyDeviceToHost), "download I_ang");
+    };
 
     struct Worker {
         int rc = RT_OK;
@@ -333,13 +358,21 @@ int rt_hip_multi_image_loop(int ndev, int N, const rt_beam *beam, const rt_gain 
                 }
             } else {
                 rc = plan_create_on(&p, up_q, pd, N, beam, gain, seed, method, scale);
+                if (rc == RT_OK && step)
+                    rc = rt_hip_plan_enable_step(p, 1);
                 // contiguous ray chunks, as RayTraceImageThreadLoop splits them (RayTraceImage.cpp:107)
                 const size_t chunk = n_rays / (size_t) ndev + 1;
                 const size_t begin = std::min((size_t) d * chunk, n_rays);
                 const size_t count = std::min(chunk, n_rays - begin);
-                if (rc == RT_OK)
+                if (rc == RT_OK && strided) {
+                    // rays N_start + it N_parallel with N_start = d, N_parallel = ndev (RayTraceImage.cpp:300-313); a
+                    // device beyond the last ray generates none and contributes a record of zeros
+                    const size_t mine = (size_t) d < n_rays ? (n_rays - (size_t) d + (size_t) ndev - 1) / (size_t) ndev : 0;
+                    rc = plan_set_guessed_grid(p, G, (int64_t) d, (int64_t) mine, (int64_t) ndev);
+                } else if (rc == RT_OK) {
                     rc = is_grid ? plan_set_guessed_grid(p, G, (int64_t) begin, (int64_t) count)
                                  : rt_hip_plan_set_rays(p, count ? rays + begin : nullptr, count);
+                }
             }
             if (rc != RT_OK)
                 fail(rc, rt_hip_last_error());
@@ -349,13 +382,19 @@ int rt_hip_multi_image_loop(int ndev, int N, const rt_beam *beam, const rt_gain 
             if (w.rc == RT_OK && d == 0) {
                 if (tiles || loopback > 0)
                     hip_ok(pool_alloc(0, (void **) &recv0, (size_t) ndev * stride * sizeof(double)), "gather buffer");
-                hip_ok(pool_alloc(0, (void **) &out0, (n_img + n_ang) * sizeof(double)), "image buffer");
+                hip_ok(pool_alloc(0, (void **) &out0, n_out0 * sizeof(double)), "image buffer");
             }
         }
         if (w.rc == RT_OK && tiles && stride > (size_t) p->n_image + n_ang) // padding of a narrower tile travels too
             hip_ok(hipMemsetAsync(buf, 0, stride * sizeof(double), q), "hipMemsetAsync");
+        if (w.rc == RT_OK && step) { // the record is lent to the plan; what lies between and behind its arrays travels as zeros
+            hip_ok(hipMemsetAsync(buf, 0, stride * sizeof(double), q), "hipMemsetAsync");
+            const int rc = rt_hip_plan_set_step_buffers(p, buf, buf + nf_off);
+            if (rc != RT_OK)
+                fail(rc, rt_hip_last_error());
+        }
         if (w.rc == RT_OK) {
-            const int rc = rt_hip_plan_run(p, q, buf, buf + n_tile_max);
+            const int rc = rt_hip_plan_run(p, q, step ? nullptr : buf, buf + ang_off);
             if (rc != RT_OK)
                 fail(rc, rt_hip_last_error());
         }
@@ -393,10 +432,8 @@ int rt_hip_multi_image_loop(int ndev, int N, const rt_beam *beam, const rt_gain 
                                        ndev, (unsigned long long) stride, out0);
                 hip_ok(hipGetLastError(), "assembly kernel");
                 hip_ok(hipStreamSynchronize(q), "hipStreamSynchronize");
-                if (w.rc == RT_OK) {
-                    hip_ok(hipMemcpy(image, out0, n_img * sizeof(double), hipMemcpyDeviceToHost), "download image");
-                    hip_ok(hipMemcpy(I_ang, out0 + n_img, n_ang * sizeof(double), hipMemcpyDeviceToHost), "download I_ang");
-                }
+                if (w.rc == RT_OK)
+                    download(out0, hip_ok);
             }
         } else if (meet.arrive(w.rc == RT_OK && grid_ok)) {
             ncclResult_t r = ncclSuccess;
@@ -458,10 +495,8 @@ int rt_hip_multi_image_loop(int ndev, int N, const rt_beam *beam, const rt_gain 
                 if (w.rc == RT_OK && g_comms_aborted.load())
                     fail(RT_ERR_HIP, "collective aborted: another device failed");
             }
-            if (w.rc == RT_OK && d == 0) {
-                hip_ok(hipMemcpy(image, out0, n_img * sizeof(double), hipMemcpyDeviceToHost), "download image");
-                hip_ok(hipMemcpy(I_ang, out0 + n_img, n_ang * sizeof(double), hipMemcpyDeviceToHost), "download I_ang");
-            }
+            if (w.rc == RT_OK && d == 0)
+                download(out0, hip_ok);
         }
         // every worker is past the collective before any buffer of it goes back to the pool
         meet.arrive(true);
@@ -521,6 +556,39 @@ int rt_hip_multi_image_loop(int ndev, int N, const rt_beam *beam, const rt_gain 
     if (rc == RT_RETRY)
         rc = attempt(false);
     return rc;
+}
+
+} // namespace
+
+extern "C" {
+
+int rt_hip_multi_last_mode(void) { return g_multi_mode; }
+
+int rt_hip_multi_image_loop(int ndev, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed,
+                            int method, const rt_ray *rays, size_t n_rays, double scale, double *image,
+                            double *I_ang, unsigned int *failure_code, rt_ray *failed_rays, int max_failed,
+                            int *n_failed, rt_stats *stats)
+{
+    if (!beam || !gain || !image || !I_ang)
+        return fail_arg("rt_hip_multi_image_loop: NULL argument");
+    if (!rays && n_rays)
+        return fail_arg("rt_hip_multi_image_loop: NULL ray list");
+    return multi_loop("rt_hip_multi_image_loop", ndev, N, beam, gain, seed, method, rays, n_rays, scale,
+                      MultiOut{ image, nullptr, nullptr, I_ang }, failure_code, failed_rays, max_failed, n_failed, stats);
+}
+
+int rt_hip_multi_step_loop(int ndev, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed, int method,
+                           const rt_ray *rays, size_t n_rays, double scale, double *E_v, double *nf, double *I_ang,
+                           unsigned int *failure_code, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats)
+{
+    if (!beam || !gain || !E_v || !nf || !I_ang)
+        return fail_arg("rt_hip_multi_step_loop: NULL argument");
+    if (!rays && n_rays)
+        return fail_arg("rt_hip_multi_step_loop: NULL ray list");
+    if (n_rays > MAX_LIST_RAYS)
+        return fail_arg("rt_hip_multi_step_loop: 2^32 - 4096 rays or more: split the call");
+    return multi_loop("rt_hip_multi_step_loop", ndev, N, beam, gain, seed, method, rays, n_rays, scale,
+                      MultiOut{ nullptr, E_v, nf, I_ang }, failure_code, failed_rays, max_failed, n_failed, stats);
 }
 
 } // extern "C"

@@ -603,6 +603,8 @@ void rtr::plan_stage_outputs(rt_hip_plan *p)
     constexpr size_t ctl_tail = offsetof(rt::DevCtl, failure_code), ctl_bytes = sizeof(rt::DevCtl) - ctl_tail;
     if (!p || !p->ran || !p->last_stream)
         return;
+    if (p->last_step && p->last_step_lent) // E_v and nf are the caller's, and not one range: fetched the ordinary way
+        return;
     // (a step run: E_v and nf travel where the image does)
     const double *big    = p->last_step ? p->step_dev : p->last_image;
     const size_t n_big   = p->last_step ? p->step_doubles : p->n_image;
@@ -899,6 +901,20 @@ int rt_hip_plan_enable_step(rt_hip_plan *p, int on)
     return RT_OK;
 }
 
+int rt_hip_plan_set_step_buffers(rt_hip_plan *p, double *E_v_dev, double *nf_dev)
+{
+    if (!p)
+        return fail_arg("rt_hip_plan_set_step_buffers: NULL plan");
+    if ((E_v_dev == nullptr) != (nf_dev == nullptr))
+        return fail_arg("rt_hip_plan_set_step_buffers: E_v and nf are lent together or not at all");
+    // (what the kernels need: 8-byte atomics and stores, the zeroing launch writes 8-byte words)
+    if (reinterpret_cast<uintptr_t>(E_v_dev) % sizeof(double) || reinterpret_cast<uintptr_t>(nf_dev) % sizeof(double))
+        return fail_arg("rt_hip_plan_set_step_buffers: a pointer is not aligned to 8 bytes");
+    p->step_ev_lent = E_v_dev; // taken by the next step run; the last run's buffers stay those of rt_hip_plan_fetch_step
+    p->step_nf_lent = nf_dev;
+    return RT_OK;
+}
+
 int rt_hip_plan_step_ptrs(rt_hip_plan *p, double **E_v_dev, double **nf_dev)
 {
     if (!p || !p->ran || !p->last_step)
@@ -962,15 +978,17 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
         return fail_arg("rt_hip_plan_run: step mode together with spectra mode or the path tracer");
     if (step && image_dev)
         return fail_arg("rt_hip_plan_run: a step run takes no image buffer");
-    if (step && !p->step_dev) {
-        const size_t nf_off = align_up((size_t) p->P.K * sizeof(double), 256) / sizeof(double);
+    const bool lent = step && p->step_ev_lent; // E_v and nf in the caller's memory (rt_hip_plan_set_step_buffers)
+    const size_t nf_off = align_up((size_t) p->P.K * sizeof(double), 256) / sizeof(double);
+    if (step && !lent && !p->step_dev) {
         // (one row and a cell to spare: on an axis of one grid point the reference's getIndex answers 1 for the coordinate
         // g[0] + d/2 exactly, deposit_index4 of rt_freq.hip likewise)
         p->step_doubles     = nf_off + (size_t) p->P.beam.nx * (size_t) p->P.beam.ny + (size_t) p->P.beam.nx + 2;
         HIP_TRY(pool_alloc(p->device, (void **) &p->step_dev, p->step_doubles * sizeof(double)));
-        p->step.E_v = p->step_dev;
-        p->step.nf  = p->step_dev + nf_off;
     }
+    rt::StepOut step_out = {};
+    if (step)
+        step_out = lent ? rt::StepOut{ p->step_ev_lent, p->step_nf_lent } : rt::StepOut{ p->step_dev, p->step_dev + nf_off };
     if (!spectra && !step && !image_dev) {
         if (!p->image_own)
             HIP_TRY(pool_alloc(p->device, (void **) &p->image_own, p->n_image * sizeof(double)));
@@ -992,13 +1010,17 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
     static_assert(sizeof(rt::DevCtl) % 8 == 0 && alignof(rt::DevCtl) >= 8, "zeroed in 8-byte words");
     // (exclusive mode writes every image row exactly once: its image is not zeroed)
     // (step mode: E_v and nf take the image's place in the zeroing launch, exclusive or not)
-    rc = step ? launch_zero3(stream, p->step_dev, p->step_doubles * sizeof(double), iang_dev, p->n_iang * sizeof(double), p->ctl, sizeof(rt::DevCtl))
+    rc = lent ? launch_zero4(stream, step_out.E_v, (size_t) p->P.K * sizeof(double), step_out.nf,
+                             (size_t) p->P.beam.nx * (size_t) p->P.beam.ny * sizeof(double), iang_dev, p->n_iang * sizeof(double), p->ctl, sizeof(rt::DevCtl))
+         : step ? launch_zero3(stream, p->step_dev, p->step_doubles * sizeof(double), iang_dev, p->n_iang * sizeof(double), p->ctl, sizeof(rt::DevCtl))
               : launch_zero3(stream, (p->P.exclusive || spectra) ? nullptr : image_dev, p->n_image * sizeof(double), iang_dev,
                              p->n_iang * sizeof(double), p->ctl, sizeof(rt::DevCtl));
     if (rc != RT_OK)
         return rc;
     p->P.image   = image_dev;
     p->P.iang    = iang_dev;
+    if (step)
+        p->step = step_out;
     p->P.n_tiles = (unsigned) ((p->n_rays + rt::WAVE - 1) / rt::WAVE);
     if (!p->ring.empty()) {
         const size_t slot = (size_t) (p->runs % (p->ring.size() / 3)) * 3;
@@ -1016,6 +1038,7 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
     p->last_iang   = iang_dev;
     p->last_spectra = spectra;
     p->last_step   = step;
+    p->last_step_lent = lent;
     p->spec_last   = p->spec_sel;
     p->ran         = true;
     p->queued      = false; // (`ran` + last_stream cover it from here)
@@ -1025,6 +1048,48 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
 }
 
 } // extern "C"
+
+// A run with more failing rays than the report holds (RT_N_FAILED_MAX): which of them the kernels let into the report
+// is decided by the order in which waves reach the counter of the control block -- two runs of the same rays, let alone
+// two partitions of them, report different rays.  After the checking repeat the marks say which rays fail with error
+// -2 / -3: the report becomes the first RT_N_FAILED_MAX of them in list order, the rays RayTraceImageCPULoop pushes first
+// (RayTraceImageCPU.cpp:32-33).  Fewer marked rays than that (the rest of the count are invalid rays, which carry no
+// mark): the report stays as the kernels left it.
+static int plan_report_first_failed(rt_hip_plan *p)
+{
+    const size_t n = (size_t) p->n_rays;
+    if (!p->bad_dev || p->bad_rays < n)
+        return RT_OK;
+    std::vector<unsigned char> bad(n);
+    HIP_TRY(hipMemcpy(bad.data(), p->bad_dev, n, hipMemcpyDeviceToHost));
+    const rt::DevRays &R = p->P.rays;
+    std::vector<double> g;
+    if (!R.list) {
+        g.resize((size_t) R.ngx + (size_t) R.ngy + (size_t) R.nga + (size_t) R.ngb);
+        HIP_TRY(hipMemcpy(g.data(), p->grid_dev, g.size() * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    rt_ray first[RT_N_FAILED_MAX];
+    int k = 0;
+    for (size_t t = 0; t < n && k < RT_N_FAILED_MAX; t++) {
+        if (!bad[t])
+            continue;
+        if (R.list) {
+            HIP_TRY(hipMemcpy(&first[k], R.list + t, sizeof(rt_ray), hipMemcpyDeviceToHost));
+        } else { // ray t of the grid: ijkm = first + t stride, b fastest (rt_hip_plan_set_ray_grid)
+            const long long ijkm = R.first + (long long) t * R.stride;
+            const long long m = ijkm % R.ngb, a = (ijkm / R.ngb) % R.nga, j = (ijkm / ((long long) R.ngb * R.nga)) % R.ngy,
+                            i = ijkm / ((long long) R.ngb * R.nga * R.ngy);
+            first[k].x = (float) g[(size_t) i];
+            first[k].y = (float) g[(size_t) R.ngx + (size_t) j];
+            first[k].a = (float) g[(size_t) R.ngx + (size_t) R.ngy + (size_t) a];
+            first[k].b = (float) g[(size_t) R.ngx + (size_t) R.ngy + (size_t) R.nga + (size_t) m];
+        }
+        k++;
+    }
+    if (k == RT_N_FAILED_MAX)
+        HIP_TRY(hipMemcpy(p->ctl->failed, first, sizeof(first), hipMemcpyHostToDevice));
+    return RT_OK;
+}
 
 // Wait for the last run and read the control block behind the chunk counters (failure code, failed rays, statistics);
 // a run whose frequency pass reported failing rays is repeated without them first.  `staged`: the outputs that
@@ -1053,6 +1118,12 @@ static int plan_settle(rt_hip_plan *p, rt::DevCtl &c, bool &staged)
         p->repeated   = true; // this run's outputs are final; a second fetch must not repeat again
         p->out_staged = staged = false;
         HIP_TRY(read_ctl());
+        if (c.n_failed > RT_N_FAILED_MAX) { // more failing rays than the report holds: the first of them in list order
+            const int rf = plan_report_first_failed(p);
+            if (rf != RT_OK)
+                return rf;
+            HIP_TRY(read_ctl());
+        }
     }
     return RT_OK;
 }

@@ -160,10 +160,10 @@ bool verify_ray_grid(const rt_ray *rays, size_t n, const GridGuess &G, unsigned 
     return ok.load();
 }
 
-int plan_set_guessed_grid(rt_hip_plan *p, const GridGuess &G, int64_t first, int64_t count)
+int plan_set_guessed_grid(rt_hip_plan *p, const GridGuess &G, int64_t first, int64_t count, int64_t stride)
 {
     return rt_hip_plan_set_ray_grid(p, G.g[0].data(), (int) G.g[0].size(), G.g[1].data(), (int) G.g[1].size(),
-                                    G.g[2].data(), (int) G.g[2].size(), G.g[3].data(), (int) G.g[3].size(), first, 1, count);
+                                    G.g[2].data(), (int) G.g[2].size(), G.g[3].data(), (int) G.g[3].size(), first, stride, count);
 }
 
 // x / d for every x < 2^31 as mulhi(x, mul) >> sh (DevRays::div_mul): with s = ceil(log2 d), mul = floor(2^(31+s) / d) + 1

@@ -7,7 +7,7 @@
 //   rt_raygrid.hip  a ray list that is really a tensor grid: recognition + bit-wise verification,
 //                   list-mode launch tangents and the probe of the host's libm
 //   rt_launch.hip   the kernels (rt_march.hip, rt_freq.hip, rt_path.hip, rt_spec.hip, rt_step.hip) and how a run puts them on a queue
-//   rt_multi.hip    all devices of the node: RCCL loader, communicator, rt_hip_multi_image_loop
+//   rt_multi.hip    all devices of the node: RCCL loader, communicator, rt_hip_multi_image_loop, rt_hip_multi_step_loop
 // Only rt_launch.hip and rt_multi.hip contain device code.
 #pragma once
 
@@ -55,7 +55,11 @@ struct rt_hip_plan {
     bool last_step     = false;   // the last run was a step run
     double *step_dev   = nullptr;
     size_t step_doubles = 0;      // doubles of the allocation
-    rt::StepOut step   = {};
+    rt::StepOut step   = {};      // E_v and nf of the last step run (the plan's own or the caller's)
+    // the caller's E_v [K] and nf [nx * ny] (rt_hip_plan_set_step_buffers; both NULL: the plan's own allocation above), taken
+    // by the next step run; last_step_lent: the last step run wrote the caller's
+    double *step_ev_lent = nullptr, *step_nf_lent = nullptr;
+    bool last_step_lent  = false;
     size_t rec_bytes   = 0;
     hipEvent_t evm     = nullptr; // between march and frequency kernels
     const rt_ray *host_rays = nullptr; // ray list still on the host, uploaded by the next run (rt_hip_image_loop)
@@ -165,7 +169,7 @@ struct GridGuess {
 inline bool same_bits(float a, float b) { return __builtin_memcmp(&a, &b, sizeof(float)) == 0; }
 bool guess_ray_grid(const rt_ray *rays, size_t n, GridGuess &G);
 bool verify_ray_grid(const rt_ray *rays, size_t n, const GridGuess &G, unsigned threads);
-int plan_set_guessed_grid(rt_hip_plan *p, const GridGuess &G, int64_t first, int64_t count);
+int plan_set_guessed_grid(rt_hip_plan *p, const GridGuess &G, int64_t first, int64_t count, int64_t stride = 1);
 // RayTraceImageCPU.cpp:11-16 on the host: grid point i (as the float a ray carries) falls into deposit cell i
 bool grid_points_in_own_cells(const double *g, int n, double d);
 // x / d for every x < 2^31 as mulhi(x, mul) >> sh (DevRays::div_mul)
@@ -185,5 +189,7 @@ int launch_seed_tab(const rt::DevSeed &sd, const rt::DevRays &R, size_t n_points
 int launch_selftest(unsigned long long *counts_dev);
 // zero up to three device ranges (8-byte multiples; NULL = none) with one launch
 int launch_zero3(hipStream_t stream, void *a, size_t a_bytes, void *b, size_t b_bytes, void *c, size_t c_bytes);
+// ... and four (a step run into the caller's E_v and nf: E_v, nf, I_ang, control block)
+int launch_zero4(hipStream_t stream, void *a, size_t a_bytes, void *b, size_t b_bytes, void *c, size_t c_bytes, void *d, size_t d_bytes);
 
 } // namespace rtr

@@ -15,6 +15,9 @@
 //   RayTraceImageStepHipLoop      the one-device loop with the per-step record (intensity_step_struct,
 //        src/RayTraceStructures.h:361-369) in place of the image cube: E_v[nv], the frequency-integrated image[nx*ny],
 //        I_ang -- through rt_hip_step_loop
+//   RayTraceImageStepHipMultiGPULoop  the same record from all devices of the node through rt_hip_multi_step_loop: device d
+//        traces rays d, d + ndev, ... of the grid on the full beam, one RCCL sum-reduce of (E_v | nf | I_ang) assembles
+//        them -- the application's multi-rank step (src/RayTraceImage.cpp:300-313, intensity_step_struct::sum_reduce)
 //   RayTraceCalcRaysHip           n calls of RayTrace::calc_ray (src/RayTraceImage.cpp:189-204) in one, through
 //        rt_hip_calc_rays: per-ray spectrum, exit ray and return code
 #include "RayTrace.h"
@@ -161,6 +164,32 @@ void RayTraceImageHipMultiGPULoop(int N, const RayTrace::EUV_beam_struct &beam,
     int rc = rt_hip_multi_image_loop(0, N, &f.beam, f.gain.data(), f.has_seed ? &f.seed : NULL, method,
                                      rays.empty() ? NULL : reinterpret_cast<const rt_ray *>(&rays[0]), rays.size(), scale,
                                      image, I_ang, &code, failed, RT_N_FAILED_MAX, &n_failed, &g_last_stats);
+    if (rc != RT_OK)
+        RAY_ERROR(std::string("HIP backend error: ") + rt_hip_last_error());
+    failure_code |= code;
+    for (int i = 0; i < n_failed; i++) {
+        ray_struct r;
+        memcpy(&r, &failed[i], sizeof(r));
+        failed_rays.push_back(r);
+    }
+}
+
+// RayTraceImageStepHipLoop on all devices of the node: same signature, same outputs up to summation order.  The cube
+// exists on no device; what crosses the links is one sum-reduce of nv + nx*ny + na*nb doubles.
+void RayTraceImageStepHipMultiGPULoop(int N, const RayTrace::EUV_beam_struct &beam, const RayTrace::ray_gain_struct *gain,
+    const RayTrace::ray_seed_struct *seed, int method, const std::vector<ray_struct> &rays, double scale,
+    double *E_v, double *nf, double *I_ang, unsigned int &failure_code, std::vector<ray_struct> &failed_rays)
+{
+    failure_code = 0;
+    if (rt_hip_device_count() < 1)
+        RAY_ERROR("Hip-MultiGPU is not availible");
+    Flat f = flatten(N, beam, gain, seed);
+    rt_ray failed[RT_N_FAILED_MAX];
+    int n_failed      = 0;
+    unsigned int code = 0;
+    int rc = rt_hip_multi_step_loop(0, N, &f.beam, f.gain.data(), f.has_seed ? &f.seed : NULL, method,
+                                    rays.empty() ? NULL : reinterpret_cast<const rt_ray *>(&rays[0]), rays.size(), scale,
+                                    E_v, nf, I_ang, &code, failed, RT_N_FAILED_MAX, &n_failed, &g_last_stats);
     if (rc != RT_OK)
         RAY_ERROR(std::string("HIP backend error: ") + rt_hip_last_error());
     failure_code |= code;

@@ -11,6 +11,9 @@ shard / Assembler (one process per GPU, torch.distributed; backend "nccl" is RCC
     seeded : source columns are dealt the same way, every rank holds a full private image, assembly
              is ONE sum-reduce of (image | I_ang) (the analogue of intensity_step_struct::sum_reduce,
              src/RayTraceStructures.cpp:1603-1646).
+StepAssembler (the same form for the application's per-step record): every rank runs step mode on the FULL beam over
+    rays rank, rank + world, ... (src/RayTraceImage.cpp:300-313) into one buffer (E_v | nf | I_ang); assembly is ONE
+    sum-reduce of that buffer -- nv + nx ny + na nb doubles, never the cube.
 """
 from __future__ import annotations
 
@@ -121,3 +124,70 @@ def assemble(problem: Problem, tile_image, tile_iang, rank: int, world: int, gro
     if img is None:
         return None, None
     return img.clone(), ang.clone()
+
+
+class StepAssembler:
+    """Per-rank step record and the ONE collective per step that sums it on rank `dst`.
+
+    `buffer` = (E_v [nv] | nf [nx * ny] | I_ang [na * nb]) on the full beam, the same length on every rank; `E_v`, `nf`
+    and `iang` are views of it.  attach(plan) lends them to a plan in step mode (Plan.set_step_buffers for E_v and nf;
+    I_ang goes to Plan.run(iang_ptr=a.iang_ptr)) and deals the rays out as the application deals them to its ranks:
+    plan.set_ray_grid(first=rank, stride=world).  assemble() is one torch.distributed.reduce(SUM) of the buffer to rank
+    dst -- the analogue of intensity_step_struct::sum_reduce (src/RayTraceStructures.cpp:1603-1646); world 1 takes no
+    collective.  Backend "nccl" is RCCL on ROCm; the CPU tests run the same code over gloo."""
+
+    def __init__(self, problem: Problem, rank: int, world: int, device=None, group=None, dst: int = 0,
+                 via_host: bool = False):
+        import torch
+
+        b = problem.beam
+        self.problem, self.rank, self.world, self.group, self.dst = problem, rank, world, group, dst
+        self.n_v, self.n_pix, self.n_ang = b.nv, b.nx * b.ny, b.na * b.nb
+        # (on an axis of one grid point a ray can land one cell behind the array, include/rt_hip.h: nf and I_ang are then
+        # followed by spare cells, which travel with the record and are not part of the views)
+        self._nf_spare = b.nx + 2 if min(b.nx, b.ny) < 2 else 0
+        self._ang_spare = b.na + 2 if min(b.na, b.nb) < 2 else 0
+        self._ang_off = self.n_v + self.n_pix + self._nf_spare
+        dev = device if device is not None else torch.device("cpu")
+        self.buffer = torch.zeros(self._ang_off + self.n_ang + self._ang_spare, dtype=torch.float64, device=dev)
+        self.E_v = self.buffer[:self.n_v]
+        self.nf = self.buffer[self.n_v:self.n_v + self.n_pix]
+        self.iang = self.buffer[self._ang_off:self._ang_off + self.n_ang]
+        self.via_host = via_host and dev.type != "cpu"
+        self.last_collective = None  # what the last assemble() ran, for describe()
+
+    @property
+    def iang_ptr(self) -> int:
+        return self.iang.data_ptr()
+
+    def attach(self, plan):
+        """Step mode on `plan` with E_v and nf in this buffer and this rank's rays of the problem's ray grid; run it with
+        plan.run(stream, iang_ptr=self.iang_ptr)."""
+        plan.enable_step().set_step_buffers(self.E_v.data_ptr(), self.nf.data_ptr())
+        plan.set_ray_grid(first=self.rank, stride=self.world)
+        return plan
+
+    def describe(self) -> str:
+        plan = (f"reduce(sum, f64) of {self.buffer.numel() * 8} B (E_v | nf | I_ang) to rank {self.dst}, rays "
+                f"{self.rank} + it * {self.world}")
+        ran = self.last_collective or "none yet"
+        return f"{plan}; last run: {ran}"
+
+    def _views(self, buf):
+        return (buf[:self.n_v], buf[self.n_v:self.n_v + self.n_pix], buf[self._ang_off:self._ang_off + self.n_ang])
+
+    def assemble(self, buffer=None):
+        """Returns dict(E_v, nf, I_ang) of flat tensors on rank dst, None elsewhere."""
+        import torch.distributed as dist
+
+        buf = self.buffer if buffer is None else buffer
+        if self.world > 1:
+            if self.via_host:
+                buf = buf.cpu()
+            backend = dist.get_backend(self.group) + (" via host copies" if self.via_host else "")
+            dist.reduce(buf, dst=self.dst, op=dist.ReduceOp.SUM, group=self.group)
+            self.last_collective = f"torch.distributed.reduce(SUM) over {backend}, world {self.world}"
+            if self.rank != self.dst:
+                return None
+        E_v, nf, iang = self._views(buf)
+        return dict(E_v=E_v, nf=nf, I_ang=iang)
