@@ -378,6 +378,39 @@ int rt_hip_step_loop(int device, int N, const rt_beam *beam, const rt_gain *gain
                      const rt_ray *rays, size_t n_rays, double scale, double *E_v, double *nf, double *I_ang,
                      unsigned int *failure_code, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats);
 
+/*
+ * The gain tables of a resident plan replaced in place: a time loop whose plasma evolves has new n, g0, E0 and gv on the
+ * same grids at every step, and keeps its plan -- ray grid, tangent and seed-factor tables, output mode, lent step
+ * buffers, probe and timing ring included.  rt_gain_values holds the values of one length, in the shapes of the rt_gain
+ * the plan was created with (gv: [cells][K], tight).  vals[0] is ignored as gain[0] is; N must equal the plan's; n, g0 and
+ * gv must be non-NULL for lengths 1 .. N-1; E0 may be NULL and packs as zeros, as at creation.  use_emis, the grids, K,
+ * the beam and the seed stay as created.
+ *   Both calls first settle the plan's last run as rt_hip_plan_fetch does before it copies (wait, control block, the
+ *   checking repeat of a run with error -2 / -3), so that a later fetch of that run serves ITS tables' result; device
+ *   buffers of that run stay valid.
+ *   Then: scan, validate, pack (raytrace-miniapp_amd/csrc/rt_tables.hip).  No run ever reads tables whose scan has not
+ *   passed: a non-finite index of refraction -- on which the integrator would never advance -- a NULL pointer or a wrong N
+ *   is RT_ERR_ARG and leaves every table of the plan untouched.  The scan recomputes, bit for bit, the four facts
+ *   rt_hip_plan_create derives from the tables and every run is chosen by (rt_hip_plan_table_flags).
+ *   update_gain_dev: device pointers, each checked to be device memory of the plan's device (anything else is
+ *   RT_ERR_ARG).  The call enqueues on `stream`, waits once for the scan's summary, enqueues the pack and records an
+ *   event, which the next rt_hip_plan_run waits for on whatever stream it runs.  The inputs follow stream semantics:
+ *   unchanged until the work enqueued on `stream` has completed.
+ *   update_gain: host pointers, free when the call returns: the raw values are uploaded into a scratch block and take
+ *   the same device path.
+ * table_flags: tables_bounded, ntest_proven (see rt_hip_plan_last_march_instance), whether a lineshape value is a NaN or
+ * an infinity (emission mode), and gs_cap = 708 / max |gv|.  Any pointer may be NULL.
+ */
+typedef struct rt_gain_values {
+    const double *n; /* [Nx*Ny] */
+    const float *g0; /* [Nx*Ny] */
+    const float *E0; /* [Nx*Ny], may be NULL */
+    const float *gv; /* [Nx*Ny*Nv] */
+} rt_gain_values;
+int rt_hip_plan_update_gain(rt_hip_plan *plan, int N, const rt_gain_values *vals);
+int rt_hip_plan_update_gain_dev(rt_hip_plan *plan, int N, const rt_gain_values *vals, void *stream);
+int rt_hip_plan_table_flags(rt_hip_plan *plan, int *bounded, int *ntest_proven, int *gv_nonfinite, float *gs_cap);
+
 /* Profiling aid (no reference counterpart): bit 0 = skip the frequency / deposit kernel, bit 1 = skip
  * the march and run the frequency pass over the records of the previous run of this plan, bit 2 = the
  * frequency kernel keeps its per-work-group I_ang sums to itself (I_ang stays zero).  0 = normal. */

@@ -268,6 +268,44 @@ class Plan:
         ang = self.iang_ptr
         return dict(E_v=view(e, (b.nv,)), nf=view(n, (b.ny, b.nx)), I_ang=view(ang, (b.nb, b.na)) if ang else None)
 
+    # -- tables -------------------------------------------------------------
+    def update_gain(self, gain, stream: int | None = None) -> "Plan":
+        """New n, g0, E0 and gv on the plan's grids (include/rt_hip.h, rt_hip_plan_update_gain): everything else about the
+        plan stays -- rays, output mode, lent buffers, probe.  `gain`: a Problem, a list of Gain, or a list of per-length
+        dicts / tuples (n, g0, E0, gv); entry 0 is ignored.  numpy arrays take the host call; torch tensors on the plan's
+        device take the device call on `stream` (a hipStream_t value; default: torch's current stream, so that the
+        allocator's ordering holds) and must stay unchanged until the work on that stream has completed.  Shapes, dtypes
+        and contiguity are checked here (ValueError); a table the scan rejects -- a non-finite index of refraction -- raises
+        RayTraceError and leaves the plan as it was.  With host arrays, self.problem is replaced by one that carries the
+        new tables."""
+        import copy
+        import dataclasses
+
+        old = self.problem.gain
+        gv = cabi.GainValues(gain, [(g.Nx, g.Ny) for g in old], self.problem.beam.nv, self.device)
+        if gv.on_device:
+            if stream is None:
+                import torch
+                stream = torch.cuda.current_stream(self.device).cuda_stream
+            rc = self.hl.lib.rt_hip_plan_update_gain_dev(self._h, gv.N, gv.vals, C.c_void_p(stream))
+            self.hl.check(rc, "rt_hip_plan_update_gain_dev")
+            self._gain_dev = gv           # (the tensors live at least until the next update)
+        else:
+            self.hl.check(self.hl.lib.rt_hip_plan_update_gain(self._h, gv.N, gv.vals), "rt_hip_plan_update_gain")
+            q = copy.copy(self.problem)
+            q.gain = [old[0]] + [dataclasses.replace(old[i], n=t[0], g0=t[1], E0=t[2], gv=t[3]) for i, t in enumerate(gv.tables) if i]
+            q.golden_image = q.golden_I_ang = None
+            self.problem = q
+        return self
+
+    def table_flags(self) -> dict:
+        """The four facts of the tables every run is chosen by (rt_hip_plan_table_flags): bounded, ntest_proven,
+        gv_nonfinite (0 / 1) and gs_cap (numpy float32)."""
+        b, t, g, cap = C.c_int(0), C.c_int(0), C.c_int(0), C.c_float(0)
+        self.hl.check(self.hl.lib.rt_hip_plan_table_flags(self._h, C.byref(b), C.byref(t), C.byref(g), C.byref(cap)),
+                      "rt_hip_plan_table_flags")
+        return dict(bounded=b.value, ntest_proven=t.value, gv_nonfinite=g.value, gs_cap=np.float32(cap.value))
+
     def kernel_ms(self) -> float:
         """Device time of the last run's trace kernel (waits for it)."""
         ms = C.c_float(0)

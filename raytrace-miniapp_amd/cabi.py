@@ -47,6 +47,11 @@ class RtGain(C.Structure):
     ]
 
 
+class RtGainValues(C.Structure):
+    """rt_gain_values: the values of one length of a table update, shapes as in the RtGain the plan was created with."""
+    _fields_ = [("n", c_double_p), ("g0", c_float_p), ("E0", c_float_p), ("gv", c_float_p)]
+
+
 class RtSeed(C.Structure):
     _fields_ = [
         ("dim", C.c_int32 * 5),
@@ -110,6 +115,83 @@ class Marshalled:
     @property
     def seed_ref(self):
         return C.byref(self.seed) if self.seed is not None else None
+
+
+def _is_tensor(a) -> bool:
+    return hasattr(a, "data_ptr") and hasattr(a, "is_cuda")   # a torch tensor, without importing torch
+
+
+class GainValues:
+    """The tables of a Plan.update_gain laid out as rt_gain_values[N]; holds a reference to every array it points into.
+
+    `gain`: a Problem, or N entries (entry 0 is ignored and may be None) that are Gain records, dicts with the keys
+    n, g0, E0 (optional), gv, or tuples (n, g0, E0, gv); E0 may be None.  `shapes` = [(Nx, Ny)] * N and K are the plan's.
+    Either all arrays are numpy arrays (on_device False: rt_hip_plan_update_gain) or all are torch tensors on
+    cuda:`device` (on_device True: rt_hip_plan_update_gain_dev).  Everything else is a ValueError, raised here, before any
+    native call: wrong N, shapes, dtypes (float64 for n, float32 for the rest), non-contiguous arrays, a tensor on the
+    CPU or on another device, host and device arrays mixed."""
+
+    def __init__(self, gain, shapes, K: int, device: int = 0):
+        entries = list(gain.gain) if hasattr(gain, "gain") and hasattr(gain, "beam") else list(gain)
+        if len(entries) != len(shapes):
+            raise ValueError(f"update_gain: {len(entries)} lengths given, the plan has N = {len(shapes)}")
+        self.N = len(entries)
+        self.vals = (RtGainValues * self.N)()
+        self.tables = [None] * self.N      # per length (n, g0, E0, gv) as given
+        self._keep = []
+        kinds = set()
+        for i in range(1, self.N):
+            e = entries[i]
+            if isinstance(e, dict):
+                t = (e["n"], e["g0"], e.get("E0"), e["gv"])
+            elif isinstance(e, (tuple, list)):
+                if len(e) != 4:
+                    raise ValueError(f"update_gain: length {i}: expected (n, g0, E0, gv)")
+                t = tuple(e)
+            elif e is not None and all(hasattr(e, k) for k in ("n", "g0", "E0", "gv")):
+                t = (e.n, e.g0, e.E0, e.gv)
+            else:
+                raise ValueError(f"update_gain: length {i}: expected a Gain, a dict or a tuple (n, g0, E0, gv)")
+            Nx, Ny = shapes[i]
+            cells = Nx * Ny
+            ptrs = []
+            for name, a, dt, ok_shapes in (("n", t[0], "float64", ((cells,), (Ny, Nx))), ("g0", t[1], "float32", ((cells,), (Ny, Nx))),
+                                           ("E0", t[2], "float32", ((cells,), (Ny, Nx))),
+                                           ("gv", t[3], "float32", ((cells * K,), (cells, K), (Ny, Nx, K)))):
+                if a is None:
+                    if name != "E0":
+                        raise ValueError(f"update_gain: length {i}: {name} is missing (only E0 may be None)")
+                    ptrs.append(None)
+                    continue
+                if _is_tensor(a):
+                    if not a.is_cuda:
+                        raise ValueError(f"update_gain: length {i}: {name} is a torch tensor on the CPU (pass numpy arrays, or tensors on the plan's device)")
+                    if a.device.index != device:
+                        raise ValueError(f"update_gain: length {i}: {name} is on {a.device}, the plan on device {device}")
+                    kinds.add("device")
+                    dtype, shape, contiguous = str(a.dtype).replace("torch.", ""), tuple(a.shape), a.is_contiguous()
+                    addr = a.data_ptr()
+                elif isinstance(a, np.ndarray):
+                    kinds.add("host")
+                    dtype, shape, contiguous = str(a.dtype), a.shape, a.flags.c_contiguous
+                    addr = a.ctypes.data
+                else:
+                    raise ValueError(f"update_gain: length {i}: {name} is neither a numpy array nor a torch tensor")
+                if dtype != dt:
+                    raise ValueError(f"update_gain: length {i}: {name} has dtype {dtype}, expected {dt}")
+                if shape not in ok_shapes:
+                    raise ValueError(f"update_gain: length {i}: {name} has shape {shape}, the plan's tables have {ok_shapes[-1]}")
+                if not contiguous:
+                    raise ValueError(f"update_gain: length {i}: {name} is not contiguous")
+                self._keep.append(a)
+                ptrs.append(addr)
+            if len(kinds) > 1:
+                raise ValueError("update_gain: host (numpy) and device (torch) arrays mixed in one update")
+            self.tables[i] = t
+            self.vals[i] = RtGainValues(C.cast(ptrs[0], c_double_p), C.cast(ptrs[1], c_float_p),
+                                        C.cast(ptrs[2], c_float_p) if ptrs[2] is not None else c_float_p(),
+                                        C.cast(ptrs[3], c_float_p))
+        self.on_device = kinds == {"device"}
 
 
 def rays_ptr(rays: np.ndarray):
@@ -231,6 +313,13 @@ def declare_hip_api(lib: C.CDLL) -> None:
         lib.rt_hip_plan_set_step_buffers.restype = C.c_int
         lib.rt_hip_multi_step_loop.argtypes = list(lib.rt_hip_step_loop.argtypes)
         lib.rt_hip_multi_step_loop.restype = C.c_int
+    if hasattr(lib, "rt_hip_plan_update_gain"):   # (likewise)
+        lib.rt_hip_plan_update_gain.argtypes = [vp, C.c_int, P(RtGainValues)]
+        lib.rt_hip_plan_update_gain.restype = C.c_int
+        lib.rt_hip_plan_update_gain_dev.argtypes = [vp, C.c_int, P(RtGainValues), vp]
+        lib.rt_hip_plan_update_gain_dev.restype = C.c_int
+        lib.rt_hip_plan_table_flags.argtypes = [vp, P(C.c_int), P(C.c_int), P(C.c_int), c_float_p]
+        lib.rt_hip_plan_table_flags.restype = C.c_int
     lib.rt_hip_plan_set_debug.argtypes = [vp, C.c_uint]
     lib.rt_hip_plan_set_debug.restype = C.c_int
     lib.rt_hip_plan_destroy.argtypes = [vp]
@@ -247,5 +336,6 @@ HIP_API_SYMBOLS = [
     "rt_hip_plan_fetch_path", "rt_hip_plan_enable_spectra", "rt_hip_plan_fetch_spectra", "rt_hip_plan_spectra_ptr",
     "rt_hip_calc_rays", "rt_hip_plan_enable_step", "rt_hip_plan_fetch_step", "rt_hip_plan_step_ptrs", "rt_hip_step_loop",
     "rt_hip_plan_set_step_buffers", "rt_hip_multi_step_loop",
+    "rt_hip_plan_update_gain", "rt_hip_plan_update_gain_dev", "rt_hip_plan_table_flags",
     "rt_hip_plan_set_debug", "rt_hip_plan_destroy",
 ]

@@ -180,6 +180,16 @@ void rt_hip_plan_destroy(rt_hip_plan *p)
     }
     for (hipEvent_t e : p->ring) // (with a ring, ev0 / evm / ev1 alias one of its slots)
         (void) hipEventDestroy(e);
+    if (p->tab_ev) { // the pack of a table update no run has waited for reads tab_work (rt_tables.hip)
+        if (hipEventSynchronize(p->tab_ev) != hipSuccess)
+            (void) hipGetLastError();
+        (void) hipEventDestroy(p->tab_ev);
+    }
+    for (hipEvent_t e : p->tab_t)
+        if (e)
+            (void) hipEventDestroy(e);
+    pool_free(p->device, p->tab_work);
+    pinned_free(p->tab_pin);
 
     pool_free(p->device, p->tan_dev);
     pool_free(p->device, p->rec);
@@ -352,6 +362,7 @@ int rtr::plan_create_on(rt_hip_plan **out, hipStream_t upload_q, int device, int
     // verbatim by rt_march_kernel<true>
     std::vector<unsigned char> blob(align_up(sizeof(rt::BlobGain) * (size_t) N, 16));
     bool tiny_spacing = false, bad_index = false, all_bounded = true, ntest_proven = true;
+    p->tab.assign((size_t) N, rt_hip_plan::TableShape());
     for (int i = 1; i < N; i++) {
         const rt_gain &g  = gain[i];
         const size_t npix = (size_t) g.Nx * (size_t) g.Ny;
@@ -446,11 +457,18 @@ int rtr::plan_create_on(rt_hip_plan **out, hipStream_t upload_q, int device, int
             const double fy = g.y[0] >= 0.0 ? std::max(1.2, 1.0 + 2.0 * g.y[0] / (g.y[1] - g.y[0])) : 1.2;
             if (!(8.0 * 0.1 * (1.2 + fy) * dn <= 0.05 - 1e-5))
                 ntest_proven = false;
+            // (the grids stay; rt_hip_plan_update_gain scans new values against these)
+            p->tab[(size_t) i].Nx    = g.Nx;
+            p->tab[(size_t) i].Ny    = g.Ny;
+            p->tab[(size_t) i].w_min = w_min;
+            p->tab[(size_t) i].fy    = fy;
+            p->tab[(size_t) i].off_node = (size_t) h.off_node;
         }
     }
     // (dz: a straight ray in a medium without refraction advances by up to 1250 cm per integrator step, Helper.h:288-297;
     // 1e6 cm keeps a sub-segment within a few hundred steps -- beyond it the instance with the watchdog marches)
-    if (!(beam->dz >= 1e-12 && beam->dz <= 1e6))
+    p->dz_bounded = beam->dz >= 1e-12 && beam->dz <= 1e6;
+    if (!p->dz_bounded)
         all_bounded = false;
     p->tables_bounded = all_bounded;
     p->ntest_proven   = all_bounded && ntest_proven;
@@ -1005,6 +1023,14 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
     // from here on work is queued: whatever happens below, destroy / quiesce must wait for this queue
     p->queued_stream = stream;
     p->queued        = true;
+    if (p->tab_pending) { // tables rewritten by rt_hip_plan_update_gain, possibly on another queue: not read before the pack is done
+        if (hipEventQuery(p->tab_ev) == hipSuccess) {
+            p->tab_pending = false;
+        } else {
+            (void) hipGetLastError(); // (hipErrorNotReady)
+            HIP_TRY(hipStreamWaitEvent(stream, p->tab_ev, 0));
+        }
+    }
     if (p->probe_on && p->n_rays)
         HIP_TRY(hipMemsetAsync(p->probe, 0, (size_t) p->n_rays * (sizeof(rt_ray) + 8), stream));
     static_assert(sizeof(rt::DevCtl) % 8 == 0 && alignof(rt::DevCtl) >= 8, "zeroed in 8-byte words");
@@ -1126,6 +1152,13 @@ static int plan_settle(rt_hip_plan *p, rt::DevCtl &c, bool &staged)
         }
     }
     return RT_OK;
+}
+
+int rtr::plan_settle_last_run(rt_hip_plan *p)
+{
+    rt::DevCtl c;
+    bool staged = false;
+    return plan_settle(p, c, staged);
 }
 
 extern "C" {

@@ -1,6 +1,6 @@
 // rt_runtime.h -- what the host-side translation units of librt_hip.so share (internal, not part of the C ABI).
 //
-// The C ABI of include/rt_hip.h is implemented by five translation units:
+// The C ABI of include/rt_hip.h is implemented by six translation units:
 //   rt_pool.hip     error text, device-memory pool, leased queues, environment overrides
 //   rt_plan.hip     the plan: arena packing, ray list / ray grid, run, fetch, probe and path outputs,
 //                   rt_hip_image_loop (the host-pointer entry the C++ adapter calls)
@@ -8,7 +8,8 @@
 //                   list-mode launch tangents and the probe of the host's libm
 //   rt_launch.hip   the kernels (rt_march.hip, rt_freq.hip, rt_path.hip, rt_spec.hip, rt_step.hip) and how a run puts them on a queue
 //   rt_multi.hip    all devices of the node: RCCL loader, communicator, rt_hip_multi_image_loop, rt_hip_multi_step_loop
-// Only rt_launch.hip and rt_multi.hip contain device code.
+//   rt_tables.hip   the gain tables of a resident plan rewritten in place: scan and pack kernels, rt_hip_plan_update_gain
+// Only rt_launch.hip, rt_multi.hip and rt_tables.hip contain device code.
 #pragma once
 
 #include "rt_device.h"
@@ -109,6 +110,22 @@ struct rt_hip_plan {
     bool last_fused       = false;
     // LDS a work-group may ask for on this device (hipDeviceAttributeMaxSharedMemoryPerBlock; 160 KB on gfx950)
     size_t lds_limit      = 0;
+    // rt_hip_plan_update_gain (rt_tables.hip).  What rt_hip_plan_create derives from the GRIDS of a length, kept so that
+    // an update recomputes tables_bounded and ntest_proven from the scan of the new values alone, and where its nodes lie
+    struct TableShape {
+        int Nx = 0, Ny = 0;
+        double w_min = 0.0;                // smallest grid spacing of both axes
+        double fy    = 1.2;                // weight of the edge differences of gyn (mirrored half plane)
+        size_t off_node = 0;               // Node[Nx * Ny] of the length: byte offset inside the march blob
+    };
+    std::vector<TableShape> tab; // [N], entry 0 unused
+    bool dz_bounded = false;     // beam.dz lies in the range tables_bounded asks for
+    unsigned char *tab_work = nullptr; // device: [descriptors | partials of the scan], grown on demand
+    unsigned char *tab_pin  = nullptr; // ... and its page-locked twin
+    size_t tab_work_bytes   = 0;
+    hipEvent_t tab_ev = nullptr; // behind the pack of the last update: the next run waits for it on its own queue
+    bool tab_pending  = false;
+    hipEvent_t tab_t[3] = { nullptr, nullptr, nullptr }; // RT_HIP_TIMING: before / behind the scan, before the pack
 };
 
 namespace rtr {
@@ -159,6 +176,9 @@ void plan_stage_outputs(rt_hip_plan *p);
 // what rt_hip_plan_create does).  Everything that reads the tables must then run on that queue, or after a wait for it.
 int plan_create_on(rt_hip_plan **out, hipStream_t upload_q, int device, int N, const rt_beam *beam, const rt_gain *gain,
                    const rt_seed *seed, int method, double scale);
+// what rt_hip_plan_fetch does before it copies: wait for the last run, read the control block, repeat a run whose rays
+// failed with -2 / -3 in the checking mode (the plan must have run)
+int plan_settle_last_run(rt_hip_plan *p);
 // most rays a list may hold (the kernels index rays with 32 bits)
 extern const size_t MAX_LIST_RAYS;
 

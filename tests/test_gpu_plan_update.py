@@ -1,0 +1,345 @@
+"""Plan.update_gain on the GPU (rt_table_scan_kernel, rt_table_pack_kernel): a resident plan whose tables are replaced
+must be indistinguishable from a plan freshly created on the same tables.
+
+Gates:
+    march records through the probe (gvl, evl, ivl, steps, flags, ray2)    bit-identical to the fresh plan's
+    table_flags() (bounded, ntest_proven, gv_nonfinite, gs_cap)            equal, gs_cap bit for bit
+    image and I_ang against the fresh plan                                 element_gate.reordering_tol(n_e, K)
+    image and I_ang against the oracle on the new tables                   DEFAULT_TIER (emission), TIGHT_TIER (seeded)
+    step outputs against the reductions of the oracle's cube               the bounds of tests/test_gpu_step.py
+Every case is a sparse ray list of the shipped fixtures (about 4 K rays)."""
+import copy
+import importlib
+
+import numpy as np
+import pytest
+
+import table_variants as tv
+from element_gate import DEFAULT_TIER, EPS, TIGHT_TIER, assert_elements, contribution_counts, counts_from_oracle, gate_outputs
+
+rt = importlib.import_module("raytrace-miniapp_amd")
+problem_mod = importlib.import_module("raytrace-miniapp_amd.problem")
+pytestmark = pytest.mark.gpu
+
+RECORD_KEYS = ("gvl", "evl", "ivl", "steps", "flags", "ray2")
+
+
+# ---------------------------------------------------------------------------------------------- helpers
+def run_probed(plan):
+    """(outputs, march records) of one run of a plan with the probe enabled."""
+    out = plan.run().fetch()
+    return out, plan.fetch_probe()
+
+
+def same_records(got, want, label):
+    for key in RECORD_KEYS:
+        a, b = np.ascontiguousarray(got[key]), np.ascontiguousarray(want[key])
+        assert np.array_equal(a.view(np.uint32) if a.dtype != np.int32 else a, b.view(np.uint32) if b.dtype != np.int32 else b), \
+            f"{label}: march records differ in {key}"
+
+
+def same_flags(got, want, label):
+    assert {k: got[k] for k in ("bounded", "ntest_proven", "gv_nonfinite")} == {k: want[k] for k in ("bounded", "ntest_proven", "gv_nonfinite")}, \
+        f"{label}: {got} against {want}"
+    assert np.float32(got["gs_cap"]).view(np.uint32) == np.float32(want["gs_cap"]).view(np.uint32), f"{label}: gs_cap {got['gs_cap']!r} against {want['gs_cap']!r}"
+
+
+def ray_set(rays):
+    return sorted(tuple(np.asarray(r.tolist(), dtype=np.float32).view(np.uint32).tolist()) for r in rays)
+
+
+def on_device(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
+
+
+def fresh(hip, p, rays):
+    with hip.Plan(p) as plan:
+        plan.set_rays(rays).enable_probe()
+        out, rec = run_probed(plan)
+        return out, rec, plan.table_flags()
+
+
+def update(plan, p, path):
+    """p's tables into the plan from numpy arrays or from torch tensors on the device."""
+    return plan.update_gain(p if path == "host" else tv.as_tables(p, on_device))
+
+
+def sparse_rays(p, stride):
+    return p.build_rays(np.arange(0, p.n_rays_total, stride, dtype=np.int64))
+
+
+def updated_against_fresh_and_oracle(hip, oracle, a, b, rays, tier, label, path="host", counts=None):
+    """Create on a, run, update to b, run: records and flags of the fresh plan on b, outputs within the reordering of the
+    fresh plan's and within the tier of the oracle's.  Returns what the updated plan gave."""
+    with hip.Plan(a) as plan:
+        plan.set_rays(rays).enable_probe()
+        run_probed(plan)
+        update(plan, b, path)
+        flags = plan.table_flags()
+        out, rec = run_probed(plan)
+    want, want_rec, want_flags = fresh(hip, b, rays)
+    ora = oracle.image_loop(b, rays, n_threads=4)
+    assert out["failure_code"] == want["failure_code"] == ora["failure_code"] == 0, label
+    assert out["stats"]["cell_steps"] == want["stats"]["cell_steps"] == ora["counters"]["cell_steps"], label
+    same_records(rec, want_rec, label)
+    same_flags(flags, want_flags, label)
+    if counts is None:
+        counts = contribution_counts(b, rays) if b.seed is None else counts_from_oracle(oracle, b, rays, n_threads=4)
+    gate_outputs(out, want, b, counts, "reordering", f"{label} / updated against a fresh plan")
+    gate_outputs(out, ora, b, counts, tier, f"{label} / updated against the oracle")
+    return out, rec, flags
+
+
+@pytest.fixture(scope="module")
+def ase(hip, oracle, ase_small):
+    """ASE_small, every 97th ray, tables A and B: the fresh plans' records, outputs and flags, computed once."""
+    a, b = ase_small, tv.tables_b(ase_small)
+    rays = sparse_rays(a, 97)
+    assert 4000 <= len(rays) <= 4200
+    out_a, rec_a, flags_a = fresh(hip, a, rays)
+    out_b, rec_b, flags_b = fresh(hip, b, rays)
+    assert not np.array_equal(rec_a["gvl"], rec_b["gvl"]) and not np.array_equal(rec_a["steps"], rec_b["steps"]), \
+        "B must march differently from A, or nothing below tests anything"
+    return dict(a=a, b=b, rays=rays, counts=contribution_counts(a, rays), out_a=out_a, rec_a=rec_a, flags_a=flags_a,
+                out_b=out_b, rec_b=rec_b, flags_b=flags_b)
+
+
+# ---------------------------------------------------------------------------------------------- 1. time loop
+def test_time_loop(hip, oracle, ase):
+    a, b, rays = ase["a"], ase["b"], ase["rays"]
+    with hip.Plan(a) as plan:
+        plan.set_rays(rays).enable_probe()
+        out0, rec0 = run_probed(plan)
+        same_records(rec0, ase["rec_a"], "tables A, first run")
+        assert plan.update_gain(b) is plan
+        assert plan.problem is not a and np.shares_memory(plan.problem.gain[1].g0, b.gain[1].g0) and plan.problem.beam is a.beam
+        same_flags(plan.table_flags(), ase["flags_b"], "A -> B")
+        out1, rec1 = run_probed(plan)
+        plan.update_gain(a.gain)                                   # a list of Gain
+        same_flags(plan.table_flags(), ase["flags_a"], "A -> B -> A")
+        out2, rec2 = run_probed(plan)
+    ora = oracle.image_loop(b, rays, n_threads=4)
+    assert out1["failure_code"] == ora["failure_code"] == 0 and out1["stats"]["cell_steps"] == ora["counters"]["cell_steps"]
+    same_records(rec1, ase["rec_b"], "A -> B")
+    gate_outputs(out1, ase["out_b"], b, ase["counts"], "reordering", "A -> B / updated against a fresh plan")
+    gate_outputs(out1, ora, b, ase["counts"], DEFAULT_TIER, "A -> B / updated against the oracle")
+    same_records(rec2, rec0, "A -> B -> A: nothing stale survives")
+    gate_outputs(out2, out0, a, ase["counts"], "reordering", "A -> B -> A against the first run")
+
+
+# ---------------------------------------------------------------------------------------------- 2. device path
+def test_device_path(hip, ase):
+    import torch
+
+    a, b, rays = ase["a"], ase["b"], ase["rays"]
+    with hip.Plan(a) as plan:
+        plan.set_rays(rays).enable_probe()
+        run_probed(plan)
+        tensors = tv.as_tables(b, on_device)
+        plan.update_gain(tensors)                                  # on torch's current stream
+        assert plan.problem is a, "device tables: the host-side problem is left alone"
+        same_flags(plan.table_flags(), ase["flags_b"], "device path")
+        out, rec = run_probed(plan)
+        same_records(rec, ase["rec_b"], "device path")
+        gate_outputs(out, ase["out_b"], b, ase["counts"], "reordering", "device path / updated against a fresh plan")
+        # back to A on a side stream, the run on the default stream: the run waits for the pack's event
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            back = tv.as_tables(a, on_device)
+            plan.update_gain(back, stream=side.cuda_stream)
+        same_flags(plan.table_flags(), ase["flags_a"], "device path, side stream")
+        out, rec = run_probed(plan)
+        same_records(rec, ase["rec_a"], "device path, side stream")
+        torch.cuda.synchronize()
+    # the C entry refuses what is not device memory of the plan's device, before anything is enqueued
+    with hip.Plan(a) as plan:
+        plan.set_rays(rays).enable_probe()
+        m = rt.cabi.GainValues(b, [(g.Nx, g.Ny) for g in a.gain], a.beam.nv)       # numpy arrays: host pointers
+        rc = plan.hl.lib.rt_hip_plan_update_gain_dev(plan._h, m.N, m.vals, None)
+        assert rc == rt.cabi.RT_ERR_ARG and b"not device memory" in plan.hl.lib.rt_hip_last_error()
+        same_flags(plan.table_flags(), ase["flags_a"], "refused host pointers")
+        same_records(run_probed(plan)[1], ase["rec_a"], "refused host pointers")
+
+
+# ---------------------------------------------------------------------------------------------- 3. row padding
+def one_frequency(p):
+    q = copy.copy(p)
+    q.beam = copy.copy(p.beam)
+    q.beam.dv = np.ascontiguousarray(p.beam.dv[20:21])
+    K = p.beam.nv
+    q.gain = [rt.Gain(g.x, g.y, g.n, g.g0, g.E0, g.gv.reshape(-1, K)[:, 20:21].copy(), 1) for g in p.gain]
+    return q
+
+
+@pytest.mark.parametrize("path", ["host", "device"])
+def test_row_padding_seeded_nv_82(hip, oracle, seed_small, path):
+    assert seed_small.beam.nv == 82                                # Kp = 84: two padding columns per row
+    rays = sparse_rays(seed_small, 1201)
+    assert 4000 <= len(rays) <= 8000
+    updated_against_fresh_and_oracle(hip, oracle, seed_small, tv.tables_b(seed_small), rays, TIGHT_TIER, f"seed_small, nv 82, {path}", path)
+
+
+@pytest.mark.parametrize("nv,path", [(5, "host"), (5, "device"), (1, "host"), (1, "device")])
+def test_row_padding_smallest_shapes(hip, oracle, ase_small, nv, path):
+    """nv = 5 (Kp = 8) and nv = 1 (Kp = 4): the smallest shapes where a row stride of K and one of Kp differ."""
+    a = problem_mod.resample_frequency(ase_small, nv) if nv > 1 else one_frequency(ase_small)
+    assert a.beam.nv == nv
+    updated_against_fresh_and_oracle(hip, oracle, a, tv.tables_b(a), sparse_rays(a, 97), DEFAULT_TIER, f"nv = {nv}, {path}", path)
+
+
+# ---------------------------------------------------------------------------------------------- 4. N = 4, unequal shapes
+@pytest.mark.parametrize("path", ["host", "device"])
+def test_four_lengths_of_unequal_shapes(hip, oracle, ase_small, path):
+    a = tv.four_lengths(ase_small)
+    updated_against_fresh_and_oracle(hip, oracle, a, tv.tables_b(a), sparse_rays(a, 97), DEFAULT_TIER, f"N = 4, {path}", path)
+
+
+# ---------------------------------------------------------------------------------------------- 5. flags without a run
+@pytest.mark.parametrize("path", ["host", "device"])
+def test_flags_of_crafted_tables_without_a_run(hip, ase_small, path):
+    a = ase_small
+    with hip.Plan(a) as plan:
+        flags_a = plan.table_flags()
+        same_flags(flags_a, tv.expected_flags(a), "tables A against the restatement")
+        for name in ("crafted_row_wrap", "crafted_unbounded", "crafted_huge_lineshape", "crafted_no_e0"):
+            q = getattr(tv, name)(a)
+            update(plan, q, path)
+            got = plan.table_flags()
+            with hip.Plan(q) as other:
+                want = other.table_flags()
+            same_flags(got, want, f"{name}, {path}")
+            same_flags(got, tv.expected_flags(q), f"{name}, {path}, against the restatement")
+            if name == "crafted_row_wrap":
+                assert got["ntest_proven"] == 1, "the scan compared a row's first node with the previous row's last"
+            if name == "crafted_unbounded":
+                assert got["bounded"] == 0 and got["ntest_proven"] == 0
+            if name == "crafted_huge_lineshape":
+                assert got["gs_cap"] == np.float32(708.0) / np.float32(1e30)
+            update(plan, a, path)
+            same_flags(plan.table_flags(), flags_a, f"{name}, {path}: back to A")
+
+
+# ---------------------------------------------------------------------------------------------- 6. non-finite lineshape
+@pytest.mark.parametrize("path", ["host", "device"])
+def test_non_finite_lineshape(hip, ase, path):
+    a, rays = ase["a"], ase["rays"]
+    q = tv.crafted_nan_lineshape(a)
+    with hip.Plan(q) as other:
+        want = other.set_rays(rays).run().fetch()
+        want_flags = other.table_flags()
+    assert want_flags["gv_nonfinite"] == 1 and want["failure_code"] == 1 << 3 and len(want["failed_rays"]) > 0
+    with hip.Plan(a) as plan:
+        plan.set_rays(rays)
+        assert plan.table_flags()["gv_nonfinite"] == 0
+        update(plan, q, path)
+        same_flags(plan.table_flags(), want_flags, f"NaN lineshape, {path}")
+        out = plan.run().fetch()
+    assert out["failure_code"] == want["failure_code"]
+    assert ray_set(out["failed_rays"]) == ray_set(want["failed_rays"])
+    assert out["stats"]["n_skipped"] == want["stats"]["n_skipped"] and out["stats"]["cell_steps"] == want["stats"]["cell_steps"]
+
+
+# ---------------------------------------------------------------------------------------------- 7. rejected updates
+def test_rejected_updates_leave_the_plan_as_it_was(hip, ase):
+    import torch
+
+    a, b, rays = ase["a"], ase["b"], ase["rays"]
+    bad_n = tv.crafted_nan_index(b)
+    t = tv.as_tables(b)
+    with hip.Plan(a) as plan:
+        plan.set_rays(rays).enable_probe()
+        _, rec0 = run_probed(plan)
+        with pytest.raises(hip.RayTraceError, match="non-finite index of refraction"):
+            plan.update_gain(bad_n)
+        with pytest.raises(hip.RayTraceError, match="non-finite index of refraction"):
+            plan.update_gain(tv.as_tables(bad_n, on_device))
+        with pytest.raises(ValueError, match="N = 3"):
+            plan.update_gain(t[:2])
+        with pytest.raises(ValueError, match="n has shape"):
+            plan.update_gain([None, (t[1][0][:-1].copy(),) + t[1][1:], t[2]])
+        with pytest.raises(ValueError, match="torch tensor on the CPU"):
+            plan.update_gain(tv.as_tables(b, torch.from_numpy))
+        with pytest.raises(ValueError, match="mixed"):
+            plan.update_gain([None, t[1], tv.as_tables(b, on_device)[2]])
+        # the C entries themselves: wrong N, a NULL table
+        m = rt.cabi.GainValues(b, [(g.Nx, g.Ny) for g in a.gain], a.beam.nv)
+        lib = plan.hl.lib
+        assert lib.rt_hip_plan_update_gain(plan._h, 4, m.vals) == rt.cabi.RT_ERR_ARG and b"N differs" in lib.rt_hip_last_error()
+        m.vals[2].gv = rt.cabi.c_float_p()
+        assert lib.rt_hip_plan_update_gain(plan._h, 3, m.vals) == rt.cabi.RT_ERR_ARG and b"incomplete gain table" in lib.rt_hip_last_error()
+        assert plan.problem is a
+        same_flags(plan.table_flags(), ase["flags_a"], "after the rejected updates")
+        _, rec1 = run_probed(plan)
+        same_records(rec1, rec0, "after the rejected updates")
+        same_records(rec1, ase["rec_a"], "after the rejected updates, against a fresh plan")
+
+
+# ---------------------------------------------------------------------------------------------- 8. between a run and its fetch
+def test_update_between_a_run_and_its_fetch(hip, oracle, ase):
+    a, b, rays = ase["a"], ase["b"], ase["rays"]
+    q = tv.crafted_nan_lineshape(a)
+    with hip.Plan(q) as other:
+        want = other.set_rays(rays).run().fetch()
+    assert want["failure_code"] == 1 << 3
+    with hip.Plan(q) as plan:
+        plan.set_rays(rays).enable_probe()
+        plan.run()
+        plan.update_gain(b)               # settles the run (its checking repeat reads the NaN table) before B goes in
+        out = plan.fetch()
+        assert out["failure_code"] == want["failure_code"] and ray_set(out["failed_rays"]) == ray_set(want["failed_rays"])
+        counts = counts_from_oracle(oracle, q, rays, n_threads=4)      # (failing rays deposit nothing and are not counted)
+        gate_outputs(out, want, q, counts, "reordering", "fetch after the update against a fresh plan's fetch on the NaN table")
+        out_b, rec_b = run_probed(plan)
+        assert out_b["failure_code"] == 0
+        same_records(rec_b, ase["rec_b"], "the next run is B's")
+        gate_outputs(out_b, ase["out_b"], b, ase["counts"], "reordering", "the next run is B's")
+
+
+# ---------------------------------------------------------------------------------------------- 9. other output modes
+def test_step_mode_with_lent_buffers_and_a_ray_grid(hip, oracle, ase_small):
+    """The bounds of tests/test_gpu_step.py (gate_step there): nf and I_ang at the tier, E_v at the tier + (n + K) 2^-52."""
+    import torch
+
+    a = copy.copy(ase_small)
+    a.N_start, a.N_parallel = 0, 97                               # the strided ray grid: every 97th ray
+    b = tv.tables_b(a)
+    bm = a.beam
+    dev = torch.device("cuda", 0)
+    nf_off = (bm.nv * 8 + 255) // 256 * 32
+    record = torch.full((nf_off + bm.nx * bm.ny + bm.na * bm.nb,), 7.0, dtype=torch.float64, device=dev)
+    ev_t, nf_t, ang_t = record[:bm.nv], record[nf_off:nf_off + bm.nx * bm.ny], record[nf_off + bm.nx * bm.ny:]
+    with hip.Plan(a) as plan:
+        plan.set_ray_grid().enable_step().set_step_buffers(ev_t.data_ptr(), nf_t.data_ptr())
+        plan.run(iang_ptr=ang_t.data_ptr()).fetch_step()
+        plan.update_gain(b)
+        plan.run(iang_ptr=ang_t.data_ptr())
+        got = plan.fetch_step()
+        assert plan.fetch()["failure_code"] == 0 and plan.n_rays == len(a.ray_ids())
+        torch.cuda.synchronize()
+        assert plan.step_ptrs() == (ev_t.data_ptr(), nf_t.data_ptr()), "the lent buffers survive the update"
+        for key, t in (("E_v", ev_t), ("nf", nf_t), ("I_ang", ang_t)):
+            assert np.array_equal(t.cpu().numpy(), got[key]), key
+    rays = b.build_rays()
+    ora = oracle.image_loop(b, rays, n_threads=4)
+    ref = hip.step_outputs_from_image(b, ora["image"])
+    n_img, n_ang = contribution_counts(b, rays)
+    n_dep = int(np.sum(n_img))
+    assert_elements(got["nf"], ref["nf"], n_img, DEFAULT_TIER, "step mode after an update / nf")
+    assert_elements(got["E_v"], ref["E_v"], np.array([n_dep]), DEFAULT_TIER + (n_dep + bm.nv) * EPS, "step mode after an update / E_v")
+    assert_elements(got["I_ang"], ora["I_ang"], n_ang, DEFAULT_TIER, "step mode after an update / I_ang", (bm.nb, bm.na))
+
+
+def test_spectra_mode_after_an_update(hip, ase):
+    a, b, rays = ase["a"], ase["b"], ase["rays"]
+    with hip.Plan(b) as other:
+        want = other.set_rays(rays).enable_spectra().run().fetch_spectra()
+    with hip.Plan(a) as plan:
+        plan.set_rays(rays).enable_spectra().run()
+        first = plan.fetch_spectra()
+        plan.update_gain(b).run()
+        got = plan.fetch_spectra()
+    assert not np.array_equal(first["Iv"], got["Iv"])
+    assert np.array_equal(got["Iv"].view(np.uint64), want["Iv"].view(np.uint64)), "Iv of an updated plan differs from a fresh plan's"
+    assert np.array_equal(got["err"], want["err"]) and np.array_equal(got["ray2"].view(np.uint32), want["ray2"].view(np.uint32))
