@@ -33,6 +33,7 @@ extern "C" {
 
 #define RT_N_SUB 3         /* sub-segments per length (RayTraceImageHelper.h:31) */
 #define RT_N_FAILED_MAX 32 /* failed rays reported back (RayTraceImageHelper.h:32) */
+#define RT_N_SEED_MAX 2    /* seed beams of one step record (N_SEED_MAX, RayTraceStructures.h:15) */
 
 /* Status codes returned by every entry point. */
 enum {
@@ -410,6 +411,46 @@ typedef struct rt_gain_values {
 int rt_hip_plan_update_gain(rt_hip_plan *plan, int N, const rt_gain_values *vals);
 int rt_hip_plan_update_gain_dev(rt_hip_plan *plan, int N, const rt_gain_values *vals, void *stream);
 int rt_hip_plan_table_flags(rt_hip_plan *plan, int *bounded, int *ntest_proven, int *gv_nonfinite, float *gs_cap);
+
+/*
+ * A seed set on a plan: the records of several seed beams from ONE march.  The application's per-step record
+ * (intensity_step_struct, src/RayTraceStructures.h:361-369) holds one triple E_v_seed[s], image_seed[s], E_ang_seed[s] per
+ * seed beam, s < N_seed <= N_SEED_MAX = RT_N_SEED_MAX.  The march does not depend on the seed (Helper.h:428-521); the seed
+ * enters the frequency pass only, as Iv[k] = f0_s f_s[4][k] exp(gl[k]) (Helper.h:523-533, 569-580).  With a set installed
+ * a step-mode run traces the rays once and leaves one record per seed (rt_step_seeds_kernel,
+ * raytrace-miniapp_amd/csrc/rt_step_seeds.hip, in place of rt_step_kernel; reported as freq_ms): every Iv_s[k] is the
+ * double a plan created with seed s computes, the sums differ from that plan's by summation order only.
+ * set_seeds: the plan must have been created with a seed -- that decides the gain-only mode and the method, both stay as
+ *   created; the creation seed is not part of the set (a caller who wants it passes it again).  n_seed = 1 ..
+ *   RT_N_SEED_MAX installs seeds[0 .. n_seed), each validated as rt_hip_plan_create validates its seed (five complete
+ *   tables, dim[4] == nv; dim[0 .. 3] are free); n_seed = 0 removes the set, the plan is then exactly as created.  The
+ *   call first settles the plan's last run (as rt_hip_plan_update_gain does), copies the tables -- the caller's arrays are
+ *   free when it returns -- and works before or after set_ray_grid / set_rays: on a forward ray grid every seed gets its
+ *   own factor tables, rebuilt whenever the grid or the set changes.  A rejected call (RT_ERR_ARG) leaves the plan's set
+ *   as it was.
+ * With a set installed only step mode runs: rt_hip_plan_run outside step mode, with lent step buffers
+ *   (rt_hip_plan_set_step_buffers) or with a non-NULL image_dev or iang_dev is RT_ERR_ARG, and so are
+ *   rt_hip_plan_enable_path and rt_hip_plan_enable_spectra.  The probe, the timing ring, rt_hip_plan_kernel_times,
+ *   rt_hip_plan_set_step_factor and rt_hip_plan_update_gain / _dev work as on any step plan; an update keeps the set.
+ * Outputs: ONE allocation of the plan, n_seed blocks of equal stride, each
+ *   (E_v[nv] | pad to 256 bytes | nf[nx*ny] (+ nx + 2 spare on a one-point x or y axis) | I_ang[na*nb] (+ na + 2 spare
+ *   on a one-point a or b axis)) -- the layout of the buffer rt_hip_multi_step_loop builds per device -- the stride
+ *   rounded up to 256 bytes, zeroed by the run's zeroing launch: a collective can take all records as one buffer.
+ *   seed_step_ptrs: the device pointers of block s (any may be NULL), valid while the plan lives and the set stays.
+ *   fetch_seed_step: waits for the run, runs the checking repeat where needed and copies block s; any pointer may be
+ *   NULL; *failure_code is the code of seed s.  rt_hip_plan_fetch_step and rt_hip_plan_step_ptrs serve seed 0, and so
+ *   does I_ang of rt_hip_plan_fetch.
+ * Failures follow the reference run once per seed: error -1 does not depend on the seed -- the ray deposits into no
+ *   record and every seed's code has the bit; error -2 / -3 under seed s removes the ray from record s only
+ *   (RayTraceImageCPU.cpp:29-36, per create_image call).  rt_hip_plan_fetch reports the OR of the per-seed codes and the
+ *   rays that fail under any seed, each once (more than RT_N_FAILED_MAX: the first of them in list order); the counters
+ *   are those of one run, the rays being traced once.
+ * Not taken with a set: image mode, spectra mode, the path tracer, the host-pointer and multi-device loops.
+ */
+int rt_hip_plan_set_seeds(rt_hip_plan *plan, int n_seed, const rt_seed *seeds);
+int rt_hip_plan_fetch_seed_step(rt_hip_plan *plan, int s, double *E_v, double *nf, double *I_ang,
+                                unsigned int *failure_code);
+int rt_hip_plan_seed_step_ptrs(rt_hip_plan *plan, int s, double **E_v_dev, double **nf_dev, double **iang_dev);
 
 /* Profiling aid (no reference counterpart): bit 0 = skip the frequency / deposit kernel, bit 1 = skip
  * the march and run the frequency pass over the records of the previous run of this plan, bit 2 = the

@@ -9,6 +9,7 @@ mirror of the reference's operator interface for this path.
                         src/RayTraceImage.cpp:47-75
   step_loop(...)        the same loop with the application's per-step record in place of the image cube: E_v, nf, I_ang
   multi_step_loop(...)  step_loop on all devices of the node: strided ray grid per device, one sum-reduce of the record
+  seed_step_loop(...)   the step records of up to RT_N_SEED_MAX seed beams from one march (Plan.set_seeds)
   step_outputs_from_image  their definition as reductions of a cube, in numpy (no device)
   calc_rays / calc_ray  RayTrace::calc_ray (src/RayTraceImage.cpp:189-204), batched: per-ray spectrum, exit ray, code
   create_image(p, method)
@@ -26,7 +27,7 @@ from pathlib import Path
 import numpy as np
 
 from . import cabi
-from .problem import Problem
+from .problem import Problem, Seed
 
 CSRC = Path(__file__).resolve().parent / "csrc"
 LIB_PATH = CSRC / "librt_hip.so"
@@ -268,6 +269,66 @@ class Plan:
         ang = self.iang_ptr
         return dict(E_v=view(e, (b.nv,)), nf=view(n, (b.ny, b.nx)), I_ang=view(ang, (b.nb, b.na)) if ang else None)
 
+    # -- seed set -----------------------------------------------------------
+    def set_seeds(self, seeds) -> "Plan":
+        """A seed set (include/rt_hip.h, rt_hip_plan_set_seeds): up to RT_N_SEED_MAX Seed records whose step records one
+        run leaves, from one march; [] removes the set.  The plan must have been created with a seed.  More seeds than
+        that, or anything that is not a Seed, is a ValueError raised here, before any native call."""
+        seeds = list(seeds)
+        if len(seeds) > cabi.RT_N_SEED_MAX:
+            raise ValueError(f"set_seeds: {len(seeds)} seeds given, at most RT_N_SEED_MAX = {cabi.RT_N_SEED_MAX} fit into a set")
+        for i, sd in enumerate(seeds):
+            if not isinstance(sd, Seed):
+                raise ValueError(f"set_seeds: entry {i} is a {type(sd).__name__}, not a Seed")
+        keep = []
+        arr = (cabi.RtSeed * max(1, len(seeds)))()
+        for i, sd in enumerate(seeds):
+            arr[i] = cabi.seed_record(sd, keep)
+        self.hl.check(self.hl.lib.rt_hip_plan_set_seeds(self._h, len(seeds), arr if seeds else None), "rt_hip_plan_set_seeds")
+        self._n_seed = len(seeds)
+        return self
+
+    def fetch_seed_steps(self) -> list:
+        """[dict(E_v [nv], nf [nx * ny], I_ang [na * nb], failure_code)] per seed of the set of the last step run (waits for
+        it; a failing run is repeated in the checking mode first)."""
+        b = self.problem.beam
+        out = []
+        for s in range(getattr(self, "_n_seed", 0)):
+            E_v, nf, iang = np.empty(b.nv), np.empty(b.nx * b.ny), np.empty(b.na * b.nb)
+            code = C.c_uint(0)
+            self.hl.check(self.hl.lib.rt_hip_plan_fetch_seed_step(self._h, s, cabi._dp(E_v), cabi._dp(nf), cabi._dp(iang), C.byref(code)),
+                          "rt_hip_plan_fetch_seed_step")
+            out.append(dict(E_v=E_v, nf=nf, I_ang=iang, failure_code=code.value))
+        return out
+
+    def seed_step_ptrs(self, s: int) -> tuple:
+        """Device pointers (E_v, nf, I_ang) of the record of seed s of the last step run with a set."""
+        e, n, a = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self.hl.check(self.hl.lib.rt_hip_plan_seed_step_ptrs(self._h, int(s), C.byref(e), C.byref(n), C.byref(a)),
+                      "rt_hip_plan_seed_step_ptrs")
+        return int(e.value or 0), int(n.value or 0), int(a.value or 0)
+
+    def seed_step_tensors(self) -> list:
+        """Per seed of the set: torch views (float64, on the plan's device, no copy) of E_v [nv], nf [ny][nx] and I_ang
+        [nb][na] of the last step run -- blocks of one allocation, valid until the plan's next run; read them on the
+        run's stream or after a fetch."""
+        import torch
+
+        class _View:  # the CUDA array interface, which torch.as_tensor reads
+            pass
+
+        def view(ptr, shape):
+            v = _View()
+            v.__cuda_array_interface__ = dict(shape=shape, typestr="<f8", data=(ptr, False), version=2, strides=None)
+            return torch.as_tensor(v, device=torch.device("cuda", self.device))
+
+        b = self.problem.beam
+        out = []
+        for s in range(getattr(self, "_n_seed", 0)):
+            e, n, a = self.seed_step_ptrs(s)
+            out.append(dict(E_v=view(e, (b.nv,)), nf=view(n, (b.ny, b.nx)), I_ang=view(a, (b.nb, b.na))))
+        return out
+
     # -- tables -------------------------------------------------------------
     def update_gain(self, gain, stream: int | None = None) -> "Plan":
         """New n, g0, E0 and gv on the plan's grids (include/rt_hip.h, rt_hip_plan_update_gain): everything else about the
@@ -463,6 +524,24 @@ def multi_step_loop(problem: Problem, rays: np.ndarray | None = None, n_devices:
     return dict(E_v=E_v, nf=nf, I_ang=iang, failure_code=code.value, failed_rays=failed[:nfail.value].copy(),
                 stats={k: getattr(st, k) for k, _ in cabi.RtStats._fields_}, mode=int(hl.lib.rt_hip_multi_last_mode()),
                 call_ms=call_ms)
+
+
+def seed_step_loop(problem: Problem, seeds, rays: np.ndarray | None = None, device: int = 0) -> dict:
+    """The step records of the seed beams `seeds` (a list of Seed, at most RT_N_SEED_MAX) from ONE march of the
+    problem's rays (rays None: the problem's ray grid, generated on the device): a convenience over a Plan in step mode
+    with a seed set.  The problem must carry a seed -- it decides the gain-only mode and the method; it is not part of
+    the set.  Returns dict(records = [dict(E_v, nf, I_ang, failure_code)] per seed, failure_code = their OR,
+    failed_rays = the rays that fail under any seed, stats)."""
+    with Plan(problem, device) as plan:   # (without a device: RayTraceError, "no HIP device", as the other entries)
+        plan.set_seeds(seeds)
+        if rays is None:
+            plan.set_ray_grid()
+        else:
+            plan.set_rays(rays)
+        plan.enable_step().run()
+        records = plan.fetch_seed_steps()
+        info = plan.fetch()
+    return dict(records=records, failure_code=info["failure_code"], failed_rays=info["failed_rays"], stats=info["stats"])
 
 
 def step_outputs_from_image(problem: Problem, image) -> dict:

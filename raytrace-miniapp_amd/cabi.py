@@ -13,6 +13,7 @@ import numpy as np
 
 RT_N_SUB = 3
 RT_N_FAILED_MAX = 32
+RT_N_SEED_MAX = 2
 
 RT_OK, RT_ERR_ARG, RT_ERR_NO_DEVICE, RT_ERR_HIP, RT_ERR_NOMEM = range(5)
 
@@ -79,6 +80,18 @@ def _fp(a: np.ndarray | None):
         return c_float_p()
     assert a.dtype == np.float32 and a.flags.c_contiguous
     return a.ctypes.data_as(c_float_p)
+
+
+def seed_record(seed, keep: list) -> "RtSeed":
+    """A Seed laid out as rt_seed; the arrays it points into are appended to `keep`."""
+    s = RtSeed()
+    for i in range(5):
+        s.dim[i] = int(seed.x[i].shape[0])
+        s.x[i] = _dp(seed.x[i])
+        s.f[i] = _dp(seed.f[i])
+        keep += [seed.x[i], seed.f[i]]
+    s.f0 = seed.f0
+    return s
 
 
 class Marshalled:
@@ -320,6 +333,13 @@ def declare_hip_api(lib: C.CDLL) -> None:
         lib.rt_hip_plan_update_gain_dev.restype = C.c_int
         lib.rt_hip_plan_table_flags.argtypes = [vp, P(C.c_int), P(C.c_int), P(C.c_int), c_float_p]
         lib.rt_hip_plan_table_flags.restype = C.c_int
+    if hasattr(lib, "rt_hip_plan_set_seeds"):   # (likewise)
+        lib.rt_hip_plan_set_seeds.argtypes = [vp, C.c_int, P(RtSeed)]
+        lib.rt_hip_plan_set_seeds.restype = C.c_int
+        lib.rt_hip_plan_fetch_seed_step.argtypes = [vp, C.c_int, c_double_p, c_double_p, c_double_p, P(C.c_uint)]
+        lib.rt_hip_plan_fetch_seed_step.restype = C.c_int
+        lib.rt_hip_plan_seed_step_ptrs.argtypes = [vp, C.c_int, P(vp), P(vp), P(vp)]
+        lib.rt_hip_plan_seed_step_ptrs.restype = C.c_int
     lib.rt_hip_plan_set_debug.argtypes = [vp, C.c_uint]
     lib.rt_hip_plan_set_debug.restype = C.c_int
     lib.rt_hip_plan_destroy.argtypes = [vp]
@@ -337,5 +357,6 @@ HIP_API_SYMBOLS = [
     "rt_hip_calc_rays", "rt_hip_plan_enable_step", "rt_hip_plan_fetch_step", "rt_hip_plan_step_ptrs", "rt_hip_step_loop",
     "rt_hip_plan_set_step_buffers", "rt_hip_multi_step_loop",
     "rt_hip_plan_update_gain", "rt_hip_plan_update_gain_dev", "rt_hip_plan_table_flags",
+    "rt_hip_plan_set_seeds", "rt_hip_plan_fetch_seed_step", "rt_hip_plan_seed_step_ptrs",
     "rt_hip_plan_set_debug", "rt_hip_plan_destroy",
 ]

@@ -142,6 +142,8 @@ struct DevCtl {
     unsigned long long n_skipped;
     unsigned long long n_rays;
     rt_ray failed[RT_N_FAILED_MAX];
+    // rt_step_seeds_kernel: the failure code of every seed of the plan's seed set (failure_code above is their OR)
+    unsigned int seed_code[RT_N_SEED_MAX];
 };
 
 // probe outputs of the frequency kernel (gvl / evl / ivl are read back from the records)

@@ -11,6 +11,7 @@
 #include "rt_fused.hip" // both as two phases of one launch
 #include "rt_spec.hip" // spectra mode: per-ray spectra in place of the deposit
 #include "rt_step.hip" // step mode: E_v, nf and I_ang, the image cube reduced on the way
+#include "rt_step_seeds.hip" // step mode with a seed set: one record per seed from one march
 
 #include "rt_runtime.h"
 
@@ -245,12 +246,58 @@ template <int SF, bool EMIS> int launch_step(rt_hip_plan *p, hipStream_t stream)
     return RT_OK;
 }
 
+// step mode with a seed set: rt_step_seeds_kernel over all tiles, one 16-wave work-group per CU; one I_ang histogram per
+// seed in LDS where rt_step_kernel keeps its one there and all of them fit, global atomics otherwise
+template <int SF> int launch_step_seeds(rt_hip_plan *p, hipStream_t stream)
+{
+    const int wg_waves = rt::FREQ_WG_WAVES;
+    const int n_seed   = p->n_seed;
+    bool in_lds        = p->n_iang * sizeof(double) <= 32 * 1024;
+    size_t lds         = rt::step_seeds_lds_doubles(in_lds, (int) p->n_iang, p->P.Kp, wg_waves, n_seed) * sizeof(double);
+    if (in_lds && lds > p->lds_limit) {
+        in_lds = false;
+        lds    = rt::step_seeds_lds_doubles(false, (int) p->n_iang, p->P.Kp, wg_waves, n_seed) * sizeof(double);
+    }
+    if (lds > p->lds_limit)
+        return fail_arg("step kernel of a seed set: the E_v accumulators (nv doubles per seed) do not fit into the LDS of this device");
+    const unsigned long long want = ((unsigned long long) (p->P.tile_end - p->P.tile_begin) + (unsigned) wg_waves - 1) / (unsigned) wg_waves;
+    const unsigned grid           = (unsigned) (want < (unsigned long long) p->cu_count ? want : (unsigned long long) p->cu_count);
+    if (grid == 0)
+        return RT_OK;
+    const rt::FreqKArg f = freq_args(p, in_lds, 0, (unsigned long long) grid * (unsigned) wg_waves);
+    rt::SeedsKArg a;
+    memset(&a, 0, sizeof(a));
+    a.hot         = f.hot;
+    a.hot.image   = nullptr; // never touched: there is no cube
+    a.hot.seed_fk = nullptr; // (the creation seed is not part of the set)
+    a.cold        = f.cold;
+    a.set.n_seed  = n_seed;
+    for (int s = 0; s < n_seed; s++) {
+        double *blk       = p->seeds_dev + (size_t) s * p->seeds_stride;
+        a.set.out[s]      = rt::SeedRec{ blk, blk + p->seeds_nf_off, blk + p->seeds_ang_off };
+        a.set.fk[s]       = p->seed_set[s].f[4];
+        a.set.sf[s]       = p->P.rays.sf ? p->seedset_sf[s] : nullptr;
+        a.set.sin[s]      = p->P.rays.sf ? p->seedset_sin[s] : nullptr;
+        a.set.seed[s]     = p->seed_set[s];
+        if (p->P.rays.sf && (!a.set.sf[s] || !a.set.sin[s]))
+            return fail_arg("step kernel of a seed set: the factor tables of the set were not built for this ray grid");
+    }
+    const int rc = allow_lds(reinterpret_cast<const void *>(&rt::rt_step_seeds_kernel<SF>), p->device, lds, p->lds_limit);
+    if (rc != RT_OK)
+        return rc;
+    hipLaunchKernelGGL((rt::rt_step_seeds_kernel<SF>), dim3(grid), dim3((unsigned) wg_waves * 64), lds, stream, a);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
 int launch_step_any(rt_hip_plan *p, hipStream_t stream)
 {
     p->P.tile_begin = 0;
     p->P.tile_end   = p->P.n_tiles;
     p->P.freq_id    = 0;
     const int S = p->P.L * RT_N_SUB;
+    if (p->n_seed > 0) // (a seeded plan: gain-only)
+        return (S == 6) ? launch_step_seeds<6>(p, stream) : launch_step_seeds<0>(p, stream);
     if (p->P.use_emis)
         return (S == 6) ? launch_step<6, true>(p, stream) : launch_step<0, true>(p, stream);
     return (S == 6) ? launch_step<6, false>(p, stream) : launch_step<0, false>(p, stream);
@@ -360,6 +407,7 @@ int plan_repeat_checked(rt_hip_plan *p)
     HIP_TRY(hipMemsetAsync(p->bad_dev, 0, (size_t) p->n_rays, stream));
     HIP_TRY(hipMemsetAsync(&p->ctl->failure_code, 0, sizeof(unsigned), stream));
     HIP_TRY(hipMemsetAsync(&p->ctl->n_failed, 0, sizeof(unsigned), stream));
+    HIP_TRY(hipMemsetAsync(p->ctl->seed_code, 0, sizeof(p->ctl->seed_code), stream));
     HIP_TRY(hipMemsetAsync(p->ctl->next_tile_f, 0, sizeof(p->ctl->next_tile_f), stream));
     p->P.bad  = p->bad_dev;
     p->P.safe = 1;
@@ -369,7 +417,9 @@ int plan_repeat_checked(rt_hip_plan *p)
         if (step && p->last_step_lent) { // (the caller's buffers: exactly the K and nx * ny doubles that are the run's)
             HIP_TRY(hipMemsetAsync(p->step.E_v, 0, (size_t) p->P.K * sizeof(double), stream));
             HIP_TRY(hipMemsetAsync(p->step.nf, 0, (size_t) p->P.beam.nx * (size_t) p->P.beam.ny * sizeof(double), stream));
-        } else if (step)
+        } else if (step && p->last_n_seed > 0) // (a seed set: every record, its I_ang included, is in the one allocation)
+            HIP_TRY(hipMemsetAsync(p->seeds_dev, 0, p->seeds_doubles * sizeof(double), stream));
+        else if (step)
             HIP_TRY(hipMemsetAsync(p->step_dev, 0, p->step_doubles * sizeof(double), stream));
         else if (!p->P.exclusive)
             HIP_TRY(hipMemsetAsync(p->last_image, 0, p->n_image * sizeof(double), stream));

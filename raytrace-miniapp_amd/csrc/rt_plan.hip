@@ -198,6 +198,9 @@ void rt_hip_plan_destroy(rt_hip_plan *p)
     (void) hipFree(p->spec[0].Iv); // (ray2 and err of a set live in the same allocation)
     (void) hipFree(p->spec[1].Iv);
     pool_free(p->device, p->step_dev);
+    pool_free(p->device, p->seeds_dev);
+    (void) hipFree(p->seedset_arena);
+    (void) hipFree(p->seedset_tab);
     pool_free(p->device, p->arena);
     pool_free(p->device, p->rays_dev);
     pool_free(p->device, p->grid_dev);
@@ -613,6 +616,36 @@ int rtr::plan_create_on(rt_hip_plan **out, hipStream_t upload_q, int device, int
     return RT_OK;
 }
 
+// What rt_hip_plan_set_ray_grid does for the creation seed, for every seed of the set: on a forward ray grid the seed
+// profile is a product of one factor per grid axis, tabulated per grid point by rt_seed_tab_kernel (DevRays::sf / sin).
+// Called when the grid or the set has changed, with the plan quiet.
+int rtr::plan_build_seedset_tabs(rt_hip_plan *p)
+{
+    (void) hipFree(p->seedset_tab);
+    p->seedset_tab = nullptr;
+    for (int s = 0; s < RT_N_SEED_MAX; s++) {
+        p->seedset_sf[s]  = nullptr;
+        p->seedset_sin[s] = nullptr;
+    }
+    const rt::DevRays &R = p->P.rays;
+    if (p->n_seed < 1 || !R.sf) // (R.sf: a ray grid, a seeded plan, the forward method)
+        return RT_OK;
+    const size_t nn = (size_t) R.ngx + (size_t) R.ngy + (size_t) R.nga + (size_t) R.ngb;
+    const size_t per_seed = align_up(nn * sizeof(double) + nn, 256);
+    HIP_TRY(dev_malloc((void **) &p->seedset_tab, per_seed * (size_t) p->n_seed));
+    for (int s = 0; s < p->n_seed; s++) {
+        double *sf           = reinterpret_cast<double *>(p->seedset_tab + per_seed * (size_t) s);
+        unsigned char *flags = reinterpret_cast<unsigned char *>(sf + nn);
+        const int rc         = launch_seed_tab(p->seed_set[s], R, nn, sf, flags);
+        if (rc != RT_OK)
+            return rc;
+        p->seedset_sf[s]  = sf;
+        p->seedset_sin[s] = flags;
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    return RT_OK;
+}
+
 // rt_hip_image_loop only: the outputs of a run that are a few megabytes at most follow its kernels down the queue into
 // page-locked staging -- one wait in rt_hip_plan_fetch instead of a wait and three blocking copies (larger images are
 // fetched directly: copying them once more on the host would cost what the queueing saves).
@@ -621,7 +654,7 @@ void rtr::plan_stage_outputs(rt_hip_plan *p)
     constexpr size_t ctl_tail = offsetof(rt::DevCtl, failure_code), ctl_bytes = sizeof(rt::DevCtl) - ctl_tail;
     if (!p || !p->ran || !p->last_stream)
         return;
-    if (p->last_step && p->last_step_lent) // E_v and nf are the caller's, and not one range: fetched the ordinary way
+    if (p->last_step && (p->last_step_lent || p->last_n_seed > 0)) // E_v and nf are the caller's, or a seed set's: fetched the ordinary way
         return;
     // (a step run: E_v and nf travel where the image does)
     const double *big    = p->last_step ? p->step_dev : p->last_image;
@@ -820,7 +853,7 @@ int rt_hip_plan_set_ray_grid(rt_hip_plan *p, const double *gx, int ngx, const do
                          : 0u;
     // (with emission only: the gain-only instance of the frequency kernel carries no exclusive deposit)
     p->P.exclusive = (p->P.own_cells && p->P.use_emis && nga == 1 && ngb == 1 && first == 0 && stride == 1 && count == total) ? 1u : 0u;
-    return RT_OK;
+    return plan_build_seedset_tabs(p); // (a seed set installed before the grid)
 }
 
 int rt_hip_plan_set_exact_emission(rt_hip_plan *p, int on)
@@ -858,6 +891,8 @@ int rt_hip_plan_enable_path(rt_hip_plan *p, int on)
         return fail_arg("rt_hip_plan_enable_path: the plan is in spectra mode (one per-ray output at a time)");
     if (on && p->step_on)
         return fail_arg("rt_hip_plan_enable_path: the plan is in step mode (one output mode at a time)");
+    if (on && p->n_seed > 0)
+        return fail_arg("rt_hip_plan_enable_path: the plan holds a seed set (step mode only)");
     p->path_on = on != 0;
     return RT_OK;
 }
@@ -884,6 +919,8 @@ int rt_hip_plan_enable_spectra(rt_hip_plan *p, int on)
         return fail_arg("rt_hip_plan_enable_spectra: the path tracer is enabled (one per-ray output at a time)");
     if (on && p->step_on)
         return fail_arg("rt_hip_plan_enable_spectra: the plan is in step mode (one output mode at a time)");
+    if (on && p->n_seed > 0)
+        return fail_arg("rt_hip_plan_enable_spectra: the plan holds a seed set (step mode only)");
     p->spectra_on = on != 0;
     return RT_OK;
 }
@@ -998,7 +1035,32 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
         return fail_arg("rt_hip_plan_run: a step run takes no image buffer");
     const bool lent = step && p->step_ev_lent; // E_v and nf in the caller's memory (rt_hip_plan_set_step_buffers)
     const size_t nf_off = align_up((size_t) p->P.K * sizeof(double), 256) / sizeof(double);
-    if (step && !lent && !p->step_dev) {
+    const int n_seed = p->n_seed; // a seed set: one record per seed, all in one allocation of the plan
+    if (n_seed > 0) {
+        if (!step || p->path_on)
+            return fail_arg("rt_hip_plan_run: the plan holds a seed set, which runs in step mode only");
+        if (lent)
+            return fail_arg("rt_hip_plan_run: a seed set writes the plan's own records, not lent step buffers");
+        if (image_dev || iang_dev)
+            return fail_arg("rt_hip_plan_run: a run with a seed set takes no image and no I_ang buffer");
+        const rt::DevBeam &B = p->P.beam;
+        // (the spare cells of the one-point-axis case: rt_multi.hip, multi_step's buffer)
+        const size_t ang_off = nf_off + (size_t) B.nx * (size_t) B.ny + ((B.nx < 2 || B.ny < 2) ? (size_t) B.nx + 2 : 0);
+        const size_t stride  = align_up((ang_off + p->n_iang + ((B.na < 2 || B.nb < 2) ? (size_t) B.na + 2 : 0)) * sizeof(double), 256) / sizeof(double);
+        if (!p->seeds_dev || p->seeds_doubles != stride * (size_t) n_seed) {
+            plan_quiesce(p);
+            pool_free(p->device, p->seeds_dev);
+            p->seeds_dev     = nullptr;
+            p->seeds_doubles = 0;
+            HIP_TRY(pool_alloc(p->device, (void **) &p->seeds_dev, stride * (size_t) n_seed * sizeof(double)));
+            p->seeds_doubles = stride * (size_t) n_seed;
+        }
+        p->seeds_stride  = stride;
+        p->seeds_nf_off  = nf_off;
+        p->seeds_ang_off = ang_off;
+        iang_dev         = p->seeds_dev + ang_off; // seed 0's: what rt_hip_plan_fetch and fetch_step serve
+    }
+    if (step && !lent && !n_seed && !p->step_dev) {
         // (one row and a cell to spare: on an axis of one grid point the reference's getIndex answers 1 for the coordinate
         // g[0] + d/2 exactly, deposit_index4 of rt_freq.hip likewise)
         p->step_doubles     = nf_off + (size_t) p->P.beam.nx * (size_t) p->P.beam.ny + (size_t) p->P.beam.nx + 2;
@@ -1006,7 +1068,8 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
     }
     rt::StepOut step_out = {};
     if (step)
-        step_out = lent ? rt::StepOut{ p->step_ev_lent, p->step_nf_lent } : rt::StepOut{ p->step_dev, p->step_dev + nf_off };
+        step_out = lent ? rt::StepOut{ p->step_ev_lent, p->step_nf_lent }
+                 : n_seed ? rt::StepOut{ p->seeds_dev, p->seeds_dev + nf_off } : rt::StepOut{ p->step_dev, p->step_dev + nf_off };
     if (!spectra && !step && !image_dev) {
         if (!p->image_own)
             HIP_TRY(pool_alloc(p->device, (void **) &p->image_own, p->n_image * sizeof(double)));
@@ -1038,6 +1101,7 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
     // (step mode: E_v and nf take the image's place in the zeroing launch, exclusive or not)
     rc = lent ? launch_zero4(stream, step_out.E_v, (size_t) p->P.K * sizeof(double), step_out.nf,
                              (size_t) p->P.beam.nx * (size_t) p->P.beam.ny * sizeof(double), iang_dev, p->n_iang * sizeof(double), p->ctl, sizeof(rt::DevCtl))
+         : n_seed ? launch_zero3(stream, p->seeds_dev, p->seeds_doubles * sizeof(double), nullptr, 0, p->ctl, sizeof(rt::DevCtl))
          : step ? launch_zero3(stream, p->step_dev, p->step_doubles * sizeof(double), iang_dev, p->n_iang * sizeof(double), p->ctl, sizeof(rt::DevCtl))
               : launch_zero3(stream, (p->P.exclusive || spectra) ? nullptr : image_dev, p->n_image * sizeof(double), iang_dev,
                              p->n_iang * sizeof(double), p->ctl, sizeof(rt::DevCtl));
@@ -1065,6 +1129,7 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
     p->last_spectra = spectra;
     p->last_step   = step;
     p->last_step_lent = lent;
+    p->last_n_seed = n_seed;
     p->spec_last   = p->spec_sel;
     p->ran         = true;
     p->queued      = false; // (`ran` + last_stream cover it from here)
@@ -1245,6 +1310,113 @@ int rt_hip_plan_fetch_step(rt_hip_plan *p, double *E_v, double *nf, double *I_an
             HIP_TRY(hipMemcpy(I_ang, p->last_iang, p->n_iang * sizeof(double), hipMemcpyDeviceToHost));
     }
     return RT_OK;
+}
+
+int rt_hip_plan_fetch_seed_step(rt_hip_plan *p, int s, double *E_v, double *nf, double *I_ang, unsigned int *failure_code)
+{
+    if (!p || !p->ran || !p->last_step || p->last_n_seed < 1)
+        return fail_arg("rt_hip_plan_fetch_seed_step: the last run was not a step run with a seed set");
+    if (s < 0 || s >= p->last_n_seed)
+        return fail_arg("rt_hip_plan_fetch_seed_step: no such seed in the set of the last run");
+    rt::DevCtl c;
+    bool staged  = false;
+    const int rs = plan_settle(p, c, staged); // (a failing run is repeated here as rt_hip_plan_fetch repeats it)
+    if (rs != RT_OK)
+        return rs;
+    const double *blk = p->seeds_dev + (size_t) s * p->seeds_stride;
+    if (E_v)
+        HIP_TRY(hipMemcpy(E_v, blk, (size_t) p->P.K * sizeof(double), hipMemcpyDeviceToHost));
+    if (nf)
+        HIP_TRY(hipMemcpy(nf, blk + p->seeds_nf_off, (size_t) p->P.beam.nx * (size_t) p->P.beam.ny * sizeof(double), hipMemcpyDeviceToHost));
+    if (I_ang)
+        HIP_TRY(hipMemcpy(I_ang, blk + p->seeds_ang_off, p->n_iang * sizeof(double), hipMemcpyDeviceToHost));
+    if (failure_code)
+        *failure_code = c.seed_code[s];
+    return RT_OK;
+}
+
+int rt_hip_plan_seed_step_ptrs(rt_hip_plan *p, int s, double **E_v_dev, double **nf_dev, double **iang_dev)
+{
+    if (!p || !p->ran || !p->last_step || p->last_n_seed < 1)
+        return fail_arg("rt_hip_plan_seed_step_ptrs: the last run was not a step run with a seed set");
+    if (s < 0 || s >= p->last_n_seed)
+        return fail_arg("rt_hip_plan_seed_step_ptrs: no such seed in the set of the last run");
+    double *blk = p->seeds_dev + (size_t) s * p->seeds_stride;
+    if (E_v_dev)
+        *E_v_dev = blk;
+    if (nf_dev)
+        *nf_dev = blk + p->seeds_nf_off;
+    if (iang_dev)
+        *iang_dev = blk + p->seeds_ang_off;
+    return RT_OK;
+}
+
+int rt_hip_plan_set_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds)
+{
+    if (!p)
+        return fail_arg("rt_hip_plan_set_seeds: NULL plan");
+    if (!p->P.has_seed)
+        return fail_arg("rt_hip_plan_set_seeds: the plan was created without a seed (a set needs the gain-only mode)");
+    if (n_seed < 0 || n_seed > RT_N_SEED_MAX)
+        return fail_arg("rt_hip_plan_set_seeds: n_seed must be 0 .. RT_N_SEED_MAX");
+    if (n_seed > 0 && !seeds)
+        return fail_arg("rt_hip_plan_set_seeds: NULL seeds");
+    const int K = p->P.K, Kp = p->P.Kp;
+    for (int s = 0; s < n_seed; s++) // (as rt_hip_plan_create validates its seed)
+        for (int i = 0; i < 5; i++) {
+            if (seeds[s].dim[i] < 2 || !seeds[s].x[i] || !seeds[s].f[i])
+                return fail_arg("rt_hip_plan_set_seeds: incomplete seed table");
+            if (i == 4 && seeds[s].dim[4] != K)
+                return fail_arg("rt_hip_plan_set_seeds: seed.dim[4] != beam.nv");
+        }
+    if (n_seed > 0 && (p->path_on || p->spectra_on))
+        return fail_arg("rt_hip_plan_set_seeds: the path tracer or spectra mode is enabled (a set runs in step mode only)");
+    HIP_TRY(hipSetDevice(p->device));
+    if (p->ran) { // the last run keeps its set until it is final (wait, control block, the checking repeat)
+        const int rs = plan_settle_last_run(p);
+        if (rs != RT_OK)
+            return rs;
+    }
+    plan_quiesce(p);
+    // the tables of the set, packed as the arena packs the creation seed's: x[i], f[i], the frequency profile padded to Kp
+    std::vector<unsigned char> h;
+    size_t off_x[RT_N_SEED_MAX][5], off_f[RT_N_SEED_MAX][5];
+    auto put = [&](const double *src, size_t n, size_t n_padded) {
+        const size_t off = align_up(h.size(), 256);
+        h.resize(off + n_padded * sizeof(double), 0);
+        memcpy(h.data() + off, src, n * sizeof(double));
+        return off;
+    };
+    for (int s = 0; s < n_seed; s++)
+        for (int i = 0; i < 5; i++) {
+            const size_t n = (size_t) seeds[s].dim[i];
+            off_x[s][i]    = put(seeds[s].x[i], n, n);
+            off_f[s][i]    = put(seeds[s].f[i], n, i == 4 ? (size_t) Kp : n);
+        }
+    unsigned char *arena = nullptr;
+    if (n_seed > 0) {
+        HIP_TRY(dev_malloc((void **) &arena, h.size() + 16));
+        const hipError_t e = hipMemcpy(arena, h.data(), h.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void) hipFree(arena);
+            HIP_TRY(e);
+        }
+    }
+    (void) hipFree(p->seedset_arena);
+    p->seedset_arena = arena;
+    p->n_seed        = n_seed;
+    for (int s = 0; s < RT_N_SEED_MAX; s++) {
+        p->seed_set[s] = rt::DevSeed{};
+        if (s < n_seed) {
+            for (int i = 0; i < 5; i++) {
+                p->seed_set[s].x[i]   = reinterpret_cast<const double *>(arena + off_x[s][i]);
+                p->seed_set[s].f[i]   = reinterpret_cast<const double *>(arena + off_f[s][i]);
+                p->seed_set[s].dim[i] = seeds[s].dim[i];
+            }
+            p->seed_set[s].f0 = seeds[s].f0;
+        }
+    }
+    return plan_build_seedset_tabs(p);
 }
 
 int rt_hip_plan_kernel_ms(rt_hip_plan *p, float *ms)

@@ -6,7 +6,7 @@
 //                   rt_hip_image_loop (the host-pointer entry the C++ adapter calls)
 //   rt_raygrid.hip  a ray list that is really a tensor grid: recognition + bit-wise verification,
 //                   list-mode launch tangents and the probe of the host's libm
-//   rt_launch.hip   the kernels (rt_march.hip, rt_freq.hip, rt_path.hip, rt_spec.hip, rt_step.hip) and how a run puts them on a queue
+//   rt_launch.hip   the kernels (rt_march.hip, rt_freq.hip, rt_path.hip, rt_spec.hip, rt_step.hip, rt_step_seeds.hip) and how a run puts them on a queue
 //   rt_multi.hip    all devices of the node: RCCL loader, communicator, rt_hip_multi_image_loop, rt_hip_multi_step_loop
 //   rt_tables.hip   the gain tables of a resident plan rewritten in place: scan and pack kernels, rt_hip_plan_update_gain
 // Only rt_launch.hip, rt_multi.hip and rt_tables.hip contain device code.
@@ -61,6 +61,21 @@ struct rt_hip_plan {
     // by the next step run; last_step_lent: the last step run wrote the caller's
     double *step_ev_lent = nullptr, *step_nf_lent = nullptr;
     bool last_step_lent  = false;
+    // seed set (rt_hip_plan_set_seeds): up to RT_N_SEED_MAX seed profiles whose records one step run leaves.  The tables of
+    // the set live in one device block of their own (seedset_arena; seed_set[s] points into it, f[4] padded to Kp); on a
+    // forward ray grid seedset_tab holds, per seed, what seedtab_dev holds for the creation seed.  All records are ONE
+    // allocation, zeroed by the run's zeroing launch: n_seed blocks of seeds_stride doubles, each
+    // E_v [K] | pad to 256 bytes | nf [nx * ny] + spare | I_ang [na * nb] + spare (the per-device buffer of rt_multi.hip).
+    int n_seed = 0;
+    rt::DevSeed seed_set[RT_N_SEED_MAX] = {};
+    unsigned char *seedset_arena = nullptr;
+    unsigned char *seedset_tab   = nullptr;
+    const double *seedset_sf[RT_N_SEED_MAX]         = {};
+    const unsigned char *seedset_sin[RT_N_SEED_MAX] = {};
+    double *seeds_dev    = nullptr;
+    size_t seeds_doubles = 0;                                    // doubles of the allocation
+    size_t seeds_stride = 0, seeds_nf_off = 0, seeds_ang_off = 0; // doubles: block to block, E_v to nf, E_v to I_ang
+    int last_n_seed = 0;                                         // seeds of the last run (0: it ran without a set)
     size_t rec_bytes   = 0;
     hipEvent_t evm     = nullptr; // between march and frequency kernels
     const rt_ray *host_rays = nullptr; // ray list still on the host, uploaded by the next run (rt_hip_image_loop)
@@ -179,6 +194,9 @@ int plan_create_on(rt_hip_plan **out, hipStream_t upload_q, int device, int N, c
 // what rt_hip_plan_fetch does before it copies: wait for the last run, read the control block, repeat a run whose rays
 // failed with -2 / -3 in the checking mode (the plan must have run)
 int plan_settle_last_run(rt_hip_plan *p);
+// the factor tables of every seed of the plan's set on its forward ray grid (rt_seed_tab_kernel), rebuilt whenever the
+// grid or the set changes; without a set, a grid or the forward method: none
+int plan_build_seedset_tabs(rt_hip_plan *p);
 // most rays a list may hold (the kernels index rays with 32 bits)
 extern const size_t MAX_LIST_RAYS;
 
