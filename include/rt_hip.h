@@ -323,7 +323,8 @@ int rt_hip_calc_rays(int device, int N, double dz, const rt_gain *gain, const rt
  *     I_ang                                                     exactly as in image mode
  * and never allocates or writes an nx*ny*nv buffer.  The parent code's physical normalisation constants are not part of
  * the miniapp: they are linear factors, which the caller applies to these arrays.  W is not computed on this path.
- * The march runs as in image mode (two-kernel form; rt_hip_plan_last_fused is 0), rt_step_kernel
+ * The march runs as in image mode (two-kernel form; rt_hip_plan_last_fused is 0 -- unless the plan was told
+ * otherwise, rt_hip_plan_set_step_one_launch below), rt_step_kernel
  * (raytrace-miniapp_amd/csrc/rt_step.hip) takes the place of the frequency kernel and computes every Iv of every ray as
  * that kernel does, bit for bit, rt_hip_plan_set_exact_emission included: rt_hip_plan_kernel_times and the timing ring
  * report it as freq_ms.  E_v is summed per work-group in LDS and added to the result once per work-group, nf with one
@@ -378,6 +379,23 @@ int rt_hip_multi_step_loop(int ndev, int N, const rt_beam *beam, const rt_gain *
 int rt_hip_step_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed, int method,
                      const rt_ray *rays, size_t n_rays, double scale, double *E_v, double *nf, double *I_ang,
                      unsigned int *failure_code, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats);
+
+/* Step mode in ONE launch (opt-in; raytrace-miniapp_amd/csrc/rt_fused_step.hip): the march and the step pass as two phases
+ * of the same persistent waves, what the one-launch run is for image mode.  on = 1: every following step run that can
+ * takes it; on = 0 (the default, or RT_HIP_STEP_ONE_LAUNCH=1 in the environment at plan creation for on = 1): every step
+ * run is the march kernel and rt_step_kernel.  Any other value is RT_ERR_ARG.  The call is accepted in any mode and takes
+ * effect on step runs only; image, spectra and path runs are chosen as ever.
+ *   Taken by: emission (no seed), backward method, on a ray grid of the beam (rt_hip_plan_set_ray_grid with the beam's own
+ *   axes; first / stride / count included, any number of rays per pixel), march tables and step pass together within the
+ *   LDS of a compute unit, an I_ang histogram of at most 32 KB.  Lent step buffers, the caller's iang_dev, exact emission
+ *   and rt_hip_plan_update_gain work as in any step run.
+ *   Keeps two kernels, silently: ray lists, seeded plans and seed sets, the probe, any debug bit, a grid with one ray per
+ *   pixel on the beam's own image grid (the exclusive mode, whose nf is written by plain stores), tables that leave no
+ *   room in LDS, RT_HIP_FUSED=2 in the environment, and the checking repeat of a failing run.
+ * After a run that took it rt_hip_plan_last_fused is 1 and rt_hip_plan_kernel_times reports (launch, 0).  Every Iv of
+ * every ray is the double rt_step_kernel computes; E_v, nf and I_ang differ from the two-kernel run's by summation order
+ * only (the last tiles of a work-group are integrated in four parts of the frequency range, each adding its share). */
+int rt_hip_plan_set_step_one_launch(rt_hip_plan *plan, int on);
 
 /*
  * The gain tables of a resident plan replaced in place: a time loop whose plasma evolves has new n, g0, E0 and gv on the

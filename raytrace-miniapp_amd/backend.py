@@ -236,6 +236,17 @@ class Plan:
                       "rt_hip_plan_set_step_buffers")
         return self
 
+    def set_step_one_launch(self, on: bool = True) -> "Plan":
+        """Step runs as ONE launch where that applies (include/rt_hip.h, rt_hip_plan_set_step_one_launch): emission on a ray
+        grid of the beam, tables in LDS; everything else keeps the march and the step kernel.  Off by default.  Anything
+        but a bool or 0 / 1 is a ValueError raised here, before any native call."""
+        if isinstance(on, bool):
+            on = int(on)
+        if not isinstance(on, (int, np.integer)) or on not in (0, 1):
+            raise ValueError(f"set_step_one_launch: on is True / False (or 1 / 0), not {on!r}")
+        self.hl.check(self.hl.lib.rt_hip_plan_set_step_one_launch(self._h, int(on)), "rt_hip_plan_set_step_one_launch")
+        return self
+
     def fetch_step(self) -> dict:
         """E_v [nv], nf [nx * ny] (p = ix + iy nx), I_ang [na * nb] of the last step run (waits for it)."""
         b = self.problem.beam

@@ -340,6 +340,9 @@ def declare_hip_api(lib: C.CDLL) -> None:
         lib.rt_hip_plan_fetch_seed_step.restype = C.c_int
         lib.rt_hip_plan_seed_step_ptrs.argtypes = [vp, C.c_int, P(vp), P(vp), P(vp)]
         lib.rt_hip_plan_seed_step_ptrs.restype = C.c_int
+    if hasattr(lib, "rt_hip_plan_set_step_one_launch"):   # (likewise)
+        lib.rt_hip_plan_set_step_one_launch.argtypes = [vp, C.c_int]
+        lib.rt_hip_plan_set_step_one_launch.restype = C.c_int
     lib.rt_hip_plan_set_debug.argtypes = [vp, C.c_uint]
     lib.rt_hip_plan_set_debug.restype = C.c_int
     lib.rt_hip_plan_destroy.argtypes = [vp]
@@ -358,5 +361,6 @@ HIP_API_SYMBOLS = [
     "rt_hip_plan_set_step_buffers", "rt_hip_multi_step_loop",
     "rt_hip_plan_update_gain", "rt_hip_plan_update_gain_dev", "rt_hip_plan_table_flags",
     "rt_hip_plan_set_seeds", "rt_hip_plan_fetch_seed_step", "rt_hip_plan_seed_step_ptrs",
+    "rt_hip_plan_set_step_one_launch",
     "rt_hip_plan_set_debug", "rt_hip_plan_destroy",
 ]

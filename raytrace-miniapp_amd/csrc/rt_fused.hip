@@ -27,7 +27,8 @@
 //     wave of the work-group before they touch them (they are the last to run dry anyway).
 // The frequency pass itself is freq_tile of rt_freq.hip, unchanged; the stand-alone frequency kernel stays for
 // everything this kernel does not take (rt_launch.hip: seeded mode, the exclusive mode, probes, the path tracer,
-// the checking repeat of a failing run, tables that do not fit LDS).
+// the checking repeat of a failing run, tables that do not fit LDS).  Step mode is not taken here either: its one-launch
+// run is a kernel of its own with this kernel's first phase and the step pass as the second (rt_fused_step.hip, opt-in).
 #include "rt_freq.hip"
 
 namespace rt {

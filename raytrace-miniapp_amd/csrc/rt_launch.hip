@@ -3,7 +3,8 @@
 // Replaces the launch half of RayTraceImageCudaLoop (src/RayTraceImageCuda.cu:198-203: one thread-per-ray
 // launch): a run is the march kernel (persistent lanes over LDS-resident tables, rt_march.hip) -> one
 // 96-byte record per ray -> the frequency / deposit kernel (rt_freq.hip), back to back on one queue, or the
-// path tracer (rt_path.hip), the spectra kernel (rt_spec.hip) or the step kernel (rt_step.hip) in place of the frequency kernel.  This is the only translation unit with the
+// path tracer (rt_path.hip), the spectra kernel (rt_spec.hip) or the step kernel (rt_step.hip) in place of the frequency kernel -- or march and
+// frequency / step pass as ONE launch (rt_fused.hip, rt_fused_step.hip).  This is the only translation unit with the
 // kernels of the path in it; the rest of the library reaches them through the functions declared in
 // rt_runtime.h.
 #include "rt_path.hip" // debug path tracer (before rt_freq.hip: no FMA contraction there)
@@ -12,6 +13,7 @@
 #include "rt_spec.hip" // spectra mode: per-ray spectra in place of the deposit
 #include "rt_step.hip" // step mode: E_v, nf and I_ang, the image cube reduced on the way
 #include "rt_step_seeds.hip" // step mode with a seed set: one record per seed from one march
+#include "rt_fused_step.hip" // step mode as two phases of one launch (opt-in)
 
 #include "rt_runtime.h"
 
@@ -216,6 +218,11 @@ template <bool LDS_TAB, int MODE> void (*march_bounded(int opt))(const rt::DevPa
 template <int SF, int MAXQ, bool EMIS> void (*fused_bounded(int opt))(const rt::FusedKArg)
 {
     return opt == 7 ? rt::rt_fused_kernel<true, SF, MAXQ, EMIS, 7> : opt == 3 ? rt::rt_fused_kernel<true, SF, MAXQ, EMIS, 3> : rt::rt_fused_kernel<true, SF, MAXQ, EMIS, 0>;
+}
+
+template <int SF> void (*fused_step_bounded(int opt))(const rt::FusedStepKArg)
+{
+    return opt == 7 ? rt::rt_fused_step_kernel<true, SF, 7> : opt == 3 ? rt::rt_fused_step_kernel<true, SF, 3> : rt::rt_fused_step_kernel<true, SF, 0>;
 }
 
 // step mode: rt_step_kernel over all tiles, one 16-wave work-group per CU; the I_ang histogram in LDS where the frequency
@@ -502,8 +509,17 @@ int plan_launch_run(rt_hip_plan *p, hipStream_t stream)
     const bool fused_cand = lds_tab && n_launch == 1 && p->n_rays > 0 && !p->path_on && !p->spectra_on && !p->step_on && !p->probe_on && p->P.debug == 0 &&
                             (fused_emis || fused_gain) && !p->P.exclusive && p->P.safe == 0 &&
                             p->n_iang * sizeof(double) <= 32 * 1024 && env_unsigned("RT_HIP_FUSED", 1, 1, 2) == 1;
+    // ---- step mode in ONE launch (rt_fused_step.hip), where the caller has asked for it (rt_hip_plan_set_step_one_launch):
+    // the conditions of the emission run above without those that exist for the few-runs image deposit only -- the step
+    // pass writes no image, so neither 32 rays per pixel nor "a tile spans at most three pixels" is asked for.  Ray lists,
+    // seeded plans, seed sets, the exclusive mode (its plain stores into nf must not meet a split tile) and tables that
+    // leave no room keep the two kernels.
+    const bool step_cand = p->step_on && p->step_one_launch && lds_tab && n_launch == 1 && p->n_rays > 0 && p->P.use_emis && p->P.method == 1 &&
+                           p->P.own_cells && !p->probe_on && !p->path_on && !p->spectra_on && p->P.debug == 0 && p->P.safe == 0 &&
+                           !p->P.exclusive && p->n_seed == 0 && p->n_iang * sizeof(double) <= 32 * 1024 &&
+                           env_unsigned("RT_HIP_FUSED", 1, 1, 2) == 1;
     unsigned bthr = lds_tab ? 1024u : 256u;
-    if (lds_tab && !fused_cand) {
+    if (lds_tab && !fused_cand && !step_cand) {
         // Few rays per lane leave the persistent lanes waiting for the longest ray of a short
         // queue: below about three rays per lane, fewer and busier lanes win (ASE_small, 399 000
         // rays on 256 CUs: 0.65 ms with 1024 threads per CU, 0.44 ms with 512; 8 waves per CU is
@@ -614,7 +630,7 @@ int plan_launch_run(rt_hip_plan *p, hipStream_t stream)
     p->P.late_chunks = 0;
     p->P.late_waves  = 0;
     p->P.late_first  = 0;
-    if (fused_cand && grid > 0) {
+    if ((fused_cand || step_cand) && grid > 0) {
         const unsigned nw       = bthr / 64;
         // doubles per wave: transposition rows + window totals of the few-runs deposit for 2 pixel runs per tile (a pixel
         // has at least 64 rays) or 3, no row cache
@@ -623,10 +639,14 @@ int plan_launch_run(rt_hip_plan *p, hipStream_t stream)
         // gain-only: rows of the per-wave row cache (a seeded tile holds ~7 pixels; fewer than 4 rows is not worth having)
         int nslot               = emis ? 0 : (int) env_unsigned("RT_HIP_FUSED_ROWS", 7, 4, 16);
         size_t per_wave         = (size_t) rt::fused_wave_doubles(maxq) + (size_t) nslot * (size_t) rt::freq_row_stride(p->P.Kp);
+        if (step_cand) // the transposition rows of the wave sum, nothing else (rt_step.hip)
+            per_wave = (size_t) 4 * rt::XP_ROW;
         rt::FusedLay lay;
         lay.off_exp  = (unsigned) align_up(p->P.blob_bytes, 16);
         lay.off_iang = lay.off_exp + 2u * rt::EXP_TAB * (unsigned) sizeof(double);
         lay.off_ctl  = lay.off_iang + (unsigned) (((p->n_iang + 1) & ~(size_t) 1) * sizeof(double));
+        if (step_cand) // E_v [Kp] of the work-group behind the histogram: beside the tables, never under an overlaid buffer
+            lay.off_ctl = lay.off_iang + rt::fused_step_ev_off((int) p->n_iang) + (unsigned) ((size_t) p->P.Kp * sizeof(double));
         lay.off_rem  = lay.off_ctl + 16u;
         lay.off_nodes = lay.off_rem + nw * 32u * (unsigned) sizeof(unsigned);
         // nodes of the work-group's tile list in LDS: room for twice a work-group's share of the entries (a tile is one
@@ -688,28 +708,48 @@ int plan_launch_run(rt_hip_plan *p, hipStream_t stream)
             p->P.tile_begin = 0;
             p->P.tile_end   = p->P.n_tiles;
             p->P.freq_id    = 0;
-            rt::FusedKArg fa;
-            fa.P         = p->P;
-            fa.F         = freq_args(p, true, nslot, (unsigned long long) grid * nw);
-            fa.tile_next = p->tile_next;
-            fa.lay       = lay;
             const int S  = p->P.L * RT_N_SUB;
-            using fused_fn = void (*)(const rt::FusedKArg);
-            const fused_fn fk =
-                !emis     ? (S == 6 ? (bounded ? fused_bounded<6, 3, false>(opt) : rt::rt_fused_kernel<false, 6, 3, false>)
-                                    : (bounded ? fused_bounded<0, 3, false>(opt) : rt::rt_fused_kernel<false, 0, 3, false>))
-                : maxq == 2 ? (S == 6 ? (bounded ? fused_bounded<6, 2, true>(opt) : rt::rt_fused_kernel<false, 6, 2>)
-                                    : (bounded ? fused_bounded<0, 2, true>(opt) : rt::rt_fused_kernel<false, 0, 2>))
-                          : (S == 6 ? (bounded ? fused_bounded<6, 3, true>(opt) : rt::rt_fused_kernel<false, 6, 3>)
-                                    : (bounded ? fused_bounded<0, 3, true>(opt) : rt::rt_fused_kernel<false, 0, 3>));
-            {
+            unsigned long long fwant = ((unsigned long long) p->n_rays + bthr - 1) / bthr;
+            const unsigned fgrid     = (unsigned) (fwant < (unsigned long long) p->cu_count ? fwant : (unsigned long long) p->cu_count);
+            if (step_cand) {
+                // the step kernel's argument block as launch_step fills it (lent buffers and the run's I_ang through p->step
+                // and freq_args), behind the march's
+                const rt::FreqKArg f = freq_args(p, true, 0, (unsigned long long) grid * nw);
+                rt::FusedStepKArg sa;
+                memset(&sa, 0, sizeof(sa));
+                sa.P           = p->P;
+                sa.S.hot       = f.hot;
+                sa.S.hot.image = nullptr; // never touched: there is no cube
+                sa.S.cold      = f.cold;
+                sa.S.out       = p->step;
+                sa.tile_next   = p->tile_next;
+                sa.lay         = lay;
+                using fstep_fn = void (*)(const rt::FusedStepKArg);
+                const fstep_fn sk = S == 6 ? (bounded ? fused_step_bounded<6>(opt) : rt::rt_fused_step_kernel<false, 6>)
+                                           : (bounded ? fused_step_bounded<0>(opt) : rt::rt_fused_step_kernel<false, 0>);
+                const int rc = allow_lds(reinterpret_cast<const void *>(sk), p->device, flds, p->lds_limit);
+                if (rc != RT_OK)
+                    return rc;
+                hipLaunchKernelGGL(sk, dim3(fgrid), dim3(bthr), flds, stream, sa);
+            } else {
+                rt::FusedKArg fa;
+                fa.P         = p->P;
+                fa.F         = freq_args(p, true, nslot, (unsigned long long) grid * nw);
+                fa.tile_next = p->tile_next;
+                fa.lay       = lay;
+                using fused_fn = void (*)(const rt::FusedKArg);
+                const fused_fn fk =
+                    !emis     ? (S == 6 ? (bounded ? fused_bounded<6, 3, false>(opt) : rt::rt_fused_kernel<false, 6, 3, false>)
+                                        : (bounded ? fused_bounded<0, 3, false>(opt) : rt::rt_fused_kernel<false, 0, 3, false>))
+                    : maxq == 2 ? (S == 6 ? (bounded ? fused_bounded<6, 2, true>(opt) : rt::rt_fused_kernel<false, 6, 2>)
+                                        : (bounded ? fused_bounded<0, 2, true>(opt) : rt::rt_fused_kernel<false, 0, 2>))
+                              : (S == 6 ? (bounded ? fused_bounded<6, 3, true>(opt) : rt::rt_fused_kernel<false, 6, 3>)
+                                        : (bounded ? fused_bounded<0, 3, true>(opt) : rt::rt_fused_kernel<false, 0, 3>));
                 const int rc = allow_lds(reinterpret_cast<const void *>(fk), p->device, flds, p->lds_limit);
                 if (rc != RT_OK)
                     return rc;
+                hipLaunchKernelGGL(fk, dim3(fgrid), dim3(bthr), flds, stream, fa);
             }
-            unsigned long long fwant = ((unsigned long long) p->n_rays + bthr - 1) / bthr;
-            const unsigned fgrid     = (unsigned) (fwant < (unsigned long long) p->cu_count ? fwant : (unsigned long long) p->cu_count);
-            hipLaunchKernelGGL(fk, dim3(fgrid), dim3(bthr), flds, stream, fa);
             HIP_TRY(hipGetLastError());
             p->host_rays = nullptr;
             HIP_TRY(hipEventRecord(p->evm, stream));

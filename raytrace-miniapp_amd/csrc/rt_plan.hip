@@ -476,6 +476,7 @@ int rtr::plan_create_on(rt_hip_plan **out, hipStream_t upload_q, int device, int
     p->tables_bounded = all_bounded;
     p->ntest_proven   = all_bounded && ntest_proven;
     p->march_prune    = (int) env_unsigned("RT_HIP_MARCH_PRUNE", 1, 0, 2);
+    p->step_one_launch = env_unsigned("RT_HIP_STEP_ONE_LAUNCH", 0, 0, 1) == 1;
     if (tiny_spacing) {
         delete p;
         return fail_arg("rt_hip_plan_create: gain grid not strictly increasing, or spacing below 1e-30");
@@ -953,6 +954,16 @@ int rt_hip_plan_enable_step(rt_hip_plan *p, int on)
     if (on && (p->path_on || p->spectra_on))
         return fail_arg("rt_hip_plan_enable_step: the path tracer or spectra mode is enabled (one output mode at a time)");
     p->step_on = on != 0;
+    return RT_OK;
+}
+
+int rt_hip_plan_set_step_one_launch(rt_hip_plan *p, int on)
+{
+    if (!p)
+        return fail_arg("rt_hip_plan_set_step_one_launch: NULL plan");
+    if (on != 0 && on != 1)
+        return fail_arg("rt_hip_plan_set_step_one_launch: on is 0 or 1");
+    p->step_one_launch = on == 1; // (any mode: the next step run reads it, plan_launch_run)
     return RT_OK;
 }
 
@@ -1484,6 +1495,10 @@ int rt_hip_plan_kernel_times(rt_hip_plan *p, float *march_ms, float *freq_ms)
     HIP_TRY(hipEventSynchronize(p->ev1));
     HIP_TRY(hipEventElapsedTime(march_ms, p->ev0, p->evm));
     HIP_TRY(hipEventElapsedTime(freq_ms, p->evm, p->ev1));
+    // (a step run in one launch is (launch, 0) as include/rt_hip.h states it: what lies between its two last events is
+    // the distance of two event records on a queue, ~5 us -- 5 % of a launch of one ray)
+    if (p->last_fused && p->last_step)
+        *freq_ms = 0.0f;
     return RT_OK;
 }
 

@@ -6,7 +6,7 @@
 //                   rt_hip_image_loop (the host-pointer entry the C++ adapter calls)
 //   rt_raygrid.hip  a ray list that is really a tensor grid: recognition + bit-wise verification,
 //                   list-mode launch tangents and the probe of the host's libm
-//   rt_launch.hip   the kernels (rt_march.hip, rt_freq.hip, rt_path.hip, rt_spec.hip, rt_step.hip, rt_step_seeds.hip) and how a run puts them on a queue
+//   rt_launch.hip   the kernels (rt_march.hip, rt_freq.hip, rt_path.hip, rt_spec.hip, rt_step.hip, rt_step_seeds.hip, rt_fused_step.hip) and how a run puts them on a queue
 //   rt_multi.hip    all devices of the node: RCCL loader, communicator, rt_hip_multi_image_loop, rt_hip_multi_step_loop
 //   rt_tables.hip   the gain tables of a resident plan rewritten in place: scan and pack kernels, rt_hip_plan_update_gain
 // Only rt_launch.hip, rt_multi.hip and rt_tables.hip contain device code.
@@ -123,6 +123,9 @@ struct rt_hip_plan {
     unsigned *tile_next   = nullptr;
     size_t tile_next_n    = 0;
     bool last_fused       = false;
+    // step runs as ONE launch where that applies (rt_fused_step.hip): rt_hip_plan_set_step_one_launch, initial value from
+    // RT_HIP_STEP_ONE_LAUNCH at plan creation; off: every step run is the march and rt_step_kernel
+    bool step_one_launch  = false;
     // LDS a work-group may ask for on this device (hipDeviceAttributeMaxSharedMemoryPerBlock; 160 KB on gfx950)
     size_t lds_limit      = 0;
     // rt_hip_plan_update_gain (rt_tables.hip).  What rt_hip_plan_create derives from the GRIDS of a length, kept so that
