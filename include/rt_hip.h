@@ -248,6 +248,56 @@ int rt_hip_plan_last_fused(rt_hip_plan *plan);
  * size.  Every instance gives the same march records. */
 int rt_hip_plan_last_march_instance(rt_hip_plan *plan);
 
+/* What a run would look like on the device, decided from plain numbers: the function a run itself calls to choose its
+ * kernels, grids, LDS layout and chunking (raytrace-miniapp_amd/csrc/rt_run_shape.h), without a plan, a device or any
+ * device call -- so that the launch rules can be tested on a machine that has no GPU.  The RT_HIP_* tuning knobs are read
+ * from the environment exactly as a run reads them.  Both structs start with their own sizeof in `size` (set it in both
+ * before the call); NULL, a wrong size, cu_count < 1 or lds_limit == 0 fail with an argument error.
+ * facts: what a run takes from its plan.  rays_per_pixel = nga * ngb of the ray grid (0: a list); has_ray_list: the rays
+ * are a list on the device; host_rays: the list is still on the host (rt_hip_image_loop); occupancy_per_cu stands for the
+ * one device query a run makes (resident work-groups of the march instance per compute unit), consulted where a run
+ * consults the device and nowhere else -- occupancy_asked says whether it was. */
+typedef struct rt_hip_run_facts {
+    unsigned size;
+    int cu_count;
+    unsigned long long lds_limit, n_rays, blob_bytes, n_iang;
+    unsigned n_tiles;
+    int K, Kp, L, rays_per_pixel, n_seed, march_prune, method;
+    float c_h3;
+    unsigned safe, debug;
+    int use_emis, own_cells, exclusive, path_on, spectra_on, step_on, step_one_launch, probe_on, has_ray_list, host_rays,
+        tables_bounded, ntest_proven, gv_has_nan;
+    int occupancy_per_cu;
+} rt_hip_run_facts;
+/* kind: 0 = march and second pass as two kernels, 1 = the image run in one launch, 2 = the step run in one launch.
+ * The march (of a one-launch run: its march phase): lds_tab (tables in LDS) ... late_chunks; bounded, mode, opt and
+ * lds_tab name its instance, last_march_inst is what rt_hip_plan_last_march_instance would report.  chunk is that of a
+ * run of one march launch; with n_launch > 1 every upload slice takes the same rule on its own rays.
+ * maxq ... fgrid: a one-launch run only (else 0) -- the layout of its work-group in LDS (off_*, node_cap, n_free,
+ * per_wave in doubles, split, k_part, n_consumers, consumers_first), its LDS bytes, the links of its tile lists and
+ * its grid.  key_s6 / key_emis / key_excl pick the instance of the second pass.
+ * pass_*: the second pass this run takes (pass_kind 0 frequency, 1 spectra, 2 step, 3 step of a seed set, 4 path
+ * tracer: all zero); for a one-launch run the frequency (step) phase of that launch. */
+typedef struct rt_hip_run_shape {
+    unsigned size;
+    int kind, lds_tab;
+    unsigned n_launch, bthr;
+    int mode, bounded, opt, last_march_inst;
+    unsigned long long mlds;
+    unsigned grid, chunk, park, spin_limit, no_skip, late_first, late_waves, late_chunks;
+    int occupancy_asked;
+    int maxq, nslot;
+    unsigned off_exp, off_iang, off_ctl, off_rem, off_nodes, off_buf, node_cap, n_free, per_wave, split, k_part, n_consumers,
+        consumers_first;
+    unsigned long long flds, tile_links;
+    unsigned fgrid;
+    int key_s6, key_emis, key_excl;
+    int pass_kind, pass_wg_waves, pass_in_lds, pass_nslot;
+    unsigned long long pass_lds;
+    unsigned pass_grid, pass_fetch_shift;
+} rt_hip_run_shape;
+int rt_hip_debug_run_shape(const rt_hip_run_facts *facts, rt_hip_run_shape *out);
+
 /* Timing many back-to-back runs without waiting for each: keep the event triples of the last n_runs runs
  * (1 <= n_runs <= 4096); rt_hip_plan_ring_times waits for the last run and returns the kernel durations of
  * the most recent runs, oldest first (at most max_runs of them; *n_runs = how many).  Without a ring a plan

@@ -70,6 +70,29 @@ class RtStats(C.Structure):
     ]
 
 
+def _fields(spec: str) -> list:
+    """'uint: a b; ull: c' -> ctypes fields in that order (the diagnostic structs of rt_hip_debug_run_shape)."""
+    types = {"uint": C.c_uint, "int": C.c_int, "ull": C.c_ulonglong, "float": C.c_float}
+    return [(name, types[t.strip()]) for t, names in (g.split(":") for g in spec.split(";")) for name in names.split()]
+
+
+class RtRunFacts(C.Structure):
+    _fields_ = _fields(
+        "uint: size; int: cu_count; ull: lds_limit n_rays blob_bytes n_iang; uint: n_tiles;"
+        "int: K Kp L rays_per_pixel n_seed march_prune method; float: c_h3; uint: safe debug;"
+        "int: use_emis own_cells exclusive path_on spectra_on step_on step_one_launch probe_on has_ray_list host_rays"
+        " tables_bounded ntest_proven gv_has_nan; int: occupancy_per_cu")
+
+
+class RtRunShape(C.Structure):
+    _fields_ = _fields(
+        "uint: size; int: kind lds_tab; uint: n_launch bthr; int: mode bounded opt last_march_inst; ull: mlds;"
+        "uint: grid chunk park spin_limit no_skip late_first late_waves late_chunks; int: occupancy_asked; int: maxq nslot;"
+        "uint: off_exp off_iang off_ctl off_rem off_nodes off_buf node_cap n_free per_wave split k_part n_consumers"
+        " consumers_first; ull: flds tile_links; uint: fgrid; int: key_s6 key_emis key_excl;"
+        "int: pass_kind pass_wg_waves pass_in_lds pass_nslot; ull: pass_lds; uint: pass_grid pass_fetch_shift")
+
+
 def _dp(a: np.ndarray):
     assert a.dtype == np.float64 and a.flags.c_contiguous
     return a.ctypes.data_as(c_double_p)
@@ -343,6 +366,9 @@ def declare_hip_api(lib: C.CDLL) -> None:
     if hasattr(lib, "rt_hip_plan_set_step_one_launch"):   # (likewise)
         lib.rt_hip_plan_set_step_one_launch.argtypes = [vp, C.c_int]
         lib.rt_hip_plan_set_step_one_launch.restype = C.c_int
+    if hasattr(lib, "rt_hip_debug_run_shape"):   # (likewise)
+        lib.rt_hip_debug_run_shape.argtypes = [P(RtRunFacts), P(RtRunShape)]
+        lib.rt_hip_debug_run_shape.restype = C.c_int
     lib.rt_hip_plan_set_debug.argtypes = [vp, C.c_uint]
     lib.rt_hip_plan_set_debug.restype = C.c_int
     lib.rt_hip_plan_destroy.argtypes = [vp]
@@ -361,6 +387,6 @@ HIP_API_SYMBOLS = [
     "rt_hip_plan_set_step_buffers", "rt_hip_multi_step_loop",
     "rt_hip_plan_update_gain", "rt_hip_plan_update_gain_dev", "rt_hip_plan_table_flags",
     "rt_hip_plan_set_seeds", "rt_hip_plan_fetch_seed_step", "rt_hip_plan_seed_step_ptrs",
-    "rt_hip_plan_set_step_one_launch",
+    "rt_hip_plan_set_step_one_launch", "rt_hip_debug_run_shape",
     "rt_hip_plan_set_debug", "rt_hip_plan_destroy",
 ]

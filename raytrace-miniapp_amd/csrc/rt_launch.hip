@@ -6,7 +6,8 @@
 // path tracer (rt_path.hip), the spectra kernel (rt_spec.hip) or the step kernel (rt_step.hip) in place of the frequency kernel -- or march and
 // frequency / step pass as ONE launch (rt_fused.hip, rt_fused_step.hip).  This is the only translation unit with the
 // kernels of the path in it; the rest of the library reaches them through the functions declared in
-// rt_runtime.h.
+// rt_runtime.h.  What a run looks like is decided by the pure functions of rt_run_shape.h (facts of the plan + tuning from
+// the environment -> RunShape / PassShape); this file selects the instances, fills the argument blocks and enqueues.
 #include "rt_path.hip" // debug path tracer (before rt_freq.hip: no FMA contraction there)
 #include "rt_freq.hip" // kernel B (includes rt_march.hip, kernel A)
 #include "rt_fused.hip" // both as two phases of one launch
@@ -16,6 +17,7 @@
 #include "rt_fused_step.hip" // step mode as two phases of one launch (opt-in)
 
 #include "rt_runtime.h"
+#include "rt_run_shape.h" // what a run looks like: the pure decision (facts + tuning -> shape) this file enqueues
 
 #include <atomic>
 #include <cstdlib>
@@ -45,9 +47,98 @@ int allow_lds(const void *kernel, int device, size_t bytes, size_t limit)
     return RT_OK;
 }
 
+// every launch of the path: the LDS attribute where the launch needs it, the launch, its error
+template <typename Arg>
+int launch(const rt_hip_plan *p, void (*kernel)(const Arg), unsigned grid, unsigned block, size_t lds, hipStream_t stream, const Arg &a)
+{
+    const int rc = allow_lds(reinterpret_cast<const void *>(kernel), p->device, lds, p->lds_limit);
+    if (rc != RT_OK)
+        return rc;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, stream, a);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// ---- from a small key to the kernel instance, one function per family ----------------------------------------------
+// (the set of instances is what these functions name and nothing else: unbounded tables have no OPT and, of the MODEs,
+// only 0 and 1; the global-table march has MODE 0 only; the gain-only one-launch kernel MAXQ = 3 only)
+using march_fn      = void (*)(const rt::DevParams);
+using fused_fn      = void (*)(const rt::FusedKArg);
+using fused_step_fn = void (*)(const rt::FusedStepKArg);
+
+// the BOUNDED instances of the march by OPT (rt_march.hip): 0 as before; 3 = h1 pruned, no |n - n0| test; 7 = h2 and h4
+// pruned as well
+template <bool LDS_TAB, int MODE> march_fn march_bounded(int opt)
+{
+    return opt == 7 ? rt::rt_march_kernel<LDS_TAB, true, MODE, 7> : opt == 3 ? rt::rt_march_kernel<LDS_TAB, true, MODE, 3> : rt::rt_march_kernel<LDS_TAB, true, MODE, 0>;
+}
+march_fn march_kernel(bool lds_tab, bool bounded, int mode, int opt)
+{
+    if (!lds_tab)
+        return bounded ? march_bounded<false, 0>(opt) : rt::rt_march_kernel<false, false, 0>;
+    if (!bounded)
+        return mode == 1 ? rt::rt_march_kernel<true, false, 1> : rt::rt_march_kernel<true, false, 0>;
+    return mode == 1 ? march_bounded<true, 1>(opt) : mode == 2 ? march_bounded<true, 2>(opt) : mode == 3 ? march_bounded<true, 3>(opt)
+         : mode == 4 ? march_bounded<true, 4>(opt) : march_bounded<true, 0>(opt);
+}
+
+template <int SF, int MAXQ, bool EMIS> fused_fn fused_bounded(int opt)
+{
+    return opt == 7 ? rt::rt_fused_kernel<true, SF, MAXQ, EMIS, 7> : opt == 3 ? rt::rt_fused_kernel<true, SF, MAXQ, EMIS, 3> : rt::rt_fused_kernel<true, SF, MAXQ, EMIS, 0>;
+}
+template <int SF> fused_fn fused_kernel_sf(bool bounded, int maxq, bool emis, int opt)
+{
+    if (!emis)
+        return bounded ? fused_bounded<SF, 3, false>(opt) : rt::rt_fused_kernel<false, SF, 3, false>;
+    if (maxq == 2)
+        return bounded ? fused_bounded<SF, 2, true>(opt) : rt::rt_fused_kernel<false, SF, 2>;
+    return bounded ? fused_bounded<SF, 3, true>(opt) : rt::rt_fused_kernel<false, SF, 3>;
+}
+fused_fn fused_kernel(bool bounded, bool s6, int maxq, bool emis, int opt)
+{
+    return s6 ? fused_kernel_sf<6>(bounded, maxq, emis, opt) : fused_kernel_sf<0>(bounded, maxq, emis, opt);
+}
+
+template <int SF> fused_step_fn fused_step_bounded(int opt)
+{
+    return opt == 7 ? rt::rt_fused_step_kernel<true, SF, 7> : opt == 3 ? rt::rt_fused_step_kernel<true, SF, 3> : rt::rt_fused_step_kernel<true, SF, 0>;
+}
+fused_step_fn fused_step_kernel(bool bounded, bool s6, int opt)
+{
+    return s6 ? (bounded ? fused_step_bounded<6>(opt) : rt::rt_fused_step_kernel<false, 6>)
+              : (bounded ? fused_step_bounded<0>(opt) : rt::rt_fused_step_kernel<false, 0>);
+}
+
+// frequency kernel variants: SF = compile-time number of sub-segments (6 <=> N = 3, the shipped inputs; 0 = any N)
+void (*freq_kernel(bool s6, bool emis, bool excl))(const rt::FreqKArg)
+{
+    if (emis && excl)
+        return s6 ? rt::rt_freq_kernel<6, true, true> : rt::rt_freq_kernel<0, true, true>;
+    if (emis)
+        return s6 ? rt::rt_freq_kernel<6, true, false> : rt::rt_freq_kernel<0, true, false>;
+    return s6 ? rt::rt_freq_kernel<6, false, false> : rt::rt_freq_kernel<0, false, false>;
+}
+void (*spec_kernel(bool s6, bool emis))(const rt::SpecKArg)
+{
+    return emis ? (s6 ? rt::rt_spec_kernel<6, true> : rt::rt_spec_kernel<0, true>) : (s6 ? rt::rt_spec_kernel<6, false> : rt::rt_spec_kernel<0, false>);
+}
+void (*step_kernel(bool s6, bool emis))(const rt::StepKArg)
+{
+    return emis ? (s6 ? rt::rt_step_kernel<6, true> : rt::rt_step_kernel<0, true>) : (s6 ? rt::rt_step_kernel<6, false> : rt::rt_step_kernel<0, false>);
+}
+void (*seeds_kernel(bool s6))(const rt::SeedsKArg) { return s6 ? rt::rt_step_seeds_kernel<6> : rt::rt_step_seeds_kernel<0>; }
+
+// what a launch of the frequency pass covers: tiles [tile_begin, tile_end) on tile counter freq_id (a run is one launch
+// over all tiles; the range exists for experiments that split it), and the marks of the checking repeat (DevParams::safe)
+struct PassRun {
+    unsigned tile_begin, tile_end, freq_id;
+    unsigned safe;
+    unsigned char *bad;
+};
+
 // the frequency pass's own argument block (rt_device.h): hot = what the frequency loop reads, cold = what the
 // per-ray preamble of a tile reads
-rt::FreqKArg freq_args(const rt_hip_plan *p, bool iang_in_lds, int nslot, unsigned long long grid_waves)
+rt::FreqKArg freq_args(const rt_hip_plan *p, bool iang_in_lds, int nslot, unsigned fetch_shift, const PassRun &r)
 {
     const rt::DevParams &P = p->P;
     rt::FreqKArg a;
@@ -61,7 +152,7 @@ rt::FreqKArg freq_args(const rt_hip_plan *p, bool iang_in_lds, int nslot, unsign
     a.hot.ctl        = P.ctl;
     a.hot.dv2        = p->dv2_dev;
     a.hot.seed_fk    = P.has_seed ? P.seed.f[4] : nullptr;
-    a.hot.bad        = P.bad;
+    a.hot.bad        = r.bad;
     a.hot.scale      = P.scale;
     a.hot.gs_cap     = P.gs_cap;
     a.hot.K          = P.K;
@@ -70,21 +161,16 @@ rt::FreqKArg freq_args(const rt_hip_plan *p, bool iang_in_lds, int nslot, unsign
     a.hot.method     = P.method;
     a.hot.rec_stride = P.rec_stride;
     a.hot.n_rays     = (unsigned) P.rays.count;
-    a.hot.tile_begin = P.tile_begin;
-    a.hot.tile_end   = P.tile_end;
-    a.hot.freq_id    = P.freq_id;
-    {
-        unsigned sh = 0;
-        while ((1ull << sh) < 2ull * grid_waves) // 2 x waves
-            sh++;
-        a.hot.fetch_shift = sh;
-    }
+    a.hot.tile_begin = r.tile_begin;
+    a.hot.tile_end   = r.tile_end;
+    a.hot.freq_id    = r.freq_id;
+    a.hot.fetch_shift = fetch_shift;
     a.hot.nslot      = nslot;
     a.hot.nx         = P.beam.nx;
     a.hot.ny         = P.beam.ny;
     a.hot.n_ang      = P.beam.na * P.beam.nb;
-    a.hot.flags      = (P.exclusive ? rt::FQ_EXCLUSIVE : 0u) | (P.safe == 1 ? rt::FQ_SAFE_CHECK : 0u) |
-                  (P.safe == 2 ? rt::FQ_SAFE_SKIP : 0u) | (P.exact_emis ? rt::FQ_EXACT_EMIS : 0u) |
+    a.hot.flags      = (P.exclusive ? rt::FQ_EXCLUSIVE : 0u) | (r.safe == 1 ? rt::FQ_SAFE_CHECK : 0u) |
+                  (r.safe == 2 ? rt::FQ_SAFE_SKIP : 0u) | (P.exact_emis ? rt::FQ_EXACT_EMIS : 0u) |
                   (P.has_seed ? rt::FQ_HAS_SEED : 0u) | (P.probe_on ? rt::FQ_PROBE : 0u) |
                   (p->gv_has_nan ? rt::FQ_GV_NAN : 0u) | (iang_in_lds ? rt::FQ_IANG_LDS : 0u) |
                   ((P.method != 1 || P.has_seed || P.probe_on) ? rt::FQ_NEED_EXIT : 0u) |
@@ -96,226 +182,103 @@ rt::FreqKArg freq_args(const rt_hip_plan *p, bool iang_in_lds, int nslot, unsign
     return a;
 }
 
-// frequency kernel variants: SF = compile-time number of sub-segments (6 <=> N = 3,
-// the shipped inputs; 0 = any N)
-template <int SF, bool EMIS, bool EXCL> int launch_freq(rt_hip_plan *p, hipStream_t stream, unsigned cap_blocks)
+RunFacts run_facts(const rt_hip_plan *p)
 {
-    const size_t ang_bytes = p->n_iang * sizeof(double);
-    // (one global atomic per ray on na*nb addresses serialises badly: the histogram stays in LDS)
-    const int in_lds       = ang_bytes <= 32 * 1024;
-    // Work-groups of FREQ_WG_WAVES waves; the register budget allows `waves` per SIMD, i.e. wg_per_cu work-groups.
-    // Per-wave row cache for tiles with several pixel runs (seeded): up to 16 rows of Kp doubles, as many as fit
-    // into the work-group's share of the 160 KB beside the exponent tables, the I_ang histogram and the per-wave
-    // transposition rows (rt_freq.hip: freq_lds_doubles); fewer than 4 rows is not worth having.
-    const int waves       = EMIS ? rt::FREQ_WAVES : rt::FREQ_WAVES_SEED;
-    constexpr bool excl   = EXCL; // (= p->P.exclusive: launch_freq_any picks the instance)
-    // (exclusive mode: while its flush wrote 8 bytes per lane with a pixel look-up per store, 12 waves per CU ran 3.6 %
-    // faster than 16; with the regular-tile flush of 16-byte stores 16 waves win -- 22.15 against 23.0 ms on the
-    // 4096^2 x 512 image, tools/config5_waves.py)
-    int wg_waves          = (int) env_unsigned("RT_HIP_FREQ_WG_WAVES", (unsigned) rt::FREQ_WG_WAVES, 1, (unsigned) rt::FREQ_WG_WAVES);
-    int wg_per_cu         = waves * 4 / wg_waves;
-    wg_per_cu             = wg_per_cu < 1 ? 1 : wg_per_cu;
-    auto lds_of           = [&](int rows) { return rt::freq_lds_doubles(in_lds != 0, (int) p->n_iang, excl, rows, p->P.Kp, wg_waves) * sizeof(double); };
-    auto rows_that_fit    = [&](size_t budget) {
-        int rows = 0;
-        while (rows < 16 && lds_of(rows + 1) + 1024 <= budget)
-            rows++;
-        return rows;
-    };
-    int nslot = 0;
-    if (!excl) { // (exclusive mode: no reduction at all; the space holds the store staging rows instead)
-        nslot = rows_that_fit(p->lds_limit / (size_t) wg_per_cu);
-        const int min_rows = (int) env_unsigned("RT_HIP_FREQ_MIN_ROWS", 7, 0, 16);
-        if (!EMIS && nslot < min_rows && wg_per_cu > 1) { // seeded tiles hold ~7 pixels: rather one work-group less per CU than no row for them
-            wg_per_cu--;
-            nslot = rows_that_fit(p->lds_limit / (size_t) wg_per_cu);
-        }
-        nslot = nslot < 4 ? 0 : nslot;
-    }
-    const size_t lds = lds_of(nslot);
-    // persistent grid: as many work-groups per CU as LDS (160 KB) and the wave slots allow; the
-    // occupancy API under-reports large-LDS kernels, and an over-sized grid is harmless here
-    // (surplus work-groups find the tile counter exhausted and leave)
-    int per_cu = (int) (p->lds_limit / (lds + 512));
-    per_cu     = per_cu > wg_per_cu ? wg_per_cu : (per_cu < 1 ? 1 : per_cu);
-    per_cu = (int) env_unsigned("RT_HIP_FREQ_WGS", (unsigned) per_cu, 1, 16); // tuning override
-    unsigned long long want = ((unsigned long long) (p->P.tile_end - p->P.tile_begin) + (unsigned) wg_waves - 1) / (unsigned) wg_waves;
-    unsigned long long cap  = (unsigned long long) p->cu_count * (unsigned) per_cu;
-    if (cap_blocks && cap > cap_blocks)
-        cap = cap_blocks;
-    const unsigned grid = (unsigned) (want < cap ? want : cap);
-    if (grid > 0) {
-        const rt::FreqKArg a = freq_args(p, in_lds != 0, nslot, (unsigned long long) grid * (unsigned) wg_waves);
-        if (lds > p->lds_limit) {
-            char msg[256];
-            snprintf(msg, sizeof(msg), "frequency kernel: %zu bytes of LDS per work-group (I_ang histogram of %zu cells, %d waves) "
-                     "exceed the device's %zu", lds, p->n_iang, wg_waves, p->lds_limit);
-            return fail_arg(msg);
-        }
-        {
-            const int rc = allow_lds(reinterpret_cast<const void *>(&rt::rt_freq_kernel<SF, EMIS, EXCL>), p->device, lds, p->lds_limit);
-            if (rc != RT_OK)
-                return rc;
-        }
-        hipLaunchKernelGGL((rt::rt_freq_kernel<SF, EMIS, EXCL>), dim3(grid), dim3((unsigned) wg_waves * 64), lds, stream, a);
-        HIP_TRY(hipGetLastError());
-    }
-    return RT_OK;
+    const rt::DevParams &P = p->P;
+    RunFacts f;
+    f.cu_count        = p->cu_count;
+    f.lds_limit       = p->lds_limit;
+    f.n_rays          = p->n_rays;
+    f.n_tiles         = P.n_tiles;
+    f.blob_bytes      = P.blob_bytes;
+    f.K               = P.K;
+    f.Kp              = P.Kp;
+    f.L               = P.L;
+    f.n_iang          = p->n_iang;
+    f.rays_per_pixel  = P.rays.nga * P.rays.ngb;
+    f.n_seed          = p->n_seed;
+    f.c_h3            = P.c_h3;
+    f.march_prune     = p->march_prune;
+    f.method          = P.method;
+    f.safe            = P.safe;
+    f.debug           = P.debug;
+    f.use_emis        = P.use_emis != 0;
+    f.own_cells       = P.own_cells != 0;
+    f.exclusive       = P.exclusive != 0;
+    f.path_on         = p->path_on;
+    f.spectra_on      = p->spectra_on;
+    f.step_on         = p->step_on;
+    f.step_one_launch = p->step_one_launch;
+    f.probe_on        = p->probe_on;
+    f.has_ray_list    = P.rays.list != nullptr;
+    f.host_rays       = p->host_rays != nullptr;
+    f.tables_bounded  = p->tables_bounded;
+    f.ntest_proven    = p->ntest_proven;
+    f.gv_has_nan      = p->gv_has_nan;
+    return f;
 }
 
-int launch_freq_any(rt_hip_plan *p, hipStream_t stream, unsigned tile_begin = 0, unsigned tile_end = ~0u,
-                           unsigned freq_id = 0)
+// The second pass over all tiles as a kernel of its own: the frequency / deposit kernel, or in its place the spectra
+// kernel (per-ray spectra, no image), the step kernel (E_v, nf and I_ang, no image cube) or the step kernel of a seed set.
+int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kind, hipStream_t stream, unsigned safe = 0, unsigned char *bad = nullptr)
 {
-    p->P.tile_begin = tile_begin;
-    p->P.tile_end   = tile_end < p->P.n_tiles ? tile_end : p->P.n_tiles;
-    p->P.freq_id    = freq_id;
-    const int S = p->P.L * RT_N_SUB;
-    if (p->P.use_emis && p->P.exclusive)
-        return (S == 6) ? launch_freq<6, true, true>(p, stream, 0) : launch_freq<0, true, true>(p, stream, 0);
-    if (p->P.use_emis)
-        return (S == 6) ? launch_freq<6, true, false>(p, stream, 0) : launch_freq<0, true, false>(p, stream, 0);
-    // (rt_hip_plan_set_ray_grid grants the exclusive mode with emission only)
-    return (S == 6) ? launch_freq<6, false, false>(p, stream, 0) : launch_freq<0, false, false>(p, stream, 0);
-}
-
-// spectra mode: rt_spec_kernel over all tiles, one 16-wave work-group per CU (the staging rows of 16 waves and the
-// exponent tables take 148 KB of LDS)
-template <int SF, bool EMIS> int launch_spec(rt_hip_plan *p, hipStream_t stream)
-{
-    const int wg_waves = rt::FREQ_WG_WAVES;
-    const size_t lds   = ((size_t) 2 * rt::EXP_TAB + (size_t) wg_waves * rt::WAVE * rt::XS_ROW) * sizeof(double);
-    if (lds > p->lds_limit)
+    const PassShape s = pass_shape(kind, f, t);
+    if (kind == PASS_SPEC && s.lds > f.lds_limit)
         return fail_arg("spectra kernel: the staging rows do not fit into the LDS of this device");
-    const unsigned long long want = ((unsigned long long) p->P.n_tiles + (unsigned) wg_waves - 1) / (unsigned) wg_waves;
-    const unsigned grid           = (unsigned) (want < (unsigned long long) p->cu_count ? want : (unsigned long long) p->cu_count);
-    if (grid == 0)
-        return RT_OK;
-    p->P.tile_begin = 0;
-    p->P.tile_end   = p->P.n_tiles;
-    p->P.freq_id    = 0;
-    const rt::FreqKArg f = freq_args(p, false, 0, (unsigned long long) grid * (unsigned) wg_waves);
-    rt::SpecKArg a;
-    memset(&a, 0, sizeof(a));
-    a.hot       = f.hot;
-    a.hot.image = nullptr;
-    a.hot.iang  = nullptr;
-    a.cold      = f.cold;
-    a.out       = p->spec[p->spec_sel];
-    const int rc = allow_lds(reinterpret_cast<const void *>(&rt::rt_spec_kernel<SF, EMIS>), p->device, lds, p->lds_limit);
-    if (rc != RT_OK)
-        return rc;
-    hipLaunchKernelGGL((rt::rt_spec_kernel<SF, EMIS>), dim3(grid), dim3((unsigned) wg_waves * 64), lds, stream, a);
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
-}
-
-// the BOUNDED instances of the march by OPT (rt_march.hip): 0 as before; 3 = h1 pruned, no |n - n0| test; 7 = h2 and h4
-// pruned as well
-template <bool LDS_TAB, int MODE> void (*march_bounded(int opt))(const rt::DevParams)
-{
-    return opt == 7 ? rt::rt_march_kernel<LDS_TAB, true, MODE, 7> : opt == 3 ? rt::rt_march_kernel<LDS_TAB, true, MODE, 3> : rt::rt_march_kernel<LDS_TAB, true, MODE, 0>;
-}
-template <int SF, int MAXQ, bool EMIS> void (*fused_bounded(int opt))(const rt::FusedKArg)
-{
-    return opt == 7 ? rt::rt_fused_kernel<true, SF, MAXQ, EMIS, 7> : opt == 3 ? rt::rt_fused_kernel<true, SF, MAXQ, EMIS, 3> : rt::rt_fused_kernel<true, SF, MAXQ, EMIS, 0>;
-}
-
-template <int SF> void (*fused_step_bounded(int opt))(const rt::FusedStepKArg)
-{
-    return opt == 7 ? rt::rt_fused_step_kernel<true, SF, 7> : opt == 3 ? rt::rt_fused_step_kernel<true, SF, 3> : rt::rt_fused_step_kernel<true, SF, 0>;
-}
-
-// step mode: rt_step_kernel over all tiles, one 16-wave work-group per CU; the I_ang histogram in LDS where the frequency
-// kernel keeps it there
-template <int SF, bool EMIS> int launch_step(rt_hip_plan *p, hipStream_t stream)
-{
-    const int wg_waves = rt::FREQ_WG_WAVES;
-    const bool in_lds  = p->n_iang * sizeof(double) <= 32 * 1024;
-    const size_t lds   = rt::step_lds_doubles(in_lds, (int) p->n_iang, p->P.Kp, wg_waves) * sizeof(double);
-    if (lds > p->lds_limit)
+    if (kind == PASS_STEP && s.lds > f.lds_limit)
         return fail_arg("step kernel: the E_v accumulator (nv doubles) does not fit into the LDS of this device");
-    const unsigned long long want = ((unsigned long long) (p->P.tile_end - p->P.tile_begin) + (unsigned) wg_waves - 1) / (unsigned) wg_waves;
-    const unsigned grid           = (unsigned) (want < (unsigned long long) p->cu_count ? want : (unsigned long long) p->cu_count);
-    if (grid == 0)
-        return RT_OK;
-    const rt::FreqKArg f = freq_args(p, in_lds, 0, (unsigned long long) grid * (unsigned) wg_waves);
-    rt::StepKArg a;
-    memset(&a, 0, sizeof(a));
-    a.hot       = f.hot;
-    a.hot.image = nullptr; // never touched: there is no cube
-    a.cold      = f.cold;
-    a.out       = p->step;
-    const int rc = allow_lds(reinterpret_cast<const void *>(&rt::rt_step_kernel<SF, EMIS>), p->device, lds, p->lds_limit);
-    if (rc != RT_OK)
-        return rc;
-    hipLaunchKernelGGL((rt::rt_step_kernel<SF, EMIS>), dim3(grid), dim3((unsigned) wg_waves * 64), lds, stream, a);
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
-}
-
-// step mode with a seed set: rt_step_seeds_kernel over all tiles, one 16-wave work-group per CU; one I_ang histogram per
-// seed in LDS where rt_step_kernel keeps its one there and all of them fit, global atomics otherwise
-template <int SF> int launch_step_seeds(rt_hip_plan *p, hipStream_t stream)
-{
-    const int wg_waves = rt::FREQ_WG_WAVES;
-    const int n_seed   = p->n_seed;
-    bool in_lds        = p->n_iang * sizeof(double) <= 32 * 1024;
-    size_t lds         = rt::step_seeds_lds_doubles(in_lds, (int) p->n_iang, p->P.Kp, wg_waves, n_seed) * sizeof(double);
-    if (in_lds && lds > p->lds_limit) {
-        in_lds = false;
-        lds    = rt::step_seeds_lds_doubles(false, (int) p->n_iang, p->P.Kp, wg_waves, n_seed) * sizeof(double);
-    }
-    if (lds > p->lds_limit)
+    if (kind == PASS_SEEDS && s.lds > f.lds_limit)
         return fail_arg("step kernel of a seed set: the E_v accumulators (nv doubles per seed) do not fit into the LDS of this device");
-    const unsigned long long want = ((unsigned long long) (p->P.tile_end - p->P.tile_begin) + (unsigned) wg_waves - 1) / (unsigned) wg_waves;
-    const unsigned grid           = (unsigned) (want < (unsigned long long) p->cu_count ? want : (unsigned long long) p->cu_count);
-    if (grid == 0)
+    if (s.grid == 0)
         return RT_OK;
-    const rt::FreqKArg f = freq_args(p, in_lds, 0, (unsigned long long) grid * (unsigned) wg_waves);
+    if (s.lds > f.lds_limit) {
+        char msg[256];
+        snprintf(msg, sizeof(msg), "frequency kernel: %zu bytes of LDS per work-group (I_ang histogram of %zu cells, %d waves) "
+                 "exceed the device's %zu", s.lds, f.n_iang, s.wg_waves, f.lds_limit);
+        return fail_arg(msg);
+    }
+    const rt::FreqKArg fa = freq_args(p, s.in_lds, s.nslot, s.fetch_shift, PassRun{ 0, f.n_tiles, 0, safe, bad });
+    const unsigned block  = (unsigned) s.wg_waves * 64;
+    if (kind == PASS_FREQ)
+        return launch(p, freq_kernel(f.s6(), f.use_emis, f.use_emis && f.exclusive), s.grid, block, s.lds, stream, fa);
+    if (kind == PASS_SPEC) {
+        rt::SpecKArg a;
+        memset(&a, 0, sizeof(a));
+        a.hot       = fa.hot;
+        a.hot.image = nullptr;
+        a.hot.iang  = nullptr;
+        a.cold      = fa.cold;
+        a.out       = p->spec[p->spec_sel];
+        return launch(p, spec_kernel(f.s6(), f.use_emis), s.grid, block, s.lds, stream, a);
+    }
+    if (kind == PASS_STEP) {
+        rt::StepKArg a;
+        memset(&a, 0, sizeof(a));
+        a.hot       = fa.hot;
+        a.hot.image = nullptr; // never touched: there is no cube
+        a.cold      = fa.cold;
+        a.out       = p->step;
+        return launch(p, step_kernel(f.s6(), f.use_emis), s.grid, block, s.lds, stream, a);
+    }
+    // a seed set (a seeded plan: gain-only): one record per seed
     rt::SeedsKArg a;
     memset(&a, 0, sizeof(a));
-    a.hot         = f.hot;
+    a.hot         = fa.hot;
     a.hot.image   = nullptr; // never touched: there is no cube
     a.hot.seed_fk = nullptr; // (the creation seed is not part of the set)
-    a.cold        = f.cold;
-    a.set.n_seed  = n_seed;
-    for (int s = 0; s < n_seed; s++) {
-        double *blk       = p->seeds_dev + (size_t) s * p->seeds_stride;
-        a.set.out[s]      = rt::SeedRec{ blk, blk + p->seeds_nf_off, blk + p->seeds_ang_off };
-        a.set.fk[s]       = p->seed_set[s].f[4];
-        a.set.sf[s]       = p->P.rays.sf ? p->seedset_sf[s] : nullptr;
-        a.set.sin[s]      = p->P.rays.sf ? p->seedset_sin[s] : nullptr;
-        a.set.seed[s]     = p->seed_set[s];
-        if (p->P.rays.sf && (!a.set.sf[s] || !a.set.sin[s]))
+    a.cold        = fa.cold;
+    a.set.n_seed  = f.n_seed;
+    for (int i = 0; i < f.n_seed; i++) {
+        double *blk   = p->seeds_dev + (size_t) i * p->seeds_stride;
+        a.set.out[i]  = rt::SeedRec{ blk, blk + p->seeds_nf_off, blk + p->seeds_ang_off };
+        a.set.fk[i]   = p->seed_set[i].f[4];
+        a.set.sf[i]   = p->P.rays.sf ? p->seedset_sf[i] : nullptr;
+        a.set.sin[i]  = p->P.rays.sf ? p->seedset_sin[i] : nullptr;
+        a.set.seed[i] = p->seed_set[i];
+        if (p->P.rays.sf && (!a.set.sf[i] || !a.set.sin[i]))
             return fail_arg("step kernel of a seed set: the factor tables of the set were not built for this ray grid");
     }
-    const int rc = allow_lds(reinterpret_cast<const void *>(&rt::rt_step_seeds_kernel<SF>), p->device, lds, p->lds_limit);
-    if (rc != RT_OK)
-        return rc;
-    hipLaunchKernelGGL((rt::rt_step_seeds_kernel<SF>), dim3(grid), dim3((unsigned) wg_waves * 64), lds, stream, a);
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
-}
-
-int launch_step_any(rt_hip_plan *p, hipStream_t stream)
-{
-    p->P.tile_begin = 0;
-    p->P.tile_end   = p->P.n_tiles;
-    p->P.freq_id    = 0;
-    const int S = p->P.L * RT_N_SUB;
-    if (p->n_seed > 0) // (a seeded plan: gain-only)
-        return (S == 6) ? launch_step_seeds<6>(p, stream) : launch_step_seeds<0>(p, stream);
-    if (p->P.use_emis)
-        return (S == 6) ? launch_step<6, true>(p, stream) : launch_step<0, true>(p, stream);
-    return (S == 6) ? launch_step<6, false>(p, stream) : launch_step<0, false>(p, stream);
-}
-
-int launch_spec_any(rt_hip_plan *p, hipStream_t stream)
-{
-    const int S = p->P.L * RT_N_SUB;
-    if (p->P.use_emis)
-        return (S == 6) ? launch_spec<6, true>(p, stream) : launch_spec<0, true>(p, stream);
-    return (S == 6) ? launch_spec<6, false>(p, stream) : launch_spec<0, false>(p, stream);
+    return launch(p, seeds_kernel(f.s6()), s.grid, block, s.lds, stream, a);
 }
 
 } // namespace
@@ -416,10 +379,11 @@ int plan_repeat_checked(rt_hip_plan *p)
     HIP_TRY(hipMemsetAsync(&p->ctl->n_failed, 0, sizeof(unsigned), stream));
     HIP_TRY(hipMemsetAsync(p->ctl->seed_code, 0, sizeof(p->ctl->seed_code), stream));
     HIP_TRY(hipMemsetAsync(p->ctl->next_tile_f, 0, sizeof(p->ctl->next_tile_f), stream));
-    p->P.bad  = p->bad_dev;
-    p->P.safe = 1;
     const bool step = p->last_step; // a step run: the step kernel honours the same marks, E_v and nf start over
-    int rc    = step ? launch_step_any(p, stream) : launch_freq_any(p, stream);
+    const RunFacts f    = run_facts(p);
+    const Tuning t      = read_tuning();
+    const PassKind kind = step ? (f.n_seed > 0 ? PASS_SEEDS : PASS_STEP) : PASS_FREQ;
+    int rc              = launch_pass(p, f, t, kind, stream, 1, p->bad_dev);
     if (rc == RT_OK) {
         if (step && p->last_step_lent) { // (the caller's buffers: exactly the K and nx * ny doubles that are the run's)
             HIP_TRY(hipMemsetAsync(p->step.E_v, 0, (size_t) p->P.K * sizeof(double), stream));
@@ -432,46 +396,34 @@ int plan_repeat_checked(rt_hip_plan *p)
             HIP_TRY(hipMemsetAsync(p->last_image, 0, p->n_image * sizeof(double), stream));
         HIP_TRY(hipMemsetAsync(p->last_iang, 0, p->n_iang * sizeof(double), stream));
         HIP_TRY(hipMemsetAsync(p->ctl->next_tile_f, 0, sizeof(p->ctl->next_tile_f), stream));
-        p->P.safe = 2;
-        rc        = step ? launch_step_any(p, stream) : launch_freq_any(p, stream);
+        rc = launch_pass(p, f, t, kind, stream, 2, p->bad_dev);
     }
-    p->P.safe = 0;
-    p->P.bad  = nullptr;
     if (rc != RT_OK)
         return rc;
     HIP_TRY(hipStreamSynchronize(stream));
     return RT_OK;
 }
 
-// The chunks at the end of the ray list that only the oldest wave of every SIMD takes (rt_march.hip, "The end of a
-// launch"): about as many rays as those waves march in one drain period, RT_HIP_LATE_X10 tenths of a ray per lane of
-// theirs (0: no such zone), at most RT_HIP_LATE_CAP per cent of the launch (20: swept 8 ... 35 on the 8- and 16-rank shards and
-// ASE_small.dat, profiles/r05_fused_end.txt).
-static void late_zone(rt_hip_plan *p, unsigned grid, unsigned waves_per_wg, unsigned first_marching_wave, const char *env = "RT_HIP_LATE_X10",
-                      unsigned def_x10 = 32)
+// ---- the steps of a run --------------------------------------------------------------------------------------------
+// step 2's device query: what hipOccupancyMaxActiveBlocksPerMultiprocessor says of the march instance `s` names (its LDS
+// attribute raised first, as the launch will need it anyway)
+static int march_occupancy(const rt_hip_plan *p, const RunShape &s, int &rc)
 {
-    // (the waves that take the late chunks must be waves that march: waves_per_wg counts the marching waves,
-    // first_marching_wave is where they start inside the work-group)
-    p->P.late_first = first_marching_wave;
-    const unsigned x10   = env_unsigned(env, def_x10, 0, 1000);
-    const unsigned waves = env_unsigned("RT_HIP_LATE_WAVES", 4, 0, 16);
-    p->P.late_waves  = waves < waves_per_wg ? waves : waves_per_wg;
-    p->P.late_chunks = 0;
-    if (x10 == 0 || p->P.late_waves == 0 || p->P.chunk == 0)
-        return;
-    unsigned long long rays = (unsigned long long) grid * p->P.late_waves * 64ull * x10 / 10ull;
-    const unsigned long long cap = p->n_rays * env_unsigned("RT_HIP_LATE_CAP", 20, 0, 100) / 100ull; // (per cent of the launch)
-    rays                    = rays > cap ? cap : rays;
-    p->P.late_chunks        = (unsigned) (rays / p->P.chunk);
+    const march_fn kernel = march_kernel(s.lds_tab, s.bounded, s.mode, s.opt);
+    int per_cu            = 0;
+    rc = allow_lds(reinterpret_cast<const void *>(kernel), p->device, s.mlds, p->lds_limit);
+    if (rc == RT_OK) {
+        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, (int) s.bthr, s.mlds);
+        if (e != hipSuccess)
+            rc = fail_hip(e, "hipOccupancyMaxActiveBlocksPerMultiprocessor(march kernel)", __FILE__, __LINE__);
+    }
+    return per_cu;
 }
 
-// One run on a queue: the march (persistent lanes) -> one record per ray -> the frequency pass, as ONE launch
-// (rt_fused.hip) where that applies, as two kernels otherwise (or the path tracer in place of the frequency kernel).
-int plan_launch_run(rt_hip_plan *p, hipStream_t stream)
+// step 3: the buffers the run writes -- march records, path tracer outputs, the spectra set of this run, the links of a
+// one-launch run's tile lists -- kept while they are large enough
+static int ensure_buffers(rt_hip_plan *p, const RunShape &s, hipStream_t stream)
 {
-    // the kernels index rays with 32 bits and round the ray count up to whole chunks of at most 4096 rays
-    if (p->n_rays > (unsigned long long) MAX_LIST_RAYS)
-        return fail_arg("more than 2^32 - 4096 rays in one run");
     const size_t need = rt::rec_bytes(p->n_rays, p->P.rec_stride); // (whole 64-ray tiles: the records are tile-wise)
     if (need > p->rec_bytes || !p->rec) {
         plan_quiesce(p);
@@ -481,117 +433,6 @@ int plan_launch_run(rt_hip_plan *p, hipStream_t stream)
         p->rec_bytes = need;
     }
     p->P.rec = p->rec;
-    // march, LDS variant: the whole march blob in LDS, one work-group of up to 1024 threads per CU;
-    // global variant (persistent 256-thread work-groups) when the blob does not fit (RT_HIP_MARCH=global forces it)
-    const char *force   = getenv("RT_HIP_MARCH");
-    const bool lds_tab  = p->P.blob_bytes + 8 * 1024 <= p->lds_limit && !(force && strcmp(force, "global") == 0);
-    // A run is one march launch -- or three, when the ray list is still on the host
-    // (rt_hip_image_loop): the list crosses PCIe in slices, each with a synchronous copy (the fast
-    // pageable path, ~35 GB/s; asynchronous copies of pageable memory reach a third of that), and
-    // the march of a slice runs on image_loop's non-blocking queue while the host copies the next
-    // one (16 B/ray: 102 MB, ~3 ms for the 6.4 M-ray case; swept: 3 slices 5.8 ms, 1 slice 6.9, 8 slices 7.3).
-    unsigned n_launch = (p->host_rays && p->n_rays >= (2ull << 20)) ? 3u : 1u;
-    if (p->host_rays)
-        n_launch = env_unsigned("RT_HIP_UPLOAD_SLICES", n_launch, 1, 8); // tuning
-    n_launch = n_launch < 1 ? 1 : (n_launch > 8 ? 8 : n_launch);
-    // ---- the whole path in ONE launch (rt_fused.hip) where it applies: emission mode on the beam's own ray grid
-    // with at least 32 rays per pixel (a 64-ray tile then spans at most three pixels: the few-runs deposit, which
-    // needs no row cache), tables in LDS, nothing that wants the march records to itself (probe, path tracer,
-    // the checking repeat, profiling switches), and room in LDS for the frequency pass beside the tables
-    // (The gain-only mode -- a seed, forward method -- on a ray grid can run as one launch as well: its frequency pass needs a
-    // row cache per wave, so only the handful of waves whose buffers fit beside the march tables run it during the march
-    // (the layout below).  Built and measured in round 5, profiles/r05_seed_fused_ab.txt: seed_small.dat 3.28 against
-    // 3.33 ms with four such waves, twice the rays 5.97 against 5.93 ms -- a wash, because what the one launch buys is the
-    // idle end of the march, which is a fifth of a 0.5 ms launch and a hundredth of a 6 ms one, and what it costs is five
-    // of sixteen waves marching less.  Two kernels stay the rule for this mode; RT_HIP_FUSED_SEED=1 takes the one launch.)
-    const bool fused_emis = p->P.use_emis && p->P.method == 1 && p->P.own_cells && p->P.rays.nga * p->P.rays.ngb >= 32;
-    const bool fused_gain = !p->P.use_emis && p->P.rays.list == nullptr && env_unsigned("RT_HIP_FUSED_SEED", 0, 0, 1) == 1;
-    const bool fused_cand = lds_tab && n_launch == 1 && p->n_rays > 0 && !p->path_on && !p->spectra_on && !p->step_on && !p->probe_on && p->P.debug == 0 &&
-                            (fused_emis || fused_gain) && !p->P.exclusive && p->P.safe == 0 &&
-                            p->n_iang * sizeof(double) <= 32 * 1024 && env_unsigned("RT_HIP_FUSED", 1, 1, 2) == 1;
-    // ---- step mode in ONE launch (rt_fused_step.hip), where the caller has asked for it (rt_hip_plan_set_step_one_launch):
-    // the conditions of the emission run above without those that exist for the few-runs image deposit only -- the step
-    // pass writes no image, so neither 32 rays per pixel nor "a tile spans at most three pixels" is asked for.  Ray lists,
-    // seeded plans, seed sets, the exclusive mode (its plain stores into nf must not meet a split tile) and tables that
-    // leave no room keep the two kernels.
-    const bool step_cand = p->step_on && p->step_one_launch && lds_tab && n_launch == 1 && p->n_rays > 0 && p->P.use_emis && p->P.method == 1 &&
-                           p->P.own_cells && !p->probe_on && !p->path_on && !p->spectra_on && p->P.debug == 0 && p->P.safe == 0 &&
-                           !p->P.exclusive && p->n_seed == 0 && p->n_iang * sizeof(double) <= 32 * 1024 &&
-                           env_unsigned("RT_HIP_FUSED", 1, 1, 2) == 1;
-    unsigned bthr = lds_tab ? 1024u : 256u;
-    if (lds_tab && !fused_cand && !step_cand) {
-        // Few rays per lane leave the persistent lanes waiting for the longest ray of a short
-        // queue: below about three rays per lane, fewer and busier lanes win (ASE_small, 399 000
-        // rays on 256 CUs: 0.65 ms with 1024 threads per CU, 0.44 ms with 512; 8 waves per CU is
-        // the least that still hides latency).
-        const unsigned long long per_cu_rays = p->cu_count ? p->n_rays / (unsigned long long) p->cu_count : 0;
-        // (tools/shard_threads.py on pixel-column shards of the stand-in: 3117 rays per CU 0.461 ms with 768 threads,
-        // 0.472 with 1024; 4156 per CU: equal; 1558 per CU: 0.376 ms with 512, 0.432 with 1024)
-        bthr = per_cu_rays >= 4ull * 1024 ? 1024u : (per_cu_rays >= 2560ull ? 768u : 512u);
-    }
-    // (the one-launch run always takes sixteen waves per CU: a quarter of them run the frequency pass from the start and
-    // the end of the ray list is kept for the oldest wave of every SIMD, see below -- with those two the full
-    // work-group wins at every size measured, 399 K rays ... 6.4 M, profiles/r05_fused_end.txt)
-    bthr = env_unsigned("RT_HIP_MARCH_THREADS", bthr, 64, lds_tab ? 1024 : 256) / 64 * 64; // occupancy experiments
-    const size_t mlds   = lds_tab ? (size_t) p->P.blob_bytes : 0;
-    int per_cu          = 0;
-    // the integrator's divisions without range bookkeeping where the tables and the step factor allow it
-    // (rt_math.h, fdiv_nr; RT_HIP_MARCH_IEEE=1 forces the full IEEE sequences)
-    const bool force_ieee = getenv("RT_HIP_MARCH_IEEE") != nullptr;
-    const bool bounded = p->tables_bounded && p->P.c_h3 >= 1e-8f && !force_ieee;
-    using march_fn = void (*)(const rt::DevParams);
-    // (the instance with method and emission switch fixed at compile time for the emission / backward pair, rt_march.hip
-    // MODE: the one-launch run -2.1 % with it; profiles/r05_loop_head.txt)
-    int mode = (p->P.use_emis && p->P.method == 1 && !p->path_on) ? 1 : 0;
-    // (gain-only, forward: only the method at compile time -- MODE 3, -0.7 %; with the emission switch fixed as well, or
-    // alone, the same source compiles to a march that is 5 - 9 % SLOWER: RT_HIP_MARCH_MODE = 2 / 4 / 0 to see it)
-    if (!p->P.use_emis && p->P.method == 2 && !p->path_on)
-        mode = (int) env_unsigned("RT_HIP_MARCH_MODE", 3, 0, 4);
-    // (the two shortcuts of block [C], rt_march.hip OPT: BOUNDED instances whose tables allow the proof of the |n - n0|
-    // test -- every shipped one; other tables keep the old instance, as RT_HIP_MARCH_PRUNE=0 at plan creation does.
-    // The branch round the divisions of h2 and h4 pays where the waves compete for issue slots and costs where a
-    // launch is a few rays per lane -- measured, profiles/step_prune_ab.txt: 24.9 K rays per CU -2.0 %, 3.1 K a wash,
-    // 1.6 K +1 ... 2 %, nothing in between -- so it is taken from 8 K rays per CU and launch; RT_HIP_MARCH_PRUNE=2
-    // takes it at every size, for the tests)
-    const unsigned long long launch_rays = p->n_rays / n_launch;
-    const bool prune_h24 = p->march_prune == 2 || (p->cu_count && launch_rays / (unsigned long long) p->cu_count >= 8192ull);
-    const int opt = (bounded && p->march_prune && p->ntest_proven)
-                        ? (rt::MARCH_OPT_PRUNE | rt::MARCH_OPT_NO_NTEST | (prune_h24 ? rt::MARCH_OPT_PRUNE_H24 : 0)) : 0;
-    p->last_march_inst = (bounded ? 1 : 0) | (opt << 1);
-    const march_fn kernel =
-        lds_tab ? (bounded ? (mode == 1 ? march_bounded<true, 1>(opt) : mode == 2 ? march_bounded<true, 2>(opt) : mode == 3 ? march_bounded<true, 3>(opt) : mode == 4 ? march_bounded<true, 4>(opt) : march_bounded<true, 0>(opt))
-                           : (mode == 1 ? rt::rt_march_kernel<true, false, 1> : rt::rt_march_kernel<true, false, 0>))
-                : (bounded ? march_bounded<false, 0>(opt) : rt::rt_march_kernel<false, false, 0>);
-    if (lds_tab) {
-        const int rc = allow_lds(reinterpret_cast<const void *>(kernel), p->device, mlds, p->lds_limit);
-        if (rc != RT_OK)
-            return rc;
-        per_cu = 1; // one work-group per CU: the tables take more than half of the LDS... or the work-group all wave slots
-        if (2 * mlds + 1024 <= p->lds_limit && bthr <= 512)
-            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, (int) bthr, mlds));
-    } else {
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, (int) bthr, mlds));
-    }
-    if (per_cu < 1)
-        per_cu = 1;
-    unsigned long long want = ((unsigned long long) p->n_rays + bthr - 1) / bthr;
-    unsigned long long cap  = (unsigned long long) p->cu_count * (unsigned) per_cu;
-    const unsigned grid     = (unsigned) (want < cap ? want : cap);
-    // rays reserved per counter fetch: big enough to amortise the atomic, small enough that the last
-    // chunks balance (about 8 chunks per wave), within 64 ... 192 -- swept on the stand-in and on its
-    // strong-scaling shards (tools/shard_sweep2.py): a whole 64-ray refill per fetch is the least that
-    // pays (798 K rays: 0.88 ms at 16, 0.55 at 32, 0.44 at 64, 0.60 at 96), 64 ... 192 is flat at 6.4 M
-    // rays (2.02 ms; 2.66 at 32, 2.05 at 256)
-    unsigned long long ch = grid ? p->n_rays / ((unsigned long long) grid * (bthr / 64) * 8) : 64;
-    ch                    = ch < 64 ? 64 : (ch > 192 ? 192 : ch);
-    p->P.chunk            = (unsigned) ((ch + 15) / 16 * 16);
-    p->P.chunk = env_unsigned("RT_HIP_MARCH_CHUNK", p->P.chunk, 1, 4096); // tuning
-    // lanes that must wait for block [A] of the march before it runs (swept 1 ... 40 on the 6.4 M-ray
-    // stand-in: 2.36 ms at 1, flat optimum 2.12 ms at 8 ... 24, 2.63 ms at 40)
-    p->P.park    = env_unsigned("RT_HIP_MARCH_PARK", 12, 1, 64);
-    p->P.path_on = p->path_on ? 1u : 0u;
-    p->P.spin_limit = env_unsigned("RT_HIP_MARCH_SPIN_LIMIT", 1u << 24, 1024, 0x7fffffffu); // (tests lower it)
-    p->P.no_skip = p->gv_has_nan ? 1u : 0u; // the CPU loop multiplies 0 * gv[row 0] for sub-segments a ray never entered
     if (p->path_on) {
         const size_t n2 = (size_t) p->P.L * RT_N_SUB + 1;
         if (p->path_rays != (size_t) p->n_rays || !p->path_dev) {
@@ -625,141 +466,68 @@ int plan_launch_run(rt_hip_plan *p, hipStream_t stream)
             p->spec_rays[p->spec_sel] = n;
         }
     }
-    HIP_TRY(hipEventRecord(p->ev0, stream));
-    p->last_fused = false;
-    p->P.late_chunks = 0;
-    p->P.late_waves  = 0;
-    p->P.late_first  = 0;
-    if ((fused_cand || step_cand) && grid > 0) {
-        const unsigned nw       = bthr / 64;
-        // doubles per wave: transposition rows + window totals of the few-runs deposit for 2 pixel runs per tile (a pixel
-        // has at least 64 rays) or 3, no row cache
-        const bool emis         = p->P.use_emis != 0;
-        const int maxq          = emis && p->P.rays.nga * p->P.rays.ngb >= 64 ? 2 : 3;
-        // gain-only: rows of the per-wave row cache (a seeded tile holds ~7 pixels; fewer than 4 rows is not worth having)
-        int nslot               = emis ? 0 : (int) env_unsigned("RT_HIP_FUSED_ROWS", 7, 4, 16);
-        size_t per_wave         = (size_t) rt::fused_wave_doubles(maxq) + (size_t) nslot * (size_t) rt::freq_row_stride(p->P.Kp);
-        if (step_cand) // the transposition rows of the wave sum, nothing else (rt_step.hip)
-            per_wave = (size_t) 4 * rt::XP_ROW;
-        rt::FusedLay lay;
-        lay.off_exp  = (unsigned) align_up(p->P.blob_bytes, 16);
-        lay.off_iang = lay.off_exp + 2u * rt::EXP_TAB * (unsigned) sizeof(double);
-        lay.off_ctl  = lay.off_iang + (unsigned) (((p->n_iang + 1) & ~(size_t) 1) * sizeof(double));
-        if (step_cand) // E_v [Kp] of the work-group behind the histogram: beside the tables, never under an overlaid buffer
-            lay.off_ctl = lay.off_iang + rt::fused_step_ev_off((int) p->n_iang) + (unsigned) ((size_t) p->P.Kp * sizeof(double));
-        lay.off_rem  = lay.off_ctl + 16u;
-        lay.off_nodes = lay.off_rem + nw * 32u * (unsigned) sizeof(unsigned);
-        // nodes of the work-group's tile list in LDS: room for twice a work-group's share of the entries (a tile is one
-        // entry, a split tile four; a work-group that marches faster owes more), within 64 ... 1024; the surplus of a
-        // work-group that pushes more takes the global links
-        {
-            const unsigned long long wgs = (p->n_rays + bthr - 1) / bthr < (unsigned long long) p->cu_count ? (p->n_rays + bthr - 1) / bthr
-                                                                                                          : (unsigned long long) p->cu_count;
-            unsigned long long cap = wgs ? 2ull * ((unsigned long long) p->P.n_tiles / wgs + 1) + 32 : 64;
-            cap           = cap < 64 ? 64 : (cap > 1024 ? 1024 : cap);
-            if (!emis) // (LDS is what the row caches are short of; the consumers keep the list short)
-                cap = cap > 256 ? 256 : cap;
-            lay.node_cap  = env_unsigned("RT_HIP_FUSED_NODES", (unsigned) cap, 0, 4096);
-        }
-        lay.off_buf  = (unsigned) align_up(lay.off_nodes + lay.node_cap * 2u * (unsigned) sizeof(unsigned), 16);
-        size_t room = p->lds_limit > lay.off_buf ? (p->lds_limit - lay.off_buf) / (per_wave * sizeof(double)) : 0;
-        if (!emis && room < 5 && nslot > 5) { // one more buffer beside the tables is worth two rows of each cache
-            nslot    = 5;
-            per_wave = (size_t) rt::fused_wave_doubles(maxq) + (size_t) nslot * (size_t) rt::freq_row_stride(p->P.Kp);
-            room     = p->lds_limit > lay.off_buf ? (p->lds_limit - lay.off_buf) / (per_wave * sizeof(double)) : 0;
-        }
-        lay.per_wave = (unsigned) per_wave;
-        lay.n_free   = (unsigned) (room < nw ? room : nw);
-        // emission: at least half the buffers beside the tables (the others overlay them once the march is over);
-        // gain-only: at least three, and they are the consumers'
-        const bool fits = (emis ? 2 * lay.n_free >= nw : (lay.n_free >= 3 && nw >= 8)) &&
-                          (size_t) (nw - lay.n_free) * per_wave * sizeof(double) <= p->P.blob_bytes;
-        if (fits) {
-            const size_t flds     = (size_t) lay.off_buf + (size_t) lay.n_free * per_wave * sizeof(double);
-            const size_t n_tiles  = 4 * (size_t) p->P.n_tiles; // one link per (tile, part)
-            // the last tiles of a work-group in four parts of the frequency range (whole groups of 4 frequencies; not
-            // worth it below 32 frequencies); RT_HIP_FUSED_SPLIT = 2: never, 3: every tile (tests)
-            const unsigned split_env = env_unsigned("RT_HIP_FUSED_SPLIT", 1, 1, 3);
-            lay.split  = split_env == 2 ? 0u : (split_env == 3 ? 2u : 1u);
-            lay.k_part = p->P.K >= 32 && emis ? (unsigned) (((p->P.K + 3) / 4 + 3) / 4 * 4) : 0u;
-            // a quarter of the work-group -- its last, youngest waves, one per SIMD -- never marches (rt_fused.hip);
-            // gain-only: the same, all of them with a buffer beside the tables (four measured better than five or six)
-            lay.n_consumers = env_unsigned("RT_HIP_FUSED_CONSUMERS", emis ? nw / 4 : (lay.n_free < nw / 4 ? lay.n_free : nw / 4), 0, nw > 1 ? nw - 1 : 0);
-            if (lay.n_consumers >= nw)
-                lay.n_consumers = nw - 1;
-            lay.consumers_first = env_unsigned("RT_HIP_FUSED_CONSUMERS_FIRST", 0, 0, 1);
-            if (p->tile_next_n < n_tiles || !p->tile_next) {
-                plan_quiesce(p);
-                pool_free(p->device, p->tile_next);
-                p->tile_next = nullptr;
-                HIP_TRY(pool_alloc(p->device, (void **) &p->tile_next, n_tiles * sizeof(unsigned) + 16));
-                p->tile_next_n = n_tiles;
-            }
-            p->P.ray_begin = 0;
-            p->P.ray_end   = (unsigned) p->n_rays;
-            p->P.launch_id = 0;
-            p->P.chunk     = (p->P.chunk + 32) / 64 * 64; // whole tiles per reservation (64 ... 192 rays)
-            p->P.chunk     = p->P.chunk < 64 ? 64 : p->P.chunk;
-            // (gain-only: the waves that run the frequency pass during the march are the youngest of their SIMD already,
-            // nothing starves the last marchers: no late zone)
-            if (emis)
-                late_zone(p, (unsigned) ((p->n_rays + bthr - 1) / bthr < (unsigned long long) p->cu_count ? (p->n_rays + bthr - 1) / bthr : p->cu_count),
-                          nw - lay.n_consumers, lay.consumers_first ? lay.n_consumers : 0u);
-            p->P.tile_begin = 0;
-            p->P.tile_end   = p->P.n_tiles;
-            p->P.freq_id    = 0;
-            const int S  = p->P.L * RT_N_SUB;
-            unsigned long long fwant = ((unsigned long long) p->n_rays + bthr - 1) / bthr;
-            const unsigned fgrid     = (unsigned) (fwant < (unsigned long long) p->cu_count ? fwant : (unsigned long long) p->cu_count);
-            if (step_cand) {
-                // the step kernel's argument block as launch_step fills it (lent buffers and the run's I_ang through p->step
-                // and freq_args), behind the march's
-                const rt::FreqKArg f = freq_args(p, true, 0, (unsigned long long) grid * nw);
-                rt::FusedStepKArg sa;
-                memset(&sa, 0, sizeof(sa));
-                sa.P           = p->P;
-                sa.S.hot       = f.hot;
-                sa.S.hot.image = nullptr; // never touched: there is no cube
-                sa.S.cold      = f.cold;
-                sa.S.out       = p->step;
-                sa.tile_next   = p->tile_next;
-                sa.lay         = lay;
-                using fstep_fn = void (*)(const rt::FusedStepKArg);
-                const fstep_fn sk = S == 6 ? (bounded ? fused_step_bounded<6>(opt) : rt::rt_fused_step_kernel<false, 6>)
-                                           : (bounded ? fused_step_bounded<0>(opt) : rt::rt_fused_step_kernel<false, 0>);
-                const int rc = allow_lds(reinterpret_cast<const void *>(sk), p->device, flds, p->lds_limit);
-                if (rc != RT_OK)
-                    return rc;
-                hipLaunchKernelGGL(sk, dim3(fgrid), dim3(bthr), flds, stream, sa);
-            } else {
-                rt::FusedKArg fa;
-                fa.P         = p->P;
-                fa.F         = freq_args(p, true, nslot, (unsigned long long) grid * nw);
-                fa.tile_next = p->tile_next;
-                fa.lay       = lay;
-                using fused_fn = void (*)(const rt::FusedKArg);
-                const fused_fn fk =
-                    !emis     ? (S == 6 ? (bounded ? fused_bounded<6, 3, false>(opt) : rt::rt_fused_kernel<false, 6, 3, false>)
-                                        : (bounded ? fused_bounded<0, 3, false>(opt) : rt::rt_fused_kernel<false, 0, 3, false>))
-                    : maxq == 2 ? (S == 6 ? (bounded ? fused_bounded<6, 2, true>(opt) : rt::rt_fused_kernel<false, 6, 2>)
-                                        : (bounded ? fused_bounded<0, 2, true>(opt) : rt::rt_fused_kernel<false, 0, 2>))
-                              : (S == 6 ? (bounded ? fused_bounded<6, 3, true>(opt) : rt::rt_fused_kernel<false, 6, 3>)
-                                        : (bounded ? fused_bounded<0, 3, true>(opt) : rt::rt_fused_kernel<false, 0, 3>));
-                const int rc = allow_lds(reinterpret_cast<const void *>(fk), p->device, flds, p->lds_limit);
-                if (rc != RT_OK)
-                    return rc;
-                hipLaunchKernelGGL(fk, dim3(fgrid), dim3(bthr), flds, stream, fa);
-            }
-            HIP_TRY(hipGetLastError());
-            p->host_rays = nullptr;
-            HIP_TRY(hipEventRecord(p->evm, stream));
-            HIP_TRY(hipEventRecord(p->ev1, stream));
-            p->last_fused = true;
-            return RT_OK;
-        }
+    if (s.kind != RUN_TWO_KERNELS && (p->tile_next_n < s.tile_links || !p->tile_next)) {
+        plan_quiesce(p);
+        pool_free(p->device, p->tile_next);
+        p->tile_next = nullptr;
+        HIP_TRY(pool_alloc(p->device, (void **) &p->tile_next, s.tile_links * sizeof(unsigned) + 16));
+        p->tile_next_n = s.tile_links;
     }
-    for (unsigned c = 0; c < n_launch && grid > 0 && !(p->P.debug & 2u); c++) {
-        const unsigned long long b = p->n_rays * c / n_launch, e = p->n_rays * (c + 1) / n_launch;
+    return RT_OK;
+}
+
+// what the kernels of this run get: the plan's parameter block with the numbers of this run in it (of its one march
+// launch; launch_march adjusts the copy per upload slice)
+static rt::DevParams run_params(const rt_hip_plan *p, const RunShape &s)
+{
+    rt::DevParams P = p->P;
+    P.chunk       = s.chunk;
+    P.park        = s.park;
+    P.path_on     = p->path_on ? 1u : 0u;
+    P.spin_limit  = s.spin_limit;
+    P.no_skip     = s.no_skip;
+    P.late_first  = s.late_first;
+    P.late_waves  = s.late_waves;
+    P.late_chunks = s.late_chunks;
+    P.ray_begin   = 0;
+    P.ray_end     = (unsigned) p->n_rays;
+    P.launch_id   = 0;
+    return P;
+}
+
+// step 5, the whole path in one launch: the march's parameter block, the argument block of the frequency (or step) pass
+// behind it, the links and the layout
+static int launch_one(rt_hip_plan *p, const RunFacts &f, const RunShape &s, const rt::DevParams &P, hipStream_t stream)
+{
+    const rt::FreqKArg fa = freq_args(p, true, s.nslot, s.fetch_shift, PassRun{ 0, f.n_tiles, 0, 0, nullptr });
+    if (s.kind == RUN_STEP_ONE_LAUNCH) {
+        // the step kernel's argument block as launch_pass fills it (lent buffers and the run's I_ang through p->step and freq_args)
+        rt::FusedStepKArg sa;
+        memset(&sa, 0, sizeof(sa));
+        sa.P           = P;
+        sa.S.hot       = fa.hot;
+        sa.S.hot.image = nullptr; // never touched: there is no cube
+        sa.S.cold      = fa.cold;
+        sa.S.out       = p->step;
+        sa.tile_next   = p->tile_next;
+        sa.lay         = s.lay;
+        return launch(p, fused_step_kernel(s.bounded, f.s6(), s.opt), s.fgrid, s.bthr, s.flds, stream, sa);
+    }
+    rt::FusedKArg a;
+    a.P         = P;
+    a.F         = fa;
+    a.tile_next = p->tile_next;
+    a.lay       = s.lay;
+    return launch(p, fused_kernel(s.bounded, f.s6(), s.maxq, s.emis, s.opt), s.fgrid, s.bthr, s.flds, stream, a);
+}
+
+// step 5, the march as a kernel of its own: one launch per upload slice of a ray list that is still on the host, each
+// behind the synchronous copy of its slice
+static int launch_march(rt_hip_plan *p, const RunShape &s, rt::DevParams &P, hipStream_t stream)
+{
+    const march_fn kernel = march_kernel(s.lds_tab, s.bounded, s.mode, s.opt);
+    for (unsigned c = 0; c < s.n_launch && s.grid > 0 && !(P.debug & 2u); c++) {
+        const unsigned long long b = p->n_rays * c / s.n_launch, e = p->n_rays * (c + 1) / s.n_launch;
         if (p->host_rays) {
             HIP_TRY(hipMemcpy(p->rays_dev + b, p->host_rays + b, (size_t) (e - b) * sizeof(rt_ray), hipMemcpyHostToDevice));
             // Helper.h:409-410 for every ray of the slice, at full lane occupancy, before its march
@@ -773,53 +541,173 @@ int plan_launch_run(rt_hip_plan *p, hipStream_t stream)
                 HIP_TRY(hipGetLastError());
             }
         }
-        if (n_launch > 1) { // rays reserved per counter fetch, for this slice
-            unsigned long long cs = (e - b) / ((unsigned long long) grid * (bthr / 64) * 8);
-            cs                    = cs < 64 ? 64 : (cs > 192 ? 192 : cs);
-            p->P.chunk            = (unsigned) ((cs + 15) / 16 * 16);
-        }
-        p->P.ray_begin = (unsigned) b;
-        p->P.ray_end   = (unsigned) e;
-        p->P.launch_id = c;
-        // (the march as a kernel of its own: the end of the list for the oldest wave of every SIMD as well -- its tail is the
-        // drain of the last rays, and one wave per SIMD runs it at the pace of a wave that has the SIMD to itself)
-        if (n_launch == 1 && lds_tab)
-            late_zone(p, grid, bthr / 64, 0u, "RT_HIP_LATE2_X10", 60); // (seed_small -0.8 %, stand-in as two kernels -1.5 %, its 8-rank shard -6 %)
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(bthr), mlds, stream, p->P);
-        HIP_TRY(hipGetLastError());
+        if (s.n_launch > 1) // rays reserved per counter fetch, for this slice
+            P.chunk = march_chunk(e - b, s.grid, s.bthr);
+        P.ray_begin = (unsigned) b;
+        P.ray_end   = (unsigned) e;
+        P.launch_id = c;
+        const int rc = launch(p, kernel, s.grid, s.bthr, s.mlds, stream, P);
+        if (rc != RT_OK)
+            return rc;
     }
-    p->host_rays = nullptr; // consumed: the list is on the device now
-    HIP_TRY(hipEventRecord(p->evm, stream));
-    if (p->path_on) {
-        // the tracer replaces the frequency / deposit kernel: no image is produced
+    return RT_OK;
+}
+
+// step 6: the second pass of a two-kernel run
+static int launch_second(rt_hip_plan *p, const RunFacts &f, const Tuning &t, const rt::DevParams &P, hipStream_t stream)
+{
+    const PassKind kind = pass_kind(f);
+    if (kind == PASS_PATH) { // the tracer replaces the frequency / deposit kernel: no image is produced
         if (p->n_rays) {
-            hipLaunchKernelGGL(rt::rt_path_kernel, dim3((unsigned) ((p->n_rays + 255) / 256)), dim3(256), 0, stream, p->P);
+            hipLaunchKernelGGL(rt::rt_path_kernel, dim3((unsigned) ((p->n_rays + 255) / 256)), dim3(256), 0, stream, P);
             HIP_TRY(hipGetLastError());
         }
-    } else if (p->spectra_on) {
-        // the spectra kernel replaces the frequency / deposit kernel: no image is produced
-        const int rc = launch_spec_any(p, stream);
-        if (rc != RT_OK)
-            return rc;
-    } else if (p->step_on) {
-        // the step kernel replaces the frequency / deposit kernel: E_v, nf and I_ang, no image cube
-        if (!(p->P.debug & 1u)) {
-            const int rc = launch_step_any(p, stream);
-            if (rc != RT_OK)
-                return rc;
-        }
-    } else if (!(p->P.debug & 1u)) {
-        const int rc = launch_freq_any(p, stream);
-        if (rc != RT_OK)
-            return rc;
+        return RT_OK;
     }
+    if (kind != PASS_SPEC && (f.debug & 1u)) // (profiling: the march alone)
+        return RT_OK;
+    return launch_pass(p, f, t, kind, stream);
+}
+
+// One run on a queue: the march (persistent lanes) -> one record per ray -> the frequency pass, as ONE launch
+// (rt_fused.hip) where that applies, as two kernels otherwise (or the path tracer in place of the frequency kernel).
+// What the run looks like is run_shape's decision (rt_run_shape.h); nothing per-launch is written into the plan's
+// parameter block.
+int plan_launch_run(rt_hip_plan *p, hipStream_t stream)
+{
+    // the kernels index rays with 32 bits and round the ray count up to whole chunks of at most 4096 rays
+    if (p->n_rays > (unsigned long long) MAX_LIST_RAYS)
+        return fail_arg("more than 2^32 - 4096 rays in one run");
+    const RunFacts f = run_facts(p);
+    const Tuning t   = read_tuning();
+    int rc           = RT_OK;
+    const RunShape s = run_shape(f, t, [&](const RunShape &m) { return march_occupancy(p, m, rc); });
+    if (rc != RT_OK)
+        return rc;
+    p->last_march_inst = s.last_march_inst;
+    if ((rc = ensure_buffers(p, s, stream)) != RT_OK)
+        return rc;
+    HIP_TRY(hipEventRecord(p->ev0, stream));
+    p->last_fused  = false;
+    rt::DevParams P = run_params(p, s);
+    const bool one = s.kind != RUN_TWO_KERNELS;
+    if ((rc = one ? launch_one(p, f, s, P, stream) : launch_march(p, s, P, stream)) != RT_OK)
+        return rc;
+    p->host_rays = nullptr; // consumed: the list is on the device now
+    HIP_TRY(hipEventRecord(p->evm, stream));
+    if (!one && (rc = launch_second(p, f, t, P, stream)) != RT_OK)
+        return rc;
     HIP_TRY(hipEventRecord(p->ev1, stream));
+    p->last_fused = one;
     return RT_OK;
 }
 
 } // namespace rtr
 
 extern "C" {
+
+// What a run of these facts would look like, by the very functions plan_launch_run calls; no device call.
+int rt_hip_debug_run_shape(const rt_hip_run_facts *facts, rt_hip_run_shape *out)
+{
+    if (!facts || !out || facts->size != sizeof(rt_hip_run_facts) || out->size != sizeof(rt_hip_run_shape))
+        return fail_arg("rt_hip_debug_run_shape: NULL argument or a size field that is not this library's sizeof");
+    if (facts->cu_count < 1 || facts->lds_limit == 0)
+        return fail_arg("rt_hip_debug_run_shape: cu_count < 1 or lds_limit == 0");
+    RunFacts f;
+    f.cu_count        = facts->cu_count;
+    f.lds_limit       = (size_t) facts->lds_limit;
+    f.n_rays          = facts->n_rays;
+    f.n_tiles         = facts->n_tiles;
+    f.blob_bytes      = (size_t) facts->blob_bytes;
+    f.K               = facts->K;
+    f.Kp              = facts->Kp;
+    f.L               = facts->L;
+    f.n_iang          = (size_t) facts->n_iang;
+    f.rays_per_pixel  = facts->rays_per_pixel;
+    f.n_seed          = facts->n_seed;
+    f.c_h3            = facts->c_h3;
+    f.march_prune     = facts->march_prune;
+    f.method          = facts->method;
+    f.safe            = facts->safe;
+    f.debug           = facts->debug;
+    f.use_emis        = facts->use_emis != 0;
+    f.own_cells       = facts->own_cells != 0;
+    f.exclusive       = facts->exclusive != 0;
+    f.path_on         = facts->path_on != 0;
+    f.spectra_on      = facts->spectra_on != 0;
+    f.step_on         = facts->step_on != 0;
+    f.step_one_launch = facts->step_one_launch != 0;
+    f.probe_on        = facts->probe_on != 0;
+    f.has_ray_list    = facts->has_ray_list != 0;
+    f.host_rays       = facts->host_rays != 0;
+    f.tables_bounded  = facts->tables_bounded != 0;
+    f.ntest_proven    = facts->ntest_proven != 0;
+    f.gv_has_nan      = facts->gv_has_nan != 0;
+    const Tuning t    = read_tuning();
+    const RunShape s  = run_shape(f, t, [&](const RunShape &) { return facts->occupancy_per_cu; });
+    const unsigned size = out->size;
+    memset(out, 0, sizeof(*out));
+    out->size            = size;
+    out->kind            = (int) s.kind;
+    out->lds_tab         = s.lds_tab;
+    out->n_launch        = s.n_launch;
+    out->bthr            = s.bthr;
+    out->mode            = s.mode;
+    out->bounded         = s.bounded;
+    out->opt             = s.opt;
+    out->last_march_inst = s.last_march_inst;
+    out->mlds            = s.mlds;
+    out->grid            = s.grid;
+    out->chunk           = s.chunk;
+    out->park            = s.park;
+    out->spin_limit      = s.spin_limit;
+    out->no_skip         = s.no_skip;
+    out->late_first      = s.late_first;
+    out->late_waves      = s.late_waves;
+    out->late_chunks     = s.late_chunks;
+    out->occupancy_asked = s.occupancy_asked;
+    out->key_s6          = f.s6();
+    out->key_emis        = f.use_emis;
+    out->key_excl        = f.use_emis && f.exclusive;
+    if (s.kind != RUN_TWO_KERNELS) { // the one launch; its frequency (or step) phase stands where the second pass stands
+        out->maxq            = s.maxq;
+        out->nslot           = s.nslot;
+        out->off_exp         = s.lay.off_exp;
+        out->off_iang        = s.lay.off_iang;
+        out->off_ctl         = s.lay.off_ctl;
+        out->off_rem         = s.lay.off_rem;
+        out->off_nodes       = s.lay.off_nodes;
+        out->off_buf         = s.lay.off_buf;
+        out->node_cap        = s.lay.node_cap;
+        out->n_free          = s.lay.n_free;
+        out->per_wave        = s.lay.per_wave;
+        out->split           = s.lay.split;
+        out->k_part          = s.lay.k_part;
+        out->n_consumers     = s.lay.n_consumers;
+        out->consumers_first = s.lay.consumers_first;
+        out->flds            = s.flds;
+        out->tile_links      = s.tile_links;
+        out->fgrid           = s.fgrid;
+        out->pass_kind       = s.kind == RUN_STEP_ONE_LAUNCH ? (int) PASS_STEP : (int) PASS_FREQ;
+        out->pass_wg_waves   = (int) (s.bthr / 64);
+        out->pass_in_lds     = 1;
+        out->pass_nslot      = s.nslot;
+        out->pass_lds        = s.flds;
+        out->pass_grid       = s.fgrid;
+        out->pass_fetch_shift = s.fetch_shift;
+        return RT_OK;
+    }
+    const PassKind kind   = pass_kind(f);
+    const PassShape ps    = pass_shape(kind, f, t);
+    out->pass_kind        = (int) kind;
+    out->pass_wg_waves    = ps.wg_waves;
+    out->pass_in_lds      = ps.in_lds;
+    out->pass_nslot       = ps.nslot;
+    out->pass_lds         = ps.lds;
+    out->pass_grid        = ps.grid;
+    out->pass_fetch_shift = ps.fetch_shift;
+    return RT_OK;
+}
 
 #ifdef RT_WAVETIMES
 // diagnostic build only: wave start / dry / end times of the LAST march launch (100 MHz ticks), then reset

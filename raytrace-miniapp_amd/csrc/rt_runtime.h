@@ -6,7 +6,12 @@
 //                   rt_hip_image_loop (the host-pointer entry the C++ adapter calls)
 //   rt_raygrid.hip  a ray list that is really a tensor grid: recognition + bit-wise verification,
 //                   list-mode launch tangents and the probe of the host's libm
-//   rt_launch.hip   the kernels (rt_march.hip, rt_freq.hip, rt_path.hip, rt_spec.hip, rt_step.hip, rt_step_seeds.hip, rt_fused_step.hip) and how a run puts them on a queue
+//   rt_launch.hip   the kernels (rt_march.hip, rt_freq.hip, rt_path.hip, rt_spec.hip, rt_step.hip, rt_step_seeds.hip, rt_fused_step.hip) and how a run puts them on a queue:
+//                   WHAT a run looks like -- tables in LDS or not, one launch or two, instance, grid, chunk, late zone, the
+//                   LDS layout of a one-launch run, the shape of the second pass -- is decided by pure functions of plain
+//                   numbers (rt_run_shape.h, included by rt_launch.hip alone: RunFacts from the plan + Tuning from the
+//                   environment -> run_shape / pass_shape; rt_hip_debug_run_shape hands them to tests without a device);
+//                   plan_launch_run enqueues what they say and writes nothing per-launch into the plan's DevParams
 //   rt_multi.hip    all devices of the node: RCCL loader, communicator, rt_hip_multi_image_loop, rt_hip_multi_step_loop
 //   rt_tables.hip   the gain tables of a resident plan rewritten in place: scan and pack kernels, rt_hip_plan_update_gain
 // Only rt_launch.hip, rt_multi.hip and rt_tables.hip contain device code.
@@ -221,9 +226,13 @@ void host_tangents(const rt_ray *rays, size_t n, float *sxy);
 int tan_mode(int device);
 
 // ---- rt_launch.hip -----------------------------------------------------------------------------------
-// march -> records -> frequency pass (or the path tracer) on `stream`; records ev0 / evm / ev1 of the plan
+// march -> records -> frequency pass (or the path tracer) on `stream`; records ev0 / evm / ev1 of the plan.  Six steps:
+// facts and tuning, run_shape, the buffers (records, path, spectra, tile links), ev0, the first kernel(s) with the slice
+// upload, the second pass.  The kernels get a copy of p->P with the numbers of the launch in it; of p->P itself only rec,
+// path and path_err are set.
 int plan_launch_run(rt_hip_plan *p, hipStream_t stream);
-// a run that reported failing rays: repeat the frequency pass (in step mode: the step kernel) without them
+// a run that reported failing rays: repeat the frequency pass (in step mode: the step kernel) without them (the marks and
+// the pass of the repeat, DevParams::safe, go to the launch as arguments; p->P stays as it is)
 int plan_repeat_checked(rt_hip_plan *p);
 int launch_tan(const rt_ray *rays_dev, unsigned long long n, float *sxy_dev, hipStream_t stream);
 int launch_seed_tab(const rt::DevSeed &sd, const rt::DevRays &R, size_t n_points, double *sf, unsigned char *sin);
