@@ -210,10 +210,10 @@ class Reference:
                                             cabi.c_double_p]
         L.ref_create_image_file.restype = C.c_int
         L.ref_calc_rays_file.argtypes = [C.c_char_p, C.c_size_t, C.c_size_t, cabi.c_double_p,
-                                         cabi.c_double_p, P(C.c_int), cabi.c_double_p]
+                                         cabi.c_double_p, P(C.c_int), cabi.c_double_p, C.c_int]
         L.ref_calc_rays_file.restype = C.c_int
         L.ref_calc_ray_path_file.argtypes = [C.c_char_p, P(C.c_int), P(C.c_int), C.c_double, cabi.c_float_p,
-                                             cabi.c_float_p, cabi.c_float_p]
+                                             cabi.c_float_p, cabi.c_float_p, C.c_int]
         L.ref_calc_ray_path_file.restype = C.c_int
 
     def calc_seed(self, seed, pts):
@@ -321,8 +321,8 @@ class Reference:
         return dict(image=image, I_ang=iang, golden_image=gimg, golden_I_ang=gang,
                     seconds=sec.value, dims=d)
 
-    def calc_ray_path_file(self, path, i0, n, c: float = 0.5):
-        """RayTrace::calc_ray_path on the sub-grid [i0, i0+n) of the file's ray grid.
+    def calc_ray_path_file(self, path, i0, n, c: float = 0.5, method: int = 0):
+        """RayTrace::calc_ray_path on the sub-grid [i0, i0+n) of the file's ray grid; method 0: decided by the file's seed.
         Returns x, y, I as [nb][na][ny][nx][N2] arrays (the reference's layout) and the error count."""
         d = self.file_dims(path)
         N2 = (d["N"] - 1) * cabi.RT_N_SUB + 1
@@ -330,20 +330,21 @@ class Reference:
         xr, yr, ir = (np.zeros(tot, np.float32) for _ in range(3))
         a0 = (C.c_int * 4)(*i0)
         an = (C.c_int * 4)(*n)
-        nerr = self.lib.ref_calc_ray_path_file(str(path).encode(), a0, an, c, cabi._fp(xr), cabi._fp(yr), cabi._fp(ir))
+        nerr = self.lib.ref_calc_ray_path_file(str(path).encode(), a0, an, c, cabi._fp(xr), cabi._fp(yr), cabi._fp(ir), method)
         if nerr < 0:
             raise RuntimeError("ref_calc_ray_path_file failed")
         shp = (n[3], n[2], n[1], n[0], N2)
         return dict(x=xr.reshape(shp), y=yr.reshape(shp), I=ir.reshape(shp), n_errors=nerr)
 
-    def calc_rays_file(self, path, stride: int, n: int):
+    def calc_rays_file(self, path, stride: int, n: int, method: int = 0):
+        """RayTrace::calc_ray on rays 0, stride, 2 stride, ... of the file's ray grid; method 0: decided by the file's seed."""
         d = self.file_dims(path)
         Iv = np.zeros((n, d["nv"]))
         ray2 = np.zeros((n, 4))
         rin = np.zeros((n, 4))
         err = (C.c_int * n)()
         rc = self.lib.ref_calc_rays_file(str(path).encode(), stride, n, cabi._dp(Iv),
-                                         cabi._dp(ray2), err, cabi._dp(rin))
+                                         cabi._dp(ray2), err, cabi._dp(rin), method)
         if rc != 0:
             raise RuntimeError("ref_calc_rays_file failed")
         return dict(Iv=Iv, ray2=ray2, rays=rin, err=np.array(list(err), np.int32))

@@ -211,9 +211,10 @@ int ref_create_image_file(const char *path, const char *method, double *image_ou
 /* RayTrace::calc_ray on the first n rays the reference itself would build for
  * this file (src/RayTraceImage.cpp:300-328), for per-ray checks: Iv_out
  * [n][nv], ray2_out [n][4] (as double), err_out [n]; stride picks every
- * stride-th ray of the list. */
+ * stride-th ray of the list.  method_arg: 1 or 2 is handed to calc_ray as it is, whatever the file's seed says
+ * (the ray grid stays the one the file's seed decides); 0: decided by the file's seed, as create_image does. */
 int ref_calc_rays_file(const char *path, size_t stride, size_t n, double *Iv_out,
-                       double *ray2_out, int *err_out, double *ray_in_out)
+                       double *ray2_out, int *err_out, double *ray_in_out, int method_arg)
 {
     RayTrace::create_image_struct *info = load_file(path);
     if (!info)
@@ -229,6 +230,8 @@ int ref_calc_rays_file(const char *path, size_t stride, size_t n, double *Iv_out
         g[0] = info->seed_beam->x; g[1] = info->seed_beam->y;
         g[2] = info->seed_beam->a; g[3] = info->seed_beam->b;
     }
+    if (method_arg != 0)
+        method = method_arg;
     const long Nt = (long) N2[0] * N2[1] * N2[2] * N2[3];
     for (size_t r = 0; r < n; r++) {
         long ijkm = (long) (r * stride);
@@ -292,9 +295,10 @@ int ref_scale_file(const char *path, double scale, int which, int *dims, double 
 
 /* RayTrace::calc_ray_path (src/RayTraceImage.cpp:440-477) on a sub-grid of the file's own
  * ray grid: n[4] points starting at i0[4] along x, y, a, b.  xr/yr/Ir: the reference's
- * layout, N2 * (i + j*nx + k*nx*ny + m*nx*ny*na) + step.  Returns the error count. */
+ * layout, N2 * (i + j*nx + k*nx*ny + m*nx*ny*na) + step.  method_arg as in ref_calc_rays_file.  Returns the error
+ * count. */
 int ref_calc_ray_path_file(const char *path, const int *i0, const int *n, double c, float *xr, float *yr,
-                           float *Ir)
+                           float *Ir, int method_arg)
 {
     RayTrace::create_image_struct *info = load_file(path);
     if (!info)
@@ -307,6 +311,8 @@ int ref_calc_ray_path_file(const char *path, const int *i0, const int *n, double
         g[0] = info->seed_beam->x; g[1] = info->seed_beam->y;
         g[2] = info->seed_beam->a; g[3] = info->seed_beam->b;
     }
+    if (method_arg != 0)
+        method = method_arg;
     std::vector<float> vx, vy, vi;
     int nerr = RayTrace::calc_ray_path(n[0], n[1], n[2], n[3], g[0] + i0[0], g[1] + i0[1], g[2] + i0[2],
                                        g[3] + i0[3], info->N, eb->dz, info->gain, info->seed, eb->nv, eb->dv,

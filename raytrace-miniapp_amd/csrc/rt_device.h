@@ -263,7 +263,7 @@ struct FreqHot {
     double *iang;
     DevCtl *ctl;
     const double *dv2;      // [Kp] 2 * beam.dv (RayTraceImageCPU.cpp:66), zero padded
-    const double *seed_fk;  // [Kp] seed.f[4], zero padded; NULL without a seed
+    const double *seed_fk;  // [Kp] seed.f[4], zero padded; without a seed some finite row of Kp doubles (the factor is 0 then)
     unsigned char *bad;     // [n_rays] failing-ray marks of the checking repeat, else NULL
     double scale;
     float gs_cap;

@@ -151,7 +151,9 @@ rt::FreqKArg freq_args(const rt_hip_plan *p, bool iang_in_lds, int nslot, unsign
     a.hot.iang       = P.iang;
     a.hot.ctl        = P.ctl;
     a.hot.dv2        = p->dv2_dev;
-    a.hot.seed_fk    = P.has_seed ? P.seed.f[4] : nullptr;
+    // (gain-only without a seed -- tables without E0 -- multiplies this row by f0 = 0, as the CPU starts from Iv = 0 and keeps
+    // 0 * exp(gl): any finite row of Kp doubles serves, a NULL one is read all the same)
+    a.hot.seed_fk    = P.has_seed ? P.seed.f[4] : p->dv2_dev;
     a.hot.bad        = r.bad;
     a.hot.scale      = P.scale;
     a.hot.gs_cap     = P.gs_cap;

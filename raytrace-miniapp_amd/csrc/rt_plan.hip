@@ -343,7 +343,8 @@ int rtr::plan_create_on(rt_hip_plan **out, hipStream_t upload_q, int device, int
     size_t off_sx[5] = { 0 }, off_sf[5] = { 0 };
     if (seed) {
         for (int i = 0; i < 5; i++) {
-            if (seed->dim[i] < 2 || !seed->x[i] || !seed->f[i]) {
+            // (axes 0 .. 3 are interpolated: two points at least; the fifth is a table of nv values, and nv = 1 is a problem like any other)
+            if (seed->dim[i] < (i < 4 ? 2 : 1) || !seed->x[i] || !seed->f[i]) {
                 delete p;
                 return fail_arg("rt_hip_plan_create: incomplete seed table");
             }
@@ -1375,7 +1376,7 @@ int rt_hip_plan_set_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds)
     const int K = p->P.K, Kp = p->P.Kp;
     for (int s = 0; s < n_seed; s++) // (as rt_hip_plan_create validates its seed)
         for (int i = 0; i < 5; i++) {
-            if (seeds[s].dim[i] < 2 || !seeds[s].x[i] || !seeds[s].f[i])
+            if (seeds[s].dim[i] < (i < 4 ? 2 : 1) || !seeds[s].x[i] || !seeds[s].f[i])
                 return fail_arg("rt_hip_plan_set_seeds: incomplete seed table");
             if (i == 4 && seeds[s].dim[4] != K)
                 return fail_arg("rt_hip_plan_set_seeds: seed.dim[4] != beam.nv");

@@ -20,6 +20,8 @@ and ASE_small_ref_slice.npz: image / I_ang of the reference's CPU loop
 (RayTraceImageCPULoop) on the ray list 100000 ... 139999 of ASE_small.
 and seed_profiles_ref.npz (main_seed_profiles): RayTrace::calc_seed and the interpolant it evaluates on the crafted seed
 profiles of tests/seed_profiles.py, and RayTraceImageCPULoop on one 450-ray problem that carries such a profile.
+and ASE_small_fwd_ref.npz / seed_small_bwd_ref.npz (main_method_pairs, --method-pairs): the reference's CPU loop, calc_ray and
+calc_ray_path with the method its callers may choose against the seed (no seed with method 2, a seed with method 1).
 Only data is stored -- no reference source text in any encoding.
 """
 import hashlib
@@ -144,7 +146,43 @@ def main_seed_profiles():
     print(f"seed_profiles_ref.npz: {(OUT / 'seed_profiles_ref.npz').stat().st_size} bytes")
 
 
+PAIR_STRIDE, PAIR_SPECTRA = 97, 200
+
+
+def main_method_pairs():
+    """ASE_small_fwd_ref.npz (no seed, method 2) and seed_small_bwd_ref.npz (seed, method 1): the two (method, seed) pairs
+    that create_image never picks but RayTrace::calc_ray, calc_ray_path and the back-end loops take from their caller.
+    Per file: image / I_ang / failure_code of RayTraceImageCPULoop on every 97th ray of the file's own ray grid, calc_ray's
+    Iv / ray2 / err of the first 200 of those rays, and calc_ray_path's x / y / I / nerr at c = 0.5 on the sub-grid of
+    <name>_ref_path.npz."""
+    sys.path.insert(0, str(ROOT / "tests"))
+    import method_pairs as mp
+    build(ref=True)
+    ref = Reference()
+    largest = max(f.stat().st_size for f in OUT.glob("*") if f.suffix in (".npz", ".xz") and "_fwd_ref" not in f.name and "_bwd_ref" not in f.name)
+    for name, method, out in (("ASE_small", 2, "ASE_small_fwd_ref.npz"), ("seed_small", 1, "seed_small_bwd_ref.npz")):
+        src = REF / f"{name}.dat"
+        assert hashlib.sha256(src.read_bytes()).hexdigest() == SHA256[name], f"{name}: unexpected input file"
+        p = mp.with_method(rt.datfile.load(OUT / f"{name}.dat.xz"), method)
+        ids = mp.strided_ids(p, PAIR_STRIDE)
+        s = ref.cpu_loop(p, p.build_rays(ids))
+        q = ref.calc_rays_file(src, PAIR_STRIDE, PAIR_SPECTRA, method)
+        fx = np.load(OUT / f"{name}_ref_path.npz")
+        t = ref.calc_ray_path_file(src, [int(v) for v in fx["i0"]], [int(v) for v in fx["n"]], 0.5, method)
+        np.savez_compressed(OUT / out, method=method, stride=PAIR_STRIDE, n_rays=len(ids), image=s["image"], I_ang=s["I_ang"],
+                            failure_code=s["failure_code"], Iv=q["Iv"], ray2=q["ray2"], rays=q["rays"], err=q["err"],
+                            i0=fx["i0"], n=fx["n"], x_path=t["x"], y_path=t["y"], I_path=t["I"], nerr_path=t["n_errors"])
+        size = (OUT / out).stat().st_size
+        assert size <= largest, f"{out}: {size} bytes, more than the largest fixture ({largest}): take every 197th ray"
+        print(f"{out}: {len(ids)} rays, failure code {s['failure_code']}, non-zero image elements {int(np.count_nonzero(s['image']))} "
+              f"of {s['image'].size}, I_ang {int(np.count_nonzero(s['I_ang']))} of {s['I_ang'].size}, spectra rows non-zero "
+              f"{int(q['Iv'].any(axis=1).sum())} of {PAIR_SPECTRA}, path errors {t['n_errors']}, {size} bytes")
+
+
 if __name__ == "__main__":
+    if "--method-pairs" in sys.argv:
+        main_method_pairs()
+        sys.exit(0)
     if "--seed-profiles" in sys.argv:
         main_seed_profiles()
         sys.exit(0)
@@ -152,3 +190,4 @@ if __name__ == "__main__":
         main()
     main_scaled_and_sliced()
     main_seed_profiles()
+    main_method_pairs()

@@ -21,6 +21,7 @@ import importlib
 import numpy as np
 import pytest
 
+import method_pairs as mp
 import seed_profiles as sp
 import table_variants as tv
 from element_gate import TIGHT_TIER, counts_from_oracle
@@ -184,21 +185,11 @@ def test_generic_instance_five_lengths(hip, oracle, seed_small):
     gate_pair(hip, oracle, (pa, pb), rays, recs, info, "N = 5, (limiter, narrow'), ray list", ("N5", "list"))
 
 
-class _Backward(problem_mod.Problem):
-    """A seeded problem traced with method 1 (Problem.method follows the seed; the C ABI takes any pair)."""
-
-    @property
-    def method(self):
-        return 1
-
-
 def test_backward_method(hip, oracle, seed_small):
     """Method 1 on a seeded plan: the seed factor is seed_factor at the EXIT ray (Helper.h:523-533), per seed; the deposit
     is at the launch ray.  A ray list (the counts of a whole grid in method 1 assume the beam's own grid)."""
     def backward(p):
-        q = copy.copy(p)
-        q.__class__ = _Backward
-        return q
+        return mp.with_method(p, 1)      # (Problem.method follows the seed; the C ABI takes any pair)
 
     pa, pb = pair_problems(seed_small, "limiter", "narrow", backward, "method1")
     assert pa.method == 1 and pb.method == 1

@@ -6,7 +6,9 @@
    reference's own .dat files (src/CreateImageHelpers.cpp:66-100);
 3. per-ray: RayTrace::calc_ray outputs of 400 strided rays per file, bit for bit;
 4. when the compiled reference travelled with the repo (oracle/_ref/), live
-   bitwise comparison on a slice of rays.
+   bitwise comparison on a slice of rays;
+5. the two (method, seed) pairs create_image never picks -- no seed with method 2, a seed with method 1 -- bit for bit
+   against the reference's CPU loop, calc_ray and calc_ray_path (tests/golden/ASE_small_fwd_ref.npz, seed_small_bwd_ref.npz).
 """
 import importlib
 
@@ -137,6 +139,65 @@ def test_path_tracer_bitwise_vs_reference_calc_ray_path(oracle, name):
             mine = out[key].reshape(*n, N2).transpose(3, 2, 1, 0, 4)
             assert np.array_equal(mine.view(np.uint32), fx[f"{key}_c{c}"].view(np.uint32))
         assert int((out["err"] != 0).sum()) == int(fx[f"nerr_c{c}"])
+
+
+# ---- the two (method, seed) pairs create_image never picks: no seed with method 2, a seed with method 1 (fixtures made by
+# ---- tests/golden/make_golden.py --method-pairs from the reference's CPU loop, calc_ray and calc_ray_path)
+def method_pair(name):
+    import method_pairs as mp
+    base = rt.datfile.load(GOLDEN / f"{name}.dat.xz")
+    p = mp.ase_forward(base) if name == "ASE_small" else mp.seed_backward(base)
+    return p, np.load(GOLDEN / ("ASE_small_fwd_ref.npz" if name == "ASE_small" else "seed_small_bwd_ref.npz")), mp
+
+
+@pytest.mark.parametrize("name,n_rays", [("ASE_small", 4114), ("seed_small", 80444)])
+def test_method_pairs_image_loop_bitwise(oracle, name, n_rays):
+    p, fx, mp = method_pair(name)
+    assert int(fx["method"]) == p.method == (2 if name == "ASE_small" else 1) and int(fx["stride"]) == 97
+    rays = p.build_rays(mp.strided_ids(p, 97))
+    assert len(rays) == n_rays == int(fx["n_rays"])
+    out = oracle.image_loop(p, rays)
+    assert out["failure_code"] == int(fx["failure_code"]) == 0
+    assert np.array_equal(out["image"].view(np.uint64), fx["image"].view(np.uint64))
+    assert np.array_equal(out["I_ang"].view(np.uint64), fx["I_ang"].view(np.uint64))
+    # far from trivial: most of the image, and the other method's image of the same rays is another one
+    assert np.count_nonzero(fx["image"]) > fx["image"].size // 2 and np.count_nonzero(fx["I_ang"]) >= 25
+    base = rt.datfile.load(GOLDEN / f"{name}.dat.xz")
+    assert not np.array_equal(oracle.image_loop(base, rays)["image"], fx["image"])
+
+
+@pytest.mark.parametrize("name", ["ASE_small", "seed_small"])
+def test_method_pairs_calc_ray_bitwise(oracle, name):
+    p, fx, mp = method_pair(name)
+    n = fx["Iv"].shape[0]
+    assert n == 200
+    rays = p.build_rays(mp.strided_ids(p, 97)[:n])
+    for q, key in enumerate("xyab"):
+        assert np.array_equal(rays[key], fx["rays"][:, q].astype(np.float32))
+    pr = oracle.probe(p, rays, want_Iv=True)
+    assert np.array_equal(pr["err"], fx["err"])
+    ok = fx["err"] == 0
+    assert ok.sum() >= 150
+    assert np.array_equal(pr["Iv"][ok].view(np.uint64), fx["Iv"][ok].view(np.uint64))
+    for q, key in enumerate("xyab"):
+        assert np.array_equal(pr["ray2"][key][ok].astype(np.float64).view(np.uint64), fx["ray2"][ok, q].view(np.uint64))
+
+
+@pytest.mark.parametrize("name", ["ASE_small", "seed_small"])
+def test_method_pairs_calc_ray_path_bitwise(oracle, name):
+    p, fx, mp = method_pair(name)
+    ids, _ = mp.path_sub_grid(p, fx)
+    n = fx["n"]
+    out = oracle.calc_ray_path(p, p.build_rays(ids), 0.5)
+    N2 = out["x"].shape[1]
+    for key in "xyI":
+        mine = np.ascontiguousarray(out[key].reshape(*n, N2).transpose(3, 2, 1, 0, 4))
+        assert np.array_equal(mine.view(np.uint32), fx[f"{key}_path"].view(np.uint32)), key
+    assert int((out["err"] != 0).sum()) == int(fx["nerr_path"])
+    assert float(np.abs(fx["I_path"]).max()) > 0
+    # the path of the other method is another one (positions are the same march; the intensities are not)
+    other = np.load(GOLDEN / f"{name}_ref_path.npz")
+    assert not np.array_equal(fx["I_path"], other["I_c0.5"])
 
 
 # ---- the full-size configurations pinned to the reference itself (fixtures made by tests/golden/make_golden.py from

@@ -175,6 +175,49 @@ def test_knobs_are_honoured_and_clamped(hl, monkeypatch):
     has(shape(hl, **A), park=12, bthr=512, chunk=64, lds_tab=1, bounded=1)
 
 
+# ---- the two (method, seed) pairs Problem.method never produces (include/rt_hip.h takes any pair): emission with the
+# ---- forward method, and gain-only with the backward method
+FWD_EMIS = dict(B, method=2, own_cells=0)                  # (rt_hip_plan_set_ray_grid grants own_cells to method 1 only)
+BWD_GAIN = dict(B, use_emis=0, method=1, own_cells=0)      # a seeded plan on the seed beam's grid
+BWD_GAIN_OWN = dict(BWD_GAIN, own_cells=1)                 # ... and on the beam's own grid
+
+
+def test_forward_emission_keeps_two_kernels_and_the_run_time_mode(hl):
+    """The one-launch runs deposit at the launch ray by the few-runs rule: a deposit at the exit ray must not get there."""
+    has(shape(hl, **FWD_EMIS), kind=TWO, mode=0, key_emis=1, pass_kind=0)
+    has(shape(hl, **dict(FWD_EMIS, step_on=1, step_one_launch=1)), kind=TWO, mode=0, key_emis=1, pass_kind=2)
+    # ... whatever own_cells says (the plan never sets it for method 2; the rule must not lean on that)
+    has(shape(hl, **dict(FWD_EMIS, own_cells=1)), kind=TWO, mode=0)
+    has(shape(hl, **dict(FWD_EMIS, own_cells=1, step_on=1, step_one_launch=1)), kind=TWO, mode=0)
+    has(shape(hl, **dict(FWD_EMIS, has_ray_list=1)), kind=TWO, mode=0, key_emis=1)
+    # the pair next to it is untouched
+    has(shape(hl, **B), kind=IMAGE_ONE, mode=1, key_emis=1)
+    has(shape(hl, **dict(B, has_ray_list=1, own_cells=0)), kind=TWO, mode=1)
+
+
+@pytest.mark.parametrize("march_mode", [None, 0, 1, 2, 3, 4])
+@pytest.mark.parametrize("facts", [BWD_GAIN, BWD_GAIN_OWN, dict(BWD_GAIN, has_ray_list=1)])
+def test_backward_gain_only_takes_the_run_time_mode_under_every_march_mode(hl, monkeypatch, march_mode, facts):
+    """RT_HIP_MARCH_MODE picks among the instances compiled for the gain-only FORWARD pair; none of them is backward."""
+    knobs = {} if march_mode is None else {"RT_HIP_MARCH_MODE": march_mode}
+    has(shape(hl, knobs, monkeypatch, **facts), kind=TWO, mode=0, key_emis=0, pass_kind=0)
+    # (the forward pair does follow the knob: the case above is no accident of the harness)
+    has(shape(hl, knobs, monkeypatch, **dict(facts, method=2, own_cells=0)), mode=3 if march_mode is None else march_mode)
+
+
+@pytest.mark.parametrize("facts", [BWD_GAIN, BWD_GAIN_OWN])
+def test_backward_gain_only_on_a_grid_may_take_the_one_launch(hl, monkeypatch, facts):
+    """fused_gain does not ask for the method: RT_HIP_FUSED_SEED=1 takes a backward seeded grid into the one launch, with
+    the run-time mode of the march and the gain-only deposit (row caches, consumer waves with a buffer of their own)."""
+    out = shape(hl, {"RT_HIP_FUSED_SEED": 1}, monkeypatch, **facts)
+    has(out, kind=IMAGE_ONE, mode=0, key_emis=0, key_excl=0, nslot=7, maxq=3, k_part=0, late_chunks=0, pass_kind=0)
+    assert 3 <= out.n_free <= 16 and 1 <= out.n_consumers <= 4
+    has(shape(hl, {"RT_HIP_FUSED_SEED": 1}, monkeypatch, **dict(facts, has_ray_list=1)), kind=TWO, mode=0)
+    has(shape(hl, {"RT_HIP_FUSED_SEED": 1}, monkeypatch, **dict(facts, step_on=1)), kind=TWO, mode=0, pass_kind=2)
+    monkeypatch.delenv("RT_HIP_FUSED_SEED")
+    has(shape(hl, **facts), kind=TWO, mode=0)
+
+
 def test_argument_errors(hl):
     lib = hl.lib
 
