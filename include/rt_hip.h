@@ -268,6 +268,7 @@ typedef struct rt_hip_run_facts {
     int use_emis, own_cells, exclusive, path_on, spectra_on, step_on, step_one_launch, probe_on, has_ray_list, host_rays,
         tables_bounded, ntest_proven, gv_has_nan;
     int occupancy_per_cu;
+    int scan_on; /* a length scan (rt_hip_plan_enable_length_scan): the scan march and pass_kind 5, one record per length 1 .. L */
 } rt_hip_run_facts;
 /* kind: 0 = march and second pass as two kernels, 1 = the image run in one launch, 2 = the step run in one launch.
  * The march (of a one-launch run: its march phase): lds_tab (tables in LDS) ... late_chunks; bounded, mode, opt and
@@ -277,7 +278,7 @@ typedef struct rt_hip_run_facts {
  * per_wave in doubles, split, k_part, n_consumers, consumers_first), its LDS bytes, the links of its tile lists and
  * its grid.  key_s6 / key_emis / key_excl pick the instance of the second pass.
  * pass_*: the second pass this run takes (pass_kind 0 frequency, 1 spectra, 2 step, 3 step of a seed set, 4 path
- * tracer: all zero); for a one-launch run the frequency (step) phase of that launch. */
+ * tracer: all zero, 5 step of a length scan; pass_lds above lds_limit: the run is refused); for a one-launch run the frequency (step) phase of that launch. */
 typedef struct rt_hip_run_shape {
     unsigned size;
     int kind, lds_tab;
@@ -519,6 +520,46 @@ int rt_hip_plan_set_seeds(rt_hip_plan *plan, int n_seed, const rt_seed *seeds);
 int rt_hip_plan_fetch_seed_step(rt_hip_plan *plan, int s, double *E_v, double *nf, double *I_ang,
                                 unsigned int *failure_code);
 int rt_hip_plan_seed_step_ptrs(rt_hip_plan *plan, int s, double **E_v_dev, double **nf_dev, double **iang_dev);
+
+/*
+ * A length scan on a plan: the step record at EVERY plasma length n = 2 .. N from ONE forward march -- the gain-length
+ * curve, which the application asks for with one create_image call per length (info->N = n, the first n tables).  With
+ * the forward method RayTrace_calc_ray walks the lengths in order (Helper.h:430-441): its run with n lengths is the first
+ * n - 1 iterations of its run with N.  Record n is, by definition, what a step run of the PREFIX problem leaves: the same
+ * beam, rays, seed, scale and method with the tables gain[0 .. n); record N is the plain step record.
+ *   The scan instance of the march (rt_march.hip, MARCH_OPT_SCAN) stores, beside the records, the state with which a ray
+ *   crosses every length boundary; rt_step_scan_kernel (raytrace-miniapp_amd/csrc/rt_step_scan.hip, in place of
+ *   rt_step_kernel; reported as freq_ms) places every ray once per length -- a ray that escapes inside length e counts as
+ *   escaped for the lengths j >= e and as not escaped, with its boundary state, for j < e -- and deposits the running
+ *   intensity whenever its walk over the sub-segments reaches a length.
+ * enable_length_scan(on != 0): the plan's method must be 2 (forward), 3 <= N and N - 1 <= RT_N_SCAN_MAX, and it must hold
+ *   no seed set; anything else is RT_ERR_ARG.  on = 0 restores the plan exactly as it was.  The call settles the plan's
+ *   last run first.  With the scan on only step mode runs: rt_hip_plan_run outside step mode, with lent step buffers or
+ *   with a non-NULL image_dev or iang_dev is RT_ERR_ARG, and so are rt_hip_plan_enable_path, rt_hip_plan_enable_spectra
+ *   and rt_hip_plan_set_seeds with a non-empty set.  rt_hip_plan_set_step_one_launch is accepted, the run keeps two
+ *   kernels.  Ray lists and ray grids (first / stride included), seeded and emission plans, exact emission, the probe, the
+ *   timing ring, rt_hip_plan_set_step_factor and rt_hip_plan_update_gain / _dev work as on any step plan; an update keeps
+ *   the scan on.
+ * Outputs: ONE allocation of the plan, N - 1 blocks of the layout and stride of a seed set's (E_v | pad to 256 bytes | nf
+ *   | I_ang, spares included), block n - 2 for n lengths, zeroed by the run's zeroing launch.  length_step_ptrs /
+ *   fetch_length_step: n = 2 .. N as create_image counts lengths; any pointer may be NULL; *failure_code is the code of
+ *   the run with n lengths.  rt_hip_plan_fetch_step, rt_hip_plan_step_ptrs and I_ang of rt_hip_plan_fetch serve record N.
+ * Failures follow the reference run once per length: error -1 is s.z^2 < 0.01 of the state that serves the length and
+ *   sets bit 1 in the codes of the lengths where it holds; error -2 / -3 at a length removes the ray from that length's
+ *   record only.  rt_hip_plan_fetch reports the OR of the codes and the rays that fail at any length, each once (more than
+ *   RT_N_FAILED_MAX: the first of them in list order); the counters are those of one run.
+ * rt_hip_length_scan_loop: the host-pointer form, rt_hip_step_loop's arguments with one record per length: E_v
+ *   [N-1][nv], nf [N-1][nx*ny], I_ang [N-1][na*nb], failure_codes [N-1], row n - 2 for n lengths (any may be NULL).
+ * Not taken with the scan: the backward method (a run of n lengths starts in gain[n - 1]: no prefix), seed sets, the
+ *   one-launch form, the multi-device loops, image, spectra and path runs.
+ */
+#define RT_N_SCAN_MAX 32 /* lengths of one scan: one mark bit per length and ray in the checking repeat */
+int rt_hip_plan_enable_length_scan(rt_hip_plan *plan, int on);
+int rt_hip_plan_fetch_length_step(rt_hip_plan *plan, int n, double *E_v, double *nf, double *I_ang, unsigned int *failure_code);
+int rt_hip_plan_length_step_ptrs(rt_hip_plan *plan, int n, double **E_v_dev, double **nf_dev, double **iang_dev);
+int rt_hip_length_scan_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed, int method,
+                            const rt_ray *rays, size_t n_rays, double scale, double *E_v, double *nf, double *I_ang,
+                            unsigned int *failure_codes, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats);
 
 /* Profiling aid (no reference counterpart): bit 0 = skip the frequency / deposit kernel, bit 1 = skip
  * the march and run the frequency pass over the records of the previous run of this plan, bit 2 = the

@@ -10,6 +10,7 @@ mirror of the reference's operator interface for this path.
   step_loop(...)        the same loop with the application's per-step record in place of the image cube: E_v, nf, I_ang
   multi_step_loop(...)  step_loop on all devices of the node: strided ray grid per device, one sum-reduce of the record
   seed_step_loop(...)   the step records of up to RT_N_SEED_MAX seed beams from one march (Plan.set_seeds)
+  length_scan_loop(...) the step record at every plasma length n = 2 .. N from one forward march (Plan.enable_length_scan)
   step_outputs_from_image  their definition as reductions of a cube, in numpy (no device)
   calc_rays / calc_ray  RayTrace::calc_ray (src/RayTraceImage.cpp:189-204), batched: per-ray spectrum, exit ray, code
   create_image(p, method)
@@ -340,6 +341,70 @@ class Plan:
             out.append(dict(E_v=view(e, (b.nv,)), nf=view(n, (b.ny, b.nx)), I_ang=view(a, (b.nb, b.na))))
         return out
 
+    # -- length scan --------------------------------------------------------
+    def enable_length_scan(self, on: bool = True) -> "Plan":
+        """The length scan (include/rt_hip.h, rt_hip_plan_enable_length_scan): a step run then leaves the step record at
+        every plasma length n = 2 .. N -- record n is what a step run of problem.prefix_lengths(p, n) leaves -- from ONE
+        march.  Forward method only, 3 <= N <= RT_N_SCAN_MAX + 1.  Anything else, or an `on` that is not a bool or 0 / 1, is
+        a ValueError raised here, before any native call."""
+        if isinstance(on, bool):
+            on = int(on)
+        if not isinstance(on, (int, np.integer)) or on not in (0, 1):
+            raise ValueError(f"enable_length_scan: on is True / False (or 1 / 0), not {on!r}")
+        if on:
+            p = self.problem
+            if p.method != 2:
+                raise ValueError(f"enable_length_scan: the problem's method is {p.method}; only the forward method (2) has the "
+                                 "marches of fewer lengths as prefixes of its own")
+            if p.N < 3:
+                raise ValueError(f"enable_length_scan: N = {p.N}; a scan needs at least two lengths (N >= 3)")
+            if p.N - 1 > cabi.RT_N_SCAN_MAX:
+                raise ValueError(f"enable_length_scan: N - 1 = {p.N - 1} lengths, at most RT_N_SCAN_MAX = {cabi.RT_N_SCAN_MAX} fit into a scan")
+        self.hl.check(self.hl.lib.rt_hip_plan_enable_length_scan(self._h, int(on)), "rt_hip_plan_enable_length_scan")
+        self._scan = bool(on)
+        return self
+
+    def fetch_length_steps(self) -> list:
+        """[dict(n, E_v [nv], nf [nx * ny], I_ang [na * nb], failure_code)] for n = 2 .. N lengths of the last step run with
+        the scan on (waits for it; a failing run is repeated in the checking mode first)."""
+        b = self.problem.beam
+        out = []
+        for n in range(2, self.problem.N + 1 if getattr(self, "_scan", False) else 2):
+            E_v, nf, iang = np.empty(b.nv), np.empty(b.nx * b.ny), np.empty(b.na * b.nb)
+            code = C.c_uint(0)
+            self.hl.check(self.hl.lib.rt_hip_plan_fetch_length_step(self._h, n, cabi._dp(E_v), cabi._dp(nf), cabi._dp(iang), C.byref(code)),
+                          "rt_hip_plan_fetch_length_step")
+            out.append(dict(n=n, E_v=E_v, nf=nf, I_ang=iang, failure_code=code.value))
+        return out
+
+    def length_step_ptrs(self, n: int) -> tuple:
+        """Device pointers (E_v, nf, I_ang) of the record of n lengths of the last step run with the scan on."""
+        e, f, a = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self.hl.check(self.hl.lib.rt_hip_plan_length_step_ptrs(self._h, int(n), C.byref(e), C.byref(f), C.byref(a)),
+                      "rt_hip_plan_length_step_ptrs")
+        return int(e.value or 0), int(f.value or 0), int(a.value or 0)
+
+    def length_step_tensors(self) -> list:
+        """Per n = 2 .. N: dict(n, E_v [nv], nf [ny][nx], I_ang [nb][na]) of torch views (float64, on the plan's device, no
+        copy) of the last step run with the scan on -- blocks of one allocation, valid until the plan's next run; read them
+        on the run's stream or after a fetch."""
+        import torch
+
+        class _View:  # the CUDA array interface, which torch.as_tensor reads
+            pass
+
+        def view(ptr, shape):
+            v = _View()
+            v.__cuda_array_interface__ = dict(shape=shape, typestr="<f8", data=(ptr, False), version=2, strides=None)
+            return torch.as_tensor(v, device=torch.device("cuda", self.device))
+
+        b = self.problem.beam
+        out = []
+        for n in range(2, self.problem.N + 1 if getattr(self, "_scan", False) else 2):
+            e, f, a = self.length_step_ptrs(n)
+            out.append(dict(n=n, E_v=view(e, (b.nv,)), nf=view(f, (b.ny, b.nx)), I_ang=view(a, (b.nb, b.na))))
+        return out
+
     # -- tables -------------------------------------------------------------
     def update_gain(self, gain, stream: int | None = None) -> "Plan":
         """New n, g0, E0 and gv on the plan's grids (include/rt_hip.h, rt_hip_plan_update_gain): everything else about the
@@ -553,6 +618,39 @@ def seed_step_loop(problem: Problem, seeds, rays: np.ndarray | None = None, devi
         records = plan.fetch_seed_steps()
         info = plan.fetch()
     return dict(records=records, failure_code=info["failure_code"], failed_rays=info["failed_rays"], stats=info["stats"])
+
+
+def length_scan_loop(problem: Problem, rays: np.ndarray | None = None, device: int = 0) -> dict:
+    """The step record at every plasma length n = 2 .. N from ONE forward march of the problem's rays
+    (rt_hip_length_scan_loop; rays None: the problem's ray grid as a list, which the library recognises).  Returns
+    dict(records = [dict(n, E_v, nf, I_ang, failure_code)], failure_code = the OR of the codes, failed_rays = the rays
+    that fail at any length, stats).  A problem the scan does not take (backward method, N < 3, more than RT_N_SCAN_MAX
+    lengths) is a ValueError raised here, before any native call."""
+    if problem.method != 2:
+        raise ValueError(f"length_scan_loop: the problem's method is {problem.method}; the scan takes the forward method (2) only")
+    if problem.N < 3 or problem.N - 1 > cabi.RT_N_SCAN_MAX:
+        raise ValueError(f"length_scan_loop: N = {problem.N}; a scan takes 3 <= N <= RT_N_SCAN_MAX + 1 = {cabi.RT_N_SCAN_MAX + 1}")
+    hl = HipLibrary.get()
+    m = cabi.Marshalled(problem)
+    if rays is None:
+        rays = problem.build_rays()
+    rays = np.ascontiguousarray(rays, dtype=cabi.RAY_DTYPE)
+    b, L = problem.beam, problem.N - 1
+    E_v, nf, iang = np.zeros((L, b.nv)), np.zeros((L, b.nx * b.ny)), np.zeros((L, b.na * b.nb))
+    codes = (C.c_uint * L)()
+    nfail = C.c_int(0)
+    failed = np.zeros(cabi.RT_N_FAILED_MAX, dtype=cabi.RAY_DTYPE)
+    st = cabi.RtStats()
+    rc = hl.lib.rt_hip_length_scan_loop(device, m.N, C.byref(m.beam), m.gain, m.seed_ref, problem.method,
+                                        cabi.rays_ptr(rays), len(rays), problem.scale, cabi._dp(E_v), cabi._dp(nf),
+                                        cabi._dp(iang), codes, cabi.rays_ptr(failed), cabi.RT_N_FAILED_MAX, C.byref(nfail), C.byref(st))
+    hl.check(rc, "rt_hip_length_scan_loop")
+    records = [dict(n=i + 2, E_v=E_v[i].copy(), nf=nf[i].copy(), I_ang=iang[i].copy(), failure_code=int(codes[i])) for i in range(L)]
+    code = 0
+    for r in records:
+        code |= r["failure_code"]
+    return dict(records=records, failure_code=code, failed_rays=failed[:nfail.value].copy(),
+                stats={k: getattr(st, k) for k, _ in cabi.RtStats._fields_})
 
 
 def step_outputs_from_image(problem: Problem, image) -> dict:

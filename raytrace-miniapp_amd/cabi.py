@@ -14,6 +14,7 @@ import numpy as np
 RT_N_SUB = 3
 RT_N_FAILED_MAX = 32
 RT_N_SEED_MAX = 2
+RT_N_SCAN_MAX = 32
 
 RT_OK, RT_ERR_ARG, RT_ERR_NO_DEVICE, RT_ERR_HIP, RT_ERR_NOMEM = range(5)
 
@@ -81,7 +82,7 @@ class RtRunFacts(C.Structure):
         "uint: size; int: cu_count; ull: lds_limit n_rays blob_bytes n_iang; uint: n_tiles;"
         "int: K Kp L rays_per_pixel n_seed march_prune method; float: c_h3; uint: safe debug;"
         "int: use_emis own_cells exclusive path_on spectra_on step_on step_one_launch probe_on has_ray_list host_rays"
-        " tables_bounded ntest_proven gv_has_nan; int: occupancy_per_cu")
+        " tables_bounded ntest_proven gv_has_nan; int: occupancy_per_cu scan_on")
 
 
 class RtRunShape(C.Structure):
@@ -369,6 +370,15 @@ def declare_hip_api(lib: C.CDLL) -> None:
     if hasattr(lib, "rt_hip_debug_run_shape"):   # (likewise)
         lib.rt_hip_debug_run_shape.argtypes = [P(RtRunFacts), P(RtRunShape)]
         lib.rt_hip_debug_run_shape.restype = C.c_int
+    if hasattr(lib, "rt_hip_plan_enable_length_scan"):   # (likewise)
+        lib.rt_hip_plan_enable_length_scan.argtypes = [vp, C.c_int]
+        lib.rt_hip_plan_enable_length_scan.restype = C.c_int
+        lib.rt_hip_plan_fetch_length_step.argtypes = [vp, C.c_int, c_double_p, c_double_p, c_double_p, P(C.c_uint)]
+        lib.rt_hip_plan_fetch_length_step.restype = C.c_int
+        lib.rt_hip_plan_length_step_ptrs.argtypes = [vp, C.c_int, P(vp), P(vp), P(vp)]
+        lib.rt_hip_plan_length_step_ptrs.restype = C.c_int
+        lib.rt_hip_length_scan_loop.argtypes = list(lib.rt_hip_step_loop.argtypes)   # (one row per length where step_loop has one array)
+        lib.rt_hip_length_scan_loop.restype = C.c_int
     lib.rt_hip_plan_set_debug.argtypes = [vp, C.c_uint]
     lib.rt_hip_plan_set_debug.restype = C.c_int
     lib.rt_hip_plan_destroy.argtypes = [vp]
@@ -387,6 +397,7 @@ HIP_API_SYMBOLS = [
     "rt_hip_plan_set_step_buffers", "rt_hip_multi_step_loop",
     "rt_hip_plan_update_gain", "rt_hip_plan_update_gain_dev", "rt_hip_plan_table_flags",
     "rt_hip_plan_set_seeds", "rt_hip_plan_fetch_seed_step", "rt_hip_plan_seed_step_ptrs",
+    "rt_hip_plan_enable_length_scan", "rt_hip_plan_fetch_length_step", "rt_hip_plan_length_step_ptrs", "rt_hip_length_scan_loop",
     "rt_hip_plan_set_step_one_launch", "rt_hip_debug_run_shape",
     "rt_hip_plan_set_debug", "rt_hip_plan_destroy",
 ]

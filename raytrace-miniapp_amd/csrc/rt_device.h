@@ -144,6 +144,9 @@ struct DevCtl {
     rt_ray failed[RT_N_FAILED_MAX];
     // rt_step_seeds_kernel: the failure code of every seed of the plan's seed set (failure_code above is their OR)
     unsigned int seed_code[RT_N_SEED_MAX];
+    // rt_step_scan_kernel: the failure code of every length of a length scan, [n - 2] for n = 2 .. N lengths (failure_code
+    // above is their OR)
+    unsigned int len_code[RT_N_SCAN_MAX];
 };
 
 // probe outputs of the frequency kernel (gvl / evl / ivl are read back from the records)
@@ -218,7 +221,9 @@ struct DevParams {
     // (RayTraceImageCPU.cpp:29-36); after the repeat so does this image.  0 = the normal pass.
     unsigned int safe;
     unsigned int park; // march: lanes that must wait for block [A] before it runs (rt_march.hip); 1 = every iteration
-    unsigned int pad_march[4]; // (unused; kept because the register allocation of the kernels depends on the layout of this block)
+    // [0], [1]: low and high word of the boundary buffer's address, read by the scan instance of the march alone
+    // (MARCH_OPT_SCAN, rt_march.hip); [2], [3] unused.  (The block keeps its layout: the register allocation of the kernels depends on it.)
+    unsigned int pad_march[4];
     // the last late_chunks chunks of a march launch are handed out to the first late_waves waves of each work-group only
     // (rt_march.hip, "The end of a launch"); 0: no such zone
     unsigned int late_chunks, late_waves, late_first; // late_first: the first of those waves (the first MARCHING wave of a work-group)

@@ -15,6 +15,7 @@
 #include "rt_step.hip" // step mode: E_v, nf and I_ang, the image cube reduced on the way
 #include "rt_step_seeds.hip" // step mode with a seed set: one record per seed from one march
 #include "rt_fused_step.hip" // step mode as two phases of one launch (opt-in)
+#include "rt_step_scan.hip" // step mode with a length scan: one record per plasma length from one forward march
 
 #include "rt_runtime.h"
 #include "rt_run_shape.h" // what a run looks like: the pure decision (facts + tuning -> shape) this file enqueues
@@ -61,7 +62,8 @@ int launch(const rt_hip_plan *p, void (*kernel)(const Arg), unsigned grid, unsig
 
 // ---- from a small key to the kernel instance, one function per family ----------------------------------------------
 // (the set of instances is what these functions name and nothing else: unbounded tables have no OPT and, of the MODEs,
-// only 0 and 1; the global-table march has MODE 0 only; the gain-only one-launch kernel MAXQ = 3 only)
+// only 0 and 1; the global-table march has MODE 0 only; the gain-only one-launch kernel MAXQ = 3 only; the scan instance
+// of the march, MODE 3 with MARCH_OPT_SCAN alone, exists for all four combinations of LDS_TAB and BOUNDED)
 using march_fn      = void (*)(const rt::DevParams);
 using fused_fn      = void (*)(const rt::FusedKArg);
 using fused_step_fn = void (*)(const rt::FusedStepKArg);
@@ -74,6 +76,9 @@ template <bool LDS_TAB, int MODE> march_fn march_bounded(int opt)
 }
 march_fn march_kernel(bool lds_tab, bool bounded, int mode, int opt)
 {
+    if (opt & rt::MARCH_OPT_SCAN) // the length scan: forward method at compile time (MODE 3), boundary stores, no pruning
+        return lds_tab ? (bounded ? rt::rt_march_kernel<true, true, 3, rt::MARCH_OPT_SCAN> : rt::rt_march_kernel<true, false, 3, rt::MARCH_OPT_SCAN>)
+                       : (bounded ? rt::rt_march_kernel<false, true, 3, rt::MARCH_OPT_SCAN> : rt::rt_march_kernel<false, false, 3, rt::MARCH_OPT_SCAN>);
     if (!lds_tab)
         return bounded ? march_bounded<false, 0>(opt) : rt::rt_march_kernel<false, false, 0>;
     if (!bounded)
@@ -127,6 +132,7 @@ void (*step_kernel(bool s6, bool emis))(const rt::StepKArg)
     return emis ? (s6 ? rt::rt_step_kernel<6, true> : rt::rt_step_kernel<0, true>) : (s6 ? rt::rt_step_kernel<6, false> : rt::rt_step_kernel<0, false>);
 }
 void (*seeds_kernel(bool s6))(const rt::SeedsKArg) { return s6 ? rt::rt_step_seeds_kernel<6> : rt::rt_step_seeds_kernel<0>; }
+void (*scan_kernel(bool emis))(const rt::ScanKArg) { return emis ? rt::rt_step_scan_kernel<true> : rt::rt_step_scan_kernel<false>; }
 
 // what a launch of the frequency pass covers: tiles [tile_begin, tile_end) on tile counter freq_id (a run is one launch
 // over all tiles; the range exists for experiments that split it), and the marks of the checking repeat (DevParams::safe)
@@ -217,6 +223,7 @@ RunFacts run_facts(const rt_hip_plan *p)
     f.tables_bounded  = p->tables_bounded;
     f.ntest_proven    = p->ntest_proven;
     f.gv_has_nan      = p->gv_has_nan;
+    f.scan_on         = p->scan_on && p->step_on;
     return f;
 }
 
@@ -231,6 +238,8 @@ int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kin
         return fail_arg("step kernel: the E_v accumulator (nv doubles) does not fit into the LDS of this device");
     if (kind == PASS_SEEDS && s.lds > f.lds_limit)
         return fail_arg("step kernel of a seed set: the E_v accumulators (nv doubles per seed) do not fit into the LDS of this device");
+    if (kind == PASS_SCAN && s.lds > f.lds_limit)
+        return fail_arg("step kernel of a length scan: the E_v accumulators (nv doubles per length) do not fit into the LDS of this device");
     if (s.grid == 0)
         return RT_OK;
     if (s.lds > f.lds_limit) {
@@ -261,6 +270,22 @@ int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kin
         a.cold      = fa.cold;
         a.out       = p->step;
         return launch(p, step_kernel(f.s6(), f.use_emis), s.grid, block, s.lds, stream, a);
+    }
+    if (kind == PASS_SCAN) { // a length scan: one record per length, the blocks of the seed-set allocation
+        if (!p->scan_bnd || !p->seeds_dev)
+            return fail_arg("step kernel of a length scan: the boundary states or the records of this run were not allocated");
+        rt::ScanKArg a;
+        memset(&a, 0, sizeof(a));
+        a.hot          = fa.hot;
+        a.hot.image    = nullptr; // never touched: there is no cube
+        a.hot.iang     = nullptr; // (every record's I_ang lies in its block)
+        a.cold         = fa.cold;
+        a.scan.bnd     = p->scan_bnd;
+        a.scan.out     = p->seeds_dev;
+        a.scan.stride  = p->seeds_stride;
+        a.scan.nf_off  = p->seeds_nf_off;
+        a.scan.ang_off = p->seeds_ang_off;
+        return launch(p, scan_kernel(f.use_emis), s.grid, block, s.lds, stream, a);
     }
     // a seed set (a seeded plan: gain-only): one record per seed
     rt::SeedsKArg a;
@@ -370,27 +395,33 @@ int launch_selftest(unsigned long long *counts_dev)
 int plan_repeat_checked(rt_hip_plan *p)
 {
     hipStream_t stream = p->last_stream;
-    if (p->bad_rays < (size_t) p->n_rays || !p->bad_dev) {
+    // (a length scan marks one bit per length in a 32-bit word per ray, every other run one byte per ray)
+    const bool scan       = p->last_step && p->last_scan_L > 0;
+    const size_t bad_word = scan ? sizeof(unsigned) : 1;
+    if (p->bad_rays < (size_t) p->n_rays * bad_word || !p->bad_dev) {
         (void) hipFree(p->bad_dev);
         p->bad_dev = nullptr;
-        HIP_TRY(dev_malloc((void **) &p->bad_dev, (size_t) p->n_rays + 16));
-        p->bad_rays = (size_t) p->n_rays;
+        HIP_TRY(dev_malloc((void **) &p->bad_dev, (size_t) p->n_rays * bad_word + 16));
+        p->bad_rays = (size_t) p->n_rays * bad_word;
     }
-    HIP_TRY(hipMemsetAsync(p->bad_dev, 0, (size_t) p->n_rays, stream));
+    p->bad_word = bad_word;
+    HIP_TRY(hipMemsetAsync(p->bad_dev, 0, (size_t) p->n_rays * bad_word, stream));
     HIP_TRY(hipMemsetAsync(&p->ctl->failure_code, 0, sizeof(unsigned), stream));
     HIP_TRY(hipMemsetAsync(&p->ctl->n_failed, 0, sizeof(unsigned), stream));
     HIP_TRY(hipMemsetAsync(p->ctl->seed_code, 0, sizeof(p->ctl->seed_code), stream));
+    HIP_TRY(hipMemsetAsync(p->ctl->len_code, 0, sizeof(p->ctl->len_code), stream));
     HIP_TRY(hipMemsetAsync(p->ctl->next_tile_f, 0, sizeof(p->ctl->next_tile_f), stream));
     const bool step = p->last_step; // a step run: the step kernel honours the same marks, E_v and nf start over
-    const RunFacts f    = run_facts(p);
+    RunFacts f          = run_facts(p);
+    f.scan_on           = scan; // (the run that is repeated decides, not what the plan has been switched to since)
     const Tuning t      = read_tuning();
-    const PassKind kind = step ? (f.n_seed > 0 ? PASS_SEEDS : PASS_STEP) : PASS_FREQ;
+    const PassKind kind = step ? (scan ? PASS_SCAN : f.n_seed > 0 ? PASS_SEEDS : PASS_STEP) : PASS_FREQ;
     int rc              = launch_pass(p, f, t, kind, stream, 1, p->bad_dev);
     if (rc == RT_OK) {
         if (step && p->last_step_lent) { // (the caller's buffers: exactly the K and nx * ny doubles that are the run's)
             HIP_TRY(hipMemsetAsync(p->step.E_v, 0, (size_t) p->P.K * sizeof(double), stream));
             HIP_TRY(hipMemsetAsync(p->step.nf, 0, (size_t) p->P.beam.nx * (size_t) p->P.beam.ny * sizeof(double), stream));
-        } else if (step && p->last_n_seed > 0) // (a seed set: every record, its I_ang included, is in the one allocation)
+        } else if (step && (p->last_n_seed > 0 || scan)) // (a seed set, a length scan: every record, its I_ang included, is in the one allocation)
             HIP_TRY(hipMemsetAsync(p->seeds_dev, 0, p->seeds_doubles * sizeof(double), stream));
         else if (step)
             HIP_TRY(hipMemsetAsync(p->step_dev, 0, p->step_doubles * sizeof(double), stream));
@@ -435,6 +466,17 @@ static int ensure_buffers(rt_hip_plan *p, const RunShape &s, hipStream_t stream)
         p->rec_bytes = need;
     }
     p->P.rec = p->rec;
+    if (p->scan_on && p->step_on) { // a length scan: the boundary states of the march, from the plan's pool while the scan is on
+        const size_t bnd = rt::scan_bnd_bytes(p->n_rays, p->P.L);
+        if (bnd > p->scan_bnd_bytes || !p->scan_bnd) {
+            plan_quiesce(p);
+            pool_free(p->device, p->scan_bnd);
+            p->scan_bnd       = nullptr;
+            p->scan_bnd_bytes = 0;
+            HIP_TRY(pool_alloc(p->device, (void **) &p->scan_bnd, bnd ? bnd : 16));
+            p->scan_bnd_bytes = bnd;
+        }
+    }
     if (p->path_on) {
         const size_t n2 = (size_t) p->P.L * RT_N_SUB + 1;
         if (p->path_rays != (size_t) p->n_rays || !p->path_dev) {
@@ -494,6 +536,11 @@ static rt::DevParams run_params(const rt_hip_plan *p, const RunShape &s)
     P.ray_begin   = 0;
     P.ray_end     = (unsigned) p->n_rays;
     P.launch_id   = 0;
+    if (s.opt & rt::MARCH_OPT_SCAN) { // the scan instance of the march reads the boundary buffer's address here
+        const unsigned long long b = (unsigned long long) (uintptr_t) p->scan_bnd;
+        P.pad_march[0]             = (unsigned) (b & 0xffffffffull);
+        P.pad_march[1]             = (unsigned) (b >> 32);
+    }
     return P;
 }
 
@@ -645,6 +692,7 @@ int rt_hip_debug_run_shape(const rt_hip_run_facts *facts, rt_hip_run_shape *out)
     f.tables_bounded  = facts->tables_bounded != 0;
     f.ntest_proven    = facts->ntest_proven != 0;
     f.gv_has_nan      = facts->gv_has_nan != 0;
+    f.scan_on         = facts->scan_on != 0;
     const Tuning t    = read_tuning();
     const RunShape s  = run_shape(f, t, [&](const RunShape &) { return facts->occupancy_per_cu; });
     const unsigned size = out->size;

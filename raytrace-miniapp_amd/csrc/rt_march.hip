@@ -775,7 +775,24 @@ template <bool LDS_TAB> __device__ __forceinline__ void march_load_tables(const 
 // bit 2 (MARCH_OPT_PRUNE_H24, large launches) -- likewise those of h2 and h4, behind one branch; bit 1
 // (MARCH_OPT_NO_NTEST) -- rt_hip_plan_create has proved that |n - n0| < 0.05 (Helper.h:280) holds in every step these
 // tables allow, and the loop condition of [C] goes without it.  The march records are the same floats in every instance.
-enum : int { MARCH_OPT_PRUNE = 1, MARCH_OPT_NO_NTEST = 2, MARCH_OPT_PRUNE_H24 = 4 };
+// Bit 3 (MARCH_OPT_SCAN, the length scan of rt_step_scan.hip; forward method only, rt_launch.hip pairs it with MODE 3 and
+// takes it with bounded and unbounded tables alike): where a ray crosses a length boundary, block [A1], the instance also
+// stores the state it crosses with -- {px, py, sx, sy, sz}, what RecMeta keeps of the exit state -- into the boundary
+// buffer (scan_bnd_off below; its address travels in DevParams::pad_march[0 .. 1], which no other instance reads).
+enum : int { MARCH_OPT_PRUNE = 1, MARCH_OPT_NO_NTEST = 2, MARCH_OPT_PRUNE_H24 = 4, MARCH_OPT_SCAN = 8 };
+// The boundary states of a length scan, tile-wise like the records (rt_device.h): the 64 rays of tile t share a block of
+// (L - 1) rows at t * (L - 1) * SCAN_BND_ROW, boundary j = 1 .. L - 1 (the state with which the ray left length j) of ray
+// 64 t + l at (j - 1) * SCAN_BND_ROW + l * SCAN_BND_BYTES: the scan pass reads boundary j of its 64 lanes as one
+// contiguous run.  A ray that escapes inside segment e has written boundaries 1 .. e - 1 and no other.
+constexpr unsigned SCAN_BND_BYTES = 20u, SCAN_BND_ROW = WAVE * SCAN_BND_BYTES;
+RT_HD inline size_t scan_bnd_off(unsigned ridx, int j, int L)
+{
+    return ((size_t) (ridx >> 6) * (size_t) (L - 1) + (size_t) (j - 1)) * SCAN_BND_ROW + (size_t) (ridx & 63u) * SCAN_BND_BYTES;
+}
+RT_HD inline size_t scan_bnd_bytes(unsigned long long n_rays, int L)
+{
+    return (size_t) ((n_rays + WAVE - 1) / WAVE) * (size_t) (L > 1 ? L - 1 : 0) * SCAN_BND_ROW;
+}
 template <bool LDS_TAB, bool BOUNDED, bool FUSED, int MODE = 0, int OPT = 0>
 __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *lds_raw, const TileList done)
 {
@@ -1072,6 +1089,15 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
                 z               = wrap ? 0.0f : z;
                 st              = fin ? ST_DONE : ST_CELL;
                 if (wrap & !fin) { // twice per ray
+                    if (OPT & MARCH_OPT_SCAN) { // the ray leaves length seg + 1 for the next: its state there (rt_step_scan.hip)
+                        unsigned char *bnd = reinterpret_cast<unsigned char *>(((unsigned long long) P.pad_march[1] << 32) | (unsigned long long) P.pad_march[0]);
+                        float *q           = reinterpret_cast<float *>(bnd + scan_bnd_off(ridx, seg + 1, L));
+                        q[0]               = px;
+                        q[1]               = py;
+                        q[2]               = sx;
+                        q[3]               = sy;
+                        q[4]               = sz;
+                    }
                     seg++;
                     ii = backward ? P.N - seg - 1 : seg + 1;
                     G  = hdr[ii];

@@ -199,6 +199,7 @@ void rt_hip_plan_destroy(rt_hip_plan *p)
     (void) hipFree(p->spec[1].Iv);
     pool_free(p->device, p->step_dev);
     pool_free(p->device, p->seeds_dev);
+    pool_free(p->device, p->scan_bnd);
     (void) hipFree(p->seedset_arena);
     (void) hipFree(p->seedset_tab);
     pool_free(p->device, p->arena);
@@ -656,7 +657,7 @@ void rtr::plan_stage_outputs(rt_hip_plan *p)
     constexpr size_t ctl_tail = offsetof(rt::DevCtl, failure_code), ctl_bytes = sizeof(rt::DevCtl) - ctl_tail;
     if (!p || !p->ran || !p->last_stream)
         return;
-    if (p->last_step && (p->last_step_lent || p->last_n_seed > 0)) // E_v and nf are the caller's, or a seed set's: fetched the ordinary way
+    if (p->last_step && (p->last_step_lent || p->last_n_seed > 0 || p->last_scan_L > 0)) // E_v and nf are the caller's, a seed set's or a length scan's: fetched the ordinary way
         return;
     // (a step run: E_v and nf travel where the image does)
     const double *big    = p->last_step ? p->step_dev : p->last_image;
@@ -895,6 +896,8 @@ int rt_hip_plan_enable_path(rt_hip_plan *p, int on)
         return fail_arg("rt_hip_plan_enable_path: the plan is in step mode (one output mode at a time)");
     if (on && p->n_seed > 0)
         return fail_arg("rt_hip_plan_enable_path: the plan holds a seed set (step mode only)");
+    if (on && p->scan_on)
+        return fail_arg("rt_hip_plan_enable_path: the length scan is on (step mode only)");
     p->path_on = on != 0;
     return RT_OK;
 }
@@ -923,6 +926,8 @@ int rt_hip_plan_enable_spectra(rt_hip_plan *p, int on)
         return fail_arg("rt_hip_plan_enable_spectra: the plan is in step mode (one output mode at a time)");
     if (on && p->n_seed > 0)
         return fail_arg("rt_hip_plan_enable_spectra: the plan holds a seed set (step mode only)");
+    if (on && p->scan_on)
+        return fail_arg("rt_hip_plan_enable_spectra: the length scan is on (step mode only)");
     p->spectra_on = on != 0;
     return RT_OK;
 }
@@ -1048,6 +1053,16 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
     const bool lent = step && p->step_ev_lent; // E_v and nf in the caller's memory (rt_hip_plan_set_step_buffers)
     const size_t nf_off = align_up((size_t) p->P.K * sizeof(double), 256) / sizeof(double);
     const int n_seed = p->n_seed; // a seed set: one record per seed, all in one allocation of the plan
+    const int scan_L = p->scan_on ? p->P.L : 0; // a length scan: one record per length, the same allocation (never both)
+    const int n_rec  = n_seed > 0 ? n_seed : scan_L;
+    if (scan_L > 0) {
+        if (!step || p->path_on)
+            return fail_arg("rt_hip_plan_run: the length scan is on, which runs in step mode only");
+        if (lent)
+            return fail_arg("rt_hip_plan_run: a length scan writes the plan's own records, not lent step buffers");
+        if (image_dev || iang_dev)
+            return fail_arg("rt_hip_plan_run: a run with the length scan on takes no image and no I_ang buffer");
+    }
     if (n_seed > 0) {
         if (!step || p->path_on)
             return fail_arg("rt_hip_plan_run: the plan holds a seed set, which runs in step mode only");
@@ -1055,24 +1070,27 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
             return fail_arg("rt_hip_plan_run: a seed set writes the plan's own records, not lent step buffers");
         if (image_dev || iang_dev)
             return fail_arg("rt_hip_plan_run: a run with a seed set takes no image and no I_ang buffer");
+    }
+    if (n_rec > 0) {
         const rt::DevBeam &B = p->P.beam;
         // (the spare cells of the one-point-axis case: rt_multi.hip, multi_step's buffer)
         const size_t ang_off = nf_off + (size_t) B.nx * (size_t) B.ny + ((B.nx < 2 || B.ny < 2) ? (size_t) B.nx + 2 : 0);
         const size_t stride  = align_up((ang_off + p->n_iang + ((B.na < 2 || B.nb < 2) ? (size_t) B.na + 2 : 0)) * sizeof(double), 256) / sizeof(double);
-        if (!p->seeds_dev || p->seeds_doubles != stride * (size_t) n_seed) {
+        if (!p->seeds_dev || p->seeds_doubles != stride * (size_t) n_rec) {
             plan_quiesce(p);
             pool_free(p->device, p->seeds_dev);
             p->seeds_dev     = nullptr;
             p->seeds_doubles = 0;
-            HIP_TRY(pool_alloc(p->device, (void **) &p->seeds_dev, stride * (size_t) n_seed * sizeof(double)));
-            p->seeds_doubles = stride * (size_t) n_seed;
+            HIP_TRY(pool_alloc(p->device, (void **) &p->seeds_dev, stride * (size_t) n_rec * sizeof(double)));
+            p->seeds_doubles = stride * (size_t) n_rec;
         }
         p->seeds_stride  = stride;
         p->seeds_nf_off  = nf_off;
         p->seeds_ang_off = ang_off;
-        iang_dev         = p->seeds_dev + ang_off; // seed 0's: what rt_hip_plan_fetch and fetch_step serve
+        // seed 0's, or the record of all N lengths: what rt_hip_plan_fetch and fetch_step serve
+        iang_dev         = p->seeds_dev + (scan_L > 0 ? (size_t) (scan_L - 1) * stride : 0) + ang_off;
     }
-    if (step && !lent && !n_seed && !p->step_dev) {
+    if (step && !lent && !n_rec && !p->step_dev) {
         // (one row and a cell to spare: on an axis of one grid point the reference's getIndex answers 1 for the coordinate
         // g[0] + d/2 exactly, deposit_index4 of rt_freq.hip likewise)
         p->step_doubles     = nf_off + (size_t) p->P.beam.nx * (size_t) p->P.beam.ny + (size_t) p->P.beam.nx + 2;
@@ -1081,6 +1099,7 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
     rt::StepOut step_out = {};
     if (step)
         step_out = lent ? rt::StepOut{ p->step_ev_lent, p->step_nf_lent }
+                 : scan_L ? rt::StepOut{ p->seeds_dev + (size_t) (scan_L - 1) * p->seeds_stride, p->seeds_dev + (size_t) (scan_L - 1) * p->seeds_stride + nf_off }
                  : n_seed ? rt::StepOut{ p->seeds_dev, p->seeds_dev + nf_off } : rt::StepOut{ p->step_dev, p->step_dev + nf_off };
     if (!spectra && !step && !image_dev) {
         if (!p->image_own)
@@ -1113,7 +1132,7 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
     // (step mode: E_v and nf take the image's place in the zeroing launch, exclusive or not)
     rc = lent ? launch_zero4(stream, step_out.E_v, (size_t) p->P.K * sizeof(double), step_out.nf,
                              (size_t) p->P.beam.nx * (size_t) p->P.beam.ny * sizeof(double), iang_dev, p->n_iang * sizeof(double), p->ctl, sizeof(rt::DevCtl))
-         : n_seed ? launch_zero3(stream, p->seeds_dev, p->seeds_doubles * sizeof(double), nullptr, 0, p->ctl, sizeof(rt::DevCtl))
+         : n_rec ? launch_zero3(stream, p->seeds_dev, p->seeds_doubles * sizeof(double), nullptr, 0, p->ctl, sizeof(rt::DevCtl))
          : step ? launch_zero3(stream, p->step_dev, p->step_doubles * sizeof(double), iang_dev, p->n_iang * sizeof(double), p->ctl, sizeof(rt::DevCtl))
               : launch_zero3(stream, (p->P.exclusive || spectra) ? nullptr : image_dev, p->n_image * sizeof(double), iang_dev,
                              p->n_iang * sizeof(double), p->ctl, sizeof(rt::DevCtl));
@@ -1142,6 +1161,7 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
     p->last_step   = step;
     p->last_step_lent = lent;
     p->last_n_seed = n_seed;
+    p->last_scan_L = scan_L;
     p->spec_last   = p->spec_sel;
     p->ran         = true;
     p->queued      = false; // (`ran` + last_stream cover it from here)
@@ -1160,11 +1180,19 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
 // mark): the report stays as the kernels left it.
 static int plan_report_first_failed(rt_hip_plan *p)
 {
-    const size_t n = (size_t) p->n_rays;
-    if (!p->bad_dev || p->bad_rays < n)
+    const size_t n = (size_t) p->n_rays, word = p->bad_word; // (a length scan: a 32-bit word per ray, marked under anything = any byte set)
+    if (!p->bad_dev || p->bad_rays < n * word)
         return RT_OK;
-    std::vector<unsigned char> bad(n);
-    HIP_TRY(hipMemcpy(bad.data(), p->bad_dev, n, hipMemcpyDeviceToHost));
+    std::vector<unsigned char> bad(n * word);
+    HIP_TRY(hipMemcpy(bad.data(), p->bad_dev, n * word, hipMemcpyDeviceToHost));
+    if (word > 1) {
+        for (size_t t = 0; t < n; t++) {
+            unsigned char any = 0;
+            for (size_t b = 0; b < word; b++)
+                any |= bad[t * word + b];
+            bad[t] = any;
+        }
+    }
     const rt::DevRays &R = p->P.rays;
     std::vector<double> g;
     if (!R.list) {
@@ -1363,6 +1391,79 @@ int rt_hip_plan_seed_step_ptrs(rt_hip_plan *p, int s, double **E_v_dev, double *
     return RT_OK;
 }
 
+int rt_hip_plan_enable_length_scan(rt_hip_plan *p, int on)
+{
+    if (!p)
+        return fail_arg("rt_hip_plan_enable_length_scan: NULL plan");
+    if (on) {
+        if (p->P.method != 2)
+            return fail_arg("rt_hip_plan_enable_length_scan: the plan's method is not 2 (only the forward march of N lengths holds the marches of fewer)");
+        if (p->P.N < 3)
+            return fail_arg("rt_hip_plan_enable_length_scan: N < 3 (one length: the step record is the scan)");
+        if (p->P.N - 1 > RT_N_SCAN_MAX)
+            return fail_arg("rt_hip_plan_enable_length_scan: more than RT_N_SCAN_MAX lengths");
+        if (p->n_seed > 0)
+            return fail_arg("rt_hip_plan_enable_length_scan: the plan holds a seed set (a seed set and a length scan exclude each other)");
+        if (p->path_on || p->spectra_on)
+            return fail_arg("rt_hip_plan_enable_length_scan: the path tracer or spectra mode is enabled (the scan runs in step mode only)");
+    }
+    if ((on != 0) == p->scan_on)
+        return RT_OK;
+    HIP_TRY(hipSetDevice(p->device));
+    if (p->ran) { // the last run keeps its records until it is final (wait, control block, the checking repeat)
+        const int rs = plan_settle_last_run(p);
+        if (rs != RT_OK)
+            return rs;
+    }
+    plan_quiesce(p);
+    p->scan_on = on != 0;
+    if (!p->scan_on) { // the boundary states exist only while the scan is on
+        pool_free(p->device, p->scan_bnd);
+        p->scan_bnd       = nullptr;
+        p->scan_bnd_bytes = 0;
+    }
+    return RT_OK;
+}
+
+int rt_hip_plan_fetch_length_step(rt_hip_plan *p, int n, double *E_v, double *nf, double *I_ang, unsigned int *failure_code)
+{
+    if (!p || !p->ran || !p->last_step || p->last_scan_L < 1)
+        return fail_arg("rt_hip_plan_fetch_length_step: the last run was not a step run with the length scan on");
+    if (n < 2 || n - 1 > p->last_scan_L)
+        return fail_arg("rt_hip_plan_fetch_length_step: n must be 2 .. N of the last run");
+    rt::DevCtl c;
+    bool staged  = false;
+    const int rs = plan_settle(p, c, staged); // (a failing run is repeated here as rt_hip_plan_fetch repeats it)
+    if (rs != RT_OK)
+        return rs;
+    const double *blk = p->seeds_dev + (size_t) (n - 2) * p->seeds_stride;
+    if (E_v)
+        HIP_TRY(hipMemcpy(E_v, blk, (size_t) p->P.K * sizeof(double), hipMemcpyDeviceToHost));
+    if (nf)
+        HIP_TRY(hipMemcpy(nf, blk + p->seeds_nf_off, (size_t) p->P.beam.nx * (size_t) p->P.beam.ny * sizeof(double), hipMemcpyDeviceToHost));
+    if (I_ang)
+        HIP_TRY(hipMemcpy(I_ang, blk + p->seeds_ang_off, p->n_iang * sizeof(double), hipMemcpyDeviceToHost));
+    if (failure_code)
+        *failure_code = c.len_code[n - 2];
+    return RT_OK;
+}
+
+int rt_hip_plan_length_step_ptrs(rt_hip_plan *p, int n, double **E_v_dev, double **nf_dev, double **iang_dev)
+{
+    if (!p || !p->ran || !p->last_step || p->last_scan_L < 1)
+        return fail_arg("rt_hip_plan_length_step_ptrs: the last run was not a step run with the length scan on");
+    if (n < 2 || n - 1 > p->last_scan_L)
+        return fail_arg("rt_hip_plan_length_step_ptrs: n must be 2 .. N of the last run");
+    double *blk = p->seeds_dev + (size_t) (n - 2) * p->seeds_stride;
+    if (E_v_dev)
+        *E_v_dev = blk;
+    if (nf_dev)
+        *nf_dev = blk + p->seeds_nf_off;
+    if (iang_dev)
+        *iang_dev = blk + p->seeds_ang_off;
+    return RT_OK;
+}
+
 int rt_hip_plan_set_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds)
 {
     if (!p)
@@ -1381,6 +1482,8 @@ int rt_hip_plan_set_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds)
             if (i == 4 && seeds[s].dim[4] != K)
                 return fail_arg("rt_hip_plan_set_seeds: seed.dim[4] != beam.nv");
         }
+    if (n_seed > 0 && p->scan_on)
+        return fail_arg("rt_hip_plan_set_seeds: the length scan is on (a seed set and a length scan exclude each other)");
     if (n_seed > 0 && (p->path_on || p->spectra_on))
         return fail_arg("rt_hip_plan_set_seeds: the path tracer or spectra mode is enabled (a set runs in step mode only)");
     HIP_TRY(hipSetDevice(p->device));
@@ -1551,8 +1654,9 @@ int rt_hip_plan_fetch_probe(rt_hip_plan *p, float *gvl, float *evl, int32_t *ivl
 static int host_pointer_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed,
                              int method, const rt_ray *rays, size_t n_rays, double scale, double *image, double *E_v, double *nf,
                              double *I_ang, unsigned int *failure_code, rt_ray *failed_rays, int max_failed,
-                             int *n_failed, rt_stats *stats)
+                             int *n_failed, rt_stats *stats, bool scan = false)
 {
+    // (scan: rt_hip_length_scan_loop -- E_v, nf and I_ang hold one row per length n = 2 .. N, failure_code one code per row)
     const bool step = image == nullptr;
     // RT_HIP_TIMING=1: wall-clock split of this call on stderr (diagnostic)
     static const bool timing = getenv("RT_HIP_TIMING") != nullptr;
@@ -1575,6 +1679,8 @@ static int host_pointer_loop(int device, int N, const rt_beam *beam, const rt_ga
     }
     if (step) {
         rc = rt_hip_plan_enable_step(p, 1);
+        if (rc == RT_OK && scan)
+            rc = rt_hip_plan_enable_length_scan(p, 1);
         if (rc != RT_OK) {
             rt_hip_plan_destroy(p);
             release_queue(device, q);
@@ -1612,9 +1718,14 @@ static int host_pointer_loop(int device, int N, const rt_beam *beam, const rt_ga
             plan_stage_outputs(p);
     }
     if (rc == RT_OK)
-        rc = rt_hip_plan_fetch(p, image, step ? nullptr : I_ang, failure_code, failed_rays, max_failed, n_failed, stats);
-    if (rc == RT_OK && step)
+        rc = rt_hip_plan_fetch(p, image, step ? nullptr : I_ang, scan ? nullptr : failure_code, failed_rays, max_failed, n_failed, stats);
+    if (rc == RT_OK && step && !scan)
         rc = rt_hip_plan_fetch_step(p, E_v, nf, I_ang);
+    for (int n = 2; rc == RT_OK && scan && n <= N; n++) {
+        const size_t r = (size_t) (n - 2);
+        rc = rt_hip_plan_fetch_length_step(p, n, E_v ? E_v + r * (size_t) beam->nv : nullptr, nf ? nf + r * (size_t) beam->nx * (size_t) beam->ny : nullptr,
+                                           I_ang ? I_ang + r * (size_t) beam->na * (size_t) beam->nb : nullptr, failure_code ? failure_code + r : nullptr);
+    }
     lap("fetch (wait + D2H)");
     rt_hip_plan_destroy(p); // waits for whatever is still in flight
     release_queue(device, q);
@@ -1651,6 +1762,21 @@ int rt_hip_step_loop(int device, int N, const rt_beam *beam, const rt_gain *gain
         return fail_arg("rt_hip_step_loop: 2^32 - 4096 rays or more: split the call");
     return host_pointer_loop(device, N, beam, gain, seed, method, rays, n_rays, scale, nullptr, E_v, nf, I_ang, failure_code,
                              failed_rays, max_failed, n_failed, stats);
+}
+
+int rt_hip_length_scan_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed, int method,
+                            const rt_ray *rays, size_t n_rays, double scale, double *E_v, double *nf, double *I_ang,
+                            unsigned int *failure_codes, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats)
+{
+    if (!beam)
+        return fail_arg("rt_hip_length_scan_loop: NULL beam");
+    if (!rays && n_rays)
+        return fail_arg("rt_hip_length_scan_loop: NULL ray list");
+    if (n_rays > MAX_LIST_RAYS)
+        return fail_arg("rt_hip_length_scan_loop: 2^32 - 4096 rays or more: split the call");
+    // (method, N: rt_hip_plan_enable_length_scan refuses what the scan does not take)
+    return host_pointer_loop(device, N, beam, gain, seed, method, rays, n_rays, scale, nullptr, E_v, nf, I_ang, failure_codes,
+                             failed_rays, max_failed, n_failed, stats, true);
 }
 
 int rt_hip_calc_rays(int device, int N, double dz, const rt_gain *gain, const rt_seed *seed, int K, int method, const double *rays,

@@ -30,6 +30,7 @@ struct RunFacts {
     bool use_emis = false, own_cells = false, exclusive = false, path_on = false, spectra_on = false, step_on = false,
          step_one_launch = false, probe_on = false, has_ray_list = false, host_rays = false, tables_bounded = false,
          ntest_proven = false, gv_has_nan = false;
+    bool scan_on = false; // a length scan (rt_hip_plan_enable_length_scan): one step record per length from one forward march
     bool s6() const { return L * RT_N_SUB == 6; } // N = 3, the shipped inputs: the instances with SF = 6
 };
 
@@ -258,7 +259,7 @@ inline RunShape run_shape(const RunFacts &f, const Tuning &t, const Occupancy &o
     // leave no room keep the two kernels.
     const bool step_cand = f.step_on && f.step_one_launch && s.lds_tab && s.n_launch == 1 && f.n_rays > 0 && f.use_emis && f.method == 1 &&
                            f.own_cells && !f.probe_on && !f.path_on && !f.spectra_on && f.debug == 0 && f.safe == 0 && !f.exclusive &&
-                           f.n_seed == 0 && iang_fits && t.fused == 1;
+                           f.n_seed == 0 && !f.scan_on && iang_fits && t.fused == 1;
     s.bthr = s.lds_tab ? 1024u : 256u;
     if (s.lds_tab && !fused_cand && !step_cand) {
         // Few rays per lane leave the persistent lanes waiting for the longest ray of a short
@@ -292,6 +293,12 @@ inline RunShape run_shape(const RunFacts &f, const Tuning &t, const Occupancy &o
     const unsigned long long launch_rays = f.n_rays / s.n_launch;
     const bool prune_h24 = f.march_prune == 2 || (f.cu_count && launch_rays / (unsigned long long) f.cu_count >= 8192ull);
     s.opt = (s.bounded && f.march_prune && f.ntest_proven) ? (rt::MARCH_OPT_PRUNE | rt::MARCH_OPT_NO_NTEST | (prune_h24 ? rt::MARCH_OPT_PRUNE_H24 : 0)) : 0;
+    // (a length scan: the instance that stores the boundary states, rt_march.hip MARCH_OPT_SCAN -- forward method at compile
+    // time, the emission switch as DevParams says, no pruning; with bounded and unbounded tables, in LDS or not)
+    if (f.scan_on) {
+        s.mode = 3;
+        s.opt  = rt::MARCH_OPT_SCAN;
+    }
     s.last_march_inst = (s.bounded ? 1 : 0) | (s.opt << 1);
     // one work-group per CU: the tables take more than half of the LDS... or the work-group all wave slots
     int per_cu = 1;
@@ -342,11 +349,11 @@ inline RunShape run_shape(const RunFacts &f, const Tuning &t, const Occupancy &o
 }
 
 // ---- the second pass -----------------------------------------------------------------------------------------------
-enum PassKind { PASS_FREQ = 0, PASS_SPEC = 1, PASS_STEP = 2, PASS_SEEDS = 3, PASS_PATH = 4 };
+enum PassKind { PASS_FREQ = 0, PASS_SPEC = 1, PASS_STEP = 2, PASS_SEEDS = 3, PASS_PATH = 4, PASS_SCAN = 5 };
 
 inline PassKind pass_kind(const RunFacts &f)
 {
-    return f.path_on ? PASS_PATH : f.spectra_on ? PASS_SPEC : f.step_on ? (f.n_seed > 0 ? PASS_SEEDS : PASS_STEP) : PASS_FREQ;
+    return f.path_on ? PASS_PATH : f.spectra_on ? PASS_SPEC : f.step_on ? (f.scan_on ? PASS_SCAN : f.n_seed > 0 ? PASS_SEEDS : PASS_STEP) : PASS_FREQ;
 }
 
 struct PassShape {
@@ -405,14 +412,18 @@ inline PassShape pass_shape(PassKind kind, const RunFacts &f, const Tuning &t)
     if (kind == PASS_FREQ)
         freq_pass_shape(s, f, t);
     else {
-        // spectra, step, step of a seed set: one 16-wave work-group per CU
+        // spectra, step, step of a seed set or of a length scan: one 16-wave work-group per CU
         s.wg_waves = rt::FREQ_WG_WAVES;
-        auto seeds_lds = [&](bool in_lds) { return rt::step_seeds_lds_doubles(in_lds, (int) f.n_iang, f.Kp, s.wg_waves, f.n_seed) * sizeof(double); };
+        // (a seed set keeps one I_ang histogram and one E_v accumulator per seed, a length scan one of each per length)
+        auto seeds_lds = [&](bool in_lds) {
+            return (kind == PASS_SCAN ? rt::step_scan_lds_doubles(in_lds, (int) f.n_iang, f.Kp, s.wg_waves, f.L)
+                                      : rt::step_seeds_lds_doubles(in_lds, (int) f.n_iang, f.Kp, s.wg_waves, f.n_seed)) * sizeof(double);
+        };
         // (spectra: the staging rows of 16 waves and the exponent tables take 148 KB of LDS)
         s.lds = kind == PASS_SPEC ? ((size_t) 2 * rt::EXP_TAB + (size_t) s.wg_waves * rt::WAVE * rt::XS_ROW) * sizeof(double)
               : kind == PASS_STEP ? rt::step_lds_doubles(s.in_lds, (int) f.n_iang, f.Kp, s.wg_waves) * sizeof(double)
                                   : seeds_lds(s.in_lds);
-        if (kind == PASS_SEEDS && s.in_lds && s.lds > f.lds_limit) { // one histogram per seed does not fit: global atomics
+        if ((kind == PASS_SEEDS || kind == PASS_SCAN) && s.in_lds && s.lds > f.lds_limit) { // one histogram per seed (length) does not fit: global atomics
             s.in_lds = false;
             s.lds    = seeds_lds(false);
         }

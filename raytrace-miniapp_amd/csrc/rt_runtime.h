@@ -81,6 +81,15 @@ struct rt_hip_plan {
     size_t seeds_doubles = 0;                                    // doubles of the allocation
     size_t seeds_stride = 0, seeds_nf_off = 0, seeds_ang_off = 0; // doubles: block to block, E_v to nf, E_v to I_ang
     int last_n_seed = 0;                                         // seeds of the last run (0: it ran without a set)
+    // length scan (rt_hip_plan_enable_length_scan): one step record per plasma length n = 2 .. N from one forward march.
+    // The records are the blocks of the seed-set allocation above (seeds_dev, seeds_stride, ...: a scan and a set exclude
+    // each other), block n - 2 for n lengths; scan_bnd holds the state with which every ray crossed every length boundary
+    // (rt_march.hip, scan_bnd_off), from the plan's pool while the scan is on.
+    bool scan_on          = false;
+    int last_scan_L       = 0; // records of the last run (0: it ran without the scan)
+    unsigned char *scan_bnd = nullptr;
+    size_t scan_bnd_bytes = 0;
+    size_t bad_word       = 1; // bytes per ray of bad_dev in the last checking repeat (4: a length scan, one bit per length)
     size_t rec_bytes   = 0;
     hipEvent_t evm     = nullptr; // between march and frequency kernels
     const rt_ray *host_rays = nullptr; // ray list still on the host, uploaded by the next run (rt_hip_image_loop)

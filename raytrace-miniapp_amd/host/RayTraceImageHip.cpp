@@ -18,6 +18,8 @@
 //   RayTraceImageStepHipMultiGPULoop  the same record from all devices of the node through rt_hip_multi_step_loop: device d
 //        traces rays d, d + ndev, ... of the grid on the full beam, one RCCL sum-reduce of (E_v | nf | I_ang) assembles
 //        them -- the application's multi-rank step (src/RayTraceImage.cpp:300-313, intensity_step_struct::sum_reduce)
+//   RayTraceImageLengthScanHipLoop  the per-step record at EVERY plasma length n = 2 .. N -- what N - 1 create_image calls with
+//        info->N = n and the first n tables leave -- from one forward march, through rt_hip_length_scan_loop
 //   RayTraceCalcRaysHip           n calls of RayTrace::calc_ray (src/RayTraceImage.cpp:189-204) in one, through
 //        rt_hip_calc_rays: per-ray spectrum, exit ray and return code
 #include "RayTrace.h"
@@ -140,6 +142,37 @@ void RayTraceImageStepHipLoop(int N, const RayTrace::EUV_beam_struct &beam, cons
     if (rc != RT_OK)
         RAY_ERROR(std::string("HIP backend error: ") + rt_hip_last_error());
     failure_code |= code;
+    for (int i = 0; i < n_failed; i++) {
+        ray_struct r;
+        memcpy(&r, &failed[i], sizeof(r));
+        failed_rays.push_back(r);
+    }
+}
+
+// RayTraceImageStepHipLoop for every plasma length at once (forward method, 3 <= N <= RT_N_SCAN_MAX + 1): row n - 2 of
+// E_v [N-1][nv], nf [N-1][nx*ny], I_ang [N-1][na*nb] and failure_codes [N-1] is what RayTraceImageStepHipLoop leaves for
+// the first n of the tables (create_image_struct::pack is "for a single length": the caller packs N - 1 times, or once and
+// calls this).  failure_code is the OR of the codes; failed_rays the rays that fail at any length, each once.
+void RayTraceImageLengthScanHipLoop(int N, const RayTrace::EUV_beam_struct &beam, const RayTrace::ray_gain_struct *gain,
+    const RayTrace::ray_seed_struct *seed, int method, const std::vector<ray_struct> &rays, double scale,
+    double *E_v, double *nf, double *I_ang, unsigned int *failure_codes, unsigned int &failure_code,
+    std::vector<ray_struct> &failed_rays)
+{
+    failure_code = 0;
+    Flat f       = flatten(N, beam, gain, seed);
+    rt_ray failed[RT_N_FAILED_MAX];
+    int n_failed = 0;
+    std::vector<unsigned int> codes((size_t) (N > 1 ? N - 1 : 1), 0u);
+    int rc = rt_hip_length_scan_loop(0, N, &f.beam, f.gain.data(), f.has_seed ? &f.seed : NULL, method,
+                                     rays.empty() ? NULL : reinterpret_cast<const rt_ray *>(&rays[0]), rays.size(), scale, E_v, nf,
+                                     I_ang, codes.data(), failed, RT_N_FAILED_MAX, &n_failed, &g_last_stats);
+    if (rc != RT_OK)
+        RAY_ERROR(std::string("HIP backend error: ") + rt_hip_last_error());
+    for (int n = 2; n <= N; n++) {
+        failure_code |= codes[(size_t) (n - 2)];
+        if (failure_codes)
+            failure_codes[n - 2] = codes[(size_t) (n - 2)];
+    }
     for (int i = 0; i < n_failed; i++) {
         ray_struct r;
         memcpy(&r, &failed[i], sizeof(r));

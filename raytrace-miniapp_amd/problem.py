@@ -236,6 +236,20 @@ def scale_problem(p: Problem, scale: float) -> Problem:
     return q
 
 
+def prefix_lengths(p: Problem, n: int) -> Problem:
+    """The prefix problem of n lengths: p with the tables gain[0 .. n) -- same beam, rays, seed, scale and method.  What
+    the application traces when it asks for the record of a shorter plasma (create_image with info->N = n); record n of a
+    length scan (backend.Plan.enable_length_scan) is, by definition, the step record of this problem."""
+    if not isinstance(n, (int, np.integer)) or isinstance(n, bool) or n < 2 or n > p.N:
+        raise ValueError(f"prefix_lengths: n = {n!r}, must be an integer 2 .. N = {p.N}")
+    q = copy.copy(p)
+    q.gain = list(p.gain[:int(n)])
+    q.golden_image = None
+    q.golden_I_ang = None
+    q.label = f"{p.label} / first {int(n)} lengths"
+    return q
+
+
 def regrid_beam(p: Problem, nx=None, ny=None, na=None, nb=None, a_centre=None, b_centre=None) -> Problem:
     """Cell-centred regrid of chosen beam axes to explicit sizes over the same
     extents (the scale_beam formula applied per axis); na/nb = 1 with a centre
