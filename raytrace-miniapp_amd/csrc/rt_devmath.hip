@@ -1,6 +1,8 @@
 // rt_devmath.hip -- test-only unit: the float64 building blocks of the frequency pass (rt_freq.hip), the two float
 // kernels of the march (rt_march.hip) and the seed-profile interpolation (pchip_eval / seed_factor of rt_math.h, and
-// rt_seed_tab_kernel itself), each behind one elementwise kernel, so that tests/test_gpu_devmath.py and
+// rt_seed_tab_kernel itself), each behind one elementwise kernel, and the two wave primitives of the step deposit (the E_v
+// wave sum rt_step_evsum.inc, the segmented scan rt_wave_runs.inc / rt_wave_runscan.inc), each behind a kernel of one
+// work-group, so that tests/test_gpu_devmath.py and
 // tests/test_gpu_seed_profiles.py can run them on a device on inputs of their own choosing.  Builds to librt_hip_devmath.so with the product's flags; nothing
 // of it is linked into librt_hip.so.
 //
@@ -161,6 +163,61 @@ __global__ void __launch_bounds__(DM_BLOCK) dm_seed_factor_kernel(const DevSeed 
     const size_t stride = (size_t) gridDim.x * blockDim.x;
     for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < m; i += stride)
         f[i] = seed_factor(sd, pts[4 * i + 0], pts[4 * i + 1], pts[4 * i + 2], pts[4 * i + 3]);
+}
+
+// ---- the two wave primitives of the step deposit, each on ONE work-group of DM_BLOCK threads: four waves, every wave with
+// transposition rows and a pixel pattern of its own -----------------------------------------------------------------------
+constexpr int DM_EV_KP_MAX = 64;
+
+// rt_step_evsum.inc as a step tile includes it: Iv [256][Kp] (thread, frequency), deposits [256]; out [Kp] = the
+// work-group's accumulator = scale * sum over the depositing threads
+__global__ void __launch_bounds__(DM_BLOCK) dm_ev_sum_kernel(const double *Iv_in, const unsigned char *deposits, double scale, int Kp,
+                                                            double *out)
+{
+    __shared__ double lds_ev[DM_EV_KP_MAX];
+    __shared__ __align__(16) double rows[DM_BLOCK / WAVE][4 * XP_ROW];
+    const struct {
+        double scale;
+    } H           = { scale };
+    const int lane = lane_id();
+    double *xpose  = rows[threadIdx.x >> 6];
+    for (int c = (int) threadIdx.x; c < Kp; c += (int) blockDim.x)
+        lds_ev[c] = 0.0;
+    __syncthreads();
+    const bool dep = deposits[threadIdx.x] != 0;
+    for (int kb = 0; kb < Kp; kb += VEC) {
+        double Iv[VEC];
+#pragma unroll
+        for (int j = 0; j < VEC; j++)
+            Iv[j] = Iv_in[(size_t) threadIdx.x * (size_t) Kp + kb + j];
+#define EV_SUM_DEPOSITS dep
+#define EV_SUM_INDEX kb
+#include "rt_step_evsum.inc"
+#undef EV_SUM_DEPOSITS
+#undef EV_SUM_INDEX
+    }
+    __syncthreads();
+    for (int c = (int) threadIdx.x; c < Kp; c += (int) blockDim.x)
+        out[c] = lds_ev[c];
+}
+
+// rt_wave_runs.inc and rt_wave_runscan.inc as the nf deposit of a step tile includes them: pix [256] (-1: no pixel),
+// val [256]; nf [n_pix] += scale * val per pixel, one atomic per run of equal pixel and wave (the host face zeroes nf and
+// has checked pix < n_pix)
+__global__ void __launch_bounds__(DM_BLOCK) dm_nf_scan_kernel(const int *pix_in, const double *val, double scale, double *nf)
+{
+    const int lane = lane_id();
+    const int pix  = pix_in[threadIdx.x];
+    const bool dep = pix >= 0;
+#define RUNS_PIX pix
+#define RUNS_DEPOSITS dep
+#include "rt_wave_runs.inc"
+#undef RUNS_PIX
+#undef RUNS_DEPOSITS
+    double a = dep ? val[threadIdx.x] * scale : 0.0;
+#include "rt_wave_runscan.inc"
+    if (tail && a != 0.0)
+        unsafeAtomicAdd(&nf[pix], a);
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------
@@ -399,6 +456,40 @@ DM_API int rt_devmath_seed_factor(const int *dim, const double *const *xs, const
     DM_TRY(B.out((void **) &df, m * sizeof(double)));
     dm_seed_factor_kernel<<<grid_for(m), DM_BLOCK>>>(sd, dpts, df, m);
     return B.release(finish(f, df, m * sizeof(double)));
+}
+
+// one work-group: Iv [256][Kp], deposits [256] (0 / not 0), Kp a multiple of VEC up to 64; out [Kp]
+DM_API int rt_devmath_ev_sum(const double *Iv, const unsigned char *deposits, double scale, int Kp, double *out)
+{
+    Bufs B;
+    double *dIv, *dout;
+    unsigned char *ddep;
+    if (Kp < VEC || Kp > DM_EV_KP_MAX || Kp % VEC != 0)
+        return (int) hipErrorInvalidValue;
+    DM_TRY(B.in((void **) &dIv, Iv, (size_t) DM_BLOCK * Kp * sizeof(double)));
+    DM_TRY(B.in((void **) &ddep, deposits, DM_BLOCK));
+    DM_TRY(B.out((void **) &dout, (size_t) Kp * sizeof(double)));
+    dm_ev_sum_kernel<<<1, DM_BLOCK>>>(dIv, ddep, scale, Kp, dout);
+    return B.release(finish(out, dout, (size_t) Kp * sizeof(double)));
+}
+
+// one work-group: pix [256] in -1 .. n_pix - 1, val [256]; nf [n_pix]
+DM_API int rt_devmath_nf_scan(const int *pix, const double *val, double scale, int n_pix, double *nf)
+{
+    Bufs B;
+    int *dpix;
+    double *dval, *dnf;
+    if (n_pix < 1)
+        return (int) hipErrorInvalidValue;
+    for (int i = 0; i < DM_BLOCK; i++)
+        if (pix[i] < -1 || pix[i] >= n_pix)
+            return (int) hipErrorInvalidValue;
+    DM_TRY(B.in((void **) &dpix, pix, DM_BLOCK * sizeof(int)));
+    DM_TRY(B.in((void **) &dval, val, DM_BLOCK * sizeof(double)));
+    DM_TRY(B.out((void **) &dnf, (size_t) n_pix * sizeof(double)));
+    DM_TRY(hipMemset(dnf, 0, (size_t) n_pix * sizeof(double)));
+    dm_nf_scan_kernel<<<1, DM_BLOCK>>>(dpix, dval, scale, dnf);
+    return B.release(finish(nf, dnf, (size_t) n_pix * sizeof(double)));
 }
 
 // rt_seed_tab_kernel of rt_march.hip, unchanged, on a DevRays made of the four grids g[a] [n_grid[a]], n_grid[a] >= 1:

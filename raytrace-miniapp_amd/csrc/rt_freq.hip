@@ -396,6 +396,20 @@ __device__ __forceinline__ RecSlot rec_slot_lazy(const unsigned char *rec, unsig
 // (Round 4 ran it for every ray of a launch in a pass of its own before the frequency kernel, result left in the
 // record: seed_small 1.446 against 1.222 ms -- the pass re-reads and re-writes every line of the 750 MB of records,
 // which costs more than the chain of loads it takes out of the tile preamble, where four waves per SIMD cover it.)
+// The seed factor of a launch ray that is a point of the forward ray grid (DevRays::sf), one definition for place_ray,
+// step_seeds_tile (rt_step_seeds.hip: the grid point once, the factor per seed) and step_scan_tile (rt_step_scan.hip); macros
+// for the reason RT_FILL_EXP_TABLES is one.  RT_SEED_GRID_POINT declares the grid point gi, gj, gk, gm of ray ridx and where
+// the tables of the axes begin; RT_SEED_GRID_FACTOR sets `out` (0.0 before) to f0 times the four tabulated factors
+// (rt_seed_tab_kernel) in seed_factor's order, clamped at 0 -- inside the support of every axis only.
+#define RT_SEED_GRID_POINT(R, ridx)      \
+    unsigned gi, gj, gk, gm;             \
+    grid_index(R, ridx, gi, gj, gk, gm); \
+    const unsigned oj = (unsigned) R.ngx, ok = oj + (unsigned) R.ngy, om = ok + (unsigned) R.nga;
+#define RT_SEED_GRID_FACTOR(out, f0, sf, sin)                         \
+    if (sin[gi] & sin[oj + gj] & sin[ok + gk] & sin[om + gm]) {      \
+        out = f0 * sf[gi] * sf[oj + gj] * sf[ok + gk] * sf[om + gm]; \
+        out = out < 0.0 ? 0.0 : out;                                 \
+    }
 struct Placed {
     double f0; // seed factor (0 without a seed, for escaped rays and outside the profile)
     int pix;   // pixel i + j nx, or -1
@@ -418,14 +432,9 @@ __device__ __forceinline__ Placed place_ray(const unsigned hflags, ColdPtr C, co
             P.f0 = backward ? seed_factor(SD, (double) m.px, (double) m.py, (double) r2.a, (double) r2.b)
                             : seed_factor(SD, (double) ray.x, (double) ray.y, (double) ray.a, (double) ray.b);
         } else {
-            // the launch ray is a grid point: product of the tabulated factors, in seed_factor's order
-            unsigned gi, gj, gk, gm;
-            grid_index(R, ridx, gi, gj, gk, gm);
-            const unsigned oj = (unsigned) R.ngx, ok = oj + (unsigned) R.ngy, om = ok + (unsigned) R.nga;
-            if (R.sin[gi] & R.sin[oj + gj] & R.sin[ok + gk] & R.sin[om + gm]) {
-                P.f0 = C->seed.f0 * R.sf[gi] * R.sf[oj + gj] * R.sf[ok + gk] * R.sf[om + gm];
-                P.f0 = P.f0 < 0.0 ? 0.0 : P.f0;
-            }
+            // the launch ray is a grid point: product of the tabulated factors (RT_SEED_GRID_FACTOR)
+            RT_SEED_GRID_POINT(R, ridx)
+            RT_SEED_GRID_FACTOR(P.f0, C->seed.f0, R.sf, R.sin)
         }
     }
     if (hflags & FQ_PROBE)
@@ -741,28 +750,17 @@ __device__ __forceinline__ void freq_tile(const FreqHot &H, const unsigned hflag
             }
         });
     } else {
-        // segmented shuffle scan over the runs, one atomic per run and frequency
-        const int pix_prev = __shfl_up(pix, 1, WAVE);
-        const bool head    = lane == 0 || pix_prev != pix;
-        int run_start      = head ? lane : -1;
-#pragma unroll
-        for (int o = 1; o < WAVE; o <<= 1) {
-            const int t = __shfl_up(run_start, o, WAVE);
-            if (lane >= o && t > run_start)
-                run_start = t;
-        }
-        const int head_next = __shfl_down(head ? 1 : 0, 1, WAVE);
-        const bool tail     = (lane == WAVE - 1 || head_next != 0) && pix >= 0;
+        // segmented shuffle scan over the runs (rt_wave_runs.inc, rt_wave_runscan.inc), one atomic per run and frequency
+#define RUNS_PIX pix
+#define RUNS_DEPOSITS pix >= 0
+#include "rt_wave_runs.inc"
+#undef RUNS_PIX
+#undef RUNS_DEPOSITS
         frequency_loop([&](int kb, double (&v)[VEC]) {
 #pragma unroll
             for (int j = 0; j < VEC; j++) {
                 double a = v[j];
-#pragma unroll
-                for (int i = 0; i < 6; i++) {
-                    const double t = __shfl_up(a, 1 << i, WAVE);
-                    if ((lane - (1 << i)) >= run_start)
-                        a += t;
-                }
+#include "rt_wave_runscan.inc"
                 if (tail && kb + j < k_end)
                     unsafeAtomicAdd(&img_row[kb + j], a);
             }

@@ -11,8 +11,9 @@
 // the TileList, the consumer waves, the late zone (host), buffer slots beside the tables and over them.  It is restated
 // here and not shared as a function, so that every rt_fused_kernel instance keeps the instruction stream it was measured
 // with.  Phase 2 pops tiles as rt_fused_kernel does and runs the step pass on each (step_tile_part below: step_tile's
-// text, rt_tile_step.inc), whole or on one of the four parts [k0, k1) of its frequency range (TILE_PART_FLAG); at the
-// end the work-group flushes E_v and the I_ang histogram with the f64 atomics of rt_step_kernel.
+// text, rt_tile_step.inc, and with it the deposit fragments rt_step_evsum.inc, rt_wave_runs.inc, rt_wave_runscan.inc), whole
+// or on one of the four parts [k0, k1) of its frequency range (TILE_PART_FLAG); at the end the work-group flushes E_v and
+// the I_ang histogram with f64 atomics, zeros skipped, as the epilogue of a step pass does (rt_step_wg.inc).
 //
 // Split tiles (the rules of freq_tile): a part integrates the batches k0 .. min(k1, K); error -1 is reported by the part
 // with k0 == 0 only; E_v is per frequency anyway, and each part's share of the lane's sum over k goes into I_ang and nf
@@ -181,7 +182,8 @@ __global__ void __launch_bounds__(1024) rt_fused_step_kernel(const FusedStepKArg
         }
     }
 #endif
-    // the work-group's sums leave once, as rt_step_kernel's do
+    // the work-group's sums leave once.  (An epilogue of its own, not rt_step_wg.inc's: FusedLay always holds the histogram, and
+    // it leaves unconditionally -- the shared text, with its two tests, is not this kernel's instruction stream.)
     __syncthreads();
     for (int c = (int) threadIdx.x; c < H.K; c += (int) blockDim.x) {
         const double v = lds_ev[c];

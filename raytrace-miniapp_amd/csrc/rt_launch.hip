@@ -227,19 +227,33 @@ RunFacts run_facts(const rt_hip_plan *p)
     return f;
 }
 
+// the argument block of a pass that stands in the frequency kernel's place: its two halves, without the cube (never touched)
+template <typename KArg> KArg pass_args(const rt::FreqKArg &fa)
+{
+    KArg a;
+    memset(&a, 0, sizeof(a));
+    a.hot       = fa.hot;
+    a.hot.image = nullptr;
+    a.cold      = fa.cold;
+    return a;
+}
+
 // The second pass over all tiles as a kernel of its own: the frequency / deposit kernel, or in its place the spectra
 // kernel (per-ray spectra, no image), the step kernel (E_v, nf and I_ang, no image cube) or the step kernel of a seed set.
 int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kind, hipStream_t stream, unsigned safe = 0, unsigned char *bad = nullptr)
 {
     const PassShape s = pass_shape(kind, f, t);
-    if (kind == PASS_SPEC && s.lds > f.lds_limit)
-        return fail_arg("spectra kernel: the staging rows do not fit into the LDS of this device");
-    if (kind == PASS_STEP && s.lds > f.lds_limit)
-        return fail_arg("step kernel: the E_v accumulator (nv doubles) does not fit into the LDS of this device");
-    if (kind == PASS_SEEDS && s.lds > f.lds_limit)
-        return fail_arg("step kernel of a seed set: the E_v accumulators (nv doubles per seed) do not fit into the LDS of this device");
-    if (kind == PASS_SCAN && s.lds > f.lds_limit)
-        return fail_arg("step kernel of a length scan: the E_v accumulators (nv doubles per length) do not fit into the LDS of this device");
+    // (what of a one-work-group-per-CU pass does not fit, by kind; the frequency kernel's message, below, carries figures)
+    static const char *const too_big[] = {
+        nullptr, // PASS_FREQ
+        "spectra kernel: the staging rows do not fit into the LDS of this device",
+        "step kernel: the E_v accumulator (nv doubles) does not fit into the LDS of this device",
+        "step kernel of a seed set: the E_v accumulators (nv doubles per seed) do not fit into the LDS of this device",
+        nullptr, // PASS_PATH
+        "step kernel of a length scan: the E_v accumulators (nv doubles per length) do not fit into the LDS of this device" };
+    static_assert(PASS_SPEC == 1 && PASS_STEP == 2 && PASS_SEEDS == 3 && PASS_SCAN == 5, "too_big[] is indexed by PassKind");
+    if (too_big[kind] && s.lds > f.lds_limit)
+        return fail_arg(too_big[kind]);
     if (s.grid == 0)
         return RT_OK;
     if (s.lds > f.lds_limit) {
@@ -253,33 +267,21 @@ int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kin
     if (kind == PASS_FREQ)
         return launch(p, freq_kernel(f.s6(), f.use_emis, f.use_emis && f.exclusive), s.grid, block, s.lds, stream, fa);
     if (kind == PASS_SPEC) {
-        rt::SpecKArg a;
-        memset(&a, 0, sizeof(a));
-        a.hot       = fa.hot;
-        a.hot.image = nullptr;
+        rt::SpecKArg a = pass_args<rt::SpecKArg>(fa);
         a.hot.iang  = nullptr;
-        a.cold      = fa.cold;
         a.out       = p->spec[p->spec_sel];
         return launch(p, spec_kernel(f.s6(), f.use_emis), s.grid, block, s.lds, stream, a);
     }
     if (kind == PASS_STEP) {
-        rt::StepKArg a;
-        memset(&a, 0, sizeof(a));
-        a.hot       = fa.hot;
-        a.hot.image = nullptr; // never touched: there is no cube
-        a.cold      = fa.cold;
+        rt::StepKArg a = pass_args<rt::StepKArg>(fa);
         a.out       = p->step;
         return launch(p, step_kernel(f.s6(), f.use_emis), s.grid, block, s.lds, stream, a);
     }
     if (kind == PASS_SCAN) { // a length scan: one record per length, the blocks of the seed-set allocation
         if (!p->scan_bnd || !p->seeds_dev)
             return fail_arg("step kernel of a length scan: the boundary states or the records of this run were not allocated");
-        rt::ScanKArg a;
-        memset(&a, 0, sizeof(a));
-        a.hot          = fa.hot;
-        a.hot.image    = nullptr; // never touched: there is no cube
+        rt::ScanKArg a = pass_args<rt::ScanKArg>(fa);
         a.hot.iang     = nullptr; // (every record's I_ang lies in its block)
-        a.cold         = fa.cold;
         a.scan.bnd     = p->scan_bnd;
         a.scan.out     = p->seeds_dev;
         a.scan.stride  = p->seeds_stride;
@@ -288,12 +290,8 @@ int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kin
         return launch(p, scan_kernel(f.use_emis), s.grid, block, s.lds, stream, a);
     }
     // a seed set (a seeded plan: gain-only): one record per seed
-    rt::SeedsKArg a;
-    memset(&a, 0, sizeof(a));
-    a.hot         = fa.hot;
-    a.hot.image   = nullptr; // never touched: there is no cube
+    rt::SeedsKArg a = pass_args<rt::SeedsKArg>(fa);
     a.hot.seed_fk = nullptr; // (the creation seed is not part of the set)
-    a.cold        = fa.cold;
     a.set.n_seed  = f.n_seed;
     for (int i = 0; i < f.n_seed; i++) {
         double *blk   = p->seeds_dev + (size_t) i * p->seeds_stride;
@@ -554,9 +552,7 @@ static int launch_one(rt_hip_plan *p, const RunFacts &f, const RunShape &s, cons
         rt::FusedStepKArg sa;
         memset(&sa, 0, sizeof(sa));
         sa.P           = P;
-        sa.S.hot       = fa.hot;
-        sa.S.hot.image = nullptr; // never touched: there is no cube
-        sa.S.cold      = fa.cold;
+        sa.S           = pass_args<rt::StepKArg>(fa);
         sa.S.out       = p->step;
         sa.tile_next   = p->tile_next;
         sa.lay         = s.lay;

@@ -415,17 +415,14 @@ inline PassShape pass_shape(PassKind kind, const RunFacts &f, const Tuning &t)
         // spectra, step, step of a seed set or of a length scan: one 16-wave work-group per CU
         s.wg_waves = rt::FREQ_WG_WAVES;
         // (a seed set keeps one I_ang histogram and one E_v accumulator per seed, a length scan one of each per length)
-        auto seeds_lds = [&](bool in_lds) {
-            return (kind == PASS_SCAN ? rt::step_scan_lds_doubles(in_lds, (int) f.n_iang, f.Kp, s.wg_waves, f.L)
-                                      : rt::step_seeds_lds_doubles(in_lds, (int) f.n_iang, f.Kp, s.wg_waves, f.n_seed)) * sizeof(double);
-        };
+        const int n_rec      = kind == PASS_SCAN ? f.L : kind == PASS_SEEDS ? f.n_seed : 1;
+        const int ang_stride = kind == PASS_STEP ? rt::step_ang_stride((int) f.n_iang) : rt::seeds_ang_stride((int) f.n_iang);
+        auto step_lds        = [&](bool in_lds) { return rt::step_lds_doubles(in_lds, ang_stride, f.Kp, s.wg_waves, n_rec) * sizeof(double); };
         // (spectra: the staging rows of 16 waves and the exponent tables take 148 KB of LDS)
-        s.lds = kind == PASS_SPEC ? ((size_t) 2 * rt::EXP_TAB + (size_t) s.wg_waves * rt::WAVE * rt::XS_ROW) * sizeof(double)
-              : kind == PASS_STEP ? rt::step_lds_doubles(s.in_lds, (int) f.n_iang, f.Kp, s.wg_waves) * sizeof(double)
-                                  : seeds_lds(s.in_lds);
+        s.lds = kind == PASS_SPEC ? ((size_t) 2 * rt::EXP_TAB + (size_t) s.wg_waves * rt::WAVE * rt::XS_ROW) * sizeof(double) : step_lds(s.in_lds);
         if ((kind == PASS_SEEDS || kind == PASS_SCAN) && s.in_lds && s.lds > f.lds_limit) { // one histogram per seed (length) does not fit: global atomics
             s.in_lds = false;
-            s.lds    = seeds_lds(false);
+            s.lds    = step_lds(false);
         }
         s.grid = one_wg_per_cu(f.n_tiles, (unsigned) s.wg_waves, f.cu_count);
     }

@@ -29,8 +29,10 @@
 // frequency batch the walk over the slots starts at slot 0: the slots below the chunk are integrated again without
 // depositing, 3 LCH (c - 1) of them for chunk c.  Whenever the walk
 // reaches a length (slot 3 j - 1) the kernel finishes Iv_j (gain-only: one exp_tab_vec), updates the length's sum over k
-// and its sign / NaN test, and adds the E_v wave sum of rt_tile_step.inc to the length's accumulator in LDS; at the end of
-// the chunk, per length, the I_ang add and the segmented nf scan.
+// and its sign / NaN test, and adds the E_v wave sum (rt_step_evsum.inc) to the length's accumulator in LDS; at the end of
+// the chunk, per length, the I_ang add and the segmented nf scan (rt_wave_runs.inc, rt_wave_runscan.inc).  The kernel's
+// shell -- LDS, prologue, epilogue, tile hand-out -- is the text rt_step_kernel includes (rt_step_wg.inc,
+// rt_step_handout.inc), the grid-point seed factor the macro of place_ray (RT_SEED_GRID_FACTOR, rt_freq.hip).
 //
 // Failures follow the reference run once per length: error -1 at length j sets bit 1 of that length's code and keeps the
 // ray out of record j; error -2 / -3 at length j removes the ray from record j only.  A ray that fails at any length is
@@ -57,12 +59,6 @@ struct ScanKArg {
     ScanArg scan;
 };
 typedef const RT_CONST_AS ScanArg *ScanPtr;
-
-// doubles of dynamic LDS of a work-group: the layout of rt_step_seeds_kernel with one histogram and one E_v accumulator per length
-inline size_t step_scan_lds_doubles(bool iang_in_lds, int n_ang, int Kp, int wg_waves, int L)
-{
-    return step_seeds_lds_doubles(iang_in_lds, n_ang, Kp, wg_waves, L);
-}
 
 // seed_factor (rt_math.h), statement by statement, with pchip_eval held to a call as the other kernels have it: inlined
 // four times into this kernel it left the gain-only instance a 48-byte stack frame (that nothing read)
@@ -127,14 +123,9 @@ __device__ __forceinline__ void step_scan_tile(const FreqHot &H, const unsigned 
             const DevSeed SD = load_cold(&C->seed);
             f0_launch        = scan_seed_factor(SD, (double) launch.x, (double) launch.y, (double) launch.a, (double) launch.b);
         } else {
-            // the launch ray is a grid point: product of the tabulated factors, in seed_factor's order
-            unsigned gi, gj, gk, gm;
-            grid_index(R, ridx, gi, gj, gk, gm);
-            const unsigned oj = (unsigned) R.ngx, ok = oj + (unsigned) R.ngy, om = ok + (unsigned) R.nga;
-            if (R.sin[gi] & R.sin[oj + gj] & R.sin[ok + gk] & R.sin[om + gm]) {
-                f0_launch = C->seed.f0 * R.sf[gi] * R.sf[oj + gj] * R.sf[ok + gk] * R.sf[om + gm];
-                f0_launch = f0_launch < 0.0 ? 0.0 : f0_launch;
-            }
+            // the launch ray is a grid point: product of the tabulated factors (RT_SEED_GRID_FACTOR)
+            RT_SEED_GRID_POINT(R, ridx)
+            RT_SEED_GRID_FACTOR(f0_launch, C->seed.f0, R.sf, R.sin)
         }
     }
 
@@ -283,21 +274,13 @@ __device__ __forceinline__ void step_scan_tile(const FreqHot &H, const unsigned 
                         angsum[li] += dv2[kb + v] * Iv[v]; // RayTraceImageCPU.cpp:66: (2.0 * dv) * Iv
                     }
                     if (!safe_check) { // the checking pass of a failing run integrates without depositing
-                        // E_v of this length: the wave sum of rt_tile_step.inc over the lanes that deposit at this length
+                        // E_v of this length: the wave sum over the lanes that deposit at this length, into the length's accumulator
                         const bool dep = pix[li] >= 0;
-#pragma unroll
-                        for (int v = 0; v < VEC; v++)
-                            xpose[v * XP_ROW + lane] = dep ? Iv[v] : 0.0;
-                        __builtin_amdgcn_wave_barrier();
-                        const double *src = xpose + (lane >> 4) * XP_ROW + 4 * (lane & 15);
-                        double t2         = (src[0] + src[1]) + (src[2] + src[3]);
-                        __builtin_amdgcn_wave_barrier();
-                        t2 = dpp_step<0x111, 0xf>(t2);
-                        t2 = dpp_step<0x112, 0xf>(t2);
-                        t2 = dpp_step<0x114, 0xf>(t2);
-                        t2 = dpp_step<0x118, 0xf>(t2);
-                        if ((lane & 15) == 15 && t2 != 0.0) // (kb + 3 < Kp: every accumulator has Kp entries)
-                            unsafeAtomicAdd(&lds_ev[(j0 + li) * Kp + kb + (lane >> 4)], t2 * H.scale); // RayTraceImageCPU.cpp:59
+#define EV_SUM_DEPOSITS dep
+#define EV_SUM_INDEX (j0 + li) * Kp + kb
+#include "rt_step_evsum.inc"
+#undef EV_SUM_DEPOSITS
+#undef EV_SUM_INDEX
                     }
                 }
             }
@@ -324,27 +307,16 @@ __device__ __forceinline__ void step_scan_tile(const FreqHot &H, const unsigned 
                         else
                             unsafeAtomicAdd(&blk[Q->ang_off + (unsigned) ang[li]], angsum[li]);
                     }
-                    // nf: the segmented scan of rt_tile_step.inc over the runs of equal pixel AT THIS LENGTH
-                    const int px       = pix[li];
-                    const bool dep     = px >= 0;
-                    const int pix_prev = __shfl_up(px, 1, WAVE);
-                    const bool head    = lane == 0 || pix_prev != px;
-                    int run_start      = head ? lane : -1;
-#pragma unroll
-                    for (int o = 1; o < WAVE; o <<= 1) {
-                        const int t2 = __shfl_up(run_start, o, WAVE);
-                        if (lane >= o && t2 > run_start)
-                            run_start = t2;
-                    }
-                    const int head_next = __shfl_down(head ? 1 : 0, 1, WAVE);
-                    const bool tail     = (lane == WAVE - 1 || head_next != 0) && dep;
-                    double a            = (dep && !failing) ? angsum[li] * H.scale : 0.0;
-#pragma unroll
-                    for (int i = 0; i < 6; i++) {
-                        const double t2 = __shfl_up(a, 1 << i, WAVE);
-                        if ((lane - (1 << i)) >= run_start)
-                            a += t2;
-                    }
+                    // nf: the segmented scan over the runs of equal pixel AT THIS LENGTH (rt_wave_runs.inc, rt_wave_runscan.inc)
+                    const int px   = pix[li];
+                    const bool dep = px >= 0;
+#define RUNS_PIX px
+#define RUNS_DEPOSITS dep
+#include "rt_wave_runs.inc"
+#undef RUNS_PIX
+#undef RUNS_DEPOSITS
+                    double a = (dep && !failing) ? angsum[li] * H.scale : 0.0;
+#include "rt_wave_runscan.inc"
                     if (tail && a != 0.0)
                         unsafeAtomicAdd(&blk[Q->nf_off + (unsigned) px], a);
                 }
@@ -358,87 +330,44 @@ __device__ __forceinline__ void step_scan_tile(const FreqHot &H, const unsigned 
     }
 }
 
-// One work-group of FREQ_WG_WAVES waves per CU, tiles handed out as rt_step_kernel hands them out.  LDS of a work-group,
-// all dynamic (pass_shape sizes it with step_scan_lds_doubles):
-//   [the two exponent tables][per length: I_ang histogram, seeds_ang_stride(na*nb) doubles (if they fit)]
-//   [per length: E_v accumulator, Kp doubles][per wave: the transposition rows [4][XP_ROW] of the wave sum]
+// The shell of rt_step_kernel (rt_step_wg.inc, rt_step_handout.inc) with one record per length: per length an I_ang
+// histogram, seeds_ang_stride(na*nb) doubles apart, and an E_v accumulator.
 template <bool EMIS>
 __global__ void __launch_bounds__(FREQ_WG_WAVES * 64, EMIS ? FREQ_WAVES : FREQ_WAVES_SEED) rt_step_scan_kernel(const ScanKArg A)
 {
-    extern __shared__ __align__(16) unsigned char step_scan_lds[];
-    const FreqHot &H       = A.hot;
-    const bool iang_in_lds = (H.flags & FQ_IANG_LDS) != 0;
-    const int n_ang        = H.n_ang;
-    const int L            = H.L;
-    const int ang_stride   = seeds_ang_stride(n_ang);
-    double *exp2_tab       = reinterpret_cast<double *>(step_scan_lds);
-    double *lds_iang       = iang_in_lds ? exp2_tab + 2 * EXP_TAB : nullptr;
-    double *lds_ev         = exp2_tab + 2 * EXP_TAB + (iang_in_lds ? L * ang_stride : 0);
-    double *xpose          = lds_ev + L * H.Kp + (size_t) (unsigned) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6)) * (size_t) (4 * XP_ROW);
-    RT_FILL_EXP_TABLES(exp2_tab)
-    if (lds_iang) {
-        for (int c = (int) threadIdx.x; c < L * ang_stride; c += (int) blockDim.x)
-            lds_iang[c] = 0.0;
-    }
-    for (int c = (int) threadIdx.x; c < L * H.Kp; c += (int) blockDim.x)
-        lds_ev[c] = 0.0;
-    __syncthreads();
-    const int lane             = lane_id();
-    const unsigned n_tiles_run = H.tile_end - H.tile_begin;
-    unsigned shard = blockIdx.x & 7u, tried = 0;
-    auto shard_size = [&](unsigned sh) { return (n_tiles_run + 7u - sh) / 8u; };
-    unsigned s_n    = shard_size(shard);
-    const unsigned sh_shift = H.fetch_shift > 3 ? H.fetch_shift - 3 : 0;
-    constexpr unsigned TILES_PER_FETCH = EMIS ? FREQ_TILES_PER_FETCH_EMIS : FREQ_TILES_PER_FETCH_GAIN;
-    auto chunk_of = [&](unsigned left) {
-        const unsigned c = left >> sh_shift;
-        return c < 1u ? 1u : (c > TILES_PER_FETCH ? TILES_PER_FETCH : c);
-    };
-    unsigned tch = chunk_of(s_n);
-    for (;;) {
-        unsigned base = 0;
-        if (lane == 0)
-            base = atomicAdd(&H.ctl->next_tile_f[H.freq_id][shard][0], tch);
-        base = (unsigned) __builtin_amdgcn_readfirstlane((int) base);
-        if (base >= s_n) { // this shard is empty: on to the next one, until all eight have been seen empty
-            if (++tried == 8)
-                break;
-            shard = (shard + 1) & 7u;
-            s_n   = shard_size(shard);
-            tch   = 1; // a guest takes single tiles
-            continue;
-        }
-        const unsigned t_end = s_n - base < tch ? s_n : base + tch;
-        tch                  = chunk_of(s_n - t_end);
-        for (unsigned t = base; t < t_end; t++) {
-            const unsigned tile = H.tile_begin + t * 8u + shard;
-            // the cold half and the scan block of the argument block, the flag word and the lane number opaque per tile
-            ColdPtr C = (ColdPtr) ((const RT_CONST_AS char *) __builtin_amdgcn_kernarg_segment_ptr() + offsetof(ScanKArg, cold));
-            ScanPtr Q = (ScanPtr) ((const RT_CONST_AS char *) __builtin_amdgcn_kernarg_segment_ptr() + offsetof(ScanKArg, scan));
-            asm volatile("" : "+s"(C), "+s"(Q));
-            unsigned hflags = H.flags;
-            int lane_t      = lane;
-            asm volatile("" : "+s"(hflags), "+v"(lane_t));
-            step_scan_tile<EMIS>(H, hflags, C, Q, lds_iang, lds_ev, exp2_tab, xpose, tile, lane_t);
-        }
-    }
-    // the work-group's sums leave once, per length: coalesced native f64 atomics (zeros stay)
-    __syncthreads();
-    for (int j = 0; j < L; j++) {
-        double *blk = A.scan.out + (size_t) j * (size_t) A.scan.stride;
-        for (int c = (int) threadIdx.x; c < H.K; c += (int) blockDim.x) {
-            const double v = lds_ev[j * H.Kp + c];
-            if (v != 0.0)
-                unsafeAtomicAdd(&blk[c], v);
-        }
-        if (lds_iang && !(H.flags & FQ_DBG_NOFLUSH)) {
-            for (int c = (int) threadIdx.x; c < n_ang; c += (int) blockDim.x) {
-                const double v = lds_iang[j * ang_stride + c];
-                if (v != 0.0)
-                    unsafeAtomicAdd(&blk[A.scan.ang_off + c], v);
-            }
-        }
-    }
+    const FreqHot &H = A.hot;
+#define STEP_WG_NREC H.L
+#define STEP_WG_ANG_STRIDE seeds_ang_stride(n_ang)
+#define STEP_WG_ANG_ZERO n_rec * ang_stride
+#define STEP_WG_RECORD(r) double *blk = A.scan.out + (size_t) r * (size_t) A.scan.stride;
+#define STEP_WG_EV(r, c) blk[c]
+#define STEP_WG_IANG(r, c) blk[A.scan.ang_off + c]
+#define STEP_WG_PROLOGUE
+#include "rt_step_wg.inc"
+#undef STEP_WG_PROLOGUE
+    const int lane = lane_id();
+    // the cold half and the scan block of the argument block, the flag word and the lane number opaque per tile
+#define HANDOUT_TILES_PER_FETCH (EMIS ? FREQ_TILES_PER_FETCH_EMIS : FREQ_TILES_PER_FETCH_GAIN)
+#define HANDOUT_TILE                                                                                                                   \
+    ColdPtr C = (ColdPtr) ((const RT_CONST_AS char *) __builtin_amdgcn_kernarg_segment_ptr() + offsetof(ScanKArg, cold));            \
+    ScanPtr Q = (ScanPtr) ((const RT_CONST_AS char *) __builtin_amdgcn_kernarg_segment_ptr() + offsetof(ScanKArg, scan));             \
+    asm volatile("" : "+s"(C), "+s"(Q));                                                                                               \
+    unsigned hflags = H.flags;                                                                                                         \
+    int lane_t      = lane;                                                                                                            \
+    asm volatile("" : "+s"(hflags), "+v"(lane_t));                                                                                     \
+    step_scan_tile<EMIS>(H, hflags, C, Q, lds_iang, lds_ev, exp2_tab, xpose, tile, lane_t);
+#include "rt_step_handout.inc"
+#undef HANDOUT_TILES_PER_FETCH
+#undef HANDOUT_TILE
+#define STEP_WG_EPILOGUE
+#include "rt_step_wg.inc"
+#undef STEP_WG_EPILOGUE
+#undef STEP_WG_NREC
+#undef STEP_WG_ANG_STRIDE
+#undef STEP_WG_ANG_ZERO
+#undef STEP_WG_RECORD
+#undef STEP_WG_EV
+#undef STEP_WG_IANG
 }
 
 } // namespace rt

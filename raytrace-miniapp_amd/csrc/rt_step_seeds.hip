@@ -13,8 +13,11 @@
 // the seed's tabulated factors with the clamp, otherwise seed_factor on the seed's DevSeed.  Per frequency batch: gl[] and
 // exp_tab_vec once (needed if any seed's f0 != 0, or gl > 700, or gl is a NaN), then per seed in turn
 // Iv_s[j] = (f0_s sfk_s[kb + j]) eg[j] -- the double rt_step_kernel computes for that seed, in its association -- the lane's
-// sums and the E_v wave sum into the seed's accumulator in LDS; only f0_s, angsum_s and iv_min_s are live per seed.
-// Per tile end and seed: the I_ang add and the segmented nf scan of rt_step.hip (the runs of equal pixel are found once).
+// sums and the E_v wave sum (rt_step_evsum.inc) into the seed's accumulator in LDS; only f0_s, angsum_s and iv_min_s are
+// live per seed.  Per tile end and seed: the I_ang add and the segmented nf scan (rt_wave_runscan.inc over the runs of equal
+// pixel, which rt_wave_runs.inc finds once).  The kernel's shell -- LDS, prologue, epilogue, tile hand-out -- is the text
+// rt_step_kernel includes (rt_step_wg.inc, rt_step_handout.inc), the grid-point seed factor the macro place_ray expands
+// (RT_SEED_GRID_FACTOR, rt_freq.hip).
 //
 // Failures follow the reference run once per seed: error -1 does not depend on the seed (the ray deposits into no record,
 // every seed's code carries the bit); error -2 / -3 under seed s removes the ray from record s only
@@ -48,15 +51,6 @@ struct SeedsKArg {
     SeedSetArg set;
 };
 typedef const RT_CONST_AS SeedSetArg *SetPtr;
-
-// doubles from one seed's I_ang histogram in LDS to the next: na * nb and two cells to spare (on an axis of one grid point
-// the angle cell of a ray can be one past the grid, see rt_hip_plan_run; such a cell must not be the next seed's), even
-__host__ __device__ constexpr int seeds_ang_stride(int n_ang) { return (n_ang + 3) & ~1; }
-// doubles of dynamic LDS of a work-group (layout: rt_step_seeds_kernel)
-inline size_t step_seeds_lds_doubles(bool iang_in_lds, int n_ang, int Kp, int wg_waves, int n_seed)
-{
-    return (size_t) 2 * EXP_TAB + (size_t) n_seed * ((iang_in_lds ? (size_t) seeds_ang_stride(n_ang) : 0) + (size_t) Kp) + (size_t) wg_waves * (size_t) (4 * XP_ROW);
-}
 
 template <int SF>
 __device__ __forceinline__ void step_seeds_tile(const FreqHot &H, const unsigned hflags, ColdPtr C, SetPtr Q, const int n_seed, double *lds_iang,
@@ -105,19 +99,14 @@ __device__ __forceinline__ void step_seeds_tile(const FreqHot &H, const unsigned
                     }
                 }
             } else {
-                // the launch ray is a grid point: product of the seed's tabulated factors, in seed_factor's order
-                unsigned gi, gj, gk, gm;
-                grid_index(R, ridx, gi, gj, gk, gm);
-                const unsigned oj = (unsigned) R.ngx, ok = oj + (unsigned) R.ngy, om = ok + (unsigned) R.nga;
+                // the launch ray is a grid point: product of the seed's tabulated factors (RT_SEED_GRID_FACTOR)
+                RT_SEED_GRID_POINT(R, ridx)
 #pragma unroll
                 for (int s = 0; s < NS; s++) {
                     if (s < n_seed) {
                         const double *sf         = Q->sf[s];
                         const unsigned char *sin = Q->sin[s];
-                        if (sin[gi] & sin[oj + gj] & sin[ok + gk] & sin[om + gm]) {
-                            const double v = Q->seed[s].f0 * sf[gi] * sf[oj + gj] * sf[ok + gk] * sf[om + gm];
-                            f0[s]          = v < 0.0 ? 0.0 : v;
-                        }
+                        RT_SEED_GRID_FACTOR(f0[s], Q->seed[s].f0, sf, sin)
                     }
                 }
             }
@@ -222,21 +211,13 @@ __device__ __forceinline__ void step_seeds_tile(const FreqHot &H, const unsigned
                     angsum[s] += dv2[kb + j] * Iv[j]; // RayTraceImageCPU.cpp:66: (2.0 * dv) * Iv
                 }
                 if (!safe_check) { // the checking pass of a failing run integrates without depositing
-                    // E_v of seed s: the wave sum of rt_step.hip over the lanes that deposit under this seed
+                    // E_v of seed s: the wave sum over the lanes that deposit under this seed, into the seed's accumulator
                     const bool dep_s = dep && !((marked >> s) & 1u);
-#pragma unroll
-                    for (int j = 0; j < VEC; j++)
-                        xpose[j * XP_ROW + lane] = dep_s ? Iv[j] : 0.0;
-                    __builtin_amdgcn_wave_barrier();
-                    const double *src = xpose + (lane >> 4) * XP_ROW + 4 * (lane & 15);
-                    double t          = (src[0] + src[1]) + (src[2] + src[3]);
-                    __builtin_amdgcn_wave_barrier();
-                    t = dpp_step<0x111, 0xf>(t);
-                    t = dpp_step<0x112, 0xf>(t);
-                    t = dpp_step<0x114, 0xf>(t);
-                    t = dpp_step<0x118, 0xf>(t);
-                    if ((lane & 15) == 15 && t != 0.0) // (kb + 3 < Kp: every accumulator has Kp entries)
-                        unsafeAtomicAdd(&lds_ev[s * Kp + kb + (lane >> 4)], t * H.scale); // RayTraceImageCPU.cpp:59, once per summed value
+#define EV_SUM_DEPOSITS dep_s
+#define EV_SUM_INDEX s * Kp + kb
+#include "rt_step_evsum.inc"
+#undef EV_SUM_DEPOSITS
+#undef EV_SUM_INDEX
                 }
             }
         }
@@ -264,18 +245,12 @@ __device__ __forceinline__ void step_seeds_tile(const FreqHot &H, const unsigned
     }
     if (safe_check)
         return;
-    // runs of lanes with equal pixel, found once: the segmented scan of rt_step.hip; the last lane of a run owns the total
-    const int pix_prev = __shfl_up(pix, 1, WAVE);
-    const bool head    = lane == 0 || pix_prev != pix;
-    int run_start      = head ? lane : -1;
-#pragma unroll
-    for (int o = 1; o < WAVE; o <<= 1) {
-        const int t = __shfl_up(run_start, o, WAVE);
-        if (lane >= o && t > run_start)
-            run_start = t;
-    }
-    const int head_next = __shfl_down(head ? 1 : 0, 1, WAVE);
-    const bool tail     = (lane == WAVE - 1 || head_next != 0) && dep;
+    // runs of lanes with equal pixel, found once for all seeds (rt_wave_runs.inc); the last lane of a run owns the total
+#define RUNS_PIX pix
+#define RUNS_DEPOSITS dep
+#include "rt_wave_runs.inc"
+#undef RUNS_PIX
+#undef RUNS_DEPOSITS
 #pragma unroll
     for (int s = 0; s < NS; s++) {
         if (s < n_seed) {
@@ -288,97 +263,51 @@ __device__ __forceinline__ void step_seeds_tile(const FreqHot &H, const unsigned
                     unsafeAtomicAdd(&Q->out[s].iang[ang], angsum[s]);
             }
             double a = (dep && ok) ? angsum[s] * H.scale : 0.0;
-#pragma unroll
-            for (int i = 0; i < 6; i++) {
-                const double t = __shfl_up(a, 1 << i, WAVE);
-                if ((lane - (1 << i)) >= run_start)
-                    a += t;
-            }
+#include "rt_wave_runscan.inc"
             if (tail && a != 0.0)
                 unsafeAtomicAdd(&Q->out[s].nf[pix], a);
         }
     }
 }
 
-// One work-group of FREQ_WG_WAVES waves per CU, tiles handed out as rt_step_kernel hands them out.  LDS of a work-group,
-// all dynamic (launch_step_seeds sizes it with step_seeds_lds_doubles):
-//   [the two exponent tables][per seed: I_ang histogram, seeds_ang_stride(na*nb) doubles (if they fit)]
-//   [per seed: E_v accumulator, Kp doubles][per wave: the transposition rows [4][XP_ROW] of the wave sum]
+// The shell of rt_step_kernel (rt_step_wg.inc, rt_step_handout.inc) with one record per seed: per seed an I_ang histogram,
+// seeds_ang_stride(na*nb) doubles apart, and an E_v accumulator.
 template <int SF>
 __global__ void __launch_bounds__(FREQ_WG_WAVES * 64, FREQ_WAVES_SEED) rt_step_seeds_kernel(const SeedsKArg A)
 {
-    extern __shared__ __align__(16) unsigned char step_seeds_lds[];
-    const FreqHot &H       = A.hot;
-    const bool iang_in_lds = (H.flags & FQ_IANG_LDS) != 0;
-    const int n_ang        = H.n_ang;
-    const int n_seed       = A.set.n_seed;
-    const int ang_stride   = seeds_ang_stride(n_ang);
-    double *exp2_tab       = reinterpret_cast<double *>(step_seeds_lds);
-    double *lds_iang       = iang_in_lds ? exp2_tab + 2 * EXP_TAB : nullptr;
-    double *lds_ev         = exp2_tab + 2 * EXP_TAB + (iang_in_lds ? n_seed * ang_stride : 0);
-    double *xpose          = lds_ev + n_seed * H.Kp + (size_t) (unsigned) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6)) * (size_t) (4 * XP_ROW);
-    RT_FILL_EXP_TABLES(exp2_tab)
-    if (lds_iang) {
-        for (int c = (int) threadIdx.x; c < n_seed * ang_stride; c += (int) blockDim.x)
-            lds_iang[c] = 0.0;
-    }
-    for (int c = (int) threadIdx.x; c < n_seed * H.Kp; c += (int) blockDim.x)
-        lds_ev[c] = 0.0;
-    __syncthreads();
-    const int lane             = lane_id();
-    const unsigned n_tiles_run = H.tile_end - H.tile_begin;
-    unsigned shard = blockIdx.x & 7u, tried = 0;
-    auto shard_size = [&](unsigned sh) { return (n_tiles_run + 7u - sh) / 8u; };
-    unsigned s_n    = shard_size(shard);
-    const unsigned sh_shift = H.fetch_shift > 3 ? H.fetch_shift - 3 : 0;
-    auto chunk_of = [&](unsigned left) {
-        const unsigned c = left >> sh_shift;
-        return c < 1u ? 1u : (c > FREQ_TILES_PER_FETCH_GAIN ? FREQ_TILES_PER_FETCH_GAIN : c);
-    };
-    unsigned tch = chunk_of(s_n);
-    for (;;) {
-        unsigned base = 0;
-        if (lane == 0)
-            base = atomicAdd(&H.ctl->next_tile_f[H.freq_id][shard][0], tch);
-        base = (unsigned) __builtin_amdgcn_readfirstlane((int) base);
-        if (base >= s_n) { // this shard is empty: on to the next one, until all eight have been seen empty
-            if (++tried == 8)
-                break;
-            shard = (shard + 1) & 7u;
-            s_n   = shard_size(shard);
-            tch   = 1; // a guest takes single tiles
-            continue;
-        }
-        const unsigned t_end = s_n - base < tch ? s_n : base + tch;
-        tch                  = chunk_of(s_n - t_end);
-        for (unsigned t = base; t < t_end; t++) {
-            const unsigned tile = H.tile_begin + t * 8u + shard;
-            // the cold half and the seed set of the argument block, the flag word and the lane number opaque per tile
-            ColdPtr C = (ColdPtr) ((const RT_CONST_AS char *) __builtin_amdgcn_kernarg_segment_ptr() + offsetof(SeedsKArg, cold));
-            SetPtr Q  = (SetPtr) ((const RT_CONST_AS char *) __builtin_amdgcn_kernarg_segment_ptr() + offsetof(SeedsKArg, set));
-            asm volatile("" : "+s"(C), "+s"(Q));
-            unsigned hflags = H.flags;
-            int lane_t      = lane;
-            asm volatile("" : "+s"(hflags), "+v"(lane_t));
-            step_seeds_tile<SF>(H, hflags, C, Q, n_seed, lds_iang, lds_ev, exp2_tab, xpose, tile, lane_t);
-        }
-    }
-    // the work-group's sums leave once, per seed: coalesced native f64 atomics (zeros stay)
-    __syncthreads();
-    for (int s = 0; s < n_seed; s++) {
-        for (int c = (int) threadIdx.x; c < H.K; c += (int) blockDim.x) {
-            const double v = lds_ev[s * H.Kp + c];
-            if (v != 0.0)
-                unsafeAtomicAdd(&A.set.out[s].E_v[c], v);
-        }
-        if (lds_iang && !(H.flags & FQ_DBG_NOFLUSH)) {
-            for (int c = (int) threadIdx.x; c < n_ang; c += (int) blockDim.x) {
-                const double v = lds_iang[s * ang_stride + c];
-                if (v != 0.0)
-                    unsafeAtomicAdd(&A.set.out[s].iang[c], v);
-            }
-        }
-    }
+    const FreqHot &H = A.hot;
+#define STEP_WG_NREC A.set.n_seed
+#define STEP_WG_ANG_STRIDE seeds_ang_stride(n_ang)
+#define STEP_WG_ANG_ZERO n_rec * ang_stride
+#define STEP_WG_RECORD(r)
+#define STEP_WG_EV(r, c) A.set.out[r].E_v[c]
+#define STEP_WG_IANG(r, c) A.set.out[r].iang[c]
+#define STEP_WG_PROLOGUE
+#include "rt_step_wg.inc"
+#undef STEP_WG_PROLOGUE
+    const int lane = lane_id();
+    // the cold half and the seed set of the argument block, the flag word and the lane number opaque per tile
+#define HANDOUT_TILES_PER_FETCH FREQ_TILES_PER_FETCH_GAIN
+#define HANDOUT_TILE                                                                                                                   \
+    ColdPtr C = (ColdPtr) ((const RT_CONST_AS char *) __builtin_amdgcn_kernarg_segment_ptr() + offsetof(SeedsKArg, cold));           \
+    SetPtr Q  = (SetPtr) ((const RT_CONST_AS char *) __builtin_amdgcn_kernarg_segment_ptr() + offsetof(SeedsKArg, set));              \
+    asm volatile("" : "+s"(C), "+s"(Q));                                                                                               \
+    unsigned hflags = H.flags;                                                                                                         \
+    int lane_t      = lane;                                                                                                            \
+    asm volatile("" : "+s"(hflags), "+v"(lane_t));                                                                                     \
+    step_seeds_tile<SF>(H, hflags, C, Q, n_rec, lds_iang, lds_ev, exp2_tab, xpose, tile, lane_t);
+#include "rt_step_handout.inc"
+#undef HANDOUT_TILES_PER_FETCH
+#undef HANDOUT_TILE
+#define STEP_WG_EPILOGUE
+#include "rt_step_wg.inc"
+#undef STEP_WG_EPILOGUE
+#undef STEP_WG_NREC
+#undef STEP_WG_ANG_STRIDE
+#undef STEP_WG_ANG_ZERO
+#undef STEP_WG_RECORD
+#undef STEP_WG_EV
+#undef STEP_WG_IANG
 }
 
 } // namespace rt

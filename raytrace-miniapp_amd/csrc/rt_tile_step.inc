@@ -82,22 +82,12 @@ for (int kb = TILE_K0; kb < TILE_K_END; kb += VEC) {
         angsum += dv2[kb + j] * Iv[j]; // RayTraceImageCPU.cpp:66: (2.0 * dv) * Iv
     }
     if (!safe_check) { // the checking pass of a failing run integrates without depositing
-        // E_v: the wave sum of the few-runs deposit (rt_freq.hip) over the depositing lanes -- the lanes park their
-        // four values in [4][XP_ROW], lane (j, q) = (lane / 16, lane % 16) adds four neighbours of frequency j, a
-        // row_shr tree finishes the sum in lane 15 of the row; one LDS atomic per frequency and tile
-#pragma unroll
-        for (int j = 0; j < VEC; j++)
-            xpose[j * XP_ROW + lane] = dep ? Iv[j] : 0.0;
-        __builtin_amdgcn_wave_barrier();
-        const double *src = xpose + (lane >> 4) * XP_ROW + 4 * (lane & 15);
-        double t          = (src[0] + src[1]) + (src[2] + src[3]);
-        __builtin_amdgcn_wave_barrier();
-        t = dpp_step<0x111, 0xf>(t);
-        t = dpp_step<0x112, 0xf>(t);
-        t = dpp_step<0x114, 0xf>(t);
-        t = dpp_step<0x118, 0xf>(t);
-        if ((lane & 15) == 15 && t != 0.0) // (kb + 3 < Kp: the accumulator has Kp entries)
-            unsafeAtomicAdd(&lds_ev[kb + (lane >> 4)], t * H.scale); // RayTraceImageCPU.cpp:59, once per summed value
+        // E_v: the wave sum over the depositing lanes into the one accumulator
+#define EV_SUM_DEPOSITS dep
+#define EV_SUM_INDEX kb
+#include "rt_step_evsum.inc"
+#undef EV_SUM_DEPOSITS
+#undef EV_SUM_INDEX
     }
 }
 // a NaN intensity makes the I_ang sum NaN (Helper.h:590-593: error -3, after the sign test)
@@ -118,27 +108,17 @@ if (ang >= 0 && !failing) {
         unsafeAtomicAdd(&H.iang[ang], angsum);
 }
 // nf: the same per-ray sum, scaled, summed over each run of lanes with equal pixel (the segmented scan of the
-// seeded deposit, once per tile instead of once per frequency); the last lane of a run owns the total
+// seeded deposit, once per tile instead of once per frequency: rt_wave_runs.inc, rt_wave_runscan.inc); the last lane of a
+// run owns the total
 {
     const double mine  = (dep && !failing) ? angsum * H.scale : 0.0;
-    const int pix_prev = __shfl_up(pix, 1, WAVE);
-    const bool head    = lane == 0 || pix_prev != pix;
-    int run_start      = head ? lane : -1;
-#pragma unroll
-    for (int o = 1; o < WAVE; o <<= 1) {
-        const int t = __shfl_up(run_start, o, WAVE);
-        if (lane >= o && t > run_start)
-            run_start = t;
-    }
-    const int head_next = __shfl_down(head ? 1 : 0, 1, WAVE);
-    const bool tail     = (lane == WAVE - 1 || head_next != 0) && dep;
-    double a            = mine;
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        const double t = __shfl_up(a, 1 << i, WAVE);
-        if ((lane - (1 << i)) >= run_start)
-            a += t;
-    }
+#define RUNS_PIX pix
+#define RUNS_DEPOSITS dep
+#include "rt_wave_runs.inc"
+#undef RUNS_PIX
+#undef RUNS_DEPOSITS
+    double a = mine;
+#include "rt_wave_runscan.inc"
     if (tail) {
         // (the output pointer is read from the argument block here, behind the cold half, rather than kept across the tile)
         double *nf_out = reinterpret_cast<const RT_CONST_AS StepOut *>(reinterpret_cast<const RT_CONST_AS char *>(C) + (offsetof(StepKArg, out) - offsetof(StepKArg, cold)))->nf;

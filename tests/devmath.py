@@ -3,7 +3,8 @@
   Ref      tests/devmath_ref.c compiled with the host `cc -O2 -ffp-contract=off`: the restatement of exp_tab, exp_tab_vec,
            ase_step, ase_step_f32 and ase_update (tables handed in), and loops over the host libm's tanf / atanf
   Device   ctypes binding of csrc/librt_hip_devmath.so (rt_devmath.hip): the same functions on a device, and the seed-profile
-           interpolation (pchip, seed_factor, seed_tab: tests/test_gpu_seed_profiles.py).  Load it only
+           interpolation (pchip, seed_factor, seed_tab: tests/test_gpu_seed_profiles.py) and the two wave primitives of the
+           step deposit (ev_sum, nf_scan).  Load it only
            after the `hip` fixture of conftest.py has brought torch in -- one HIP runtime per process
   the high-precision reference: numpy.longdouble (>= 64 significand bits, asserted) exp / expm1, guarded by a cross-check
            of a 2 000-point subsample against mpmath (or the stdlib decimal module at 40 digits)
@@ -166,8 +167,11 @@ class Device:
         L.rt_devmath_pchip.argtypes = [ci, _PD, _PD, _PD, _PD, sz]
         L.rt_devmath_seed_factor.argtypes = [pi, ppd, ppd, ctypes.c_double, _PD, _PD, sz]
         L.rt_devmath_seed_tab.argtypes = [pi, ppd, ppd, ctypes.c_double, pi, ppd, ctypes.c_uint, _PD, ctypes.POINTER(ctypes.c_ubyte)]
+        L.rt_devmath_ev_sum.argtypes = [_PD, ctypes.POINTER(ctypes.c_ubyte), ctypes.c_double, ci, _PD]
+        L.rt_devmath_nf_scan.argtypes = [pi, _PD, ctypes.c_double, ci, _PD]
         for f in (L.rt_devmath_tables, L.rt_devmath_exp, L.rt_devmath_update, L.rt_devmath_step, L.rt_devmath_div,
-                  L.rt_devmath_deposit, L.rt_devmath_tan, L.rt_devmath_pchip, L.rt_devmath_seed_factor, L.rt_devmath_seed_tab):
+                  L.rt_devmath_deposit, L.rt_devmath_tan, L.rt_devmath_pchip, L.rt_devmath_seed_factor, L.rt_devmath_seed_tab,
+                  L.rt_devmath_ev_sum, L.rt_devmath_nf_scan):
             f.restype = ci
         assert L.rt_devmath_vec() == VEC
 
@@ -229,6 +233,29 @@ class Device:
         out = np.empty_like(x)
         self._check(self.lib.rt_devmath_tan(which, _ptr(x, ctypes.c_float), _ptr(out, ctypes.c_float), x.size), "rt_devmath_tan")
         return out
+
+    def ev_sum(self, Iv, deposits, scale):
+        """The E_v wave sum (csrc/rt_step_evsum.inc) on one work-group of four waves: Iv [4][64][Kp] (wave, lane, frequency),
+        deposits [4][64] bool -> the work-group's accumulator [Kp] = scale * sum of Iv over the depositing lanes."""
+        Iv = _f64(Iv)
+        deposits = np.ascontiguousarray(deposits, dtype=np.uint8)
+        assert Iv.ndim == 3 and Iv.shape[:2] == (4, 64) and deposits.shape == (4, 64)
+        out = np.empty(Iv.shape[2], np.float64)
+        self._check(self.lib.rt_devmath_ev_sum(_ptr(Iv, ctypes.c_double), _ptr(deposits, ctypes.c_ubyte), float(scale), Iv.shape[2],
+                                               _ptr(out, ctypes.c_double)), "rt_devmath_ev_sum")
+        return out
+
+    def nf_scan(self, pix, val, scale, n_pix):
+        """The segmented scan of the nf deposit (csrc/rt_wave_runs.inc, rt_wave_runscan.inc) on one work-group of four waves:
+        pix [4][64] (wave, lane; -1: the lane deposits nothing), val [4][64] -> nf [n_pix], nf[p] = scale * sum of val over the
+        lanes of pixel p."""
+        pix = np.ascontiguousarray(pix, dtype=np.int32)
+        val = _f64(val)
+        assert pix.shape == val.shape == (4, 64)
+        nf = np.empty(n_pix, np.float64)
+        self._check(self.lib.rt_devmath_nf_scan(_ptr(pix, ctypes.c_int), _ptr(val, ctypes.c_double), float(scale), n_pix,
+                                                _ptr(nf, ctypes.c_double)), "rt_devmath_nf_scan")
+        return nf
 
     def pchip(self, xs, ys, x):
         """pchip_eval (csrc/rt_math.h) of one axis xs, ys [n >= 2] at x [m]."""

@@ -18,6 +18,11 @@ What is asserted:
                 here against the plain bisection) on every input, and each other
   tan / atan    bit-equal to the host libm's tanf up to 1.375 rad / atanf below 0.4375; beyond, within 1 float ulp of the
                 correctly rounded value; libm's answers for +-inf and NaN
+  E_v wave sum  rt_step_evsum.inc on one work-group of four waves: the accumulator equals numpy's sum over the depositing
+                lanes, ==.  The inputs are integers up to 2^20 in doubles and the scale is a power of two, so every
+                association of the additions is exact and no tolerance is needed
+  nf scan       rt_wave_runs.inc / rt_wave_runscan.inc on one work-group of four waves: nf equals np.add.at over the lanes
+                that hold a pixel, ==, on the same kind of input
 
 Every test prints its worst figures and where they occur; with DEVMATH_PARITY_FILE set they are appended to that file
 (profiles/devmath_parity.txt is such a run on an MI355X).
@@ -286,3 +291,65 @@ def test_tanf_kernel(dev, ref):
 def test_atanf_kernel(dev, ref):
     x = di.atan_args()
     _float_kernel(dev, ref, D.ATAN, "atan", x, np.abs(x) < np.float32(0.4375), ref.host_atanf)
+
+
+# ------------------------------------------------------------------------------------------------------- the step deposit
+def _integers(rng, shape):
+    """doubles holding integers of magnitude <= 2^20: sums of 256 of them, times a power of two, are exact in any order"""
+    return rng.integers(-2 ** 20, 2 ** 20, size=shape, endpoint=True).astype(np.float64)
+
+
+EV_MASKS = {
+    "every lane": np.ones(64, bool),
+    "no lane": np.zeros(64, bool),
+    "alternating lanes": np.arange(64) % 2 == 0,
+    "only lane 0": np.arange(64) == 0,
+    "only lane 63": np.arange(64) == 63,
+}
+
+
+@pytest.mark.parametrize("case", list(EV_MASKS))
+def test_ev_wave_sum_is_the_sum_over_the_depositing_lanes(dev, case):
+    Kp, scale = 8, 2.0 ** -5          # two batches of VEC frequencies: the index of the accumulator entry moves
+    assert Kp == 2 * dm.VEC
+    rng = np.random.default_rng(11)
+    Iv = _integers(rng, (4, 64, Kp))
+    deposits = np.broadcast_to(EV_MASKS[case], (4, 64))
+    got = dev.ev_sum(Iv, deposits, scale)
+    want = scale * (Iv * deposits[:, :, None]).sum(axis=(0, 1))
+    dm.note(f"device E_v wave sum, {case}: {int(deposits.sum())} depositing lanes in four waves, {int((got != want).sum())} of {Kp} sums differ")
+    assert np.array_equal(got, want), (case, got, want)
+    if case == "no lane":
+        assert (got == 0.0).all() and not np.signbit(got).any()      # the accumulator stays as it was zeroed
+
+
+def _lanes(runs):
+    """(pixel, lanes) runs -> the 64 pixels of a wave"""
+    pix = np.concatenate([np.full(n, p) for p, n in runs])
+    assert pix.size == 64
+    return pix
+
+
+NF_PATTERNS = {
+    "one run of 64": [(5, 64)],
+    "64 runs of one": [(p, 1) for p in range(3, 67)],
+    "mixed runs": [(9, 1), (10, 2), (11, 3), (12, 5), (20, 8), (21, 13), (69, 32)],
+    "holes inside and at both ends": [(-1, 3), (4, 7), (-1, 1), (5, 2), (-1, 20), (6, 1), (7, 25), (-1, 5)],
+    "the same pixel in two runs": [(30, 10), (31, 4), (30, 17), (0, 1), (31, 32)],
+    "a run from lane 0, a run to lane 63": [(68, 31), (2, 2), (69, 31)],
+}
+
+
+@pytest.mark.parametrize("case", list(NF_PATTERNS))
+def test_nf_segmented_scan_equals_add_at(dev, case):
+    n_pix, scale = 70, 2.0 ** 3
+    base = _lanes(NF_PATTERNS[case])
+    # four waves: the pattern on other pixels (equal pixels stay equal, holes stay holes), so that waves meet in a pixel
+    pix = np.stack([np.where(base >= 0, (base + 17 * w) % n_pix, -1) for w in range(4)])
+    val = _integers(np.random.default_rng(13), (4, 64))
+    got = dev.nf_scan(pix, val, scale, n_pix)
+    want = np.zeros(n_pix)
+    hold = pix >= 0
+    np.add.at(want, pix[hold], val[hold] * scale)
+    dm.note(f"device nf scan, {case}: {int(hold.sum())} lanes with a pixel in four waves, {int((got != want).sum())} of {n_pix} pixels differ")
+    assert np.array_equal(got, want), (case, np.flatnonzero(got != want))
