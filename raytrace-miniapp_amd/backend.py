@@ -11,6 +11,7 @@ mirror of the reference's operator interface for this path.
   multi_step_loop(...)  step_loop on all devices of the node: strided ray grid per device, one sum-reduce of the record
   seed_step_loop(...)   the step records of up to RT_N_SEED_MAX seed beams from one march (Plan.set_seeds)
   length_scan_loop(...) the step record at every plasma length n = 2 .. N from one forward march (Plan.enable_length_scan)
+  seed_length_scan_loop(...) ... of up to RT_N_SEED_MAX seed beams at every length, from that one march (Plan.set_scan_seeds)
   step_outputs_from_image  their definition as reductions of a cube, in numpy (no device)
   calc_rays / calc_ray  RayTrace::calc_ray (src/RayTraceImage.cpp:189-204), batched: per-ray spectrum, exit ray, code
   create_image(p, method)
@@ -362,6 +363,8 @@ class Plan:
                 raise ValueError(f"enable_length_scan: N - 1 = {p.N - 1} lengths, at most RT_N_SCAN_MAX = {cabi.RT_N_SCAN_MAX} fit into a scan")
         self.hl.check(self.hl.lib.rt_hip_plan_enable_length_scan(self._h, int(on)), "rt_hip_plan_enable_length_scan")
         self._scan = bool(on)
+        if not on:
+            self._n_scan_seed = 0   # (switching the scan off drops its seeds)
         return self
 
     def fetch_length_steps(self) -> list:
@@ -403,6 +406,79 @@ class Plan:
         for n in range(2, self.problem.N + 1 if getattr(self, "_scan", False) else 2):
             e, f, a = self.length_step_ptrs(n)
             out.append(dict(n=n, E_v=view(e, (b.nv,)), nf=view(f, (b.ny, b.nx)), I_ang=view(a, (b.nb, b.na))))
+        return out
+
+    # -- the seeds of a scan ------------------------------------------------
+    def set_scan_seeds(self, seeds) -> "Plan":
+        """The seeds of the length scan (include/rt_hip.h, rt_hip_plan_set_scan_seeds): up to RT_N_SEED_MAX Seed records; a
+        step run with the scan on then leaves one record per seed and length n = 2 .. N from one march; [] removes them.
+        The scan must be on and the plan created with a seed.  More seeds than that, or anything that is not a Seed, is a
+        ValueError raised here, before any native call."""
+        seeds = list(seeds)
+        if len(seeds) > cabi.RT_N_SEED_MAX:
+            raise ValueError(f"set_scan_seeds: {len(seeds)} seeds given, at most RT_N_SEED_MAX = {cabi.RT_N_SEED_MAX} fit into a scan")
+        for i, sd in enumerate(seeds):
+            if not isinstance(sd, Seed):
+                raise ValueError(f"set_scan_seeds: entry {i} is a {type(sd).__name__}, not a Seed")
+        keep = []
+        arr = (cabi.RtSeed * max(1, len(seeds)))()
+        for i, sd in enumerate(seeds):
+            arr[i] = cabi.seed_record(sd, keep)
+        self.hl.check(self.hl.lib.rt_hip_plan_set_scan_seeds(self._h, len(seeds), arr if seeds else None), "rt_hip_plan_set_scan_seeds")
+        self._n_scan_seed = len(seeds)
+        return self
+
+    def _scan_seed_range(self):
+        on = getattr(self, "_scan", False)
+        return range(getattr(self, "_n_scan_seed", 0) if on else 0), range(2, self.problem.N + 1 if on else 2)
+
+    def fetch_seed_length_steps(self) -> list:
+        """Per scan seed: [dict(n, E_v [nv], nf [nx * ny], I_ang [na * nb], failure_code)] for n = 2 .. N lengths of the last
+        step run (waits for it; a failing run is repeated in the checking mode first)."""
+        b = self.problem.beam
+        seeds, lengths = self._scan_seed_range()
+        out = []
+        for s in seeds:
+            curve = []
+            for n in lengths:
+                E_v, nf, iang = np.empty(b.nv), np.empty(b.nx * b.ny), np.empty(b.na * b.nb)
+                code = C.c_uint(0)
+                self.hl.check(self.hl.lib.rt_hip_plan_fetch_seed_length_step(self._h, s, n, cabi._dp(E_v), cabi._dp(nf), cabi._dp(iang),
+                                                                             C.byref(code)), "rt_hip_plan_fetch_seed_length_step")
+                curve.append(dict(n=n, E_v=E_v, nf=nf, I_ang=iang, failure_code=code.value))
+            out.append(curve)
+        return out
+
+    def seed_length_step_ptrs(self, s: int, n: int) -> tuple:
+        """Device pointers (E_v, nf, I_ang) of the record of scan seed s at n lengths of the last step run."""
+        e, f, a = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self.hl.check(self.hl.lib.rt_hip_plan_seed_length_step_ptrs(self._h, int(s), int(n), C.byref(e), C.byref(f), C.byref(a)),
+                      "rt_hip_plan_seed_length_step_ptrs")
+        return int(e.value or 0), int(f.value or 0), int(a.value or 0)
+
+    def seed_length_step_tensors(self) -> list:
+        """Per scan seed, per n = 2 .. N: dict(n, E_v [nv], nf [ny][nx], I_ang [nb][na]) of torch views (float64, on the plan's
+        device, no copy) of the last step run -- blocks of one allocation, valid until the plan's next run; read them on the
+        run's stream or after a fetch."""
+        import torch
+
+        class _View:  # the CUDA array interface, which torch.as_tensor reads
+            pass
+
+        def view(ptr, shape):
+            v = _View()
+            v.__cuda_array_interface__ = dict(shape=shape, typestr="<f8", data=(ptr, False), version=2, strides=None)
+            return torch.as_tensor(v, device=torch.device("cuda", self.device))
+
+        b = self.problem.beam
+        seeds, lengths = self._scan_seed_range()
+        out = []
+        for s in seeds:
+            curve = []
+            for n in lengths:
+                e, f, a = self.seed_length_step_ptrs(s, n)
+                curve.append(dict(n=n, E_v=view(e, (b.nv,)), nf=view(f, (b.ny, b.nx)), I_ang=view(a, (b.nb, b.na))))
+            out.append(curve)
         return out
 
     # -- tables -------------------------------------------------------------
@@ -649,6 +725,53 @@ def length_scan_loop(problem: Problem, rays: np.ndarray | None = None, device: i
     code = 0
     for r in records:
         code |= r["failure_code"]
+    return dict(records=records, failure_code=code, failed_rays=failed[:nfail.value].copy(),
+                stats={k: getattr(st, k) for k, _ in cabi.RtStats._fields_})
+
+
+def seed_length_scan_loop(problem: Problem, seeds, rays: np.ndarray | None = None, device: int = 0) -> dict:
+    """The step record of every seed beam of `seeds` (a list of Seed, 1 .. RT_N_SEED_MAX) at every plasma length n = 2 .. N
+    from ONE forward march of the problem's rays (rt_hip_seed_length_scan_loop; rays None: the problem's ray grid as a list,
+    which the library recognises).  The problem must carry a seed -- it decides the gain-only mode and the method; it is not
+    part of the set.  Returns dict(records = per seed [dict(n, E_v, nf, I_ang, failure_code)], failure_code = the OR of the
+    codes, failed_rays = the rays that fail anywhere, stats).  What the scan does not take (backward method, N < 3, more than
+    RT_N_SCAN_MAX lengths), no seed or more than RT_N_SEED_MAX, or an entry that is not a Seed is a ValueError raised here,
+    before any native call."""
+    if problem.method != 2:
+        raise ValueError(f"seed_length_scan_loop: the problem's method is {problem.method}; the scan takes the forward method (2) only")
+    if problem.N < 3 or problem.N - 1 > cabi.RT_N_SCAN_MAX:
+        raise ValueError(f"seed_length_scan_loop: N = {problem.N}; a scan takes 3 <= N <= RT_N_SCAN_MAX + 1 = {cabi.RT_N_SCAN_MAX + 1}")
+    seeds = list(seeds)
+    if not 1 <= len(seeds) <= cabi.RT_N_SEED_MAX:
+        raise ValueError(f"seed_length_scan_loop: {len(seeds)} seeds given, 1 .. RT_N_SEED_MAX = {cabi.RT_N_SEED_MAX} are taken")
+    for i, sd in enumerate(seeds):
+        if not isinstance(sd, Seed):
+            raise ValueError(f"seed_length_scan_loop: entry {i} is a {type(sd).__name__}, not a Seed")
+    hl = HipLibrary.get()
+    m = cabi.Marshalled(problem)
+    if rays is None:
+        rays = problem.build_rays()
+    rays = np.ascontiguousarray(rays, dtype=cabi.RAY_DTYPE)
+    keep = []
+    arr = (cabi.RtSeed * len(seeds))()
+    for i, sd in enumerate(seeds):
+        arr[i] = cabi.seed_record(sd, keep)
+    b, L, ns = problem.beam, problem.N - 1, len(seeds)
+    E_v, nf, iang = np.zeros((ns, L, b.nv)), np.zeros((ns, L, b.nx * b.ny)), np.zeros((ns, L, b.na * b.nb))
+    codes = (C.c_uint * (ns * L))()
+    nfail = C.c_int(0)
+    failed = np.zeros(cabi.RT_N_FAILED_MAX, dtype=cabi.RAY_DTYPE)
+    st = cabi.RtStats()
+    rc = hl.lib.rt_hip_seed_length_scan_loop(device, m.N, C.byref(m.beam), m.gain, m.seed_ref, problem.method,
+                                             cabi.rays_ptr(rays), len(rays), problem.scale, ns, arr, cabi._dp(E_v), cabi._dp(nf),
+                                             cabi._dp(iang), codes, cabi.rays_ptr(failed), cabi.RT_N_FAILED_MAX, C.byref(nfail), C.byref(st))
+    hl.check(rc, "rt_hip_seed_length_scan_loop")
+    records = [[dict(n=i + 2, E_v=E_v[s, i].copy(), nf=nf[s, i].copy(), I_ang=iang[s, i].copy(), failure_code=int(codes[s * L + i]))
+                for i in range(L)] for s in range(ns)]
+    code = 0
+    for curve in records:
+        for r in curve:
+            code |= r["failure_code"]
     return dict(records=records, failure_code=code, failed_rays=failed[:nfail.value].copy(),
                 stats={k: getattr(st, k) for k, _ in cabi.RtStats._fields_})
 

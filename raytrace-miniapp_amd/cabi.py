@@ -379,6 +379,16 @@ def declare_hip_api(lib: C.CDLL) -> None:
         lib.rt_hip_plan_length_step_ptrs.restype = C.c_int
         lib.rt_hip_length_scan_loop.argtypes = list(lib.rt_hip_step_loop.argtypes)   # (one row per length where step_loop has one array)
         lib.rt_hip_length_scan_loop.restype = C.c_int
+    if hasattr(lib, "rt_hip_plan_set_scan_seeds"):   # (likewise)
+        lib.rt_hip_plan_set_scan_seeds.argtypes = [vp, C.c_int, P(RtSeed)]
+        lib.rt_hip_plan_set_scan_seeds.restype = C.c_int
+        lib.rt_hip_plan_fetch_seed_length_step.argtypes = [vp, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, P(C.c_uint)]
+        lib.rt_hip_plan_fetch_seed_length_step.restype = C.c_int
+        lib.rt_hip_plan_seed_length_step_ptrs.argtypes = [vp, C.c_int, C.c_int, P(vp), P(vp), P(vp)]
+        lib.rt_hip_plan_seed_length_step_ptrs.restype = C.c_int
+        a = list(lib.rt_hip_step_loop.argtypes)   # (n_seed, seeds behind scale; one row per seed and length where step_loop has one array)
+        lib.rt_hip_seed_length_scan_loop.argtypes = a[:9] + [C.c_int, P(RtSeed)] + a[9:]
+        lib.rt_hip_seed_length_scan_loop.restype = C.c_int
     lib.rt_hip_plan_set_debug.argtypes = [vp, C.c_uint]
     lib.rt_hip_plan_set_debug.restype = C.c_int
     lib.rt_hip_plan_destroy.argtypes = [vp]
@@ -398,6 +408,8 @@ HIP_API_SYMBOLS = [
     "rt_hip_plan_update_gain", "rt_hip_plan_update_gain_dev", "rt_hip_plan_table_flags",
     "rt_hip_plan_set_seeds", "rt_hip_plan_fetch_seed_step", "rt_hip_plan_seed_step_ptrs",
     "rt_hip_plan_enable_length_scan", "rt_hip_plan_fetch_length_step", "rt_hip_plan_length_step_ptrs", "rt_hip_length_scan_loop",
+    "rt_hip_plan_set_scan_seeds", "rt_hip_plan_fetch_seed_length_step", "rt_hip_plan_seed_length_step_ptrs",
+    "rt_hip_seed_length_scan_loop",
     "rt_hip_plan_set_step_one_launch", "rt_hip_debug_run_shape",
     "rt_hip_plan_set_debug", "rt_hip_plan_destroy",
 ]

@@ -147,6 +147,9 @@ struct DevCtl {
     // rt_step_scan_kernel: the failure code of every length of a length scan, [n - 2] for n = 2 .. N lengths (failure_code
     // above is their OR)
     unsigned int len_code[RT_N_SCAN_MAX];
+    // rt_step_scan_seeds_kernel: the failure code of every (seed, length) of a length scan with scan seeds, [s][n - 2]
+    // (failure_code above is their OR).  At the end: everything above keeps its offset.
+    unsigned int seed_len_code[RT_N_SEED_MAX][RT_N_SCAN_MAX];
 };
 
 // probe outputs of the frequency kernel (gvl / evl / ivl are read back from the records)

@@ -16,6 +16,7 @@
 #include "rt_step_seeds.hip" // step mode with a seed set: one record per seed from one march
 #include "rt_fused_step.hip" // step mode as two phases of one launch (opt-in)
 #include "rt_step_scan.hip" // step mode with a length scan: one record per plasma length from one forward march
+#include "rt_step_scan_seeds.hip" // ... with the seeds of the scan: one record per (seed, length) from that march
 
 #include "rt_runtime.h"
 #include "rt_run_shape.h" // what a run looks like: the pure decision (facts + tuning -> shape) this file enqueues
@@ -204,7 +205,7 @@ RunFacts run_facts(const rt_hip_plan *p)
     f.L               = P.L;
     f.n_iang          = p->n_iang;
     f.rays_per_pixel  = P.rays.nga * P.rays.ngb;
-    f.n_seed          = p->n_seed;
+    f.n_seed          = p->scan_on ? p->n_scan_seed : p->n_seed; // (a set and the seeds of a scan exclude each other)
     f.c_h3            = P.c_h3;
     f.march_prune     = p->march_prune;
     f.method          = P.method;
@@ -250,8 +251,9 @@ int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kin
         "step kernel: the E_v accumulator (nv doubles) does not fit into the LDS of this device",
         "step kernel of a seed set: the E_v accumulators (nv doubles per seed) do not fit into the LDS of this device",
         nullptr, // PASS_PATH
-        "step kernel of a length scan: the E_v accumulators (nv doubles per length) do not fit into the LDS of this device" };
-    static_assert(PASS_SPEC == 1 && PASS_STEP == 2 && PASS_SEEDS == 3 && PASS_SCAN == 5, "too_big[] is indexed by PassKind");
+        "step kernel of a length scan: the E_v accumulators (nv doubles per length) do not fit into the LDS of this device",
+        "step kernel of a length scan with scan seeds: the E_v accumulators (nv doubles per seed and length) do not fit into the LDS of this device" };
+    static_assert(PASS_SPEC == 1 && PASS_STEP == 2 && PASS_SEEDS == 3 && PASS_SCAN == 5 && PASS_SCAN_SEEDS == 6, "too_big[] is indexed by PassKind");
     if (too_big[kind] && s.lds > f.lds_limit)
         return fail_arg(too_big[kind]);
     if (s.grid == 0)
@@ -288,6 +290,32 @@ int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kin
         a.scan.nf_off  = p->seeds_nf_off;
         a.scan.ang_off = p->seeds_ang_off;
         return launch(p, scan_kernel(f.use_emis), s.grid, block, s.lds, stream, a);
+    }
+    if (kind == PASS_SCAN_SEEDS) { // a length scan with scan seeds (a seeded plan: gain-only): one record per (seed, length)
+        if (!p->scan_bnd || !p->seeds_dev)
+            return fail_arg("step kernel of a length scan with scan seeds: the boundary states or the records of this run were not allocated");
+        if (f.n_seed < 1 || f.n_seed > RT_N_SEED_MAX || f.L > RT_N_SCAN_MAX || f.use_emis)
+            return fail_arg("step kernel of a length scan with scan seeds: not a gain-only run of 1 .. RT_N_SEED_MAX seeds and at most RT_N_SCAN_MAX lengths");
+        if (p->seeds_doubles < (size_t) f.n_seed * (size_t) f.L * p->seeds_stride)
+            return fail_arg("step kernel of a length scan with scan seeds: the records of this run are smaller than n_seed (N - 1) blocks");
+        rt::ScanSeedsKArg a = pass_args<rt::ScanSeedsKArg>(fa);
+        a.hot.iang     = nullptr; // (every record's I_ang lies in its block)
+        a.hot.seed_fk  = nullptr; // (the creation seed is not part of the set)
+        a.scan.bnd     = p->scan_bnd;
+        a.scan.out     = p->seeds_dev;
+        a.scan.stride  = p->seeds_stride;
+        a.scan.nf_off  = p->seeds_nf_off;
+        a.scan.ang_off = p->seeds_ang_off;
+        a.set.n_seed   = f.n_seed;
+        for (int i = 0; i < f.n_seed; i++) {
+            a.set.fk[i]   = p->seed_set[i].f[4];
+            a.set.sf[i]   = p->P.rays.sf ? p->seedset_sf[i] : nullptr;
+            a.set.sin[i]  = p->P.rays.sf ? p->seedset_sin[i] : nullptr;
+            a.set.seed[i] = p->seed_set[i];
+            if (p->P.rays.sf && (!a.set.sf[i] || !a.set.sin[i]))
+                return fail_arg("step kernel of a length scan with scan seeds: the factor tables of the seeds were not built for this ray grid");
+        }
+        return launch(p, rt::rt_step_scan_seeds_kernel, s.grid, block, s.lds, stream, a);
     }
     // a seed set (a seeded plan: gain-only): one record per seed
     rt::SeedsKArg a = pass_args<rt::SeedsKArg>(fa);
@@ -393,9 +421,11 @@ int launch_selftest(unsigned long long *counts_dev)
 int plan_repeat_checked(rt_hip_plan *p)
 {
     hipStream_t stream = p->last_stream;
-    // (a length scan marks one bit per length in a 32-bit word per ray, every other run one byte per ray)
+    // (a length scan marks one bit per length in a 32-bit word per ray, with scan seeds one bit per (seed, length) in a 64-bit
+    // word, every other run one byte per ray)
     const bool scan       = p->last_step && p->last_scan_L > 0;
-    const size_t bad_word = scan ? sizeof(unsigned) : 1;
+    const int scan_seeds  = scan ? p->last_scan_n_seed : 0;
+    const size_t bad_word = scan_seeds > 0 ? sizeof(unsigned long long) : scan ? sizeof(unsigned) : 1;
     if (p->bad_rays < (size_t) p->n_rays * bad_word || !p->bad_dev) {
         (void) hipFree(p->bad_dev);
         p->bad_dev = nullptr;
@@ -408,12 +438,15 @@ int plan_repeat_checked(rt_hip_plan *p)
     HIP_TRY(hipMemsetAsync(&p->ctl->n_failed, 0, sizeof(unsigned), stream));
     HIP_TRY(hipMemsetAsync(p->ctl->seed_code, 0, sizeof(p->ctl->seed_code), stream));
     HIP_TRY(hipMemsetAsync(p->ctl->len_code, 0, sizeof(p->ctl->len_code), stream));
+    HIP_TRY(hipMemsetAsync(p->ctl->seed_len_code, 0, sizeof(p->ctl->seed_len_code), stream));
     HIP_TRY(hipMemsetAsync(p->ctl->next_tile_f, 0, sizeof(p->ctl->next_tile_f), stream));
     const bool step = p->last_step; // a step run: the step kernel honours the same marks, E_v and nf start over
     RunFacts f          = run_facts(p);
     f.scan_on           = scan; // (the run that is repeated decides, not what the plan has been switched to since)
+    if (scan)
+        f.n_seed = scan_seeds;
     const Tuning t      = read_tuning();
-    const PassKind kind = step ? (scan ? PASS_SCAN : f.n_seed > 0 ? PASS_SEEDS : PASS_STEP) : PASS_FREQ;
+    const PassKind kind = step ? (scan ? (scan_seeds > 0 ? PASS_SCAN_SEEDS : PASS_SCAN) : f.n_seed > 0 ? PASS_SEEDS : PASS_STEP) : PASS_FREQ;
     int rc              = launch_pass(p, f, t, kind, stream, 1, p->bad_dev);
     if (rc == RT_OK) {
         if (step && p->last_step_lent) { // (the caller's buffers: exactly the K and nx * ny doubles that are the run's)

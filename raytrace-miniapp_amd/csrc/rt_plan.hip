@@ -631,12 +631,13 @@ int rtr::plan_build_seedset_tabs(rt_hip_plan *p)
         p->seedset_sin[s] = nullptr;
     }
     const rt::DevRays &R = p->P.rays;
-    if (p->n_seed < 1 || !R.sf) // (R.sf: a ray grid, a seeded plan, the forward method)
+    const int n_set = p->n_seed > 0 ? p->n_seed : p->n_scan_seed; // (a seed set, or the seeds of a scan: never both)
+    if (n_set < 1 || !R.sf) // (R.sf: a ray grid, a seeded plan, the forward method)
         return RT_OK;
     const size_t nn = (size_t) R.ngx + (size_t) R.ngy + (size_t) R.nga + (size_t) R.ngb;
     const size_t per_seed = align_up(nn * sizeof(double) + nn, 256);
-    HIP_TRY(dev_malloc((void **) &p->seedset_tab, per_seed * (size_t) p->n_seed));
-    for (int s = 0; s < p->n_seed; s++) {
+    HIP_TRY(dev_malloc((void **) &p->seedset_tab, per_seed * (size_t) n_set));
+    for (int s = 0; s < n_set; s++) {
         double *sf           = reinterpret_cast<double *>(p->seedset_tab + per_seed * (size_t) s);
         unsigned char *flags = reinterpret_cast<unsigned char *>(sf + nn);
         const int rc         = launch_seed_tab(p->seed_set[s], R, nn, sf, flags);
@@ -1054,7 +1055,8 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
     const size_t nf_off = align_up((size_t) p->P.K * sizeof(double), 256) / sizeof(double);
     const int n_seed = p->n_seed; // a seed set: one record per seed, all in one allocation of the plan
     const int scan_L = p->scan_on ? p->P.L : 0; // a length scan: one record per length, the same allocation (never both)
-    const int n_rec  = n_seed > 0 ? n_seed : scan_L;
+    const int scan_seeds = scan_L > 0 ? p->n_scan_seed : 0; // the seeds of the scan: one record per (seed, length), seed 0's curve first
+    const int n_rec  = n_seed > 0 ? n_seed : scan_seeds > 0 ? scan_seeds * scan_L : scan_L;
     if (scan_L > 0) {
         if (!step || p->path_on)
             return fail_arg("rt_hip_plan_run: the length scan is on, which runs in step mode only");
@@ -1162,6 +1164,7 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
     p->last_step_lent = lent;
     p->last_n_seed = n_seed;
     p->last_scan_L = scan_L;
+    p->last_scan_n_seed = scan_seeds;
     p->spec_last   = p->spec_sel;
     p->ran         = true;
     p->queued      = false; // (`ran` + last_stream cover it from here)
@@ -1421,6 +1424,14 @@ int rt_hip_plan_enable_length_scan(rt_hip_plan *p, int on)
         pool_free(p->device, p->scan_bnd);
         p->scan_bnd       = nullptr;
         p->scan_bnd_bytes = 0;
+        if (p->n_scan_seed > 0) { // ... and so do the seeds of the scan
+            p->n_scan_seed = 0;
+            (void) hipFree(p->seedset_arena);
+            p->seedset_arena = nullptr;
+            for (int s = 0; s < RT_N_SEED_MAX; s++)
+                p->seed_set[s] = rt::DevSeed{};
+            return plan_build_seedset_tabs(p); // (frees the factor tables)
+        }
     }
     return RT_OK;
 }
@@ -1444,7 +1455,7 @@ int rt_hip_plan_fetch_length_step(rt_hip_plan *p, int n, double *E_v, double *nf
     if (I_ang)
         HIP_TRY(hipMemcpy(I_ang, blk + p->seeds_ang_off, p->n_iang * sizeof(double), hipMemcpyDeviceToHost));
     if (failure_code)
-        *failure_code = c.len_code[n - 2];
+        *failure_code = p->last_scan_n_seed > 0 ? c.seed_len_code[0][n - 2] : c.len_code[n - 2]; // (with scan seeds: seed 0's curve)
     return RT_OK;
 }
 
@@ -1464,28 +1475,70 @@ int rt_hip_plan_length_step_ptrs(rt_hip_plan *p, int n, double **E_v_dev, double
     return RT_OK;
 }
 
+} // extern "C"
+
+// What rt_hip_plan_set_seeds and rt_hip_plan_set_scan_seeds share.  The arguments of either, validated: `who` names the
+// entry point in the messages.
+static int seeds_validate(const rt_hip_plan *p, const char *who, int n_seed, const rt_seed *seeds)
+{
+    auto fail = [&](const char *what) { return fail_arg((std::string(who) + what).c_str()); };
+    if (n_seed < 0 || n_seed > RT_N_SEED_MAX)
+        return fail(": n_seed must be 0 .. RT_N_SEED_MAX");
+    if (n_seed > 0 && !seeds)
+        return fail(": NULL seeds");
+    const int K = p->P.K;
+    for (int s = 0; s < n_seed; s++) // (as rt_hip_plan_create validates its seed)
+        for (int i = 0; i < 5; i++) {
+            if (seeds[s].dim[i] < (i < 4 ? 2 : 1) || !seeds[s].x[i] || !seeds[s].f[i])
+                return fail(": incomplete seed table");
+            if (i == 4 && seeds[s].dim[4] != K)
+                return fail(": seed.dim[4] != beam.nv");
+        }
+    return RT_OK;
+}
+static int seeds_install(rt_hip_plan *p, int n_seed, const rt_seed *seeds, bool of_scan);
+
+extern "C" {
+
 int rt_hip_plan_set_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds)
 {
     if (!p)
         return fail_arg("rt_hip_plan_set_seeds: NULL plan");
     if (!p->P.has_seed)
         return fail_arg("rt_hip_plan_set_seeds: the plan was created without a seed (a set needs the gain-only mode)");
-    if (n_seed < 0 || n_seed > RT_N_SEED_MAX)
-        return fail_arg("rt_hip_plan_set_seeds: n_seed must be 0 .. RT_N_SEED_MAX");
-    if (n_seed > 0 && !seeds)
-        return fail_arg("rt_hip_plan_set_seeds: NULL seeds");
-    const int K = p->P.K, Kp = p->P.Kp;
-    for (int s = 0; s < n_seed; s++) // (as rt_hip_plan_create validates its seed)
-        for (int i = 0; i < 5; i++) {
-            if (seeds[s].dim[i] < (i < 4 ? 2 : 1) || !seeds[s].x[i] || !seeds[s].f[i])
-                return fail_arg("rt_hip_plan_set_seeds: incomplete seed table");
-            if (i == 4 && seeds[s].dim[4] != K)
-                return fail_arg("rt_hip_plan_set_seeds: seed.dim[4] != beam.nv");
-        }
+    const int rv = seeds_validate(p, "rt_hip_plan_set_seeds", n_seed, seeds);
+    if (rv != RT_OK)
+        return rv;
     if (n_seed > 0 && p->scan_on)
         return fail_arg("rt_hip_plan_set_seeds: the length scan is on (a seed set and a length scan exclude each other)");
     if (n_seed > 0 && (p->path_on || p->spectra_on))
         return fail_arg("rt_hip_plan_set_seeds: the path tracer or spectra mode is enabled (a set runs in step mode only)");
+    if (n_seed == 0 && p->n_scan_seed > 0) // (the seeds of a scan are rt_hip_plan_set_scan_seeds': there is no set to remove)
+        return RT_OK;
+    return seeds_install(p, n_seed, seeds, false);
+}
+
+int rt_hip_plan_set_scan_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds)
+{
+    if (!p)
+        return fail_arg("rt_hip_plan_set_scan_seeds: NULL plan");
+    if (!p->P.has_seed)
+        return fail_arg("rt_hip_plan_set_scan_seeds: the plan was created without a seed (scan seeds need the gain-only mode)");
+    if (!p->scan_on)
+        return fail_arg("rt_hip_plan_set_scan_seeds: the length scan is off (rt_hip_plan_enable_length_scan first)");
+    const int rv = seeds_validate(p, "rt_hip_plan_set_scan_seeds", n_seed, seeds);
+    if (rv != RT_OK)
+        return rv;
+    return seeds_install(p, n_seed, seeds, true);
+}
+
+} // extern "C"
+
+// Settles the last run, packs the tables of the seeds into one device block and makes them the plan's seed set
+// (of_scan: the seeds of its scan); n_seed = 0 removes them.
+static int seeds_install(rt_hip_plan *p, int n_seed, const rt_seed *seeds, bool of_scan)
+{
+    const int Kp = p->P.Kp;
     HIP_TRY(hipSetDevice(p->device));
     if (p->ran) { // the last run keeps its set until it is final (wait, control block, the checking repeat)
         const int rs = plan_settle_last_run(p);
@@ -1519,7 +1572,8 @@ int rt_hip_plan_set_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds)
     }
     (void) hipFree(p->seedset_arena);
     p->seedset_arena = arena;
-    p->n_seed        = n_seed;
+    p->n_seed        = of_scan ? 0 : n_seed;
+    p->n_scan_seed   = of_scan ? n_seed : 0;
     for (int s = 0; s < RT_N_SEED_MAX; s++) {
         p->seed_set[s] = rt::DevSeed{};
         if (s < n_seed) {
@@ -1532,6 +1586,51 @@ int rt_hip_plan_set_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds)
         }
     }
     return plan_build_seedset_tabs(p);
+}
+
+extern "C" {
+
+int rt_hip_plan_fetch_seed_length_step(rt_hip_plan *p, int s, int n, double *E_v, double *nf, double *I_ang, unsigned int *failure_code)
+{
+    if (!p || !p->ran || !p->last_step || p->last_scan_L < 1 || p->last_scan_n_seed < 1)
+        return fail_arg("rt_hip_plan_fetch_seed_length_step: the last run was not a step run of a length scan with scan seeds");
+    if (s < 0 || s >= p->last_scan_n_seed)
+        return fail_arg("rt_hip_plan_fetch_seed_length_step: no such seed among the scan seeds of the last run");
+    if (n < 2 || n - 1 > p->last_scan_L)
+        return fail_arg("rt_hip_plan_fetch_seed_length_step: n must be 2 .. N of the last run");
+    rt::DevCtl c;
+    bool staged  = false;
+    const int rs = plan_settle(p, c, staged); // (a failing run is repeated here as rt_hip_plan_fetch repeats it)
+    if (rs != RT_OK)
+        return rs;
+    const double *blk = p->seeds_dev + ((size_t) s * (size_t) p->last_scan_L + (size_t) (n - 2)) * p->seeds_stride;
+    if (E_v)
+        HIP_TRY(hipMemcpy(E_v, blk, (size_t) p->P.K * sizeof(double), hipMemcpyDeviceToHost));
+    if (nf)
+        HIP_TRY(hipMemcpy(nf, blk + p->seeds_nf_off, (size_t) p->P.beam.nx * (size_t) p->P.beam.ny * sizeof(double), hipMemcpyDeviceToHost));
+    if (I_ang)
+        HIP_TRY(hipMemcpy(I_ang, blk + p->seeds_ang_off, p->n_iang * sizeof(double), hipMemcpyDeviceToHost));
+    if (failure_code)
+        *failure_code = c.seed_len_code[s][n - 2];
+    return RT_OK;
+}
+
+int rt_hip_plan_seed_length_step_ptrs(rt_hip_plan *p, int s, int n, double **E_v_dev, double **nf_dev, double **iang_dev)
+{
+    if (!p || !p->ran || !p->last_step || p->last_scan_L < 1 || p->last_scan_n_seed < 1)
+        return fail_arg("rt_hip_plan_seed_length_step_ptrs: the last run was not a step run of a length scan with scan seeds");
+    if (s < 0 || s >= p->last_scan_n_seed)
+        return fail_arg("rt_hip_plan_seed_length_step_ptrs: no such seed among the scan seeds of the last run");
+    if (n < 2 || n - 1 > p->last_scan_L)
+        return fail_arg("rt_hip_plan_seed_length_step_ptrs: n must be 2 .. N of the last run");
+    double *blk = p->seeds_dev + ((size_t) s * (size_t) p->last_scan_L + (size_t) (n - 2)) * p->seeds_stride;
+    if (E_v_dev)
+        *E_v_dev = blk;
+    if (nf_dev)
+        *nf_dev = blk + p->seeds_nf_off;
+    if (iang_dev)
+        *iang_dev = blk + p->seeds_ang_off;
+    return RT_OK;
 }
 
 int rt_hip_plan_kernel_ms(rt_hip_plan *p, float *ms)
@@ -1654,8 +1753,9 @@ int rt_hip_plan_fetch_probe(rt_hip_plan *p, float *gvl, float *evl, int32_t *ivl
 static int host_pointer_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed,
                              int method, const rt_ray *rays, size_t n_rays, double scale, double *image, double *E_v, double *nf,
                              double *I_ang, unsigned int *failure_code, rt_ray *failed_rays, int max_failed,
-                             int *n_failed, rt_stats *stats, bool scan = false)
+                             int *n_failed, rt_stats *stats, bool scan = false, int n_scan_seed = 0, const rt_seed *scan_seeds = nullptr)
 {
+    // (n_scan_seed > 0: rt_hip_seed_length_scan_loop -- the rows of a scan once per seed, [n_seed][N - 1][...])
     // (scan: rt_hip_length_scan_loop -- E_v, nf and I_ang hold one row per length n = 2 .. N, failure_code one code per row)
     const bool step = image == nullptr;
     // RT_HIP_TIMING=1: wall-clock split of this call on stderr (diagnostic)
@@ -1681,6 +1781,8 @@ static int host_pointer_loop(int device, int N, const rt_beam *beam, const rt_ga
         rc = rt_hip_plan_enable_step(p, 1);
         if (rc == RT_OK && scan)
             rc = rt_hip_plan_enable_length_scan(p, 1);
+        if (rc == RT_OK && scan && n_scan_seed > 0)
+            rc = rt_hip_plan_set_scan_seeds(p, n_scan_seed, scan_seeds);
         if (rc != RT_OK) {
             rt_hip_plan_destroy(p);
             release_queue(device, q);
@@ -1721,11 +1823,19 @@ static int host_pointer_loop(int device, int N, const rt_beam *beam, const rt_ga
         rc = rt_hip_plan_fetch(p, image, step ? nullptr : I_ang, scan ? nullptr : failure_code, failed_rays, max_failed, n_failed, stats);
     if (rc == RT_OK && step && !scan)
         rc = rt_hip_plan_fetch_step(p, E_v, nf, I_ang);
-    for (int n = 2; rc == RT_OK && scan && n <= N; n++) {
+    for (int n = 2; rc == RT_OK && scan && n_scan_seed == 0 && n <= N; n++) {
         const size_t r = (size_t) (n - 2);
         rc = rt_hip_plan_fetch_length_step(p, n, E_v ? E_v + r * (size_t) beam->nv : nullptr, nf ? nf + r * (size_t) beam->nx * (size_t) beam->ny : nullptr,
                                            I_ang ? I_ang + r * (size_t) beam->na * (size_t) beam->nb : nullptr, failure_code ? failure_code + r : nullptr);
     }
+    for (int s = 0; scan && s < n_scan_seed; s++)
+        for (int n = 2; rc == RT_OK && n <= N; n++) {
+            const size_t r = (size_t) s * (size_t) (N - 1) + (size_t) (n - 2);
+            rc = rt_hip_plan_fetch_seed_length_step(p, s, n, E_v ? E_v + r * (size_t) beam->nv : nullptr,
+                                                    nf ? nf + r * (size_t) beam->nx * (size_t) beam->ny : nullptr,
+                                                    I_ang ? I_ang + r * (size_t) beam->na * (size_t) beam->nb : nullptr,
+                                                    failure_code ? failure_code + r : nullptr);
+        }
     lap("fetch (wait + D2H)");
     rt_hip_plan_destroy(p); // waits for whatever is still in flight
     release_queue(device, q);
@@ -1777,6 +1887,23 @@ int rt_hip_length_scan_loop(int device, int N, const rt_beam *beam, const rt_gai
     // (method, N: rt_hip_plan_enable_length_scan refuses what the scan does not take)
     return host_pointer_loop(device, N, beam, gain, seed, method, rays, n_rays, scale, nullptr, E_v, nf, I_ang, failure_codes,
                              failed_rays, max_failed, n_failed, stats, true);
+}
+
+int rt_hip_seed_length_scan_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed, int method,
+                                 const rt_ray *rays, size_t n_rays, double scale, int n_seed, const rt_seed *seeds, double *E_v, double *nf,
+                                 double *I_ang, unsigned int *failure_codes, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats)
+{
+    if (!beam)
+        return fail_arg("rt_hip_seed_length_scan_loop: NULL beam");
+    if (!rays && n_rays)
+        return fail_arg("rt_hip_seed_length_scan_loop: NULL ray list");
+    if (n_rays > MAX_LIST_RAYS)
+        return fail_arg("rt_hip_seed_length_scan_loop: 2^32 - 4096 rays or more: split the call");
+    if (n_seed < 1 || n_seed > RT_N_SEED_MAX || !seeds)
+        return fail_arg("rt_hip_seed_length_scan_loop: n_seed must be 1 .. RT_N_SEED_MAX, with seeds");
+    // (method, N, the creation seed, the tables of the seeds: the plan's entry points refuse what the scan does not take)
+    return host_pointer_loop(device, N, beam, gain, seed, method, rays, n_rays, scale, nullptr, E_v, nf, I_ang, failure_codes,
+                             failed_rays, max_failed, n_failed, stats, true, n_seed, seeds);
 }
 
 int rt_hip_calc_rays(int device, int N, double dz, const rt_gain *gain, const rt_seed *seed, int K, int method, const double *rays,

@@ -89,7 +89,12 @@ struct rt_hip_plan {
     int last_scan_L       = 0; // records of the last run (0: it ran without the scan)
     unsigned char *scan_bnd = nullptr;
     size_t scan_bnd_bytes = 0;
-    size_t bad_word       = 1; // bytes per ray of bad_dev in the last checking repeat (4: a length scan, one bit per length)
+    size_t bad_word       = 1; // bytes per ray of bad_dev in the last checking repeat (4: a length scan, one bit per length; 8: with scan seeds)
+    // the seeds of a scan (rt_hip_plan_set_scan_seeds): while the scan is on the plan may carry 1 .. RT_N_SEED_MAX seeds whose
+    // records every length gets -- n_scan_seed (N - 1) blocks of the allocation above, block s (N - 1) + (n - 2).  Their tables
+    // live where a seed set's live (seed_set[], seedset_arena, seedset_tab: a set and a scan exclude each other); n_seed stays 0.
+    int n_scan_seed      = 0;
+    int last_scan_n_seed = 0; // scan seeds of the last run (0: it ran without them)
     size_t rec_bytes   = 0;
     hipEvent_t evm     = nullptr; // between march and frequency kernels
     const rt_ray *host_rays = nullptr; // ray list still on the host, uploaded by the next run (rt_hip_image_loop)

@@ -1,7 +1,8 @@
 // rt_step_handout.inc -- the tile hand-out of a step pass: which tiles of the launch a wave takes, and the walk over them.
 //
 // A fragment of a kernel body, not a header (rt_tile_rec.inc says why text and not a function template): rt_step_kernel
-// (rt_step.hip), rt_step_seeds_kernel (rt_step_seeds.hip) and rt_step_scan_kernel (rt_step_scan.hip) include it once,
+// (rt_step.hip), rt_step_seeds_kernel (rt_step_seeds.hip), rt_step_scan_kernel (rt_step_scan.hip) and rt_step_scan_seeds_kernel
+// (rt_step_scan_seeds.hip) include it once,
 // between the work-group prologue and epilogue (rt_step_wg.inc).
 //
 // The eight sharded counters of the control block (DevCtl::next_tile_f, rt_freq_kernel says why eight): a wave starts on

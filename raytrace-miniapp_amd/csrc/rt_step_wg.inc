@@ -4,7 +4,8 @@
 //   [the two exponent tables of rt_freq_kernel][n_rec I_ang histograms, ang_stride doubles apart (if they fit: FQ_IANG_LDS)]
 //   [n_rec E_v accumulators, Kp doubles each][per wave: the transposition rows [4][XP_ROW] of the wave sum (rt_step_evsum.inc)]
 // Three parts; the includer defines which one it wants.  The two kernel parts are fragments of a kernel body (rt_tile_rec.inc
-// says why text) of rt_step_kernel, rt_step_seeds_kernel and rt_step_scan_kernel; rt_fused_step_kernel has FusedLay's layout.
+// says why text) of rt_step_kernel, rt_step_seeds_kernel, rt_step_scan_kernel and rt_step_scan_seeds_kernel (one record per
+// (seed, length)); rt_fused_step_kernel has FusedLay's layout.
 //   STEP_WG_SIZE       namespace scope, once (rt_step.hip): step_ang_stride, seeds_ang_stride, step_lds_doubles
 //   STEP_WG_PROLOGUE   carves the LDS, fills the exponent tables, zeroes histograms and accumulators, ends in a barrier.
 //                      Reads H, A and
