@@ -606,6 +606,54 @@ int rt_hip_seed_length_scan_loop(int device, int N, const rt_beam *beam, const r
                                  double *nf, double *I_ang, unsigned int *failure_codes, rt_ray *failed_rays, int max_failed,
                                  int *n_failed, rt_stats *stats);
 
+/*
+ * ASE seeds on an emission plan: the WHOLE per-step record from ONE march.  intensity_step_struct is one buffer: the ASE
+ * triple E_v | image | E_ang and one seeded triple per seed beam (N_seed <= RT_N_SEED_MAX).  The trajectory, gvl, ivl, the
+ * exit state, the escape flag and the step count of RayTrace_calc_ray do not depend on use_emis, only evl does
+ * (Helper.h:486-489, 502): the march of an emission plan leaves everything the gain-only pass of a seeded run reads.  With
+ * ASE seeds installed a step-mode run marches once and rt_step_ase_seeds_kernel
+ * (raytrace-miniapp_amd/csrc/rt_step_ase_seeds.hip, in place of rt_step_kernel; reported as freq_ms) leaves 1 + n_seed
+ * records:
+ *   record 0      the plan's own emission step record, what the plan leaves without the seeds;
+ *   record 1 + s  what a step run leaves of the SAME PROBLEM CREATED WITH SEED s -- the same tables (E0 present but unused:
+ *                 use_emis = E0 != NULL && seed == NULL), method and rays, scale scales[s]: gain-only,
+ *                 Iv[k] = f0_s f_s[4][k] exp(gl[k]), the seed factor at the launch ray (method 2) or the exit ray (method 1).
+ *   Every Iv is the double the plain emission plan, respectively the plain single-seed plan, computes; the sums differ from
+ *   those plans' by summation order only.  The seeded records are sampled on the PLAN'S RAY SET, not on a separate
+ *   seed-beam grid: the caller chooses one grid for all records (rt_hip_plan_set_ray_grid with its own axes, or a list).
+ *   A ray whose march sums are all zero (counted in n_skipped) adds +0 to record 0 and is left out of it as ever, but it
+ *   carries f0_s f_s[4][k] under a seed and is part of the seed records.
+ * set_ase_seeds: accepted only on a plan created WITHOUT a seed whose tables carry E0 (an emission plan) and whose length
+ *   scan is off; anything else is RT_ERR_ARG (rt_hip_plan_set_seeds keeps refusing such a plan).  n_seed = 1 ..
+ *   RT_N_SEED_MAX installs seeds[0 .. n_seed), validated and copied as rt_hip_plan_set_seeds does it, factor tables per
+ *   seed on a forward ray grid included (rebuilt when the grid or the seeds change); scales[s] is the scale of record
+ *   1 + s, NULL: the plan's scale for all.  n_seed = 0 removes them, the plan is then a plain emission plan.  The call
+ *   settles the plan's last run first; a rejected call changes nothing.
+ * While installed only step mode runs: rt_hip_plan_run outside step mode, with lent step buffers or with a non-NULL
+ *   image_dev or iang_dev is RT_ERR_ARG, and so are rt_hip_plan_enable_path, rt_hip_plan_enable_spectra and
+ *   rt_hip_plan_enable_length_scan.  rt_hip_plan_set_step_one_launch is accepted, the run keeps two kernels.
+ *   rt_hip_plan_update_gain / _dev (the seeds stay), exact emission, the probe, the timing ring and
+ *   rt_hip_plan_set_step_factor work as on any step plan.
+ * Outputs: ONE allocation of the plan, 1 + n_seed blocks of the seed-set layout and stride (E_v | pad | nf | I_ang), block 0
+ *   ASE, block 1 + s seed s: a collective can take the application's whole buffer at once.  full_step_ptrs /
+ *   fetch_full_step: r = 0 .. n_seed; any pointer may be NULL; *failure_code is the code of record r.
+ *   rt_hip_plan_fetch_step, rt_hip_plan_step_ptrs and I_ang of rt_hip_plan_fetch serve block 0.
+ * Failures follow the reference run once per record: error -1 puts the ray in no record and sets the bit in every
+ *   record's code; error -2 / -3 under record r removes the ray from record r only.  rt_hip_plan_fetch reports the OR of
+ *   the codes and the rays that fail under any record, each once (more than RT_N_FAILED_MAX: the first of them in list
+ *   order); the counters are those of one run.
+ * rt_hip_full_step_loop: the host-pointer form (a ray list): E_v [1+n_seed][nv], nf [1+n_seed][nx*ny], I_ang
+ *   [1+n_seed][na*nb], failure_codes [1+n_seed] (may be NULL), row 0 ASE; n_seed = 1 .. RT_N_SEED_MAX.
+ * Not taken: the multi-device loops, the one-launch form, a length scan, image, spectra and path runs.
+ */
+int rt_hip_plan_set_ase_seeds(rt_hip_plan *plan, int n_seed, const rt_seed *seeds, const double *scales);
+int rt_hip_plan_fetch_full_step(rt_hip_plan *plan, int r, double *E_v, double *nf, double *I_ang, unsigned int *failure_code);
+int rt_hip_plan_full_step_ptrs(rt_hip_plan *plan, int r, double **E_v_dev, double **nf_dev, double **iang_dev);
+int rt_hip_full_step_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, int method, const rt_ray *rays,
+                          size_t n_rays, double scale, int n_seed, const rt_seed *seeds, const double *scales, double *E_v,
+                          double *nf, double *I_ang, unsigned int *failure_codes, rt_ray *failed_rays, int max_failed,
+                          int *n_failed, rt_stats *stats);
+
 /* Profiling aid (no reference counterpart): bit 0 = skip the frequency / deposit kernel, bit 1 = skip
  * the march and run the frequency pass over the records of the previous run of this plan, bit 2 = the
  * frequency kernel keeps its per-work-group I_ang sums to itself (I_ang stays zero).  0 = normal. */

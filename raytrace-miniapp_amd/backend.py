@@ -10,6 +10,7 @@ mirror of the reference's operator interface for this path.
   step_loop(...)        the same loop with the application's per-step record in place of the image cube: E_v, nf, I_ang
   multi_step_loop(...)  step_loop on all devices of the node: strided ray grid per device, one sum-reduce of the record
   seed_step_loop(...)   the step records of up to RT_N_SEED_MAX seed beams from one march (Plan.set_seeds)
+  full_step_loop(...)   the ASE record and the records of up to RT_N_SEED_MAX seed beams from one march (Plan.set_ase_seeds)
   length_scan_loop(...) the step record at every plasma length n = 2 .. N from one forward march (Plan.enable_length_scan)
   seed_length_scan_loop(...) ... of up to RT_N_SEED_MAX seed beams at every length, from that one march (Plan.set_scan_seeds)
   step_outputs_from_image  their definition as reductions of a cube, in numpy (no device)
@@ -102,6 +103,7 @@ class Plan:
                                             problem.method if method is None else method, problem.scale)
         self.hl.check(rc, "rt_hip_plan_create")
         self.n_rays = 0
+        self._n_ase_seed = 0    # ASE seeds installed (set_ase_seeds)
 
     # -- rays ---------------------------------------------------------------
     def set_rays(self, rays: np.ndarray) -> "Plan":
@@ -341,6 +343,75 @@ class Plan:
             e, n, a = self.seed_step_ptrs(s)
             out.append(dict(E_v=view(e, (b.nv,)), nf=view(n, (b.ny, b.nx)), I_ang=view(a, (b.nb, b.na))))
         return out
+
+    # -- ASE seeds ----------------------------------------------------------
+    def set_ase_seeds(self, seeds, scales=None) -> "Plan":
+        """ASE seeds (include/rt_hip.h, rt_hip_plan_set_ase_seeds): up to RT_N_SEED_MAX Seed records on an EMISSION plan
+        (created without a seed, tables with E0).  A step run then leaves the plan's own emission record and, from the same
+        march, the gain-only record of the same problem created with each seed, scale scales[s] (None: the plan's scale);
+        [] removes them.  More seeds than that, anything that is not a Seed, or scales of another length is a ValueError
+        raised here, before any native call."""
+        seeds = list(seeds)
+        if len(seeds) > cabi.RT_N_SEED_MAX:
+            raise ValueError(f"set_ase_seeds: {len(seeds)} seeds given, at most RT_N_SEED_MAX = {cabi.RT_N_SEED_MAX} fit into a step record")
+        for i, sd in enumerate(seeds):
+            if not isinstance(sd, Seed):
+                raise ValueError(f"set_ase_seeds: entry {i} is a {type(sd).__name__}, not a Seed")
+        sc = None
+        if scales is not None:
+            sc = np.ascontiguousarray(scales, dtype=np.float64)
+            if sc.shape != (len(seeds),):
+                raise ValueError(f"set_ase_seeds: {sc.size} scales for {len(seeds)} seeds")
+        keep = []
+        arr = (cabi.RtSeed * max(1, len(seeds)))()
+        for i, sd in enumerate(seeds):
+            arr[i] = cabi.seed_record(sd, keep)
+        self.hl.check(self.hl.lib.rt_hip_plan_set_ase_seeds(self._h, len(seeds), arr if seeds else None,
+                                                            cabi._dp(sc) if sc is not None and len(seeds) else None),
+                      "rt_hip_plan_set_ase_seeds")
+        self._n_ase_seed = len(seeds)
+        return self
+
+    def fetch_full_step(self) -> dict:
+        """dict(ase=rec, seeds=[rec ...]) of the last step run with ASE seeds (waits for it; a failing run is repeated in
+        the checking mode first); every rec is dict(E_v [nv], nf [nx * ny], I_ang [na * nb], failure_code)."""
+        b = self.problem.beam
+        recs = []
+        for r in range(1 + self._n_ase_seed):
+            E_v, nf, iang = np.empty(b.nv), np.empty(b.nx * b.ny), np.empty(b.na * b.nb)
+            code = C.c_uint(0)
+            self.hl.check(self.hl.lib.rt_hip_plan_fetch_full_step(self._h, r, cabi._dp(E_v), cabi._dp(nf), cabi._dp(iang), C.byref(code)),
+                          "rt_hip_plan_fetch_full_step")
+            recs.append(dict(E_v=E_v, nf=nf, I_ang=iang, failure_code=code.value))
+        return dict(ase=recs[0], seeds=recs[1:])
+
+    def full_step_ptrs(self, r: int) -> tuple:
+        """Device pointers (E_v, nf, I_ang) of record r (0: ASE, 1 + s: seed s) of the last step run with ASE seeds."""
+        e, n, a = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self.hl.check(self.hl.lib.rt_hip_plan_full_step_ptrs(self._h, int(r), C.byref(e), C.byref(n), C.byref(a)),
+                      "rt_hip_plan_full_step_ptrs")
+        return int(e.value or 0), int(n.value or 0), int(a.value or 0)
+
+    def full_step_tensors(self) -> dict:
+        """dict(ase=views, seeds=[views ...]): torch views (float64, on the plan's device, no copy) of E_v [nv], nf [ny][nx]
+        and I_ang [nb][na] of every record of the last step run with ASE seeds -- blocks of one allocation, valid until the
+        plan's next run; read them on the run's stream or after a fetch."""
+        import torch
+
+        class _View:  # the CUDA array interface, which torch.as_tensor reads
+            pass
+
+        def view(ptr, shape):
+            v = _View()
+            v.__cuda_array_interface__ = dict(shape=shape, typestr="<f8", data=(ptr, False), version=2, strides=None)
+            return torch.as_tensor(v, device=torch.device("cuda", self.device))
+
+        b = self.problem.beam
+        recs = []
+        for r in range(1 + self._n_ase_seed):
+            e, n, a = self.full_step_ptrs(r)
+            recs.append(dict(E_v=view(e, (b.nv,)), nf=view(n, (b.ny, b.nx)), I_ang=view(a, (b.nb, b.na))))
+        return dict(ase=recs[0], seeds=recs[1:])
 
     # -- length scan --------------------------------------------------------
     def enable_length_scan(self, on: bool = True) -> "Plan":
@@ -694,6 +765,54 @@ def seed_step_loop(problem: Problem, seeds, rays: np.ndarray | None = None, devi
         records = plan.fetch_seed_steps()
         info = plan.fetch()
     return dict(records=records, failure_code=info["failure_code"], failed_rays=info["failed_rays"], stats=info["stats"])
+
+
+def full_step_loop(problem: Problem, seeds, scales=None, rays: np.ndarray | None = None, device: int = 0) -> dict:
+    """The whole per-step record from ONE march of the problem's rays (rt_hip_full_step_loop, host pointers; rays None: the
+    problem's ray grid as a list): the emission record of `problem`, which must carry no seed and tables with E0, and the
+    gain-only record of the same problem under each Seed of `seeds` (1 .. RT_N_SEED_MAX) with scale scales[s] (None: the
+    problem's scale).  Returns dict(ase = rec, seeds = [rec ...], failure_code = the OR of the codes, failed_rays, stats),
+    every rec dict(E_v, nf, I_ang, failure_code).  No seed or too many, an entry that is not a Seed, scales of another
+    length or a problem with a seed is a ValueError raised here, before any native call."""
+    seeds = list(seeds)
+    if not 1 <= len(seeds) <= cabi.RT_N_SEED_MAX:
+        raise ValueError(f"full_step_loop: {len(seeds)} seeds given, 1 .. RT_N_SEED_MAX = {cabi.RT_N_SEED_MAX} are taken")
+    for i, sd in enumerate(seeds):
+        if not isinstance(sd, Seed):
+            raise ValueError(f"full_step_loop: entry {i} is a {type(sd).__name__}, not a Seed")
+    if problem.seed is not None:
+        raise ValueError("full_step_loop: the problem carries a seed; the ASE record needs an emission problem")
+    sc = None
+    if scales is not None:
+        sc = np.ascontiguousarray(scales, dtype=np.float64)
+        if sc.shape != (len(seeds),):
+            raise ValueError(f"full_step_loop: {sc.size} scales for {len(seeds)} seeds")
+    hl = HipLibrary.get()
+    m = cabi.Marshalled(problem)
+    if rays is None:
+        rays = problem.build_rays()
+    rays = np.ascontiguousarray(rays, dtype=cabi.RAY_DTYPE)
+    keep = []
+    arr = (cabi.RtSeed * len(seeds))()
+    for i, sd in enumerate(seeds):
+        arr[i] = cabi.seed_record(sd, keep)
+    b, nr = problem.beam, 1 + len(seeds)
+    E_v, nf, iang = np.zeros((nr, b.nv)), np.zeros((nr, b.nx * b.ny)), np.zeros((nr, b.na * b.nb))
+    codes = (C.c_uint * nr)()
+    nfail = C.c_int(0)
+    failed = np.zeros(cabi.RT_N_FAILED_MAX, dtype=cabi.RAY_DTYPE)
+    st = cabi.RtStats()
+    rc = hl.lib.rt_hip_full_step_loop(device, m.N, C.byref(m.beam), m.gain, problem.method, cabi.rays_ptr(rays), len(rays),
+                                      problem.scale, len(seeds), arr, cabi._dp(sc) if sc is not None else None, cabi._dp(E_v),
+                                      cabi._dp(nf), cabi._dp(iang), codes, cabi.rays_ptr(failed), cabi.RT_N_FAILED_MAX,
+                                      C.byref(nfail), C.byref(st))
+    hl.check(rc, "rt_hip_full_step_loop")
+    recs = [dict(E_v=E_v[r].copy(), nf=nf[r].copy(), I_ang=iang[r].copy(), failure_code=int(codes[r])) for r in range(nr)]
+    code = 0
+    for r in recs:
+        code |= r["failure_code"]
+    return dict(ase=recs[0], seeds=recs[1:], failure_code=code, failed_rays=failed[:nfail.value].copy(),
+                stats={k: getattr(st, k) for k, _ in cabi.RtStats._fields_})
 
 
 def length_scan_loop(problem: Problem, rays: np.ndarray | None = None, device: int = 0) -> dict:

@@ -150,6 +150,9 @@ struct DevCtl {
     // rt_step_scan_seeds_kernel: the failure code of every (seed, length) of a length scan with scan seeds, [s][n - 2]
     // (failure_code above is their OR).  At the end: everything above keeps its offset.
     unsigned int seed_len_code[RT_N_SEED_MAX][RT_N_SCAN_MAX];
+    // rt_step_ase_seeds_kernel: the failure code of every record of an emission plan with ASE seeds, [0] the ASE record,
+    // [1 + s] seed s (failure_code above is their OR; the last entry pads the block to 8-byte words).  At the end likewise.
+    unsigned int rec_code[RT_N_SEED_MAX + 2];
 };
 
 // probe outputs of the frequency kernel (gvl / evl / ivl are read back from the records)

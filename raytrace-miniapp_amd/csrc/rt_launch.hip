@@ -17,6 +17,7 @@
 #include "rt_fused_step.hip" // step mode as two phases of one launch (opt-in)
 #include "rt_step_scan.hip" // step mode with a length scan: one record per plasma length from one forward march
 #include "rt_step_scan_seeds.hip" // ... with the seeds of the scan: one record per (seed, length) from that march
+#include "rt_step_ase_seeds.hip"  // step kernel of an emission plan with ASE seeds: the ASE record and one per seed from one march
 
 #include "rt_runtime.h"
 #include "rt_run_shape.h" // what a run looks like: the pure decision (facts + tuning -> shape) this file enqueues
@@ -133,6 +134,7 @@ void (*step_kernel(bool s6, bool emis))(const rt::StepKArg)
     return emis ? (s6 ? rt::rt_step_kernel<6, true> : rt::rt_step_kernel<0, true>) : (s6 ? rt::rt_step_kernel<6, false> : rt::rt_step_kernel<0, false>);
 }
 void (*seeds_kernel(bool s6))(const rt::SeedsKArg) { return s6 ? rt::rt_step_seeds_kernel<6> : rt::rt_step_seeds_kernel<0>; }
+void (*ase_seeds_kernel(bool s6))(const rt::AseSeedsKArg) { return s6 ? rt::rt_step_ase_seeds_kernel<6> : rt::rt_step_ase_seeds_kernel<0>; }
 void (*scan_kernel(bool emis))(const rt::ScanKArg) { return emis ? rt::rt_step_scan_kernel<true> : rt::rt_step_scan_kernel<false>; }
 
 // what a launch of the frequency pass covers: tiles [tile_begin, tile_end) on tile counter freq_id (a run is one launch
@@ -252,8 +254,11 @@ int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kin
         "step kernel of a seed set: the E_v accumulators (nv doubles per seed) do not fit into the LDS of this device",
         nullptr, // PASS_PATH
         "step kernel of a length scan: the E_v accumulators (nv doubles per length) do not fit into the LDS of this device",
-        "step kernel of a length scan with scan seeds: the E_v accumulators (nv doubles per seed and length) do not fit into the LDS of this device" };
-    static_assert(PASS_SPEC == 1 && PASS_STEP == 2 && PASS_SEEDS == 3 && PASS_SCAN == 5 && PASS_SCAN_SEEDS == 6, "too_big[] is indexed by PassKind");
+        "step kernel of a length scan with scan seeds: the E_v accumulators (nv doubles per seed and length) do not fit into the LDS of this device",
+        "step kernel of an emission plan with ASE seeds: the E_v accumulators (nv doubles for ASE and per seed) do not fit into the LDS of this device" };
+    static_assert(PASS_SPEC == 1 && PASS_STEP == 2 && PASS_SEEDS == 3 && PASS_SCAN == 5 && PASS_SCAN_SEEDS == 6 && PASS_ASE_SEEDS == 7 &&
+                      sizeof(too_big) / sizeof(too_big[0]) == 8,
+                  "too_big[] is indexed by PassKind");
     if (too_big[kind] && s.lds > f.lds_limit)
         return fail_arg(too_big[kind]);
     if (s.grid == 0)
@@ -316,6 +321,34 @@ int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kin
                 return fail_arg("step kernel of a length scan with scan seeds: the factor tables of the seeds were not built for this ray grid");
         }
         return launch(p, rt::rt_step_scan_seeds_kernel, s.grid, block, s.lds, stream, a);
+    }
+    if (kind == PASS_ASE_SEEDS) { // an emission plan with ASE seeds: block 0 the ASE record, block 1 + s the record of seed s
+        if (f.n_seed < 1 || f.n_seed > RT_N_SEED_MAX || !f.use_emis || !p->seeds_dev)
+            return fail_arg("step kernel of an emission plan with ASE seeds: not an emission run of 1 .. RT_N_SEED_MAX seeds with its records allocated");
+        if (p->seeds_doubles < (size_t) (1 + f.n_seed) * p->seeds_stride)
+            return fail_arg("step kernel of an emission plan with ASE seeds: the records of this run are smaller than 1 + n_seed blocks");
+        rt::AseSeedsKArg a = pass_args<rt::AseSeedsKArg>(fa);
+        a.hot.seed_fk  = nullptr; // (an emission plan has no creation seed)
+        a.hot.flags &= ~(unsigned) rt::FQ_EXCLUSIVE; // (nf of every record by atomics: the plain store is rt_step_kernel's alone)
+        a.set.n_seed   = f.n_seed;
+        // the factor tables of the seeds serve a forward ray GRID only, and the ray set decides: a list set behind the grid
+        // (rt_hip_plan_set_rays resets P.rays, not the tables) takes seed_factor at its launch rays.  (A seeded plan has
+        // P.rays.sf for this; an emission plan has no creation seed and hence none.)
+        const bool grid_tabs = p->P.rays.gx && !p->P.rays.list && p->P.method != 1 && p->seedset_sf[0] != nullptr;
+        for (int r = 0; r <= f.n_seed; r++) {
+            double *blk    = p->seeds_dev + (size_t) r * p->seeds_stride;
+            a.set.out[r]   = rt::SeedRec{ blk, blk + p->seeds_nf_off, blk + p->seeds_ang_off };
+            a.set.scale[r] = r == 0 ? p->P.scale : p->ase_scale[r - 1];
+        }
+        for (int i = 0; i < f.n_seed; i++) {
+            a.set.fk[i]   = p->seed_set[i].f[4];
+            a.set.sf[i]   = grid_tabs ? p->seedset_sf[i] : nullptr;
+            a.set.sin[i]  = grid_tabs ? p->seedset_sin[i] : nullptr;
+            a.set.seed[i] = p->seed_set[i];
+            if (grid_tabs && (!a.set.sf[i] || !a.set.sin[i]))
+                return fail_arg("step kernel of an emission plan with ASE seeds: the factor tables of the seeds were not built for this ray grid");
+        }
+        return launch(p, ase_seeds_kernel(f.s6()), s.grid, block, s.lds, stream, a);
     }
     // a seed set (a seeded plan: gain-only): one record per seed
     rt::SeedsKArg a = pass_args<rt::SeedsKArg>(fa);
@@ -439,6 +472,7 @@ int plan_repeat_checked(rt_hip_plan *p)
     HIP_TRY(hipMemsetAsync(p->ctl->seed_code, 0, sizeof(p->ctl->seed_code), stream));
     HIP_TRY(hipMemsetAsync(p->ctl->len_code, 0, sizeof(p->ctl->len_code), stream));
     HIP_TRY(hipMemsetAsync(p->ctl->seed_len_code, 0, sizeof(p->ctl->seed_len_code), stream));
+    HIP_TRY(hipMemsetAsync(p->ctl->rec_code, 0, sizeof(p->ctl->rec_code), stream));
     HIP_TRY(hipMemsetAsync(p->ctl->next_tile_f, 0, sizeof(p->ctl->next_tile_f), stream));
     const bool step = p->last_step; // a step run: the step kernel honours the same marks, E_v and nf start over
     RunFacts f          = run_facts(p);
@@ -446,7 +480,7 @@ int plan_repeat_checked(rt_hip_plan *p)
     if (scan)
         f.n_seed = scan_seeds;
     const Tuning t      = read_tuning();
-    const PassKind kind = step ? (scan ? (scan_seeds > 0 ? PASS_SCAN_SEEDS : PASS_SCAN) : f.n_seed > 0 ? PASS_SEEDS : PASS_STEP) : PASS_FREQ;
+    const PassKind kind = step ? (scan ? (scan_seeds > 0 ? PASS_SCAN_SEEDS : PASS_SCAN) : f.n_seed > 0 ? (f.use_emis ? PASS_ASE_SEEDS : PASS_SEEDS) : PASS_STEP) : PASS_FREQ;
     int rc              = launch_pass(p, f, t, kind, stream, 1, p->bad_dev);
     if (rc == RT_OK) {
         if (step && p->last_step_lent) { // (the caller's buffers: exactly the K and nx * ny doubles that are the run's)

@@ -632,7 +632,10 @@ int rtr::plan_build_seedset_tabs(rt_hip_plan *p)
     }
     const rt::DevRays &R = p->P.rays;
     const int n_set = p->n_seed > 0 ? p->n_seed : p->n_scan_seed; // (a seed set, or the seeds of a scan: never both)
-    if (n_set < 1 || !R.sf) // (R.sf: a ray grid, a seeded plan, the forward method)
+    // (R.sf: a ray grid, a seeded plan, the forward method; ASE seeds on an emission plan, which has no creation seed and
+    // hence no R.sf: the same grid and method)
+    const bool ase_grid = p->P.use_emis && p->n_seed > 0 && !R.list && R.gx && p->P.method != 1;
+    if (n_set < 1 || (!R.sf && !ase_grid))
         return RT_OK;
     const size_t nn = (size_t) R.ngx + (size_t) R.ngy + (size_t) R.nga + (size_t) R.ngb;
     const size_t per_seed = align_up(nn * sizeof(double) + nn, 256);
@@ -1056,7 +1059,8 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
     const int n_seed = p->n_seed; // a seed set: one record per seed, all in one allocation of the plan
     const int scan_L = p->scan_on ? p->P.L : 0; // a length scan: one record per length, the same allocation (never both)
     const int scan_seeds = scan_L > 0 ? p->n_scan_seed : 0; // the seeds of the scan: one record per (seed, length), seed 0's curve first
-    const int n_rec  = n_seed > 0 ? n_seed : scan_seeds > 0 ? scan_seeds * scan_L : scan_L;
+    const bool ase   = n_seed > 0 && p->P.use_emis; // ASE seeds on an emission plan: the ASE record in block 0, the seeds behind it
+    const int n_rec  = n_seed > 0 ? n_seed + (ase ? 1 : 0) : scan_seeds > 0 ? scan_seeds * scan_L : scan_L;
     if (scan_L > 0) {
         if (!step || p->path_on)
             return fail_arg("rt_hip_plan_run: the length scan is on, which runs in step mode only");
@@ -1163,6 +1167,7 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
     p->last_step   = step;
     p->last_step_lent = lent;
     p->last_n_seed = n_seed;
+    p->last_ase    = ase;
     p->last_scan_L = scan_L;
     p->last_scan_n_seed = scan_seeds;
     p->spec_last   = p->spec_sel;
@@ -1357,7 +1362,7 @@ int rt_hip_plan_fetch_step(rt_hip_plan *p, double *E_v, double *nf, double *I_an
 
 int rt_hip_plan_fetch_seed_step(rt_hip_plan *p, int s, double *E_v, double *nf, double *I_ang, unsigned int *failure_code)
 {
-    if (!p || !p->ran || !p->last_step || p->last_n_seed < 1)
+    if (!p || !p->ran || !p->last_step || p->last_n_seed < 1 || p->last_ase)
         return fail_arg("rt_hip_plan_fetch_seed_step: the last run was not a step run with a seed set");
     if (s < 0 || s >= p->last_n_seed)
         return fail_arg("rt_hip_plan_fetch_seed_step: no such seed in the set of the last run");
@@ -1380,7 +1385,7 @@ int rt_hip_plan_fetch_seed_step(rt_hip_plan *p, int s, double *E_v, double *nf, 
 
 int rt_hip_plan_seed_step_ptrs(rt_hip_plan *p, int s, double **E_v_dev, double **nf_dev, double **iang_dev)
 {
-    if (!p || !p->ran || !p->last_step || p->last_n_seed < 1)
+    if (!p || !p->ran || !p->last_step || p->last_n_seed < 1 || p->last_ase)
         return fail_arg("rt_hip_plan_seed_step_ptrs: the last run was not a step run with a seed set");
     if (s < 0 || s >= p->last_n_seed)
         return fail_arg("rt_hip_plan_seed_step_ptrs: no such seed in the set of the last run");
@@ -1587,6 +1592,73 @@ static int seeds_install(rt_hip_plan *p, int n_seed, const rt_seed *seeds, bool 
     }
     return plan_build_seedset_tabs(p);
 }
+
+
+extern "C" {
+
+// ASE seeds: up to RT_N_SEED_MAX seed beams on an EMISSION plan (include/rt_hip.h).  The seeds travel as a set's do
+// (seeds_validate, seeds_install); what makes them ASE seeds is the plan: use_emis with n_seed > 0.
+int rt_hip_plan_set_ase_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds, const double *scales)
+{
+    if (!p)
+        return fail_arg("rt_hip_plan_set_ase_seeds: NULL plan");
+    if (p->P.has_seed || !p->P.use_emis)
+        return fail_arg("rt_hip_plan_set_ase_seeds: not an emission plan (created without a seed, tables with E0)");
+    const int rv = seeds_validate(p, "rt_hip_plan_set_ase_seeds", n_seed, seeds);
+    if (rv != RT_OK)
+        return rv;
+    if (p->scan_on)
+        return fail_arg("rt_hip_plan_set_ase_seeds: the length scan is on (ASE seeds and a length scan exclude each other)");
+    if (n_seed > 0 && (p->path_on || p->spectra_on))
+        return fail_arg("rt_hip_plan_set_ase_seeds: the path tracer or spectra mode is enabled (ASE seeds run in step mode only)");
+    const int rc = seeds_install(p, n_seed, seeds, false);
+    if (rc != RT_OK)
+        return rc;
+    for (int s = 0; s < RT_N_SEED_MAX; s++)
+        p->ase_scale[s] = (s < n_seed && scales) ? scales[s] : p->P.scale;
+    return RT_OK;
+}
+
+int rt_hip_plan_fetch_full_step(rt_hip_plan *p, int r, double *E_v, double *nf, double *I_ang, unsigned int *failure_code)
+{
+    if (!p || !p->ran || !p->last_step || !p->last_ase)
+        return fail_arg("rt_hip_plan_fetch_full_step: the last run was not a step run of an emission plan with ASE seeds");
+    if (r < 0 || r > p->last_n_seed)
+        return fail_arg("rt_hip_plan_fetch_full_step: r must be 0 (ASE) .. n_seed of the last run");
+    rt::DevCtl c;
+    bool staged  = false;
+    const int rs = plan_settle(p, c, staged); // (a failing run is repeated here as rt_hip_plan_fetch repeats it)
+    if (rs != RT_OK)
+        return rs;
+    const double *blk = p->seeds_dev + (size_t) r * p->seeds_stride;
+    if (E_v)
+        HIP_TRY(hipMemcpy(E_v, blk, (size_t) p->P.K * sizeof(double), hipMemcpyDeviceToHost));
+    if (nf)
+        HIP_TRY(hipMemcpy(nf, blk + p->seeds_nf_off, (size_t) p->P.beam.nx * (size_t) p->P.beam.ny * sizeof(double), hipMemcpyDeviceToHost));
+    if (I_ang)
+        HIP_TRY(hipMemcpy(I_ang, blk + p->seeds_ang_off, p->n_iang * sizeof(double), hipMemcpyDeviceToHost));
+    if (failure_code)
+        *failure_code = c.rec_code[r];
+    return RT_OK;
+}
+
+int rt_hip_plan_full_step_ptrs(rt_hip_plan *p, int r, double **E_v_dev, double **nf_dev, double **iang_dev)
+{
+    if (!p || !p->ran || !p->last_step || !p->last_ase)
+        return fail_arg("rt_hip_plan_full_step_ptrs: the last run was not a step run of an emission plan with ASE seeds");
+    if (r < 0 || r > p->last_n_seed)
+        return fail_arg("rt_hip_plan_full_step_ptrs: r must be 0 (ASE) .. n_seed of the last run");
+    double *blk = p->seeds_dev + (size_t) r * p->seeds_stride;
+    if (E_v_dev)
+        *E_v_dev = blk;
+    if (nf_dev)
+        *nf_dev = blk + p->seeds_nf_off;
+    if (iang_dev)
+        *iang_dev = blk + p->seeds_ang_off;
+    return RT_OK;
+}
+
+} // extern "C"
 
 extern "C" {
 
@@ -1904,6 +1976,46 @@ int rt_hip_seed_length_scan_loop(int device, int N, const rt_beam *beam, const r
     // (method, N, the creation seed, the tables of the seeds: the plan's entry points refuse what the scan does not take)
     return host_pointer_loop(device, N, beam, gain, seed, method, rays, n_rays, scale, nullptr, E_v, nf, I_ang, failure_codes,
                              failed_rays, max_failed, n_failed, stats, true, n_seed, seeds);
+}
+
+// The whole per-step record through host pointers: an emission plan of its own with the seeds as ASE seeds, the list
+// uploaded, one run; row 0 of every output is the ASE record, row 1 + s seed s.
+int rt_hip_full_step_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, int method, const rt_ray *rays, size_t n_rays,
+                          double scale, int n_seed, const rt_seed *seeds, const double *scales, double *E_v, double *nf, double *I_ang,
+                          unsigned int *failure_codes, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats)
+{
+    if (!beam)
+        return fail_arg("rt_hip_full_step_loop: NULL beam");
+    if (!E_v || !nf || !I_ang)
+        return fail_arg("rt_hip_full_step_loop: NULL output");
+    if (!rays && n_rays)
+        return fail_arg("rt_hip_full_step_loop: NULL ray list");
+    if (n_rays > MAX_LIST_RAYS)
+        return fail_arg("rt_hip_full_step_loop: 2^32 - 4096 rays or more: split the call");
+    if (n_seed < 1 || n_seed > RT_N_SEED_MAX || !seeds)
+        return fail_arg("rt_hip_full_step_loop: n_seed must be 1 .. RT_N_SEED_MAX, with seeds");
+    hipStream_t q  = lease_queue(device);
+    rt_hip_plan *p = nullptr;
+    int rc         = plan_create_on(&p, q, device, N, beam, gain, nullptr, method, scale);
+    if (rc != RT_OK) {
+        release_queue(device, q);
+        return rc;
+    }
+    rc = rt_hip_plan_enable_step(p, 1);
+    if (rc == RT_OK)
+        rc = rt_hip_plan_set_ase_seeds(p, n_seed, seeds, scales);
+    if (rc == RT_OK)
+        rc = plan_set_rays_deferred(p, rays, n_rays);
+    if (rc == RT_OK)
+        rc = rt_hip_plan_run(p, q, nullptr, nullptr);
+    if (rc == RT_OK)
+        rc = rt_hip_plan_fetch(p, nullptr, nullptr, nullptr, failed_rays, max_failed, n_failed, stats);
+    for (int r = 0; rc == RT_OK && r <= n_seed; r++)
+        rc = rt_hip_plan_fetch_full_step(p, r, E_v + (size_t) r * (size_t) beam->nv, nf + (size_t) r * (size_t) beam->nx * (size_t) beam->ny,
+                                         I_ang + (size_t) r * (size_t) beam->na * (size_t) beam->nb, failure_codes ? failure_codes + r : nullptr);
+    rt_hip_plan_destroy(p); // waits for whatever is still in flight
+    release_queue(device, q);
+    return rc;
 }
 
 int rt_hip_calc_rays(int device, int N, double dz, const rt_gain *gain, const rt_seed *seed, int K, int method, const double *rays,

@@ -81,6 +81,12 @@ struct rt_hip_plan {
     size_t seeds_doubles = 0;                                    // doubles of the allocation
     size_t seeds_stride = 0, seeds_nf_off = 0, seeds_ang_off = 0; // doubles: block to block, E_v to nf, E_v to I_ang
     int last_n_seed = 0;                                         // seeds of the last run (0: it ran without a set)
+    // ASE seeds (rt_hip_plan_set_ase_seeds): the n_seed seeds above on an EMISSION plan (P.use_emis, no creation seed -- the
+    // one case of use_emis with n_seed > 0).  A step run then leaves 1 + n_seed blocks of the allocation above from one march
+    // (rt_step_ase_seeds.hip): block 0 the plan's own emission record, block 1 + s the gain-only record of seed s with scale
+    // ase_scale[s].  The tables live where a set's live; on a forward ray grid the factor tables are built as for a set.
+    double ase_scale[RT_N_SEED_MAX] = {};
+    bool last_ase = false; // the last run left such records (last_n_seed seeds behind the ASE block)
     // length scan (rt_hip_plan_enable_length_scan): one step record per plasma length n = 2 .. N from one forward march.
     // The records are the blocks of the seed-set allocation above (seeds_dev, seeds_stride, ...: a scan and a set exclude
     // each other), block n - 2 for n lengths; scan_bnd holds the state with which every ray crossed every length boundary

@@ -15,7 +15,13 @@
 //   EV_SUM_INDEX      index in lds_ev of the accumulator entry of frequency kb.  It is substituted without parentheses,
 //                     `lds_ev[EV_SUM_INDEX + (lane >> 4)]`: as `(lds_ev + index)[lane >> 4]` nine instruction streams
 //                     changed.  (kb + 3 < Kp: every accumulator has Kp entries.)
+//   EV_SUM_SCALE      (optional) the scale of this record where it is not H.scale (rt_step_ase_seeds.hip: one scale per
+//                     record); undefined, H.scale as ever
 // Declares nothing outside its block.
+#ifndef EV_SUM_SCALE
+#define EV_SUM_SCALE H.scale
+#define EV_SUM_SCALE_IS_DEFAULT
+#endif
 {
 #pragma unroll
     for (int j = 0; j < VEC; j++)
@@ -29,5 +35,9 @@
     t = dpp_step<0x114, 0xf>(t);
     t = dpp_step<0x118, 0xf>(t);
     if ((lane & 15) == 15 && t != 0.0)
-        unsafeAtomicAdd(&lds_ev[EV_SUM_INDEX + (lane >> 4)], t * H.scale); // RayTraceImageCPU.cpp:59, once per summed value
+        unsafeAtomicAdd(&lds_ev[EV_SUM_INDEX + (lane >> 4)], t * EV_SUM_SCALE); // RayTraceImageCPU.cpp:59, once per summed value
 }
+#ifdef EV_SUM_SCALE_IS_DEFAULT
+#undef EV_SUM_SCALE
+#undef EV_SUM_SCALE_IS_DEFAULT
+#endif

@@ -15,6 +15,10 @@
 //                   (rt_freq.hip: the load behind the test, no scratch; spectra and step mode)
 //   TILE_REREAD     the lane may read its record again on the irregular path (else e = 0): true in image mode, `have` in
 //                   step mode, `live` in spectra mode, whose other lanes carry zeroed slots
+//   TILE_BATCH_ROWS_LOADED   (optional, rt_step_ase_seeds.hip) the including scope has declared FVec w[SF] and loaded the
+//                   rows of this batch itself, because something else reads them as well; undefined, the text is as it was
+//   TILE_BATCH_SLOT(g, w)    (optional, likewise) statements on the gain sum and the row of every slot of the generic-S
+//                   emission loop; undefined, nothing
 // Writes: double Iv[VEC], declared by the including scope.  No masking: what a lane without a live ray gets is the
 // including function's to drop; the padding columns K .. Kp-1 carry w = dv = 0, hence Iv = 0.
 if (EMIS) {
@@ -22,8 +26,10 @@ if (EMIS) {
     for (int j = 0; j < VEC; j++)
         Iv[j] = 0.0;
     if (SF) {
+#ifndef TILE_BATCH_ROWS_LOADED
         FVec w[SF ? SF : 1];
         load_rows(w, kb);
+#endif
         if (all_small) {
 #pragma unroll
             for (int s = 0; s < SF; s++)
@@ -70,6 +76,9 @@ if (EMIS) {
 #pragma unroll
             for (int j = 0; j < VEC; j++)
                 wnan[j] = wnan[j] || !(fabsf(w.v[j]) <= FLT_MAX);
+#ifdef TILE_BATCH_SLOT
+            TILE_BATCH_SLOT(g1, w)
+#endif
             if (fabsf(g1) >= RT_RS_MIN && fabsf(g1) <= H.gs_cap && !exact_emis) {
                 const double r1 = div_fast((double) e1, (double) g1);
                 ase_step(Iv, g1, r1, w.v, tab);
