@@ -88,6 +88,34 @@ class HipLibrary:
             raise RayTraceError(f"{what} failed (status {rc}): {msg}")
 
 
+class _View:  # the CUDA array interface, which torch.as_tensor reads
+    def __init__(self, ptr: int, shape: tuple):
+        self.__cuda_array_interface__ = dict(shape=shape, typestr="<f8", data=(ptr, False), version=2, strides=None)
+
+
+def _view(ptr: int, shape: tuple, device: int):
+    """torch view (float64, on `device`, no copy) of the doubles at device pointer ptr."""
+    import torch
+
+    return torch.as_tensor(_View(ptr, shape), device=torch.device("cuda", device))
+
+
+def _seed_array(seeds, who: str, what: str) -> tuple:
+    """(seeds as a list, their RtSeed array, what the array points into) for `who`; more than RT_N_SEED_MAX of them (`what`:
+    where they would have to fit) or an entry that is not a Seed is a ValueError."""
+    seeds = list(seeds)
+    if len(seeds) > cabi.RT_N_SEED_MAX:
+        raise ValueError(f"{who}: {len(seeds)} seeds given, at most RT_N_SEED_MAX = {cabi.RT_N_SEED_MAX} fit into {what}")
+    for i, sd in enumerate(seeds):
+        if not isinstance(sd, Seed):
+            raise ValueError(f"{who}: entry {i} is a {type(sd).__name__}, not a Seed")
+    keep = []
+    arr = (cabi.RtSeed * max(1, len(seeds)))()
+    for i, sd in enumerate(seeds):
+        arr[i] = cabi.seed_record(sd, keep)
+    return seeds, arr, keep
+
+
 class Plan:
     """A problem resident in HBM: tables uploaded once, runnable many times."""
 
@@ -215,16 +243,10 @@ class Plan:
         the plan's next run."""
         import torch
 
-        class _View:  # the CUDA array interface, which torch.as_tensor reads
-            pass
-
         ptr = self.spectra_ptr()
         if not ptr or not self.n_rays:
             return torch.empty((0, self.problem.beam.nv), dtype=torch.float64, device=torch.device("cuda", self.device))
-        v = _View()
-        v.__cuda_array_interface__ = dict(shape=(self.n_rays, self.problem.beam.nv), typestr="<f8", data=(ptr, False),
-                                          version=2, strides=None)
-        return torch.as_tensor(v, device=torch.device("cuda", self.device))
+        return _view(ptr, (self.n_rays, self.problem.beam.nv), self.device)
 
     def enable_step(self, on: bool = True) -> "Plan":
         """Step mode (include/rt_hip.h): a run produces E_v, nf and I_ang -- the image cube reduced on the way, never
@@ -269,36 +291,37 @@ class Plan:
         """torch views (float64, on the plan's device, no copy) of E_v [nv], nf [ny][nx] and I_ang [nb][na] (the plan's own
         buffer; None if every run was handed the caller's) of the last step run: valid until the plan's next run; read
         them on the run's stream or after a fetch."""
-        import torch
-
-        class _View:  # the CUDA array interface, which torch.as_tensor reads
-            pass
-
-        def view(ptr, shape):
-            v = _View()
-            v.__cuda_array_interface__ = dict(shape=shape, typestr="<f8", data=(ptr, False), version=2, strides=None)
-            return torch.as_tensor(v, device=torch.device("cuda", self.device))
-
-        b = self.problem.beam
         e, n = self.step_ptrs()
-        ang = self.iang_ptr
-        return dict(E_v=view(e, (b.nv,)), nf=view(n, (b.ny, b.nx)), I_ang=view(ang, (b.nb, b.na)) if ang else None)
+        return self._record_views((e, n, self.iang_ptr))
+
+    # -- the records of a run that leaves several (a seed set, ASE seeds, a length scan, the seeds of a scan) --
+    def _fetch_record(self, name: str, *index) -> dict:
+        """dict(E_v [nv], nf [nx * ny], I_ang [na * nb], failure_code) by the C entry point `name` at `index`."""
+        b = self.problem.beam
+        E_v, nf, iang = np.empty(b.nv), np.empty(b.nx * b.ny), np.empty(b.na * b.nb)
+        code = C.c_uint(0)
+        self.hl.check(getattr(self.hl.lib, name)(self._h, *index, cabi._dp(E_v), cabi._dp(nf), cabi._dp(iang), C.byref(code)), name)
+        return dict(E_v=E_v, nf=nf, I_ang=iang, failure_code=code.value)
+
+    def _record_ptrs(self, name: str, *index) -> tuple:
+        """Device pointers (E_v, nf, I_ang) by the C entry point `name` at `index`."""
+        e, n, a = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self.hl.check(getattr(self.hl.lib, name)(self._h, *(int(i) for i in index), C.byref(e), C.byref(n), C.byref(a)), name)
+        return int(e.value or 0), int(n.value or 0), int(a.value or 0)
+
+    def _record_views(self, ptrs: tuple) -> dict:
+        """torch views of E_v [nv], nf [ny][nx] and I_ang [nb][na] (None without a pointer) at the pointers of a record."""
+        b = self.problem.beam
+        e, n, a = ptrs
+        return dict(E_v=_view(e, (b.nv,), self.device), nf=_view(n, (b.ny, b.nx), self.device),
+                    I_ang=_view(a, (b.nb, b.na), self.device) if a else None)
 
     # -- seed set -----------------------------------------------------------
     def set_seeds(self, seeds) -> "Plan":
         """A seed set (include/rt_hip.h, rt_hip_plan_set_seeds): up to RT_N_SEED_MAX Seed records whose step records one
         run leaves, from one march; [] removes the set.  The plan must have been created with a seed.  More seeds than
         that, or anything that is not a Seed, is a ValueError raised here, before any native call."""
-        seeds = list(seeds)
-        if len(seeds) > cabi.RT_N_SEED_MAX:
-            raise ValueError(f"set_seeds: {len(seeds)} seeds given, at most RT_N_SEED_MAX = {cabi.RT_N_SEED_MAX} fit into a set")
-        for i, sd in enumerate(seeds):
-            if not isinstance(sd, Seed):
-                raise ValueError(f"set_seeds: entry {i} is a {type(sd).__name__}, not a Seed")
-        keep = []
-        arr = (cabi.RtSeed * max(1, len(seeds)))()
-        for i, sd in enumerate(seeds):
-            arr[i] = cabi.seed_record(sd, keep)
+        seeds, arr, _keep = _seed_array(seeds, "set_seeds", "a set")
         self.hl.check(self.hl.lib.rt_hip_plan_set_seeds(self._h, len(seeds), arr if seeds else None), "rt_hip_plan_set_seeds")
         self._n_seed = len(seeds)
         return self
@@ -306,43 +329,17 @@ class Plan:
     def fetch_seed_steps(self) -> list:
         """[dict(E_v [nv], nf [nx * ny], I_ang [na * nb], failure_code)] per seed of the set of the last step run (waits for
         it; a failing run is repeated in the checking mode first)."""
-        b = self.problem.beam
-        out = []
-        for s in range(getattr(self, "_n_seed", 0)):
-            E_v, nf, iang = np.empty(b.nv), np.empty(b.nx * b.ny), np.empty(b.na * b.nb)
-            code = C.c_uint(0)
-            self.hl.check(self.hl.lib.rt_hip_plan_fetch_seed_step(self._h, s, cabi._dp(E_v), cabi._dp(nf), cabi._dp(iang), C.byref(code)),
-                          "rt_hip_plan_fetch_seed_step")
-            out.append(dict(E_v=E_v, nf=nf, I_ang=iang, failure_code=code.value))
-        return out
+        return [self._fetch_record("rt_hip_plan_fetch_seed_step", s) for s in range(getattr(self, "_n_seed", 0))]
 
     def seed_step_ptrs(self, s: int) -> tuple:
         """Device pointers (E_v, nf, I_ang) of the record of seed s of the last step run with a set."""
-        e, n, a = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        self.hl.check(self.hl.lib.rt_hip_plan_seed_step_ptrs(self._h, int(s), C.byref(e), C.byref(n), C.byref(a)),
-                      "rt_hip_plan_seed_step_ptrs")
-        return int(e.value or 0), int(n.value or 0), int(a.value or 0)
+        return self._record_ptrs("rt_hip_plan_seed_step_ptrs", s)
 
     def seed_step_tensors(self) -> list:
         """Per seed of the set: torch views (float64, on the plan's device, no copy) of E_v [nv], nf [ny][nx] and I_ang
         [nb][na] of the last step run -- blocks of one allocation, valid until the plan's next run; read them on the
         run's stream or after a fetch."""
-        import torch
-
-        class _View:  # the CUDA array interface, which torch.as_tensor reads
-            pass
-
-        def view(ptr, shape):
-            v = _View()
-            v.__cuda_array_interface__ = dict(shape=shape, typestr="<f8", data=(ptr, False), version=2, strides=None)
-            return torch.as_tensor(v, device=torch.device("cuda", self.device))
-
-        b = self.problem.beam
-        out = []
-        for s in range(getattr(self, "_n_seed", 0)):
-            e, n, a = self.seed_step_ptrs(s)
-            out.append(dict(E_v=view(e, (b.nv,)), nf=view(n, (b.ny, b.nx)), I_ang=view(a, (b.nb, b.na))))
-        return out
+        return [self._record_views(self.seed_step_ptrs(s)) for s in range(getattr(self, "_n_seed", 0))]
 
     # -- ASE seeds ----------------------------------------------------------
     def set_ase_seeds(self, seeds, scales=None) -> "Plan":
@@ -351,21 +348,12 @@ class Plan:
         march, the gain-only record of the same problem created with each seed, scale scales[s] (None: the plan's scale);
         [] removes them.  More seeds than that, anything that is not a Seed, or scales of another length is a ValueError
         raised here, before any native call."""
-        seeds = list(seeds)
-        if len(seeds) > cabi.RT_N_SEED_MAX:
-            raise ValueError(f"set_ase_seeds: {len(seeds)} seeds given, at most RT_N_SEED_MAX = {cabi.RT_N_SEED_MAX} fit into a step record")
-        for i, sd in enumerate(seeds):
-            if not isinstance(sd, Seed):
-                raise ValueError(f"set_ase_seeds: entry {i} is a {type(sd).__name__}, not a Seed")
+        seeds, arr, _keep = _seed_array(seeds, "set_ase_seeds", "a step record")
         sc = None
         if scales is not None:
             sc = np.ascontiguousarray(scales, dtype=np.float64)
             if sc.shape != (len(seeds),):
                 raise ValueError(f"set_ase_seeds: {sc.size} scales for {len(seeds)} seeds")
-        keep = []
-        arr = (cabi.RtSeed * max(1, len(seeds)))()
-        for i, sd in enumerate(seeds):
-            arr[i] = cabi.seed_record(sd, keep)
         self.hl.check(self.hl.lib.rt_hip_plan_set_ase_seeds(self._h, len(seeds), arr if seeds else None,
                                                             cabi._dp(sc) if sc is not None and len(seeds) else None),
                       "rt_hip_plan_set_ase_seeds")
@@ -375,42 +363,18 @@ class Plan:
     def fetch_full_step(self) -> dict:
         """dict(ase=rec, seeds=[rec ...]) of the last step run with ASE seeds (waits for it; a failing run is repeated in
         the checking mode first); every rec is dict(E_v [nv], nf [nx * ny], I_ang [na * nb], failure_code)."""
-        b = self.problem.beam
-        recs = []
-        for r in range(1 + self._n_ase_seed):
-            E_v, nf, iang = np.empty(b.nv), np.empty(b.nx * b.ny), np.empty(b.na * b.nb)
-            code = C.c_uint(0)
-            self.hl.check(self.hl.lib.rt_hip_plan_fetch_full_step(self._h, r, cabi._dp(E_v), cabi._dp(nf), cabi._dp(iang), C.byref(code)),
-                          "rt_hip_plan_fetch_full_step")
-            recs.append(dict(E_v=E_v, nf=nf, I_ang=iang, failure_code=code.value))
+        recs = [self._fetch_record("rt_hip_plan_fetch_full_step", r) for r in range(1 + self._n_ase_seed)]
         return dict(ase=recs[0], seeds=recs[1:])
 
     def full_step_ptrs(self, r: int) -> tuple:
         """Device pointers (E_v, nf, I_ang) of record r (0: ASE, 1 + s: seed s) of the last step run with ASE seeds."""
-        e, n, a = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        self.hl.check(self.hl.lib.rt_hip_plan_full_step_ptrs(self._h, int(r), C.byref(e), C.byref(n), C.byref(a)),
-                      "rt_hip_plan_full_step_ptrs")
-        return int(e.value or 0), int(n.value or 0), int(a.value or 0)
+        return self._record_ptrs("rt_hip_plan_full_step_ptrs", r)
 
     def full_step_tensors(self) -> dict:
         """dict(ase=views, seeds=[views ...]): torch views (float64, on the plan's device, no copy) of E_v [nv], nf [ny][nx]
         and I_ang [nb][na] of every record of the last step run with ASE seeds -- blocks of one allocation, valid until the
         plan's next run; read them on the run's stream or after a fetch."""
-        import torch
-
-        class _View:  # the CUDA array interface, which torch.as_tensor reads
-            pass
-
-        def view(ptr, shape):
-            v = _View()
-            v.__cuda_array_interface__ = dict(shape=shape, typestr="<f8", data=(ptr, False), version=2, strides=None)
-            return torch.as_tensor(v, device=torch.device("cuda", self.device))
-
-        b = self.problem.beam
-        recs = []
-        for r in range(1 + self._n_ase_seed):
-            e, n, a = self.full_step_ptrs(r)
-            recs.append(dict(E_v=view(e, (b.nv,)), nf=view(n, (b.ny, b.nx)), I_ang=view(a, (b.nb, b.na))))
+        recs = [self._record_views(self.full_step_ptrs(r)) for r in range(1 + self._n_ase_seed)]
         return dict(ase=recs[0], seeds=recs[1:])
 
     # -- length scan --------------------------------------------------------
@@ -441,43 +405,17 @@ class Plan:
     def fetch_length_steps(self) -> list:
         """[dict(n, E_v [nv], nf [nx * ny], I_ang [na * nb], failure_code)] for n = 2 .. N lengths of the last step run with
         the scan on (waits for it; a failing run is repeated in the checking mode first)."""
-        b = self.problem.beam
-        out = []
-        for n in range(2, self.problem.N + 1 if getattr(self, "_scan", False) else 2):
-            E_v, nf, iang = np.empty(b.nv), np.empty(b.nx * b.ny), np.empty(b.na * b.nb)
-            code = C.c_uint(0)
-            self.hl.check(self.hl.lib.rt_hip_plan_fetch_length_step(self._h, n, cabi._dp(E_v), cabi._dp(nf), cabi._dp(iang), C.byref(code)),
-                          "rt_hip_plan_fetch_length_step")
-            out.append(dict(n=n, E_v=E_v, nf=nf, I_ang=iang, failure_code=code.value))
-        return out
+        return [dict(n=n, **self._fetch_record("rt_hip_plan_fetch_length_step", n)) for n in self._scan_seed_range()[1]]
 
     def length_step_ptrs(self, n: int) -> tuple:
         """Device pointers (E_v, nf, I_ang) of the record of n lengths of the last step run with the scan on."""
-        e, f, a = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        self.hl.check(self.hl.lib.rt_hip_plan_length_step_ptrs(self._h, int(n), C.byref(e), C.byref(f), C.byref(a)),
-                      "rt_hip_plan_length_step_ptrs")
-        return int(e.value or 0), int(f.value or 0), int(a.value or 0)
+        return self._record_ptrs("rt_hip_plan_length_step_ptrs", n)
 
     def length_step_tensors(self) -> list:
         """Per n = 2 .. N: dict(n, E_v [nv], nf [ny][nx], I_ang [nb][na]) of torch views (float64, on the plan's device, no
         copy) of the last step run with the scan on -- blocks of one allocation, valid until the plan's next run; read them
         on the run's stream or after a fetch."""
-        import torch
-
-        class _View:  # the CUDA array interface, which torch.as_tensor reads
-            pass
-
-        def view(ptr, shape):
-            v = _View()
-            v.__cuda_array_interface__ = dict(shape=shape, typestr="<f8", data=(ptr, False), version=2, strides=None)
-            return torch.as_tensor(v, device=torch.device("cuda", self.device))
-
-        b = self.problem.beam
-        out = []
-        for n in range(2, self.problem.N + 1 if getattr(self, "_scan", False) else 2):
-            e, f, a = self.length_step_ptrs(n)
-            out.append(dict(n=n, E_v=view(e, (b.nv,)), nf=view(f, (b.ny, b.nx)), I_ang=view(a, (b.nb, b.na))))
-        return out
+        return [dict(n=n, **self._record_views(self.length_step_ptrs(n))) for n in self._scan_seed_range()[1]]
 
     # -- the seeds of a scan ------------------------------------------------
     def set_scan_seeds(self, seeds) -> "Plan":
@@ -485,16 +423,7 @@ class Plan:
         step run with the scan on then leaves one record per seed and length n = 2 .. N from one march; [] removes them.
         The scan must be on and the plan created with a seed.  More seeds than that, or anything that is not a Seed, is a
         ValueError raised here, before any native call."""
-        seeds = list(seeds)
-        if len(seeds) > cabi.RT_N_SEED_MAX:
-            raise ValueError(f"set_scan_seeds: {len(seeds)} seeds given, at most RT_N_SEED_MAX = {cabi.RT_N_SEED_MAX} fit into a scan")
-        for i, sd in enumerate(seeds):
-            if not isinstance(sd, Seed):
-                raise ValueError(f"set_scan_seeds: entry {i} is a {type(sd).__name__}, not a Seed")
-        keep = []
-        arr = (cabi.RtSeed * max(1, len(seeds)))()
-        for i, sd in enumerate(seeds):
-            arr[i] = cabi.seed_record(sd, keep)
+        seeds, arr, _keep = _seed_array(seeds, "set_scan_seeds", "a scan")
         self.hl.check(self.hl.lib.rt_hip_plan_set_scan_seeds(self._h, len(seeds), arr if seeds else None), "rt_hip_plan_set_scan_seeds")
         self._n_scan_seed = len(seeds)
         return self
@@ -506,51 +435,19 @@ class Plan:
     def fetch_seed_length_steps(self) -> list:
         """Per scan seed: [dict(n, E_v [nv], nf [nx * ny], I_ang [na * nb], failure_code)] for n = 2 .. N lengths of the last
         step run (waits for it; a failing run is repeated in the checking mode first)."""
-        b = self.problem.beam
         seeds, lengths = self._scan_seed_range()
-        out = []
-        for s in seeds:
-            curve = []
-            for n in lengths:
-                E_v, nf, iang = np.empty(b.nv), np.empty(b.nx * b.ny), np.empty(b.na * b.nb)
-                code = C.c_uint(0)
-                self.hl.check(self.hl.lib.rt_hip_plan_fetch_seed_length_step(self._h, s, n, cabi._dp(E_v), cabi._dp(nf), cabi._dp(iang),
-                                                                             C.byref(code)), "rt_hip_plan_fetch_seed_length_step")
-                curve.append(dict(n=n, E_v=E_v, nf=nf, I_ang=iang, failure_code=code.value))
-            out.append(curve)
-        return out
+        return [[dict(n=n, **self._fetch_record("rt_hip_plan_fetch_seed_length_step", s, n)) for n in lengths] for s in seeds]
 
     def seed_length_step_ptrs(self, s: int, n: int) -> tuple:
         """Device pointers (E_v, nf, I_ang) of the record of scan seed s at n lengths of the last step run."""
-        e, f, a = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        self.hl.check(self.hl.lib.rt_hip_plan_seed_length_step_ptrs(self._h, int(s), int(n), C.byref(e), C.byref(f), C.byref(a)),
-                      "rt_hip_plan_seed_length_step_ptrs")
-        return int(e.value or 0), int(f.value or 0), int(a.value or 0)
+        return self._record_ptrs("rt_hip_plan_seed_length_step_ptrs", s, n)
 
     def seed_length_step_tensors(self) -> list:
         """Per scan seed, per n = 2 .. N: dict(n, E_v [nv], nf [ny][nx], I_ang [nb][na]) of torch views (float64, on the plan's
         device, no copy) of the last step run -- blocks of one allocation, valid until the plan's next run; read them on the
         run's stream or after a fetch."""
-        import torch
-
-        class _View:  # the CUDA array interface, which torch.as_tensor reads
-            pass
-
-        def view(ptr, shape):
-            v = _View()
-            v.__cuda_array_interface__ = dict(shape=shape, typestr="<f8", data=(ptr, False), version=2, strides=None)
-            return torch.as_tensor(v, device=torch.device("cuda", self.device))
-
-        b = self.problem.beam
         seeds, lengths = self._scan_seed_range()
-        out = []
-        for s in seeds:
-            curve = []
-            for n in lengths:
-                e, f, a = self.seed_length_step_ptrs(s, n)
-                curve.append(dict(n=n, E_v=view(e, (b.nv,)), nf=view(f, (b.ny, b.nx)), I_ang=view(a, (b.nb, b.na))))
-            out.append(curve)
-        return out
+        return [[dict(n=n, **self._record_views(self.seed_length_step_ptrs(s, n))) for n in lengths] for s in seeds]
 
     # -- tables -------------------------------------------------------------
     def update_gain(self, gain, stream: int | None = None) -> "Plan":
@@ -792,10 +689,7 @@ def full_step_loop(problem: Problem, seeds, scales=None, rays: np.ndarray | None
     if rays is None:
         rays = problem.build_rays()
     rays = np.ascontiguousarray(rays, dtype=cabi.RAY_DTYPE)
-    keep = []
-    arr = (cabi.RtSeed * len(seeds))()
-    for i, sd in enumerate(seeds):
-        arr[i] = cabi.seed_record(sd, keep)
+    _, arr, _keep = _seed_array(seeds, "full_step_loop", "a step record")   # (checked above: marshalled only)
     b, nr = problem.beam, 1 + len(seeds)
     E_v, nf, iang = np.zeros((nr, b.nv)), np.zeros((nr, b.nx * b.ny)), np.zeros((nr, b.na * b.nb))
     codes = (C.c_uint * nr)()
@@ -871,10 +765,7 @@ def seed_length_scan_loop(problem: Problem, seeds, rays: np.ndarray | None = Non
     if rays is None:
         rays = problem.build_rays()
     rays = np.ascontiguousarray(rays, dtype=cabi.RAY_DTYPE)
-    keep = []
-    arr = (cabi.RtSeed * len(seeds))()
-    for i, sd in enumerate(seeds):
-        arr[i] = cabi.seed_record(sd, keep)
+    _, arr, _keep = _seed_array(seeds, "seed_length_scan_loop", "a scan")   # (checked above: marshalled only)
     b, L, ns = problem.beam, problem.N - 1, len(seeds)
     E_v, nf, iang = np.zeros((ns, L, b.nv)), np.zeros((ns, L, b.nx * b.ny)), np.zeros((ns, L, b.na * b.nb))
     codes = (C.c_uint * (ns * L))()

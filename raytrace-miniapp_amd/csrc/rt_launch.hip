@@ -241,8 +241,33 @@ template <typename KArg> KArg pass_args(const rt::FreqKArg &fa)
     return a;
 }
 
+// ---- what the passes with several records share (rt_records.h: the blocks of the plan's one allocation) --------------
+// block r as the kernels of a seed set and of ASE seeds take it
+rt::SeedRec seed_rec(const rt_hip_plan *p, int r)
+{
+    double *blk = p->recs_dev + (size_t) r * p->recs_stride;
+    return rt::SeedRec{ blk, blk + p->recs_nf_off, blk + p->recs_ang_off };
+}
+// ... and all of them as the kernels of a length scan do, with the boundary states of the march
+void fill_scan(rt::ScanArg &a, const rt_hip_plan *p) { a = rt::ScanArg{ p->scan_bnd, p->recs_dev, p->recs_stride, p->recs_nf_off, p->recs_ang_off }; }
+// the tables of the plan's first n_seed seeds; grid_tabs: with their factor tables on the forward ray grid, which must then
+// have been built (`who`: the kernel and what it calls them, for the message)
+int fill_seed_tabs(rt::SeedTabs &tb, const rt_hip_plan *p, int n_seed, bool grid_tabs, const char *who)
+{
+    for (int i = 0; i < n_seed; i++) {
+        tb.fk[i]   = p->seed_set[i].f[4];
+        tb.sf[i]   = grid_tabs ? p->seedset_sf[i] : nullptr;
+        tb.sin[i]  = grid_tabs ? p->seedset_sin[i] : nullptr;
+        tb.seed[i] = p->seed_set[i];
+        if (grid_tabs && (!tb.sf[i] || !tb.sin[i]))
+            return fail_arg((std::string(who) + " were not built for this ray grid").c_str());
+    }
+    return RT_OK;
+}
+
 // The second pass over all tiles as a kernel of its own: the frequency / deposit kernel, or in its place the spectra
-// kernel (per-ray spectra, no image), the step kernel (E_v, nf and I_ang, no image cube) or the step kernel of a seed set.
+// kernel (per-ray spectra, no image), the step kernel (E_v, nf and I_ang, no image cube) or one of the step kernels that
+// leave several records (a seed set, ASE seeds, a length scan, a scan with its seeds: record_set(f) says how many).
 int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kind, hipStream_t stream, unsigned safe = 0, unsigned char *bad = nullptr)
 {
     const PassShape s = pass_shape(kind, f, t);
@@ -271,6 +296,7 @@ int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kin
     }
     const rt::FreqKArg fa = freq_args(p, s.in_lds, s.nslot, s.fetch_shift, PassRun{ 0, f.n_tiles, 0, safe, bad });
     const unsigned block  = (unsigned) s.wg_waves * 64;
+    const int n_rec       = record_set(f).n_rec();
     if (kind == PASS_FREQ)
         return launch(p, freq_kernel(f.s6(), f.use_emis, f.use_emis && f.exclusive), s.grid, block, s.lds, stream, fa);
     if (kind == PASS_SPEC) {
@@ -284,87 +310,57 @@ int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kin
         a.out       = p->step;
         return launch(p, step_kernel(f.s6(), f.use_emis), s.grid, block, s.lds, stream, a);
     }
-    if (kind == PASS_SCAN) { // a length scan: one record per length, the blocks of the seed-set allocation
-        if (!p->scan_bnd || !p->seeds_dev)
+    if (kind == PASS_SCAN) { // a length scan: one record per length
+        if (!p->scan_bnd || !p->recs_dev)
             return fail_arg("step kernel of a length scan: the boundary states or the records of this run were not allocated");
         rt::ScanKArg a = pass_args<rt::ScanKArg>(fa);
         a.hot.iang     = nullptr; // (every record's I_ang lies in its block)
-        a.scan.bnd     = p->scan_bnd;
-        a.scan.out     = p->seeds_dev;
-        a.scan.stride  = p->seeds_stride;
-        a.scan.nf_off  = p->seeds_nf_off;
-        a.scan.ang_off = p->seeds_ang_off;
+        fill_scan(a.scan, p);
         return launch(p, scan_kernel(f.use_emis), s.grid, block, s.lds, stream, a);
     }
     if (kind == PASS_SCAN_SEEDS) { // a length scan with scan seeds (a seeded plan: gain-only): one record per (seed, length)
-        if (!p->scan_bnd || !p->seeds_dev)
+        if (!p->scan_bnd || !p->recs_dev)
             return fail_arg("step kernel of a length scan with scan seeds: the boundary states or the records of this run were not allocated");
         if (f.n_seed < 1 || f.n_seed > RT_N_SEED_MAX || f.L > RT_N_SCAN_MAX || f.use_emis)
             return fail_arg("step kernel of a length scan with scan seeds: not a gain-only run of 1 .. RT_N_SEED_MAX seeds and at most RT_N_SCAN_MAX lengths");
-        if (p->seeds_doubles < (size_t) f.n_seed * (size_t) f.L * p->seeds_stride)
+        if (p->recs_doubles < (size_t) n_rec * p->recs_stride)
             return fail_arg("step kernel of a length scan with scan seeds: the records of this run are smaller than n_seed (N - 1) blocks");
         rt::ScanSeedsKArg a = pass_args<rt::ScanSeedsKArg>(fa);
         a.hot.iang     = nullptr; // (every record's I_ang lies in its block)
         a.hot.seed_fk  = nullptr; // (the creation seed is not part of the set)
-        a.scan.bnd     = p->scan_bnd;
-        a.scan.out     = p->seeds_dev;
-        a.scan.stride  = p->seeds_stride;
-        a.scan.nf_off  = p->seeds_nf_off;
-        a.scan.ang_off = p->seeds_ang_off;
+        fill_scan(a.scan, p);
         a.set.n_seed   = f.n_seed;
-        for (int i = 0; i < f.n_seed; i++) {
-            a.set.fk[i]   = p->seed_set[i].f[4];
-            a.set.sf[i]   = p->P.rays.sf ? p->seedset_sf[i] : nullptr;
-            a.set.sin[i]  = p->P.rays.sf ? p->seedset_sin[i] : nullptr;
-            a.set.seed[i] = p->seed_set[i];
-            if (p->P.rays.sf && (!a.set.sf[i] || !a.set.sin[i]))
-                return fail_arg("step kernel of a length scan with scan seeds: the factor tables of the seeds were not built for this ray grid");
-        }
-        return launch(p, rt::rt_step_scan_seeds_kernel, s.grid, block, s.lds, stream, a);
+        const int rc   = fill_seed_tabs(a.set.tabs, p, f.n_seed, p->P.rays.sf != nullptr, "step kernel of a length scan with scan seeds: the factor tables of the seeds");
+        return rc != RT_OK ? rc : launch(p, rt::rt_step_scan_seeds_kernel, s.grid, block, s.lds, stream, a);
     }
     if (kind == PASS_ASE_SEEDS) { // an emission plan with ASE seeds: block 0 the ASE record, block 1 + s the record of seed s
-        if (f.n_seed < 1 || f.n_seed > RT_N_SEED_MAX || !f.use_emis || !p->seeds_dev)
+        if (f.n_seed < 1 || f.n_seed > RT_N_SEED_MAX || !f.use_emis || !p->recs_dev)
             return fail_arg("step kernel of an emission plan with ASE seeds: not an emission run of 1 .. RT_N_SEED_MAX seeds with its records allocated");
-        if (p->seeds_doubles < (size_t) (1 + f.n_seed) * p->seeds_stride)
+        if (p->recs_doubles < (size_t) n_rec * p->recs_stride)
             return fail_arg("step kernel of an emission plan with ASE seeds: the records of this run are smaller than 1 + n_seed blocks");
         rt::AseSeedsKArg a = pass_args<rt::AseSeedsKArg>(fa);
         a.hot.seed_fk  = nullptr; // (an emission plan has no creation seed)
         a.hot.flags &= ~(unsigned) rt::FQ_EXCLUSIVE; // (nf of every record by atomics: the plain store is rt_step_kernel's alone)
         a.set.n_seed   = f.n_seed;
+        for (int r = 0; r < n_rec; r++) {
+            a.set.out[r]   = seed_rec(p, r);
+            a.set.scale[r] = r == 0 ? p->P.scale : p->ase_scale[r - 1];
+        }
         // the factor tables of the seeds serve a forward ray GRID only, and the ray set decides: a list set behind the grid
         // (rt_hip_plan_set_rays resets P.rays, not the tables) takes seed_factor at its launch rays.  (A seeded plan has
         // P.rays.sf for this; an emission plan has no creation seed and hence none.)
         const bool grid_tabs = p->P.rays.gx && !p->P.rays.list && p->P.method != 1 && p->seedset_sf[0] != nullptr;
-        for (int r = 0; r <= f.n_seed; r++) {
-            double *blk    = p->seeds_dev + (size_t) r * p->seeds_stride;
-            a.set.out[r]   = rt::SeedRec{ blk, blk + p->seeds_nf_off, blk + p->seeds_ang_off };
-            a.set.scale[r] = r == 0 ? p->P.scale : p->ase_scale[r - 1];
-        }
-        for (int i = 0; i < f.n_seed; i++) {
-            a.set.fk[i]   = p->seed_set[i].f[4];
-            a.set.sf[i]   = grid_tabs ? p->seedset_sf[i] : nullptr;
-            a.set.sin[i]  = grid_tabs ? p->seedset_sin[i] : nullptr;
-            a.set.seed[i] = p->seed_set[i];
-            if (grid_tabs && (!a.set.sf[i] || !a.set.sin[i]))
-                return fail_arg("step kernel of an emission plan with ASE seeds: the factor tables of the seeds were not built for this ray grid");
-        }
-        return launch(p, ase_seeds_kernel(f.s6()), s.grid, block, s.lds, stream, a);
+        const int rc = fill_seed_tabs(a.set.tabs, p, f.n_seed, grid_tabs, "step kernel of an emission plan with ASE seeds: the factor tables of the seeds");
+        return rc != RT_OK ? rc : launch(p, ase_seeds_kernel(f.s6()), s.grid, block, s.lds, stream, a);
     }
     // a seed set (a seeded plan: gain-only): one record per seed
     rt::SeedsKArg a = pass_args<rt::SeedsKArg>(fa);
     a.hot.seed_fk = nullptr; // (the creation seed is not part of the set)
     a.set.n_seed  = f.n_seed;
-    for (int i = 0; i < f.n_seed; i++) {
-        double *blk   = p->seeds_dev + (size_t) i * p->seeds_stride;
-        a.set.out[i]  = rt::SeedRec{ blk, blk + p->seeds_nf_off, blk + p->seeds_ang_off };
-        a.set.fk[i]   = p->seed_set[i].f[4];
-        a.set.sf[i]   = p->P.rays.sf ? p->seedset_sf[i] : nullptr;
-        a.set.sin[i]  = p->P.rays.sf ? p->seedset_sin[i] : nullptr;
-        a.set.seed[i] = p->seed_set[i];
-        if (p->P.rays.sf && (!a.set.sf[i] || !a.set.sin[i]))
-            return fail_arg("step kernel of a seed set: the factor tables of the set were not built for this ray grid");
-    }
-    return launch(p, seeds_kernel(f.s6()), s.grid, block, s.lds, stream, a);
+    for (int r = 0; r < n_rec; r++)
+        a.set.out[r] = seed_rec(p, r);
+    const int rc = fill_seed_tabs(a.set.tabs, p, f.n_seed, p->P.rays.sf != nullptr, "step kernel of a seed set: the factor tables of the set");
+    return rc != RT_OK ? rc : launch(p, seeds_kernel(f.s6()), s.grid, block, s.lds, stream, a);
 }
 
 } // namespace
@@ -454,11 +450,8 @@ int launch_selftest(unsigned long long *counts_dev)
 int plan_repeat_checked(rt_hip_plan *p)
 {
     hipStream_t stream = p->last_stream;
-    // (a length scan marks one bit per length in a 32-bit word per ray, with scan seeds one bit per (seed, length) in a 64-bit
-    // word, every other run one byte per ray)
-    const bool scan       = p->last_step && p->last_scan_L > 0;
-    const int scan_seeds  = scan ? p->last_scan_n_seed : 0;
-    const size_t bad_word = scan_seeds > 0 ? sizeof(unsigned long long) : scan ? sizeof(unsigned) : 1;
+    const RecordSet &R    = p->last_records;
+    const size_t bad_word = R.bad_word();
     if (p->bad_rays < (size_t) p->n_rays * bad_word || !p->bad_dev) {
         (void) hipFree(p->bad_dev);
         p->bad_dev = nullptr;
@@ -476,18 +469,19 @@ int plan_repeat_checked(rt_hip_plan *p)
     HIP_TRY(hipMemsetAsync(p->ctl->next_tile_f, 0, sizeof(p->ctl->next_tile_f), stream));
     const bool step = p->last_step; // a step run: the step kernel honours the same marks, E_v and nf start over
     RunFacts f          = run_facts(p);
-    f.scan_on           = scan; // (the run that is repeated decides, not what the plan has been switched to since)
-    if (scan)
-        f.n_seed = scan_seeds;
+    f.step_on           = step; // (the run that is repeated decides, not what the plan has been switched to since)
+    f.path_on = f.spectra_on = false;
+    f.scan_on           = R.scan();
+    f.n_seed            = R.n_seed;
     const Tuning t      = read_tuning();
-    const PassKind kind = step ? (scan ? (scan_seeds > 0 ? PASS_SCAN_SEEDS : PASS_SCAN) : f.n_seed > 0 ? (f.use_emis ? PASS_ASE_SEEDS : PASS_SEEDS) : PASS_STEP) : PASS_FREQ;
+    const PassKind kind = pass_kind(f); // (of record_set(f), which is R again)
     int rc              = launch_pass(p, f, t, kind, stream, 1, p->bad_dev);
     if (rc == RT_OK) {
         if (step && p->last_step_lent) { // (the caller's buffers: exactly the K and nx * ny doubles that are the run's)
             HIP_TRY(hipMemsetAsync(p->step.E_v, 0, (size_t) p->P.K * sizeof(double), stream));
             HIP_TRY(hipMemsetAsync(p->step.nf, 0, (size_t) p->P.beam.nx * (size_t) p->P.beam.ny * sizeof(double), stream));
-        } else if (step && (p->last_n_seed > 0 || scan)) // (a seed set, a length scan: every record, its I_ang included, is in the one allocation)
-            HIP_TRY(hipMemsetAsync(p->seeds_dev, 0, p->seeds_doubles * sizeof(double), stream));
+        } else if (step && R.n_rec() > 0) // (every record, its I_ang included, is in the one allocation)
+            HIP_TRY(hipMemsetAsync(p->recs_dev, 0, p->recs_doubles * sizeof(double), stream));
         else if (step)
             HIP_TRY(hipMemsetAsync(p->step_dev, 0, p->step_doubles * sizeof(double), stream));
         else if (!p->P.exclusive)
@@ -501,6 +495,8 @@ int plan_repeat_checked(rt_hip_plan *p)
     HIP_TRY(hipStreamSynchronize(stream));
     return RT_OK;
 }
+
+RecordSet plan_record_set(const rt_hip_plan *p) { return record_set(run_facts(p)); }
 
 // ---- the steps of a run --------------------------------------------------------------------------------------------
 // step 2's device query: what hipOccupancyMaxActiveBlocksPerMultiprocessor says of the march instance `s` names (its LDS

@@ -198,7 +198,7 @@ void rt_hip_plan_destroy(rt_hip_plan *p)
     (void) hipFree(p->spec[0].Iv); // (ray2 and err of a set live in the same allocation)
     (void) hipFree(p->spec[1].Iv);
     pool_free(p->device, p->step_dev);
-    pool_free(p->device, p->seeds_dev);
+    pool_free(p->device, p->recs_dev);
     pool_free(p->device, p->scan_bnd);
     (void) hipFree(p->seedset_arena);
     (void) hipFree(p->seedset_tab);
@@ -661,7 +661,7 @@ void rtr::plan_stage_outputs(rt_hip_plan *p)
     constexpr size_t ctl_tail = offsetof(rt::DevCtl, failure_code), ctl_bytes = sizeof(rt::DevCtl) - ctl_tail;
     if (!p || !p->ran || !p->last_stream)
         return;
-    if (p->last_step && (p->last_step_lent || p->last_n_seed > 0 || p->last_scan_L > 0)) // E_v and nf are the caller's, a seed set's or a length scan's: fetched the ordinary way
+    if (p->last_step && (p->last_step_lent || p->last_records.n_rec() > 0)) // E_v and nf are the caller's, or one record of several: fetched the ordinary way
         return;
     // (a step run: E_v and nf travel where the image does)
     const double *big    = p->last_step ? p->step_dev : p->last_image;
@@ -1056,12 +1056,7 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
         return fail_arg("rt_hip_plan_run: a step run takes no image buffer");
     const bool lent = step && p->step_ev_lent; // E_v and nf in the caller's memory (rt_hip_plan_set_step_buffers)
     const size_t nf_off = align_up((size_t) p->P.K * sizeof(double), 256) / sizeof(double);
-    const int n_seed = p->n_seed; // a seed set: one record per seed, all in one allocation of the plan
-    const int scan_L = p->scan_on ? p->P.L : 0; // a length scan: one record per length, the same allocation (never both)
-    const int scan_seeds = scan_L > 0 ? p->n_scan_seed : 0; // the seeds of the scan: one record per (seed, length), seed 0's curve first
-    const bool ase   = n_seed > 0 && p->P.use_emis; // ASE seeds on an emission plan: the ASE record in block 0, the seeds behind it
-    const int n_rec  = n_seed > 0 ? n_seed + (ase ? 1 : 0) : scan_seeds > 0 ? scan_seeds * scan_L : scan_L;
-    if (scan_L > 0) {
+    if (p->scan_on) {
         if (!step || p->path_on)
             return fail_arg("rt_hip_plan_run: the length scan is on, which runs in step mode only");
         if (lent)
@@ -1069,7 +1064,7 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
         if (image_dev || iang_dev)
             return fail_arg("rt_hip_plan_run: a run with the length scan on takes no image and no I_ang buffer");
     }
-    if (n_seed > 0) {
+    if (p->n_seed > 0) {
         if (!step || p->path_on)
             return fail_arg("rt_hip_plan_run: the plan holds a seed set, which runs in step mode only");
         if (lent)
@@ -1077,24 +1072,28 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
         if (image_dev || iang_dev)
             return fail_arg("rt_hip_plan_run: a run with a seed set takes no image and no I_ang buffer");
     }
+    // the records this run leaves (a seed set, ASE seeds, a length scan, a scan with its seeds): all in one allocation of the plan
+    const RecordSet recs = plan_record_set(p);
+    const int n_rec      = recs.n_rec();
+    double *primary      = nullptr; // the record rt_hip_plan_fetch and fetch_step serve: seed 0's or the ASE record, of all N lengths
     if (n_rec > 0) {
         const rt::DevBeam &B = p->P.beam;
         // (the spare cells of the one-point-axis case: rt_multi.hip, multi_step's buffer)
         const size_t ang_off = nf_off + (size_t) B.nx * (size_t) B.ny + ((B.nx < 2 || B.ny < 2) ? (size_t) B.nx + 2 : 0);
         const size_t stride  = align_up((ang_off + p->n_iang + ((B.na < 2 || B.nb < 2) ? (size_t) B.na + 2 : 0)) * sizeof(double), 256) / sizeof(double);
-        if (!p->seeds_dev || p->seeds_doubles != stride * (size_t) n_rec) {
+        if (!p->recs_dev || p->recs_doubles != stride * (size_t) n_rec) {
             plan_quiesce(p);
-            pool_free(p->device, p->seeds_dev);
-            p->seeds_dev     = nullptr;
-            p->seeds_doubles = 0;
-            HIP_TRY(pool_alloc(p->device, (void **) &p->seeds_dev, stride * (size_t) n_rec * sizeof(double)));
-            p->seeds_doubles = stride * (size_t) n_rec;
+            pool_free(p->device, p->recs_dev);
+            p->recs_dev     = nullptr;
+            p->recs_doubles = 0;
+            HIP_TRY(pool_alloc(p->device, (void **) &p->recs_dev, stride * (size_t) n_rec * sizeof(double)));
+            p->recs_doubles = stride * (size_t) n_rec;
         }
-        p->seeds_stride  = stride;
-        p->seeds_nf_off  = nf_off;
-        p->seeds_ang_off = ang_off;
-        // seed 0's, or the record of all N lengths: what rt_hip_plan_fetch and fetch_step serve
-        iang_dev         = p->seeds_dev + (scan_L > 0 ? (size_t) (scan_L - 1) * stride : 0) + ang_off;
+        p->recs_stride  = stride;
+        p->recs_nf_off  = nf_off;
+        p->recs_ang_off = ang_off;
+        primary         = p->recs_dev + (size_t) recs.primary() * stride;
+        iang_dev        = primary + ang_off;
     }
     if (step && !lent && !n_rec && !p->step_dev) {
         // (one row and a cell to spare: on an axis of one grid point the reference's getIndex answers 1 for the coordinate
@@ -1104,9 +1103,7 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
     }
     rt::StepOut step_out = {};
     if (step)
-        step_out = lent ? rt::StepOut{ p->step_ev_lent, p->step_nf_lent }
-                 : scan_L ? rt::StepOut{ p->seeds_dev + (size_t) (scan_L - 1) * p->seeds_stride, p->seeds_dev + (size_t) (scan_L - 1) * p->seeds_stride + nf_off }
-                 : n_seed ? rt::StepOut{ p->seeds_dev, p->seeds_dev + nf_off } : rt::StepOut{ p->step_dev, p->step_dev + nf_off };
+        step_out = lent ? rt::StepOut{ p->step_ev_lent, p->step_nf_lent } : primary ? rt::StepOut{ primary, primary + nf_off } : rt::StepOut{ p->step_dev, p->step_dev + nf_off };
     if (!spectra && !step && !image_dev) {
         if (!p->image_own)
             HIP_TRY(pool_alloc(p->device, (void **) &p->image_own, p->n_image * sizeof(double)));
@@ -1138,7 +1135,7 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
     // (step mode: E_v and nf take the image's place in the zeroing launch, exclusive or not)
     rc = lent ? launch_zero4(stream, step_out.E_v, (size_t) p->P.K * sizeof(double), step_out.nf,
                              (size_t) p->P.beam.nx * (size_t) p->P.beam.ny * sizeof(double), iang_dev, p->n_iang * sizeof(double), p->ctl, sizeof(rt::DevCtl))
-         : n_rec ? launch_zero3(stream, p->seeds_dev, p->seeds_doubles * sizeof(double), nullptr, 0, p->ctl, sizeof(rt::DevCtl))
+         : n_rec ? launch_zero3(stream, p->recs_dev, p->recs_doubles * sizeof(double), nullptr, 0, p->ctl, sizeof(rt::DevCtl))
          : step ? launch_zero3(stream, p->step_dev, p->step_doubles * sizeof(double), iang_dev, p->n_iang * sizeof(double), p->ctl, sizeof(rt::DevCtl))
               : launch_zero3(stream, (p->P.exclusive || spectra) ? nullptr : image_dev, p->n_image * sizeof(double), iang_dev,
                              p->n_iang * sizeof(double), p->ctl, sizeof(rt::DevCtl));
@@ -1166,10 +1163,7 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
     p->last_spectra = spectra;
     p->last_step   = step;
     p->last_step_lent = lent;
-    p->last_n_seed = n_seed;
-    p->last_ase    = ase;
-    p->last_scan_L = scan_L;
-    p->last_scan_n_seed = scan_seeds;
+    p->last_records = recs;
     p->spec_last   = p->spec_sel;
     p->ran         = true;
     p->queued      = false; // (`ran` + last_stream cover it from here)
@@ -1274,6 +1268,59 @@ int rtr::plan_settle_last_run(rt_hip_plan *p)
     return plan_settle(p, c, staged);
 }
 
+// ---- the records of the last run (rt_records.h: RecordSet says which blocks there are) ---------------------------------
+// Every rt_hip_plan_fetch_*_step / rt_hip_plan_*_step_ptrs pair below is a test of the kind, a test of the index and one
+// of these two on the block the index means.
+static int record_ptrs(rt_hip_plan *p, int block, double **E_v_dev, double **nf_dev, double **iang_dev)
+{
+    double *blk = p->recs_dev + (size_t) block * p->recs_stride;
+    if (E_v_dev)
+        *E_v_dev = blk;
+    if (nf_dev)
+        *nf_dev = blk + p->recs_nf_off;
+    if (iang_dev)
+        *iang_dev = blk + p->recs_ang_off;
+    return RT_OK;
+}
+// the code of a block: the one place that knows which array of the control block a kind's kernel writes
+static unsigned record_code(const rt::DevCtl &c, const RecordSet &R, int block)
+{
+    switch (R.kind) {
+    case REC_SEEDS: return c.seed_code[block];
+    case REC_ASE_SEEDS: return c.rec_code[block];
+    case REC_SCAN: return c.len_code[block];
+    case REC_SCAN_SEEDS: return c.seed_len_code[block / R.L][block % R.L];
+    default: return c.failure_code;
+    }
+}
+static int record_fetch(rt_hip_plan *p, int block, double *E_v, double *nf, double *I_ang, unsigned int *code)
+{
+    rt::DevCtl c;
+    bool staged  = false;
+    const int rs = plan_settle(p, c, staged); // (a failing run is repeated here as rt_hip_plan_fetch repeats it)
+    if (rs != RT_OK)
+        return rs;
+    const double *blk = p->recs_dev + (size_t) block * p->recs_stride;
+    if (E_v)
+        HIP_TRY(hipMemcpy(E_v, blk, (size_t) p->P.K * sizeof(double), hipMemcpyDeviceToHost));
+    if (nf)
+        HIP_TRY(hipMemcpy(nf, blk + p->recs_nf_off, (size_t) p->P.beam.nx * (size_t) p->P.beam.ny * sizeof(double), hipMemcpyDeviceToHost));
+    if (I_ang)
+        HIP_TRY(hipMemcpy(I_ang, blk + p->recs_ang_off, p->n_iang * sizeof(double), hipMemcpyDeviceToHost));
+    if (code)
+        *code = record_code(c, p->last_records, block);
+    return RT_OK;
+}
+// every record of the last run through host pointers: row r of each output is block r
+static int record_fetch_rows(rt_hip_plan *p, double *E_v, double *nf, double *I_ang, unsigned int *codes)
+{
+    int rc = RT_OK;
+    for (int r = 0; rc == RT_OK && r < p->last_records.n_rec(); r++)
+        rc = record_fetch(p, r, E_v ? E_v + (size_t) r * (size_t) p->P.K : nullptr, nf ? nf + (size_t) r * (size_t) p->P.beam.nx * (size_t) p->P.beam.ny : nullptr,
+                          I_ang ? I_ang + (size_t) r * p->n_iang : nullptr, codes ? codes + r : nullptr);
+    return rc;
+}
+
 extern "C" {
 
 int rt_hip_plan_fetch(rt_hip_plan *p, double *image, double *I_ang, unsigned int *failure_code,
@@ -1362,41 +1409,20 @@ int rt_hip_plan_fetch_step(rt_hip_plan *p, double *E_v, double *nf, double *I_an
 
 int rt_hip_plan_fetch_seed_step(rt_hip_plan *p, int s, double *E_v, double *nf, double *I_ang, unsigned int *failure_code)
 {
-    if (!p || !p->ran || !p->last_step || p->last_n_seed < 1 || p->last_ase)
+    if (!p || p->last_records.kind != REC_SEEDS)
         return fail_arg("rt_hip_plan_fetch_seed_step: the last run was not a step run with a seed set");
-    if (s < 0 || s >= p->last_n_seed)
+    if (p->last_records.block(s) < 0)
         return fail_arg("rt_hip_plan_fetch_seed_step: no such seed in the set of the last run");
-    rt::DevCtl c;
-    bool staged  = false;
-    const int rs = plan_settle(p, c, staged); // (a failing run is repeated here as rt_hip_plan_fetch repeats it)
-    if (rs != RT_OK)
-        return rs;
-    const double *blk = p->seeds_dev + (size_t) s * p->seeds_stride;
-    if (E_v)
-        HIP_TRY(hipMemcpy(E_v, blk, (size_t) p->P.K * sizeof(double), hipMemcpyDeviceToHost));
-    if (nf)
-        HIP_TRY(hipMemcpy(nf, blk + p->seeds_nf_off, (size_t) p->P.beam.nx * (size_t) p->P.beam.ny * sizeof(double), hipMemcpyDeviceToHost));
-    if (I_ang)
-        HIP_TRY(hipMemcpy(I_ang, blk + p->seeds_ang_off, p->n_iang * sizeof(double), hipMemcpyDeviceToHost));
-    if (failure_code)
-        *failure_code = c.seed_code[s];
-    return RT_OK;
+    return record_fetch(p, p->last_records.block(s), E_v, nf, I_ang, failure_code);
 }
 
 int rt_hip_plan_seed_step_ptrs(rt_hip_plan *p, int s, double **E_v_dev, double **nf_dev, double **iang_dev)
 {
-    if (!p || !p->ran || !p->last_step || p->last_n_seed < 1 || p->last_ase)
+    if (!p || p->last_records.kind != REC_SEEDS)
         return fail_arg("rt_hip_plan_seed_step_ptrs: the last run was not a step run with a seed set");
-    if (s < 0 || s >= p->last_n_seed)
+    if (p->last_records.block(s) < 0)
         return fail_arg("rt_hip_plan_seed_step_ptrs: no such seed in the set of the last run");
-    double *blk = p->seeds_dev + (size_t) s * p->seeds_stride;
-    if (E_v_dev)
-        *E_v_dev = blk;
-    if (nf_dev)
-        *nf_dev = blk + p->seeds_nf_off;
-    if (iang_dev)
-        *iang_dev = blk + p->seeds_ang_off;
-    return RT_OK;
+    return record_ptrs(p, p->last_records.block(s), E_v_dev, nf_dev, iang_dev);
 }
 
 int rt_hip_plan_enable_length_scan(rt_hip_plan *p, int on)
@@ -1441,43 +1467,23 @@ int rt_hip_plan_enable_length_scan(rt_hip_plan *p, int on)
     return RT_OK;
 }
 
+// (on a scan with scan seeds a length alone means seed 0's curve)
 int rt_hip_plan_fetch_length_step(rt_hip_plan *p, int n, double *E_v, double *nf, double *I_ang, unsigned int *failure_code)
 {
-    if (!p || !p->ran || !p->last_step || p->last_scan_L < 1)
+    if (!p || !p->last_records.scan())
         return fail_arg("rt_hip_plan_fetch_length_step: the last run was not a step run with the length scan on");
-    if (n < 2 || n - 1 > p->last_scan_L)
+    if (p->last_records.block(0, n) < 0)
         return fail_arg("rt_hip_plan_fetch_length_step: n must be 2 .. N of the last run");
-    rt::DevCtl c;
-    bool staged  = false;
-    const int rs = plan_settle(p, c, staged); // (a failing run is repeated here as rt_hip_plan_fetch repeats it)
-    if (rs != RT_OK)
-        return rs;
-    const double *blk = p->seeds_dev + (size_t) (n - 2) * p->seeds_stride;
-    if (E_v)
-        HIP_TRY(hipMemcpy(E_v, blk, (size_t) p->P.K * sizeof(double), hipMemcpyDeviceToHost));
-    if (nf)
-        HIP_TRY(hipMemcpy(nf, blk + p->seeds_nf_off, (size_t) p->P.beam.nx * (size_t) p->P.beam.ny * sizeof(double), hipMemcpyDeviceToHost));
-    if (I_ang)
-        HIP_TRY(hipMemcpy(I_ang, blk + p->seeds_ang_off, p->n_iang * sizeof(double), hipMemcpyDeviceToHost));
-    if (failure_code)
-        *failure_code = p->last_scan_n_seed > 0 ? c.seed_len_code[0][n - 2] : c.len_code[n - 2]; // (with scan seeds: seed 0's curve)
-    return RT_OK;
+    return record_fetch(p, p->last_records.block(0, n), E_v, nf, I_ang, failure_code);
 }
 
 int rt_hip_plan_length_step_ptrs(rt_hip_plan *p, int n, double **E_v_dev, double **nf_dev, double **iang_dev)
 {
-    if (!p || !p->ran || !p->last_step || p->last_scan_L < 1)
+    if (!p || !p->last_records.scan())
         return fail_arg("rt_hip_plan_length_step_ptrs: the last run was not a step run with the length scan on");
-    if (n < 2 || n - 1 > p->last_scan_L)
+    if (p->last_records.block(0, n) < 0)
         return fail_arg("rt_hip_plan_length_step_ptrs: n must be 2 .. N of the last run");
-    double *blk = p->seeds_dev + (size_t) (n - 2) * p->seeds_stride;
-    if (E_v_dev)
-        *E_v_dev = blk;
-    if (nf_dev)
-        *nf_dev = blk + p->seeds_nf_off;
-    if (iang_dev)
-        *iang_dev = blk + p->seeds_ang_off;
-    return RT_OK;
+    return record_ptrs(p, p->last_records.block(0, n), E_v_dev, nf_dev, iang_dev);
 }
 
 } // extern "C"
@@ -1621,41 +1627,20 @@ int rt_hip_plan_set_ase_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds, 
 
 int rt_hip_plan_fetch_full_step(rt_hip_plan *p, int r, double *E_v, double *nf, double *I_ang, unsigned int *failure_code)
 {
-    if (!p || !p->ran || !p->last_step || !p->last_ase)
+    if (!p || p->last_records.kind != REC_ASE_SEEDS)
         return fail_arg("rt_hip_plan_fetch_full_step: the last run was not a step run of an emission plan with ASE seeds");
-    if (r < 0 || r > p->last_n_seed)
+    if (p->last_records.block(r) < 0)
         return fail_arg("rt_hip_plan_fetch_full_step: r must be 0 (ASE) .. n_seed of the last run");
-    rt::DevCtl c;
-    bool staged  = false;
-    const int rs = plan_settle(p, c, staged); // (a failing run is repeated here as rt_hip_plan_fetch repeats it)
-    if (rs != RT_OK)
-        return rs;
-    const double *blk = p->seeds_dev + (size_t) r * p->seeds_stride;
-    if (E_v)
-        HIP_TRY(hipMemcpy(E_v, blk, (size_t) p->P.K * sizeof(double), hipMemcpyDeviceToHost));
-    if (nf)
-        HIP_TRY(hipMemcpy(nf, blk + p->seeds_nf_off, (size_t) p->P.beam.nx * (size_t) p->P.beam.ny * sizeof(double), hipMemcpyDeviceToHost));
-    if (I_ang)
-        HIP_TRY(hipMemcpy(I_ang, blk + p->seeds_ang_off, p->n_iang * sizeof(double), hipMemcpyDeviceToHost));
-    if (failure_code)
-        *failure_code = c.rec_code[r];
-    return RT_OK;
+    return record_fetch(p, p->last_records.block(r), E_v, nf, I_ang, failure_code);
 }
 
 int rt_hip_plan_full_step_ptrs(rt_hip_plan *p, int r, double **E_v_dev, double **nf_dev, double **iang_dev)
 {
-    if (!p || !p->ran || !p->last_step || !p->last_ase)
+    if (!p || p->last_records.kind != REC_ASE_SEEDS)
         return fail_arg("rt_hip_plan_full_step_ptrs: the last run was not a step run of an emission plan with ASE seeds");
-    if (r < 0 || r > p->last_n_seed)
+    if (p->last_records.block(r) < 0)
         return fail_arg("rt_hip_plan_full_step_ptrs: r must be 0 (ASE) .. n_seed of the last run");
-    double *blk = p->seeds_dev + (size_t) r * p->seeds_stride;
-    if (E_v_dev)
-        *E_v_dev = blk;
-    if (nf_dev)
-        *nf_dev = blk + p->seeds_nf_off;
-    if (iang_dev)
-        *iang_dev = blk + p->seeds_ang_off;
-    return RT_OK;
+    return record_ptrs(p, p->last_records.block(r), E_v_dev, nf_dev, iang_dev);
 }
 
 } // extern "C"
@@ -1664,45 +1649,24 @@ extern "C" {
 
 int rt_hip_plan_fetch_seed_length_step(rt_hip_plan *p, int s, int n, double *E_v, double *nf, double *I_ang, unsigned int *failure_code)
 {
-    if (!p || !p->ran || !p->last_step || p->last_scan_L < 1 || p->last_scan_n_seed < 1)
+    if (!p || p->last_records.kind != REC_SCAN_SEEDS)
         return fail_arg("rt_hip_plan_fetch_seed_length_step: the last run was not a step run of a length scan with scan seeds");
-    if (s < 0 || s >= p->last_scan_n_seed)
+    if (p->last_records.block(s, 2) < 0) // (every scan has length 2)
         return fail_arg("rt_hip_plan_fetch_seed_length_step: no such seed among the scan seeds of the last run");
-    if (n < 2 || n - 1 > p->last_scan_L)
+    if (p->last_records.block(s, n) < 0)
         return fail_arg("rt_hip_plan_fetch_seed_length_step: n must be 2 .. N of the last run");
-    rt::DevCtl c;
-    bool staged  = false;
-    const int rs = plan_settle(p, c, staged); // (a failing run is repeated here as rt_hip_plan_fetch repeats it)
-    if (rs != RT_OK)
-        return rs;
-    const double *blk = p->seeds_dev + ((size_t) s * (size_t) p->last_scan_L + (size_t) (n - 2)) * p->seeds_stride;
-    if (E_v)
-        HIP_TRY(hipMemcpy(E_v, blk, (size_t) p->P.K * sizeof(double), hipMemcpyDeviceToHost));
-    if (nf)
-        HIP_TRY(hipMemcpy(nf, blk + p->seeds_nf_off, (size_t) p->P.beam.nx * (size_t) p->P.beam.ny * sizeof(double), hipMemcpyDeviceToHost));
-    if (I_ang)
-        HIP_TRY(hipMemcpy(I_ang, blk + p->seeds_ang_off, p->n_iang * sizeof(double), hipMemcpyDeviceToHost));
-    if (failure_code)
-        *failure_code = c.seed_len_code[s][n - 2];
-    return RT_OK;
+    return record_fetch(p, p->last_records.block(s, n), E_v, nf, I_ang, failure_code);
 }
 
 int rt_hip_plan_seed_length_step_ptrs(rt_hip_plan *p, int s, int n, double **E_v_dev, double **nf_dev, double **iang_dev)
 {
-    if (!p || !p->ran || !p->last_step || p->last_scan_L < 1 || p->last_scan_n_seed < 1)
+    if (!p || p->last_records.kind != REC_SCAN_SEEDS)
         return fail_arg("rt_hip_plan_seed_length_step_ptrs: the last run was not a step run of a length scan with scan seeds");
-    if (s < 0 || s >= p->last_scan_n_seed)
+    if (p->last_records.block(s, 2) < 0)
         return fail_arg("rt_hip_plan_seed_length_step_ptrs: no such seed among the scan seeds of the last run");
-    if (n < 2 || n - 1 > p->last_scan_L)
+    if (p->last_records.block(s, n) < 0)
         return fail_arg("rt_hip_plan_seed_length_step_ptrs: n must be 2 .. N of the last run");
-    double *blk = p->seeds_dev + ((size_t) s * (size_t) p->last_scan_L + (size_t) (n - 2)) * p->seeds_stride;
-    if (E_v_dev)
-        *E_v_dev = blk;
-    if (nf_dev)
-        *nf_dev = blk + p->seeds_nf_off;
-    if (iang_dev)
-        *iang_dev = blk + p->seeds_ang_off;
-    return RT_OK;
+    return record_ptrs(p, p->last_records.block(s, n), E_v_dev, nf_dev, iang_dev);
 }
 
 int rt_hip_plan_kernel_ms(rt_hip_plan *p, float *ms)
@@ -1895,19 +1859,8 @@ static int host_pointer_loop(int device, int N, const rt_beam *beam, const rt_ga
         rc = rt_hip_plan_fetch(p, image, step ? nullptr : I_ang, scan ? nullptr : failure_code, failed_rays, max_failed, n_failed, stats);
     if (rc == RT_OK && step && !scan)
         rc = rt_hip_plan_fetch_step(p, E_v, nf, I_ang);
-    for (int n = 2; rc == RT_OK && scan && n_scan_seed == 0 && n <= N; n++) {
-        const size_t r = (size_t) (n - 2);
-        rc = rt_hip_plan_fetch_length_step(p, n, E_v ? E_v + r * (size_t) beam->nv : nullptr, nf ? nf + r * (size_t) beam->nx * (size_t) beam->ny : nullptr,
-                                           I_ang ? I_ang + r * (size_t) beam->na * (size_t) beam->nb : nullptr, failure_code ? failure_code + r : nullptr);
-    }
-    for (int s = 0; scan && s < n_scan_seed; s++)
-        for (int n = 2; rc == RT_OK && n <= N; n++) {
-            const size_t r = (size_t) s * (size_t) (N - 1) + (size_t) (n - 2);
-            rc = rt_hip_plan_fetch_seed_length_step(p, s, n, E_v ? E_v + r * (size_t) beam->nv : nullptr,
-                                                    nf ? nf + r * (size_t) beam->nx * (size_t) beam->ny : nullptr,
-                                                    I_ang ? I_ang + r * (size_t) beam->na * (size_t) beam->nb : nullptr,
-                                                    failure_code ? failure_code + r : nullptr);
-        }
+    if (rc == RT_OK && scan) // one row per length, with scan seeds the rows of a scan once per seed
+        rc = record_fetch_rows(p, E_v, nf, I_ang, failure_code);
     lap("fetch (wait + D2H)");
     rt_hip_plan_destroy(p); // waits for whatever is still in flight
     release_queue(device, q);
@@ -2010,9 +1963,8 @@ int rt_hip_full_step_loop(int device, int N, const rt_beam *beam, const rt_gain 
         rc = rt_hip_plan_run(p, q, nullptr, nullptr);
     if (rc == RT_OK)
         rc = rt_hip_plan_fetch(p, nullptr, nullptr, nullptr, failed_rays, max_failed, n_failed, stats);
-    for (int r = 0; rc == RT_OK && r <= n_seed; r++)
-        rc = rt_hip_plan_fetch_full_step(p, r, E_v + (size_t) r * (size_t) beam->nv, nf + (size_t) r * (size_t) beam->nx * (size_t) beam->ny,
-                                         I_ang + (size_t) r * (size_t) beam->na * (size_t) beam->nb, failure_codes ? failure_codes + r : nullptr);
+    if (rc == RT_OK)
+        rc = record_fetch_rows(p, E_v, nf, I_ang, failure_codes);
     rt_hip_plan_destroy(p); // waits for whatever is still in flight
     release_queue(device, q);
     return rc;

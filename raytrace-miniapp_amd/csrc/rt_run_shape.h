@@ -6,6 +6,8 @@
 // its numbers from pass_shape.  rt_hip_debug_run_shape hands the same functions to a test that has no device.
 #pragma once
 
+#include "rt_records.h"
+
 #include <cstdlib>
 #include <cstring>
 #include <functional>
@@ -355,12 +357,21 @@ inline RunShape run_shape(const RunFacts &f, const Tuning &t, const Occupancy &o
 }
 
 // ---- the second pass -----------------------------------------------------------------------------------------------
-// (PASS_ASE_SEEDS: an emission plan with ASE seeds, rt_step_ase_seeds.hip -- use_emis with n_seed > 0 is that and nothing else)
-enum PassKind { PASS_FREQ = 0, PASS_SPEC = 1, PASS_STEP = 2, PASS_SEEDS = 3, PASS_PATH = 4, PASS_SCAN = 5, PASS_SCAN_SEEDS = 6, PASS_ASE_SEEDS = 7 };
+// the records a step run of these facts leaves (rt_records.h): the one place that decides kind and counts
+inline RecordSet record_set(const RunFacts &f)
+{
+    RecordSet r;
+    if (!f.step_on || f.path_on || f.spectra_on)
+        return r;
+    r.kind   = f.scan_on ? (f.n_seed > 0 ? REC_SCAN_SEEDS : REC_SCAN) : f.n_seed > 0 ? (f.use_emis ? REC_ASE_SEEDS : REC_SEEDS) : REC_NONE;
+    r.n_seed = f.n_seed;
+    r.L      = f.scan_on ? f.L : 0;
+    return r;
+}
 
 inline PassKind pass_kind(const RunFacts &f)
 {
-    return f.path_on ? PASS_PATH : f.spectra_on ? PASS_SPEC : f.step_on ? (f.scan_on ? (f.n_seed > 0 ? PASS_SCAN_SEEDS : PASS_SCAN) : f.n_seed > 0 ? (f.use_emis ? PASS_ASE_SEEDS : PASS_SEEDS) : PASS_STEP) : PASS_FREQ;
+    return f.path_on ? PASS_PATH : f.spectra_on ? PASS_SPEC : f.step_on ? record_set(f).pass_kind() : PASS_FREQ;
 }
 
 struct PassShape {
@@ -423,7 +434,7 @@ inline PassShape pass_shape(PassKind kind, const RunFacts &f, const Tuning &t)
         s.wg_waves = rt::FREQ_WG_WAVES;
         // (a seed set keeps one I_ang histogram and one E_v accumulator per seed, a length scan one of each per length, a scan
         // with scan seeds one of each per (seed, length), an emission plan with ASE seeds one of each for ASE and per seed)
-        const int n_rec      = kind == PASS_SCAN_SEEDS ? f.n_seed * f.L : kind == PASS_SCAN ? f.L : kind == PASS_SEEDS ? f.n_seed : kind == PASS_ASE_SEEDS ? 1 + f.n_seed : 1;
+        const int n_rec      = kind == PASS_STEP || kind == PASS_SPEC ? 1 : record_set(f).n_rec();
         const int ang_stride = kind == PASS_STEP ? rt::step_ang_stride((int) f.n_iang) : rt::seeds_ang_stride((int) f.n_iang);
         auto step_lds        = [&](bool in_lds) { return rt::step_lds_doubles(in_lds, ang_stride, f.Kp, s.wg_waves, n_rec) * sizeof(double); };
         // (spectra: the staging rows of 16 waves and the exponent tables take 148 KB of LDS)

@@ -6,11 +6,14 @@
 //                   rt_hip_image_loop (the host-pointer entry the C++ adapter calls)
 //   rt_raygrid.hip  a ray list that is really a tensor grid: recognition + bit-wise verification,
 //                   list-mode launch tangents and the probe of the host's libm
-//   rt_launch.hip   the kernels (rt_march.hip, rt_freq.hip, rt_path.hip, rt_spec.hip, rt_step.hip, rt_step_seeds.hip, rt_fused_step.hip) and how a run puts them on a queue:
+//   rt_launch.hip   the kernels (rt_march.hip, rt_freq.hip, rt_path.hip, rt_spec.hip, rt_step.hip, rt_step_seeds.hip, rt_fused_step.hip,
+//                   rt_step_scan.hip, rt_step_scan_seeds.hip, rt_step_ase_seeds.hip) and how a run puts them on a queue:
 //                   WHAT a run looks like -- tables in LDS or not, one launch or two, instance, grid, chunk, late zone, the
 //                   LDS layout of a one-launch run, the shape of the second pass -- is decided by pure functions of plain
 //                   numbers (rt_run_shape.h, included by rt_launch.hip alone: RunFacts from the plan + Tuning from the
-//                   environment -> run_shape / pass_shape; rt_hip_debug_run_shape hands them to tests without a device);
+//                   environment -> run_shape / pass_shape / record_set; rt_hip_debug_run_shape hands them to tests without a
+//                   device; which records a step run leaves and how they are numbered is RecordSet, rt_records.h: the plan
+//                   keeps the one of its last run, and rt_plan.hip serves the records by it);
 //                   plan_launch_run enqueues what they say and writes nothing per-launch into the plan's DevParams
 //   rt_multi.hip    all devices of the node: RCCL loader, communicator, rt_hip_multi_image_loop, rt_hip_multi_step_loop
 //   rt_tables.hip   the gain tables of a resident plan rewritten in place: scan and pack kernels, rt_hip_plan_update_gain
@@ -18,6 +21,7 @@
 #pragma once
 
 #include "rt_device.h"
+#include "rt_records.h"
 #include "rt_spec.h"
 #include "rt_step.h"
 
@@ -66,41 +70,34 @@ struct rt_hip_plan {
     // by the next step run; last_step_lent: the last step run wrote the caller's
     double *step_ev_lent = nullptr, *step_nf_lent = nullptr;
     bool last_step_lent  = false;
-    // seed set (rt_hip_plan_set_seeds): up to RT_N_SEED_MAX seed profiles whose records one step run leaves.  The tables of
-    // the set live in one device block of their own (seedset_arena; seed_set[s] points into it, f[4] padded to Kp); on a
-    // forward ray grid seedset_tab holds, per seed, what seedtab_dev holds for the creation seed.  All records are ONE
-    // allocation, zeroed by the run's zeroing launch: n_seed blocks of seeds_stride doubles, each
-    // E_v [K] | pad to 256 bytes | nf [nx * ny] + spare | I_ang [na * nb] + spare (the per-device buffer of rt_multi.hip).
-    int n_seed = 0;
+    // the seeds a step run takes beside the creation seed: up to RT_N_SEED_MAX profiles, installed as a seed set
+    // (rt_hip_plan_set_seeds, a seeded plan: n_seed), as the seeds of a length scan (rt_hip_plan_set_scan_seeds, while the scan
+    // is on: n_scan_seed, n_seed stays 0) or as ASE seeds (rt_hip_plan_set_ase_seeds, an EMISSION plan: n_seed with
+    // P.use_emis, the one case of use_emis with n_seed > 0; ase_scale[s] is the scale of seed s).  A set and a scan exclude
+    // each other, so their tables live in the same place: one device block (seedset_arena; seed_set[s] points into it, f[4]
+    // padded to Kp) and, on a forward ray grid, per seed what seedtab_dev holds for the creation seed (seedset_tab).
+    int n_seed      = 0;
+    int n_scan_seed = 0;
     rt::DevSeed seed_set[RT_N_SEED_MAX] = {};
     unsigned char *seedset_arena = nullptr;
     unsigned char *seedset_tab   = nullptr;
     const double *seedset_sf[RT_N_SEED_MAX]         = {};
     const unsigned char *seedset_sin[RT_N_SEED_MAX] = {};
-    double *seeds_dev    = nullptr;
-    size_t seeds_doubles = 0;                                    // doubles of the allocation
-    size_t seeds_stride = 0, seeds_nf_off = 0, seeds_ang_off = 0; // doubles: block to block, E_v to nf, E_v to I_ang
-    int last_n_seed = 0;                                         // seeds of the last run (0: it ran without a set)
-    // ASE seeds (rt_hip_plan_set_ase_seeds): the n_seed seeds above on an EMISSION plan (P.use_emis, no creation seed -- the
-    // one case of use_emis with n_seed > 0).  A step run then leaves 1 + n_seed blocks of the allocation above from one march
-    // (rt_step_ase_seeds.hip): block 0 the plan's own emission record, block 1 + s the gain-only record of seed s with scale
-    // ase_scale[s].  The tables live where a set's live; on a forward ray grid the factor tables are built as for a set.
     double ase_scale[RT_N_SEED_MAX] = {};
-    bool last_ase = false; // the last run left such records (last_n_seed seeds behind the ASE block)
-    // length scan (rt_hip_plan_enable_length_scan): one step record per plasma length n = 2 .. N from one forward march.
-    // The records are the blocks of the seed-set allocation above (seeds_dev, seeds_stride, ...: a scan and a set exclude
-    // each other), block n - 2 for n lengths; scan_bnd holds the state with which every ray crossed every length boundary
-    // (rt_march.hip, scan_bnd_off), from the plan's pool while the scan is on.
+    // length scan (rt_hip_plan_enable_length_scan): one step record per plasma length n = 2 .. N from one forward march;
+    // scan_bnd holds the state with which every ray crossed every length boundary (rt_march.hip, scan_bnd_off), from the
+    // plan's pool while the scan is on.
     bool scan_on          = false;
-    int last_scan_L       = 0; // records of the last run (0: it ran without the scan)
     unsigned char *scan_bnd = nullptr;
     size_t scan_bnd_bytes = 0;
-    size_t bad_word       = 1; // bytes per ray of bad_dev in the last checking repeat (4: a length scan, one bit per length; 8: with scan seeds)
-    // the seeds of a scan (rt_hip_plan_set_scan_seeds): while the scan is on the plan may carry 1 .. RT_N_SEED_MAX seeds whose
-    // records every length gets -- n_scan_seed (N - 1) blocks of the allocation above, block s (N - 1) + (n - 2).  Their tables
-    // live where a seed set's live (seed_set[], seedset_arena, seedset_tab: a set and a scan exclude each other); n_seed stays 0.
-    int n_scan_seed      = 0;
-    int last_scan_n_seed = 0; // scan seeds of the last run (0: it ran without them)
+    // the records of such a run (rt_records.h says which, and how they are numbered): ONE allocation, zeroed by the run's
+    // zeroing launch, of n_rec() blocks of recs_stride doubles, each
+    // E_v [K] | pad to 256 bytes | nf [nx * ny] + spare | I_ang [na * nb] + spare (the per-device buffer of rt_multi.hip).
+    double *recs_dev    = nullptr;
+    size_t recs_doubles = 0;                                  // doubles of the allocation
+    size_t recs_stride = 0, recs_nf_off = 0, recs_ang_off = 0; // doubles: block to block, E_v to nf, E_v to I_ang
+    rtr::RecordSet last_records;                              // what the last run left there (REC_NONE: nothing, or no step run)
+    size_t bad_word = 1; // bytes per ray of bad_dev in the last checking repeat (RecordSet::bad_word)
     size_t rec_bytes   = 0;
     hipEvent_t evm     = nullptr; // between march and frequency kernels
     const rt_ray *host_rays = nullptr; // ray list still on the host, uploaded by the next run (rt_hip_image_loop)
@@ -251,6 +248,8 @@ int tan_mode(int device);
 // upload, the second pass.  The kernels get a copy of p->P with the numbers of the launch in it; of p->P itself only rec,
 // path and path_err are set.
 int plan_launch_run(rt_hip_plan *p, hipStream_t stream);
+// the records the next run of the plan leaves: record_set (rt_run_shape.h) of the plan's facts
+RecordSet plan_record_set(const rt_hip_plan *p);
 // a run that reported failing rays: repeat the frequency pass (in step mode: the step kernel) without them (the marks and
 // the pass of the repeat, DevParams::safe, go to the launch as arguments; p->P stays as it is)
 int plan_repeat_checked(rt_hip_plan *p);

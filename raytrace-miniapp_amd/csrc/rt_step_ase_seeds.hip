@@ -47,11 +47,11 @@ struct AseSeedsArg {
     int pad;
     SeedRec out[1 + RT_N_SEED_MAX];          // record 0: ASE; record 1 + s: seed s
     double scale[1 + RT_N_SEED_MAX];         // of every record (scale[0] is the plan's, FreqHot::scale)
-    const double *fk[RT_N_SEED_MAX];         // [Kp] f[4] of the seed, zero padded
-    const double *sf[RT_N_SEED_MAX];         // forward ray grid: the seed's factor tables (rt_seed_tab_kernel), else NULL
-    const unsigned char *sin[RT_N_SEED_MAX]; // ... and its support flags
-    DevSeed seed[RT_N_SEED_MAX];
+    SeedTabs tabs;
 };
+static_assert(offsetof(AseSeedsArg, tabs) == 8 + (sizeof(SeedRec) + sizeof(double)) * (1 + RT_N_SEED_MAX) &&
+                  sizeof(AseSeedsArg) == offsetof(AseSeedsArg, tabs) + sizeof(SeedTabs),
+              "nesting SeedTabs moves no byte of the argument block");
 struct AseSeedsKArg {
     FreqHot hot;
     FreqCold cold;
@@ -135,7 +135,7 @@ __device__ __forceinline__ void step_ase_seeds_tile(const FreqHot &H, const unsi
             fs[s] = 0.0;
         if (!(live >> 1) || (fl & F_ESCAPED)) // (live under no seed: whatever the lane integrates is dropped)
             return;
-        const double *sf0 = Q->sf[0]; // (the tables of the seeds exist on a forward ray grid, for all seeds or none)
+        const double *sf0 = Q->tabs.sf[0]; // (the tables of the seeds exist on a forward ray grid, for all seeds or none)
         if (backward || !sf0) {
             double qx, qy, qa, qb;
             if (backward) { // the exit ray, Helper.h:518-521: atanf(s.x / s.z) * 1e3f
@@ -156,7 +156,7 @@ __device__ __forceinline__ void step_ase_seeds_tile(const FreqHot &H, const unsi
 #pragma unroll
             for (int s = 0; s < NS; s++) {
                 if (s < n_seed) {
-                    const DevSeed SD = load_cold(&Q->seed[s]);
+                    const DevSeed SD = load_cold(&Q->tabs.seed[s]);
                     fs[s]            = seed_factor(SD, qx, qy, qa, qb);
                 }
             }
@@ -166,9 +166,9 @@ __device__ __forceinline__ void step_ase_seeds_tile(const FreqHot &H, const unsi
 #pragma unroll
             for (int s = 0; s < NS; s++) {
                 if (s < n_seed) {
-                    const double *sf         = Q->sf[s];
-                    const unsigned char *sin = Q->sin[s];
-                    RT_SEED_GRID_FACTOR(fs[s], Q->seed[s].f0, sf, sin)
+                    const double *sf         = Q->tabs.sf[s];
+                    const unsigned char *sin = Q->tabs.sin[s];
+                    RT_SEED_GRID_FACTOR(fs[s], Q->tabs.seed[s].f0, sf, sin)
                 }
             }
         }
@@ -276,7 +276,7 @@ __device__ __forceinline__ void step_ase_seeds_tile(const FreqHot &H, const unsi
 #pragma unroll
             for (int s = 0; s < NS; s++) {
                 if (s < n_seed) {
-                    const ConstF64 sk = (ConstF64) (unsigned long long) Q->fk[s];
+                    const ConstF64 sk = (ConstF64) (unsigned long long) Q->tabs.fk[s];
 #pragma unroll
                     for (int j = 0; j < VEC; j++)
                         Iv[j] = fs[s] * sk[kb + j];

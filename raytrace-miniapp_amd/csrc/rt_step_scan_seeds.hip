@@ -42,11 +42,9 @@ static_assert(RT_N_SEED_MAX * 32 <= 64 && RT_N_SCAN_MAX <= 32, "one mark bit per
 struct ScanSeedsArg {
     int n_seed;
     int pad;
-    const double *fk[RT_N_SEED_MAX];         // [Kp] f[4] of the seed, zero padded
-    const double *sf[RT_N_SEED_MAX];         // forward ray grid: the seed's factor tables (rt_seed_tab_kernel), else NULL
-    const unsigned char *sin[RT_N_SEED_MAX]; // ... and its support flags
-    DevSeed seed[RT_N_SEED_MAX];
+    SeedTabs tabs;
 };
+static_assert(offsetof(ScanSeedsArg, tabs) == 8 && sizeof(ScanSeedsArg) == 8 + sizeof(SeedTabs), "nesting SeedTabs moves no byte of the argument block");
 struct ScanSeedsKArg {
     FreqHot hot;
     FreqCold cold;
@@ -102,7 +100,7 @@ __device__ __forceinline__ void step_scan_seeds_tile(const FreqHot &H, const uns
 #pragma unroll
             for (int s = 0; s < NS; s++) {
                 if (s < n_seed) {
-                    const DevSeed SD = load_cold(&Z->seed[s]);
+                    const DevSeed SD = load_cold(&Z->tabs.seed[s]);
                     f0_launch[s]     = scan_seed_factor(SD, (double) launch.x, (double) launch.y, (double) launch.a, (double) launch.b);
                 }
             }
@@ -112,9 +110,9 @@ __device__ __forceinline__ void step_scan_seeds_tile(const FreqHot &H, const uns
 #pragma unroll
             for (int s = 0; s < NS; s++) {
                 if (s < n_seed) {
-                    const double *sf         = Z->sf[s];
-                    const unsigned char *sin = Z->sin[s];
-                    RT_SEED_GRID_FACTOR(f0_launch[s], Z->seed[s].f0, sf, sin)
+                    const double *sf         = Z->tabs.sf[s];
+                    const unsigned char *sin = Z->tabs.sin[s];
+                    RT_SEED_GRID_FACTOR(f0_launch[s], Z->tabs.seed[s].f0, sf, sin)
                 }
             }
         }
@@ -242,7 +240,7 @@ __device__ __forceinline__ void step_scan_seeds_tile(const FreqHot &H, const uns
 #pragma unroll
                     for (int s = 0; s < NS; s++) {
                         if (s < n_seed) {
-                            const ConstF64 sfk = (ConstF64) (unsigned long long) Z->fk[s];
+                            const ConstF64 sfk = (ConstF64) (unsigned long long) Z->tabs.fk[s];
                             const double f0    = carries ? f0_launch[s] : 0.0;
                             double Iv[VEC];
 #pragma unroll

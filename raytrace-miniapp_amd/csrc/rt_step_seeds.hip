@@ -34,17 +34,25 @@ namespace rt {
 struct SeedRec {
     double *E_v, *nf, *iang;
 };
+// the tables of the seeds of a pass: the last member of SeedSetArg, ScanSeedsArg (rt_step_scan_seeds.hip) and AseSeedsArg
+// (rt_step_ase_seeds.hip), filled by one function of rt_launch.hip
+struct SeedTabs {
+    const double *fk[RT_N_SEED_MAX];         // [Kp] f[4] of the seed, zero padded
+    const double *sf[RT_N_SEED_MAX];         // forward ray grid: the seed's factor tables (rt_seed_tab_kernel), else NULL
+    const unsigned char *sin[RT_N_SEED_MAX]; // ... and its support flags
+    DevSeed seed[RT_N_SEED_MAX];
+};
 // what rt_step_seeds_kernel reads beside the frequency kernel's block: read through the constant address space where it
 // is needed (as the cold half is), so that nothing of it is live across the frequency loop
 struct SeedSetArg {
     int n_seed;
     int pad;
     SeedRec out[RT_N_SEED_MAX];
-    const double *fk[RT_N_SEED_MAX];         // [Kp] f[4] of the seed, zero padded
-    const double *sf[RT_N_SEED_MAX];         // forward ray grid: the seed's factor tables (rt_seed_tab_kernel), else NULL
-    const unsigned char *sin[RT_N_SEED_MAX]; // ... and its support flags
-    DevSeed seed[RT_N_SEED_MAX];
+    SeedTabs tabs;
 };
+static_assert(offsetof(SeedSetArg, tabs) == 8 + sizeof(SeedRec) * RT_N_SEED_MAX && offsetof(SeedTabs, fk) == 0 &&
+                  offsetof(SeedTabs, seed) == 3 * sizeof(void *) * RT_N_SEED_MAX && sizeof(SeedSetArg) == offsetof(SeedSetArg, tabs) + sizeof(SeedTabs),
+              "nesting SeedTabs moves no byte of the argument block");
 struct SeedsKArg {
     FreqHot hot;
     FreqCold cold;
@@ -93,7 +101,7 @@ __device__ __forceinline__ void step_seeds_tile(const FreqHot &H, const unsigned
 #pragma unroll
                 for (int s = 0; s < NS; s++) {
                     if (s < n_seed) {
-                        const DevSeed SD = load_cold(&Q->seed[s]);
+                        const DevSeed SD = load_cold(&Q->tabs.seed[s]);
                         f0[s] = backward ? seed_factor(SD, (double) m.px, (double) m.py, (double) ra, (double) rb)
                                          : seed_factor(SD, (double) ray.x, (double) ray.y, (double) ray.a, (double) ray.b);
                     }
@@ -104,9 +112,9 @@ __device__ __forceinline__ void step_seeds_tile(const FreqHot &H, const unsigned
 #pragma unroll
                 for (int s = 0; s < NS; s++) {
                     if (s < n_seed) {
-                        const double *sf         = Q->sf[s];
-                        const unsigned char *sin = Q->sin[s];
-                        RT_SEED_GRID_FACTOR(f0[s], Q->seed[s].f0, sf, sin)
+                        const double *sf         = Q->tabs.sf[s];
+                        const unsigned char *sin = Q->tabs.sin[s];
+                        RT_SEED_GRID_FACTOR(f0[s], Q->tabs.seed[s].f0, sf, sin)
                     }
                 }
             }
@@ -195,7 +203,7 @@ __device__ __forceinline__ void step_seeds_tile(const FreqHot &H, const unsigned
 #pragma unroll
         for (int s = 0; s < NS; s++) {
             if (s < n_seed) {
-                const ConstF64 sfk = (ConstF64) (unsigned long long) Q->fk[s];
+                const ConstF64 sfk = (ConstF64) (unsigned long long) Q->tabs.fk[s];
                 double Iv[VEC];
 #pragma unroll
                 for (int j = 0; j < VEC; j++)
