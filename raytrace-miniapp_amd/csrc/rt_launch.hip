@@ -890,6 +890,17 @@ int rt_hip_debug_prune_counters(unsigned long long *out4)
     return RT_OK;
 }
 #endif
+#ifdef RT_TIMEBLOCKS
+// diagnostic build only: read and clear the counters of the retirement of finished rays (rt_march.hip, g_retire)
+int rt_hip_debug_retire_counters(unsigned long long *out4)
+{
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpyFromSymbol(out4, HIP_SYMBOL(rt::g_retire), 4 * sizeof(unsigned long long)));
+    unsigned long long z[4] = { 0 };
+    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(rt::g_retire), z, sizeof(z)));
+    return RT_OK;
+}
+#endif
 #if defined(RT_INSTRUMENT) || defined(RT_TIMEBLOCKS)
 // diagnostic builds only: read and clear the loop-occupancy / block-clock counters
 int rt_hip_debug_counters(unsigned long long *out8)

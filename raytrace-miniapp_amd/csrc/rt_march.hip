@@ -29,7 +29,9 @@
 
 namespace rt {
 
-enum : int { ST_IDLE = 0, ST_CELL = 1, ST_XSETUP = 2, ST_STEP = 3, ST_DONE = 4 };
+// (ST_DONE: the lane's ray has finished and waits to be retired, march_wave "ray finished"; it sorts below ST_IDLE so that
+// one comparison, st <= ST_IDLE, finds the lanes without a marching ray)
+enum : int { ST_DONE = -1, ST_IDLE = 0, ST_CELL = 1, ST_XSETUP = 2, ST_STEP = 3 };
 
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -438,9 +440,14 @@ __device__ unsigned long long g_prune[4];
 __device__ unsigned short g_ray_iters[1u << 23]; // loop iterations each ray occupied its lane for (ray number < 2^23)
 #endif
 #ifdef RT_TIMEBLOCKS
-// -DRT_TIMEBLOCKS: wave clock spent in each block of the march loop, g_inst[i] = cycles between mark i and mark i+1
-// summed over waves, g_inst[7] = iterations
+// -DRT_TIMEBLOCKS: wave clock spent in each block of the march loop, g_inst[i] = cycles that ended at a mark(i) (since the
+// mark before it, whichever that was) summed over waves: 0 loop head and refill (two marks in an iteration that retires:
+// before the retirement block and after the hand-out), 1 [A1], 2 [A2], 3 retirement (at the loop head, between the two
+// marks of 0), 4 [B], 5 [C]; g_inst[7] = iterations
 __device__ unsigned long long g_inst[8];
+// ... and the retirement of finished rays, wave-iterations: in which a ray finished [0], in which the retirement block ran
+// for some lane [1], which refilled the wave [2], after the ray counters ran dry [3] (tools/retire_block_share.py)
+__device__ unsigned long long g_retire[4];
 #endif
 #ifdef RT_WAVETIMES // start / counters-dry / end time of every wave of the last launch (100 MHz clock)
 __device__ unsigned long long g_wt[8];
@@ -467,6 +474,9 @@ struct MarchDiag {
 #endif
 #if defined(RT_TIMEBLOCKS) || defined(RT_WAVEBLOCKS)
     unsigned long long tb_acc[6] = { 0, 0, 0, 0, 0, 0 }, tb_last = __builtin_readcyclecounter(), tb_iters = 0;
+#endif
+#ifdef RT_TIMEBLOCKS
+    unsigned rt_fin = 0, rt_blk = 0, rt_refill = 0, rt_dry = 0;
 #endif
 #ifdef RT_WAVETIMES
     const unsigned long long wt_start = __builtin_amdgcn_s_memrealtime();
@@ -496,7 +506,7 @@ struct MarchDiag {
     __device__ __forceinline__ void iteration(int st, int lane, int n_idle)
     {
 #ifdef RT_INSTRUMENT
-        ray_iters += st != ST_IDLE ? 1u : 0u;
+        ray_iters += st > ST_IDLE ? 1u : 0u; // (not the iterations a finished ray waits to be retired)
 #endif
 #ifdef RT_TIMEBLOCKS
         tb_iters++;
@@ -534,6 +544,28 @@ struct MarchDiag {
 #ifdef RT_WAVETIMES
         wt_a_runs += a_runs ? 1u : 0u;
         wt_b_runs += __ballot(lane_wants_b) != 0ull ? 1u : 0u;
+#endif
+    }
+    // the retirement of finished rays (g_retire): [A1] has run, and a ray of the wave finished in it; the retirement block
+    // is reached, and runs for some lane; the wave refills.  (The lane's state as it is, as for `iteration`.)
+    __device__ __forceinline__ void finishing(int st)
+    {
+#ifdef RT_TIMEBLOCKS
+        // (called by the lanes in [A1] only: one of them counts, and wave_end adds the lanes up, as for `tick`)
+        rt_fin += (__ballot(st == ST_DONE) != 0ull && first_active_lane()) ? 1u : 0u;
+#endif
+    }
+    __device__ __forceinline__ void retire_block(int st, bool more)
+    {
+#ifdef RT_TIMEBLOCKS
+        rt_blk += __ballot(st == ST_DONE) != 0ull ? 1u : 0u;
+        rt_dry += more ? 0u : 1u;
+#endif
+    }
+    __device__ __forceinline__ void refill()
+    {
+#ifdef RT_TIMEBLOCKS
+        rt_refill++;
 #endif
     }
     // the calling lane's ray retires
@@ -607,10 +639,15 @@ struct MarchDiag {
         }
 #endif
 #ifdef RT_TIMEBLOCKS
+        const unsigned fin_wave = wave_sum_u32(rt_fin); // (counted by whichever lane was first in [A1])
         if (lane == 0) {
             for (int i = 0; i < 6; i++)
                 atomicAdd(&g_inst[i], tb_acc[i]);
             atomicAdd(&g_inst[7], tb_iters);
+            atomicAdd(&g_retire[0], (unsigned long long) fin_wave);
+            atomicAdd(&g_retire[1], (unsigned long long) rt_blk);
+            atomicAdd(&g_retire[2], (unsigned long long) rt_refill);
+            atomicAdd(&g_retire[3], (unsigned long long) rt_dry);
         }
 #endif
 #ifdef RT_INSTRUMENT
@@ -631,6 +668,9 @@ struct MarchDiag { // the product build: nothing
     __device__ __forceinline__ void iteration(int, int, int) {}
     __device__ __forceinline__ void counters_dry() {}
     __device__ __forceinline__ void blocks_run(bool, bool) {}
+    __device__ __forceinline__ void finishing(int) {}
+    __device__ __forceinline__ void retire_block(int, bool) {}
+    __device__ __forceinline__ void refill() {}
     __device__ __forceinline__ void ray_retired(unsigned) {}
     __device__ __forceinline__ void publish_begin() {}
     __device__ __forceinline__ void publish_stores_landed() {}
@@ -827,6 +867,9 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
     unsigned fetched_end = 0, cur_slot = 0; // (wave-uniform) slot of done.rem of the window's tile
     unsigned cslot       = 0;                               // (per lane) slot of the tile of the lane's ray
     bool more           = true;             // wave-uniform: the ray counters are not exhausted
+    // (wave-uniform) the number of idle lanes at which the loop head turns to retirement and refill: REFILL while the counters
+    // have rays, 0 -- every iteration -- once they are dry: `more` folded into the one scalar comparison of the head
+    unsigned refill_at = (unsigned) REFILL;
     // The rays of a launch are handed out in chunks of CH by eight counters (shard sh owns the chunks sh, sh + 8,
     // ...; a wave starts on shard blockIdx.x % 8 and moves on when its own is empty): one counter serves ~88
     // returning atomics per microsecond chip-wide, which a launch of a few hundred thousand rays comes close to
@@ -886,9 +929,11 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
         // ------------------------------------------------------------ refill
         // (one ballot per iteration: the lane masks of the loop head come from `idle2`, which is taken again only when
         // a refill has changed the states; a wave all of whose lanes are idle with nothing left to fetch leaves below)
-        unsigned long long idle2      = __ballot(st == ST_IDLE);
+        // (a lane whose ray has finished and waits to be retired, ST_DONE, is idle for every purpose of the loop head)
+        unsigned long long idle2      = __ballot(st <= ST_IDLE);
         const unsigned long long idle = idle2;
-        const int n_idle              = (int) __popcll(idle);
+        int n_idle                    = (int) __popcll(idle);
+        asm volatile("" : "+s"(n_idle)); // (a 32-bit scalar: left alone the compiler compares the 64-bit count in the vector unit)
         diag.iteration(st, lane, n_idle);
         // Watchdog of the instance that takes tables and step sizes as they come (BOUNDED = false: something is outside
         // the ranges rt_hip_plan_create verifies -- an index far from 1, a gradient beyond 1e12, a dz beyond 1e6 cm).
@@ -903,134 +948,197 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
         if (!BOUNDED) {
             if (((++spin) & 0xfffu) == 0u && spin >= P.spin_limit) {
                 spin = 0;
-                if (st != ST_IDLE) {
+                if (st > ST_IDLE) { // (not a lane that waits to be retired: it would retire twice)
                     escaped = true;
                     sx = sy = sz = 0.0f;
                     st           = ST_CELL;
                 }
             }
         }
-        if (more && (n_idle >= REFILL)) {
-            const int rank = (int) __builtin_amdgcn_mbcnt_hi((unsigned) (idle >> 32),
-                                                             __builtin_amdgcn_mbcnt_lo((unsigned) idle, 0u));
-            int need = n_idle, off = 0;
-            bool got = false;
-            while (need > 0) {
-                if (chunk_next == chunk_end && !(FUSED && chunk_next != fetched_end)) {
-                    unsigned c = 0;
-                    if (lane == 0)
-                        c = atomicAdd(&P.ctl->next_tile[P.launch_id][shard][zone * 8u], 1u);
-                    c = (unsigned) __builtin_amdgcn_readfirstlane((int) c) * 8u + shard + zone * n_main; // chunk number
-                    if (c >= (zone ? n_chunks : n_main)) { // this shard is empty: the next one, until all eight have been seen empty
-                        if (++shards_seen_empty == 8) {
-                            if (zone == 0u && late_wave && n_main < n_chunks) { // on to the chunks kept for the old waves
-                                zone              = 1u;
-                                shards_seen_empty = 0;
-                                continue;
+        if ((unsigned) n_idle >= refill_at) { // (one scalar compare and branch take the other iterations past retirement and refill)
+            // ------------------------------------------------------------ ray finished
+            // The lanes whose ray finished in [A1] (ST_DONE) since this block last ran: their meta blocks, the launch counters,
+            // their tiles' counters.  Such a lane has nothing to do until the wave refills, so it is retired when the wave
+            // refills (every ~7 iterations while the counters have rays), before the hand-out, which may need a tile counter
+            // this block sets free; once the counters are dry there is no refill and the block is reached in every iteration, so
+            // that no lane reaches the end of the loop unretired.  The lanes stand still in between: px .. cslot are what [A1]
+            // left.  (At the end of [A], where a ray finishes, the block ran in 40 % of the stand-in's iterations for four lanes,
+            // here in 15 % for eleven, profiles/retire_block_share.txt, and its compare, s_and_saveexec and branch closed every
+            // [A]; here it hides behind the refill test, and that test is one scalar compare: -2 %)
+            diag.mark(0);
+            diag.retire_block(st, more);
+            if (st == ST_DONE) {
+                unsigned fl = F_VALID;
+                if (escaped)
+                    fl |= F_ESCAPED;
+                if (use_emis && any_bits == 0u)
+                    fl |= F_SKIP; // every frequency update is the identity: contributes exactly +0 (finite lineshape)
+                RecMeta m;
+                m.px          = px;
+                m.py          = py;
+                m.sx          = sx;
+                m.sy          = sy;
+                m.sz          = sz;
+                // (the per-ray step count of the record saturates at 2^20 - 1; the launch total below is exact)
+                m.flags_steps = fl | ((unsigned) sub << REC_NDONE_SHIFT) |
+                                ((steps < 0xfffffu ? steps : 0xfffffu) << REC_STEPS_SHIFT);
+                // `sub` slots were committed: recp stands that many slot rows above slot 0 (forward) or below
+                // slot S-1 (backward); the meta blocks of the tile follow slot row S-1, 24 bytes per ray where a slot has 12
+                unsigned char *metap = recp + (int) REC_SLOT_ROW * (backward ? sub + 1 : S - sub) + lane12;
+#ifndef RT_ABL_NOMETA
+                *reinterpret_cast<RecMeta *>(metap) = m;
+#else
+                if (m.px == 1234.5f) // profiling only: the store stays reachable, but never happens
+                    *reinterpret_cast<RecMeta *>(metap) = m;
+#endif
+                diag.ray_retired(ridx);
+                tot_steps += steps;
+                tot_esc += escaped ? 1u : 0u;
+                tot_skip += (fl & F_SKIP) ? 1u : 0u;
+                tot_rays++;
+                st = ST_IDLE;
+                // One ray of the lane's tile less; the lane that takes the counter to zero has finished the tile and
+                // publishes it on the spot: every record of the tile was stored by THIS wave (the other rays retired in
+                // earlier runs of this block or in this one), so once the wave's stores have landed the tile may be read;
+                // one wait serves every tile that completes in this run.
+                // (Round 4 collected those lanes with a ballot after the block -- in every iteration, for an event that
+                // happens once in ~35: the loop head pays for every instruction, DESIGN.md 4.5.)
+                if (FUSED) {
+                    if (__hip_atomic_fetch_add(&done.rem[cslot], 0xffffffffu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) == 1u) {
+                        diag.publish_begin();
+                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                        diag.publish_stores_landed();
+                        tile_publish(done, ridx >> 6);
+                        diag.publish_end();
+                    }
+                }
+            }
+            diag.mark(3); // DONE
+            // ------------------------------------------------------------ refill
+            if (more) { // (here with n_idle >= REFILL)
+                diag.refill();
+                const int rank = (int) __builtin_amdgcn_mbcnt_hi((unsigned) (idle >> 32),
+                                                                 __builtin_amdgcn_mbcnt_lo((unsigned) idle, 0u));
+                int need = n_idle, off = 0;
+                bool got = false;
+                while (need > 0) {
+                    if (chunk_next == chunk_end && !(FUSED && chunk_next != fetched_end)) {
+                        unsigned c = 0;
+                        if (lane == 0)
+                            c = atomicAdd(&P.ctl->next_tile[P.launch_id][shard][zone * 8u], 1u);
+                        c = (unsigned) __builtin_amdgcn_readfirstlane((int) c) * 8u + shard + zone * n_main; // chunk number
+                        if (c >= (zone ? n_chunks : n_main)) { // this shard is empty: the next one, until all eight have been seen empty
+                            if (++shards_seen_empty == 8) {
+                                if (zone == 0u && late_wave && n_main < n_chunks) { // on to the chunks kept for the old waves
+                                    zone              = 1u;
+                                    shards_seen_empty = 0;
+                                    continue;
+                                }
+                                more = false;
+                                refill_at = 0u;
+                                diag.counters_dry();
+                                break;
                             }
-                            more = false;
-                            diag.counters_dry();
-                            break;
+                            shard = (shard + 1) & 7u;
+                            continue;
                         }
-                        shard = (shard + 1) & 7u;
-                        continue;
+                        chunk_next = P.ray_begin + c * CH;
+                        chunk_end  = (n_rays - chunk_next < CH) ? n_rays : chunk_next + CH;
+                        if (FUSED) {
+                            fetched_end = chunk_end;
+                            chunk_end   = chunk_next; // (no tile of the reservation is open yet)
+                        }
                     }
-                    chunk_next = P.ray_begin + c * CH;
-                    chunk_end  = (n_rays - chunk_next < CH) ? n_rays : chunk_next + CH;
-                    if (FUSED) {
-                        fetched_end = chunk_end;
-                        chunk_end   = chunk_next; // (no tile of the reservation is open yet)
+                    if (FUSED && chunk_next == chunk_end) {
+                        // open the next tile of the reservation: a free counter slot, loaded with the tile's ray count
+                        // (a slot is free when its counter is back at zero: the lane that took it there published the tile in
+                        // the same breath, below; looked up here, once per tile, instead of being tracked in every iteration)
+                        const unsigned in_use    = lane < 32 ? __hip_atomic_load(&done.rem[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) : 1u;
+                        const unsigned slot_busy = ~(unsigned) __ballot(lane < 32 && in_use == 0u);
+                        const int fs = __builtin_ffs((int) ~slot_busy) - 1;
+                        if (fs < 0)
+                            break; // 32 tiles of this wave in flight (never observed): no new rays until one completes
+                        chunk_end = fetched_end - chunk_next < (unsigned) WAVE ? fetched_end : chunk_next + (unsigned) WAVE;
+                        cur_slot  = (unsigned) fs;
+                        if (lane == 0)
+                            __hip_atomic_store(&done.rem[fs], chunk_end - chunk_next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
                     }
+                    int avail = (int) (chunk_end - chunk_next);
+                    int take  = avail < need ? avail : need;
+                    if (st == ST_IDLE && !got && rank >= off && rank < off + take) {
+                        ridx = chunk_next + (unsigned) (rank - off);
+                        got  = true;
+                        if (FUSED)
+                            cslot = cur_slot;
+                    }
+                    chunk_next += (unsigned) take;
+                    need -= take;
+                    off += take;
                 }
-                if (FUSED && chunk_next == chunk_end) {
-                    // open the next tile of the reservation: a free counter slot, loaded with the tile's ray count
-                    // (a slot is free when its counter is back at zero: the lane that took it there published the tile in
-                    // the same breath, below; looked up here, once per tile, instead of being tracked in every iteration)
-                    const unsigned in_use    = lane < 32 ? __hip_atomic_load(&done.rem[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) : 1u;
-                    const unsigned slot_busy = ~(unsigned) __ballot(lane < 32 && in_use == 0u);
-                    const int fs = __builtin_ffs((int) ~slot_busy) - 1;
-                    if (fs < 0)
-                        break; // 32 tiles of this wave in flight (never observed): no new rays until one completes
-                    chunk_end = fetched_end - chunk_next < (unsigned) WAVE ? fetched_end : chunk_next + (unsigned) WAVE;
-                    cur_slot  = (unsigned) fs;
-                    if (lane == 0)
-                        __hip_atomic_store(&done.rem[fs], chunk_end - chunk_next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                // (the watchdog restarts only when the wave really took rays: a refill that hands out nothing -- the ray
+                // counters dry for this wave, or, FUSED, all 32 tile slots held open by tiles with a ray that does not
+                // advance -- must not keep resetting it, or a wave with eight idle lanes would never reach the limit)
+                if (!BOUNDED && __ballot(got) != 0ull)
+                    spin = 0;
+                if (got) {
+                    // Helper.h:404-418
+                    rt_ray ray;
+                    float ta = 0, tb = 0;
+                    load_ray(P.rays, ridx, ray, ta, tb, true);
+                    px = ray.x;
+                    py = ray.y;
+                    pz = 0.0f;
+                    sx = ta;
+                    sy = tb;
+                    sz = 1.0f;
+                    if (backward) {
+                        sx = -sx;
+                        sy = -sy;
+                        sz = -sz;
+                    }
+                    renormalise(sx, sy, sz);
+                    // A NaN in the start of a ray (a NaN or infinite launch angle -- tanf gives NaN for both --, a NaN
+                    // position) that does not escape at once: every comparison of the escape test and of the cell box
+                    // fails on it, z never advances, and the reference's cell loop (Helper.h:463-504) spins for ever from
+                    // the second segment on.  Such a ray is reported as an invalid ray instead (error -1, what
+                    // Helper.h:515 reports for a direction it cannot use): no march, direction zeroed so that the
+                    // s.z^2 < 0.01 test of the frequency kernel sees it.  (A NaN ray that starts outside the plasma
+                    // escapes in the reference as well and is left alone.)
+                    const BlobGain G0 = hdr[backward ? P.N - 1 : 1];
+                    const float dsum  = sx + sy + sz;
+                    const bool wild   = ((px != px) | (py != py) | (dsum != dsum)) &
+                                      !((px < G0.lo_x) | (px > G0.hi_x) | (py < G0.lo_y) | (py > G0.hi_y));
+                    if (path_on) { // Helper.h:419-426
+                        float *pp = P.path + (size_t) ridx * 3 * (size_t) (S + 1) + 3 * (size_t) (backward ? S : 0);
+                        pp[0]     = px;
+                        pp[1]     = py;
+                    }
+                    // the record's slots are visited in marching order: up from slot 0, or down from slot S-1
+                    recp      = P.rec + rec_slot_off(ridx, backward ? S - 1 : 0, P.rec_stride);
+                    lane12    = (ridx & 63u) * 12u; // (kept for the meta store at retirement)
+                    seg       = 0;
+                    iz        = 0;
+                    ii        = backward ? P.N - 1 : 1;
+                    G         = G0;
+                    z         = 0.0f;
+                    z_stop    = zs0;
+                    gacc      = 0.0f;
+                    eacc      = 0.0f;
+                    cell_last = 0;
+                    steps     = 0;
+                    escaped   = wild; // (an escaped ray commits one empty slot and retires, block [A1])
+                    sx        = wild ? 0.0f : sx;
+                    sy        = wild ? 0.0f : sy;
+                    sz        = wild ? 0.0f : sz;
+                    any_bits  = P.no_skip; // (non-zero: this ray is never marked F_SKIP -- a lineshape table holds a NaN, see DevParams)
+                    sub       = 0;
+                    st        = ST_CELL;
                 }
-                int avail = (int) (chunk_end - chunk_next);
-                int take  = avail < need ? avail : need;
-                if (st == ST_IDLE && !got && rank >= off && rank < off + take) {
-                    ridx = chunk_next + (unsigned) (rank - off);
-                    got  = true;
-                    if (FUSED)
-                        cslot = cur_slot;
-                }
-                chunk_next += (unsigned) take;
-                need -= take;
-                off += take;
+                idle2 = __ballot(st == ST_IDLE); // (no lane waits to be retired here)
             }
-            // (the watchdog restarts only when the wave really took rays: a refill that hands out nothing -- the ray
-            // counters dry for this wave, or, FUSED, all 32 tile slots held open by tiles with a ray that does not
-            // advance -- must not keep resetting it, or a wave with eight idle lanes would never reach the limit)
-            if (!BOUNDED && __ballot(got) != 0ull)
-                spin = 0;
-            if (got) {
-                // Helper.h:404-418
-                rt_ray ray;
-                float ta = 0, tb = 0;
-                load_ray(P.rays, ridx, ray, ta, tb, true);
-                px = ray.x;
-                py = ray.y;
-                pz = 0.0f;
-                sx = ta;
-                sy = tb;
-                sz = 1.0f;
-                if (backward) {
-                    sx = -sx;
-                    sy = -sy;
-                    sz = -sz;
-                }
-                renormalise(sx, sy, sz);
-                // A NaN in the start of a ray (a NaN or infinite launch angle -- tanf gives NaN for both --, a NaN
-                // position) that does not escape at once: every comparison of the escape test and of the cell box
-                // fails on it, z never advances, and the reference's cell loop (Helper.h:463-504) spins for ever from
-                // the second segment on.  Such a ray is reported as an invalid ray instead (error -1, what
-                // Helper.h:515 reports for a direction it cannot use): no march, direction zeroed so that the
-                // s.z^2 < 0.01 test of the frequency kernel sees it.  (A NaN ray that starts outside the plasma
-                // escapes in the reference as well and is left alone.)
-                const BlobGain G0 = hdr[backward ? P.N - 1 : 1];
-                const float dsum  = sx + sy + sz;
-                const bool wild   = ((px != px) | (py != py) | (dsum != dsum)) &
-                                  !((px < G0.lo_x) | (px > G0.hi_x) | (py < G0.lo_y) | (py > G0.hi_y));
-                if (path_on) { // Helper.h:419-426
-                    float *pp = P.path + (size_t) ridx * 3 * (size_t) (S + 1) + 3 * (size_t) (backward ? S : 0);
-                    pp[0]     = px;
-                    pp[1]     = py;
-                }
-                // the record's slots are visited in marching order: up from slot 0, or down from slot S-1
-                recp      = P.rec + rec_slot_off(ridx, backward ? S - 1 : 0, P.rec_stride);
-                lane12    = (ridx & 63u) * 12u; // (kept for the meta store at retirement: that block runs in almost every iteration)
-                seg       = 0;
-                iz        = 0;
-                ii        = backward ? P.N - 1 : 1;
-                G         = G0;
-                z         = 0.0f;
-                z_stop    = zs0;
-                gacc      = 0.0f;
-                eacc      = 0.0f;
-                cell_last = 0;
-                steps     = 0;
-                escaped   = wild; // (an escaped ray commits one empty slot and retires, block [A1])
-                sx        = wild ? 0.0f : sx;
-                sy        = wild ? 0.0f : sy;
-                sz        = wild ? 0.0f : sz;
-                any_bits  = P.no_skip; // (non-zero: this ray is never marked F_SKIP -- a lineshape table holds a NaN, see DevParams)
-                sub       = 0;
-                st        = ST_CELL;
-            }
-            idle2 = __ballot(st == ST_IDLE);
-        }
-        // (at this point every lane is idle, waits for [A], or is in [B] / [C]: the three lane masks the loop
-        // head needs follow from two ballots)
+        } // retirement and refill
+        // (at this point every lane is idle or waits to be retired, waits for [A], or is in [B] / [C]: the three lane
+        // masks the loop head needs follow from two ballots)
         if (idle2 == ~0ull) {
             if (!more)
                 break;
@@ -1087,7 +1195,8 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
                 const bool fin  = escaped | (sub == S);
                 iz              = wrap ? 0 : iz + 1;
                 z               = wrap ? 0.0f : z;
-                st              = fin ? ST_DONE : ST_CELL;
+                st              = fin ? ST_DONE : ST_CELL; // (finished: retired at the loop head, "ray finished")
+                diag.finishing(st);
                 if (wrap & !fin) { // twice per ray
                     if (OPT & MARCH_OPT_SCAN) { // the ray leaves length seg + 1 for the next: its state there (rt_step_scan.hip)
                         unsigned char *bnd = reinterpret_cast<unsigned char *>(((unsigned long long) P.pad_march[1] << 32) | (unsigned long long) P.pad_march[0]);
@@ -1215,55 +1324,8 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
                     }
                 }
             }
-            diag.mark(2); // [A2]
-            // ---------------------------------------------------------- ray finished
-            if (st == ST_DONE) {
-                unsigned fl = F_VALID;
-                if (escaped)
-                    fl |= F_ESCAPED;
-                if (use_emis && any_bits == 0u)
-                    fl |= F_SKIP; // every frequency update is the identity: contributes exactly +0 (finite lineshape)
-                RecMeta m;
-                m.px          = px;
-                m.py          = py;
-                m.sx          = sx;
-                m.sy          = sy;
-                m.sz          = sz;
-                // (the per-ray step count of the record saturates at 2^20 - 1; the launch total below is exact)
-                m.flags_steps = fl | ((unsigned) sub << REC_NDONE_SHIFT) |
-                                ((steps < 0xfffffu ? steps : 0xfffffu) << REC_STEPS_SHIFT);
-                // `sub` slots were committed: recp stands that many slot rows above slot 0 (forward) or below
-                // slot S-1 (backward); the meta blocks of the tile follow slot row S-1, 24 bytes per ray where a slot has 12
-                unsigned char *metap = recp + (int) REC_SLOT_ROW * (backward ? sub + 1 : S - sub) + lane12;
-#ifndef RT_ABL_NOMETA
-                *reinterpret_cast<RecMeta *>(metap) = m;
-#else
-                if (m.px == 1234.5f) // profiling only: the store stays reachable, but never happens
-                    *reinterpret_cast<RecMeta *>(metap) = m;
-#endif
-                diag.ray_retired(ridx);
-                tot_steps += steps;
-                tot_esc += escaped ? 1u : 0u;
-                tot_skip += (fl & F_SKIP) ? 1u : 0u;
-                tot_rays++;
-                st = ST_IDLE;
-                // One ray of the lane's tile less; the lane that takes the counter to zero has finished the tile and
-                // publishes it on the spot: every record of the tile was stored by THIS wave (the other rays retired in
-                // earlier iterations or in this very block), so once the wave's stores have landed the tile may be read.
-                // (Round 4 collected those lanes with a ballot after the block -- in every iteration, for an event that
-                // happens once in ~35: the loop head pays for every instruction, DESIGN.md 4.5.)
-                if (FUSED) {
-                    if (__hip_atomic_fetch_add(&done.rem[cslot], 0xffffffffu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) == 1u) {
-                        diag.publish_begin();
-                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                        diag.publish_stores_landed();
-                        tile_publish(done, ridx >> 6);
-                        diag.publish_end();
-                    }
-                }
-            }
         }
-        diag.mark(3); // DONE
+        diag.mark(2); // [A2] (a lane that finished in [A1] stays ST_DONE: retired at the loop head, "ray finished")
         // ------------------------------------------------------------ [B] cross-cell setup (Helper.h:328-342)
         if (st == ST_XSETUP) {
             const float ya   = mirror ? fabsf(py) : py;
