@@ -654,6 +654,52 @@ int rt_hip_full_step_loop(int device, int N, const rt_beam *beam, const rt_gain 
                           double *nf, double *I_ang, unsigned int *failure_codes, rt_ray *failed_rays, int max_failed,
                           int *n_failed, rt_stats *stats);
 
+/*
+ * ASE seeds of a length scan: the WHOLE per-step record at EVERY plasma length from ONE forward march.  The two premises
+ * are those of the two sections above: the march does not depend on the emission switch apart from evl, and the forward run
+ * of n lengths is a prefix of the run of N.  With scan ASE seeds installed a step run of an emission scan plan marches once
+ * (the scan march unchanged) and rt_step_scan_ase_seeds_kernel (raytrace-miniapp_amd/csrc/rt_step_scan_ase_seeds.hip, in
+ * place of rt_step_scan_kernel; reported as freq_ms) leaves record (r, n) for r = 0 .. n_seed and n = 2 .. N:
+ *   (0, n)      record n of the plain emission scan plan: what a step run of the prefix problem of n lengths leaves;
+ *   (1 + s, n)  what a step run leaves of that prefix problem CREATED WITH SEED s -- the same tables, rays and method, scale
+ *               scales[s]: gain-only, Iv[k] = f0_s f_s[4][k] exp(gl_n[k]), the seed factor at the launch ray, 0 where the
+ *               ray has escaped by that length.
+ *   Every Iv is the double the plain emission scan plan, respectively the scan plan created with a seed and holding seed s
+ *   among its scan seeds, computes; the sums differ from those plans' by summation order only.  A ray whose march sums over
+ *   the whole N-run are all zero (n_skipped) is left out of the ASE records and is part of the seed records.
+ * set_scan_ase_seeds: accepted only on an emission plan (created without a seed, tables with E0) while its length scan is
+ *   on; anything else is RT_ERR_ARG.  n_seed = 1 .. RT_N_SEED_MAX installs seeds[0 .. n_seed), validated and copied as
+ *   rt_hip_plan_set_ase_seeds does it; scales[s] is the scale of the curve of seed s, NULL: the plan's scale for all.
+ *   n_seed = 0 removes them: the plan is then a plain emission scan plan.  rt_hip_plan_enable_length_scan(plan, 0) drops
+ *   them; rt_hip_plan_update_gain / _dev keep them; set_rays / set_ray_grid work before or after (the ray set of the run
+ *   decides between the factor tables of a forward ray grid and the launch rays).  rt_hip_plan_set_step_one_launch is
+ *   accepted, the run keeps two kernels.  The refusals of the neighbours stay: rt_hip_plan_set_ase_seeds refuses a scan
+ *   plan, rt_hip_plan_enable_length_scan a plan with rt_hip_plan_set_ase_seeds seeds, rt_hip_plan_set_scan_seeds a plan
+ *   created without a seed; everything the scan refuses stays refused (lent step buffers, image_dev / iang_dev, path,
+ *   spectra).
+ * Outputs: ONE allocation of the plan: (1 + n_seed) (N - 1) blocks of the seed-set layout and stride, record (r, n) = block
+ *   r (N - 1) + (n - 2) -- a record's curve is contiguous, the ASE curve first.  full_length_step_ptrs /
+ *   fetch_full_length_step: r = 0 .. n_seed, n = 2 .. N (anything else is RT_ERR_ARG); any pointer may be NULL;
+ *   *failure_code is the code of (r, n).  rt_hip_plan_fetch_length_step and rt_hip_plan_length_step_ptrs serve the ASE
+ *   curve; rt_hip_plan_fetch_step, rt_hip_plan_step_ptrs and I_ang of rt_hip_plan_fetch serve (0, N).
+ *   rt_hip_plan_fetch_full_step and rt_hip_plan_fetch_seed_length_step are RT_ERR_ARG after such a run.
+ * Failures follow the reference run once per (record, length): error -1 at length j puts the ray in no record of that
+ *   length; error -2 / -3 under (r, j) removes the ray from (r, j) only.  rt_hip_plan_fetch reports the OR of all codes and
+ *   the rays that fail anywhere, each once (more than RT_N_FAILED_MAX: the first of them in list order); the counters are
+ *   those of one run.  RT_N_SCAN_MAX stays 32: the checking repeat marks one bit per (record, length) in 16 bytes per ray.
+ * rt_hip_full_length_scan_loop: the host-pointer form, rt_hip_full_step_loop's arguments: E_v [1+n_seed][N-1][nv], nf
+ *   [1+n_seed][N-1][nx*ny], I_ang [1+n_seed][N-1][na*nb], failure_codes [1+n_seed][N-1] (may be NULL).
+ * Not taken: the multi-device loops, the one-launch form, image or spectra per length, the backward method.
+ */
+int rt_hip_plan_set_scan_ase_seeds(rt_hip_plan *plan, int n_seed, const rt_seed *seeds, const double *scales);
+int rt_hip_plan_fetch_full_length_step(rt_hip_plan *plan, int r, int n, double *E_v, double *nf, double *I_ang,
+                                       unsigned int *failure_code);
+int rt_hip_plan_full_length_step_ptrs(rt_hip_plan *plan, int r, int n, double **E_v_dev, double **nf_dev, double **iang_dev);
+int rt_hip_full_length_scan_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, int method, const rt_ray *rays,
+                                 size_t n_rays, double scale, int n_seed, const rt_seed *seeds, const double *scales,
+                                 double *E_v, double *nf, double *I_ang, unsigned int *failure_codes, rt_ray *failed_rays,
+                                 int max_failed, int *n_failed, rt_stats *stats);
+
 /* Profiling aid (no reference counterpart): bit 0 = skip the frequency / deposit kernel, bit 1 = skip
  * the march and run the frequency pass over the records of the previous run of this plan, bit 2 = the
  * frequency kernel keeps its per-work-group I_ang sums to itself (I_ang stays zero).  0 = normal. */

@@ -132,6 +132,7 @@ class Plan:
         self.hl.check(rc, "rt_hip_plan_create")
         self.n_rays = 0
         self._n_ase_seed = 0    # ASE seeds installed (set_ase_seeds)
+        self._n_scan_ase_seed = 0   # ASE seeds of the length scan installed (set_scan_ase_seeds)
 
     # -- rays ---------------------------------------------------------------
     def set_rays(self, rays: np.ndarray) -> "Plan":
@@ -400,6 +401,7 @@ class Plan:
         self._scan = bool(on)
         if not on:
             self._n_scan_seed = 0   # (switching the scan off drops its seeds)
+            self._n_scan_ase_seed = 0
         return self
 
     def fetch_length_steps(self) -> list:
@@ -448,6 +450,50 @@ class Plan:
         run's stream or after a fetch."""
         seeds, lengths = self._scan_seed_range()
         return [[dict(n=n, **self._record_views(self.seed_length_step_ptrs(s, n))) for n in lengths] for s in seeds]
+
+    # -- the ASE seeds of a scan --------------------------------------------
+    def set_scan_ase_seeds(self, seeds, scales=None) -> "Plan":
+        """The ASE seeds of the length scan (include/rt_hip.h, rt_hip_plan_set_scan_ase_seeds): up to RT_N_SEED_MAX Seed records
+        on an EMISSION plan (created without a seed, tables with E0) whose scan is on.  A step run then leaves, from one
+        forward march, the plan's emission record and the gain-only record of the same problem created with each seed, scale
+        scales[s] (None: the plan's scale), at every length n = 2 .. N; [] removes them.  More seeds than that, anything that is
+        not a Seed, or scales of another length is a ValueError raised here, before any native call."""
+        seeds, arr, _keep = _seed_array(seeds, "set_scan_ase_seeds", "a step record")
+        sc = None
+        if scales is not None:
+            sc = np.ascontiguousarray(scales, dtype=np.float64)
+            if sc.shape != (len(seeds),):
+                raise ValueError(f"set_scan_ase_seeds: {sc.size} scales for {len(seeds)} seeds")
+        self.hl.check(self.hl.lib.rt_hip_plan_set_scan_ase_seeds(self._h, len(seeds), arr if seeds else None,
+                                                                 cabi._dp(sc) if sc is not None and len(seeds) else None),
+                      "rt_hip_plan_set_scan_ase_seeds")
+        self._n_scan_ase_seed = len(seeds)
+        return self
+
+    def _full_length_range(self):
+        on = getattr(self, "_scan", False) and self._n_scan_ase_seed > 0
+        return range(1 + self._n_scan_ase_seed if on else 0), range(2, self.problem.N + 1 if on else 2)
+
+    def fetch_full_length_steps(self) -> dict:
+        """dict(ase=[rec per n], seeds=[[rec per n] per seed]) for n = 2 .. N lengths of the last step run of a scan with ASE
+        seeds (waits for it; a failing run is repeated in the checking mode first); every rec is dict(n, E_v [nv], nf
+        [nx * ny], I_ang [na * nb], failure_code)."""
+        recs, lengths = self._full_length_range()
+        curves = [[dict(n=n, **self._fetch_record("rt_hip_plan_fetch_full_length_step", r, n)) for n in lengths] for r in recs]
+        return dict(ase=curves[0] if curves else [], seeds=curves[1:])
+
+    def full_length_step_ptrs(self, r: int, n: int) -> tuple:
+        """Device pointers (E_v, nf, I_ang) of record r (0: ASE, 1 + s: seed s) at n lengths of the last step run of a scan
+        with ASE seeds."""
+        return self._record_ptrs("rt_hip_plan_full_length_step_ptrs", r, n)
+
+    def full_length_step_tensors(self) -> dict:
+        """dict(ase=[views per n], seeds=[[views per n] per seed]): torch views (float64, on the plan's device, no copy) of E_v
+        [nv], nf [ny][nx] and I_ang [nb][na] of every record of the last step run of a scan with ASE seeds -- blocks of one
+        allocation, valid until the plan's next run; read them on the run's stream or after a fetch."""
+        recs, lengths = self._full_length_range()
+        curves = [[dict(n=n, **self._record_views(self.full_length_step_ptrs(r, n))) for n in lengths] for r in recs]
+        return dict(ase=curves[0] if curves else [], seeds=curves[1:])
 
     # -- tables -------------------------------------------------------------
     def update_gain(self, gain, stream: int | None = None) -> "Plan":
@@ -706,6 +752,58 @@ def full_step_loop(problem: Problem, seeds, scales=None, rays: np.ndarray | None
     for r in recs:
         code |= r["failure_code"]
     return dict(ase=recs[0], seeds=recs[1:], failure_code=code, failed_rays=failed[:nfail.value].copy(),
+                stats={k: getattr(st, k) for k, _ in cabi.RtStats._fields_})
+
+
+def full_length_scan_loop(problem: Problem, seeds, scales=None, rays: np.ndarray | None = None, device: int = 0) -> dict:
+    """The whole per-step record at every plasma length n = 2 .. N from ONE forward march of the problem's rays
+    (rt_hip_full_length_scan_loop, host pointers; rays None: the problem's ray grid as a list): the emission record of
+    `problem`, which must carry no seed and tables with E0, and the gain-only record of the same problem under each Seed of
+    `seeds` (1 .. RT_N_SEED_MAX) with scale scales[s] (None: the problem's scale).  Returns dict(ase = [rec per n], seeds =
+    [[rec per n] per seed], failure_code = the OR of the codes, failed_rays, stats), every rec dict(n, E_v, nf, I_ang,
+    failure_code).  What the scan does not take, no seed or too many, an entry that is not a Seed, scales of another length
+    or a problem with a seed is a ValueError raised here, before any native call."""
+    if problem.method != 2:
+        raise ValueError(f"full_length_scan_loop: the problem's method is {problem.method}; the scan takes the forward method (2) only")
+    if problem.N < 3 or problem.N - 1 > cabi.RT_N_SCAN_MAX:
+        raise ValueError(f"full_length_scan_loop: N = {problem.N}; a scan takes 3 <= N <= RT_N_SCAN_MAX + 1 = {cabi.RT_N_SCAN_MAX + 1}")
+    seeds = list(seeds)
+    if not 1 <= len(seeds) <= cabi.RT_N_SEED_MAX:
+        raise ValueError(f"full_length_scan_loop: {len(seeds)} seeds given, 1 .. RT_N_SEED_MAX = {cabi.RT_N_SEED_MAX} are taken")
+    for i, sd in enumerate(seeds):
+        if not isinstance(sd, Seed):
+            raise ValueError(f"full_length_scan_loop: entry {i} is a {type(sd).__name__}, not a Seed")
+    if problem.seed is not None:
+        raise ValueError("full_length_scan_loop: the problem carries a seed; the ASE record needs an emission problem")
+    sc = None
+    if scales is not None:
+        sc = np.ascontiguousarray(scales, dtype=np.float64)
+        if sc.shape != (len(seeds),):
+            raise ValueError(f"full_length_scan_loop: {sc.size} scales for {len(seeds)} seeds")
+    hl = HipLibrary.get()
+    m = cabi.Marshalled(problem)
+    if rays is None:
+        rays = problem.build_rays()
+    rays = np.ascontiguousarray(rays, dtype=cabi.RAY_DTYPE)
+    _, arr, _keep = _seed_array(seeds, "full_length_scan_loop", "a step record")   # (checked above: marshalled only)
+    b, L, nr = problem.beam, problem.N - 1, 1 + len(seeds)
+    E_v, nf, iang = np.zeros((nr, L, b.nv)), np.zeros((nr, L, b.nx * b.ny)), np.zeros((nr, L, b.na * b.nb))
+    codes = (C.c_uint * (nr * L))()
+    nfail = C.c_int(0)
+    failed = np.zeros(cabi.RT_N_FAILED_MAX, dtype=cabi.RAY_DTYPE)
+    st = cabi.RtStats()
+    rc = hl.lib.rt_hip_full_length_scan_loop(device, m.N, C.byref(m.beam), m.gain, problem.method, cabi.rays_ptr(rays), len(rays),
+                                             problem.scale, len(seeds), arr, cabi._dp(sc) if sc is not None else None, cabi._dp(E_v),
+                                             cabi._dp(nf), cabi._dp(iang), codes, cabi.rays_ptr(failed), cabi.RT_N_FAILED_MAX,
+                                             C.byref(nfail), C.byref(st))
+    hl.check(rc, "rt_hip_full_length_scan_loop")
+    curves = [[dict(n=i + 2, E_v=E_v[r, i].copy(), nf=nf[r, i].copy(), I_ang=iang[r, i].copy(), failure_code=int(codes[r * L + i]))
+               for i in range(L)] for r in range(nr)]
+    code = 0
+    for curve in curves:
+        for r in curve:
+            code |= r["failure_code"]
+    return dict(ase=curves[0], seeds=curves[1:], failure_code=code, failed_rays=failed[:nfail.value].copy(),
                 stats={k: getattr(st, k) for k, _ in cabi.RtStats._fields_})
 
 

@@ -400,6 +400,15 @@ def declare_hip_api(lib: C.CDLL) -> None:
             C.c_int, C.c_int, P(RtBeam), P(RtGain), C.c_int, P(RtRay), C.c_size_t, C.c_double, C.c_int, P(RtSeed), c_double_p,
             c_double_p, c_double_p, c_double_p, P(C.c_uint), P(RtRay), C.c_int, P(C.c_int), P(RtStats)]
         lib.rt_hip_full_step_loop.restype = C.c_int
+    if hasattr(lib, "rt_hip_plan_set_scan_ase_seeds"):   # (likewise)
+        lib.rt_hip_plan_set_scan_ase_seeds.argtypes = [vp, C.c_int, P(RtSeed), c_double_p]
+        lib.rt_hip_plan_set_scan_ase_seeds.restype = C.c_int
+        lib.rt_hip_plan_fetch_full_length_step.argtypes = [vp, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, P(C.c_uint)]
+        lib.rt_hip_plan_fetch_full_length_step.restype = C.c_int
+        lib.rt_hip_plan_full_length_step_ptrs.argtypes = [vp, C.c_int, C.c_int, P(vp), P(vp), P(vp)]
+        lib.rt_hip_plan_full_length_step_ptrs.restype = C.c_int
+        lib.rt_hip_full_length_scan_loop.argtypes = list(lib.rt_hip_full_step_loop.argtypes)   # (one row per record and length)
+        lib.rt_hip_full_length_scan_loop.restype = C.c_int
     lib.rt_hip_plan_set_debug.argtypes = [vp, C.c_uint]
     lib.rt_hip_plan_set_debug.restype = C.c_int
     lib.rt_hip_plan_destroy.argtypes = [vp]
@@ -422,6 +431,8 @@ HIP_API_SYMBOLS = [
     "rt_hip_plan_set_scan_seeds", "rt_hip_plan_fetch_seed_length_step", "rt_hip_plan_seed_length_step_ptrs",
     "rt_hip_seed_length_scan_loop",
     "rt_hip_plan_set_ase_seeds", "rt_hip_plan_fetch_full_step", "rt_hip_plan_full_step_ptrs", "rt_hip_full_step_loop",
+    "rt_hip_plan_set_scan_ase_seeds", "rt_hip_plan_fetch_full_length_step", "rt_hip_plan_full_length_step_ptrs",
+    "rt_hip_full_length_scan_loop",
     "rt_hip_plan_set_step_one_launch", "rt_hip_debug_run_shape",
     "rt_hip_plan_set_debug", "rt_hip_plan_destroy",
 ]

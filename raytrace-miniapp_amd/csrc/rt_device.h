@@ -153,6 +153,9 @@ struct DevCtl {
     // rt_step_ase_seeds_kernel: the failure code of every record of an emission plan with ASE seeds, [0] the ASE record,
     // [1 + s] seed s (failure_code above is their OR; the last entry pads the block to 8-byte words).  At the end likewise.
     unsigned int rec_code[RT_N_SEED_MAX + 2];
+    // rt_step_scan_ase_seeds_kernel: the failure code of every (record, length) of a length scan with ASE seeds, [r][n - 2]
+    // with r = 0 the ASE record, 1 + s seed s (failure_code above is their OR).  At the end likewise.
+    unsigned int rec_len_code[1 + RT_N_SEED_MAX][RT_N_SCAN_MAX];
 };
 
 // probe outputs of the frequency kernel (gvl / evl / ivl are read back from the records)

@@ -18,6 +18,7 @@
 #include "rt_step_scan.hip" // step mode with a length scan: one record per plasma length from one forward march
 #include "rt_step_scan_seeds.hip" // ... with the seeds of the scan: one record per (seed, length) from that march
 #include "rt_step_ase_seeds.hip"  // step kernel of an emission plan with ASE seeds: the ASE record and one per seed from one march
+#include "rt_step_scan_ase_seeds.hip" // ... with the length scan on: that whole record at every length from one forward march
 
 #include "rt_runtime.h"
 #include "rt_run_shape.h" // what a run looks like: the pure decision (facts + tuning -> shape) this file enqueues
@@ -280,9 +281,10 @@ int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kin
         nullptr, // PASS_PATH
         "step kernel of a length scan: the E_v accumulators (nv doubles per length) do not fit into the LDS of this device",
         "step kernel of a length scan with scan seeds: the E_v accumulators (nv doubles per seed and length) do not fit into the LDS of this device",
-        "step kernel of an emission plan with ASE seeds: the E_v accumulators (nv doubles for ASE and per seed) do not fit into the LDS of this device" };
+        "step kernel of an emission plan with ASE seeds: the E_v accumulators (nv doubles for ASE and per seed) do not fit into the LDS of this device",
+        "step kernel of a length scan with ASE seeds: the E_v accumulators (nv doubles per record and length) do not fit into the LDS of this device" };
     static_assert(PASS_SPEC == 1 && PASS_STEP == 2 && PASS_SEEDS == 3 && PASS_SCAN == 5 && PASS_SCAN_SEEDS == 6 && PASS_ASE_SEEDS == 7 &&
-                      sizeof(too_big) / sizeof(too_big[0]) == 8,
+                      PASS_SCAN_ASE_SEEDS == 8 && sizeof(too_big) / sizeof(too_big[0]) == 9,
                   "too_big[] is indexed by PassKind");
     if (too_big[kind] && s.lds > f.lds_limit)
         return fail_arg(too_big[kind]);
@@ -332,6 +334,26 @@ int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kin
         a.set.n_seed   = f.n_seed;
         const int rc   = fill_seed_tabs(a.set.tabs, p, f.n_seed, p->P.rays.sf != nullptr, "step kernel of a length scan with scan seeds: the factor tables of the seeds");
         return rc != RT_OK ? rc : launch(p, rt::rt_step_scan_seeds_kernel, s.grid, block, s.lds, stream, a);
+    }
+    if (kind == PASS_SCAN_ASE_SEEDS) { // a length scan with ASE seeds (an emission plan): one record per (ASE | seed, length)
+        if (!p->scan_bnd || !p->recs_dev)
+            return fail_arg("step kernel of a length scan with ASE seeds: the boundary states or the records of this run were not allocated");
+        if (f.n_seed < 1 || f.n_seed > RT_N_SEED_MAX || f.L > RT_N_SCAN_MAX || !f.use_emis)
+            return fail_arg("step kernel of a length scan with ASE seeds: not an emission run of 1 .. RT_N_SEED_MAX seeds and at most RT_N_SCAN_MAX lengths");
+        if (p->recs_doubles < (size_t) n_rec * p->recs_stride)
+            return fail_arg("step kernel of a length scan with ASE seeds: the records of this run are smaller than (1 + n_seed) (N - 1) blocks");
+        rt::ScanAseSeedsKArg a = pass_args<rt::ScanAseSeedsKArg>(fa);
+        a.hot.iang     = nullptr; // (every record's I_ang lies in its block)
+        a.hot.seed_fk  = nullptr; // (an emission plan has no creation seed)
+        a.hot.flags &= ~(unsigned) rt::FQ_EXCLUSIVE; // (nf of every record by atomics)
+        fill_scan(a.scan, p);
+        a.set.n_seed   = f.n_seed;
+        for (int r = 0; r <= f.n_seed; r++)
+            a.set.scale[r] = r == 0 ? p->P.scale : p->ase_scale[r - 1];
+        // (the ray set of the run decides between the factor tables and the launch rays, as for PASS_ASE_SEEDS below)
+        const bool grid_tabs = p->P.rays.gx && !p->P.rays.list && p->seedset_sf[0] != nullptr;
+        const int rc = fill_seed_tabs(a.set.tabs, p, f.n_seed, grid_tabs, "step kernel of a length scan with ASE seeds: the factor tables of the seeds");
+        return rc != RT_OK ? rc : launch(p, rt::rt_step_scan_ase_seeds_kernel, s.grid, block, s.lds, stream, a);
     }
     if (kind == PASS_ASE_SEEDS) { // an emission plan with ASE seeds: block 0 the ASE record, block 1 + s the record of seed s
         if (f.n_seed < 1 || f.n_seed > RT_N_SEED_MAX || !f.use_emis || !p->recs_dev)
@@ -466,6 +488,7 @@ int plan_repeat_checked(rt_hip_plan *p)
     HIP_TRY(hipMemsetAsync(p->ctl->len_code, 0, sizeof(p->ctl->len_code), stream));
     HIP_TRY(hipMemsetAsync(p->ctl->seed_len_code, 0, sizeof(p->ctl->seed_len_code), stream));
     HIP_TRY(hipMemsetAsync(p->ctl->rec_code, 0, sizeof(p->ctl->rec_code), stream));
+    HIP_TRY(hipMemsetAsync(p->ctl->rec_len_code, 0, sizeof(p->ctl->rec_len_code), stream));
     HIP_TRY(hipMemsetAsync(p->ctl->next_tile_f, 0, sizeof(p->ctl->next_tile_f), stream));
     const bool step = p->last_step; // a step run: the step kernel honours the same marks, E_v and nf start over
     RunFacts f          = run_facts(p);

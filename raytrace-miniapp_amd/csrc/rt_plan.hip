@@ -634,7 +634,8 @@ int rtr::plan_build_seedset_tabs(rt_hip_plan *p)
     const int n_set = p->n_seed > 0 ? p->n_seed : p->n_scan_seed; // (a seed set, or the seeds of a scan: never both)
     // (R.sf: a ray grid, a seeded plan, the forward method; ASE seeds on an emission plan, which has no creation seed and
     // hence no R.sf: the same grid and method)
-    const bool ase_grid = p->P.use_emis && p->n_seed > 0 && !R.list && R.gx && p->P.method != 1;
+    // (... and the ASE seeds of a scan, which is forward by construction)
+    const bool ase_grid = p->P.use_emis && n_set > 0 && !R.list && R.gx && p->P.method != 1;
     if (n_set < 1 || (!R.sf && !ase_grid))
         return RT_OK;
     const size_t nn = (size_t) R.ngx + (size_t) R.ngy + (size_t) R.nga + (size_t) R.ngb;
@@ -1290,6 +1291,7 @@ static unsigned record_code(const rt::DevCtl &c, const RecordSet &R, int block)
     case REC_ASE_SEEDS: return c.rec_code[block];
     case REC_SCAN: return c.len_code[block];
     case REC_SCAN_SEEDS: return c.seed_len_code[block / R.L][block % R.L];
+    case REC_SCAN_ASE_SEEDS: return c.rec_len_code[block / R.L][block % R.L];
     default: return c.failure_code;
     }
 }
@@ -1467,7 +1469,7 @@ int rt_hip_plan_enable_length_scan(rt_hip_plan *p, int on)
     return RT_OK;
 }
 
-// (on a scan with scan seeds a length alone means seed 0's curve)
+// (on a scan with scan seeds a length alone means seed 0's curve, on a scan with ASE seeds the ASE curve)
 int rt_hip_plan_fetch_length_step(rt_hip_plan *p, int n, double *E_v, double *nf, double *I_ang, unsigned int *failure_code)
 {
     if (!p || !p->last_records.scan())
@@ -1623,6 +1625,49 @@ int rt_hip_plan_set_ase_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds, 
     for (int s = 0; s < RT_N_SEED_MAX; s++)
         p->ase_scale[s] = (s < n_seed && scales) ? scales[s] : p->P.scale;
     return RT_OK;
+}
+
+// ASE seeds of a length scan: the same seeds on an emission plan whose scan is on (include/rt_hip.h).  They travel as the
+// seeds of a scan do (n_scan_seed); what makes them ASE seeds is the plan again: use_emis with n_scan_seed > 0.
+int rt_hip_plan_set_scan_ase_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds, const double *scales)
+{
+    if (!p)
+        return fail_arg("rt_hip_plan_set_scan_ase_seeds: NULL plan");
+    if (p->P.has_seed || !p->P.use_emis)
+        return fail_arg("rt_hip_plan_set_scan_ase_seeds: not an emission plan (created without a seed, tables with E0)");
+    if (!p->scan_on)
+        return fail_arg("rt_hip_plan_set_scan_ase_seeds: the length scan is off (rt_hip_plan_enable_length_scan first)");
+    const int rv = seeds_validate(p, "rt_hip_plan_set_scan_ase_seeds", n_seed, seeds);
+    if (rv != RT_OK)
+        return rv;
+    const int rc = seeds_install(p, n_seed, seeds, true);
+    if (rc != RT_OK)
+        return rc;
+    for (int s = 0; s < RT_N_SEED_MAX; s++)
+        p->ase_scale[s] = (s < n_seed && scales) ? scales[s] : p->P.scale;
+    return RT_OK;
+}
+
+int rt_hip_plan_fetch_full_length_step(rt_hip_plan *p, int r, int n, double *E_v, double *nf, double *I_ang, unsigned int *failure_code)
+{
+    if (!p || p->last_records.kind != REC_SCAN_ASE_SEEDS)
+        return fail_arg("rt_hip_plan_fetch_full_length_step: the last run was not a step run of a length scan with ASE seeds");
+    if (p->last_records.block(r, 2) < 0) // (every scan has length 2)
+        return fail_arg("rt_hip_plan_fetch_full_length_step: r must be 0 (ASE) .. n_seed of the last run");
+    if (p->last_records.block(r, n) < 0)
+        return fail_arg("rt_hip_plan_fetch_full_length_step: n must be 2 .. N of the last run");
+    return record_fetch(p, p->last_records.block(r, n), E_v, nf, I_ang, failure_code);
+}
+
+int rt_hip_plan_full_length_step_ptrs(rt_hip_plan *p, int r, int n, double **E_v_dev, double **nf_dev, double **iang_dev)
+{
+    if (!p || p->last_records.kind != REC_SCAN_ASE_SEEDS)
+        return fail_arg("rt_hip_plan_full_length_step_ptrs: the last run was not a step run of a length scan with ASE seeds");
+    if (p->last_records.block(r, 2) < 0)
+        return fail_arg("rt_hip_plan_full_length_step_ptrs: r must be 0 (ASE) .. n_seed of the last run");
+    if (p->last_records.block(r, n) < 0)
+        return fail_arg("rt_hip_plan_full_length_step_ptrs: n must be 2 .. N of the last run");
+    return record_ptrs(p, p->last_records.block(r, n), E_v_dev, nf_dev, iang_dev);
 }
 
 int rt_hip_plan_fetch_full_step(rt_hip_plan *p, int r, double *E_v, double *nf, double *I_ang, unsigned int *failure_code)
@@ -1933,20 +1978,22 @@ int rt_hip_seed_length_scan_loop(int device, int N, const rt_beam *beam, const r
 
 // The whole per-step record through host pointers: an emission plan of its own with the seeds as ASE seeds, the list
 // uploaded, one run; row 0 of every output is the ASE record, row 1 + s seed s.
-int rt_hip_full_step_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, int method, const rt_ray *rays, size_t n_rays,
-                          double scale, int n_seed, const rt_seed *seeds, const double *scales, double *E_v, double *nf, double *I_ang,
+// (scan: rt_hip_full_length_scan_loop -- the length scan on, the seeds as its ASE seeds, rows [1 + n_seed][N - 1][...])
+static int full_step_loop(const char *who, bool scan, int device, int N, const rt_beam *beam, const rt_gain *gain, int method, const rt_ray *rays,
+                          size_t n_rays, double scale, int n_seed, const rt_seed *seeds, const double *scales, double *E_v, double *nf, double *I_ang,
                           unsigned int *failure_codes, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats)
 {
+    auto fail = [&](const char *what) { return fail_arg((std::string(who) + what).c_str()); };
     if (!beam)
-        return fail_arg("rt_hip_full_step_loop: NULL beam");
+        return fail(": NULL beam");
     if (!E_v || !nf || !I_ang)
-        return fail_arg("rt_hip_full_step_loop: NULL output");
+        return fail(": NULL output");
     if (!rays && n_rays)
-        return fail_arg("rt_hip_full_step_loop: NULL ray list");
+        return fail(": NULL ray list");
     if (n_rays > MAX_LIST_RAYS)
-        return fail_arg("rt_hip_full_step_loop: 2^32 - 4096 rays or more: split the call");
+        return fail(": 2^32 - 4096 rays or more: split the call");
     if (n_seed < 1 || n_seed > RT_N_SEED_MAX || !seeds)
-        return fail_arg("rt_hip_full_step_loop: n_seed must be 1 .. RT_N_SEED_MAX, with seeds");
+        return fail(": n_seed must be 1 .. RT_N_SEED_MAX, with seeds");
     hipStream_t q  = lease_queue(device);
     rt_hip_plan *p = nullptr;
     int rc         = plan_create_on(&p, q, device, N, beam, gain, nullptr, method, scale);
@@ -1955,8 +2002,10 @@ int rt_hip_full_step_loop(int device, int N, const rt_beam *beam, const rt_gain 
         return rc;
     }
     rc = rt_hip_plan_enable_step(p, 1);
+    if (rc == RT_OK && scan)
+        rc = rt_hip_plan_enable_length_scan(p, 1);
     if (rc == RT_OK)
-        rc = rt_hip_plan_set_ase_seeds(p, n_seed, seeds, scales);
+        rc = scan ? rt_hip_plan_set_scan_ase_seeds(p, n_seed, seeds, scales) : rt_hip_plan_set_ase_seeds(p, n_seed, seeds, scales);
     if (rc == RT_OK)
         rc = plan_set_rays_deferred(p, rays, n_rays);
     if (rc == RT_OK)
@@ -1968,6 +2017,23 @@ int rt_hip_full_step_loop(int device, int N, const rt_beam *beam, const rt_gain 
     rt_hip_plan_destroy(p); // waits for whatever is still in flight
     release_queue(device, q);
     return rc;
+}
+
+int rt_hip_full_step_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, int method, const rt_ray *rays, size_t n_rays,
+                          double scale, int n_seed, const rt_seed *seeds, const double *scales, double *E_v, double *nf, double *I_ang,
+                          unsigned int *failure_codes, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats)
+{
+    return full_step_loop("rt_hip_full_step_loop", false, device, N, beam, gain, method, rays, n_rays, scale, n_seed, seeds, scales, E_v, nf, I_ang,
+                          failure_codes, failed_rays, max_failed, n_failed, stats);
+}
+
+// ... at every length: the length scan on, the seeds as its ASE seeds; rows [1 + n_seed][N - 1][...], the ASE curve first
+int rt_hip_full_length_scan_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, int method, const rt_ray *rays, size_t n_rays,
+                                 double scale, int n_seed, const rt_seed *seeds, const double *scales, double *E_v, double *nf, double *I_ang,
+                                 unsigned int *failure_codes, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats)
+{
+    return full_step_loop("rt_hip_full_length_scan_loop", true, device, N, beam, gain, method, rays, n_rays, scale, n_seed, seeds, scales, E_v, nf,
+                          I_ang, failure_codes, failed_rays, max_failed, n_failed, stats);
 }
 
 int rt_hip_calc_rays(int device, int N, double dz, const rt_gain *gain, const rt_seed *seed, int K, int method, const double *rays,

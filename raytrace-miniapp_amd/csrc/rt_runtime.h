@@ -73,7 +73,8 @@ struct rt_hip_plan {
     // the seeds a step run takes beside the creation seed: up to RT_N_SEED_MAX profiles, installed as a seed set
     // (rt_hip_plan_set_seeds, a seeded plan: n_seed), as the seeds of a length scan (rt_hip_plan_set_scan_seeds, while the scan
     // is on: n_scan_seed, n_seed stays 0) or as ASE seeds (rt_hip_plan_set_ase_seeds, an EMISSION plan: n_seed with
-    // P.use_emis, the one case of use_emis with n_seed > 0; ase_scale[s] is the scale of seed s).  A set and a scan exclude
+    // P.use_emis, the one case of use_emis with n_seed > 0; ase_scale[s] is the scale of seed s) or as the ASE seeds of a
+    // scan (rt_hip_plan_set_scan_ase_seeds, an emission plan while the scan is on: n_scan_seed with P.use_emis).  A set and a scan exclude
     // each other, so their tables live in the same place: one device block (seedset_arena; seed_set[s] points into it, f[4]
     // padded to Kp) and, on a forward ray grid, per seed what seedtab_dev holds for the creation seed (seedset_tab).
     int n_seed      = 0;
