@@ -61,6 +61,43 @@ class Oracle:
 
         L.rt_oracle_calc_seed.argtypes = [P(cabi.RtSeed), C.c_size_t, cabi.c_double_p, cabi.c_double_p, cabi.c_double_p]
         L.rt_oracle_calc_seed.restype = C.c_int
+        L.rt_oracle_linear_step.argtypes = [C.c_size_t, cabi.c_float_p, C.c_float, cabi.c_float_p, P(C.c_uint8), P(C.c_uint8),
+                                            P(C.c_uint8), cabi.c_float_p]
+        L.rt_oracle_linear_step.restype = C.c_int
+        L.rt_oracle_cross_setup.argtypes = [C.c_size_t, cabi.c_float_p, cabi.c_double_p, cabi.c_double_p, P(C.c_uint8),
+                                            cabi.c_float_p]
+        L.rt_oracle_cross_setup.restype = C.c_int
+
+    def linear_step(self, state, c: float = 0.5):
+        """One integrator step per case: the loop body of step_linear_medium (Helper.h:281-311) and the loop condition
+        behind it.  state [n][14] float32 = n0, gx, gy, rx, ry, rz, sx, sy, sz, path, wx, wy, lim2, dzcap ->
+        dict(out [n][8] = n, rx, ry, rz, sx, sy, sz, path; run_geo, run_full [n] bool; winner [n] in 0 dzcap, 1 .. 4 h1 .. h4;
+        cand [n][4] = the quotients h1 .. h4)."""
+        state = np.ascontiguousarray(state, dtype=np.float32)
+        assert state.ndim == 2 and state.shape[1] == 14
+        n = state.shape[0]
+        out, cand = np.zeros((n, 8), np.float32), np.zeros((n, 4), np.float32)
+        geo, full, win = (np.zeros(n, np.uint8) for _ in range(3))
+        u8 = lambda a: a.ctypes.data_as(P(C.c_uint8))
+        rc = self.lib.rt_oracle_linear_step(n, cabi._fp(state), float(c), cabi._fp(out), u8(geo), u8(full), u8(win), cabi._fp(cand))
+        if rc != 0:
+            raise RuntimeError(f"rt_oracle_linear_step failed: {rc}")
+        return dict(out=out, run_geo=geo.astype(bool), run_full=full.astype(bool), winner=win, cand=cand)
+
+    def cross_setup(self, pos, cell, nc, mirror):
+        """The cross-cell set-up per case: the loop head of cross_cell (Helper.h:328-336).  pos [n][2] float32 = x, y;
+        cell [n][4] = xc0, xc1, yc0, yc1; nc [n][4] = the corner indices n00, n10, n01, n11; mirror [n] -> [n][3] = n0, gx, gy."""
+        pos = np.ascontiguousarray(pos, dtype=np.float32)
+        cell, nc = np.ascontiguousarray(cell, dtype=np.float64), np.ascontiguousarray(nc, dtype=np.float64)
+        mirror = np.ascontiguousarray(mirror, dtype=np.uint8)
+        n = pos.shape[0]
+        assert pos.shape == (n, 2) and cell.shape == (n, 4) and nc.shape == (n, 4) and mirror.shape == (n,)
+        out = np.zeros((n, 3), np.float32)
+        rc = self.lib.rt_oracle_cross_setup(n, cabi._fp(pos), cabi._dp(cell), cabi._dp(nc), mirror.ctypes.data_as(P(C.c_uint8)),
+                                            cabi._fp(out))
+        if rc != 0:
+            raise RuntimeError(f"rt_oracle_cross_setup failed: {rc}")
+        return out
 
     def calc_seed(self, seed, pts):
         """seed_intensity at the points pts [n][4] = (x, y, a, b) -> dict(Iv [n][dim[4]], axis [n][4]: pchip_eval of each

@@ -168,6 +168,54 @@ int rt_oracle_calc_seed(const rt_seed *seed, size_t n, const double *pts, double
     return 0;
 }
 
+/* One pass of the loop of Helper.h:279-311: the body of step_linear_medium's `while`, the single definition of the
+ * integrator step (step_linear_medium below and the batch entry rt_oracle_linear_step both call it).  Advances *r, *s,
+ * stores the index the step saw in *n and returns the step size h.  winner (or NULL): which candidate set h by the
+ * reference's `<` chain, 0 dzcap, 1 .. 4 h1 .. h4 (a tie goes to the earlier one of h1, dzcap, h2, h3, h4); cand (or
+ * NULL): the four quotients h1 .. h4 as the chain saw them. */
+static inline float linear_step(vec3f *r, vec3f *s, float *n_out, float n0, float gx, float gy, float lim2,
+                                float c, float dzcap, int *winner, float *cand)
+{
+    float n  = n0 + r->x * gx + r->y * gy;
+    float t  = (s->x * gx + s->y * gy + 1e-12f) / n;
+    float fx = gx / n - s->x * t;
+    float fy = gy / n - s->y * t;
+    float fz = -s->z * t;
+    float h  = c * 0.1f / fabsf(t);
+    float h1 = h;
+    int w    = h < dzcap ? 1 : 0;
+    h        = h < dzcap ? h : dzcap;
+    float h2 = 1.0001f * (lim2 - fabsf(r->z)) / fabsf(s->z);
+    float h3 = c * 0.05f * (fabsf(s->x) + 5e-4f) / (fabsf(fx) + 1e-8f);
+    float h4 = c * 0.05f * (fabsf(s->y) + 5e-4f) / (fabsf(fy) + 1e-8f);
+    w        = h < h2 ? w : 2;
+    h        = h < h2 ? h : h2;
+    w        = h < h3 ? w : 3;
+    h        = h < h3 ? h : h3;
+    w        = h < h4 ? w : 4;
+    h        = h < h4 ? h : h4;
+    float ht = h * t;
+    float c1 = 0.5f * h * h * (1.0f - ht / 3.0f + ht * ht / 12.0f);
+    r->x += s->x * h + c1 * fx;
+    r->y += s->y * h + c1 * fy;
+    r->z += s->z * h + c1 * fz;
+    float c2 = h * (1.0f - 0.5f * ht + ht * ht / 6.0f);
+    s->x += c2 * fx;
+    s->y += c2 * fy;
+    s->z += c2 * fz;
+    renormalise(s);
+    *n_out = n;
+    if (winner)
+        *winner = w;
+    if (cand) {
+        cand[0] = h1;
+        cand[1] = h2;
+        cand[2] = h3;
+        cand[3] = h4;
+    }
+    return h;
+}
+
 /* Helper.h:270-313 -- adaptive 2nd-order Taylor steps in a linear-index
  * medium n = n0 + gx*x + gy*y; returns the path length, displacement in *r. */
 static float step_linear_medium(vec3f *r, vec3f *s, float n0, float gx, float gy,
@@ -181,34 +229,30 @@ static float step_linear_medium(vec3f *r, vec3f *s, float n0, float gx, float gy
     float n = n0;
     while (fabsf(r->x) < lim[0] && fabsf(r->y) < lim[1] && fabsf(r->z) < lim[2] &&
            (double) fabsf(n - n0) < 0.05) {
-        n        = n0 + r->x * gx + r->y * gy;
-        float t  = (s->x * gx + s->y * gy + 1e-12f) / n;
-        float fx = gx / n - s->x * t;
-        float fy = gy / n - s->y * t;
-        float fz = -s->z * t;
-        float h  = c * 0.1f / fabsf(t);
-        h        = h < dzcap ? h : dzcap;
-        float h2 = 1.0001f * (lim[2] - fabsf(r->z)) / fabsf(s->z);
-        float h3 = c * 0.05f * (fabsf(s->x) + 5e-4f) / (fabsf(fx) + 1e-8f);
-        float h4 = c * 0.05f * (fabsf(s->y) + 5e-4f) / (fabsf(fy) + 1e-8f);
-        h        = h < h2 ? h : h2;
-        h        = h < h3 ? h : h3;
-        h        = h < h4 ? h : h4;
-        float ht = h * t;
-        float c1 = 0.5f * h * h * (1.0f - ht / 3.0f + ht * ht / 12.0f);
-        r->x += s->x * h + c1 * fx;
-        r->y += s->y * h + c1 * fy;
-        r->z += s->z * h + c1 * fz;
-        float c2 = h * (1.0f - 0.5f * ht + ht * ht / 6.0f);
-        s->x += c2 * fx;
-        s->y += c2 * fy;
-        s->z += c2 * fz;
-        renormalise(s);
-        path += h;
+        path += linear_step(r, s, &n, n0, gx, gy, lim[2], c, dzcap, NULL, NULL);
         if (iters)
             ++*iters;
     }
     return path;
+}
+
+/* Helper.h:328-336 -- the head of cross_cell's loop: the index at the ray's place in the cell and its gradient from the
+ * four corners (the single definition: cross_cell below and the batch entry rt_oracle_cross_setup both call it). */
+static inline void cross_setup(float px, float py, float ya, const double xc[2], const double yc[2], float wx, float wy,
+                               const double nc[4], int mirror_y, float *n0_out, float *gx_out, float *gy_out)
+{
+    float u  = (float) (((double) px - xc[0]) / (double) wx);
+    float v  = (float) (((double) ya - yc[0]) / (double) wy);
+    float n0 = lerp2(u, v, (float) nc[0], (float) nc[1], (float) nc[2], (float) nc[3]);
+    float gx = (float) ((1.0 - (double) v) * (nc[1] - nc[0]) / (double) wx +
+                        (double) v * (nc[3] - nc[2]) / (double) wx);
+    float gy = (float) ((1.0 - (double) u) * (nc[2] - nc[0]) / (double) wy +
+                        (double) u * (nc[3] - nc[1]) / (double) wy);
+    if (mirror_y && py < 0)
+        gy = -gy;
+    *n0_out = n0;
+    *gx_out = gx;
+    *gy_out = gy;
 }
 
 /* Helper.h:318-351 -- advance inside one cell box until the ray leaves it or
@@ -225,15 +269,8 @@ static float cross_cell(vec3f *pos, vec3f *s, float dzrem, const double xc[2], c
     while (pos->x > box[0] && pos->x < box[1] && ya > box[2] && ya < box[3] &&
            (double) z < 0.999 * (double) dzrem) {
         ya       = mirror_y ? fabsf(pos->y) : pos->y;
-        float u  = (float) (((double) pos->x - xc[0]) / (double) wx);
-        float v  = (float) (((double) ya - yc[0]) / (double) wy);
-        float n0 = lerp2(u, v, (float) nc[0], (float) nc[1], (float) nc[2], (float) nc[3]);
-        float gx = (float) ((1.0 - (double) v) * (nc[1] - nc[0]) / (double) wx +
-                            (double) v * (nc[3] - nc[2]) / (double) wx);
-        float gy = (float) ((1.0 - (double) u) * (nc[2] - nc[0]) / (double) wy +
-                            (double) u * (nc[3] - nc[1]) / (double) wy);
-        if (mirror_y && pos->y < 0)
-            gy = -gy;
+        float n0, gx, gy;
+        cross_setup(pos->x, pos->y, ya, xc, yc, wx, wy, nc, mirror_y, &n0, &gx, &gy);
         vec3f r;
         float lim[3] = { 0.1f * wx, 0.1f * wy, dzrem - z };
         path += step_linear_medium(&r, s, n0, gx, gy, lim, c, iters1);
@@ -246,6 +283,61 @@ static float cross_cell(vec3f *pos, vec3f *s, float dzrem, const double xc[2], c
             ++*iters2;
     }
     return path;
+}
+
+/* One integrator step per case (linear_step above), for the device-side unit tests of the march (tests/march_block_inputs.py
+ * says what a case is).  state_in [n][14] = n0, gx, gy, rx, ry, rz, sx, sy, sz, path, wx, wy, lim2, dzcap;
+ * state_out [n][8] = n, rx, ry, rz, sx, sy, sz, path after the step; run_geo: the three geometric tests of the loop
+ * condition (Helper.h:279) on the new r with lim = {0.1f wx, 0.1f wy, lim2}; run_full: those and (double)|n - n0| < 0.05,
+ * n the index the step saw; winner as linear_step gives it; cand [n][4] (or NULL) the quotients h1 .. h4. */
+int rt_oracle_linear_step(size_t n_cases, const float *state_in, float c, float *state_out, uint8_t *run_geo,
+                          uint8_t *run_full, uint8_t *winner, float *cand)
+{
+    if (!state_in || !state_out || !run_geo || !run_full || !winner)
+        return -1;
+    for (size_t i = 0; i < n_cases; i++) {
+        const float *in = state_in + 14 * i;
+        float *out      = state_out + 8 * i;
+        const float n0 = in[0], gx = in[1], gy = in[2];
+        vec3f r        = { in[3], in[4], in[5] };
+        vec3f s        = { in[6], in[7], in[8] };
+        const float lim[3] = { 0.1f * in[10], 0.1f * in[11], in[12] };
+        float n;
+        int w;
+        const float h = linear_step(&r, &s, &n, n0, gx, gy, lim[2], c, in[13], &w, cand ? cand + 4 * i : NULL);
+        out[0] = n;
+        out[1] = r.x;
+        out[2] = r.y;
+        out[3] = r.z;
+        out[4] = s.x;
+        out[5] = s.y;
+        out[6] = s.z;
+        out[7] = in[9] + h;
+        const int geo = fabsf(r.x) < lim[0] && fabsf(r.y) < lim[1] && fabsf(r.z) < lim[2];
+        run_geo[i]    = (uint8_t) geo;
+        run_full[i]   = (uint8_t) (geo && (double) fabsf(n - n0) < 0.05);
+        winner[i]     = (uint8_t) w;
+    }
+    return 0;
+}
+
+/* The cross-cell set-up per case (cross_setup above).  pos [n][2] = x, y of the ray; cell [n][4] = xc[0], xc[1], yc[0],
+ * yc[1]; nc [n][4] the corner indices n00, n10, n01, n11; mirror [n]; out [n][3] = n0, gx, gy. */
+int rt_oracle_cross_setup(size_t n_cases, const float *pos, const double *cell, const double *nc, const uint8_t *mirror,
+                          float *out)
+{
+    if (!pos || !cell || !nc || !mirror || !out)
+        return -1;
+    for (size_t i = 0; i < n_cases; i++) {
+        const double *xc = cell + 4 * i, *yc = cell + 4 * i + 2;
+        const float wx   = (float) (xc[1] - xc[0]);
+        const float wy   = (float) (yc[1] - yc[0]);
+        const float px = pos[2 * i], py = pos[2 * i + 1];
+        const int mirror_y = mirror[i] != 0;
+        const float ya     = mirror_y ? fabsf(py) : py;
+        cross_setup(px, py, ya, xc, yc, wx, wy, nc + 4 * i, mirror_y, out + 3 * i, out + 3 * i + 1, out + 3 * i + 2);
+    }
+    return 0;
 }
 
 /*

@@ -47,6 +47,13 @@ int rt_oracle_calc_ray_path(int N, const rt_beam *beam, const rt_gain *gain, con
                             int method, float c, const rt_ray *rays, size_t n_rays, float *path,
                             int32_t *err);
 
+/* one integrator step / one cross-cell set-up per case: the loop body of step_linear_medium and the loop head of
+ * cross_cell, the same definitions the march calls (rt_oracle.c says what the arrays hold) */
+int rt_oracle_linear_step(size_t n_cases, const float *state_in, float c, float *state_out, uint8_t *run_geo,
+                          uint8_t *run_full, uint8_t *winner, float *cand);
+int rt_oracle_cross_setup(size_t n_cases, const float *pos, const double *cell, const double *nc, const uint8_t *mirror,
+                          float *out);
+
 int rt_oracle_calc_seed(const rt_seed *seed, size_t n, const double *pts, double *Iv, double *axis);
 
 #ifdef __cplusplus

@@ -2,7 +2,9 @@
 // kernels of the march (rt_march.hip) and the seed-profile interpolation (pchip_eval / seed_factor of rt_math.h, and
 // rt_seed_tab_kernel itself), each behind one elementwise kernel, and the two wave primitives of the step deposit (the E_v
 // wave sum rt_step_evsum.inc, the segmented scan rt_wave_runs.inc / rt_wave_runscan.inc), each behind a kernel of one
-// work-group, so that tests/test_gpu_devmath.py and
+// work-group, and the float32 blocks of the march -- one integrator step (rt_march_step.inc, in the four instances the product
+// launches), the cross-cell set-up (rt_march_xsetup.inc) and the float primitives of rt_math.h -- one case per lane in whole
+// waves, so that tests/test_gpu_devmath.py, tests/test_gpu_march_blocks.py and
 // tests/test_gpu_seed_profiles.py can run them on a device on inputs of their own choosing.  Builds to librt_hip_devmath.so with the product's flags; nothing
 // of it is linked into librt_hip.so.
 //
@@ -218,6 +220,143 @@ __global__ void __launch_bounds__(DM_BLOCK) dm_nf_scan_kernel(const int *pix_in,
 #include "rt_wave_runscan.inc"
     if (tail && a != 0.0)
         unsafeAtomicAdd(&nf[pix], a);
+}
+
+// ---- the float32 blocks of the march: one case per lane.  The fragments and inv_norm take wave-level decisions
+// (__ballot), so these kernels run whole waves only: the index space is padded to a multiple of WAVE, a padding lane
+// repeats the last case and stores nothing (no lane leaves early; the grid-stride loop ends for a whole wave at once: its
+// stride is a multiple of DM_BLOCK) -------------------------------------------------------------------------------------
+// rt_freq.hip, included above, ends with FMA contraction allowed (its float64 half); rt_launch.hip includes rt_march.hip in
+// front of it.  The fragments below are float32 march code and must be compiled as march_wave compiles them:
+#pragma clang fp contract(off)
+enum : int { DM_STEP_IN = 14, DM_STEP_OUT = 8, DM_STEP_COUNTERS = 6 };
+enum : int {
+    DM_F32_INV_NORM = 0,
+    DM_F32_DIV_BY_RECIP = 1,
+    DM_F32_DIV_BY_RECIP_SIGNED = 2,
+    DM_F32_FDIV_NR = 3,
+    DM_F32_FDIV_ONE_NR = 4,
+    DM_F32_FMIN_NAN_DROP = 5
+};
+enum : int { DM_F64_DIV_BY_RECIP = 0, DM_F64_DIV_BY_RECIP_TINY_OK = 1 };
+
+__device__ __forceinline__ size_t dm_padded(size_t n) { return (n + WAVE - 1) / WAVE * WAVE; }
+
+// the step factors as rt_hip_plan_set_step_factor derives them: what block [C] reads of DevParams
+struct DmStepFactors {
+    float c_cap, c_h1, c_h3;
+};
+
+// the stand-in for MarchDiag: which wave-uniform branches of block [C] this wave took in any of its passes
+// (counters[k] += 1 per wave and launch: k = 0 .. 3 prune(k), 4 the tiny-dividend block, 5 every wave that held cases)
+struct DmMarchDiag {
+    unsigned took = 0;
+    __device__ __forceinline__ void tick(int) {}
+    __device__ __forceinline__ void tiny_dividend() { took |= 1u << 4; }
+    __device__ __forceinline__ void prune(int i) { took |= 1u << i; }
+    __device__ __forceinline__ void pass() { took |= 1u << 5; }
+    __device__ __forceinline__ void wave_end(unsigned *counters)
+    {
+        if (lane_id() == 0)
+            for (int k = 0; k < DM_STEP_COUNTERS; k++)
+                if (took >> k & 1u)
+                    atomicAdd(&counters[k], 1u);
+    }
+};
+
+// rt_march_step.inc as march_wave includes it.  in [n][14] = n0, gxn, gyn, rx, ry, rz, sx, sy, sz, hsum, w_x, w_y, lim2,
+// dzcap; out [n][8] = n, rx, ry, rz, sx, sy, sz, hsum; run [n]
+template <bool BOUNDED, int OPT>
+__global__ void __launch_bounds__(DM_BLOCK) dm_march_step_kernel(const DmStepFactors P, const float *in, float *out, unsigned char *run_out,
+                                                                unsigned *counters, size_t n_cases)
+{
+    const size_t stride = (size_t) gridDim.x * blockDim.x;
+    const size_t padded = dm_padded(n_cases);
+    DmMarchDiag diag;
+    for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < padded; i += stride) {
+        const float *c = in + DM_STEP_IN * (i < n_cases ? i : n_cases - 1);
+        diag.pass();
+        const float n0 = c[0], gxn = c[1], gyn = c[2];
+        float rx = c[3], ry = c[4], rz = c[5], sx = c[6], sy = c[7], sz = c[8], hsum = c[9], n = 0.0f;
+        const float lim0 = 0.1f * c[10], lim1 = 0.1f * c[11]; // as block [C] has them from the interval records
+        const float lim2 = c[12], dzcap = c[13];
+        bool run;
+        {
+#include "rt_march_step.inc"
+        }
+        if (i < n_cases) {
+            float *o = out + DM_STEP_OUT * i;
+            o[0]     = n;
+            o[1]     = rx;
+            o[2]     = ry;
+            o[3]     = rz;
+            o[4]     = sx;
+            o[5]     = sy;
+            o[6]     = sz;
+            o[7]     = hsum;
+            run_out[i] = run ? 1 : 0;
+        }
+    }
+    diag.wave_end(counters);
+}
+
+// rt_march_xsetup.inc as march_wave includes it.  fin [n][4] = px, py, w_x, w_y; din [n][8] = lo_x, rw_x, lo_y, rw_y and the
+// corner indices n00, n10, n01, n11 (rounded and differenced here as block [A2] does it); mirror [n]; out [n][3] = n0, gxn, gyn
+__global__ void __launch_bounds__(DM_BLOCK) dm_march_xsetup_kernel(const float *fin, const double *din, const unsigned char *mirror_in,
+                                                                  float *out, size_t n_cases)
+{
+    const size_t stride = (size_t) gridDim.x * blockDim.x;
+    const size_t padded = dm_padded(n_cases);
+    for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < padded; i += stride) {
+        const size_t c  = i < n_cases ? i : n_cases - 1;
+        const float px = fin[4 * c], py = fin[4 * c + 1];
+        const bool mirror = mirror_in[c] != 0;
+        const double *d   = din + 8 * c;
+        const f64x2 ix0 = { d[0], d[1] }, iy0 = { d[2], d[3] };
+        const f32x4 ix1 = { fin[4 * c + 2], 0.0f, 0.0f, 0.0f }, iy1 = { fin[4 * c + 3], 0.0f, 0.0f, 0.0f };
+        const double n00 = d[4], n10 = d[5], n01 = d[6], n11 = d[7];
+        const float f00 = (float) n00, f10 = (float) n10, f01 = (float) n01, f11 = (float) n11;
+        const double dnx0 = n10 - n00, dnx1 = n11 - n01, dny0 = n01 - n00, dny1 = n11 - n10;
+        float n0, gxn, gyn;
+        {
+#include "rt_march_xsetup.inc"
+        }
+        if (i < n_cases) {
+            out[3 * i]     = n0;
+            out[3 * i + 1] = gxn;
+            out[3 * i + 2] = gyn;
+        }
+    }
+}
+
+// the float primitives of rt_math.h, elementwise: out = f(a, b, y) (an argument a primitive does not take is not read)
+__global__ void __launch_bounds__(DM_BLOCK) dm_f32_kernel(int which, const float *a, const float *b, const float *y, float *out,
+                                                         size_t n_cases)
+{
+    const size_t stride = (size_t) gridDim.x * blockDim.x;
+    const size_t padded = dm_padded(n_cases);
+    for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < padded; i += stride) {
+        const size_t c = i < n_cases ? i : n_cases - 1;
+        float r;
+        switch (which) {
+        case DM_F32_INV_NORM: r = inv_norm(a[c]); break;
+        case DM_F32_DIV_BY_RECIP: r = div_by_recip<false>(a[c], b[c], y[c]); break;
+        case DM_F32_DIV_BY_RECIP_SIGNED: r = div_by_recip_signed(a[c], b[c], y[c]); break;
+        case DM_F32_FDIV_NR: r = fdiv_nr(a[c], b[c]); break;
+        case DM_F32_FDIV_ONE_NR: r = fdiv_one_nr(b[c]); break;
+        default: r = fmin_nan_drop(a[c], b[c]); break;
+        }
+        if (i < n_cases)
+            out[i] = r;
+    }
+}
+
+__global__ void __launch_bounds__(DM_BLOCK) dm_f64_div_kernel(int which, const double *a, const double *b, const double *y, double *out,
+                                                             size_t n_cases)
+{
+    const size_t stride = (size_t) gridDim.x * blockDim.x;
+    for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < n_cases; i += stride)
+        out[i] = which == DM_F64_DIV_BY_RECIP ? div_by_recip<false>(a[i], b[i], y[i]) : div_by_recip<true>(a[i], b[i], y[i]);
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------
@@ -537,4 +676,90 @@ DM_API int rt_devmath_seed_tab(const int *dim, const double *const *xs, const do
         return B.release(rc);
     DM_TRY(hipMemcpy(sin, dsin, nn, hipMemcpyDeviceToHost));
     return B.release(0);
+}
+
+// One integrator step of the march per case (rt_march_step.inc), in the instance (bounded, opt) -- one of the four the
+// product launches: (0, 0), (1, 0), (1, PRUNE | NO_NTEST), (1, PRUNE | NO_NTEST | PRUNE_H24); anything else is refused.
+// c: the step factor (rt_hip_plan_set_step_factor).  in [n][14], out [n][8], run [n] as dm_march_step_kernel says;
+// counters [6]: waves of this launch that took prune(0 .. 3), the tiny-dividend block, and all waves
+DM_API int rt_devmath_march_step(int bounded, int opt, float c, const float *in, float *out, unsigned char *run, unsigned *counters,
+                                 size_t n)
+{
+    Bufs B;
+    float *din, *dout;
+    unsigned char *drun;
+    unsigned *dcnt;
+    constexpr int PN = MARCH_OPT_PRUNE | MARCH_OPT_NO_NTEST, PN24 = PN | MARCH_OPT_PRUNE_H24;
+    if (!((opt == 0) || (bounded && (opt == PN || opt == PN24))) || n < 1)
+        return (int) hipErrorInvalidValue;
+    const DmStepFactors P = { c * 1.00001f, c * 0.1f, c * 0.05f };
+    DM_TRY(B.in((void **) &din, in, n * DM_STEP_IN * sizeof(float)));
+    DM_TRY(B.out((void **) &dout, n * DM_STEP_OUT * sizeof(float)));
+    DM_TRY(B.out((void **) &drun, n));
+    DM_TRY(B.out((void **) &dcnt, DM_STEP_COUNTERS * sizeof(unsigned)));
+    DM_TRY(hipMemset(dcnt, 0, DM_STEP_COUNTERS * sizeof(unsigned)));
+    const unsigned grid = grid_for(n);
+    if (!bounded)
+        dm_march_step_kernel<false, 0><<<grid, DM_BLOCK>>>(P, din, dout, drun, dcnt, n);
+    else if (opt == 0)
+        dm_march_step_kernel<true, 0><<<grid, DM_BLOCK>>>(P, din, dout, drun, dcnt, n);
+    else if (opt == PN)
+        dm_march_step_kernel<true, PN><<<grid, DM_BLOCK>>>(P, din, dout, drun, dcnt, n);
+    else
+        dm_march_step_kernel<true, PN24><<<grid, DM_BLOCK>>>(P, din, dout, drun, dcnt, n);
+    const int rc = finish(out, dout, n * DM_STEP_OUT * sizeof(float));
+    if (rc)
+        return B.release(rc);
+    DM_TRY(hipMemcpy(run, drun, n, hipMemcpyDeviceToHost));
+    DM_TRY(hipMemcpy(counters, dcnt, DM_STEP_COUNTERS * sizeof(unsigned), hipMemcpyDeviceToHost));
+    return B.release(0);
+}
+
+// The cross-cell set-up of the march per case (rt_march_xsetup.inc): fin [n][4], din [n][8], mirror [n], out [n][3] as
+// dm_march_xsetup_kernel says
+DM_API int rt_devmath_march_xsetup(const float *fin, const double *din, const unsigned char *mirror, float *out, size_t n)
+{
+    Bufs B;
+    float *dfin, *dout;
+    double *ddin;
+    unsigned char *dmir;
+    if (n < 1)
+        return (int) hipErrorInvalidValue;
+    DM_TRY(B.in((void **) &dfin, fin, n * 4 * sizeof(float)));
+    DM_TRY(B.in((void **) &ddin, din, n * 8 * sizeof(double)));
+    DM_TRY(B.in((void **) &dmir, mirror, n));
+    DM_TRY(B.out((void **) &dout, n * 3 * sizeof(float)));
+    dm_march_xsetup_kernel<<<grid_for(n), DM_BLOCK>>>(dfin, ddin, dmir, dout, n);
+    return B.release(finish(out, dout, n * 3 * sizeof(float)));
+}
+
+// a float primitive of rt_math.h elementwise: which = 0 inv_norm(a), 1 div_by_recip(a, b, y), 2 div_by_recip_signed(a, b, y),
+// 3 fdiv_nr(a, b), 4 fdiv_one_nr(b), 5 fmin_nan_drop(a, b); all three arrays hold n values whichever the primitive reads
+DM_API int rt_devmath_f32(int which, const float *a, const float *b, const float *y, float *out, size_t n)
+{
+    Bufs B;
+    float *da, *db, *dy, *dout;
+    if (which < DM_F32_INV_NORM || which > DM_F32_FMIN_NAN_DROP || n < 1)
+        return (int) hipErrorInvalidValue;
+    DM_TRY(B.in((void **) &da, a, n * sizeof(float)));
+    DM_TRY(B.in((void **) &db, b, n * sizeof(float)));
+    DM_TRY(B.in((void **) &dy, y, n * sizeof(float)));
+    DM_TRY(B.out((void **) &dout, n * sizeof(float)));
+    dm_f32_kernel<<<grid_for(n), DM_BLOCK>>>(which, da, db, dy, dout, n);
+    return B.release(finish(out, dout, n * sizeof(float)));
+}
+
+// the double div_by_recip(a, b, y) elementwise: which = 0 the guarded form, 1 TINY_OK
+DM_API int rt_devmath_f64_div(int which, const double *a, const double *b, const double *y, double *out, size_t n)
+{
+    Bufs B;
+    double *da, *db, *dy, *dout;
+    if (which != DM_F64_DIV_BY_RECIP && which != DM_F64_DIV_BY_RECIP_TINY_OK)
+        return (int) hipErrorInvalidValue;
+    DM_TRY(B.in((void **) &da, a, n * sizeof(double)));
+    DM_TRY(B.in((void **) &db, b, n * sizeof(double)));
+    DM_TRY(B.in((void **) &dy, y, n * sizeof(double)));
+    DM_TRY(B.out((void **) &dout, n * sizeof(double)));
+    dm_f64_div_kernel<<<grid_for(n), DM_BLOCK>>>(which, da, db, dy, dout, n);
+    return B.release(finish(out, dout, n * sizeof(double)));
 }

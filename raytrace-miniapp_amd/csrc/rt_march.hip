@@ -1328,18 +1328,7 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
         diag.mark(2); // [A2] (a lane that finished in [A1] stays ST_DONE: retired at the loop head, "ray finished")
         // ------------------------------------------------------------ [B] cross-cell setup (Helper.h:328-342)
         if (st == ST_XSETUP) {
-            const float ya   = mirror ? fabsf(py) : py;
-            const double dwx = (double) ix1.x, dwy = (double) iy1.x; // Helper.h:323-324
-            const double xc0 = ix0.x, yc0 = iy0.x, rwx = ix0.y, rwy = iy0.y;
-            const float u    = (float) div_by_recip<true>((double) px - xc0, dwx, rwx);
-            const float v    = (float) div_by_recip<true>((double) ya - yc0, dwy, rwy);
-            n0  = lerp2(u, v, f00, f10, f01, f11);
-            gxn = (float) (div_by_recip<true>((1.0 - (double) v) * dnx0, dwx, rwx) +
-                           div_by_recip<true>((double) v * dnx1, dwx, rwx));
-            gyn = (float) (div_by_recip<true>((1.0 - (double) u) * dny0, dwy, rwy) +
-                           div_by_recip<true>((double) u * dny1, dwy, rwy));
-            if (mirror && py < 0)
-                gyn = -gyn;
+#include "rt_march_xsetup.inc"
             lim2  = dzrem - zc;
             dzcap = P.c_cap * lim2; // Helper.h:274: c * 1.00001f * dx[2]
             rx    = 0.0f;
@@ -1359,123 +1348,12 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
             // has r = 0, n = n0 and limits that are positive (cell widths are, rt_hip_plan_create checks it;
             // lim2 = dzrem - zc > 0 is the entry condition of [B]); a lane that stays in this state was
             // tested at the end of its last step, below.  So the step runs unconditionally and the
-            // condition is evaluated once, after it.
+            // condition is evaluated once, after it.  (For a finite n0, that is: with an infinite or NaN n0
+            // the reference's test |n - n0| < 0.05 fails on entry and its loop never runs nor advances;
+            // rt_hip_plan_create refuses a non-finite index for that reason.)
             bool run;
             {
-                n        = n0 + rx * gxn + ry * gyn;
-#ifdef RT_ABL_FASTDIV
-#define RT_FDIV(a, b) ((a) * __builtin_amdgcn_rcpf(b))
-#else
-#define RT_FDIV(a, b) ((a) / (b))
-#endif
-                // one IEEE division, three exact quotients
-                const float rn = BOUNDED ? fdiv_one_nr(n) : RT_FDIV(1.0f, n);
-                float a0 = sx * gxn + sy * gyn + 1e-12f;
-                // (BOUNDED: a0 is never -0 -- x + 1e-12f is +0 or non-zero -- and rn > 0, so the corrected
-                // quotient has the sign of a0 without the sign copy)
-                float t  = BOUNDED ? fmaf(fmaf(-n, a0 * rn, a0), rn, a0 * rn) : div_by_recip_signed(a0, n, rn);
-                float qx = div_by_recip_signed(gxn, n, rn);
-                float qy = div_by_recip_signed(gyn, n, rn);
-#ifndef RT_ABL_NOGUARD
-                // div_by_recip needs a true division for non-zero dividends below 1e-29 (rt_math.h).  One
-                // wave-uniform test covers the three quotients: the smallest magnitude of the dividends is
-                // below the bound only where a lane holds an exact zero (index gradient of a uniform
-                // region; the quotient 0 is right as it is) or, once in a blue moon, such a dividend.
-                if (__ballot(fminf(fminf(fabsf(a0), fabsf(gxn)), fabsf(gyn)) < 1e-29f) != 0ull) {
-                    diag.tiny_dividend();
-                    if (fabsf(a0) < 1e-29f && a0 != 0.0f) {
-                        asm volatile("" : "+v"(a0));
-                        t = a0 / n;
-                    }
-                    if (fabsf(gxn) < 1e-29f && gxn != 0.0f) {
-                        float g = gxn;
-                        asm volatile("" : "+v"(g));
-                        qx = g / n;
-                    }
-                    if (fabsf(gyn) < 1e-29f && gyn != 0.0f) {
-                        float g = gyn;
-                        asm volatile("" : "+v"(g));
-                        qy = g / n;
-                    }
-                }
-#endif
-                float fx = qx - sx * t;
-                float fy = qy - sy * t;
-                float fz = -sz * t;
-                float h;
-                if (BOUNDED && (OPT & MARCH_OPT_PRUNE)) {
-                    // The same candidates, but a division is executed only where its quotient can matter.  Four of the
-                    // five candidates are quotients num / den with num >= 0, den >= 0, and the step is their minimum
-                    // with dzcap: a candidate whose exact quotient exceeds dzcap rounds to a float >= dzcap (or, where the
-                    // short sequence is out of its range, to something huge, infinite or NaN that the minimum passes
-                    // over, see below), so leaving it out of the minimum returns the same float.  Sufficient, without a
-                    // division: p = RN(RN(K dzcap) den) < num with K = 1.00002f.  The two products lose at most 2^-24
-                    // each, so p >= K (1 - 2^-24)^2 dzcap den > dzcap den (K - 1 = 168 x 2^-23 against the 2^-23 needed)
-                    // and num > p gives num / den > dzcap.  A product that lands in the subnormal range (absolute
-                    // error 2^-150) could only mislead a numerator below 2^-125: those of h1 and h4 are at least
-                    // 5e-12 (c_h3 >= 1e-8), and for h2 it takes |sz| dzcap < 2^-125 while num >= 2^-24 lim2, i.e.
-                    // num / |sz| > 2^101 lim2 dzcap > dzcap (lim2 >= 5e-6 dz / 3 >= 1e-18 under the BOUNDED ranges).
-                    // A comparison with a NaN or against den = inf is false: that candidate is divided as before.
-                    // K is small enough to keep pruning h2 right after a dzcap step, where h2 / dzcap is about
-                    // 1.0001 / (1.00001 |sz|) >= 1.00008.  The decision is taken for the wave (one scalar branch per
-                    // candidate or pair of candidates): on the 6.4 M-ray stand-in dzcap sets 63 % of the steps, h3 35 %, h4 0.8 %, h2 0.6 %, h1
-                    // none, so h3 is always divided.
-                    const float kd = 1.00002f * dzcap;
-                    const float at = fabsf(t), az = fabsf(sz);
-                    const float n2 = 1.0001f * (lim2 - fabsf(rz));
-                    const float n4 = P.c_h3 * (fabsf(sy) + 5e-4f), d4 = fabsf(fy) + 1e-8f;
-                    h = fmin_nan_drop(fdiv_nr(P.c_h3 * (fabsf(sx) + 5e-4f), (fabsf(fx) + 1e-8f)), dzcap);
-                    diag.prune(3);
-                    if (__ballot(!(P.c_h1 > kd * at)) != 0ull) {
-                        h = fmin_nan_drop(fdiv_nr(P.c_h1, at), h);
-                        diag.prune(0);
-                    }
-                    // h2 and h4 behind ONE branch, their two divisions interleaved when it is taken: a branch each ran the
-                    // stand-in 1.6 % faster than none but 2 - 3 % slower on launches of a few rays per lane, whose waves
-                    // wait on their own dependency chain and not on the issue slots (profiles/step_prune_ab.txt); merged
-                    // it is 2.0 % on the stand-in, and the small launches go without it (rt_launch.hip)
-                    if (!(OPT & MARCH_OPT_PRUNE_H24) || __ballot(!(n2 > kd * az) | !(n4 > kd * d4)) != 0ull) {
-                        h = fmin_nan_drop(fmin_nan_drop(fdiv_nr(n2, az), fdiv_nr(n4, d4)), h);
-                        diag.prune(1);
-                    }
-                } else if (BOUNDED) {
-                    // The step candidates (Helper.h:288-297) without the range bookkeeping of an IEEE division
-                    // (fdiv_nr, rt_math.h): exact wherever a candidate can be the minimum; a candidate that the
-                    // short sequence gets wrong is huge, infinite or NaN on both paths (its true value is above
-                    // dzcap), and the NaN-dropping minimum below passes over it as the `<` chain passes over +inf.
-                    const float h1 = fdiv_nr(P.c_h1, fabsf(t)); // c * 0.1f / |t|
-                    const float h2 = fdiv_nr(1.0001f * (lim2 - fabsf(rz)), fabsf(sz));
-                    const float h3 = fdiv_nr(P.c_h3 * (fabsf(sx) + 5e-4f), (fabsf(fx) + 1e-8f)); // c * 0.05f * ...
-                    const float h4 = fdiv_nr(P.c_h3 * (fabsf(sy) + 5e-4f), (fabsf(fy) + 1e-8f));
-                    h = fmin_nan_drop(fmin_nan_drop(h1, dzcap), fmin_nan_drop(h2, fmin_nan_drop(h3, h4)));
-                } else {
-                    h        = RT_FDIV(P.c_h1, fabsf(t)); // c * 0.1f / |t|
-                    h        = h < dzcap ? h : dzcap;
-                    float h2 = RT_FDIV(1.0001f * (lim2 - fabsf(rz)), fabsf(sz));
-                    float h3 = RT_FDIV(P.c_h3 * (fabsf(sx) + 5e-4f), (fabsf(fx) + 1e-8f)); // c * 0.05f * ...
-                    float h4 = RT_FDIV(P.c_h3 * (fabsf(sy) + 5e-4f), (fabsf(fy) + 1e-8f));
-                    h        = h < h2 ? h : h2;
-                    h        = h < h3 ? h : h3;
-                    h        = h < h4 ? h : h4;
-                }
-                float ht = h * t;
-                const float R3 = 1.0f / 3.0f, R6 = 1.0f / 6.0f, R12 = 1.0f / 12.0f; // RN(1/b), folded
-                float c1 = 0.5f * h * h * (1.0f - div_by_recip<true>(ht, 3.0f, R3) + div_by_recip<true>(ht * ht, 12.0f, R12));
-                rx += sx * h + c1 * fx;
-                ry += sy * h + c1 * fy;
-                rz += sz * h + c1 * fz;
-                float c2 = h * (1.0f - 0.5f * ht + div_by_recip<true>(ht * ht, 6.0f, R6));
-                sx += c2 * fx;
-                sy += c2 * fy;
-                sz += c2 * fz;
-                renormalise(sx, sy, sz);
-                hsum += h;
-                diag.tick(0);
-                // (double)|n - n0| < 0.05 (Helper.h:280) <=> |n - n0| < 0.05f: 0.05f is the smallest float above 0.05
-                // (MARCH_OPT_NO_NTEST: the last test is known to hold, rt_plan.hip "the largest index change a step can see")
-                run = (fabsf(rx) < lim0) & (fabsf(ry) < lim1) & (fabsf(rz) < lim2);
-                if (!(BOUNDED && (OPT & MARCH_OPT_NO_NTEST)))
-                    run = run & (fabsf(n - n0) < 0.05f);
+#include "rt_march_step.inc"
             }
             if (!run) {
                 // integrator loop over: close this cross-cell iteration (Helper.h:343-348)

@@ -93,7 +93,10 @@ __device__ __forceinline__ void renormalise(float &sx, float &sy, float &sz)
 //   * double, TINY_OK: the quotient (or its sum with another such quotient) is narrowed
 //     to float: with divisors above 1e-200 (plan_create checks the grid spacings) a
 //     quotient of a dividend below 1e-280 lies below 1e-80 and narrows to a zero of
-//     the right sign either way.
+//     the right sign either way.  (A SUM of two such quotients that nearly cancel is a
+//     zero of either sign, -0 where the correctly rounded quotients give +0 or the
+//     reverse: tests/test_gpu_march_blocks.py, setup/tiny_cancelling.  It takes corner
+//     indices of refraction below 1e-235 in magnitude.)
 template <bool TINY_OK = false> __device__ __forceinline__ float div_by_recip(float a, float b, float y)
 {
     const float q = a * y;

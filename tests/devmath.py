@@ -4,7 +4,8 @@
            ase_step, ase_step_f32 and ase_update (tables handed in), and loops over the host libm's tanf / atanf
   Device   ctypes binding of csrc/librt_hip_devmath.so (rt_devmath.hip): the same functions on a device, and the seed-profile
            interpolation (pchip, seed_factor, seed_tab: tests/test_gpu_seed_profiles.py) and the two wave primitives of the
-           step deposit (ev_sum, nf_scan).  Load it only
+           step deposit (ev_sum, nf_scan), and the float32 blocks of the march (march_step, march_xsetup, f32, f64_div:
+           tests/test_gpu_march_blocks.py).  Load it only
            after the `hip` fixture of conftest.py has brought torch in -- one HIP runtime per process
   the high-precision reference: numpy.longdouble (>= 64 significand bits, asserted) exp / expm1, guarded by a cross-check
            of a 2 000-point subsample against mpmath (or the stdlib decimal module at 40 digits)
@@ -139,6 +140,11 @@ class Device:
     STEP_F64, STEP_F32 = 0, 1
     DEPOSIT_FAST, DEPOSIT_4 = 0, 1
     TAN, ATAN = 0, 1
+    # the instances of the integrator step the product launches: (BOUNDED, OPT) of csrc/rt_march.hip
+    MARCH_OPT_PRUNE, MARCH_OPT_NO_NTEST, MARCH_OPT_PRUNE_H24 = 1, 2, 4
+    STEP_INSTANCES = {"ieee": (0, 0), "bounded": (1, 0), "prune": (1, 1 | 2), "prune_h24": (1, 1 | 2 | 4)}
+    INV_NORM, DIV_BY_RECIP, DIV_BY_RECIP_SIGNED, FDIV_NR, FDIV_ONE_NR, FMIN_NAN_DROP = range(6)
+    F64_DIV_BY_RECIP, F64_DIV_BY_RECIP_TINY_OK = 0, 1
     _inst = None
 
     @classmethod
@@ -169,9 +175,15 @@ class Device:
         L.rt_devmath_seed_tab.argtypes = [pi, ppd, ppd, ctypes.c_double, pi, ppd, ctypes.c_uint, _PD, ctypes.POINTER(ctypes.c_ubyte)]
         L.rt_devmath_ev_sum.argtypes = [_PD, ctypes.POINTER(ctypes.c_ubyte), ctypes.c_double, ci, _PD]
         L.rt_devmath_nf_scan.argtypes = [pi, _PD, ctypes.c_double, ci, _PD]
+        pu8 = ctypes.POINTER(ctypes.c_ubyte)
+        L.rt_devmath_march_step.argtypes = [ci, ci, ctypes.c_float, _PF, _PF, pu8, ctypes.POINTER(ctypes.c_uint), sz]
+        L.rt_devmath_march_xsetup.argtypes = [_PF, _PD, pu8, _PF, sz]
+        L.rt_devmath_f32.argtypes = [ci, _PF, _PF, _PF, _PF, sz]
+        L.rt_devmath_f64_div.argtypes = [ci, _PD, _PD, _PD, _PD, sz]
         for f in (L.rt_devmath_tables, L.rt_devmath_exp, L.rt_devmath_update, L.rt_devmath_step, L.rt_devmath_div,
                   L.rt_devmath_deposit, L.rt_devmath_tan, L.rt_devmath_pchip, L.rt_devmath_seed_factor, L.rt_devmath_seed_tab,
-                  L.rt_devmath_ev_sum, L.rt_devmath_nf_scan):
+                  L.rt_devmath_ev_sum, L.rt_devmath_nf_scan, L.rt_devmath_march_step, L.rt_devmath_march_xsetup, L.rt_devmath_f32,
+                  L.rt_devmath_f64_div):
             f.restype = ci
         assert L.rt_devmath_vec() == VEC
 
@@ -256,6 +268,57 @@ class Device:
         self._check(self.lib.rt_devmath_nf_scan(_ptr(pix, ctypes.c_int), _ptr(val, ctypes.c_double), float(scale), n_pix,
                                                 _ptr(nf, ctypes.c_double)), "rt_devmath_nf_scan")
         return nf
+
+    def march_step(self, instance, state, c=0.5):
+        """One integrator step of the march per case (csrc/rt_march_step.inc) in one of STEP_INSTANCES.  state [n][14] float32 =
+        n0, gxn, gyn, rx, ry, rz, sx, sy, sz, hsum, w_x, w_y, lim2, dzcap; c the step factor -> (out [n][8] = n, rx, ry, rz, sx, sy,
+        sz, hsum; run [n] bool; counters: waves of the launch that took prune(0 .. 3) and the tiny-dividend block, and all
+        waves).  The kernel runs whole waves: the last one is padded with copies of the last case."""
+        bounded, opt = self.STEP_INSTANCES[instance]
+        state = _f32(state)
+        assert state.ndim == 2 and state.shape[1] == 14 and state.shape[0] >= 1
+        n = state.shape[0]
+        out, run, cnt = np.empty((n, 8), np.float32), np.empty(n, np.uint8), np.zeros(6, np.uint32)
+        self._check(self.lib.rt_devmath_march_step(bounded, opt, float(c), _ptr(state, ctypes.c_float), _ptr(out, ctypes.c_float),
+                                                   _ptr(run, ctypes.c_ubyte), _ptr(cnt, ctypes.c_uint), n), "rt_devmath_march_step")
+        return out, run.astype(bool), dict(prune=[int(v) for v in cnt[:4]], tiny=int(cnt[4]), waves=int(cnt[5]))
+
+    def march_xsetup(self, pos, lo, w, rw, nc, mirror):
+        """The cross-cell set-up of the march per case (csrc/rt_march_xsetup.inc).  pos [n][2] float32 = px, py; lo [n][2] the
+        lower corner of the cell, w [n][2] float32 its widths, rw [n][2] = 1 / (double) w (the interval records of
+        rt_plan.hip); nc [n][4] = the corner indices n00, n10, n01, n11; mirror [n] -> [n][3] = n0, gxn, gyn."""
+        pos, w = _f32(pos), _f32(w)
+        lo, rw, nc = _f64(lo), _f64(rw), _f64(nc)
+        mirror = np.ascontiguousarray(mirror, dtype=np.uint8)
+        n = pos.shape[0]
+        assert n >= 1 and pos.shape == w.shape == lo.shape == rw.shape == (n, 2) and nc.shape == (n, 4) and mirror.shape == (n,)
+        fin = np.ascontiguousarray(np.concatenate([pos, w], axis=1))
+        din = np.ascontiguousarray(np.stack([lo[:, 0], rw[:, 0], lo[:, 1], rw[:, 1], nc[:, 0], nc[:, 1], nc[:, 2], nc[:, 3]], axis=1))
+        out = np.empty((n, 3), np.float32)
+        self._check(self.lib.rt_devmath_march_xsetup(_ptr(fin, ctypes.c_float), _ptr(din, ctypes.c_double), _ptr(mirror, ctypes.c_ubyte),
+                                                     _ptr(out, ctypes.c_float), n), "rt_devmath_march_xsetup")
+        return out
+
+    def f32(self, which, a, b=None, y=None):
+        """A float primitive of csrc/rt_math.h elementwise: INV_NORM inv_norm(a), DIV_BY_RECIP div_by_recip(a, b, y),
+        DIV_BY_RECIP_SIGNED, FDIV_NR fdiv_nr(a, b), FDIV_ONE_NR fdiv_one_nr(b), FMIN_NAN_DROP fmin_nan_drop(a, b)."""
+        ref = a if a is not None else b
+        a, b, y = (_f32(v if v is not None else np.zeros_like(ref)) for v in (a, b, y))
+        assert a.ndim == 1 and a.shape == b.shape == y.shape and a.size >= 1
+        out = np.empty_like(a)
+        self._check(self.lib.rt_devmath_f32(which, _ptr(a, ctypes.c_float), _ptr(b, ctypes.c_float), _ptr(y, ctypes.c_float),
+                                            _ptr(out, ctypes.c_float), a.size), "rt_devmath_f32")
+        return out
+
+    def f64_div(self, which, a, b, y):
+        """The double div_by_recip(a, b, y) of csrc/rt_math.h elementwise: F64_DIV_BY_RECIP the guarded form,
+        F64_DIV_BY_RECIP_TINY_OK the form of the cross-cell set-up."""
+        a, b, y = _f64(a), _f64(b), _f64(y)
+        assert a.ndim == 1 and a.shape == b.shape == y.shape
+        out = np.empty_like(a)
+        self._check(self.lib.rt_devmath_f64_div(which, _ptr(a, ctypes.c_double), _ptr(b, ctypes.c_double), _ptr(y, ctypes.c_double),
+                                                _ptr(out, ctypes.c_double), a.size), "rt_devmath_f64_div")
+        return out
 
     def pchip(self, xs, ys, x):
         """pchip_eval (csrc/rt_math.h) of one axis xs, ys [n >= 2] at x [m]."""

@@ -12,6 +12,13 @@ they are built for.
                                prunable=[h1, h2, h4] steps in which the division-free test of rt_march.hip, block [C],
                                num > RN(RN(1.00002f dzcap) den), says the candidate cannot set the step,
                                prune_wrong=such steps in which the candidate's float quotient is below dzcap after all)
+
+  steps(..., sample=(cap, stride)) adds entry_states [<= cap][14] float32: the state at the entry of integrator steps as the unit
+      kernels of the march take it (tests/march_block_inputs.py: n0, gx, gy, rx, ry, rz, sx, sy, sz, path, wx, wy, lim2, dzcap),
+      every stride-th live ray of every pass until cap states are held
+  steps(..., step_fn=f) takes every integrator step with f(states [m][14], c) -> dict(out [m][8], run_geo, run_full, winner)
+      -- Oracle.linear_step of oracle/binding.py -- in place of the numpy statement (prunable / prune_wrong stay 0)
+  steps(..., want_state=True) adds end_state [n_rays][6] = px, py, pz, sx, sy, sz when the march is over
 """
 import importlib
 
@@ -38,16 +45,17 @@ def _renorm(sx, sy, sz):
     return sx * inv, sy * inv, sz * inv
 
 
-def steps(problem, rays, c=0.5):
+def steps(problem, rays, c=0.5, sample=None, step_fn=None, want_state=False):
     old = np.seterr(all="ignore")
     try:
-        return _steps(problem, rays, F(c))
+        return _steps(problem, rays, F(c), sample, step_fn, want_state)
     finally:
         np.seterr(**old)
 
 
-def _steps(p, rays, c):
+def _steps(p, rays, c, sample=None, step_fn=None, want_state=False):
     n_r = len(rays)
+    sampled, n_sampled = [], 0
     N, method, use_emis = p.N, p.method, p.use_emis
     dz0 = F(p.beam.dz)
     px, py = rays["x"].astype(F), rays["y"].astype(F)
@@ -120,6 +128,7 @@ def _steps(p, rays, c):
                     dzcap = c * F(1.00001) * lim2
                     rx, ry, rz = np.zeros(len(j), F), np.zeros(len(j), F), np.zeros(len(j), F)
                     n = n0.copy()
+                    hs = np.zeros(len(j), F)
                     s0, s1, s2 = sx[r], sy[r], sz[r]
                     alive = np.ones(len(j), bool)
                     while True:
@@ -133,6 +142,23 @@ def _steps(p, rays, c):
                         if len(q) == 0:
                             break
                         a0, a1, a2 = s0[q], s1[q], s2[q]
+                        if sample is not None or step_fn is not None:
+                            entry = np.stack([n0[q], gx[q], gy[q], rx[q], ry[q], rz[q], a0, a1, a2, hs[q], wx[j][q], wy[j][q],
+                                              lim2[q], dzcap[q]], axis=1).astype(F)
+                            if sample is not None and n_sampled < sample[0]:
+                                take = entry[::sample[1]][:sample[0] - n_sampled]
+                                sampled.append(take)
+                                n_sampled += len(take)
+                        if step_fn is not None:
+                            o = step_fn(entry, c)
+                            n[q] = o["out"][:, 0]
+                            max_dn = max(max_dn, float(np.abs(n[q] - n0[q]).max()))
+                            rx[q], ry[q], rz[q] = o["out"][:, 1], o["out"][:, 2], o["out"][:, 3]
+                            s0[q], s1[q], s2[q] = o["out"][:, 4], o["out"][:, 5], o["out"][:, 6]
+                            hs[q] = o["out"][:, 7]
+                            winner += np.bincount(o["winner"], minlength=5)
+                            inner += len(q)
+                            continue
                         nn = n0[q] + rx[q] * gx[q] + ry[q] * gy[q]
                         n[q] = nn
                         max_dn = max(max_dn, float(np.abs(nn - n0[q]).max()))
@@ -170,6 +196,7 @@ def _steps(p, rays, c):
                         rz[q] += a2 * h + c1 * fz
                         c2 = h * (F(1) - F(0.5) * ht + ht * ht / F(6))
                         s0[q], s1[q], s2[q] = _renorm(a0 + c2 * fx, a1 + c2 * fy, a2 + c2 * fz)
+                        hs[q] += h
                     sx[r], sy[r], sz[r] = s0, s1, s2
                     px[r] += rx
                     py[r] += ry
@@ -177,7 +204,12 @@ def _steps(p, rays, c):
                     zc[j] += np.abs(rz)
                 z[i] += np.abs(pz[i])
                 cells += len(i)
-    return dict(winner=winner, inner=inner, cells=cells, n_exit=n_exit, n_exit_rays=int(exit_ray.sum()), max_dn=max_dn, prunable=prunable, prune_wrong=prune_wrong)
+    out = dict(winner=winner, inner=inner, cells=cells, n_exit=n_exit, n_exit_rays=int(exit_ray.sum()), max_dn=max_dn, prunable=prunable, prune_wrong=prune_wrong)
+    if sample is not None:
+        out["entry_states"] = np.concatenate(sampled) if sampled else np.zeros((0, 14), F)
+    if want_state:
+        out["end_state"] = np.stack([px, py, pz, sx, sy, sz], axis=1)
+    return out
 
 
 # ------------------------------------------------------------------ the synthetic tables of the march tests
