@@ -700,6 +700,77 @@ int rt_hip_full_length_scan_loop(int device, int N, const rt_beam *beam, const r
                                  double *E_v, double *nf, double *I_ang, unsigned int *failure_codes, rt_ray *failed_rays,
                                  int max_failed, int *n_failed, rt_stats *stats);
 
+/*
+ * Step history: the step records of a time loop filed ON THE DEVICE.  What the application does on the host after every
+ * step -- intensity_struct::copy_step (src/RayTraceStructures.cpp:1835-1867: E_v, image and E_ang of the ASE record and of
+ * every seed record into slab i of arrays [N_t][...], E_sum[i] = sum_j image[j]), intensity_step_struct::valid() (:1647-1682)
+ * and intensity_step_struct::add (:1579-1602) -- as ONE explicit call behind a step run, which only enqueues: two small
+ * launches (raytrace-miniapp_amd/csrc/rt_history.hip) on the run's stream, no stream synchronise, no copy to the host, no
+ * rt_hip_plan_fetch.  A step of  update_gain_dev -> run -> history_append  then has the one wait of the update left, and one
+ * fetch at the end of the loop hands back the arrays.  Nothing happens unless these calls are made.
+ * history_create: n_steps >= 1 sizes the history (an existing one is released first), n_steps = 0 releases it.  The memory
+ *   is taken from the pool and zeroed at the FIRST append, which binds the history to the record set of that run (its kind,
+ *   seeds and lengths: n_rec blocks, 1 after a plain step run) and to the beam sizes.
+ * history_append: files the records of the last run -- which must have been a step run, anything else is RT_ERR_ARG -- into
+ *   slab `step` (0 <= step < n_steps) of every array, for every block r of the run's record set at once:
+ *     E_v[r][step][nv], nf[r][step][nx*ny], I_ang[r][step][na*nb]   bit-for-bit copies (of a plain step run: the buffers
+ *                         rt_hip_plan_step_ptrs names, lent ones included, and the I_ang the run wrote, a caller's iang_dev
+ *                         included); the spare cells behind nf / I_ang of a one-point beam axis are neither copied nor summed;
+ *     E_sum[r][step]      sum of the nx*ny values of nf: a fixed partition of the pixels over work-groups, a fixed order
+ *                         inside each, the partials added in index order by the second launch -- the same double from run to
+ *                         run, whatever the slot, the block, the number of blocks or the place of the buffers (no atomics);
+ *     flags[r][step]      bit 0: some value of E_v, nf or I_ang is < 0; bit 1: some value is NaN (valid() is flags == 0);
+ *     code[r][step]       the failure code of block r, read on the device from the control block of the run;
+ *     filled[step]        1.
+ *   accumulate != 0 adds to the running sum as well: acc[r][.] = acc[r][.] + weight * x for every element of every block
+ *   (the product rounded, then the sum: `acc + weight * x` of IEEE doubles without contraction) and E_sum_acc[r] likewise
+ *   from E_sum[r][step].  weight is read only then.  stream NULL: the stream of the last run; another stream first waits for
+ *   the run's end.  The records are filed AS THEY STAND in stream order: behind a bare rt_hip_plan_run a record with failing
+ *   rays (code bits 2 / 3) is the unchecked one -- the reference gives the whole run up there ("Some rays failed") -- and a
+ *   caller who wants the checked record calls any rt_hip_plan_fetch* first (the checking repeat) and appends then.  A slot
+ *   appended twice holds the second record (the running sum took both).  A record set or beam sizes other than the ones the
+ *   history is bound to are RT_ERR_ARG and leave the history as it was.  While an append is in flight the plan keeps an
+ *   event behind it: a run on ANOTHER stream waits for it before it zeroes the records, and whatever frees or rewrites them
+ *   from the host (destroy, a re-allocation, the checking repeat) waits for it; lent buffers are the caller's to keep.
+ * history_ptrs / history_sum_ptrs: device pointers of block r (0 <= r < n_rec; after the first append): E_v [n_steps][nv], nf
+ *   [n_steps][nx*ny], I_ang [n_steps][na*nb], E_sum [n_steps], code [n_steps], flags [n_steps]; of the running sum E_v [nv], nf
+ *   [nx*ny], I_ang [na*nb], E_sum [1].  Any pointer may be NULL.  Read them on the append's stream or after a fetch.
+ * history_fetch / history_fetch_sum: wait for the last append, then copy block r to the host (the same shapes; filled
+ *   [n_steps]); any pointer may be NULL.  Before the first append everything reads zero (r = 0 only).
+ * history_info: n_steps, n_rec (0 before the first append) and the number of slots an append was queued for.
+ * rt_hip_debug_history_layout: the layout of the allocation and the shape of the two launches from plain numbers, by the
+ *   function history_append itself uses; no device.  Both structs start with their own sizeof in `size`.  Offsets and strides
+ *   in bytes: array X of block r and step i starts at off_X + r rec_X + i step_X (E_sum / code / flags: i * 8 / 4 / 4).
+ *   chunk: pixels of nf per work-group (a constant); pix_wg work-groups per block sum nf, aux_wg take E_v and I_ang; grid =
+ *   n_rec wg_per_rec work-groups of wg_threads; off_part / off_pflag: the scratch of the partials, [n_rec][wg_per_rec]
+ *   doubles / words, scratch_bytes in all; the running sum (off_acc_*, rec_acc_*) is there when accumulate != 0 -- a plan's
+ *   history always reserves it (one record per block beside n_steps of them).
+ * Not taken: W, I_it (the reference files zero) and E_tot; histories of the multi-device loops; a host-pointer loop.
+ */
+typedef struct rt_hip_history_facts {
+    unsigned size;
+    int nv, nx, ny, na, nb, n_rec, n_steps, accumulate;
+} rt_hip_history_facts;
+typedef struct rt_hip_history_layout {
+    unsigned size;
+    unsigned chunk, wg_threads, pix_wg, aux_wg, wg_per_rec, grid;
+    unsigned long long bytes, scratch_bytes;
+    unsigned long long off_E_v, rec_E_v, step_E_v, off_nf, rec_nf, step_nf, off_I_ang, rec_I_ang, step_I_ang;
+    unsigned long long off_E_sum, rec_E_sum, off_code, rec_code, off_flags, rec_flags, off_filled;
+    unsigned long long off_acc_E_v, rec_acc_E_v, off_acc_nf, rec_acc_nf, off_acc_I_ang, rec_acc_I_ang, off_acc_E_sum;
+    unsigned long long off_part, off_pflag;
+} rt_hip_history_layout;
+int rt_hip_plan_history_create(rt_hip_plan *plan, int n_steps);
+int rt_hip_plan_history_append(rt_hip_plan *plan, int step, double weight, int accumulate, void *stream);
+int rt_hip_plan_history_ptrs(rt_hip_plan *plan, int r, double **E_v, double **nf, double **I_ang, double **E_sum,
+                             unsigned int **code, unsigned int **flags);
+int rt_hip_plan_history_sum_ptrs(rt_hip_plan *plan, int r, double **E_v, double **nf, double **I_ang, double **E_sum);
+int rt_hip_plan_history_fetch(rt_hip_plan *plan, int r, double *E_v, double *nf, double *I_ang, double *E_sum,
+                              unsigned int *code, unsigned int *flags, unsigned char *filled);
+int rt_hip_plan_history_fetch_sum(rt_hip_plan *plan, int r, double *E_v, double *nf, double *I_ang, double *E_sum);
+int rt_hip_plan_history_info(rt_hip_plan *plan, int *n_steps, int *n_rec, int *n_filled);
+int rt_hip_debug_history_layout(const rt_hip_history_facts *facts, rt_hip_history_layout *out);
+
 /* Profiling aid (no reference counterpart): bit 0 = skip the frequency / deposit kernel, bit 1 = skip
  * the march and run the frequency pass over the records of the previous run of this plan, bit 2 = the
  * frequency kernel keeps its per-work-group I_ang sums to itself (I_ang stays zero).  0 = normal. */

@@ -8,6 +8,7 @@ mirror of the reference's operator interface for this path.
                         (src/RayTraceImageCuda.cu:145-221) behind the signature of
                         src/RayTraceImage.cpp:47-75
   step_loop(...)        the same loop with the application's per-step record in place of the image cube: E_v, nf, I_ang
+  step_history_loop(...) a time loop over gain tables with every step's records filed on the device (Plan.history_append)
   multi_step_loop(...)  step_loop on all devices of the node: strided ray grid per device, one sum-reduce of the record
   seed_step_loop(...)   the step records of up to RT_N_SEED_MAX seed beams from one march (Plan.set_seeds)
   full_step_loop(...)   the ASE record and the records of up to RT_N_SEED_MAX seed beams from one march (Plan.set_ase_seeds)
@@ -495,6 +496,84 @@ class Plan:
         curves = [[dict(n=n, **self._record_views(self.full_length_step_ptrs(r, n))) for n in lengths] for r in recs]
         return dict(ase=curves[0] if curves else [], seeds=curves[1:])
 
+    # -- step history -------------------------------------------------------
+    def enable_history(self, n_steps: int) -> "Plan":
+        """A device-resident step history of n_steps slots (include/rt_hip.h, rt_hip_plan_history_create); 0 releases it.  The
+        memory is taken at the first history_append, which binds the history to that run's record set."""
+        if isinstance(n_steps, bool) or not isinstance(n_steps, (int, np.integer)) or n_steps < 0:
+            raise ValueError(f"enable_history: n_steps is an int >= 0, not {n_steps!r}")
+        self.hl.check(self.hl.lib.rt_hip_plan_history_create(self._h, int(n_steps)), "rt_hip_plan_history_create")
+        return self
+
+    def history_append(self, step: int, weight: float = 1.0, accumulate: bool = False, stream: int | None = None) -> "Plan":
+        """File every record of the last step run into slot `step` of the history, with E_sum, the valid() flags and the
+        failure codes, on the device and in stream order: the call only enqueues.  accumulate: add weight * record to the
+        running sum as well.  stream: a hipStream_t value; None: the stream of the last run."""
+        self.hl.check(self.hl.lib.rt_hip_plan_history_append(self._h, int(step), float(weight), int(bool(accumulate)),
+                                                             C.c_void_p(stream or None)), "rt_hip_plan_history_append")
+        return self
+
+    def history_info(self) -> dict:
+        """dict(n_steps, n_rec (0 before the first append), n_filled (slots an append was queued for))."""
+        a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+        self.hl.check(self.hl.lib.rt_hip_plan_history_info(self._h, C.byref(a), C.byref(b), C.byref(c)), "rt_hip_plan_history_info")
+        return dict(n_steps=a.value, n_rec=b.value, n_filled=c.value)
+
+    def fetch_history(self) -> list:
+        """One dict per record block of the history (waits for the last append): E_v [n_steps][nv], nf [n_steps][nx * ny],
+        I_ang [n_steps][na * nb], E_sum [n_steps], failure_code [n_steps] and flags [n_steps] (uint32; bit 0 a negative value,
+        bit 1 a NaN) and filled [n_steps] (uint8, the same in every dict).  Slots never appended read zero."""
+        b, info = self.problem.beam, self.history_info()
+        T, out = info["n_steps"], []
+        for r in range(max(1, info["n_rec"])):
+            E_v, nf, iang, es = np.empty((T, b.nv)), np.empty((T, b.nx * b.ny)), np.empty((T, b.na * b.nb)), np.empty(T)
+            code, flags, filled = np.empty(T, np.uint32), np.empty(T, np.uint32), np.empty(T, np.uint8)
+            U, B = C.POINTER(C.c_uint), C.POINTER(C.c_ubyte)
+            self.hl.check(self.hl.lib.rt_hip_plan_history_fetch(
+                self._h, r, cabi._dp(E_v), cabi._dp(nf), cabi._dp(iang), cabi._dp(es), code.ctypes.data_as(U),
+                flags.ctypes.data_as(U), filled.ctypes.data_as(B)), "rt_hip_plan_history_fetch")
+            out.append(dict(E_v=E_v, nf=nf, I_ang=iang, E_sum=es, failure_code=code, flags=flags, filled=filled))
+        return out
+
+    def fetch_history_sum(self) -> list:
+        """One dict per record block: the running sum E_v [nv], nf [nx * ny], I_ang [na * nb] and E_sum (a float) of the
+        appends that asked for it (waits for the last append)."""
+        b, out = self.problem.beam, []
+        for r in range(max(1, self.history_info()["n_rec"])):
+            E_v, nf, iang, es = np.empty(b.nv), np.empty(b.nx * b.ny), np.empty(b.na * b.nb), np.empty(1)
+            self.hl.check(self.hl.lib.rt_hip_plan_history_fetch_sum(self._h, r, cabi._dp(E_v), cabi._dp(nf), cabi._dp(iang),
+                                                                    cabi._dp(es)), "rt_hip_plan_history_fetch_sum")
+            out.append(dict(E_v=E_v, nf=nf, I_ang=iang, E_sum=float(es[0])))
+        return out
+
+    def history_tensors(self) -> list:
+        """One dict per record block: torch views (on the plan's device, no copy) of E_v [n_steps][nv], nf [n_steps][ny][nx],
+        I_ang [n_steps][nb][na], E_sum [n_steps] (float64), failure_code and flags [n_steps] (int32 views of the 32-bit words);
+        after the first append, valid until enable_history is called again; read them on the append's stream."""
+        import torch
+
+        b, info, out = self.problem.beam, self.history_info(), []
+        T = info["n_steps"]
+        for r in range(info["n_rec"]):
+            q = [C.c_void_p() for _ in range(6)]
+            self.hl.check(self.hl.lib.rt_hip_plan_history_ptrs(self._h, r, *(C.byref(x) for x in q)), "rt_hip_plan_history_ptrs")
+            e, n, a, s, c, f = (int(x.value or 0) for x in q)
+            words = lambda ptr: _view(ptr, (T // 2 + T % 2,), self.device).view(torch.int32)[:T]   # (blocks of words are padded to 8 bytes)
+            out.append(dict(E_v=_view(e, (T, b.nv), self.device), nf=_view(n, (T, b.ny, b.nx), self.device),
+                            I_ang=_view(a, (T, b.nb, b.na), self.device), E_sum=_view(s, (T,), self.device),
+                            failure_code=words(c), flags=words(f)))
+        return out
+
+    def history_sum_tensors(self) -> list:
+        """One dict per record block: torch views of the running sum, E_v [nv], nf [ny][nx], I_ang [nb][na], E_sum [1]."""
+        out = []
+        for r in range(self.history_info()["n_rec"]):
+            q = [C.c_void_p() for _ in range(4)]
+            self.hl.check(self.hl.lib.rt_hip_plan_history_sum_ptrs(self._h, r, *(C.byref(x) for x in q)), "rt_hip_plan_history_sum_ptrs")
+            e, n, a, s = (int(x.value or 0) for x in q)
+            out.append(dict(**self._record_views((e, n, a)), E_sum=_view(s, (1,), self.device)))
+        return out
+
     # -- tables -------------------------------------------------------------
     def update_gain(self, gain, stream: int | None = None) -> "Plan":
         """New n, g0, E0 and gv on the plan's grids (include/rt_hip.h, rt_hip_plan_update_gain): everything else about the
@@ -663,6 +742,29 @@ def step_loop(problem: Problem, rays: np.ndarray | None = None, device: int = 0)
     hl.check(rc, "rt_hip_step_loop")
     return dict(E_v=E_v, nf=nf, I_ang=iang, failure_code=code.value, failed_rays=failed[:nfail.value].copy(),
                 stats={k: getattr(st, k) for k, _ in cabi.RtStats._fields_}, call_ms=call_ms)
+
+
+def step_history_loop(p: Problem, snapshots, seeds=None, scales=None, accumulate: bool = False, weights=None, device: int = 0) -> dict:
+    """A time loop over the gain tables `snapshots` (what Plan.update_gain takes, one entry per step) with the step records
+    filed on the device: one plan of `p` in step mode on its ray grid (with ASE seeds when `seeds` is given: Plan.set_ase_seeds
+    with `scales`), per snapshot update_gain -> run -> history_append(i, weights[i], accumulate), and ONE fetch at the end.
+    A convenience over the plan API.  Returns dict(records=Plan.fetch_history(), sums=Plan.fetch_history_sum() or None,
+    filled)."""
+    snapshots = list(snapshots)
+    if not snapshots:
+        raise ValueError("step_history_loop: no snapshots")
+    weights = [1.0] * len(snapshots) if weights is None else [float(w) for w in weights]
+    if len(weights) != len(snapshots):
+        raise ValueError(f"step_history_loop: {len(weights)} weights for {len(snapshots)} snapshots")
+    with Plan(p, device=device) as plan:
+        plan.set_ray_grid().enable_step()
+        if seeds is not None:
+            plan.set_ase_seeds(seeds, scales)
+        plan.enable_history(len(snapshots))
+        for i, tables in enumerate(snapshots):
+            plan.update_gain(tables).run().history_append(i, weights[i], accumulate)
+        recs = plan.fetch_history()
+        return dict(records=recs, sums=plan.fetch_history_sum() if accumulate else None, filled=recs[0]["filled"])
 
 
 def multi_step_loop(problem: Problem, rays: np.ndarray | None = None, n_devices: int = 0) -> dict:

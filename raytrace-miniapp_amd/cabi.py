@@ -94,6 +94,19 @@ class RtRunShape(C.Structure):
         "int: pass_kind pass_wg_waves pass_in_lds pass_nslot; ull: pass_lds; uint: pass_grid pass_fetch_shift")
 
 
+class RtHistoryFacts(C.Structure):
+    _fields_ = _fields("uint: size; int: nv nx ny na nb n_rec n_steps accumulate")
+
+
+class RtHistoryLayout(C.Structure):
+    _fields_ = _fields(
+        "uint: size; uint: chunk wg_threads pix_wg aux_wg wg_per_rec grid; ull: bytes scratch_bytes;"
+        "ull: off_E_v rec_E_v step_E_v off_nf rec_nf step_nf off_I_ang rec_I_ang step_I_ang;"
+        "ull: off_E_sum rec_E_sum off_code rec_code off_flags rec_flags off_filled;"
+        "ull: off_acc_E_v rec_acc_E_v off_acc_nf rec_acc_nf off_acc_I_ang rec_acc_I_ang off_acc_E_sum;"
+        "ull: off_part off_pflag")
+
+
 def _dp(a: np.ndarray):
     assert a.dtype == np.float64 and a.flags.c_contiguous
     return a.ctypes.data_as(c_double_p)
@@ -409,6 +422,24 @@ def declare_hip_api(lib: C.CDLL) -> None:
         lib.rt_hip_plan_full_length_step_ptrs.restype = C.c_int
         lib.rt_hip_full_length_scan_loop.argtypes = list(lib.rt_hip_full_step_loop.argtypes)   # (one row per record and length)
         lib.rt_hip_full_length_scan_loop.restype = C.c_int
+    if hasattr(lib, "rt_hip_plan_history_create"):   # (likewise)
+        up, bp = P(C.c_uint), P(C.c_ubyte)
+        lib.rt_hip_plan_history_create.argtypes = [vp, C.c_int]
+        lib.rt_hip_plan_history_create.restype = C.c_int
+        lib.rt_hip_plan_history_append.argtypes = [vp, C.c_int, C.c_double, C.c_int, vp]
+        lib.rt_hip_plan_history_append.restype = C.c_int
+        lib.rt_hip_plan_history_ptrs.argtypes = [vp, C.c_int, P(vp), P(vp), P(vp), P(vp), P(vp), P(vp)]
+        lib.rt_hip_plan_history_ptrs.restype = C.c_int
+        lib.rt_hip_plan_history_sum_ptrs.argtypes = [vp, C.c_int, P(vp), P(vp), P(vp), P(vp)]
+        lib.rt_hip_plan_history_sum_ptrs.restype = C.c_int
+        lib.rt_hip_plan_history_fetch.argtypes = [vp, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, up, up, bp]
+        lib.rt_hip_plan_history_fetch.restype = C.c_int
+        lib.rt_hip_plan_history_fetch_sum.argtypes = [vp, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p]
+        lib.rt_hip_plan_history_fetch_sum.restype = C.c_int
+        lib.rt_hip_plan_history_info.argtypes = [vp, P(C.c_int), P(C.c_int), P(C.c_int)]
+        lib.rt_hip_plan_history_info.restype = C.c_int
+        lib.rt_hip_debug_history_layout.argtypes = [P(RtHistoryFacts), P(RtHistoryLayout)]
+        lib.rt_hip_debug_history_layout.restype = C.c_int
     lib.rt_hip_plan_set_debug.argtypes = [vp, C.c_uint]
     lib.rt_hip_plan_set_debug.restype = C.c_int
     lib.rt_hip_plan_destroy.argtypes = [vp]
@@ -434,5 +465,7 @@ HIP_API_SYMBOLS = [
     "rt_hip_plan_set_scan_ase_seeds", "rt_hip_plan_fetch_full_length_step", "rt_hip_plan_full_length_step_ptrs",
     "rt_hip_full_length_scan_loop",
     "rt_hip_plan_set_step_one_launch", "rt_hip_debug_run_shape",
+    "rt_hip_plan_history_create", "rt_hip_plan_history_append", "rt_hip_plan_history_ptrs", "rt_hip_plan_history_sum_ptrs",
+    "rt_hip_plan_history_fetch", "rt_hip_plan_history_fetch_sum", "rt_hip_plan_history_info", "rt_hip_debug_history_layout",
     "rt_hip_plan_set_debug", "rt_hip_plan_destroy",
 ]

@@ -113,6 +113,7 @@ const size_t rtr::MAX_LIST_RAYS = 0xffffffffull - 4096;
 // another plan may be handed a parked block at once (pool_alloc) and overwrite it.
 void rtr::plan_quiesce(rt_hip_plan *p)
 {
+    history_wait(p); // an append of the step history, possibly on another queue, reads the records and the control block
     if (p && p->ran) {
         if (hipStreamSynchronize(p->last_stream) != hipSuccess)
             (void) hipGetLastError(); // a caller's stream that is gone: nothing is in flight on it
@@ -190,6 +191,7 @@ void rt_hip_plan_destroy(rt_hip_plan *p)
             (void) hipEventDestroy(e);
     pool_free(p->device, p->tab_work);
     pinned_free(p->tab_pin);
+    history_release(p);
 
     pool_free(p->device, p->tan_dev);
     pool_free(p->device, p->rec);
@@ -1129,6 +1131,17 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
             HIP_TRY(hipStreamWaitEvent(stream, p->tab_ev, 0));
         }
     }
+    // an append of the step history still reads the records and the control block this run zeroes: behind it on the same
+    // queue anyway, on another queue after its event
+    if (p->hist.pending) {
+        if (hipEventQuery(p->hist.ev) == hipSuccess) {
+            p->hist.pending = false;
+        } else {
+            (void) hipGetLastError(); // (hipErrorNotReady)
+            if (p->hist.stream != stream)
+                HIP_TRY(hipStreamWaitEvent(stream, p->hist.ev, 0));
+        }
+    }
     if (p->probe_on && p->n_rays)
         HIP_TRY(hipMemsetAsync(p->probe, 0, (size_t) p->n_rays * (sizeof(rt_ray) + 8), stream));
     static_assert(sizeof(rt::DevCtl) % 8 == 0 && alignof(rt::DevCtl) >= 8, "zeroed in 8-byte words");
@@ -1232,6 +1245,7 @@ static int plan_settle(rt_hip_plan *p, rt::DevCtl &c, bool &staged)
 {
     HIP_TRY(hipSetDevice(p->device));
     HIP_TRY(hipStreamSynchronize(p->last_stream));
+    history_wait(p); // (an append on another queue: the checking repeat below rewrites what it reads)
     constexpr size_t ctl_tail = offsetof(rt::DevCtl, failure_code), ctl_bytes = sizeof(rt::DevCtl) - ctl_tail;
     auto read_ctl = [&]() {
         return hipMemcpy(reinterpret_cast<unsigned char *>(&c) + ctl_tail, reinterpret_cast<const unsigned char *>(p->ctl) + ctl_tail,
@@ -1283,17 +1297,13 @@ static int record_ptrs(rt_hip_plan *p, int block, double **E_v_dev, double **nf_
         *iang_dev = blk + p->recs_ang_off;
     return RT_OK;
 }
-// the code of a block: the one place that knows which array of the control block a kind's kernel writes
+// the code of a block, by the one table that knows which array of the control block a kind's kernel writes (rt_runtime.h)
 static unsigned record_code(const rt::DevCtl &c, const RecordSet &R, int block)
 {
-    switch (R.kind) {
-    case REC_SEEDS: return c.seed_code[block];
-    case REC_ASE_SEEDS: return c.rec_code[block];
-    case REC_SCAN: return c.len_code[block];
-    case REC_SCAN_SEEDS: return c.seed_len_code[block / R.L][block % R.L];
-    case REC_SCAN_ASE_SEEDS: return c.rec_len_code[block / R.L][block % R.L];
-    default: return c.failure_code;
-    }
+    // (REC_NONE has the one code of the run, whatever the block: record_code_slot's default at block 0)
+    unsigned code = 0;
+    memcpy(&code, reinterpret_cast<const unsigned char *>(&c) + sizeof(unsigned) * record_code_slot(R).word(R.kind == REC_NONE ? 0 : block), sizeof(code));
+    return code;
 }
 static int record_fetch(rt_hip_plan *p, int block, double *E_v, double *nf, double *I_ang, unsigned int *code)
 {

@@ -1,6 +1,6 @@
 // rt_runtime.h -- what the host-side translation units of librt_hip.so share (internal, not part of the C ABI).
 //
-// The C ABI of include/rt_hip.h is implemented by six translation units:
+// The C ABI of include/rt_hip.h is implemented by seven translation units:
 //   rt_pool.hip     error text, device-memory pool, leased queues, environment overrides
 //   rt_plan.hip     the plan: arena packing, ray list / ray grid, run, fetch, probe and path outputs,
 //                   rt_hip_image_loop (the host-pointer entry the C++ adapter calls)
@@ -17,7 +17,9 @@
 //                   plan_launch_run enqueues what they say and writes nothing per-launch into the plan's DevParams
 //   rt_multi.hip    all devices of the node: RCCL loader, communicator, rt_hip_multi_image_loop, rt_hip_multi_step_loop
 //   rt_tables.hip   the gain tables of a resident plan rewritten in place: scan and pack kernels, rt_hip_plan_update_gain
-// Only rt_launch.hip, rt_multi.hip and rt_tables.hip contain device code.
+//   rt_history.hip  the step history of a time loop: the records of the last step run filed into slab i of arrays that live in
+//                   the plan, by two small launches and no host wait (rt_hip_plan_history_*, rt_hip_debug_history_layout)
+// Only rt_launch.hip, rt_multi.hip, rt_tables.hip and rt_history.hip contain device code.
 #pragma once
 
 #include "rt_device.h"
@@ -26,8 +28,31 @@
 #include "rt_step.h"
 
 #include <chrono>
+#include <cstddef>
 #include <string>
 #include <vector>
+
+namespace rtr {
+
+// The step history of a plan (rt_history.hip; include/rt_hip.h, rt_hip_plan_history_create): ONE allocation from the pool,
+// laid out by history_layout, made and zeroed at the first append and bound to that run's record set and beam sizes.
+struct History {
+    int n_steps = 0;              // 0: no history
+    bool bound  = false;          // the first append has run: dev, lay, recs and n_rec are set
+    RecordSet recs;               // ... of that run
+    int n_rec = 0;                // its blocks (REC_NONE: the one step record)
+    int nv = 0, nx = 0, ny = 0, na = 0, nb = 0;
+    unsigned char *dev = nullptr;
+    rt_hip_history_layout lay = {};
+    std::vector<unsigned char> filled; // host copy of filled[]: which slots an append was queued for
+    // behind the last append: whatever zeroes, rewrites or frees a buffer the append reads waits for it (history_wait), a
+    // run on another queue waits for it on that queue (rt_hip_plan_run), as tab_ev / tab_pending do for the table pack
+    hipEvent_t ev      = nullptr;
+    bool pending       = false;
+    hipStream_t stream = nullptr; // the queue of the last append
+};
+
+} // namespace rtr
 
 // One prepared problem on one device (opaque in include/rt_hip.h).
 struct rt_hip_plan {
@@ -167,6 +192,7 @@ struct rt_hip_plan {
     hipEvent_t tab_ev = nullptr; // behind the pack of the last update: the next run waits for it on its own queue
     bool tab_pending  = false;
     hipEvent_t tab_t[3] = { nullptr, nullptr, nullptr }; // RT_HIP_TIMING: before / behind the scan, before the pack
+    rtr::History hist; // the step history (rt_history.hip)
 };
 
 namespace rtr {
@@ -225,6 +251,26 @@ int plan_settle_last_run(rt_hip_plan *p);
 int plan_build_seedset_tabs(rt_hip_plan *p);
 // most rays a list may hold (the kernels index rays with 32 bits)
 extern const size_t MAX_LIST_RAYS;
+// Where the failure code of a block of a record set lies in the control block, as 32-bit words from its start: word
+// base + (block / div) row + block % div.  The ONE place that knows which array of DevCtl a kind's kernel writes: the host
+// reads a fetched control block through it (record_code, rt_plan.hip), rt_history_finish_kernel the one on the device.
+struct CodeSlot {
+    unsigned base = 0, div = 1, row = 0;
+    unsigned word(int block) const { return base + ((unsigned) block / div) * row + (unsigned) block % div; }
+};
+inline CodeSlot record_code_slot(const RecordSet &R)
+{
+    constexpr unsigned W = sizeof(unsigned);
+    const unsigned all   = 1u << 30; // (a kind with one row: block / div is 0)
+    switch (R.kind) {
+    case REC_SEEDS: return { (unsigned) (offsetof(rt::DevCtl, seed_code) / W), all, 0 };
+    case REC_ASE_SEEDS: return { (unsigned) (offsetof(rt::DevCtl, rec_code) / W), all, 0 };
+    case REC_SCAN: return { (unsigned) (offsetof(rt::DevCtl, len_code) / W), all, 0 };
+    case REC_SCAN_SEEDS: return { (unsigned) (offsetof(rt::DevCtl, seed_len_code) / W), (unsigned) R.L, RT_N_SCAN_MAX };
+    case REC_SCAN_ASE_SEEDS: return { (unsigned) (offsetof(rt::DevCtl, rec_len_code) / W), (unsigned) R.L, RT_N_SCAN_MAX };
+    default: return { (unsigned) (offsetof(rt::DevCtl, failure_code) / W), all, 0 }; // (block 0: the run's code)
+    }
+}
 
 // ---- rt_raygrid.hip ----------------------------------------------------------------------------------
 struct GridGuess {
@@ -261,5 +307,11 @@ int launch_selftest(unsigned long long *counts_dev);
 int launch_zero3(hipStream_t stream, void *a, size_t a_bytes, void *b, size_t b_bytes, void *c, size_t c_bytes);
 // ... and four (a step run into the caller's E_v and nf: E_v, nf, I_ang, control block)
 int launch_zero4(hipStream_t stream, void *a, size_t a_bytes, void *b, size_t b_bytes, void *c, size_t c_bytes, void *d, size_t d_bytes);
+
+// ---- rt_history.hip ----------------------------------------------------------------------------------
+// wait for the last append of the plan's history, if one is still pending (no history, nothing pending: nothing)
+void history_wait(rt_hip_plan *p);
+// ... and give the history back to the pool (rt_hip_plan_destroy)
+void history_release(rt_hip_plan *p);
 
 } // namespace rtr
