@@ -460,7 +460,8 @@ int rt_hip_plan_set_step_one_launch(rt_hip_plan *plan, int on);
  *   checking repeat of a run with error -2 / -3), so that a later fetch of that run serves ITS tables' result; device
  *   buffers of that run stay valid.
  *   Then: scan, validate, pack (raytrace-miniapp_amd/csrc/rt_tables.hip).  No run ever reads tables whose scan has not
- *   passed: a non-finite index of refraction -- on which the integrator would never advance -- a NULL pointer or a wrong N
+ *   passed: an index of refraction that is not finite as the float the march rounds it to (a NaN, an infinity, a double
+ *   beyond the largest float; rt_hip_plan_create refuses the same) -- on which the integrator would never advance -- a NULL pointer or a wrong N
  *   is RT_ERR_ARG and leaves every table of the plan untouched.  The scan recomputes, bit for bit, the four facts
  *   rt_hip_plan_create derives from the tables and every run is chosen by (rt_hip_plan_table_flags).
  *   update_gain_dev: device pointers, each checked to be device memory of the plan's device (anything else is

@@ -67,6 +67,28 @@ class Oracle:
         L.rt_oracle_cross_setup.argtypes = [C.c_size_t, cabi.c_float_p, cabi.c_double_p, cabi.c_double_p, P(C.c_uint8),
                                             cabi.c_float_p]
         L.rt_oracle_cross_setup.restype = C.c_int
+        L.rt_oracle_cell_setup.argtypes = [C.c_size_t, C.c_int, P(cabi.RtGain), C.c_int, cabi.c_float_p, P(C.c_int32),
+                                           P(C.c_int32), cabi.c_double_p, cabi.c_float_p]
+        L.rt_oracle_cell_setup.restype = C.c_int
+
+    def cell_setup(self, gain, use_emis: bool, pos, ii):
+        """The head of a cell step per case: the escape test and the cell set-up of the march's cell loop (Helper.h:465-497).
+        gain: (RtGain * N) (entry 0 is not read); pos [n][5] float32 = px, py, sz, z, z_stop; ii [n] int32, the length of each
+        case -> dict(escaped, enters [n] bool; k1, k2, c00 [n] int32; mirror [n] bool; cell [n][4] = xc0, xc1, yc0, yc1;
+        nc [n][4] = n00, n10, n01, n11; g0, E0, dzrem [n] float32; box [n][4] float32).  Zeros where a case escapes."""
+        pos = np.ascontiguousarray(pos, dtype=np.float32)
+        ii = np.ascontiguousarray(ii, dtype=np.int32)
+        n = pos.shape[0]
+        assert pos.shape == (n, 5) and ii.shape == (n,)
+        io, do, fo = np.zeros((n, 6), np.int32), np.zeros((n, 8), np.float64), np.zeros((n, 7), np.float32)
+        i32 = lambda a: a.ctypes.data_as(P(C.c_int32))
+        rc = self.lib.rt_oracle_cell_setup(n, len(gain), gain, 1 if use_emis else 0, cabi._fp(pos), i32(ii), i32(io),
+                                           cabi._dp(do), cabi._fp(fo))
+        if rc != 0:
+            raise RuntimeError(f"rt_oracle_cell_setup failed: {rc}")
+        return dict(escaped=io[:, 0] != 0, enters=io[:, 1] != 0, k1=io[:, 2].copy(), k2=io[:, 3].copy(), c00=io[:, 4].copy(),
+                    mirror=io[:, 5] != 0, cell=do[:, :4].copy(), nc=do[:, 4:].copy(), g0=fo[:, 0].copy(), E0=fo[:, 1].copy(),
+                    box=fo[:, 2:6].copy(), dzrem=fo[:, 6].copy())
 
     def linear_step(self, state, c: float = 0.5):
         """One integrator step per case: the loop body of step_linear_medium (Helper.h:281-311) and the loop condition

@@ -255,6 +255,13 @@ static inline void cross_setup(float px, float py, float ya, const double xc[2],
     *gy_out = gy;
 }
 
+/* Helper.h:326-327 -- the loop condition of cross_cell (the single definition: cross_cell below and the batch entry
+ * rt_oracle_cell_setup, which reports whether a cell step enters the loop at all, both call it). */
+static inline int cross_cond(float px, float ya, const float box[4], float z, float dzrem)
+{
+    return px > box[0] && px < box[1] && ya > box[2] && ya < box[3] && (double) z < 0.999 * (double) dzrem;
+}
+
 /* Helper.h:318-351 -- advance inside one cell box until the ray leaves it or
  * reaches dzrem; index gradient recomputed from the 4 corners each pass. */
 static float cross_cell(vec3f *pos, vec3f *s, float dzrem, const double xc[2], const double yc[2],
@@ -266,8 +273,7 @@ static float cross_cell(vec3f *pos, vec3f *s, float dzrem, const double xc[2], c
     const float wx = (float) (xc[1] - xc[0]);
     const float wy = (float) (yc[1] - yc[0]);
     float ya       = mirror_y ? fabsf(pos->y) : pos->y;
-    while (pos->x > box[0] && pos->x < box[1] && ya > box[2] && ya < box[3] &&
-           (double) z < 0.999 * (double) dzrem) {
+    while (cross_cond(pos->x, ya, box, z, dzrem)) {
         ya       = mirror_y ? fabsf(pos->y) : pos->y;
         float n0, gx, gy;
         cross_setup(pos->x, pos->y, ya, xc, yc, wx, wy, nc, mirror_y, &n0, &gx, &gy);
@@ -340,6 +346,146 @@ int rt_oracle_cross_setup(size_t n_cases, const float *pos, const double *cell, 
     return 0;
 }
 
+/* Helper.h:445-453 -- the plasma box of one length as floats; a grid that starts at y >= 0 is mirrored about y = 0. */
+typedef struct {
+    float lo_x, hi_x, lo_y, hi_y;
+    int mirror_y;
+} plasma_box;
+
+static inline plasma_box plasma_box_of(const rt_gain *g)
+{
+    const uint32_t Nx = (uint32_t) g->Nx, Ny = (uint32_t) g->Ny;
+    plasma_box b;
+    b.lo_x     = (float) g->x[0];
+    b.hi_x     = (float) g->x[Nx - 1];
+    b.lo_y     = (float) g->y[0];
+    b.hi_y     = (float) g->y[Ny - 1];
+    b.mirror_y = 0;
+    if (b.lo_y >= 0) {
+        b.lo_y     = -b.hi_y;
+        b.mirror_y = 1;
+    }
+    return b;
+}
+
+/* What the head of a cell step leaves for cross_cell and for the sums behind it. */
+typedef struct {
+    uint32_t k1, k2, c00;
+    double xc[2], yc[2], nc[4];
+    float g0, E0, box[4];
+} cell_state;
+
+/* Helper.h:465-497 -- the head of the cell loop's body: the escape test, then the cell the ray stands in, its corner
+ * coordinates and indices, g0 and E0 at the ray and the cell box with its 10 % margin (the single definition: march_impl
+ * below and the batch entry rt_oracle_cell_setup both call it).  Returns 1 when the ray has escaped (cs is not written). */
+static inline int cell_setup(const rt_gain *g, const plasma_box *pb, int use_emis, vec3f *pos_io, const vec3f *s_in,
+                             cell_state *cs)
+{
+    const uint32_t Nx = (uint32_t) g->Nx, Ny = (uint32_t) g->Ny;
+    const float lo_x = pb->lo_x, hi_x = pb->hi_x, lo_y = pb->lo_y, hi_y = pb->hi_y;
+    const int mirror_y = pb->mirror_y;
+    vec3f pos = *pos_io;
+    const vec3f s = *s_in;
+    if (pos.x < lo_x || pos.x > hi_x || pos.y < lo_y || pos.y > hi_y ||
+        (double) (s.z * s.z) < 0.01) {
+        return 1;
+    }
+    float ya    = mirror_y ? fabsf(pos.y) : pos.y;
+    uint32_t k1 = interval_index(g->x, Nx, (double) pos.x);
+    uint32_t k2 = interval_index(g->y, Ny, (double) ya);
+    uint32_t c00 = (k1 - 1) + (k2 - 1) * Nx;
+    uint32_t c10 = k1 + (k2 - 1) * Nx;
+    uint32_t c01 = (k1 - 1) + k2 * Nx;
+    uint32_t c11 = k1 + k2 * Nx;
+    double xc[2] = { g->x[k1 - 1], g->x[k1] };
+    double yc[2] = { g->y[k2 - 1], g->y[k2] };
+    double nc[4] = { g->n[c00], g->n[c10], g->n[c01], g->n[c11] };
+    float u = (float) (((double) pos.x - g->x[k1 - 1]) / (g->x[k1] - g->x[k1 - 1]));
+    float v = (float) (((double) ya - g->y[k2 - 1]) / (g->y[k2] - g->y[k2 - 1]));
+    float g0 = lerp2(u, v, g->g0[c00], g->g0[c10], g->g0[c01], g->g0[c11]);
+    float E0 = 0.0f;
+    if (use_emis) {
+        E0 = lerp2(u, v, g->E0[c00], g->E0[c10], g->E0[c01], g->E0[c11]);
+        E0 = E0 >= 0 ? E0 : 0.0f;
+    }
+    pos.z = 0.0f;
+    float box[4] = { (float) (xc[0] - 0.1 * (g->x[k1] - g->x[k1 - 1])),
+                     (float) (xc[1] + 0.1 * (g->x[k1] - g->x[k1 - 1])),
+                     (float) (yc[0] - 0.1 * (g->y[k2] - g->y[k2 - 1])),
+                     (float) (yc[1] + 0.1 * (g->y[k2] - g->y[k2 - 1])) };
+    if (mirror_y && k2 <= 1)
+        box[2] = -box[3];
+    *pos_io = pos;
+    cs->k1  = k1;
+    cs->k2  = k2;
+    cs->c00 = c00;
+    cs->g0  = g0;
+    cs->E0  = E0;
+    for (int t = 0; t < 2; t++) {
+        cs->xc[t] = xc[t];
+        cs->yc[t] = yc[t];
+    }
+    for (int t = 0; t < 4; t++) {
+        cs->nc[t]  = nc[t];
+        cs->box[t] = box[t];
+    }
+    return 0;
+}
+
+/* The head of a cell step per case (cell_setup above), for the device-side unit test of block [A2] of the march
+ * (tests/march_cell_inputs.py says what a case is).  pos [n][5] = px, py, sz, z, z_stop; ii [n] the length of the case, 1 <= ii
+ * < N.  iout [n][6] = escaped, enters (the loop condition of cross_cell on its first evaluation, z = 0, dzrem = z_stop - z),
+ * k1, k2, c00, mirror_y; dout [n][8] = xc[0], xc[1], yc[0], yc[1], nc[0 .. 3]; fout [n][7] = g0, E0, box[0 .. 3], dzrem.
+ * An escaped case has escaped = 1 and zeros elsewhere. */
+int rt_oracle_cell_setup(size_t n_cases, int N, const rt_gain *gain, int use_emis, const float *pos_in, const int32_t *ii,
+                         int32_t *iout, double *dout, float *fout)
+{
+    if (!gain || !pos_in || !ii || !iout || !dout || !fout || N < 2)
+        return -1;
+    for (int i = 1; i < N; i++)
+        if (gain[i].Nx < 2 || gain[i].Ny < 2 || !gain[i].x || !gain[i].y || !gain[i].n || !gain[i].g0 ||
+            (use_emis && !gain[i].E0))
+            return -1;
+    for (size_t i = 0; i < n_cases; i++) {
+        const float *in = pos_in + 5 * i;
+        int32_t *io     = iout + 6 * i;
+        double *dd      = dout + 8 * i;
+        float *fo       = fout + 7 * i;
+        memset(io, 0, sizeof(int32_t) * 6);
+        memset(dd, 0, sizeof(double) * 8);
+        memset(fo, 0, sizeof(float) * 7);
+        if (ii[i] < 1 || ii[i] >= N)
+            return -1;
+        const rt_gain *g    = &gain[ii[i]];
+        const plasma_box pb = plasma_box_of(g);
+        vec3f pos = { in[0], in[1], 0.0f }, s = { 0.0f, 0.0f, in[2] };
+        cell_state cs;
+        if (cell_setup(g, &pb, use_emis, &pos, &s, &cs)) {
+            io[0] = 1;
+            continue;
+        }
+        const float dzrem = in[4] - in[3];
+        const float ya    = pb.mirror_y ? fabsf(pos.y) : pos.y;
+        io[1]             = cross_cond(pos.x, ya, cs.box, 0.0f, dzrem);
+        io[2]             = (int32_t) cs.k1;
+        io[3]             = (int32_t) cs.k2;
+        io[4]             = (int32_t) cs.c00;
+        io[5]             = pb.mirror_y;
+        dd[0]             = cs.xc[0];
+        dd[1]             = cs.xc[1];
+        dd[2]             = cs.yc[0];
+        dd[3]             = cs.yc[1];
+        for (int t = 0; t < 4; t++) {
+            dd[4 + t] = cs.nc[t];
+            fo[2 + t] = cs.box[t];
+        }
+        fo[0] = cs.g0;
+        fo[1] = cs.E0;
+        fo[6] = dzrem;
+    }
+    return 0;
+}
+
 /*
  * March one ray (Helper.h:404-533 minus the seed lookup).  Fills
  * gvl/evl/ivl [L][3] (L = N-1), the exit ray and flags.
@@ -380,55 +526,23 @@ static int march_impl(const rt_ray *ray, int N, float dz0, const rt_gain *gain, 
     for (int seg = 0; seg < L && !escaped; seg++) {
         const int ii      = (method == 1) ? N - seg - 1 : seg + 1;
         const rt_gain *g  = &gain[ii];
-        const uint32_t Nx = (uint32_t) g->Nx, Ny = (uint32_t) g->Ny;
-        float lo_x = (float) g->x[0], hi_x = (float) g->x[Nx - 1];
-        float lo_y = (float) g->y[0], hi_y = (float) g->y[Ny - 1];
-        int mirror_y = 0;
-        if (lo_y >= 0) {
-            lo_y     = -hi_y;
-            mirror_y = 1;
-        }
+        const plasma_box pb = plasma_box_of(g);
         float z = 0.0f;
         for (int iz = 0; iz < RT_N_SUB; iz++) {
             const int is = (method == 1) ? RT_N_SUB - iz - 1 : iz;
             float z_stop = (dz0 * ((float) iz + 1.0f) / RT_N_SUB);
             while (z < 0.995f * z_stop) {
-                if (pos.x < lo_x || pos.x > hi_x || pos.y < lo_y || pos.y > hi_y ||
-                    (double) (s.z * s.z) < 0.01) {
+                cell_state cs;
+                if (cell_setup(g, &pb, use_emis, &pos, &s, &cs)) {
                     escaped = 1;
                     break;
                 }
-                float ya    = mirror_y ? fabsf(pos.y) : pos.y;
-                uint32_t k1 = interval_index(g->x, Nx, (double) pos.x);
-                uint32_t k2 = interval_index(g->y, Ny, (double) ya);
-                uint32_t c00 = (k1 - 1) + (k2 - 1) * Nx;
-                uint32_t c10 = k1 + (k2 - 1) * Nx;
-                uint32_t c01 = (k1 - 1) + k2 * Nx;
-                uint32_t c11 = k1 + k2 * Nx;
-                double xc[2] = { g->x[k1 - 1], g->x[k1] };
-                double yc[2] = { g->y[k2 - 1], g->y[k2] };
-                double nc[4] = { g->n[c00], g->n[c10], g->n[c01], g->n[c11] };
-                float u = (float) (((double) pos.x - g->x[k1 - 1]) / (g->x[k1] - g->x[k1 - 1]));
-                float v = (float) (((double) ya - g->y[k2 - 1]) / (g->y[k2] - g->y[k2 - 1]));
-                float g0 = lerp2(u, v, g->g0[c00], g->g0[c10], g->g0[c01], g->g0[c11]);
-                float E0 = 0.0f;
-                if (use_emis) {
-                    E0 = lerp2(u, v, g->E0[c00], g->E0[c10], g->E0[c01], g->E0[c11]);
-                    E0 = E0 >= 0 ? E0 : 0.0f;
-                }
-                pos.z = 0.0f;
-                float box[4] = { (float) (xc[0] - 0.1 * (g->x[k1] - g->x[k1 - 1])),
-                                 (float) (xc[1] + 0.1 * (g->x[k1] - g->x[k1 - 1])),
-                                 (float) (yc[0] - 0.1 * (g->y[k2] - g->y[k2 - 1])),
-                                 (float) (yc[1] + 0.1 * (g->y[k2] - g->y[k2 - 1])) };
-                if (mirror_y && k2 <= 1)
-                    box[2] = -box[3];
-                float path = cross_cell(&pos, &s, z_stop - z, xc, yc, box, nc, mirror_y, c, &it2, &it1);
+                float path = cross_cell(&pos, &s, z_stop - z, cs.xc, cs.yc, cs.box, cs.nc, pb.mirror_y, c, &it2, &it1);
                 z += fabsf(pos.z);
                 const int slot = (ii - 1) * RT_N_SUB + is;
-                gvl[slot] += g0 * path;
-                evl[slot] += E0 * path;
-                ivl[slot] = (int32_t) c00;
+                gvl[slot] += cs.g0 * path;
+                evl[slot] += cs.E0 * path;
+                ivl[slot] = (int32_t) cs.c00;
                 steps++;
             }
             if (path) { /* Helper.h:505-511: position at the end of every sub-segment */

@@ -53,6 +53,9 @@ int rt_oracle_linear_step(size_t n_cases, const float *state_in, float c, float 
                           uint8_t *run_full, uint8_t *winner, float *cand);
 int rt_oracle_cross_setup(size_t n_cases, const float *pos, const double *cell, const double *nc, const uint8_t *mirror,
                           float *out);
+/* ... and the head of a cell step per case: the escape test and the cell set-up of march's cell loop, up to the cell box */
+int rt_oracle_cell_setup(size_t n_cases, int N, const rt_gain *gain, int use_emis, const float *pos_in, const int32_t *ii,
+                         int32_t *iout, double *dout, float *fout);
 
 int rt_oracle_calc_seed(const rt_seed *seed, size_t n, const double *pts, double *Iv, double *axis);
 

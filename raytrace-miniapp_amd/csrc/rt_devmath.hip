@@ -3,8 +3,9 @@
 // rt_seed_tab_kernel itself), each behind one elementwise kernel, and the two wave primitives of the step deposit (the E_v
 // wave sum rt_step_evsum.inc, the segmented scan rt_wave_runs.inc / rt_wave_runscan.inc), each behind a kernel of one
 // work-group, and the float32 blocks of the march -- one integrator step (rt_march_step.inc, in the four instances the product
-// launches), the cross-cell set-up (rt_march_xsetup.inc) and the float primitives of rt_math.h -- one case per lane in whole
-// waves, so that tests/test_gpu_devmath.py, tests/test_gpu_march_blocks.py and
+// launches), the cross-cell set-up (rt_march_xsetup.inc), the escape test and cell set-up (rt_march_cell.inc, gathering from
+// LDS and from global memory) and the float primitives of rt_math.h -- one case per lane in whole
+// waves, so that tests/test_gpu_devmath.py, tests/test_gpu_march_blocks.py, tests/test_gpu_march_cell.py and
 // tests/test_gpu_seed_profiles.py can run them on a device on inputs of their own choosing.  Builds to librt_hip_devmath.so with the product's flags; nothing
 // of it is linked into librt_hip.so.
 //
@@ -14,9 +15,13 @@
 // fill the product's kernels run -- and __syncthreads() before the first use.
 #include "rt_freq.hip" // (includes rt_march.hip), as rt_launch.hip has it
 
+#include "rt_blob_pack.h" // the host-side packing of the march blob, as rt_plan.hip has it
+
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <cstring>
+#include <vector>
 
 namespace {
 
@@ -325,6 +330,104 @@ __global__ void __launch_bounds__(DM_BLOCK) dm_march_xsetup_kernel(const float *
             out[3 * i]     = n0;
             out[3 * i + 1] = gxn;
             out[3 * i + 2] = gyn;
+        }
+    }
+}
+
+// rt_march_cell.inc as march_wave includes it: the escape test and the cell set-up, block [A2].  blob: the march blob as
+// rt_hip_plan_create packs it (rt_blob_pack.h), blob_bytes a multiple of 16; LDS_TAB copies it to dynamic LDS, which starts at
+// LDS address 0 (this kernel has no static LDS: the fragment's ds_read_b128 gather relies on it, as in rt_march_kernel), and the
+// gather is the product's; otherwise the blob is read where it lies.  fin [n][5] = px, py, sz, z, z_stop; len [n] = the length
+// ii of the case (checked by the host entry).  Every case starts from the same lane state -- the one below -- so that what
+// a lane leaves untouched (an escaping lane: everything but `escaped`) is known.
+// iout [n][DM_CELL_I] = escaped, st, c00, mirror, second gather taken, steps, cell_last, 0;
+// fout [n][DM_CELL_F] = g0, E0, dzrem, ix1.xyzw, iy1.xyzw, f00, f10, f01, f11, z, gacc, eacc, pz, zc, path;
+// dout [n][DM_CELL_D] = ix0.xy, iy0.xy, dnx0, dnx1, dny0, dny1.
+// The second-gather flag is observed, not derived: bisect_interval is called on that arm of the fragment and nowhere else, and
+// inside the include its name also raises the flag (a macro does not expand inside its own expansion).
+enum : int { DM_CELL_IN = 5, DM_CELL_I = 8, DM_CELL_F = 21, DM_CELL_D = 8 };
+template <bool LDS_TAB>
+__global__ void __launch_bounds__(DM_BLOCK) dm_march_cell_kernel(const unsigned char *blob, unsigned blob_bytes, int use_emis_in,
+                                                                const float *fin, const int *len, int *iout, float *fout, double *dout,
+                                                                size_t n_cases)
+{
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    if (LDS_TAB) {
+        const uint4 *src = reinterpret_cast<const uint4 *>(blob);
+        uint4 *dst       = reinterpret_cast<uint4 *>(lds_raw);
+        for (unsigned i = threadIdx.x; i < blob_bytes / 16; i += blockDim.x)
+            dst[i] = src[i];
+        __syncthreads();
+    }
+    const unsigned char *tab = LDS_TAB ? lds_raw : blob;
+    const BlobGain *hdr      = reinterpret_cast<const BlobGain *>(tab);
+    const unsigned lds_base  = LDS_TAB ? (unsigned) (size_t) (__attribute__((address_space(3))) unsigned char *) lds_raw : 0u;
+    const bool use_emis      = use_emis_in != 0;
+    DmMarchDiag diag;
+    const size_t stride = (size_t) gridDim.x * blockDim.x;
+    const size_t padded = dm_padded(n_cases);
+    for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < padded; i += stride) {
+        const size_t c = i < n_cases ? i : n_cases - 1;
+        const float px = fin[DM_CELL_IN * c], py = fin[DM_CELL_IN * c + 1], sz = fin[DM_CELL_IN * c + 2];
+        float z = fin[DM_CELL_IN * c + 3];
+        const float z_stop = fin[DM_CELL_IN * c + 4];
+        const BlobGain G   = hdr[len[c]];
+        // the lane state block [A2] writes, as march_wave declares it
+        int st = ST_CELL, c00 = -1, cell_last = -1;
+        unsigned steps = 0;
+        bool escaped = false, mirror = false, regather = false;
+        float f00 = 1, f10 = 1, f01 = 1, f11 = 1;
+        double dnx0 = 0, dnx1 = 0, dny0 = 0, dny1 = 0;
+        f64x2 ix0 = { 0.0, 1.0 }, iy0 = { 0.0, 1.0 };
+        f32x4 ix1 = { 1.0f, 0.0f, 0.0f, 0.0f }, iy1 = { 1.0f, 0.0f, 0.0f, 0.0f };
+        float g0 = 0, E0 = 0, gacc = 0, eacc = 0;
+        float dzrem = 0, zc = -1.0f, path = -1.0f, pz = -1.0f;
+        {
+#define bisect_interval(iv, n, v) (regather = true, bisect_interval(iv, n, v))
+#include "rt_march_cell.inc"
+#undef bisect_interval
+        }
+        if (i < n_cases) {
+            int *io    = iout + DM_CELL_I * i;
+            float *fo  = fout + DM_CELL_F * i;
+            double *dd = dout + DM_CELL_D * i;
+            io[0]      = escaped ? 1 : 0;
+            io[1]      = st;
+            io[2]      = c00;
+            io[3]      = mirror ? 1 : 0;
+            io[4]      = regather ? 1 : 0;
+            io[5]      = (int) steps;
+            io[6]      = cell_last;
+            io[7]      = 0;
+            fo[0]      = g0;
+            fo[1]      = E0;
+            fo[2]      = dzrem;
+            fo[3]      = ix1.x;
+            fo[4]      = ix1.y;
+            fo[5]      = ix1.z;
+            fo[6]      = ix1.w;
+            fo[7]      = iy1.x;
+            fo[8]      = iy1.y;
+            fo[9]      = iy1.z;
+            fo[10]     = iy1.w;
+            fo[11]     = f00;
+            fo[12]     = f10;
+            fo[13]     = f01;
+            fo[14]     = f11;
+            fo[15]     = z;
+            fo[16]     = gacc;
+            fo[17]     = eacc;
+            fo[18]     = pz;
+            fo[19]     = zc;
+            fo[20]     = path;
+            dd[0]      = ix0.x;
+            dd[1]      = ix0.y;
+            dd[2]      = iy0.x;
+            dd[3]      = iy0.y;
+            dd[4]      = dnx0;
+            dd[5]      = dnx1;
+            dd[6]      = dny0;
+            dd[7]      = dny1;
         }
     }
 }
@@ -731,6 +834,101 @@ DM_API int rt_devmath_march_xsetup(const float *fin, const double *din, const un
     DM_TRY(B.out((void **) &dout, n * 3 * sizeof(float)));
     dm_march_xsetup_kernel<<<grid_for(n), DM_BLOCK>>>(dfin, ddin, dmir, dout, n);
     return B.release(finish(out, dout, n * 3 * sizeof(float)));
+}
+
+// The march blob of the tables gain[1 .. N-1] (gain[0] is not read) as rt_hip_plan_create packs it: the same function,
+// rt_blob_pack.h.  Host code only -- no device is touched.  Tables that rt_hip_plan_create refuses (a grid not strictly
+// increasing or with a spacing below 1e-30, an index not finite as a float) are refused here.
+static int pack_march_blob(int N, const rt_gain *gain, std::vector<unsigned char> &blob)
+{
+    if (N < 2 || !gain)
+        return (int) hipErrorInvalidValue;
+    for (int i = 1; i < N; i++)
+        if (gain[i].Nx < 2 || gain[i].Ny < 2 || !gain[i].x || !gain[i].y || !gain[i].n || !gain[i].g0)
+            return (int) hipErrorInvalidValue;
+    blob.assign((sizeof(BlobGain) * (size_t) N + 15) / 16 * 16, 0);
+    bool tiny_spacing = false, bad_index = false;
+    for (int i = 1; i < N; i++)
+        (void) blob_pack_length(blob, (size_t) i, gain[i].Nx, gain[i].Ny, gain[i].x, gain[i].y, gain[i].n, gain[i].g0, gain[i].E0,
+                                tiny_spacing, bad_index);
+    return tiny_spacing || bad_index ? (int) hipErrorInvalidValue : 0;
+}
+
+// every record a case of length i can reach lies inside the blob: the header's counts and offsets against its size
+static bool blob_length_in_bounds(const std::vector<unsigned char> &blob, int i)
+{
+    BlobGain h;
+    memcpy(&h, blob.data() + sizeof(BlobGain) * (size_t) i, sizeof(h));
+    const size_t size = blob.size();
+    auto inside       = [size](int off, size_t bytes) { return off >= 0 && off % 16 == 0 && (size_t) off <= size && bytes <= size - (size_t) off; };
+    return h.Nx >= 2 && h.Ny >= 2 && inside(h.off_ix, sizeof(Interval) * (size_t) h.Nx) &&
+           inside(h.off_iy, sizeof(Interval) * (size_t) h.Ny) && inside(h.off_node, sizeof(Node) * (size_t) h.Nx * (size_t) h.Ny);
+}
+
+// the blob itself, for the host-side tests of its records: *bytes = its size; copied to out when out != NULL and cap suffices
+DM_API int rt_devmath_march_blob(int N, const rt_gain *gain, unsigned char *out, size_t cap, size_t *bytes)
+{
+    std::vector<unsigned char> blob;
+    const int rc = pack_march_blob(N, gain, blob);
+    if (rc || !bytes)
+        return rc ? rc : (int) hipErrorInvalidValue;
+    *bytes = blob.size();
+    if (out) {
+        if (cap < blob.size())
+            return (int) hipErrorInvalidValue;
+        memcpy(out, blob.data(), blob.size());
+    }
+    return 0;
+}
+
+// The escape test and the cell set-up of the march per case (rt_march_cell.inc), on the march blob of gain[1 .. N-1]; lds_tab:
+// the instance that gathers from LDS.  fin [n][5], len [n], iout [n][8], fout [n][21], dout [n][8] as dm_march_cell_kernel says.
+// Nothing is launched unless every len names a length of the blob, every offset of the headers lies inside it and (lds_tab)
+// the blob fits the LDS a work-group may have.
+DM_API int rt_devmath_march_cell(int lds_tab, int N, const rt_gain *gain, int use_emis, const float *fin, const int *len, size_t n,
+                                 int *iout, float *fout, double *dout)
+{
+    std::vector<unsigned char> blob;
+    int rc = pack_march_blob(N, gain, blob);
+    if (rc)
+        return rc;
+    if (n < 1 || !fin || !len || !iout || !fout || !dout || blob.size() % 16 != 0 || blob.size() >= (1ull << 31))
+        return (int) hipErrorInvalidValue;
+    for (int i = 1; i < N; i++)
+        if (!blob_length_in_bounds(blob, i) || (use_emis && !gain[i].E0))
+            return (int) hipErrorInvalidValue;
+    for (size_t c = 0; c < n; c++)
+        if (len[c] < 1 || len[c] >= N)
+            return (int) hipErrorInvalidValue;
+    if (lds_tab) {
+        int dev = 0, limit = 0;
+        DM_TRY(hipGetDevice(&dev));
+        DM_TRY(hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+        if (limit < 1 || blob.size() > (size_t) limit)
+            return (int) hipErrorInvalidValue;
+        DM_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(dm_march_cell_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, limit));
+    }
+    Bufs B;
+    unsigned char *dblob;
+    float *dfin, *dfout;
+    int *dlen, *diout;
+    double *ddout;
+    DM_TRY(B.in((void **) &dblob, blob.data(), blob.size()));
+    DM_TRY(B.in((void **) &dfin, fin, n * DM_CELL_IN * sizeof(float)));
+    DM_TRY(B.in((void **) &dlen, len, n * sizeof(int)));
+    DM_TRY(B.out((void **) &diout, n * DM_CELL_I * sizeof(int)));
+    DM_TRY(B.out((void **) &dfout, n * DM_CELL_F * sizeof(float)));
+    DM_TRY(B.out((void **) &ddout, n * DM_CELL_D * sizeof(double)));
+    if (lds_tab)
+        dm_march_cell_kernel<true><<<grid_for(n), DM_BLOCK, blob.size()>>>(dblob, (unsigned) blob.size(), use_emis, dfin, dlen, diout, dfout, ddout, n);
+    else
+        dm_march_cell_kernel<false><<<grid_for(n), DM_BLOCK>>>(dblob, (unsigned) blob.size(), use_emis, dfin, dlen, diout, dfout, ddout, n);
+    rc = finish(iout, diout, n * DM_CELL_I * sizeof(int));
+    if (rc)
+        return B.release(rc);
+    DM_TRY(hipMemcpy(fout, dfout, n * DM_CELL_F * sizeof(float), hipMemcpyDeviceToHost));
+    DM_TRY(hipMemcpy(dout, ddout, n * DM_CELL_D * sizeof(double), hipMemcpyDeviceToHost));
+    return B.release(0);
 }
 
 // a float primitive of rt_math.h elementwise: which = 0 inv_norm(a), 1 div_by_recip(a, b, y), 2 div_by_recip_signed(a, b, y),

@@ -1216,113 +1216,7 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
             }
             diag.mark(1); // [A1]
             if ((st == ST_CELL) & in_seg) {
-                // [A2] escape test + cell setup (Helper.h:465-497)
-                // (double)(sz*sz) < 0.01 (Helper.h:466) <=> sz*sz <= 0.01f: 0.01f is the largest float below 0.01
-                if ((px < G.lo_x) | (px > G.hi_x) | (py < G.lo_y) | (py > G.hi_y) | (sz * sz <= 0.01f)) {
-                    escaped = true; // its slot is committed by [A1] next iteration
-                } else {
-                    mirror              = G.mirror_y != 0;
-                    const Interval *ivx = reinterpret_cast<const Interval *>(tab + G.off_ix);
-                    const Interval *ivy = reinterpret_cast<const Interval *>(tab + G.off_iy);
-                    // (records are addressed by 32-bit byte offsets from the start of the blob: no
-                    // 64-bit multiplies for what is an LDS address)
-                    // One round of gathers per cell: two 48-byte interval records and four 16-byte corner nodes (the
-                    // two nodes of a grid row are neighbours), ten 16-byte reads issued together.  In the LDS variant
-                    // they are written as ds_read_b128 instructions whose results ARE the lane-state registers
-                    // (ix0, ix1, iy0, iy1) or are consumed where they land: left to itself the compiler reads the tail
-                    // of a record as ds_read_b96 and a node as b64 + b32 + b32 (issue cost per LDS instruction: b32 /
-                    // b64 5, b128 10, b96 20 VALU-equivalent ticks -- tools/ubench), and held to whole 16-byte reads
-                    // by empty asm statements (round 3) it paid for them with 34 register copies per cell set-up.
-                    f64x2 tx, ty;            // {hi, rh} of the two intervals
-                    u32x4 q00, q10, q01, q11; // corner nodes {n (f64) | g0 | E0}
-                    auto gather = [&](int k1, int k2, int c) {
-                        const unsigned ox = (unsigned) G.off_ix + (unsigned) k1 * (unsigned) sizeof(Interval);
-                        const unsigned oy = (unsigned) G.off_iy + (unsigned) k2 * (unsigned) sizeof(Interval);
-                        const unsigned oa = (unsigned) G.off_node + (unsigned) c * (unsigned) sizeof(Node);
-                        const unsigned ob = oa + (unsigned) G.Nx * (unsigned) sizeof(Node);
-                        if (LDS_TAB) {
-                            // (lds_raw starts at LDS address 0: the kernel has no static LDS; the reads complete
-                            // inside the statement, so the compiler's own wait counters stay right)
-                            asm volatile("ds_read_b128 %0, %10\n\t"
-                                         "ds_read_b128 %1, %10 offset:16\n\t"
-                                         "ds_read_b128 %2, %10 offset:32\n\t"
-                                         "ds_read_b128 %3, %11\n\t"
-                                         "ds_read_b128 %4, %11 offset:16\n\t"
-                                         "ds_read_b128 %5, %11 offset:32\n\t"
-                                         "ds_read_b128 %6, %12\n\t"
-                                         "ds_read_b128 %7, %12 offset:16\n\t"
-                                         "ds_read_b128 %8, %13\n\t"
-                                         "ds_read_b128 %9, %13 offset:16\n\t"
-                                         "s_waitcnt lgkmcnt(0)"
-                                         : "=&v"(ix0), "=&v"(ix1), "=&v"(tx), "=&v"(iy0), "=&v"(iy1), "=&v"(ty), "=&v"(q00), "=&v"(q10),
-                                           "=&v"(q01), "=&v"(q11)
-                                         : "v"(lds_base + ox), "v"(lds_base + oy), "v"(lds_base + oa), "v"(lds_base + ob));
-                        } else {
-                            const unsigned char *t = tab;
-                            ix0 = *reinterpret_cast<const f64x2 *>(t + ox);
-                            ix1 = *reinterpret_cast<const f32x4 *>(t + ox + 16);
-                            tx  = *reinterpret_cast<const f64x2 *>(t + ox + 32);
-                            iy0 = *reinterpret_cast<const f64x2 *>(t + oy);
-                            iy1 = *reinterpret_cast<const f32x4 *>(t + oy + 16);
-                            ty  = *reinterpret_cast<const f64x2 *>(t + oy + 32);
-                            q00 = *reinterpret_cast<const u32x4 *>(t + oa);
-                            q10 = *reinterpret_cast<const u32x4 *>(t + oa + 16);
-                            q01 = *reinterpret_cast<const u32x4 *>(t + ob);
-                            q11 = *reinterpret_cast<const u32x4 *>(t + ob + 16);
-                        }
-                    };
-                    auto node_n = [](const u32x4 &q) { return __hiloint2double((int) q.y, (int) q.x); };
-                    const float ya      = mirror ? fabsf(py) : py;
-                    const double pxd = (double) px, yad = (double) ya;
-                    // one round of gathers on the guessed cell: two interval records, four nodes
-                    int k1     = guess_interval(G.Nx, G.x0f, G.inv_hxf, px);
-                    int k2     = guess_interval(G.Ny, G.y0f, G.inv_hyf, ya);
-                    c00        = (k1 - 1) + (k2 - 1) * G.Nx;
-                    gather(k1, k2, c00);
-                    const bool ok = ((k1 == 1) | (ix0.x < pxd)) & ((k1 == G.Nx - 1) | (tx.x >= pxd)) &
-                                    ((k2 == 1) | (iy0.x < yad)) & ((k2 == G.Ny - 1) | (ty.x >= yad));
-                    if (!ok) {
-                        k1  = bisect_interval(ivx, G.Nx, pxd);
-                        k2  = bisect_interval(ivy, G.Ny, yad);
-                        c00 = (k1 - 1) + (k2 - 1) * G.Nx;
-                        gather(k1, k2, c00);
-                    }
-                    const double n00 = node_n(q00), n10 = node_n(q10), n01 = node_n(q01), n11 = node_n(q11);
-                    f00       = (float) n00;
-                    f10       = (float) n10;
-                    f01       = (float) n01;
-                    f11       = (float) n11;
-                    dnx0      = n10 - n00;
-                    dnx1      = n11 - n01;
-                    dny0      = n01 - n00;
-                    dny1      = n11 - n10;
-                    const float u = (float) div_by_recip<true>(pxd - ix0.x, tx.x - ix0.x, tx.y);
-                    const float v = (float) div_by_recip<true>(yad - iy0.x, ty.x - iy0.x, ty.y);
-                    g0            = lerp2(u, v, __uint_as_float(q00.z), __uint_as_float(q10.z), __uint_as_float(q01.z),
-                                          __uint_as_float(q11.z));
-                    E0            = 0.0f;
-                    if (use_emis) {
-                        E0 = lerp2(u, v, __uint_as_float(q00.w), __uint_as_float(q10.w), __uint_as_float(q01.w),
-                                   __uint_as_float(q11.w));
-                        E0 = E0 >= 0 ? E0 : 0.0f;
-                    }
-                    pz    = 0.0f;
-                    zc    = 0.0f;
-                    path  = 0.0f;
-                    dzrem = z_stop - z;
-                    // Helper.h:327 with zc = 0: 0.0 < 0.999 * (double) dzrem <=> dzrem > 0 (no underflow in double)
-                    if ((px > ix1.y) & (px < ix1.z) & (ya > iy1.y) & (ya < iy1.z) & (dzrem > 0.0f)) {
-                        st = ST_XSETUP;
-                    } else {
-                        // no cross-cell iteration at all: the cell step still counts (Helper.h:498-503)
-                        z += fabsf(pz);
-                        gacc += g0 * path;
-                        eacc += E0 * path;
-                        cell_last = c00;
-                        steps++;
-                        diag.tick(2);
-                    }
-                }
+#include "rt_march_cell.inc"
             }
         }
         diag.mark(2); // [A2] (a lane that finished in [A1] stays ST_DONE: retired at the loop head, "ray finished")

@@ -7,6 +7,7 @@
 // on one queue.  No data is cached across calls (Readme.txt:43); freed device allocations and the queues
 // of a device are (rt_pool.hip).  Host code only.
 #include "rt_runtime.h"
+#include "rt_blob_pack.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -372,61 +373,8 @@ int rtr::plan_create_on(rt_hip_plan **out, hipStream_t upload_q, int device, int
     p->tab.assign((size_t) N, rt_hip_plan::TableShape());
     for (int i = 1; i < N; i++) {
         const rt_gain &g  = gain[i];
-        const size_t npix = (size_t) g.Nx * (size_t) g.Ny;
-        rt::BlobGain h;
-        memset(&h, 0, sizeof(h));
-        h.lo_x     = (float) g.x[0]; // Helper.h:445-448
-        h.hi_x     = (float) g.x[g.Nx - 1];
-        h.lo_y     = (float) g.y[0];
-        h.hi_y     = (float) g.y[g.Ny - 1];
-        h.mirror_y = 0;
-        if (h.lo_y >= 0) { // Helper.h:449-453
-            h.lo_y     = -h.hi_y;
-            h.mirror_y = 1;
-        }
-        h.Nx     = g.Nx;
-        h.Ny     = g.Ny;
-        h.x0f = (float) g.x[0];
-        h.y0f = (float) g.y[0];
-        const double ihx = (double) (g.Nx - 1) / (g.x[g.Nx - 1] - g.x[0]);
-        const double ihy = (double) (g.Ny - 1) / (g.y[g.Ny - 1] - g.y[0]);
-        h.inv_hxf        = std::isfinite(ihx) && fabs(ihx) < 1e30 ? (float) ihx : 0.0f;
-        h.inv_hyf        = std::isfinite(ihy) && fabs(ihy) < 1e30 ? (float) ihy : 0.0f;
-        // per-interval records of both axes (entry 0 unused)
-        auto put_intervals = [&](const double *gp, int n, bool mirrored) {
-            const int off = (int) blob.size();
-            blob.resize(blob.size() + sizeof(rt::Interval) * (size_t) n);
-            rt::Interval *iv = reinterpret_cast<rt::Interval *>(blob.data() + off);
-            memset(iv, 0, sizeof(rt::Interval) * (size_t) n);
-            for (int k = 1; k < n; k++) {
-                const double lo = gp[k - 1], hi = gp[k], hk = hi - lo;
-                if (!(hk >= 1e-30)) // see rt_math.h, div_by_recip<TINY_OK>; and the integrator's step limits
-                    tiny_spacing = true; // 0.1f * (float) hk must be positive (rt_march.hip, block [C])
-                iv[k].lo   = lo;
-                iv[k].hi   = hi;
-                iv[k].rh   = 1.0 / hk;
-                iv[k].rw   = 1.0 / (double) (float) hk;
-                iv[k].w    = (float) hk;
-                iv[k].b_lo = (float) (lo - 0.1 * hk);
-                iv[k].b_hi = (float) (hi + 0.1 * hk);
-                if (mirrored && k == 1)
-                    iv[k].b_lo = -iv[k].b_hi;
-            }
-            return off;
-        };
-        h.off_ix   = put_intervals(g.x, g.Nx, false);
-        h.off_iy   = put_intervals(g.y, g.Ny, h.mirror_y != 0);
-        h.off_node = (int) blob.size();
-        blob.resize(blob.size() + sizeof(rt::Node) * npix);
-        rt::Node *nd = reinterpret_cast<rt::Node *>(blob.data() + h.off_node);
-        for (size_t c = 0; c < npix; c++) { // the three gathered quantities fused per grid point
-            if (!std::isfinite(g.n[c]))
-                bad_index = true; // (the reference's integrator loop would never advance: Helper.h:279-280)
-            nd[c].n  = g.n[c];
-            nd[c].g0 = g.g0[c];
-            nd[c].E0 = g.E0 ? g.E0[c] : 0.0f;
-        }
-        memcpy(blob.data() + sizeof(rt::BlobGain) * (size_t) i, &h, sizeof(h));
+        // (the header, the interval records of both axes and the fused nodes of this length: rt_blob_pack.h)
+        const rt::BlobGain h = rt::blob_pack_length(blob, (size_t) i, g.Nx, g.Ny, g.x, g.y, g.n, g.g0, g.E0, tiny_spacing, bad_index);
         // Ranges for the short division sequences of the integrator (rt_math.h, fdiv_nr): with dn = the largest
         // difference of the index between neighbouring nodes, a step sees n within [min n - dn, max n + dn]
         // (bilinear value on the cell box with its 10 % margin, plus |r| < 0.1 w times a gradient of at most

@@ -50,7 +50,7 @@ struct TabDesc {
 struct TabPart {
     double n_lo, n_hi, dn;
     unsigned gv_finite, gv_all; // largest magnitude bits below infinity / of everything
-    unsigned bad_n;             // some n is a NaN or an infinity
+    unsigned bad_n;             // some n is a NaN or an infinity as a float (a double beyond the largest float included)
     unsigned length;
 };
 
@@ -99,7 +99,9 @@ extern "C" __global__ void __launch_bounds__(TAB_WG) rt_table_scan_kernel(const 
         const unsigned stride = (d.scan_gv0 - d.scan_n0) * TAB_WG;
         for (unsigned c = (wg - d.scan_n0) * TAB_WG + tid; c < d.cells; c += stride) {
             const double v = d.n[c];
-            bad |= ((unsigned) (__double_as_longlong(v) >> 32) & 0x7ff00000u) == 0x7ff00000u ? 1u : 0u;
+            // (not finite as the float the march rounds it to, rt_march_cell.inc: rt_hip_plan_create's test, rt_blob_pack.h --
+            // inf, NaN, and a double beyond the largest float, which rounds to inf)
+            bad |= (__float_as_uint((float) v) & 0x7f800000u) == 0x7f800000u ? 1u : 0u;
             n_lo = fmin(n_lo, v);
             n_hi = fmax(n_hi, v);
             // horizontal and vertical neighbours: column 0 has no horizontal one (c - 1 is the previous row's last node)

@@ -5,7 +5,7 @@
   Device   ctypes binding of csrc/librt_hip_devmath.so (rt_devmath.hip): the same functions on a device, and the seed-profile
            interpolation (pchip, seed_factor, seed_tab: tests/test_gpu_seed_profiles.py) and the two wave primitives of the
            step deposit (ev_sum, nf_scan), and the float32 blocks of the march (march_step, march_xsetup, f32, f64_div:
-           tests/test_gpu_march_blocks.py).  Load it only
+           tests/test_gpu_march_blocks.py; march_cell: tests/test_gpu_march_cell.py).  Load it only
            after the `hip` fixture of conftest.py has brought torch in -- one HIP runtime per process
   the high-precision reference: numpy.longdouble (>= 64 significand bits, asserted) exp / expm1, guarded by a cross-check
            of a 2 000-point subsample against mpmath (or the stdlib decimal module at 40 digits)
@@ -298,6 +298,26 @@ class Device:
         self._check(self.lib.rt_devmath_march_xsetup(_ptr(fin, ctypes.c_float), _ptr(din, ctypes.c_double), _ptr(mirror, ctypes.c_ubyte),
                                                      _ptr(out, ctypes.c_float), n), "rt_devmath_march_xsetup")
         return out
+
+    def march_cell(self, lds_tab, gain, use_emis, pos, ii):
+        """The escape test and the cell set-up of the march per case (csrc/rt_march_cell.inc) on the march blob of the tables
+        gain = (RtGain * N), packed by the product's own function; lds_tab: the instance that gathers from LDS with the
+        product's ds_read_b128 sequence, otherwise from global memory.  pos [n][5] float32 = px, py, sz, z, z_stop; ii [n] int32 ->
+        (iout [n][8] int32, fout [n][21] float32, dout [n][8] float64) as dm_march_cell_kernel lays them out
+        (tests/march_cell_inputs.py names the columns)."""
+        import importlib
+        cabi = importlib.import_module("raytrace-miniapp_amd").cabi
+        pos, ii = _f32(pos), np.ascontiguousarray(ii, dtype=np.int32)
+        n = len(ii)
+        assert n >= 1 and pos.shape == (n, 5)
+        fn = self.lib.rt_devmath_march_cell
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(cabi.RtGain), ctypes.c_int, _PF, ctypes.POINTER(ctypes.c_int),
+                       ctypes.c_size_t, ctypes.POINTER(ctypes.c_int), _PF, _PD]
+        io, fo, do = np.full((n, 8), -7, np.int32), np.full((n, 21), np.nan, np.float32), np.full((n, 8), np.nan, np.float64)
+        self._check(fn(1 if lds_tab else 0, len(gain), gain, 1 if use_emis else 0, _ptr(pos, ctypes.c_float), _ptr(ii, ctypes.c_int), n,
+                       _ptr(io, ctypes.c_int), _ptr(fo, ctypes.c_float), _ptr(do, ctypes.c_double)), "rt_devmath_march_cell")
+        return io, fo, do
 
     def f32(self, which, a, b=None, y=None):
         """A float primitive of csrc/rt_math.h elementwise: INV_NORM inv_norm(a), DIV_BY_RECIP div_by_recip(a, b, y),

@@ -77,6 +77,21 @@ def crafted_nan_index(p, i=2):
     return _one_length(p, i, " one NaN in n", n=n)
 
 
+# the smallest double that rounds to an infinite float (the midpoint of FLT_MAX and 2^128: the tie goes to even, which is
+# 2^128), and the double below it, which rounds to FLT_MAX
+FLOAT_INF_AS_FLOAT = 2.0 ** 128 - 2.0 ** 103
+LARGEST_FINITE_AS_FLOAT = float(np.nextafter(FLOAT_INF_AS_FLOAT, 0.0))
+
+
+def crafted_large_index(p, value, i=2):
+    """One node of n set to `value`, a finite double: with FLOAT_INF_AS_FLOAT the march would round it to an infinite float
+    (creation and update refuse the table like a NaN), with LARGEST_FINITE_AS_FLOAT to FLT_MAX (accepted, outside every
+    verified range)."""
+    n = p.gain[i].n.copy()
+    n[len(n) // 2] = value
+    return _one_length(p, i, f" one index of {value!r}", n=n)
+
+
 def four_lengths(p):
     """N = 4 from the lengths of a three-length problem; the second is sub-sampled to every second grid column, so that
     Nx Ny differs from length to length and is no multiple of 64."""

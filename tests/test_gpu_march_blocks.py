@@ -122,9 +122,8 @@ def test_step_outside_the_envelope_in_the_generic_instance(dev, group):
     that step_linear_medium never takes.  Block [C] divides by the reciprocal, a0 * (1 / inf) corrected by fma(-inf, 0, a0):
     NaN where a true division gives 0.  Measured on an MI355X: n and run equal the oracle's in all 517 cases, the seven other
     outputs are NaN in all 517 where the oracle's are finite.  Asserted there: n and run -- what the reference defines -- are
-    equal, and every other output is the oracle's float or a NaN, never a finite value of its own.  (A table whose index is
-    finite as a double and infinite as a float is not refused by the plan today: DESIGN.md, "How the integrator step is
-    pinned", lists it with what remains uncovered.)"""
+    equal, and every other output is the oracle's float or a NaN, never a finite value of its own.  (The plan refuses every
+    index that is not finite as a float, a double beyond the largest float included: tests/test_gpu_plan_update.py.)"""
     g = {g.name: g for g in mi.outside()}[group]
     ref = step_reference(g.name)
     bad, cnt, (out, run) = check_step(dev, "ieee", g)

@@ -276,6 +276,39 @@ def test_rejected_updates_leave_the_plan_as_it_was(hip, ase):
         same_records(rec1, ase["rec_a"], "after the rejected updates, against a fresh plan")
 
 
+def test_an_index_infinite_as_a_float_is_refused_like_a_nan(hip, ase):
+    """2^128 - 2^103 is a finite double that the march's cell set-up rounds to an infinite float: the reference takes no step
+    on it and never advances.  Creation and both update paths refuse it with the message of a NaN index and leave the plan
+    as it was; its double predecessor rounds to FLT_MAX and is accepted, with the flags of a table outside every verified
+    range.  No march runs on either value: only the unchanged plan's."""
+    a, b, rays = ase["a"], ase["b"], ase["rays"]
+    with np.errstate(over="ignore"):
+        assert np.isinf(np.float32(tv.FLOAT_INF_AS_FLOAT)) and np.isfinite(tv.FLOAT_INF_AS_FLOAT)
+    assert np.float32(tv.LARGEST_FINITE_AS_FLOAT) == np.finfo(np.float32).max
+    assert np.nextafter(tv.LARGEST_FINITE_AS_FLOAT, np.inf) == tv.FLOAT_INF_AS_FLOAT
+    refused, accepted = tv.crafted_large_index(b, tv.FLOAT_INF_AS_FLOAT), tv.crafted_large_index(b, tv.LARGEST_FINITE_AS_FLOAT)
+    with pytest.raises(hip.RayTraceError, match="non-finite index of refraction"):
+        hip.Plan(refused)
+    with hip.Plan(a) as plan:
+        plan.set_rays(rays).enable_probe()
+        for path in ("host", "device"):
+            with pytest.raises(hip.RayTraceError, match="non-finite index of refraction"):
+                update(plan, refused, path)
+            assert plan.problem is a
+            same_flags(plan.table_flags(), ase["flags_a"], f"after the refused {path} update")
+        _, rec = run_probed(plan)
+        same_records(rec, ase["rec_a"], "after the refused updates, against a fresh plan")
+        want = tv.expected_flags(accepted)
+        assert want["bounded"] == 0 and want["ntest_proven"] == 0
+        for path in ("host", "device"):
+            update(plan, accepted, path)
+            same_flags(plan.table_flags(), want, f"the largest index finite as a float, {path}")
+            update(plan, a, path)
+            same_flags(plan.table_flags(), ase["flags_a"], f"back to A, {path}")
+    with hip.Plan(accepted) as other:
+        same_flags(other.table_flags(), want, "the largest index finite as a float, created")
+
+
 # ---------------------------------------------------------------------------------------------- 8. between a run and its fetch
 def test_update_between_a_run_and_its_fetch(hip, oracle, ase):
     a, b, rays = ase["a"], ase["b"], ase["rays"]
