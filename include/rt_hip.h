@@ -268,7 +268,8 @@ typedef struct rt_hip_run_facts {
     int use_emis, own_cells, exclusive, path_on, spectra_on, step_on, step_one_launch, probe_on, has_ray_list, host_rays,
         tables_bounded, ntest_proven, gv_has_nan;
     int occupancy_per_cu;
-    int scan_on; /* a length scan (rt_hip_plan_enable_length_scan): the scan march and pass_kind 5, one record per length 1 .. L */
+    int scan_on; /* a length scan (rt_hip_plan_enable_length_scan): the scan march and pass_kind 5, one record per length 1 .. L;
+                    with method == 1 the suffix scan (rt_hip_plan_enable_suffix_scan): the backward scan march and pass_kind 9 */
 } rt_hip_run_facts;
 /* kind: 0 = march and second pass as two kernels, 1 = the image run in one launch, 2 = the step run in one launch.
  * The march (of a one-launch run: its march phase): lds_tab (tables in LDS) ... late_chunks; bounded, mode, opt and
@@ -560,6 +561,47 @@ int rt_hip_plan_enable_length_scan(rt_hip_plan *plan, int on);
 int rt_hip_plan_fetch_length_step(rt_hip_plan *plan, int n, double *E_v, double *nf, double *I_ang, unsigned int *failure_code);
 int rt_hip_plan_length_step_ptrs(rt_hip_plan *plan, int n, double **E_v_dev, double **nf_dev, double **iang_dev);
 int rt_hip_length_scan_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed, int method,
+                            const rt_ray *rays, size_t n_rays, double scale, double *E_v, double *nf, double *I_ang,
+                            unsigned int *failure_codes, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats);
+
+/*
+ * A suffix scan on a plan: the step record of the run of the LAST n lengths, n = 2 .. N, from ONE backward march -- the
+ * gain-length curve in the method RayTrace::create_image traces ASE with.  With the backward method RayTrace_calc_ray
+ * starts at the launch ray and walks the lengths ii = N - 1, N - 2, ..., 1 (Helper.h:430-441): its first n - 1 outer
+ * iterations are the whole run of the SUFFIX problem, an ordinary call with info->N = n and info->gain = gain + (N - n),
+ * gain[0] kept in place 0 (gain[0].E0 decides the mode, nothing else of it is read).  Record n is, by definition, what a
+ * step run of that problem leaves: the same beam, rays, seed, scale and method; record N is the plain step record.
+ *   The march is the backward march with the boundary stores of the length scan (MARCH_OPT_SCAN: boundary m is the state
+ *   after m marched segments).  rt_step_rscan_kernel (raytrace-miniapp_amd/csrc/rt_step_rscan.hip, in place of
+ *   rt_step_kernel; reported as freq_ms) places the launch ray once -- the backward method deposits there, so pixel and
+ *   angle cell are the same for every record -- and integrates the suffixes in chunks of four accumulators per walk over
+ *   the sub-segments.  The state that serves record n (m = n - 1, e = the marched segment the ray escaped in): boundary m
+ *   while m < e and m < N - 1, the ray not escaped; the final state otherwise.
+ * enable_suffix_scan(on != 0): the plan's method must be 1 (backward), 3 <= N and N - 1 <= RT_N_SCAN_MAX, and it must hold
+ *   no seed set, no ASE seeds and no length scan; anything else is RT_ERR_ARG.  on = 0 restores the plan exactly as it was.
+ *   The call settles the plan's last run first.  Emission plans and seeded (gain-only) plans are taken.  With the scan on
+ *   only step mode runs: rt_hip_plan_run outside step mode, with lent step buffers or with a non-NULL image_dev or
+ *   iang_dev is RT_ERR_ARG, and so are rt_hip_plan_enable_path, rt_hip_plan_enable_spectra, rt_hip_plan_set_seeds with a
+ *   non-empty set, rt_hip_plan_set_ase_seeds, rt_hip_plan_set_scan_seeds, rt_hip_plan_set_scan_ase_seeds and
+ *   rt_hip_plan_enable_length_scan.  rt_hip_plan_set_step_one_launch is accepted, the run keeps two kernels.  Ray lists and
+ *   ray grids (first / stride included), exact emission, the probe (exit ray, flags and steps of the whole run), the timing
+ *   ring, rt_hip_plan_set_step_factor and rt_hip_plan_update_gain / _dev work as on any step plan; an update keeps the
+ *   scan on.
+ * Outputs: the length scan's -- N - 1 blocks of one allocation, block n - 2 for the last n lengths, served by
+ *   rt_hip_plan_fetch_length_step and rt_hip_plan_length_step_ptrs; rt_hip_plan_fetch_step, rt_hip_plan_step_ptrs and
+ *   I_ang of rt_hip_plan_fetch serve record N.  rt_hip_plan_history_append files the N - 1 records of such a run.
+ * Failures follow the reference run once per record: error -1 is s.z^2 < 0.01 of the state that serves the record and
+ *   sets bit 1 in the codes of the records where it holds; the seed factor of a seeded plan is taken at that state's
+ *   position and exit angles and is 0 where the ray has escaped by then; error -2 / -3 under a record removes the ray from
+ *   that record only.  rt_hip_plan_fetch reports the OR of the codes and the rays that fail anywhere, each once (more than
+ *   RT_N_FAILED_MAX: the first of them in list order).
+ * rt_hip_suffix_scan_loop: the host-pointer form, rt_hip_length_scan_loop's arguments; row n - 2 holds the record of the
+ *   last n lengths.
+ * Not taken with the suffix scan: the forward method, seed sets, ASE seeds, scan seeds, the one-launch form, the
+ *   multi-device loops, image, spectra and path runs.
+ */
+int rt_hip_plan_enable_suffix_scan(rt_hip_plan *plan, int on);
+int rt_hip_suffix_scan_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed, int method,
                             const rt_ray *rays, size_t n_rays, double scale, double *E_v, double *nf, double *I_ang,
                             unsigned int *failure_codes, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats);
 

@@ -13,6 +13,7 @@ mirror of the reference's operator interface for this path.
   seed_step_loop(...)   the step records of up to RT_N_SEED_MAX seed beams from one march (Plan.set_seeds)
   full_step_loop(...)   the ASE record and the records of up to RT_N_SEED_MAX seed beams from one march (Plan.set_ase_seeds)
   length_scan_loop(...) the step record at every plasma length n = 2 .. N from one forward march (Plan.enable_length_scan)
+  suffix_scan_loop(...)  the step record of the last n lengths, n = 2 .. N, from one backward march (Plan.enable_suffix_scan)
   seed_length_scan_loop(...) ... of up to RT_N_SEED_MAX seed beams at every length, from that one march (Plan.set_scan_seeds)
   step_outputs_from_image  their definition as reductions of a cube, in numpy (no device)
   calc_rays / calc_ray  RayTrace::calc_ray (src/RayTraceImage.cpp:189-204), batched: per-ray spectrum, exit ray, code
@@ -419,6 +420,30 @@ class Plan:
         copy) of the last step run with the scan on -- blocks of one allocation, valid until the plan's next run; read them
         on the run's stream or after a fetch."""
         return [dict(n=n, **self._record_views(self.length_step_ptrs(n))) for n in self._scan_seed_range()[1]]
+
+    # -- suffix scan --------------------------------------------------------
+    def enable_suffix_scan(self, on: bool = True) -> "Plan":
+        """The suffix scan (include/rt_hip.h, rt_hip_plan_enable_suffix_scan): a step run then leaves the step record of the
+        run of the LAST n lengths, n = 2 .. N -- record n is what a step run of problem.suffix_lengths(p, n) leaves -- from
+        ONE backward march; fetch_length_steps, length_step_ptrs and length_step_tensors serve the records.  Backward method
+        only, 3 <= N <= RT_N_SCAN_MAX + 1.  Anything else, or an `on` that is not a bool or 0 / 1, is a ValueError raised here,
+        before any native call."""
+        if isinstance(on, bool):
+            on = int(on)
+        if not isinstance(on, (int, np.integer)) or on not in (0, 1):
+            raise ValueError(f"enable_suffix_scan: on is True / False (or 1 / 0), not {on!r}")
+        p = self.problem
+        if p.method != 1:
+            raise ValueError(f"enable_suffix_scan: the problem's method is {p.method}; only the backward method (1) begins "
+                             "with the marches of the last lengths")
+        if on:
+            if p.N < 3:
+                raise ValueError(f"enable_suffix_scan: N = {p.N}; a scan needs at least two lengths (N >= 3)")
+            if p.N - 1 > cabi.RT_N_SCAN_MAX:
+                raise ValueError(f"enable_suffix_scan: N - 1 = {p.N - 1} lengths, at most RT_N_SCAN_MAX = {cabi.RT_N_SCAN_MAX} fit into a scan")
+        self.hl.check(self.hl.lib.rt_hip_plan_enable_suffix_scan(self._h, int(on)), "rt_hip_plan_enable_suffix_scan")
+        self._scan = bool(on)   # (the records are the length scan's: _scan_seed_range counts them)
+        return self
 
     # -- the seeds of a scan ------------------------------------------------
     def set_scan_seeds(self, seeds) -> "Plan":
@@ -934,6 +959,39 @@ def length_scan_loop(problem: Problem, rays: np.ndarray | None = None, device: i
                                         cabi.rays_ptr(rays), len(rays), problem.scale, cabi._dp(E_v), cabi._dp(nf),
                                         cabi._dp(iang), codes, cabi.rays_ptr(failed), cabi.RT_N_FAILED_MAX, C.byref(nfail), C.byref(st))
     hl.check(rc, "rt_hip_length_scan_loop")
+    records = [dict(n=i + 2, E_v=E_v[i].copy(), nf=nf[i].copy(), I_ang=iang[i].copy(), failure_code=int(codes[i])) for i in range(L)]
+    code = 0
+    for r in records:
+        code |= r["failure_code"]
+    return dict(records=records, failure_code=code, failed_rays=failed[:nfail.value].copy(),
+                stats={k: getattr(st, k) for k, _ in cabi.RtStats._fields_})
+
+
+def suffix_scan_loop(problem: Problem, rays: np.ndarray | None = None, device: int = 0) -> dict:
+    """The step record of the run of the last n lengths, n = 2 .. N, from ONE backward march of the problem's rays
+    (rt_hip_suffix_scan_loop; rays None: the problem's ray grid as a list, which the library recognises).  Returns
+    dict(records = [dict(n, E_v, nf, I_ang, failure_code)], failure_code = the OR of the codes, failed_rays = the rays
+    that fail under any record, stats).  A problem the scan does not take (forward method, N < 3, more than RT_N_SCAN_MAX
+    lengths) is a ValueError raised here, before any native call."""
+    if problem.method != 1:
+        raise ValueError(f"suffix_scan_loop: the problem's method is {problem.method}; the scan takes the backward method (1) only")
+    if problem.N < 3 or problem.N - 1 > cabi.RT_N_SCAN_MAX:
+        raise ValueError(f"suffix_scan_loop: N = {problem.N}; a scan takes 3 <= N <= RT_N_SCAN_MAX + 1 = {cabi.RT_N_SCAN_MAX + 1}")
+    hl = HipLibrary.get()
+    m = cabi.Marshalled(problem)
+    if rays is None:
+        rays = problem.build_rays()
+    rays = np.ascontiguousarray(rays, dtype=cabi.RAY_DTYPE)
+    b, L = problem.beam, problem.N - 1
+    E_v, nf, iang = np.zeros((L, b.nv)), np.zeros((L, b.nx * b.ny)), np.zeros((L, b.na * b.nb))
+    codes = (C.c_uint * L)()
+    nfail = C.c_int(0)
+    failed = np.zeros(cabi.RT_N_FAILED_MAX, dtype=cabi.RAY_DTYPE)
+    st = cabi.RtStats()
+    rc = hl.lib.rt_hip_suffix_scan_loop(device, m.N, C.byref(m.beam), m.gain, m.seed_ref, problem.method,
+                                        cabi.rays_ptr(rays), len(rays), problem.scale, cabi._dp(E_v), cabi._dp(nf),
+                                        cabi._dp(iang), codes, cabi.rays_ptr(failed), cabi.RT_N_FAILED_MAX, C.byref(nfail), C.byref(st))
+    hl.check(rc, "rt_hip_suffix_scan_loop")
     records = [dict(n=i + 2, E_v=E_v[i].copy(), nf=nf[i].copy(), I_ang=iang[i].copy(), failure_code=int(codes[i])) for i in range(L)]
     code = 0
     for r in records:

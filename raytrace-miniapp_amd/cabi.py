@@ -392,6 +392,11 @@ def declare_hip_api(lib: C.CDLL) -> None:
         lib.rt_hip_plan_length_step_ptrs.restype = C.c_int
         lib.rt_hip_length_scan_loop.argtypes = list(lib.rt_hip_step_loop.argtypes)   # (one row per length where step_loop has one array)
         lib.rt_hip_length_scan_loop.restype = C.c_int
+    if hasattr(lib, "rt_hip_plan_enable_suffix_scan"):   # (likewise)
+        lib.rt_hip_plan_enable_suffix_scan.argtypes = [vp, C.c_int]
+        lib.rt_hip_plan_enable_suffix_scan.restype = C.c_int
+        lib.rt_hip_suffix_scan_loop.argtypes = list(lib.rt_hip_step_loop.argtypes)   # (row n - 2: the last n lengths)
+        lib.rt_hip_suffix_scan_loop.restype = C.c_int
     if hasattr(lib, "rt_hip_plan_set_scan_seeds"):   # (likewise)
         lib.rt_hip_plan_set_scan_seeds.argtypes = [vp, C.c_int, P(RtSeed)]
         lib.rt_hip_plan_set_scan_seeds.restype = C.c_int
@@ -461,6 +466,7 @@ HIP_API_SYMBOLS = [
     "rt_hip_plan_enable_length_scan", "rt_hip_plan_fetch_length_step", "rt_hip_plan_length_step_ptrs", "rt_hip_length_scan_loop",
     "rt_hip_plan_set_scan_seeds", "rt_hip_plan_fetch_seed_length_step", "rt_hip_plan_seed_length_step_ptrs",
     "rt_hip_seed_length_scan_loop",
+    "rt_hip_plan_enable_suffix_scan", "rt_hip_suffix_scan_loop",
     "rt_hip_plan_set_ase_seeds", "rt_hip_plan_fetch_full_step", "rt_hip_plan_full_step_ptrs", "rt_hip_full_step_loop",
     "rt_hip_plan_set_scan_ase_seeds", "rt_hip_plan_fetch_full_length_step", "rt_hip_plan_full_length_step_ptrs",
     "rt_hip_full_length_scan_loop",

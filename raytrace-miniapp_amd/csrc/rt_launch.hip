@@ -16,6 +16,7 @@
 #include "rt_step_seeds.hip" // step mode with a seed set: one record per seed from one march
 #include "rt_fused_step.hip" // step mode as two phases of one launch (opt-in)
 #include "rt_step_scan.hip" // step mode with a length scan: one record per plasma length from one forward march
+#include "rt_step_rscan.hip" // step mode with a suffix scan: one record per run of the last n lengths from one backward march
 #include "rt_step_scan_seeds.hip" // ... with the seeds of the scan: one record per (seed, length) from that march
 #include "rt_step_ase_seeds.hip"  // step kernel of an emission plan with ASE seeds: the ASE record and one per seed from one march
 #include "rt_step_scan_ase_seeds.hip" // ... with the length scan on: that whole record at every length from one forward march
@@ -66,7 +67,8 @@ int launch(const rt_hip_plan *p, void (*kernel)(const Arg), unsigned grid, unsig
 // ---- from a small key to the kernel instance, one function per family ----------------------------------------------
 // (the set of instances is what these functions name and nothing else: unbounded tables have no OPT and, of the MODEs,
 // only 0 and 1; the global-table march has MODE 0 only; the gain-only one-launch kernel MAXQ = 3 only; the scan instance
-// of the march, MODE 3 with MARCH_OPT_SCAN alone, exists for all four combinations of LDS_TAB and BOUNDED)
+// of the march, MODE 3 with MARCH_OPT_SCAN alone, exists for all four combinations of LDS_TAB and BOUNDED, and so do the
+// scan instances of the backward march, MODE 1 and MODE 0 with MARCH_OPT_SCAN alone)
 using march_fn      = void (*)(const rt::DevParams);
 using fused_fn      = void (*)(const rt::FusedKArg);
 using fused_step_fn = void (*)(const rt::FusedStepKArg);
@@ -77,8 +79,17 @@ template <bool LDS_TAB, int MODE> march_fn march_bounded(int opt)
 {
     return opt == 7 ? rt::rt_march_kernel<LDS_TAB, true, MODE, 7> : opt == 3 ? rt::rt_march_kernel<LDS_TAB, true, MODE, 3> : rt::rt_march_kernel<LDS_TAB, true, MODE, 0>;
 }
+// the scan instances of the backward march (the suffix scan, rt_step_rscan.hip): MODE 1 for an emission plan, MODE 0 for a
+// seeded one, the four combinations of LDS_TAB and BOUNDED each
+template <int MODE> march_fn march_rscan(bool lds_tab, bool bounded)
+{
+    return lds_tab ? (bounded ? rt::rt_march_kernel<true, true, MODE, rt::MARCH_OPT_SCAN> : rt::rt_march_kernel<true, false, MODE, rt::MARCH_OPT_SCAN>)
+                   : (bounded ? rt::rt_march_kernel<false, true, MODE, rt::MARCH_OPT_SCAN> : rt::rt_march_kernel<false, false, MODE, rt::MARCH_OPT_SCAN>);
+}
 march_fn march_kernel(bool lds_tab, bool bounded, int mode, int opt)
 {
+    if ((opt & rt::MARCH_OPT_SCAN) && mode != 3) // the suffix scan: the backward march with the boundary stores, no pruning
+        return mode == 1 ? march_rscan<1>(lds_tab, bounded) : march_rscan<0>(lds_tab, bounded);
     if (opt & rt::MARCH_OPT_SCAN) // the length scan: forward method at compile time (MODE 3), boundary stores, no pruning
         return lds_tab ? (bounded ? rt::rt_march_kernel<true, true, 3, rt::MARCH_OPT_SCAN> : rt::rt_march_kernel<true, false, 3, rt::MARCH_OPT_SCAN>)
                        : (bounded ? rt::rt_march_kernel<false, true, 3, rt::MARCH_OPT_SCAN> : rt::rt_march_kernel<false, false, 3, rt::MARCH_OPT_SCAN>);
@@ -137,6 +148,7 @@ void (*step_kernel(bool s6, bool emis))(const rt::StepKArg)
 void (*seeds_kernel(bool s6))(const rt::SeedsKArg) { return s6 ? rt::rt_step_seeds_kernel<6> : rt::rt_step_seeds_kernel<0>; }
 void (*ase_seeds_kernel(bool s6))(const rt::AseSeedsKArg) { return s6 ? rt::rt_step_ase_seeds_kernel<6> : rt::rt_step_ase_seeds_kernel<0>; }
 void (*scan_kernel(bool emis))(const rt::ScanKArg) { return emis ? rt::rt_step_scan_kernel<true> : rt::rt_step_scan_kernel<false>; }
+void (*rscan_kernel(bool emis))(const rt::ScanKArg) { return emis ? rt::rt_step_rscan_kernel<true> : rt::rt_step_rscan_kernel<false>; }
 
 // what a launch of the frequency pass covers: tiles [tile_begin, tile_end) on tile counter freq_id (a run is one launch
 // over all tiles; the range exists for experiments that split it), and the marks of the checking repeat (DevParams::safe)
@@ -282,9 +294,10 @@ int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kin
         "step kernel of a length scan: the E_v accumulators (nv doubles per length) do not fit into the LDS of this device",
         "step kernel of a length scan with scan seeds: the E_v accumulators (nv doubles per seed and length) do not fit into the LDS of this device",
         "step kernel of an emission plan with ASE seeds: the E_v accumulators (nv doubles for ASE and per seed) do not fit into the LDS of this device",
-        "step kernel of a length scan with ASE seeds: the E_v accumulators (nv doubles per record and length) do not fit into the LDS of this device" };
+        "step kernel of a length scan with ASE seeds: the E_v accumulators (nv doubles per record and length) do not fit into the LDS of this device",
+        "step kernel of a suffix scan: the E_v accumulators (nv doubles per length) do not fit into the LDS of this device" };
     static_assert(PASS_SPEC == 1 && PASS_STEP == 2 && PASS_SEEDS == 3 && PASS_SCAN == 5 && PASS_SCAN_SEEDS == 6 && PASS_ASE_SEEDS == 7 &&
-                      PASS_SCAN_ASE_SEEDS == 8 && sizeof(too_big) / sizeof(too_big[0]) == 9,
+                      PASS_SCAN_ASE_SEEDS == 8 && PASS_RSCAN == 9 && sizeof(too_big) / sizeof(too_big[0]) == 10,
                   "too_big[] is indexed by PassKind");
     if (too_big[kind] && s.lds > f.lds_limit)
         return fail_arg(too_big[kind]);
@@ -319,6 +332,17 @@ int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kin
         a.hot.iang     = nullptr; // (every record's I_ang lies in its block)
         fill_scan(a.scan, p);
         return launch(p, scan_kernel(f.use_emis), s.grid, block, s.lds, stream, a);
+    }
+    if (kind == PASS_RSCAN) { // a suffix scan (a backward plan): one record per run of the last n lengths
+        if (!p->scan_bnd || !p->recs_dev)
+            return fail_arg("step kernel of a suffix scan: the boundary states or the records of this run were not allocated");
+        if (f.L > RT_N_SCAN_MAX || p->recs_doubles < (size_t) n_rec * p->recs_stride)
+            return fail_arg("step kernel of a suffix scan: more than RT_N_SCAN_MAX lengths, or the records of this run are smaller than N - 1 blocks");
+        rt::ScanKArg a = pass_args<rt::ScanKArg>(fa);
+        a.hot.iang     = nullptr; // (every record's I_ang lies in its block)
+        a.hot.flags &= ~(unsigned) rt::FQ_EXCLUSIVE; // (nf of every record by atomics)
+        fill_scan(a.scan, p);
+        return launch(p, rscan_kernel(f.use_emis), s.grid, block, s.lds, stream, a);
     }
     if (kind == PASS_SCAN_SEEDS) { // a length scan with scan seeds (a seeded plan: gain-only): one record per (seed, length)
         if (!p->scan_bnd || !p->recs_dev)

@@ -815,8 +815,9 @@ template <bool LDS_TAB> __device__ __forceinline__ void march_load_tables(const 
 // bit 2 (MARCH_OPT_PRUNE_H24, large launches) -- likewise those of h2 and h4, behind one branch; bit 1
 // (MARCH_OPT_NO_NTEST) -- rt_hip_plan_create has proved that |n - n0| < 0.05 (Helper.h:280) holds in every step these
 // tables allow, and the loop condition of [C] goes without it.  The march records are the same floats in every instance.
-// Bit 3 (MARCH_OPT_SCAN, the length scan of rt_step_scan.hip; forward method only, rt_launch.hip pairs it with MODE 3 and
-// takes it with bounded and unbounded tables alike): where a ray crosses a length boundary, block [A1], the instance also
+// Bit 3 (MARCH_OPT_SCAN, the length scan of rt_step_scan.hip: forward method, rt_launch.hip pairs it with MODE 3; the suffix
+// scan of rt_step_rscan.hip: backward method, MODE 1 or 0 -- the store is indexed by the number of segments marched, which is
+// the state either pass needs; with bounded and unbounded tables alike): where a ray crosses a length boundary, block [A1], the instance also
 // stores the state it crosses with -- {px, py, sx, sy, sz}, what RecMeta keeps of the exit state -- into the boundary
 // buffer (scan_bnd_off below; its address travels in DevParams::pad_march[0 .. 1], which no other instance reads).
 enum : int { MARCH_OPT_PRUNE = 1, MARCH_OPT_NO_NTEST = 2, MARCH_OPT_PRUNE_H24 = 4, MARCH_OPT_SCAN = 8 };

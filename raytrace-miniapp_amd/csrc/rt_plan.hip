@@ -98,6 +98,9 @@ inline __attribute__((always_inline)) void magnitude_scan(const uint32_t *u, siz
     finite = m;
     all    = mall;
 }
+// scan_on of a backward plan is the suffix scan (rt_runtime.h): the refusals name the scan that is on
+bool suffix_scan(const rt_hip_plan *p) { return p->scan_on && p->P.method == 1; }
+
 void magnitude_scan_plain(const uint32_t *u, size_t n, uint32_t &finite, uint32_t &all) { magnitude_scan<0>(u, n, finite, all); }
 __attribute__((target("avx2"))) void magnitude_scan_avx2(const uint32_t *u, size_t n, uint32_t &finite, uint32_t &all)
 {
@@ -852,7 +855,8 @@ int rt_hip_plan_enable_path(rt_hip_plan *p, int on)
     if (on && p->n_seed > 0)
         return fail_arg("rt_hip_plan_enable_path: the plan holds a seed set (step mode only)");
     if (on && p->scan_on)
-        return fail_arg("rt_hip_plan_enable_path: the length scan is on (step mode only)");
+        return fail_arg(suffix_scan(p) ? "rt_hip_plan_enable_path: the suffix scan is on (step mode only)"
+                                       : "rt_hip_plan_enable_path: the length scan is on (step mode only)");
     p->path_on = on != 0;
     return RT_OK;
 }
@@ -882,7 +886,8 @@ int rt_hip_plan_enable_spectra(rt_hip_plan *p, int on)
     if (on && p->n_seed > 0)
         return fail_arg("rt_hip_plan_enable_spectra: the plan holds a seed set (step mode only)");
     if (on && p->scan_on)
-        return fail_arg("rt_hip_plan_enable_spectra: the length scan is on (step mode only)");
+        return fail_arg(suffix_scan(p) ? "rt_hip_plan_enable_spectra: the suffix scan is on (step mode only)"
+                                       : "rt_hip_plan_enable_spectra: the length scan is on (step mode only)");
     p->spectra_on = on != 0;
     return RT_OK;
 }
@@ -1007,7 +1012,14 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
         return fail_arg("rt_hip_plan_run: a step run takes no image buffer");
     const bool lent = step && p->step_ev_lent; // E_v and nf in the caller's memory (rt_hip_plan_set_step_buffers)
     const size_t nf_off = align_up((size_t) p->P.K * sizeof(double), 256) / sizeof(double);
-    if (p->scan_on) {
+    if (suffix_scan(p)) {
+        if (!step || p->path_on)
+            return fail_arg("rt_hip_plan_run: the suffix scan is on, which runs in step mode only");
+        if (lent)
+            return fail_arg("rt_hip_plan_run: a suffix scan writes the plan's own records, not lent step buffers");
+        if (image_dev || iang_dev)
+            return fail_arg("rt_hip_plan_run: a run with the suffix scan on takes no image and no I_ang buffer");
+    } else if (p->scan_on) {
         if (!step || p->path_on)
             return fail_arg("rt_hip_plan_run: the length scan is on, which runs in step mode only");
         if (lent)
@@ -1389,6 +1401,8 @@ int rt_hip_plan_enable_length_scan(rt_hip_plan *p, int on)
 {
     if (!p)
         return fail_arg("rt_hip_plan_enable_length_scan: NULL plan");
+    if (!on && suffix_scan(p)) // (on: the method test below refuses it)
+        return fail_arg("rt_hip_plan_enable_length_scan: the suffix scan is on (rt_hip_plan_enable_suffix_scan switches it off)");
     if (on) {
         if (p->P.method != 2)
             return fail_arg("rt_hip_plan_enable_length_scan: the plan's method is not 2 (only the forward march of N lengths holds the marches of fewer)");
@@ -1427,7 +1441,46 @@ int rt_hip_plan_enable_length_scan(rt_hip_plan *p, int on)
     return RT_OK;
 }
 
-// (on a scan with scan seeds a length alone means seed 0's curve, on a scan with ASE seeds the ASE curve)
+// The suffix scan of a backward plan (include/rt_hip.h).  It is the plan's scan_on with method 1: the boundary buffer, the
+// records and their accessors are the length scan's, run_shape and record_set tell the two apart by the method.
+int rt_hip_plan_enable_suffix_scan(rt_hip_plan *p, int on)
+{
+    if (!p)
+        return fail_arg("rt_hip_plan_enable_suffix_scan: NULL plan");
+    if (p->P.method != 1)
+        return fail_arg("rt_hip_plan_enable_suffix_scan: the plan's method is not 1 (only the backward march of N lengths begins with the marches of the last n)");
+    if (on) {
+        if (p->P.N < 3)
+            return fail_arg("rt_hip_plan_enable_suffix_scan: N < 3 (one length: the step record is the scan)");
+        if (p->P.N - 1 > RT_N_SCAN_MAX)
+            return fail_arg("rt_hip_plan_enable_suffix_scan: more than RT_N_SCAN_MAX lengths");
+        if (p->n_seed > 0)
+            return fail_arg(p->P.use_emis ? "rt_hip_plan_enable_suffix_scan: the plan holds ASE seeds (ASE seeds and a suffix scan exclude each other)"
+                                          : "rt_hip_plan_enable_suffix_scan: the plan holds a seed set (a seed set and a suffix scan exclude each other)");
+        if (p->path_on || p->spectra_on)
+            return fail_arg("rt_hip_plan_enable_suffix_scan: the path tracer or spectra mode is enabled (the scan runs in step mode only)");
+    }
+    // (a backward plan never has the length scan on: scan_on is the suffix scan here)
+    if ((on != 0) == p->scan_on)
+        return RT_OK;
+    HIP_TRY(hipSetDevice(p->device));
+    if (p->ran) { // the last run keeps its records until it is final (wait, control block, the checking repeat)
+        const int rs = plan_settle_last_run(p);
+        if (rs != RT_OK)
+            return rs;
+    }
+    plan_quiesce(p);
+    p->scan_on = on != 0;
+    if (!p->scan_on) { // the boundary states exist only while the scan is on
+        pool_free(p->device, p->scan_bnd);
+        p->scan_bnd       = nullptr;
+        p->scan_bnd_bytes = 0;
+    }
+    return RT_OK;
+}
+
+// (on a scan with scan seeds a length alone means seed 0's curve, on a scan with ASE seeds the ASE curve; on a suffix scan n
+// is the number of lengths of the run of the LAST n)
 int rt_hip_plan_fetch_length_step(rt_hip_plan *p, int n, double *E_v, double *nf, double *I_ang, unsigned int *failure_code)
 {
     if (!p || !p->last_records.scan())
@@ -1481,7 +1534,8 @@ int rt_hip_plan_set_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds)
     if (rv != RT_OK)
         return rv;
     if (n_seed > 0 && p->scan_on)
-        return fail_arg("rt_hip_plan_set_seeds: the length scan is on (a seed set and a length scan exclude each other)");
+        return fail_arg(suffix_scan(p) ? "rt_hip_plan_set_seeds: the suffix scan is on (a seed set and a suffix scan exclude each other)"
+                                       : "rt_hip_plan_set_seeds: the length scan is on (a seed set and a length scan exclude each other)");
     if (n_seed > 0 && (p->path_on || p->spectra_on))
         return fail_arg("rt_hip_plan_set_seeds: the path tracer or spectra mode is enabled (a set runs in step mode only)");
     if (n_seed == 0 && p->n_scan_seed > 0) // (the seeds of a scan are rt_hip_plan_set_scan_seeds': there is no set to remove)
@@ -1495,6 +1549,8 @@ int rt_hip_plan_set_scan_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds)
         return fail_arg("rt_hip_plan_set_scan_seeds: NULL plan");
     if (!p->P.has_seed)
         return fail_arg("rt_hip_plan_set_scan_seeds: the plan was created without a seed (scan seeds need the gain-only mode)");
+    if (suffix_scan(p))
+        return fail_arg("rt_hip_plan_set_scan_seeds: the suffix scan is on (it takes no scan seeds)");
     if (!p->scan_on)
         return fail_arg("rt_hip_plan_set_scan_seeds: the length scan is off (rt_hip_plan_enable_length_scan first)");
     const int rv = seeds_validate(p, "rt_hip_plan_set_scan_seeds", n_seed, seeds);
@@ -1574,7 +1630,8 @@ int rt_hip_plan_set_ase_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds, 
     if (rv != RT_OK)
         return rv;
     if (p->scan_on)
-        return fail_arg("rt_hip_plan_set_ase_seeds: the length scan is on (ASE seeds and a length scan exclude each other)");
+        return fail_arg(suffix_scan(p) ? "rt_hip_plan_set_ase_seeds: the suffix scan is on (ASE seeds and a suffix scan exclude each other)"
+                                       : "rt_hip_plan_set_ase_seeds: the length scan is on (ASE seeds and a length scan exclude each other)");
     if (n_seed > 0 && (p->path_on || p->spectra_on))
         return fail_arg("rt_hip_plan_set_ase_seeds: the path tracer or spectra mode is enabled (ASE seeds run in step mode only)");
     const int rc = seeds_install(p, n_seed, seeds, false);
@@ -1593,6 +1650,8 @@ int rt_hip_plan_set_scan_ase_seeds(rt_hip_plan *p, int n_seed, const rt_seed *se
         return fail_arg("rt_hip_plan_set_scan_ase_seeds: NULL plan");
     if (p->P.has_seed || !p->P.use_emis)
         return fail_arg("rt_hip_plan_set_scan_ase_seeds: not an emission plan (created without a seed, tables with E0)");
+    if (suffix_scan(p))
+        return fail_arg("rt_hip_plan_set_scan_ase_seeds: the suffix scan is on (it takes no ASE seeds)");
     if (!p->scan_on)
         return fail_arg("rt_hip_plan_set_scan_ase_seeds: the length scan is off (rt_hip_plan_enable_length_scan first)");
     const int rv = seeds_validate(p, "rt_hip_plan_set_scan_ase_seeds", n_seed, seeds);
@@ -1792,8 +1851,10 @@ int rt_hip_plan_fetch_probe(rt_hip_plan *p, float *gvl, float *evl, int32_t *ivl
 static int host_pointer_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed,
                              int method, const rt_ray *rays, size_t n_rays, double scale, double *image, double *E_v, double *nf,
                              double *I_ang, unsigned int *failure_code, rt_ray *failed_rays, int max_failed,
-                             int *n_failed, rt_stats *stats, bool scan = false, int n_scan_seed = 0, const rt_seed *scan_seeds = nullptr)
+                             int *n_failed, rt_stats *stats, bool scan = false, int n_scan_seed = 0, const rt_seed *scan_seeds = nullptr,
+                             bool suffix = false)
 {
+    // (suffix: rt_hip_suffix_scan_loop -- scan, with the suffix scan of a backward plan in the length scan's place)
     // (n_scan_seed > 0: rt_hip_seed_length_scan_loop -- the rows of a scan once per seed, [n_seed][N - 1][...])
     // (scan: rt_hip_length_scan_loop -- E_v, nf and I_ang hold one row per length n = 2 .. N, failure_code one code per row)
     const bool step = image == nullptr;
@@ -1819,7 +1880,7 @@ static int host_pointer_loop(int device, int N, const rt_beam *beam, const rt_ga
     if (step) {
         rc = rt_hip_plan_enable_step(p, 1);
         if (rc == RT_OK && scan)
-            rc = rt_hip_plan_enable_length_scan(p, 1);
+            rc = suffix ? rt_hip_plan_enable_suffix_scan(p, 1) : rt_hip_plan_enable_length_scan(p, 1);
         if (rc == RT_OK && scan && n_scan_seed > 0)
             rc = rt_hip_plan_set_scan_seeds(p, n_scan_seed, scan_seeds);
         if (rc != RT_OK) {
@@ -1915,6 +1976,21 @@ int rt_hip_length_scan_loop(int device, int N, const rt_beam *beam, const rt_gai
     // (method, N: rt_hip_plan_enable_length_scan refuses what the scan does not take)
     return host_pointer_loop(device, N, beam, gain, seed, method, rays, n_rays, scale, nullptr, E_v, nf, I_ang, failure_codes,
                              failed_rays, max_failed, n_failed, stats, true);
+}
+
+int rt_hip_suffix_scan_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed, int method,
+                            const rt_ray *rays, size_t n_rays, double scale, double *E_v, double *nf, double *I_ang,
+                            unsigned int *failure_codes, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats)
+{
+    if (!beam)
+        return fail_arg("rt_hip_suffix_scan_loop: NULL beam");
+    if (!rays && n_rays)
+        return fail_arg("rt_hip_suffix_scan_loop: NULL ray list");
+    if (n_rays > MAX_LIST_RAYS)
+        return fail_arg("rt_hip_suffix_scan_loop: 2^32 - 4096 rays or more: split the call");
+    // (method, N: rt_hip_plan_enable_suffix_scan refuses what the scan does not take)
+    return host_pointer_loop(device, N, beam, gain, seed, method, rays, n_rays, scale, nullptr, E_v, nf, I_ang, failure_codes,
+                             failed_rays, max_failed, n_failed, stats, true, 0, nullptr, true);
 }
 
 int rt_hip_seed_length_scan_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed, int method,

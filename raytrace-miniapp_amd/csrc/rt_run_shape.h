@@ -32,7 +32,10 @@ struct RunFacts {
     bool use_emis = false, own_cells = false, exclusive = false, path_on = false, spectra_on = false, step_on = false,
          step_one_launch = false, probe_on = false, has_ray_list = false, host_rays = false, tables_bounded = false,
          ntest_proven = false, gv_has_nan = false;
-    bool scan_on = false; // a length scan (rt_hip_plan_enable_length_scan): one step record per length from one forward march
+    // a length scan (rt_hip_plan_enable_length_scan): one step record per length from one forward march; with method == 1
+    // the suffix scan (rt_hip_plan_enable_suffix_scan): one record per run of the last n lengths from one backward march
+    bool scan_on = false;
+    bool rscan() const { return scan_on && method == 1; }
     bool s6() const { return L * RT_N_SUB == 6; } // N = 3, the shipped inputs: the instances with SF = 6
 };
 
@@ -303,8 +306,10 @@ inline RunShape run_shape(const RunFacts &f, const Tuning &t, const Occupancy &o
     s.opt = (s.bounded && f.march_prune && f.ntest_proven) ? (rt::MARCH_OPT_PRUNE | rt::MARCH_OPT_NO_NTEST | (prune_h24 ? rt::MARCH_OPT_PRUNE_H24 : 0)) : 0;
     // (a length scan: the instance that stores the boundary states, rt_march.hip MARCH_OPT_SCAN -- forward method at compile
     // time, the emission switch as DevParams says, no pruning; with bounded and unbounded tables, in LDS or not)
+    // (the suffix scan: the same stores from the backward march -- MODE 1, backward and emission at compile time, for an
+    // emission plan, MODE 0 for a seeded one)
     if (f.scan_on) {
-        s.mode = 3;
+        s.mode = f.rscan() ? (f.use_emis ? 1 : 0) : 3;
         s.opt  = rt::MARCH_OPT_SCAN;
     }
     s.last_march_inst = (s.bounded ? 1 : 0) | (s.opt << 1);
@@ -364,7 +369,7 @@ inline RecordSet record_set(const RunFacts &f)
     if (!f.step_on || f.path_on || f.spectra_on)
         return r;
     // (use_emis with n_seed > 0: ASE seeds, of the scan where it is on -- no other plan presents that pair)
-    r.kind   = f.scan_on ? (f.n_seed > 0 ? (f.use_emis ? REC_SCAN_ASE_SEEDS : REC_SCAN_SEEDS) : REC_SCAN) : f.n_seed > 0 ? (f.use_emis ? REC_ASE_SEEDS : REC_SEEDS) : REC_NONE;
+    r.kind   = f.rscan() ? REC_RSCAN : f.scan_on ? (f.n_seed > 0 ? (f.use_emis ? REC_SCAN_ASE_SEEDS : REC_SCAN_SEEDS) : REC_SCAN) : f.n_seed > 0 ? (f.use_emis ? REC_ASE_SEEDS : REC_SEEDS) : REC_NONE;
     r.n_seed = f.n_seed;
     r.L      = f.scan_on ? f.L : 0;
     return r;
@@ -435,13 +440,14 @@ inline PassShape pass_shape(PassKind kind, const RunFacts &f, const Tuning &t)
         s.wg_waves = rt::FREQ_WG_WAVES;
         // (a seed set keeps one I_ang histogram and one E_v accumulator per seed, a length scan one of each per length, a scan
         // with scan seeds one of each per (seed, length), an emission plan with ASE seeds one of each for ASE and per seed -- with
-        // the scan on, of those per length)
+        // the scan on, of those per length; a suffix scan one of each per length)
         const int n_rec      = kind == PASS_STEP || kind == PASS_SPEC ? 1 : record_set(f).n_rec();
         const int ang_stride = kind == PASS_STEP ? rt::step_ang_stride((int) f.n_iang) : rt::seeds_ang_stride((int) f.n_iang);
         auto step_lds        = [&](bool in_lds) { return rt::step_lds_doubles(in_lds, ang_stride, f.Kp, s.wg_waves, n_rec) * sizeof(double); };
         // (spectra: the staging rows of 16 waves and the exponent tables take 148 KB of LDS)
         s.lds = kind == PASS_SPEC ? ((size_t) 2 * rt::EXP_TAB + (size_t) s.wg_waves * rt::WAVE * rt::XS_ROW) * sizeof(double) : step_lds(s.in_lds);
-        if ((kind == PASS_SEEDS || kind == PASS_SCAN || kind == PASS_SCAN_SEEDS || kind == PASS_ASE_SEEDS || kind == PASS_SCAN_ASE_SEEDS) && s.in_lds &&
+        if ((kind == PASS_SEEDS || kind == PASS_SCAN || kind == PASS_SCAN_SEEDS || kind == PASS_ASE_SEEDS || kind == PASS_SCAN_ASE_SEEDS ||
+             kind == PASS_RSCAN) && s.in_lds &&
             s.lds > f.lds_limit) { // one histogram per record does not fit: global atomics
             s.in_lds = false;
             s.lds    = step_lds(false);

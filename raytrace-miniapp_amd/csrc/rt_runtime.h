@@ -112,7 +112,9 @@ struct rt_hip_plan {
     double ase_scale[RT_N_SEED_MAX] = {};
     // length scan (rt_hip_plan_enable_length_scan): one step record per plasma length n = 2 .. N from one forward march;
     // scan_bnd holds the state with which every ray crossed every length boundary (rt_march.hip, scan_bnd_off), from the
-    // plan's pool while the scan is on.
+    // plan's pool while the scan is on.  On a backward plan (P.method == 1) scan_on is the suffix scan
+    // (rt_hip_plan_enable_suffix_scan): one record per run of the LAST n lengths from one backward march, the same boundary
+    // buffer and the same records; a plan's method never changes, so the pair says which of the two is on.
     bool scan_on          = false;
     unsigned char *scan_bnd = nullptr;
     size_t scan_bnd_bytes = 0;
@@ -265,7 +267,8 @@ inline CodeSlot record_code_slot(const RecordSet &R)
     switch (R.kind) {
     case REC_SEEDS: return { (unsigned) (offsetof(rt::DevCtl, seed_code) / W), all, 0 };
     case REC_ASE_SEEDS: return { (unsigned) (offsetof(rt::DevCtl, rec_code) / W), all, 0 };
-    case REC_SCAN: return { (unsigned) (offsetof(rt::DevCtl, len_code) / W), all, 0 };
+    case REC_SCAN:
+    case REC_RSCAN: return { (unsigned) (offsetof(rt::DevCtl, len_code) / W), all, 0 };
     case REC_SCAN_SEEDS: return { (unsigned) (offsetof(rt::DevCtl, seed_len_code) / W), (unsigned) R.L, RT_N_SCAN_MAX };
     case REC_SCAN_ASE_SEEDS: return { (unsigned) (offsetof(rt::DevCtl, rec_len_code) / W), (unsigned) R.L, RT_N_SCAN_MAX };
     default: return { (unsigned) (offsetof(rt::DevCtl, failure_code) / W), all, 0 }; // (block 0: the run's code)

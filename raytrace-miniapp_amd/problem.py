@@ -250,6 +250,21 @@ def prefix_lengths(p: Problem, n: int) -> Problem:
     return q
 
 
+def suffix_lengths(p: Problem, n: int) -> Problem:
+    """The suffix problem of n lengths: p with the tables [gain[0]] + gain[N - n + 1 :] -- same beam, rays, seed, scale and
+    method.  With the backward method a run of N lengths begins with the whole run of this problem (gain[0] stays in place
+    0: its E0 decides the mode); record n of a suffix scan (backend.Plan.enable_suffix_scan) is, by definition, the step
+    record of this problem."""
+    if not isinstance(n, (int, np.integer)) or isinstance(n, bool) or n < 2 or n > p.N:
+        raise ValueError(f"suffix_lengths: n = {n!r}, must be an integer 2 .. N = {p.N}")
+    q = copy.copy(p)
+    q.gain = [p.gain[0]] + list(p.gain[p.N - int(n) + 1:])
+    q.golden_image = None
+    q.golden_I_ang = None
+    q.label = f"{p.label} / last {int(n)} lengths"
+    return q
+
+
 def regrid_beam(p: Problem, nx=None, ny=None, na=None, nb=None, a_centre=None, b_centre=None) -> Problem:
     """Cell-centred regrid of chosen beam axes to explicit sizes over the same
     extents (the scale_beam formula applied per axis); na/nb = 1 with a centre
