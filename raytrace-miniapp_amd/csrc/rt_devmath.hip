@@ -306,7 +306,9 @@ __global__ void __launch_bounds__(DM_BLOCK) dm_march_step_kernel(const DmStepFac
 }
 
 // rt_march_xsetup.inc as march_wave includes it.  fin [n][4] = px, py, w_x, w_y; din [n][8] = lo_x, rw_x, lo_y, rw_y and the
-// corner indices n00, n10, n01, n11 (rounded and differenced here as block [A2] does it); mirror [n]; out [n][3] = n0, gxn, gyn
+// corner indices n00, n10, n01, n11 (rounded and differenced here as block [A2] does it); mirror [n]; out [n][3] = n0, gxn, gyn.
+// BOUNDED: the form of the instances that run under the ranges of the short forms (no sign copy on the quotients)
+template <bool BOUNDED>
 __global__ void __launch_bounds__(DM_BLOCK) dm_march_xsetup_kernel(const float *fin, const double *din, const unsigned char *mirror_in,
                                                                   float *out, size_t n_cases)
 {
@@ -820,7 +822,7 @@ DM_API int rt_devmath_march_step(int bounded, int opt, float c, const float *in,
 
 // The cross-cell set-up of the march per case (rt_march_xsetup.inc): fin [n][4], din [n][8], mirror [n], out [n][3] as
 // dm_march_xsetup_kernel says
-DM_API int rt_devmath_march_xsetup(const float *fin, const double *din, const unsigned char *mirror, float *out, size_t n)
+static int march_xsetup(bool bounded, const float *fin, const double *din, const unsigned char *mirror, float *out, size_t n)
 {
     Bufs B;
     float *dfin, *dout;
@@ -832,8 +834,21 @@ DM_API int rt_devmath_march_xsetup(const float *fin, const double *din, const un
     DM_TRY(B.in((void **) &ddin, din, n * 8 * sizeof(double)));
     DM_TRY(B.in((void **) &dmir, mirror, n));
     DM_TRY(B.out((void **) &dout, n * 3 * sizeof(float)));
-    dm_march_xsetup_kernel<<<grid_for(n), DM_BLOCK>>>(dfin, ddin, dmir, dout, n);
+    if (bounded)
+        dm_march_xsetup_kernel<true><<<grid_for(n), DM_BLOCK>>>(dfin, ddin, dmir, dout, n);
+    else
+        dm_march_xsetup_kernel<false><<<grid_for(n), DM_BLOCK>>>(dfin, ddin, dmir, dout, n);
     return B.release(finish(out, dout, n * 3 * sizeof(float)));
+}
+// ... in the generic instance, for any tables,
+DM_API int rt_devmath_march_xsetup(const float *fin, const double *din, const unsigned char *mirror, float *out, size_t n)
+{
+    return march_xsetup(false, fin, din, mirror, out, n);
+}
+// ... and in the BOUNDED one: the cases must lie inside the ranges under which the plan selects it (rt_plan.hip)
+DM_API int rt_devmath_march_xsetup_bounded(const float *fin, const double *din, const unsigned char *mirror, float *out, size_t n)
+{
+    return march_xsetup(true, fin, din, mirror, out, n);
 }
 
 // The march blob of the tables gain[1 .. N-1] (gain[0] is not read) as rt_hip_plan_create packs it: the same function,

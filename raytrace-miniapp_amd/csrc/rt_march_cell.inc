@@ -96,8 +96,15 @@
                     dnx1      = n11 - n01;
                     dny0      = n01 - n00;
                     dny1      = n11 - n10;
-                    const float u = (float) div_by_recip<true>(pxd - ix0.x, tx.x - ix0.x, tx.y);
-                    const float v = (float) div_by_recip<true>(yad - iy0.x, ty.x - iy0.x, ty.y);
+                    // (no sign copy on the quotients, div_by_recip_pos0: it matters for a -0 dividend alone.  A rounded
+                    // difference of equal numbers is +0, so the dividend is -0 only for px = -0 on a first
+                    // interval that starts at +0 (a y axis that starts at 0 is mirrored: ya = |py|), and u = -0 reaches g0 and E0 as the term -0 * f10 beside
+                    // 1.0f * f00: absorbed by a non-zero f00, and with f00 = +0 the sum is +0 for either sign of the term.
+                    // Only a table value f00 = -0 under such a ray would give g0 or E0 the other zero, and that sign ends
+                    // here: gacc and eacc start at +0 and x + -0 = x + +0 for every x but -0.
+                    // tests/test_gpu_march_zero_signs.py holds the populations.)
+                    const float u = (float) div_by_recip_pos0(pxd - ix0.x, tx.x - ix0.x, tx.y);
+                    const float v = (float) div_by_recip_pos0(yad - iy0.x, ty.x - iy0.x, ty.y);
                     g0            = lerp2(u, v, __uint_as_float(q00.z), __uint_as_float(q10.z), __uint_as_float(q01.z),
                                           __uint_as_float(q11.z));
                     E0            = 0.0f;

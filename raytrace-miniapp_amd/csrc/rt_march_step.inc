@@ -12,7 +12,7 @@
 //   MarchDiag, or a counting stand-in.
 // Reads and writes: rx, ry, rz, sx, sy, sz, hsum.
 // Writes: n, run.
-// Declares (in the including block): rn, a0, t, qx, qy, fx, fy, fz, h, ht, R3, R6, R12, c1, c2 and the candidates of its
+// Declares (in the including block): rn, a0, t, qx, qy, fx, fy, fz, h, ht, F1, F2, c1, c2 and the candidates of its
 //   branches; defines the macro RT_FDIV.
                 n        = n0 + rx * gxn + ry * gyn;
 #ifdef RT_ABL_FASTDIV
@@ -26,6 +26,8 @@
                 // (BOUNDED: a0 is never -0 -- x + 1e-12f is +0 or non-zero -- and rn > 0, so the corrected
                 // quotient has the sign of a0 without the sign copy)
                 float t  = BOUNDED ? fmaf(fmaf(-n, a0 * rn, a0), rn, a0 * rn) : div_by_recip_signed(a0, n, rn);
+                // (qx, qy keep their sign copy: gyn = -gyn of a mirrored cell makes a -0 gradient, and with sx = -0 and
+                // t < 0 the sign of a zero qx decides between sx = -0 and +0 after the step)
                 float qx = div_by_recip_signed(gxn, n, rn);
                 float qy = div_by_recip_signed(gyn, n, rn);
 #ifndef RT_ABL_NOGUARD
@@ -115,12 +117,13 @@
                     h        = h < h4 ? h : h4;
                 }
                 float ht = h * t;
-                const float R3 = 1.0f / 3.0f, R6 = 1.0f / 6.0f, R12 = 1.0f / 12.0f; // RN(1/b), folded
-                float c1 = 0.5f * h * h * (1.0f - div_by_recip<true>(ht, 3.0f, R3) + div_by_recip<true>(ht * ht, 12.0f, R12));
+                float F1, F2; // 1 - ht / 3 + ht^2 / 12 and 1 - ht / 2 + ht^2 / 6 (rt_math.h)
+                step_factors(ht, F1, F2);
+                float c1 = 0.5f * h * h * F1;
                 rx += sx * h + c1 * fx;
                 ry += sy * h + c1 * fy;
                 rz += sz * h + c1 * fz;
-                float c2 = h * (1.0f - 0.5f * ht + div_by_recip<true>(ht * ht, 6.0f, R6));
+                float c2 = h * F2;
                 sx += c2 * fx;
                 sy += c2 * fy;
                 sz += c2 * fz;

@@ -132,6 +132,40 @@ template <bool TINY_OK = false> __device__ __forceinline__ double div_by_recip(d
 #endif
     return c;
 }
+// The double TINY_OK form without the sign copy (one v_bfi_b32 less): the same double wherever the quotient is not a
+// zero -- the correction is at most half an ulp of q; a quotient that underflows to zero has r = a exactly, and
+// fma(a, y, +-0) rounds the non-zero product to a zero of its own sign, which is q's -- and +0 for a dividend of
+// either zero (q = -0 gives r = +0, and +0 * y + -0 = +0).  For callers that show why a -0 quotient cannot reach
+// their result: the cell coordinates u, v of the cell set-up (rt_march_cell.inc) and, in the BOUNDED instances, u, v
+// and the four gradient quotients of the cross-cell set-up (rt_march_xsetup.inc).
+__device__ __forceinline__ double div_by_recip_pos0(double a, double b, double y)
+{
+    const double q = a * y;
+    const double r = fma(-b, q, a);
+    return fma(r, y, q);
+}
+
+// The two factors of the integrator step's Taylor update (Helper.h:300-306), which depend on the float ht = h * t alone:
+//     f1 = 1.0f - ht / 3.0f + (ht * ht) / 12.0f,     f2 = 1.0f - 0.5f * ht + (ht * ht) / 6.0f,
+// every operation rounded to float, left to right.  The march ran them as three Markstein divisions by the folded
+// reciprocals (div_by_recip<TINY_OK>, whose zero and tiny quotients the 1.0f absorbs), fifteen instructions; these nine
+// return the same two floats for EVERY float ht, zeros, subnormals, infinities and NaN included:
+// tests/test_step_factor_identities.py restates both sequences and compares them on all 2^32 bit patterns.
+//   * a / 3 and a / 12 in two operations: with C_HI = RN(1/b) and C_LO = RN(1/b - C_HI), fma(a, C_HI, RN(a * C_LO))
+//     is the correctly rounded a / b for these two divisors wherever that can show in f1 (where a * C_LO underflows the
+//     quotient is below 2^-100, and an infinite ht * ht gives NaN on both paths);
+//   * a / 6 = 2 RN(a / 12), exactly, outside the subnormal range, and the doubling rides in the fma that adds it;
+//   * 0.5f * ht is exact (or absorbed by the 1.0f), so 1.0f - 0.5f * ht is one fma.
+__device__ __forceinline__ void step_factors(float ht, float &f1, float &f2)
+{
+    const float C3_HI = 0x1.555556p-2f, C3_LO = -0x1.555556p-27f;   // 1/3  = C3_HI + C3_LO to 2^-49 of it
+    const float C12_HI = 0x1.555556p-4f, C12_LO = -0x1.555556p-29f; // 1/12 likewise
+    const float hh  = ht * ht;
+    const float d3  = fmaf(ht, C3_HI, ht * C3_LO);
+    const float d12 = fmaf(hh, C12_HI, hh * C12_LO);
+    f1 = 1.0f - d3 + d12;
+    f2 = fmaf(2.0f, d12, fmaf(-0.5f, ht, 1.0f));
+}
 
 // a / b as the hardware's IEEE sequence computes it (v_div_scale x2, v_rcp, five fma/mul, v_div_fmas,
 // v_div_fixup) minus the scaling and fix-up instructions: the same reciprocal, Newton step, quotient and two

@@ -401,6 +401,14 @@ int rtr::plan_create_on(rt_hip_plan **out, hipStream_t upload_q, int device, int
             }
             if (!(n_lo - dn >= 0.25 && n_hi + dn <= 4.0 && dn / w_min <= 1e12 && w_min >= 1e-12))
                 all_bounded = false;
+            // No quotient of the cross-cell set-up underflows (rt_march_xsetup.inc goes without the sign copy of a zero
+            // quotient on that ground).  The node indices are doubles in [0.25, 4]: two that differ differ by at least
+            // 2^-54, the spacing of the doubles at 0.25.  The other factor of a gradient dividend is a float v or 1 - v:
+            // not zero, it is at least 2^-149 in magnitude.  A width is the difference of two grid values a float
+            // position lies between, below 2^129.  So a non-zero gradient quotient is at least 2^-54 2^-149 2^-129 =
+            // 2^-332, far inside the double range: a gradient quotient that is a zero has a dividend that is a zero.
+            // (u and v themselves may underflow -- a position 2^-149 off a corner -- but a non-zero dividend gives the
+            // same double with and without the copy, rt_math.h: only a -0 dividend tells the forms apart.)
             // The largest index change a step can see.  The loop condition of the integrator tests the n of the step just
             // taken, n0 + rx gxn + ry gyn with the r that passed |rx| < 0.1 wx, |ry| < 0.1 wy one step earlier (no
             // overshoot enters), and |gxn| wx <= 1.2 dn (the two edge differences of the cell weighted with v, 1 - v for
