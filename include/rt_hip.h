@@ -597,8 +597,9 @@ int rt_hip_length_scan_loop(int device, int N, const rt_beam *beam, const rt_gai
  *   RT_N_FAILED_MAX: the first of them in list order).
  * rt_hip_suffix_scan_loop: the host-pointer form, rt_hip_length_scan_loop's arguments; row n - 2 holds the record of the
  *   last n lengths.
- * Not taken with the suffix scan: the forward method, seed sets, ASE seeds, scan seeds, the one-launch form, the
- *   multi-device loops, image, spectra and path runs.
+ * Not taken with the suffix scan: the forward method, seed sets, scan seeds, the ASE seeds of a plain step or of a length
+ *   scan (an emission plan takes rt_hip_plan_set_suffix_ase_seeds, below), the one-launch form, the multi-device loops,
+ *   image, spectra and path runs.
  */
 int rt_hip_plan_enable_suffix_scan(rt_hip_plan *plan, int on);
 int rt_hip_suffix_scan_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed, int method,
@@ -726,6 +727,7 @@ int rt_hip_full_step_loop(int device, int N, const rt_beam *beam, const rt_gain 
  *   *failure_code is the code of (r, n).  rt_hip_plan_fetch_length_step and rt_hip_plan_length_step_ptrs serve the ASE
  *   curve; rt_hip_plan_fetch_step, rt_hip_plan_step_ptrs and I_ang of rt_hip_plan_fetch serve (0, N).
  *   rt_hip_plan_fetch_full_step and rt_hip_plan_fetch_seed_length_step are RT_ERR_ARG after such a run.
+ *   (fetch_full_length_step and full_length_step_ptrs also serve the records of a suffix scan with ASE seeds, below.)
  * Failures follow the reference run once per (record, length): error -1 at length j puts the ray in no record of that
  *   length; error -2 / -3 under (r, j) removes the ray from (r, j) only.  rt_hip_plan_fetch reports the OR of all codes and
  *   the rays that fail anywhere, each once (more than RT_N_FAILED_MAX: the first of them in list order); the counters are
@@ -739,6 +741,46 @@ int rt_hip_plan_fetch_full_length_step(rt_hip_plan *plan, int r, int n, double *
                                        unsigned int *failure_code);
 int rt_hip_plan_full_length_step_ptrs(rt_hip_plan *plan, int r, int n, double **E_v_dev, double **nf_dev, double **iang_dev);
 int rt_hip_full_length_scan_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, int method, const rt_ray *rays,
+                                 size_t n_rays, double scale, int n_seed, const rt_seed *seeds, const double *scales,
+                                 double *E_v, double *nf, double *I_ang, unsigned int *failure_codes, rt_ray *failed_rays,
+                                 int max_failed, int *n_failed, rt_stats *stats);
+
+/*
+ * ASE seeds of a suffix scan: the WHOLE per-step record of the run of the LAST n lengths, n = 2 .. N, from ONE backward
+ * march.  RayTrace::create_image traces ASE with the backward method, so the gain-length curve of an emission step is the
+ * suffix scan above -- and the application's record of a step is the ASE triple plus one seeded triple per seed beam.  The
+ * march does not depend on the emission switch apart from evl and not on a seed at all: with suffix ASE seeds installed a
+ * step run of a backward emission plan whose suffix scan is on marches once (the suffix-scan march unchanged) and
+ * rt_step_rscan_ase_seeds_kernel (raytrace-miniapp_amd/csrc/rt_step_rscan_ase_seeds.hip, in place of rt_step_rscan_kernel;
+ * reported as freq_ms) leaves record (r, n) for r = 0 .. n_seed and n = 2 .. N:
+ *   (0, n)      record n of the plain emission suffix-scan plan;
+ *   (1 + s, n)  what a step run leaves of the suffix problem of the last n lengths CREATED WITH SEED s -- the same tables,
+ *               rays and method, scale scales[s]: gain-only, Iv[k] = f0_{s,n} f_s[4][k] exp(gl_n[k]), the seed factor at the
+ *               position and exit angles of the state that serves record n, 0 where the ray has escaped by then.
+ *   Every Iv is the double the plain emission suffix-scan plan, respectively the suffix-scan plan created with seed s,
+ *   computes; the sums differ from those plans' by summation order only.  A ray whose march sums over the whole N-run are
+ *   all zero (n_skipped) is left out of the ASE records and is part of the seed records.
+ * set_suffix_ase_seeds: accepted only on a backward (method 1) emission plan (created without a seed, tables with E0) while
+ *   its suffix scan is on; a forward plan, a plan created with a seed, a plan whose suffix scan is off, more than
+ *   RT_N_SEED_MAX seeds and a plan that holds ASE seeds, scan ASE seeds or a seed set are RT_ERR_ARG, each with its reason.
+ *   n_seed = 1 .. RT_N_SEED_MAX installs seeds[0 .. n_seed), validated and copied as rt_hip_plan_set_ase_seeds does it;
+ *   scales[s] is the scale of the curve of seed s, NULL: the plan's scale for all.  n_seed = 0 removes them: the plan is
+ *   then a plain suffix-scan plan.  rt_hip_plan_enable_suffix_scan(plan, 0) drops them; rt_hip_plan_update_gain / _dev keep
+ *   them.  Every refusal of the suffix scan stays: rt_hip_plan_set_seeds, rt_hip_plan_set_ase_seeds,
+ *   rt_hip_plan_set_scan_seeds and rt_hip_plan_set_scan_ase_seeds refuse such a plan as before.
+ * Outputs: the layout of a length scan with ASE seeds: (1 + n_seed) (N - 1) blocks of one allocation, record (r, n) = block
+ *   r (N - 1) + (n - 2), served by rt_hip_plan_fetch_full_length_step and rt_hip_plan_full_length_step_ptrs;
+ *   rt_hip_plan_fetch_length_step and rt_hip_plan_length_step_ptrs serve the ASE curve, rt_hip_plan_fetch_step,
+ *   rt_hip_plan_step_ptrs and I_ang of rt_hip_plan_fetch record (0, N).  rt_hip_plan_history_append files all of them.
+ * Failures follow the reference run once per (record, n): error -1 of the state that serves n puts the ray in no record
+ *   (r, n) and sets bit 1 in each of their codes; error -2 / -3 under (r, n) removes the ray from (r, n) only; a failing ray
+ *   is reported once.
+ * rt_hip_full_suffix_scan_loop: the host-pointer form, the arguments and rows of rt_hip_full_length_scan_loop.
+ * Not taken: the C++ adapter, the multi-device loops, the one-launch form (rt_hip_plan_set_step_one_launch is accepted, the
+ *   run keeps two kernels).
+ */
+int rt_hip_plan_set_suffix_ase_seeds(rt_hip_plan *plan, int n_seed, const rt_seed *seeds, const double *scales);
+int rt_hip_full_suffix_scan_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, int method, const rt_ray *rays,
                                  size_t n_rays, double scale, int n_seed, const rt_seed *seeds, const double *scales,
                                  double *E_v, double *nf, double *I_ang, unsigned int *failure_codes, rt_ray *failed_rays,
                                  int max_failed, int *n_failed, rt_stats *stats);

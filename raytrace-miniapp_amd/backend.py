@@ -134,7 +134,7 @@ class Plan:
         self.hl.check(rc, "rt_hip_plan_create")
         self.n_rays = 0
         self._n_ase_seed = 0    # ASE seeds installed (set_ase_seeds)
-        self._n_scan_ase_seed = 0   # ASE seeds of the length scan installed (set_scan_ase_seeds)
+        self._n_scan_ase_seed = 0   # ASE seeds of the length scan or of the suffix scan installed (set_scan_ase_seeds, set_suffix_ase_seeds)
 
     # -- rays ---------------------------------------------------------------
     def set_rays(self, rays: np.ndarray) -> "Plan":
@@ -443,6 +443,39 @@ class Plan:
                 raise ValueError(f"enable_suffix_scan: N - 1 = {p.N - 1} lengths, at most RT_N_SCAN_MAX = {cabi.RT_N_SCAN_MAX} fit into a scan")
         self.hl.check(self.hl.lib.rt_hip_plan_enable_suffix_scan(self._h, int(on)), "rt_hip_plan_enable_suffix_scan")
         self._scan = bool(on)   # (the records are the length scan's: _scan_seed_range counts them)
+        if not on:
+            self._n_scan_ase_seed = 0   # (switching the scan off drops its ASE seeds)
+        return self
+
+    def set_suffix_ase_seeds(self, seeds, scales=None) -> "Plan":
+        """The ASE seeds of the suffix scan (include/rt_hip.h, rt_hip_plan_set_suffix_ase_seeds): up to RT_N_SEED_MAX Seed
+        records on a backward EMISSION plan (created without a seed, tables with E0) whose suffix scan is on.  A step run
+        then leaves, from one backward march, the plan's emission record and the gain-only record of the same problem created
+        with each seed, scale scales[s] (None: the plan's scale), of the run of the last n lengths for n = 2 .. N;
+        fetch_full_length_steps, full_length_step_ptrs and full_length_step_tensors serve them; [] removes the seeds.  A
+        forward problem, a problem with a seed, a plan whose suffix scan is off or that holds ASE seeds or a seed set, more
+        seeds than that, anything that is not a Seed, or scales of another length is a ValueError raised here, before any
+        native call."""
+        p = self.problem
+        if p.method != 1:
+            raise ValueError(f"set_suffix_ase_seeds: the problem's method is {p.method}; the suffix scan takes the backward "
+                             "method (1) only (a forward plan takes set_scan_ase_seeds)")
+        if p.seed is not None:
+            raise ValueError("set_suffix_ase_seeds: the plan was created with a seed; the ASE record needs an emission plan")
+        if not getattr(self, "_scan", False):
+            raise ValueError("set_suffix_ase_seeds: the suffix scan is off (enable_suffix_scan first)")
+        if getattr(self, "_n_ase_seed", 0) > 0 or getattr(self, "_n_seed", 0) > 0:
+            raise ValueError("set_suffix_ase_seeds: the plan holds ASE seeds or a seed set; they and a suffix scan exclude each other")
+        seeds, arr, _keep = _seed_array(seeds, "set_suffix_ase_seeds", "a step record")
+        sc = None
+        if scales is not None:
+            sc = np.ascontiguousarray(scales, dtype=np.float64)
+            if sc.shape != (len(seeds),):
+                raise ValueError(f"set_suffix_ase_seeds: {sc.size} scales for {len(seeds)} seeds")
+        self.hl.check(self.hl.lib.rt_hip_plan_set_suffix_ase_seeds(self._h, len(seeds), arr if seeds else None,
+                                                                   cabi._dp(sc) if sc is not None and len(seeds) else None),
+                      "rt_hip_plan_set_suffix_ase_seeds")
+        self._n_scan_ase_seed = len(seeds)   # (the records are those of a length scan with ASE seeds: _full_length_range counts them)
         return self
 
     # -- the seeds of a scan ------------------------------------------------
@@ -890,40 +923,55 @@ def full_length_scan_loop(problem: Problem, seeds, scales=None, rays: np.ndarray
     [[rec per n] per seed], failure_code = the OR of the codes, failed_rays, stats), every rec dict(n, E_v, nf, I_ang,
     failure_code).  What the scan does not take, no seed or too many, an entry that is not a Seed, scales of another length
     or a problem with a seed is a ValueError raised here, before any native call."""
-    if problem.method != 2:
-        raise ValueError(f"full_length_scan_loop: the problem's method is {problem.method}; the scan takes the forward method (2) only")
+    return _full_scan_loop("full_length_scan_loop", 2, "the scan takes the forward method (2) only", problem, seeds, scales, rays, device)
+
+
+def full_suffix_scan_loop(problem: Problem, seeds, scales=None, rays: np.ndarray | None = None, device: int = 0) -> dict:
+    """The whole per-step record of the run of the LAST n lengths, n = 2 .. N, from ONE backward march of the problem's rays
+    (rt_hip_full_suffix_scan_loop, host pointers; rays None: the problem's ray grid as a list): the emission record of
+    problem.suffix_lengths(problem, n) and the gain-only record of that problem under each Seed of `seeds`
+    (1 .. RT_N_SEED_MAX) with scale scales[s] (None: the problem's scale).  Returns what full_length_scan_loop returns.  The
+    forward method, N < 3 or more than RT_N_SCAN_MAX lengths, no seed or too many, an entry that is not a Seed, scales of
+    another length or a problem with a seed is a ValueError raised here, before any native call."""
+    return _full_scan_loop("full_suffix_scan_loop", 1, "the suffix scan takes the backward method (1) only", problem, seeds, scales, rays, device)
+
+
+def _full_scan_loop(who: str, method: int, method_text: str, problem: Problem, seeds, scales, rays, device: int) -> dict:
+    """full_length_scan_loop (method 2) and full_suffix_scan_loop (method 1): the checks, the marshalling and the rows."""
+    if problem.method != method:
+        raise ValueError(f"{who}: the problem's method is {problem.method}; {method_text}")
     if problem.N < 3 or problem.N - 1 > cabi.RT_N_SCAN_MAX:
-        raise ValueError(f"full_length_scan_loop: N = {problem.N}; a scan takes 3 <= N <= RT_N_SCAN_MAX + 1 = {cabi.RT_N_SCAN_MAX + 1}")
+        raise ValueError(f"{who}: N = {problem.N}; a scan takes 3 <= N <= RT_N_SCAN_MAX + 1 = {cabi.RT_N_SCAN_MAX + 1}")
     seeds = list(seeds)
     if not 1 <= len(seeds) <= cabi.RT_N_SEED_MAX:
-        raise ValueError(f"full_length_scan_loop: {len(seeds)} seeds given, 1 .. RT_N_SEED_MAX = {cabi.RT_N_SEED_MAX} are taken")
+        raise ValueError(f"{who}: {len(seeds)} seeds given, 1 .. RT_N_SEED_MAX = {cabi.RT_N_SEED_MAX} are taken")
     for i, sd in enumerate(seeds):
         if not isinstance(sd, Seed):
-            raise ValueError(f"full_length_scan_loop: entry {i} is a {type(sd).__name__}, not a Seed")
+            raise ValueError(f"{who}: entry {i} is a {type(sd).__name__}, not a Seed")
     if problem.seed is not None:
-        raise ValueError("full_length_scan_loop: the problem carries a seed; the ASE record needs an emission problem")
+        raise ValueError(f"{who}: the problem carries a seed; the ASE record needs an emission problem")
     sc = None
     if scales is not None:
         sc = np.ascontiguousarray(scales, dtype=np.float64)
         if sc.shape != (len(seeds),):
-            raise ValueError(f"full_length_scan_loop: {sc.size} scales for {len(seeds)} seeds")
+            raise ValueError(f"{who}: {sc.size} scales for {len(seeds)} seeds")
     hl = HipLibrary.get()
     m = cabi.Marshalled(problem)
     if rays is None:
         rays = problem.build_rays()
     rays = np.ascontiguousarray(rays, dtype=cabi.RAY_DTYPE)
-    _, arr, _keep = _seed_array(seeds, "full_length_scan_loop", "a step record")   # (checked above: marshalled only)
+    _, arr, _keep = _seed_array(seeds, who, "a step record")   # (checked above: marshalled only)
     b, L, nr = problem.beam, problem.N - 1, 1 + len(seeds)
     E_v, nf, iang = np.zeros((nr, L, b.nv)), np.zeros((nr, L, b.nx * b.ny)), np.zeros((nr, L, b.na * b.nb))
     codes = (C.c_uint * (nr * L))()
     nfail = C.c_int(0)
     failed = np.zeros(cabi.RT_N_FAILED_MAX, dtype=cabi.RAY_DTYPE)
     st = cabi.RtStats()
-    rc = hl.lib.rt_hip_full_length_scan_loop(device, m.N, C.byref(m.beam), m.gain, problem.method, cabi.rays_ptr(rays), len(rays),
-                                             problem.scale, len(seeds), arr, cabi._dp(sc) if sc is not None else None, cabi._dp(E_v),
-                                             cabi._dp(nf), cabi._dp(iang), codes, cabi.rays_ptr(failed), cabi.RT_N_FAILED_MAX,
-                                             C.byref(nfail), C.byref(st))
-    hl.check(rc, "rt_hip_full_length_scan_loop")
+    rc = getattr(hl.lib, "rt_hip_" + who)(device, m.N, C.byref(m.beam), m.gain, problem.method, cabi.rays_ptr(rays), len(rays),
+                                          problem.scale, len(seeds), arr, cabi._dp(sc) if sc is not None else None, cabi._dp(E_v),
+                                          cabi._dp(nf), cabi._dp(iang), codes, cabi.rays_ptr(failed), cabi.RT_N_FAILED_MAX,
+                                          C.byref(nfail), C.byref(st))
+    hl.check(rc, "rt_hip_" + who)
     curves = [[dict(n=i + 2, E_v=E_v[r, i].copy(), nf=nf[r, i].copy(), I_ang=iang[r, i].copy(), failure_code=int(codes[r * L + i]))
                for i in range(L)] for r in range(nr)]
     code = 0

@@ -20,6 +20,7 @@
 #include "rt_step_scan_seeds.hip" // ... with the seeds of the scan: one record per (seed, length) from that march
 #include "rt_step_ase_seeds.hip"  // step kernel of an emission plan with ASE seeds: the ASE record and one per seed from one march
 #include "rt_step_scan_ase_seeds.hip" // ... with the length scan on: that whole record at every length from one forward march
+#include "rt_step_rscan_ase_seeds.hip" // ... with the suffix scan on: that whole record of the last n lengths from one backward march
 
 #include "rt_runtime.h"
 #include "rt_run_shape.h" // what a run looks like: the pure decision (facts + tuning -> shape) this file enqueues
@@ -280,7 +281,7 @@ int fill_seed_tabs(rt::SeedTabs &tb, const rt_hip_plan *p, int n_seed, bool grid
 
 // The second pass over all tiles as a kernel of its own: the frequency / deposit kernel, or in its place the spectra
 // kernel (per-ray spectra, no image), the step kernel (E_v, nf and I_ang, no image cube) or one of the step kernels that
-// leave several records (a seed set, ASE seeds, a length scan, a scan with its seeds: record_set(f) says how many).
+// leave several records (a seed set, ASE seeds, a length scan or a suffix scan, a scan with its seeds: record_set(f) says how many).
 int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kind, hipStream_t stream, unsigned safe = 0, unsigned char *bad = nullptr)
 {
     const PassShape s = pass_shape(kind, f, t);
@@ -295,9 +296,10 @@ int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kin
         "step kernel of a length scan with scan seeds: the E_v accumulators (nv doubles per seed and length) do not fit into the LDS of this device",
         "step kernel of an emission plan with ASE seeds: the E_v accumulators (nv doubles for ASE and per seed) do not fit into the LDS of this device",
         "step kernel of a length scan with ASE seeds: the E_v accumulators (nv doubles per record and length) do not fit into the LDS of this device",
-        "step kernel of a suffix scan: the E_v accumulators (nv doubles per length) do not fit into the LDS of this device" };
+        "step kernel of a suffix scan: the E_v accumulators (nv doubles per length) do not fit into the LDS of this device",
+        "step kernel of a suffix scan with ASE seeds: the E_v accumulators (nv doubles per record and length) do not fit into the LDS of this device" };
     static_assert(PASS_SPEC == 1 && PASS_STEP == 2 && PASS_SEEDS == 3 && PASS_SCAN == 5 && PASS_SCAN_SEEDS == 6 && PASS_ASE_SEEDS == 7 &&
-                      PASS_SCAN_ASE_SEEDS == 8 && PASS_RSCAN == 9 && sizeof(too_big) / sizeof(too_big[0]) == 10,
+                      PASS_SCAN_ASE_SEEDS == 8 && PASS_RSCAN == 9 && PASS_RSCAN_ASE_SEEDS == 10 && sizeof(too_big) / sizeof(too_big[0]) == 11,
                   "too_big[] is indexed by PassKind");
     if (too_big[kind] && s.lds > f.lds_limit)
         return fail_arg(too_big[kind]);
@@ -343,6 +345,25 @@ int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kin
         a.hot.flags &= ~(unsigned) rt::FQ_EXCLUSIVE; // (nf of every record by atomics)
         fill_scan(a.scan, p);
         return launch(p, rscan_kernel(f.use_emis), s.grid, block, s.lds, stream, a);
+    }
+    if (kind == PASS_RSCAN_ASE_SEEDS) { // a suffix scan with ASE seeds (a backward emission plan): one record per (ASE | seed, n)
+        if (!p->scan_bnd || !p->recs_dev)
+            return fail_arg("step kernel of a suffix scan with ASE seeds: the boundary states or the records of this run were not allocated");
+        if (f.n_seed < 1 || f.n_seed > RT_N_SEED_MAX || f.L > RT_N_SCAN_MAX || !f.use_emis || f.method != 1)
+            return fail_arg("step kernel of a suffix scan with ASE seeds: not a backward emission run of 1 .. RT_N_SEED_MAX seeds and at most RT_N_SCAN_MAX lengths");
+        if (p->recs_doubles < (size_t) n_rec * p->recs_stride)
+            return fail_arg("step kernel of a suffix scan with ASE seeds: the records of this run are smaller than (1 + n_seed) (N - 1) blocks");
+        rt::ScanAseSeedsKArg a = pass_args<rt::ScanAseSeedsKArg>(fa);
+        a.hot.iang     = nullptr; // (every record's I_ang lies in its block)
+        a.hot.seed_fk  = nullptr; // (an emission plan has no creation seed)
+        a.hot.flags &= ~(unsigned) rt::FQ_EXCLUSIVE; // (nf of every record by atomics)
+        fill_scan(a.scan, p);
+        a.set.n_seed   = f.n_seed;
+        for (int r = 0; r <= f.n_seed; r++)
+            a.set.scale[r] = r == 0 ? p->P.scale : p->ase_scale[r - 1];
+        // (the seed factor is taken at the state that serves a record, never at a grid point: no factor tables)
+        const int rc = fill_seed_tabs(a.set.tabs, p, f.n_seed, false, "step kernel of a suffix scan with ASE seeds: the factor tables of the seeds");
+        return rc != RT_OK ? rc : launch(p, rt::rt_step_rscan_ase_seeds_kernel, s.grid, block, s.lds, stream, a);
     }
     if (kind == PASS_SCAN_SEEDS) { // a length scan with scan seeds (a seeded plan: gain-only): one record per (seed, length)
         if (!p->scan_bnd || !p->recs_dev)

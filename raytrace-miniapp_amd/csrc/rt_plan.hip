@@ -1483,6 +1483,14 @@ int rt_hip_plan_enable_suffix_scan(rt_hip_plan *p, int on)
         pool_free(p->device, p->scan_bnd);
         p->scan_bnd       = nullptr;
         p->scan_bnd_bytes = 0;
+        if (p->n_scan_seed > 0) { // ... and so do the ASE seeds of the scan (rt_hip_plan_set_suffix_ase_seeds)
+            p->n_scan_seed = 0;
+            (void) hipFree(p->seedset_arena);
+            p->seedset_arena = nullptr;
+            for (int s = 0; s < RT_N_SEED_MAX; s++)
+                p->seed_set[s] = rt::DevSeed{};
+            return plan_build_seedset_tabs(p); // (a backward plan has no factor tables: this leaves none)
+        }
     }
     return RT_OK;
 }
@@ -1673,9 +1681,38 @@ int rt_hip_plan_set_scan_ase_seeds(rt_hip_plan *p, int n_seed, const rt_seed *se
     return RT_OK;
 }
 
+// ASE seeds of a suffix scan: the same seeds on a BACKWARD emission plan whose suffix scan is on (include/rt_hip.h).  They
+// travel as the seeds of a scan do (n_scan_seed); the plan's method says which scan they belong to.
+int rt_hip_plan_set_suffix_ase_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds, const double *scales)
+{
+    if (!p)
+        return fail_arg("rt_hip_plan_set_suffix_ase_seeds: NULL plan");
+    if (p->P.method != 1)
+        return fail_arg("rt_hip_plan_set_suffix_ase_seeds: the plan's method is not 1 (a forward plan takes rt_hip_plan_set_scan_ase_seeds)");
+    if (p->P.has_seed)
+        return fail_arg("rt_hip_plan_set_suffix_ase_seeds: the plan was created with a seed (the ASE record needs an emission plan)");
+    if (!p->P.use_emis)
+        return fail_arg("rt_hip_plan_set_suffix_ase_seeds: not an emission plan (tables without E0)");
+    if (!p->scan_on)
+        return fail_arg("rt_hip_plan_set_suffix_ase_seeds: the suffix scan is off (rt_hip_plan_enable_suffix_scan first)");
+    if (n_seed > RT_N_SEED_MAX)
+        return fail_arg("rt_hip_plan_set_suffix_ase_seeds: more than RT_N_SEED_MAX seeds");
+    if (p->n_seed > 0) // (no call leads here: every installer of a set or of ASE seeds refuses a plan whose suffix scan is on)
+        return fail_arg("rt_hip_plan_set_suffix_ase_seeds: the plan holds ASE seeds or a seed set (they and a suffix scan exclude each other)");
+    const int rv = seeds_validate(p, "rt_hip_plan_set_suffix_ase_seeds", n_seed, seeds);
+    if (rv != RT_OK)
+        return rv;
+    const int rc = seeds_install(p, n_seed, seeds, true);
+    if (rc != RT_OK)
+        return rc;
+    for (int s = 0; s < RT_N_SEED_MAX; s++)
+        p->ase_scale[s] = (s < n_seed && scales) ? scales[s] : p->P.scale;
+    return RT_OK;
+}
+
 int rt_hip_plan_fetch_full_length_step(rt_hip_plan *p, int r, int n, double *E_v, double *nf, double *I_ang, unsigned int *failure_code)
 {
-    if (!p || p->last_records.kind != REC_SCAN_ASE_SEEDS)
+    if (!p || !p->last_records.ase_scan()) // (of a length scan or of a suffix scan, as rt_hip_plan_fetch_length_step serves both scans)
         return fail_arg("rt_hip_plan_fetch_full_length_step: the last run was not a step run of a length scan with ASE seeds");
     if (p->last_records.block(r, 2) < 0) // (every scan has length 2)
         return fail_arg("rt_hip_plan_fetch_full_length_step: r must be 0 (ASE) .. n_seed of the last run");
@@ -1686,7 +1723,7 @@ int rt_hip_plan_fetch_full_length_step(rt_hip_plan *p, int r, int n, double *E_v
 
 int rt_hip_plan_full_length_step_ptrs(rt_hip_plan *p, int r, int n, double **E_v_dev, double **nf_dev, double **iang_dev)
 {
-    if (!p || p->last_records.kind != REC_SCAN_ASE_SEEDS)
+    if (!p || !p->last_records.ase_scan())
         return fail_arg("rt_hip_plan_full_length_step_ptrs: the last run was not a step run of a length scan with ASE seeds");
     if (p->last_records.block(r, 2) < 0)
         return fail_arg("rt_hip_plan_full_length_step_ptrs: r must be 0 (ASE) .. n_seed of the last run");
@@ -2020,8 +2057,9 @@ int rt_hip_seed_length_scan_loop(int device, int N, const rt_beam *beam, const r
 
 // The whole per-step record through host pointers: an emission plan of its own with the seeds as ASE seeds, the list
 // uploaded, one run; row 0 of every output is the ASE record, row 1 + s seed s.
-// (scan: rt_hip_full_length_scan_loop -- the length scan on, the seeds as its ASE seeds, rows [1 + n_seed][N - 1][...])
-static int full_step_loop(const char *who, bool scan, int device, int N, const rt_beam *beam, const rt_gain *gain, int method, const rt_ray *rays,
+// (scan 1: rt_hip_full_length_scan_loop -- the length scan on, the seeds as its ASE seeds, rows [1 + n_seed][N - 1][...];
+// scan 2: rt_hip_full_suffix_scan_loop -- the same with the suffix scan of a backward plan)
+static int full_step_loop(const char *who, int scan, int device, int N, const rt_beam *beam, const rt_gain *gain, int method, const rt_ray *rays,
                           size_t n_rays, double scale, int n_seed, const rt_seed *seeds, const double *scales, double *E_v, double *nf, double *I_ang,
                           unsigned int *failure_codes, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats)
 {
@@ -2045,9 +2083,11 @@ static int full_step_loop(const char *who, bool scan, int device, int N, const r
     }
     rc = rt_hip_plan_enable_step(p, 1);
     if (rc == RT_OK && scan)
-        rc = rt_hip_plan_enable_length_scan(p, 1);
+        rc = scan == 2 ? rt_hip_plan_enable_suffix_scan(p, 1) : rt_hip_plan_enable_length_scan(p, 1);
     if (rc == RT_OK)
-        rc = scan ? rt_hip_plan_set_scan_ase_seeds(p, n_seed, seeds, scales) : rt_hip_plan_set_ase_seeds(p, n_seed, seeds, scales);
+        rc = scan == 2 ? rt_hip_plan_set_suffix_ase_seeds(p, n_seed, seeds, scales)
+             : scan  ? rt_hip_plan_set_scan_ase_seeds(p, n_seed, seeds, scales)
+                     : rt_hip_plan_set_ase_seeds(p, n_seed, seeds, scales);
     if (rc == RT_OK)
         rc = plan_set_rays_deferred(p, rays, n_rays);
     if (rc == RT_OK)
@@ -2065,7 +2105,7 @@ int rt_hip_full_step_loop(int device, int N, const rt_beam *beam, const rt_gain 
                           double scale, int n_seed, const rt_seed *seeds, const double *scales, double *E_v, double *nf, double *I_ang,
                           unsigned int *failure_codes, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats)
 {
-    return full_step_loop("rt_hip_full_step_loop", false, device, N, beam, gain, method, rays, n_rays, scale, n_seed, seeds, scales, E_v, nf, I_ang,
+    return full_step_loop("rt_hip_full_step_loop", 0, device, N, beam, gain, method, rays, n_rays, scale, n_seed, seeds, scales, E_v, nf, I_ang,
                           failure_codes, failed_rays, max_failed, n_failed, stats);
 }
 
@@ -2074,7 +2114,16 @@ int rt_hip_full_length_scan_loop(int device, int N, const rt_beam *beam, const r
                                  double scale, int n_seed, const rt_seed *seeds, const double *scales, double *E_v, double *nf, double *I_ang,
                                  unsigned int *failure_codes, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats)
 {
-    return full_step_loop("rt_hip_full_length_scan_loop", true, device, N, beam, gain, method, rays, n_rays, scale, n_seed, seeds, scales, E_v, nf,
+    return full_step_loop("rt_hip_full_length_scan_loop", 1, device, N, beam, gain, method, rays, n_rays, scale, n_seed, seeds, scales, E_v, nf,
+                          I_ang, failure_codes, failed_rays, max_failed, n_failed, stats);
+}
+
+// ... of the run of the LAST n lengths, n = 2 .. N: the suffix scan of a backward plan on, the seeds as its ASE seeds; the same rows
+int rt_hip_full_suffix_scan_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, int method, const rt_ray *rays, size_t n_rays,
+                                 double scale, int n_seed, const rt_seed *seeds, const double *scales, double *E_v, double *nf, double *I_ang,
+                                 unsigned int *failure_codes, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats)
+{
+    return full_step_loop("rt_hip_full_suffix_scan_loop", 2, device, N, beam, gain, method, rays, n_rays, scale, n_seed, seeds, scales, E_v, nf,
                           I_ang, failure_codes, failed_rays, max_failed, n_failed, stats);
 }
 
