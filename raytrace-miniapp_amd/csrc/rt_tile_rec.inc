@@ -16,7 +16,7 @@
 //               zeros, and they must not steer the tile-wide choice --; image and step mode pass true: there the choice
 //               is taken over every lane that holds a ray, live or not (the choice decides the arithmetic, and step
 //               mode's arithmetic is image mode's), and what a lane without a live ray integrates is dropped later.
-// Declares: gs[], rs[], off[], exact_emis, irregular, all_regular, big, all_small, gv_nan, load_rows.
+// Declares: gs[], rs[], off[], exact_emis, irregular, idle, all_regular, big, all_small, gv_nan, load_rows.
 //
 // off[s]: byte offset of the lineshape row of sub-segment s inside its length's table (32 bits:
 // rt_hip_plan_create refuses tables of 4 GiB), so that a row load is SGPR base + VGPR offset
@@ -45,17 +45,25 @@ if (SF) {
         irregular = irregular || (!regular && (gs[s] != 0.0f || e1 != 0.0f));
     }
 }
-// no such sub-segment in the whole tile (the rule): the six updates of a frequency batch run
-// as one straight-line block, so the table reads of one overlap the arithmetic of another
-const bool all_regular = __ballot(irregular) == 0ull;
-// ... and every |gs w| of the tile stays below 80 (the rule as well): the float32 range reduction (ase_step_f32)
-bool big = false;
+// every |gs w| of the lane stays below 80 (the rule): the float32 range reduction (ase_step_f32)
+bool big  = false;
+bool idle = false; // a slot with gs = 0: the identity (with es != 0 the lane is irregular already)
 if (SF) {
 #pragma unroll
-    for (int s = 0; s < SF; s++)
-        big = big || !(fabsf(gs[s]) <= H.gs_cap * (80.0f / 708.0f));
+    for (int s = 0; s < SF; s++) {
+        big  = big || !(fabsf(gs[s]) <= H.gs_cap * (80.0f / 708.0f));
+        idle = idle || gs[s] == 0.0f;
+    }
 }
-const bool all_small = all_regular && __ballot(big) == 0ull;
+// no irregular sub-segment in the whole tile (the rule): the six updates of a frequency batch run
+// as one straight-line block, so the table reads of one overlap the arithmetic of another.
+// That block runs an identity slot as an update with e^x - 1 = 0: exact while Iv is finite, 0 * inf = NaN once Iv has
+// overflowed, where the CPU keeps the infinity (Helper.h:549-557: Iv (1 + gl (1 + gl / 2)) with gl = 0) and the ray does
+// not fail.  Iv cannot overflow while every |gs w| <= 80: |Iv| <= SF max |rs| e^(80 SF) with |rs| <= FLT_MAX / RT_RS_MIN,
+// 6e277 for SF = 6.  So a lane that is big AND holds an identity slot (an escaped ray: the slots it never wrote) sends
+// its tile to the per-slot branch, which skips identities.
+const bool all_regular = __ballot(irregular || (idle && big)) == 0ull;
+const bool all_small   = all_regular && __ballot(big) == 0ull;
 // a NaN or an infinity among the lineshape values (the CPU's 0 * NaN, 0 * inf and inf / inf: every one of them
 // leaves Iv = NaN, Helper.h:549-557) is tested per frequency only when the host scan of the tables found one
 const bool gv_nan = (hflags & FQ_GV_NAN) != 0;
