@@ -118,8 +118,56 @@ def _seed_array(seeds, who: str, what: str) -> tuple:
     return seeds, arr, keep
 
 
+def _taken_seeds(who: str, seeds) -> list:
+    """`seeds` as a list for a loop that takes 1 .. RT_N_SEED_MAX of them, every entry a Seed; anything else is a ValueError."""
+    seeds = list(seeds)
+    if not 1 <= len(seeds) <= cabi.RT_N_SEED_MAX:
+        raise ValueError(f"{who}: {len(seeds)} seeds given, 1 .. RT_N_SEED_MAX = {cabi.RT_N_SEED_MAX} are taken")
+    for i, sd in enumerate(seeds):
+        if not isinstance(sd, Seed):
+            raise ValueError(f"{who}: entry {i} is a {type(sd).__name__}, not a Seed")
+    return seeds
+
+
+def _scales_arg(who: str, scales, n: int):
+    """`scales` as a float64 array of n entries (None stays None: the plan's scale); another length is a ValueError."""
+    if scales is None:
+        return None
+    sc = np.ascontiguousarray(scales, dtype=np.float64)
+    if sc.shape != (n,):
+        raise ValueError(f"{who}: {sc.size} scales for {n} seeds")
+    return sc
+
+
+def _on_arg(who: str, on) -> int:
+    """`on` as 0 / 1; anything but a bool or 0 / 1 is a ValueError."""
+    if isinstance(on, bool):
+        on = int(on)
+    if not isinstance(on, (int, np.integer)) or on not in (0, 1):
+        raise ValueError(f"{who}: on is True / False (or 1 / 0), not {on!r}")
+    return int(on)
+
+
+def _scan_takes(who: str, problem: Problem, method: int, only: str) -> None:
+    """The loops of a scan: another method than the scan's, N < 3 or more than RT_N_SCAN_MAX lengths is a ValueError."""
+    if problem.method != method:
+        raise ValueError(f"{who}: the problem's method is {problem.method}; {only}")
+    if problem.N < 3 or problem.N - 1 > cabi.RT_N_SCAN_MAX:
+        raise ValueError(f"{who}: N = {problem.N}; a scan takes 3 <= N <= RT_N_SCAN_MAX + 1 = {cabi.RT_N_SCAN_MAX + 1}")
+
+
 class Plan:
     """A problem resident in HBM: tables uploaded once, runnable many times."""
+
+    # What the plan has been switched to, as the methods below record it.  Class-level defaults: they hold for a plan of any
+    # making (the host tests build one without a device, around __init__).
+    _spectra = _step = False    # the output mode (enable_spectra, enable_step)
+    _ring = 0                   # runs of the timing ring (set_timing_ring)
+    _scan = False               # the length scan or the suffix scan is on (enable_length_scan, enable_suffix_scan)
+    _n_seed = 0                 # seeds of the set (set_seeds)
+    _n_scan_seed = 0            # seeds of the length scan (set_scan_seeds)
+    _n_ase_seed = 0             # ASE seeds (set_ase_seeds)
+    _n_scan_ase_seed = 0        # ASE seeds of the length scan or of the suffix scan (set_scan_ase_seeds, set_suffix_ase_seeds)
 
     def __init__(self, problem: Problem, device: int = 0, lib: HipLibrary | None = None,
                  method: int | None = None):
@@ -133,8 +181,6 @@ class Plan:
                                             problem.method if method is None else method, problem.scale)
         self.hl.check(rc, "rt_hip_plan_create")
         self.n_rays = 0
-        self._n_ase_seed = 0    # ASE seeds installed (set_ase_seeds)
-        self._n_scan_ase_seed = 0   # ASE seeds of the length scan or of the suffix scan installed (set_scan_ase_seeds, set_suffix_ase_seeds)
 
     # -- rays ---------------------------------------------------------------
     def set_rays(self, rays: np.ndarray) -> "Plan":
@@ -176,9 +222,9 @@ class Plan:
 
     def fetch(self, want_image: bool = True) -> dict:
         b = self.problem.beam
-        want_image = want_image and not getattr(self, "_spectra", False)  # a spectra run has no image
+        want_image = want_image and not self._spectra  # a spectra run has no image
         want_iang = want_image
-        want_image = want_image and not getattr(self, "_step", False)     # ... and a step run has I_ang only
+        want_image = want_image and not self._step     # ... and a step run has I_ang only
         image = np.empty(b.nx * b.ny * b.nv) if want_image else None
         iang = np.empty(b.na * b.nb) if want_iang else None
         code = C.c_uint(0)
@@ -269,11 +315,8 @@ class Plan:
         """Step runs as ONE launch where that applies (include/rt_hip.h, rt_hip_plan_set_step_one_launch): emission on a ray
         grid of the beam, tables in LDS; everything else keeps the march and the step kernel.  Off by default.  Anything
         but a bool or 0 / 1 is a ValueError raised here, before any native call."""
-        if isinstance(on, bool):
-            on = int(on)
-        if not isinstance(on, (int, np.integer)) or on not in (0, 1):
-            raise ValueError(f"set_step_one_launch: on is True / False (or 1 / 0), not {on!r}")
-        self.hl.check(self.hl.lib.rt_hip_plan_set_step_one_launch(self._h, int(on)), "rt_hip_plan_set_step_one_launch")
+        on = _on_arg("set_step_one_launch", on)
+        self.hl.check(self.hl.lib.rt_hip_plan_set_step_one_launch(self._h, on), "rt_hip_plan_set_step_one_launch")
         return self
 
     def fetch_step(self) -> dict:
@@ -332,7 +375,7 @@ class Plan:
     def fetch_seed_steps(self) -> list:
         """[dict(E_v [nv], nf [nx * ny], I_ang [na * nb], failure_code)] per seed of the set of the last step run (waits for
         it; a failing run is repeated in the checking mode first)."""
-        return [self._fetch_record("rt_hip_plan_fetch_seed_step", s) for s in range(getattr(self, "_n_seed", 0))]
+        return [self._fetch_record("rt_hip_plan_fetch_seed_step", s) for s in range(self._n_seed)]
 
     def seed_step_ptrs(self, s: int) -> tuple:
         """Device pointers (E_v, nf, I_ang) of the record of seed s of the last step run with a set."""
@@ -342,7 +385,7 @@ class Plan:
         """Per seed of the set: torch views (float64, on the plan's device, no copy) of E_v [nv], nf [ny][nx] and I_ang
         [nb][na] of the last step run -- blocks of one allocation, valid until the plan's next run; read them on the
         run's stream or after a fetch."""
-        return [self._record_views(self.seed_step_ptrs(s)) for s in range(getattr(self, "_n_seed", 0))]
+        return [self._record_views(self.seed_step_ptrs(s)) for s in range(self._n_seed)]
 
     # -- ASE seeds ----------------------------------------------------------
     def set_ase_seeds(self, seeds, scales=None) -> "Plan":
@@ -351,17 +394,18 @@ class Plan:
         march, the gain-only record of the same problem created with each seed, scale scales[s] (None: the plan's scale);
         [] removes them.  More seeds than that, anything that is not a Seed, or scales of another length is a ValueError
         raised here, before any native call."""
-        seeds, arr, _keep = _seed_array(seeds, "set_ase_seeds", "a step record")
-        sc = None
-        if scales is not None:
-            sc = np.ascontiguousarray(scales, dtype=np.float64)
-            if sc.shape != (len(seeds),):
-                raise ValueError(f"set_ase_seeds: {sc.size} scales for {len(seeds)} seeds")
-        self.hl.check(self.hl.lib.rt_hip_plan_set_ase_seeds(self._h, len(seeds), arr if seeds else None,
-                                                            cabi._dp(sc) if sc is not None and len(seeds) else None),
-                      "rt_hip_plan_set_ase_seeds")
-        self._n_ase_seed = len(seeds)
+        self._n_ase_seed = self._install_ase_seeds("set_ase_seeds", seeds, scales)
         return self
+
+    def _install_ase_seeds(self, who: str, seeds, scales) -> int:
+        """set_ase_seeds, set_scan_ase_seeds and set_suffix_ase_seeds behind their own checks: the seeds and their scales,
+        checked and marshalled, through rt_hip_plan_<who>; returns how many were installed."""
+        seeds, arr, _keep = _seed_array(seeds, who, "a step record")
+        sc = _scales_arg(who, scales, len(seeds))
+        self.hl.check(getattr(self.hl.lib, "rt_hip_plan_" + who)(self._h, len(seeds), arr if seeds else None,
+                                                                 cabi._dp(sc) if sc is not None and len(seeds) else None),
+                      "rt_hip_plan_" + who)
+        return len(seeds)
 
     def fetch_full_step(self) -> dict:
         """dict(ase=rec, seeds=[rec ...]) of the last step run with ASE seeds (waits for it; a failing run is repeated in
@@ -386,24 +430,23 @@ class Plan:
         every plasma length n = 2 .. N -- record n is what a step run of problem.prefix_lengths(p, n) leaves -- from ONE
         march.  Forward method only, 3 <= N <= RT_N_SCAN_MAX + 1.  Anything else, or an `on` that is not a bool or 0 / 1, is
         a ValueError raised here, before any native call."""
-        if isinstance(on, bool):
-            on = int(on)
-        if not isinstance(on, (int, np.integer)) or on not in (0, 1):
-            raise ValueError(f"enable_length_scan: on is True / False (or 1 / 0), not {on!r}")
+        return self._enable_scan("enable_length_scan", on, 2, "forward method (2) has the marches of fewer lengths as prefixes of its own")
+
+    def _enable_scan(self, who: str, on, method: int, only: str) -> "Plan":
+        """enable_length_scan (method 2, which it asks for when switching on) and enable_suffix_scan (method 1, always)."""
+        on = _on_arg(who, on)
+        p = self.problem
+        if (on or method == 1) and p.method != method:
+            raise ValueError(f"{who}: the problem's method is {p.method}; only the {only}")
         if on:
-            p = self.problem
-            if p.method != 2:
-                raise ValueError(f"enable_length_scan: the problem's method is {p.method}; only the forward method (2) has the "
-                                 "marches of fewer lengths as prefixes of its own")
             if p.N < 3:
-                raise ValueError(f"enable_length_scan: N = {p.N}; a scan needs at least two lengths (N >= 3)")
+                raise ValueError(f"{who}: N = {p.N}; a scan needs at least two lengths (N >= 3)")
             if p.N - 1 > cabi.RT_N_SCAN_MAX:
-                raise ValueError(f"enable_length_scan: N - 1 = {p.N - 1} lengths, at most RT_N_SCAN_MAX = {cabi.RT_N_SCAN_MAX} fit into a scan")
-        self.hl.check(self.hl.lib.rt_hip_plan_enable_length_scan(self._h, int(on)), "rt_hip_plan_enable_length_scan")
-        self._scan = bool(on)
+                raise ValueError(f"{who}: N - 1 = {p.N - 1} lengths, at most RT_N_SCAN_MAX = {cabi.RT_N_SCAN_MAX} fit into a scan")
+        self.hl.check(getattr(self.hl.lib, "rt_hip_plan_" + who)(self._h, on), "rt_hip_plan_" + who)
+        self._scan = bool(on)   # (the records of either scan are the length scan's: _scan_seed_range counts them)
         if not on:
-            self._n_scan_seed = 0   # (switching the scan off drops its seeds)
-            self._n_scan_ase_seed = 0
+            self._n_scan_seed = self._n_scan_ase_seed = 0   # (switching the scan off drops its seeds)
         return self
 
     def fetch_length_steps(self) -> list:
@@ -428,24 +471,7 @@ class Plan:
         ONE backward march; fetch_length_steps, length_step_ptrs and length_step_tensors serve the records.  Backward method
         only, 3 <= N <= RT_N_SCAN_MAX + 1.  Anything else, or an `on` that is not a bool or 0 / 1, is a ValueError raised here,
         before any native call."""
-        if isinstance(on, bool):
-            on = int(on)
-        if not isinstance(on, (int, np.integer)) or on not in (0, 1):
-            raise ValueError(f"enable_suffix_scan: on is True / False (or 1 / 0), not {on!r}")
-        p = self.problem
-        if p.method != 1:
-            raise ValueError(f"enable_suffix_scan: the problem's method is {p.method}; only the backward method (1) begins "
-                             "with the marches of the last lengths")
-        if on:
-            if p.N < 3:
-                raise ValueError(f"enable_suffix_scan: N = {p.N}; a scan needs at least two lengths (N >= 3)")
-            if p.N - 1 > cabi.RT_N_SCAN_MAX:
-                raise ValueError(f"enable_suffix_scan: N - 1 = {p.N - 1} lengths, at most RT_N_SCAN_MAX = {cabi.RT_N_SCAN_MAX} fit into a scan")
-        self.hl.check(self.hl.lib.rt_hip_plan_enable_suffix_scan(self._h, int(on)), "rt_hip_plan_enable_suffix_scan")
-        self._scan = bool(on)   # (the records are the length scan's: _scan_seed_range counts them)
-        if not on:
-            self._n_scan_ase_seed = 0   # (switching the scan off drops its ASE seeds)
-        return self
+        return self._enable_scan("enable_suffix_scan", on, 1, "backward method (1) begins with the marches of the last lengths")
 
     def set_suffix_ase_seeds(self, seeds, scales=None) -> "Plan":
         """The ASE seeds of the suffix scan (include/rt_hip.h, rt_hip_plan_set_suffix_ase_seeds): up to RT_N_SEED_MAX Seed
@@ -462,20 +488,12 @@ class Plan:
                              "method (1) only (a forward plan takes set_scan_ase_seeds)")
         if p.seed is not None:
             raise ValueError("set_suffix_ase_seeds: the plan was created with a seed; the ASE record needs an emission plan")
-        if not getattr(self, "_scan", False):
+        if not self._scan:
             raise ValueError("set_suffix_ase_seeds: the suffix scan is off (enable_suffix_scan first)")
-        if getattr(self, "_n_ase_seed", 0) > 0 or getattr(self, "_n_seed", 0) > 0:
+        if self._n_ase_seed > 0 or self._n_seed > 0:
             raise ValueError("set_suffix_ase_seeds: the plan holds ASE seeds or a seed set; they and a suffix scan exclude each other")
-        seeds, arr, _keep = _seed_array(seeds, "set_suffix_ase_seeds", "a step record")
-        sc = None
-        if scales is not None:
-            sc = np.ascontiguousarray(scales, dtype=np.float64)
-            if sc.shape != (len(seeds),):
-                raise ValueError(f"set_suffix_ase_seeds: {sc.size} scales for {len(seeds)} seeds")
-        self.hl.check(self.hl.lib.rt_hip_plan_set_suffix_ase_seeds(self._h, len(seeds), arr if seeds else None,
-                                                                   cabi._dp(sc) if sc is not None and len(seeds) else None),
-                      "rt_hip_plan_set_suffix_ase_seeds")
-        self._n_scan_ase_seed = len(seeds)   # (the records are those of a length scan with ASE seeds: _full_length_range counts them)
+        # (the records are those of a length scan with ASE seeds: _full_length_range counts them)
+        self._n_scan_ase_seed = self._install_ase_seeds("set_suffix_ase_seeds", seeds, scales)
         return self
 
     # -- the seeds of a scan ------------------------------------------------
@@ -490,8 +508,8 @@ class Plan:
         return self
 
     def _scan_seed_range(self):
-        on = getattr(self, "_scan", False)
-        return range(getattr(self, "_n_scan_seed", 0) if on else 0), range(2, self.problem.N + 1 if on else 2)
+        on = self._scan
+        return range(self._n_scan_seed if on else 0), range(2, self.problem.N + 1 if on else 2)
 
     def fetch_seed_length_steps(self) -> list:
         """Per scan seed: [dict(n, E_v [nv], nf [nx * ny], I_ang [na * nb], failure_code)] for n = 2 .. N lengths of the last
@@ -517,20 +535,11 @@ class Plan:
         forward march, the plan's emission record and the gain-only record of the same problem created with each seed, scale
         scales[s] (None: the plan's scale), at every length n = 2 .. N; [] removes them.  More seeds than that, anything that is
         not a Seed, or scales of another length is a ValueError raised here, before any native call."""
-        seeds, arr, _keep = _seed_array(seeds, "set_scan_ase_seeds", "a step record")
-        sc = None
-        if scales is not None:
-            sc = np.ascontiguousarray(scales, dtype=np.float64)
-            if sc.shape != (len(seeds),):
-                raise ValueError(f"set_scan_ase_seeds: {sc.size} scales for {len(seeds)} seeds")
-        self.hl.check(self.hl.lib.rt_hip_plan_set_scan_ase_seeds(self._h, len(seeds), arr if seeds else None,
-                                                                 cabi._dp(sc) if sc is not None and len(seeds) else None),
-                      "rt_hip_plan_set_scan_ase_seeds")
-        self._n_scan_ase_seed = len(seeds)
+        self._n_scan_ase_seed = self._install_ase_seeds("set_scan_ase_seeds", seeds, scales)
         return self
 
     def _full_length_range(self):
-        on = getattr(self, "_scan", False) and self._n_scan_ase_seed > 0
+        on = self._scan and self._n_scan_ase_seed > 0
         return range(1 + self._n_scan_ase_seed if on else 0), range(2, self.problem.N + 1 if on else 2)
 
     def fetch_full_length_steps(self) -> dict:
@@ -700,7 +709,7 @@ class Plan:
 
     def ring_times(self) -> list:
         """[(march_ms, freq_ms)] of the most recent runs, oldest first (waits for the last run)."""
-        n = getattr(self, "_ring", 0)
+        n = self._ring
         if n < 1:
             return []
         a = np.zeros(n, np.float32)
@@ -750,56 +759,70 @@ class Plan:
             pass
 
 
-def image_loop(problem: Problem, rays: np.ndarray | None = None, device: int = 0) -> dict:
-    """RayTraceImageHipLoop through the host-pointer entry point
-    (rt_hip_image_loop): upload, trace, download.  Returns image, I_ang,
-    failure_code, failed_rays, stats."""
+def _host_loop(entry: str, problem: Problem, rays, device: int, lead: tuple = (), seeds=None, scales=None, ase: bool = False,
+               image: bool = False) -> dict:
+    """One call of the host-pointer entry point `entry` of the C ABI: the problem, the rays (None: the problem's ray grid as a
+    list) and the seeds (None: the entry point takes none; `ase`: an entry point of ASE seeds -- no creation seed, `scales`
+    behind the seeds) marshalled, the outputs allocated -- `image`: the cube and I_ang; else E_v, nf and I_ang with the leading
+    shape `lead` of the rows: (), (L,), (ns, L), (nr,) or (nr, L) --, the call timed and checked.  Returns dict(outs = the
+    output arrays, codes = the failure codes [lead], failure_code = their OR, failed_rays, stats, call_ms = the C call alone
+    (what a C++ caller of the adapter waits for))."""
     hl = HipLibrary.get()
     m = cabi.Marshalled(problem)
     if rays is None:
         rays = problem.build_rays()
     rays = np.ascontiguousarray(rays, dtype=cabi.RAY_DTYPE)
     b = problem.beam
-    image = np.zeros(b.nx * b.ny * b.nv)
-    iang = np.zeros(b.na * b.nb)
-    code = C.c_uint(0)
-    nf = C.c_int(0)
+    sizes = (b.nx * b.ny * b.nv, b.na * b.nb) if image else (b.nv, b.nx * b.ny, b.na * b.nb)
+    outs = [np.zeros(lead + (n,)) for n in sizes]
+    codes = np.zeros(lead, np.uint32)
+    nfail = C.c_int(0)
     failed = np.zeros(cabi.RT_N_FAILED_MAX, dtype=cabi.RAY_DTYPE)
     st = cabi.RtStats()
+    args = [device, m.N, C.byref(m.beam), m.gain] + ([] if ase else [m.seed_ref])
+    args += [problem.method, cabi.rays_ptr(rays), len(rays), problem.scale]
+    if seeds is not None:
+        _, arr, _keep = _seed_array(seeds, entry, "a call")   # (checked by the caller: marshalled only)
+        args += [len(seeds), arr] + ([cabi._dp(scales) if scales is not None else None] if ase else [])
+    args += [cabi._dp(o) for o in outs] + [codes.ctypes.data_as(C.POINTER(C.c_uint)), cabi.rays_ptr(failed), cabi.RT_N_FAILED_MAX,
+                                          C.byref(nfail), C.byref(st)]
     t0 = time.perf_counter()
-    rc = hl.lib.rt_hip_image_loop(device, m.N, C.byref(m.beam), m.gain, m.seed_ref, problem.method,
-                                  cabi.rays_ptr(rays), len(rays), problem.scale, cabi._dp(image),
-                                  cabi._dp(iang), C.byref(code), cabi.rays_ptr(failed),
-                                  cabi.RT_N_FAILED_MAX, C.byref(nf), C.byref(st))
-    call_ms = (time.perf_counter() - t0) * 1e3  # the C call alone (what a C++ caller of the adapter waits for)
-    hl.check(rc, "rt_hip_image_loop")
-    return dict(image=image, I_ang=iang, failure_code=code.value, failed_rays=failed[:nf.value].copy(),
+    rc = getattr(hl.lib, entry)(*args)
+    call_ms = (time.perf_counter() - t0) * 1e3
+    hl.check(rc, entry)
+    return dict(outs=outs, codes=codes, failure_code=int(np.bitwise_or.reduce(codes, axis=None)), failed_rays=failed[:nfail.value].copy(),
                 stats={k: getattr(st, k) for k, _ in cabi.RtStats._fields_}, call_ms=call_ms)
+
+
+def _rec(out: dict, index: tuple, **first) -> dict:
+    """Row `index` of the outputs of a _host_loop as a record: dict(**first, E_v, nf, I_ang, failure_code)."""
+    E_v, nf, iang = out["outs"]
+    return dict(**first, E_v=E_v[index].copy(), nf=nf[index].copy(), I_ang=iang[index].copy(), failure_code=int(out["codes"][index]))
+
+
+def _curve(out: dict, L: int, *row) -> list:
+    """The records of row `row` at n = 2 .. L + 1 lengths: [dict(n, E_v, nf, I_ang, failure_code)]."""
+    return [_rec(out, row + (i,), n=i + 2) for i in range(L)]
+
+
+def _tail(out: dict, *keys) -> dict:
+    """What every loop returns behind its outputs: failure_code, failed_rays, stats, and of `keys` what the loop has always had."""
+    return {k: out[k] for k in ("failure_code", "failed_rays", "stats") + keys}
+
+
+def image_loop(problem: Problem, rays: np.ndarray | None = None, device: int = 0) -> dict:
+    """RayTraceImageHipLoop through the host-pointer entry point
+    (rt_hip_image_loop): upload, trace, download.  Returns image, I_ang,
+    failure_code, failed_rays, stats."""
+    out = _host_loop("rt_hip_image_loop", problem, rays, device, image=True)
+    return dict(image=out["outs"][0], I_ang=out["outs"][1], **_tail(out, "call_ms"))
 
 
 def step_loop(problem: Problem, rays: np.ndarray | None = None, device: int = 0) -> dict:
     """image_loop with the small outputs (rt_hip_step_loop): E_v [nv], nf [nx * ny], I_ang, failure_code, failed_rays,
     stats -- the image cube is never built."""
-    hl = HipLibrary.get()
-    m = cabi.Marshalled(problem)
-    if rays is None:
-        rays = problem.build_rays()
-    rays = np.ascontiguousarray(rays, dtype=cabi.RAY_DTYPE)
-    b = problem.beam
-    E_v, nf, iang = np.zeros(b.nv), np.zeros(b.nx * b.ny), np.zeros(b.na * b.nb)
-    code = C.c_uint(0)
-    nfail = C.c_int(0)
-    failed = np.zeros(cabi.RT_N_FAILED_MAX, dtype=cabi.RAY_DTYPE)
-    st = cabi.RtStats()
-    t0 = time.perf_counter()
-    rc = hl.lib.rt_hip_step_loop(device, m.N, C.byref(m.beam), m.gain, m.seed_ref, problem.method,
-                                 cabi.rays_ptr(rays), len(rays), problem.scale, cabi._dp(E_v), cabi._dp(nf),
-                                 cabi._dp(iang), C.byref(code), cabi.rays_ptr(failed),
-                                 cabi.RT_N_FAILED_MAX, C.byref(nfail), C.byref(st))
-    call_ms = (time.perf_counter() - t0) * 1e3
-    hl.check(rc, "rt_hip_step_loop")
-    return dict(E_v=E_v, nf=nf, I_ang=iang, failure_code=code.value, failed_rays=failed[:nfail.value].copy(),
-                stats={k: getattr(st, k) for k, _ in cabi.RtStats._fields_}, call_ms=call_ms)
+    out = _host_loop("rt_hip_step_loop", problem, rays, device)
+    return dict(zip(("E_v", "nf", "I_ang"), out["outs"]), **_tail(out, "call_ms"))
 
 
 def step_history_loop(p: Problem, snapshots, seeds=None, scales=None, accumulate: bool = False, weights=None, device: int = 0) -> dict:
@@ -829,27 +852,9 @@ def multi_step_loop(problem: Problem, rays: np.ndarray | None = None, n_devices:
     """step_loop on all devices of the node (rt_hip_multi_step_loop): every device traces its share of the rays on the
     full beam into one buffer (E_v | nf | I_ang), ONE RCCL sum-reduce assembles them (include/rt_hip.h).  n_devices <= 0:
     every device.  Returns what step_loop returns plus `mode` (3 = strided ray grid, 2 = chunks of the list)."""
-    hl = HipLibrary.get()
-    m = cabi.Marshalled(problem)
-    if rays is None:
-        rays = problem.build_rays()
-    rays = np.ascontiguousarray(rays, dtype=cabi.RAY_DTYPE)
-    b = problem.beam
-    E_v, nf, iang = np.zeros(b.nv), np.zeros(b.nx * b.ny), np.zeros(b.na * b.nb)
-    code = C.c_uint(0)
-    nfail = C.c_int(0)
-    failed = np.zeros(cabi.RT_N_FAILED_MAX, dtype=cabi.RAY_DTYPE)
-    st = cabi.RtStats()
-    t0 = time.perf_counter()
-    rc = hl.lib.rt_hip_multi_step_loop(n_devices, m.N, C.byref(m.beam), m.gain, m.seed_ref, problem.method,
-                                       cabi.rays_ptr(rays), len(rays), problem.scale, cabi._dp(E_v), cabi._dp(nf),
-                                       cabi._dp(iang), C.byref(code), cabi.rays_ptr(failed),
-                                       cabi.RT_N_FAILED_MAX, C.byref(nfail), C.byref(st))
-    call_ms = (time.perf_counter() - t0) * 1e3
-    hl.check(rc, "rt_hip_multi_step_loop")
-    return dict(E_v=E_v, nf=nf, I_ang=iang, failure_code=code.value, failed_rays=failed[:nfail.value].copy(),
-                stats={k: getattr(st, k) for k, _ in cabi.RtStats._fields_}, mode=int(hl.lib.rt_hip_multi_last_mode()),
-                call_ms=call_ms)
+    out = _host_loop("rt_hip_multi_step_loop", problem, rays, n_devices)
+    return dict(zip(("E_v", "nf", "I_ang"), out["outs"]), **_tail(out), mode=int(HipLibrary.get().lib.rt_hip_multi_last_mode()),
+                call_ms=out["call_ms"])
 
 
 def seed_step_loop(problem: Problem, seeds, rays: np.ndarray | None = None, device: int = 0) -> dict:
@@ -870,6 +875,14 @@ def seed_step_loop(problem: Problem, seeds, rays: np.ndarray | None = None, devi
     return dict(records=records, failure_code=info["failure_code"], failed_rays=info["failed_rays"], stats=info["stats"])
 
 
+def _ase_loop_args(who: str, problem: Problem, seeds, scales) -> tuple:
+    """(seeds, scales) of a loop with ASE seeds, checked: 1 .. RT_N_SEED_MAX Seeds, an emission problem, one scale per seed."""
+    seeds = _taken_seeds(who, seeds)
+    if problem.seed is not None:
+        raise ValueError(f"{who}: the problem carries a seed; the ASE record needs an emission problem")
+    return seeds, _scales_arg(who, scales, len(seeds))
+
+
 def full_step_loop(problem: Problem, seeds, scales=None, rays: np.ndarray | None = None, device: int = 0) -> dict:
     """The whole per-step record from ONE march of the problem's rays (rt_hip_full_step_loop, host pointers; rays None: the
     problem's ray grid as a list): the emission record of `problem`, which must carry no seed and tables with E0, and the
@@ -877,42 +890,10 @@ def full_step_loop(problem: Problem, seeds, scales=None, rays: np.ndarray | None
     problem's scale).  Returns dict(ase = rec, seeds = [rec ...], failure_code = the OR of the codes, failed_rays, stats),
     every rec dict(E_v, nf, I_ang, failure_code).  No seed or too many, an entry that is not a Seed, scales of another
     length or a problem with a seed is a ValueError raised here, before any native call."""
-    seeds = list(seeds)
-    if not 1 <= len(seeds) <= cabi.RT_N_SEED_MAX:
-        raise ValueError(f"full_step_loop: {len(seeds)} seeds given, 1 .. RT_N_SEED_MAX = {cabi.RT_N_SEED_MAX} are taken")
-    for i, sd in enumerate(seeds):
-        if not isinstance(sd, Seed):
-            raise ValueError(f"full_step_loop: entry {i} is a {type(sd).__name__}, not a Seed")
-    if problem.seed is not None:
-        raise ValueError("full_step_loop: the problem carries a seed; the ASE record needs an emission problem")
-    sc = None
-    if scales is not None:
-        sc = np.ascontiguousarray(scales, dtype=np.float64)
-        if sc.shape != (len(seeds),):
-            raise ValueError(f"full_step_loop: {sc.size} scales for {len(seeds)} seeds")
-    hl = HipLibrary.get()
-    m = cabi.Marshalled(problem)
-    if rays is None:
-        rays = problem.build_rays()
-    rays = np.ascontiguousarray(rays, dtype=cabi.RAY_DTYPE)
-    _, arr, _keep = _seed_array(seeds, "full_step_loop", "a step record")   # (checked above: marshalled only)
-    b, nr = problem.beam, 1 + len(seeds)
-    E_v, nf, iang = np.zeros((nr, b.nv)), np.zeros((nr, b.nx * b.ny)), np.zeros((nr, b.na * b.nb))
-    codes = (C.c_uint * nr)()
-    nfail = C.c_int(0)
-    failed = np.zeros(cabi.RT_N_FAILED_MAX, dtype=cabi.RAY_DTYPE)
-    st = cabi.RtStats()
-    rc = hl.lib.rt_hip_full_step_loop(device, m.N, C.byref(m.beam), m.gain, problem.method, cabi.rays_ptr(rays), len(rays),
-                                      problem.scale, len(seeds), arr, cabi._dp(sc) if sc is not None else None, cabi._dp(E_v),
-                                      cabi._dp(nf), cabi._dp(iang), codes, cabi.rays_ptr(failed), cabi.RT_N_FAILED_MAX,
-                                      C.byref(nfail), C.byref(st))
-    hl.check(rc, "rt_hip_full_step_loop")
-    recs = [dict(E_v=E_v[r].copy(), nf=nf[r].copy(), I_ang=iang[r].copy(), failure_code=int(codes[r])) for r in range(nr)]
-    code = 0
-    for r in recs:
-        code |= r["failure_code"]
-    return dict(ase=recs[0], seeds=recs[1:], failure_code=code, failed_rays=failed[:nfail.value].copy(),
-                stats={k: getattr(st, k) for k, _ in cabi.RtStats._fields_})
+    seeds, sc = _ase_loop_args("full_step_loop", problem, seeds, scales)
+    out = _host_loop("rt_hip_full_step_loop", problem, rays, device, (1 + len(seeds),), seeds, sc, ase=True)
+    recs = [_rec(out, (r,)) for r in range(1 + len(seeds))]
+    return dict(ase=recs[0], seeds=recs[1:], **_tail(out))
 
 
 def full_length_scan_loop(problem: Problem, seeds, scales=None, rays: np.ndarray | None = None, device: int = 0) -> dict:
@@ -937,49 +918,20 @@ def full_suffix_scan_loop(problem: Problem, seeds, scales=None, rays: np.ndarray
 
 
 def _full_scan_loop(who: str, method: int, method_text: str, problem: Problem, seeds, scales, rays, device: int) -> dict:
-    """full_length_scan_loop (method 2) and full_suffix_scan_loop (method 1): the checks, the marshalling and the rows."""
-    if problem.method != method:
-        raise ValueError(f"{who}: the problem's method is {problem.method}; {method_text}")
-    if problem.N < 3 or problem.N - 1 > cabi.RT_N_SCAN_MAX:
-        raise ValueError(f"{who}: N = {problem.N}; a scan takes 3 <= N <= RT_N_SCAN_MAX + 1 = {cabi.RT_N_SCAN_MAX + 1}")
-    seeds = list(seeds)
-    if not 1 <= len(seeds) <= cabi.RT_N_SEED_MAX:
-        raise ValueError(f"{who}: {len(seeds)} seeds given, 1 .. RT_N_SEED_MAX = {cabi.RT_N_SEED_MAX} are taken")
-    for i, sd in enumerate(seeds):
-        if not isinstance(sd, Seed):
-            raise ValueError(f"{who}: entry {i} is a {type(sd).__name__}, not a Seed")
-    if problem.seed is not None:
-        raise ValueError(f"{who}: the problem carries a seed; the ASE record needs an emission problem")
-    sc = None
-    if scales is not None:
-        sc = np.ascontiguousarray(scales, dtype=np.float64)
-        if sc.shape != (len(seeds),):
-            raise ValueError(f"{who}: {sc.size} scales for {len(seeds)} seeds")
-    hl = HipLibrary.get()
-    m = cabi.Marshalled(problem)
-    if rays is None:
-        rays = problem.build_rays()
-    rays = np.ascontiguousarray(rays, dtype=cabi.RAY_DTYPE)
-    _, arr, _keep = _seed_array(seeds, who, "a step record")   # (checked above: marshalled only)
-    b, L, nr = problem.beam, problem.N - 1, 1 + len(seeds)
-    E_v, nf, iang = np.zeros((nr, L, b.nv)), np.zeros((nr, L, b.nx * b.ny)), np.zeros((nr, L, b.na * b.nb))
-    codes = (C.c_uint * (nr * L))()
-    nfail = C.c_int(0)
-    failed = np.zeros(cabi.RT_N_FAILED_MAX, dtype=cabi.RAY_DTYPE)
-    st = cabi.RtStats()
-    rc = getattr(hl.lib, "rt_hip_" + who)(device, m.N, C.byref(m.beam), m.gain, problem.method, cabi.rays_ptr(rays), len(rays),
-                                          problem.scale, len(seeds), arr, cabi._dp(sc) if sc is not None else None, cabi._dp(E_v),
-                                          cabi._dp(nf), cabi._dp(iang), codes, cabi.rays_ptr(failed), cabi.RT_N_FAILED_MAX,
-                                          C.byref(nfail), C.byref(st))
-    hl.check(rc, "rt_hip_" + who)
-    curves = [[dict(n=i + 2, E_v=E_v[r, i].copy(), nf=nf[r, i].copy(), I_ang=iang[r, i].copy(), failure_code=int(codes[r * L + i]))
-               for i in range(L)] for r in range(nr)]
-    code = 0
-    for curve in curves:
-        for r in curve:
-            code |= r["failure_code"]
-    return dict(ase=curves[0], seeds=curves[1:], failure_code=code, failed_rays=failed[:nfail.value].copy(),
-                stats={k: getattr(st, k) for k, _ in cabi.RtStats._fields_})
+    """full_length_scan_loop (method 2) and full_suffix_scan_loop (method 1): the checks, the call and the rows."""
+    _scan_takes(who, problem, method, method_text)
+    seeds, sc = _ase_loop_args(who, problem, seeds, scales)
+    L, nr = problem.N - 1, 1 + len(seeds)
+    out = _host_loop("rt_hip_" + who, problem, rays, device, (nr, L), seeds, sc, ase=True)
+    curves = [_curve(out, L, r) for r in range(nr)]
+    return dict(ase=curves[0], seeds=curves[1:], **_tail(out))
+
+
+def _scan_loop(who: str, method: int, method_text: str, problem: Problem, rays, device: int) -> dict:
+    """length_scan_loop (method 2) and suffix_scan_loop (method 1): the checks, the call and the rows."""
+    _scan_takes(who, problem, method, method_text)
+    out = _host_loop("rt_hip_" + who, problem, rays, device, (problem.N - 1,))
+    return dict(records=_curve(out, problem.N - 1), **_tail(out))
 
 
 def length_scan_loop(problem: Problem, rays: np.ndarray | None = None, device: int = 0) -> dict:
@@ -988,31 +940,7 @@ def length_scan_loop(problem: Problem, rays: np.ndarray | None = None, device: i
     dict(records = [dict(n, E_v, nf, I_ang, failure_code)], failure_code = the OR of the codes, failed_rays = the rays
     that fail at any length, stats).  A problem the scan does not take (backward method, N < 3, more than RT_N_SCAN_MAX
     lengths) is a ValueError raised here, before any native call."""
-    if problem.method != 2:
-        raise ValueError(f"length_scan_loop: the problem's method is {problem.method}; the scan takes the forward method (2) only")
-    if problem.N < 3 or problem.N - 1 > cabi.RT_N_SCAN_MAX:
-        raise ValueError(f"length_scan_loop: N = {problem.N}; a scan takes 3 <= N <= RT_N_SCAN_MAX + 1 = {cabi.RT_N_SCAN_MAX + 1}")
-    hl = HipLibrary.get()
-    m = cabi.Marshalled(problem)
-    if rays is None:
-        rays = problem.build_rays()
-    rays = np.ascontiguousarray(rays, dtype=cabi.RAY_DTYPE)
-    b, L = problem.beam, problem.N - 1
-    E_v, nf, iang = np.zeros((L, b.nv)), np.zeros((L, b.nx * b.ny)), np.zeros((L, b.na * b.nb))
-    codes = (C.c_uint * L)()
-    nfail = C.c_int(0)
-    failed = np.zeros(cabi.RT_N_FAILED_MAX, dtype=cabi.RAY_DTYPE)
-    st = cabi.RtStats()
-    rc = hl.lib.rt_hip_length_scan_loop(device, m.N, C.byref(m.beam), m.gain, m.seed_ref, problem.method,
-                                        cabi.rays_ptr(rays), len(rays), problem.scale, cabi._dp(E_v), cabi._dp(nf),
-                                        cabi._dp(iang), codes, cabi.rays_ptr(failed), cabi.RT_N_FAILED_MAX, C.byref(nfail), C.byref(st))
-    hl.check(rc, "rt_hip_length_scan_loop")
-    records = [dict(n=i + 2, E_v=E_v[i].copy(), nf=nf[i].copy(), I_ang=iang[i].copy(), failure_code=int(codes[i])) for i in range(L)]
-    code = 0
-    for r in records:
-        code |= r["failure_code"]
-    return dict(records=records, failure_code=code, failed_rays=failed[:nfail.value].copy(),
-                stats={k: getattr(st, k) for k, _ in cabi.RtStats._fields_})
+    return _scan_loop("length_scan_loop", 2, "the scan takes the forward method (2) only", problem, rays, device)
 
 
 def suffix_scan_loop(problem: Problem, rays: np.ndarray | None = None, device: int = 0) -> dict:
@@ -1021,31 +949,7 @@ def suffix_scan_loop(problem: Problem, rays: np.ndarray | None = None, device: i
     dict(records = [dict(n, E_v, nf, I_ang, failure_code)], failure_code = the OR of the codes, failed_rays = the rays
     that fail under any record, stats).  A problem the scan does not take (forward method, N < 3, more than RT_N_SCAN_MAX
     lengths) is a ValueError raised here, before any native call."""
-    if problem.method != 1:
-        raise ValueError(f"suffix_scan_loop: the problem's method is {problem.method}; the scan takes the backward method (1) only")
-    if problem.N < 3 or problem.N - 1 > cabi.RT_N_SCAN_MAX:
-        raise ValueError(f"suffix_scan_loop: N = {problem.N}; a scan takes 3 <= N <= RT_N_SCAN_MAX + 1 = {cabi.RT_N_SCAN_MAX + 1}")
-    hl = HipLibrary.get()
-    m = cabi.Marshalled(problem)
-    if rays is None:
-        rays = problem.build_rays()
-    rays = np.ascontiguousarray(rays, dtype=cabi.RAY_DTYPE)
-    b, L = problem.beam, problem.N - 1
-    E_v, nf, iang = np.zeros((L, b.nv)), np.zeros((L, b.nx * b.ny)), np.zeros((L, b.na * b.nb))
-    codes = (C.c_uint * L)()
-    nfail = C.c_int(0)
-    failed = np.zeros(cabi.RT_N_FAILED_MAX, dtype=cabi.RAY_DTYPE)
-    st = cabi.RtStats()
-    rc = hl.lib.rt_hip_suffix_scan_loop(device, m.N, C.byref(m.beam), m.gain, m.seed_ref, problem.method,
-                                        cabi.rays_ptr(rays), len(rays), problem.scale, cabi._dp(E_v), cabi._dp(nf),
-                                        cabi._dp(iang), codes, cabi.rays_ptr(failed), cabi.RT_N_FAILED_MAX, C.byref(nfail), C.byref(st))
-    hl.check(rc, "rt_hip_suffix_scan_loop")
-    records = [dict(n=i + 2, E_v=E_v[i].copy(), nf=nf[i].copy(), I_ang=iang[i].copy(), failure_code=int(codes[i])) for i in range(L)]
-    code = 0
-    for r in records:
-        code |= r["failure_code"]
-    return dict(records=records, failure_code=code, failed_rays=failed[:nfail.value].copy(),
-                stats={k: getattr(st, k) for k, _ in cabi.RtStats._fields_})
+    return _scan_loop("suffix_scan_loop", 1, "the scan takes the backward method (1) only", problem, rays, device)
 
 
 def seed_length_scan_loop(problem: Problem, seeds, rays: np.ndarray | None = None, device: int = 0) -> dict:
@@ -1056,40 +960,11 @@ def seed_length_scan_loop(problem: Problem, seeds, rays: np.ndarray | None = Non
     codes, failed_rays = the rays that fail anywhere, stats).  What the scan does not take (backward method, N < 3, more than
     RT_N_SCAN_MAX lengths), no seed or more than RT_N_SEED_MAX, or an entry that is not a Seed is a ValueError raised here,
     before any native call."""
-    if problem.method != 2:
-        raise ValueError(f"seed_length_scan_loop: the problem's method is {problem.method}; the scan takes the forward method (2) only")
-    if problem.N < 3 or problem.N - 1 > cabi.RT_N_SCAN_MAX:
-        raise ValueError(f"seed_length_scan_loop: N = {problem.N}; a scan takes 3 <= N <= RT_N_SCAN_MAX + 1 = {cabi.RT_N_SCAN_MAX + 1}")
-    seeds = list(seeds)
-    if not 1 <= len(seeds) <= cabi.RT_N_SEED_MAX:
-        raise ValueError(f"seed_length_scan_loop: {len(seeds)} seeds given, 1 .. RT_N_SEED_MAX = {cabi.RT_N_SEED_MAX} are taken")
-    for i, sd in enumerate(seeds):
-        if not isinstance(sd, Seed):
-            raise ValueError(f"seed_length_scan_loop: entry {i} is a {type(sd).__name__}, not a Seed")
-    hl = HipLibrary.get()
-    m = cabi.Marshalled(problem)
-    if rays is None:
-        rays = problem.build_rays()
-    rays = np.ascontiguousarray(rays, dtype=cabi.RAY_DTYPE)
-    _, arr, _keep = _seed_array(seeds, "seed_length_scan_loop", "a scan")   # (checked above: marshalled only)
-    b, L, ns = problem.beam, problem.N - 1, len(seeds)
-    E_v, nf, iang = np.zeros((ns, L, b.nv)), np.zeros((ns, L, b.nx * b.ny)), np.zeros((ns, L, b.na * b.nb))
-    codes = (C.c_uint * (ns * L))()
-    nfail = C.c_int(0)
-    failed = np.zeros(cabi.RT_N_FAILED_MAX, dtype=cabi.RAY_DTYPE)
-    st = cabi.RtStats()
-    rc = hl.lib.rt_hip_seed_length_scan_loop(device, m.N, C.byref(m.beam), m.gain, m.seed_ref, problem.method,
-                                             cabi.rays_ptr(rays), len(rays), problem.scale, ns, arr, cabi._dp(E_v), cabi._dp(nf),
-                                             cabi._dp(iang), codes, cabi.rays_ptr(failed), cabi.RT_N_FAILED_MAX, C.byref(nfail), C.byref(st))
-    hl.check(rc, "rt_hip_seed_length_scan_loop")
-    records = [[dict(n=i + 2, E_v=E_v[s, i].copy(), nf=nf[s, i].copy(), I_ang=iang[s, i].copy(), failure_code=int(codes[s * L + i]))
-                for i in range(L)] for s in range(ns)]
-    code = 0
-    for curve in records:
-        for r in curve:
-            code |= r["failure_code"]
-    return dict(records=records, failure_code=code, failed_rays=failed[:nfail.value].copy(),
-                stats={k: getattr(st, k) for k, _ in cabi.RtStats._fields_})
+    _scan_takes("seed_length_scan_loop", problem, 2, "the scan takes the forward method (2) only")
+    seeds = _taken_seeds("seed_length_scan_loop", seeds)
+    L = problem.N - 1
+    out = _host_loop("rt_hip_seed_length_scan_loop", problem, rays, device, (len(seeds), L), seeds)
+    return dict(records=[_curve(out, L, s) for s in range(len(seeds))], **_tail(out))
 
 
 def step_outputs_from_image(problem: Problem, image) -> dict:
@@ -1113,28 +988,9 @@ def multi_image_loop(problem: Problem, rays: np.ndarray | None = None, n_devices
     """RayTraceImageHipMultiGPULoop through rt_hip_multi_image_loop: all devices of the node, one RCCL
     collective per image (include/rt_hip.h).  n_devices <= 0: every device.  Returns what image_loop
     returns plus `mode` (1 = pixel-column tiles + gather, 2 = ray chunks + sum-reduce)."""
-    hl = HipLibrary.get()
-    m = cabi.Marshalled(problem)
-    if rays is None:
-        rays = problem.build_rays()
-    rays = np.ascontiguousarray(rays, dtype=cabi.RAY_DTYPE)
-    b = problem.beam
-    image = np.zeros(b.nx * b.ny * b.nv)
-    iang = np.zeros(b.na * b.nb)
-    code = C.c_uint(0)
-    nf = C.c_int(0)
-    failed = np.zeros(cabi.RT_N_FAILED_MAX, dtype=cabi.RAY_DTYPE)
-    st = cabi.RtStats()
-    t0 = time.perf_counter()
-    rc = hl.lib.rt_hip_multi_image_loop(n_devices, m.N, C.byref(m.beam), m.gain, m.seed_ref, problem.method,
-                                        cabi.rays_ptr(rays), len(rays), problem.scale, cabi._dp(image),
-                                        cabi._dp(iang), C.byref(code), cabi.rays_ptr(failed),
-                                        cabi.RT_N_FAILED_MAX, C.byref(nf), C.byref(st))
-    call_ms = (time.perf_counter() - t0) * 1e3
-    hl.check(rc, "rt_hip_multi_image_loop")
-    return dict(image=image, I_ang=iang, failure_code=code.value, failed_rays=failed[:nf.value].copy(),
-                stats={k: getattr(st, k) for k, _ in cabi.RtStats._fields_}, mode=int(hl.lib.rt_hip_multi_last_mode()),
-                call_ms=call_ms)
+    out = _host_loop("rt_hip_multi_image_loop", problem, rays, n_devices, image=True)
+    return dict(image=out["outs"][0], I_ang=out["outs"][1], **_tail(out), mode=int(HipLibrary.get().lib.rt_hip_multi_last_mode()),
+                call_ms=out["call_ms"])
 
 
 def ray_list_grid_dims(rays: np.ndarray):

@@ -279,30 +279,77 @@ int fill_seed_tabs(rt::SeedTabs &tb, const rt_hip_plan *p, int n_seed, bool grid
     return RT_OK;
 }
 
+// Whether the seeds' factor tables on the forward ray grid serve this run.  A seeded plan has P.rays.sf exactly then.  An
+// emission plan has no creation seed and hence none: there the tables serve a forward ray GRID only, and the ray set
+// decides -- a list set behind the grid (rt_hip_plan_set_rays resets P.rays, not the tables) takes seed_factor at its launch
+// rays, and a backward run takes it at the state that serves a record, never at a grid point.
+bool seeds_on_grid(const rt_hip_plan *p, const RecordKindRow &k)
+{
+    return k.ase ? p->P.rays.gx && !p->P.rays.list && p->P.method != 1 && p->seedset_sf[0] != nullptr : p->P.rays.sf != nullptr;
+}
+// What no valid plan reaches: a pass of several records whose buffers or facts are not its kind's.
+int records_ready(const rt_hip_plan *p, const RunFacts &f, const RecordSet &R)
+{
+    const RecordKindRow &k = R.row();
+    auto fail = [&](const char *what) { return fail_arg((std::string("step kernel of ") + k.name + what).c_str()); };
+    if (!p->recs_dev || (k.lengths && !p->scan_bnd))
+        return fail(": the records or the boundary states of this run were not allocated");
+    if (p->recs_doubles < (size_t) R.n_rec() * p->recs_stride)
+        return fail(": the records of this run are smaller than the blocks of its kind");
+    if (k.lengths && f.L > RT_N_SCAN_MAX)
+        return fail(": more than RT_N_SCAN_MAX lengths");
+    if (k.seeds && (f.n_seed < 1 || f.n_seed > RT_N_SEED_MAX || f.use_emis != k.ase || (k.suffix && f.method != 1)))
+        return fail(": not 1 .. RT_N_SEED_MAX seeds on the plan (emission or gain-only, forward or backward) the kind takes");
+    return RT_OK;
+}
+// The argument block of such a pass.  With lengths every record's I_ang lies in its block; the creation seed is not among
+// the seeds a kind carries (an emission plan has none); with an ASE record or the suffix form nf of every record goes by
+// atomics (the plain store is rt_step_kernel's and the forward kernels' without ASE alone).
+template <typename KArg> KArg records_args(const rt::FreqKArg &fa, const RecordKindRow &k)
+{
+    KArg a = pass_args<KArg>(fa);
+    if (k.lengths)
+        a.hot.iang = nullptr;
+    if (k.seeds)
+        a.hot.seed_fk = nullptr;
+    if (k.ase || k.suffix)
+        a.hot.flags &= ~(unsigned) rt::FQ_EXCLUSIVE;
+    return a;
+}
+// ... its seeds: their count and tables
+template <typename Set> int fill_set(Set &set, const rt_hip_plan *p, int n_seed, const RecordKindRow &k)
+{
+    set.n_seed = n_seed;
+    return fill_seed_tabs(set.tabs, p, n_seed, seeds_on_grid(p, k), (std::string("step kernel of ") + k.name + ": the factor tables of the seeds").c_str());
+}
+// ... the scale of every record: the plan's for the ASE record, its own for a seed's
+template <typename Set> void fill_scales(Set &set, const rt_hip_plan *p, int n_seed)
+{
+    for (int r = 0; r <= n_seed; r++)
+        set.scale[r] = r == 0 ? p->P.scale : p->ase_scale[r - 1];
+}
+// ... and the blocks, for the kernels without lengths (the others take all of them through fill_scan)
+template <typename Set> void fill_out(Set &set, const rt_hip_plan *p, int n_rec)
+{
+    for (int r = 0; r < n_rec; r++)
+        set.out[r] = seed_rec(p, r);
+}
+
 // The second pass over all tiles as a kernel of its own: the frequency / deposit kernel, or in its place the spectra
 // kernel (per-ray spectra, no image), the step kernel (E_v, nf and I_ang, no image cube) or one of the step kernels that
-// leave several records (a seed set, ASE seeds, a length scan or a suffix scan, a scan with its seeds: record_set(f) says how many).
+// leave several records (record_set(f) says which kind and how many; the row of the kind, rt_records.h, what its block takes).
 int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kind, hipStream_t stream, unsigned safe = 0, unsigned char *bad = nullptr)
 {
-    const PassShape s = pass_shape(kind, f, t);
+    const PassShape s      = pass_shape(kind, f, t);
+    const RecordSet R      = record_set(f);
+    const RecordKindRow &k = R.row();
     // (what of a one-work-group-per-CU pass does not fit, by kind; the frequency kernel's message, below, carries figures)
-    static const char *const too_big[] = {
-        nullptr, // PASS_FREQ
-        "spectra kernel: the staging rows do not fit into the LDS of this device",
-        "step kernel: the E_v accumulator (nv doubles) does not fit into the LDS of this device",
-        "step kernel of a seed set: the E_v accumulators (nv doubles per seed) do not fit into the LDS of this device",
-        nullptr, // PASS_PATH
-        "step kernel of a length scan: the E_v accumulators (nv doubles per length) do not fit into the LDS of this device",
-        "step kernel of a length scan with scan seeds: the E_v accumulators (nv doubles per seed and length) do not fit into the LDS of this device",
-        "step kernel of an emission plan with ASE seeds: the E_v accumulators (nv doubles for ASE and per seed) do not fit into the LDS of this device",
-        "step kernel of a length scan with ASE seeds: the E_v accumulators (nv doubles per record and length) do not fit into the LDS of this device",
-        "step kernel of a suffix scan: the E_v accumulators (nv doubles per length) do not fit into the LDS of this device",
-        "step kernel of a suffix scan with ASE seeds: the E_v accumulators (nv doubles per record and length) do not fit into the LDS of this device" };
-    static_assert(PASS_SPEC == 1 && PASS_STEP == 2 && PASS_SEEDS == 3 && PASS_SCAN == 5 && PASS_SCAN_SEEDS == 6 && PASS_ASE_SEEDS == 7 &&
-                      PASS_SCAN_ASE_SEEDS == 8 && PASS_RSCAN == 9 && PASS_RSCAN_ASE_SEEDS == 10 && sizeof(too_big) / sizeof(too_big[0]) == 11,
-                  "too_big[] is indexed by PassKind");
-    if (too_big[kind] && s.lds > f.lds_limit)
-        return fail_arg(too_big[kind]);
+    if (s.lds > f.lds_limit && kind == PASS_SPEC)
+        return fail_arg("spectra kernel: the staging rows do not fit into the LDS of this device");
+    if (s.lds > f.lds_limit && kind == PASS_STEP)
+        return fail_arg("step kernel: the E_v accumulator (nv doubles) does not fit into the LDS of this device");
+    if (s.lds > f.lds_limit && kind != PASS_FREQ && kind != PASS_PATH)
+        return fail_arg((std::string("step kernel of ") + k.name + ": the E_v accumulators (nv doubles " + k.acc + ") do not fit into the LDS of this device").c_str());
     if (s.grid == 0)
         return RT_OK;
     if (s.lds > f.lds_limit) {
@@ -313,7 +360,6 @@ int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kin
     }
     const rt::FreqKArg fa = freq_args(p, s.in_lds, s.nslot, s.fetch_shift, PassRun{ 0, f.n_tiles, 0, safe, bad });
     const unsigned block  = (unsigned) s.wg_waves * 64;
-    const int n_rec       = record_set(f).n_rec();
     if (kind == PASS_FREQ)
         return launch(p, freq_kernel(f.s6(), f.use_emis, f.use_emis && f.exclusive), s.grid, block, s.lds, stream, fa);
     if (kind == PASS_SPEC) {
@@ -327,106 +373,39 @@ int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kin
         a.out       = p->step;
         return launch(p, step_kernel(f.s6(), f.use_emis), s.grid, block, s.lds, stream, a);
     }
-    if (kind == PASS_SCAN) { // a length scan: one record per length
-        if (!p->scan_bnd || !p->recs_dev)
-            return fail_arg("step kernel of a length scan: the boundary states or the records of this run were not allocated");
-        rt::ScanKArg a = pass_args<rt::ScanKArg>(fa);
-        a.hot.iang     = nullptr; // (every record's I_ang lies in its block)
+    // ---- the passes that leave several records: per kind its argument block and its kernel ----
+    int rc = records_ready(p, f, R);
+    if (rc != RT_OK)
+        return rc;
+    if (kind == PASS_SCAN || kind == PASS_RSCAN) { // one record per length, or per run of the last n lengths (a backward plan)
+        rt::ScanKArg a = records_args<rt::ScanKArg>(fa, k);
         fill_scan(a.scan, p);
-        return launch(p, scan_kernel(f.use_emis), s.grid, block, s.lds, stream, a);
+        return launch(p, k.suffix ? rscan_kernel(f.use_emis) : scan_kernel(f.use_emis), s.grid, block, s.lds, stream, a);
     }
-    if (kind == PASS_RSCAN) { // a suffix scan (a backward plan): one record per run of the last n lengths
-        if (!p->scan_bnd || !p->recs_dev)
-            return fail_arg("step kernel of a suffix scan: the boundary states or the records of this run were not allocated");
-        if (f.L > RT_N_SCAN_MAX || p->recs_doubles < (size_t) n_rec * p->recs_stride)
-            return fail_arg("step kernel of a suffix scan: more than RT_N_SCAN_MAX lengths, or the records of this run are smaller than N - 1 blocks");
-        rt::ScanKArg a = pass_args<rt::ScanKArg>(fa);
-        a.hot.iang     = nullptr; // (every record's I_ang lies in its block)
-        a.hot.flags &= ~(unsigned) rt::FQ_EXCLUSIVE; // (nf of every record by atomics)
+    if (kind == PASS_SCAN_ASE_SEEDS || kind == PASS_RSCAN_ASE_SEEDS) { // an emission plan: one record per (ASE | seed, n)
+        rt::ScanAseSeedsKArg a = records_args<rt::ScanAseSeedsKArg>(fa, k);
         fill_scan(a.scan, p);
-        return launch(p, rscan_kernel(f.use_emis), s.grid, block, s.lds, stream, a);
+        fill_scales(a.set, p, f.n_seed);
+        rc = fill_set(a.set, p, f.n_seed, k);
+        return rc != RT_OK ? rc : launch(p, k.suffix ? rt::rt_step_rscan_ase_seeds_kernel : rt::rt_step_scan_ase_seeds_kernel, s.grid, block, s.lds, stream, a);
     }
-    if (kind == PASS_RSCAN_ASE_SEEDS) { // a suffix scan with ASE seeds (a backward emission plan): one record per (ASE | seed, n)
-        if (!p->scan_bnd || !p->recs_dev)
-            return fail_arg("step kernel of a suffix scan with ASE seeds: the boundary states or the records of this run were not allocated");
-        if (f.n_seed < 1 || f.n_seed > RT_N_SEED_MAX || f.L > RT_N_SCAN_MAX || !f.use_emis || f.method != 1)
-            return fail_arg("step kernel of a suffix scan with ASE seeds: not a backward emission run of 1 .. RT_N_SEED_MAX seeds and at most RT_N_SCAN_MAX lengths");
-        if (p->recs_doubles < (size_t) n_rec * p->recs_stride)
-            return fail_arg("step kernel of a suffix scan with ASE seeds: the records of this run are smaller than (1 + n_seed) (N - 1) blocks");
-        rt::ScanAseSeedsKArg a = pass_args<rt::ScanAseSeedsKArg>(fa);
-        a.hot.iang     = nullptr; // (every record's I_ang lies in its block)
-        a.hot.seed_fk  = nullptr; // (an emission plan has no creation seed)
-        a.hot.flags &= ~(unsigned) rt::FQ_EXCLUSIVE; // (nf of every record by atomics)
+    if (kind == PASS_SCAN_SEEDS) { // a seeded plan (gain-only): one record per (seed, length)
+        rt::ScanSeedsKArg a = records_args<rt::ScanSeedsKArg>(fa, k);
         fill_scan(a.scan, p);
-        a.set.n_seed   = f.n_seed;
-        for (int r = 0; r <= f.n_seed; r++)
-            a.set.scale[r] = r == 0 ? p->P.scale : p->ase_scale[r - 1];
-        // (the seed factor is taken at the state that serves a record, never at a grid point: no factor tables)
-        const int rc = fill_seed_tabs(a.set.tabs, p, f.n_seed, false, "step kernel of a suffix scan with ASE seeds: the factor tables of the seeds");
-        return rc != RT_OK ? rc : launch(p, rt::rt_step_rscan_ase_seeds_kernel, s.grid, block, s.lds, stream, a);
-    }
-    if (kind == PASS_SCAN_SEEDS) { // a length scan with scan seeds (a seeded plan: gain-only): one record per (seed, length)
-        if (!p->scan_bnd || !p->recs_dev)
-            return fail_arg("step kernel of a length scan with scan seeds: the boundary states or the records of this run were not allocated");
-        if (f.n_seed < 1 || f.n_seed > RT_N_SEED_MAX || f.L > RT_N_SCAN_MAX || f.use_emis)
-            return fail_arg("step kernel of a length scan with scan seeds: not a gain-only run of 1 .. RT_N_SEED_MAX seeds and at most RT_N_SCAN_MAX lengths");
-        if (p->recs_doubles < (size_t) n_rec * p->recs_stride)
-            return fail_arg("step kernel of a length scan with scan seeds: the records of this run are smaller than n_seed (N - 1) blocks");
-        rt::ScanSeedsKArg a = pass_args<rt::ScanSeedsKArg>(fa);
-        a.hot.iang     = nullptr; // (every record's I_ang lies in its block)
-        a.hot.seed_fk  = nullptr; // (the creation seed is not part of the set)
-        fill_scan(a.scan, p);
-        a.set.n_seed   = f.n_seed;
-        const int rc   = fill_seed_tabs(a.set.tabs, p, f.n_seed, p->P.rays.sf != nullptr, "step kernel of a length scan with scan seeds: the factor tables of the seeds");
+        rc = fill_set(a.set, p, f.n_seed, k);
         return rc != RT_OK ? rc : launch(p, rt::rt_step_scan_seeds_kernel, s.grid, block, s.lds, stream, a);
     }
-    if (kind == PASS_SCAN_ASE_SEEDS) { // a length scan with ASE seeds (an emission plan): one record per (ASE | seed, length)
-        if (!p->scan_bnd || !p->recs_dev)
-            return fail_arg("step kernel of a length scan with ASE seeds: the boundary states or the records of this run were not allocated");
-        if (f.n_seed < 1 || f.n_seed > RT_N_SEED_MAX || f.L > RT_N_SCAN_MAX || !f.use_emis)
-            return fail_arg("step kernel of a length scan with ASE seeds: not an emission run of 1 .. RT_N_SEED_MAX seeds and at most RT_N_SCAN_MAX lengths");
-        if (p->recs_doubles < (size_t) n_rec * p->recs_stride)
-            return fail_arg("step kernel of a length scan with ASE seeds: the records of this run are smaller than (1 + n_seed) (N - 1) blocks");
-        rt::ScanAseSeedsKArg a = pass_args<rt::ScanAseSeedsKArg>(fa);
-        a.hot.iang     = nullptr; // (every record's I_ang lies in its block)
-        a.hot.seed_fk  = nullptr; // (an emission plan has no creation seed)
-        a.hot.flags &= ~(unsigned) rt::FQ_EXCLUSIVE; // (nf of every record by atomics)
-        fill_scan(a.scan, p);
-        a.set.n_seed   = f.n_seed;
-        for (int r = 0; r <= f.n_seed; r++)
-            a.set.scale[r] = r == 0 ? p->P.scale : p->ase_scale[r - 1];
-        // (the ray set of the run decides between the factor tables and the launch rays, as for PASS_ASE_SEEDS below)
-        const bool grid_tabs = p->P.rays.gx && !p->P.rays.list && p->seedset_sf[0] != nullptr;
-        const int rc = fill_seed_tabs(a.set.tabs, p, f.n_seed, grid_tabs, "step kernel of a length scan with ASE seeds: the factor tables of the seeds");
-        return rc != RT_OK ? rc : launch(p, rt::rt_step_scan_ase_seeds_kernel, s.grid, block, s.lds, stream, a);
-    }
-    if (kind == PASS_ASE_SEEDS) { // an emission plan with ASE seeds: block 0 the ASE record, block 1 + s the record of seed s
-        if (f.n_seed < 1 || f.n_seed > RT_N_SEED_MAX || !f.use_emis || !p->recs_dev)
-            return fail_arg("step kernel of an emission plan with ASE seeds: not an emission run of 1 .. RT_N_SEED_MAX seeds with its records allocated");
-        if (p->recs_doubles < (size_t) n_rec * p->recs_stride)
-            return fail_arg("step kernel of an emission plan with ASE seeds: the records of this run are smaller than 1 + n_seed blocks");
-        rt::AseSeedsKArg a = pass_args<rt::AseSeedsKArg>(fa);
-        a.hot.seed_fk  = nullptr; // (an emission plan has no creation seed)
-        a.hot.flags &= ~(unsigned) rt::FQ_EXCLUSIVE; // (nf of every record by atomics: the plain store is rt_step_kernel's alone)
-        a.set.n_seed   = f.n_seed;
-        for (int r = 0; r < n_rec; r++) {
-            a.set.out[r]   = seed_rec(p, r);
-            a.set.scale[r] = r == 0 ? p->P.scale : p->ase_scale[r - 1];
-        }
-        // the factor tables of the seeds serve a forward ray GRID only, and the ray set decides: a list set behind the grid
-        // (rt_hip_plan_set_rays resets P.rays, not the tables) takes seed_factor at its launch rays.  (A seeded plan has
-        // P.rays.sf for this; an emission plan has no creation seed and hence none.)
-        const bool grid_tabs = p->P.rays.gx && !p->P.rays.list && p->P.method != 1 && p->seedset_sf[0] != nullptr;
-        const int rc = fill_seed_tabs(a.set.tabs, p, f.n_seed, grid_tabs, "step kernel of an emission plan with ASE seeds: the factor tables of the seeds");
+    if (kind == PASS_ASE_SEEDS) { // an emission plan: block 0 the ASE record, block 1 + s the record of seed s
+        rt::AseSeedsKArg a = records_args<rt::AseSeedsKArg>(fa, k);
+        fill_out(a.set, p, R.n_rec());
+        fill_scales(a.set, p, f.n_seed);
+        rc = fill_set(a.set, p, f.n_seed, k);
         return rc != RT_OK ? rc : launch(p, ase_seeds_kernel(f.s6()), s.grid, block, s.lds, stream, a);
     }
     // a seed set (a seeded plan: gain-only): one record per seed
-    rt::SeedsKArg a = pass_args<rt::SeedsKArg>(fa);
-    a.hot.seed_fk = nullptr; // (the creation seed is not part of the set)
-    a.set.n_seed  = f.n_seed;
-    for (int r = 0; r < n_rec; r++)
-        a.set.out[r] = seed_rec(p, r);
-    const int rc = fill_seed_tabs(a.set.tabs, p, f.n_seed, p->P.rays.sf != nullptr, "step kernel of a seed set: the factor tables of the set");
+    rt::SeedsKArg a = records_args<rt::SeedsKArg>(fa, k);
+    fill_out(a.set, p, R.n_rec());
+    rc = fill_set(a.set, p, f.n_seed, k);
     return rc != RT_OK ? rc : launch(p, seeds_kernel(f.s6()), s.grid, block, s.lds, stream, a);
 }
 

@@ -1387,41 +1387,78 @@ int rt_hip_plan_fetch_step(rt_hip_plan *p, double *E_v, double *nf, double *I_an
     return RT_OK;
 }
 
-int rt_hip_plan_fetch_seed_step(rt_hip_plan *p, int s, double *E_v, double *nf, double *I_ang, unsigned int *failure_code)
+} // extern "C"
+
+// An accessor pair of the C ABI: the kinds of last run it serves (bits by RecordKind), what it says after a run of another
+// kind, and what of a first index (seed or record) that the run has not.
+struct Accessor {
+    unsigned kinds;
+    const char *not_kind, *bad_first;
+};
+constexpr unsigned kind_bit(RecordKind k) { return 1u << k; }
+static const Accessor ACC_SEED        = { kind_bit(REC_SEEDS), ": the last run was not a step run with a seed set", ": no such seed in the set of the last run" };
+// (on a scan with scan seeds a length alone means seed 0's curve, on a scan with ASE seeds the ASE curve; on a suffix scan n
+// is the number of lengths of the run of the LAST n)
+static const Accessor ACC_LENGTH      = { kind_bit(REC_SCAN) | kind_bit(REC_SCAN_SEEDS) | kind_bit(REC_SCAN_ASE_SEEDS) | kind_bit(REC_RSCAN) | kind_bit(REC_RSCAN_ASE_SEEDS),
+                                          ": the last run was not a step run with the length scan on", "" };
+static const Accessor ACC_FULL        = { kind_bit(REC_ASE_SEEDS), ": the last run was not a step run of an emission plan with ASE seeds",
+                                          ": r must be 0 (ASE) .. n_seed of the last run" };
+// (of a length scan or of a suffix scan, as rt_hip_plan_fetch_length_step serves both scans)
+static const Accessor ACC_FULL_LENGTH = { kind_bit(REC_SCAN_ASE_SEEDS) | kind_bit(REC_RSCAN_ASE_SEEDS), ": the last run was not a step run of a length scan with ASE seeds",
+                                          ": r must be 0 (ASE) .. n_seed of the last run" };
+static const Accessor ACC_SEED_LENGTH = { kind_bit(REC_SCAN_SEEDS), ": the last run was not a step run of a length scan with scan seeds",
+                                          ": no such seed among the scan seeds of the last run" };
+
+// The block of the last run that (s, n) means to the accessor `who`, or -1 behind its refusal: the kind, the first index,
+// the length.
+static int record_block(const rt_hip_plan *p, const char *who, const Accessor &a, int s, int n)
 {
-    if (!p || p->last_records.kind != REC_SEEDS)
-        return fail_arg("rt_hip_plan_fetch_seed_step: the last run was not a step run with a seed set");
-    if (p->last_records.block(s) < 0)
-        return fail_arg("rt_hip_plan_fetch_seed_step: no such seed in the set of the last run");
-    return record_fetch(p, p->last_records.block(s), E_v, nf, I_ang, failure_code);
+    auto fail = [&](const char *what) { return (void) fail_arg((std::string(who) + what).c_str()), -1; };
+    if (!p || !(a.kinds & kind_bit(p->last_records.kind)))
+        return fail(a.not_kind);
+    const RecordSet &R = p->last_records;
+    if (R.block(s, 2) < 0) // (every scan has length 2, a kind without lengths takes no notice of it)
+        return fail(a.bad_first);
+    if (R.block(s, n) < 0)
+        return fail(": n must be 2 .. N of the last run");
+    return R.block(s, n);
+}
+static int fetch_at(rt_hip_plan *p, const char *who, const Accessor &a, int s, int n, double *E_v, double *nf, double *I_ang, unsigned int *code)
+{
+    const int block = record_block(p, who, a, s, n);
+    return block < 0 ? RT_ERR_ARG : record_fetch(p, block, E_v, nf, I_ang, code);
+}
+static int ptrs_at(rt_hip_plan *p, const char *who, const Accessor &a, int s, int n, double **E_v_dev, double **nf_dev, double **iang_dev)
+{
+    const int block = record_block(p, who, a, s, n);
+    return block < 0 ? RT_ERR_ARG : record_ptrs(p, block, E_v_dev, nf_dev, iang_dev);
 }
 
-int rt_hip_plan_seed_step_ptrs(rt_hip_plan *p, int s, double **E_v_dev, double **nf_dev, double **iang_dev)
+// rt_hip_plan_enable_length_scan and rt_hip_plan_enable_suffix_scan (include/rt_hip.h).  Both are the plan's scan_on: the
+// boundary buffer, the records and their accessors are one scan's, run_shape and record_set tell the two apart by the method
+// (1: the suffix scan of a backward plan, which never has the length scan on).
+static int scan_switch(rt_hip_plan *p, const char *who, bool suffix, int on)
 {
-    if (!p || p->last_records.kind != REC_SEEDS)
-        return fail_arg("rt_hip_plan_seed_step_ptrs: the last run was not a step run with a seed set");
-    if (p->last_records.block(s) < 0)
-        return fail_arg("rt_hip_plan_seed_step_ptrs: no such seed in the set of the last run");
-    return record_ptrs(p, p->last_records.block(s), E_v_dev, nf_dev, iang_dev);
-}
-
-int rt_hip_plan_enable_length_scan(rt_hip_plan *p, int on)
-{
+    auto fail = [&](const char *what) { return fail_arg((std::string(who) + what).c_str()); };
     if (!p)
-        return fail_arg("rt_hip_plan_enable_length_scan: NULL plan");
-    if (!on && suffix_scan(p)) // (on: the method test below refuses it)
-        return fail_arg("rt_hip_plan_enable_length_scan: the suffix scan is on (rt_hip_plan_enable_suffix_scan switches it off)");
+        return fail(": NULL plan");
+    if (suffix && p->P.method != 1)
+        return fail(": the plan's method is not 1 (only the backward march of N lengths begins with the marches of the last n)");
+    if (!suffix && !on && suffix_scan(p)) // (on: the method test below refuses it)
+        return fail(": the suffix scan is on (rt_hip_plan_enable_suffix_scan switches it off)");
     if (on) {
-        if (p->P.method != 2)
-            return fail_arg("rt_hip_plan_enable_length_scan: the plan's method is not 2 (only the forward march of N lengths holds the marches of fewer)");
+        if (!suffix && p->P.method != 2)
+            return fail(": the plan's method is not 2 (only the forward march of N lengths holds the marches of fewer)");
         if (p->P.N < 3)
-            return fail_arg("rt_hip_plan_enable_length_scan: N < 3 (one length: the step record is the scan)");
+            return fail(": N < 3 (one length: the step record is the scan)");
         if (p->P.N - 1 > RT_N_SCAN_MAX)
-            return fail_arg("rt_hip_plan_enable_length_scan: more than RT_N_SCAN_MAX lengths");
+            return fail(": more than RT_N_SCAN_MAX lengths");
         if (p->n_seed > 0)
-            return fail_arg("rt_hip_plan_enable_length_scan: the plan holds a seed set (a seed set and a length scan exclude each other)");
+            return fail(!suffix          ? ": the plan holds a seed set (a seed set and a length scan exclude each other)"
+                        : p->P.use_emis ? ": the plan holds ASE seeds (ASE seeds and a suffix scan exclude each other)"
+                                        : ": the plan holds a seed set (a seed set and a suffix scan exclude each other)");
         if (p->path_on || p->spectra_on)
-            return fail_arg("rt_hip_plan_enable_length_scan: the path tracer or spectra mode is enabled (the scan runs in step mode only)");
+            return fail(": the path tracer or spectra mode is enabled (the scan runs in step mode only)");
     }
     if ((on != 0) == p->scan_on)
         return RT_OK;
@@ -1443,82 +1480,61 @@ int rt_hip_plan_enable_length_scan(rt_hip_plan *p, int on)
             p->seedset_arena = nullptr;
             for (int s = 0; s < RT_N_SEED_MAX; s++)
                 p->seed_set[s] = rt::DevSeed{};
-            return plan_build_seedset_tabs(p); // (frees the factor tables)
+            return plan_build_seedset_tabs(p); // (frees the factor tables; a backward plan has none)
         }
     }
     return RT_OK;
 }
 
-// The suffix scan of a backward plan (include/rt_hip.h).  It is the plan's scan_on with method 1: the boundary buffer, the
-// records and their accessors are the length scan's, run_shape and record_set tell the two apart by the method.
-int rt_hip_plan_enable_suffix_scan(rt_hip_plan *p, int on)
+extern "C" {
+
+int rt_hip_plan_fetch_seed_step(rt_hip_plan *p, int s, double *E_v, double *nf, double *I_ang, unsigned int *failure_code)
 {
-    if (!p)
-        return fail_arg("rt_hip_plan_enable_suffix_scan: NULL plan");
-    if (p->P.method != 1)
-        return fail_arg("rt_hip_plan_enable_suffix_scan: the plan's method is not 1 (only the backward march of N lengths begins with the marches of the last n)");
-    if (on) {
-        if (p->P.N < 3)
-            return fail_arg("rt_hip_plan_enable_suffix_scan: N < 3 (one length: the step record is the scan)");
-        if (p->P.N - 1 > RT_N_SCAN_MAX)
-            return fail_arg("rt_hip_plan_enable_suffix_scan: more than RT_N_SCAN_MAX lengths");
-        if (p->n_seed > 0)
-            return fail_arg(p->P.use_emis ? "rt_hip_plan_enable_suffix_scan: the plan holds ASE seeds (ASE seeds and a suffix scan exclude each other)"
-                                          : "rt_hip_plan_enable_suffix_scan: the plan holds a seed set (a seed set and a suffix scan exclude each other)");
-        if (p->path_on || p->spectra_on)
-            return fail_arg("rt_hip_plan_enable_suffix_scan: the path tracer or spectra mode is enabled (the scan runs in step mode only)");
-    }
-    // (a backward plan never has the length scan on: scan_on is the suffix scan here)
-    if ((on != 0) == p->scan_on)
-        return RT_OK;
-    HIP_TRY(hipSetDevice(p->device));
-    if (p->ran) { // the last run keeps its records until it is final (wait, control block, the checking repeat)
-        const int rs = plan_settle_last_run(p);
-        if (rs != RT_OK)
-            return rs;
-    }
-    plan_quiesce(p);
-    p->scan_on = on != 0;
-    if (!p->scan_on) { // the boundary states exist only while the scan is on
-        pool_free(p->device, p->scan_bnd);
-        p->scan_bnd       = nullptr;
-        p->scan_bnd_bytes = 0;
-        if (p->n_scan_seed > 0) { // ... and so do the ASE seeds of the scan (rt_hip_plan_set_suffix_ase_seeds)
-            p->n_scan_seed = 0;
-            (void) hipFree(p->seedset_arena);
-            p->seedset_arena = nullptr;
-            for (int s = 0; s < RT_N_SEED_MAX; s++)
-                p->seed_set[s] = rt::DevSeed{};
-            return plan_build_seedset_tabs(p); // (a backward plan has no factor tables: this leaves none)
-        }
-    }
-    return RT_OK;
+    return fetch_at(p, "rt_hip_plan_fetch_seed_step", ACC_SEED, s, 0, E_v, nf, I_ang, failure_code);
 }
-
-// (on a scan with scan seeds a length alone means seed 0's curve, on a scan with ASE seeds the ASE curve; on a suffix scan n
-// is the number of lengths of the run of the LAST n)
+int rt_hip_plan_seed_step_ptrs(rt_hip_plan *p, int s, double **E_v_dev, double **nf_dev, double **iang_dev)
+{
+    return ptrs_at(p, "rt_hip_plan_seed_step_ptrs", ACC_SEED, s, 0, E_v_dev, nf_dev, iang_dev);
+}
 int rt_hip_plan_fetch_length_step(rt_hip_plan *p, int n, double *E_v, double *nf, double *I_ang, unsigned int *failure_code)
 {
-    if (!p || !p->last_records.scan())
-        return fail_arg("rt_hip_plan_fetch_length_step: the last run was not a step run with the length scan on");
-    if (p->last_records.block(0, n) < 0)
-        return fail_arg("rt_hip_plan_fetch_length_step: n must be 2 .. N of the last run");
-    return record_fetch(p, p->last_records.block(0, n), E_v, nf, I_ang, failure_code);
+    return fetch_at(p, "rt_hip_plan_fetch_length_step", ACC_LENGTH, 0, n, E_v, nf, I_ang, failure_code);
 }
-
 int rt_hip_plan_length_step_ptrs(rt_hip_plan *p, int n, double **E_v_dev, double **nf_dev, double **iang_dev)
 {
-    if (!p || !p->last_records.scan())
-        return fail_arg("rt_hip_plan_length_step_ptrs: the last run was not a step run with the length scan on");
-    if (p->last_records.block(0, n) < 0)
-        return fail_arg("rt_hip_plan_length_step_ptrs: n must be 2 .. N of the last run");
-    return record_ptrs(p, p->last_records.block(0, n), E_v_dev, nf_dev, iang_dev);
+    return ptrs_at(p, "rt_hip_plan_length_step_ptrs", ACC_LENGTH, 0, n, E_v_dev, nf_dev, iang_dev);
 }
+int rt_hip_plan_fetch_full_step(rt_hip_plan *p, int r, double *E_v, double *nf, double *I_ang, unsigned int *failure_code)
+{
+    return fetch_at(p, "rt_hip_plan_fetch_full_step", ACC_FULL, r, 0, E_v, nf, I_ang, failure_code);
+}
+int rt_hip_plan_full_step_ptrs(rt_hip_plan *p, int r, double **E_v_dev, double **nf_dev, double **iang_dev)
+{
+    return ptrs_at(p, "rt_hip_plan_full_step_ptrs", ACC_FULL, r, 0, E_v_dev, nf_dev, iang_dev);
+}
+int rt_hip_plan_fetch_full_length_step(rt_hip_plan *p, int r, int n, double *E_v, double *nf, double *I_ang, unsigned int *failure_code)
+{
+    return fetch_at(p, "rt_hip_plan_fetch_full_length_step", ACC_FULL_LENGTH, r, n, E_v, nf, I_ang, failure_code);
+}
+int rt_hip_plan_full_length_step_ptrs(rt_hip_plan *p, int r, int n, double **E_v_dev, double **nf_dev, double **iang_dev)
+{
+    return ptrs_at(p, "rt_hip_plan_full_length_step_ptrs", ACC_FULL_LENGTH, r, n, E_v_dev, nf_dev, iang_dev);
+}
+int rt_hip_plan_fetch_seed_length_step(rt_hip_plan *p, int s, int n, double *E_v, double *nf, double *I_ang, unsigned int *failure_code)
+{
+    return fetch_at(p, "rt_hip_plan_fetch_seed_length_step", ACC_SEED_LENGTH, s, n, E_v, nf, I_ang, failure_code);
+}
+int rt_hip_plan_seed_length_step_ptrs(rt_hip_plan *p, int s, int n, double **E_v_dev, double **nf_dev, double **iang_dev)
+{
+    return ptrs_at(p, "rt_hip_plan_seed_length_step_ptrs", ACC_SEED_LENGTH, s, n, E_v_dev, nf_dev, iang_dev);
+}
+
+int rt_hip_plan_enable_length_scan(rt_hip_plan *p, int on) { return scan_switch(p, "rt_hip_plan_enable_length_scan", false, on); }
+int rt_hip_plan_enable_suffix_scan(rt_hip_plan *p, int on) { return scan_switch(p, "rt_hip_plan_enable_suffix_scan", true, on); }
 
 } // extern "C"
 
-// What rt_hip_plan_set_seeds and rt_hip_plan_set_scan_seeds share.  The arguments of either, validated: `who` names the
-// entry point in the messages.
+// The seeds every rt_hip_plan_set_*seeds takes, validated: `who` names the entry point in the messages.
 static int seeds_validate(const rt_hip_plan *p, const char *who, int n_seed, const rt_seed *seeds)
 {
     auto fail = [&](const char *what) { return fail_arg((std::string(who) + what).c_str()); };
@@ -1536,46 +1552,6 @@ static int seeds_validate(const rt_hip_plan *p, const char *who, int n_seed, con
         }
     return RT_OK;
 }
-static int seeds_install(rt_hip_plan *p, int n_seed, const rt_seed *seeds, bool of_scan);
-
-extern "C" {
-
-int rt_hip_plan_set_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds)
-{
-    if (!p)
-        return fail_arg("rt_hip_plan_set_seeds: NULL plan");
-    if (!p->P.has_seed)
-        return fail_arg("rt_hip_plan_set_seeds: the plan was created without a seed (a set needs the gain-only mode)");
-    const int rv = seeds_validate(p, "rt_hip_plan_set_seeds", n_seed, seeds);
-    if (rv != RT_OK)
-        return rv;
-    if (n_seed > 0 && p->scan_on)
-        return fail_arg(suffix_scan(p) ? "rt_hip_plan_set_seeds: the suffix scan is on (a seed set and a suffix scan exclude each other)"
-                                       : "rt_hip_plan_set_seeds: the length scan is on (a seed set and a length scan exclude each other)");
-    if (n_seed > 0 && (p->path_on || p->spectra_on))
-        return fail_arg("rt_hip_plan_set_seeds: the path tracer or spectra mode is enabled (a set runs in step mode only)");
-    if (n_seed == 0 && p->n_scan_seed > 0) // (the seeds of a scan are rt_hip_plan_set_scan_seeds': there is no set to remove)
-        return RT_OK;
-    return seeds_install(p, n_seed, seeds, false);
-}
-
-int rt_hip_plan_set_scan_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds)
-{
-    if (!p)
-        return fail_arg("rt_hip_plan_set_scan_seeds: NULL plan");
-    if (!p->P.has_seed)
-        return fail_arg("rt_hip_plan_set_scan_seeds: the plan was created without a seed (scan seeds need the gain-only mode)");
-    if (suffix_scan(p))
-        return fail_arg("rt_hip_plan_set_scan_seeds: the suffix scan is on (it takes no scan seeds)");
-    if (!p->scan_on)
-        return fail_arg("rt_hip_plan_set_scan_seeds: the length scan is off (rt_hip_plan_enable_length_scan first)");
-    const int rv = seeds_validate(p, "rt_hip_plan_set_scan_seeds", n_seed, seeds);
-    if (rv != RT_OK)
-        return rv;
-    return seeds_install(p, n_seed, seeds, true);
-}
-
-} // extern "C"
 
 // Settles the last run, packs the tables of the seeds into one device block and makes them the plan's seed set
 // (of_scan: the seeds of its scan); n_seed = 0 removes them.
@@ -1631,149 +1607,93 @@ static int seeds_install(rt_hip_plan *p, int n_seed, const rt_seed *seeds, bool 
     return plan_build_seedset_tabs(p);
 }
 
+// What an installer of seeds requires of the plan: its flavour -- an emission plan (the seeds are ASE seeds and bring their
+// scales) or a seeded one -- and its scans; and the words of its refusals that are its own.
+enum ScanNeed { SCANS_OFF, LENGTH_SCAN_ON, SUFFIX_SCAN_ON };
+struct SeedsEntry {
+    const char *who;
+    bool emission;
+    ScanNeed scan;
+    const char *with_seed, *no_E0; // the wrong flavour: a seed where none may be (or none where one must be), tables without E0
+    const char *noun, *runs;       // the seeds, as the refusals by the plan's scans and output modes name them
+};
+static const SeedsEntry SET_SEEDS = { "rt_hip_plan_set_seeds", false, SCANS_OFF, ": the plan was created without a seed (a set needs the gain-only mode)", nullptr,
+                                      "a seed set", "a set runs" };
+static const SeedsEntry SET_SCAN_SEEDS = { "rt_hip_plan_set_scan_seeds", false, LENGTH_SCAN_ON,
+                                           ": the plan was created without a seed (scan seeds need the gain-only mode)", nullptr, "scan seeds", nullptr };
+// ASE seeds: up to RT_N_SEED_MAX seed beams on an EMISSION plan (include/rt_hip.h).  The seeds travel as a set's do; what
+// makes them ASE seeds is the plan: use_emis with n_seed > 0.
+static const SeedsEntry SET_ASE_SEEDS = { "rt_hip_plan_set_ase_seeds", true, SCANS_OFF, ": not an emission plan (created without a seed, tables with E0)",
+                                          ": not an emission plan (created without a seed, tables with E0)", "ASE seeds", "ASE seeds run" };
+// ... of a length scan: they travel as the seeds of a scan do (n_scan_seed); use_emis with n_scan_seed > 0
+static const SeedsEntry SET_SCAN_ASE_SEEDS = { "rt_hip_plan_set_scan_ase_seeds", true, LENGTH_SCAN_ON, ": not an emission plan (created without a seed, tables with E0)",
+                                               ": not an emission plan (created without a seed, tables with E0)", "ASE seeds", nullptr };
+// ... of a suffix scan, on a BACKWARD emission plan: the plan's method says which scan the seeds of a scan belong to
+static const SeedsEntry SET_SUFFIX_ASE_SEEDS = { "rt_hip_plan_set_suffix_ase_seeds", true, SUFFIX_SCAN_ON,
+                                                 ": the plan was created with a seed (the ASE record needs an emission plan)",
+                                                 ": not an emission plan (tables without E0)", nullptr, nullptr };
+
+// The five rt_hip_plan_set_*seeds: the plan's flavour, its scans, the seeds' tables (before the scans where the scans must be
+// off, as each entry point has always ordered them), the install, the scales.
+static int seeds_set(rt_hip_plan *p, const SeedsEntry &e, int n_seed, const rt_seed *seeds, const double *scales)
+{
+    auto fail = [&](const std::string &what) { return fail_arg((e.who + what).c_str()); };
+    if (!p)
+        return fail(": NULL plan");
+    if (e.scan == SUFFIX_SCAN_ON && p->P.method != 1)
+        return fail(": the plan's method is not 1 (a forward plan takes rt_hip_plan_set_scan_ase_seeds)");
+    if (e.emission == (p->P.has_seed != 0))
+        return fail(e.with_seed);
+    if (e.emission && !p->P.use_emis)
+        return fail(e.no_E0);
+    if (e.scan == SCANS_OFF) {
+        const int rv = seeds_validate(p, e.who, n_seed, seeds);
+        if (rv != RT_OK)
+            return rv;
+        const std::string scan = suffix_scan(p) ? "suffix" : "length";
+        if ((e.emission || n_seed > 0) && p->scan_on)
+            return fail(": the " + scan + " scan is on (" + e.noun + " and a " + scan + " scan exclude each other)");
+        if (n_seed > 0 && (p->path_on || p->spectra_on))
+            return fail(std::string(": the path tracer or spectra mode is enabled (") + e.runs + " in step mode only)");
+        if (!e.emission && n_seed == 0 && p->n_scan_seed > 0) // (the seeds of a scan are rt_hip_plan_set_scan_seeds': there is no set to remove)
+            return RT_OK;
+    } else {
+        if (e.scan == LENGTH_SCAN_ON && suffix_scan(p))
+            return fail(std::string(": the suffix scan is on (it takes no ") + e.noun + ")");
+        if (!p->scan_on)
+            return fail(e.scan == LENGTH_SCAN_ON ? ": the length scan is off (rt_hip_plan_enable_length_scan first)"
+                                                 : ": the suffix scan is off (rt_hip_plan_enable_suffix_scan first)");
+        if (e.scan == SUFFIX_SCAN_ON && n_seed > RT_N_SEED_MAX)
+            return fail(": more than RT_N_SEED_MAX seeds");
+        if (e.scan == SUFFIX_SCAN_ON && p->n_seed > 0) // (no call leads here: every installer of a set or of ASE seeds refuses a plan whose suffix scan is on)
+            return fail(": the plan holds ASE seeds or a seed set (they and a suffix scan exclude each other)");
+        const int rv = seeds_validate(p, e.who, n_seed, seeds);
+        if (rv != RT_OK)
+            return rv;
+    }
+    const int rc = seeds_install(p, n_seed, seeds, e.scan != SCANS_OFF);
+    if (rc != RT_OK || !e.emission)
+        return rc;
+    for (int s = 0; s < RT_N_SEED_MAX; s++)
+        p->ase_scale[s] = (s < n_seed && scales) ? scales[s] : p->P.scale;
+    return RT_OK;
+}
 
 extern "C" {
 
-// ASE seeds: up to RT_N_SEED_MAX seed beams on an EMISSION plan (include/rt_hip.h).  The seeds travel as a set's do
-// (seeds_validate, seeds_install); what makes them ASE seeds is the plan: use_emis with n_seed > 0.
+int rt_hip_plan_set_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds) { return seeds_set(p, SET_SEEDS, n_seed, seeds, nullptr); }
+int rt_hip_plan_set_scan_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds) { return seeds_set(p, SET_SCAN_SEEDS, n_seed, seeds, nullptr); }
 int rt_hip_plan_set_ase_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds, const double *scales)
 {
-    if (!p)
-        return fail_arg("rt_hip_plan_set_ase_seeds: NULL plan");
-    if (p->P.has_seed || !p->P.use_emis)
-        return fail_arg("rt_hip_plan_set_ase_seeds: not an emission plan (created without a seed, tables with E0)");
-    const int rv = seeds_validate(p, "rt_hip_plan_set_ase_seeds", n_seed, seeds);
-    if (rv != RT_OK)
-        return rv;
-    if (p->scan_on)
-        return fail_arg(suffix_scan(p) ? "rt_hip_plan_set_ase_seeds: the suffix scan is on (ASE seeds and a suffix scan exclude each other)"
-                                       : "rt_hip_plan_set_ase_seeds: the length scan is on (ASE seeds and a length scan exclude each other)");
-    if (n_seed > 0 && (p->path_on || p->spectra_on))
-        return fail_arg("rt_hip_plan_set_ase_seeds: the path tracer or spectra mode is enabled (ASE seeds run in step mode only)");
-    const int rc = seeds_install(p, n_seed, seeds, false);
-    if (rc != RT_OK)
-        return rc;
-    for (int s = 0; s < RT_N_SEED_MAX; s++)
-        p->ase_scale[s] = (s < n_seed && scales) ? scales[s] : p->P.scale;
-    return RT_OK;
+    return seeds_set(p, SET_ASE_SEEDS, n_seed, seeds, scales);
 }
-
-// ASE seeds of a length scan: the same seeds on an emission plan whose scan is on (include/rt_hip.h).  They travel as the
-// seeds of a scan do (n_scan_seed); what makes them ASE seeds is the plan again: use_emis with n_scan_seed > 0.
 int rt_hip_plan_set_scan_ase_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds, const double *scales)
 {
-    if (!p)
-        return fail_arg("rt_hip_plan_set_scan_ase_seeds: NULL plan");
-    if (p->P.has_seed || !p->P.use_emis)
-        return fail_arg("rt_hip_plan_set_scan_ase_seeds: not an emission plan (created without a seed, tables with E0)");
-    if (suffix_scan(p))
-        return fail_arg("rt_hip_plan_set_scan_ase_seeds: the suffix scan is on (it takes no ASE seeds)");
-    if (!p->scan_on)
-        return fail_arg("rt_hip_plan_set_scan_ase_seeds: the length scan is off (rt_hip_plan_enable_length_scan first)");
-    const int rv = seeds_validate(p, "rt_hip_plan_set_scan_ase_seeds", n_seed, seeds);
-    if (rv != RT_OK)
-        return rv;
-    const int rc = seeds_install(p, n_seed, seeds, true);
-    if (rc != RT_OK)
-        return rc;
-    for (int s = 0; s < RT_N_SEED_MAX; s++)
-        p->ase_scale[s] = (s < n_seed && scales) ? scales[s] : p->P.scale;
-    return RT_OK;
+    return seeds_set(p, SET_SCAN_ASE_SEEDS, n_seed, seeds, scales);
 }
-
-// ASE seeds of a suffix scan: the same seeds on a BACKWARD emission plan whose suffix scan is on (include/rt_hip.h).  They
-// travel as the seeds of a scan do (n_scan_seed); the plan's method says which scan they belong to.
 int rt_hip_plan_set_suffix_ase_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds, const double *scales)
 {
-    if (!p)
-        return fail_arg("rt_hip_plan_set_suffix_ase_seeds: NULL plan");
-    if (p->P.method != 1)
-        return fail_arg("rt_hip_plan_set_suffix_ase_seeds: the plan's method is not 1 (a forward plan takes rt_hip_plan_set_scan_ase_seeds)");
-    if (p->P.has_seed)
-        return fail_arg("rt_hip_plan_set_suffix_ase_seeds: the plan was created with a seed (the ASE record needs an emission plan)");
-    if (!p->P.use_emis)
-        return fail_arg("rt_hip_plan_set_suffix_ase_seeds: not an emission plan (tables without E0)");
-    if (!p->scan_on)
-        return fail_arg("rt_hip_plan_set_suffix_ase_seeds: the suffix scan is off (rt_hip_plan_enable_suffix_scan first)");
-    if (n_seed > RT_N_SEED_MAX)
-        return fail_arg("rt_hip_plan_set_suffix_ase_seeds: more than RT_N_SEED_MAX seeds");
-    if (p->n_seed > 0) // (no call leads here: every installer of a set or of ASE seeds refuses a plan whose suffix scan is on)
-        return fail_arg("rt_hip_plan_set_suffix_ase_seeds: the plan holds ASE seeds or a seed set (they and a suffix scan exclude each other)");
-    const int rv = seeds_validate(p, "rt_hip_plan_set_suffix_ase_seeds", n_seed, seeds);
-    if (rv != RT_OK)
-        return rv;
-    const int rc = seeds_install(p, n_seed, seeds, true);
-    if (rc != RT_OK)
-        return rc;
-    for (int s = 0; s < RT_N_SEED_MAX; s++)
-        p->ase_scale[s] = (s < n_seed && scales) ? scales[s] : p->P.scale;
-    return RT_OK;
-}
-
-int rt_hip_plan_fetch_full_length_step(rt_hip_plan *p, int r, int n, double *E_v, double *nf, double *I_ang, unsigned int *failure_code)
-{
-    if (!p || !p->last_records.ase_scan()) // (of a length scan or of a suffix scan, as rt_hip_plan_fetch_length_step serves both scans)
-        return fail_arg("rt_hip_plan_fetch_full_length_step: the last run was not a step run of a length scan with ASE seeds");
-    if (p->last_records.block(r, 2) < 0) // (every scan has length 2)
-        return fail_arg("rt_hip_plan_fetch_full_length_step: r must be 0 (ASE) .. n_seed of the last run");
-    if (p->last_records.block(r, n) < 0)
-        return fail_arg("rt_hip_plan_fetch_full_length_step: n must be 2 .. N of the last run");
-    return record_fetch(p, p->last_records.block(r, n), E_v, nf, I_ang, failure_code);
-}
-
-int rt_hip_plan_full_length_step_ptrs(rt_hip_plan *p, int r, int n, double **E_v_dev, double **nf_dev, double **iang_dev)
-{
-    if (!p || !p->last_records.ase_scan())
-        return fail_arg("rt_hip_plan_full_length_step_ptrs: the last run was not a step run of a length scan with ASE seeds");
-    if (p->last_records.block(r, 2) < 0)
-        return fail_arg("rt_hip_plan_full_length_step_ptrs: r must be 0 (ASE) .. n_seed of the last run");
-    if (p->last_records.block(r, n) < 0)
-        return fail_arg("rt_hip_plan_full_length_step_ptrs: n must be 2 .. N of the last run");
-    return record_ptrs(p, p->last_records.block(r, n), E_v_dev, nf_dev, iang_dev);
-}
-
-int rt_hip_plan_fetch_full_step(rt_hip_plan *p, int r, double *E_v, double *nf, double *I_ang, unsigned int *failure_code)
-{
-    if (!p || p->last_records.kind != REC_ASE_SEEDS)
-        return fail_arg("rt_hip_plan_fetch_full_step: the last run was not a step run of an emission plan with ASE seeds");
-    if (p->last_records.block(r) < 0)
-        return fail_arg("rt_hip_plan_fetch_full_step: r must be 0 (ASE) .. n_seed of the last run");
-    return record_fetch(p, p->last_records.block(r), E_v, nf, I_ang, failure_code);
-}
-
-int rt_hip_plan_full_step_ptrs(rt_hip_plan *p, int r, double **E_v_dev, double **nf_dev, double **iang_dev)
-{
-    if (!p || p->last_records.kind != REC_ASE_SEEDS)
-        return fail_arg("rt_hip_plan_full_step_ptrs: the last run was not a step run of an emission plan with ASE seeds");
-    if (p->last_records.block(r) < 0)
-        return fail_arg("rt_hip_plan_full_step_ptrs: r must be 0 (ASE) .. n_seed of the last run");
-    return record_ptrs(p, p->last_records.block(r), E_v_dev, nf_dev, iang_dev);
-}
-
-} // extern "C"
-
-extern "C" {
-
-int rt_hip_plan_fetch_seed_length_step(rt_hip_plan *p, int s, int n, double *E_v, double *nf, double *I_ang, unsigned int *failure_code)
-{
-    if (!p || p->last_records.kind != REC_SCAN_SEEDS)
-        return fail_arg("rt_hip_plan_fetch_seed_length_step: the last run was not a step run of a length scan with scan seeds");
-    if (p->last_records.block(s, 2) < 0) // (every scan has length 2)
-        return fail_arg("rt_hip_plan_fetch_seed_length_step: no such seed among the scan seeds of the last run");
-    if (p->last_records.block(s, n) < 0)
-        return fail_arg("rt_hip_plan_fetch_seed_length_step: n must be 2 .. N of the last run");
-    return record_fetch(p, p->last_records.block(s, n), E_v, nf, I_ang, failure_code);
-}
-
-int rt_hip_plan_seed_length_step_ptrs(rt_hip_plan *p, int s, int n, double **E_v_dev, double **nf_dev, double **iang_dev)
-{
-    if (!p || p->last_records.kind != REC_SCAN_SEEDS)
-        return fail_arg("rt_hip_plan_seed_length_step_ptrs: the last run was not a step run of a length scan with scan seeds");
-    if (p->last_records.block(s, 2) < 0)
-        return fail_arg("rt_hip_plan_seed_length_step_ptrs: no such seed among the scan seeds of the last run");
-    if (p->last_records.block(s, n) < 0)
-        return fail_arg("rt_hip_plan_seed_length_step_ptrs: n must be 2 .. N of the last run");
-    return record_ptrs(p, p->last_records.block(s, n), E_v_dev, nf_dev, iang_dev);
+    return seeds_set(p, SET_SUFFIX_ASE_SEEDS, n_seed, seeds, scales);
 }
 
 int rt_hip_plan_kernel_ms(rt_hip_plan *p, float *ms)
@@ -1892,16 +1812,52 @@ int rt_hip_plan_fetch_probe(rt_hip_plan *p, float *gvl, float *evl, int32_t *ivl
 
 } // extern "C"
 
-// rt_hip_image_loop, and rt_hip_step_loop (image == NULL: E_v and nf instead, through step mode)
+// What a host-pointer loop asks of its plan beyond one image or one step record: which scan, which seeds, installed how.
+struct LoopRecords {
+    ScanNeed scan        = SCANS_OFF;
+    int n_seed           = 0;       // > 0: seeds[0 .. n_seed) are the seeds of the scan, or
+    const rt_seed *seeds = nullptr;
+    bool ase             = false;   // ... ASE seeds with `scales` (of the scan, where one is on): an emission plan of its own, no creation seed
+    const double *scales = nullptr;
+    // E_v, nf and I_ang hold one row per record of the run (rt_records.h: block r is row r), failure_code one code per row
+    bool rows() const { return scan != SCANS_OFF || ase; }
+};
+// step mode, the scan and the seeds of such a loop, on its fresh plan (the plan's entry points refuse what they do not take:
+// method, N, the creation seed, the tables of the seeds)
+static int loop_records(rt_hip_plan *p, const LoopRecords &o)
+{
+    int rc = rt_hip_plan_enable_step(p, 1);
+    if (rc == RT_OK && o.scan != SCANS_OFF)
+        rc = scan_switch(p, o.scan == SUFFIX_SCAN_ON ? "rt_hip_plan_enable_suffix_scan" : "rt_hip_plan_enable_length_scan", o.scan == SUFFIX_SCAN_ON, 1);
+    if (rc == RT_OK && o.n_seed > 0)
+        rc = seeds_set(p, !o.ase ? SET_SCAN_SEEDS : o.scan == SUFFIX_SCAN_ON ? SET_SUFFIX_ASE_SEEDS : o.scan == LENGTH_SCAN_ON ? SET_SCAN_ASE_SEEDS : SET_ASE_SEEDS,
+                       o.n_seed, o.seeds, o.scales);
+    return rc;
+}
+// the argument checks the host-pointer entry points share, in the order every one of them makes its own in
+static int loop_check(const char *who, bool beam_ok, bool out_ok, const rt_ray *rays, size_t n_rays, bool seeds_ok = true)
+{
+    auto fail = [&](const char *what) { return fail_arg((std::string(who) + what).c_str()); };
+    if (!beam_ok)
+        return fail(": NULL beam");
+    if (!out_ok)
+        return fail(": NULL output");
+    if (!rays && n_rays)
+        return fail(": NULL ray list");
+    if (n_rays > MAX_LIST_RAYS)
+        return fail(": 2^32 - 4096 rays or more: split the call");
+    if (!seeds_ok)
+        return fail(": n_seed must be 1 .. RT_N_SEED_MAX, with seeds");
+    return RT_OK;
+}
+
+// Every rt_hip_*_loop of one device: a plan of its own on a queue of its own, one run, the outputs through host pointers.
+// image != NULL: the image cube and I_ang; else step mode with E_v, nf and I_ang -- one record, or the rows `o` asks for.
 static int host_pointer_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed,
                              int method, const rt_ray *rays, size_t n_rays, double scale, double *image, double *E_v, double *nf,
                              double *I_ang, unsigned int *failure_code, rt_ray *failed_rays, int max_failed,
-                             int *n_failed, rt_stats *stats, bool scan = false, int n_scan_seed = 0, const rt_seed *scan_seeds = nullptr,
-                             bool suffix = false)
+                             int *n_failed, rt_stats *stats, const LoopRecords &o = LoopRecords())
 {
-    // (suffix: rt_hip_suffix_scan_loop -- scan, with the suffix scan of a backward plan in the length scan's place)
-    // (n_scan_seed > 0: rt_hip_seed_length_scan_loop -- the rows of a scan once per seed, [n_seed][N - 1][...])
-    // (scan: rt_hip_length_scan_loop -- E_v, nf and I_ang hold one row per length n = 2 .. N, failure_code one code per row)
     const bool step = image == nullptr;
     // RT_HIP_TIMING=1: wall-clock split of this call on stderr (diagnostic)
     static const bool timing = getenv("RT_HIP_TIMING") != nullptr;
@@ -1922,26 +1878,20 @@ static int host_pointer_loop(int device, int N, const rt_beam *beam, const rt_ga
         release_queue(device, q);
         return rc;
     }
-    if (step) {
-        rc = rt_hip_plan_enable_step(p, 1);
-        if (rc == RT_OK && scan)
-            rc = suffix ? rt_hip_plan_enable_suffix_scan(p, 1) : rt_hip_plan_enable_length_scan(p, 1);
-        if (rc == RT_OK && scan && n_scan_seed > 0)
-            rc = rt_hip_plan_set_scan_seeds(p, n_scan_seed, scan_seeds);
-        if (rc != RT_OK) {
-            rt_hip_plan_destroy(p);
-            release_queue(device, q);
-            return rc;
-        }
+    if (step && (rc = loop_records(p, o)) != RT_OK) {
+        rt_hip_plan_destroy(p);
+        release_queue(device, q);
+        return rc;
     }
     // (the seed-factor tables of a seeded plan are filled by a kernel outside this queue: rt_hip_plan_set_ray_grid)
     if (seed && q && hipStreamSynchronize(q) != hipSuccess)
         (void) hipGetLastError();
     lap("plan_create");
     // A list that is a whole tensor grid (what create_image builds) is not uploaded: the device
-    // generates the rays while host threads check the list against the grid, ray by ray.
+    // generates the rays while host threads check the list against the grid, ray by ray.  (Not with ASE seeds: their loops
+    // upload the list, and their outputs are not staged.)
     GridGuess G;
-    bool as_grid = n_rays >= (1u << 16) && !getenv("RT_HIP_NO_GRID_DETECT") && guess_ray_grid(rays, n_rays, G);
+    bool as_grid = !o.ase && n_rays >= (1u << 16) && !getenv("RT_HIP_NO_GRID_DETECT") && guess_ray_grid(rays, n_rays, G);
     lap("guess grid");
     if (as_grid) {
         rc = plan_set_guessed_grid(p, G, 0, (int64_t) n_rays);
@@ -1961,15 +1911,13 @@ static int host_pointer_loop(int device, int N, const rt_beam *beam, const rt_ga
         rc = plan_set_rays_deferred(p, rays, n_rays);
         if (rc == RT_OK)
             rc = rt_hip_plan_run(p, q, nullptr, nullptr);
-        if (rc == RT_OK)
+        if (rc == RT_OK && !o.ase)
             plan_stage_outputs(p);
     }
     if (rc == RT_OK)
-        rc = rt_hip_plan_fetch(p, image, step ? nullptr : I_ang, scan ? nullptr : failure_code, failed_rays, max_failed, n_failed, stats);
-    if (rc == RT_OK && step && !scan)
-        rc = rt_hip_plan_fetch_step(p, E_v, nf, I_ang);
-    if (rc == RT_OK && scan) // one row per length, with scan seeds the rows of a scan once per seed
-        rc = record_fetch_rows(p, E_v, nf, I_ang, failure_code);
+        rc = rt_hip_plan_fetch(p, image, step ? nullptr : I_ang, o.rows() ? nullptr : failure_code, failed_rays, max_failed, n_failed, stats);
+    if (rc == RT_OK && step)
+        rc = o.rows() ? record_fetch_rows(p, E_v, nf, I_ang, failure_code) : rt_hip_plan_fetch_step(p, E_v, nf, I_ang);
     lap("fetch (wait + D2H)");
     rt_hip_plan_destroy(p); // waits for whatever is still in flight
     release_queue(device, q);
@@ -1984,147 +1932,79 @@ int rt_hip_image_loop(int device, int N, const rt_beam *beam, const rt_gain *gai
                       double *I_ang, unsigned int *failure_code, rt_ray *failed_rays, int max_failed,
                       int *n_failed, rt_stats *stats)
 {
-    if (!image || !I_ang)
-        return fail_arg("rt_hip_image_loop: NULL output");
-    if (!rays && n_rays)
-        return fail_arg("rt_hip_image_loop: NULL ray list");
-    if (n_rays > MAX_LIST_RAYS)
-        return fail_arg("rt_hip_image_loop: 2^32 - 4096 rays or more: split the call");
-    return host_pointer_loop(device, N, beam, gain, seed, method, rays, n_rays, scale, image, nullptr, nullptr, I_ang, failure_code,
-                             failed_rays, max_failed, n_failed, stats);
+    const int rc = loop_check("rt_hip_image_loop", true, image && I_ang, rays, n_rays);
+    return rc != RT_OK ? rc : host_pointer_loop(device, N, beam, gain, seed, method, rays, n_rays, scale, image, nullptr, nullptr, I_ang, failure_code,
+                                                failed_rays, max_failed, n_failed, stats);
 }
 
 int rt_hip_step_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed, int method,
                      const rt_ray *rays, size_t n_rays, double scale, double *E_v, double *nf, double *I_ang,
                      unsigned int *failure_code, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats)
 {
-    if (!E_v || !nf || !I_ang)
-        return fail_arg("rt_hip_step_loop: NULL output");
-    if (!rays && n_rays)
-        return fail_arg("rt_hip_step_loop: NULL ray list");
-    if (n_rays > MAX_LIST_RAYS)
-        return fail_arg("rt_hip_step_loop: 2^32 - 4096 rays or more: split the call");
-    return host_pointer_loop(device, N, beam, gain, seed, method, rays, n_rays, scale, nullptr, E_v, nf, I_ang, failure_code,
-                             failed_rays, max_failed, n_failed, stats);
+    const int rc = loop_check("rt_hip_step_loop", true, E_v && nf && I_ang, rays, n_rays);
+    return rc != RT_OK ? rc : host_pointer_loop(device, N, beam, gain, seed, method, rays, n_rays, scale, nullptr, E_v, nf, I_ang, failure_code,
+                                                failed_rays, max_failed, n_failed, stats);
+}
+
+// The loops that return rows.  Of a scan: one row per length n = 2 .. N, with its seeds once per seed, [n_seed][N - 1][...].
+// With ASE seeds (seed == NULL): row 0 of every output is the ASE record, row 1 + s seed s; of a scan the rows
+// [1 + n_seed][N - 1][...], the ASE curve first.  with_seeds: the entry point takes seeds, 1 .. RT_N_SEED_MAX of them.
+static int rows_loop(const char *who, const LoopRecords &o, bool with_seeds, int device, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed,
+                     int method, const rt_ray *rays, size_t n_rays, double scale, double *E_v, double *nf, double *I_ang, unsigned int *failure_codes,
+                     rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats)
+{
+    const int rc = loop_check(who, beam != nullptr, !o.ase || (E_v && nf && I_ang), rays, n_rays,
+                              !with_seeds || (o.n_seed >= 1 && o.n_seed <= RT_N_SEED_MAX && o.seeds));
+    return rc != RT_OK ? rc : host_pointer_loop(device, N, beam, gain, seed, method, rays, n_rays, scale, nullptr, E_v, nf, I_ang, failure_codes,
+                                                failed_rays, max_failed, n_failed, stats, o);
 }
 
 int rt_hip_length_scan_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed, int method,
                             const rt_ray *rays, size_t n_rays, double scale, double *E_v, double *nf, double *I_ang,
                             unsigned int *failure_codes, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats)
 {
-    if (!beam)
-        return fail_arg("rt_hip_length_scan_loop: NULL beam");
-    if (!rays && n_rays)
-        return fail_arg("rt_hip_length_scan_loop: NULL ray list");
-    if (n_rays > MAX_LIST_RAYS)
-        return fail_arg("rt_hip_length_scan_loop: 2^32 - 4096 rays or more: split the call");
-    // (method, N: rt_hip_plan_enable_length_scan refuses what the scan does not take)
-    return host_pointer_loop(device, N, beam, gain, seed, method, rays, n_rays, scale, nullptr, E_v, nf, I_ang, failure_codes,
-                             failed_rays, max_failed, n_failed, stats, true);
+    return rows_loop("rt_hip_length_scan_loop", LoopRecords{ LENGTH_SCAN_ON }, false, device, N, beam, gain, seed, method, rays, n_rays, scale, E_v, nf, I_ang,
+                     failure_codes, failed_rays, max_failed, n_failed, stats);
 }
 
 int rt_hip_suffix_scan_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed, int method,
                             const rt_ray *rays, size_t n_rays, double scale, double *E_v, double *nf, double *I_ang,
                             unsigned int *failure_codes, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats)
 {
-    if (!beam)
-        return fail_arg("rt_hip_suffix_scan_loop: NULL beam");
-    if (!rays && n_rays)
-        return fail_arg("rt_hip_suffix_scan_loop: NULL ray list");
-    if (n_rays > MAX_LIST_RAYS)
-        return fail_arg("rt_hip_suffix_scan_loop: 2^32 - 4096 rays or more: split the call");
-    // (method, N: rt_hip_plan_enable_suffix_scan refuses what the scan does not take)
-    return host_pointer_loop(device, N, beam, gain, seed, method, rays, n_rays, scale, nullptr, E_v, nf, I_ang, failure_codes,
-                             failed_rays, max_failed, n_failed, stats, true, 0, nullptr, true);
+    return rows_loop("rt_hip_suffix_scan_loop", LoopRecords{ SUFFIX_SCAN_ON }, false, device, N, beam, gain, seed, method, rays, n_rays, scale, E_v, nf, I_ang,
+                     failure_codes, failed_rays, max_failed, n_failed, stats);
 }
 
 int rt_hip_seed_length_scan_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed, int method,
                                  const rt_ray *rays, size_t n_rays, double scale, int n_seed, const rt_seed *seeds, double *E_v, double *nf,
                                  double *I_ang, unsigned int *failure_codes, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats)
 {
-    if (!beam)
-        return fail_arg("rt_hip_seed_length_scan_loop: NULL beam");
-    if (!rays && n_rays)
-        return fail_arg("rt_hip_seed_length_scan_loop: NULL ray list");
-    if (n_rays > MAX_LIST_RAYS)
-        return fail_arg("rt_hip_seed_length_scan_loop: 2^32 - 4096 rays or more: split the call");
-    if (n_seed < 1 || n_seed > RT_N_SEED_MAX || !seeds)
-        return fail_arg("rt_hip_seed_length_scan_loop: n_seed must be 1 .. RT_N_SEED_MAX, with seeds");
-    // (method, N, the creation seed, the tables of the seeds: the plan's entry points refuse what the scan does not take)
-    return host_pointer_loop(device, N, beam, gain, seed, method, rays, n_rays, scale, nullptr, E_v, nf, I_ang, failure_codes,
-                             failed_rays, max_failed, n_failed, stats, true, n_seed, seeds);
-}
-
-// The whole per-step record through host pointers: an emission plan of its own with the seeds as ASE seeds, the list
-// uploaded, one run; row 0 of every output is the ASE record, row 1 + s seed s.
-// (scan 1: rt_hip_full_length_scan_loop -- the length scan on, the seeds as its ASE seeds, rows [1 + n_seed][N - 1][...];
-// scan 2: rt_hip_full_suffix_scan_loop -- the same with the suffix scan of a backward plan)
-static int full_step_loop(const char *who, int scan, int device, int N, const rt_beam *beam, const rt_gain *gain, int method, const rt_ray *rays,
-                          size_t n_rays, double scale, int n_seed, const rt_seed *seeds, const double *scales, double *E_v, double *nf, double *I_ang,
-                          unsigned int *failure_codes, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats)
-{
-    auto fail = [&](const char *what) { return fail_arg((std::string(who) + what).c_str()); };
-    if (!beam)
-        return fail(": NULL beam");
-    if (!E_v || !nf || !I_ang)
-        return fail(": NULL output");
-    if (!rays && n_rays)
-        return fail(": NULL ray list");
-    if (n_rays > MAX_LIST_RAYS)
-        return fail(": 2^32 - 4096 rays or more: split the call");
-    if (n_seed < 1 || n_seed > RT_N_SEED_MAX || !seeds)
-        return fail(": n_seed must be 1 .. RT_N_SEED_MAX, with seeds");
-    hipStream_t q  = lease_queue(device);
-    rt_hip_plan *p = nullptr;
-    int rc         = plan_create_on(&p, q, device, N, beam, gain, nullptr, method, scale);
-    if (rc != RT_OK) {
-        release_queue(device, q);
-        return rc;
-    }
-    rc = rt_hip_plan_enable_step(p, 1);
-    if (rc == RT_OK && scan)
-        rc = scan == 2 ? rt_hip_plan_enable_suffix_scan(p, 1) : rt_hip_plan_enable_length_scan(p, 1);
-    if (rc == RT_OK)
-        rc = scan == 2 ? rt_hip_plan_set_suffix_ase_seeds(p, n_seed, seeds, scales)
-             : scan  ? rt_hip_plan_set_scan_ase_seeds(p, n_seed, seeds, scales)
-                     : rt_hip_plan_set_ase_seeds(p, n_seed, seeds, scales);
-    if (rc == RT_OK)
-        rc = plan_set_rays_deferred(p, rays, n_rays);
-    if (rc == RT_OK)
-        rc = rt_hip_plan_run(p, q, nullptr, nullptr);
-    if (rc == RT_OK)
-        rc = rt_hip_plan_fetch(p, nullptr, nullptr, nullptr, failed_rays, max_failed, n_failed, stats);
-    if (rc == RT_OK)
-        rc = record_fetch_rows(p, E_v, nf, I_ang, failure_codes);
-    rt_hip_plan_destroy(p); // waits for whatever is still in flight
-    release_queue(device, q);
-    return rc;
+    return rows_loop("rt_hip_seed_length_scan_loop", LoopRecords{ LENGTH_SCAN_ON, n_seed, seeds }, true, device, N, beam, gain, seed, method, rays, n_rays,
+                     scale, E_v, nf, I_ang, failure_codes, failed_rays, max_failed, n_failed, stats);
 }
 
 int rt_hip_full_step_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, int method, const rt_ray *rays, size_t n_rays,
                           double scale, int n_seed, const rt_seed *seeds, const double *scales, double *E_v, double *nf, double *I_ang,
                           unsigned int *failure_codes, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats)
 {
-    return full_step_loop("rt_hip_full_step_loop", 0, device, N, beam, gain, method, rays, n_rays, scale, n_seed, seeds, scales, E_v, nf, I_ang,
-                          failure_codes, failed_rays, max_failed, n_failed, stats);
+    return rows_loop("rt_hip_full_step_loop", LoopRecords{ SCANS_OFF, n_seed, seeds, true, scales }, true, device, N, beam, gain, nullptr, method, rays,
+                     n_rays, scale, E_v, nf, I_ang, failure_codes, failed_rays, max_failed, n_failed, stats);
 }
 
-// ... at every length: the length scan on, the seeds as its ASE seeds; rows [1 + n_seed][N - 1][...], the ASE curve first
 int rt_hip_full_length_scan_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, int method, const rt_ray *rays, size_t n_rays,
                                  double scale, int n_seed, const rt_seed *seeds, const double *scales, double *E_v, double *nf, double *I_ang,
                                  unsigned int *failure_codes, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats)
 {
-    return full_step_loop("rt_hip_full_length_scan_loop", 1, device, N, beam, gain, method, rays, n_rays, scale, n_seed, seeds, scales, E_v, nf,
-                          I_ang, failure_codes, failed_rays, max_failed, n_failed, stats);
+    return rows_loop("rt_hip_full_length_scan_loop", LoopRecords{ LENGTH_SCAN_ON, n_seed, seeds, true, scales }, true, device, N, beam, gain, nullptr, method,
+                     rays, n_rays, scale, E_v, nf, I_ang, failure_codes, failed_rays, max_failed, n_failed, stats);
 }
 
-// ... of the run of the LAST n lengths, n = 2 .. N: the suffix scan of a backward plan on, the seeds as its ASE seeds; the same rows
 int rt_hip_full_suffix_scan_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, int method, const rt_ray *rays, size_t n_rays,
                                  double scale, int n_seed, const rt_seed *seeds, const double *scales, double *E_v, double *nf, double *I_ang,
                                  unsigned int *failure_codes, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats)
 {
-    return full_step_loop("rt_hip_full_suffix_scan_loop", 2, device, N, beam, gain, method, rays, n_rays, scale, n_seed, seeds, scales, E_v, nf,
-                          I_ang, failure_codes, failed_rays, max_failed, n_failed, stats);
+    return rows_loop("rt_hip_full_suffix_scan_loop", LoopRecords{ SUFFIX_SCAN_ON, n_seed, seeds, true, scales }, true, device, N, beam, gain, nullptr, method,
+                     rays, n_rays, scale, E_v, nf, I_ang, failure_codes, failed_rays, max_failed, n_failed, stats);
 }
 
 int rt_hip_calc_rays(int device, int N, double dz, const rt_gain *gain, const rt_seed *seed, int K, int method, const double *rays,

@@ -14,6 +14,11 @@
 //   REC_SCAN_ASE_SEEDS   (1 + n_seed) L  (r, n) -> r L + n - 2; n alone: the ASE curve  L - 1 (ASE, all N lengths)
 //   REC_RSCAN            L               the LAST n lengths, n = 2 .. L + 1 -> n - 2    L - 1 (all N lengths)
 //   REC_RSCAN_ASE_SEEDS  (1 + n_seed) L  (r, n) -> r L + n - 2, the LAST n lengths         L - 1 (ASE, all N lengths)
+//
+// The table is code twice below: record_kinds[] holds what tells the kinds apart, one row each, and RecordSet derives every
+// column from the row; the static_asserts at the end restate the table at n_seed = 2, L = 3, in range and out of it.  A new
+// kind is one row here (and its static_assert), one kernel block in launch_pass (rt_launch.hip) and thin extern "C" callers
+// of the shared installer, accessors and loop driver (rt_plan.hip).
 #pragma once
 
 #include <cstddef>
@@ -31,47 +36,91 @@ enum PassKind {
 };
 
 enum RecordKind { REC_NONE = 0, REC_SEEDS, REC_ASE_SEEDS, REC_SCAN, REC_SCAN_SEEDS, REC_SCAN_ASE_SEEDS, REC_RSCAN, REC_RSCAN_ASE_SEEDS };
+constexpr int REC_N_KINDS = REC_RSCAN_ASE_SEEDS + 1;
+
+// What tells the kinds apart, one row per kind; everything RecordSet says of a kind is derived from its row.
+struct RecordKindRow {
+    bool lengths;     // one block per length n = 2 .. L + 1 (of every seed or record)
+    bool ase;         // a leading ASE record: r = 0 .. n_seed
+    bool seeds;       // it carries seeds: s = 0 .. n_seed - 1 (behind the ASE record where there is one)
+    bool suffix;      // the suffix form: the lengths are the LAST n of a backward march
+    PassKind pass;    // the kernel that leaves the records (rt_launch.hip, launch_pass)
+    size_t bad_word;  // bytes per ray of the marks of a checking repeat: one bit per seed in a byte, per length in a 32-bit word,
+                      // per (seed, length) in a 64-bit word, per (record, length) in four 32-bit words
+    const char *name; // as the messages name the kind ("step kernel of <name>")
+    const char *acc;  // its E_v accumulators in the LDS, as the message of a pass that does not fit names them
+};
+constexpr RecordKindRow record_kinds[REC_N_KINDS] = {
+    // lengths ase  seeds  suffix
+    { false, false, false, false, PASS_STEP, 1, "a step run", "" },                                             // REC_NONE
+    { false, false, true, false, PASS_SEEDS, 1, "a seed set", "per seed" },                                     // REC_SEEDS
+    { false, true, true, false, PASS_ASE_SEEDS, 1, "an emission plan with ASE seeds", "for ASE and per seed" }, // REC_ASE_SEEDS
+    { true, false, false, false, PASS_SCAN, 4, "a length scan", "per length" },                                 // REC_SCAN
+    { true, false, true, false, PASS_SCAN_SEEDS, 8, "a length scan with scan seeds", "per seed and length" },   // REC_SCAN_SEEDS
+    { true, true, true, false, PASS_SCAN_ASE_SEEDS, 16, "a length scan with ASE seeds", "per record and length" }, // REC_SCAN_ASE_SEEDS
+    { true, false, false, true, PASS_RSCAN, 4, "a suffix scan", "per length" },                                 // REC_RSCAN
+    { true, true, true, true, PASS_RSCAN_ASE_SEEDS, 16, "a suffix scan with ASE seeds", "per record and length" }, // REC_RSCAN_ASE_SEEDS
+};
 
 struct RecordSet {
     RecordKind kind = REC_NONE; // REC_NONE: one step record in the plan's step buffers (or no step run at all)
     int n_seed      = 0;        // seeds of the set, ASE seeds, seeds of the scan
     int L           = 0;        // lengths of a scan (N - 1)
 
-    bool scan() const { return kind == REC_SCAN || kind == REC_SCAN_SEEDS || ase_scan() || kind == REC_RSCAN; }
+    constexpr const RecordKindRow &row() const { return record_kinds[kind]; }
+    constexpr bool scan() const { return row().lengths; }
     // the whole step record at every n: the ASE curve and one curve per seed, of a length scan or of a suffix scan
-    bool ase_scan() const { return kind == REC_SCAN_ASE_SEEDS || kind == REC_RSCAN_ASE_SEEDS; }
-    int n_rec() const
-    {
-        return kind == REC_SEEDS ? n_seed : kind == REC_ASE_SEEDS ? 1 + n_seed : kind == REC_SCAN || kind == REC_RSCAN ? L : kind == REC_SCAN_SEEDS ? n_seed * L :
-               ase_scan() ? (1 + n_seed) * L : 0;
-    }
+    constexpr bool ase_scan() const { return row().lengths && row().ase; }
+    // values of the first index: the ASE record and the seeds, the seeds, or 0 alone (a scan without seeds)
+    constexpr int n_first() const { return row().seeds ? (row().ase ? 1 : 0) + n_seed : 1; }
+    constexpr int n_rec() const { return kind == REC_NONE ? 0 : n_first() * (row().lengths ? L : 1); }
     // the block of seed (or ASE record) s and length n, -1 where the set has no such record; a kind without lengths takes
     // no notice of n, a scan without seeds has s = 0 only
-    int block(int s, int n = 0) const
+    constexpr int block(int s, int n = 0) const
     {
-        const bool n_ok = n >= 2 && n - 1 <= L;
-        switch (kind) {
-        case REC_SEEDS: return s >= 0 && s < n_seed ? s : -1;
-        case REC_ASE_SEEDS: return s >= 0 && s <= n_seed ? s : -1;
-        case REC_SCAN:
-        case REC_RSCAN: return s == 0 && n_ok ? n - 2 : -1;
-        case REC_SCAN_SEEDS: return s >= 0 && s < n_seed && n_ok ? s * L + n - 2 : -1;
-        case REC_SCAN_ASE_SEEDS:
-        case REC_RSCAN_ASE_SEEDS: return s >= 0 && s <= n_seed && n_ok ? s * L + n - 2 : -1;
-        default: return -1;
-        }
+        if (kind == REC_NONE || s < 0 || s >= n_first())
+            return -1;
+        if (!row().lengths)
+            return s;
+        return n >= 2 && n - 1 <= L ? s * L + n - 2 : -1;
     }
     // the record rt_hip_plan_fetch and rt_hip_plan_fetch_step serve
-    int primary() const { return scan() ? L - 1 : 0; }
-    PassKind pass_kind() const
-    {
-        return kind == REC_SEEDS ? PASS_SEEDS : kind == REC_ASE_SEEDS ? PASS_ASE_SEEDS : kind == REC_SCAN ? PASS_SCAN : kind == REC_SCAN_SEEDS ? PASS_SCAN_SEEDS :
-               kind == REC_SCAN_ASE_SEEDS ? PASS_SCAN_ASE_SEEDS : kind == REC_RSCAN ? PASS_RSCAN : kind == REC_RSCAN_ASE_SEEDS ? PASS_RSCAN_ASE_SEEDS :
-               PASS_STEP;
-    }
-    // bytes per ray of the marks of a checking repeat: one bit per seed in a byte, per length in a 32-bit word, per
-    // (seed, length) in a 64-bit word, per (record, length) in four 32-bit words
-    size_t bad_word() const { return kind == REC_SCAN || kind == REC_RSCAN ? 4 : kind == REC_SCAN_SEEDS ? 8 : ase_scan() ? 16 : 1; }
+    constexpr int primary() const { return scan() ? L - 1 : 0; }
+    constexpr PassKind pass_kind() const { return row().pass; }
+    constexpr size_t bad_word() const { return row().bad_word; }
 };
+
+// ---- the table of the header comment at n_seed = 2, L = 3 (n = 2 .. 4), checked at every compile ------------------------
+namespace records_check {
+constexpr RecordSet of(RecordKind k) { return RecordSet{ k, 2, 3 }; }
+// blocks(k, first, lengths): every (s, n) of s = -1 .. first, n = 1 .. 5 maps as the table says -- inside first x lengths to
+// s L + n - 2 (without lengths: to s, whatever n), outside to -1
+constexpr bool blocks(RecordKind k, int first, bool lengths)
+{
+    for (int s = -1; s <= first + 1; s++)
+        for (int n = 0; n <= 5; n++) {
+            const bool in  = s >= 0 && s < first && (!lengths || (n >= 2 && n <= 4));
+            const int want = !in ? -1 : lengths ? s * 3 + n - 2 : s;
+            if (of(k).block(s, n) != want)
+                return false;
+        }
+    return of(k).block(0) == (first > 0 && !lengths ? 0 : -1); // (n left out: no length of a scan)
+}
+constexpr bool is(RecordKind k, int n_rec, int primary, bool scan, bool ase_scan, PassKind pass, size_t bad_word)
+{
+    return of(k).n_rec() == n_rec && of(k).primary() == primary && of(k).scan() == scan && of(k).ase_scan() == ase_scan &&
+           of(k).pass_kind() == pass && of(k).bad_word() == bad_word;
+}
+static_assert(blocks(REC_NONE, 0, false) && is(REC_NONE, 0, 0, false, false, PASS_STEP, 1), "REC_NONE: no block");
+static_assert(blocks(REC_SEEDS, 2, false) && is(REC_SEEDS, 2, 0, false, false, PASS_SEEDS, 1), "REC_SEEDS: seed s -> s");
+static_assert(blocks(REC_ASE_SEEDS, 3, false) && is(REC_ASE_SEEDS, 3, 0, false, false, PASS_ASE_SEEDS, 1), "REC_ASE_SEEDS: record r -> r");
+static_assert(blocks(REC_SCAN, 1, true) && is(REC_SCAN, 3, 2, true, false, PASS_SCAN, 4), "REC_SCAN: n -> n - 2");
+static_assert(blocks(REC_SCAN_SEEDS, 2, true) && is(REC_SCAN_SEEDS, 6, 2, true, false, PASS_SCAN_SEEDS, 8), "REC_SCAN_SEEDS: (s, n) -> s L + n - 2");
+static_assert(blocks(REC_SCAN_ASE_SEEDS, 3, true) && is(REC_SCAN_ASE_SEEDS, 9, 2, true, true, PASS_SCAN_ASE_SEEDS, 16),
+              "REC_SCAN_ASE_SEEDS: (r, n) -> r L + n - 2");
+static_assert(blocks(REC_RSCAN, 1, true) && is(REC_RSCAN, 3, 2, true, false, PASS_RSCAN, 4), "REC_RSCAN: n -> n - 2");
+static_assert(blocks(REC_RSCAN_ASE_SEEDS, 3, true) && is(REC_RSCAN_ASE_SEEDS, 9, 2, true, true, PASS_RSCAN_ASE_SEEDS, 16),
+              "REC_RSCAN_ASE_SEEDS: (r, n) -> r L + n - 2");
+} // namespace records_check
 
 } // namespace rtr
