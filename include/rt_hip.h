@@ -597,9 +597,9 @@ int rt_hip_length_scan_loop(int device, int N, const rt_beam *beam, const rt_gai
  *   RT_N_FAILED_MAX: the first of them in list order).
  * rt_hip_suffix_scan_loop: the host-pointer form, rt_hip_length_scan_loop's arguments; row n - 2 holds the record of the
  *   last n lengths.
- * Not taken with the suffix scan: the forward method, seed sets, scan seeds, the ASE seeds of a plain step or of a length
- *   scan (an emission plan takes rt_hip_plan_set_suffix_ase_seeds, below), the one-launch form, the multi-device loops,
- *   image, spectra and path runs.
+ * Not taken with the suffix scan: the forward method, seed sets, the scan seeds of a length scan, the ASE seeds of a plain
+ *   step or of a length scan (an emission plan takes rt_hip_plan_set_suffix_ase_seeds, a seeded plan
+ *   rt_hip_plan_set_suffix_seeds, both below), the one-launch form, the multi-device loops, image, spectra and path runs.
  */
 int rt_hip_plan_enable_suffix_scan(rt_hip_plan *plan, int on);
 int rt_hip_suffix_scan_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed, int method,
@@ -784,6 +784,44 @@ int rt_hip_full_suffix_scan_loop(int device, int N, const rt_beam *beam, const r
                                  size_t n_rays, double scale, int n_seed, const rt_seed *seeds, const double *scales,
                                  double *E_v, double *nf, double *I_ang, unsigned int *failure_codes, rt_ray *failed_rays,
                                  int max_failed, int *n_failed, rt_stats *stats);
+
+/*
+ * The seeds of a suffix scan: the step record of every seed beam of the run of the LAST n lengths, n = 2 .. N, from ONE
+ * backward march -- what rt_hip_plan_set_scan_seeds is to the length scan, for a seeded amplifier traced with the backward
+ * method.  Neither the march nor the boundary states depend on the seed: with suffix seeds installed a step run of a seeded
+ * backward plan whose suffix scan is on marches once (the suffix-scan march of the seeded plan unchanged) and
+ * rt_step_rscan_seeds_kernel (raytrace-miniapp_amd/csrc/rt_step_rscan_seeds.hip, in place of rt_step_rscan_kernel; reported
+ * as freq_ms) leaves record (s, n) for s < n_seed and n = 2 .. N:
+ *   (s, n)  what a step run leaves of the suffix problem of the last n lengths CREATED WITH SEED s -- the same tables, rays,
+ *           method and scale: Iv[k] = f0_{s,n} f_s[4][k] exp(gl_n[k]), the seed factor at the position and exit angles of the
+ *           state that serves record n, 0 where the ray has escaped by then.
+ *   Every Iv is the double the suffix-scan plan created with seed s computes -- exp(gl_n) is taken once for all seeds --; the
+ *   sums differ from that plan's by summation order only.
+ * set_suffix_seeds: accepted only on a backward (method 1) plan created with a seed (which fixes the gain-only mode and is
+ *   not part of the seeds, as with rt_hip_plan_set_scan_seeds) while its suffix scan is on; a forward plan, a plan created
+ *   without a seed and a plan whose suffix scan is off are RT_ERR_ARG, each with its reason.  n_seed = 1 .. RT_N_SEED_MAX
+ *   installs seeds[0 .. n_seed), validated and copied as rt_hip_plan_set_seeds does it (no factor tables: the backward
+ *   method never takes the factor at a grid point); n_seed = 0 removes them: the plan is then a plain suffix-scan plan, bit
+ *   for bit.  A rejected call leaves the installed seeds as they were.  rt_hip_plan_enable_suffix_scan(plan, 0) drops them;
+ *   rt_hip_plan_update_gain / _dev keep them; rt_hip_plan_set_step_one_launch is accepted, the run keeps two kernels.  Every
+ *   refusal of the suffix scan stays: rt_hip_plan_set_seeds, rt_hip_plan_set_ase_seeds, rt_hip_plan_set_scan_seeds,
+ *   rt_hip_plan_set_scan_ase_seeds and rt_hip_plan_set_suffix_ase_seeds refuse such a plan as before.
+ * Outputs: the layout of a length scan with scan seeds: n_seed (N - 1) blocks of one allocation, record (s, n) = block
+ *   s (N - 1) + (n - 2), served by rt_hip_plan_fetch_seed_length_step and rt_hip_plan_seed_length_step_ptrs;
+ *   rt_hip_plan_fetch_length_step and rt_hip_plan_length_step_ptrs serve seed 0's curve, rt_hip_plan_fetch_step,
+ *   rt_hip_plan_step_ptrs and I_ang of rt_hip_plan_fetch record (0, N).  rt_hip_plan_history_append files all of them.
+ * Failures follow the reference run once per (seed, n): error -1 of the state that serves n puts the ray in no record
+ *   (s, n) and sets bit 1 in each of their codes; error -2 / -3 under (s, n) removes the ray from (s, n) only; a failing ray
+ *   is reported once (more than RT_N_FAILED_MAX: the first of them in list order).  The checking repeat marks one bit per
+ *   (seed, n) in a 64-bit word per ray.
+ * rt_hip_seed_suffix_scan_loop: the host-pointer form, the arguments and rows of rt_hip_seed_length_scan_loop; method 1.
+ * Not taken: the C++ adapter, the multi-device loops, the one-launch form.
+ */
+int rt_hip_plan_set_suffix_seeds(rt_hip_plan *plan, int n_seed, const rt_seed *seeds);
+int rt_hip_seed_suffix_scan_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed, int method,
+                                 const rt_ray *rays, size_t n_rays, double scale, int n_seed, const rt_seed *seeds, double *E_v,
+                                 double *nf, double *I_ang, unsigned int *failure_codes, rt_ray *failed_rays, int max_failed,
+                                 int *n_failed, rt_stats *stats);
 
 /*
  * Step history: the step records of a time loop filed ON THE DEVICE.  What the application does on the host after every

@@ -165,7 +165,7 @@ class Plan:
     _ring = 0                   # runs of the timing ring (set_timing_ring)
     _scan = False               # the length scan or the suffix scan is on (enable_length_scan, enable_suffix_scan)
     _n_seed = 0                 # seeds of the set (set_seeds)
-    _n_scan_seed = 0            # seeds of the length scan (set_scan_seeds)
+    _n_scan_seed = 0            # seeds of the length scan or of the suffix scan (set_scan_seeds, set_suffix_seeds)
     _n_ase_seed = 0             # ASE seeds (set_ase_seeds)
     _n_scan_ase_seed = 0        # ASE seeds of the length scan or of the suffix scan (set_scan_ase_seeds, set_suffix_ase_seeds)
 
@@ -367,10 +367,15 @@ class Plan:
         """A seed set (include/rt_hip.h, rt_hip_plan_set_seeds): up to RT_N_SEED_MAX Seed records whose step records one
         run leaves, from one march; [] removes the set.  The plan must have been created with a seed.  More seeds than
         that, or anything that is not a Seed, is a ValueError raised here, before any native call."""
-        seeds, arr, _keep = _seed_array(seeds, "set_seeds", "a set")
-        self.hl.check(self.hl.lib.rt_hip_plan_set_seeds(self._h, len(seeds), arr if seeds else None), "rt_hip_plan_set_seeds")
-        self._n_seed = len(seeds)
+        self._n_seed = self._install_seeds("set_seeds", seeds, "a set")
         return self
+
+    def _install_seeds(self, who: str, seeds, what: str) -> int:
+        """set_seeds, set_scan_seeds and set_suffix_seeds behind their own checks: the seeds, checked and marshalled, through
+        rt_hip_plan_<who>; returns how many were installed."""
+        seeds, arr, _keep = _seed_array(seeds, who, what)
+        self.hl.check(getattr(self.hl.lib, "rt_hip_plan_" + who)(self._h, len(seeds), arr if seeds else None), "rt_hip_plan_" + who)
+        return len(seeds)
 
     def fetch_seed_steps(self) -> list:
         """[dict(E_v [nv], nf [nx * ny], I_ang [na * nb], failure_code)] per seed of the set of the last step run (waits for
@@ -502,9 +507,26 @@ class Plan:
         step run with the scan on then leaves one record per seed and length n = 2 .. N from one march; [] removes them.
         The scan must be on and the plan created with a seed.  More seeds than that, or anything that is not a Seed, is a
         ValueError raised here, before any native call."""
-        seeds, arr, _keep = _seed_array(seeds, "set_scan_seeds", "a scan")
-        self.hl.check(self.hl.lib.rt_hip_plan_set_scan_seeds(self._h, len(seeds), arr if seeds else None), "rt_hip_plan_set_scan_seeds")
-        self._n_scan_seed = len(seeds)
+        self._n_scan_seed = self._install_seeds("set_scan_seeds", seeds, "a scan")
+        return self
+
+    def set_suffix_seeds(self, seeds) -> "Plan":
+        """The seeds of the suffix scan (include/rt_hip.h, rt_hip_plan_set_suffix_seeds): up to RT_N_SEED_MAX Seed records on
+        a backward plan created with a seed whose suffix scan is on.  A step run then leaves, from one backward march, one
+        record per seed of the run of the last n lengths for n = 2 .. N; fetch_seed_length_steps, seed_length_step_ptrs and
+        seed_length_step_tensors serve them, fetch_length_steps seed 0's curve; [] removes the seeds.  A forward problem, a
+        problem without a seed, a plan whose suffix scan is off, more seeds than that, or anything that is not a Seed is a
+        ValueError raised here, before any native call."""
+        p = self.problem
+        if p.method != 1:
+            raise ValueError(f"set_suffix_seeds: the problem's method is {p.method}; the suffix scan takes the backward "
+                             "method (1) only (a forward plan takes set_scan_seeds)")
+        if p.seed is None:
+            raise ValueError("set_suffix_seeds: the plan was created without a seed (an emission plan takes set_suffix_ase_seeds)")
+        if not self._scan:
+            raise ValueError("set_suffix_seeds: the suffix scan is off (enable_suffix_scan first)")
+        # (the records are those of a length scan with scan seeds: _scan_seed_range counts them)
+        self._n_scan_seed = self._install_seeds("set_suffix_seeds", seeds, "a scan")
         return self
 
     def _scan_seed_range(self):
@@ -960,10 +982,25 @@ def seed_length_scan_loop(problem: Problem, seeds, rays: np.ndarray | None = Non
     codes, failed_rays = the rays that fail anywhere, stats).  What the scan does not take (backward method, N < 3, more than
     RT_N_SCAN_MAX lengths), no seed or more than RT_N_SEED_MAX, or an entry that is not a Seed is a ValueError raised here,
     before any native call."""
-    _scan_takes("seed_length_scan_loop", problem, 2, "the scan takes the forward method (2) only")
-    seeds = _taken_seeds("seed_length_scan_loop", seeds)
+    return _seed_scan_loop("seed_length_scan_loop", 2, "the scan takes the forward method (2) only", problem, seeds, rays, device)
+
+
+def seed_suffix_scan_loop(problem: Problem, seeds, rays: np.ndarray | None = None, device: int = 0) -> dict:
+    """The step record of every seed beam of `seeds` (a list of Seed, 1 .. RT_N_SEED_MAX) of the run of the last n lengths,
+    n = 2 .. N, from ONE backward march of the problem's rays (rt_hip_seed_suffix_scan_loop; rays None: the problem's ray
+    grid as a list).  The problem must carry a seed, which is not part of `seeds`.  Returns what seed_length_scan_loop
+    returns, records[s][n - 2] the record of seed s of the last n lengths.  What the scan does not take (forward method,
+    N < 3, more than RT_N_SCAN_MAX lengths), no seed or more than RT_N_SEED_MAX, or an entry that is not a Seed is a
+    ValueError raised here, before any native call."""
+    return _seed_scan_loop("seed_suffix_scan_loop", 1, "the suffix scan takes the backward method (1) only", problem, seeds, rays, device)
+
+
+def _seed_scan_loop(who: str, method: int, method_text: str, problem: Problem, seeds, rays, device: int) -> dict:
+    """seed_length_scan_loop (method 2) and seed_suffix_scan_loop (method 1): the checks, the call and the rows."""
+    _scan_takes(who, problem, method, method_text)
+    seeds = _taken_seeds(who, seeds)
     L = problem.N - 1
-    out = _host_loop("rt_hip_seed_length_scan_loop", problem, rays, device, (len(seeds), L), seeds)
+    out = _host_loop("rt_hip_" + who, problem, rays, device, (len(seeds), L), seeds)
     return dict(records=[_curve(out, L, s) for s in range(len(seeds))], **_tail(out))
 
 

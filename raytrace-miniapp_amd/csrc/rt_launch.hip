@@ -22,6 +22,8 @@
 #include "rt_step_scan_ase_seeds.hip" // ... with the length scan on: that whole record at every length from one forward march
 #include "rt_step_rscan_ase_seeds.hip" // ... with the suffix scan on: that whole record of the last n lengths from one backward march
 
+#include "rt_step_rscan_seeds.hip" // the suffix scan of a seeded plan with the seeds of the scan: one record per (seed, run of the last n)
+
 #include "rt_runtime.h"
 #include "rt_run_shape.h" // what a run looks like: the pure decision (facts + tuning -> shape) this file enqueues
 
@@ -389,11 +391,11 @@ int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kin
         rc = fill_set(a.set, p, f.n_seed, k);
         return rc != RT_OK ? rc : launch(p, k.suffix ? rt::rt_step_rscan_ase_seeds_kernel : rt::rt_step_scan_ase_seeds_kernel, s.grid, block, s.lds, stream, a);
     }
-    if (kind == PASS_SCAN_SEEDS) { // a seeded plan (gain-only): one record per (seed, length)
+    if (kind == PASS_SCAN_SEEDS || kind == PASS_RSCAN_SEEDS) { // a seeded plan (gain-only): one record per (seed, length), or per (seed, run of the last n)
         rt::ScanSeedsKArg a = records_args<rt::ScanSeedsKArg>(fa, k);
         fill_scan(a.scan, p);
         rc = fill_set(a.set, p, f.n_seed, k);
-        return rc != RT_OK ? rc : launch(p, rt::rt_step_scan_seeds_kernel, s.grid, block, s.lds, stream, a);
+        return rc != RT_OK ? rc : launch(p, k.suffix ? rt::rt_step_rscan_seeds_kernel : rt::rt_step_scan_seeds_kernel, s.grid, block, s.lds, stream, a);
     }
     if (kind == PASS_ASE_SEEDS) { // an emission plan: block 0 the ASE record, block 1 + s the record of seed s
         rt::AseSeedsKArg a = records_args<rt::AseSeedsKArg>(fa, k);

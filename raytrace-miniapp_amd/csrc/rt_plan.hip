@@ -1399,14 +1399,16 @@ constexpr unsigned kind_bit(RecordKind k) { return 1u << k; }
 static const Accessor ACC_SEED        = { kind_bit(REC_SEEDS), ": the last run was not a step run with a seed set", ": no such seed in the set of the last run" };
 // (on a scan with scan seeds a length alone means seed 0's curve, on a scan with ASE seeds the ASE curve; on a suffix scan n
 // is the number of lengths of the run of the LAST n)
-static const Accessor ACC_LENGTH      = { kind_bit(REC_SCAN) | kind_bit(REC_SCAN_SEEDS) | kind_bit(REC_SCAN_ASE_SEEDS) | kind_bit(REC_RSCAN) | kind_bit(REC_RSCAN_ASE_SEEDS),
+static const Accessor ACC_LENGTH      = { kind_bit(REC_SCAN) | kind_bit(REC_SCAN_SEEDS) | kind_bit(REC_SCAN_ASE_SEEDS) | kind_bit(REC_RSCAN) | kind_bit(REC_RSCAN_ASE_SEEDS) |
+                                              kind_bit(REC_RSCAN_SEEDS),
                                           ": the last run was not a step run with the length scan on", "" };
 static const Accessor ACC_FULL        = { kind_bit(REC_ASE_SEEDS), ": the last run was not a step run of an emission plan with ASE seeds",
                                           ": r must be 0 (ASE) .. n_seed of the last run" };
 // (of a length scan or of a suffix scan, as rt_hip_plan_fetch_length_step serves both scans)
 static const Accessor ACC_FULL_LENGTH = { kind_bit(REC_SCAN_ASE_SEEDS) | kind_bit(REC_RSCAN_ASE_SEEDS), ": the last run was not a step run of a length scan with ASE seeds",
                                           ": r must be 0 (ASE) .. n_seed of the last run" };
-static const Accessor ACC_SEED_LENGTH = { kind_bit(REC_SCAN_SEEDS), ": the last run was not a step run of a length scan with scan seeds",
+// (of a length scan or of a suffix scan, likewise)
+static const Accessor ACC_SEED_LENGTH = { kind_bit(REC_SCAN_SEEDS) | kind_bit(REC_RSCAN_SEEDS), ": the last run was not a step run of a length scan with scan seeds",
                                           ": no such seed among the scan seeds of the last run" };
 
 // The block of the last run that (s, n) means to the accessor `who`, or -1 behind its refusal: the kind, the first index,
@@ -1616,6 +1618,7 @@ struct SeedsEntry {
     ScanNeed scan;
     const char *with_seed, *no_E0; // the wrong flavour: a seed where none may be (or none where one must be), tables without E0
     const char *noun, *runs;       // the seeds, as the refusals by the plan's scans and output modes name them
+    const char *forward = nullptr; // (the seeds of a suffix scan) the installer a forward plan takes in this one's place
 };
 static const SeedsEntry SET_SEEDS = { "rt_hip_plan_set_seeds", false, SCANS_OFF, ": the plan was created without a seed (a set needs the gain-only mode)", nullptr,
                                       "a seed set", "a set runs" };
@@ -1631,9 +1634,14 @@ static const SeedsEntry SET_SCAN_ASE_SEEDS = { "rt_hip_plan_set_scan_ase_seeds",
 // ... of a suffix scan, on a BACKWARD emission plan: the plan's method says which scan the seeds of a scan belong to
 static const SeedsEntry SET_SUFFIX_ASE_SEEDS = { "rt_hip_plan_set_suffix_ase_seeds", true, SUFFIX_SCAN_ON,
                                                  ": the plan was created with a seed (the ASE record needs an emission plan)",
-                                                 ": not an emission plan (tables without E0)", nullptr, nullptr };
+                                                 ": not an emission plan (tables without E0)", nullptr, nullptr, "rt_hip_plan_set_scan_ase_seeds" };
+// The seeds of a suffix scan on a SEEDED backward plan: what rt_hip_plan_set_scan_seeds is to the length scan (gain-only, the
+// creation seed not among them, the plan's scale); REC_RSCAN_SEEDS, rt_step_rscan_seeds.hip
+static const SeedsEntry SET_SUFFIX_SEEDS = { "rt_hip_plan_set_suffix_seeds", false, SUFFIX_SCAN_ON,
+                                             ": the plan was created without a seed (an emission plan takes rt_hip_plan_set_suffix_ase_seeds)", nullptr,
+                                             nullptr, nullptr, "rt_hip_plan_set_scan_seeds" };
 
-// The five rt_hip_plan_set_*seeds: the plan's flavour, its scans, the seeds' tables (before the scans where the scans must be
+// The six rt_hip_plan_set_*seeds: the plan's flavour, its scans, the seeds' tables (before the scans where the scans must be
 // off, as each entry point has always ordered them), the install, the scales.
 static int seeds_set(rt_hip_plan *p, const SeedsEntry &e, int n_seed, const rt_seed *seeds, const double *scales)
 {
@@ -1641,7 +1649,7 @@ static int seeds_set(rt_hip_plan *p, const SeedsEntry &e, int n_seed, const rt_s
     if (!p)
         return fail(": NULL plan");
     if (e.scan == SUFFIX_SCAN_ON && p->P.method != 1)
-        return fail(": the plan's method is not 1 (a forward plan takes rt_hip_plan_set_scan_ase_seeds)");
+        return fail(std::string(": the plan's method is not 1 (a forward plan takes ") + e.forward + ")");
     if (e.emission == (p->P.has_seed != 0))
         return fail(e.with_seed);
     if (e.emission && !p->P.use_emis)
@@ -1663,7 +1671,7 @@ static int seeds_set(rt_hip_plan *p, const SeedsEntry &e, int n_seed, const rt_s
         if (!p->scan_on)
             return fail(e.scan == LENGTH_SCAN_ON ? ": the length scan is off (rt_hip_plan_enable_length_scan first)"
                                                  : ": the suffix scan is off (rt_hip_plan_enable_suffix_scan first)");
-        if (e.scan == SUFFIX_SCAN_ON && n_seed > RT_N_SEED_MAX)
+        if (e.scan == SUFFIX_SCAN_ON && e.emission && n_seed > RT_N_SEED_MAX)
             return fail(": more than RT_N_SEED_MAX seeds");
         if (e.scan == SUFFIX_SCAN_ON && p->n_seed > 0) // (no call leads here: every installer of a set or of ASE seeds refuses a plan whose suffix scan is on)
             return fail(": the plan holds ASE seeds or a seed set (they and a suffix scan exclude each other)");
@@ -1695,6 +1703,8 @@ int rt_hip_plan_set_suffix_ase_seeds(rt_hip_plan *p, int n_seed, const rt_seed *
 {
     return seeds_set(p, SET_SUFFIX_ASE_SEEDS, n_seed, seeds, scales);
 }
+
+int rt_hip_plan_set_suffix_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds) { return seeds_set(p, SET_SUFFIX_SEEDS, n_seed, seeds, nullptr); }
 
 int rt_hip_plan_kernel_ms(rt_hip_plan *p, float *ms)
 {
@@ -1830,7 +1840,7 @@ static int loop_records(rt_hip_plan *p, const LoopRecords &o)
     if (rc == RT_OK && o.scan != SCANS_OFF)
         rc = scan_switch(p, o.scan == SUFFIX_SCAN_ON ? "rt_hip_plan_enable_suffix_scan" : "rt_hip_plan_enable_length_scan", o.scan == SUFFIX_SCAN_ON, 1);
     if (rc == RT_OK && o.n_seed > 0)
-        rc = seeds_set(p, !o.ase ? SET_SCAN_SEEDS : o.scan == SUFFIX_SCAN_ON ? SET_SUFFIX_ASE_SEEDS : o.scan == LENGTH_SCAN_ON ? SET_SCAN_ASE_SEEDS : SET_ASE_SEEDS,
+        rc = seeds_set(p, !o.ase ? (o.scan == SUFFIX_SCAN_ON ? SET_SUFFIX_SEEDS : SET_SCAN_SEEDS) : o.scan == SUFFIX_SCAN_ON ? SET_SUFFIX_ASE_SEEDS : o.scan == LENGTH_SCAN_ON ? SET_SCAN_ASE_SEEDS : SET_ASE_SEEDS,
                        o.n_seed, o.seeds, o.scales);
     return rc;
 }
@@ -1980,6 +1990,14 @@ int rt_hip_seed_length_scan_loop(int device, int N, const rt_beam *beam, const r
                                  double *I_ang, unsigned int *failure_codes, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats)
 {
     return rows_loop("rt_hip_seed_length_scan_loop", LoopRecords{ LENGTH_SCAN_ON, n_seed, seeds }, true, device, N, beam, gain, seed, method, rays, n_rays,
+                     scale, E_v, nf, I_ang, failure_codes, failed_rays, max_failed, n_failed, stats);
+}
+
+int rt_hip_seed_suffix_scan_loop(int device, int N, const rt_beam *beam, const rt_gain *gain, const rt_seed *seed, int method,
+                                 const rt_ray *rays, size_t n_rays, double scale, int n_seed, const rt_seed *seeds, double *E_v, double *nf,
+                                 double *I_ang, unsigned int *failure_codes, rt_ray *failed_rays, int max_failed, int *n_failed, rt_stats *stats)
+{
+    return rows_loop("rt_hip_seed_suffix_scan_loop", LoopRecords{ SUFFIX_SCAN_ON, n_seed, seeds }, true, device, N, beam, gain, seed, method, rays, n_rays,
                      scale, E_v, nf, I_ang, failure_codes, failed_rays, max_failed, n_failed, stats);
 }
 

@@ -14,6 +14,7 @@
 //   REC_SCAN_ASE_SEEDS   (1 + n_seed) L  (r, n) -> r L + n - 2; n alone: the ASE curve  L - 1 (ASE, all N lengths)
 //   REC_RSCAN            L               the LAST n lengths, n = 2 .. L + 1 -> n - 2    L - 1 (all N lengths)
 //   REC_RSCAN_ASE_SEEDS  (1 + n_seed) L  (r, n) -> r L + n - 2, the LAST n lengths         L - 1 (ASE, all N lengths)
+//   REC_RSCAN_SEEDS      n_seed L        (s, n) -> s L + n - 2, the LAST n lengths; n alone: seed 0  L - 1 (seed 0, all N lengths)
 //
 // The table is code twice below: record_kinds[] holds what tells the kinds apart, one row each, and RecordSet derives every
 // column from the row; the static_asserts at the end restate the table at n_seed = 2, L = 3, in range and out of it.  A new
@@ -29,14 +30,16 @@ namespace rtr {
 // (PASS_ASE_SEEDS: an emission plan with ASE seeds, rt_step_ase_seeds.hip -- use_emis with n_seed > 0 and no scan is that and
 // nothing else; PASS_SCAN_ASE_SEEDS: the same with the length scan on, rt_step_scan_ase_seeds.hip; PASS_RSCAN: the suffix
 // scan of a backward plan, rt_step_rscan.hip -- scan_on with method 1 and no seeds is that and nothing else;
-// PASS_RSCAN_ASE_SEEDS: the suffix scan of an emission plan with ASE seeds, rt_step_rscan_ase_seeds.hip)
+// PASS_RSCAN_ASE_SEEDS: the suffix scan of an emission plan with ASE seeds, rt_step_rscan_ase_seeds.hip; PASS_RSCAN_SEEDS:
+// the suffix scan of a seeded backward plan with the seeds of the scan, rt_step_rscan_seeds.hip)
 enum PassKind {
     PASS_FREQ = 0, PASS_SPEC = 1, PASS_STEP = 2, PASS_SEEDS = 3, PASS_PATH = 4, PASS_SCAN = 5, PASS_SCAN_SEEDS = 6, PASS_ASE_SEEDS = 7,
-    PASS_SCAN_ASE_SEEDS = 8, PASS_RSCAN = 9, PASS_RSCAN_ASE_SEEDS = 10
+    PASS_SCAN_ASE_SEEDS = 8, PASS_RSCAN = 9, PASS_RSCAN_ASE_SEEDS = 10, PASS_RSCAN_SEEDS = 11
 };
 
-enum RecordKind { REC_NONE = 0, REC_SEEDS, REC_ASE_SEEDS, REC_SCAN, REC_SCAN_SEEDS, REC_SCAN_ASE_SEEDS, REC_RSCAN, REC_RSCAN_ASE_SEEDS };
-constexpr int REC_N_KINDS = REC_RSCAN_ASE_SEEDS + 1;
+enum RecordKind { REC_NONE = 0, REC_SEEDS, REC_ASE_SEEDS, REC_SCAN, REC_SCAN_SEEDS, REC_SCAN_ASE_SEEDS, REC_RSCAN, REC_RSCAN_ASE_SEEDS,
+                  REC_RSCAN_SEEDS };
+constexpr int REC_N_KINDS = REC_RSCAN_SEEDS + 1;
 
 // What tells the kinds apart, one row per kind; everything RecordSet says of a kind is derived from its row.
 struct RecordKindRow {
@@ -60,6 +63,7 @@ constexpr RecordKindRow record_kinds[REC_N_KINDS] = {
     { true, true, true, false, PASS_SCAN_ASE_SEEDS, 16, "a length scan with ASE seeds", "per record and length" }, // REC_SCAN_ASE_SEEDS
     { true, false, false, true, PASS_RSCAN, 4, "a suffix scan", "per length" },                                 // REC_RSCAN
     { true, true, true, true, PASS_RSCAN_ASE_SEEDS, 16, "a suffix scan with ASE seeds", "per record and length" }, // REC_RSCAN_ASE_SEEDS
+    { true, false, true, true, PASS_RSCAN_SEEDS, 8, "a suffix scan with scan seeds", "per seed and length" },   // REC_RSCAN_SEEDS
 };
 
 struct RecordSet {
@@ -121,6 +125,7 @@ static_assert(blocks(REC_SCAN_ASE_SEEDS, 3, true) && is(REC_SCAN_ASE_SEEDS, 9, 2
 static_assert(blocks(REC_RSCAN, 1, true) && is(REC_RSCAN, 3, 2, true, false, PASS_RSCAN, 4), "REC_RSCAN: n -> n - 2");
 static_assert(blocks(REC_RSCAN_ASE_SEEDS, 3, true) && is(REC_RSCAN_ASE_SEEDS, 9, 2, true, true, PASS_RSCAN_ASE_SEEDS, 16),
               "REC_RSCAN_ASE_SEEDS: (r, n) -> r L + n - 2");
+static_assert(blocks(REC_RSCAN_SEEDS, 2, true) && is(REC_RSCAN_SEEDS, 6, 2, true, false, PASS_RSCAN_SEEDS, 8), "REC_RSCAN_SEEDS: (s, n) -> s L + n - 2");
 } // namespace records_check
 
 } // namespace rtr

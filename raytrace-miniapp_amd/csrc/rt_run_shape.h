@@ -77,7 +77,7 @@ struct Tuning {
     unsigned freq_wg_waves;
     unsigned freq_min_rows; // RT_HIP_FREQ_MIN_ROWS: seeded tiles hold ~7 pixels
     unsigned freq_wgs;      // RT_HIP_FREQ_WGS 1 ... 16 (knob; tuning override)
-    // RT_HIP_STEP_SERIAL=1: every step pass (step, seed set, length scan, scan seeds, ASE seeds, scan ASE seeds, suffix ASE seeds) as ONE work-group of ONE wave.  The
+    // RT_HIP_STEP_SERIAL=1: every step pass (step, seed set, length scan, scan seeds, ASE seeds, scan ASE seeds, suffix ASE seeds, suffix seeds) as ONE work-group of ONE wave.  The
     // passes add with f64 atomics in the order in which waves arrive, so two runs of the same rays differ in the last bits;
     // one wave takes the tiles in a fixed order and its sums are the same doubles run after run -- for comparisons bit for
     // bit (tests), at the pace of one wave.  The one-launch step run is not affected.
@@ -370,7 +370,8 @@ inline RecordSet record_set(const RunFacts &f)
         return r;
     // (use_emis with n_seed > 0: ASE seeds, of the scan where it is on -- no other plan presents that pair)
     // (... and of the suffix scan: rscan() with use_emis and n_seed > 0, the march the plain suffix-scan march)
-    r.kind   = f.rscan() ? (f.use_emis && f.n_seed > 0 ? REC_RSCAN_ASE_SEEDS : REC_RSCAN) : f.scan_on ? (f.n_seed > 0 ? (f.use_emis ? REC_SCAN_ASE_SEEDS : REC_SCAN_SEEDS) : REC_SCAN) : f.n_seed > 0 ? (f.use_emis ? REC_ASE_SEEDS : REC_SEEDS) : REC_NONE;
+    // (... or, on a seeded plan, the seeds of the suffix scan: rscan() without use_emis and n_seed > 0, the same march)
+    r.kind   = f.rscan() ? (f.n_seed > 0 ? (f.use_emis ? REC_RSCAN_ASE_SEEDS : REC_RSCAN_SEEDS) : REC_RSCAN) : f.scan_on ? (f.n_seed > 0 ? (f.use_emis ? REC_SCAN_ASE_SEEDS : REC_SCAN_SEEDS) : REC_SCAN) : f.n_seed > 0 ? (f.use_emis ? REC_ASE_SEEDS : REC_SEEDS) : REC_NONE;
     r.n_seed = f.n_seed;
     r.L      = f.scan_on ? f.L : 0;
     return r;
@@ -441,14 +442,15 @@ inline PassShape pass_shape(PassKind kind, const RunFacts &f, const Tuning &t)
         s.wg_waves = rt::FREQ_WG_WAVES;
         // (a seed set keeps one I_ang histogram and one E_v accumulator per seed, a length scan one of each per length, a scan
         // with scan seeds one of each per (seed, length), an emission plan with ASE seeds one of each for ASE and per seed -- with
-        // the scan on, of those per length; a suffix scan one of each per length, with ASE seeds one per (record, length))
+        // the scan on, of those per length; a suffix scan one of each per length, with ASE seeds one per (record, length), with
+        // scan seeds one per (seed, length))
         const int n_rec      = kind == PASS_STEP || kind == PASS_SPEC ? 1 : record_set(f).n_rec();
         const int ang_stride = kind == PASS_STEP ? rt::step_ang_stride((int) f.n_iang) : rt::seeds_ang_stride((int) f.n_iang);
         auto step_lds        = [&](bool in_lds) { return rt::step_lds_doubles(in_lds, ang_stride, f.Kp, s.wg_waves, n_rec) * sizeof(double); };
         // (spectra: the staging rows of 16 waves and the exponent tables take 148 KB of LDS)
         s.lds = kind == PASS_SPEC ? ((size_t) 2 * rt::EXP_TAB + (size_t) s.wg_waves * rt::WAVE * rt::XS_ROW) * sizeof(double) : step_lds(s.in_lds);
         if ((kind == PASS_SEEDS || kind == PASS_SCAN || kind == PASS_SCAN_SEEDS || kind == PASS_ASE_SEEDS || kind == PASS_SCAN_ASE_SEEDS ||
-             kind == PASS_RSCAN || kind == PASS_RSCAN_ASE_SEEDS) && s.in_lds &&
+             kind == PASS_RSCAN || kind == PASS_RSCAN_ASE_SEEDS || kind == PASS_RSCAN_SEEDS) && s.in_lds &&
             s.lds > f.lds_limit) { // one histogram per record does not fit: global atomics
             s.in_lds = false;
             s.lds    = step_lds(false);

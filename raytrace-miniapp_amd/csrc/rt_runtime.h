@@ -100,7 +100,8 @@ struct rt_hip_plan {
     // is on: n_scan_seed, n_seed stays 0) or as ASE seeds (rt_hip_plan_set_ase_seeds, an EMISSION plan: n_seed with
     // P.use_emis, the one case of use_emis with n_seed > 0; ase_scale[s] is the scale of seed s) or as the ASE seeds of a
     // scan (rt_hip_plan_set_scan_ase_seeds, an emission plan while the scan is on: n_scan_seed with P.use_emis; on a backward
-    // plan rt_hip_plan_set_suffix_ase_seeds, while the suffix scan is on: the same two fields).  A set and a scan exclude
+    // plan rt_hip_plan_set_suffix_ase_seeds, while the suffix scan is on: the same two fields; on a SEEDED backward plan
+    // rt_hip_plan_set_suffix_seeds, while the suffix scan is on: n_scan_seed without P.use_emis).  A set and a scan exclude
     // each other, so their tables live in the same place: one device block (seedset_arena; seed_set[s] points into it, f[4]
     // padded to Kp) and, on a forward ray grid, per seed what seedtab_dev holds for the creation seed (seedset_tab).
     int n_seed      = 0;
@@ -270,7 +271,8 @@ inline CodeSlot record_code_slot(const RecordSet &R)
     case REC_ASE_SEEDS: return { (unsigned) (offsetof(rt::DevCtl, rec_code) / W), all, 0 };
     case REC_SCAN:
     case REC_RSCAN: return { (unsigned) (offsetof(rt::DevCtl, len_code) / W), all, 0 };
-    case REC_SCAN_SEEDS: return { (unsigned) (offsetof(rt::DevCtl, seed_len_code) / W), (unsigned) R.L, RT_N_SCAN_MAX };
+    case REC_SCAN_SEEDS:
+    case REC_RSCAN_SEEDS: return { (unsigned) (offsetof(rt::DevCtl, seed_len_code) / W), (unsigned) R.L, RT_N_SCAN_MAX };
     case REC_SCAN_ASE_SEEDS:
     case REC_RSCAN_ASE_SEEDS: return { (unsigned) (offsetof(rt::DevCtl, rec_len_code) / W), (unsigned) R.L, RT_N_SCAN_MAX };
     default: return { (unsigned) (offsetof(rt::DevCtl, failure_code) / W), all, 0 }; // (block 0: the run's code)

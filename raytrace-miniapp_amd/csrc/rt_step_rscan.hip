@@ -94,6 +94,28 @@ static __device__ __attribute__((noinline)) double ase_update_call(double Iv, fl
     return ase_update(Iv, gs, es, w, tab);
 }
 
+// scan_seed_factor (rt_step_scan.hip), statement by statement, on a seed that stays in the argument block: every table
+// pointer and dimension is read through the constant address space where it is used, not as a copy of the whole DevSeed
+// held in scalar registers across the four calls (with the copy the kernel kept a stack frame that nothing read).  The
+// kernels that carry the seeds of a suffix scan take it (rt_step_rscan_ase_seeds.hip, rt_step_rscan_seeds.hip).
+__device__ __forceinline__ double rscan_seed_factor(const RT_CONST_AS DevSeed *sd, double x, double y, double a, double b)
+{
+    auto xs  = [&](int d) { return (ConstF64) (unsigned long long) sd->x[d]; };
+    auto fs  = [&](int d) { return reinterpret_cast<const double *>((unsigned long long) sd->f[d]); };
+    double f = 0.0;
+    if (x >= xs(0)[0] && x <= xs(0)[sd->dim[0] - 1] && y >= xs(1)[0] && y <= xs(1)[sd->dim[1] - 1] && a >= xs(2)[0] &&
+        a <= xs(2)[sd->dim[2] - 1] && b >= xs(3)[0] && b <= xs(3)[sd->dim[3] - 1]) {
+        double fx, fy, fa, fb;
+        [[clang::noinline]] fx = pchip_eval(sd->dim[0], reinterpret_cast<const double *>((unsigned long long) sd->x[0]), fs(0), x);
+        [[clang::noinline]] fy = pchip_eval(sd->dim[1], reinterpret_cast<const double *>((unsigned long long) sd->x[1]), fs(1), y);
+        [[clang::noinline]] fa = pchip_eval(sd->dim[2], reinterpret_cast<const double *>((unsigned long long) sd->x[2]), fs(2), a);
+        [[clang::noinline]] fb = pchip_eval(sd->dim[3], reinterpret_cast<const double *>((unsigned long long) sd->x[3]), fs(3), b);
+        f = sd->f0 * fx * fy * fa * fb;
+        f = f < 0.0 ? 0.0 : f;
+    }
+    return f;
+}
+
 template <bool EMIS>
 __device__ __forceinline__ void step_rscan_tile(const FreqHot &H, const unsigned hflags, ColdPtr C, ScanPtr Q, double *lds_iang, double *lds_ev,
                                                 const double *tab, double *xpose, const unsigned tile, const int lane)
