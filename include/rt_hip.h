@@ -271,6 +271,10 @@ typedef struct rt_hip_run_facts {
     int scan_on; /* a length scan (rt_hip_plan_enable_length_scan): the scan march and pass_kind 5, one record per length 1 .. L;
                     with method == 1 the suffix scan (rt_hip_plan_enable_suffix_scan): the backward scan march and pass_kind 9 */
 } rt_hip_run_facts;
+/* spectra_on = 2 stands for length spectra (rt_hip_plan_enable_length_spectra; any other non-zero value: spectra mode): the
+ * scan march of the plan's method and pass_kind 12, with the LDS of the spectra pass.  The struct keeps its layout and still
+ * ends with scan_on: the mode is a value of the fact that names the per-ray spectra, not a member of its own.  (Before length
+ * spectra existed every non-zero spectra_on, 2 included, was spectra mode: a caller that wrote 2 for "on" now gets this.) */
 /* kind: 0 = march and second pass as two kernels, 1 = the image run in one launch, 2 = the step run in one launch.
  * The march (of a one-launch run: its march phase): lds_tab (tables in LDS) ... late_chunks; bounded, mode, opt and
  * lds_tab name its instance, last_march_inst is what rt_hip_plan_last_march_instance would report.  chunk is that of a
@@ -280,7 +284,7 @@ typedef struct rt_hip_run_facts {
  * its grid.  key_s6 / key_emis / key_excl pick the instance of the second pass.
  * pass_*: the second pass this run takes (pass_kind 0 frequency, 1 spectra, 2 step, 3 step of a seed set, 4 path
  * tracer: all zero, 5 step of a length scan, 6 step of a length scan with scan seeds (scan_on, n_seed > 0: one record per
- * seed and length); pass_lds above lds_limit: the run is refused); for a one-launch run the frequency (step) phase of that launch. */
+ * seed and length), 12 length spectra (spectra_on = 2); pass_lds above lds_limit: the run is refused); for a one-launch run the frequency (step) phase of that launch. */
 typedef struct rt_hip_run_shape {
     unsigned size;
     int kind, lds_tab;
@@ -355,6 +359,37 @@ int rt_hip_plan_fetch_path(rt_hip_plan *plan, float *path, int32_t *err);
 int rt_hip_plan_enable_spectra(rt_hip_plan *plan, int on);
 int rt_hip_plan_fetch_spectra(rt_hip_plan *plan, double *Iv, rt_ray *ray2, int32_t *err);
 double *rt_hip_plan_spectra_ptr(rt_hip_plan *plan);
+
+/* Length spectra: RayTrace::calc_ray for every ray of the plan at EVERY plasma length n = 2 .. N, from ONE march.  A mode
+ * of its own beside spectra mode.  With it on a run marches once, with the scan instance of the march (the one a length
+ * scan or a suffix scan takes: rt_hip_plan_last_march_instance carries its bit), and rt_spec_scan_kernel
+ * (raytrace-miniapp_amd/csrc/rt_spec_scan.hip) leaves per ray and n what calc_ray returns on the sub-problem of n lengths
+ * -- gain[0 .. n-1] on a forward plan (method 2), gain[0] and the LAST n - 1 lengths on a backward plan (method 1): the
+ * spectrum Iv [K], the exit ray ray2 and the code err (0, -1, -2, -3; a negative intensity wins over a NaN).  Rows follow
+ * spectra mode: error -1 gives a row of zeros and ray2 = 0, a row that is all zero on the CPU is all zero here, the
+ * spectrum of a -2 / -3 row is not meant to be read.  In gain-only mode and with rt_hip_plan_set_exact_emission every
+ * value is the double a spectra-mode plan of the sub-problem computes; in the default emission mode the two differ as the
+ * records of a scan differ from a step plan's (the choice of the update is taken per sub-segment here).
+ * enable_length_spectra(on != 0): 3 <= N and N - 1 <= RT_N_SCAN_MAX, and none of step mode, spectra mode, the path tracer,
+ *   a length or suffix scan, a seed set, ASE seeds or the seeds of a scan may be on -- each is RT_ERR_ARG with its own
+ *   text; the call settles the last run first.  While the mode is on each of those switches and installers is RT_ERR_ARG.
+ *   on = 0 restores the plan exactly (the boundary states and the rows go back to the pool).  Seeded and emission plans,
+ *   ray lists and ray grids (first / stride included), exact emission, the probe (of the whole run), the timing ring,
+ *   rt_hip_plan_set_step_factor and rt_hip_plan_update_gain / _dev work as in spectra mode; an update keeps the mode.
+ *   rt_hip_plan_set_step_one_launch is accepted and the run keeps two kernels (rt_hip_plan_last_fused is 0,
+ *   rt_hip_plan_kernel_times reports the pass as freq_ms).
+ * rt_hip_plan_run takes (NULL, NULL) in this mode and rt_hip_plan_fetch no image pointers; it reports the OR of the codes
+ *   over all (ray, n), the rays that fail under any n, each once (more than RT_N_FAILED_MAX: the first of them in list
+ *   order), and the counters of the one march.  There is no checking repeat: nothing is deposited.
+ * fetch_length_spectra / length_spectra_ptrs: n = 2 .. N of the last run, anything else is RT_ERR_ARG; Iv [n_rays][K] (row
+ *   stride K), ray2 [n_rays], err [n_rays], any pointer may be NULL.  On the device the rows of all lengths are one
+ *   allocation, length-major (Iv [N-1][n_rays][K], ray2 and err [N-1][n_rays]); the pointers are valid until the next run or
+ *   a change of the ray set.  The allocation is (N-1) n_rays K 8 bytes: a run that cannot have it fails with RT_ERR_NOMEM.
+ * Not built: a chunked host-pointer loop like rt_hip_calc_rays, seed sets per length, the multi-device arms, the C++
+ *   adapter, the one-launch form. */
+int rt_hip_plan_enable_length_spectra(rt_hip_plan *plan, int on);
+int rt_hip_plan_fetch_length_spectra(rt_hip_plan *plan, int n, double *Iv, rt_ray *ray2, int32_t *err);
+int rt_hip_plan_length_spectra_ptrs(rt_hip_plan *plan, int n, double **Iv_dev, rt_ray **ray2_dev, int32_t **err_dev);
 
 /* Host-pointer batched form of RayTrace::calc_ray: n independent calls in one.  rays and ray2 are [n][4] doubles
  * (x, y, a, b) as calc_ray takes and returns them; the coordinates are rounded to float exactly as calc_ray rounds

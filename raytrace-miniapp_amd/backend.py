@@ -91,8 +91,8 @@ class HipLibrary:
 
 
 class _View:  # the CUDA array interface, which torch.as_tensor reads
-    def __init__(self, ptr: int, shape: tuple):
-        self.__cuda_array_interface__ = dict(shape=shape, typestr="<f8", data=(ptr, False), version=2, strides=None)
+    def __init__(self, ptr: int, shape: tuple, typestr: str = "<f8"):
+        self.__cuda_array_interface__ = dict(shape=shape, typestr=typestr, data=(ptr, False), version=2, strides=None)
 
 
 def _view(ptr: int, shape: tuple, device: int):
@@ -162,6 +162,7 @@ class Plan:
     # What the plan has been switched to, as the methods below record it.  Class-level defaults: they hold for a plan of any
     # making (the host tests build one without a device, around __init__).
     _spectra = _step = False    # the output mode (enable_spectra, enable_step)
+    _length_spectra = False     # length spectra are on (enable_length_spectra): a run without image and I_ang, as a spectra run
     _ring = 0                   # runs of the timing ring (set_timing_ring)
     _scan = False               # the length scan or the suffix scan is on (enable_length_scan, enable_suffix_scan)
     _n_seed = 0                 # seeds of the set (set_seeds)
@@ -222,7 +223,7 @@ class Plan:
 
     def fetch(self, want_image: bool = True) -> dict:
         b = self.problem.beam
-        want_image = want_image and not self._spectra  # a spectra run has no image
+        want_image = want_image and not self._spectra and not self._length_spectra  # a spectra run has no image
         want_iang = want_image
         want_image = want_image and not self._step     # ... and a step run has I_ang only
         image = np.empty(b.nx * b.ny * b.nv) if want_image else None
@@ -296,6 +297,52 @@ class Plan:
         if not ptr or not self.n_rays:
             return torch.empty((0, self.problem.beam.nv), dtype=torch.float64, device=torch.device("cuda", self.device))
         return _view(ptr, (self.n_rays, self.problem.beam.nv), self.device)
+
+    def enable_length_spectra(self, on: bool = True) -> "Plan":
+        """Length spectra (include/rt_hip.h, rt_hip_plan_enable_length_spectra): a run marches once and leaves Iv, ray2
+        and err per ray at EVERY plasma length n = 2 .. N -- calc_ray on prefix_lengths(n) of a forward plan, on
+        suffix_lengths(n) of a backward one.  A mode of its own: not together with spectra, step, path, a scan or seeds."""
+        on = _on_arg("enable_length_spectra", on)
+        self.hl.check(self.hl.lib.rt_hip_plan_enable_length_spectra(self._h, on), "rt_hip_plan_enable_length_spectra")
+        self._length_spectra = bool(on)   # (fetch() reads it; spectra mode keeps its own flag: switching this off on a plan in spectra mode changes nothing)
+        return self
+
+    def fetch_length_spectra(self) -> list:
+        """[dict(n, Iv [n_rays][K], ray2 (RAY_DTYPE), err [n_rays] int32)] for n = 2 .. N of the last length-spectra run."""
+        nr, K = self.n_rays, self.problem.beam.nv
+        out = []
+        for n in range(2, self.problem.N + 1):
+            Iv = np.empty((nr, K))
+            ray2 = np.zeros(nr, cabi.RAY_DTYPE)
+            err = np.zeros(nr, np.int32)
+            self.hl.check(self.hl.lib.rt_hip_plan_fetch_length_spectra(self._h, n, cabi._dp(Iv), cabi.rays_ptr(ray2),
+                                                                       err.ctypes.data_as(C.POINTER(C.c_int32))),
+                          "rt_hip_plan_fetch_length_spectra")
+            out.append(dict(n=n, Iv=Iv, ray2=ray2, err=err))
+        return out
+
+    def length_spectra_ptrs(self, n: int) -> tuple:
+        """Device pointers (Iv, ray2, err) of the rows of length n of the last length-spectra run."""
+        iv, r2, er = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self.hl.check(self.hl.lib.rt_hip_plan_length_spectra_ptrs(self._h, int(n), C.byref(iv), C.byref(r2), C.byref(er)),
+                      "rt_hip_plan_length_spectra_ptrs")
+        return int(iv.value or 0), int(r2.value or 0), int(er.value or 0)
+
+    def length_spectra_tensors(self) -> dict:
+        """torch views of the last length-spectra run, length-major and without a copy: Iv [N-1][n_rays][K] float64, ray2
+        [N-1][n_rays][4] float32 (x, y, a, b), err [N-1][n_rays] int32; block n - 2 is length n.  Valid until the plan's
+        next run or a change of its ray set."""
+        import torch
+
+        L, nr, K = self.problem.N - 1, self.n_rays, self.problem.beam.nv
+        dev = torch.device("cuda", self.device)
+        if not nr:
+            return dict(Iv=torch.empty((L, 0, K), dtype=torch.float64, device=dev), ray2=torch.empty((L, 0, 4), dtype=torch.float32, device=dev),
+                        err=torch.empty((L, 0), dtype=torch.int32, device=dev))
+        iv, r2, er = self.length_spectra_ptrs(2)   # (block 0: the arrays are length-major)
+
+        return dict(Iv=_view(iv, (L, nr, K), self.device), ray2=torch.as_tensor(_View(r2, (L, nr, 4), "<f4"), device=dev),
+                    err=torch.as_tensor(_View(er, (L, nr), "<i4"), device=dev))
 
     def enable_step(self, on: bool = True) -> "Plan":
         """Step mode (include/rt_hip.h): a run produces E_v, nf and I_ang -- the image cube reduced on the way, never
@@ -1093,6 +1140,28 @@ def calc_rays(problem: Problem, rays, method: int | None = None, device: int = 0
     hl.check(rc, "rt_hip_calc_rays")
     return dict(Iv=Iv, ray2=cabi.rays_from_array(ray2), err=err,
                 stats={k: getattr(st, k) for k, _ in cabi.RtStats._fields_})
+
+
+def calc_rays_lengths(problem: Problem, rays, exact: bool = False, device: int = 0) -> dict:
+    """RayTrace::calc_ray for every ray at EVERY plasma length n = 2 .. N, from one march: one call over a plan in length
+    spectra mode (Plan.enable_length_spectra).  The problem's method decides the sub-problems: prefix_lengths(n) with the
+    forward method, suffix_lengths(n) with the backward one.  `rays`: RAY_DTYPE records or an [n][4] float64 array of
+    (x, y, a, b), rounded to float as calc_ray rounds its arguments; `exact`: Plan.set_exact_emission.  Device memory is
+    (N - 1) n K 8 bytes: there is no chunking as in calc_rays.
+
+    Returns dict(lengths=[dict(n, Iv [n_rays][K], ray2 (RAY_DTYPE), err [n_rays] int32)], failure_code, failed_rays, stats)."""
+    if problem.N < 3 or problem.N - 1 > cabi.RT_N_SCAN_MAX:
+        raise ValueError(f"calc_rays_lengths: N = {problem.N}; length spectra take 3 <= N <= RT_N_SCAN_MAX + 1 = {cabi.RT_N_SCAN_MAX + 1}")
+    rays = np.asarray(rays)
+    if rays.dtype != cabi.RAY_DTYPE:
+        rays = cabi.rays_from_array(np.asarray(rays, np.float64).reshape(-1, 4))
+    with Plan(problem, device=device) as plan:
+        plan.set_rays(rays)
+        if exact:
+            plan.set_exact_emission(True)
+        plan.enable_length_spectra(True).run()
+        out = plan.fetch(want_image=False)
+        return dict(lengths=plan.fetch_length_spectra(), failure_code=out["failure_code"], failed_rays=out["failed_rays"], stats=out["stats"])
 
 
 def calc_ray(problem: Problem, ray, method: int | None = None, device: int = 0):

@@ -437,6 +437,13 @@ def declare_hip_api(lib: C.CDLL) -> None:
         lib.rt_hip_plan_set_suffix_seeds.restype = C.c_int
         lib.rt_hip_seed_suffix_scan_loop.argtypes = list(lib.rt_hip_seed_length_scan_loop.argtypes)   # (row (s, n - 2): the last n lengths)
         lib.rt_hip_seed_suffix_scan_loop.restype = C.c_int
+    if hasattr(lib, "rt_hip_plan_enable_length_spectra"):   # (likewise)
+        lib.rt_hip_plan_enable_length_spectra.argtypes = [vp, C.c_int]
+        lib.rt_hip_plan_enable_length_spectra.restype = C.c_int
+        lib.rt_hip_plan_fetch_length_spectra.argtypes = [vp, C.c_int, c_double_p, P(RtRay), P(C.c_int32)]
+        lib.rt_hip_plan_fetch_length_spectra.restype = C.c_int
+        lib.rt_hip_plan_length_spectra_ptrs.argtypes = [vp, C.c_int, P(vp), P(vp), P(vp)]
+        lib.rt_hip_plan_length_spectra_ptrs.restype = C.c_int
     if hasattr(lib, "rt_hip_plan_history_create"):   # (likewise)
         up, bp = P(C.c_uint), P(C.c_ubyte)
         lib.rt_hip_plan_history_create.argtypes = [vp, C.c_int]
@@ -482,6 +489,7 @@ HIP_API_SYMBOLS = [
     "rt_hip_full_length_scan_loop",
     "rt_hip_plan_set_suffix_ase_seeds", "rt_hip_full_suffix_scan_loop",
     "rt_hip_plan_set_suffix_seeds", "rt_hip_seed_suffix_scan_loop",
+    "rt_hip_plan_enable_length_spectra", "rt_hip_plan_fetch_length_spectra", "rt_hip_plan_length_spectra_ptrs",
     "rt_hip_plan_set_step_one_launch", "rt_hip_debug_run_shape",
     "rt_hip_plan_history_create", "rt_hip_plan_history_append", "rt_hip_plan_history_ptrs", "rt_hip_plan_history_sum_ptrs",
     "rt_hip_plan_history_fetch", "rt_hip_plan_history_fetch_sum", "rt_hip_plan_history_info", "rt_hip_debug_history_layout",

@@ -23,6 +23,7 @@
 #include "rt_step_rscan_ase_seeds.hip" // ... with the suffix scan on: that whole record of the last n lengths from one backward march
 
 #include "rt_step_rscan_seeds.hip" // the suffix scan of a seeded plan with the seeds of the scan: one record per (seed, run of the last n)
+#include "rt_spec_scan.hip" // length spectra: per-ray spectra, exit rays and codes at every length from one scan march
 
 #include "rt_runtime.h"
 #include "rt_run_shape.h" // what a run looks like: the pure decision (facts + tuning -> shape) this file enqueues
@@ -152,6 +153,11 @@ void (*seeds_kernel(bool s6))(const rt::SeedsKArg) { return s6 ? rt::rt_step_see
 void (*ase_seeds_kernel(bool s6))(const rt::AseSeedsKArg) { return s6 ? rt::rt_step_ase_seeds_kernel<6> : rt::rt_step_ase_seeds_kernel<0>; }
 void (*scan_kernel(bool emis))(const rt::ScanKArg) { return emis ? rt::rt_step_scan_kernel<true> : rt::rt_step_scan_kernel<false>; }
 void (*rscan_kernel(bool emis))(const rt::ScanKArg) { return emis ? rt::rt_step_rscan_kernel<true> : rt::rt_step_rscan_kernel<false>; }
+void (*spec_scan_kernel(bool emis, bool backward))(const rt::SpecScanKArg)
+{
+    return emis ? (backward ? rt::rt_spec_scan_kernel<true, true> : rt::rt_spec_scan_kernel<true, false>)
+                : (backward ? rt::rt_spec_scan_kernel<false, true> : rt::rt_spec_scan_kernel<false, false>);
+}
 
 // what a launch of the frequency pass covers: tiles [tile_begin, tile_end) on tile counter freq_id (a run is one launch
 // over all tiles; the range exists for experiments that split it), and the marks of the checking repeat (DevParams::safe)
@@ -243,6 +249,7 @@ RunFacts run_facts(const rt_hip_plan *p)
     f.ntest_proven    = p->ntest_proven;
     f.gv_has_nan      = p->gv_has_nan;
     f.scan_on         = p->scan_on && p->step_on;
+    f.length_spectra_on = p->lspec_on;
     return f;
 }
 
@@ -348,6 +355,8 @@ int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kin
     // (what of a one-work-group-per-CU pass does not fit, by kind; the frequency kernel's message, below, carries figures)
     if (s.lds > f.lds_limit && kind == PASS_SPEC)
         return fail_arg("spectra kernel: the staging rows do not fit into the LDS of this device");
+    if (s.lds > f.lds_limit && kind == PASS_SPEC_SCAN)
+        return fail_arg("length spectra kernel: the staging rows do not fit into the LDS of this device");
     if (s.lds > f.lds_limit && kind == PASS_STEP)
         return fail_arg("step kernel: the E_v accumulator (nv doubles) does not fit into the LDS of this device");
     if (s.lds > f.lds_limit && kind != PASS_FREQ && kind != PASS_PATH)
@@ -369,6 +378,16 @@ int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kin
         a.hot.iang  = nullptr;
         a.out       = p->spec[p->spec_sel];
         return launch(p, spec_kernel(f.s6(), f.use_emis), s.grid, block, s.lds, stream, a);
+    }
+    if (kind == PASS_SPEC_SCAN) { // length spectra: the rows of every length, from the boundary states of the scan march
+        if (!p->lspec.Iv || !p->scan_bnd)
+            return fail_arg("length spectra kernel: the outputs or the boundary states of this run were not allocated");
+        if (f.L < 2 || f.L > RT_N_SCAN_MAX)
+            return fail_arg("length spectra kernel: not 2 .. RT_N_SCAN_MAX lengths");
+        rt::SpecScanKArg a = pass_args<rt::SpecScanKArg>(fa);
+        a.hot.iang = nullptr;
+        a.scan     = rt::SpecScanArg{ p->lspec, p->scan_bnd };
+        return launch(p, spec_scan_kernel(f.use_emis, f.method == 1), s.grid, block, s.lds, stream, a);
     }
     if (kind == PASS_STEP) {
         rt::StepKArg a = pass_args<rt::StepKArg>(fa);
@@ -576,7 +595,7 @@ static int ensure_buffers(rt_hip_plan *p, const RunShape &s, hipStream_t stream)
         p->rec_bytes = need;
     }
     p->P.rec = p->rec;
-    if (p->scan_on && p->step_on) { // a length scan: the boundary states of the march, from the plan's pool while the scan is on
+    if ((p->scan_on && p->step_on) || p->lspec_on) { // a length scan or length spectra: the boundary states of the march, from the plan's pool while the mode is on
         const size_t bnd = rt::scan_bnd_bytes(p->n_rays, p->P.L);
         if (bnd > p->scan_bnd_bytes || !p->scan_bnd) {
             plan_quiesce(p);
@@ -619,6 +638,31 @@ static int ensure_buffers(rt_hip_plan *p, const RunShape &s, hipStream_t stream)
             o.err  = reinterpret_cast<int32_t *>(b + iv_bytes + align_up(n * sizeof(rt_ray) + 16, 256));
             p->spec_rays[p->spec_sel] = n;
         }
+    }
+    if (p->lspec_on) {
+        // Iv [L][n][K] | ray2 [L][n] | err [L][n] in one allocation from the pool, kept while it is large enough (no zeroing:
+        // the kernel writes every element); a run that cannot have it fails with RT_ERR_NOMEM
+        const size_t n = (size_t) p->n_rays, Lr = (size_t) p->P.L;
+        const size_t iv_bytes = align_up(Lr * n * (size_t) p->P.K * sizeof(double) + 16, 256), r2_bytes = align_up(Lr * n * sizeof(rt_ray) + 16, 256);
+        const size_t need_ls  = iv_bytes + r2_bytes + Lr * n * sizeof(int32_t) + 16;
+        if (need_ls > p->lspec_bytes || !p->lspec_dev) {
+            plan_quiesce(p);
+            pool_free(p->device, p->lspec_dev);
+            p->lspec_dev   = nullptr;
+            p->lspec_bytes = 0;
+            p->lspec       = {};
+            const hipError_t e = pool_alloc(p->device, (void **) &p->lspec_dev, need_ls);
+            if (e == hipErrorOutOfMemory) {
+                (void) hipGetLastError();
+                fail_arg("length spectra: the rows of every length (L n K 8 bytes) do not fit into device memory");
+                return RT_ERR_NOMEM;
+            }
+            HIP_TRY(e);
+            p->lspec_bytes = need_ls;
+        }
+        p->lspec.Iv   = reinterpret_cast<double *>(p->lspec_dev);
+        p->lspec.ray2 = reinterpret_cast<rt_ray *>(p->lspec_dev + iv_bytes);
+        p->lspec.err  = reinterpret_cast<int32_t *>(p->lspec_dev + iv_bytes + r2_bytes);
     }
     if (s.kind != RUN_TWO_KERNELS && (p->tile_next_n < s.tile_links || !p->tile_next)) {
         plan_quiesce(p);
@@ -721,7 +765,7 @@ static int launch_second(rt_hip_plan *p, const RunFacts &f, const Tuning &t, con
         }
         return RT_OK;
     }
-    if (kind != PASS_SPEC && (f.debug & 1u)) // (profiling: the march alone)
+    if (kind != PASS_SPEC && kind != PASS_SPEC_SCAN && (f.debug & 1u)) // (profiling: the march alone)
         return RT_OK;
     return launch_pass(p, f, t, kind, stream);
 }
@@ -801,6 +845,9 @@ int rt_hip_debug_run_shape(const rt_hip_run_facts *facts, rt_hip_run_shape *out)
     f.ntest_proven    = facts->ntest_proven != 0;
     f.gv_has_nan      = facts->gv_has_nan != 0;
     f.scan_on         = facts->scan_on != 0;
+    // (length spectra travel as value 2 of spectra_on: the struct keeps its layout, include/rt_hip.h)
+    f.length_spectra_on = facts->spectra_on == 2;
+    f.spectra_on        = facts->spectra_on != 0 && facts->spectra_on != 2;
     const Tuning t    = read_tuning();
     const RunShape s  = run_shape(f, t, [&](const RunShape &) { return facts->occupancy_per_cu; });
     const unsigned size = out->size;

@@ -206,6 +206,7 @@ void rt_hip_plan_destroy(rt_hip_plan *p)
     pool_free(p->device, p->step_dev);
     pool_free(p->device, p->recs_dev);
     pool_free(p->device, p->scan_bnd);
+    pool_free(p->device, p->lspec_dev);
     (void) hipFree(p->seedset_arena);
     (void) hipFree(p->seedset_tab);
     pool_free(p->device, p->arena);
@@ -865,6 +866,8 @@ int rt_hip_plan_enable_path(rt_hip_plan *p, int on)
     if (on && p->scan_on)
         return fail_arg(suffix_scan(p) ? "rt_hip_plan_enable_path: the suffix scan is on (step mode only)"
                                        : "rt_hip_plan_enable_path: the length scan is on (step mode only)");
+    if (on && p->lspec_on)
+        return fail_arg("rt_hip_plan_enable_path: length spectra are on (one per-ray output at a time)");
     p->path_on = on != 0;
     return RT_OK;
 }
@@ -896,13 +899,15 @@ int rt_hip_plan_enable_spectra(rt_hip_plan *p, int on)
     if (on && p->scan_on)
         return fail_arg(suffix_scan(p) ? "rt_hip_plan_enable_spectra: the suffix scan is on (step mode only)"
                                        : "rt_hip_plan_enable_spectra: the length scan is on (step mode only)");
+    if (on && p->lspec_on)
+        return fail_arg("rt_hip_plan_enable_spectra: length spectra are on (a mode of their own: rt_hip_plan_enable_length_spectra switches them off)");
     p->spectra_on = on != 0;
     return RT_OK;
 }
 
 int rt_hip_plan_fetch_spectra(rt_hip_plan *p, double *Iv, rt_ray *ray2, int32_t *err)
 {
-    if (!p || !p->ran || !p->last_spectra)
+    if (!p || !p->ran || !p->last_spectra || p->last_lspec)
         return fail_arg("rt_hip_plan_fetch_spectra: the last run was not a spectra run");
     HIP_TRY(hipSetDevice(p->device));
     HIP_TRY(hipStreamSynchronize(p->last_stream));
@@ -919,7 +924,100 @@ int rt_hip_plan_fetch_spectra(rt_hip_plan *p, double *Iv, rt_ray *ray2, int32_t 
     return RT_OK;
 }
 
-double *rt_hip_plan_spectra_ptr(rt_hip_plan *p) { return p && p->ran && p->last_spectra ? p->spec[p->spec_last].Iv : nullptr; }
+double *rt_hip_plan_spectra_ptr(rt_hip_plan *p) { return p && p->ran && p->last_spectra && !p->last_lspec ? p->spec[p->spec_last].Iv : nullptr; }
+
+// Length spectra (include/rt_hip.h): a mode of its own beside spectra mode and the scans.  The switch owns the boundary
+// states of the march while it is on, as scan_switch does for a scan; the method of the plan says prefix or suffix.
+int rt_hip_plan_enable_length_spectra(rt_hip_plan *p, int on)
+{
+    auto fail = [&](const char *what) { return fail_arg((std::string("rt_hip_plan_enable_length_spectra") + what).c_str()); };
+    if (!p)
+        return fail(": NULL plan");
+    if (on) {
+        if (p->P.N < 3)
+            return fail(": N < 3 (one length: spectra mode is the whole curve)");
+        if (p->P.N - 1 > RT_N_SCAN_MAX)
+            return fail(": more than RT_N_SCAN_MAX lengths");
+        if (p->step_on)
+            return fail(": the plan is in step mode (one output mode at a time)");
+        if (p->spectra_on)
+            return fail(": the plan is in spectra mode (length spectra are a mode of their own)");
+        if (p->path_on)
+            return fail(": the path tracer is enabled (one per-ray output at a time)");
+        if (p->scan_on)
+            return fail(suffix_scan(p) ? ": the suffix scan is on (it leaves step records, not spectra)" : ": the length scan is on (it leaves step records, not spectra)");
+        if (p->n_seed > 0)
+            return fail(p->P.use_emis ? ": the plan holds ASE seeds (length spectra take the creation seed alone)"
+                                      : ": the plan holds a seed set (length spectra take the creation seed alone)");
+    }
+    if ((on != 0) == p->lspec_on)
+        return RT_OK;
+    HIP_TRY(hipSetDevice(p->device));
+    if (p->ran) { // the last run keeps its buffers until it is final
+        const int rs = plan_settle_last_run(p);
+        if (rs != RT_OK)
+            return rs;
+    }
+    plan_quiesce(p);
+    p->lspec_on = on != 0;
+    if (!p->lspec_on) { // the boundary states and the rows exist only while the mode is on
+        pool_free(p->device, p->scan_bnd);
+        p->scan_bnd       = nullptr;
+        p->scan_bnd_bytes = 0;
+        pool_free(p->device, p->lspec_dev);
+        p->lspec_dev   = nullptr;
+        p->lspec_bytes = 0;
+        p->lspec       = {};
+        if (p->last_lspec) // (its rows are gone: the accessors say so, rt_hip_plan_fetch keeps the report and the counters)
+            p->lspec_rays = 0;
+    }
+    return RT_OK;
+}
+
+// block n - 2 of the last length-spectra run, or -1 behind the refusal
+static int lspec_block(const rt_hip_plan *p, const char *who, int n)
+{
+    auto fail = [&](const char *what) { return (void) fail_arg((std::string(who) + what).c_str()), -1; };
+    if (!p || !p->ran || !p->last_lspec || !p->lspec.Iv)
+        return fail(": the last run was not a length-spectra run (or length spectra have been switched off since)");
+    if (n < 2 || n - 1 > p->lspec_L)
+        return fail(": n must be 2 .. N of the last run");
+    return n - 2;
+}
+
+int rt_hip_plan_fetch_length_spectra(rt_hip_plan *p, int n, double *Iv, rt_ray *ray2, int32_t *err)
+{
+    const int b = lspec_block(p, "rt_hip_plan_fetch_length_spectra", n);
+    if (b < 0)
+        return RT_ERR_ARG;
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipStreamSynchronize(p->last_stream));
+    const size_t nr = p->lspec_rays;
+    if (nr == 0)
+        return RT_OK;
+    if (Iv)
+        HIP_TRY(hipMemcpy(Iv, p->lspec.Iv + (size_t) b * nr * (size_t) p->P.K, nr * (size_t) p->P.K * sizeof(double), hipMemcpyDeviceToHost));
+    if (ray2)
+        HIP_TRY(hipMemcpy(ray2, p->lspec.ray2 + (size_t) b * nr, nr * sizeof(rt_ray), hipMemcpyDeviceToHost));
+    if (err)
+        HIP_TRY(hipMemcpy(err, p->lspec.err + (size_t) b * nr, nr * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_hip_plan_length_spectra_ptrs(rt_hip_plan *p, int n, double **Iv_dev, rt_ray **ray2_dev, int32_t **err_dev)
+{
+    const int b = lspec_block(p, "rt_hip_plan_length_spectra_ptrs", n);
+    if (b < 0)
+        return RT_ERR_ARG;
+    const size_t nr = p->lspec_rays;
+    if (Iv_dev)
+        *Iv_dev = p->lspec.Iv + (size_t) b * nr * (size_t) p->P.K;
+    if (ray2_dev)
+        *ray2_dev = p->lspec.ray2 + (size_t) b * nr;
+    if (err_dev)
+        *err_dev = p->lspec.err + (size_t) b * nr;
+    return RT_OK;
+}
 
 int rt_hip_plan_enable_step(rt_hip_plan *p, int on)
 {
@@ -927,6 +1025,8 @@ int rt_hip_plan_enable_step(rt_hip_plan *p, int on)
         return fail_arg("rt_hip_plan_enable_step: NULL plan");
     if (on && (p->path_on || p->spectra_on))
         return fail_arg("rt_hip_plan_enable_step: the path tracer or spectra mode is enabled (one output mode at a time)");
+    if (on && p->lspec_on)
+        return fail_arg("rt_hip_plan_enable_step: length spectra are on (one output mode at a time)");
     p->step_on = on != 0;
     return RT_OK;
 }
@@ -1008,7 +1108,12 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
         return fail_arg("rt_hip_plan_run: NULL plan");
     HIP_TRY(hipSetDevice(p->device));
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
-    const bool spectra = p->spectra_on; // no image, no I_ang: neither allocated nor zeroed
+    const bool lspec   = p->lspec_on; // length spectra: a spectra run at every length (rt_spec_scan.hip)
+    if (lspec && (image_dev || iang_dev))
+        return fail_arg("rt_hip_plan_run: a length-spectra run takes no image buffers");
+    if (lspec && (p->spectra_on || p->step_on || p->path_on || p->scan_on || p->n_seed > 0)) // (no call leads here: every switch refuses the other)
+        return fail_arg("rt_hip_plan_run: length spectra together with another output mode");
+    const bool spectra = p->spectra_on || lspec; // no image, no I_ang: neither allocated nor zeroed
     if (spectra && (image_dev || iang_dev))
         return fail_arg("rt_hip_plan_run: a spectra run takes no image buffers");
     if (spectra && p->path_on)
@@ -1143,6 +1248,12 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
     p->last_image  = image_dev;
     p->last_iang   = iang_dev;
     p->last_spectra = spectra;
+    p->last_lspec  = lspec;
+    p->lspec_first_done = false;
+    if (lspec) {
+        p->lspec_rays = (size_t) p->n_rays;
+        p->lspec_L    = p->P.L;
+    }
     p->last_step   = step;
     p->last_step_lent = lent;
     p->last_records = recs;
@@ -1162,6 +1273,7 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
 // -2 / -3: the report becomes the first RT_N_FAILED_MAX of them in list order, the rays RayTraceImageCPULoop pushes first
 // (RayTraceImageCPU.cpp:32-33).  Fewer marked rays than that (the rest of the count are invalid rays, which carry no
 // mark): the report stays as the kernels left it.
+static int report_first_marked(rt_hip_plan *p, const std::vector<unsigned char> &bad); // (below: the marks, one byte per ray, to the report)
 static int plan_report_first_failed(rt_hip_plan *p)
 {
     const size_t n = (size_t) p->n_rays, word = p->bad_word; // (a length scan: a 32-bit word per ray, marked under anything = any byte set)
@@ -1177,6 +1289,27 @@ static int plan_report_first_failed(rt_hip_plan *p)
             bad[t] = any;
         }
     }
+    return report_first_marked(p, bad);
+}
+
+// ... after a length-spectra run the codes err [L][n] say which rays fail, under any n and with any code (error -1
+// included: the rows are the report, nothing was deposited)
+static int lspec_report_first_failed(rt_hip_plan *p)
+{
+    const size_t n = p->lspec_rays, L = (size_t) p->lspec_L;
+    std::vector<int32_t> err(n * L);
+    if (n * L)
+        HIP_TRY(hipMemcpy(err.data(), p->lspec.err, n * L * sizeof(int32_t), hipMemcpyDeviceToHost));
+    std::vector<unsigned char> bad(n, 0);
+    for (size_t j = 0; j < L; j++)
+        for (size_t t = 0; t < n; t++)
+            bad[t] |= err[j * n + t] != 0;
+    return report_first_marked(p, bad);
+}
+
+static int report_first_marked(rt_hip_plan *p, const std::vector<unsigned char> &bad)
+{
+    const size_t n       = bad.size();
     const rt::DevRays &R = p->P.rays;
     std::vector<double> g;
     if (!R.list) {
@@ -1240,6 +1373,15 @@ static int plan_settle(rt_hip_plan *p, rt::DevCtl &c, bool &staged)
                 return rf;
             HIP_TRY(read_ctl());
         }
+    }
+    // length spectra: no repeat (nothing was deposited); more failing rays than the report holds: the first in list order
+    if (p->last_lspec && c.n_failed > RT_N_FAILED_MAX && !p->lspec_first_done) {
+        const int rf = lspec_report_first_failed(p);
+        if (rf != RT_OK)
+            return rf;
+        p->lspec_first_done = true;
+        p->out_staged = staged = false;
+        HIP_TRY(read_ctl());
     }
     return RT_OK;
 }
@@ -1308,6 +1450,8 @@ int rt_hip_plan_fetch(rt_hip_plan *p, double *image, double *I_ang, unsigned int
 {
     if (!p || !p->ran)
         return fail_arg("rt_hip_plan_fetch: plan has not run");
+    if (p->last_lspec && (image || I_ang))
+        return fail_arg("rt_hip_plan_fetch: the last run was a length-spectra run, it has no image (rt_hip_plan_fetch_length_spectra)");
     if (p->last_spectra && (image || I_ang))
         return fail_arg("rt_hip_plan_fetch: the last run was a spectra run, it has no image (rt_hip_plan_fetch_spectra)");
     if (p->last_step && image)
@@ -1448,6 +1592,8 @@ static int scan_switch(rt_hip_plan *p, const char *who, bool suffix, int on)
         return fail(": the plan's method is not 1 (only the backward march of N lengths begins with the marches of the last n)");
     if (!suffix && !on && suffix_scan(p)) // (on: the method test below refuses it)
         return fail(": the suffix scan is on (rt_hip_plan_enable_suffix_scan switches it off)");
+    if (on && p->lspec_on)
+        return fail(": length spectra are on (they and a scan of step records exclude each other)");
     if (on) {
         if (!suffix && p->P.method != 2)
             return fail(": the plan's method is not 2 (only the forward march of N lengths holds the marches of fewer)");
@@ -1648,6 +1794,8 @@ static int seeds_set(rt_hip_plan *p, const SeedsEntry &e, int n_seed, const rt_s
     auto fail = [&](const std::string &what) { return fail_arg((e.who + what).c_str()); };
     if (!p)
         return fail(": NULL plan");
+    if (p->lspec_on)
+        return fail(": length spectra are on (they take the creation seed alone)");
     if (e.scan == SUFFIX_SCAN_ON && p->P.method != 1)
         return fail(std::string(": the plan's method is not 1 (a forward plan takes ") + e.forward + ")");
     if (e.emission == (p->P.has_seed != 0))

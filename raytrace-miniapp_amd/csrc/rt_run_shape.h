@@ -35,7 +35,11 @@ struct RunFacts {
     // a length scan (rt_hip_plan_enable_length_scan): one step record per length from one forward march; with method == 1
     // the suffix scan (rt_hip_plan_enable_suffix_scan): one record per run of the last n lengths from one backward march
     bool scan_on = false;
-    bool rscan() const { return scan_on && method == 1; }
+    // length spectra (rt_hip_plan_enable_length_spectra): per-ray spectra at every length from the same scan march, forward
+    // or backward by the method; a mode of its own, never together with step_on, spectra_on or scan_on
+    bool length_spectra_on = false;
+    bool scan_march() const { return scan_on || length_spectra_on; } // the run takes the scan instance of the march
+    bool rscan() const { return scan_march() && method == 1; }
     bool s6() const { return L * RT_N_SUB == 6; } // N = 3, the shipped inputs: the instances with SF = 6
 };
 
@@ -261,7 +265,7 @@ inline RunShape run_shape(const RunFacts &f, const Tuning &t, const Occupancy &o
     const bool iang_fits  = f.n_iang * sizeof(double) <= 32 * 1024;
     const bool fused_emis = f.use_emis && f.method == 1 && f.own_cells && f.rays_per_pixel >= 32;
     const bool fused_gain = !f.use_emis && !f.has_ray_list && t.fused_seed == 1;
-    const bool fused_cand = s.lds_tab && s.n_launch == 1 && f.n_rays > 0 && !f.path_on && !f.spectra_on && !f.step_on && !f.probe_on && f.debug == 0 &&
+    const bool fused_cand = s.lds_tab && s.n_launch == 1 && f.n_rays > 0 && !f.path_on && !f.spectra_on && !f.length_spectra_on && !f.step_on && !f.probe_on && f.debug == 0 &&
                             (fused_emis || fused_gain) && !f.exclusive && f.safe == 0 && iang_fits && t.fused == 1;
     // ---- step mode in ONE launch (rt_fused_step.hip), where the caller has asked for it (rt_hip_plan_set_step_one_launch):
     // the conditions of the emission run above without those that exist for the few-runs image deposit only -- the step
@@ -308,7 +312,8 @@ inline RunShape run_shape(const RunFacts &f, const Tuning &t, const Occupancy &o
     // time, the emission switch as DevParams says, no pruning; with bounded and unbounded tables, in LDS or not)
     // (the suffix scan: the same stores from the backward march -- MODE 1, backward and emission at compile time, for an
     // emission plan, MODE 0 for a seeded one)
-    if (f.scan_on) {
+    // (length spectra take the same instances: the march does not know which pass reads its boundary states)
+    if (f.scan_march()) {
         s.mode = f.rscan() ? (f.use_emis ? 1 : 0) : 3;
         s.opt  = rt::MARCH_OPT_SCAN;
     }
@@ -379,7 +384,7 @@ inline RecordSet record_set(const RunFacts &f)
 
 inline PassKind pass_kind(const RunFacts &f)
 {
-    return f.path_on ? PASS_PATH : f.spectra_on ? PASS_SPEC : f.step_on ? record_set(f).pass_kind() : PASS_FREQ;
+    return f.path_on ? PASS_PATH : f.spectra_on ? PASS_SPEC : f.length_spectra_on ? PASS_SPEC_SCAN : f.step_on ? record_set(f).pass_kind() : PASS_FREQ;
 }
 
 struct PassShape {
@@ -434,21 +439,26 @@ inline PassShape pass_shape(PassKind kind, const RunFacts &f, const Tuning &t)
     if (kind == PASS_PATH)
         return s;
     // (one global atomic per ray on na*nb addresses serialises badly: the histogram stays in LDS)
-    s.in_lds = kind != PASS_SPEC && f.n_iang * sizeof(double) <= 32 * 1024;
+    s.in_lds = kind != PASS_SPEC && kind != PASS_SPEC_SCAN && f.n_iang * sizeof(double) <= 32 * 1024;
     if (kind == PASS_FREQ)
         freq_pass_shape(s, f, t);
     else {
         // spectra, step, step of a seed set, of a length scan or of a scan with its seeds: one 16-wave work-group per CU
         s.wg_waves = rt::FREQ_WG_WAVES;
+        // (length spectra: RT_HIP_FREQ_WG_WAVES applies, for the measurement of fewer waves per work-group -- DESIGN.md 4.18,
+        // staging candidate (c); the default is the sixteen of every pass here)
+        if (kind == PASS_SPEC_SCAN)
+            s.wg_waves = (int) t.freq_wg_waves;
         // (a seed set keeps one I_ang histogram and one E_v accumulator per seed, a length scan one of each per length, a scan
         // with scan seeds one of each per (seed, length), an emission plan with ASE seeds one of each for ASE and per seed -- with
         // the scan on, of those per length; a suffix scan one of each per length, with ASE seeds one per (record, length), with
         // scan seeds one per (seed, length))
-        const int n_rec      = kind == PASS_STEP || kind == PASS_SPEC ? 1 : record_set(f).n_rec();
+        const int n_rec      = kind == PASS_STEP || kind == PASS_SPEC || kind == PASS_SPEC_SCAN ? 1 : record_set(f).n_rec();
         const int ang_stride = kind == PASS_STEP ? rt::step_ang_stride((int) f.n_iang) : rt::seeds_ang_stride((int) f.n_iang);
         auto step_lds        = [&](bool in_lds) { return rt::step_lds_doubles(in_lds, ang_stride, f.Kp, s.wg_waves, n_rec) * sizeof(double); };
-        // (spectra: the staging rows of 16 waves and the exponent tables take 148 KB of LDS)
-        s.lds = kind == PASS_SPEC ? ((size_t) 2 * rt::EXP_TAB + (size_t) s.wg_waves * rt::WAVE * rt::XS_ROW) * sizeof(double) : step_lds(s.in_lds);
+        // (spectra: the staging rows of 16 waves and the exponent tables take 148 KB of LDS; length spectra cut the same rows
+        // into VEC frequencies of four lengths, rt_spec_scan.hip)
+        s.lds = kind == PASS_SPEC || kind == PASS_SPEC_SCAN ? ((size_t) 2 * rt::EXP_TAB + (size_t) s.wg_waves * rt::WAVE * rt::XS_ROW) * sizeof(double) : step_lds(s.in_lds);
         if ((kind == PASS_SEEDS || kind == PASS_SCAN || kind == PASS_SCAN_SEEDS || kind == PASS_ASE_SEEDS || kind == PASS_SCAN_ASE_SEEDS ||
              kind == PASS_RSCAN || kind == PASS_RSCAN_ASE_SEEDS || kind == PASS_RSCAN_SEEDS) && s.in_lds &&
             s.lds > f.lds_limit) { // one histogram per record does not fit: global atomics
@@ -456,7 +466,7 @@ inline PassShape pass_shape(PassKind kind, const RunFacts &f, const Tuning &t)
             s.lds    = step_lds(false);
         }
         s.grid = one_wg_per_cu(f.n_tiles, (unsigned) s.wg_waves, f.cu_count);
-        if (kind != PASS_SPEC && t.step_serial == 1) { // one wave, one work-group: sums in a fixed order (Tuning::step_serial)
+        if (kind != PASS_SPEC && kind != PASS_SPEC_SCAN && t.step_serial == 1) { // one wave, one work-group: sums in a fixed order (Tuning::step_serial)
             s.wg_waves = 1;
             s.lds      = step_lds(s.in_lds);
             s.grid     = f.n_tiles ? 1u : 0u;

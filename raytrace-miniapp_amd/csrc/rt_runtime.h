@@ -7,7 +7,7 @@
 //   rt_raygrid.hip  a ray list that is really a tensor grid: recognition + bit-wise verification,
 //                   list-mode launch tangents and the probe of the host's libm
 //   rt_launch.hip   the kernels (rt_march.hip, rt_freq.hip, rt_path.hip, rt_spec.hip, rt_step.hip, rt_step_seeds.hip, rt_fused_step.hip,
-//                   rt_step_scan.hip, rt_step_scan_seeds.hip, rt_step_ase_seeds.hip) and how a run puts them on a queue:
+//                   rt_step_scan.hip, rt_step_scan_seeds.hip, rt_step_ase_seeds.hip, rt_spec_scan.hip) and how a run puts them on a queue:
 //                   WHAT a run looks like -- tables in LDS or not, one launch or two, instance, grid, chunk, late zone, the
 //                   LDS layout of a one-launch run, the shape of the second pass -- is decided by pure functions of plain
 //                   numbers (rt_run_shape.h, included by rt_launch.hip alone: RunFacts from the plan + Tuning from the
@@ -84,6 +84,18 @@ struct rt_hip_plan {
     unsigned spec_last = 0;       // ... and the one the last run wrote
     rt::SpecOut spec[2] = {};
     size_t spec_rays[2] = { 0, 0 }; // rays each set has room for
+    // length spectra (rt_hip_plan_enable_length_spectra): what spectra mode leaves, at every length n = 2 .. N from one scan
+    // march (rt_spec_scan.hip).  A mode of its own: never together with step, spectra, path, a scan or any seeds.  One
+    // allocation from the pool, Iv [L][n][K] | ray2 [L][n] | err [L][n], not zeroed: the kernel writes every element.  The
+    // boundary states of the march live in scan_bnd (below) while the mode is on, as a scan's do.
+    bool lspec_on      = false;
+    bool last_lspec    = false;   // the last run was a length-spectra run (last_spectra is set as well: no image, no checking repeat)
+    bool lspec_first_done = false; // ... and its report of more than RT_N_FAILED_MAX failing rays has been put into list order
+    rt::SpecOut lspec  = {};      // block n - 2 of each array: the rows of the sub-problem of n lengths
+    unsigned char *lspec_dev = nullptr;
+    size_t lspec_bytes = 0;
+    size_t lspec_rays  = 0;       // rays of the last length-spectra run (the block stride of the arrays)
+    int lspec_L        = 0;       // ... and its lengths
     // step mode (rt_hip_plan_enable_step): E_v and nf instead of the image cube.  One allocation, zeroed by the run's
     // zeroing launch: E_v [K] at its start, nf [nx * ny] behind it at a 256-byte boundary.
     bool step_on       = false;

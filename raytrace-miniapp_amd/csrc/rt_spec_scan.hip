@@ -1,0 +1,506 @@
+#pragma once
+// rt_spec_scan.hip -- length spectra (rt_hip_plan_enable_length_spectra): RayTrace::calc_ray for every ray at every
+// plasma length n = 2 .. N from ONE march.
+//
+// The scan instance of the march (rt_march.hip, MARCH_OPT_SCAN) runs unchanged and leaves the state with which every ray
+// crossed every length boundary.  With the forward method the sub-problem of n lengths is problem.prefix_lengths: the first
+// 3 (n - 1) slots of the march record (rt_step_scan.hip); with the backward method it is problem.suffix_lengths: the last
+// 3 (n - 1) slots (rt_step_rscan.hip).  Which state serves row block n (m = n - 1 marched segments, L = N - 1; e = the
+// marched segment the ray escaped in, L + 1 if never) is the table of those two files:
+//   not escaped, m < L      boundary m                          not escaped, m = L      the final RecMeta
+//   escaped,     m < e      boundary m, the ray NOT escaped     escaped,     m >= e     the final RecMeta, escaped
+// Error -1 of block n is s.z^2 < 0.01 of that state, ray2 its position and exit angles (atanf_flt32_kernel), the seed
+// factor (gain-only mode) is taken at the launch ray (forward) or at that state (backward) and is 0 once the ray has
+// escaped.  Rows follow rt_spec.hip: error -1 and a ray whose every update is the identity give a row of zeros, -2 wins
+// over -3.
+//
+// rt_spec_scan_kernel<EMIS, BACKWARD> stands where rt_spec_kernel stands and has its shell: one 16-wave work-group per CU,
+// tiles from the eight sharded counters, lanes = rays, the LDS of rt_spec_kernel (the exponent tables and [64][XS_ROW]
+// staging doubles per wave), its launch bounds.  The tile text is that of the scan kernels: rt_tile_ray.inc, rt_tile_rec.inc
+// with SF = 0, rec_slot_lazy, so the arithmetic of a slot is rt_tile_batch.inc's for SF = 0.
+//   forward   the prefixes share one running spectrum: per frequency batch ONE walk over the slots, and the running Iv
+//             (gain-only: one exp_tab_vec of the running gl) after the three sub-segments of length j is row n = j + 1.
+//   backward  suffix n starts with its own initial value at slot 3 (N - n): the walk of rt_step_rscan.hip, LSPEC_LCH
+//             accumulators per walk that join one segment after the other, e^gl - 1 of a slot taken once (ase_factor),
+//             irregular sub-segments and the exact mode through ase_update_factors; gain-only one f64 product sum per suffix.
+// In gain-only mode and with exact emission every Iv_n[k] is the double rt_spec_kernel computes on the sub-problem.  (The plan
+// of the N = 3 sub-problem takes rt_spec_kernel<6, true>, which contracts the last line of ase_update otherwise than
+// rt_spec_kernel<0, true>: with exact emission the rows of n = 3 are integrated in that form, AseUpdate::apply_n3 -- forward by a
+// second running spectrum over the first six slots, backward in the accumulator of that suffix)  In the
+// default emission mode the sub-problem's plan may take another update (its tile-wide choice sees other slots, and its
+// N = 3 instance has SF = 6), as the records of the scan kernels differ from a step plan's.
+//
+// Outputs, length-major: Iv [L][n_rays][K] (row stride K), ray2 [L][n_rays], err [L][n_rays]; block n - 2 has the shape
+// of spectra mode's output of the sub-problem.  Every element is written.
+//
+// The stores.  A wave cannot hold L stagings of 16 frequencies, so the staging rows are cut the other way: VEC frequencies
+// of LSPEC_LCH = 4 lengths per lane ([64][XS_ROW], column li * VEC + v).  When four lengths are staged (forward: every
+// fourth length of the walk; backward: the end of a chunk's walk) each length leaves as 64 row pieces of 32 bytes, 16 bytes
+// per lane and 32 rows per instruction; the next frequency batches complete the cache lines in L2, as rt_spec.hip found
+// ordinary stores do.  No slot is integrated twice for the stores' sake.  Ragged last tiles and odd K keep rt_spec.hip's
+// 8-byte path; a last batch of two frequencies (K = 4 i + 2) leaves as one 16-byte piece per row.
+#include "rt_spec.hip"
+#include "rt_step_rscan.hip"
+
+namespace rt {
+
+#pragma clang fp contract(fast) // (the float64 half, as in rt_freq.hip and rt_spec.hip: the same contractions, the same doubles)
+
+constexpr int LSPEC_LCH = 4; // lengths per staging: LSPEC_LCH * VEC doubles of a staging row
+static_assert(LSPEC_LCH * VEC <= XS_ROW - 2 && VEC == 4, "a staging row holds VEC frequencies of LSPEC_LCH lengths");
+
+// what rt_spec_scan_kernel reads beside the frequency kernel's block (through the constant address space, as the cold half)
+struct SpecScanArg {
+    SpecOut out;              // Iv [L][n_rays][K], ray2 [L][n_rays], err [L][n_rays]
+    const unsigned char *bnd; // boundary states of the march (scan_bnd_off)
+};
+struct SpecScanKArg {
+    FreqHot hot;
+    FreqCold cold;
+    SpecScanArg scan;
+};
+typedef const RT_CONST_AS SpecScanArg *SpecScanPtr;
+
+// ase_update (rt_freq.hip) for several accumulators of one (sub-segment, frequency): what of the update does not depend on Iv
+// is taken once -- small |gl|: Iv' = el X + Iv B, else Iv' = (el / gl) (e^gl - 1) + Iv e^gl -- and apply() finishes it per
+// accumulator.  The roundings are written out as the compiler contracts ase_update where it stands alone (ase_update_call,
+// rt_step_rscan.hip): fma(X, el, Iv B) and fma(Iv, e^gl, t).  (That call itself is not taken here: with one more caller of it,
+// or with another function held to a call beside it, rt_step_rscan_kernel<true> and rt_step_rscan_ase_seeds_kernel came out of
+// the compiler with other registers; ase_update inlined per accumulator and frequency left the backward emission instance 176
+// bytes of scratch.  profiles/length_spectra_kernel_resources.txt)
+struct AseUpdate {
+    double a, b, c; // small |gl|: X, B, el; else: t = (el / gl) (e^gl - 1), e^gl, unused
+    bool small;
+    __device__ __forceinline__ double apply(const double Iv) const { return small ? fma(a, c, Iv * b) : fma(Iv, b, a); }
+    // ... as rt_spec_kernel<6, true> contracts it, the instance a spectra-mode plan of an N = 3 problem takes: there the two
+    // branches meet behind the product that does not hold Iv, so the small branch is fma(Iv, B, el X) as well (read from
+    // its device assembly: 24 of 24 updates; the other branch is the same in both instances).  With exact emission the rows
+    // of n = 3 take this form, so that they are the doubles of that plan (measured otherwise: one unit in the last place
+    // in 4 % of the values).  This restates by hand what the compiler made of ase_update inside ANOTHER kernel: it holds for
+    // that code object and no longer.  A compiler update, or an edit of rt_spec.hip, rt_tile_batch.inc or rt_freq.hip, may move
+    // the contraction there without a word, and only tests/test_gpu_length_spectra.py (exact emission, n = 3) would notice;
+    // writing the form out in rt_spec_kernel<6> as well, so that both sides are explicit, is left to a change that may
+    // touch that kernel.
+    __device__ __forceinline__ double apply_n3(const double Iv) const { return fma(Iv, b, small ? a * c : a); }
+};
+__device__ __forceinline__ AseUpdate ase_update_factors(const float gs, const float es, const float w, const double *tab)
+{
+    const double gl = (double) (gs * w); // f32 product, then widened (Helper.h:549-550)
+    const double el = (double) (es * w);
+    AseUpdate u;
+    u.small = fabs(gl) < 1e-3;
+    if (u.small) {
+        u.a = fma(0.5 * gl, fma(gl, 0.3333333333, 1.0), 1.0);
+        u.b = fma(fma(gl, 0.5, 1.0), gl, 1.0);
+        u.c = el;
+    } else {
+        const double eg = exp_tab(gl, tab);
+        u.a             = div_fast(el, gl) * (eg - 1.0);
+        u.b             = eg;
+        u.c             = 0.0;
+    }
+    return u;
+}
+
+template <bool EMIS, bool BACKWARD>
+__device__ __forceinline__ void spec_scan_tile(const FreqHot &H, const unsigned hflags, ColdPtr C, SpecScanPtr Q, const double *tab, double *stage,
+                                               const unsigned tile, const int lane)
+{
+    constexpr int SF      = 0; // (the text fragments below read it: slots at run time)
+    constexpr int LCH     = LSPEC_LCH;
+    const int L           = H.L;
+    const int S           = L * RT_N_SUB;
+    const int K           = H.K;
+    const int Kp          = H.Kp;
+    const unsigned n_rays = H.n_rays;
+    const unsigned row0   = tile * WAVE;
+    const unsigned ridx   = row0 + (unsigned) lane;
+    const bool have       = ridx < n_rays;
+    const bool backward   = BACKWARD;
+    const unsigned rrec      = have ? ridx : 0u;
+    const unsigned char *rec = H.rec;
+    const bool probe_on   = (hflags & FQ_PROBE) != 0;
+    const bool seeded     = !EMIS && (hflags & FQ_HAS_SEED) != 0; // (the emission recurrence takes no seed factor)
+
+    // ---- per-ray preamble, once: the final state of the ray (rt_tile_ray.inc) ----
+#define TILE_NEED_RAY false
+#include "rt_tile_ray.inc"
+#undef TILE_NEED_RAY
+    (void) err1; // (of the final state: every block takes the test of its own state, open_block)
+    if (__ballot(have) == 0ull)
+        return;
+    // the marched segment the ray escaped in (never: L + 1)
+    const int n_done           = (int) ((m.flags_steps >> REC_NDONE_SHIFT) & REC_NDONE_MASK);
+    const unsigned flags_steps = m.flags_steps;
+    const int e_seg            = (fl & F_ESCAPED) ? (n_done > 0 ? (n_done - 1) / RT_N_SUB + 1 : 1) : L + 1;
+    const bool skip            = (fl & F_SKIP) != 0u; // every update is the identity: rows of zeros at every n
+
+    // the seed factor at the launch ray (forward, Helper.h:530-533), in place_ray's own arithmetic as rt_step_scan.hip takes it
+    double f0_launch = 0.0;
+    if (!BACKWARD && have && seeded) {
+        if (!R.sf) {
+            rt_ray launch = ray;
+            float ta, tb;
+            load_ray(R, ridx, launch, ta, tb, false);
+            // (rscan_seed_factor: scan_seed_factor on a seed that stays in the argument block -- with the copy this instance kept
+            // a 48-byte stack frame that nothing read)
+            f0_launch = rscan_seed_factor(&C->seed, (double) launch.x, (double) launch.y, (double) launch.a, (double) launch.b);
+        } else {
+            RT_SEED_GRID_POINT(R, ridx)
+            RT_SEED_GRID_FACTOR(f0_launch, C->seed.f0, R.sf, R.sin)
+        }
+    }
+
+    // ---- the march record of this lane's ray (rt_tile_rec.inc; SF = 0: nothing to decode up front) ----
+#define TILE_MASK true
+#include "rt_tile_rec.inc"
+#undef TILE_MASK
+    (void) gs;
+    (void) rs;
+    (void) off;
+    (void) all_small;
+    (void) all_regular;
+    (void) load_rows;
+    (void) gv_nan; // (SF = 0 tests every frequency's lineshape values as it reads them)
+    const ConstF64 sfk = (ConstF64) (unsigned long long) H.seed_fk;
+
+    // one bit per row block (bit m - 1 = block n - 2): error -1, live, not escaped (carries the seed factor), a negative
+    // value seen, a NaN seen
+    unsigned e1m = 0u, livem = 0u, seedm = 0u, negm = 0u, nanm = 0u;
+    const size_t blk_rays = (size_t) n_rays;
+
+    // the state that serves block m - 1: the -1 test, the exit ray (stored here), the bits; returns the seed factor of the
+    // backward method, taken at that state (Helper.h:518-529)
+    auto open_block = [&](const int mseg) -> double {
+        float spx = m.px, spy = m.py, ssx = m.sx, ssy = m.sy, ssz = m.sz;
+        bool esc  = (fl & F_ESCAPED) != 0u;
+        if (have && mseg < L && mseg < e_seg) {
+            const float *q = reinterpret_cast<const float *>(Q->bnd + scan_bnd_off(ridx, mseg, L));
+            spx            = q[0];
+            spy            = q[1];
+            ssx            = q[2];
+            ssy            = q[3];
+            ssz            = q[4];
+            esc            = false;
+        }
+        const unsigned bit = 1u << (mseg - 1);
+        const bool e1      = have && (double) (ssz * ssz) < 0.01; // Helper.h:515
+        rt_ray r2          = { 0.0f, 0.0f, 0.0f, 0.0f };          // (zeros under error -1, as rt_spec.hip leaves them)
+        double f0          = 0.0;
+        if (have && !e1) {
+            r2.x = spx; // Helper.h:518-521
+            r2.y = spy;
+            r2.a = atanf_flt32_kernel(ssx / ssz) * 1e3f;
+            r2.b = atanf_flt32_kernel(ssy / ssz) * 1e3f;
+            if (!skip)
+                livem |= bit;
+            if (seeded && !esc) {
+                seedm |= bit;
+                if (BACKWARD)
+                    f0 = rscan_seed_factor(&C->seed, (double) spx, (double) spy, (double) r2.a, (double) r2.b);
+            }
+        }
+        if (e1)
+            e1m |= bit;
+        if (have) {
+            Q->out.ray2[(size_t) (mseg - 1) * blk_rays + ridx] = r2;
+            if (probe_on && mseg == L) { // the probe is that of the whole run
+                C->probe.ray2[ridx]  = r2;
+                C->probe.flags[ridx] = fl | (e1 ? F_ERR1 : 0u);
+                C->probe.steps[ridx] = steps;
+            }
+        }
+        return f0;
+    };
+
+    // a full tile and an even K: the pieces of a row leave as 16-byte stores
+    const bool wide_ok = row0 + WAVE <= n_rays && (K & 1) == 0;
+    // the lane's VEC values of block jb into column `col` of its staging row, the -2 / -3 scan on the way (Helper.h:582-587)
+    auto stage_row = [&](const int col, const int jb, const double (&Iv)[VEC], const int kb) {
+        const bool lv = ((livem >> jb) & 1u) != 0u;
+        double *mine  = stage + lane * XS_ROW + col * VEC;
+#pragma unroll
+        for (int v = 0; v < VEC; v++) {
+            const double x = (lv && kb + v < K) ? Iv[v] : 0.0; // (the padding columns K .. Kp-1 are not part of the spectrum)
+            negm |= x < 0.0 ? 1u << jb : 0u;
+            nanm |= x != x ? 1u << jb : 0u;
+            mine[v] = x;
+        }
+    };
+    // column `col` of the 64 staging rows to block jb, frequencies kb .. kb + VEC - 1
+    auto flush_row = [&](const int col, const int jb, const int kb) {
+        double *blk     = Q->out.Iv + (size_t) jb * blk_rays * (size_t) K;
+        const int width = K - kb < VEC ? K - kb : VEC;
+        if (wide_ok && width == VEC) {
+            // two lanes cover the 32 staged bytes of a row, a store instruction 32 rows
+#pragma unroll
+            for (int g = 0; g < 2; g++) {
+                const unsigned row = (unsigned) (32 * g + (lane >> 1));
+                SPEC_STORE16(stage + row * XS_ROW + col * VEC + 2 * (lane & 1), blk + ((size_t) (row0 + row) * (size_t) K + (size_t) (kb + 2 * (lane & 1))));
+            }
+        } else if (wide_ok) { // K = 4 i + 2: the last two frequencies of a row, one piece per lane
+            SPEC_STORE16(stage + lane * XS_ROW + col * VEC, blk + ((size_t) (row0 + (unsigned) lane) * (size_t) K + (size_t) kb));
+        } else {
+            // ragged tile or odd K: 8 bytes per lane, sixteen rows per instruction
+            const int k = kb + (lane & 3);
+#pragma unroll
+            for (int g = 0; g < WAVE / 16; g++) {
+                const unsigned row = (unsigned) (16 * g + (lane >> 2));
+                if (row0 + row < n_rays && k < K)
+                    blk[(size_t) (row0 + row) * (size_t) K + (size_t) k] = stage[row * XS_ROW + col * VEC + (lane & 3)];
+            }
+        }
+    };
+    // Iv of a row from its accumulator: emission, the running value unless a NaN or an infinity was among the lineshape
+    // values (0 * NaN on the CPU); gain-only, f0 f[4][k] exp(gl), the exponential skipped by a wave that has no use for it
+    // (rt_tile_batch.inc)
+    auto finish = [&](const double (&acc)[VEC], const unsigned wn, const double f0, const int kb, double (&Iv)[VEC]) {
+        if (EMIS) {
+#pragma unroll
+            for (int v = 0; v < VEC; v++)
+                Iv[v] = ((wn >> v) & 1u) ? __builtin_nan("") : acc[v];
+        } else {
+            bool need = f0 != 0.0;
+#pragma unroll
+            for (int v = 0; v < VEC; v++)
+                need = need || acc[v] > 700.0 || acc[v] != acc[v];
+#pragma unroll
+            for (int v = 0; v < VEC; v++)
+                Iv[v] = f0 * sfk[kb + v];
+            if (__ballot(need) != 0ull) {
+                double eg[VEC];
+                exp_tab_vec(acc, tab, eg);
+#pragma unroll
+                for (int v = 0; v < VEC; v++)
+                    Iv[v] *= eg[v];
+            }
+        }
+    };
+
+    if (!BACKWARD) {
+        // ---- forward: every block's state first, then one walk per frequency batch ----
+#pragma unroll 1
+        for (int j = 1; j <= L; j++)
+            (void) open_block(j);
+        const bool any_live = __ballot(livem != 0u) != 0ull; // (else nothing to integrate: the rows are zeros)
+        for (int kb = 0; kb < K; kb += VEC) {
+            double acc[VEC]; // emission: the running Iv; gain-only: the running gl
+            double acc3[VEC]; // exact emission: the running Iv of the first two lengths in the arithmetic of the N = 3 plan (AseUpdate::apply_n3)
+            unsigned wn = 0u; // emission, bit v: a NaN or infinity among frequency v's lineshape values so far
+#pragma unroll
+            for (int v = 0; v < VEC; v++)
+                acc[v] = acc3[v] = 0.0;
+#pragma unroll 1
+            for (int j = 0; j < L; j++) {
+                if (any_live) {
+#pragma unroll 1
+                    for (int t = 0; t < RT_N_SUB; t++) {
+                        // one sub-segment: the SF = 0 text of rt_tile_batch.inc
+                        int s = j * RT_N_SUB + t;
+                        asm volatile("" : "+s"(s));
+                        const RecSlot sl = rec_slot_lazy(rec, rrec, H.rec_stride, s, S, flags_steps, backward);
+                        const float *row = H.gain[s / RT_N_SUB + 1].gv + (size_t) sl.c * (size_t) Kp + kb;
+                        const FVec w     = *reinterpret_cast<const FVec *>(row);
+                        if (EMIS) {
+                            const float g1 = sl.g, e1 = sl.e;
+#pragma unroll
+                            for (int v = 0; v < VEC; v++)
+                                wn |= !(fabsf(w.v[v]) <= FLT_MAX) ? 1u << v : 0u;
+                            if (fabsf(g1) >= RT_RS_MIN && fabsf(g1) <= H.gs_cap && !exact_emis) {
+                                const double r1 = div_fast((double) e1, (double) g1);
+                                ase_step(acc, g1, r1, w.v, tab);
+                            } else if (g1 != 0.0f || e1 != 0.0f) {
+#pragma unroll
+                                for (int v = 0; v < VEC; v++)
+                                    acc[v] = ase_update(acc[v], g1, e1, w.v[v], tab);
+                                if (exact_emis && j < 2) { // (every update of the exact mode comes here: acc3 misses none)
+#pragma unroll
+                                    for (int v = 0; v < VEC; v++)
+                                        acc3[v] = ase_update_factors(g1, e1, w.v[v], tab).apply_n3(acc3[v]);
+                                }
+                            }
+                        } else {
+#pragma unroll
+                            for (int v = 0; v < VEC; v++)
+                                acc[v] += (double) sl.g * (double) w.v[v];
+                        }
+                    }
+                }
+                // ---- the walk has reached length j + 1: row block j ----
+                double Iv[VEC];
+                finish(acc, wn, ((seedm >> j) & 1u) ? f0_launch : 0.0, kb, Iv);
+                if (EMIS && exact_emis && j == 1) { // the rows of n = 3 (wn as above: the same slots)
+#pragma unroll
+                    for (int v = 0; v < VEC; v++)
+                        Iv[v] = ((wn >> v) & 1u) ? __builtin_nan("") : acc3[v];
+                }
+                stage_row(j & (LCH - 1), j, Iv, kb);
+                if ((j & (LCH - 1)) == LCH - 1 || j == L - 1) {
+                    __builtin_amdgcn_wave_barrier();
+#pragma unroll 1
+                    for (int jj = j & ~(LCH - 1); jj <= j; jj++)
+                        flush_row(jj & (LCH - 1), jj, kb);
+                    __builtin_amdgcn_wave_barrier();
+                }
+            }
+        }
+    } else {
+        // ---- backward: the suffixes in chunks of LCH start segments a0 .. a0 + LCH - 1 (start segment a is block L - 1 - a) ----
+        for (int a0 = 0; a0 < L; a0 += LCH) {
+            double f0[LCH];
+#pragma unroll
+            for (int i = 0; i < LCH; i++) {
+                f0[i] = 0.0;
+                if (a0 + i < L) {
+                    const double f = open_block(L - (a0 + i));
+                    if (!EMIS)
+                        f0[i] = f;
+                }
+                // (one state after the other, as rt_step_rscan.hip takes them)
+                asm volatile("" ::: "memory");
+            }
+            unsigned chunk_bits = 0u; // the blocks of this chunk
+#pragma unroll
+            for (int i = 0; i < LCH; i++)
+                chunk_bits |= a0 + i < L ? 1u << (L - 1 - (a0 + i)) : 0u;
+            const bool any_live = __ballot((livem & chunk_bits) != 0u) != 0ull;
+            // exact emission: the accumulator of n = 3 (m = 2 marched segments) takes the arithmetic of the N = 3 plan
+            const int i_n3 = exact_emis ? L - 2 - a0 : -1;
+
+            for (int kb = 0; kb < K; kb += VEC) {
+                double acc[LCH][VEC]; // emission: the running Iv of every suffix; gain-only: its running gl
+                unsigned wnan = 0u;   // emission, bit i * VEC + v: a NaN or infinity among frequency v's lineshape values since suffix i began
+#pragma unroll
+                for (int i = 0; i < LCH; i++) {
+#pragma unroll
+                    for (int v = 0; v < VEC; v++)
+                        acc[i][v] = 0.0;
+                }
+                // one sub-segment for the first NL accumulators: the walk of rt_step_rscan.hip, its factor taken once
+                auto slot_step = [&](auto nl_tag, int s) {
+                    constexpr int NL = decltype(nl_tag)::value;
+                    asm volatile("" : "+s"(s));
+                    const RecSlot sl = rec_slot_lazy(rec, rrec, H.rec_stride, s, S, flags_steps, backward);
+                    const float *row = H.gain[s / RT_N_SUB + 1].gv + (size_t) sl.c * (size_t) Kp + kb;
+                    const FVec w     = *reinterpret_cast<const FVec *>(row);
+                    if (EMIS) {
+                        const float g1 = sl.g, e1 = sl.e;
+                        unsigned wn = 0u;
+#pragma unroll
+                        for (int v = 0; v < VEC; v++)
+                            wn |= !(fabsf(w.v[v]) <= FLT_MAX) ? 1u << v : 0u;
+                        constexpr unsigned spread = NL >= 4 ? 0x1111u : NL == 3 ? 0x111u : NL == 2 ? 0x11u : 0x1u;
+                        static_assert(VEC == 4 && LCH <= 4, "wnan keeps VEC bits per accumulator, four accumulators at most");
+                        wnan |= wn * spread;
+                        if (fabsf(g1) >= RT_RS_MIN && fabsf(g1) <= H.gs_cap && !exact_emis) {
+                            const double r1 = div_fast((double) e1, (double) g1);
+                            ase_factor(g1, w.v, tab, [&](const int v, const double em1) {
+#pragma unroll
+                                for (int i = 0; i < NL; i++)
+                                    acc[i][v] = fma(em1, acc[i][v] + r1, acc[i][v]);
+                            });
+                        } else if (g1 != 0.0f || e1 != 0.0f) {
+#pragma unroll
+                            for (int v = 0; v < VEC; v++) {
+                                const AseUpdate u = ase_update_factors(g1, e1, w.v[v], tab);
+#pragma unroll
+                                for (int i = 0; i < NL; i++)
+                                    acc[i][v] = i == i_n3 ? u.apply_n3(acc[i][v]) : u.apply(acc[i][v]);
+                            }
+                        }
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < NL; i++) {
+#pragma unroll
+                            for (int v = 0; v < VEC; v++)
+                                acc[i][v] += (double) sl.g * (double) w.v[v];
+                        }
+                    }
+                };
+                if (any_live) {
+                    // the joining part: segment a0 + I is walked with accumulators 0 .. I
+#define LSPEC_JOIN(I)                                                                                            \
+    if (I < LCH && a0 + I < L) {                                                                                 \
+        _Pragma("unroll 1") for (int t = 0; t < RT_N_SUB; t++)                                                   \
+            slot_step(std::integral_constant<int, (I < LCH ? I + 1 : LCH)>{}, (a0 + I) * RT_N_SUB + t);          \
+    }
+                    LSPEC_JOIN(0)
+                    LSPEC_JOIN(1)
+                    LSPEC_JOIN(2)
+                    LSPEC_JOIN(3)
+#undef LSPEC_JOIN
+                    // ... and the segments behind the chunk's last start with all of them
+#pragma unroll 1
+                    for (int s = (a0 + LCH) * RT_N_SUB; s < S; s++)
+                        slot_step(std::integral_constant<int, LCH>{}, s);
+                }
+                // ---- the walk has reached the end of the record: the rows of the chunk ----
+#pragma unroll
+                for (int i = 0; i < LCH; i++) {
+                    if (a0 + i < L) {
+                        double Iv[VEC];
+                        finish(acc[i], wnan >> (i * VEC), f0[i], kb, Iv);
+                        stage_row(i, L - 1 - (a0 + i), Iv, kb);
+                    }
+                }
+                __builtin_amdgcn_wave_barrier();
+#pragma unroll 1
+                for (int i = 0; i < LCH && a0 + i < L; i++)
+                    flush_row(i, L - 1 - (a0 + i), kb);
+                __builtin_amdgcn_wave_barrier();
+            }
+        }
+    }
+
+    // ---- the codes: -1 of the state, else -2 over -3 (Helper.h:588-593: negative wins); a failing ray is reported once ----
+    if (have) {
+#pragma unroll 1
+        for (int jb = 0; jb < L; jb++) {
+            const unsigned bit = 1u << jb;
+            Q->out.err[(size_t) jb * blk_rays + ridx] = (e1m & bit) ? -1 : ((negm & bit) ? -2 : ((nanm & bit) ? -3 : 0));
+        }
+    }
+    const unsigned only_nan = nanm & ~negm;
+    const unsigned code     = (e1m ? 1u << 1 : 0u) | (negm ? 1u << 2 : 0u) | (only_nan ? 1u << 3 : 0u);
+    if (code)
+        report_failure(code);
+}
+
+// The shell of rt_spec_kernel: one work-group of FREQ_WG_WAVES waves per CU, tiles from the eight sharded counters, one
+// tile per fetch; LDS, all dynamic: the two exponent tables, then [64][XS_ROW] staging doubles per wave.
+template <bool EMIS, bool BACKWARD>
+__global__ void __launch_bounds__(FREQ_WG_WAVES * 64, EMIS ? FREQ_WAVES : FREQ_WAVES_SEED) rt_spec_scan_kernel(const SpecScanKArg A)
+{
+    extern __shared__ __align__(16) unsigned char spec_scan_lds[];
+    const FreqHot &H = A.hot;
+    double *exp2_tab = reinterpret_cast<double *>(spec_scan_lds);
+    double *stage    = exp2_tab + 2 * EXP_TAB + (size_t) (unsigned) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6)) * (size_t) (WAVE * XS_ROW);
+    RT_FILL_EXP_TABLES(exp2_tab)
+    __syncthreads();
+    const int lane             = lane_id();
+    const unsigned n_tiles_run = H.tile_end - H.tile_begin;
+    unsigned shard = blockIdx.x & 7u, tried = 0;
+    for (;;) {
+        unsigned t = 0;
+        if (lane == 0)
+            t = atomicAdd(&H.ctl->next_tile_f[H.freq_id][shard][0], 1u);
+        t = (unsigned) __builtin_amdgcn_readfirstlane((int) t);
+        if (t >= (n_tiles_run + 7u - shard) / 8u) { // this shard is empty: on to the next one, until all eight have been seen empty
+            if (++tried == 8)
+                break;
+            shard = (shard + 1) & 7u;
+            continue;
+        }
+        const unsigned tile = H.tile_begin + t * 8u + shard;
+        // the cold half and the scan block of the argument block, the flag word and the lane number opaque per tile
+        ColdPtr C     = (ColdPtr) ((const RT_CONST_AS char *) __builtin_amdgcn_kernarg_segment_ptr() + offsetof(SpecScanKArg, cold));
+        SpecScanPtr Q = (SpecScanPtr) ((const RT_CONST_AS char *) __builtin_amdgcn_kernarg_segment_ptr() + offsetof(SpecScanKArg, scan));
+        asm volatile("" : "+s"(C), "+s"(Q));
+        unsigned hflags = H.flags;
+        int lane_t      = lane;
+        asm volatile("" : "+s"(hflags), "+v"(lane_t));
+        spec_scan_tile<EMIS, BACKWARD>(H, hflags, C, Q, exp2_tab, stage, tile, lane_t);
+    }
+}
+
+} // namespace rt
