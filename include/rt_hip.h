@@ -284,7 +284,8 @@ typedef struct rt_hip_run_facts {
  * its grid.  key_s6 / key_emis / key_excl pick the instance of the second pass.
  * pass_*: the second pass this run takes (pass_kind 0 frequency, 1 spectra, 2 step, 3 step of a seed set, 4 path
  * tracer: all zero, 5 step of a length scan, 6 step of a length scan with scan seeds (scan_on, n_seed > 0: one record per
- * seed and length), 12 length spectra (spectra_on = 2); pass_lds above lds_limit: the run is refused); for a one-launch run the frequency (step) phase of that launch. */
+ * seed and length), 12 length spectra (spectra_on = 2), 13 / 14 spectra mode / length spectra with spectra seeds (spectra_on = 1 / 2
+ * with n_seed > 0); pass_lds above lds_limit: the run is refused); for a one-launch run the frequency (step) phase of that launch. */
 typedef struct rt_hip_run_shape {
     unsigned size;
     int kind, lds_tab;
@@ -385,11 +386,46 @@ double *rt_hip_plan_spectra_ptr(rt_hip_plan *plan);
  *   stride K), ray2 [n_rays], err [n_rays], any pointer may be NULL.  On the device the rows of all lengths are one
  *   allocation, length-major (Iv [N-1][n_rays][K], ray2 and err [N-1][n_rays]); the pointers are valid until the next run or
  *   a change of the ray set.  The allocation is (N-1) n_rays K 8 bytes: a run that cannot have it fails with RT_ERR_NOMEM.
- * Not built: a chunked host-pointer loop like rt_hip_calc_rays, seed sets per length, the multi-device arms, the C++
- *   adapter, the one-launch form. */
+ * Not built: a chunked host-pointer loop like rt_hip_calc_rays, the multi-device arms, the C++ adapter, the one-launch form.
+ *   (Several seed beams per length: rt_hip_plan_set_spectra_seeds, below.) */
 int rt_hip_plan_enable_length_spectra(rt_hip_plan *plan, int on);
 int rt_hip_plan_fetch_length_spectra(rt_hip_plan *plan, int n, double *Iv, rt_ray *ray2, int32_t *err);
 int rt_hip_plan_length_spectra_ptrs(rt_hip_plan *plan, int n, double **Iv_dev, rt_ray **ray2_dev, int32_t **err_dev);
+
+/* Spectra seeds: RayTrace::calc_ray under SEVERAL seed beams from one march -- the per-ray side of what rt_hip_plan_set_seeds,
+ * _set_scan_seeds and _set_suffix_seeds do for the summed step records.  Neither the march record nor the boundary states hold
+ * anything of the seed; it enters as Iv_s[k] = (f0_s f_s[4][k]) exp(gl[k]) only, so one march, one walk over the record and one
+ * exponential per row serve every seed (rt_spec_seeds.hip in spectra mode, rt_spec_scan_seeds.hip in length spectra).
+ * set_spectra_seeds installs seeds[0 .. n_seed), 1 <= n_seed <= RT_N_SEED_MAX, each validated as rt_hip_plan_create
+ *   validates its seed, on a plan created WITH a seed (either method) whose spectra mode or length spectra are on.  The
+ *   creation seed is not among them (pass it again if its rows are wanted); gain-only mode, method, scale and tables stay as
+ *   created; on a forward ray grid the seeds' factor tables are built as for a set.  RT_ERR_ARG, each with its own text: a
+ *   NULL plan, a plan created without a seed (an emission plan: per-ray spectra with ASE seeds are not built), neither of
+ *   the two modes on, more than RT_N_SEED_MAX seeds, invalid seeds; a rejected call leaves the installed seeds as they
+ *   were.  n_seed = 0 removes the seeds and leaves the plain mode of the creation seed, bit for bit (these passes have no
+ *   atomics on data).  rt_hip_plan_enable_spectra(0) and rt_hip_plan_enable_length_spectra(0) drop the seeds;
+ *   rt_hip_plan_update_gain / _dev keep them.  While they are installed one of the two modes is on, so every switch and
+ *   installer that refuses that mode refuses as before.
+ * Outputs, seed-major in the one allocation of the mode: spectra mode Iv [n_seed][n_rays][K], err [n_seed][n_rays], ray2
+ *   [n_rays]; length spectra Iv [n_seed][N-1][n_rays][K], err [n_seed][N-1][n_rays], ray2 [N-1][n_rays].  Error -1 and the exit
+ *   ray do not depend on the seed.  Block 0 is seed 0: rt_hip_plan_fetch_spectra, _spectra_ptr, _fetch_length_spectra and
+ *   _length_spectra_ptrs serve it unchanged.  A run that cannot have the allocation fails as the mode does (RT_ERR_NOMEM).
+ *   Rows follow the single-seed modes: error -1 gives zeros and ray2 = 0 under every seed; a ray that fails -2 / -3 under
+ *   seed s carries that code in err[s] only, -2 wins over -3; a row that is all zero on the CPU is all zero here.  Every
+ *   Iv_s is the double the spectra (length-spectra) plan CREATED with seed s computes.
+ * rt_hip_plan_fetch reports the OR of the codes over all (seed, ray, n), every failing ray once (more than RT_N_FAILED_MAX:
+ *   the first of them in list order); err[s] holds seed s's codes ray by ray.  There is no checking repeat.
+ * fetch_seed_spectra / seed_spectra_ptrs: s = 0 .. n_seed - 1 of the last spectra-mode run with seeds;
+ * fetch_seed_length_spectra / seed_length_spectra_ptrs: likewise with n = 2 .. N of the last length-spectra run with seeds.
+ *   Anything else is RT_ERR_ARG; any pointer may be NULL; device pointers are valid until the next run or a change of the
+ *   ray set.
+ * Not built: emission plans (the ASE spectrum plus seeded spectra), a chunked host-pointer loop, the multi-device arms, the
+ *   C++ adapter, the one-launch form. */
+int rt_hip_plan_set_spectra_seeds(rt_hip_plan *plan, int n_seed, const rt_seed *seeds);
+int rt_hip_plan_fetch_seed_spectra(rt_hip_plan *plan, int s, double *Iv, rt_ray *ray2, int32_t *err);
+int rt_hip_plan_seed_spectra_ptrs(rt_hip_plan *plan, int s, double **Iv_dev, rt_ray **ray2_dev, int32_t **err_dev);
+int rt_hip_plan_fetch_seed_length_spectra(rt_hip_plan *plan, int s, int n, double *Iv, rt_ray *ray2, int32_t *err);
+int rt_hip_plan_seed_length_spectra_ptrs(rt_hip_plan *plan, int s, int n, double **Iv_dev, rt_ray **ray2_dev, int32_t **err_dev);
 
 /* Host-pointer batched form of RayTrace::calc_ray: n independent calls in one.  rays and ray2 are [n][4] doubles
  * (x, y, a, b) as calc_ray takes and returns them; the coordinates are rounded to float exactly as calc_ray rounds

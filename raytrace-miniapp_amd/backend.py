@@ -166,6 +166,7 @@ class Plan:
     _ring = 0                   # runs of the timing ring (set_timing_ring)
     _scan = False               # the length scan or the suffix scan is on (enable_length_scan, enable_suffix_scan)
     _n_seed = 0                 # seeds of the set (set_seeds)
+    _n_spec_seed = 0            # seeds of spectra mode or of length spectra (set_spectra_seeds)
     _n_scan_seed = 0            # seeds of the length scan or of the suffix scan (set_scan_seeds, set_suffix_seeds)
     _n_ase_seed = 0             # ASE seeds (set_ase_seeds)
     _n_scan_ase_seed = 0        # ASE seeds of the length scan or of the suffix scan (set_scan_ase_seeds, set_suffix_ase_seeds)
@@ -270,6 +271,8 @@ class Plan:
     def enable_spectra(self, on: bool = True) -> "Plan":
         """Spectra mode (RayTrace::calc_ray for every ray): a run produces Iv, ray2, err per ray instead of the image."""
         self.hl.check(self.hl.lib.rt_hip_plan_enable_spectra(self._h, int(on)), "rt_hip_plan_enable_spectra")
+        if self._spectra and not on:
+            self._n_spec_seed = 0   # (switching the mode off drops its seeds)
         self._spectra = bool(on)
         return self
 
@@ -304,6 +307,8 @@ class Plan:
         suffix_lengths(n) of a backward one.  A mode of its own: not together with spectra, step, path, a scan or seeds."""
         on = _on_arg("enable_length_spectra", on)
         self.hl.check(self.hl.lib.rt_hip_plan_enable_length_spectra(self._h, on), "rt_hip_plan_enable_length_spectra")
+        if self._length_spectra and not on:
+            self._n_spec_seed = 0   # (switching the mode off drops its seeds)
         self._length_spectra = bool(on)   # (fetch() reads it; spectra mode keeps its own flag: switching this off on a plan in spectra mode changes nothing)
         return self
 
@@ -343,6 +348,76 @@ class Plan:
 
         return dict(Iv=_view(iv, (L, nr, K), self.device), ray2=torch.as_tensor(_View(r2, (L, nr, 4), "<f4"), device=dev),
                     err=torch.as_tensor(_View(er, (L, nr), "<i4"), device=dev))
+
+    # -- spectra seeds: the per-ray outputs of several seed beams from one march --
+    def set_spectra_seeds(self, seeds) -> "Plan":
+        """Spectra seeds (include/rt_hip.h, rt_hip_plan_set_spectra_seeds): up to RT_N_SEED_MAX Seed records on a plan created
+        with a seed whose spectra mode or length spectra are on.  A run then leaves Iv and err once per seed, seed-major, from
+        one march (ray2 does not depend on the seed); the creation seed is not among them.  [] removes the seeds.  More
+        seeds than that, or anything that is not a Seed, is a ValueError raised here, before any native call."""
+        self._n_spec_seed = self._install_seeds("set_spectra_seeds", seeds, "spectra mode")
+        return self
+
+    def _spec_rows(self, name: str, *index) -> dict:
+        nr, K = self.n_rays, self.problem.beam.nv
+        Iv = np.empty((nr, K))
+        ray2 = np.zeros(nr, cabi.RAY_DTYPE)
+        err = np.zeros(nr, np.int32)
+        self.hl.check(getattr(self.hl.lib, name)(self._h, *index, cabi._dp(Iv), cabi.rays_ptr(ray2), err.ctypes.data_as(C.POINTER(C.c_int32))), name)
+        return dict(Iv=Iv, ray2=ray2, err=err)
+
+    def fetch_seed_spectra(self) -> list:
+        """[dict(Iv [n_rays][K], ray2 (RAY_DTYPE), err [n_rays] int32)] per spectra seed of the last spectra-mode run."""
+        return [self._spec_rows("rt_hip_plan_fetch_seed_spectra", s) for s in range(self._n_spec_seed)]
+
+    def fetch_seed_length_spectra(self) -> list:
+        """Per spectra seed of the last length-spectra run: [dict(n, Iv [n_rays][K], ray2 (RAY_DTYPE), err [n_rays] int32)]
+        for n = 2 .. N."""
+        return [[dict(n=n, **self._spec_rows("rt_hip_plan_fetch_seed_length_spectra", s, n)) for n in range(2, self.problem.N + 1)]
+                for s in range(self._n_spec_seed)]
+
+    def _spec_ptrs(self, name: str, *index) -> tuple:
+        iv, r2, er = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self.hl.check(getattr(self.hl.lib, name)(self._h, *(int(i) for i in index), C.byref(iv), C.byref(r2), C.byref(er)), name)
+        return int(iv.value or 0), int(r2.value or 0), int(er.value or 0)
+
+    def seed_spectra_ptrs(self, s: int) -> tuple:
+        """Device pointers (Iv, ray2, err) of the rows of spectra seed s of the last spectra-mode run with seeds."""
+        return self._spec_ptrs("rt_hip_plan_seed_spectra_ptrs", s)
+
+    def seed_length_spectra_ptrs(self, s: int, n: int) -> tuple:
+        """Device pointers (Iv, ray2, err) of the rows of (spectra seed s, length n) of the last length-spectra run with seeds."""
+        return self._spec_ptrs("rt_hip_plan_seed_length_spectra_ptrs", s, n)
+
+    def seed_spectra_tensors(self) -> dict:
+        """torch views of the last spectra-mode run with spectra seeds, seed-major and without a copy: Iv [n_seed][n_rays][K]
+        float64, err [n_seed][n_rays] int32, ray2 [n_rays][4] float32 (x, y, a, b: the same for every seed).  Valid until
+        the plan's next run or a change of its ray set."""
+        import torch
+
+        ns, nr, K = self._n_spec_seed, self.n_rays, self.problem.beam.nv
+        dev = torch.device("cuda", self.device)
+        if not nr or not ns:
+            return dict(Iv=torch.empty((ns, 0, K), dtype=torch.float64, device=dev), ray2=torch.empty((0, 4), dtype=torch.float32, device=dev),
+                        err=torch.empty((ns, 0), dtype=torch.int32, device=dev))
+        iv, r2, er = self.seed_spectra_ptrs(0)   # (block 0: the arrays are seed-major)
+        return dict(Iv=_view(iv, (ns, nr, K), self.device), ray2=torch.as_tensor(_View(r2, (nr, 4), "<f4"), device=dev),
+                    err=torch.as_tensor(_View(er, (ns, nr), "<i4"), device=dev))
+
+    def seed_length_spectra_tensors(self) -> dict:
+        """torch views of the last length-spectra run with spectra seeds, seed-major then length-major and without a copy:
+        Iv [n_seed][N-1][n_rays][K] float64, err [n_seed][N-1][n_rays] int32, ray2 [N-1][n_rays][4] float32; block n - 2 is
+        length n.  Valid until the plan's next run or a change of its ray set."""
+        import torch
+
+        ns, L, nr, K = self._n_spec_seed, self.problem.N - 1, self.n_rays, self.problem.beam.nv
+        dev = torch.device("cuda", self.device)
+        if not nr or not ns:
+            return dict(Iv=torch.empty((ns, L, 0, K), dtype=torch.float64, device=dev), ray2=torch.empty((L, 0, 4), dtype=torch.float32, device=dev),
+                        err=torch.empty((ns, L, 0), dtype=torch.int32, device=dev))
+        iv, r2, er = self.seed_length_spectra_ptrs(0, 2)   # (block (0, 0))
+        return dict(Iv=_view(iv, (ns, L, nr, K), self.device), ray2=torch.as_tensor(_View(r2, (L, nr, 4), "<f4"), device=dev),
+                    err=torch.as_tensor(_View(er, (ns, L, nr), "<i4"), device=dev))
 
     def enable_step(self, on: bool = True) -> "Plan":
         """Step mode (include/rt_hip.h): a run produces E_v, nf and I_ang -- the image cube reduced on the way, never
@@ -1162,6 +1237,46 @@ def calc_rays_lengths(problem: Problem, rays, exact: bool = False, device: int =
         plan.enable_length_spectra(True).run()
         out = plan.fetch(want_image=False)
         return dict(lengths=plan.fetch_length_spectra(), failure_code=out["failure_code"], failed_rays=out["failed_rays"], stats=out["stats"])
+
+
+def _rays_arg(rays):
+    rays = np.asarray(rays)
+    if rays.dtype != cabi.RAY_DTYPE:
+        rays = cabi.rays_from_array(np.asarray(rays, np.float64).reshape(-1, 4))
+    return rays
+
+
+def calc_rays_seeds(problem: Problem, seeds, rays, device: int = 0) -> dict:
+    """RayTrace::calc_ray for every ray under every seed beam of `seeds` (1 .. RT_N_SEED_MAX Seed records), from one march:
+    one call over a plan in spectra mode with spectra seeds (Plan.set_spectra_seeds).  `problem` must carry a seed (it makes
+    the plan gain-only; it is not among the seeds unless passed again); `rays` as calc_rays_lengths takes them.  Device
+    memory is n_seed n K 8 bytes: there is no chunking as in calc_rays.
+
+    Returns dict(seeds=[dict(Iv [n_rays][K], ray2 (RAY_DTYPE), err [n_rays] int32)], failure_code, failed_rays, stats)."""
+    seeds = _taken_seeds("calc_rays_seeds", seeds)   # (the refusals of the Python face, before a plan exists)
+    rays = _rays_arg(rays)
+    with Plan(problem, device=device) as plan:
+        plan.set_rays(rays)
+        plan.enable_spectra(True).set_spectra_seeds(seeds).run()
+        out = plan.fetch(want_image=False)
+        return dict(seeds=plan.fetch_seed_spectra(), failure_code=out["failure_code"], failed_rays=out["failed_rays"], stats=out["stats"])
+
+
+def calc_rays_seeds_lengths(problem: Problem, seeds, rays, device: int = 0) -> dict:
+    """calc_rays_seeds at EVERY plasma length n = 2 .. N, from one march: one call over a plan in length spectra mode with
+    spectra seeds.  The problem's method decides the sub-problems as in calc_rays_lengths.  Device memory is
+    n_seed (N - 1) n K 8 bytes.
+
+    Returns dict(seeds=[[dict(n, Iv, ray2, err)] for n = 2 .. N] per seed, failure_code, failed_rays, stats)."""
+    if problem.N < 3 or problem.N - 1 > cabi.RT_N_SCAN_MAX:
+        raise ValueError(f"calc_rays_seeds_lengths: N = {problem.N}; length spectra take 3 <= N <= RT_N_SCAN_MAX + 1 = {cabi.RT_N_SCAN_MAX + 1}")
+    seeds = _taken_seeds("calc_rays_seeds_lengths", seeds)
+    rays = _rays_arg(rays)
+    with Plan(problem, device=device) as plan:
+        plan.set_rays(rays)
+        plan.enable_length_spectra(True).set_spectra_seeds(seeds).run()
+        out = plan.fetch(want_image=False)
+        return dict(seeds=plan.fetch_seed_length_spectra(), failure_code=out["failure_code"], failed_rays=out["failed_rays"], stats=out["stats"])
 
 
 def calc_ray(problem: Problem, ray, method: int | None = None, device: int = 0):

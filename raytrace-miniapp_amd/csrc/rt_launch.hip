@@ -24,6 +24,8 @@
 
 #include "rt_step_rscan_seeds.hip" // the suffix scan of a seeded plan with the seeds of the scan: one record per (seed, run of the last n)
 #include "rt_spec_scan.hip" // length spectra: per-ray spectra, exit rays and codes at every length from one scan march
+#include "rt_spec_seeds.hip" // spectra mode with the seeds of rt_hip_plan_set_spectra_seeds: those outputs once per seed beam
+#include "rt_spec_scan_seeds.hip" // ... and length spectra with them: once per (seed beam, length)
 
 #include "rt_runtime.h"
 #include "rt_run_shape.h" // what a run looks like: the pure decision (facts + tuning -> shape) this file enqueues
@@ -158,6 +160,11 @@ void (*spec_scan_kernel(bool emis, bool backward))(const rt::SpecScanKArg)
     return emis ? (backward ? rt::rt_spec_scan_kernel<true, true> : rt::rt_spec_scan_kernel<true, false>)
                 : (backward ? rt::rt_spec_scan_kernel<false, true> : rt::rt_spec_scan_kernel<false, false>);
 }
+void (*spec_seeds_kernel(bool s6))(const rt::SpecSeedsKArg) { return s6 ? rt::rt_spec_seeds_kernel<6> : rt::rt_spec_seeds_kernel<0>; }
+void (*spec_scan_seeds_kernel(bool backward))(const rt::SpecScanSeedsKArg)
+{
+    return backward ? rt::rt_spec_scan_seeds_kernel<true> : rt::rt_spec_scan_seeds_kernel<false>;
+}
 
 // what a launch of the frequency pass covers: tiles [tile_begin, tile_end) on tile counter freq_id (a run is one launch
 // over all tiles; the range exists for experiments that split it), and the marks of the checking repeat (DevParams::safe)
@@ -230,6 +237,8 @@ RunFacts run_facts(const rt_hip_plan *p)
     f.n_iang          = p->n_iang;
     f.rays_per_pixel  = P.rays.nga * P.rays.ngb;
     f.n_seed          = p->scan_on ? p->n_scan_seed : p->n_seed; // (a set and the seeds of a scan exclude each other)
+    if (p->n_spec_seed > 0) // (the seeds of the two spectra modes: neither a set nor the seeds of a scan is installed beside them)
+        f.n_seed = p->n_spec_seed;
     f.c_h3            = P.c_h3;
     f.march_prune     = p->march_prune;
     f.method          = P.method;
@@ -353,9 +362,9 @@ int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kin
     const RecordSet R      = record_set(f);
     const RecordKindRow &k = R.row();
     // (what of a one-work-group-per-CU pass does not fit, by kind; the frequency kernel's message, below, carries figures)
-    if (s.lds > f.lds_limit && kind == PASS_SPEC)
+    if (s.lds > f.lds_limit && (kind == PASS_SPEC || kind == PASS_SPEC_SEEDS))
         return fail_arg("spectra kernel: the staging rows do not fit into the LDS of this device");
-    if (s.lds > f.lds_limit && kind == PASS_SPEC_SCAN)
+    if (s.lds > f.lds_limit && (kind == PASS_SPEC_SCAN || kind == PASS_SPEC_SCAN_SEEDS))
         return fail_arg("length spectra kernel: the staging rows do not fit into the LDS of this device");
     if (s.lds > f.lds_limit && kind == PASS_STEP)
         return fail_arg("step kernel: the E_v accumulator (nv doubles) does not fit into the LDS of this device");
@@ -388,6 +397,36 @@ int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kin
         a.hot.iang = nullptr;
         a.scan     = rt::SpecScanArg{ p->lspec, p->scan_bnd };
         return launch(p, spec_scan_kernel(f.use_emis, f.method == 1), s.grid, block, s.lds, stream, a);
+    }
+    if (kind == PASS_SPEC_SEEDS || kind == PASS_SPEC_SCAN_SEEDS) { // ... with the seeds of rt_hip_plan_set_spectra_seeds: once per seed beam
+        const char *who = kind == PASS_SPEC_SEEDS ? "spectra kernel with seeds" : "length spectra kernel with seeds";
+        auto fail       = [&](const char *what) { return fail_arg((std::string(who) + what).c_str()); };
+        if (f.n_seed < 1 || f.n_seed > RT_N_SEED_MAX || f.use_emis || !p->P.has_seed)
+            return fail(": not 1 .. RT_N_SEED_MAX seeds on a plan created with a seed");
+        const std::string tabs_who = std::string(who) + ": the factor tables of the seeds";
+        if (kind == PASS_SPEC_SEEDS) {
+            if (!p->spec[p->spec_sel].Iv)
+                return fail(": the outputs of this run were not allocated");
+            rt::SpecSeedsKArg a = pass_args<rt::SpecSeedsKArg>(fa);
+            a.hot.iang    = nullptr;
+            a.hot.seed_fk = nullptr;
+            a.set.n_seed  = f.n_seed;
+            a.set.out     = p->spec[p->spec_sel];
+            const int rc  = fill_seed_tabs(a.set.tabs, p, f.n_seed, p->P.rays.sf != nullptr, tabs_who.c_str());
+            return rc != RT_OK ? rc : launch(p, spec_seeds_kernel(f.s6()), s.grid, block, s.lds, stream, a);
+        }
+        if (!p->lspec.Iv || !p->scan_bnd)
+            return fail(": the outputs or the boundary states of this run were not allocated");
+        if (f.L < 2 || f.L > RT_N_SCAN_MAX)
+            return fail(": not 2 .. RT_N_SCAN_MAX lengths");
+        rt::SpecScanSeedsKArg a = pass_args<rt::SpecScanSeedsKArg>(fa);
+        a.hot.iang    = nullptr;
+        a.hot.seed_fk = nullptr;
+        a.set.n_seed  = f.n_seed;
+        a.set.out     = p->lspec;
+        a.set.bnd     = p->scan_bnd;
+        const int rc  = fill_seed_tabs(a.set.tabs, p, f.n_seed, p->P.rays.sf != nullptr, tabs_who.c_str());
+        return rc != RT_OK ? rc : launch(p, spec_scan_seeds_kernel(f.method == 1), s.grid, block, s.lds, stream, a);
     }
     if (kind == PASS_STEP) {
         rt::StepKArg a = pass_args<rt::StepKArg>(fa);
@@ -624,13 +663,16 @@ static int ensure_buffers(rt_hip_plan *p, const RunShape &s, hipStream_t stream)
     }
     if (p->spectra_on) {
         // the buffers of this run's set, kept while they are large enough (no zeroing: the kernel writes every element)
+        // (with the seeds of rt_hip_plan_set_spectra_seeds: one block of rows per seed, Iv [n_seed][n_rays][K] and err
+        // [n_seed][n_rays] with the strides of THIS run's ray count; ray2 [n_rays] serves every seed)
         rt::SpecOut &o = p->spec[p->spec_sel];
-        if (p->spec_rays[p->spec_sel] < (size_t) p->n_rays || !o.Iv) {
+        const size_t rows = (size_t) p->n_rays * (size_t) (p->n_spec_seed > 1 ? p->n_spec_seed : 1);
+        if (p->spec_rays[p->spec_sel] < rows || !o.Iv) {
             plan_quiesce(p);
             (void) hipFree(o.Iv);
             o = {};
             p->spec_rays[p->spec_sel] = 0;
-            const size_t n = (size_t) p->n_rays, iv_bytes = align_up(n * (size_t) p->P.K * sizeof(double) + 16, 256);
+            const size_t n = rows, iv_bytes = align_up(n * (size_t) p->P.K * sizeof(double) + 16, 256);
             unsigned char *b = nullptr;
             HIP_TRY(dev_malloc((void **) &b, iv_bytes + align_up(n * sizeof(rt_ray) + 16, 256) + n * sizeof(int32_t) + 16));
             o.Iv   = reinterpret_cast<double *>(b);
@@ -642,9 +684,10 @@ static int ensure_buffers(rt_hip_plan *p, const RunShape &s, hipStream_t stream)
     if (p->lspec_on) {
         // Iv [L][n][K] | ray2 [L][n] | err [L][n] in one allocation from the pool, kept while it is large enough (no zeroing:
         // the kernel writes every element); a run that cannot have it fails with RT_ERR_NOMEM
-        const size_t n = (size_t) p->n_rays, Lr = (size_t) p->P.L;
-        const size_t iv_bytes = align_up(Lr * n * (size_t) p->P.K * sizeof(double) + 16, 256), r2_bytes = align_up(Lr * n * sizeof(rt_ray) + 16, 256);
-        const size_t need_ls  = iv_bytes + r2_bytes + Lr * n * sizeof(int32_t) + 16;
+        // (with the seeds of rt_hip_plan_set_spectra_seeds: Iv [n_seed][L][n][K] and err [n_seed][L][n], seed-major; ray2 [L][n])
+        const size_t n = (size_t) p->n_rays, Lr = (size_t) p->P.L, Lb = Lr * (size_t) (p->n_spec_seed > 1 ? p->n_spec_seed : 1);
+        const size_t iv_bytes = align_up(Lb * n * (size_t) p->P.K * sizeof(double) + 16, 256), r2_bytes = align_up(Lr * n * sizeof(rt_ray) + 16, 256);
+        const size_t need_ls  = iv_bytes + r2_bytes + Lb * n * sizeof(int32_t) + 16;
         if (need_ls > p->lspec_bytes || !p->lspec_dev) {
             plan_quiesce(p);
             pool_free(p->device, p->lspec_dev);
@@ -765,7 +808,7 @@ static int launch_second(rt_hip_plan *p, const RunFacts &f, const Tuning &t, con
         }
         return RT_OK;
     }
-    if (kind != PASS_SPEC && kind != PASS_SPEC_SCAN && (f.debug & 1u)) // (profiling: the march alone)
+    if (!spectra_pass(kind) && (f.debug & 1u)) // (profiling: the march alone)
         return RT_OK;
     return launch_pass(p, f, t, kind, stream);
 }

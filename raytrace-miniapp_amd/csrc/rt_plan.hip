@@ -593,7 +593,7 @@ int rtr::plan_build_seedset_tabs(rt_hip_plan *p)
         p->seedset_sin[s] = nullptr;
     }
     const rt::DevRays &R = p->P.rays;
-    const int n_set = p->n_seed > 0 ? p->n_seed : p->n_scan_seed; // (a seed set, or the seeds of a scan: never both)
+    const int n_set = p->n_seed > 0 ? p->n_seed : p->n_scan_seed > 0 ? p->n_scan_seed : p->n_spec_seed; // (a seed set, the seeds of a scan or those of the spectra modes: never two of them)
     // (R.sf: a ray grid, a seeded plan, the forward method; ASE seeds on an emission plan, which has no creation seed and
     // hence no R.sf: the same grid and method)
     // (... and the ASE seeds of a scan, which is forward by construction)
@@ -853,6 +853,12 @@ int rt_hip_plan_set_debug(rt_hip_plan *p, unsigned bits)
     return RT_OK;
 }
 
+} // extern "C"
+// (below, with the installers: the seeds of a set, of a scan or of the spectra modes into the plan; n_seed = 0 removes them)
+enum SeedsOwner { SEEDS_OF_SET = 0, SEEDS_OF_SCAN = 1, SEEDS_OF_SPECTRA = 2 };
+static int seeds_install(rt_hip_plan *p, int n_seed, const rt_seed *seeds, SeedsOwner owner);
+extern "C" {
+
 int rt_hip_plan_enable_path(rt_hip_plan *p, int on)
 {
     if (!p)
@@ -901,6 +907,11 @@ int rt_hip_plan_enable_spectra(rt_hip_plan *p, int on)
                                        : "rt_hip_plan_enable_spectra: the length scan is on (step mode only)");
     if (on && p->lspec_on)
         return fail_arg("rt_hip_plan_enable_spectra: length spectra are on (a mode of their own: rt_hip_plan_enable_length_spectra switches them off)");
+    if (!on && p->spectra_on && p->n_spec_seed > 0) { // the seeds of rt_hip_plan_set_spectra_seeds exist only while the mode is on
+        const int rc = seeds_install(p, 0, nullptr, SEEDS_OF_SPECTRA);
+        if (rc != RT_OK)
+            return rc;
+    }
     p->spectra_on = on != 0;
     return RT_OK;
 }
@@ -925,6 +936,52 @@ int rt_hip_plan_fetch_spectra(rt_hip_plan *p, double *Iv, rt_ray *ray2, int32_t 
 }
 
 double *rt_hip_plan_spectra_ptr(rt_hip_plan *p) { return p && p->ran && p->last_spectra && !p->last_lspec ? p->spec[p->spec_last].Iv : nullptr; }
+
+// The rows of seed s of the last spectra run with the seeds of rt_hip_plan_set_spectra_seeds: block s of Iv and err (seed-major,
+// the stride the ray count of that run), the one ray2.  -1 behind the refusal.
+static int spec_seed_block(const rt_hip_plan *p, const char *who, int s)
+{
+    auto fail = [&](const char *what) { return (void) fail_arg((std::string(who) + what).c_str()), -1; };
+    if (!p || !p->ran || !p->last_spectra || p->last_lspec || p->last_spec_seed < 1 || !p->spec[p->spec_last].Iv)
+        return fail(": the last run was not a spectra run with spectra seeds");
+    if (s < 0 || s >= p->last_spec_seed)
+        return fail(": s must be 0 .. n_seed - 1 of the last run");
+    return s;
+}
+
+int rt_hip_plan_fetch_seed_spectra(rt_hip_plan *p, int s, double *Iv, rt_ray *ray2, int32_t *err)
+{
+    if (spec_seed_block(p, "rt_hip_plan_fetch_seed_spectra", s) < 0)
+        return RT_ERR_ARG;
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipStreamSynchronize(p->last_stream));
+    const size_t nr      = p->last_spec_rays;
+    const rt::SpecOut &o = p->spec[p->spec_last];
+    if (nr == 0)
+        return RT_OK;
+    if (Iv)
+        HIP_TRY(hipMemcpy(Iv, o.Iv + (size_t) s * nr * (size_t) p->P.K, nr * (size_t) p->P.K * sizeof(double), hipMemcpyDeviceToHost));
+    if (ray2)
+        HIP_TRY(hipMemcpy(ray2, o.ray2, nr * sizeof(rt_ray), hipMemcpyDeviceToHost));
+    if (err)
+        HIP_TRY(hipMemcpy(err, o.err + (size_t) s * nr, nr * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_hip_plan_seed_spectra_ptrs(rt_hip_plan *p, int s, double **Iv_dev, rt_ray **ray2_dev, int32_t **err_dev)
+{
+    if (spec_seed_block(p, "rt_hip_plan_seed_spectra_ptrs", s) < 0)
+        return RT_ERR_ARG;
+    const size_t nr      = p->last_spec_rays;
+    const rt::SpecOut &o = p->spec[p->spec_last];
+    if (Iv_dev)
+        *Iv_dev = o.Iv + (size_t) s * nr * (size_t) p->P.K;
+    if (ray2_dev)
+        *ray2_dev = o.ray2;
+    if (err_dev)
+        *err_dev = o.err + (size_t) s * nr;
+    return RT_OK;
+}
 
 // Length spectra (include/rt_hip.h): a mode of its own beside spectra mode and the scans.  The switch owns the boundary
 // states of the march while it is on, as scan_switch does for a scan; the method of the plan says prefix or suffix.
@@ -970,6 +1027,8 @@ int rt_hip_plan_enable_length_spectra(rt_hip_plan *p, int on)
         p->lspec       = {};
         if (p->last_lspec) // (its rows are gone: the accessors say so, rt_hip_plan_fetch keeps the report and the counters)
             p->lspec_rays = 0;
+        if (p->n_spec_seed > 0) // ... and so do the seeds of rt_hip_plan_set_spectra_seeds
+            return seeds_install(p, 0, nullptr, SEEDS_OF_SPECTRA);
     }
     return RT_OK;
 }
@@ -1016,6 +1075,54 @@ int rt_hip_plan_length_spectra_ptrs(rt_hip_plan *p, int n, double **Iv_dev, rt_r
         *ray2_dev = p->lspec.ray2 + (size_t) b * nr;
     if (err_dev)
         *err_dev = p->lspec.err + (size_t) b * nr;
+    return RT_OK;
+}
+
+// ... with the seeds of rt_hip_plan_set_spectra_seeds: block (s, n) = s L + n - 2 of Iv and err, block n - 2 of ray2
+static int lspec_seed_block(const rt_hip_plan *p, const char *who, int s, int n)
+{
+    const int b = lspec_block(p, who, n);
+    if (b < 0)
+        return -1;
+    auto fail = [&](const char *what) { return (void) fail_arg((std::string(who) + what).c_str()), -1; };
+    if (p->last_spec_seed < 1)
+        return fail(": the last run carried no spectra seeds");
+    if (s < 0 || s >= p->last_spec_seed)
+        return fail(": s must be 0 .. n_seed - 1 of the last run");
+    return s * p->lspec_L + b;
+}
+
+int rt_hip_plan_fetch_seed_length_spectra(rt_hip_plan *p, int s, int n, double *Iv, rt_ray *ray2, int32_t *err)
+{
+    const int sb = lspec_seed_block(p, "rt_hip_plan_fetch_seed_length_spectra", s, n);
+    if (sb < 0)
+        return RT_ERR_ARG;
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipStreamSynchronize(p->last_stream));
+    const size_t nr = p->lspec_rays;
+    if (nr == 0)
+        return RT_OK;
+    if (Iv)
+        HIP_TRY(hipMemcpy(Iv, p->lspec.Iv + (size_t) sb * nr * (size_t) p->P.K, nr * (size_t) p->P.K * sizeof(double), hipMemcpyDeviceToHost));
+    if (ray2)
+        HIP_TRY(hipMemcpy(ray2, p->lspec.ray2 + (size_t) (n - 2) * nr, nr * sizeof(rt_ray), hipMemcpyDeviceToHost));
+    if (err)
+        HIP_TRY(hipMemcpy(err, p->lspec.err + (size_t) sb * nr, nr * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_hip_plan_seed_length_spectra_ptrs(rt_hip_plan *p, int s, int n, double **Iv_dev, rt_ray **ray2_dev, int32_t **err_dev)
+{
+    const int sb = lspec_seed_block(p, "rt_hip_plan_seed_length_spectra_ptrs", s, n);
+    if (sb < 0)
+        return RT_ERR_ARG;
+    const size_t nr = p->lspec_rays;
+    if (Iv_dev)
+        *Iv_dev = p->lspec.Iv + (size_t) sb * nr * (size_t) p->P.K;
+    if (ray2_dev)
+        *ray2_dev = p->lspec.ray2 + (size_t) (n - 2) * nr;
+    if (err_dev)
+        *err_dev = p->lspec.err + (size_t) sb * nr;
     return RT_OK;
 }
 
@@ -1250,6 +1357,8 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
     p->last_spectra = spectra;
     p->last_lspec  = lspec;
     p->lspec_first_done = false;
+    p->last_spec_seed   = spectra ? p->n_spec_seed : 0;
+    p->last_spec_rays   = (size_t) p->n_rays;
     if (lspec) {
         p->lspec_rays = (size_t) p->n_rays;
         p->lspec_L    = p->P.L;
@@ -1294,12 +1403,15 @@ static int plan_report_first_failed(rt_hip_plan *p)
 
 // ... after a length-spectra run the codes err [L][n] say which rays fail, under any n and with any code (error -1
 // included: the rows are the report, nothing was deposited)
+// (with the seeds of rt_hip_plan_set_spectra_seeds: err [n_seed][L][n], and after a spectra-mode run with them err [n_seed][n])
 static int lspec_report_first_failed(rt_hip_plan *p)
 {
-    const size_t n = p->lspec_rays, L = (size_t) p->lspec_L;
+    const size_t nb = (size_t) (p->last_spec_seed > 1 ? p->last_spec_seed : 1);
+    const size_t n  = p->last_lspec ? p->lspec_rays : p->last_spec_rays, L = (p->last_lspec ? (size_t) p->lspec_L : 1) * nb;
+    const int32_t *err_dev = p->last_lspec ? p->lspec.err : p->spec[p->spec_last].err;
     std::vector<int32_t> err(n * L);
     if (n * L)
-        HIP_TRY(hipMemcpy(err.data(), p->lspec.err, n * L * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(err.data(), err_dev, n * L * sizeof(int32_t), hipMemcpyDeviceToHost));
     std::vector<unsigned char> bad(n, 0);
     for (size_t j = 0; j < L; j++)
         for (size_t t = 0; t < n; t++)
@@ -1375,7 +1487,8 @@ static int plan_settle(rt_hip_plan *p, rt::DevCtl &c, bool &staged)
         }
     }
     // length spectra: no repeat (nothing was deposited); more failing rays than the report holds: the first in list order
-    if (p->last_lspec && c.n_failed > RT_N_FAILED_MAX && !p->lspec_first_done) {
+    // (a spectra-mode run with spectra seeds takes the same rule: a ray that fails under either seed is reported once)
+    if ((p->last_lspec || (p->last_spectra && p->last_spec_seed > 0)) && c.n_failed > RT_N_FAILED_MAX && !p->lspec_first_done) {
         const int rf = lspec_report_first_failed(p);
         if (rf != RT_OK)
             return rf;
@@ -1702,8 +1815,8 @@ static int seeds_validate(const rt_hip_plan *p, const char *who, int n_seed, con
 }
 
 // Settles the last run, packs the tables of the seeds into one device block and makes them the plan's seed set
-// (of_scan: the seeds of its scan); n_seed = 0 removes them.
-static int seeds_install(rt_hip_plan *p, int n_seed, const rt_seed *seeds, bool of_scan)
+// (owner: a set, the seeds of its scan, or those of its spectra modes); n_seed = 0 removes them.
+static int seeds_install(rt_hip_plan *p, int n_seed, const rt_seed *seeds, SeedsOwner owner)
 {
     const int Kp = p->P.Kp;
     HIP_TRY(hipSetDevice(p->device));
@@ -1739,8 +1852,9 @@ static int seeds_install(rt_hip_plan *p, int n_seed, const rt_seed *seeds, bool 
     }
     (void) hipFree(p->seedset_arena);
     p->seedset_arena = arena;
-    p->n_seed        = of_scan ? 0 : n_seed;
-    p->n_scan_seed   = of_scan ? n_seed : 0;
+    p->n_seed        = owner == SEEDS_OF_SET ? n_seed : 0;
+    p->n_scan_seed   = owner == SEEDS_OF_SCAN ? n_seed : 0;
+    p->n_spec_seed   = owner == SEEDS_OF_SPECTRA ? n_seed : 0;
     for (int s = 0; s < RT_N_SEED_MAX; s++) {
         p->seed_set[s] = rt::DevSeed{};
         if (s < n_seed) {
@@ -1757,7 +1871,7 @@ static int seeds_install(rt_hip_plan *p, int n_seed, const rt_seed *seeds, bool 
 
 // What an installer of seeds requires of the plan: its flavour -- an emission plan (the seeds are ASE seeds and bring their
 // scales) or a seeded one -- and its scans; and the words of its refusals that are its own.
-enum ScanNeed { SCANS_OFF, LENGTH_SCAN_ON, SUFFIX_SCAN_ON };
+enum ScanNeed { SCANS_OFF, LENGTH_SCAN_ON, SUFFIX_SCAN_ON, SPECTRA_ON };
 struct SeedsEntry {
     const char *who;
     bool emission;
@@ -1787,13 +1901,33 @@ static const SeedsEntry SET_SUFFIX_SEEDS = { "rt_hip_plan_set_suffix_seeds", fal
                                              ": the plan was created without a seed (an emission plan takes rt_hip_plan_set_suffix_ase_seeds)", nullptr,
                                              nullptr, nullptr, "rt_hip_plan_set_scan_seeds" };
 
-// The six rt_hip_plan_set_*seeds: the plan's flavour, its scans, the seeds' tables (before the scans where the scans must be
+// The seeds of the two spectra modes on a SEEDED plan (rt_hip_plan_set_spectra_seeds): spectra mode or length spectra must be
+// on; gain-only, the creation seed not among them, either method; rt_spec_seeds.hip and rt_spec_scan_seeds.hip
+static const SeedsEntry SET_SPECTRA_SEEDS = { "rt_hip_plan_set_spectra_seeds", false, SPECTRA_ON,
+                                              ": the plan was created without a seed (an emission plan: per-ray spectra with ASE seeds are not built)",
+                                              nullptr, "spectra seeds", nullptr };
+
+// The seven rt_hip_plan_set_*seeds: the plan's flavour, its scans, the seeds' tables (before the scans where the scans must be
 // off, as each entry point has always ordered them), the install, the scales.
 static int seeds_set(rt_hip_plan *p, const SeedsEntry &e, int n_seed, const rt_seed *seeds, const double *scales)
 {
     auto fail = [&](const std::string &what) { return fail_arg((e.who + what).c_str()); };
     if (!p)
         return fail(": NULL plan");
+    if (e.scan == SPECTRA_ON) { // the seeds of the per-ray modes: their own requirements, then the path of every installer
+        if (!p->P.has_seed)
+            return fail(e.with_seed);
+        if (!p->spectra_on && !p->lspec_on)
+            return fail(": neither spectra mode nor length spectra are on (rt_hip_plan_enable_spectra or rt_hip_plan_enable_length_spectra first)");
+        if (n_seed > RT_N_SEED_MAX)
+            return fail(": more than RT_N_SEED_MAX seeds");
+        const int rv = seeds_validate(p, e.who, n_seed, seeds);
+        if (rv != RT_OK)
+            return rv;
+        if (n_seed == 0 && p->n_spec_seed == 0) // (nothing to remove: the plan stays as it is)
+            return RT_OK;
+        return seeds_install(p, n_seed, seeds, SEEDS_OF_SPECTRA);
+    }
     if (p->lspec_on)
         return fail(": length spectra are on (they take the creation seed alone)");
     if (e.scan == SUFFIX_SCAN_ON && p->P.method != 1)
@@ -1811,7 +1945,7 @@ static int seeds_set(rt_hip_plan *p, const SeedsEntry &e, int n_seed, const rt_s
             return fail(": the " + scan + " scan is on (" + e.noun + " and a " + scan + " scan exclude each other)");
         if (n_seed > 0 && (p->path_on || p->spectra_on))
             return fail(std::string(": the path tracer or spectra mode is enabled (") + e.runs + " in step mode only)");
-        if (!e.emission && n_seed == 0 && p->n_scan_seed > 0) // (the seeds of a scan are rt_hip_plan_set_scan_seeds': there is no set to remove)
+        if (!e.emission && n_seed == 0 && (p->n_scan_seed > 0 || p->n_spec_seed > 0)) // (the seeds of a scan are rt_hip_plan_set_scan_seeds', those of spectra mode rt_hip_plan_set_spectra_seeds': there is no set to remove)
             return RT_OK;
     } else {
         if (e.scan == LENGTH_SCAN_ON && suffix_scan(p))
@@ -1827,7 +1961,7 @@ static int seeds_set(rt_hip_plan *p, const SeedsEntry &e, int n_seed, const rt_s
         if (rv != RT_OK)
             return rv;
     }
-    const int rc = seeds_install(p, n_seed, seeds, e.scan != SCANS_OFF);
+    const int rc = seeds_install(p, n_seed, seeds, e.scan != SCANS_OFF ? SEEDS_OF_SCAN : SEEDS_OF_SET);
     if (rc != RT_OK || !e.emission)
         return rc;
     for (int s = 0; s < RT_N_SEED_MAX; s++)
@@ -1853,6 +1987,7 @@ int rt_hip_plan_set_suffix_ase_seeds(rt_hip_plan *p, int n_seed, const rt_seed *
 }
 
 int rt_hip_plan_set_suffix_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds) { return seeds_set(p, SET_SUFFIX_SEEDS, n_seed, seeds, nullptr); }
+int rt_hip_plan_set_spectra_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds) { return seeds_set(p, SET_SPECTRA_SEEDS, n_seed, seeds, nullptr); }
 
 int rt_hip_plan_kernel_ms(rt_hip_plan *p, float *ms)
 {

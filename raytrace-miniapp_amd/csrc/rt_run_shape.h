@@ -384,8 +384,18 @@ inline RecordSet record_set(const RunFacts &f)
 
 inline PassKind pass_kind(const RunFacts &f)
 {
-    return f.path_on ? PASS_PATH : f.spectra_on ? PASS_SPEC : f.length_spectra_on ? PASS_SPEC_SCAN : f.step_on ? record_set(f).pass_kind() : PASS_FREQ;
+    // (n_seed > 0 beside one of the two spectra modes: the seeds of rt_hip_plan_set_spectra_seeds -- a set and the seeds of a
+    // scan live in step mode only; the march is that of the single-seed mode, it knows nothing of a seed)
+    if (f.path_on)
+        return PASS_PATH;
+    if (f.spectra_on)
+        return f.n_seed > 0 ? PASS_SPEC_SEEDS : PASS_SPEC;
+    if (f.length_spectra_on)
+        return f.n_seed > 0 ? PASS_SPEC_SCAN_SEEDS : PASS_SPEC_SCAN;
+    return f.step_on ? record_set(f).pass_kind() : PASS_FREQ;
 }
+// the passes that leave per-ray spectra: one 16-wave work-group per CU with the staging rows of rt_spec.hip, no histogram
+inline bool spectra_pass(PassKind kind) { return kind == PASS_SPEC || kind == PASS_SPEC_SCAN || kind == PASS_SPEC_SEEDS || kind == PASS_SPEC_SCAN_SEEDS; }
 
 struct PassShape {
     int wg_waves = 0, nslot = 0;
@@ -439,7 +449,7 @@ inline PassShape pass_shape(PassKind kind, const RunFacts &f, const Tuning &t)
     if (kind == PASS_PATH)
         return s;
     // (one global atomic per ray on na*nb addresses serialises badly: the histogram stays in LDS)
-    s.in_lds = kind != PASS_SPEC && kind != PASS_SPEC_SCAN && f.n_iang * sizeof(double) <= 32 * 1024;
+    s.in_lds = !spectra_pass(kind) && f.n_iang * sizeof(double) <= 32 * 1024;
     if (kind == PASS_FREQ)
         freq_pass_shape(s, f, t);
     else {
@@ -453,12 +463,13 @@ inline PassShape pass_shape(PassKind kind, const RunFacts &f, const Tuning &t)
         // with scan seeds one of each per (seed, length), an emission plan with ASE seeds one of each for ASE and per seed -- with
         // the scan on, of those per length; a suffix scan one of each per length, with ASE seeds one per (record, length), with
         // scan seeds one per (seed, length))
-        const int n_rec      = kind == PASS_STEP || kind == PASS_SPEC || kind == PASS_SPEC_SCAN ? 1 : record_set(f).n_rec();
+        const int n_rec      = kind == PASS_STEP || spectra_pass(kind) ? 1 : record_set(f).n_rec();
         const int ang_stride = kind == PASS_STEP ? rt::step_ang_stride((int) f.n_iang) : rt::seeds_ang_stride((int) f.n_iang);
         auto step_lds        = [&](bool in_lds) { return rt::step_lds_doubles(in_lds, ang_stride, f.Kp, s.wg_waves, n_rec) * sizeof(double); };
         // (spectra: the staging rows of 16 waves and the exponent tables take 148 KB of LDS; length spectra cut the same rows
-        // into VEC frequencies of four lengths, rt_spec_scan.hip)
-        s.lds = kind == PASS_SPEC || kind == PASS_SPEC_SCAN ? ((size_t) 2 * rt::EXP_TAB + (size_t) s.wg_waves * rt::WAVE * rt::XS_ROW) * sizeof(double) : step_lds(s.in_lds);
+        // into VEC frequencies of four lengths, rt_spec_scan.hip; with the seeds of rt_hip_plan_set_spectra_seeds the seeds share
+        // the one staging of a wave, rt_spec_seeds.hip and rt_spec_scan_seeds.hip: the LDS is that of the single-seed pass)
+        s.lds = spectra_pass(kind) ? ((size_t) 2 * rt::EXP_TAB + (size_t) s.wg_waves * rt::WAVE * rt::XS_ROW) * sizeof(double) : step_lds(s.in_lds);
         if ((kind == PASS_SEEDS || kind == PASS_SCAN || kind == PASS_SCAN_SEEDS || kind == PASS_ASE_SEEDS || kind == PASS_SCAN_ASE_SEEDS ||
              kind == PASS_RSCAN || kind == PASS_RSCAN_ASE_SEEDS || kind == PASS_RSCAN_SEEDS) && s.in_lds &&
             s.lds > f.lds_limit) { // one histogram per record does not fit: global atomics
@@ -466,7 +477,7 @@ inline PassShape pass_shape(PassKind kind, const RunFacts &f, const Tuning &t)
             s.lds    = step_lds(false);
         }
         s.grid = one_wg_per_cu(f.n_tiles, (unsigned) s.wg_waves, f.cu_count);
-        if (kind != PASS_SPEC && kind != PASS_SPEC_SCAN && t.step_serial == 1) { // one wave, one work-group: sums in a fixed order (Tuning::step_serial)
+        if (!spectra_pass(kind) && t.step_serial == 1) { // one wave, one work-group: sums in a fixed order (Tuning::step_serial)
             s.wg_waves = 1;
             s.lds      = step_lds(s.in_lds);
             s.grid     = f.n_tiles ? 1u : 0u;

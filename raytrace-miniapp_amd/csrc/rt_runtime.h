@@ -7,7 +7,7 @@
 //   rt_raygrid.hip  a ray list that is really a tensor grid: recognition + bit-wise verification,
 //                   list-mode launch tangents and the probe of the host's libm
 //   rt_launch.hip   the kernels (rt_march.hip, rt_freq.hip, rt_path.hip, rt_spec.hip, rt_step.hip, rt_step_seeds.hip, rt_fused_step.hip,
-//                   rt_step_scan.hip, rt_step_scan_seeds.hip, rt_step_ase_seeds.hip, rt_spec_scan.hip) and how a run puts them on a queue:
+//                   rt_step_scan.hip, rt_step_scan_seeds.hip, rt_step_ase_seeds.hip, rt_spec_scan.hip, rt_spec_seeds.hip, rt_spec_scan_seeds.hip) and how a run puts them on a queue:
 //                   WHAT a run looks like -- tables in LDS or not, one launch or two, instance, grid, chunk, late zone, the
 //                   LDS layout of a one-launch run, the shape of the second pass -- is decided by pure functions of plain
 //                   numbers (rt_run_shape.h, included by rt_launch.hip alone: RunFacts from the plan + Tuning from the
@@ -96,6 +96,13 @@ struct rt_hip_plan {
     size_t lspec_bytes = 0;
     size_t lspec_rays  = 0;       // rays of the last length-spectra run (the block stride of the arrays)
     int lspec_L        = 0;       // ... and its lengths
+    // the seeds of the two spectra modes (rt_hip_plan_set_spectra_seeds): 1 .. RT_N_SEED_MAX seed beams whose per-ray outputs
+    // one march serves (rt_spec_seeds.hip, rt_spec_scan_seeds.hip).  They travel as a set's do (seed_set, seedset_arena, the
+    // factor tables on a forward ray grid) under a count of their own: n_seed and n_scan_seed stay 0 beside them, so every
+    // refusal that names a set or the seeds of a scan reads as it did.  Iv and err of a run are seed-major, block 0 seed 0.
+    int n_spec_seed    = 0;
+    int last_spec_seed = 0;       // ... of the last spectra or length-spectra run (0: the creation seed alone)
+    size_t last_spec_rays = 0;    // rays of the last spectra-mode run with seeds (the block stride of its arrays)
     // step mode (rt_hip_plan_enable_step): E_v and nf instead of the image cube.  One allocation, zeroed by the run's
     // zeroing launch: E_v [K] at its start, nf [nx * ny] behind it at a 256-byte boundary.
     bool step_on       = false;
