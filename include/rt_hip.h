@@ -285,7 +285,7 @@ typedef struct rt_hip_run_facts {
  * pass_*: the second pass this run takes (pass_kind 0 frequency, 1 spectra, 2 step, 3 step of a seed set, 4 path
  * tracer: all zero, 5 step of a length scan, 6 step of a length scan with scan seeds (scan_on, n_seed > 0: one record per
  * seed and length), 12 length spectra (spectra_on = 2), 13 / 14 spectra mode / length spectra with spectra seeds (spectra_on = 1 / 2
- * with n_seed > 0); pass_lds above lds_limit: the run is refused); for a one-launch run the frequency (step) phase of that launch. */
+ * with n_seed > 0), 15 spectra mode of an emission plan with ASE seeds (spectra_on = 1, use_emis, n_seed > 0); pass_lds above lds_limit: the run is refused); for a one-launch run the frequency (step) phase of that launch. */
 typedef struct rt_hip_run_shape {
     unsigned size;
     int kind, lds_tab;
@@ -400,7 +400,7 @@ int rt_hip_plan_length_spectra_ptrs(rt_hip_plan *plan, int n, double **Iv_dev, r
  *   validates its seed, on a plan created WITH a seed (either method) whose spectra mode or length spectra are on.  The
  *   creation seed is not among them (pass it again if its rows are wanted); gain-only mode, method, scale and tables stay as
  *   created; on a forward ray grid the seeds' factor tables are built as for a set.  RT_ERR_ARG, each with its own text: a
- *   NULL plan, a plan created without a seed (an emission plan: per-ray spectra with ASE seeds are not built), neither of
+ *   NULL plan, a plan created without a seed (an emission plan takes rt_hip_plan_set_spectra_ase_seeds), neither of
  *   the two modes on, more than RT_N_SEED_MAX seeds, invalid seeds; a rejected call leaves the installed seeds as they
  *   were.  n_seed = 0 removes the seeds and leaves the plain mode of the creation seed, bit for bit (these passes have no
  *   atomics on data).  rt_hip_plan_enable_spectra(0) and rt_hip_plan_enable_length_spectra(0) drop the seeds;
@@ -419,13 +419,43 @@ int rt_hip_plan_length_spectra_ptrs(rt_hip_plan *plan, int n, double **Iv_dev, r
  * fetch_seed_length_spectra / seed_length_spectra_ptrs: likewise with n = 2 .. N of the last length-spectra run with seeds.
  *   Anything else is RT_ERR_ARG; any pointer may be NULL; device pointers are valid until the next run or a change of the
  *   ray set.
- * Not built: emission plans (the ASE spectrum plus seeded spectra), a chunked host-pointer loop, the multi-device arms, the
- *   C++ adapter, the one-launch form. */
+ * Not built: a chunked host-pointer loop, the multi-device arms, the C++ adapter, the one-launch form.
+ *   (An emission plan -- the ASE spectrum plus seeded spectra: rt_hip_plan_set_spectra_ase_seeds, below.) */
 int rt_hip_plan_set_spectra_seeds(rt_hip_plan *plan, int n_seed, const rt_seed *seeds);
 int rt_hip_plan_fetch_seed_spectra(rt_hip_plan *plan, int s, double *Iv, rt_ray *ray2, int32_t *err);
 int rt_hip_plan_seed_spectra_ptrs(rt_hip_plan *plan, int s, double **Iv_dev, rt_ray **ray2_dev, int32_t **err_dev);
 int rt_hip_plan_fetch_seed_length_spectra(rt_hip_plan *plan, int s, int n, double *Iv, rt_ray *ray2, int32_t *err);
 int rt_hip_plan_seed_length_spectra_ptrs(rt_hip_plan *plan, int s, int n, double **Iv_dev, rt_ray **ray2_dev, int32_t **err_dev);
+
+/* Spectra mode with ASE seeds: RayTrace::calc_ray of an EMISSION problem and of the same problem under its seed beams from one
+ * march -- the per-ray side of what rt_hip_plan_set_ase_seeds does for the summed step record.  Only evl depends on use_emis,
+ * so the march record of an emission plan holds everything the gain-only pass of a seeded run of the same problem reads; one
+ * march and one pass (rt_spec_ase_seeds.hip) leave 1 + n_seed blocks of rows per ray.
+ * set_spectra_ase_seeds installs seeds[0 .. n_seed), 1 <= n_seed <= RT_N_SEED_MAX, each validated as rt_hip_plan_create
+ *   validates its seed, on an emission plan (created without a seed, tables with E0, either method) whose spectra mode is on.
+ *   There are no scales: calc_ray has none.  On a forward ray grid the seeds' factor tables are built as for a set.
+ *   RT_ERR_ARG, each with its own text: a NULL plan, a plan created with a seed (it takes rt_hip_plan_set_spectra_seeds),
+ *   tables without E0, spectra mode off, length spectra on (per-ray ASE seeds at every length are not built), more than
+ *   RT_N_SEED_MAX seeds, invalid seeds; a rejected call leaves the installed seeds as they were.  n_seed = 0 removes the seeds
+ *   and leaves plain spectra mode, bit for bit (the pass has no atomics on data).  rt_hip_plan_enable_spectra(0) drops the
+ *   seeds; rt_hip_plan_update_gain / _dev keep them.  While they are installed spectra mode is on, so every switch and
+ *   installer that refuses that mode refuses as before.
+ * Outputs, block-major in the one allocation of the mode: Iv [1 + n_seed][n_rays][K] (row stride K), err [1 + n_seed][n_rays],
+ *   ray2 [n_rays].  Block 0 is the plan's own ASE spectrum -- the row the plan leaves without seeds, bit for bit, exact
+ *   emission included --, so rt_hip_plan_fetch_spectra and _spectra_ptr serve it unchanged; block 1 + s is the row a
+ *   spectra-mode plan leaves of the same problem created with seed s (E0 present, unused), bit for bit.  The allocation is
+ *   (1 + n_seed) n_rays K 8 bytes: a run that cannot have it fails with RT_ERR_NOMEM.  Every element is written.  Error -1
+ *   and the exit ray do not depend on the block: a -1 ray has zeros and -1 in every block; -2 / -3 are per block, -2 wins.
+ *   A ray whose march sums are all zero has a row of zeros in block 0 and f0_s f_s[4][k] in block 1 + s.
+ * rt_hip_plan_fetch reports the OR of the codes over all blocks, every failing ray once (more than RT_N_FAILED_MAX: the first
+ *   of them in list order); err of block r holds its codes ray by ray.  There is no checking repeat.
+ * fetch_full_spectra / full_spectra_ptrs: r = 0 (ASE) .. n_seed (1 + s: seed s) of the last such run.  Anything else is
+ *   RT_ERR_ARG; any pointer may be NULL; device pointers are valid until the next run or a change of the ray set.
+ * Not built: length spectra with ASE seeds (refused, above), a chunked host-pointer loop, the multi-device arms, the C++
+ *   adapter, the one-launch form. */
+int rt_hip_plan_set_spectra_ase_seeds(rt_hip_plan *plan, int n_seed, const rt_seed *seeds);
+int rt_hip_plan_fetch_full_spectra(rt_hip_plan *plan, int r, double *Iv, rt_ray *ray2, int32_t *err);   /* r = 0: ASE, 1 + s: seed s */
+int rt_hip_plan_full_spectra_ptrs(rt_hip_plan *plan, int r, double **Iv_dev, rt_ray **ray2_dev, int32_t **err_dev);
 
 /* Host-pointer batched form of RayTrace::calc_ray: n independent calls in one.  rays and ray2 are [n][4] doubles
  * (x, y, a, b) as calc_ray takes and returns them; the coordinates are rounded to float exactly as calc_ray rounds

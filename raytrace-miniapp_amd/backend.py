@@ -167,6 +167,7 @@ class Plan:
     _scan = False               # the length scan or the suffix scan is on (enable_length_scan, enable_suffix_scan)
     _n_seed = 0                 # seeds of the set (set_seeds)
     _n_spec_seed = 0            # seeds of spectra mode or of length spectra (set_spectra_seeds)
+    _n_spec_ase_seed = 0        # ASE seeds of spectra mode (set_spectra_ase_seeds)
     _n_scan_seed = 0            # seeds of the length scan or of the suffix scan (set_scan_seeds, set_suffix_seeds)
     _n_ase_seed = 0             # ASE seeds (set_ase_seeds)
     _n_scan_ase_seed = 0        # ASE seeds of the length scan or of the suffix scan (set_scan_ase_seeds, set_suffix_ase_seeds)
@@ -273,6 +274,7 @@ class Plan:
         self.hl.check(self.hl.lib.rt_hip_plan_enable_spectra(self._h, int(on)), "rt_hip_plan_enable_spectra")
         if self._spectra and not on:
             self._n_spec_seed = 0   # (switching the mode off drops its seeds)
+            self._n_spec_ase_seed = 0
         self._spectra = bool(on)
         return self
 
@@ -418,6 +420,42 @@ class Plan:
         iv, r2, er = self.seed_length_spectra_ptrs(0, 2)   # (block (0, 0))
         return dict(Iv=_view(iv, (ns, L, nr, K), self.device), ray2=torch.as_tensor(_View(r2, (L, nr, 4), "<f4"), device=dev),
                     err=torch.as_tensor(_View(er, (ns, L, nr), "<i4"), device=dev))
+
+    # -- spectra mode with ASE seeds: the ASE rows and the seeded rows of an emission plan from one march --
+    def set_spectra_ase_seeds(self, seeds) -> "Plan":
+        """ASE seeds of spectra mode (include/rt_hip.h, rt_hip_plan_set_spectra_ase_seeds): up to RT_N_SEED_MAX Seed records on
+        an EMISSION plan (created without a seed, tables with E0) whose spectra mode is on.  A run then leaves, from one march,
+        the plan's own ASE rows (block 0) and per seed the rows of the same problem created with that seed (block 1 + s); ray2
+        does not depend on the block.  There are no scales: calc_ray has none.  [] removes the seeds.  More seeds than that,
+        or anything that is not a Seed, is a ValueError raised here, before any native call."""
+        self._n_spec_ase_seed = self._install_seeds("set_spectra_ase_seeds", seeds, "spectra mode")
+        return self
+
+    def fetch_full_spectra(self) -> dict:
+        """dict(ase=rows, seeds=[rows ...]) of the last spectra-mode run with ASE seeds; every rows is dict(Iv [n_rays][K],
+        ray2 (RAY_DTYPE), err [n_rays] int32)."""
+        return dict(ase=self._spec_rows("rt_hip_plan_fetch_full_spectra", 0),
+                    seeds=[self._spec_rows("rt_hip_plan_fetch_full_spectra", 1 + s) for s in range(self._n_spec_ase_seed)])
+
+    def full_spectra_ptrs(self, r: int) -> tuple:
+        """Device pointers (Iv, ray2, err) of block r of the last spectra-mode run with ASE seeds: r = 0 the ASE rows, 1 + s
+        those of seed s."""
+        return self._spec_ptrs("rt_hip_plan_full_spectra_ptrs", r)
+
+    def full_spectra_tensors(self) -> dict:
+        """torch views of the last spectra-mode run with ASE seeds, block-major and without a copy: Iv [1 + n_seed][n_rays][K]
+        float64, err [1 + n_seed][n_rays] int32, ray2 [n_rays][4] float32 (x, y, a, b: the same for every block); block 0 is
+        the ASE block.  Valid until the plan's next run or a change of its ray set."""
+        import torch
+
+        nb, nr, K = 1 + self._n_spec_ase_seed, self.n_rays, self.problem.beam.nv
+        dev = torch.device("cuda", self.device)
+        if not nr:
+            return dict(Iv=torch.empty((nb, 0, K), dtype=torch.float64, device=dev), ray2=torch.empty((0, 4), dtype=torch.float32, device=dev),
+                        err=torch.empty((nb, 0), dtype=torch.int32, device=dev))
+        iv, r2, er = self.full_spectra_ptrs(0)   # (block 0: the arrays are block-major)
+        return dict(Iv=_view(iv, (nb, nr, K), self.device), ray2=torch.as_tensor(_View(r2, (nr, 4), "<f4"), device=dev),
+                    err=torch.as_tensor(_View(er, (nb, nr), "<i4"), device=dev))
 
     def enable_step(self, on: bool = True) -> "Plan":
         """Step mode (include/rt_hip.h): a run produces E_v, nf and I_ang -- the image cube reduced on the way, never
@@ -1260,6 +1298,26 @@ def calc_rays_seeds(problem: Problem, seeds, rays, device: int = 0) -> dict:
         plan.enable_spectra(True).set_spectra_seeds(seeds).run()
         out = plan.fetch(want_image=False)
         return dict(seeds=plan.fetch_seed_spectra(), failure_code=out["failure_code"], failed_rays=out["failed_rays"], stats=out["stats"])
+
+
+def calc_rays_ase_seeds(problem: Problem, seeds, rays, exact: bool = False, device: int = 0) -> dict:
+    """RayTrace::calc_ray for every ray of an EMISSION problem and of the same problem under every seed beam of `seeds`
+    (1 .. RT_N_SEED_MAX Seed records), from one march: one call over a plan in spectra mode with ASE seeds
+    (Plan.set_spectra_ase_seeds).  `problem` must carry no seed and tables with E0; `rays` as calc_rays_lengths takes them;
+    `exact`: rt_hip_plan_set_exact_emission.  Device memory is (1 + n_seed) n K 8 bytes: there is no chunking as in calc_rays.
+
+    Returns dict(ase=dict(Iv [n_rays][K], ray2 (RAY_DTYPE), err [n_rays] int32), seeds=[dict ...], failure_code, failed_rays,
+    stats)."""
+    seeds = _taken_seeds("calc_rays_ase_seeds", seeds)   # (the refusals of the Python face, before a plan exists)
+    rays = _rays_arg(rays)
+    with Plan(problem, device=device) as plan:
+        plan.set_rays(rays)
+        if exact:
+            plan.set_exact_emission(True)
+        plan.enable_spectra(True).set_spectra_ase_seeds(seeds).run()
+        out = plan.fetch(want_image=False)
+        full = plan.fetch_full_spectra()
+        return dict(ase=full["ase"], seeds=full["seeds"], failure_code=out["failure_code"], failed_rays=out["failed_rays"], stats=out["stats"])
 
 
 def calc_rays_seeds_lengths(problem: Problem, seeds, rays, device: int = 0) -> dict:

@@ -26,6 +26,7 @@
 #include "rt_spec_scan.hip" // length spectra: per-ray spectra, exit rays and codes at every length from one scan march
 #include "rt_spec_seeds.hip" // spectra mode with the seeds of rt_hip_plan_set_spectra_seeds: those outputs once per seed beam
 #include "rt_spec_scan_seeds.hip" // ... and length spectra with them: once per (seed beam, length)
+#include "rt_spec_ase_seeds.hip" // spectra mode of an emission plan with the seeds of rt_hip_plan_set_spectra_ase_seeds: the ASE rows and a block per seed beam
 
 #include "rt_runtime.h"
 #include "rt_run_shape.h" // what a run looks like: the pure decision (facts + tuning -> shape) this file enqueues
@@ -161,6 +162,7 @@ void (*spec_scan_kernel(bool emis, bool backward))(const rt::SpecScanKArg)
                 : (backward ? rt::rt_spec_scan_kernel<false, true> : rt::rt_spec_scan_kernel<false, false>);
 }
 void (*spec_seeds_kernel(bool s6))(const rt::SpecSeedsKArg) { return s6 ? rt::rt_spec_seeds_kernel<6> : rt::rt_spec_seeds_kernel<0>; }
+void (*spec_ase_seeds_kernel(bool s6))(const rt::SpecSeedsKArg) { return s6 ? rt::rt_spec_ase_seeds_kernel<6> : rt::rt_spec_ase_seeds_kernel<0>; }
 void (*spec_scan_seeds_kernel(bool backward))(const rt::SpecScanSeedsKArg)
 {
     return backward ? rt::rt_spec_scan_seeds_kernel<true> : rt::rt_spec_scan_seeds_kernel<false>;
@@ -362,7 +364,7 @@ int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kin
     const RecordSet R      = record_set(f);
     const RecordKindRow &k = R.row();
     // (what of a one-work-group-per-CU pass does not fit, by kind; the frequency kernel's message, below, carries figures)
-    if (s.lds > f.lds_limit && (kind == PASS_SPEC || kind == PASS_SPEC_SEEDS))
+    if (s.lds > f.lds_limit && (kind == PASS_SPEC || kind == PASS_SPEC_SEEDS || kind == PASS_SPEC_ASE_SEEDS))
         return fail_arg("spectra kernel: the staging rows do not fit into the LDS of this device");
     if (s.lds > f.lds_limit && (kind == PASS_SPEC_SCAN || kind == PASS_SPEC_SCAN_SEEDS))
         return fail_arg("length spectra kernel: the staging rows do not fit into the LDS of this device");
@@ -427,6 +429,22 @@ int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kin
         a.set.bnd     = p->scan_bnd;
         const int rc  = fill_seed_tabs(a.set.tabs, p, f.n_seed, p->P.rays.sf != nullptr, tabs_who.c_str());
         return rc != RT_OK ? rc : launch(p, spec_scan_seeds_kernel(f.method == 1), s.grid, block, s.lds, stream, a);
+    }
+    if (kind == PASS_SPEC_ASE_SEEDS) { // spectra mode of an emission plan with the seeds of rt_hip_plan_set_spectra_ase_seeds: block 0 ASE, block 1 + s seed s
+        auto fail = [&](const char *what) { return fail_arg((std::string("spectra kernel with ASE seeds") + what).c_str()); };
+        if (f.n_seed < 1 || f.n_seed > RT_N_SEED_MAX || !f.use_emis || p->P.has_seed)
+            return fail(": not 1 .. RT_N_SEED_MAX seeds on an emission plan");
+        if (!p->spec[p->spec_sel].Iv)
+            return fail(": the outputs of this run were not allocated");
+        rt::SpecSeedsKArg a = pass_args<rt::SpecSeedsKArg>(fa);
+        a.hot.iang    = nullptr;
+        a.set.n_seed  = f.n_seed;
+        a.set.out     = p->spec[p->spec_sel];
+        // (an emission plan has no creation seed and hence no P.rays.sf: the seeds' factor tables serve a forward ray GRID
+        // only, and the ray set decides -- seeds_on_grid says the same of the step passes with ASE seeds)
+        const bool grid_tabs = p->P.rays.gx && !p->P.rays.list && p->P.method != 1 && p->seedset_sf[0] != nullptr;
+        const int rc = fill_seed_tabs(a.set.tabs, p, f.n_seed, grid_tabs, "spectra kernel with ASE seeds: the factor tables of the seeds");
+        return rc != RT_OK ? rc : launch(p, spec_ase_seeds_kernel(f.s6()), s.grid, block, s.lds, stream, a);
     }
     if (kind == PASS_STEP) {
         rt::StepKArg a = pass_args<rt::StepKArg>(fa);
@@ -666,7 +684,9 @@ static int ensure_buffers(rt_hip_plan *p, const RunShape &s, hipStream_t stream)
         // (with the seeds of rt_hip_plan_set_spectra_seeds: one block of rows per seed, Iv [n_seed][n_rays][K] and err
         // [n_seed][n_rays] with the strides of THIS run's ray count; ray2 [n_rays] serves every seed)
         rt::SpecOut &o = p->spec[p->spec_sel];
-        const size_t rows = (size_t) p->n_rays * (size_t) (p->n_spec_seed > 1 ? p->n_spec_seed : 1);
+        // (on an emission plan, the seeds of rt_hip_plan_set_spectra_ase_seeds: 1 + n_seed blocks, block 0 the ASE rows)
+        const size_t blocks = (size_t) p->n_spec_seed + (p->P.use_emis && p->n_spec_seed > 0 ? 1u : 0u);
+        const size_t rows = (size_t) p->n_rays * (blocks > 1 ? blocks : 1);
         if (p->spec_rays[p->spec_sel] < rows || !o.Iv) {
             plan_quiesce(p);
             (void) hipFree(o.Iv);

@@ -942,7 +942,7 @@ double *rt_hip_plan_spectra_ptr(rt_hip_plan *p) { return p && p->ran && p->last_
 static int spec_seed_block(const rt_hip_plan *p, const char *who, int s)
 {
     auto fail = [&](const char *what) { return (void) fail_arg((std::string(who) + what).c_str()), -1; };
-    if (!p || !p->ran || !p->last_spectra || p->last_lspec || p->last_spec_seed < 1 || !p->spec[p->spec_last].Iv)
+    if (!p || !p->ran || !p->last_spectra || p->last_lspec || p->last_spec_seed < 1 || p->last_spec_ase || !p->spec[p->spec_last].Iv)
         return fail(": the last run was not a spectra run with spectra seeds");
     if (s < 0 || s >= p->last_spec_seed)
         return fail(": s must be 0 .. n_seed - 1 of the last run");
@@ -980,6 +980,52 @@ int rt_hip_plan_seed_spectra_ptrs(rt_hip_plan *p, int s, double **Iv_dev, rt_ray
         *ray2_dev = o.ray2;
     if (err_dev)
         *err_dev = o.err + (size_t) s * nr;
+    return RT_OK;
+}
+
+// Block r of the last spectra run of an emission plan with the seeds of rt_hip_plan_set_spectra_ase_seeds: r = 0 the ASE rows,
+// r = 1 + s those of seed s (block-major, the stride the ray count of that run), the one ray2.  -1 behind the refusal.
+static int spec_full_block(const rt_hip_plan *p, const char *who, int r)
+{
+    auto fail = [&](const char *what) { return (void) fail_arg((std::string(who) + what).c_str()), -1; };
+    if (!p || !p->ran || !p->last_spectra || p->last_lspec || !p->last_spec_ase || p->last_spec_seed < 1 || !p->spec[p->spec_last].Iv)
+        return fail(": the last run was not a spectra run with ASE seeds");
+    if (r < 0 || r > p->last_spec_seed)
+        return fail(": r must be 0 .. n_seed of the last run");
+    return r;
+}
+
+int rt_hip_plan_fetch_full_spectra(rt_hip_plan *p, int r, double *Iv, rt_ray *ray2, int32_t *err)
+{
+    if (spec_full_block(p, "rt_hip_plan_fetch_full_spectra", r) < 0)
+        return RT_ERR_ARG;
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipStreamSynchronize(p->last_stream));
+    const size_t nr      = p->last_spec_rays;
+    const rt::SpecOut &o = p->spec[p->spec_last];
+    if (nr == 0)
+        return RT_OK;
+    if (Iv)
+        HIP_TRY(hipMemcpy(Iv, o.Iv + (size_t) r * nr * (size_t) p->P.K, nr * (size_t) p->P.K * sizeof(double), hipMemcpyDeviceToHost));
+    if (ray2)
+        HIP_TRY(hipMemcpy(ray2, o.ray2, nr * sizeof(rt_ray), hipMemcpyDeviceToHost));
+    if (err)
+        HIP_TRY(hipMemcpy(err, o.err + (size_t) r * nr, nr * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_hip_plan_full_spectra_ptrs(rt_hip_plan *p, int r, double **Iv_dev, rt_ray **ray2_dev, int32_t **err_dev)
+{
+    if (spec_full_block(p, "rt_hip_plan_full_spectra_ptrs", r) < 0)
+        return RT_ERR_ARG;
+    const size_t nr      = p->last_spec_rays;
+    const rt::SpecOut &o = p->spec[p->spec_last];
+    if (Iv_dev)
+        *Iv_dev = o.Iv + (size_t) r * nr * (size_t) p->P.K;
+    if (ray2_dev)
+        *ray2_dev = o.ray2;
+    if (err_dev)
+        *err_dev = o.err + (size_t) r * nr;
     return RT_OK;
 }
 
@@ -1359,6 +1405,7 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
     p->lspec_first_done = false;
     p->last_spec_seed   = spectra ? p->n_spec_seed : 0;
     p->last_spec_rays   = (size_t) p->n_rays;
+    p->last_spec_ase    = spectra && !lspec && p->P.use_emis && p->n_spec_seed > 0;
     if (lspec) {
         p->lspec_rays = (size_t) p->n_rays;
         p->lspec_L    = p->P.L;
@@ -1406,7 +1453,8 @@ static int plan_report_first_failed(rt_hip_plan *p)
 // (with the seeds of rt_hip_plan_set_spectra_seeds: err [n_seed][L][n], and after a spectra-mode run with them err [n_seed][n])
 static int lspec_report_first_failed(rt_hip_plan *p)
 {
-    const size_t nb = (size_t) (p->last_spec_seed > 1 ? p->last_spec_seed : 1);
+    // (... and after one with the seeds of rt_hip_plan_set_spectra_ase_seeds err [1 + n_seed][n]: the ASE block first)
+    const size_t nb = (size_t) (p->last_spec_seed > 1 || p->last_spec_ase ? p->last_spec_seed + (p->last_spec_ase ? 1 : 0) : 1);
     const size_t n  = p->last_lspec ? p->lspec_rays : p->last_spec_rays, L = (p->last_lspec ? (size_t) p->lspec_L : 1) * nb;
     const int32_t *err_dev = p->last_lspec ? p->lspec.err : p->spec[p->spec_last].err;
     std::vector<int32_t> err(n * L);
@@ -1907,7 +1955,14 @@ static const SeedsEntry SET_SPECTRA_SEEDS = { "rt_hip_plan_set_spectra_seeds", f
                                               ": the plan was created without a seed (an emission plan: per-ray spectra with ASE seeds are not built)",
                                               nullptr, "spectra seeds", nullptr };
 
-// The seven rt_hip_plan_set_*seeds: the plan's flavour, its scans, the seeds' tables (before the scans where the scans must be
+// ASE seeds of spectra mode on an EMISSION plan (rt_hip_plan_set_spectra_ase_seeds): spectra mode must be on, length spectra off;
+// no scales (calc_ray has none); they travel as the spectra seeds do (n_spec_seed) -- what makes them ASE seeds is the plan:
+// use_emis with n_spec_seed > 0; rt_spec_ase_seeds.hip
+static const SeedsEntry SET_SPECTRA_ASE_SEEDS = { "rt_hip_plan_set_spectra_ase_seeds", true, SPECTRA_ON,
+                                                  ": the plan was created with a seed (a seeded plan takes rt_hip_plan_set_spectra_seeds)",
+                                                  ": not an emission plan (tables without E0)", "ASE seeds", nullptr };
+
+// The eight rt_hip_plan_set_*seeds: the plan's flavour, its scans, the seeds' tables (before the scans where the scans must be
 // off, as each entry point has always ordered them), the install, the scales.
 static int seeds_set(rt_hip_plan *p, const SeedsEntry &e, int n_seed, const rt_seed *seeds, const double *scales)
 {
@@ -1915,8 +1970,14 @@ static int seeds_set(rt_hip_plan *p, const SeedsEntry &e, int n_seed, const rt_s
     if (!p)
         return fail(": NULL plan");
     if (e.scan == SPECTRA_ON) { // the seeds of the per-ray modes: their own requirements, then the path of every installer
-        if (!p->P.has_seed)
+        if (e.emission == (p->P.has_seed != 0))
             return fail(e.with_seed);
+        if (e.emission && !p->P.use_emis)
+            return fail(e.no_E0);
+        if (e.emission && p->lspec_on)
+            return fail(": length spectra are on (per-ray ASE seeds at every length are not built)");
+        if (e.emission && !p->spectra_on)
+            return fail(": spectra mode is off (rt_hip_plan_enable_spectra first)");
         if (!p->spectra_on && !p->lspec_on)
             return fail(": neither spectra mode nor length spectra are on (rt_hip_plan_enable_spectra or rt_hip_plan_enable_length_spectra first)");
         if (n_seed > RT_N_SEED_MAX)
@@ -1946,6 +2007,8 @@ static int seeds_set(rt_hip_plan *p, const SeedsEntry &e, int n_seed, const rt_s
         if (n_seed > 0 && (p->path_on || p->spectra_on))
             return fail(std::string(": the path tracer or spectra mode is enabled (") + e.runs + " in step mode only)");
         if (!e.emission && n_seed == 0 && (p->n_scan_seed > 0 || p->n_spec_seed > 0)) // (the seeds of a scan are rt_hip_plan_set_scan_seeds', those of spectra mode rt_hip_plan_set_spectra_seeds': there is no set to remove)
+            return RT_OK;
+        if (e.emission && n_seed == 0 && p->n_spec_seed > 0) // (likewise the ASE seeds of spectra mode, rt_hip_plan_set_spectra_ase_seeds': no ASE seeds of step mode to remove)
             return RT_OK;
     } else {
         if (e.scan == LENGTH_SCAN_ON && suffix_scan(p))
@@ -1988,6 +2051,10 @@ int rt_hip_plan_set_suffix_ase_seeds(rt_hip_plan *p, int n_seed, const rt_seed *
 
 int rt_hip_plan_set_suffix_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds) { return seeds_set(p, SET_SUFFIX_SEEDS, n_seed, seeds, nullptr); }
 int rt_hip_plan_set_spectra_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds) { return seeds_set(p, SET_SPECTRA_SEEDS, n_seed, seeds, nullptr); }
+int rt_hip_plan_set_spectra_ase_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds)
+{
+    return seeds_set(p, SET_SPECTRA_ASE_SEEDS, n_seed, seeds, nullptr);
+}
 
 int rt_hip_plan_kernel_ms(rt_hip_plan *p, float *ms)
 {

@@ -34,11 +34,13 @@ namespace rtr {
 // the suffix scan of a seeded backward plan with the seeds of the scan, rt_step_rscan_seeds.hip; PASS_SPEC_SCAN: length
 // spectra, rt_spec_scan.hip -- per-ray spectra at every length from the scan march, no step record: no RecordKind has it;
 // PASS_SPEC_SEEDS / PASS_SPEC_SCAN_SEEDS: spectra mode / length spectra with the seeds of rt_hip_plan_set_spectra_seeds,
-// rt_spec_seeds.hip / rt_spec_scan_seeds.hip -- the same per-ray outputs once per seed beam; nothing deposited, no RecordKind)
+// rt_spec_seeds.hip / rt_spec_scan_seeds.hip -- the same per-ray outputs once per seed beam; nothing deposited, no RecordKind;
+// PASS_SPEC_ASE_SEEDS: spectra mode of an emission plan with the seeds of rt_hip_plan_set_spectra_ase_seeds, rt_spec_ase_seeds.hip --
+// the ASE rows and one block of rows per seed beam; likewise no RecordKind: the step history does not apply)
 enum PassKind {
     PASS_FREQ = 0, PASS_SPEC = 1, PASS_STEP = 2, PASS_SEEDS = 3, PASS_PATH = 4, PASS_SCAN = 5, PASS_SCAN_SEEDS = 6, PASS_ASE_SEEDS = 7,
     PASS_SCAN_ASE_SEEDS = 8, PASS_RSCAN = 9, PASS_RSCAN_ASE_SEEDS = 10, PASS_RSCAN_SEEDS = 11, PASS_SPEC_SCAN = 12,
-    PASS_SPEC_SEEDS = 13, PASS_SPEC_SCAN_SEEDS = 14
+    PASS_SPEC_SEEDS = 13, PASS_SPEC_SCAN_SEEDS = 14, PASS_SPEC_ASE_SEEDS = 15
 };
 
 enum RecordKind { REC_NONE = 0, REC_SEEDS, REC_ASE_SEEDS, REC_SCAN, REC_SCAN_SEEDS, REC_SCAN_ASE_SEEDS, REC_RSCAN, REC_RSCAN_ASE_SEEDS,

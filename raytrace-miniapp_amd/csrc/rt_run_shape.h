@@ -388,14 +388,15 @@ inline PassKind pass_kind(const RunFacts &f)
     // scan live in step mode only; the march is that of the single-seed mode, it knows nothing of a seed)
     if (f.path_on)
         return PASS_PATH;
+    // (... on an emission plan they are the seeds of rt_hip_plan_set_spectra_ase_seeds: the ASE rows and a block per seed)
     if (f.spectra_on)
-        return f.n_seed > 0 ? PASS_SPEC_SEEDS : PASS_SPEC;
+        return f.n_seed > 0 ? (f.use_emis ? PASS_SPEC_ASE_SEEDS : PASS_SPEC_SEEDS) : PASS_SPEC;
     if (f.length_spectra_on)
         return f.n_seed > 0 ? PASS_SPEC_SCAN_SEEDS : PASS_SPEC_SCAN;
     return f.step_on ? record_set(f).pass_kind() : PASS_FREQ;
 }
 // the passes that leave per-ray spectra: one 16-wave work-group per CU with the staging rows of rt_spec.hip, no histogram
-inline bool spectra_pass(PassKind kind) { return kind == PASS_SPEC || kind == PASS_SPEC_SCAN || kind == PASS_SPEC_SEEDS || kind == PASS_SPEC_SCAN_SEEDS; }
+inline bool spectra_pass(PassKind kind) { return kind == PASS_SPEC || kind == PASS_SPEC_SCAN || kind == PASS_SPEC_SEEDS || kind == PASS_SPEC_SCAN_SEEDS || kind == PASS_SPEC_ASE_SEEDS; }
 
 struct PassShape {
     int wg_waves = 0, nslot = 0;
@@ -468,7 +469,8 @@ inline PassShape pass_shape(PassKind kind, const RunFacts &f, const Tuning &t)
         auto step_lds        = [&](bool in_lds) { return rt::step_lds_doubles(in_lds, ang_stride, f.Kp, s.wg_waves, n_rec) * sizeof(double); };
         // (spectra: the staging rows of 16 waves and the exponent tables take 148 KB of LDS; length spectra cut the same rows
         // into VEC frequencies of four lengths, rt_spec_scan.hip; with the seeds of rt_hip_plan_set_spectra_seeds the seeds share
-        // the one staging of a wave, rt_spec_seeds.hip and rt_spec_scan_seeds.hip: the LDS is that of the single-seed pass)
+        // the one staging of a wave, rt_spec_seeds.hip and rt_spec_scan_seeds.hip: the LDS is that of the single-seed pass; so do the
+        // two halves of rt_spec_ase_seeds.hip, one after the other)
         s.lds = spectra_pass(kind) ? ((size_t) 2 * rt::EXP_TAB + (size_t) s.wg_waves * rt::WAVE * rt::XS_ROW) * sizeof(double) : step_lds(s.in_lds);
         if ((kind == PASS_SEEDS || kind == PASS_SCAN || kind == PASS_SCAN_SEEDS || kind == PASS_ASE_SEEDS || kind == PASS_SCAN_ASE_SEEDS ||
              kind == PASS_RSCAN || kind == PASS_RSCAN_ASE_SEEDS || kind == PASS_RSCAN_SEEDS) && s.in_lds &&

@@ -7,7 +7,7 @@
 //   rt_raygrid.hip  a ray list that is really a tensor grid: recognition + bit-wise verification,
 //                   list-mode launch tangents and the probe of the host's libm
 //   rt_launch.hip   the kernels (rt_march.hip, rt_freq.hip, rt_path.hip, rt_spec.hip, rt_step.hip, rt_step_seeds.hip, rt_fused_step.hip,
-//                   rt_step_scan.hip, rt_step_scan_seeds.hip, rt_step_ase_seeds.hip, rt_spec_scan.hip, rt_spec_seeds.hip, rt_spec_scan_seeds.hip) and how a run puts them on a queue:
+//                   rt_step_scan.hip, rt_step_scan_seeds.hip, rt_step_ase_seeds.hip, rt_spec_scan.hip, rt_spec_seeds.hip, rt_spec_scan_seeds.hip, rt_spec_ase_seeds.hip) and how a run puts them on a queue:
 //                   WHAT a run looks like -- tables in LDS or not, one launch or two, instance, grid, chunk, late zone, the
 //                   LDS layout of a one-launch run, the shape of the second pass -- is decided by pure functions of plain
 //                   numbers (rt_run_shape.h, included by rt_launch.hip alone: RunFacts from the plan + Tuning from the
@@ -103,6 +103,10 @@ struct rt_hip_plan {
     int n_spec_seed    = 0;
     int last_spec_seed = 0;       // ... of the last spectra or length-spectra run (0: the creation seed alone)
     size_t last_spec_rays = 0;    // rays of the last spectra-mode run with seeds (the block stride of its arrays)
+    // ... on an EMISSION plan in spectra mode they are the seeds of rt_hip_plan_set_spectra_ase_seeds (rt_spec_ase_seeds.hip):
+    // P.use_emis with n_spec_seed > 0 -- no other plan presents that pair.  A run then leaves 1 + n_spec_seed blocks, block 0 the
+    // ASE rows.
+    bool last_spec_ase = false;   // the last spectra-mode run was such a run: blocks 0 .. last_spec_seed
     // step mode (rt_hip_plan_enable_step): E_v and nf instead of the image cube.  One allocation, zeroed by the run's
     // zeroing launch: E_v [K] at its start, nf [nx * ny] behind it at a 256-byte boundary.
     bool step_on       = false;
