@@ -355,8 +355,10 @@ int rt_hip_plan_fetch_path(rt_hip_plan *plan, float *path, int32_t *err);
  * rt_hip_plan_kernel_times reports it as freq_ms.  rt_hip_plan_run takes no image buffers in this mode (NULL, NULL) and
  * rt_hip_plan_fetch no image pointers; it still reports failure_code (bit -err of every failing ray), the first failed
  * rays and the counters.  Works with ray lists and ray grids and together with the probe; together with the path tracer
- * it is RT_ERR_ARG.  Any pointer of fetch_spectra may be NULL.  spectra_ptr: device pointer of Iv of the last run (valid
- * until the next run or change of the ray set), for torch views. */
+ * it is RT_ERR_ARG.  Any pointer of fetch_spectra may be NULL; it copies the rows of the last RUN -- as many as that run had
+ * rays, whatever ray set the plan has been given since.  spectra_ptr: device pointer of Iv of the last run (valid
+ * until the next run or change of the ray set), for torch views.  (Which blocks of rows a run of either spectra mode leaves,
+ * and what an index of the accessors below means: the table of RowSet, raytrace-miniapp_amd/csrc/rt_records.h.) */
 int rt_hip_plan_enable_spectra(rt_hip_plan *plan, int on);
 int rt_hip_plan_fetch_spectra(rt_hip_plan *plan, double *Iv, rt_ray *ray2, int32_t *err);
 double *rt_hip_plan_spectra_ptr(rt_hip_plan *plan);

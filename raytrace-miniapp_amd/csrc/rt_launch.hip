@@ -27,6 +27,7 @@
 #include "rt_spec_seeds.hip" // spectra mode with the seeds of rt_hip_plan_set_spectra_seeds: those outputs once per seed beam
 #include "rt_spec_scan_seeds.hip" // ... and length spectra with them: once per (seed beam, length)
 #include "rt_spec_ase_seeds.hip" // spectra mode of an emission plan with the seeds of rt_hip_plan_set_spectra_ase_seeds: the ASE rows and a block per seed beam
+// (rt_spec_wg.inc: the kernel shell the five spectra passes above share, as text)
 
 #include "rt_runtime.h"
 #include "rt_run_shape.h" // what a run looks like: the pure decision (facts + tuning -> shape) this file enqueues
@@ -363,11 +364,10 @@ int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kin
     const PassShape s      = pass_shape(kind, f, t);
     const RecordSet R      = record_set(f);
     const RecordKindRow &k = R.row();
+    const RowSet W         = row_set(f); // (the rows of a per-ray spectra pass, rt_records.h)
     // (what of a one-work-group-per-CU pass does not fit, by kind; the frequency kernel's message, below, carries figures)
-    if (s.lds > f.lds_limit && (kind == PASS_SPEC || kind == PASS_SPEC_SEEDS || kind == PASS_SPEC_ASE_SEEDS))
-        return fail_arg("spectra kernel: the staging rows do not fit into the LDS of this device");
-    if (s.lds > f.lds_limit && (kind == PASS_SPEC_SCAN || kind == PASS_SPEC_SCAN_SEEDS))
-        return fail_arg("length spectra kernel: the staging rows do not fit into the LDS of this device");
+    if (s.lds > f.lds_limit && spectra_pass(kind))
+        return fail_arg((std::string(W.row().mode) + ": the staging rows do not fit into the LDS of this device").c_str());
     if (s.lds > f.lds_limit && kind == PASS_STEP)
         return fail_arg("step kernel: the E_v accumulator (nv doubles) does not fit into the LDS of this device");
     if (s.lds > f.lds_limit && kind != PASS_FREQ && kind != PASS_PATH)
@@ -384,67 +384,50 @@ int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kin
     const unsigned block  = (unsigned) s.wg_waves * 64;
     if (kind == PASS_FREQ)
         return launch(p, freq_kernel(f.s6(), f.use_emis, f.use_emis && f.exclusive), s.grid, block, s.lds, stream, fa);
-    if (kind == PASS_SPEC) {
-        rt::SpecKArg a = pass_args<rt::SpecKArg>(fa);
-        a.hot.iang  = nullptr;
-        a.out       = p->spec[p->spec_sel];
-        return launch(p, spec_kernel(f.s6(), f.use_emis), s.grid, block, s.lds, stream, a);
-    }
-    if (kind == PASS_SPEC_SCAN) { // length spectra: the rows of every length, from the boundary states of the scan march
-        if (!p->lspec.Iv || !p->scan_bnd)
-            return fail_arg("length spectra kernel: the outputs or the boundary states of this run were not allocated");
-        if (f.L < 2 || f.L > RT_N_SCAN_MAX)
-            return fail_arg("length spectra kernel: not 2 .. RT_N_SCAN_MAX lengths");
-        rt::SpecScanKArg a = pass_args<rt::SpecScanKArg>(fa);
-        a.hot.iang = nullptr;
-        a.scan     = rt::SpecScanArg{ p->lspec, p->scan_bnd };
-        return launch(p, spec_scan_kernel(f.use_emis, f.method == 1), s.grid, block, s.lds, stream, a);
-    }
-    if (kind == PASS_SPEC_SEEDS || kind == PASS_SPEC_SCAN_SEEDS) { // ... with the seeds of rt_hip_plan_set_spectra_seeds: once per seed beam
-        const char *who = kind == PASS_SPEC_SEEDS ? "spectra kernel with seeds" : "length spectra kernel with seeds";
+    if (spectra_pass(kind)) { // ---- the passes that leave per-ray rows: per kind its argument block and its kernel ----
+        const char *who = W.row().who;
         auto fail       = [&](const char *what) { return fail_arg((std::string(who) + what).c_str()); };
-        if (f.n_seed < 1 || f.n_seed > RT_N_SEED_MAX || f.use_emis || !p->P.has_seed)
-            return fail(": not 1 .. RT_N_SEED_MAX seeds on a plan created with a seed");
-        const std::string tabs_who = std::string(who) + ": the factor tables of the seeds";
-        if (kind == PASS_SPEC_SEEDS) {
-            if (!p->spec[p->spec_sel].Iv)
-                return fail(": the outputs of this run were not allocated");
-            rt::SpecSeedsKArg a = pass_args<rt::SpecSeedsKArg>(fa);
-            a.hot.iang    = nullptr;
-            a.hot.seed_fk = nullptr;
-            a.set.n_seed  = f.n_seed;
-            a.set.out     = p->spec[p->spec_sel];
-            const int rc  = fill_seed_tabs(a.set.tabs, p, f.n_seed, p->P.rays.sf != nullptr, tabs_who.c_str());
-            return rc != RT_OK ? rc : launch(p, spec_seeds_kernel(f.s6()), s.grid, block, s.lds, stream, a);
-        }
-        if (!p->lspec.Iv || !p->scan_bnd)
-            return fail(": the outputs or the boundary states of this run were not allocated");
-        if (f.L < 2 || f.L > RT_N_SCAN_MAX)
+        // (the seeds of rt_hip_plan_set_spectra_seeds on a plan created with a seed, of rt_hip_plan_set_spectra_ase_seeds on an emission plan)
+        if (W.row().seeds && (f.n_seed < 1 || f.n_seed > RT_N_SEED_MAX || f.use_emis != W.row().ase || (p->P.has_seed != 0) == W.row().ase))
+            return fail(W.row().ase ? ": not 1 .. RT_N_SEED_MAX seeds on an emission plan" : ": not 1 .. RT_N_SEED_MAX seeds on a plan created with a seed");
+        const rt::SpecOut &out = W.lengths() ? p->lspec : p->spec[p->spec_sel];
+        if (kind != PASS_SPEC && (!out.Iv || (W.lengths() && !p->scan_bnd)))
+            return fail(W.lengths() ? ": the outputs or the boundary states of this run were not allocated" : ": the outputs of this run were not allocated");
+        if (W.lengths() && (f.L < 2 || f.L > RT_N_SCAN_MAX))
             return fail(": not 2 .. RT_N_SCAN_MAX lengths");
-        rt::SpecScanSeedsKArg a = pass_args<rt::SpecScanSeedsKArg>(fa);
-        a.hot.iang    = nullptr;
-        a.hot.seed_fk = nullptr;
-        a.set.n_seed  = f.n_seed;
-        a.set.out     = p->lspec;
-        a.set.bnd     = p->scan_bnd;
-        const int rc  = fill_seed_tabs(a.set.tabs, p, f.n_seed, p->P.rays.sf != nullptr, tabs_who.c_str());
-        return rc != RT_OK ? rc : launch(p, spec_scan_seeds_kernel(f.method == 1), s.grid, block, s.lds, stream, a);
-    }
-    if (kind == PASS_SPEC_ASE_SEEDS) { // spectra mode of an emission plan with the seeds of rt_hip_plan_set_spectra_ase_seeds: block 0 ASE, block 1 + s seed s
-        auto fail = [&](const char *what) { return fail_arg((std::string("spectra kernel with ASE seeds") + what).c_str()); };
-        if (f.n_seed < 1 || f.n_seed > RT_N_SEED_MAX || !f.use_emis || p->P.has_seed)
-            return fail(": not 1 .. RT_N_SEED_MAX seeds on an emission plan");
-        if (!p->spec[p->spec_sel].Iv)
-            return fail(": the outputs of this run were not allocated");
-        rt::SpecSeedsKArg a = pass_args<rt::SpecSeedsKArg>(fa);
-        a.hot.iang    = nullptr;
-        a.set.n_seed  = f.n_seed;
-        a.set.out     = p->spec[p->spec_sel];
+        rt::FreqKArg fs = fa;
+        fs.hot.iang     = nullptr;
         // (an emission plan has no creation seed and hence no P.rays.sf: the seeds' factor tables serve a forward ray GRID
         // only, and the ray set decides -- seeds_on_grid says the same of the step passes with ASE seeds)
-        const bool grid_tabs = p->P.rays.gx && !p->P.rays.list && p->P.method != 1 && p->seedset_sf[0] != nullptr;
-        const int rc = fill_seed_tabs(a.set.tabs, p, f.n_seed, grid_tabs, "spectra kernel with ASE seeds: the factor tables of the seeds");
-        return rc != RT_OK ? rc : launch(p, spec_ase_seeds_kernel(f.s6()), s.grid, block, s.lds, stream, a);
+        const bool grid_tabs       = W.row().ase ? p->P.rays.gx && !p->P.rays.list && p->P.method != 1 && p->seedset_sf[0] != nullptr : p->P.rays.sf != nullptr;
+        const std::string tabs_who = std::string(who) + ": the factor tables of the seeds";
+        if (kind == PASS_SPEC) {
+            rt::SpecKArg a = pass_args<rt::SpecKArg>(fs);
+            a.out          = out;
+            return launch(p, spec_kernel(f.s6(), f.use_emis), s.grid, block, s.lds, stream, a);
+        }
+        if (kind == PASS_SPEC_SCAN) { // length spectra: the rows of every length, from the boundary states of the scan march
+            rt::SpecScanKArg a = pass_args<rt::SpecScanKArg>(fs);
+            a.scan             = rt::SpecScanArg{ out, p->scan_bnd };
+            return launch(p, spec_scan_kernel(f.use_emis, f.method == 1), s.grid, block, s.lds, stream, a);
+        }
+        if (kind == PASS_SPEC_SCAN_SEEDS) { // ... with the seeds of rt_hip_plan_set_spectra_seeds: once per (seed beam, length)
+            rt::SpecScanSeedsKArg a = pass_args<rt::SpecScanSeedsKArg>(fs);
+            a.hot.seed_fk = nullptr;
+            a.set.n_seed  = f.n_seed;
+            a.set.out     = out;
+            a.set.bnd     = p->scan_bnd;
+            const int rc  = fill_seed_tabs(a.set.tabs, p, f.n_seed, grid_tabs, tabs_who.c_str());
+            return rc != RT_OK ? rc : launch(p, spec_scan_seeds_kernel(f.method == 1), s.grid, block, s.lds, stream, a);
+        }
+        // spectra mode with seeds: once per seed beam -- or, on an emission plan, block 0 ASE and block 1 + s seed s
+        rt::SpecSeedsKArg a = pass_args<rt::SpecSeedsKArg>(fs);
+        if (!W.row().ase)
+            a.hot.seed_fk = nullptr;
+        a.set.n_seed = f.n_seed;
+        a.set.out    = out;
+        const int rc = fill_seed_tabs(a.set.tabs, p, f.n_seed, grid_tabs, tabs_who.c_str());
+        return rc != RT_OK ? rc : launch(p, W.row().ase ? spec_ase_seeds_kernel(f.s6()) : spec_seeds_kernel(f.s6()), s.grid, block, s.lds, stream, a);
     }
     if (kind == PASS_STEP) {
         rt::StepKArg a = pass_args<rt::StepKArg>(fa);
@@ -622,6 +605,7 @@ int plan_repeat_checked(rt_hip_plan *p)
 }
 
 RecordSet plan_record_set(const rt_hip_plan *p) { return record_set(run_facts(p)); }
+RowSet plan_row_set(const rt_hip_plan *p) { return row_set(run_facts(p)); }
 
 // ---- the steps of a run --------------------------------------------------------------------------------------------
 // step 2's device query: what hipOccupancyMaxActiveBlocksPerMultiprocessor says of the march instance `s` names (its LDS
@@ -679,35 +663,34 @@ static int ensure_buffers(rt_hip_plan *p, const RunShape &s, hipStream_t stream)
         p->P.path     = p->path_dev;
         p->P.path_err = p->path_err;
     }
-    if (p->spectra_on) {
-        // the buffers of this run's set, kept while they are large enough (no zeroing: the kernel writes every element)
-        // (with the seeds of rt_hip_plan_set_spectra_seeds: one block of rows per seed, Iv [n_seed][n_rays][K] and err
-        // [n_seed][n_rays] with the strides of THIS run's ray count; ray2 [n_rays] serves every seed)
+    // the rows of a per-ray spectra run (rt_records.h, RowSet: the blocks of THIS run, with the strides of its ray count), no
+    // zeroing: the kernel writes every element.  Iv [n_blocks][n][K] | ray2 | err [n_blocks][n], each part padded by 16 bytes
+    // and, the last apart, to 256
+    const RowSet R = row_set(run_facts(p));
+    const size_t n = (size_t) p->n_rays, rows = n * (size_t) R.n_blocks();
+    if (R.any() && !R.lengths()) {
+        // spectra mode: the buffers of this run's set, kept while they are large enough (and then laid out as they were made);
+        // ray2 [n] serves every block, its part has room for as many rows as the others
         rt::SpecOut &o = p->spec[p->spec_sel];
-        // (on an emission plan, the seeds of rt_hip_plan_set_spectra_ase_seeds: 1 + n_seed blocks, block 0 the ASE rows)
-        const size_t blocks = (size_t) p->n_spec_seed + (p->P.use_emis && p->n_spec_seed > 0 ? 1u : 0u);
-        const size_t rows = (size_t) p->n_rays * (blocks > 1 ? blocks : 1);
         if (p->spec_rays[p->spec_sel] < rows || !o.Iv) {
             plan_quiesce(p);
             (void) hipFree(o.Iv);
             o = {};
             p->spec_rays[p->spec_sel] = 0;
-            const size_t n = rows, iv_bytes = align_up(n * (size_t) p->P.K * sizeof(double) + 16, 256);
+            const size_t iv_bytes = align_up(rows * (size_t) p->P.K * sizeof(double) + 16, 256), r2_bytes = align_up(rows * sizeof(rt_ray) + 16, 256);
             unsigned char *b = nullptr;
-            HIP_TRY(dev_malloc((void **) &b, iv_bytes + align_up(n * sizeof(rt_ray) + 16, 256) + n * sizeof(int32_t) + 16));
+            HIP_TRY(dev_malloc((void **) &b, iv_bytes + r2_bytes + rows * sizeof(int32_t) + 16));
             o.Iv   = reinterpret_cast<double *>(b);
             o.ray2 = reinterpret_cast<rt_ray *>(b + iv_bytes);
-            o.err  = reinterpret_cast<int32_t *>(b + iv_bytes + align_up(n * sizeof(rt_ray) + 16, 256));
-            p->spec_rays[p->spec_sel] = n;
+            o.err  = reinterpret_cast<int32_t *>(b + iv_bytes + r2_bytes);
+            p->spec_rays[p->spec_sel] = rows;
         }
     }
-    if (p->lspec_on) {
-        // Iv [L][n][K] | ray2 [L][n] | err [L][n] in one allocation from the pool, kept while it is large enough (no zeroing:
-        // the kernel writes every element); a run that cannot have it fails with RT_ERR_NOMEM
-        // (with the seeds of rt_hip_plan_set_spectra_seeds: Iv [n_seed][L][n][K] and err [n_seed][L][n], seed-major; ray2 [L][n])
-        const size_t n = (size_t) p->n_rays, Lr = (size_t) p->P.L, Lb = Lr * (size_t) (p->n_spec_seed > 1 ? p->n_spec_seed : 1);
-        const size_t iv_bytes = align_up(Lb * n * (size_t) p->P.K * sizeof(double) + 16, 256), r2_bytes = align_up(Lr * n * sizeof(rt_ray) + 16, 256);
-        const size_t need_ls  = iv_bytes + r2_bytes + Lb * n * sizeof(int32_t) + 16;
+    if (R.lengths()) {
+        // length spectra: one allocation from the pool, kept while it is large enough and laid out anew by every run; ray2
+        // [L][n]; a run that cannot have it fails with RT_ERR_NOMEM
+        const size_t iv_bytes = align_up(rows * (size_t) p->P.K * sizeof(double) + 16, 256), r2_bytes = align_up((size_t) R.n_ray2_blocks() * n * sizeof(rt_ray) + 16, 256);
+        const size_t need_ls  = iv_bytes + r2_bytes + rows * sizeof(int32_t) + 16;
         if (need_ls > p->lspec_bytes || !p->lspec_dev) {
             plan_quiesce(p);
             pool_free(p->device, p->lspec_dev);

@@ -916,118 +916,7 @@ int rt_hip_plan_enable_spectra(rt_hip_plan *p, int on)
     return RT_OK;
 }
 
-int rt_hip_plan_fetch_spectra(rt_hip_plan *p, double *Iv, rt_ray *ray2, int32_t *err)
-{
-    if (!p || !p->ran || !p->last_spectra || p->last_lspec)
-        return fail_arg("rt_hip_plan_fetch_spectra: the last run was not a spectra run");
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipStreamSynchronize(p->last_stream));
-    const size_t n       = (size_t) p->n_rays;
-    const rt::SpecOut &o = p->spec[p->spec_last];
-    if (n == 0)
-        return RT_OK;
-    if (Iv)
-        HIP_TRY(hipMemcpy(Iv, o.Iv, n * (size_t) p->P.K * sizeof(double), hipMemcpyDeviceToHost));
-    if (ray2)
-        HIP_TRY(hipMemcpy(ray2, o.ray2, n * sizeof(rt_ray), hipMemcpyDeviceToHost));
-    if (err)
-        HIP_TRY(hipMemcpy(err, o.err, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-double *rt_hip_plan_spectra_ptr(rt_hip_plan *p) { return p && p->ran && p->last_spectra && !p->last_lspec ? p->spec[p->spec_last].Iv : nullptr; }
-
-// The rows of seed s of the last spectra run with the seeds of rt_hip_plan_set_spectra_seeds: block s of Iv and err (seed-major,
-// the stride the ray count of that run), the one ray2.  -1 behind the refusal.
-static int spec_seed_block(const rt_hip_plan *p, const char *who, int s)
-{
-    auto fail = [&](const char *what) { return (void) fail_arg((std::string(who) + what).c_str()), -1; };
-    if (!p || !p->ran || !p->last_spectra || p->last_lspec || p->last_spec_seed < 1 || p->last_spec_ase || !p->spec[p->spec_last].Iv)
-        return fail(": the last run was not a spectra run with spectra seeds");
-    if (s < 0 || s >= p->last_spec_seed)
-        return fail(": s must be 0 .. n_seed - 1 of the last run");
-    return s;
-}
-
-int rt_hip_plan_fetch_seed_spectra(rt_hip_plan *p, int s, double *Iv, rt_ray *ray2, int32_t *err)
-{
-    if (spec_seed_block(p, "rt_hip_plan_fetch_seed_spectra", s) < 0)
-        return RT_ERR_ARG;
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipStreamSynchronize(p->last_stream));
-    const size_t nr      = p->last_spec_rays;
-    const rt::SpecOut &o = p->spec[p->spec_last];
-    if (nr == 0)
-        return RT_OK;
-    if (Iv)
-        HIP_TRY(hipMemcpy(Iv, o.Iv + (size_t) s * nr * (size_t) p->P.K, nr * (size_t) p->P.K * sizeof(double), hipMemcpyDeviceToHost));
-    if (ray2)
-        HIP_TRY(hipMemcpy(ray2, o.ray2, nr * sizeof(rt_ray), hipMemcpyDeviceToHost));
-    if (err)
-        HIP_TRY(hipMemcpy(err, o.err + (size_t) s * nr, nr * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-int rt_hip_plan_seed_spectra_ptrs(rt_hip_plan *p, int s, double **Iv_dev, rt_ray **ray2_dev, int32_t **err_dev)
-{
-    if (spec_seed_block(p, "rt_hip_plan_seed_spectra_ptrs", s) < 0)
-        return RT_ERR_ARG;
-    const size_t nr      = p->last_spec_rays;
-    const rt::SpecOut &o = p->spec[p->spec_last];
-    if (Iv_dev)
-        *Iv_dev = o.Iv + (size_t) s * nr * (size_t) p->P.K;
-    if (ray2_dev)
-        *ray2_dev = o.ray2;
-    if (err_dev)
-        *err_dev = o.err + (size_t) s * nr;
-    return RT_OK;
-}
-
-// Block r of the last spectra run of an emission plan with the seeds of rt_hip_plan_set_spectra_ase_seeds: r = 0 the ASE rows,
-// r = 1 + s those of seed s (block-major, the stride the ray count of that run), the one ray2.  -1 behind the refusal.
-static int spec_full_block(const rt_hip_plan *p, const char *who, int r)
-{
-    auto fail = [&](const char *what) { return (void) fail_arg((std::string(who) + what).c_str()), -1; };
-    if (!p || !p->ran || !p->last_spectra || p->last_lspec || !p->last_spec_ase || p->last_spec_seed < 1 || !p->spec[p->spec_last].Iv)
-        return fail(": the last run was not a spectra run with ASE seeds");
-    if (r < 0 || r > p->last_spec_seed)
-        return fail(": r must be 0 .. n_seed of the last run");
-    return r;
-}
-
-int rt_hip_plan_fetch_full_spectra(rt_hip_plan *p, int r, double *Iv, rt_ray *ray2, int32_t *err)
-{
-    if (spec_full_block(p, "rt_hip_plan_fetch_full_spectra", r) < 0)
-        return RT_ERR_ARG;
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipStreamSynchronize(p->last_stream));
-    const size_t nr      = p->last_spec_rays;
-    const rt::SpecOut &o = p->spec[p->spec_last];
-    if (nr == 0)
-        return RT_OK;
-    if (Iv)
-        HIP_TRY(hipMemcpy(Iv, o.Iv + (size_t) r * nr * (size_t) p->P.K, nr * (size_t) p->P.K * sizeof(double), hipMemcpyDeviceToHost));
-    if (ray2)
-        HIP_TRY(hipMemcpy(ray2, o.ray2, nr * sizeof(rt_ray), hipMemcpyDeviceToHost));
-    if (err)
-        HIP_TRY(hipMemcpy(err, o.err + (size_t) r * nr, nr * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-int rt_hip_plan_full_spectra_ptrs(rt_hip_plan *p, int r, double **Iv_dev, rt_ray **ray2_dev, int32_t **err_dev)
-{
-    if (spec_full_block(p, "rt_hip_plan_full_spectra_ptrs", r) < 0)
-        return RT_ERR_ARG;
-    const size_t nr      = p->last_spec_rays;
-    const rt::SpecOut &o = p->spec[p->spec_last];
-    if (Iv_dev)
-        *Iv_dev = o.Iv + (size_t) r * nr * (size_t) p->P.K;
-    if (ray2_dev)
-        *ray2_dev = o.ray2;
-    if (err_dev)
-        *err_dev = o.err + (size_t) r * nr;
-    return RT_OK;
-}
+// (the accessors of the rows of a spectra run, of either mode: below, with the one table and the one path they share)
 
 // Length spectra (include/rt_hip.h): a mode of its own beside spectra mode and the scans.  The switch owns the boundary
 // states of the march while it is on, as scan_switch does for a scan; the method of the plan says prefix or suffix.
@@ -1071,105 +960,131 @@ int rt_hip_plan_enable_length_spectra(rt_hip_plan *p, int on)
         p->lspec_dev   = nullptr;
         p->lspec_bytes = 0;
         p->lspec       = {};
-        if (p->last_lspec) // (its rows are gone: the accessors say so, rt_hip_plan_fetch keeps the report and the counters)
-            p->lspec_rays = 0;
+        // (the rows of a last length-spectra run are gone: the accessors say so by the buffer, rt_hip_plan_fetch keeps the
+        // report and the counters)
         if (p->n_spec_seed > 0) // ... and so do the seeds of rt_hip_plan_set_spectra_seeds
             return seeds_install(p, 0, nullptr, SEEDS_OF_SPECTRA);
     }
     return RT_OK;
 }
 
-// block n - 2 of the last length-spectra run, or -1 behind the refusal
-static int lspec_block(const rt_hip_plan *p, const char *who, int n)
+} // extern "C"
+
+// ---- the rows of the last per-ray spectra run (rt_records.h: RowSet says which blocks there are) ---------------------------
+// An accessor pair of the C ABI: the kinds of last run it serves (bits by RowKind), what it says after a run of another
+// kind, and what of an index the run has not -- the length first, then "no seeds" where the pair asks for a seed and the run
+// carried none, then the first index (nullptr: the pair has no such index, or no such refusal).
+struct RowsAccessor {
+    unsigned kinds;
+    const char *not_kind, *bad_n, *no_seeds, *bad_first;
+};
+constexpr unsigned rows_bit(RowKind k) { return 1u << k; }
+static const char NOT_LSPEC[] = ": the last run was not a length-spectra run (or length spectra have been switched off since)";
+// (the plain pair serves block 0 of all three spectra-mode kinds: seed 0, or the ASE rows)
+static const RowsAccessor ACC_SPEC      = { rows_bit(ROWS_SPEC) | rows_bit(ROWS_SPEC_SEEDS) | rows_bit(ROWS_SPEC_ASE_SEEDS), ": the last run was not a spectra run", nullptr,
+                                            nullptr, nullptr };
+static const RowsAccessor ACC_SEED_SPEC = { rows_bit(ROWS_SPEC_SEEDS), ": the last run was not a spectra run with spectra seeds", nullptr, nullptr,
+                                            ": s must be 0 .. n_seed - 1 of the last run" };
+static const RowsAccessor ACC_FULL_SPEC = { rows_bit(ROWS_SPEC_ASE_SEEDS), ": the last run was not a spectra run with ASE seeds", nullptr, nullptr,
+                                            ": r must be 0 .. n_seed of the last run" };
+// (a length alone means seed 0 of a run with seeds)
+static const RowsAccessor ACC_LSPEC      = { rows_bit(ROWS_LSPEC) | rows_bit(ROWS_LSPEC_SEEDS), NOT_LSPEC, ": n must be 2 .. N of the last run", nullptr, nullptr };
+static const RowsAccessor ACC_SEED_LSPEC = { rows_bit(ROWS_LSPEC) | rows_bit(ROWS_LSPEC_SEEDS), NOT_LSPEC, ": n must be 2 .. N of the last run",
+                                             ": the last run carried no spectra seeds", ": s must be 0 .. n_seed - 1 of the last run" };
+
+// what the last run wrote: the set of spectra mode it took, or the one block of length spectra (all NULL once length spectra
+// have been switched off: the rows are gone, a fact of the buffer and not of the descriptor)
+static const rt::SpecOut &rows_out(const rt_hip_plan *p) { return p->last_rows.lengths() ? p->lspec : p->spec[p->spec_last]; }
+
+// The block of Iv and err of the last run that (s, n) means to the accessor `who`, or -1 behind its refusal (who == nullptr:
+// behind no text at all, for the one accessor that answers NULL).
+static int rows_block(const rt_hip_plan *p, const char *who, const RowsAccessor &a, int s, int n)
 {
-    auto fail = [&](const char *what) { return (void) fail_arg((std::string(who) + what).c_str()), -1; };
-    if (!p || !p->ran || !p->last_lspec || !p->lspec.Iv)
-        return fail(": the last run was not a length-spectra run (or length spectra have been switched off since)");
-    if (n < 2 || n - 1 > p->lspec_L)
-        return fail(": n must be 2 .. N of the last run");
-    return n - 2;
+    auto fail = [&](const char *what) { return (void) (who ? fail_arg((std::string(who) + what).c_str()) : 0), -1; };
+    if (!p || !p->ran || !(a.kinds & rows_bit(p->last_rows.kind)) || !rows_out(p).Iv)
+        return fail(a.not_kind);
+    const RowSet &R = p->last_rows;
+    if (a.bad_n && R.ray2_block(n) < 0)
+        return fail(a.bad_n);
+    if (a.no_seeds && !R.row().seeds)
+        return fail(a.no_seeds);
+    if (R.block(s, n) < 0)
+        return fail(a.bad_first);
+    return R.block(s, n);
+}
+// ... the addresses of its rows (ray2 has the block of the length alone), and the rows through host pointers: as many as the
+// RUN had rays, whatever ray set the plan has been given since
+static int rows_ptrs(rt_hip_plan *p, const char *who, const RowsAccessor &a, int s, int n, double **Iv_dev, rt_ray **ray2_dev, int32_t **err_dev)
+{
+    const int b = rows_block(p, who, a, s, n);
+    if (b < 0)
+        return RT_ERR_ARG;
+    const size_t nr = p->last_rows.n_rays;
+    const rt::SpecOut &o = rows_out(p);
+    if (Iv_dev)
+        *Iv_dev = o.Iv + (size_t) b * nr * (size_t) p->P.K;
+    if (ray2_dev)
+        *ray2_dev = o.ray2 + (size_t) p->last_rows.ray2_block(n) * nr;
+    if (err_dev)
+        *err_dev = o.err + (size_t) b * nr;
+    return RT_OK;
+}
+static int rows_fetch(rt_hip_plan *p, const char *who, const RowsAccessor &a, int s, int n, double *Iv, rt_ray *ray2, int32_t *err)
+{
+    double *Iv_dev   = nullptr;
+    rt_ray *ray2_dev = nullptr;
+    int32_t *err_dev = nullptr;
+    if (rows_ptrs(p, who, a, s, n, &Iv_dev, &ray2_dev, &err_dev) != RT_OK)
+        return RT_ERR_ARG;
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipStreamSynchronize(p->last_stream));
+    const size_t nr = p->last_rows.n_rays;
+    if (nr == 0)
+        return RT_OK;
+    if (Iv)
+        HIP_TRY(hipMemcpy(Iv, Iv_dev, nr * (size_t) p->P.K * sizeof(double), hipMemcpyDeviceToHost));
+    if (ray2)
+        HIP_TRY(hipMemcpy(ray2, ray2_dev, nr * sizeof(rt_ray), hipMemcpyDeviceToHost));
+    if (err)
+        HIP_TRY(hipMemcpy(err, err_dev, nr * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return RT_OK;
 }
 
+extern "C" {
+
+int rt_hip_plan_fetch_spectra(rt_hip_plan *p, double *Iv, rt_ray *ray2, int32_t *err) { return rows_fetch(p, "rt_hip_plan_fetch_spectra", ACC_SPEC, 0, 0, Iv, ray2, err); }
+double *rt_hip_plan_spectra_ptr(rt_hip_plan *p) { return rows_block(p, nullptr, ACC_SPEC, 0, 0) < 0 ? nullptr : rows_out(p).Iv; }
+int rt_hip_plan_fetch_seed_spectra(rt_hip_plan *p, int s, double *Iv, rt_ray *ray2, int32_t *err)
+{
+    return rows_fetch(p, "rt_hip_plan_fetch_seed_spectra", ACC_SEED_SPEC, s, 0, Iv, ray2, err);
+}
+int rt_hip_plan_seed_spectra_ptrs(rt_hip_plan *p, int s, double **Iv_dev, rt_ray **ray2_dev, int32_t **err_dev)
+{
+    return rows_ptrs(p, "rt_hip_plan_seed_spectra_ptrs", ACC_SEED_SPEC, s, 0, Iv_dev, ray2_dev, err_dev);
+}
+int rt_hip_plan_fetch_full_spectra(rt_hip_plan *p, int r, double *Iv, rt_ray *ray2, int32_t *err)
+{
+    return rows_fetch(p, "rt_hip_plan_fetch_full_spectra", ACC_FULL_SPEC, r, 0, Iv, ray2, err);
+}
+int rt_hip_plan_full_spectra_ptrs(rt_hip_plan *p, int r, double **Iv_dev, rt_ray **ray2_dev, int32_t **err_dev)
+{
+    return rows_ptrs(p, "rt_hip_plan_full_spectra_ptrs", ACC_FULL_SPEC, r, 0, Iv_dev, ray2_dev, err_dev);
+}
 int rt_hip_plan_fetch_length_spectra(rt_hip_plan *p, int n, double *Iv, rt_ray *ray2, int32_t *err)
 {
-    const int b = lspec_block(p, "rt_hip_plan_fetch_length_spectra", n);
-    if (b < 0)
-        return RT_ERR_ARG;
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipStreamSynchronize(p->last_stream));
-    const size_t nr = p->lspec_rays;
-    if (nr == 0)
-        return RT_OK;
-    if (Iv)
-        HIP_TRY(hipMemcpy(Iv, p->lspec.Iv + (size_t) b * nr * (size_t) p->P.K, nr * (size_t) p->P.K * sizeof(double), hipMemcpyDeviceToHost));
-    if (ray2)
-        HIP_TRY(hipMemcpy(ray2, p->lspec.ray2 + (size_t) b * nr, nr * sizeof(rt_ray), hipMemcpyDeviceToHost));
-    if (err)
-        HIP_TRY(hipMemcpy(err, p->lspec.err + (size_t) b * nr, nr * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return RT_OK;
+    return rows_fetch(p, "rt_hip_plan_fetch_length_spectra", ACC_LSPEC, 0, n, Iv, ray2, err);
 }
-
 int rt_hip_plan_length_spectra_ptrs(rt_hip_plan *p, int n, double **Iv_dev, rt_ray **ray2_dev, int32_t **err_dev)
 {
-    const int b = lspec_block(p, "rt_hip_plan_length_spectra_ptrs", n);
-    if (b < 0)
-        return RT_ERR_ARG;
-    const size_t nr = p->lspec_rays;
-    if (Iv_dev)
-        *Iv_dev = p->lspec.Iv + (size_t) b * nr * (size_t) p->P.K;
-    if (ray2_dev)
-        *ray2_dev = p->lspec.ray2 + (size_t) b * nr;
-    if (err_dev)
-        *err_dev = p->lspec.err + (size_t) b * nr;
-    return RT_OK;
+    return rows_ptrs(p, "rt_hip_plan_length_spectra_ptrs", ACC_LSPEC, 0, n, Iv_dev, ray2_dev, err_dev);
 }
-
-// ... with the seeds of rt_hip_plan_set_spectra_seeds: block (s, n) = s L + n - 2 of Iv and err, block n - 2 of ray2
-static int lspec_seed_block(const rt_hip_plan *p, const char *who, int s, int n)
-{
-    const int b = lspec_block(p, who, n);
-    if (b < 0)
-        return -1;
-    auto fail = [&](const char *what) { return (void) fail_arg((std::string(who) + what).c_str()), -1; };
-    if (p->last_spec_seed < 1)
-        return fail(": the last run carried no spectra seeds");
-    if (s < 0 || s >= p->last_spec_seed)
-        return fail(": s must be 0 .. n_seed - 1 of the last run");
-    return s * p->lspec_L + b;
-}
-
 int rt_hip_plan_fetch_seed_length_spectra(rt_hip_plan *p, int s, int n, double *Iv, rt_ray *ray2, int32_t *err)
 {
-    const int sb = lspec_seed_block(p, "rt_hip_plan_fetch_seed_length_spectra", s, n);
-    if (sb < 0)
-        return RT_ERR_ARG;
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipStreamSynchronize(p->last_stream));
-    const size_t nr = p->lspec_rays;
-    if (nr == 0)
-        return RT_OK;
-    if (Iv)
-        HIP_TRY(hipMemcpy(Iv, p->lspec.Iv + (size_t) sb * nr * (size_t) p->P.K, nr * (size_t) p->P.K * sizeof(double), hipMemcpyDeviceToHost));
-    if (ray2)
-        HIP_TRY(hipMemcpy(ray2, p->lspec.ray2 + (size_t) (n - 2) * nr, nr * sizeof(rt_ray), hipMemcpyDeviceToHost));
-    if (err)
-        HIP_TRY(hipMemcpy(err, p->lspec.err + (size_t) sb * nr, nr * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return RT_OK;
+    return rows_fetch(p, "rt_hip_plan_fetch_seed_length_spectra", ACC_SEED_LSPEC, s, n, Iv, ray2, err);
 }
-
 int rt_hip_plan_seed_length_spectra_ptrs(rt_hip_plan *p, int s, int n, double **Iv_dev, rt_ray **ray2_dev, int32_t **err_dev)
 {
-    const int sb = lspec_seed_block(p, "rt_hip_plan_seed_length_spectra_ptrs", s, n);
-    if (sb < 0)
-        return RT_ERR_ARG;
-    const size_t nr = p->lspec_rays;
-    if (Iv_dev)
-        *Iv_dev = p->lspec.Iv + (size_t) sb * nr * (size_t) p->P.K;
-    if (ray2_dev)
-        *ray2_dev = p->lspec.ray2 + (size_t) (n - 2) * nr;
-    if (err_dev)
-        *err_dev = p->lspec.err + (size_t) sb * nr;
-    return RT_OK;
+    return rows_ptrs(p, "rt_hip_plan_seed_length_spectra_ptrs", ACC_SEED_LSPEC, s, n, Iv_dev, ray2_dev, err_dev);
 }
 
 int rt_hip_plan_enable_step(rt_hip_plan *p, int on)
@@ -1303,6 +1218,7 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
     }
     // the records this run leaves (a seed set, ASE seeds, a length scan, a scan with its seeds): all in one allocation of the plan
     const RecordSet recs = plan_record_set(p);
+    const RowSet rows    = plan_row_set(p); // ... and the rows, of a per-ray spectra run (ROWS_NONE: of no other)
     const int n_rec      = recs.n_rec();
     double *primary      = nullptr; // the record rt_hip_plan_fetch and fetch_step serve: seed 0's or the ASE record, of all N lengths
     if (n_rec > 0) {
@@ -1400,16 +1316,8 @@ int rt_hip_plan_run(rt_hip_plan *p, void *stream_v, double *image_dev, double *i
     p->last_stream = stream;
     p->last_image  = image_dev;
     p->last_iang   = iang_dev;
-    p->last_spectra = spectra;
-    p->last_lspec  = lspec;
+    p->last_rows   = rows;
     p->lspec_first_done = false;
-    p->last_spec_seed   = spectra ? p->n_spec_seed : 0;
-    p->last_spec_rays   = (size_t) p->n_rays;
-    p->last_spec_ase    = spectra && !lspec && p->P.use_emis && p->n_spec_seed > 0;
-    if (lspec) {
-        p->lspec_rays = (size_t) p->n_rays;
-        p->lspec_L    = p->P.L;
-    }
     p->last_step   = step;
     p->last_step_lent = lent;
     p->last_records = recs;
@@ -1454,14 +1362,13 @@ static int plan_report_first_failed(rt_hip_plan *p)
 static int lspec_report_first_failed(rt_hip_plan *p)
 {
     // (... and after one with the seeds of rt_hip_plan_set_spectra_ase_seeds err [1 + n_seed][n]: the ASE block first)
-    const size_t nb = (size_t) (p->last_spec_seed > 1 || p->last_spec_ase ? p->last_spec_seed + (p->last_spec_ase ? 1 : 0) : 1);
-    const size_t n  = p->last_lspec ? p->lspec_rays : p->last_spec_rays, L = (p->last_lspec ? (size_t) p->lspec_L : 1) * nb;
-    const int32_t *err_dev = p->last_lspec ? p->lspec.err : p->spec[p->spec_last].err;
-    std::vector<int32_t> err(n * L);
-    if (n * L)
-        HIP_TRY(hipMemcpy(err.data(), err_dev, n * L * sizeof(int32_t), hipMemcpyDeviceToHost));
+    const size_t n = p->last_rows.n_rays, nb = (size_t) p->last_rows.n_blocks();
+    const int32_t *err_dev = rows_out(p).err;
+    std::vector<int32_t> err(n * nb);
+    if (n * nb && err_dev)
+        HIP_TRY(hipMemcpy(err.data(), err_dev, n * nb * sizeof(int32_t), hipMemcpyDeviceToHost));
     std::vector<unsigned char> bad(n, 0);
-    for (size_t j = 0; j < L; j++)
+    for (size_t j = 0; j < nb; j++)
         for (size_t t = 0; t < n; t++)
             bad[t] |= err[j * n + t] != 0;
     return report_first_marked(p, bad);
@@ -1520,7 +1427,7 @@ static int plan_settle(rt_hip_plan *p, rt::DevCtl &c, bool &staged)
         HIP_TRY(read_ctl());
     // rays that failed in the frequency pass have been deposited: repeat the pass without them
     // (not after a spectra run: nothing was deposited, and the per-ray codes say which rays failed)
-    if ((c.failure_code & ((1u << 2) | (1u << 3))) && !p->path_on && !p->last_spectra && !(p->P.debug & 1u) && !p->repeated) {
+    if ((c.failure_code & ((1u << 2) | (1u << 3))) && !p->path_on && !p->last_rows.any() && !(p->P.debug & 1u) && !p->repeated) {
         const int rc = plan_repeat_checked(p);
         if (rc != RT_OK)
             return rc;
@@ -1536,7 +1443,7 @@ static int plan_settle(rt_hip_plan *p, rt::DevCtl &c, bool &staged)
     }
     // length spectra: no repeat (nothing was deposited); more failing rays than the report holds: the first in list order
     // (a spectra-mode run with spectra seeds takes the same rule: a ray that fails under either seed is reported once)
-    if ((p->last_lspec || (p->last_spectra && p->last_spec_seed > 0)) && c.n_failed > RT_N_FAILED_MAX && !p->lspec_first_done) {
+    if (p->last_rows.any() && p->last_rows.kind != ROWS_SPEC && c.n_failed > RT_N_FAILED_MAX && !p->lspec_first_done) {
         const int rf = lspec_report_first_failed(p);
         if (rf != RT_OK)
             return rf;
@@ -1611,9 +1518,9 @@ int rt_hip_plan_fetch(rt_hip_plan *p, double *image, double *I_ang, unsigned int
 {
     if (!p || !p->ran)
         return fail_arg("rt_hip_plan_fetch: plan has not run");
-    if (p->last_lspec && (image || I_ang))
+    if (p->last_rows.lengths() && (image || I_ang))
         return fail_arg("rt_hip_plan_fetch: the last run was a length-spectra run, it has no image (rt_hip_plan_fetch_length_spectra)");
-    if (p->last_spectra && (image || I_ang))
+    if (p->last_rows.any() && (image || I_ang))
         return fail_arg("rt_hip_plan_fetch: the last run was a spectra run, it has no image (rt_hip_plan_fetch_spectra)");
     if (p->last_step && image)
         return fail_arg("rt_hip_plan_fetch: the last run was a step run, it has no image (rt_hip_plan_fetch_step)");

@@ -1,4 +1,4 @@
-// rt_records.h -- the records a step run leaves, as plain numbers.
+// rt_records.h -- the records a step run leaves and the rows a per-ray spectra run leaves, as plain numbers.
 //
 // A step run of a seed set, of ASE seeds, of a length scan or of a scan with its seeds leaves several records from one
 // march.  They are the blocks of ONE allocation of the plan (rt_hip_plan::rec_dev): n_rec() blocks of E_v | nf | I_ang.
@@ -133,5 +133,110 @@ static_assert(blocks(REC_RSCAN_ASE_SEEDS, 3, true) && is(REC_RSCAN_ASE_SEEDS, 9,
               "REC_RSCAN_ASE_SEEDS: (r, n) -> r L + n - 2");
 static_assert(blocks(REC_RSCAN_SEEDS, 2, true) && is(REC_RSCAN_SEEDS, 6, 2, true, false, PASS_RSCAN_SEEDS, 8), "REC_RSCAN_SEEDS: (s, n) -> s L + n - 2");
 } // namespace records_check
+
+// ---- the rows a per-ray spectra run leaves ---------------------------------------------------------------------------------
+// A run of spectra mode or of length spectra leaves, per ray, a spectrum Iv [K], the exit ray ray2 and a code err -- once
+// (plain spectra mode), once per seed beam, once per length, or once per (seed beam, length), all from one march.  They are
+// the blocks of ONE allocation, Iv [n_blocks()][n_rays][K] | ray2 [n_ray2_blocks()][n_rays] | err [n_blocks()][n_rays]: the
+// ray count of the run is the block stride, so it belongs here.  RowSet says which blocks a run has and what an index of the
+// C ABI means; rt_run_shape.h builds it from the facts of a run (row_set), the plan keeps the one of its last run
+// (rt_runtime.h), and rt_plan.hip serves the rows by it.
+//
+//   kind                 blocks of Iv / err   blocks of ray2   index of the C ABI -> block
+//   ROWS_NONE            0                    0                none (no spectra run)
+//   ROWS_SPEC            1                    1                -> 0
+//   ROWS_SPEC_SEEDS      n_seed               1                seed s -> s
+//   ROWS_SPEC_ASE_SEEDS  1 + n_seed           1                block r -> r (0: ASE, 1 + s: seed s)
+//   ROWS_LSPEC           L                    L                length n = 2 .. L + 1 -> n - 2
+//   ROWS_LSPEC_SEEDS     n_seed L             L                (s, n) -> s L + n - 2; n alone: seed 0
+//
+// As above the table is code twice: row_kinds[] holds what tells the kinds apart, RowSet derives every column from the row,
+// and the static_asserts restate the table at n_seed = 2, L = 3.  A new kind is one row here (and its static_assert), one
+// kernel block in launch_pass (rt_launch.hip) and thin extern "C" callers of the shared accessors (rt_plan.hip).
+enum RowKind { ROWS_NONE = 0, ROWS_SPEC, ROWS_SPEC_SEEDS, ROWS_SPEC_ASE_SEEDS, ROWS_LSPEC, ROWS_LSPEC_SEEDS };
+constexpr int ROWS_N_KINDS = ROWS_LSPEC_SEEDS + 1;
+
+struct RowKindRow {
+    bool lengths;     // one block per length n = 2 .. L + 1 (of every seed), of ray2 as well
+    bool ase;         // a leading block of ASE rows: r = 0 .. n_seed
+    bool seeds;       // it carries seeds: s = 0 .. n_seed - 1 (behind the ASE block where there is one)
+    PassKind pass;    // the kernel that leaves the rows (rt_launch.hip, launch_pass)
+    const char *mode; // the mode, as the message of a pass that does not fit names its kernel
+    const char *who;  // the kernel, as the messages of launch_pass name it
+};
+constexpr RowKindRow row_kinds[ROWS_N_KINDS] = {
+    // lengths ase  seeds
+    { false, false, false, PASS_FREQ, "", "" },                                                                   // ROWS_NONE
+    { false, false, false, PASS_SPEC, "spectra kernel", "spectra kernel" },                                       // ROWS_SPEC
+    { false, false, true, PASS_SPEC_SEEDS, "spectra kernel", "spectra kernel with seeds" },                       // ROWS_SPEC_SEEDS
+    { false, true, true, PASS_SPEC_ASE_SEEDS, "spectra kernel", "spectra kernel with ASE seeds" },                // ROWS_SPEC_ASE_SEEDS
+    { true, false, false, PASS_SPEC_SCAN, "length spectra kernel", "length spectra kernel" },                     // ROWS_LSPEC
+    { true, false, true, PASS_SPEC_SCAN_SEEDS, "length spectra kernel", "length spectra kernel with seeds" },     // ROWS_LSPEC_SEEDS
+};
+// the passes that leave per-ray spectra: the pass of some row
+constexpr bool spectra_pass(PassKind kind)
+{
+    for (int k = ROWS_SPEC; k < ROWS_N_KINDS; k++)
+        if (row_kinds[k].pass == kind)
+            return true;
+    return false;
+}
+
+struct RowSet {
+    RowKind kind  = ROWS_NONE; // ROWS_NONE: no spectra run (an image, a step run, the path tracer, or no run at all)
+    int n_seed    = 0;         // seeds of rt_hip_plan_set_spectra_seeds / rt_hip_plan_set_spectra_ase_seeds
+    int L         = 0;         // lengths of length spectra (N - 1)
+    size_t n_rays = 0;         // rays of the run: the stride from block to block, in rows
+
+    constexpr const RowKindRow &row() const { return row_kinds[kind]; }
+    constexpr bool any() const { return kind != ROWS_NONE; }
+    constexpr bool lengths() const { return row().lengths; }
+    // values of the first index: the ASE block and the seeds, the seeds, or 0 alone
+    constexpr int n_first() const { return row().seeds ? (row().ase ? 1 : 0) + n_seed : 1; }
+    constexpr int n_blocks() const { return any() ? n_first() * (row().lengths ? L : 1) : 0; }
+    constexpr int n_ray2_blocks() const { return any() ? (row().lengths ? L : 1) : 0; }
+    // the block of Iv and err of seed (or block) s and length n, -1 where the run left no such rows; a kind without lengths
+    // takes no notice of n, a kind without seeds has s = 0 only
+    constexpr int block(int s, int n = 0) const
+    {
+        if (!any() || s < 0 || s >= n_first())
+            return -1;
+        if (!row().lengths)
+            return s;
+        return n >= 2 && n - 1 <= L ? s * L + n - 2 : -1;
+    }
+    // ... and the block of ray2, which does not depend on the seed
+    constexpr int ray2_block(int n = 0) const { return block(0, n); }
+    constexpr PassKind pass_kind() const { return row().pass; }
+};
+
+// ---- that table at n_seed = 2, L = 3 (n = 2 .. 4) and 70 rays, checked at every compile ----------------------------------
+namespace rows_check {
+constexpr RowSet of(RowKind k) { return RowSet{ k, 2, 3, 70 }; }
+constexpr bool blocks(RowKind k, int first, bool lengths)
+{
+    for (int s = -1; s <= first + 1; s++)
+        for (int n = 0; n <= 5; n++) {
+            const bool in_n = !lengths || (n >= 2 && n <= 4), in = s >= 0 && s < first && in_n;
+            if (of(k).block(s, n) != (!in ? -1 : lengths ? s * 3 + n - 2 : s))
+                return false;
+            if (of(k).ray2_block(n) != (first == 0 || !in_n ? -1 : lengths ? n - 2 : 0))
+                return false;
+        }
+    return true;
+}
+constexpr bool is(RowKind k, int n_blocks, int n_ray2_blocks, bool lengths, PassKind pass)
+{
+    return of(k).n_blocks() == n_blocks && of(k).n_ray2_blocks() == n_ray2_blocks && of(k).lengths() == lengths && of(k).pass_kind() == pass &&
+           spectra_pass(pass) == (k != ROWS_NONE);
+}
+static_assert(blocks(ROWS_NONE, 0, false) && is(ROWS_NONE, 0, 0, false, PASS_FREQ), "ROWS_NONE: no block");
+static_assert(blocks(ROWS_SPEC, 1, false) && is(ROWS_SPEC, 1, 1, false, PASS_SPEC), "ROWS_SPEC: -> 0");
+static_assert(blocks(ROWS_SPEC_SEEDS, 2, false) && is(ROWS_SPEC_SEEDS, 2, 1, false, PASS_SPEC_SEEDS), "ROWS_SPEC_SEEDS: seed s -> s");
+static_assert(blocks(ROWS_SPEC_ASE_SEEDS, 3, false) && is(ROWS_SPEC_ASE_SEEDS, 3, 1, false, PASS_SPEC_ASE_SEEDS), "ROWS_SPEC_ASE_SEEDS: block r -> r");
+static_assert(blocks(ROWS_LSPEC, 1, true) && is(ROWS_LSPEC, 3, 3, true, PASS_SPEC_SCAN), "ROWS_LSPEC: n -> n - 2");
+static_assert(blocks(ROWS_LSPEC_SEEDS, 2, true) && is(ROWS_LSPEC_SEEDS, 6, 3, true, PASS_SPEC_SCAN_SEEDS), "ROWS_LSPEC_SEEDS: (s, n) -> s L + n - 2");
+static_assert(!spectra_pass(PASS_STEP) && !spectra_pass(PASS_PATH) && !spectra_pass(PASS_SCAN_SEEDS), "the step passes leave no rows");
+} // namespace rows_check
 
 } // namespace rtr

@@ -382,21 +382,32 @@ inline RecordSet record_set(const RunFacts &f)
     return r;
 }
 
-inline PassKind pass_kind(const RunFacts &f)
+// the rows a per-ray spectra run of these facts leaves (rt_records.h): the one place that decides kind and counts
+inline RowSet row_set(const RunFacts &f)
 {
+    RowSet r;
+    if (f.path_on || (!f.spectra_on && !f.length_spectra_on))
+        return r;
     // (n_seed > 0 beside one of the two spectra modes: the seeds of rt_hip_plan_set_spectra_seeds -- a set and the seeds of a
     // scan live in step mode only; the march is that of the single-seed mode, it knows nothing of a seed)
+    // (... on an emission plan in spectra mode they are the seeds of rt_hip_plan_set_spectra_ase_seeds: the ASE rows and a block per seed)
+    r.kind   = f.spectra_on ? (f.n_seed > 0 ? (f.use_emis ? ROWS_SPEC_ASE_SEEDS : ROWS_SPEC_SEEDS) : ROWS_SPEC) : f.n_seed > 0 ? ROWS_LSPEC_SEEDS : ROWS_LSPEC;
+    r.n_seed = f.n_seed;
+    r.L      = r.lengths() ? f.L : 0;
+    r.n_rays = (size_t) f.n_rays;
+    return r;
+}
+
+inline PassKind pass_kind(const RunFacts &f)
+{
     if (f.path_on)
         return PASS_PATH;
-    // (... on an emission plan they are the seeds of rt_hip_plan_set_spectra_ase_seeds: the ASE rows and a block per seed)
-    if (f.spectra_on)
-        return f.n_seed > 0 ? (f.use_emis ? PASS_SPEC_ASE_SEEDS : PASS_SPEC_SEEDS) : PASS_SPEC;
-    if (f.length_spectra_on)
-        return f.n_seed > 0 ? PASS_SPEC_SCAN_SEEDS : PASS_SPEC_SCAN;
+    // (the passes that leave per-ray spectra, one 16-wave work-group per CU with the staging rows of rt_spec.hip and no histogram:
+    // spectra_pass(kind), rt_records.h)
+    if (row_set(f).any())
+        return row_set(f).pass_kind();
     return f.step_on ? record_set(f).pass_kind() : PASS_FREQ;
 }
-// the passes that leave per-ray spectra: one 16-wave work-group per CU with the staging rows of rt_spec.hip, no histogram
-inline bool spectra_pass(PassKind kind) { return kind == PASS_SPEC || kind == PASS_SPEC_SCAN || kind == PASS_SPEC_SEEDS || kind == PASS_SPEC_SCAN_SEEDS || kind == PASS_SPEC_ASE_SEEDS; }
 
 struct PassShape {
     int wg_waves = 0, nslot = 0;
@@ -471,7 +482,7 @@ inline PassShape pass_shape(PassKind kind, const RunFacts &f, const Tuning &t)
         // into VEC frequencies of four lengths, rt_spec_scan.hip; with the seeds of rt_hip_plan_set_spectra_seeds the seeds share
         // the one staging of a wave, rt_spec_seeds.hip and rt_spec_scan_seeds.hip: the LDS is that of the single-seed pass; so do the
         // two halves of rt_spec_ase_seeds.hip, one after the other)
-        s.lds = spectra_pass(kind) ? ((size_t) 2 * rt::EXP_TAB + (size_t) s.wg_waves * rt::WAVE * rt::XS_ROW) * sizeof(double) : step_lds(s.in_lds);
+        s.lds = spectra_pass(kind) ? rt::spec_lds_doubles(s.wg_waves) * sizeof(double) : step_lds(s.in_lds);
         if ((kind == PASS_SEEDS || kind == PASS_SCAN || kind == PASS_SCAN_SEEDS || kind == PASS_ASE_SEEDS || kind == PASS_SCAN_ASE_SEEDS ||
              kind == PASS_RSCAN || kind == PASS_RSCAN_ASE_SEEDS || kind == PASS_RSCAN_SEEDS) && s.in_lds &&
             s.lds > f.lds_limit) { // one histogram per record does not fit: global atomics

@@ -7,13 +7,14 @@
 //   rt_raygrid.hip  a ray list that is really a tensor grid: recognition + bit-wise verification,
 //                   list-mode launch tangents and the probe of the host's libm
 //   rt_launch.hip   the kernels (rt_march.hip, rt_freq.hip, rt_path.hip, rt_spec.hip, rt_step.hip, rt_step_seeds.hip, rt_fused_step.hip,
-//                   rt_step_scan.hip, rt_step_scan_seeds.hip, rt_step_ase_seeds.hip, rt_spec_scan.hip, rt_spec_seeds.hip, rt_spec_scan_seeds.hip, rt_spec_ase_seeds.hip) and how a run puts them on a queue:
+//                   rt_step_scan.hip, rt_step_scan_seeds.hip, rt_step_ase_seeds.hip, rt_spec_scan.hip, rt_spec_seeds.hip, rt_spec_scan_seeds.hip, rt_spec_ase_seeds.hip; rt_spec_wg.inc the kernel shell the five spectra passes share) and how a run puts them on a queue:
 //                   WHAT a run looks like -- tables in LDS or not, one launch or two, instance, grid, chunk, late zone, the
 //                   LDS layout of a one-launch run, the shape of the second pass -- is decided by pure functions of plain
 //                   numbers (rt_run_shape.h, included by rt_launch.hip alone: RunFacts from the plan + Tuning from the
 //                   environment -> run_shape / pass_shape / record_set; rt_hip_debug_run_shape hands them to tests without a
 //                   device; which records a step run leaves and how they are numbered is RecordSet, rt_records.h: the plan
-//                   keeps the one of its last run, and rt_plan.hip serves the records by it);
+//                   keeps the one of its last run, and rt_plan.hip serves the records by it; RowSet is the same for the rows of a
+//                   per-ray spectra run);
 //                   plan_launch_run enqueues what they say and writes nothing per-launch into the plan's DevParams
 //   rt_multi.hip    all devices of the node: RCCL loader, communicator, rt_hip_multi_image_loop, rt_hip_multi_step_loop
 //   rt_tables.hip   the gain tables of a resident plan rewritten in place: scan and pack kernels, rt_hip_plan_update_gain
@@ -79,7 +80,9 @@ struct rt_hip_plan {
     // spectra mode (rt_hip_plan_enable_spectra): per-ray spectra instead of the image.  Two buffer sets, so that the
     // host-pointer entry (rt_hip_calc_rays) can download one chunk while the next runs; a plan of its own uses set 0.
     bool spectra_on    = false;
-    bool last_spectra  = false;   // the last run was a spectra run
+    // the rows the last run left (rt_records.h: kind, seeds, lengths and the ray count of THAT run; ROWS_NONE: it was no spectra
+    // run, of either mode) -- the accessors of rt_plan.hip serve the rows by it, never by what the plan has been given since
+    rtr::RowSet last_rows;
     unsigned spec_sel  = 0;       // buffer set the next run writes
     unsigned spec_last = 0;       // ... and the one the last run wrote
     rt::SpecOut spec[2] = {};
@@ -89,24 +92,18 @@ struct rt_hip_plan {
     // allocation from the pool, Iv [L][n][K] | ray2 [L][n] | err [L][n], not zeroed: the kernel writes every element.  The
     // boundary states of the march live in scan_bnd (below) while the mode is on, as a scan's do.
     bool lspec_on      = false;
-    bool last_lspec    = false;   // the last run was a length-spectra run (last_spectra is set as well: no image, no checking repeat)
-    bool lspec_first_done = false; // ... and its report of more than RT_N_FAILED_MAX failing rays has been put into list order
+    bool lspec_first_done = false; // the report of more than RT_N_FAILED_MAX failing rays of the last run with several blocks of rows has been put into list order
     rt::SpecOut lspec  = {};      // block n - 2 of each array: the rows of the sub-problem of n lengths
     unsigned char *lspec_dev = nullptr;
     size_t lspec_bytes = 0;
-    size_t lspec_rays  = 0;       // rays of the last length-spectra run (the block stride of the arrays)
-    int lspec_L        = 0;       // ... and its lengths
     // the seeds of the two spectra modes (rt_hip_plan_set_spectra_seeds): 1 .. RT_N_SEED_MAX seed beams whose per-ray outputs
     // one march serves (rt_spec_seeds.hip, rt_spec_scan_seeds.hip).  They travel as a set's do (seed_set, seedset_arena, the
     // factor tables on a forward ray grid) under a count of their own: n_seed and n_scan_seed stay 0 beside them, so every
     // refusal that names a set or the seeds of a scan reads as it did.  Iv and err of a run are seed-major, block 0 seed 0.
     int n_spec_seed    = 0;
-    int last_spec_seed = 0;       // ... of the last spectra or length-spectra run (0: the creation seed alone)
-    size_t last_spec_rays = 0;    // rays of the last spectra-mode run with seeds (the block stride of its arrays)
     // ... on an EMISSION plan in spectra mode they are the seeds of rt_hip_plan_set_spectra_ase_seeds (rt_spec_ase_seeds.hip):
     // P.use_emis with n_spec_seed > 0 -- no other plan presents that pair.  A run then leaves 1 + n_spec_seed blocks, block 0 the
     // ASE rows.
-    bool last_spec_ase = false;   // the last spectra-mode run was such a run: blocks 0 .. last_spec_seed
     // step mode (rt_hip_plan_enable_step): E_v and nf instead of the image cube.  One allocation, zeroed by the run's
     // zeroing launch: E_v [K] at its start, nf [nx * ny] behind it at a 256-byte boundary.
     bool step_on       = false;
@@ -327,6 +324,8 @@ int tan_mode(int device);
 int plan_launch_run(rt_hip_plan *p, hipStream_t stream);
 // the records the next run of the plan leaves: record_set (rt_run_shape.h) of the plan's facts
 RecordSet plan_record_set(const rt_hip_plan *p);
+// ... and the rows, where it is a per-ray spectra run: row_set of the same facts
+RowSet plan_row_set(const rt_hip_plan *p);
 // a run that reported failing rays: repeat the frequency pass (in step mode: the step kernel) without them (the marks and
 // the pass of the repeat, DevParams::safe, go to the launch as arguments; p->P stays as it is)
 int plan_repeat_checked(rt_hip_plan *p);

@@ -316,37 +316,20 @@ __device__ __forceinline__ void spec_seeds_tile(const FreqHot &H, const unsigned
 template <int SF>
 __global__ void __launch_bounds__(FREQ_WG_WAVES * 64, FREQ_WAVES_SEED) rt_spec_seeds_kernel(const SpecSeedsKArg A)
 {
-    extern __shared__ __align__(16) unsigned char spec_seeds_lds[];
-    const FreqHot &H = A.hot;
-    double *exp2_tab = reinterpret_cast<double *>(spec_seeds_lds);
-    double *stage    = exp2_tab + 2 * EXP_TAB + (size_t) (unsigned) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6)) * (size_t) (WAVE * XS_ROW);
-    RT_FILL_EXP_TABLES(exp2_tab)
-    __syncthreads();
-    const int lane             = lane_id();
-    const int n_seed           = A.set.n_seed;
-    const unsigned n_tiles_run = H.tile_end - H.tile_begin;
-    unsigned shard = blockIdx.x & 7u, tried = 0;
-    for (;;) {
-        unsigned t = 0;
-        if (lane == 0)
-            t = atomicAdd(&H.ctl->next_tile_f[H.freq_id][shard][0], 1u);
-        t = (unsigned) __builtin_amdgcn_readfirstlane((int) t);
-        if (t >= (n_tiles_run + 7u - shard) / 8u) { // this shard is empty: on to the next one, until all eight have been seen empty
-            if (++tried == 8)
-                break;
-            shard = (shard + 1) & 7u;
-            continue;
-        }
-        const unsigned tile = H.tile_begin + t * 8u + shard;
-        // the cold half and the seeds of the argument block, the flag word and the lane number opaque per tile
-        ColdPtr C      = (ColdPtr) ((const RT_CONST_AS char *) __builtin_amdgcn_kernarg_segment_ptr() + offsetof(SpecSeedsKArg, cold));
-        SpecSeedsPtr Q = (SpecSeedsPtr) ((const RT_CONST_AS char *) __builtin_amdgcn_kernarg_segment_ptr() + offsetof(SpecSeedsKArg, set));
-        asm volatile("" : "+s"(C), "+s"(Q));
-        unsigned hflags = H.flags;
-        int lane_t      = lane;
-        asm volatile("" : "+s"(hflags), "+v"(lane_t));
-        spec_seeds_tile<SF>(H, hflags, C, Q, n_seed, exp2_tab, stage, tile, lane_t);
-    }
+    const int n_seed = A.set.n_seed;
+    // per tile: the cold half and the seeds of the argument block, the flag word and the lane number opaque
+#define SPEC_WG_KERNEL
+#define SPEC_WG_TILE                                                                                                    \
+    ColdPtr C = (ColdPtr) ((const RT_CONST_AS char *) __builtin_amdgcn_kernarg_segment_ptr() + offsetof(SpecSeedsKArg, cold)); \
+    SpecSeedsPtr Q = (SpecSeedsPtr) ((const RT_CONST_AS char *) __builtin_amdgcn_kernarg_segment_ptr() + offsetof(SpecSeedsKArg, set)); \
+    asm volatile("" : "+s"(C), "+s"(Q)); \
+    unsigned hflags = H.flags; \
+    int lane_t      = lane; \
+    asm volatile("" : "+s"(hflags), "+v"(lane_t)); \
+    spec_seeds_tile<SF>(H, hflags, C, Q, n_seed, exp2_tab, stage, tile, lane_t);
+#include "rt_spec_wg.inc"
+#undef SPEC_WG_TILE
+#undef SPEC_WG_KERNEL
 }
 
 } // namespace rt
