@@ -389,7 +389,8 @@ double *rt_hip_plan_spectra_ptr(rt_hip_plan *plan);
  *   allocation, length-major (Iv [N-1][n_rays][K], ray2 and err [N-1][n_rays]); the pointers are valid until the next run or
  *   a change of the ray set.  The allocation is (N-1) n_rays K 8 bytes: a run that cannot have it fails with RT_ERR_NOMEM.
  * Not built: a chunked host-pointer loop like rt_hip_calc_rays, the multi-device arms, the C++ adapter, the one-launch form.
- *   (Several seed beams per length: rt_hip_plan_set_spectra_seeds, below.) */
+ *   (Several seed beams per length: rt_hip_plan_set_spectra_seeds, below; the ASE curve plus seeded curves of an emission plan:
+ *   rt_hip_plan_set_length_spectra_ase_seeds, further below.) */
 int rt_hip_plan_enable_length_spectra(rt_hip_plan *plan, int on);
 int rt_hip_plan_fetch_length_spectra(rt_hip_plan *plan, int n, double *Iv, rt_ray *ray2, int32_t *err);
 int rt_hip_plan_length_spectra_ptrs(rt_hip_plan *plan, int n, double **Iv_dev, rt_ray **ray2_dev, int32_t **err_dev);
@@ -437,7 +438,8 @@ int rt_hip_plan_seed_length_spectra_ptrs(rt_hip_plan *plan, int s, int n, double
  *   validates its seed, on an emission plan (created without a seed, tables with E0, either method) whose spectra mode is on.
  *   There are no scales: calc_ray has none.  On a forward ray grid the seeds' factor tables are built as for a set.
  *   RT_ERR_ARG, each with its own text: a NULL plan, a plan created with a seed (it takes rt_hip_plan_set_spectra_seeds),
- *   tables without E0, spectra mode off, length spectra on (per-ray ASE seeds at every length are not built), more than
+ *   tables without E0, spectra mode off, length spectra on (the text says "per-ray ASE seeds at every length are not built"; such
+ *   a plan takes rt_hip_plan_set_length_spectra_ase_seeds, below, and this installer keeps its refusal), more than
  *   RT_N_SEED_MAX seeds, invalid seeds; a rejected call leaves the installed seeds as they were.  n_seed = 0 removes the seeds
  *   and leaves plain spectra mode, bit for bit (the pass has no atomics on data).  rt_hip_plan_enable_spectra(0) drops the
  *   seeds; rt_hip_plan_update_gain / _dev keep them.  While they are installed spectra mode is on, so every switch and
@@ -453,11 +455,44 @@ int rt_hip_plan_seed_length_spectra_ptrs(rt_hip_plan *plan, int s, int n, double
  *   of them in list order); err of block r holds its codes ray by ray.  There is no checking repeat.
  * fetch_full_spectra / full_spectra_ptrs: r = 0 (ASE) .. n_seed (1 + s: seed s) of the last such run.  Anything else is
  *   RT_ERR_ARG; any pointer may be NULL; device pointers are valid until the next run or a change of the ray set.
- * Not built: length spectra with ASE seeds (refused, above), a chunked host-pointer loop, the multi-device arms, the C++
- *   adapter, the one-launch form. */
+ * Not built: a chunked host-pointer loop, the multi-device arms, the C++ adapter, the one-launch form.
+ *   (Length spectra with ASE seeds: rt_hip_plan_set_length_spectra_ase_seeds, below.) */
 int rt_hip_plan_set_spectra_ase_seeds(rt_hip_plan *plan, int n_seed, const rt_seed *seeds);
 int rt_hip_plan_fetch_full_spectra(rt_hip_plan *plan, int r, double *Iv, rt_ray *ray2, int32_t *err);   /* r = 0: ASE, 1 + s: seed s */
 int rt_hip_plan_full_spectra_ptrs(rt_hip_plan *plan, int r, double **Iv_dev, rt_ray **ray2_dev, int32_t **err_dev);
+
+/* Length spectra with ASE seeds: RayTrace::calc_ray of an EMISSION problem and of the same problem under its seed beams at
+ * EVERY plasma length n = 2 .. N, from ONE scan march and one pass (rt_spec_scan_ase_seeds.hip) -- the per-ray side of what
+ * rt_hip_plan_set_scan_ase_seeds and _set_suffix_ase_seeds do for the summed step records, and what an emission length-spectra
+ * plan plus a seeded length-spectra plan with rt_hip_plan_set_spectra_seeds leave from two marches.
+ * set_length_spectra_ase_seeds installs seeds[0 .. n_seed), 1 <= n_seed <= RT_N_SEED_MAX, each validated as rt_hip_plan_create
+ *   validates its seed, on an emission plan (created without a seed, tables with E0, either method) whose length spectra are
+ *   on.  There are no scales: calc_ray has none.  The seeds' factor tables serve a forward ray grid only; the ray set of the
+ *   run decides.  RT_ERR_ARG, each with its own text, in this order: a NULL plan, a plan created with a seed (it takes
+ *   rt_hip_plan_set_spectra_seeds), tables without E0, spectra mode on (it takes rt_hip_plan_set_spectra_ase_seeds), length
+ *   spectra off (rt_hip_plan_enable_length_spectra first), more than RT_N_SEED_MAX seeds, invalid seeds; a rejected call
+ *   leaves the installed seeds as they were.  n_seed = 0 removes the seeds and leaves plain length spectra, bit for bit (the
+ *   pass has no atomics on data).  rt_hip_plan_enable_length_spectra(0) drops the seeds; rt_hip_plan_update_gain / _dev keep
+ *   them.  While they are installed length spectra are on, so every switch and installer that refuses that mode refuses as
+ *   before.
+ * A run does the scan march of the plan's method once, that march instance unchanged, and leaves, with L = N - 1, block-major
+ *   then length-major in the one allocation of the mode: Iv [1 + n_seed][L][n_rays][K] (row stride K), err [1 + n_seed][L][n_rays],
+ *   ray2 [L][n_rays]; block r L + n - 2 is curve r (0: ASE, 1 + s: seed s) at length n.  Block (0, n) is the row the plan leaves
+ *   in plain length spectra, bit for bit, exact emission and its n = 3 rows included, so rt_hip_plan_fetch_length_spectra and
+ *   _length_spectra_ptrs serve the ASE curve unchanged; block (1 + s, n) is the row a length-spectra plan leaves of the same
+ *   problem created with seed s (E0 present, unused), bit for bit.  The state that serves length n is that of length spectra.
+ *   Error -1 and ray2 do not depend on r: a -1 ray has zeros and -1 in every block of that n; -2 / -3 are per (r, n), -2 wins.
+ *   A ray whose march sums are all zero has rows of zeros in the ASE curve and f0_s f_s[4][k] under seed s.  Every element is
+ *   written; the allocation is (1 + n_seed) L n_rays K 8 bytes, and a run that cannot have it fails with RT_ERR_NOMEM.
+ * rt_hip_plan_fetch reports the OR of the codes over all (r, ray, n), every failing ray once (more than RT_N_FAILED_MAX: the
+ *   first of them in list order).  There is no checking repeat.
+ * fetch_full_length_spectra / full_length_spectra_ptrs: r = 0 (ASE) .. n_seed (1 + s: seed s) and n = 2 .. N of the last such
+ *   run.  Anything else is RT_ERR_ARG; any pointer may be NULL; device pointers are valid until the next run or a change of
+ *   the ray set.
+ * Not built: a chunked host-pointer loop, the multi-device arms, the C++ adapter, the one-launch form. */
+int rt_hip_plan_set_length_spectra_ase_seeds(rt_hip_plan *plan, int n_seed, const rt_seed *seeds);
+int rt_hip_plan_fetch_full_length_spectra(rt_hip_plan *plan, int r, int n, double *Iv, rt_ray *ray2, int32_t *err);   /* r = 0: ASE, 1 + s: seed s */
+int rt_hip_plan_full_length_spectra_ptrs(rt_hip_plan *plan, int r, int n, double **Iv_dev, rt_ray **ray2_dev, int32_t **err_dev);
 
 /* Host-pointer batched form of RayTrace::calc_ray: n independent calls in one.  rays and ray2 are [n][4] doubles
  * (x, y, a, b) as calc_ray takes and returns them; the coordinates are rounded to float exactly as calc_ray rounds

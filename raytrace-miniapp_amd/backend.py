@@ -168,6 +168,7 @@ class Plan:
     _n_seed = 0                 # seeds of the set (set_seeds)
     _n_spec_seed = 0            # seeds of spectra mode or of length spectra (set_spectra_seeds)
     _n_spec_ase_seed = 0        # ASE seeds of spectra mode (set_spectra_ase_seeds)
+    _n_lspec_ase_seed = 0       # ASE seeds of length spectra (set_length_spectra_ase_seeds)
     _n_scan_seed = 0            # seeds of the length scan or of the suffix scan (set_scan_seeds, set_suffix_seeds)
     _n_ase_seed = 0             # ASE seeds (set_ase_seeds)
     _n_scan_ase_seed = 0        # ASE seeds of the length scan or of the suffix scan (set_scan_ase_seeds, set_suffix_ase_seeds)
@@ -311,6 +312,7 @@ class Plan:
         self.hl.check(self.hl.lib.rt_hip_plan_enable_length_spectra(self._h, on), "rt_hip_plan_enable_length_spectra")
         if self._length_spectra and not on:
             self._n_spec_seed = 0   # (switching the mode off drops its seeds)
+            self._n_lspec_ase_seed = 0
         self._length_spectra = bool(on)   # (fetch() reads it; spectra mode keeps its own flag: switching this off on a plan in spectra mode changes nothing)
         return self
 
@@ -456,6 +458,44 @@ class Plan:
         iv, r2, er = self.full_spectra_ptrs(0)   # (block 0: the arrays are block-major)
         return dict(Iv=_view(iv, (nb, nr, K), self.device), ray2=torch.as_tensor(_View(r2, (nr, 4), "<f4"), device=dev),
                     err=torch.as_tensor(_View(er, (nb, nr), "<i4"), device=dev))
+
+    # -- length spectra with ASE seeds: the ASE curve and the seeded curves of an emission plan, per ray, from one march --
+    def set_length_spectra_ase_seeds(self, seeds) -> "Plan":
+        """ASE seeds of length spectra (include/rt_hip.h, rt_hip_plan_set_length_spectra_ase_seeds): up to RT_N_SEED_MAX Seed
+        records on an EMISSION plan (created without a seed, tables with E0) whose length spectra are on.  A run then leaves,
+        from one scan march, at every length n = 2 .. N the plan's own ASE rows (curve 0) and per seed the rows of the same
+        problem created with that seed (curve 1 + s); ray2 does not depend on the curve.  There are no scales: calc_ray has
+        none.  [] removes the seeds.  More seeds than that, or anything that is not a Seed, is a ValueError raised here, before
+        any native call."""
+        self._n_lspec_ase_seed = self._install_seeds("set_length_spectra_ase_seeds", seeds, "length spectra")
+        return self
+
+    def fetch_full_length_spectra(self) -> dict:
+        """dict(ase=[rows per n], seeds=[[rows per n] per seed]) of the last length-spectra run with ASE seeds, n = 2 .. N;
+        every rows is dict(n, Iv [n_rays][K], ray2 (RAY_DTYPE), err [n_rays] int32)."""
+        curve = lambda r: [dict(n=n, **self._spec_rows("rt_hip_plan_fetch_full_length_spectra", r, n)) for n in range(2, self.problem.N + 1)]
+        return dict(ase=curve(0), seeds=[curve(1 + s) for s in range(self._n_lspec_ase_seed)])
+
+    def full_length_spectra_ptrs(self, r: int, n: int) -> tuple:
+        """Device pointers (Iv, ray2, err) of block (r, n) of the last length-spectra run with ASE seeds: r = 0 the ASE curve,
+        1 + s that of seed s; n = 2 .. N."""
+        return self._spec_ptrs("rt_hip_plan_full_length_spectra_ptrs", r, n)
+
+    def full_length_spectra_tensors(self) -> dict:
+        """torch views of the last length-spectra run with ASE seeds, curve-major then length-major and without a copy: Iv
+        [1 + n_seed][N-1][n_rays][K] float64, err [1 + n_seed][N-1][n_rays] int32, ray2 [N-1][n_rays][4] float32 (x, y, a, b: the
+        same for every curve); curve 0 is the ASE curve, block n - 2 length n.  Valid until the plan's next run or a change
+        of its ray set."""
+        import torch
+
+        nb, L, nr, K = 1 + self._n_lspec_ase_seed, self.problem.N - 1, self.n_rays, self.problem.beam.nv
+        dev = torch.device("cuda", self.device)
+        if not nr:
+            return dict(Iv=torch.empty((nb, L, 0, K), dtype=torch.float64, device=dev), ray2=torch.empty((L, 0, 4), dtype=torch.float32, device=dev),
+                        err=torch.empty((nb, L, 0), dtype=torch.int32, device=dev))
+        iv, r2, er = self.full_length_spectra_ptrs(0, 2)   # (block (0, 0))
+        return dict(Iv=_view(iv, (nb, L, nr, K), self.device), ray2=torch.as_tensor(_View(r2, (L, nr, 4), "<f4"), device=dev),
+                    err=torch.as_tensor(_View(er, (nb, L, nr), "<i4"), device=dev))
 
     def enable_step(self, on: bool = True) -> "Plan":
         """Step mode (include/rt_hip.h): a run produces E_v, nf and I_ang -- the image cube reduced on the way, never
@@ -1335,6 +1375,27 @@ def calc_rays_seeds_lengths(problem: Problem, seeds, rays, device: int = 0) -> d
         plan.enable_length_spectra(True).set_spectra_seeds(seeds).run()
         out = plan.fetch(want_image=False)
         return dict(seeds=plan.fetch_seed_length_spectra(), failure_code=out["failure_code"], failed_rays=out["failed_rays"], stats=out["stats"])
+
+
+def calc_rays_ase_seeds_lengths(problem: Problem, seeds, rays, exact: bool = False, device: int = 0) -> dict:
+    """calc_rays_ase_seeds at EVERY plasma length n = 2 .. N, from one march: one call over a plan in length spectra mode with
+    ASE seeds (Plan.set_length_spectra_ase_seeds).  `problem` must carry no seed and tables with E0; its method decides the
+    sub-problems as in calc_rays_lengths; `exact`: rt_hip_plan_set_exact_emission.  Device memory is
+    (1 + n_seed) (N - 1) n K 8 bytes.
+
+    Returns dict(ase=[dict(n, Iv, ray2, err)] for n = 2 .. N, seeds=[the same per seed], failure_code, failed_rays, stats)."""
+    if problem.N < 3 or problem.N - 1 > cabi.RT_N_SCAN_MAX:
+        raise ValueError(f"calc_rays_ase_seeds_lengths: N = {problem.N}; length spectra take 3 <= N <= RT_N_SCAN_MAX + 1 = {cabi.RT_N_SCAN_MAX + 1}")
+    seeds = _taken_seeds("calc_rays_ase_seeds_lengths", seeds)   # (the refusals of the Python face, before a plan exists)
+    rays = _rays_arg(rays)
+    with Plan(problem, device=device) as plan:
+        plan.set_rays(rays)
+        if exact:
+            plan.set_exact_emission(True)
+        plan.enable_length_spectra(True).set_length_spectra_ase_seeds(seeds).run()
+        out = plan.fetch(want_image=False)
+        full = plan.fetch_full_length_spectra()
+        return dict(ase=full["ase"], seeds=full["seeds"], failure_code=out["failure_code"], failed_rays=out["failed_rays"], stats=out["stats"])
 
 
 def calc_ray(problem: Problem, ray, method: int | None = None, device: int = 0):

@@ -462,6 +462,13 @@ def declare_hip_api(lib: C.CDLL) -> None:
         lib.rt_hip_plan_fetch_full_spectra.restype = C.c_int
         lib.rt_hip_plan_full_spectra_ptrs.argtypes = [vp, C.c_int, P(vp), P(vp), P(vp)]
         lib.rt_hip_plan_full_spectra_ptrs.restype = C.c_int
+    if hasattr(lib, "rt_hip_plan_set_length_spectra_ase_seeds"):   # (likewise)
+        lib.rt_hip_plan_set_length_spectra_ase_seeds.argtypes = [vp, C.c_int, P(RtSeed)]
+        lib.rt_hip_plan_set_length_spectra_ase_seeds.restype = C.c_int
+        lib.rt_hip_plan_fetch_full_length_spectra.argtypes = [vp, C.c_int, C.c_int, c_double_p, P(RtRay), P(C.c_int32)]
+        lib.rt_hip_plan_fetch_full_length_spectra.restype = C.c_int
+        lib.rt_hip_plan_full_length_spectra_ptrs.argtypes = [vp, C.c_int, C.c_int, P(vp), P(vp), P(vp)]
+        lib.rt_hip_plan_full_length_spectra_ptrs.restype = C.c_int
     if hasattr(lib, "rt_hip_plan_history_create"):   # (likewise)
         up, bp = P(C.c_uint), P(C.c_ubyte)
         lib.rt_hip_plan_history_create.argtypes = [vp, C.c_int]
@@ -511,6 +518,7 @@ HIP_API_SYMBOLS = [
     "rt_hip_plan_set_spectra_seeds", "rt_hip_plan_fetch_seed_spectra", "rt_hip_plan_seed_spectra_ptrs",
     "rt_hip_plan_fetch_seed_length_spectra", "rt_hip_plan_seed_length_spectra_ptrs",
     "rt_hip_plan_set_spectra_ase_seeds", "rt_hip_plan_fetch_full_spectra", "rt_hip_plan_full_spectra_ptrs",
+    "rt_hip_plan_set_length_spectra_ase_seeds", "rt_hip_plan_fetch_full_length_spectra", "rt_hip_plan_full_length_spectra_ptrs",
     "rt_hip_plan_set_step_one_launch", "rt_hip_debug_run_shape",
     "rt_hip_plan_history_create", "rt_hip_plan_history_append", "rt_hip_plan_history_ptrs", "rt_hip_plan_history_sum_ptrs",
     "rt_hip_plan_history_fetch", "rt_hip_plan_history_fetch_sum", "rt_hip_plan_history_info", "rt_hip_debug_history_layout",

@@ -27,6 +27,7 @@
 #include "rt_spec_seeds.hip" // spectra mode with the seeds of rt_hip_plan_set_spectra_seeds: those outputs once per seed beam
 #include "rt_spec_scan_seeds.hip" // ... and length spectra with them: once per (seed beam, length)
 #include "rt_spec_ase_seeds.hip" // spectra mode of an emission plan with the seeds of rt_hip_plan_set_spectra_ase_seeds: the ASE rows and a block per seed beam
+#include "rt_spec_scan_ase_seeds.hip" // ... and length spectra of one with the seeds of rt_hip_plan_set_length_spectra_ase_seeds: a block per (curve, length)
 // (rt_spec_wg.inc: the kernel shell the five spectra passes above share, as text)
 
 #include "rt_runtime.h"
@@ -167,6 +168,10 @@ void (*spec_ase_seeds_kernel(bool s6))(const rt::SpecSeedsKArg) { return s6 ? rt
 void (*spec_scan_seeds_kernel(bool backward))(const rt::SpecScanSeedsKArg)
 {
     return backward ? rt::rt_spec_scan_seeds_kernel<true> : rt::rt_spec_scan_seeds_kernel<false>;
+}
+void (*spec_scan_ase_seeds_kernel(bool backward))(const rt::SpecScanSeedsKArg)
+{
+    return backward ? rt::rt_spec_scan_ase_seeds_kernel<true> : rt::rt_spec_scan_ase_seeds_kernel<false>;
 }
 
 // what a launch of the frequency pass covers: tiles [tile_begin, tile_end) on tile counter freq_id (a run is one launch
@@ -411,14 +416,17 @@ int launch_pass(rt_hip_plan *p, const RunFacts &f, const Tuning &t, PassKind kin
             a.scan             = rt::SpecScanArg{ out, p->scan_bnd };
             return launch(p, spec_scan_kernel(f.use_emis, f.method == 1), s.grid, block, s.lds, stream, a);
         }
-        if (kind == PASS_SPEC_SCAN_SEEDS) { // ... with the seeds of rt_hip_plan_set_spectra_seeds: once per (seed beam, length)
+        // ... with the seeds of rt_hip_plan_set_spectra_seeds: once per (seed beam, length) -- or, on an emission plan with those of
+        // rt_hip_plan_set_length_spectra_ase_seeds, blocks (0, n) the ASE curve and blocks (1 + s, n) the curve of seed s
+        if (kind == PASS_SPEC_SCAN_SEEDS || kind == PASS_SPEC_SCAN_ASE_SEEDS) {
             rt::SpecScanSeedsKArg a = pass_args<rt::SpecScanSeedsKArg>(fs);
-            a.hot.seed_fk = nullptr;
+            if (!W.row().ase) // (the emission half names the row of a plan without a seed, freq_args: never read)
+                a.hot.seed_fk = nullptr;
             a.set.n_seed  = f.n_seed;
             a.set.out     = out;
             a.set.bnd     = p->scan_bnd;
             const int rc  = fill_seed_tabs(a.set.tabs, p, f.n_seed, grid_tabs, tabs_who.c_str());
-            return rc != RT_OK ? rc : launch(p, spec_scan_seeds_kernel(f.method == 1), s.grid, block, s.lds, stream, a);
+            return rc != RT_OK ? rc : launch(p, W.row().ase ? spec_scan_ase_seeds_kernel(f.method == 1) : spec_scan_seeds_kernel(f.method == 1), s.grid, block, s.lds, stream, a);
         }
         // spectra mode with seeds: once per seed beam -- or, on an emission plan, block 0 ASE and block 1 + s seed s
         rt::SpecSeedsKArg a = pass_args<rt::SpecSeedsKArg>(fs);

@@ -962,7 +962,7 @@ int rt_hip_plan_enable_length_spectra(rt_hip_plan *p, int on)
         p->lspec       = {};
         // (the rows of a last length-spectra run are gone: the accessors say so by the buffer, rt_hip_plan_fetch keeps the
         // report and the counters)
-        if (p->n_spec_seed > 0) // ... and so do the seeds of rt_hip_plan_set_spectra_seeds
+        if (p->n_spec_seed > 0) // ... and so do the seeds of rt_hip_plan_set_spectra_seeds or rt_hip_plan_set_length_spectra_ase_seeds
             return seeds_install(p, 0, nullptr, SEEDS_OF_SPECTRA);
     }
     return RT_OK;
@@ -988,9 +988,14 @@ static const RowsAccessor ACC_SEED_SPEC = { rows_bit(ROWS_SPEC_SEEDS), ": the la
 static const RowsAccessor ACC_FULL_SPEC = { rows_bit(ROWS_SPEC_ASE_SEEDS), ": the last run was not a spectra run with ASE seeds", nullptr, nullptr,
                                             ": r must be 0 .. n_seed of the last run" };
 // (a length alone means seed 0 of a run with seeds)
-static const RowsAccessor ACC_LSPEC      = { rows_bit(ROWS_LSPEC) | rows_bit(ROWS_LSPEC_SEEDS), NOT_LSPEC, ": n must be 2 .. N of the last run", nullptr, nullptr };
+// (... or the ASE curve of a run with ASE seeds)
+static const RowsAccessor ACC_LSPEC      = { rows_bit(ROWS_LSPEC) | rows_bit(ROWS_LSPEC_SEEDS) | rows_bit(ROWS_LSPEC_ASE_SEEDS), NOT_LSPEC, ": n must be 2 .. N of the last run", nullptr, nullptr };
 static const RowsAccessor ACC_SEED_LSPEC = { rows_bit(ROWS_LSPEC) | rows_bit(ROWS_LSPEC_SEEDS), NOT_LSPEC, ": n must be 2 .. N of the last run",
                                              ": the last run carried no spectra seeds", ": s must be 0 .. n_seed - 1 of the last run" };
+
+static const RowsAccessor ACC_FULL_LSPEC = { rows_bit(ROWS_LSPEC_ASE_SEEDS),
+                                             ": the last run was not a length-spectra run with ASE seeds (or length spectra have been switched off since)",
+                                             ": n must be 2 .. N of the last run", nullptr, ": r must be 0 .. n_seed of the last run" };
 
 // what the last run wrote: the set of spectra mode it took, or the one block of length spectra (all NULL once length spectra
 // have been switched off: the rows are gone, a fact of the buffer and not of the descriptor)
@@ -1085,6 +1090,15 @@ int rt_hip_plan_fetch_seed_length_spectra(rt_hip_plan *p, int s, int n, double *
 int rt_hip_plan_seed_length_spectra_ptrs(rt_hip_plan *p, int s, int n, double **Iv_dev, rt_ray **ray2_dev, int32_t **err_dev)
 {
     return rows_ptrs(p, "rt_hip_plan_seed_length_spectra_ptrs", ACC_SEED_LSPEC, s, n, Iv_dev, ray2_dev, err_dev);
+}
+
+int rt_hip_plan_fetch_full_length_spectra(rt_hip_plan *p, int r, int n, double *Iv, rt_ray *ray2, int32_t *err)
+{
+    return rows_fetch(p, "rt_hip_plan_fetch_full_length_spectra", ACC_FULL_LSPEC, r, n, Iv, ray2, err);
+}
+int rt_hip_plan_full_length_spectra_ptrs(rt_hip_plan *p, int r, int n, double **Iv_dev, rt_ray **ray2_dev, int32_t **err_dev)
+{
+    return rows_ptrs(p, "rt_hip_plan_full_length_spectra_ptrs", ACC_FULL_LSPEC, r, n, Iv_dev, ray2_dev, err_dev);
 }
 
 int rt_hip_plan_enable_step(rt_hip_plan *p, int on)
@@ -1826,7 +1840,7 @@ static int seeds_install(rt_hip_plan *p, int n_seed, const rt_seed *seeds, Seeds
 
 // What an installer of seeds requires of the plan: its flavour -- an emission plan (the seeds are ASE seeds and bring their
 // scales) or a seeded one -- and its scans; and the words of its refusals that are its own.
-enum ScanNeed { SCANS_OFF, LENGTH_SCAN_ON, SUFFIX_SCAN_ON, SPECTRA_ON };
+enum ScanNeed { SCANS_OFF, LENGTH_SCAN_ON, SUFFIX_SCAN_ON, SPECTRA_ON, LSPEC_ON };
 struct SeedsEntry {
     const char *who;
     bool emission;
@@ -1869,21 +1883,32 @@ static const SeedsEntry SET_SPECTRA_ASE_SEEDS = { "rt_hip_plan_set_spectra_ase_s
                                                   ": the plan was created with a seed (a seeded plan takes rt_hip_plan_set_spectra_seeds)",
                                                   ": not an emission plan (tables without E0)", "ASE seeds", nullptr };
 
-// The eight rt_hip_plan_set_*seeds: the plan's flavour, its scans, the seeds' tables (before the scans where the scans must be
+// ASE seeds of length spectra on an EMISSION plan (rt_hip_plan_set_length_spectra_ase_seeds): length spectra must be on (and so
+// spectra mode off); no scales; they travel as the spectra seeds do (n_spec_seed) -- use_emis with n_spec_seed > 0 and length
+// spectra on; rt_spec_scan_ase_seeds.hip
+static const SeedsEntry SET_LSPEC_ASE_SEEDS = { "rt_hip_plan_set_length_spectra_ase_seeds", true, LSPEC_ON,
+                                                ": the plan was created with a seed (a seeded plan takes rt_hip_plan_set_spectra_seeds)",
+                                                ": not an emission plan (tables without E0)", "ASE seeds", nullptr };
+
+// The nine rt_hip_plan_set_*seeds: the plan's flavour, its scans, the seeds' tables (before the scans where the scans must be
 // off, as each entry point has always ordered them), the install, the scales.
 static int seeds_set(rt_hip_plan *p, const SeedsEntry &e, int n_seed, const rt_seed *seeds, const double *scales)
 {
     auto fail = [&](const std::string &what) { return fail_arg((e.who + what).c_str()); };
     if (!p)
         return fail(": NULL plan");
-    if (e.scan == SPECTRA_ON) { // the seeds of the per-ray modes: their own requirements, then the path of every installer
+    if (e.scan == SPECTRA_ON || e.scan == LSPEC_ON) { // the seeds of the per-ray modes: their own requirements, then the path of every installer
         if (e.emission == (p->P.has_seed != 0))
             return fail(e.with_seed);
         if (e.emission && !p->P.use_emis)
             return fail(e.no_E0);
-        if (e.emission && p->lspec_on)
+        if (e.scan == LSPEC_ON && p->spectra_on)
+            return fail(": spectra mode is on (a plan in spectra mode takes rt_hip_plan_set_spectra_ase_seeds)");
+        if (e.scan == LSPEC_ON && !p->lspec_on)
+            return fail(": length spectra are off (rt_hip_plan_enable_length_spectra first)");
+        if (e.scan == SPECTRA_ON && e.emission && p->lspec_on) // (the text is older than rt_hip_plan_set_length_spectra_ase_seeds, which takes such a plan)
             return fail(": length spectra are on (per-ray ASE seeds at every length are not built)");
-        if (e.emission && !p->spectra_on)
+        if (e.scan == SPECTRA_ON && e.emission && !p->spectra_on)
             return fail(": spectra mode is off (rt_hip_plan_enable_spectra first)");
         if (!p->spectra_on && !p->lspec_on)
             return fail(": neither spectra mode nor length spectra are on (rt_hip_plan_enable_spectra or rt_hip_plan_enable_length_spectra first)");
@@ -1961,6 +1986,11 @@ int rt_hip_plan_set_spectra_seeds(rt_hip_plan *p, int n_seed, const rt_seed *see
 int rt_hip_plan_set_spectra_ase_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds)
 {
     return seeds_set(p, SET_SPECTRA_ASE_SEEDS, n_seed, seeds, nullptr);
+}
+
+int rt_hip_plan_set_length_spectra_ase_seeds(rt_hip_plan *p, int n_seed, const rt_seed *seeds)
+{
+    return seeds_set(p, SET_LSPEC_ASE_SEEDS, n_seed, seeds, nullptr);
 }
 
 int rt_hip_plan_kernel_ms(rt_hip_plan *p, float *ms)

@@ -36,11 +36,13 @@ namespace rtr {
 // PASS_SPEC_SEEDS / PASS_SPEC_SCAN_SEEDS: spectra mode / length spectra with the seeds of rt_hip_plan_set_spectra_seeds,
 // rt_spec_seeds.hip / rt_spec_scan_seeds.hip -- the same per-ray outputs once per seed beam; nothing deposited, no RecordKind;
 // PASS_SPEC_ASE_SEEDS: spectra mode of an emission plan with the seeds of rt_hip_plan_set_spectra_ase_seeds, rt_spec_ase_seeds.hip --
-// the ASE rows and one block of rows per seed beam; likewise no RecordKind: the step history does not apply)
+// the ASE rows and one block of rows per seed beam; likewise no RecordKind: the step history does not apply;
+// PASS_SPEC_SCAN_ASE_SEEDS: length spectra of an emission plan with the seeds of rt_hip_plan_set_length_spectra_ase_seeds,
+// rt_spec_scan_ase_seeds.hip -- the ASE curve and one curve per seed beam, a block of rows per (curve, length); no RecordKind)
 enum PassKind {
     PASS_FREQ = 0, PASS_SPEC = 1, PASS_STEP = 2, PASS_SEEDS = 3, PASS_PATH = 4, PASS_SCAN = 5, PASS_SCAN_SEEDS = 6, PASS_ASE_SEEDS = 7,
     PASS_SCAN_ASE_SEEDS = 8, PASS_RSCAN = 9, PASS_RSCAN_ASE_SEEDS = 10, PASS_RSCAN_SEEDS = 11, PASS_SPEC_SCAN = 12,
-    PASS_SPEC_SEEDS = 13, PASS_SPEC_SCAN_SEEDS = 14, PASS_SPEC_ASE_SEEDS = 15
+    PASS_SPEC_SEEDS = 13, PASS_SPEC_SCAN_SEEDS = 14, PASS_SPEC_ASE_SEEDS = 15, PASS_SPEC_SCAN_ASE_SEEDS = 16
 };
 
 enum RecordKind { REC_NONE = 0, REC_SEEDS, REC_ASE_SEEDS, REC_SCAN, REC_SCAN_SEEDS, REC_SCAN_ASE_SEEDS, REC_RSCAN, REC_RSCAN_ASE_SEEDS,
@@ -149,12 +151,13 @@ static_assert(blocks(REC_RSCAN_SEEDS, 2, true) && is(REC_RSCAN_SEEDS, 6, 2, true
 //   ROWS_SPEC_ASE_SEEDS  1 + n_seed           1                block r -> r (0: ASE, 1 + s: seed s)
 //   ROWS_LSPEC           L                    L                length n = 2 .. L + 1 -> n - 2
 //   ROWS_LSPEC_SEEDS     n_seed L             L                (s, n) -> s L + n - 2; n alone: seed 0
+//   ROWS_LSPEC_ASE_SEEDS (1 + n_seed) L       L                (r, n) -> r L + n - 2 (0: ASE, 1 + s: seed s); n alone: the ASE curve
 //
 // As above the table is code twice: row_kinds[] holds what tells the kinds apart, RowSet derives every column from the row,
 // and the static_asserts restate the table at n_seed = 2, L = 3.  A new kind is one row here (and its static_assert), one
 // kernel block in launch_pass (rt_launch.hip) and thin extern "C" callers of the shared accessors (rt_plan.hip).
-enum RowKind { ROWS_NONE = 0, ROWS_SPEC, ROWS_SPEC_SEEDS, ROWS_SPEC_ASE_SEEDS, ROWS_LSPEC, ROWS_LSPEC_SEEDS };
-constexpr int ROWS_N_KINDS = ROWS_LSPEC_SEEDS + 1;
+enum RowKind { ROWS_NONE = 0, ROWS_SPEC, ROWS_SPEC_SEEDS, ROWS_SPEC_ASE_SEEDS, ROWS_LSPEC, ROWS_LSPEC_SEEDS, ROWS_LSPEC_ASE_SEEDS };
+constexpr int ROWS_N_KINDS = ROWS_LSPEC_ASE_SEEDS + 1;
 
 struct RowKindRow {
     bool lengths;     // one block per length n = 2 .. L + 1 (of every seed), of ray2 as well
@@ -172,6 +175,7 @@ constexpr RowKindRow row_kinds[ROWS_N_KINDS] = {
     { false, true, true, PASS_SPEC_ASE_SEEDS, "spectra kernel", "spectra kernel with ASE seeds" },                // ROWS_SPEC_ASE_SEEDS
     { true, false, false, PASS_SPEC_SCAN, "length spectra kernel", "length spectra kernel" },                     // ROWS_LSPEC
     { true, false, true, PASS_SPEC_SCAN_SEEDS, "length spectra kernel", "length spectra kernel with seeds" },     // ROWS_LSPEC_SEEDS
+    { true, true, true, PASS_SPEC_SCAN_ASE_SEEDS, "length spectra kernel", "length spectra kernel with ASE seeds" }, // ROWS_LSPEC_ASE_SEEDS
 };
 // the passes that leave per-ray spectra: the pass of some row
 constexpr bool spectra_pass(PassKind kind)
@@ -184,7 +188,7 @@ constexpr bool spectra_pass(PassKind kind)
 
 struct RowSet {
     RowKind kind  = ROWS_NONE; // ROWS_NONE: no spectra run (an image, a step run, the path tracer, or no run at all)
-    int n_seed    = 0;         // seeds of rt_hip_plan_set_spectra_seeds / rt_hip_plan_set_spectra_ase_seeds
+    int n_seed    = 0;         // seeds of rt_hip_plan_set_spectra_seeds / rt_hip_plan_set_spectra_ase_seeds / rt_hip_plan_set_length_spectra_ase_seeds
     int L         = 0;         // lengths of length spectra (N - 1)
     size_t n_rays = 0;         // rays of the run: the stride from block to block, in rows
 
@@ -236,6 +240,8 @@ static_assert(blocks(ROWS_SPEC_SEEDS, 2, false) && is(ROWS_SPEC_SEEDS, 2, 1, fal
 static_assert(blocks(ROWS_SPEC_ASE_SEEDS, 3, false) && is(ROWS_SPEC_ASE_SEEDS, 3, 1, false, PASS_SPEC_ASE_SEEDS), "ROWS_SPEC_ASE_SEEDS: block r -> r");
 static_assert(blocks(ROWS_LSPEC, 1, true) && is(ROWS_LSPEC, 3, 3, true, PASS_SPEC_SCAN), "ROWS_LSPEC: n -> n - 2");
 static_assert(blocks(ROWS_LSPEC_SEEDS, 2, true) && is(ROWS_LSPEC_SEEDS, 6, 3, true, PASS_SPEC_SCAN_SEEDS), "ROWS_LSPEC_SEEDS: (s, n) -> s L + n - 2");
+static_assert(blocks(ROWS_LSPEC_ASE_SEEDS, 3, true) && is(ROWS_LSPEC_ASE_SEEDS, 9, 3, true, PASS_SPEC_SCAN_ASE_SEEDS),
+              "ROWS_LSPEC_ASE_SEEDS: (r, n) -> r L + n - 2");
 static_assert(!spectra_pass(PASS_STEP) && !spectra_pass(PASS_PATH) && !spectra_pass(PASS_SCAN_SEEDS), "the step passes leave no rows");
 } // namespace rows_check
 

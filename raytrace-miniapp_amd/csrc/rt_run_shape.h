@@ -391,7 +391,9 @@ inline RowSet row_set(const RunFacts &f)
     // (n_seed > 0 beside one of the two spectra modes: the seeds of rt_hip_plan_set_spectra_seeds -- a set and the seeds of a
     // scan live in step mode only; the march is that of the single-seed mode, it knows nothing of a seed)
     // (... on an emission plan in spectra mode they are the seeds of rt_hip_plan_set_spectra_ase_seeds: the ASE rows and a block per seed)
-    r.kind   = f.spectra_on ? (f.n_seed > 0 ? (f.use_emis ? ROWS_SPEC_ASE_SEEDS : ROWS_SPEC_SEEDS) : ROWS_SPEC) : f.n_seed > 0 ? ROWS_LSPEC_SEEDS : ROWS_LSPEC;
+    // (... and in length spectra those of rt_hip_plan_set_length_spectra_ase_seeds: the ASE curve and a curve per seed)
+    r.kind   = f.spectra_on ? (f.n_seed > 0 ? (f.use_emis ? ROWS_SPEC_ASE_SEEDS : ROWS_SPEC_SEEDS) : ROWS_SPEC)
+                            : f.n_seed > 0 ? (f.use_emis ? ROWS_LSPEC_ASE_SEEDS : ROWS_LSPEC_SEEDS) : ROWS_LSPEC;
     r.n_seed = f.n_seed;
     r.L      = r.lengths() ? f.L : 0;
     r.n_rays = (size_t) f.n_rays;
@@ -481,7 +483,7 @@ inline PassShape pass_shape(PassKind kind, const RunFacts &f, const Tuning &t)
         // (spectra: the staging rows of 16 waves and the exponent tables take 148 KB of LDS; length spectra cut the same rows
         // into VEC frequencies of four lengths, rt_spec_scan.hip; with the seeds of rt_hip_plan_set_spectra_seeds the seeds share
         // the one staging of a wave, rt_spec_seeds.hip and rt_spec_scan_seeds.hip: the LDS is that of the single-seed pass; so do the
-        // two halves of rt_spec_ase_seeds.hip, one after the other)
+        // two halves of rt_spec_ase_seeds.hip and of rt_spec_scan_ase_seeds.hip, one after the other)
         s.lds = spectra_pass(kind) ? rt::spec_lds_doubles(s.wg_waves) * sizeof(double) : step_lds(s.in_lds);
         if ((kind == PASS_SEEDS || kind == PASS_SCAN || kind == PASS_SCAN_SEEDS || kind == PASS_ASE_SEEDS || kind == PASS_SCAN_ASE_SEEDS ||
              kind == PASS_RSCAN || kind == PASS_RSCAN_ASE_SEEDS || kind == PASS_RSCAN_SEEDS) && s.in_lds &&

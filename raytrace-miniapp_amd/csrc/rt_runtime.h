@@ -7,7 +7,7 @@
 //   rt_raygrid.hip  a ray list that is really a tensor grid: recognition + bit-wise verification,
 //                   list-mode launch tangents and the probe of the host's libm
 //   rt_launch.hip   the kernels (rt_march.hip, rt_freq.hip, rt_path.hip, rt_spec.hip, rt_step.hip, rt_step_seeds.hip, rt_fused_step.hip,
-//                   rt_step_scan.hip, rt_step_scan_seeds.hip, rt_step_ase_seeds.hip, rt_spec_scan.hip, rt_spec_seeds.hip, rt_spec_scan_seeds.hip, rt_spec_ase_seeds.hip; rt_spec_wg.inc the kernel shell the five spectra passes share) and how a run puts them on a queue:
+//                   rt_step_scan.hip, rt_step_scan_seeds.hip, rt_step_ase_seeds.hip, rt_spec_scan.hip, rt_spec_seeds.hip, rt_spec_scan_seeds.hip, rt_spec_ase_seeds.hip, rt_spec_scan_ase_seeds.hip; rt_spec_wg.inc the kernel shell the six spectra passes share) and how a run puts them on a queue:
 //                   WHAT a run looks like -- tables in LDS or not, one launch or two, instance, grid, chunk, late zone, the
 //                   LDS layout of a one-launch run, the shape of the second pass -- is decided by pure functions of plain
 //                   numbers (rt_run_shape.h, included by rt_launch.hip alone: RunFacts from the plan + Tuning from the
@@ -103,7 +103,8 @@ struct rt_hip_plan {
     int n_spec_seed    = 0;
     // ... on an EMISSION plan in spectra mode they are the seeds of rt_hip_plan_set_spectra_ase_seeds (rt_spec_ase_seeds.hip):
     // P.use_emis with n_spec_seed > 0 -- no other plan presents that pair.  A run then leaves 1 + n_spec_seed blocks, block 0 the
-    // ASE rows.
+    // ASE rows.  With length spectra on they are the seeds of rt_hip_plan_set_length_spectra_ase_seeds (rt_spec_scan_ase_seeds.hip): a
+    // run leaves (1 + n_spec_seed) (N - 1) blocks, the ASE curve first.
     // step mode (rt_hip_plan_enable_step): E_v and nf instead of the image cube.  One allocation, zeroed by the run's
     // zeroing launch: E_v [K] at its start, nf [nx * ny] behind it at a 256-byte boundary.
     bool step_on       = false;

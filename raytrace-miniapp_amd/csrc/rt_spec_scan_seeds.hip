@@ -87,35 +87,11 @@ __device__ __forceinline__ void spec_scan_seeds_tile(const FreqHot &H, const uns
     const int e_seg            = (fl & F_ESCAPED) ? (n_done > 0 ? (n_done - 1) / RT_N_SUB + 1 : 1) : L + 1;
     const bool skip            = (fl & F_SKIP) != 0u; // every update is the identity: rows of zeros at every n
 
-    // the seed factors at the launch ray (forward, Helper.h:530-533), in place_ray's own arithmetic as rt_step_scan_seeds.hip takes them
-    double f0_launch[NS];
-#pragma unroll
-    for (int s = 0; s < NS; s++)
-        f0_launch[s] = 0.0;
-    if (!BACKWARD && have) {
-        if (!R.sf) {
-            rt_ray launch = ray;
-            float ta, tb;
-            load_ray(R, ridx, launch, ta, tb, false);
-#pragma unroll 1
-            for (int s = 0; s < n_seed; s++) {
-                const double f = rscan_seed_factor(&Q->tabs.seed[s], (double) launch.x, (double) launch.y, (double) launch.a, (double) launch.b);
-#pragma unroll
-                for (int t = 0; t < NS; t++)
-                    f0_launch[t] = t == s ? f : f0_launch[t];
-            }
-        } else {
-            RT_SEED_GRID_POINT(R, ridx)
-#pragma unroll
-            for (int s = 0; s < NS; s++) {
-                if (s < n_seed) {
-                    const double *sf         = Q->tabs.sf[s];
-                    const unsigned char *sin = Q->tabs.sin[s];
-                    RT_SEED_GRID_FACTOR(f0_launch[s], Q->tabs.seed[s].f0, sf, sin)
-                }
-            }
-        }
-    }
+#define SSS_WALK_F0
+#define SSS_GRID_TABS R.sf
+#include "rt_spec_scan_seeds_walk.inc"
+#undef SSS_GRID_TABS
+#undef SSS_WALK_F0
 
     // ---- the march record of this lane's ray (rt_tile_rec.inc; SF = 0: nothing to decode up front) ----
 #define TILE_MASK true
@@ -194,192 +170,12 @@ __device__ __forceinline__ void spec_scan_seeds_tile(const FreqHot &H, const uns
         }
     };
 
-    // a full tile and an even K: the pieces of a row leave as 16-byte stores
-    const bool wide_ok = row0 + WAVE <= n_rays && (K & 1) == 0;
-    // column `col` of the 64 staging rows to block jb of seed s, frequencies kb .. kb + VEC - 1 (rt_spec_scan.hip, flush_row)
-    auto flush_row = [&](const int col, const int s, const int jb, const int kb) {
-        double *blk     = Q->out.Iv + ((size_t) s * (size_t) L + (size_t) jb) * blk_rays * (size_t) K;
-        const int width = K - kb < VEC ? K - kb : VEC;
-        if (wide_ok && width == VEC) {
-            // two lanes cover the 32 staged bytes of a row, a store instruction 32 rows
-#pragma unroll
-            for (int g = 0; g < 2; g++) {
-                const unsigned row = (unsigned) (32 * g + (lane >> 1));
-                SPEC_STORE16(stage + row * XS_ROW + col * VEC + 2 * (lane & 1), blk + ((size_t) (row0 + row) * (size_t) K + (size_t) (kb + 2 * (lane & 1))));
-            }
-        } else if (wide_ok) { // K = 4 i + 2: the last two frequencies of a row, one piece per lane
-            SPEC_STORE16(stage + lane * XS_ROW + col * VEC, blk + ((size_t) (row0 + (unsigned) lane) * (size_t) K + (size_t) kb));
-        } else {
-            // ragged tile or odd K: 8 bytes per lane, sixteen rows per instruction
-            const int k = kb + (lane & 3);
-#pragma unroll
-            for (int g = 0; g < WAVE / 16; g++) {
-                const unsigned row = (unsigned) (16 * g + (lane >> 2));
-                if (row0 + row < n_rays && k < K)
-                    blk[(size_t) (row0 + row) * (size_t) K + (size_t) k] = stage[row * XS_ROW + col * VEC + (lane & 3)];
-            }
-        }
-    };
-    // The rows of block jb under every seed from the running gl of the block: exp(gl) once for all seeds, skipped by a wave
-    // that has no use for it; then per seed Iv = (f0_s f_s[4][k]) eg, the -2 / -3 scan (Helper.h:582-587) and the lane's VEC
-    // values into columns li * NS + s of its staging row
-    auto finish_rows = [&](const int li, const int jb, const double (&acc)[VEC], const double (&fs)[NS], const int kb) {
-        const bool lv = ((livem >> jb) & 1u) != 0u;
-        bool need     = false;
-#pragma unroll
-        for (int s = 0; s < NS; s++)
-            need = need || fs[s] != 0.0;
-#pragma unroll
-        for (int v = 0; v < VEC; v++)
-            need = need || acc[v] > 700.0 || acc[v] != acc[v];
-        const bool with_exp = __ballot(need) != 0ull;
-        double eg[VEC];
-#pragma unroll
-        for (int v = 0; v < VEC; v++)
-            eg[v] = 1.0;
-        if (with_exp)
-            exp_tab_vec(acc, tab, eg);
-#pragma unroll
-        for (int s = 0; s < NS; s++) {
-            if (s < n_seed) {
-                const ConstF64 sfk = (ConstF64) (unsigned long long) Q->tabs.fk[s];
-                double *mine       = stage + lane * XS_ROW + (li * NS + s) * VEC;
-#pragma unroll
-                for (int v = 0; v < VEC; v++) {
-                    double x = fs[s] * sfk[kb + v];
-                    if (with_exp)
-                        x *= eg[v];
-                    x = (lv && kb + v < K) ? x : 0.0; // (the padding columns K .. Kp-1 are not part of the spectrum)
-                    negm[s] |= x < 0.0 ? 1u << jb : 0u;
-                    nanm[s] |= x != x ? 1u << jb : 0u;
-                    mine[v] = x;
-                }
-            }
-        }
-    };
-
-    if (!BACKWARD) {
-        // ---- forward: every block's state first, then one walk per frequency batch ----
-#pragma unroll 1
-        for (int j = 1; j <= L; j++) {
-            double unused[NS];
-            open_block(j, unused);
-            (void) unused;
-        }
-        const bool any_live = __ballot(livem != 0u) != 0ull; // (else nothing to integrate: the rows are zeros)
-        for (int kb = 0; kb < K; kb += VEC) {
-            double acc[VEC]; // the running gl
-#pragma unroll
-            for (int v = 0; v < VEC; v++)
-                acc[v] = 0.0;
-#pragma unroll 1
-            for (int j = 0; j < L; j++) {
-                if (any_live) {
-#pragma unroll 1
-                    for (int t = 0; t < RT_N_SUB; t++) {
-                        // one sub-segment: the gain-only SF = 0 text of rt_tile_batch.inc
-                        int s = j * RT_N_SUB + t;
-                        asm volatile("" : "+s"(s));
-                        const RecSlot sl = rec_slot_lazy(rec, rrec, H.rec_stride, s, S, flags_steps, backward);
-                        const float *row = H.gain[s / RT_N_SUB + 1].gv + (size_t) sl.c * (size_t) Kp + kb;
-                        const FVec w     = *reinterpret_cast<const FVec *>(row);
-#pragma unroll
-                        for (int v = 0; v < VEC; v++)
-                            acc[v] += (double) sl.g * (double) w.v[v];
-                    }
-                }
-                // ---- the walk has reached length j + 1: row block j of every seed ----
-                double fs[NS];
-#pragma unroll
-                for (int s = 0; s < NS; s++)
-                    fs[s] = ((seedm >> j) & 1u) ? f0_launch[s] : 0.0;
-                finish_rows(j & (LCH - 1), j, acc, fs, kb);
-                if ((j & (LCH - 1)) == LCH - 1 || j == L - 1) {
-                    __builtin_amdgcn_wave_barrier();
-#pragma unroll 1
-                    for (int jj = j & ~(LCH - 1); jj <= j; jj++) {
-#pragma unroll 1
-                        for (int s = 0; s < n_seed; s++)
-                            flush_row((jj & (LCH - 1)) * NS + s, s, jj, kb);
-                    }
-                    __builtin_amdgcn_wave_barrier();
-                }
-            }
-        }
-    } else {
-        // ---- backward: the suffixes in chunks of LCH start segments a0 .. a0 + LCH - 1 (start segment a is block L - 1 - a) ----
-        for (int a0 = 0; a0 < L; a0 += LCH) {
-            double f0[LCH][NS];
-#pragma unroll
-            for (int i = 0; i < LCH; i++) {
-#pragma unroll
-                for (int s = 0; s < NS; s++)
-                    f0[i][s] = 0.0;
-                if (a0 + i < L)
-                    open_block(L - (a0 + i), f0[i]);
-                // (one state after the other, as rt_step_rscan.hip takes them)
-                asm volatile("" ::: "memory");
-            }
-            unsigned chunk_bits = 0u; // the blocks of this chunk
-#pragma unroll
-            for (int i = 0; i < LCH; i++)
-                chunk_bits |= a0 + i < L ? 1u << (L - 1 - (a0 + i)) : 0u;
-            const bool any_live = __ballot((livem & chunk_bits) != 0u) != 0ull;
-
-            for (int kb = 0; kb < K; kb += VEC) {
-                double acc[LCH][VEC]; // the running gl of every suffix
-#pragma unroll
-                for (int i = 0; i < LCH; i++) {
-#pragma unroll
-                    for (int v = 0; v < VEC; v++)
-                        acc[i][v] = 0.0;
-                }
-                // one sub-segment for the first NL accumulators: the walk of rt_step_rscan.hip
-                auto slot_step = [&](auto nl_tag, int s) {
-                    constexpr int NL = decltype(nl_tag)::value;
-                    asm volatile("" : "+s"(s));
-                    const RecSlot sl = rec_slot_lazy(rec, rrec, H.rec_stride, s, S, flags_steps, backward);
-                    const float *row = H.gain[s / RT_N_SUB + 1].gv + (size_t) sl.c * (size_t) Kp + kb;
-                    const FVec w     = *reinterpret_cast<const FVec *>(row);
-#pragma unroll
-                    for (int i = 0; i < NL; i++) {
-#pragma unroll
-                        for (int v = 0; v < VEC; v++)
-                            acc[i][v] += (double) sl.g * (double) w.v[v];
-                    }
-                };
-                if (any_live) {
-                    // the joining part: segment a0 + I is walked with accumulators 0 .. I
-#define SSS_JOIN(I)                                                                                              \
-    if (I < LCH && a0 + I < L) {                                                                                 \
-        _Pragma("unroll 1") for (int t = 0; t < RT_N_SUB; t++)                                                   \
-            slot_step(std::integral_constant<int, (I < LCH ? I + 1 : LCH)>{}, (a0 + I) * RT_N_SUB + t);          \
-    }
-                    SSS_JOIN(0)
-                    SSS_JOIN(1)
-#undef SSS_JOIN
-                    // ... and the segments behind the chunk's last start with all of them
-#pragma unroll 1
-                    for (int s = (a0 + LCH) * RT_N_SUB; s < S; s++)
-                        slot_step(std::integral_constant<int, LCH>{}, s);
-                }
-                // ---- the walk has reached the end of the record: the rows of the chunk, every seed ----
-#pragma unroll
-                for (int i = 0; i < LCH; i++) {
-                    if (a0 + i < L)
-                        finish_rows(i, L - 1 - (a0 + i), acc[i], f0[i], kb);
-                }
-                __builtin_amdgcn_wave_barrier();
-#pragma unroll 1
-                for (int i = 0; i < LCH && a0 + i < L; i++) {
-#pragma unroll 1
-                    for (int s = 0; s < n_seed; s++)
-                        flush_row(i * NS + s, s, L - 1 - (a0 + i), kb);
-                }
-                __builtin_amdgcn_wave_barrier();
-            }
-        }
-    }
+    // ---- the stores and the walk, forward or backward: rt_spec_scan_seeds_walk.inc ----
+#define SSS_WALK_TILE
+#define SSS_OUT_IV Q->out.Iv
+#include "rt_spec_scan_seeds_walk.inc"
+#undef SSS_OUT_IV
+#undef SSS_WALK_TILE
 
     // ---- the codes per seed: -1 of the state, else -2 over -3 (Helper.h:588-593: negative wins); a failing ray is reported once ----
     unsigned code = e1m ? 1u << 1 : 0u;

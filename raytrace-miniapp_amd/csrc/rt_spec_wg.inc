@@ -7,13 +7,13 @@
 //   SPEC_WG_SIZE     namespace scope, once (rt_spec.hip): spec_lds_doubles
 //   SPEC_WG_KERNEL   the whole body of a kernel whose argument block is `A`, hot half first (rt_tile_rec.inc says why text and
 //                    not a function template): rt_spec_kernel, rt_spec_scan_kernel, rt_spec_seeds_kernel,
-//                    rt_spec_scan_seeds_kernel and rt_spec_ase_seeds_kernel.  Carves the LDS, fills the exponent tables, ends
+//                    rt_spec_scan_seeds_kernel, rt_spec_ase_seeds_kernel and rt_spec_scan_ase_seeds_kernel.  Carves the LDS, fills the exponent tables, ends
 //                    the prologue in a barrier and walks the tiles.  Reads
 //                      SPEC_WG_TILE   the statements of one tile: they read H, `tile`, `lane`, exp2_tab and stage, form the
 //                                     pointers to the blocks of the argument block behind the hot half with the kernel's own
 //                                     offsetof, make them, the flag word and the lane number opaque, and call the tile function
 //                    Declares spec_lds[], H, exp2_tab, stage, lane, n_tiles_run, shard, tried, and in the loop t and tile.
-// (What the tile function takes beside these -- the seed count of the three passes with seeds -- the kernel reads from its
+// (What the tile function takes beside these -- the seed count of the four passes with seeds -- the kernel reads from its
 // argument block before the include.  The five kernels are the ones their five copies of this shell gave, instruction for
 // instruction: profiles/spectra_share_kernel_resources.txt.)
 #if defined(SPEC_WG_SIZE)
