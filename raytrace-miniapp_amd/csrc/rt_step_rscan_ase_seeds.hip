@@ -14,9 +14,10 @@
 //                Iv[k] = f0_{s,n} f_s[4][k] exp(gl_n[k]), gl_n the f64 product sum over the suffix's slots in slot order, the
 //                seed factor at the position and exit angles of the state that serves record n (the table of
 //                rt_step_rscan.hip, scan_seed_factor), 0 where the ray has escaped by m = n - 1; scale scales[s]
-// The shell is that of every step pass (rt_step_wg.inc, rt_step_handout.inc), rt_tile_ray.inc / rt_tile_rec.inc with SF = 0;
-// the backward method deposits at the LAUNCH ray, so pixel, angle cell and the runs of equal pixel are taken once per tile
-// for all records.
+// The kernel is made of the fragments of the scan passes: the shell (rt_step_scan_wg.inc), the tile preamble with the
+// placement at the LAUNCH ray, once per tile for all records (rt_step_scan_tile.inc), the serving state and the seed factors
+// (rt_step_scan_state.inc), the backward walk in its emission form and in its form with a seed set (rt_step_rscan_walk.inc)
+// and the close of a record (rt_step_scan_close.inc).
 //
 // Per tile the frequencies are walked in two halves (the HALVES of rt_step_ase_seeds.hip and rt_step_scan_ase_seeds.hip):
 //   the emission half   the chunked suffix walk of step_rscan_tile<true>, RSCAN_ASE_LCH_EMIS start segments per walk, and
@@ -51,89 +52,38 @@ namespace rt {
 
 constexpr int RSCAN_ASE_LCH_EMIS = 4, RSCAN_ASE_LCH_SEED = 3; // suffixes (start segments) per walk over a tile, per half
 
-// (rscan_seed_factor, the seed factor on a seed that stays in the argument block: rt_step_rscan.hip, shared with
-// rt_step_rscan_seeds.hip)
-
 __device__ __forceinline__ void step_rscan_ase_seeds_tile(const FreqHot &H, const unsigned hflags, ColdPtr C, ScanPtr Q, ScanAsePtr Z, const int n_seed,
                                                           double *lds_iang, double *lds_ev, const double *tab, double *xpose, const unsigned tile,
                                                           const int lane)
 {
-    constexpr int SF      = 0; // (the text fragments below read it: slots at run time)
-    constexpr int NS      = RT_N_SEED_MAX;
-    const int L           = H.L;
-    const int S           = L * RT_N_SUB;
-    const int K           = H.K;
-    const int Kp          = H.Kp;
-    const unsigned n_rays = H.n_rays;
-    const unsigned ridx   = tile * WAVE + (unsigned) lane;
-    const bool have       = ridx < n_rays;
-    const bool backward   = true; // the backward method: the suffix scan takes no other
-    const unsigned rrec      = have ? ridx : 0u;
-    const unsigned char *rec = H.rec;
-    const bool safe_check = (hflags & FQ_SAFE_CHECK) != 0, safe_skip = (hflags & FQ_SAFE_SKIP) != 0;
-    const bool probe_on   = (hflags & FQ_PROBE) != 0;
-    unsigned *bad32       = reinterpret_cast<unsigned *>(H.bad); // four words per ray: word r the records (r, n) of the ray, bit n - 2
-
-    // ---- per-ray preamble, once: the final state of the ray, its launch ray (rt_tile_ray.inc) ----
-#define TILE_NEED_RAY false
-#include "rt_tile_ray.inc"
-#undef TILE_NEED_RAY
-    if (__ballot(have) == 0ull)
-        return;
-    if (have && probe_on) {
-        C->probe.flags[ridx] = fl | (err1 ? F_ERR1 : 0u);
-        C->probe.steps[ridx] = steps;
-    }
-    // the marched segment the ray escaped in (never: L + 1)
-    const int n_done = (int) ((m.flags_steps >> REC_NDONE_SHIFT) & REC_NDONE_MASK);
-    const unsigned flags_steps = m.flags_steps; // (what the walks need of the final state; the rest is read again per chunk)
-    const int e_seg  = (fl & F_ESCAPED) ? (n_done > 0 ? (n_done - 1) / RT_N_SUB + 1 : 1) : L + 1;
-    // pixel and angle cell of the LAUNCH ray, one placement for all records, as step_rscan_tile takes it -- of a ray marked
-    // F_SKIP as well: the seed records take it
-    int pix = -1, ang = -1;
-    if (have) {
-        const unsigned pf = (hflags & ~(unsigned) (FQ_HAS_SEED | FQ_PROBE)) | (err1 ? 0u : (hflags & (unsigned) FQ_PROBE));
-        rt_ray launch     = ray;
-        if (!(hflags & FQ_OWN_CELLS)) { // (own cells: the grid point is the placement, no coordinate is read)
-            float ta, tb;
-            load_ray(R, ridx, launch, ta, tb, false);
-        }
-        const Placed P = place_ray(pf, C, R, H.nx, backward, ridx, m, fl, launch);
-        pix            = P.pix;
-        ang            = P.ang;
-    }
-    // the runs of equal pixel, one structure for all records: the last lane of a run owns the run's total of every record
-    // (a record's own depositing lanes are a subset of the run: the others add 0.0)
-    const bool has_pix = pix >= 0;
-#define RUNS_PIX pix
-#define RUNS_DEPOSITS has_pix
-#include "rt_wave_runs.inc"
-#undef RUNS_PIX
-#undef RUNS_DEPOSITS
-    (void) pix_prev;
-
-    // ---- the march record of this lane's ray (rt_tile_rec.inc; SF = 0: nothing to decode up front) ----
-#define TILE_MASK true
-#include "rt_tile_rec.inc"
-#undef TILE_MASK
-    (void) gs;
-    (void) rs;
-    (void) off;
-    (void) all_small;
-    (void) all_regular;
-    (void) load_rows;
-    (void) gv_nan; // (SF = 0 tests every frequency's lineshape values as it reads them)
-    const ConstF64 dv2 = (ConstF64) (unsigned long long) H.dv2;
+    constexpr int SF = 0; // (the text fragments below read it: slots at run time)
+    constexpr int NS = RT_N_SEED_MAX;
+#define SCAN_TILE_BACKWARD true // the backward method: the suffix scan takes no other
+#define SCAN_TILE_MARK unsigned // four words per ray: word r the records (r, n) of the ray, bit n - 2
+#define SCAN_TILE_HEAD
+#include "rt_step_scan_tile.inc"
+#undef SCAN_TILE_HEAD
+#undef SCAN_TILE_BACKWARD
+#undef SCAN_TILE_MARK
+    // one placement for all records, as step_rscan_tile takes it -- of a ray marked F_SKIP as well: the seed records take it
+#define SCAN_TILE_PLACED true
+#define SCAN_TILE_LAUNCH_PLACE
+#include "rt_step_scan_tile.inc"
+#undef SCAN_TILE_LAUNCH_PLACE
+#undef SCAN_TILE_PLACED
+#define SCAN_TILE_REC
+#include "rt_step_scan_tile.inc"
+#undef SCAN_TILE_REC
 
     unsigned code = 0u; // OR of this ray's codes over records and n
     // (both halves read the final state again per chunk, from memory: five registers that need not live across the
     // frequency loops, rt_step_rscan.hip)
 
-    // ================= the emission half: records (0, n), the text of step_rscan_tile<true> =================
+    // ================= the emission half: records (0, n), the walk of step_rscan_tile<true> =================
     // (a ray marked F_SKIP is not live for record 0: a tile of such rays, or of rays that are out for other reasons, skips it)
     if (__ballot(have && !(fl & F_SKIP)) != 0ull) {
         constexpr int LCH     = RSCAN_ASE_LCH_EMIS;
-        const unsigned marked = (safe_skip && have) ? bad32[4u * ridx] : 0u;
+        const unsigned marked = (safe_skip && have) ? mark[4u * ridx] : 0u;
         for (int a0 = 0; a0 < L; a0 += LCH) {
             // accumulator i of the chunk: the suffix whose first slot is 3 (a0 + i) -- the run of m = L - (a0 + i) marched
             // segments, record n = m + 1, block and bit m - 1
@@ -147,10 +97,15 @@ __device__ __forceinline__ void step_rscan_ase_seeds_tile(const FreqHot &H, cons
                 angsum[i] = 0.0;
                 if (a0 + i < L) {
                     const int mseg = L - (a0 + i);
-                    float ssz      = mc.sz;
-                    if (have && mseg < L && mseg < e_seg)
-                        ssz = reinterpret_cast<const float *>(Q->bnd + scan_bnd_off(ridx, mseg, L))[4];
-                    const bool e1 = have && (double) (ssz * ssz) < 0.01; // Helper.h:515 (reported by the seed half, for every record)
+                    // the state that serves this record: sz is all this half reads of it (error -1 is reported by the seed half,
+                    // for every record)
+#define SCAN_STATE_SEG mseg
+#define SCAN_STATE_SILENT
+#define SCAN_STATE_HELD
+#include "rt_step_scan_state.inc"
+#undef SCAN_STATE_HELD
+#undef SCAN_STATE_SILENT
+#undef SCAN_STATE_SEG
                     if (have && !e1 && !(fl & F_SKIP) && !((marked >> (mseg - 1)) & 1u))
                         live |= 1u << i;
                 }
@@ -159,122 +114,56 @@ __device__ __forceinline__ void step_rscan_ase_seeds_tile(const FreqHot &H, cons
             if (__ballot(live != 0u) == 0ull)
                 continue;
 
-            for (int kb = 0; kb < K; kb += VEC) {
-                double acc[LCH][VEC]; // the running Iv of every suffix
-                unsigned wnan = 0u;   // bit i * VEC + v: a NaN or infinity among frequency v's lineshape values since suffix i began
-#pragma unroll
-                for (int i = 0; i < LCH; i++) {
-#pragma unroll
-                    for (int v = 0; v < VEC; v++)
-                        acc[i][v] = 0.0;
-                }
-                // one sub-segment for the first NL accumulators: the SF = 0 text of rt_tile_batch.inc, its factor taken once
-                auto slot_step = [&](auto nl_tag, int s) {
-                    constexpr int NL = decltype(nl_tag)::value;
-                    asm volatile("" : "+s"(s)); // (opaque, as in rt_step_scan.hip: no slot addresses hoisted out of the frequency loop)
-                    const RecSlot sl = rec_slot_lazy(rec, rrec, H.rec_stride, s, S, flags_steps, backward);
-                    const float *row = H.gain[s / RT_N_SUB + 1].gv + (size_t) sl.c * (size_t) Kp + kb;
-                    const FVec w     = *reinterpret_cast<const FVec *>(row);
-                    const float g1 = sl.g, e1 = sl.e;
-                    unsigned wn = 0u;
-#pragma unroll
-                    for (int v = 0; v < VEC; v++)
-                        wn |= !(fabsf(w.v[v]) <= FLT_MAX) ? 1u << v : 0u;
-                    constexpr unsigned spread = NL >= 4 ? 0x1111u : NL == 3 ? 0x111u : NL == 2 ? 0x11u : 0x1u;
-                    static_assert(VEC == 4 && LCH <= 4, "wnan keeps VEC bits per accumulator, four accumulators at most");
-                    wnan |= wn * spread;
-                    if (fabsf(g1) >= RT_RS_MIN && fabsf(g1) <= H.gs_cap && !exact_emis) {
-                        const double r1 = div_fast((double) e1, (double) g1);
-                        ase_factor(g1, w.v, tab, [&](const int v, const double em1) {
-#pragma unroll
-                            for (int i = 0; i < NL; i++)
-                                acc[i][v] = fma(em1, acc[i][v] + r1, acc[i][v]);
-                        });
-                    } else if (g1 != 0.0f || e1 != 0.0f) {
-#pragma unroll
-                        for (int i = 0; i < NL; i++) {
-#pragma unroll
-                            for (int v = 0; v < VEC; v++)
-                                acc[i][v] = ase_update_call(acc[i][v], g1, e1, w.v[v], tab);
-                        }
-                    }
-                };
-                // the joining part: segment a0 + I is walked with accumulators 0 .. I (rt_step_rscan.hip)
-#define RSCAN_JOIN(I)                                                                                            \
-    if (I < LCH && a0 + I < L) {                                                                                 \
-        _Pragma("unroll 1") for (int t = 0; t < RT_N_SUB; t++)                                                   \
-            slot_step(std::integral_constant<int, (I < LCH ? I + 1 : LCH)>{}, (a0 + I) * RT_N_SUB + t);          \
-    }
-                RSCAN_JOIN(0)
-                RSCAN_JOIN(1)
-                RSCAN_JOIN(2)
-                RSCAN_JOIN(3)
-#undef RSCAN_JOIN
-                // ... and the segments behind the chunk's last start with all of them
-#pragma unroll 1
-                for (int s = (a0 + LCH) * RT_N_SUB; s < S; s++)
-                    slot_step(std::integral_constant<int, LCH>{}, s);
-
-                // ---- the walk has reached the end of the record: Iv of every suffix of the chunk ----
-#pragma unroll
-                for (int i = 0; i < LCH; i++) {
-                    if (a0 + i < L) {
-                        double Iv[VEC];
-#pragma unroll
-                        for (int v = 0; v < VEC; v++)
-                            Iv[v] = ((wnan >> (i * VEC + v)) & 1u) ? __builtin_nan("") : acc[i][v];
-#pragma unroll
-                        for (int v = 0; v < VEC; v++) {
-                            neg |= Iv[v] < 0.0 ? 1u << i : 0u; // (min over k of Iv negative, NaNs ignored: error -2, Helper.h:582-594)
-                            angsum[i] += dv2[kb + v] * Iv[v]; // RayTraceImageCPU.cpp:66: (2.0 * dv) * Iv
-                        }
-                        if (!safe_check) { // the checking pass of a failing run integrates without depositing
-                            const bool dep = has_pix && ((live >> i) & 1u);
-#define EV_SUM_DEPOSITS dep
-#define EV_SUM_INDEX (L - 1 - (a0 + i)) * Kp + kb
-#include "rt_step_evsum.inc"
-#undef EV_SUM_DEPOSITS
-#undef EV_SUM_INDEX
-                        }
-                    }
-                }
-            }
-            // ---- per record of the chunk: the failure test (Helper.h:582-594), the I_ang add, the segmented nf scan ----
+#define RSCAN_WALK_SUM(s) angsum[i]
+#define RSCAN_WALK_EMISSION
+#include "rt_step_rscan_walk.inc"
+#undef RSCAN_WALK_EMISSION
+#undef RSCAN_WALK_SUM
+            // ---- per record of the chunk: its close (rt_step_scan_close.inc) ----
 #pragma unroll
             for (int i = 0; i < LCH; i++) {
                 if (a0 + i < L) {
-                    const int jb       = L - 1 - (a0 + i); // block (within the ASE curve) and bit of this record
-                    const bool lv      = ((live >> i) & 1u) != 0u;
-                    const bool bad_neg = ((neg >> i) & 1u) != 0u, bad_nan = angsum[i] != angsum[i];
-                    const bool failing = bad_neg || bad_nan;
-                    if (lv && failing && !safe_skip) {
-                        const unsigned c = bad_neg ? (1u << 2) : (1u << 3);
-                        code |= c;
-                        atomicOr(&H.ctl->rec_len_code[0][jb], c);
-                        if (safe_check) // the lane that holds the ray writes its bits, chunk by chunk (a chunk's records are its own)
-                            bad32[4u * ridx] |= 1u << jb;
-                    }
+                    const int jb  = L - 1 - (a0 + i); // block (within the ASE curve) and bit of this record
+                    const bool lv = ((live >> i) & 1u) != 0u;
+#define SCAN_CLOSE_SUM angsum[i]
+#define SCAN_CLOSE_BIT i
+#define SCAN_CLOSE_LIVE lv
+#define SCAN_CLOSE_CODE H.ctl->rec_len_code[0][jb]
+                    // (the lane that holds the ray writes its bits, chunk by chunk: a chunk's records are its own)
+#define SCAN_CLOSE_MARK                                                                                          \
+    if (safe_check)                                                                                              \
+        mark[4u * ridx] |= 1u << jb;
+#define SCAN_CLOSE_TEST
+#include "rt_step_scan_close.inc"
+#undef SCAN_CLOSE_TEST
+#undef SCAN_CLOSE_BIT
+#undef SCAN_CLOSE_LIVE
+#undef SCAN_CLOSE_CODE
+#undef SCAN_CLOSE_MARK
                     if (!safe_check) {
-                        double *blk = Q->out + (size_t) jb * (size_t) Q->stride;
-                        // a failing ray adds nothing to this record (RayTraceImageCPU.cpp:29-36)
-                        if (ang >= 0 && lv && !failing) {
-                            if (lds_iang)
-                                unsafeAtomicAdd(&lds_iang[jb * seeds_ang_stride(H.n_ang) + ang], angsum[i]);
-                            else
-                                unsafeAtomicAdd(&blk[Q->ang_off + (unsigned) ang], angsum[i]);
-                        }
-                        // nf: the segmented scan over the runs of equal pixel of the tile (rt_wave_runscan.inc), one atomic per run tail
-                        double a = (has_pix && lv && !failing) ? angsum[i] * H.scale : 0.0;
-#include "rt_wave_runscan.inc"
-                        if (tail && a != 0.0)
-                            unsafeAtomicAdd(&blk[Q->nf_off + (unsigned) pix], a);
+#define SCAN_CLOSE_OK lv && !failing
+#define SCAN_CLOSE_BLOCK jb
+#define SCAN_CLOSE_ANG ang
+#define SCAN_CLOSE_PIX pix
+#define SCAN_CLOSE_HAS_PIX has_pix
+#define SCAN_CLOSE_SCALE H.scale
+#define SCAN_CLOSE_DEPOSIT
+#include "rt_step_scan_close.inc"
+#undef SCAN_CLOSE_DEPOSIT
+#undef SCAN_CLOSE_OK
+#undef SCAN_CLOSE_BLOCK
+#undef SCAN_CLOSE_ANG
+#undef SCAN_CLOSE_PIX
+#undef SCAN_CLOSE_HAS_PIX
+#undef SCAN_CLOSE_SCALE
                     }
+#undef SCAN_CLOSE_SUM
                 }
             }
         }
     }
 
-    // ================= the seed half: records (1 + s, n), the gain-only text of step_rscan_tile<false> per seed =================
+    // ================= the seed half: records (1 + s, n), the walk of step_rscan_seeds_tile, each record with its scale =================
     {
         constexpr int LCH = RSCAN_ASE_LCH_SEED;
         static_assert(NS * LCH <= 16, "live and neg keep one bit per (seed, accumulator)");
@@ -290,56 +179,30 @@ __device__ __forceinline__ void step_rscan_ase_seeds_tile(const FreqHot &H, cons
                 }
                 if (a0 + i < L) {
                     const int mseg = L - (a0 + i);
-                    // the state that serves this record: a boundary state or the final one, which begin with the same five floats
-                    // (position, direction) -- read where it is needed, so that no state is held across the seed factors
-                    static_assert(offsetof(RecMeta, px) == 0 && offsetof(RecMeta, sz) == 16, "a boundary state and a RecMeta begin alike");
-                    const bool at_bnd = mseg < L && mseg < e_seg;
-                    const bool esc    = !at_bnd && (fl & F_ESCAPED) != 0u;
-                    float spx = 0.0f, spy = 0.0f, ssx = 0.0f, ssy = 0.0f, ssz = 1.0f;
-                    if (have) {
-                        const float *q = reinterpret_cast<const float *>(at_bnd ? Q->bnd + scan_bnd_off(ridx, mseg, L)
-                                                                                : rec + rec_meta_off(rrec, S, H.rec_stride));
-                        spx            = q[0];
-                        spy            = q[1];
-                        ssx            = q[2];
-                        ssy            = q[3];
-                        ssz            = q[4];
-                    }
-                    const bool e1 = have && (double) (ssz * ssz) < 0.01; // Helper.h:515
-                    if (e1 && !safe_skip) { // error -1 under n, whatever the record: reported (once, below), out of every record (r, n)
-                        code |= 1u << 1;
-#pragma unroll
-                        for (int r = 0; r < 1 + NS; r++)
-                            if (r <= n_seed)
-                                atomicOr(&H.ctl->rec_len_code[r][mseg - 1], 1u << 1);
-                    }
+                    // the state that serves this record (error -1 under n whatever the record: out of every record (r, n))
+#define SCAN_STATE_SEG mseg
+#define SCAN_STATE_REPORT(b)                                                                                     \
+    _Pragma("unroll") for (int r = 0; r < 1 + NS; r++) if (r <= n_seed) atomicOr(&H.ctl->rec_len_code[r][b], 1u << 1);
+#define SCAN_STATE_READ
+#include "rt_step_scan_state.inc"
+#undef SCAN_STATE_READ
                     if (have && !e1) {
                         unsigned lv = 0u;
 #pragma unroll
                         for (int s = 0; s < NS; s++) {
                             if (s < n_seed) {
-                                const unsigned marked = safe_skip ? bad32[4u * ridx + 1u + (unsigned) s] : 0u;
+                                const unsigned marked = safe_skip ? mark[4u * ridx + 1u + (unsigned) s] : 0u;
                                 if (!((marked >> (mseg - 1)) & 1u))
                                     lv |= 1u << (s * LCH + i);
                             }
                         }
                         live |= lv;
-                        // the seed factors at this state's position and exit angles (place_ray's backward half, Helper.h:518-529);
-                        // 0 where the ray has escaped by m
-                        if (lv && !esc) {
-                            const float ea = atanf_flt32_kernel(ssx / ssz) * 1e3f;
-                            const float eb = atanf_flt32_kernel(ssy / ssz) * 1e3f;
-                            // (one copy of the text per accumulator: the seeds in a loop the compiler does not unroll, the factor
-                            // filed by selects)
-#pragma unroll 1
-                            for (int s = 0; s < n_seed; s++) {
-                                const double f = rscan_seed_factor(&Z->tabs.seed[s], (double) spx, (double) spy, (double) ea, (double) eb);
-#pragma unroll
-                                for (int t = 0; t < NS; t++)
-                                    f0[t][i] = t == s ? f : f0[t][i];
-                            }
-                        }
+#define SCAN_STATE_FACTORS
+#include "rt_step_scan_state.inc"
+#undef SCAN_STATE_FACTORS
                     }
+#undef SCAN_STATE_SEG
+#undef SCAN_STATE_REPORT
                 }
                 // (one state after the other, as rt_step_scan.hip places one length after the other)
                 asm volatile("" ::: "memory");
@@ -347,97 +210,16 @@ __device__ __forceinline__ void step_rscan_ase_seeds_tile(const FreqHot &H, cons
             if (__ballot(live != 0u) == 0ull)
                 continue;
 
-            for (int kb = 0; kb < K; kb += VEC) {
-                double acc[LCH][VEC]; // the running gl of every suffix
-#pragma unroll
-                for (int i = 0; i < LCH; i++) {
-#pragma unroll
-                    for (int v = 0; v < VEC; v++)
-                        acc[i][v] = 0.0;
-                }
-                // one sub-segment for the first NL accumulators: the gain-only SF = 0 text of rt_tile_batch.inc
-                auto slot_step = [&](auto nl_tag, int s) {
-                    constexpr int NL = decltype(nl_tag)::value;
-                    asm volatile("" : "+s"(s)); // (opaque, as in rt_step_scan.hip)
-                    const RecSlot sl = rec_slot_lazy(rec, rrec, H.rec_stride, s, S, flags_steps, backward);
-                    const float *row = H.gain[s / RT_N_SUB + 1].gv + (size_t) sl.c * (size_t) Kp + kb;
-                    const FVec w     = *reinterpret_cast<const FVec *>(row);
-#pragma unroll
-                    for (int i = 0; i < NL; i++) {
-#pragma unroll
-                        for (int v = 0; v < VEC; v++)
-                            acc[i][v] += (double) sl.g * (double) w.v[v];
-                    }
-                };
-#define RSCAN_JOIN(I)                                                                                            \
-    if (I < LCH && a0 + I < L) {                                                                                 \
-        _Pragma("unroll 1") for (int t = 0; t < RT_N_SUB; t++)                                                   \
-            slot_step(std::integral_constant<int, (I < LCH ? I + 1 : LCH)>{}, (a0 + I) * RT_N_SUB + t);          \
-    }
-                RSCAN_JOIN(0)
-                RSCAN_JOIN(1)
-                RSCAN_JOIN(2)
-                RSCAN_JOIN(3)
-#undef RSCAN_JOIN
-#pragma unroll 1
-                for (int s = (a0 + LCH) * RT_N_SUB; s < S; s++)
-                    slot_step(std::integral_constant<int, LCH>{}, s);
-
-                // ---- the walk has reached the end of the record: exp(gl) once per suffix, then Iv per seed ----
-#pragma unroll
-                for (int i = 0; i < LCH; i++) {
-                    if (a0 + i < L) {
-                        // a wave none of whose lanes needs the exponential skips it (rt_tile_batch.inc)
-                        bool need = false;
-#pragma unroll
-                        for (int s = 0; s < NS; s++)
-                            need = need || f0[s][i] != 0.0;
-#pragma unroll
-                        for (int v = 0; v < VEC; v++)
-                            need = need || acc[i][v] > 700.0 || acc[i][v] != acc[i][v];
-                        const bool with_exp = __ballot(need) != 0ull;
-                        double eg[VEC];
-#pragma unroll
-                        for (int v = 0; v < VEC; v++)
-                            eg[v] = 1.0;
-                        if (with_exp)
-                            exp_tab_vec(acc[i], tab, eg);
-#pragma unroll
-                        for (int s = 0; s < NS; s++) {
-                            if (s < n_seed) {
-                                const ConstF64 sfk = (ConstF64) (unsigned long long) Z->tabs.fk[s];
-                                double Iv[VEC];
-#pragma unroll
-                                for (int v = 0; v < VEC; v++)
-                                    Iv[v] = f0[s][i] * sfk[kb + v];
-                                if (with_exp) {
-#pragma unroll
-                                    for (int v = 0; v < VEC; v++)
-                                        Iv[v] *= eg[v];
-                                }
-#pragma unroll
-                                for (int v = 0; v < VEC; v++) {
-                                    neg |= Iv[v] < 0.0 ? 1u << (s * LCH + i) : 0u; // (error -2, Helper.h:582-594)
-                                    angsum[s][i] += dv2[kb + v] * Iv[v];           // RayTraceImageCPU.cpp:66: (2.0 * dv) * Iv
-                                }
-                                if (!safe_check) {
-                                    // E_v of (1 + s, n): the wave sum over the lanes that deposit into that record, its scale, its accumulator
-                                    const bool dep       = has_pix && ((live >> (s * LCH + i)) & 1u) != 0u;
-                                    const double scale_s = Z->scale[1 + s];
-#define EV_SUM_DEPOSITS dep
-#define EV_SUM_INDEX ((1 + s) * L + L - 1 - (a0 + i)) * Kp + kb
-#define EV_SUM_SCALE scale_s
-#include "rt_step_evsum.inc"
-#undef EV_SUM_DEPOSITS
-#undef EV_SUM_INDEX
-#undef EV_SUM_SCALE
-                                }
-                            }
-                        }
-                    }
-                }
-            }
-            // ---- per (seed, record) of the chunk: the failure test (Helper.h:582-594), the I_ang add, the segmented nf scan ----
+#define RSCAN_WALK_REC(s) (1 + s)
+#define RSCAN_WALK_SUM(s) angsum[s][i]
+#define RSCAN_WALK_SCALE(s) Z->scale[1 + s]
+#define RSCAN_WALK_SEEDS
+#include "rt_step_rscan_walk.inc"
+#undef RSCAN_WALK_SEEDS
+#undef RSCAN_WALK_REC
+#undef RSCAN_WALK_SUM
+#undef RSCAN_WALK_SCALE
+            // ---- per (seed, record) of the chunk: its close (rt_step_scan_close.inc) ----
 #pragma unroll
             for (int i = 0; i < LCH; i++) {
                 if (a0 + i < L) {
@@ -445,30 +227,39 @@ __device__ __forceinline__ void step_rscan_ase_seeds_tile(const FreqHot &H, cons
 #pragma unroll
                     for (int s = 0; s < NS; s++) {
                         if (s < n_seed) {
-                            const bool lv      = ((live >> (s * LCH + i)) & 1u) != 0u;
-                            const bool bad_neg = ((neg >> (s * LCH + i)) & 1u) != 0u, bad_nan = angsum[s][i] != angsum[s][i];
-                            const bool failing = bad_neg || bad_nan;
-                            if (lv && failing && !safe_skip) {
-                                const unsigned c = bad_neg ? (1u << 2) : (1u << 3);
-                                code |= c;
-                                atomicOr(&H.ctl->rec_len_code[1 + s][jb], c);
-                                if (safe_check)
-                                    bad32[4u * ridx + 1u + (unsigned) s] |= 1u << jb;
-                            }
+                            const bool lv = ((live >> (s * LCH + i)) & 1u) != 0u;
+#define SCAN_CLOSE_SUM angsum[s][i]
+#define SCAN_CLOSE_BIT s * LCH + i
+#define SCAN_CLOSE_LIVE lv
+#define SCAN_CLOSE_CODE H.ctl->rec_len_code[1 + s][jb]
+#define SCAN_CLOSE_MARK                                                                                          \
+    if (safe_check)                                                                                              \
+        mark[4u * ridx + 1u + (unsigned) s] |= 1u << jb;
+#define SCAN_CLOSE_TEST
+#include "rt_step_scan_close.inc"
+#undef SCAN_CLOSE_TEST
+#undef SCAN_CLOSE_BIT
+#undef SCAN_CLOSE_LIVE
+#undef SCAN_CLOSE_CODE
+#undef SCAN_CLOSE_MARK
                             if (!safe_check) {
-                                double *blk = Q->out + (size_t) ((1 + s) * L + jb) * (size_t) Q->stride;
-                                // a ray that fails under (1 + s, n) adds nothing to that record (RayTraceImageCPU.cpp:29-36)
-                                if (ang >= 0 && lv && !failing) {
-                                    if (lds_iang)
-                                        unsafeAtomicAdd(&lds_iang[((1 + s) * L + jb) * seeds_ang_stride(H.n_ang) + ang], angsum[s][i]);
-                                    else
-                                        unsafeAtomicAdd(&blk[Q->ang_off + (unsigned) ang], angsum[s][i]);
-                                }
-                                double a = (has_pix && lv && !failing) ? angsum[s][i] * Z->scale[1 + s] : 0.0;
-#include "rt_wave_runscan.inc"
-                                if (tail && a != 0.0)
-                                    unsafeAtomicAdd(&blk[Q->nf_off + (unsigned) pix], a);
+#define SCAN_CLOSE_OK lv && !failing
+#define SCAN_CLOSE_BLOCK (1 + s) * L + jb
+#define SCAN_CLOSE_ANG ang
+#define SCAN_CLOSE_PIX pix
+#define SCAN_CLOSE_HAS_PIX has_pix
+#define SCAN_CLOSE_SCALE Z->scale[1 + s]
+#define SCAN_CLOSE_DEPOSIT
+#include "rt_step_scan_close.inc"
+#undef SCAN_CLOSE_DEPOSIT
+#undef SCAN_CLOSE_OK
+#undef SCAN_CLOSE_BLOCK
+#undef SCAN_CLOSE_ANG
+#undef SCAN_CLOSE_PIX
+#undef SCAN_CLOSE_HAS_PIX
+#undef SCAN_CLOSE_SCALE
                             }
+#undef SCAN_CLOSE_SUM
                         }
                     }
                 }
@@ -479,45 +270,20 @@ __device__ __forceinline__ void step_rscan_ase_seeds_tile(const FreqHot &H, cons
         report_failure(code);
 }
 
-// The shell of rt_step_scan_ase_seeds_kernel, word for word: one record per (record of the step, n), per record an I_ang
-// histogram, seeds_ang_stride(na*nb) doubles apart, and an E_v accumulator.  The launch bounds of rt_step_rscan_kernel<true>.
+// (the launch bounds of rt_step_rscan_kernel<true>)
 __global__ void __launch_bounds__(FREQ_WG_WAVES * 64, FREQ_WAVES) rt_step_rscan_ase_seeds_kernel(const ScanAseSeedsKArg A)
 {
-    const FreqHot &H = A.hot;
-#define STEP_WG_NREC (1 + A.set.n_seed) * H.L
-#define STEP_WG_ANG_STRIDE seeds_ang_stride(n_ang)
-#define STEP_WG_ANG_ZERO n_rec * ang_stride
-#define STEP_WG_RECORD(r) double *blk = A.scan.out + (size_t) r * (size_t) A.scan.stride;
-#define STEP_WG_EV(r, c) blk[c]
-#define STEP_WG_IANG(r, c) blk[A.scan.ang_off + c]
-#define STEP_WG_PROLOGUE
-#include "rt_step_wg.inc"
-#undef STEP_WG_PROLOGUE
-    const int lane = lane_id();
-    // the cold half, the scan block and the seeds of the argument block, the flag word and the lane number opaque per tile
-#define HANDOUT_TILES_PER_FETCH FREQ_TILES_PER_FETCH_EMIS
-#define HANDOUT_TILE                                                                                                                   \
-    ColdPtr C    = (ColdPtr) ((const RT_CONST_AS char *) __builtin_amdgcn_kernarg_segment_ptr() + offsetof(ScanAseSeedsKArg, cold));  \
-    ScanPtr Q    = (ScanPtr) ((const RT_CONST_AS char *) __builtin_amdgcn_kernarg_segment_ptr() + offsetof(ScanAseSeedsKArg, scan));  \
-    ScanAsePtr Z = (ScanAsePtr) ((const RT_CONST_AS char *) __builtin_amdgcn_kernarg_segment_ptr() + offsetof(ScanAseSeedsKArg, set)); \
-    asm volatile("" : "+s"(C), "+s"(Q), "+s"(Z));                                                                                      \
-    unsigned hflags = H.flags;                                                                                                         \
-    int lane_t      = lane;                                                                                                            \
-    int n_seed_t    = A.set.n_seed;                                                                                                    \
-    asm volatile("" : "+s"(hflags), "+v"(lane_t), "+s"(n_seed_t));                                                                     \
-    step_rscan_ase_seeds_tile(H, hflags, C, Q, Z, n_seed_t, lds_iang, lds_ev, exp2_tab, xpose, tile, lane_t);
-#include "rt_step_handout.inc"
-#undef HANDOUT_TILES_PER_FETCH
-#undef HANDOUT_TILE
-#define STEP_WG_EPILOGUE
-#include "rt_step_wg.inc"
-#undef STEP_WG_EPILOGUE
-#undef STEP_WG_NREC
-#undef STEP_WG_ANG_STRIDE
-#undef STEP_WG_ANG_ZERO
-#undef STEP_WG_RECORD
-#undef STEP_WG_EV
-#undef STEP_WG_IANG
+#define SCAN_WG_KARG ScanAseSeedsKArg
+#define SCAN_WG_NREC (1 + A.set.n_seed) * H.L
+#define SCAN_WG_TILES_PER_FETCH FREQ_TILES_PER_FETCH_EMIS
+#define SCAN_WG_SET ScanAsePtr
+#define SCAN_WG_TILE step_rscan_ase_seeds_tile
+#include "rt_step_scan_wg.inc"
+#undef SCAN_WG_KARG
+#undef SCAN_WG_NREC
+#undef SCAN_WG_TILES_PER_FETCH
+#undef SCAN_WG_SET
+#undef SCAN_WG_TILE
 }
 
 } // namespace rt
