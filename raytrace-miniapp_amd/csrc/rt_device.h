@@ -38,6 +38,9 @@ struct DevGain {
 // out so that a work-group can copy the whole blob into LDS verbatim.
 //   blob = BlobGain[N] | per length: Interval x[Nx] | Interval y[Ny] | Node[Nx*Ny]
 // off_* are byte offsets from the start of the blob (16-byte aligned).
+// rt_hip_plan_create refuses a length with more than RT_MARCH_MAX_NODES grid points and a blob of 2^31 bytes or more: the
+// march forms `off + number x size` with a 24-bit multiply in 32 bits (rt_march_cell.inc).
+constexpr unsigned long long RT_MARCH_MAX_NODES = (1ull << 24) - 1ull, RT_MARCH_MAX_BLOB = 1ull << 31;
 struct alignas(16) BlobGain {
     float lo_x, hi_x, lo_y, hi_y; // plasma box as floats (Helper.h:445-453), lo_y = -hi_y if mirrored
     int Nx, Ny, mirror_y, off_ix;

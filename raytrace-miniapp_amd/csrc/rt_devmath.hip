@@ -317,7 +317,8 @@ __global__ void __launch_bounds__(DM_BLOCK) dm_march_xsetup_kernel(const float *
     for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < padded; i += stride) {
         const size_t c  = i < n_cases ? i : n_cases - 1;
         const float px = fin[4 * c], py = fin[4 * c + 1];
-        const bool mirror = mirror_in[c] != 0;
+        BlobGain G        = {}; // (the fragment reads one word of the lane's header: whether the y axis is mirrored)
+        G.mirror_y        = mirror_in[c] != 0 ? 1 : 0;
         const double *d   = din + 8 * c;
         const f64x2 ix0 = { d[0], d[1] }, iy0 = { d[2], d[3] };
         const f32x4 ix1 = { fin[4 * c + 2], 0.0f, 0.0f, 0.0f }, iy1 = { fin[4 * c + 3], 0.0f, 0.0f, 0.0f };
@@ -373,11 +374,11 @@ __global__ void __launch_bounds__(DM_BLOCK) dm_march_cell_kernel(const unsigned 
         const float px = fin[DM_CELL_IN * c], py = fin[DM_CELL_IN * c + 1], sz = fin[DM_CELL_IN * c + 2];
         float z = fin[DM_CELL_IN * c + 3];
         const float z_stop = fin[DM_CELL_IN * c + 4];
-        const BlobGain G   = hdr[len[c]];
+        const BlobGain G   = march_blob_header(hdr, len[c], lds_base);
         // the lane state block [A2] writes, as march_wave declares it
         int st = ST_CELL, c00 = -1, cell_last = -1;
         unsigned steps = 0;
-        bool escaped = false, mirror = false, regather = false;
+        bool regather  = false;
         float f00 = 1, f10 = 1, f01 = 1, f11 = 1;
         double dnx0 = 0, dnx1 = 0, dny0 = 0, dny1 = 0;
         f64x2 ix0 = { 0.0, 1.0 }, iy0 = { 0.0, 1.0 };
@@ -393,10 +394,13 @@ __global__ void __launch_bounds__(DM_BLOCK) dm_march_cell_kernel(const unsigned 
             int *io    = iout + DM_CELL_I * i;
             float *fo  = fout + DM_CELL_F * i;
             double *dd = dout + DM_CELL_D * i;
+            // (whether the ray escaped is one of the lane's states, and the mirrored axis a word of its header: the columns
+            // keep what they held when the two were flags beside `st` -- 1 = the lane waits for block [A], 2 = for [B])
+            const bool escaped = st == ST_ESC;
             io[0]      = escaped ? 1 : 0;
-            io[1]      = st;
+            io[1]      = st == ST_XSETUP ? 2 : 1;
             io[2]      = c00;
-            io[3]      = mirror ? 1 : 0;
+            io[3]      = (!escaped && G.mirror_y != 0) ? 1 : 0;
             io[4]      = regather ? 1 : 0;
             io[5]      = (int) steps;
             io[6]      = cell_last;

@@ -31,7 +31,16 @@ namespace rt {
 
 // (ST_DONE: the lane's ray has finished and waits to be retired, march_wave "ray finished"; it sorts below ST_IDLE so that
 // one comparison, st <= ST_IDLE, finds the lanes without a marching ray)
-enum : int { ST_DONE = -1, ST_IDLE = 0, ST_CELL = 1, ST_XSETUP = 2, ST_STEP = 3 };
+// Whether the lane's ray has escaped is part of the state, not a flag beside it: ST_ESC is the cell state of an escaped ray --
+// it waits for block [A] as ST_CELL does, commits its slot in [A1] and finishes there -- and ST_DONE_ESC is ST_DONE for such
+// a ray.  The two states that wait for [A] sort above the others, so that one comparison, st >= ST_CELL, finds them, and
+// [A1] finishes a ray of either kind with one subtraction: ST_CELL + ST_DONE - st.  (Lane state that is written under
+// divergent control flow lives in a VGPR: as a `bool` the compiler keeps it as a 64-bit lane mask in an SGPR pair and
+// re-merges the mask at the closing brace of every nested `if` that may set it)
+enum : int { ST_DONE_ESC = -2, ST_DONE = -1, ST_IDLE = 0, ST_STEP = 1, ST_XSETUP = 2, ST_CELL = 3, ST_ESC = 4 };
+static_assert(ST_CELL + ST_DONE - ST_CELL == ST_DONE && ST_CELL + ST_DONE - ST_ESC == ST_DONE_ESC && ST_DONE_ESC < ST_IDLE &&
+                  ST_DONE < ST_IDLE && ST_ESC > ST_CELL && ST_CELL > ST_XSETUP && ST_CELL > ST_STEP,
+              "the order of the lane states");
 
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -552,13 +561,13 @@ struct MarchDiag {
     {
 #ifdef RT_TIMEBLOCKS
         // (called by the lanes in [A1] only: one of them counts, and wave_end adds the lanes up, as for `tick`)
-        rt_fin += (__ballot(st == ST_DONE) != 0ull && first_active_lane()) ? 1u : 0u;
+        rt_fin += (__ballot(st < ST_IDLE) != 0ull && first_active_lane()) ? 1u : 0u;
 #endif
     }
     __device__ __forceinline__ void retire_block(int st, bool more)
     {
 #ifdef RT_TIMEBLOCKS
-        rt_blk += __ballot(st == ST_DONE) != 0ull ? 1u : 0u;
+        rt_blk += __ballot(st < ST_IDLE) != 0ull ? 1u : 0u;
         rt_dry += more ? 0u : 1u;
 #endif
     }
@@ -834,6 +843,16 @@ RT_HD inline size_t scan_bnd_bytes(unsigned long long n_rays, int L)
 {
     return (size_t) ((n_rays + WAVE - 1) / WAVE) * (size_t) (L > 1 ? L - 1 : 0) * SCAN_BND_ROW;
 }
+// Header of length i of the march blob as the lane state G holds it: the three table offsets with the blob's LDS address
+// added (lds_base; 0 for a blob read in place), so that block [A2] adds nothing to them per gather (rt_march_cell.inc).
+__device__ __forceinline__ BlobGain march_blob_header(const BlobGain *hdr, int i, unsigned lds_base)
+{
+    BlobGain g = hdr[i];
+    g.off_ix   = (int) ((unsigned) g.off_ix + lds_base);
+    g.off_iy   = (int) ((unsigned) g.off_iy + lds_base);
+    g.off_node = (int) ((unsigned) g.off_node + lds_base);
+    return g;
+}
 template <bool LDS_TAB, bool BOUNDED, bool FUSED, int MODE = 0, int OPT = 0>
 __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *lds_raw, const TileList done)
 {
@@ -898,14 +917,16 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
     unsigned ridx = 0;
     int seg = 0, iz = 0, ii = 0;
     float z = 0.0f, z_stop = 0.0f;
+    float z_lim = 0.0f; // 0.995f * z_stop, what [A1] tests z against (Helper.h:463): formed where z_stop is assigned
     float px = 0, py = 0, pz = 0, sx = 0, sy = 0, sz = 1;
     float gacc = 0, eacc = 0;
     int cell_last = 0, sub = 0; // sub: sub-segments committed so far (slots written), 0 .. S
     unsigned char *recp = P.rec; // slot of the lane's current sub-segment inside its ray's record
     unsigned lane12     = 0;     // 12 x (the ray's place in its tile): what the meta block lies beyond the tile's slot rows
-    BlobGain G    = hdr[1]; // header of the lane's current length ii, re-read only when ii changes
+    // header of the lane's current length ii, re-read only when ii changes; G.mirror_y is what [A2], [B] and the close of [C]
+    // test for the mirrored y axis: a lane reaches [B] and [C] only behind an [A2] that ran with the same G
+    BlobGain G    = march_blob_header(hdr, 1, lds_base);
     unsigned steps = 0;
-    bool escaped = false, mirror = false;
     unsigned any_bits = 0; // OR of the magnitude bits of every committed gain / emission sum: 0 <=> all were zero
     // cell
     int c00 = 0;                              // index of the lower-left corner node of the current cell
@@ -950,9 +971,8 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
             if (((++spin) & 0xfffu) == 0u && spin >= P.spin_limit) {
                 spin = 0;
                 if (st > ST_IDLE) { // (not a lane that waits to be retired: it would retire twice)
-                    escaped = true;
                     sx = sy = sz = 0.0f;
-                    st           = ST_CELL;
+                    st           = ST_ESC;
                 }
             }
         }
@@ -968,8 +988,9 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
             // [A]; here it hides behind the refill test, and that test is one scalar compare: -2 %)
             diag.mark(0);
             diag.retire_block(st, more);
-            if (st == ST_DONE) {
-                unsigned fl = F_VALID;
+            if (st < ST_IDLE) { // ST_DONE, ST_DONE_ESC
+                const bool escaped = st == ST_DONE_ESC;
+                unsigned fl        = F_VALID;
                 if (escaped)
                     fl |= F_ESCAPED;
                 if (use_emis && any_bits == 0u)
@@ -1105,7 +1126,7 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
                     // Helper.h:515 reports for a direction it cannot use): no march, direction zeroed so that the
                     // s.z^2 < 0.01 test of the frequency kernel sees it.  (A NaN ray that starts outside the plasma
                     // escapes in the reference as well and is left alone.)
-                    const BlobGain G0 = hdr[backward ? P.N - 1 : 1];
+                    const BlobGain G0 = march_blob_header(hdr, backward ? P.N - 1 : 1, lds_base);
                     const float dsum  = sx + sy + sz;
                     const bool wild   = ((px != px) | (py != py) | (dsum != dsum)) &
                                       !((px < G0.lo_x) | (px > G0.hi_x) | (py < G0.lo_y) | (py > G0.hi_y));
@@ -1123,17 +1144,17 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
                     G         = G0;
                     z         = 0.0f;
                     z_stop    = zs0;
+                    z_lim     = 0.995f * zs0;
                     gacc      = 0.0f;
                     eacc      = 0.0f;
                     cell_last = 0;
                     steps     = 0;
-                    escaped   = wild; // (an escaped ray commits one empty slot and retires, block [A1])
                     sx        = wild ? 0.0f : sx;
                     sy        = wild ? 0.0f : sy;
                     sz        = wild ? 0.0f : sz;
                     any_bits  = P.no_skip; // (non-zero: this ray is never marked F_SKIP -- a lineshape table holds a NaN, see DevParams)
                     sub       = 0;
-                    st        = ST_CELL;
+                    st        = wild ? ST_ESC : ST_CELL; // (an escaped ray commits one empty slot and retires, block [A1])
                 }
                 idle2 = __ballot(st == ST_IDLE); // (no lane waits to be retired here)
             }
@@ -1158,7 +1179,7 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
         // each of them wait for all the others: 1024 rays took 0.34 ms with it, as long as 400 000)
         // (while the ray counter still has rays the wave holds more than 64 - REFILL of them, a fifth of which is 12:
         // for P.park <= 12 the threshold is P.park itself, and the adaptive form runs only in the tail of the launch)
-        const unsigned long long want_a = __ballot(st == ST_CELL);
+        const unsigned long long want_a = __ballot(st >= ST_CELL); // ST_CELL, ST_ESC
         int park_at = (int) P.park;
         if (!more || (int) P.park > 12 || REFILL > 8) {
             const int n_live = WAVE - (int) __popcll(idle2);
@@ -1167,8 +1188,8 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
         }
         const bool do_a = (int) __popcll(want_a) >= park_at || (~(idle2 | want_a)) == 0ull;
         diag.blocks_run(do_a && want_a != 0ull, st == ST_XSETUP);
-        if (do_a && st == ST_CELL) {
-            bool in_seg        = !escaped & (z < 0.995f * z_stop);
+        if (do_a && st >= ST_CELL) {
+            bool in_seg        = (st == ST_CELL) & (z < z_lim);
             if (!in_seg) {
                 // [A1] end of this sub-segment: commit its slot (Helper.h:501-503 accumulate from 0),
                 // slot (ii - 1) * 3 + (backward ? 2 - iz : iz); straight-line, selects instead of branches
@@ -1180,7 +1201,7 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
                 if (path_on) { // Helper.h:505-511: every remaining sub-segment of an escaped ray's
                                  // segment records the same position, later segments stay zero
                     float *pp = P.path + (size_t) ridx * 3 * (size_t) (S + 1);
-                    for (int zz = iz; zz < (escaped ? RT_N_SUB : iz + 1); zz++) {
+                    for (int zz = iz; zz < (st == ST_ESC ? RT_N_SUB : iz + 1); zz++) {
                         const int idx = RT_N_SUB * (ii - 1) + (backward ? RT_N_SUB - zz - 1 : zz + 1);
                         pp[3 * idx]     = px;
                         pp[3 * idx + 1] = py;
@@ -1193,10 +1214,11 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
                 // an escaped ray never enters its remaining sub-segments: `sub` tells the readers
                 // (RecMeta n_done); otherwise on to the next sub-segment, or the next segment
                 const bool wrap = iz == RT_N_SUB - 1;
-                const bool fin  = escaped | (sub == S);
+                const bool fin  = (st == ST_ESC) | (sub == S);
                 iz              = wrap ? 0 : iz + 1;
                 z               = wrap ? 0.0f : z;
-                st              = fin ? ST_DONE : ST_CELL; // (finished: retired at the loop head, "ray finished")
+                // (finished: ST_DONE, or ST_DONE_ESC from ST_ESC; retired at the loop head, "ray finished")
+                st              = fin ? ST_CELL + ST_DONE - st : ST_CELL;
                 diag.finishing(st);
                 if (wrap & !fin) { // twice per ray
                     if (OPT & MARCH_OPT_SCAN) { // the ray leaves length seg + 1 for the next: its state there (rt_step_scan.hip)
@@ -1210,13 +1232,14 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
                     }
                     seg++;
                     ii = backward ? P.N - seg - 1 : seg + 1;
-                    G  = hdr[ii];
+                    G  = march_blob_header(hdr, ii, lds_base);
                 }
                 z_stop = iz == 0 ? zs0 : (iz == 1 ? zs1 : zs2);
-                in_seg = !fin & (z < 0.995f * z_stop);
+                z_lim  = 0.995f * z_stop;
+                in_seg = !fin & (z < z_lim);
             }
             diag.mark(1); // [A1]
-            if ((st == ST_CELL) & in_seg) {
+            if (in_seg) { // (a lane in ST_CELL whose ray has not escaped, with or without [A1])
 #include "rt_march_cell.inc"
             }
         }
@@ -1257,7 +1280,7 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
                 py += ry;
                 pz += rz;
                 zc += fabsf(rz);
-                const float ya = mirror ? fabsf(py) : py;
+                const float ya = G.mirror_y != 0 ? fabsf(py) : py; // (G: the header [A2] ran with)
                 if ((px > ix1.y) & (px < ix1.z) & (ya > iy1.y) & (ya < iy1.z) & ((double) zc < 0.999 * (double) dzrem)) {
                     st = ST_XSETUP;
                 } else {

@@ -4,13 +4,14 @@
 // cell, g0 and E0 at the ray, and whether a cross-cell iteration happens at all.
 //
 // A fragment of a function body, not a header (rt_tile_rec.inc says why text): march_wave includes it inside
-// `if ((st == ST_CELL) & in_seg)`, behind the sub-segment commit [A1], which stays there; the unit test dm_march_cell_kernel
+// `if (in_seg)` (a lane in ST_CELL whose ray has not escaped), behind the sub-segment commit [A1], which stays there; the unit test dm_march_cell_kernel
 // (rt_devmath.hip) includes it alone, one case per lane.
 //
-// Reads from the including scope: px, py, sz, z, z_stop; G, the BlobGain header of the lane's length; tab, the march blob
-//   (global memory, or LDS when LDS_TAB) and lds_base, its LDS address (LDS_TAB only: the ds_read_b128 gather addresses LDS from
-//   there, and the kernel must have no static LDS in front of it); use_emis; the template parameter LDS_TAB; diag (tick).
-// Writes: escaped (set, never cleared), or else mirror, c00, the lane state ix0, ix1, iy0, iy1 = {lo, rw}, {w, b_lo, b_hi, -} of
+// Reads from the including scope: px, py, sz, z, z_stop; G, the BlobGain header of the lane's length, with lds_base already added
+//   to its three offsets off_ix, off_iy, off_node (march_blob_header, rt_march.hip: once per header load, not once per gather);
+//   tab, the march blob (global memory, or LDS when LDS_TAB) and lds_base, its LDS address (0 unless LDS_TAB; the ds_read_b128
+//   gather addresses LDS by G's offsets as they are); use_emis; the template parameter LDS_TAB; diag (tick).
+// Writes: st = ST_ESC for a ray that has escaped (its slot is committed by [A1] in the next iteration), or else c00, the lane state ix0, ix1, iy0, iy1 = {lo, rw}, {w, b_lo, b_hi, -} of
 //   either axis, the corner indices as floats f00, f10, f01, f11 and their edge differences dnx0, dnx1, dny0, dny1, g0, E0,
 //   pz = zc = path = 0, dzrem, and st = ST_XSETUP -- or, with no cross-cell iteration, the closed cell step: z, gacc, eacc,
 //   cell_last, steps (st stays ST_CELL).
@@ -19,13 +20,14 @@
                 // [A2] escape test + cell setup (Helper.h:465-497)
                 // (double)(sz*sz) < 0.01 (Helper.h:466) <=> sz*sz <= 0.01f: 0.01f is the largest float below 0.01
                 if ((px < G.lo_x) | (px > G.hi_x) | (py < G.lo_y) | (py > G.hi_y) | (sz * sz <= 0.01f)) {
-                    escaped = true; // its slot is committed by [A1] next iteration
+                    st = ST_ESC; // its slot is committed by [A1] next iteration
                 } else {
-                    mirror              = G.mirror_y != 0;
-                    const Interval *ivx = reinterpret_cast<const Interval *>(tab + G.off_ix);
-                    const Interval *ivy = reinterpret_cast<const Interval *>(tab + G.off_iy);
+                    const Interval *ivx = reinterpret_cast<const Interval *>(tab + ((unsigned) G.off_ix - lds_base));
+                    const Interval *ivy = reinterpret_cast<const Interval *>(tab + ((unsigned) G.off_iy - lds_base));
                     // (records are addressed by 32-bit byte offsets from the start of the blob: no
-                    // 64-bit multiplies for what is an LDS address)
+                    // 64-bit multiplies for what is an LDS address.  Interval and node numbers are below 2^24 and the blob
+                    // is below 2^31 bytes -- rt_hip_plan_create refuses anything else, RT_MARCH_MAX_NODES / RT_MARCH_MAX_BLOB
+                    // in rt_device.h -- so a 24-bit multiply-add forms the offset exactly: one v_mad_u32_u24 each.)
                     // One round of gathers per cell: two 48-byte interval records and four 16-byte corner nodes (the
                     // two nodes of a grid row are neighbours), ten 16-byte reads issued together.  In the LDS variant
                     // they are written as ds_read_b128 instructions whose results ARE the lane-state registers
@@ -36,13 +38,16 @@
                     f64x2 tx, ty;            // {hi, rh} of the two intervals
                     u32x4 q00, q10, q01, q11; // corner nodes {n (f64) | g0 | E0}
                     auto gather = [&](int k1, int k2, int c) {
-                        const unsigned ox = (unsigned) G.off_ix + (unsigned) k1 * (unsigned) sizeof(Interval);
-                        const unsigned oy = (unsigned) G.off_iy + (unsigned) k2 * (unsigned) sizeof(Interval);
-                        const unsigned oa = (unsigned) G.off_node + (unsigned) c * (unsigned) sizeof(Node);
-                        const unsigned ob = oa + (unsigned) G.Nx * (unsigned) sizeof(Node);
+                        const unsigned ox = __umul24((unsigned) k1, (unsigned) sizeof(Interval)) + (unsigned) G.off_ix;
+                        const unsigned oy = __umul24((unsigned) k2, (unsigned) sizeof(Interval)) + (unsigned) G.off_iy;
+                        // (a node is 16 bytes: shift-adds, v_lshl_add_u32 -- a 24-bit multiply by a power of two becomes
+                        // a shift and a mask)
+                        static_assert(sizeof(Node) == 16, "node offsets are formed by a shift");
+                        const unsigned oa = ((unsigned) c << 4) + (unsigned) G.off_node;
+                        const unsigned ob = ((unsigned) G.Nx << 4) + oa;
                         if (LDS_TAB) {
-                            // (lds_raw starts at LDS address 0: the kernel has no static LDS; the reads complete
-                            // inside the statement, so the compiler's own wait counters stay right)
+                            // (G's offsets are LDS addresses here; the reads complete inside the statement, so the
+                            // compiler's own wait counters stay right)
                             asm volatile("ds_read_b128 %0, %10\n\t"
                                          "ds_read_b128 %1, %10 offset:16\n\t"
                                          "ds_read_b128 %2, %10 offset:32\n\t"
@@ -56,9 +61,9 @@
                                          "s_waitcnt lgkmcnt(0)"
                                          : "=&v"(ix0), "=&v"(ix1), "=&v"(tx), "=&v"(iy0), "=&v"(iy1), "=&v"(ty), "=&v"(q00), "=&v"(q10),
                                            "=&v"(q01), "=&v"(q11)
-                                         : "v"(lds_base + ox), "v"(lds_base + oy), "v"(lds_base + oa), "v"(lds_base + ob));
+                                         : "v"(ox), "v"(oy), "v"(oa), "v"(ob));
                         } else {
-                            const unsigned char *t = tab;
+                            const unsigned char *t = tab; // (lds_base = 0: 64-bit base + 32-bit offset)
                             ix0 = *reinterpret_cast<const f64x2 *>(t + ox);
                             ix1 = *reinterpret_cast<const f32x4 *>(t + ox + 16);
                             tx  = *reinterpret_cast<const f64x2 *>(t + ox + 32);
@@ -72,19 +77,19 @@
                         }
                     };
                     auto node_n = [](const u32x4 &q) { return __hiloint2double((int) q.y, (int) q.x); };
-                    const float ya      = mirror ? fabsf(py) : py;
+                    const float ya      = G.mirror_y != 0 ? fabsf(py) : py; // (a header word, not lane state: [B] and [C] test it themselves)
                     const double pxd = (double) px, yad = (double) ya;
                     // one round of gathers on the guessed cell: two interval records, four nodes
                     int k1     = guess_interval(G.Nx, G.x0f, G.inv_hxf, px);
                     int k2     = guess_interval(G.Ny, G.y0f, G.inv_hyf, ya);
-                    c00        = (k1 - 1) + (k2 - 1) * G.Nx;
+                    c00        = (k1 - 1) + __mul24(k2 - 1, G.Nx); // (a node number: both factors and the product below 2^24)
                     gather(k1, k2, c00);
                     const bool ok = ((k1 == 1) | (ix0.x < pxd)) & ((k1 == G.Nx - 1) | (tx.x >= pxd)) &
                                     ((k2 == 1) | (iy0.x < yad)) & ((k2 == G.Ny - 1) | (ty.x >= yad));
                     if (!ok) {
                         k1  = bisect_interval(ivx, G.Nx, pxd);
                         k2  = bisect_interval(ivy, G.Ny, yad);
-                        c00 = (k1 - 1) + (k2 - 1) * G.Nx;
+                        c00 = (k1 - 1) + __mul24(k2 - 1, G.Nx);
                         gather(k1, k2, c00);
                     }
                     const double n00 = node_n(q00), n10 = node_n(q10), n01 = node_n(q01), n11 = node_n(q11);

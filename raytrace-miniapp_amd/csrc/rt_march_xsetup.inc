@@ -5,12 +5,13 @@
 // `if (st == ST_XSETUP)`, in front of the state resets of the integrator (lim2, dzcap, r = 0, ...), which stay there; the unit
 // test dm_march_xsetup_kernel (rt_devmath.hip) includes it alone, one case per lane.
 //
-// Reads from the including scope: the template parameter BOUNDED; px, py, mirror; the interval pair of either axis as
+// Reads from the including scope: the template parameter BOUNDED; px, py; G.mirror_y, the header word of the lane's length (the
+//   header block [A2] ran with: a lane reaches [B] only behind an [A2] of the same G); the interval pair of either axis as
 //   block [A2] leaves it, ix0 / iy0 = {lo, rw = 1 / (double) w} and ix1.x / iy1.x = w = (float) (hi - lo); the corner indices rounded to float f00, f10, f01,
 //   f11 and their four edge differences in double dnx0, dnx1, dny0, dny1.
 // Writes: n0, gxn, gyn.
 // Declares (in the including block): ya, dwx, dwy, xc0, yc0, rwx, rwy, quot, u, v.
-            const float ya   = mirror ? fabsf(py) : py;
+            const float ya   = G.mirror_y != 0 ? fabsf(py) : py;
             const double dwx = (double) ix1.x, dwy = (double) iy1.x; // Helper.h:323-324
             const double xc0 = ix0.x, yc0 = iy0.x, rwx = ix0.y, rwy = iy0.y;
             // BOUNDED: no sign copy on the six quotients (div_by_recip_pos0, rt_math.h: the same double unless the dividend
@@ -32,5 +33,5 @@
             n0  = lerp2(u, v, f00, f10, f01, f11);
             gxn = (float) (quot((1.0 - (double) v) * dnx0, dwx, rwx) + quot((double) v * dnx1, dwx, rwx));
             gyn = (float) (quot((1.0 - (double) u) * dny0, dwy, rwy) + quot((double) u * dny1, dwy, rwy));
-            if (mirror && py < 0)
+            if ((G.mirror_y != 0) & (py < 0))
                 gyn = -gyn;

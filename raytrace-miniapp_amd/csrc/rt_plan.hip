@@ -252,6 +252,11 @@ int rtr::plan_create_on(rt_hip_plan **out, hipStream_t upload_q, int device, int
             return fail_arg("rt_hip_plan_create: incomplete gain table");
         if (gain[i].Nv != K)
             return fail_arg("rt_hip_plan_create: gain.Nv != beam.nv");
+        // The cell set-up of the march forms its gather offsets as 24-bit multiply-adds (rt_march_cell.inc: interval number
+        // x 48, node number x 16): interval and node numbers stay below 2^24.  (Checked before a device is asked for: the
+        // refusal needs none.)
+        if ((unsigned long long) gain[i].Nx * (unsigned long long) gain[i].Ny > rt::RT_MARCH_MAX_NODES)
+            return fail_arg("rt_hip_plan_create: a gain table of more than 2^24 - 1 grid points is not supported");
     }
     int ndev = rt_hip_device_count();
     if (ndev <= 0) {
@@ -309,6 +314,10 @@ int rtr::plan_create_on(rt_hip_plan **out, hipStream_t upload_q, int device, int
             const size_t cells = (size_t) gain[i].Nx * (size_t) gain[i].Ny;
             capacity += piece(cells * kp * sizeof(float));
             blob_bytes += sizeof(rt::Interval) * ((size_t) gain[i].Nx + (size_t) gain[i].Ny) + sizeof(rt::Node) * cells;
+        }
+        if (blob_bytes >= rt::RT_MARCH_MAX_BLOB) { // (BlobGain::off_* are ints, and the march adds to them in 32 bits)
+            delete p;
+            return fail_arg("rt_hip_plan_create: march tables of 2 GiB or more are not supported");
         }
         capacity += piece(blob_bytes);
         capacity += piece(sizeof(double) * (size_t) beam->nx) + piece(sizeof(double) * (size_t) beam->ny) +
