@@ -28,7 +28,7 @@
 #include "rt_spec_scan_seeds.hip" // ... and length spectra with them: once per (seed beam, length)
 #include "rt_spec_ase_seeds.hip" // spectra mode of an emission plan with the seeds of rt_hip_plan_set_spectra_ase_seeds: the ASE rows and a block per seed beam
 #include "rt_spec_scan_ase_seeds.hip" // ... and length spectra of one with the seeds of rt_hip_plan_set_length_spectra_ase_seeds: a block per (curve, length)
-// (rt_spec_wg.inc: the kernel shell the five spectra passes above share, as text)
+// (rt_spec_wg.inc: the kernel shell the six spectra passes above share, as text; rt_spec_tile.inc and rt_spec_scan_tile.inc: their tile text)
 
 #include "rt_runtime.h"
 #include "rt_run_shape.h" // what a run looks like: the pure decision (facts + tuning -> shape) this file enqueues

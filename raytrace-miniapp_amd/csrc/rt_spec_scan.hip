@@ -17,7 +17,9 @@
 // rt_spec_scan_kernel<EMIS, BACKWARD> stands where rt_spec_kernel stands and has its shell: one 16-wave work-group per CU,
 // tiles from the eight sharded counters, lanes = rays, the LDS of rt_spec_kernel (the exponent tables and [64][XS_ROW]
 // staging doubles per wave), its launch bounds.  The tile text is that of the scan kernels: rt_tile_ray.inc, rt_tile_rec.inc
-// with SF = 0, rec_slot_lazy, so the arithmetic of a slot is rt_tile_batch.inc's for SF = 0.
+// with SF = 0, rec_slot_lazy, so the arithmetic of a slot is rt_tile_batch.inc's for SF = 0.  The tile head, the state that
+// serves a block and the codes of a curve are the text the three tile functions of length spectra share
+// (rt_spec_scan_tile.inc), the walk and its stores that of rt_spec_scan_walk.inc.
 //   forward   the prefixes share one running spectrum: per frequency batch ONE walk over the slots, and the running Iv
 //             (gain-only: one exp_tab_vec of the running gl) after the three sub-segments of length j is row n = j + 1.
 //   backward  suffix n starts with its own initial value at slot 3 (N - n): the walk of rt_step_rscan.hip, LSPEC_LCH
@@ -108,32 +110,12 @@ __device__ __forceinline__ void spec_scan_tile(const FreqHot &H, const unsigned 
 {
     constexpr int SF      = 0; // (the text fragments below read it: slots at run time)
     constexpr int LCH     = LSPEC_LCH;
-    const int L           = H.L;
-    const int S           = L * RT_N_SUB;
-    const int K           = H.K;
-    const int Kp          = H.Kp;
-    const unsigned n_rays = H.n_rays;
-    const unsigned row0   = tile * WAVE;
-    const unsigned ridx   = row0 + (unsigned) lane;
-    const bool have       = ridx < n_rays;
-    const bool backward   = BACKWARD;
-    const unsigned rrec      = have ? ridx : 0u;
-    const unsigned char *rec = H.rec;
-    const bool probe_on   = (hflags & FQ_PROBE) != 0;
     const bool seeded     = !EMIS && (hflags & FQ_HAS_SEED) != 0; // (the emission recurrence takes no seed factor)
 
-    // ---- per-ray preamble, once: the final state of the ray (rt_tile_ray.inc) ----
-#define TILE_NEED_RAY false
-#include "rt_tile_ray.inc"
-#undef TILE_NEED_RAY
-    (void) err1; // (of the final state: every block takes the test of its own state, open_block)
-    if (__ballot(have) == 0ull)
-        return;
-    // the marched segment the ray escaped in (never: L + 1)
-    const int n_done           = (int) ((m.flags_steps >> REC_NDONE_SHIFT) & REC_NDONE_MASK);
-    const unsigned flags_steps = m.flags_steps;
-    const int e_seg            = (fl & F_ESCAPED) ? (n_done > 0 ? (n_done - 1) / RT_N_SUB + 1 : 1) : L + 1;
-    const bool skip            = (fl & F_SKIP) != 0u; // every update is the identity: rows of zeros at every n
+    // ---- the tile head of length spectra, once: the final state of the ray, the segment it escaped in (rt_spec_scan_tile.inc) ----
+#define SPEC_SCAN_HEAD
+#include "rt_spec_scan_tile.inc"
+#undef SPEC_SCAN_HEAD
 
     // the seed factor at the launch ray (forward, Helper.h:530-533), in place_ray's own arithmetic as rt_step_scan.hip takes it
     double f0_launch = 0.0;
@@ -152,16 +134,9 @@ __device__ __forceinline__ void spec_scan_tile(const FreqHot &H, const unsigned 
     }
 
     // ---- the march record of this lane's ray (rt_tile_rec.inc; SF = 0: nothing to decode up front) ----
-#define TILE_MASK true
-#include "rt_tile_rec.inc"
-#undef TILE_MASK
-    (void) gs;
-    (void) rs;
-    (void) off;
-    (void) all_small;
-    (void) all_regular;
-    (void) load_rows;
-    (void) gv_nan; // (SF = 0 tests every frequency's lineshape values as it reads them)
+#define SPEC_SCAN_REC
+#include "rt_spec_scan_tile.inc"
+#undef SPEC_SCAN_REC
     const ConstF64 sfk = (ConstF64) (unsigned long long) H.seed_fk;
 
     // one bit per row block (bit m - 1 = block n - 2): error -1, live, not escaped (carries the seed factor), a negative
@@ -172,62 +147,42 @@ __device__ __forceinline__ void spec_scan_tile(const FreqHot &H, const unsigned 
     // the state that serves block m - 1: the -1 test, the exit ray (stored here), the bits; returns the seed factor of the
     // backward method, taken at that state (Helper.h:518-529)
     auto open_block = [&](const int mseg) -> double {
-        float spx = m.px, spy = m.py, ssx = m.sx, ssy = m.sy, ssz = m.sz;
-        bool esc  = (fl & F_ESCAPED) != 0u;
-        if (have && mseg < L && mseg < e_seg) {
-            const float *q = reinterpret_cast<const float *>(Q->bnd + scan_bnd_off(ridx, mseg, L));
-            spx            = q[0];
-            spy            = q[1];
-            ssx            = q[2];
-            ssy            = q[3];
-            ssz            = q[4];
-            esc            = false;
-        }
-        const unsigned bit = 1u << (mseg - 1);
-        const bool e1      = have && (double) (ssz * ssz) < 0.01; // Helper.h:515
-        rt_ray r2          = { 0.0f, 0.0f, 0.0f, 0.0f };          // (zeros under error -1, as rt_spec.hip leaves them)
-        double f0          = 0.0;
-        if (have && !e1) {
-            r2.x = spx; // Helper.h:518-521
-            r2.y = spy;
-            r2.a = atanf_flt32_kernel(ssx / ssz) * 1e3f;
-            r2.b = atanf_flt32_kernel(ssy / ssz) * 1e3f;
-            if (!skip)
-                livem |= bit;
-            if (seeded && !esc) {
-                seedm |= bit;
-                if (BACKWARD)
-                    f0 = rscan_seed_factor(&C->seed, (double) spx, (double) spy, (double) r2.a, (double) r2.b);
-            }
-        }
-        if (e1)
-            e1m |= bit;
-        if (have) {
-            Q->out.ray2[(size_t) (mseg - 1) * blk_rays + ridx] = r2;
-            if (probe_on && mseg == L) { // the probe is that of the whole run
-                C->probe.ray2[ridx]  = r2;
-                C->probe.flags[ridx] = fl | (e1 ? F_ERR1 : 0u);
-                C->probe.steps[ridx] = steps;
-            }
-        }
+#define SPEC_SCAN_STATE
+#define SPEC_SCAN_STATE_SEG mseg
+#define SPEC_SCAN_STATE_HELD
+#define SPEC_SCAN_STATE_F0 double f0 = 0.0;
+#define SPEC_SCAN_STATE_BITS                                                                                                   \
+    if (!skip)                                                                                                                 \
+        livem |= bit;                                                                                                          \
+    if (seeded && !esc) {                                                                                                      \
+        seedm |= bit;                                                                                                          \
+        if (BACKWARD)                                                                                                          \
+            f0 = rscan_seed_factor(&C->seed, (double) spx, (double) spy, (double) r2.a, (double) r2.b);                        \
+    }
+#include "rt_spec_scan_tile.inc"
+#undef SPEC_SCAN_STATE_BITS
+#undef SPEC_SCAN_STATE_F0
+#undef SPEC_SCAN_STATE_HELD
+#undef SPEC_SCAN_STATE_SEG
+#undef SPEC_SCAN_STATE
         return f0;
     };
 
     // ---- the stores and the walk, forward or backward: rt_spec_scan_walk.inc ----
 #include "rt_spec_scan_walk.inc"
 
-    // ---- the codes: -1 of the state, else -2 over -3 (Helper.h:588-593: negative wins); a failing ray is reported once ----
-    if (have) {
-#pragma unroll 1
-        for (int jb = 0; jb < L; jb++) {
-            const unsigned bit = 1u << jb;
-            Q->out.err[(size_t) jb * blk_rays + ridx] = (e1m & bit) ? -1 : ((negm & bit) ? -2 : ((nanm & bit) ? -3 : 0));
-        }
-    }
-    const unsigned only_nan = nanm & ~negm;
-    const unsigned code     = (e1m ? 1u << 1 : 0u) | (negm ? 1u << 2 : 0u) | (only_nan ? 1u << 3 : 0u);
-    if (code)
-        report_failure(code);
+    // ---- the codes (rt_spec_scan_tile.inc: no code word beside the ray's); a failing ray is reported once ----
+#define SPEC_SCAN_CODES
+#define SPEC_SCAN_CODES_CURVE 0
+#define SPEC_SCAN_CODES_NEG negm
+#define SPEC_SCAN_CODES_NAN nanm
+#include "rt_spec_scan_tile.inc"
+#undef SPEC_SCAN_CODES_NAN
+#undef SPEC_SCAN_CODES_NEG
+#undef SPEC_SCAN_CODES_CURVE
+#undef SPEC_SCAN_CODES
+    if (c)
+        report_failure(c);
 }
 
 // The shell of rt_spec_kernel: one work-group of FREQ_WG_WAVES waves per CU, tiles from the eight sharded counters, one
@@ -235,18 +190,16 @@ __device__ __forceinline__ void spec_scan_tile(const FreqHot &H, const unsigned 
 template <bool EMIS, bool BACKWARD>
 __global__ void __launch_bounds__(FREQ_WG_WAVES * 64, EMIS ? FREQ_WAVES : FREQ_WAVES_SEED) rt_spec_scan_kernel(const SpecScanKArg A)
 {
-    // per tile: the cold half and the scan block of the argument block, the flag word and the lane number opaque
 #define SPEC_WG_KERNEL
-#define SPEC_WG_TILE                                                                                                    \
-    ColdPtr C     = (ColdPtr) ((const RT_CONST_AS char *) __builtin_amdgcn_kernarg_segment_ptr() + offsetof(SpecScanKArg, cold)); \
-    SpecScanPtr Q = (SpecScanPtr) ((const RT_CONST_AS char *) __builtin_amdgcn_kernarg_segment_ptr() + offsetof(SpecScanKArg, scan)); \
-    asm volatile("" : "+s"(C), "+s"(Q)); \
-    unsigned hflags = H.flags; \
-    int lane_t      = lane; \
-    asm volatile("" : "+s"(hflags), "+v"(lane_t)); \
-    spec_scan_tile<EMIS, BACKWARD>(H, hflags, C, Q, exp2_tab, stage, tile, lane_t);
+#define SPEC_WG_KARG SpecScanKArg
+#define SPEC_WG_BLOCK scan
+#define SPEC_WG_BLOCK_PTR SpecScanPtr
+#define SPEC_WG_CALL spec_scan_tile<EMIS, BACKWARD>(H, hflags, C, Q, exp2_tab, stage, tile, lane_t);
 #include "rt_spec_wg.inc"
-#undef SPEC_WG_TILE
+#undef SPEC_WG_CALL
+#undef SPEC_WG_BLOCK_PTR
+#undef SPEC_WG_BLOCK
+#undef SPEC_WG_KARG
 #undef SPEC_WG_KERNEL
 }
 

@@ -16,9 +16,9 @@
 //                     association (f0_s sfk_s[k]) eg and the exponential-skip rule with `need` over all seeds
 // It stands where rt_spec_scan_kernel stands, with the shell, LDS and grid of the single-seed pass (rt_spec_wg.inc).
 //
-// Per tile, once: the preamble (rt_tile_ray.inc), the record decode, and per block the state that serves it -- the -1 test,
-// the exit ray (stored), the probe, one bit each for error -1, "has a row" and "not escaped" (open_state).  Then two halves
-// over the frequencies, the HALVES of rt_spec_ase_seeds.hip:
+// Per tile, once, the text of rt_spec_scan_tile.inc: the tile head and the record decode (SPEC_SCAN_HEAD, SPEC_SCAN_REC), and
+// per block the state that serves it -- the -1 test, the exit ray (stored), the probe, one bit each for error -1, "has a row"
+// and "not escaped" (open_state: SPEC_SCAN_STATE).  Then two halves over the frequencies, the HALVES of rt_spec_ase_seeds.hip:
 //   emission half  spec_scan_tile<true, BACKWARD>'s walk, LSPEC_LCH = 4 lengths per staging, into blocks (0, .); the states
 //                  are opened where that walk opens them (forward all ahead, backward chunk by chunk), each once
 //   seed half      spec_scan_seeds_tile<BACKWARD>'s walk, SSS_LCH = 2 lengths x seeds per staging, into blocks (1 + s, .).
@@ -51,107 +51,56 @@ __device__ __forceinline__ void spec_scan_ase_seeds_tile(const FreqHot &H, const
 {
     constexpr int SF      = 0; // (the text fragments below read it: slots at run time)
     constexpr int NS      = RT_N_SEED_MAX;
-    const int L           = H.L;
-    const int S           = L * RT_N_SUB;
-    const int K           = H.K;
-    const int Kp          = H.Kp;
-    const unsigned n_rays = H.n_rays;
-    const unsigned row0   = tile * WAVE;
-    unsigned ridx         = row0 + (unsigned) lane; // (the lane's numbers are made opaque between the halves, below)
-    const bool have       = ridx < n_rays;
-    const bool backward   = BACKWARD;
-    unsigned rrec            = have ? ridx : 0u;
-    const unsigned char *rec = H.rec;
-    const bool probe_on   = (hflags & FQ_PROBE) != 0;
 
-    // ---- per-ray preamble, once: the final state of the ray (rt_tile_ray.inc) ----
-#define TILE_NEED_RAY false
-#include "rt_tile_ray.inc"
-#undef TILE_NEED_RAY
-    (void) err1; // (of the final state: every block takes the test of its own state, open_state)
-    if (__ballot(have) == 0ull)
-        return;
-    // the marched segment the ray escaped in (never: L + 1)
-    const int n_done           = (int) ((m.flags_steps >> REC_NDONE_SHIFT) & REC_NDONE_MASK);
-    const unsigned flags_steps = m.flags_steps;
-    const int e_seg            = (fl & F_ESCAPED) ? (n_done > 0 ? (n_done - 1) / RT_N_SUB + 1 : 1) : L + 1;
-    const bool skip            = (fl & F_SKIP) != 0u; // every update is the identity: zeros in the ASE curve at every n
-
-    // ---- the march record of this lane's ray (rt_tile_rec.inc; SF = 0: nothing to decode up front), the mask of spec_scan_tile ----
-#define TILE_MASK true
-#include "rt_tile_rec.inc"
-#undef TILE_MASK
-    (void) gs;
-    (void) rs;
-    (void) off;
-    (void) all_small;
-    (void) all_regular;
-    (void) load_rows;
-    (void) gv_nan; // (SF = 0 tests every frequency's lineshape values as it reads them)
+    // ---- the tile head of length spectra, once (rt_spec_scan_tile.inc; the lane's numbers are made opaque between the halves,
+    // below); the march record of this lane's ray, the mask of spec_scan_tile ----
+#define SPEC_SCAN_HEAD
+#include "rt_spec_scan_tile.inc"
+#undef SPEC_SCAN_HEAD
+#define SPEC_SCAN_REC
+#include "rt_spec_scan_tile.inc"
+#undef SPEC_SCAN_REC
 
     // one bit per length (bit m - 1 = blocks (., n - 2)): error -1, the state gives rows (a ray, no error -1), not escaped
     // (carries the seed factors)
     unsigned e1m = 0u, okm = 0u, seedm = 0u;
     const size_t blk_rays = (size_t) n_rays;
-    static_assert(offsetof(RecMeta, px) == 0 && offsetof(RecMeta, sz) == 16, "a boundary state and a RecMeta begin alike");
 
-    // the state that serves the blocks of m = mseg marched segments (the table of rt_spec_scan.hip): a boundary state or the
-    // final one, read where it is needed as spec_scan_seeds_tile reads it
-    auto state_at = [&](const int mseg) -> const float * {
-        const bool at_bnd = mseg < L && mseg < e_seg;
-        return reinterpret_cast<const float *>(at_bnd ? Q->bnd + scan_bnd_off(ridx, mseg, L) : rec + rec_meta_off(rrec, S, H.rec_stride));
-    };
-    // ... once per tile and length: the -1 test, the exit ray (stored here), the probe, the bits
+    // the state that serves the blocks of m = mseg marched segments (the table of rt_spec_scan.hip), read where it is needed
+    // as spec_scan_seeds_tile reads it: state_at; once per tile and length the -1 test, the exit ray (stored here), the
+    // probe, the bits: open_state
+#define SPEC_SCAN_STATE_AT
+#include "rt_spec_scan_tile.inc"
+#undef SPEC_SCAN_STATE_AT
     auto open_state = [&](const int mseg) {
-        const bool esc = !(mseg < L && mseg < e_seg) && (fl & F_ESCAPED) != 0u;
-        float spx = 0.0f, spy = 0.0f, ssx = 0.0f, ssy = 0.0f, ssz = 1.0f;
-        if (have) {
-            const float *q = state_at(mseg);
-            spx            = q[0];
-            spy            = q[1];
-            ssx            = q[2];
-            ssy            = q[3];
-            ssz            = q[4];
-        }
-        const unsigned bit = 1u << (mseg - 1);
-        const bool e1      = have && (double) (ssz * ssz) < 0.01; // Helper.h:515
-        rt_ray r2          = { 0.0f, 0.0f, 0.0f, 0.0f };          // (zeros under error -1, as rt_spec.hip leaves them)
-        if (have && !e1) {
-            r2.x = spx; // Helper.h:518-521
-            r2.y = spy;
-            r2.a = atanf_flt32_kernel(ssx / ssz) * 1e3f;
-            r2.b = atanf_flt32_kernel(ssy / ssz) * 1e3f;
-            okm |= bit;
-            if (!esc)
-                seedm |= bit;
-        }
-        if (e1)
-            e1m |= bit;
-        if (have) {
-            Q->out.ray2[(size_t) (mseg - 1) * blk_rays + ridx] = r2;
-            if (probe_on && mseg == L) { // the probe is that of the whole run
-                C->probe.ray2[ridx]  = r2;
-                C->probe.flags[ridx] = fl | (e1 ? F_ERR1 : 0u);
-                C->probe.steps[ridx] = steps;
-            }
-        }
+#define SPEC_SCAN_STATE
+#define SPEC_SCAN_STATE_SEG mseg
+#define SPEC_SCAN_STATE_BY_LAMBDA
+#define SPEC_SCAN_STATE_BITS                                                                                                  \
+    okm |= bit;                                                                                                                \
+    if (!esc)                                                                                                                  \
+        seedm |= bit;
+#include "rt_spec_scan_tile.inc"
+#undef SPEC_SCAN_STATE_BITS
+#undef SPEC_SCAN_STATE_BY_LAMBDA
+#undef SPEC_SCAN_STATE_SEG
+#undef SPEC_SCAN_STATE
     };
 
-    // The codes of curve r from its bits (a negative value seen, a NaN seen; one bit per length), filed as soon as the half
-    // that leaves the curve is through, so that no bit of the ASE curve is held across the seed half: per (r, n) -1 of the
-    // state, else -2 over -3 (Helper.h:588-593: negative wins); returns the code of the curve for this ray
+    // The codes of curve r from its bits (rt_spec_scan_tile.inc), filed as soon as the half that leaves the curve is through,
+    // so that no bit of the ASE curve is held across the seed half; returns the code of the curve for this ray
     auto file_codes = [&](const int r, const unsigned e1m, const unsigned negm, const unsigned nanm) -> unsigned {
-        if (have) {
-#pragma unroll 1
-            for (int jb = 0; jb < L; jb++) {
-                const unsigned bit = 1u << jb;
-                Q->out.err[((size_t) r * (size_t) L + (size_t) jb) * blk_rays + ridx] = (e1m & bit) ? -1 : ((negm & bit) ? -2 : ((nanm & bit) ? -3 : 0));
-            }
-        }
-        const unsigned only_nan = nanm & ~negm;
-        const unsigned c        = (e1m ? 1u << 1 : 0u) | (negm ? 1u << 2 : 0u) | (only_nan ? 1u << 3 : 0u);
-        if (c)
-            atomicOr(&H.ctl->rec_code[r], c);
+#define SPEC_SCAN_CODES
+#define SPEC_SCAN_CODES_CURVE r
+#define SPEC_SCAN_CODES_NEG negm
+#define SPEC_SCAN_CODES_NAN nanm
+#define SPEC_SCAN_CODES_WORD H.ctl->rec_code[r]
+#include "rt_spec_scan_tile.inc"
+#undef SPEC_SCAN_CODES_WORD
+#undef SPEC_SCAN_CODES_NAN
+#undef SPEC_SCAN_CODES_NEG
+#undef SPEC_SCAN_CODES_CURVE
+#undef SPEC_SCAN_CODES
         return c;
     };
     unsigned code = 0u; // the OR over all (r, n): a failing ray is reported once
@@ -211,13 +160,13 @@ __device__ __forceinline__ void spec_scan_ase_seeds_tile(const FreqHot &H, const
                 const float *q  = state_at(mseg);
                 const float spx = q[0], spy = q[1], ssx = q[2], ssy = q[3], ssz = q[4];
                 const float ra = atanf_flt32_kernel(ssx / ssz) * 1e3f, rb = atanf_flt32_kernel(ssy / ssz) * 1e3f;
-#pragma unroll 1
-                for (int s = 0; s < n_seed; s++) {
-                    const double f = rscan_seed_factor(&Q->tabs.seed[s], (double) spx, (double) spy, (double) ra, (double) rb);
-#pragma unroll
-                    for (int t = 0; t < NS; t++)
-                        fs[t] = t == s ? f : fs[t];
-                }
+#define SPEC_TILE_FACTORS
+#define SPEC_TILE_FS fs
+#define SPEC_TILE_POINT const float px = spx, py = spy, pa = ra, pb = rb;
+#include "rt_spec_tile.inc"
+#undef SPEC_TILE_POINT
+#undef SPEC_TILE_FS
+#undef SPEC_TILE_FACTORS
             }
         };
 #define SSS_WALK_TILE
@@ -246,18 +195,16 @@ template <bool BACKWARD>
 __global__ void __launch_bounds__(FREQ_WG_WAVES * 64, FREQ_WAVES) rt_spec_scan_ase_seeds_kernel(const SpecScanSeedsKArg A)
 {
     const int n_seed = A.set.n_seed;
-    // per tile: the cold half and the seeds of the argument block, the flag word and the lane number opaque
 #define SPEC_WG_KERNEL
-#define SPEC_WG_TILE                                                                                                    \
-    ColdPtr C = (ColdPtr) ((const RT_CONST_AS char *) __builtin_amdgcn_kernarg_segment_ptr() + offsetof(SpecScanSeedsKArg, cold)); \
-    SpecScanSeedsPtr Q = (SpecScanSeedsPtr) ((const RT_CONST_AS char *) __builtin_amdgcn_kernarg_segment_ptr() + offsetof(SpecScanSeedsKArg, set)); \
-    asm volatile("" : "+s"(C), "+s"(Q)); \
-    unsigned hflags = H.flags; \
-    int lane_t      = lane; \
-    asm volatile("" : "+s"(hflags), "+v"(lane_t)); \
-    spec_scan_ase_seeds_tile<BACKWARD>(H, hflags, C, Q, n_seed, exp2_tab, stage, tile, lane_t);
+#define SPEC_WG_KARG SpecScanSeedsKArg
+#define SPEC_WG_BLOCK set
+#define SPEC_WG_BLOCK_PTR SpecScanSeedsPtr
+#define SPEC_WG_CALL spec_scan_ase_seeds_tile<BACKWARD>(H, hflags, C, Q, n_seed, exp2_tab, stage, tile, lane_t);
 #include "rt_spec_wg.inc"
-#undef SPEC_WG_TILE
+#undef SPEC_WG_CALL
+#undef SPEC_WG_BLOCK_PTR
+#undef SPEC_WG_BLOCK
+#undef SPEC_WG_KARG
 #undef SPEC_WG_KERNEL
 }
 

@@ -3,8 +3,8 @@
 // rt_spec_scan_ase_seeds.hip takes the same statements (rt_tile_rec.inc says why text and not a function template).
 //
 // Two parts; the includer defines which one it wants.
-//   SSS_WALK_F0     the seed factors at the launch ray (forward).  Reads NS, n_seed, BACKWARD, have, ridx, R, ray, Q->tabs;
-//                   declares f0_launch[NS].
+//   SSS_WALK_F0     the seed factors at the launch ray (forward), the text of spectra mode (rt_spec_tile.inc, SPEC_TILE_FACTORS).
+//                   Reads NS, n_seed, BACKWARD, have, ridx, R, ray, Q->tabs; declares f0_launch[NS].
 //                     SSS_GRID_TABS   the seeds' factor tables on the forward ray grid serve this run (a pointer or a bool)
 //   SSS_WALK_TILE   the walk.  Reads BACKWARD, SF (= 0), LCH (= SSS_LCH), NS; H, Q (Q->tabs), n_seed, tab, stage, lane, L, S, K,
 //                   Kp, n_rays, row0, rec, rrec, flags_steps, backward, f0_launch[], blk_rays; the bits livem and seedm, which
@@ -17,55 +17,30 @@
     for (int s = 0; s < NS; s++)
         f0_launch[s] = 0.0;
     if (!BACKWARD && have) {
-        if (!(SSS_GRID_TABS)) {
-            rt_ray launch = ray;
-            float ta, tb;
-            load_ray(R, ridx, launch, ta, tb, false);
-#pragma unroll 1
-            for (int s = 0; s < n_seed; s++) {
-                const double f = rscan_seed_factor(&Q->tabs.seed[s], (double) launch.x, (double) launch.y, (double) launch.a, (double) launch.b);
-#pragma unroll
-                for (int t = 0; t < NS; t++)
-                    f0_launch[t] = t == s ? f : f0_launch[t];
-            }
-        } else {
-            RT_SEED_GRID_POINT(R, ridx)
-#pragma unroll
-            for (int s = 0; s < NS; s++) {
-                if (s < n_seed) {
-                    const double *sf         = Q->tabs.sf[s];
-                    const unsigned char *sin = Q->tabs.sin[s];
-                    RT_SEED_GRID_FACTOR(f0_launch[s], Q->tabs.seed[s].f0, sf, sin)
-                }
-            }
-        }
+        // (the loop over the seeds and the product on a ray grid: the text of spectra mode, rt_spec_tile.inc)
+#define SPEC_TILE_FACTORS
+#define SPEC_TILE_FS f0_launch
+#define SPEC_TILE_AT_POINT !(SSS_GRID_TABS)
+#define SPEC_TILE_POINT                                                                                                        \
+    rt_ray launch = ray;                                                                                                       \
+    float ta, tb;                                                                                                              \
+    load_ray(R, ridx, launch, ta, tb, false);                                                                                  \
+    const double px = (double) launch.x, py = (double) launch.y, pa = (double) launch.a, pb = (double) launch.b;
+#include "rt_spec_tile.inc"
+#undef SPEC_TILE_POINT
+#undef SPEC_TILE_AT_POINT
+#undef SPEC_TILE_FS
+#undef SPEC_TILE_FACTORS
     }
 #elif defined(SSS_WALK_TILE)
     // a full tile and an even K: the pieces of a row leave as 16-byte stores
     const bool wide_ok = row0 + WAVE <= n_rays && (K & 1) == 0;
-    // column `col` of the 64 staging rows to block jb of seed s, frequencies kb .. kb + VEC - 1 (rt_spec_scan.hip, flush_row)
+    // column `col` of the 64 staging rows to block jb of seed s, frequencies kb .. kb + VEC - 1 (rt_spec_scan_tile.inc)
     auto flush_row = [&](const int col, const int s, const int jb, const int kb) {
-        double *blk     = SSS_OUT_IV + ((size_t) s * (size_t) L + (size_t) jb) * blk_rays * (size_t) K;
-        const int width = K - kb < VEC ? K - kb : VEC;
-        if (wide_ok && width == VEC) {
-            // two lanes cover the 32 staged bytes of a row, a store instruction 32 rows
-#pragma unroll
-            for (int g = 0; g < 2; g++) {
-                const unsigned row = (unsigned) (32 * g + (lane >> 1));
-                SPEC_STORE16(stage + row * XS_ROW + col * VEC + 2 * (lane & 1), blk + ((size_t) (row0 + row) * (size_t) K + (size_t) (kb + 2 * (lane & 1))));
-            }
-        } else if (wide_ok) { // K = 4 i + 2: the last two frequencies of a row, one piece per lane
-            SPEC_STORE16(stage + lane * XS_ROW + col * VEC, blk + ((size_t) (row0 + (unsigned) lane) * (size_t) K + (size_t) kb));
-        } else {
-            // ragged tile or odd K: 8 bytes per lane, sixteen rows per instruction
-            const int k = kb + (lane & 3);
-#pragma unroll
-            for (int g = 0; g < WAVE / 16; g++) {
-                const unsigned row = (unsigned) (16 * g + (lane >> 2));
-                if (row0 + row < n_rays && k < K)
-                    blk[(size_t) (row0 + row) * (size_t) K + (size_t) k] = stage[row * XS_ROW + col * VEC + (lane & 3)];
-            }
-        }
+        double *blk = SSS_OUT_IV + ((size_t) s * (size_t) L + (size_t) jb) * blk_rays * (size_t) K;
+#define SPEC_SCAN_FLUSH
+#include "rt_spec_scan_tile.inc"
+#undef SPEC_SCAN_FLUSH
     };
     // The rows of block jb under every seed from the running gl of the block: exp(gl) once for all seeds, skipped by a wave
     // that has no use for it; then per seed Iv = (f0_s f_s[4][k]) eg, the -2 / -3 scan (Helper.h:582-587) and the lane's VEC

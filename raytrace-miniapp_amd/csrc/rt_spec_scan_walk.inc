@@ -6,6 +6,7 @@
 // block jb of this walk is Iv + jb n_rays K), tab, stage, lane, L, S, K, Kp, n_rays, row0, rec, rrec, flags_steps, backward,
 // exact_emis, sfk, f0_launch, blk_rays; the bits livem and seedm, which open_block(mseg) sets and whose seed factor
 // (backward, gain-only) it returns; adds to negm and nanm.
+// The stores of a staged column (flush_row) are the text both walks include: rt_spec_scan_tile.inc, SPEC_SCAN_FLUSH.
 // Forward it opens every block first and then walks once per frequency batch; backward it opens the blocks of a chunk of
 // LCH suffixes ahead of the chunk's walks.
 
@@ -23,29 +24,12 @@
             mine[v] = x;
         }
     };
-    // column `col` of the 64 staging rows to block jb, frequencies kb .. kb + VEC - 1
+    // column `col` of the 64 staging rows to block jb, frequencies kb .. kb + VEC - 1 (rt_spec_scan_tile.inc)
     auto flush_row = [&](const int col, const int jb, const int kb) {
-        double *blk     = Q->out.Iv + (size_t) jb * blk_rays * (size_t) K;
-        const int width = K - kb < VEC ? K - kb : VEC;
-        if (wide_ok && width == VEC) {
-            // two lanes cover the 32 staged bytes of a row, a store instruction 32 rows
-#pragma unroll
-            for (int g = 0; g < 2; g++) {
-                const unsigned row = (unsigned) (32 * g + (lane >> 1));
-                SPEC_STORE16(stage + row * XS_ROW + col * VEC + 2 * (lane & 1), blk + ((size_t) (row0 + row) * (size_t) K + (size_t) (kb + 2 * (lane & 1))));
-            }
-        } else if (wide_ok) { // K = 4 i + 2: the last two frequencies of a row, one piece per lane
-            SPEC_STORE16(stage + lane * XS_ROW + col * VEC, blk + ((size_t) (row0 + (unsigned) lane) * (size_t) K + (size_t) kb));
-        } else {
-            // ragged tile or odd K: 8 bytes per lane, sixteen rows per instruction
-            const int k = kb + (lane & 3);
-#pragma unroll
-            for (int g = 0; g < WAVE / 16; g++) {
-                const unsigned row = (unsigned) (16 * g + (lane >> 2));
-                if (row0 + row < n_rays && k < K)
-                    blk[(size_t) (row0 + row) * (size_t) K + (size_t) k] = stage[row * XS_ROW + col * VEC + (lane & 3)];
-            }
-        }
+        double *blk = Q->out.Iv + (size_t) jb * blk_rays * (size_t) K;
+#define SPEC_SCAN_FLUSH
+#include "rt_spec_scan_tile.inc"
+#undef SPEC_SCAN_FLUSH
     };
     // Iv of a row from its accumulator: emission, the running value unless a NaN or an infinity was among the lineshape
     // values (0 * NaN on the CPU); gain-only, f0 f[4][k] exp(gl), the exponential skipped by a wave that has no use for it

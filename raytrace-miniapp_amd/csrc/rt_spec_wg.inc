@@ -5,17 +5,22 @@
 // eight), one tile per fetch: every tile costs the same here (the step passes reserve guided chunks, rt_step_handout.inc).
 // Two parts; the includer defines which one it wants.
 //   SPEC_WG_SIZE     namespace scope, once (rt_spec.hip): spec_lds_doubles
-//   SPEC_WG_KERNEL   the whole body of a kernel whose argument block is `A`, hot half first (rt_tile_rec.inc says why text and
-//                    not a function template): rt_spec_kernel, rt_spec_scan_kernel, rt_spec_seeds_kernel,
-//                    rt_spec_scan_seeds_kernel, rt_spec_ase_seeds_kernel and rt_spec_scan_ase_seeds_kernel.  Carves the LDS, fills the exponent tables, ends
-//                    the prologue in a barrier and walks the tiles.  Reads
-//                      SPEC_WG_TILE   the statements of one tile: they read H, `tile`, `lane`, exp2_tab and stage, form the
-//                                     pointers to the blocks of the argument block behind the hot half with the kernel's own
-//                                     offsetof, make them, the flag word and the lane number opaque, and call the tile function
-//                    Declares spec_lds[], H, exp2_tab, stage, lane, n_tiles_run, shard, tried, and in the loop t and tile.
+//   SPEC_WG_KERNEL   the whole body of a kernel whose argument block is `A`, hot half first, cold half behind it (rt_tile_rec.inc
+//                    says why text and not a function template): rt_spec_kernel, rt_spec_scan_kernel, rt_spec_seeds_kernel,
+//                    rt_spec_scan_seeds_kernel, rt_spec_ase_seeds_kernel and rt_spec_scan_ase_seeds_kernel.  Carves the LDS,
+//                    fills the exponent tables, ends the prologue in a barrier and walks the tiles.  Per tile it forms the
+//                    pointers to the blocks of the argument block behind the hot half, makes them, the flag word and the lane
+//                    number opaque (as rt_freq_kernel, and as rt_step_scan_wg.inc does for the scan passes of step mode) and
+//                    calls the tile function.  Reads
+//                      SPEC_WG_KARG        the type of A (the offsetof of its blocks)
+//                      SPEC_WG_BLOCK       (optional) the field of A behind the cold half (`scan`, `set`), and
+//                      SPEC_WG_BLOCK_PTR   its pointer type: Q points to it
+//                      SPEC_WG_CALL        the call of the tile function: reads H, hflags, C, [Q,] exp2_tab, stage, tile, lane_t
+//                    Declares spec_lds[], H, exp2_tab, stage, lane, n_tiles_run, shard, tried, and in the loop t, tile, C, [Q,]
+//                    hflags and lane_t.
 // (What the tile function takes beside these -- the seed count of the four passes with seeds -- the kernel reads from its
-// argument block before the include.  The five kernels are the ones their five copies of this shell gave, instruction for
-// instruction: profiles/spectra_share_kernel_resources.txt.)
+// argument block before the include.  The six kernels are the ones their six copies of this shell gave, instruction for
+// instruction: profiles/spectra_share_kernel_resources.txt, profiles/spectra_tiles_share_kernel_resources.txt.)
 #if defined(SPEC_WG_SIZE)
 // doubles of dynamic LDS of a work-group of wg_waves waves
 inline size_t spec_lds_doubles(int wg_waves) { return (size_t) 2 * EXP_TAB + (size_t) wg_waves * WAVE * XS_ROW; }
@@ -29,6 +34,7 @@ __syncthreads();
 const int lane             = lane_id();
 const unsigned n_tiles_run = H.tile_end - H.tile_begin;
 unsigned shard = blockIdx.x & 7u, tried = 0;
+#define SPEC_WG_PTR(T, field) (T) ((const RT_CONST_AS char *) __builtin_amdgcn_kernarg_segment_ptr() + offsetof(SPEC_WG_KARG, field))
 for (;;) {
     unsigned t = 0;
     if (lane == 0)
@@ -41,6 +47,17 @@ for (;;) {
         continue;
     }
     const unsigned tile = H.tile_begin + t * 8u + shard;
-    SPEC_WG_TILE
+    ColdPtr C = SPEC_WG_PTR(ColdPtr, cold);
+#ifdef SPEC_WG_BLOCK
+    SPEC_WG_BLOCK_PTR Q = SPEC_WG_PTR(SPEC_WG_BLOCK_PTR, SPEC_WG_BLOCK);
+    asm volatile("" : "+s"(C), "+s"(Q));
+#else
+    asm volatile("" : "+s"(C));
+#endif
+    unsigned hflags = H.flags;
+    int lane_t      = lane;
+    asm volatile("" : "+s"(hflags), "+v"(lane_t));
+    SPEC_WG_CALL
 }
+#undef SPEC_WG_PTR
 #endif
