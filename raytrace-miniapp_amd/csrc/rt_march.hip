@@ -886,10 +886,15 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
     // FUSED: the window is the part of ONE tile not handed out yet; the reservation it was cut from ends at fetched_end
     unsigned fetched_end = 0, cur_slot = 0; // (wave-uniform) slot of done.rem of the window's tile
     unsigned cslot       = 0;                               // (per lane) slot of the tile of the lane's ray
-    bool more           = true;             // wave-uniform: the ray counters are not exhausted
     // (wave-uniform) the number of idle lanes at which the loop head turns to retirement and refill: REFILL while the counters
-    // have rays, 0 -- every iteration -- once they are dry: `more` folded into the one scalar comparison of the head
+    // have rays, 0 -- every iteration -- once they are dry.  It is also the one record of "the ray counters are not
+    // exhausted" (refill_at != 0): as a bool beside it that fact lived in an SGPR pair, as a lane mask, and every test of it
+    // together with a count -- the loop's exit, the tail threshold of [A] -- became mask arithmetic in front of the branch
     unsigned refill_at = (unsigned) REFILL;
+    // (wave-uniform, loop-invariant) what refill_at is compared with to tell whether the parking threshold of [A] follows
+    // the number of live lanes: always (P.park > 12), or in the tail of the launch only, when refill_at is 0
+    // (through readfirstlane: left alone the compiler keeps the select in a VGPR and compares there, in every iteration)
+    const unsigned adaptive_at = (unsigned) __builtin_amdgcn_readfirstlane(((int) P.park > 12 || REFILL > 8) ? -1 : 0);
     // The rays of a launch are handed out in chunks of CH by eight counters (shard sh owns the chunks sh, sh + 8,
     // ...; a wave starts on shard blockIdx.x % 8 and moves on when its own is empty): one counter serves ~88
     // returning atomics per microsecond chip-wide, which a launch of a few hundred thousand rays comes close to
@@ -907,7 +912,7 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
     // with counters of its own (next_tile[..][shard][8]).
     const unsigned n_main = n_chunks - (P.late_chunks < n_chunks ? P.late_chunks : 0u);
     // (unsigned: waves late_first .. late_first + late_waves - 1; through readfirstlane, so that the compiler knows it for
-    // wave-uniform -- derived from threadIdx.x it counts as divergent, and with it `zone`, `more` and every branch of the
+    // wave-uniform -- derived from threadIdx.x it counts as divergent, and with it `zone`, `refill_at` and every branch of the
     // loop head that tests them, which then run as exec-mask code instead of scalar branches)
     const bool late_wave  = (unsigned) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6)) - P.late_first < P.late_waves;
     unsigned zone = 0;
@@ -946,16 +951,168 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
     unsigned tot_steps = 0, tot_esc = 0, tot_rays = 0, tot_skip = 0;
     unsigned spin = 0; // (BOUNDED = false only)
     MarchDiag diag;    // (diagnostic builds; empty in the product)
+    // The shape of the loop: the three blocks first, the loop head (retirement, refill) behind them, and the one exit -- no
+    // lane holds a ray and the counters are dry -- as the last statement, so that it is the loop's latch: the back edge is
+    // that scalar compare and its branch.  (With the head in front and the exit between head and blocks, the compiler
+    // carried "the loop goes on" as a lane mask to the bottom and tested it there, a constant, in every iteration: four
+    // scalar instructions, profiles/march_overhead_listing.txt.)  A wave enters with every lane idle, and so does the
+    // iteration after a refill that handed out nothing while the counters still have rays (all 32 tile slots of the wave
+    // open: never observed): no lane is in any of the three blocks, each of them is skipped by its own branch on an empty
+    // lane mask, and no test of "does any lane march" stands in front of them for the iterations that do.
+    // n_live (wave-uniform, a 32-bit scalar) is the number of lanes that hold a marching ray, taken at the loop head
+    // after the refill: what the parking threshold of [A] is capped by, and with refill_at the loop's exit test.
+    int n_live = 0;
     for (;;) {
+        {
+        diag.mark(0); // refill
+        // ------------------------------------------------------------ [A] cell loop (Helper.h:430-504)
+        // Straight-line: at most one sub-segment end [A1] and one cell setup [A2] per wave
+        // iteration (a lane that needs more -- several empty sub-segments in a row, or the
+        // commit after an escape -- simply comes back next iteration).
+        // Lane parking: block [A] costs as much as [C] but only a third of the lanes need it in any one
+        // iteration; with P.park > 1 it runs only when at least that many lanes wait for it (or nobody
+        // has anything else to do), the waiting lanes sit the iteration out.
+        // (the threshold follows the number of lanes that still hold a ray: a fifth of them, at most
+        // P.park -- in the tail of a launch, when a wave is down to a few rays, a fixed threshold would make
+        // each of them wait for all the others: 1024 rays took 0.34 ms with it, as long as 400 000)
+        // (while the ray counter still has rays the wave holds more than 64 - REFILL of them, a fifth of which is 12:
+        // for P.park <= 12 the threshold is P.park itself, and the adaptive form runs only in the tail of the launch)
+        // ("or nobody has anything else to do" in counts: the lanes that wait for [A] are among the n_live lanes that hold a
+        // ray, so all of those wait exactly when n_want == n_live, and `n_want >= park_at || n_want == n_live` is
+        // n_want >= min(park_at, n_live): one population count, one minimum, one compare, and a scalar branch round the whole
+        // of [A] -- as lane masks the same decision was two 64-bit compares with select / or / and chains in front of an
+        // s_and_saveexec, 18 scalar instructions per iteration)
+        const unsigned long long want_a = __ballot(st >= ST_CELL); // ST_CELL, ST_ESC
+        int n_want                      = (int) __popcll(want_a);
+        asm volatile("" : "+s"(n_want)); // (a 32-bit scalar, as n_idle at the loop head)
+        int park_at = (int) P.park;
+        if (refill_at <= adaptive_at) { // the counters are dry, or P.park > 12 (or REFILL > 8)
+            int fifth = (n_live * 13 + 63) >> 6; // ~ n_live / 5, at least 1 for a live lane
+            asm volatile("" : "+s"(fifth)); // (keeps the branch: speculated, the five scalar instructions of the tail ran in every iteration)
+            park_at = fifth < (int) P.park ? fifth : (int) P.park;
+        }
+        const bool do_a = n_want >= (park_at < n_live ? park_at : n_live);
+        diag.blocks_run(do_a && want_a != 0ull, st == ST_XSETUP);
+        if (do_a) { // (wave-uniform: a scalar branch)
+        asm volatile(""); // (... and stays one: without it the compiler folds do_a into the lane mask of the test below)
+        if (st >= ST_CELL) {
+            bool in_seg        = (st == ST_CELL) & (z < z_lim);
+            if (!in_seg) {
+                // [A1] end of this sub-segment: commit its slot (Helper.h:501-503 accumulate from 0),
+                // slot (ii - 1) * 3 + (backward ? 2 - iz : iz); straight-line, selects instead of branches
+#ifndef RT_ABL_NOSTORE
+                *reinterpret_cast<RecSlot *>(recp) = RecSlot{ gacc, eacc, cell_last };
+#endif
+                recp += backward ? -(int) REC_SLOT_ROW : (int) REC_SLOT_ROW; // the same ray's next slot: one slot row on
+                any_bits |= (__float_as_uint(gacc) | __float_as_uint(eacc)) & 0x7fffffffu;
+                if (path_on) { // Helper.h:505-511: every remaining sub-segment of an escaped ray's
+                                 // segment records the same position, later segments stay zero
+                    float *pp = P.path + (size_t) ridx * 3 * (size_t) (S + 1);
+                    for (int zz = iz; zz < (st == ST_ESC ? RT_N_SUB : iz + 1); zz++) {
+                        const int idx = RT_N_SUB * (ii - 1) + (backward ? RT_N_SUB - zz - 1 : zz + 1);
+                        pp[3 * idx]     = px;
+                        pp[3 * idx + 1] = py;
+                    }
+                }
+                gacc      = 0.0f;
+                eacc      = 0.0f;
+                cell_last = 0;
+                sub++;
+                // an escaped ray never enters its remaining sub-segments: `sub` tells the readers
+                // (RecMeta n_done); otherwise on to the next sub-segment, or the next segment
+                const bool wrap = iz == RT_N_SUB - 1;
+                const bool fin  = (st == ST_ESC) | (sub == S);
+                iz              = wrap ? 0 : iz + 1;
+                z               = wrap ? 0.0f : z;
+                // (finished: ST_DONE, or ST_DONE_ESC from ST_ESC; retired at the loop head, "ray finished")
+                st              = fin ? ST_CELL + ST_DONE - st : ST_CELL;
+                diag.finishing(st);
+                if (wrap & !fin) { // twice per ray
+                    if (OPT & MARCH_OPT_SCAN) { // the ray leaves length seg + 1 for the next: its state there (rt_step_scan.hip)
+                        unsigned char *bnd = reinterpret_cast<unsigned char *>(((unsigned long long) P.pad_march[1] << 32) | (unsigned long long) P.pad_march[0]);
+                        float *q           = reinterpret_cast<float *>(bnd + scan_bnd_off(ridx, seg + 1, L));
+                        q[0]               = px;
+                        q[1]               = py;
+                        q[2]               = sx;
+                        q[3]               = sy;
+                        q[4]               = sz;
+                    }
+                    seg++;
+                    ii = backward ? P.N - seg - 1 : seg + 1;
+                    G  = march_blob_header(hdr, ii, lds_base);
+                }
+                z_stop = iz == 0 ? zs0 : (iz == 1 ? zs1 : zs2);
+                z_lim  = 0.995f * z_stop;
+                in_seg = !fin & (z < z_lim);
+            }
+            diag.mark(1); // [A1]
+            if (in_seg) { // (a lane in ST_CELL whose ray has not escaped, with or without [A1])
+#include "rt_march_cell.inc"
+            }
+        }
+        } // do_a
+        diag.mark(2); // [A2] (a lane that finished in [A1] stays ST_DONE: retired at the loop head, "ray finished")
+        // ------------------------------------------------------------ [B] cross-cell setup (Helper.h:328-342)
+        if (st == ST_XSETUP) {
+#include "rt_march_xsetup.inc"
+            lim2  = dzrem - zc;
+            dzcap = P.c_cap * lim2; // Helper.h:274: c * 1.00001f * dx[2]
+            rx    = 0.0f;
+            ry    = 0.0f;
+            rz    = 0.0f;
+            n     = n0;
+            hsum  = 0.0f;
+            st    = ST_STEP;
+            diag.tick(1);
+        }
+
+        diag.mark(4); // [B]
+        // ------------------------------------------------------------ [C] one integrator step (Helper.h:279-311)
+        if (st == ST_STEP) {
+            const float lim0 = 0.1f * ix1.x, lim1 = 0.1f * iy1.x;
+            // The loop condition of Helper.h:279-280 holds for every lane that arrives here: a lane from [B]
+            // has r = 0, n = n0 and limits that are positive (cell widths are, rt_hip_plan_create checks it;
+            // lim2 = dzrem - zc > 0 is the entry condition of [B]); a lane that stays in this state was
+            // tested at the end of its last step, below.  So the step runs unconditionally and the
+            // condition is evaluated once, after it.  (For a finite n0, that is: with an infinite or NaN n0
+            // the reference's test |n - n0| < 0.05 fails on entry and its loop never runs nor advances;
+            // rt_hip_plan_create refuses a non-finite index for that reason.)
+            bool run;
+            {
+#include "rt_march_step.inc"
+            }
+            if (!run) {
+                // integrator loop over: close this cross-cell iteration (Helper.h:343-348)
+                path += hsum;
+                px += rx;
+                py += ry;
+                pz += rz;
+                zc += fabsf(rz);
+                const float ya = G.mirror_y != 0 ? fabsf(py) : py; // (G: the header [A2] ran with)
+                if ((px > ix1.y) & (px < ix1.z) & (ya > iy1.y) & (ya < iy1.z) & ((double) zc < 0.999 * (double) dzrem)) {
+                    st = ST_XSETUP;
+                } else {
+                    // cross-cell loop over: close the cell step (Helper.h:499-503)
+                    z += fabsf(pz);
+                    gacc += g0 * path;
+                    eacc += E0 * path;
+                    cell_last = c00;
+                    steps++;
+                    diag.tick(2);
+                    st = ST_CELL;
+                }
+            }
+        }
+        } // the three blocks
         diag.mark(5); // [C] of the previous iteration
-        // ------------------------------------------------------------ refill
-        // (one ballot per iteration: the lane masks of the loop head come from `idle2`, which is taken again only when
+        // ------------------------------------------------------------ loop head: refill
+        // (one ballot per iteration: the lane counts of the loop head come from `idle`, and the count is taken again only when
         // a refill has changed the states; a wave all of whose lanes are idle with nothing left to fetch leaves below)
         // (a lane whose ray has finished and waits to be retired, ST_DONE, is idle for every purpose of the loop head)
-        unsigned long long idle2      = __ballot(st <= ST_IDLE);
-        const unsigned long long idle = idle2;
+        const unsigned long long idle = __ballot(st <= ST_IDLE);
         int n_idle                    = (int) __popcll(idle);
         asm volatile("" : "+s"(n_idle)); // (a 32-bit scalar: left alone the compiler compares the 64-bit count in the vector unit)
+        int n_idle2 = n_idle; // ... after the refill
         diag.iteration(st, lane, n_idle);
         // Watchdog of the instance that takes tables and step sizes as they come (BOUNDED = false: something is outside
         // the ranges rt_hip_plan_create verifies -- an index far from 1, a gradient beyond 1e12, a dz beyond 1e6 cm).
@@ -987,7 +1144,7 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
             // here in 15 % for eleven, profiles/retire_block_share.txt, and its compare, s_and_saveexec and branch closed every
             // [A]; here it hides behind the refill test, and that test is one scalar compare: -2 %)
             diag.mark(0);
-            diag.retire_block(st, more);
+            diag.retire_block(st, refill_at != 0u);
             if (st < ST_IDLE) { // ST_DONE, ST_DONE_ESC
                 const bool escaped = st == ST_DONE_ESC;
                 unsigned fl        = F_VALID;
@@ -1037,7 +1194,7 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
             }
             diag.mark(3); // DONE
             // ------------------------------------------------------------ refill
-            if (more) { // (here with n_idle >= REFILL)
+            if (refill_at != 0u) { // the counters have rays (here with n_idle >= REFILL)
                 diag.refill();
                 const int rank = (int) __builtin_amdgcn_mbcnt_hi((unsigned) (idle >> 32),
                                                                  __builtin_amdgcn_mbcnt_lo((unsigned) idle, 0u));
@@ -1056,7 +1213,6 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
                                     shards_seen_empty = 0;
                                     continue;
                                 }
-                                more = false;
                                 refill_at = 0u;
                                 diag.counters_dry();
                                 break;
@@ -1156,146 +1312,14 @@ __device__ __forceinline__ void march_wave(const DevParams &P, unsigned char *ld
                     sub       = 0;
                     st        = wild ? ST_ESC : ST_CELL; // (an escaped ray commits one empty slot and retires, block [A1])
                 }
-                idle2 = __ballot(st == ST_IDLE); // (no lane waits to be retired here)
+                n_idle2 = (int) __popcll(__ballot(st == ST_IDLE)); // (no lane waits to be retired here)
+                asm volatile("" : "+s"(n_idle2));
             }
         } // retirement and refill
-        // (at this point every lane is idle or waits to be retired, waits for [A], or is in [B] / [C]: the three lane
-        // masks the loop head needs follow from two ballots)
-        if (idle2 == ~0ull) {
-            if (!more)
-                break;
-        } else {
-
-        diag.mark(0); // refill
-        // ------------------------------------------------------------ [A] cell loop (Helper.h:430-504)
-        // Straight-line: at most one sub-segment end [A1] and one cell setup [A2] per wave
-        // iteration (a lane that needs more -- several empty sub-segments in a row, or the
-        // commit after an escape -- simply comes back next iteration).
-        // Lane parking: block [A] costs as much as [C] but only a third of the lanes need it in any one
-        // iteration; with P.park > 1 it runs only when at least that many lanes wait for it (or nobody
-        // has anything else to do), the waiting lanes sit the iteration out.
-        // (the threshold follows the number of lanes that still hold a ray: a fifth of them, at most
-        // P.park -- in the tail of a launch, when a wave is down to a few rays, a fixed threshold would make
-        // each of them wait for all the others: 1024 rays took 0.34 ms with it, as long as 400 000)
-        // (while the ray counter still has rays the wave holds more than 64 - REFILL of them, a fifth of which is 12:
-        // for P.park <= 12 the threshold is P.park itself, and the adaptive form runs only in the tail of the launch)
-        const unsigned long long want_a = __ballot(st >= ST_CELL); // ST_CELL, ST_ESC
-        int park_at = (int) P.park;
-        if (!more || (int) P.park > 12 || REFILL > 8) {
-            const int n_live = WAVE - (int) __popcll(idle2);
-            const int fifth  = (n_live * 13 + 63) >> 6; // ~ n_live / 5, at least 1 for a live lane
-            park_at          = fifth < (int) P.park ? fifth : (int) P.park;
-        }
-        const bool do_a = (int) __popcll(want_a) >= park_at || (~(idle2 | want_a)) == 0ull;
-        diag.blocks_run(do_a && want_a != 0ull, st == ST_XSETUP);
-        if (do_a && st >= ST_CELL) {
-            bool in_seg        = (st == ST_CELL) & (z < z_lim);
-            if (!in_seg) {
-                // [A1] end of this sub-segment: commit its slot (Helper.h:501-503 accumulate from 0),
-                // slot (ii - 1) * 3 + (backward ? 2 - iz : iz); straight-line, selects instead of branches
-#ifndef RT_ABL_NOSTORE
-                *reinterpret_cast<RecSlot *>(recp) = RecSlot{ gacc, eacc, cell_last };
-#endif
-                recp += backward ? -(int) REC_SLOT_ROW : (int) REC_SLOT_ROW; // the same ray's next slot: one slot row on
-                any_bits |= (__float_as_uint(gacc) | __float_as_uint(eacc)) & 0x7fffffffu;
-                if (path_on) { // Helper.h:505-511: every remaining sub-segment of an escaped ray's
-                                 // segment records the same position, later segments stay zero
-                    float *pp = P.path + (size_t) ridx * 3 * (size_t) (S + 1);
-                    for (int zz = iz; zz < (st == ST_ESC ? RT_N_SUB : iz + 1); zz++) {
-                        const int idx = RT_N_SUB * (ii - 1) + (backward ? RT_N_SUB - zz - 1 : zz + 1);
-                        pp[3 * idx]     = px;
-                        pp[3 * idx + 1] = py;
-                    }
-                }
-                gacc      = 0.0f;
-                eacc      = 0.0f;
-                cell_last = 0;
-                sub++;
-                // an escaped ray never enters its remaining sub-segments: `sub` tells the readers
-                // (RecMeta n_done); otherwise on to the next sub-segment, or the next segment
-                const bool wrap = iz == RT_N_SUB - 1;
-                const bool fin  = (st == ST_ESC) | (sub == S);
-                iz              = wrap ? 0 : iz + 1;
-                z               = wrap ? 0.0f : z;
-                // (finished: ST_DONE, or ST_DONE_ESC from ST_ESC; retired at the loop head, "ray finished")
-                st              = fin ? ST_CELL + ST_DONE - st : ST_CELL;
-                diag.finishing(st);
-                if (wrap & !fin) { // twice per ray
-                    if (OPT & MARCH_OPT_SCAN) { // the ray leaves length seg + 1 for the next: its state there (rt_step_scan.hip)
-                        unsigned char *bnd = reinterpret_cast<unsigned char *>(((unsigned long long) P.pad_march[1] << 32) | (unsigned long long) P.pad_march[0]);
-                        float *q           = reinterpret_cast<float *>(bnd + scan_bnd_off(ridx, seg + 1, L));
-                        q[0]               = px;
-                        q[1]               = py;
-                        q[2]               = sx;
-                        q[3]               = sy;
-                        q[4]               = sz;
-                    }
-                    seg++;
-                    ii = backward ? P.N - seg - 1 : seg + 1;
-                    G  = march_blob_header(hdr, ii, lds_base);
-                }
-                z_stop = iz == 0 ? zs0 : (iz == 1 ? zs1 : zs2);
-                z_lim  = 0.995f * z_stop;
-                in_seg = !fin & (z < z_lim);
-            }
-            diag.mark(1); // [A1]
-            if (in_seg) { // (a lane in ST_CELL whose ray has not escaped, with or without [A1])
-#include "rt_march_cell.inc"
-            }
-        }
-        diag.mark(2); // [A2] (a lane that finished in [A1] stays ST_DONE: retired at the loop head, "ray finished")
-        // ------------------------------------------------------------ [B] cross-cell setup (Helper.h:328-342)
-        if (st == ST_XSETUP) {
-#include "rt_march_xsetup.inc"
-            lim2  = dzrem - zc;
-            dzcap = P.c_cap * lim2; // Helper.h:274: c * 1.00001f * dx[2]
-            rx    = 0.0f;
-            ry    = 0.0f;
-            rz    = 0.0f;
-            n     = n0;
-            hsum  = 0.0f;
-            st    = ST_STEP;
-            diag.tick(1);
-        }
-
-        diag.mark(4); // [B]
-        // ------------------------------------------------------------ [C] one integrator step (Helper.h:279-311)
-        if (st == ST_STEP) {
-            const float lim0 = 0.1f * ix1.x, lim1 = 0.1f * iy1.x;
-            // The loop condition of Helper.h:279-280 holds for every lane that arrives here: a lane from [B]
-            // has r = 0, n = n0 and limits that are positive (cell widths are, rt_hip_plan_create checks it;
-            // lim2 = dzrem - zc > 0 is the entry condition of [B]); a lane that stays in this state was
-            // tested at the end of its last step, below.  So the step runs unconditionally and the
-            // condition is evaluated once, after it.  (For a finite n0, that is: with an infinite or NaN n0
-            // the reference's test |n - n0| < 0.05 fails on entry and its loop never runs nor advances;
-            // rt_hip_plan_create refuses a non-finite index for that reason.)
-            bool run;
-            {
-#include "rt_march_step.inc"
-            }
-            if (!run) {
-                // integrator loop over: close this cross-cell iteration (Helper.h:343-348)
-                path += hsum;
-                px += rx;
-                py += ry;
-                pz += rz;
-                zc += fabsf(rz);
-                const float ya = G.mirror_y != 0 ? fabsf(py) : py; // (G: the header [A2] ran with)
-                if ((px > ix1.y) & (px < ix1.z) & (ya > iy1.y) & (ya < iy1.z) & ((double) zc < 0.999 * (double) dzrem)) {
-                    st = ST_XSETUP;
-                } else {
-                    // cross-cell loop over: close the cell step (Helper.h:499-503)
-                    z += fabsf(pz);
-                    gacc += g0 * path;
-                    eacc += E0 * path;
-                    cell_last = c00;
-                    steps++;
-                    diag.tick(2);
-                    st = ST_CELL;
-                }
-            }
-        }
-        } // some lane is marching
+        // (at this point every lane is idle or waits to be retired, waits for [A], or is in [B] / [C])
+        n_live = WAVE - n_idle2;
+        if (((unsigned) n_live | refill_at) == 0u) // no lane holds a ray and the counters are dry: the loop's one exit, and its latch
+            break;
     }
     diag.wave_end(lane);
     // ---- launch totals ----

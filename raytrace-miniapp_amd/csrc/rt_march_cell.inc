@@ -116,6 +116,10 @@
                     if (use_emis) {
                         E0 = lerp2(u, v, __uint_as_float(q00.w), __uint_as_float(q10.w), __uint_as_float(q01.w),
                                    __uint_as_float(q11.w));
+                        // (a compare and a select, not one maximum: v_max_f32 orders -0 below +0 and would turn an E0 of -0,
+                        // which this keeps, into +0.  eacc could not tell -- the zero reaches it as a term E0 * path added to a
+                        // sum that is never -0 -- but E0 itself is lane state that tests/test_gpu_march_cell.py compares with
+                        // the reference bit for bit, population "table_values": E0 interpolating to -0, kept.)
                         E0 = E0 >= 0 ? E0 : 0.0f;
                     }
                     pz    = 0.0f;
@@ -127,6 +131,15 @@
                         st = ST_XSETUP;
                     } else {
                         // no cross-cell iteration at all: the cell step still counts (Helper.h:498-503)
+                        // A rare arm -- the box b_lo .. b_hi is the cell with a margin, and dzrem > 0 for every lane that
+                        // is in_seg: a position that is a NaN, or a z_stop the float z cannot stay below, reaches it; no wave
+                        // of the stand-in does (profiles/march_overhead_ab.txt) -- that the compiler laid out as predicated
+                        // straight-line code: its eight vector instructions issued in every pass of [A2], for no lane.  The
+                        // empty statement makes the wave branch round the arm when no lane takes it (the compiler keeps
+                        // the skip of a block that holds an asm statement).  The arithmetic stays, in every instance: with
+                        // path = +0 the sums add g0 * 0 and E0 * 0, which are NaN for a table value that is not finite, and
+                        // plan creation verifies the index tables only, not g0 and E0.
+                        asm volatile("");
                         z += fabsf(pz);
                         gacc += g0 * path;
                         eacc += E0 * path;
